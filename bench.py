@@ -17,6 +17,11 @@ rank 0 over RCCL and one compositor kernel assemble the image, inside the timed 
 (16:9 frame grown to N x 2,073,600 pixels).
 
 Prints ONE JSON line on rank 0.
+
+A plain run at N = 1 sets up, warms up, times the K steps and prints the line. `--full` adds what the headline figure
+does not need: the roofline block (profiled and counting passes, stream-copy and gather peaks) and, at N = 1, the
+one-pass-per-iteration rate and the CPU baseline. `--dump-outputs DIR` writes the image the timed path computed (the
+accumulation buffer after its last step) as DIR/image.npy, float32, before any of the `--full` extras touches the device.
 """
 import argparse
 import json
@@ -71,6 +76,25 @@ def self_launch(n_gpus, argv):
     return proc.wait()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_image(outdir, img):
+    """The image a caller of the timed path receives, (H, W, 4) float32, as outdir/image.npy. An image larger than
+    DUMP_LIMIT_BYTES (the C5 frame: 133 MB) is written as a fixed sample of 2 M pixels, chosen by a seeded generator, with
+    their row-major pixel indices beside it (image_pixel_index.npy, float64: exact for any index of the frame)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(outdir, "image.npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    index = np.sort(np.random.default_rng(0).choice(flat.shape[0], 1 << 21, replace=False))
+    np.save(os.path.join(outdir, "image.npy"), flat[index])
+    np.save(os.path.join(outdir, "image_pixel_index.npy"), index.astype(np.float64))
+
+
 def pick_pmc_record(steps, batch_depth, resolution, sphere_tess=180, kernel="trace"):
     """HBM-side bytes come from rocprofv3 --pmc passes (tools/pmc_collect.sh + tools/pmc_traffic.py), which cannot run
     inside this process. A committed record is carried ONLY when it was taken at this run's launch size: same steps,
@@ -105,8 +129,12 @@ def main():
                          "cache-resident); 1000 gives 2.0 M and 2800 gives 15.7 M triangles — a scene the caches do not hold, where the HBM roofline applies")
     ap.add_argument("--native-math", action="store_true",
                     help="the opt-in approximate build (libtweeker_hip_fast.so: native sin / cos / exp / rcp / sqrt in the shading kernels, the reference's --use_fast_math mode); not bit-identical to the oracle, tests/test_gpu_native_math.py bounds it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline block and, at N = 1, the one-pass-per-iteration rate and the CPU baseline (off by default: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the timed path's last step to DIR/image.npy (float32; a seeded sample of its pixels where the image passes 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the one-pass-per-iteration rate and the roofline block")
     ap.add_argument("--no-composite-check", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the oracle sample")
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads of the CPU baseline (a 1-GPU box has a share of 16 cores)")
@@ -253,6 +281,10 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed, render_ms_max, closing_barrier_ms = float(tmax[0].item()), float(tmax[1].item()), float(tmax[2].item()) * 1.0e3
 
+    # ---- what the timed path computed in its last step: the composed frame on rank 0 at N > 1, else this device's image
+    if args.dump_outputs and rank == 0:
+        dump_image(args.dump_outputs, (composed if dist is not None else accum).cpu().numpy())
+
     # ---- N > 1: the composed image against a single-device render of the same iterations (outside the timed region)
     composite = None
     if dist is not None and rank == 0 and not args.no_composite_check and os.environ.get("TWK_BENCH_CHECK_COMPOSITE", "1") == "1":
@@ -336,7 +368,7 @@ def main():
         result["config"]["rehearsal"] = "RCCL with a world of one rank: the N > 1 path's calls on the real backend — NOT a scaling measurement"
 
     # ---- one pass per iteration (what a caller that synchronises after every launch gets, DeviceSingleGPU.cpp:147)
-    if rank == 0 and n_gpus == 1 and not multi and not args.no_roofline:
+    if args.full and rank == 0 and n_gpus == 1 and not multi and not args.no_roofline:
         dev.setLaunchBatch(1)
         k1 = max(2, min(args.steps, 16))
         for it in range(2):
@@ -350,7 +382,7 @@ def main():
         dev.setLaunchBatch(batch)
 
     # ---- roofline of the dominant kernel (traversal), measured on the same steps --------------------
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         dev.profileEnable(True)
         dev.profileReset()
         run_steps(args.warmup, args.steps, finish=False)
@@ -502,7 +534,7 @@ def main():
         }
 
     # ---- CPU baseline: the oracle on the host cores, a bounded sample of the same workload -------------
-    if not args.no_cpu_baseline and rank == 0 and n_gpus == 1 and not multi:
+    if args.full and not args.no_cpu_baseline and rank == 0 and n_gpus == 1 and not multi:
         from oracle import orc
         ref = orc.Oracle(miss=info.miss)
         ref.loadApplication(app)

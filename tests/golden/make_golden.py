@@ -16,9 +16,12 @@ oracle_cornell_objectspace.npz — the same arrays as oracle_cornell.npz made wi
   intersected in OBJECT space with the ray taken through the inverse instance transform, which is what an OptiX
   IAS -> GAS descent does (Device.cpp:1427-1489). Byte-identical to the file round 1 committed as oracle_cornell.npz
   (commit a929824) before the flatten policy existed; the default-policy file differs from it by <= 8e-3 per channel.
+reference_live.json — SHA-256 digests of the REFERENCE's outputs (oracle/_ref/libref_host.so) on the seeded inputs of
+  tests/test_oracle_vs_ref_live.py, and its struct layouts / enum values, so that test runs where the reference is absent.
 Fixtures are data only: inputs + expected outputs.
 """
 import hashlib
+import json
 import os
 import sys
 
@@ -120,6 +123,20 @@ def reference_helpers():
     print("wrote reference_helpers.npz", len(out), "arrays")
 
 
+def reference_live():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_vs_ref_live as live
+    from oracle import orc
+    ref = orc.Reference()
+    out = {"units": {k: live._sha(v) for k, v in live.units_outputs(ref, live.units_inputs()).items()},
+           "host": {k: live._sha(v) for k, v in live.host_outputs_reference(ref, live.host_inputs()).items()},
+           "layouts": live.reference_layouts(ref.lib)}
+    with open(os.path.join(HERE, "reference_live.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote reference_live.json")
+
+
 def oracle_cornell(policy=None, name="oracle_cornell.npz"):
     import tweeker_raytracer_amd as twk
     from oracle import orc
@@ -157,5 +174,6 @@ def oracle_cornell(policy=None, name="oracle_cornell.npz"):
 
 if __name__ == "__main__":
     reference_helpers()
+    reference_live()
     oracle_cornell()
     oracle_cornell(policy=(0, 0), name="oracle_cornell_objectspace.npz")

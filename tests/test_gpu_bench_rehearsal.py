@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -74,12 +75,12 @@ def test_two_ranks_weak_mode():
 
 
 def test_single_gpu_line_carries_the_contract():
-    """`python bench.py --gpus 1 --steps K --warmup W` — the driver's N = 1 command with a short CPU sample: ONE JSON line with
-    the contract's fields, the roofline block of the dominant kernel (algorithmic bytes / measured launch duration / spec
-    peak) and the CPU baseline; value = pixels x steps / the timed region."""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` — the driver's N = 1 command with everything it measures beside
+    the headline and a short CPU sample: ONE JSON line with the contract's fields, the roofline block of the dominant kernel
+    (algorithmic bytes / measured launch duration / spec peak) and the CPU baseline; value = pixels x steps / the timed region."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-seconds", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-seconds", "2", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -107,6 +108,38 @@ def test_single_gpu_line_carries_the_contract():
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in cpu, key
     assert cpu["kind"] == "port" and cpu["value"] > 0 and cpu["sample_bit_identical_to_gpu"] is True
+
+
+def test_plain_single_gpu_line_and_its_outputs(twk, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` — the plain command: the contract's fields and
+    nothing measured beside them, and DIR/image.npy = the accumulation image after the last timed step, bit for bit the
+    image of iterations 0 .. W + K - 1 rendered through the library in this process."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    res = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert key in res, key
+    assert res["steps"] == 3 and res["warmup"] == 2 and res["unit"] == "Msamples/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert abs(res["value"] - 1920 * 1080 / (res["ms_per_step"] * 1.0e3)) < 1.0e-6 * res["value"]
+    assert "roofline" not in res and "cpu_baseline" not in res and "batch1_Msamples_per_s" not in res["config"]
+    assert sorted(os.listdir(tmp_path)) == ["image.npy"]
+    img = np.load(tmp_path / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 4)
+
+    app = twk.Application(os.path.join(ROOT, "scenes", "system_rtigo3_cornell_box.txt"), os.path.join(ROOT, "scenes", "scene_rtigo3_cornell_box.txt"))
+    dev = twk.Device(ordinal=0, miss=app.info.miss)
+    app.initDevice(dev)
+    for it in range(5):
+        dev.render(it)
+    dev.synchronizeStream()
+    ref = dev.getOutputBufferHost()
+    dev.close()
+    assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
 
 
 def test_rccl_branch_with_a_world_of_one_rank():

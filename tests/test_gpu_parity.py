@@ -214,7 +214,9 @@ def test_shared_frame_strategies_equal_single_device(twk):
     at the pixels their launch indices map to; the frame equals the single-device image bit for bit. The frame here is
     device memory of the one GPU all handles share."""
     import ctypes as C
-    hip = C.CDLL("libamdhip64.so")
+    # the HIP runtime the library links, resolved through its own handle: a bare CDLL("libamdhip64.so") can bind to
+    # another copy of the runtime already in the process (the one torch ships), whose pointers the library cannot use
+    hip = twk._lib.lib
     res = (200, 120)  # not a multiple of 8 * N: the last tile column is partly outside the image
     app = load_app(twk, "system_rtigo3_cornell_box.txt", "scene_rtigo3_cornell_box.txt", res)
     single = twk.Device(ordinal=0, miss=app.info.miss)

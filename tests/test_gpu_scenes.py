@@ -193,7 +193,9 @@ def test_compositor_kernel(twk, orc):
     """twk_compositor scatters the gathered [N][H][launchWidth] tile sets into the W x H image like compositor.cu:38-64.
     Device buffers come straight from the HIP runtime the library itself links (ctypes), no torch involved."""
     import ctypes as C
-    hip = C.CDLL("libamdhip64.so")
+    # the HIP runtime the library links, resolved through its own handle: a bare CDLL("libamdhip64.so") can bind to
+    # another copy of the runtime already in the process (the one torch ships), whose pointers the library cannot use
+    hip = twk._lib.lib
     w, h, n = 200, 48, 3
     st = twk.DeviceState()
     st.resolution[0], st.resolution[1] = w, h

@@ -54,7 +54,9 @@ def test_tonemap_kernel_matches_oracle(twk, orc):
     assert got.max() > 100  # not a black frame
 
     # synthetic values through a caller-owned device buffer
-    hip = C.CDLL("libamdhip64.so")
+    # the HIP runtime the library links, resolved through its own handle: a bare CDLL("libamdhip64.so") can bind to
+    # another copy of the runtime already in the process (the one torch ships), whose pointers the library cannot use
+    hip = twk._lib.lib
     rng = np.random.default_rng(9)
     vals = np.concatenate([rng.gamma(1.0, 1.0, (1 << 18, 4)), 10.0 ** rng.uniform(-12, 12, (1 << 16, 4)), -rng.random((64, 4))]).astype(np.float32)
     vals[:5, :3] = [[np.nan, 1, 1], [np.inf, 0.5, 0.5], [0, 0, 0], [1, 1, 1], [-np.inf, 2, 3]]

@@ -1,68 +1,101 @@
-"""CPU: oracle helpers and product host layer against the REFERENCE's own code, live (oracle/_ref/libref_host.so,
-compiled from /root/reference by `make -C oracle ref`). Larger random sets than the committed fixtures. Skipped where
-the reference-built library is absent."""
+"""CPU: oracle helpers and product host layer against the REFERENCE's own code (oracle/_ref/libref_host.so, compiled
+from the reference by `make -C oracle ref`). Larger random sets than tests/golden/reference_helpers.npz. Every output
+is checked against tests/golden/reference_live.json — SHA-256 digests of the reference's outputs on these inputs and
+its struct layouts, written by tests/golden/make_golden.py — so the tests run wherever the repository is; where the
+reference-built library is present they also compare with it directly, array for array."""
+import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_host.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (reference absent)")
+FIXTURE = os.path.join(GOLDEN, "reference_live.json")
+
+
+def _live():
+    return os.path.exists(REF_SO)
 
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def test_units_against_reference(orc):
-    ref, u = orc.Reference(), orc.oracle_units()
+def _sha(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+@pytest.fixture(scope="module")
+def gold():
+    with open(FIXTURE) as f:
+        return json.load(f)
+
+
+def _agree(gold, mine, ref=None):
+    """mine[k] == the reference's output k: by digest against the fixture, and bit for bit against `ref` when given."""
+    assert sorted(mine) == sorted(gold), "fixture and test disagree on the outputs"
+    for k, a in mine.items():
+        if ref is not None:
+            assert a.dtype == ref[k].dtype and np.array_equal(a, ref[k]), k
+        assert _sha(a) == gold[k], k
+
+
+# ---- tea / rng / vector helpers / refract / TBN -------------------------------------------------------------------
+def units_inputs():
     rng = np.random.default_rng(99)
-    for _ in range(2000):
-        a, b = int(rng.integers(0, 2**32)), int(rng.integers(0, 2**32))
-        assert ref.tea4(a, b) == u.tea4(a, b)
-    for seed in rng.integers(0, 2**32, 50):
-        r, rf = ref.rng_stream(int(seed), 32)
-        o, of = u.rng_stream(int(seed), 32)
-        assert np.array_equal(_bits(r), _bits(o)) and rf == of
+    tea = [(int(rng.integers(0, 2**32)), int(rng.integers(0, 2**32))) for _ in range(2000)]
+    seeds = [int(s) for s in rng.integers(0, 2**32, 50)]
     a = rng.normal(size=(2000, 3)).astype(np.float32) * rng.choice([1e-3, 1, 1e3], (2000, 1)).astype(np.float32)
     b = rng.normal(size=(2000, 3)).astype(np.float32)
+    return tea, seeds, a, b
+
+
+def units_outputs(u, inputs):
+    """The outputs of one implementation (oracle_units() or Reference()) on units_inputs(), floats as their bits."""
+    tea, seeds, a, b = inputs
+    out = {"tea4": np.array([u.tea4(x, y) for x, y in tea], np.uint32)}
+    streams = [u.rng_stream(s, 32) for s in seeds]
+    out["rng_streams"] = np.stack([_bits(v) for v, _ in streams])
+    out["rng_final"] = np.array([f for _, f in streams], np.uint32)
     for op in range(6):
-        for x, y in zip(a, b):
-            assert np.array_equal(_bits(ref.vec3(op, x, y)), _bits(u.vec3(op, x, y)))
-    i = a / np.linalg.norm(a, axis=1, keepdims=True)
-    n = b / np.linalg.norm(b, axis=1, keepdims=True)
-    for x, y in zip(i.astype(np.float32), n.astype(np.float32)):
-        for ior in (1.5, 1 / 1.5, 1.0003):
-            r0, r1 = ref.refract(x, y, ior), u.refract(x, y, ior)
-            assert r0[0] == r1[0] and np.array_equal(_bits(r0[1]), _bits(r1[1]))
-        assert np.array_equal(_bits(ref.tbn(x, y)), _bits(u.tbn(x, y)))
+        out[f"vec3_op{op}"] = np.stack([_bits(u.vec3(op, x, y)) for x, y in zip(a, b)])
+    i = (a / np.linalg.norm(a, axis=1, keepdims=True)).astype(np.float32)
+    n = (b / np.linalg.norm(b, axis=1, keepdims=True)).astype(np.float32)
+    refr = [u.refract(x, y, ior) for x, y in zip(i, n) for ior in (1.5, 1 / 1.5, 1.0003)]
+    out["refract_ok"] = np.array([r[0] for r in refr], np.int64)
+    out["refract_dir"] = np.stack([_bits(r[1]) for r in refr])
+    out["tbn"] = np.stack([_bits(u.tbn(x, y)) for x, y in zip(i, n)])
+    return out
 
 
-def test_host_layer_against_reference(twk, orc):
-    ref = orc.Reference()
-    pi = np.float32(np.pi)
-    for (u, v, ax) in [(1, 1, 0), (1, 1, 1), (1, 1, 2), (4, 7, 0), (5, 3, 2)]:
-        r, p = ref.mesh_plane(u, v, ax), twk.mesh_plane(u, v, ax)
-        assert np.array_equal(_bits(r[0]), _bits(p[0])) and np.array_equal(r[1], p[1])
-    for (u, v, th) in [(180, 90, pi), (12, 7, np.float32(0.5) * pi), (3, 3, pi)]:
-        r, p = ref.mesh_sphere(u, v, 1.0, th), twk.mesh_sphere(u, v, 1.0, th)
-        assert np.array_equal(_bits(r[0]), _bits(p[0])) and np.array_equal(r[1], p[1])
-    for (u, v) in [(180, 180), (9, 4)]:
-        r, p = ref.mesh_torus(u, v, 0.75, 0.25), twk.mesh_torus(u, v, 0.75, 0.25)
-        assert np.array_equal(_bits(r[0]), _bits(p[0])) and np.array_equal(r[1], p[1])
-    r, p = ref.mesh_box(), twk.mesh_box()
-    assert np.array_equal(_bits(r[0]), _bits(p[0])) and np.array_equal(r[1], p[1])
+def test_units_against_reference(orc, gold):
+    inputs = units_inputs()
+    ref = units_outputs(orc.Reference(), inputs) if _live() else None
+    _agree(gold["units"], units_outputs(orc.oracle_units(), inputs), ref)
+
+
+# ---- mesh generators, Camera::getFrustum, the loader's transform stack --------------------------------------------
+PI = np.float32(np.pi)
+MESHES = [("plane", (1, 1, 0)), ("plane", (1, 1, 1)), ("plane", (1, 1, 2)), ("plane", (4, 7, 0)), ("plane", (5, 3, 2)),
+          ("sphere", (180, 90, 1.0, PI)), ("sphere", (12, 7, 1.0, np.float32(0.5) * PI)), ("sphere", (3, 3, 1.0, PI)),
+          ("torus", (180, 180, 0.75, 0.25)), ("torus", (9, 4, 0.75, 0.25)), ("box", ())]
+TRANSFORM_KINDS = {0: "rotate", 1: "scale", 2: "translate"}
+
+
+def host_inputs():
     rng = np.random.default_rng(5)
+    cameras = []
     for _ in range(50):
         c = rng.uniform(-2, 2, 3).astype(np.float32)
         phi, theta, fov, dist = (np.float32(x) for x in (rng.uniform(0, 1), rng.uniform(0.05, 0.95), rng.uniform(10, 120), rng.uniform(0.5, 20)))
         w, h = int(rng.integers(16, 4000)), int(rng.integers(16, 3000))
-        a = ref.camera_frustum(c, phi, theta, fov, dist, w, h)
-        k = twk.camera_frustum(c, phi, theta, fov, dist, float(np.float32(w) / np.float32(h)))
-        assert np.array_equal(_bits(a), _bits(np.array(list(k.P) + list(k.U) + list(k.V) + list(k.W), np.float32)))
-    kinds = {0: "rotate", 1: "scale", 2: "translate"}
+        cameras.append((c, phi, theta, fov, dist, w, h))
+    stacks = []
     for _ in range(40):
         ops = []
         for _ in range(int(rng.integers(1, 6))):
@@ -73,23 +106,77 @@ def test_host_layer_against_reference(twk, orc):
             if k == 0:
                 vals[3] = np.float32(rng.uniform(-360, 360))
             ops.append([k] + [float(x) for x in vals])
-        lines = ["material m brdf_diffuse"] + [kinds[int(o[0])] + " " + " ".join(repr(x) for x in (o[1:5] if o[0] == 0 else o[1:4])) for o in ops] + ["model box m"]
+        stacks.append(ops)
+    return cameras, stacks
+
+
+def _meshes(gen, out):
+    for n, (kind, args) in enumerate(MESHES):
+        attr, idx = getattr(gen, "mesh_" + kind)(*args)
+        out[f"mesh{n}_{kind}_attributes"] = _bits(attr)
+        out[f"mesh{n}_{kind}_indices"] = np.asarray(idx, np.int64)
+
+
+def host_outputs_reference(ref, inputs):
+    cameras, stacks = inputs
+    out = {}
+    _meshes(ref, out)
+    out["camera_frustum"] = np.stack([_bits(ref.camera_frustum(c, phi, theta, fov, dist, w, h)) for c, phi, theta, fov, dist, w, h in cameras])
+    for n, ops in enumerate(stacks):
+        out[f"transform_stack{n}"] = _bits(ref.transform_stack(np.array(ops, np.float32)))
+    return out
+
+
+def host_outputs_product(twk, inputs):
+    cameras, stacks = inputs
+    out = {}
+    _meshes(twk, out)
+    frusta = []
+    for c, phi, theta, fov, dist, w, h in cameras:
+        k = twk.camera_frustum(c, phi, theta, fov, dist, float(np.float32(w) / np.float32(h)))
+        frusta.append(_bits(np.array(list(k.P) + list(k.U) + list(k.V) + list(k.W), np.float32)))
+    out["camera_frustum"] = np.stack(frusta)
+    for n, ops in enumerate(stacks):
+        lines = ["material m brdf_diffuse"] + [TRANSFORM_KINDS[int(o[0])] + " " + " ".join(repr(x) for x in (o[1:5] if o[0] == 0 else o[1:4])) for o in ops] + ["model box m"]
         app = twk.Application(system_text="light 0\nmiss 0\n", scene_text="\n".join(lines))
-        assert np.array_equal(_bits(app.instance(0)[1]), _bits(ref.transform_stack(np.array(ops, np.float32))))
+        out[f"transform_stack{n}"] = _bits(app.instance(0)[1])
+    return out
 
 
-def test_boundary_struct_layouts_equal_the_reference_headers(twk, orc):
+def test_host_layer_against_reference(twk, orc, gold):
+    inputs = host_inputs()
+    ref = host_outputs_reference(orc.Reference(), inputs) if _live() else None
+    _agree(gold["host"], host_outputs_product(twk, inputs), ref)
+
+
+# ---- struct layouts of the replaced boundary ------------------------------------------------------------------------
+LAYOUT_STRUCTS = ("CameraDefinition", "LightDefinition", "TriangleAttributes", "Tonemapper")
+
+
+def reference_layouts(lib):
+    """Size and member offsets of each struct as the reference's own headers lay them out, and its enum values."""
+    out = {}
+    for which, name in enumerate(LAYOUT_STRUCTS):
+        buf = (C.c_int * 32)()
+        n = lib.ref_struct_layout(which, buf, 32)
+        out[name] = list(buf[:n])
+    buf = (C.c_int * 16)()
+    n = lib.ref_enum_values(buf, 16)
+    out["enum_values"] = list(buf[:n])
+    return out
+
+
+def test_boundary_struct_layouts_equal_the_reference_headers(twk, orc, gold):
     """The structs that cross the replaced boundary by pointer (INTEGRATION.md casts the reference's CameraDefinition /
     LightDefinition / TonemapperGUI / TriangleAttributes to the Twk* types): size and every member offset as the
     reference's own headers lay them out == the ctypes mirrors of include/tweeker_hip.h; FunctionIndex / LightType
     values == the plain ints of the C ABI."""
-    import ctypes as C
-    lib = orc.Reference().lib
+    ref = gold["layouts"]
+    if _live():
+        assert reference_layouts(orc.Reference().lib) == ref
     L = twk._lib if hasattr(twk, "_lib") else __import__("tweeker_raytracer_amd._lib", fromlist=["x"])
-    for which, struct in enumerate((L.CameraDefinition, L.LightDefinition, L.TriangleAttributes, L.Tonemapper)):
-        out = (C.c_int * 32)()
-        n = lib.ref_struct_layout(which, out, 32)
-        mine = [C.sizeof(struct)] + [getattr(struct, name).offset for name, _ in struct._fields_]
-        assert n == len(mine) and list(out[:n]) == mine, struct.__name__
-    out = (C.c_int * 16)()
-    assert lib.ref_enum_values(out, 16) == 7 and list(out[:7]) == [0, 1, 2, 3, 4, 0, 1]
+    for name in LAYOUT_STRUCTS:
+        struct = getattr(L, name)
+        mine = [C.sizeof(struct)] + [getattr(struct, f).offset for f, _ in struct._fields_]
+        assert ref[name] == mine, name
+    assert ref["enum_values"] == [0, 1, 2, 3, 4, 0, 1]

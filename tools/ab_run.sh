@@ -8,9 +8,9 @@ for spec in "$@"; do
   lib=""; [[ "$name" != "base" ]] && lib="TWK_LIB=build/lib_$name.so"
   out=gpurun_out/ab_${spec//[:=]/_}_s${STEPS:-64}.json
   if [[ "$name" == wt_* ]]; then   # a whole older tree built under build/<name> (git worktree): its own bench.py and library
-    ( cd build/$name && env ${envs//,/ } timeout -k 10 200 python bench.py --no-cpu-baseline --steps ${STEPS:-64} --warmup ${WARMUP:-4} ) > $out 2>/dev/null
+    ( cd build/$name && env ${envs//,/ } timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps ${STEPS:-64} --warmup ${WARMUP:-4} ) > $out 2>/dev/null
   else
-  env $lib ${envs//,/ } timeout -k 10 200 python bench.py --no-cpu-baseline --steps ${STEPS:-64} --warmup ${WARMUP:-4} > $out 2>/dev/null
+  env $lib ${envs//,/ } timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps ${STEPS:-64} --warmup ${WARMUP:-4} > $out 2>/dev/null
   fi
   python - "$spec" "$out" <<'PY'
 import json, sys

@@ -11,5 +11,5 @@ for N in 1000 2800; do
   python3 tools/pmc_traffic.py $OUT/pmc_tess$N profiles/r05_trace_hbm_traffic_tess${N}_s32.json --sphere-tess $N > /dev/null && cp profiles/r05_trace_hbm_traffic_tess${N}_s32.json $OUT/
   python3 tools/pmc_summarize.py $OUT/pmc_tess$N $OUT/pmc_counters_tess$N.md > /dev/null
   echo "pmc tess $N done"
-  python3 bench.py --sphere-tess $N --steps 32 --warmup 32 --no-cpu-baseline > $OUT/bench_tess$N.json 2> $OUT/bench_tess$N.err; echo "bench tess $N rc $?"
+  python3 bench.py --sphere-tess $N --steps 32 --warmup 32 --full --no-cpu-baseline > $OUT/bench_tess$N.json 2> $OUT/bench_tess$N.err; echo "bench tess $N rc $?"
 done

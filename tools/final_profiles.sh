@@ -17,11 +17,11 @@ python3 tools/pmc_traffic.py $OUT/pmc_s64 profiles/r05_trace_hbm_traffic_s64.jso
 python3 tools/pmc_summarize.py $OUT/pmc_s64 $OUT/pmc_summary_s64.md > /dev/null
 python3 tools/pmc_traffic.py $OUT/pmc_s64 profiles/r05_shade_hbm_traffic_s64.json --kernel shadeKernel > /dev/null && cp profiles/r05_shade_hbm_traffic_s64.json $OUT/
 echo "pmc done"
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_s20.json 2> $OUT/bench_s20.err; echo "bench s20 rc $?"
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc $?"
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_s20.json 2> $OUT/bench_s20.err; echo "bench s20 rc $?"
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc $?"
 for cfg in "s20 --steps 20 --warmup 5" "default"; do
   set -- $cfg; name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$name -o stats -- python3 bench.py "$@" --no-cpu-baseline > $OUT/bench_${name}_profiled.json 2> $OUT/stats_$name.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$name -o stats -- python3 bench.py "$@" --full --no-cpu-baseline > $OUT/bench_${name}_profiled.json 2> $OUT/stats_$name.err
   f=$(find $OUT/stats_$name -name "*kernel_stats.csv" | head -1); t=$(find $OUT/stats_$name -name "*kernel_trace.csv" | head -1)
   python3 tools/summarize_rocprof.py $f $OUT/kernel_stats_$name.md; cp $f $OUT/kernel_stats_$name.csv
   python3 tools/trace_launch_average.py $t 5 > $OUT/trace_launch_average_$name.md

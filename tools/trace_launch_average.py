@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Average launch duration of the traversal kernel per wavefront pass, from a rocprofv3 --kernel-trace CSV of
-`python bench.py`. The --stats table averages over every launch of the process (warm-up pass of 4 iterations, the
+`python bench.py --full`. The --stats table averages over every launch of the process (warm-up pass of 4 iterations, the
 one-iteration passes behind config.batch1_Msamples_per_s, the composite check); bench.py's roofline.avg_launch_ms is the
 average over the launches of the TIMED pass only. This groups the launches by pass (a pass ends with accumulateKernel)
 and prints the passes of the bench's batch depth, so the two can be compared.

@@ -7,6 +7,7 @@
 #include "error_state.h"
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -24,7 +25,7 @@ int twkSetError(int code, const std::string& message)
 }
 
 namespace twk {
-void launchTrace(const LaunchParams& p, int depth, bool count, bool primary, int gridBlocks, hipStream_t stream);
+void launchTrace(const LaunchParams& p, int depth, bool count, const TraceBuild& build, int gridBlocks, hipStream_t stream);
 void launchTraceQuery(const LaunchParams& p, const float* rays, unsigned int numRays, int anyHit, float* tBetaGamma, int* ids, int gridBlocks, hipStream_t stream);
 void launchGenerate(const LaunchParams& p, hipStream_t stream);
 void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
@@ -86,6 +87,10 @@ struct TileEntriesKey
 #define TWK_MAX_LANES 4
 #define TWK_LANE_QUEUE_PAD (TWK_QUEUE_SEGMENTS * 1024)                       // slots a lane's queue arrays may use beyond its path count (segment gaps: K x (255 + 512) at most)
 #define TWK_STREAM_PAD ((size_t) TWK_MAX_LANES * (TWK_LANE_QUEUE_PAD + 1024)) // ... of all lanes + the rounding of their shares
+// TWK_QUEUE_STRIDE gives a segment room for ceil(windows / K) shade windows of at most 256 slots (N / K rounded up to 256, + 512),
+// so a lane's K segments span at most its path count + K x (255 + 512) slots
+static_assert(TWK_SHADE_BLOCK <= 256, "a shade window (TWK_SHADE_BLOCK slots) fits TWK_QUEUE_STRIDE's rounding");
+static_assert(TWK_QUEUE_SEGMENTS * (255 + 512) <= TWK_LANE_QUEUE_PAD, "a lane's segment gaps fit TWK_LANE_QUEUE_PAD");
 #define TWK_STATS_WORDS 192 // device words of TwkLaunchStats: [0, 24) traversal + shade totals, [24, 96) the shade phases (shade_device.h PhaseScope); twice: the time view's scratch copy
 #define TWK_COUNTER_WORDS (TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2)) // one lane's counter block
 
@@ -243,6 +248,22 @@ static int calculateShift(int size) // Device.cpp:1172-1189
   return s;
 }
 
+// The build of the persistent trace kernel a launch runs, from the scene as refreshParams last described it: the seven-block
+// form (device_types.h TWK_TRACE_WAVES7) for flattened scenes of at most TWK_TRACE_WAVES7_MAX_NODES nodes, with or without
+// cutout opacity, except the PRIMARY launch. TWK_TRACE_WAVES_RUNTIME=6 / 7 forces the six- / seven-block form (7: flattened
+// scenes only).
+static TraceBuild traceBuild(TwkDevice dev, bool primary)
+{
+  const LaunchParams& p = dev->params;
+  TraceBuild b;
+  b.cutout = p.hasCutout != 0; b.twoLevel = dev->twoLevel; b.primary = primary;
+  const bool small = dev->totalNodes <= (size_t) TWK_TRACE_WAVES7_MAX_NODES;
+  b.w7 = !b.twoLevel && !primary && (dev->traceWavesForced == TWK_TRACE_WAVES7 || (dev->traceWavesForced != TWK_TRACE_WAVES && small));
+  b.blocksPerCU = traceBlocksPerCU(b.cutout, b.twoLevel, b.w7, b.primary);
+  b.topTable = b.w7 ? p.topNodes7 : p.topNodes;
+  return b;
+}
+
 static void refreshParams(TwkDevice dev)
 {
   LaunchParams& p = dev->params;
@@ -260,9 +281,7 @@ static void refreshParams(TwkDevice dev)
   p.miss = dev->miss;
   p.hasCutout = 0; p.hasAlbedoTexture = 0;
   for (const DevMaterial& m : dev->materials) { if (m.textureCutout != 0) p.hasCutout = 1; if (m.textureAlbedo != 0) p.hasAlbedoTexture = 1; }
-  // seven trace blocks per CU where the variant that fits them applies (device_types.h TWK_TRACE_WAVES7)
-  p.traceWaves = (!dev->twoLevel && (!p.hasCutout || TWK_TRACE_CUTOUT_SEVEN) && dev->totalNodes <= (size_t) TWK_TRACE_WAVES7_MAX_NODES) ? TWK_TRACE_WAVES7 : (p.hasCutout ? (dev->twoLevel ? TWK_TRACE_WAVES_CUTOUT_OTHER : TWK_TRACE_WAVES) : TWK_TRACE_WAVES);
-  if (dev->traceWavesForced == TWK_TRACE_WAVES || (dev->traceWavesForced == TWK_TRACE_WAVES7 && !dev->twoLevel)) p.traceWaves = dev->traceWavesForced;
+  p.traceWaves = traceBuild(dev, false).blocksPerCU;
   p.envCDF_U = dev->d_envCDF_U; p.envCDF_V = dev->d_envCDF_V;
   for (int k = 0; k < 2; ++k)
   {
@@ -298,7 +317,7 @@ static void refreshParams(TwkDevice dev)
   p.packedQueue = 0; // renderPass decides per pass
 }
 
-static int traceGridBlocks(TwkDevice dev) { return dev->numCUs * TWK_TRACE_WAVES7; } // the larger of the two persistent grids (sizes the spill stacks); a launch uses numCUs x params.traceWaves
+static int traceGridBlocks(TwkDevice dev) { return dev->numCUs * TWK_TRACE_WAVES7; } // the largest persistent grid (sizes the spill stacks); a launch uses numCUs x traceBuild's blocksPerCU
 
 // `samples`: samples per pixel the next wavefront pass carries; the path streams grow to what passes actually need
 // (a 64-sample pass of a 1920x1080 frame takes 46 GB, a handle that renders two iterations takes 1.4 GB).
@@ -561,6 +580,7 @@ static LaunchParams laneParams(TwkDevice dev, const LaunchParams& p, int lane, i
   q.queueStride = TWK_QUEUE_STRIDE(count);
   // the queue arrays of a lane reach beyond its path count (the gaps between a queue's segments): their bases leave room for that
   const size_t queueBase = (size_t) lane * (share + TWK_LANE_QUEUE_PAD);
+  assert(queueBase + (size_t) TWK_QUEUE_SEGMENTS * q.queueStride <= (size_t) dev->allocatedPaths + TWK_STREAM_PAD); // the lane's segments end inside the stream block
   for (int k = 0; k < 2; ++k)
   {
     q.rayOrg[k] += queueBase; q.rayDir[k] += queueBase; q.rayPixel[k] += queueBase; q.rayThroughput[k] += queueBase; q.raySeedFlags[k] += queueBase;
@@ -592,9 +612,11 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
   const int maxDepth = dev->state.pathLengths[1];
   const int lanes = chooseLanes(dev, p.numPaths);
   // every block of every lane's persistent trace kernel resident at once: the lanes share the CUs' block slots
-  int traceWaves = std::max(1, p.traceWaves / lanes);
+  const TraceBuild build = traceBuild(dev, false), primaryBuild = traceBuild(dev, true);
+  int traceWaves = std::max(1, build.blocksPerCU / lanes);
   if (lanes > 1 && dev->laneTraceWaves > 0) traceWaves = std::min(dev->laneTraceWaves, 2 * TWK_TRACE_WAVES / lanes); // TWK_LANE_TRACE_WAVES (experiments; the spill stacks hold two full grids)
   const int traceGrid = dev->numCUs * traceWaves;
+  const int primaryGrid = std::min(traceGrid, dev->numCUs * std::max(1, primaryBuild.blocksPerCU / lanes));
 
   // Every bounce runs as a per-depth trace / shade launch pair over compacted queues (the persistent tail kernel for the deep
   // bounces, rounds 1-4, lives in tools/experiments/r04_tail_kernel.patch: no faster at any launch size measured).
@@ -627,9 +649,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
     }
     if (memcmp(&key, &dev->tileEntriesKey, sizeof(key)) != 0)
     {
-      // the table the PRIMARY build of the traversal kernel caches: TWK_PRIMARY_SIX -> the six-block build's
-      const float4* topTable = (TWK_PRIMARY_SIX || p.traceWaves != TWK_TRACE_WAVES7) ? p.topNodes : p.topNodes7;
-      launchTileEntries(p, topTable, tilesX, tilesY, dev->d_tileEntries, dev->stream);
+      launchTileEntries(p, primaryBuild.topTable, tilesX, tilesY, dev->d_tileEntries, dev->stream); // the table the PRIMARY build caches
       HIP_TRY(hipGetLastError());
       dev->tileEntriesKey = key;
     }
@@ -676,16 +696,13 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
   for (int depth = 0; depth < wavefrontDepth; ++depth)
   {
     const bool primary = fusedPrimary && depth == 0;
-    // (the PRIMARY build of the traversal kernel needs more registers than seven blocks per CU leave: six at most)
-    const int primaryWaves = p.hasCutout ? TWK_TRACE_WAVES_CUTOUT_OTHER : (p.twoLevel ? TWK_TRACE_WAVES_PRIMARY_TWO_LEVEL : TWK_TRACE_WAVES_PRIMARY);
-    const int grid = (primary && TWK_PRIMARY_SIX) ? std::min(traceGrid, dev->numCUs * std::max(1, primaryWaves / lanes)) : traceGrid;
-    for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, laneS[k]); launchTrace(laneP[k], depth, dev->statsEnabled || dev->timeView, primary, grid, laneS[k]); timedLaunchEnd(dev, laneS[k]); }
+    for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, laneS[k]); launchTrace(laneP[k], depth, dev->statsEnabled || dev->timeView, primary ? primaryBuild : build, primary ? primaryGrid : traceGrid, laneS[k]); timedLaunchEnd(dev, laneS[k]); }
     for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_SHADE, laneS[k]); launchShade(laneP[k], depth, primary, shadeGrid[k], laneS[k]); timedLaunchEnd(dev, laneS[k]); }
   }
   if (maxDepth > 0)
   {
     // closest hits of queue `wavefrontDepth` (empty when wavefrontDepth == maxDepth) + the shadow rays of the last shade
-    for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, laneS[k]); launchTrace(laneP[k], wavefrontDepth, dev->statsEnabled || dev->timeView, false, traceGrid, laneS[k]); timedLaunchEnd(dev, laneS[k]); }
+    for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, laneS[k]); launchTrace(laneP[k], wavefrontDepth, dev->statsEnabled || dev->timeView, build, traceGrid, laneS[k]); timedLaunchEnd(dev, laneS[k]); }
   }
   for (int k = 0; k < active; ++k)
   {
@@ -761,7 +778,7 @@ try
   if (const char* e = getenv("TWK_TILE_ENTRIES")) dev->tileEntries = (atoi(e) != 0);
   if (const char* e = getenv("TWK_WIDE_ROOT")) dev->wideRoot = (atoi(e) != 0);
   if (const char* e = getenv("TWK_PACKED_QUEUE")) dev->packedQueue = (atoi(e) != 0);
-  if (const char* e = getenv("TWK_SHADE_SORT")) dev->shadeSort = atoi(e);
+  if (const char* e = getenv("TWK_SHADE_SORT")) dev->shadeSort = std::max(0, std::min(2, atoi(e)));
   if (const char* e = getenv("TWK_TRACE_WAVES_RUNTIME")) dev->traceWavesForced = atoi(e); // A/B: 6 or 7 blocks per CU of the persistent trace kernel
   if (const char* e = getenv("TWK_BUILD_QUALITY")) dev->builder.setQuality(atoi(e)); // A/B: 0 LBVH, 1 binned SAH (default)
   memset(&dev->buildInfo, 0, sizeof(dev->buildInfo));
@@ -1031,7 +1048,7 @@ try
   if (!dev || !info) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_build_info: NULL argument");
   if (!dev->built) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_build_info: twk_build has not been called");
   refreshParams(dev); // the traversal kernel variant depends on the materials as they are now
-  dev->buildInfo.traceBlocksPerCU = (uint64_t) dev->params.traceWaves;
+  dev->buildInfo.traceBlocksPerCU = (uint64_t) traceBuild(dev, false).blocksPerCU;
   *info = dev->buildInfo;
   return TWK_SUCCESS;
 }
@@ -1706,7 +1723,8 @@ try
     const unsigned int c = (unsigned int) numShadow;
     HIP_TRY(hipMemcpy(dev->d_counters + 0 * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_SHADOW, &c, sizeof(c), hipMemcpyHostToDevice));
   }
-  launchTrace(p, 1, dev->statsEnabled, false, dev->numCUs * p.traceWaves, dev->stream);
+  const TraceBuild build = traceBuild(dev, false);
+  launchTrace(p, 1, dev->statsEnabled, build, dev->numCUs * build.blocksPerCU, dev->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(dev->stream));
   if ((rc = checkDroppedPushes(dev, "twk_debug_trace_queue"))) return rc;

@@ -160,7 +160,7 @@ struct LaunchParams
   const float*       envCDF_U;
   const float*       envCDF_V;
   int   tlasRoot;
-  int   traceWaves;     // blocks per CU of the persistent trace kernel: TWK_TRACE_WAVES, or TWK_TRACE_WAVES7 (flattened scene, no cutout, small: see TWK_TRACE_WAVES7)
+  int   traceWaves;     // blocks per CU of the scene's non-PRIMARY trace build (device_api.hip traceBuild, which sizes the grids); no kernel reads it
   int   twoLevel;       // 0: every instance is flattened — the BVH is one world-space tree (top level + spliced instance trees) and no kernel ever enters an instance
   int   numInstances;
   int   numLights;
@@ -283,16 +283,14 @@ TWK_HD unsigned int physicalSlot(const QueueSegments& s, unsigned int stride, un
 #ifndef TWK_TRACE_WAVES
 #define TWK_TRACE_WAVES 6
 #endif
-// The variant of the persistent trace kernel for scenes whose instances are all flattened, without cutout opacity, needs 70
-// VGPRs: SEVEN blocks per CU fit the registers, and the LDS too with a 19-entry stack (the cliff on the shipped scenes is
-// between 18 and 19: 0.673 against 0.536 ms/step at 18) and a 32-node top-of-tree cache (64 -> 32 costs nothing measurable):
-// 7 x (20 KiB + 2.5 KiB) = 157.5 of 160 KiB. Measured, 6 -> 7 blocks per CU: C2 trace 0.536 -> 0.518 ms/step, whole frame
-// +1.7 % (64 iterations) / +2.7 % (20), C4 geometry +2.0 %, a C5 rank's share +3.7 %. The two-level and cutout variants
-// need 76..91 VGPRs and spill at 72 (C4 instances -11 %, C3 -16 %), and scenes of millions of triangles lose 2-6 % (the
-// smaller cache and stack matter there), so those keep six blocks, a 20-entry stack and 64 cached nodes.
-#ifndef TWK_TRACE_CUTOUT_SEVEN
-#define TWK_TRACE_CUTOUT_SEVEN 1 // a switch, not a count: 1 = the flattened build with cutout opacity runs the seven-block form like the one without (71-80 VGPRs since round 4's restart from the ray record; 19-entry stack, 32 cached nodes; scenes of at most TWK_TRACE_WAVES7_MAX_NODES nodes), 0 = TWK_TRACE_WAVES blocks per CU
-#endif
+// The variant of the persistent trace kernel for scenes whose instances are all flattened needs 65 VGPRs (71 with cutout
+// opacity since round 4's restart from the ray record): SEVEN blocks per CU fit the registers, and the LDS too with a 19-entry
+// stack (the cliff on the shipped scenes is between 18 and 19: 0.673 against 0.536 ms/step at 18) and a 32-node top-of-tree
+// cache (64 -> 32 costs nothing measurable): 7 x (20 KiB + 2.5 KiB) = 157.5 of 160 KiB. Measured, 6 -> 7 blocks per CU: C2
+// trace 0.536 -> 0.518 ms/step, whole frame +1.7 % (64 iterations) / +2.7 % (20), C4 geometry +2.0 %, a C5 rank's share
+// +3.7 %, C3 (cutout) trace 0.1949 -> 0.1904. The two-level variants need 76..91 VGPRs and spill at 72 (C4 instances -11 %),
+// and scenes of millions of triangles lose 2-6 % (the smaller cache and stack matter there), so those keep six blocks, a
+// 20-entry stack and 64 cached nodes. The PRIMARY builds have no seven-block form: seven gained nothing (HISTORY.md 4.1).
 #ifndef TWK_TRACE_WAVES_CUTOUT_OTHER
 #define TWK_TRACE_WAVES_CUTOUT_OTHER 5 // ... of its PRIMARY and two-level builds (93-94 VGPRs; at six 36-100 bytes of scratch)
 #endif
@@ -308,13 +306,26 @@ TWK_HD unsigned int physicalSlot(const QueueSegments& s, unsigned int stride, un
 #ifndef TWK_TRACE_WAVES7_MAX_NODES
 #define TWK_TRACE_WAVES7_MAX_NODES 1000000 // binary nodes (= triangle slots - 1); measured on the Cornell room: +2.7 % at 64 k, +2.3 % at 258 k, +2.9 % at 977 k, -2.5 % at 2.0 M
 #endif
+// Blocks per CU of the build traceKernel<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY>: its __launch_bounds__, and the grid the host
+// gives it (every block resident at once). W7 = the seven-block form, built for flattened scenes and launches other than PRIMARY.
+constexpr __host__ __device__ int traceBlocksPerCU(bool cutout, bool twoLevel, bool w7, bool primary)
+{
+  return w7 ? TWK_TRACE_WAVES7
+       : cutout ? ((primary || twoLevel) ? TWK_TRACE_WAVES_CUTOUT_OTHER : TWK_TRACE_WAVES)
+       : (primary && twoLevel) ? TWK_TRACE_WAVES_PRIMARY_TWO_LEVEL : (primary ? TWK_TRACE_WAVES_PRIMARY : TWK_TRACE_WAVES);
+}
+// The build a trace launch runs (COUNT aside, which the launch decides): chosen by device_api.hip traceBuild, launched by
+// trace_kernels.hip launchTrace.
+struct TraceBuild
+{
+  bool cutout, twoLevel, w7, primary;
+  int  blocksPerCU;       // traceBlocksPerCU of the build
+  const float4* topTable; // the top-of-tree table it caches: LaunchParams::topNodes7 (W7) or topNodes
+};
 #ifndef TWK_ENTRY_TILE
 #define TWK_ENTRY_TILE 8        // launch indices per side of a primary-ray entry tile
 #endif
 #define TWK_ENTRY_REFS 7        // references per tile at most (with the count: two int4)
-#ifndef TWK_PRIMARY_SIX
-#define TWK_PRIMARY_SIX 1 // the PRIMARY build of the trace kernel (shade_kernels.hip "primary rays") runs six blocks per CU (2 registers spilled), not seven (16)
-#endif
 #define TWK_TRACE_STACK_SPILL 72  // further entries per lane in HBM
 #define TWK_TRACE_BLOCK       256
 #define TWK_SHADE_BLOCKS_PER_CU 128 // grid of shadeKernel = numCUs x this at most (device_api.hip)

@@ -12,6 +12,10 @@
 #include "shade_device.h"
 #include "../../include/tweeker_hip.h"
 
+#include <array>
+#include <cassert>
+#include <utility>
+
 namespace twk {
 // One thread per path = (sample, launch index): seed, jitter, lens shader, path state reset, primary ray into
 // queue 0. A pass renders batchCount consecutive iterations at once (path = sample * numPixels + launch index, so a
@@ -141,6 +145,9 @@ TWK_D void ldsBarrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "
 #define TWK_SHADE_SORT_TABLE_BYTES 8192 // table budget of the builds that carry the exchange buffer (20 KiB): five blocks per CU = 145 of 160 KiB
 #endif
 static_assert((TWK_SHADE_BLOCK & (TWK_SHADE_BLOCK - 1)) == 0, "the sorted window wraps with a mask");
+// Which launches sort (LaunchParams::shadeSort, 0..2): the first launch of a pass only when shadeSort is 2 — neighbouring pixels
+// hit alike there, and the sort only costs (shade -2.5 %) — every other launch unless it is 0.
+TWK_HD bool shadeSorted(int shadeSort, bool primary) { return shadeSort == 2 || (shadeSort == 1 && !primary); }
 
 // Order of the classes in a sorted window: Lambert, the class with most lanes, in front; GGX, the rare expensive one (its wave
 // takes 2.4 x a Lambert wave's cycles on C2 and is what a block iteration waits for), at the end next to the classes that end the
@@ -236,7 +243,7 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   if (MEASURE) { if (threadIdx.x < 3 * TWK_SHADE_PHASES) phaseWords[threadIdx.x] = 0u; __syncthreads(); }
   const bool measurePhases = MEASURE && p.stats != nullptr; // time view alone: only the path time
   constexpr bool EXCHANGE = LDS_TABLES && (SORT || MEASURE);
-  const bool sorted = LDS_TABLES && (MEASURE ? (p.shadeSort == 2 || (p.shadeSort == 1 && !PRIMARY)) : SORT); // as launchShade chooses for the plain builds
+  const bool sorted = LDS_TABLES && (MEASURE ? shadeSorted(p.shadeSort, PRIMARY) : SORT);
   __shared__ __attribute__((aligned(16))) unsigned int classCount[TWK_SHADE_CLASSES]; // class sort: threads of the window per class (zero between uses)
   __shared__ float4 exchangeStorage[EXCHANGE ? sizeof(ShadeExchange) / 16 : 1];
   if (EXCHANGE && threadIdx.x < TWK_SHADE_CLASSES) classCount[threadIdx.x] = 0u; // the table copy's barrier is behind this
@@ -561,35 +568,38 @@ void launchGenerate(const LaunchParams& p, hipStream_t stream)
 {
   hipLaunchKernelGGL(generateKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p);
 }
-template<bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT>
-static void launchShadeVariant(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
+template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT>
+static void launchShadeBuild(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
 {
-  // the variant without what the scene does not have (shade_device.h shadePath): spherical environment, albedo textures
-  const bool env = (p.miss == 2), tex = (p.hasAlbedoTexture != 0);
-  if (env && tex)  hipLaunchKernelGGL((shadeKernel<true, true, PRIMARY, LDS_TABLES, MEASURE, SORT>),  dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
-  else if (env)    hipLaunchKernelGGL((shadeKernel<true, false, PRIMARY, LDS_TABLES, MEASURE, SORT>), dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
-  else if (tex)    hipLaunchKernelGGL((shadeKernel<false, true, PRIMARY, LDS_TABLES, MEASURE, SORT>), dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
-  else             hipLaunchKernelGGL((shadeKernel<false, false, PRIMARY, LDS_TABLES, MEASURE, SORT>), dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
+  hipLaunchKernelGGL((shadeKernel<ENV, TEX, PRIMARY, LDS_TABLES, MEASURE, SORT>), dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
 }
+// The launchers of every build launchShade chooses, indexed by the build's six flags (bit 0 ENV ... bit 5 SORT): SORT is a build
+// of the plain kernel with LDS tables; the measurement builds take the sort decision at run time.
+using ShadeLauncher = void (*)(const LaunchParams&, int, int, hipStream_t);
+template<int I>
+constexpr ShadeLauncher shadeLauncher()
+{
+  constexpr bool ENV = I & 1, TEX = I & 2, PRIMARY = I & 4, LDS_TABLES = I & 8, MEASURE = I & 16, SORT = I & 32;
+  if constexpr (SORT && (!LDS_TABLES || MEASURE)) return nullptr;
+  else return launchShadeBuild<ENV, TEX, PRIMARY, LDS_TABLES, MEASURE, SORT>;
+}
+template<int... I>
+constexpr std::array<ShadeLauncher, sizeof...(I)> shadeLaunchers(std::integer_sequence<int, I...>) { return {shadeLauncher<I>()...}; }
+
 // primary: depth 0 of a pass whose generateKernel was skipped ("primary rays" above)
 void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream)
 {
+  // the variant without what the scene does not have (shade_device.h shadePath): spherical environment, albedo textures
+  const bool env = (p.miss == 2), tex = (p.hasAlbedoTexture != 0);
+  const bool measure = p.pathTime != nullptr || p.stats != nullptr; // time view, statistics: the measurement builds
   const size_t tableBytes = (size_t) p.numInstances * sizeof(DevInstance) + (size_t) p.numMaterials * sizeof(DevMaterial) + (size_t) p.numLights * sizeof(DevLight);
-  const bool lds = TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_TABLE_BYTES;
-  const bool ldsSort = TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_SORT_TABLE_BYTES; // the builds with the exchange buffer hold smaller tables
-  if (p.pathTime != nullptr || p.stats != nullptr) // time view, statistics: the measurement builds
-  {
-    if (primary) { if (ldsSort) launchShadeVariant<true, true, true, false>(p, depth, gridBlocks, stream);  else launchShadeVariant<true, false, true, false>(p, depth, gridBlocks, stream); }
-    else         { if (ldsSort) launchShadeVariant<false, true, true, false>(p, depth, gridBlocks, stream); else launchShadeVariant<false, false, true, false>(p, depth, gridBlocks, stream); }
-    return;
-  }
-  if (p.shadeSort && ldsSort && !(p.shadeSort == 1 && primary)) // the first launch of a pass: neighbouring pixels hit alike, the sort only costs (shade -2.5 %); TWK_SHADE_SORT=2 sorts it too
-  {
-    if (primary) launchShadeVariant<true, true, false, true>(p, depth, gridBlocks, stream); else launchShadeVariant<false, true, false, true>(p, depth, gridBlocks, stream);
-    return;
-  }
-  if (primary) { if (lds) launchShadeVariant<true, true, false, false>(p, depth, gridBlocks, stream);  else launchShadeVariant<true, false, false, false>(p, depth, gridBlocks, stream); }
-  else         { if (lds) launchShadeVariant<false, true, false, false>(p, depth, gridBlocks, stream); else launchShadeVariant<false, false, false, false>(p, depth, gridBlocks, stream); }
+  const bool fitsExchange = TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_SORT_TABLE_BYTES; // the builds with the exchange buffer hold smaller tables
+  const bool sort = !measure && fitsExchange && shadeSorted(p.shadeSort, primary);
+  const bool lds = (measure || sort) ? fitsExchange : (TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_TABLE_BYTES);
+  static constexpr std::array<ShadeLauncher, 64> launchers = shadeLaunchers(std::make_integer_sequence<int, 64>());
+  const ShadeLauncher launch = launchers[(env ? 1 : 0) | (tex ? 2 : 0) | (primary ? 4 : 0) | (lds ? 8 : 0) | (measure ? 16 : 0) | (sort ? 32 : 0)];
+  assert(launch != nullptr);
+  launch(p, depth, gridBlocks, stream);
 }
 void launchAccumulate(const LaunchParams& p, hipStream_t stream)
 {

@@ -2,6 +2,10 @@
 // overflowed, the stand-alone query kernel and the entry points of the primary rays.
 #include "trace_persistent.h"
 
+#include <array>
+#include <cassert>
+#include <utility>
+
 namespace twk {
 
 // Stand-alone query kernel for twk_trace_rays (parity taps): rays 8 floats each.
@@ -112,41 +116,33 @@ traceOverflowKernel(LaunchParams p, int depth)
 }
 
 template<bool COUNT, bool CUTOUT, bool TWO_LEVEL, bool W7, bool PRIMARY>
-static void launchTraceVariant(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
+static void launchTraceBuild(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
 {
   const int overflowBlocks = gridBlocks < 64 ? gridBlocks : 64; // lanes index the same per-lane spill segments
   hipLaunchKernelGGL((traceKernel<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY>), dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, depth);
   hipLaunchKernelGGL((traceOverflowKernel<COUNT, CUTOUT, PRIMARY>), dim3(overflowBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, depth);
 }
 
-template<bool COUNT, bool PRIMARY>
-static void launchTraceOpaque(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
+// The launchers of every build device_api.hip traceBuild can return, indexed by the build's five flags (bit 0 COUNT ... bit 4
+// PRIMARY); the W7 form exists for flattened, non-PRIMARY launches only (device_types.h traceBlocksPerCU).
+using TraceLauncher = void (*)(const LaunchParams&, int, int, hipStream_t);
+template<int I>
+constexpr TraceLauncher traceLauncher()
 {
-  if (p.twoLevel)                                                      launchTraceVariant<COUNT, false, true,  false, PRIMARY>(p, depth, gridBlocks, stream);
-  else if (p.traceWaves == TWK_TRACE_WAVES7 && !(PRIMARY && TWK_PRIMARY_SIX)) launchTraceVariant<COUNT, false, false, true,  PRIMARY>(p, depth, gridBlocks, stream);
-  else                                         launchTraceVariant<COUNT, false, false, false, PRIMARY>(p, depth, gridBlocks, stream);
+  constexpr bool COUNT = I & 1, CUTOUT = I & 2, TWO_LEVEL = I & 4, W7 = I & 8, PRIMARY = I & 16;
+  if constexpr (W7 && (TWO_LEVEL || PRIMARY)) return nullptr;
+  else return launchTraceBuild<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY>;
 }
+template<int... I>
+constexpr std::array<TraceLauncher, sizeof...(I)> traceLaunchers(std::integer_sequence<int, I...>) { return {traceLauncher<I>()...}; }
 
-// gridBlocks must be numCUs x p.traceWaves (or a lane's share of it): every block of the persistent kernel resident at once.
-// primary: depth 0 of a pass whose generateKernel was skipped.
-
-void launchTrace(const LaunchParams& p, int depth, bool count, bool primary, int gridBlocks, hipStream_t stream)
+// gridBlocks must be numCUs x build.blocksPerCU (or a lane's share of it): every block of the persistent kernel resident at once.
+void launchTrace(const LaunchParams& p, int depth, bool count, const TraceBuild& build, int gridBlocks, hipStream_t stream)
 {
-  if (!p.hasCutout)
-  {
-    if (primary) { if (count) launchTraceOpaque<true, true>(p, depth, gridBlocks, stream);  else launchTraceOpaque<false, true>(p, depth, gridBlocks, stream); }
-    else         { if (count) launchTraceOpaque<true, false>(p, depth, gridBlocks, stream); else launchTraceOpaque<false, false>(p, depth, gridBlocks, stream); }
-    return;
-  }
-  if (primary)
-  {
-    if (p.twoLevel) { if (count) launchTraceVariant<true, true, true,  false, true>(p, depth, gridBlocks, stream); else launchTraceVariant<false, true, true,  false, true>(p, depth, gridBlocks, stream); }
-    else            { if (count) launchTraceVariant<true, true, false, false, true>(p, depth, gridBlocks, stream); else launchTraceVariant<false, true, false, false, true>(p, depth, gridBlocks, stream); }
-    return;
-  }
-  if (p.twoLevel) { if (count) launchTraceVariant<true, true, true,  false, false>(p, depth, gridBlocks, stream); else launchTraceVariant<false, true, true,  false, false>(p, depth, gridBlocks, stream); }
-  else if (p.traceWaves == TWK_TRACE_WAVES7) { if (count) launchTraceVariant<true, true, false, true, false>(p, depth, gridBlocks, stream); else launchTraceVariant<false, true, false, true, false>(p, depth, gridBlocks, stream); } // the flattened cutout build fits seven blocks since round 4 (71 VGPRs)
-  else            { if (count) launchTraceVariant<true, true, false, false, false>(p, depth, gridBlocks, stream); else launchTraceVariant<false, true, false, false, false>(p, depth, gridBlocks, stream); }
+  static constexpr std::array<TraceLauncher, 32> launchers = traceLaunchers(std::make_integer_sequence<int, 32>());
+  const TraceLauncher launch = launchers[(count ? 1 : 0) | (build.cutout ? 2 : 0) | (build.twoLevel ? 4 : 0) | (build.w7 ? 8 : 0) | (build.primary ? 16 : 0)];
+  assert(launch != nullptr);
+  launch(p, depth, gridBlocks, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

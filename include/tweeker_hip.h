@@ -322,13 +322,29 @@ int twk_set_next_event_estimation(TwkDevice dev, int enable);
  * NaN / infinite / negative is accumulated as super red / green / blue (1e6) instead of NaN samples being dropped; 0 (default). */
 int twk_set_debug_exceptions(TwkDevice dev, int enable);
 
+/* Output format of the accumulation and AOV buffers, ≙ Optix7Gui's compile-time USE_FP32_OUTPUT (apps/Optix7Gui/shaders/
+ * app_config.h:57-59): TWK_OUTPUT_FLOAT4 (default) = RGBA32F, 16 B per pixel; TWK_OUTPUT_HALF4 = RGBA16F (Half4, 8 B per
+ * pixel), the format of a GL_RGBA16F display texture and of OPTIX_PIXEL_FORMAT_HALF4 denoiser input. In half mode every
+ * sample is folded as in float mode from the widened half (f32 arithmetic), then rounded to nearest even
+ * (raygeneration.cu:267-317, half_common.h:36-80): what exceeds 65504 becomes +-inf. Switching synchronises the stream and
+ * reallocates the internal output and AOV buffers, zeroed; setting the current format is a no-op; an external buffer
+ * (twk_set_output_device_pointer / twk_set_shared_frame) too small for the new format is refused (TWK_ERROR_INVALID_STATE).
+ * twk_read_output / twk_read_aov keep returning RGBA32F, widened exactly; twk_read_output_raw / twk_read_aov_raw return
+ * the buffer's bytes in its format (bytes must be the pixel count times 16 or 8). */
+enum { TWK_OUTPUT_FLOAT4 = 0, TWK_OUTPUT_HALF4 = 1 };
+int twk_set_output_format(TwkDevice dev, int format);
+int twk_get_output_format(TwkDevice dev, int* format);
+int twk_read_output_raw(TwkDevice dev, void* host, size_t bytes);
+int twk_read_aov_raw(TwkDevice dev, int which, void* host, size_t bytes);
+
 /* Output. With distribution 0 the buffer is W×H (≙ outputBuffer); with distribution 1 it is the
  * packed launchWidth×H local tile buffer (≙ texelBuffer, DeviceMultiGPULocalCopy.cpp:109-172). */
 int twk_get_launch_width(TwkDevice dev, int* launchWidth);    /* ≙ m_launchWidth, DeviceMultiGPULocalCopy.cpp:84-97 */
 int twk_read_output(TwkDevice dev, float* rgbaHost, size_t numFloats); /* ≙ getOutputBufferHost, sync D2H */
 int twk_get_output_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
-/* Let the caller own the accumulation buffer (device memory of ≥ launchWidth*H*16 B, e.g. a
- * torch tensor used as RCCL send buffer). Pass NULL to return to the internal buffer. */
+/* Let the caller own the accumulation buffer (device memory of ≥ launchWidth*H*16 B, 8 B per pixel in
+ * TWK_OUTPUT_HALF4 mode, e.g. a torch tensor used as RCCL send buffer). Pass NULL to return to the internal buffer.
+ * twk_get_output_device_pointer reports launchWidth*H times the pixel size of the output format. */
 int twk_set_output_device_pointer(TwkDevice dev, void* dptr, size_t bytes);
 
 /* The reference's two other multi-GPU buffer strategies (≙ DeviceMultiGPUZeroCopy.cpp:106-118: one pinned host buffer
@@ -343,6 +359,8 @@ int twk_set_shared_frame(TwkDevice dev, void* frame, size_t bytes);
  * `tiles` is the gathered [deviceCount][H][launchWidth] RGBA32F block (device memory, rank order),
  * `output` the full W×H RGBA32F image (device memory). Runs on this handle's stream. */
 int twk_compositor(TwkDevice dev, const void* tiles, void* output);
+/* The same for RGBA16F tiles into an RGBA16F W×H frame (TWK_OUTPUT_HALF4): a plain 8-byte copy per pixel. */
+int twk_compositor_half(TwkDevice dev, const void* tiles, void* output);
 
 /* ≙ TonemapperGUI (inc/TonemapperGUI.h:34-43), same field order. Neutral defaults: gamma 1, whitePoint 1,
  * colorBalance 1 1 1, burnHighlights 1, crushBlacks 0, saturation 1, brightness 1 (Application.cpp:111-120). */
@@ -362,6 +380,9 @@ typedef struct TwkTonemapper
  * rgbaDevice NULL: the handle's own accumulation buffer (numPixels must be launchWidth*height); otherwise any
  * device buffer of numPixels float4 (e.g. the composited multi-GPU image). Synchronises the handle's stream. */
 int twk_tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaDevice, size_t numPixels, unsigned char* rgb8Host);
+/* The handle's own buffer is tonemapped in whatever format it holds. twk_tonemap_half: an explicit device buffer of numPixels
+ * RGBA16F pixels (e.g. a frame of twk_compositor_half), widened, then the same operator. */
+int twk_tonemap_half(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaHalfDevice, size_t numPixels, unsigned char* rgb8Host);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
@@ -448,6 +469,9 @@ typedef struct TwkAppInfo
 } TwkAppInfo;
 
 int twk_app_info(TwkApp app, TwkAppInfo* info);
+/* "outputFormat 0|1" of the system description (grammar extension ≙ Optix7Gui USE_FP32_OUTPUT: 1 = TWK_OUTPUT_HALF4),
+ * default 0; applied by twk_app_init_device. */
+int twk_app_get_output_format(TwkApp app, int* format);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

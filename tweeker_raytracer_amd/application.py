@@ -93,6 +93,13 @@ class Application:
         return buf.value.decode()
 
     @property
+    def outputFormat(self):
+        """"outputFormat" of the system description: 0 = RGBA32F, 1 = RGBA16F (≙ Optix7Gui USE_FP32_OUTPUT 0)."""
+        f = C.c_int(0)
+        L.check(L.lib.twk_app_get_output_format(self._h, C.byref(f)))
+        return f.value
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

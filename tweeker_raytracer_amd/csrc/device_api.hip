@@ -30,14 +30,14 @@ void launchTraceQuery(const LaunchParams& p, const float* rays, unsigned int num
 void launchGenerate(const LaunchParams& p, hipStream_t stream);
 void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
 void launchTileEntries(const LaunchParams& p, const float4* topTable, int tilesX, int tilesY, int4* out, hipStream_t stream);
-void launchAccumulate(const LaunchParams& p, hipStream_t stream);
-void launchCompositor(const float4* tiles, float4* output, int width, int height, int launchWidth, int deviceCount,
+void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream);
+void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
                       int tileSizeX, int tileShiftX, int tileShiftY, hipStream_t stream);
 void launchMathTap(int op, const float* x, const float* y, float* out, size_t n, hipStream_t stream);
 void launchStreamCopy(const float4* src, float4* dst, size_t n, hipStream_t stream);
 void launchGatherProbeFill(float4* table, size_t count, unsigned int lines, hipStream_t stream);
 void launchGatherProbe(const float4* table, unsigned int lines, int steps, float* out, int gridBlocks, hipStream_t stream);
-void launchTonemap(const float4* hdr, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
+void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
 }
 
 using namespace twk;
@@ -132,6 +132,8 @@ struct TwkDevice_t
   // per-resolution streams
   int allocatedPixels = 0;
   void* d_streamBlock = nullptr; // one allocation carved into the SoA streams
+  // output and AOV running means: RGBA32F, or RGBA16F in the same (float4-typed) pointers when outputFormat is TWK_OUTPUT_HALF4
+  int outputFormat = TWK_OUTPUT_FLOAT4; // twk_set_output_format (≙ Optix7Gui USE_FP32_OUTPUT, app_config.h:57-59)
   float4* d_outputInternal = nullptr;
   float4* d_outputExternal = nullptr; size_t outputExternalBytes = 0;
   bool outputFrame = false; // the external buffer is a shared full frame (twk_set_shared_frame)
@@ -189,6 +191,42 @@ static int activate(TwkDevice dev, const char* where, bool flush = true)
 }
 
 template<typename T> static void freeDevice(T*& p) { if (p) { (void) hipFree(p); p = nullptr; } }
+
+// Bytes of one output / AOV pixel in the handle's output format: RGBA32F 16, RGBA16F 8 (Optix7Gui Half4)
+static size_t pixelBytes(int format) { return (format == TWK_OUTPUT_HALF4) ? 8 : sizeof(float4); }
+static size_t pixelBytes(TwkDevice dev) { return pixelBytes(dev->outputFormat); }
+static bool halfOutput(TwkDevice dev) { return dev->outputFormat == TWK_OUTPUT_HALF4; }
+// Pixels of the buffer the handle accumulates into: the shared W x H frame, or its packed launchWidth x H buffer
+static size_t outputPixels(TwkDevice dev)
+{
+  return (size_t) ((dev->d_outputExternal && dev->outputFrame) ? dev->state.resolution[0] : dev->launchWidth) * dev->state.resolution[1];
+}
+
+// Exact f16 -> f32 (every half is a float): signed zeros, subnormals, +-inf and NaN payloads are kept
+static float halfToFloat(const uint16_t h)
+{
+  const uint32_t sign = (uint32_t) (h & 0x8000u) << 16, exponent = (h >> 10) & 0x1fu, mantissa = h & 0x3ffu;
+  uint32_t bits;
+  if (exponent == 0x1fu)    bits = sign | 0x7f800000u | (mantissa << 13);
+  else if (exponent != 0u)  bits = sign | ((exponent + 112u) << 23) | (mantissa << 13);
+  else if (mantissa == 0u)  bits = sign;
+  else                      bits = sign | asUint((float) mantissa * 5.9604644775390625e-8f); // mantissa * 2^-24, exact
+  return asFloat(bits);
+}
+
+// Copies `numPixels` pixels of a device output / AOV buffer to RGBA32F host memory, widening RGBA16F exactly
+static int readWidened(TwkDevice dev, const void* src, float* rgbaHost, size_t numPixels)
+{
+  if (!halfOutput(dev))
+  {
+    HIP_TRY(hipMemcpy(rgbaHost, src, numPixels * sizeof(float4), hipMemcpyDeviceToHost));
+    return TWK_SUCCESS;
+  }
+  std::vector<uint16_t> raw(numPixels * 4);
+  HIP_TRY(hipMemcpy(raw.data(), src, numPixels * 8, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < raw.size(); ++i) rgbaHost[i] = halfToFloat(raw[i]);
+  return TWK_SUCCESS;
+}
 
 // Scratch device allocation of one call; freed on every return path.
 template<typename T> struct ScopedDeviceBuffer
@@ -334,8 +372,8 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
     freeDevice(dev->d_outputInternal);
     freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
     const size_t n = (size_t) numPixels;
-    HIP_TRY(hipMalloc(&dev->d_outputInternal, n * sizeof(float4)));
-    HIP_TRY(hipMemsetAsync(dev->d_outputInternal, 0, n * sizeof(float4), dev->stream));
+    HIP_TRY(hipMalloc(&dev->d_outputInternal, n * pixelBytes(dev)));
+    HIP_TRY(hipMemsetAsync(dev->d_outputInternal, 0, n * pixelBytes(dev), dev->stream));
     HIP_TRY(hipMalloc(&dev->d_firstHit, n * sizeof(float4)));
     HIP_TRY(hipMalloc(&dev->d_firstHitInstance, n * sizeof(int)));
     dev->allocatedPixels = numPixels;
@@ -371,7 +409,7 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
     if (dev->allocatedPixels > dev->aovPixels)
     {
       freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
-      const size_t bytes = (size_t) dev->allocatedPixels * sizeof(float4);
+      const size_t bytes = (size_t) dev->allocatedPixels * pixelBytes(dev);
       HIP_TRY(hipMalloc(&dev->d_aovAlbedo, bytes));
       HIP_TRY(hipMalloc(&dev->d_aovNormal, bytes));
       HIP_TRY(hipMemsetAsync(dev->d_aovAlbedo, 0, bytes, dev->stream));
@@ -712,7 +750,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
     HIP_TRY(hipStreamWaitEvent(dev->stream, dev->laneDone[lane], 0));
   }
   // the running mean folds the samples of the pass in iteration order over ALL lanes' paths: after the join, on the handle's stream
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
@@ -841,7 +879,7 @@ try
     dev->launchWidth = (width + mask) & ~mask;
   }
   else dev->launchWidth = s->resolution[0];
-  const size_t needBytes = (size_t) (dev->outputFrame ? s->resolution[0] : dev->launchWidth) * s->resolution[1] * sizeof(float4);
+  const size_t needBytes = (size_t) (dev->outputFrame ? s->resolution[0] : dev->launchWidth) * s->resolution[1] * pixelBytes(dev);
   if (dev->d_outputExternal && dev->outputExternalBytes < needBytes)
   {
     dev->d_outputExternal = nullptr; dev->outputExternalBytes = 0; dev->outputFrame = false; // too small for the new state: fall back to the internal buffer
@@ -1341,15 +1379,58 @@ try
 {
   int rc = activate(dev, "twk_read_output"); if (rc) return rc;
   if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_output: NULL buffer");
-  const size_t n = (size_t) ((dev->d_outputExternal && dev->outputFrame) ? dev->state.resolution[0] : dev->launchWidth) * dev->state.resolution[1];
+  const size_t n = outputPixels(dev);
   if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_output: buffer must hold launchWidth*height*4 floats (width*height*4 with a shared frame)");
   const float4* src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
   if (!src) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_output: nothing has been rendered");
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(rgbaHost, src, n * sizeof(float4), hipMemcpyDeviceToHost));
+  if ((rc = readWidened(dev, src, rgbaHost, n))) return rc;
   return checkDroppedPushes(dev, "twk_read_output");
 }
 TWK_CATCH("twk_read_output")
+
+int twk_read_output_raw(TwkDevice dev, void* host, size_t bytes)
+try
+{
+  int rc = activate(dev, "twk_read_output_raw"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_output_raw: NULL buffer");
+  const size_t n = outputPixels(dev);
+  if (bytes != n * pixelBytes(dev)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_output_raw: buffer must hold launchWidth*height pixels (width*height with a shared frame) of the output format");
+  const float4* src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+  if (!src) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_output_raw: nothing has been rendered");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+  return checkDroppedPushes(dev, "twk_read_output_raw");
+}
+TWK_CATCH("twk_read_output_raw")
+
+int twk_set_output_format(TwkDevice dev, int format)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_output_format: NULL device handle");
+  if (format != TWK_OUTPUT_FLOAT4 && format != TWK_OUTPUT_HALF4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_output_format: format must be TWK_OUTPUT_FLOAT4 or TWK_OUTPUT_HALF4");
+  int rc = activate(dev, "twk_set_output_format"); if (rc) return rc;
+  if (format == dev->outputFormat) return TWK_SUCCESS;
+  if (dev->d_outputExternal && dev->stateSet && dev->outputExternalBytes < outputPixels(dev) * pixelBytes(format))
+    return twkSetError(TWK_ERROR_INVALID_STATE, "twk_set_output_format: the external output buffer is too small for the new format");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  // the internal output and AOV buffers are allocated again at the new pixel size, zeroed, by the next ensureStreams
+  freeDevice(dev->d_outputInternal);
+  freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
+  dev->outputFormat = format;
+  return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS;
+}
+TWK_CATCH("twk_set_output_format")
+
+int twk_get_output_format(TwkDevice dev, int* format)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_output_format: NULL device handle");
+  if (!format) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_output_format: NULL argument");
+  *format = dev->outputFormat;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_output_format")
 
 int twk_set_shader_variant(TwkDevice dev, int variant)
 try
@@ -1412,10 +1493,24 @@ try
   const float4* src = (which == TWK_AOV_ALBEDO) ? dev->d_aovAlbedo : dev->d_aovNormal;
   if (!dev->aovEnabled || !src || (size_t) dev->aovPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_aov: nothing has been rendered with twk_enable_aov(1)");
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(rgbaHost, src, n * sizeof(float4), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  return readWidened(dev, src, rgbaHost, n);
 }
 TWK_CATCH("twk_read_aov")
+
+int twk_read_aov_raw(TwkDevice dev, int which, void* host, size_t bytes)
+try
+{
+  int rc = activate(dev, "twk_read_aov_raw"); if (rc) return rc;
+  if (!host || (which != TWK_AOV_ALBEDO && which != TWK_AOV_NORMAL)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_aov_raw: bad arguments");
+  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
+  if (bytes != n * pixelBytes(dev)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_aov_raw: buffer must hold launchWidth*height pixels of the output format");
+  const float4* src = (which == TWK_AOV_ALBEDO) ? dev->d_aovAlbedo : dev->d_aovNormal;
+  if (!dev->aovEnabled || !src || (size_t) dev->aovPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_aov_raw: nothing has been rendered with twk_enable_aov(1)");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_aov_raw")
 
 int twk_get_output_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
@@ -1425,7 +1520,7 @@ try
   if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_output_device_pointer: twk_set_state first");
   if ((rc = ensureStreams(dev))) return rc;
   *dptr = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(float4);
+  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * pixelBytes(dev);
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_output_device_pointer")
@@ -1437,7 +1532,7 @@ try
   HIP_TRY(hipStreamSynchronize(dev->stream));
   if (dptr == nullptr) { dev->d_outputExternal = nullptr; dev->outputExternalBytes = 0; dev->outputFrame = false; return TWK_SUCCESS; }
   if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_set_output_device_pointer: twk_set_state first");
-  if (bytes < (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(float4)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_output_device_pointer: buffer smaller than launchWidth*height*16 bytes");
+  if (bytes < (size_t) dev->launchWidth * dev->state.resolution[1] * pixelBytes(dev)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_output_device_pointer: buffer smaller than launchWidth*height pixels of the output format (16 bytes RGBA32F, 8 RGBA16F)");
   dev->d_outputExternal = static_cast<float4*>(dptr); dev->outputExternalBytes = bytes; dev->outputFrame = false;
   return TWK_SUCCESS;
 }
@@ -1450,24 +1545,48 @@ try
   HIP_TRY(hipStreamSynchronize(dev->stream));
   if (frame == nullptr) { dev->d_outputExternal = nullptr; dev->outputExternalBytes = 0; dev->outputFrame = false; return TWK_SUCCESS; }
   if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_set_shared_frame: twk_set_state first");
-  if (bytes < (size_t) dev->state.resolution[0] * dev->state.resolution[1] * sizeof(float4)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_shared_frame: buffer smaller than width*height*16 bytes");
+  if (bytes < (size_t) dev->state.resolution[0] * dev->state.resolution[1] * pixelBytes(dev)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_shared_frame: buffer smaller than width*height pixels of the output format (16 bytes RGBA32F, 8 RGBA16F)");
   dev->d_outputExternal = static_cast<float4*>(frame); dev->outputExternalBytes = bytes; dev->outputFrame = true;
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_set_shared_frame")
 
-int twk_compositor(TwkDevice dev, const void* tiles, void* output)
-try
+static int compositor(TwkDevice dev, const void* tiles, void* output, bool half, const char* where)
 {
-  int rc = activate(dev, "twk_compositor"); if (rc) return rc;
-  if (!tiles || !output) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_compositor: NULL buffer");
-  if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_compositor: twk_set_state first");
-  launchCompositor(static_cast<const float4*>(tiles), static_cast<float4*>(output), dev->state.resolution[0], dev->state.resolution[1],
+  int rc = activate(dev, where); if (rc) return rc;
+  if (!tiles || !output) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + ": NULL buffer");
+  if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": twk_set_state first");
+  launchCompositor(tiles, output, half, dev->state.resolution[0], dev->state.resolution[1],
                    dev->launchWidth, dev->count, dev->state.tileSize[0], calculateShift(dev->state.tileSize[0]), calculateShift(dev->state.tileSize[1]), dev->stream);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
+
+int twk_compositor(TwkDevice dev, const void* tiles, void* output)
+try
+{
+  return compositor(dev, tiles, output, false, "twk_compositor");
+}
 TWK_CATCH("twk_compositor")
+
+int twk_compositor_half(TwkDevice dev, const void* tiles, void* output)
+try
+{
+  return compositor(dev, tiles, output, true, "twk_compositor_half");
+}
+TWK_CATCH("twk_compositor_half")
+
+static int tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* src, bool half, size_t numPixels, unsigned char* rgb8Host)
+{
+  if (numPixels == 0) return TWK_SUCCESS;
+  ScopedDeviceBuffer<unsigned char> ldr;
+  HIP_TRY(ldr.allocate(numPixels * 3));
+  launchTonemap(src, half, ldr.ptr, numPixels, *tm, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rgb8Host, ldr.ptr, numPixels * 3, hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return TWK_SUCCESS;
+}
 
 int twk_tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaDevice, size_t numPixels, unsigned char* rgb8Host)
 try
@@ -1475,23 +1594,24 @@ try
   int rc = activate(dev, "twk_tonemap"); if (rc) return rc;
   if (!tm || !rgb8Host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: NULL argument");
   if (!(tm->gamma > 0.0f) || !(tm->whitePoint > 0.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: gamma and whitePoint must be positive");
-  const float4* src = static_cast<const float4*>(rgbaDevice);
-  if (!src)
-  {
-    src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-    if (!src || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_tonemap: nothing has been rendered");
-    if (numPixels != (size_t) dev->launchWidth * dev->state.resolution[1]) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: numPixels must be launchWidth*height for the handle's own buffer");
-  }
-  if (numPixels == 0) return TWK_SUCCESS;
-  ScopedDeviceBuffer<unsigned char> ldr;
-  HIP_TRY(ldr.allocate(numPixels * 3));
-  launchTonemap(src, ldr.ptr, numPixels, *tm, dev->stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(rgb8Host, ldr.ptr, numPixels * 3, hipMemcpyDeviceToHost, dev->stream));
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  return TWK_SUCCESS;
+  if (rgbaDevice) return tonemap(dev, tm, rgbaDevice, false, numPixels, rgb8Host);
+  // the handle's own buffer, in whatever format it holds
+  const float4* src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+  if (!src || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_tonemap: nothing has been rendered");
+  if (numPixels != (size_t) dev->launchWidth * dev->state.resolution[1]) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: numPixels must be launchWidth*height for the handle's own buffer");
+  return tonemap(dev, tm, src, halfOutput(dev), numPixels, rgb8Host);
 }
 TWK_CATCH("twk_tonemap")
+
+int twk_tonemap_half(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaHalfDevice, size_t numPixels, unsigned char* rgb8Host)
+try
+{
+  int rc = activate(dev, "twk_tonemap_half"); if (rc) return rc;
+  if (!tm || !rgbaHalfDevice || !rgb8Host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap_half: NULL argument");
+  if (!(tm->gamma > 0.0f) || !(tm->whitePoint > 0.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap_half: gamma and whitePoint must be positive");
+  return tonemap(dev, tm, rgbaHalfDevice, true, numPixels, rgb8Host);
+}
+TWK_CATCH("twk_tonemap_half")
 
 // ---- measurement ------------------------------------------------------------------------------
 int twk_profile_enable(TwkDevice dev, int enable)

@@ -200,14 +200,14 @@ struct LaunchParams
   float4* pathNormal;     //   camera-space shading normal of the primary hit
   float*  pathTime;       // time view (≙ USE_TIME_VIEW, raygeneration.cu:169-171,231-244), per path, nullptr when off: shader-clock cycles the path's lanes spent in traversal and shading
   float   clockScale;     // clockFactor * 1e-9 (Device.h:350 CLOCK_FACTOR_SCALE): cycles -> the alpha the colour ramp reads
-  float4* aovAlbedo;      // their running means per launch index (raygeneration.cu:239-262)
+  float4* aovAlbedo;      // their running means per launch index (raygeneration.cu:239-262); RGBA16F like `output` in half mode
   float4* aovNormal;
   int     shaderVariant;  // TWK_SHADERS_RTIGO3 / TWK_SHADERS_OPTIX7GUI (include/tweeker_hip.h)
   int     shadeSort;      // shadeKernel shades the slots of a block's window in class order (shade_kernels.hip "class-coherent execution"): 1 = in every launch but the first of a pass (default), 2 = in the first too, 0 = slot order (TWK_SHADE_SORT)
   int     nextEventEstimation; // ≙ USE_NEXT_EVENT_ESTIMATION (shaders/config.h:50-52), a run-time switch here (twk_set_next_event_estimation): 0 = brute-force path tracing, no light sampling, no MIS weights
   int     debugExceptions;     // ≙ USE_DEBUG_EXCEPTIONS (config.h:54-56; raygeneration.cu:205-218): NaN / Inf / negative samples become super red / green / blue instead of NaN being dropped
   int     outputFrame;    // 1: `output` is a shared full W x H frame addressed by absolute pixel (ZeroCopy / PeerAccess strategies), 0: this device's packed launchWidth x H buffer
-  float4* output;         // running mean, RGBA32F
+  float4* output;         // running mean, RGBA32F; in half mode (twk_set_output_format TWK_OUTPUT_HALF4) the same bytes hold RGBA16F, which only accumulateHalfKernel addresses
   unsigned int* counters; // see CounterSlot
   unsigned long long* stats; // TwkLaunchStats as 7 u64, or nullptr
   float4* firstHit;       // debug capture (t, beta, gamma, prim) or nullptr

@@ -104,6 +104,8 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
     // description cannot reach there (they need a rebuild): USE_NEXT_EVENT_ESTIMATION and USE_DEBUG_EXCEPTIONS.
     else if (key == "nextEventEstimation") { ok = readInt(parser, i[0]); if (ok) nextEventEstimation = (i[0] != 0) ? 1 : 0; }
     else if (key == "debugExceptions")     { ok = readInt(parser, i[0]); if (ok) debugExceptions = (i[0] != 0) ? 1 : 0; }
+    // and for Optix7Gui's USE_FP32_OUTPUT (apps/Optix7Gui/shaders/app_config.h:57-59): 1 = RGBA16F output (USE_FP32_OUTPUT 0)
+    else if (key == "outputFormat")        { ok = readInt(parser, i[0]); if (ok) outputFormat = (i[0] == 1) ? 1 : 0; }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -150,6 +152,7 @@ std::string Application::systemDescription() const
   if (shaderVariant != 0) d << "shaderVariant " << shaderVariant << std::endl;
   if (nextEventEstimation != 1) d << "nextEventEstimation " << nextEventEstimation << std::endl;
   if (debugExceptions != 0) d << "debugExceptions " << debugExceptions << std::endl;
+  if (outputFormat != 0) d << "outputFormat " << outputFormat << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

@@ -87,6 +87,16 @@ try
 }
 TWK_CATCH("twk_app_info")
 
+int twk_app_get_output_format(TwkApp app, int* format)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_output_format: NULL app");
+  if (!format) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_output_format: NULL argument");
+  *format = app->app.outputFormat;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_output_format")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -178,6 +188,7 @@ try
   if ((rc = twk_set_shader_variant(dev, a.shaderVariant))) return rc;
   if ((rc = twk_set_next_event_estimation(dev, a.nextEventEstimation))) return rc;
   if ((rc = twk_set_debug_exceptions(dev, a.debugExceptions))) return rc;
+  if ((rc = twk_set_output_format(dev, a.outputFormat))) return rc;
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;
   if ((rc = twk_init_materials(dev, a.materials.data(), (int) a.materials.size()))) return rc;

@@ -147,8 +147,13 @@ int main(int argc, char* argv[])
   // Buffer strategy (Raytracer.cpp:125-176 picks the Device flavour): 1 = zero copy — one pinned host frame mapped into
   // every device (DeviceMultiGPUZeroCopy.cpp:106-118); 2 = peer access — one frame on the first device, written by its
   // peers (DeviceMultiGPUPeerAccess.cpp:110-158); 3 = local copy — packed tile buffers + compositor.
+  // "outputFormat 1" (≙ Optix7Gui USE_FP32_OUTPUT 0): every buffer below holds RGBA16F, 8 bytes per pixel
+  int outputFormat = TWK_OUTPUT_FLOAT4;
+  TWK_OK(twk_app_get_output_format(app, &outputFormat));
+  const bool half = (outputFormat == TWK_OUTPUT_HALF4);
+  const size_t pixelBytes = half ? 8 : 16;
   void* sharedFrame = nullptr;
-  const size_t frameBytes = (size_t) info.resolution[0] * info.resolution[1] * 16;
+  const size_t frameBytes = (size_t) info.resolution[0] * info.resolution[1] * pixelBytes;
   if (count > 1 && info.strategy == 1)
   {
     HIP_OK(hipHostMalloc(&sharedFrame, frameBytes, hipHostMallocPortable | hipHostMallocMapped));
@@ -206,17 +211,19 @@ int main(int argc, char* argv[])
   }
   else if (sharedFrame)
   {
-    TWK_OK(twk_tonemap(devices[0], &tonemapper, sharedFrame, numPixels, rgb8.data())); // every device wrote its pixels straight into the frame
+    // every device wrote its pixels straight into the frame
+    if (half) TWK_OK(twk_tonemap_half(devices[0], &tonemapper, sharedFrame, numPixels, rgb8.data()));
+    else      TWK_OK(twk_tonemap(devices[0], &tonemapper, sharedFrame, numPixels, rgb8.data()));
   }
   else
   {
     int launchWidth = 0;
     TWK_OK(twk_get_launch_width(devices[0], &launchWidth));
-    const size_t tileBytes = (size_t) launchWidth * height * 16;
+    const size_t tileBytes = (size_t) launchWidth * height * pixelBytes;
     void* tiles = nullptr; void* full = nullptr;
     HIP_OK(hipSetDevice(ordinals[0]));
     HIP_OK(hipMalloc(&tiles, tileBytes * count));
-    HIP_OK(hipMalloc(&full, numPixels * 16));
+    HIP_OK(hipMalloc(&full, numPixels * pixelBytes));
     for (int i = 0; i < count; ++i)
     {
       void* src = nullptr; size_t bytes = 0;
@@ -226,8 +233,16 @@ int main(int argc, char* argv[])
     // device-to-device copies return before they have finished and the handle's stream is non-blocking: wait here,
     // or the compositor reads tiles that are still in flight
     HIP_OK(hipDeviceSynchronize());
-    TWK_OK(twk_compositor(devices[0], tiles, full));
-    TWK_OK(twk_tonemap(devices[0], &tonemapper, full, numPixels, rgb8.data()));
+    if (half)
+    {
+      TWK_OK(twk_compositor_half(devices[0], tiles, full));
+      TWK_OK(twk_tonemap_half(devices[0], &tonemapper, full, numPixels, rgb8.data()));
+    }
+    else
+    {
+      TWK_OK(twk_compositor(devices[0], tiles, full));
+      TWK_OK(twk_tonemap(devices[0], &tonemapper, full, numPixels, rgb8.data()));
+    }
     HIP_OK(hipFree(tiles)); HIP_OK(hipFree(full));
   }
   char path[4096];

@@ -990,24 +990,34 @@ TWK_D void generatePath(const LaunchParams& p, const unsigned int index)
   if (index == 0) p.counters[0] = (unsigned int) p.numPaths;
 }
 
-// Body of accumulateKernel for launch index `index` (raygeneration.cu:222-253).
-TWK_D void accumulateLaunchIndex(const LaunchParams& p, const unsigned int index)
+// Where launch index `index` accumulates: its slot of the packed tile buffer (single device, LocalCopy), or — shared frame of
+// the ZeroCopy / PeerAccess strategies — the pixel it maps to, as __raygen__path_tracer addresses sysData.outputBuffer
+// (raygeneration.cu:175-183,229): index = y * W + distribute(launch index). False: the launch index has no pixel there.
+TWK_D bool accumulateTarget(const LaunchParams& p, const unsigned int index, size_t& outIndex)
 {
-  const bool aov = (p.aovAlbedo != nullptr);
-  // Where this launch index accumulates: its slot of the packed tile buffer (single device, LocalCopy), or — shared
-  // frame of the ZeroCopy / PeerAccess strategies — the pixel it maps to, as __raygen__path_tracer addresses
-  // sysData.outputBuffer (raygeneration.cu:175-183,229): index = y * W + distribute(launch index)
-  size_t outIndex = index;
+  outIndex = index;
   if (p.outputFrame)
   {
     const unsigned int lx = index % (unsigned int) p.launchWidth, ly = index / (unsigned int) p.launchWidth;
     const unsigned int column = (p.distribution && 1 < p.deviceCount) ? distribute(p, lx, ly) : lx;
-    if (column >= (unsigned int) p.resolution[0]) return;
+    if (column >= (unsigned int) p.resolution[0]) return false;
     outIndex = (size_t) ly * (unsigned int) p.resolution[0] + column;
   }
-  float4 dst = p.output[outIndex];
-  float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  return true;
+}
+
+// The buffers hold what they were given: RGBA32F (accumulateLaunchIndex). The RGBA16F build (shade_kernels.hip
+// accumulateHalfKernel) passes a functor that rounds to half and widens back.
+struct StoredAsFloat { TWK_HD float4 operator()(const float4 v) const { return v; } };
+
+// The per-sample fold of accumulateKernel (raygeneration.cu:205-253) over the batchCount samples of launch index `index`, in
+// iteration order, on the running means dst / dstAlbedo / dstNormal as read from the buffers. After every folded sample the
+// means become `stored(...)` of themselves, what the buffers would hold had the sample been written by a launch of its own, so
+// that a batch equals batchCount separate launches in either output format. Returns whether any sample was folded.
+template<typename Stored>
+TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored)
+{
+  const bool aov = (p.aovAlbedo != nullptr);
   bool touched = false;
   for (int s = 0; s < p.batchCount; ++s)
   {
@@ -1043,13 +1053,25 @@ TWK_D void accumulateLaunchIndex(const LaunchParams& p, const unsigned int index
           if (isNotNull(normal)) normal = normalize(normal);
         }
       }
-      dst = make_float4(radiance.x, radiance.y, radiance.z, alpha);
-      dstAlbedo = make_float4(albedo.x, albedo.y, albedo.z, 1.0f);
-      dstNormal = make_float4(normal.x, normal.y, normal.z, 0.0f);
+      dst = stored(make_float4(radiance.x, radiance.y, radiance.z, alpha));
+      dstAlbedo = stored(make_float4(albedo.x, albedo.y, albedo.z, 1.0f));
+      dstNormal = stored(make_float4(normal.x, normal.y, normal.z, 0.0f));
       touched = true;
     }
   }
-  if (touched)
+  return touched;
+}
+
+// Body of accumulateKernel for launch index `index` (raygeneration.cu:222-253): the RGBA32F output and AOV buffers.
+TWK_D void accumulateLaunchIndex(const LaunchParams& p, const unsigned int index)
+{
+  const bool aov = (p.aovAlbedo != nullptr);
+  size_t outIndex;
+  if (!accumulateTarget(p, index, outIndex)) return;
+  float4 dst = p.output[outIndex];
+  float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (foldSamples(p, index, dst, dstAlbedo, dstNormal, StoredAsFloat()))
   {
     p.output[outIndex] = dst;
     if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }

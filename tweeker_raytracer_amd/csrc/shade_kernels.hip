@@ -6,6 +6,7 @@
 //                    light callables (bxdf_*.cu, light_sample.cu) and the integrator loop body after the
 //                    trace raygeneration.cu:91-146
 //   accumulateKernel NaN filter + running mean                              raygeneration.cu:222-253
+//                    (accumulateHalfKernel: Optix7Gui's RGBA16F buffers     raygeneration.cu:267-317)
 //   compositorKernel compositor.cu:38-64 for all source devices at once
 // Per-path RNG draw order is the reference's: jitter rng2; per bounce the BSDF's draws, then NEE rng2
 // [+ rng when more than one light], then Russian roulette rng.
@@ -435,8 +436,49 @@ __global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p)
   accumulateLaunchIndex(p, index);
 }
 
-// compositor.cu:38-64 for every source device in one launch: tiles is [deviceCount][H][launchWidth].
-__global__ void __launch_bounds__(256) compositorKernel(const float4* __restrict__ tiles, float4* __restrict__ output,
+// Optix7Gui's RGBA16F output (USE_FP32_OUTPUT 0, app_config.h:57-59; Half4 of half_common.h:36-80). alignas(8): one
+// global_load_dwordx2 / global_store_dwordx2 per pixel (a plain struct of four _Float16 loads as a ushort plus a dword).
+struct alignas(8) Half4 { _Float16 x, y, z, w; };
+static_assert(sizeof(Half4) == 8, "RGBA16F pixel");
+
+TWK_D float4 widen(const Half4 h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); } // exact
+TWK_D float4 widen(const float4 v) { return v; }
+// f32 -> f16 round to nearest even (v_cvt_f16_f32 = __float2half; NOT v_cvt_pkrtz_f16_f32, which rounds toward zero):
+// half subnormals are kept (the code object's float_denorm_mode_16_64 is 3), what exceeds 65504 rounds to +-inf.
+TWK_D Half4 narrow(const float4 v)
+{
+  Half4 h;
+  h.x = (_Float16) v.x; h.y = (_Float16) v.y; h.z = (_Float16) v.z; h.w = (_Float16) v.w;
+  return h;
+}
+struct StoredAsHalf { TWK_D float4 operator()(const float4 v) const { return widen(narrow(v)); } };
+
+// accumulateKernel on RGBA16F output and AOV buffers (raygeneration.cu:267-317): the lerp operand is the widened half and the
+// arithmetic the f32 expression of the float build, rounded once per folded sample (foldSamples).
+__global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
+{
+  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
+  if (index >= (unsigned int) p.numPixels) return;
+  size_t outIndex;
+  if (!accumulateTarget(p, index, outIndex)) return;
+  Half4* output = reinterpret_cast<Half4*>(p.output);
+  Half4* aovAlbedo = reinterpret_cast<Half4*>(p.aovAlbedo);
+  Half4* aovNormal = reinterpret_cast<Half4*>(p.aovNormal);
+  const bool aov = (aovAlbedo != nullptr);
+  float4 dst = widen(output[outIndex]);
+  float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (foldSamples(p, index, dst, dstAlbedo, dstNormal, StoredAsHalf()))
+  {
+    output[outIndex] = narrow(dst); // dst is already a widened half: narrow() is exact here
+    if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
+  }
+}
+
+// compositor.cu:38-64 for every source device in one launch: tiles is [deviceCount][H][launchWidth]. Pixel: float4 or Half4
+// (a plain 8-byte copy).
+template<typename Pixel>
+__global__ void __launch_bounds__(256) compositorKernel(const Pixel* __restrict__ tiles, Pixel* __restrict__ output,
                                                          int width, int height, int launchWidth, int deviceCount,
                                                          int tileSizeX, int tileShiftX, int tileShiftY)
 {
@@ -486,11 +528,12 @@ TWK_D V3 pow3(const V3& v, float e) { return v3(powP(v.x, e), powP(v.y, e), powP
 TWK_D V3 max3(const V3& v, float lo) { return v3(fmaxf(lo, v.x), fmaxf(lo, v.y), fmaxf(lo, v.z)); }
 TWK_D float saturateP(float v) { return fmaxf(0.0f, fminf(v, 1.0f)); } // clamp(), vector_math.h:148-151
 
-__global__ void tonemapKernel(const float4* __restrict__ hdr, unsigned char* __restrict__ ldr, size_t numPixels, TonemapConstants c)
+template<typename Pixel> // float4, or Half4 widened first
+__global__ void tonemapKernel(const Pixel* __restrict__ hdr, unsigned char* __restrict__ ldr, size_t numPixels, TonemapConstants c)
 {
   for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < numPixels; i += (size_t) gridDim.x * blockDim.x)
   {
-    const V3 hdrColor = v3(hdr[i]);
+    const V3 hdrColor = v3(widen(hdr[i]));
     V3 ldrColor = v3(c.invWhitePoint * c.colorBalance[0], c.invWhitePoint * c.colorBalance[1], c.invWhitePoint * c.colorBalance[2]) * hdrColor; // :2275
     ldrColor = ldrColor * v3((ldrColor.x * c.burnHighlights + 1.0f) / (ldrColor.x + 1.0f),
                              (ldrColor.y * c.burnHighlights + 1.0f) / (ldrColor.y + 1.0f),
@@ -601,21 +644,27 @@ void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks,
   assert(launch != nullptr);
   launch(p, depth, gridBlocks, stream);
 }
-void launchAccumulate(const LaunchParams& p, hipStream_t stream)
+void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream)
 {
-  hipLaunchKernelGGL(accumulateKernel, dim3((p.numPixels + 255) / 256), dim3(256), 0, stream, p);
+  if (half) hipLaunchKernelGGL(accumulateHalfKernel, dim3((p.numPixels + 255) / 256), dim3(256), 0, stream, p);
+  else      hipLaunchKernelGGL(accumulateKernel, dim3((p.numPixels + 255) / 256), dim3(256), 0, stream, p);
 }
-void launchCompositor(const float4* tiles, float4* output, int width, int height, int launchWidth, int deviceCount,
+// half: tiles and output are Half4
+void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
                       int tileSizeX, int tileShiftX, int tileShiftY, hipStream_t stream)
 {
-  hipLaunchKernelGGL(compositorKernel, dim3((launchWidth + 255) / 256, height, deviceCount), dim3(256), 0, stream,
-                     tiles, output, width, height, launchWidth, deviceCount, tileSizeX, tileShiftX, tileShiftY);
+  const dim3 grid((launchWidth + 255) / 256, height, deviceCount);
+  if (half) hipLaunchKernelGGL(compositorKernel<Half4>, grid, dim3(256), 0, stream, static_cast<const Half4*>(tiles), static_cast<Half4*>(output),
+                               width, height, launchWidth, deviceCount, tileSizeX, tileShiftX, tileShiftY);
+  else      hipLaunchKernelGGL(compositorKernel<float4>, grid, dim3(256), 0, stream, static_cast<const float4*>(tiles), static_cast<float4*>(output),
+                               width, height, launchWidth, deviceCount, tileSizeX, tileShiftX, tileShiftY);
 }
 void launchMathTap(int op, const float* x, const float* y, float* out, size_t n, hipStream_t stream)
 {
   hipLaunchKernelGGL(mathTapKernel, dim3(1024), dim3(256), 0, stream, op, x, y, out, n);
 }
-void launchTonemap(const float4* hdr, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream)
+// half: hdr is Half4
+void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream)
 {
   TonemapConstants c;
   c.invGamma       = 1.0f / tm.gamma;
@@ -624,7 +673,8 @@ void launchTonemap(const float4* hdr, unsigned char* ldr, size_t numPixels, cons
   c.crushBlacks    = tm.crushBlacks + tm.crushBlacks + 1.0f;
   c.saturation     = tm.saturation;
   c.colorBalance[0] = tm.colorBalance[0]; c.colorBalance[1] = tm.colorBalance[1]; c.colorBalance[2] = tm.colorBalance[2];
-  hipLaunchKernelGGL(tonemapKernel, dim3(2048), dim3(256), 0, stream, hdr, ldr, numPixels, c);
+  if (half) hipLaunchKernelGGL(tonemapKernel<Half4>, dim3(2048), dim3(256), 0, stream, static_cast<const Half4*>(hdr), ldr, numPixels, c);
+  else      hipLaunchKernelGGL(tonemapKernel<float4>, dim3(2048), dim3(256), 0, stream, static_cast<const float4*>(hdr), ldr, numPixels, c);
 }
 void launchStreamCopy(const float4* src, float4* dst, size_t n, hipStream_t stream)
 {

@@ -129,12 +129,27 @@ class Device:
         """≙ USE_DEBUG_EXCEPTIONS (raygeneration.cu:205-218): NaN / Inf / negative samples accumulate as super red / green / blue."""
         L.check(L.lib.twk_set_debug_exceptions(self._h, int(bool(enable))))
 
-    def readAov(self, which):
-        """Denoiser AOV running means: which = 0 albedo, 1 camera-space normal; float32 [height, launchWidth, 4]."""
+    def readAov(self, which, raw=False):
+        """Denoiser AOV running means: which = 0 albedo, 1 camera-space normal; float32 [height, launchWidth, 4] (widened
+        exactly in half mode). raw=True: the buffer as it is held, float16 in half mode (float32 otherwise)."""
         h, w = self.state.resolution[1], self.launchWidth
+        if raw:
+            out = np.empty((h, w, 4), dtype=np.float16 if self.outputFormat == L.TWK_OUTPUT_HALF4 else np.float32)
+            L.check(L.lib.twk_read_aov_raw(self._h, int(which), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)))
+            return out
         out = np.empty((h, w, 4), dtype=np.float32)
         L.check(L.lib.twk_read_aov(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
+
+    def setOutputFormat(self, fmt):
+        """0 = RGBA32F (default), 1 = RGBA16F output and AOV buffers (≙ Optix7Gui USE_FP32_OUTPUT 0). Reallocates them, zeroed."""
+        L.check(L.lib.twk_set_output_format(self._h, int(fmt)))
+
+    @property
+    def outputFormat(self):
+        f = C.c_int(0)
+        L.check(L.lib.twk_get_output_format(self._h, C.byref(f)))
+        return f.value
 
     def setBuildQuality(self, quality):
         """0 = LBVH (Morton + radix tree), 1 = binned SAH (default)."""
@@ -182,6 +197,13 @@ class Device:
         L.check(L.lib.twk_read_output(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
+    def getOutputBufferHalf(self):
+        """The RGBA16F running mean as held in half mode (setOutputFormat(1)): float16 [height, launchWidth, 4]."""
+        h, w = self.state.resolution[1], (self.state.resolution[0] if getattr(self, "_sharedFrame", False) else self.launchWidth)
+        out = np.empty((h, w, 4), dtype=np.float16)
+        L.check(L.lib.twk_read_output_raw(self._h, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)))
+        return out
+
     def outputDevicePointer(self):
         p, n = C.c_void_p(), C.c_size_t(0)
         L.check(L.lib.twk_get_output_device_pointer(self._h, C.byref(p), C.byref(n)))
@@ -190,8 +212,10 @@ class Device:
     def setOutputDevicePointer(self, dptr, nbytes):
         L.check(L.lib.twk_set_output_device_pointer(self._h, C.c_void_p(dptr), C.c_size_t(nbytes)))
 
-    def compositor(self, tiles_dptr, output_dptr):
-        L.check(L.lib.twk_compositor(self._h, C.c_void_p(tiles_dptr), C.c_void_p(output_dptr)))
+    def compositor(self, tiles_dptr, output_dptr, half=False):
+        """half=True: RGBA16F tiles into an RGBA16F frame (twk_compositor_half)."""
+        fn = L.lib.twk_compositor_half if half else L.lib.twk_compositor
+        L.check(fn(self._h, C.c_void_p(tiles_dptr), C.c_void_p(output_dptr)))
 
     # ---- measurement / parity taps ------------------------------------------------------------
     def profileEnable(self, enable=True):
@@ -206,11 +230,18 @@ class Device:
         L.check(L.lib.twk_profile_get(self._h, ms, n))
         return {k: {"ms": ms[i], "launches": n[i]} for i, k in enumerate(KERNEL_CLASSES)}
 
-    def tonemap(self, tonemapper=None, rgbaDevicePointer=None, shape=None):
+    def tonemap(self, tonemapper=None, rgbaDevicePointer=None, shape=None, half=False):
         """RGBA32F → RGB8 with the reference's tonemapper (Application.cpp:2259-2297) on the device. Without a pointer
-        the handle's own accumulation buffer (launchWidth x height) is converted; returns uint8 [H, W, 3], row 0 at the
-        bottom like the float buffer."""
+        the handle's own accumulation buffer (launchWidth x height, in its output format) is converted; returns uint8
+        [H, W, 3], row 0 at the bottom like the float buffer. half=True: rgbaDevicePointer holds RGBA16F (twk_tonemap_half)."""
         tm = tonemapper if tonemapper is not None else L.Tonemapper()
+        if half:
+            assert rgbaDevicePointer is not None, "tonemap(half=True) needs an explicit RGBA16F device buffer"
+            h, w = shape
+            out = np.empty((h, w, 3), dtype=np.uint8)
+            L.check(L.lib.twk_tonemap_half(self._h, C.byref(tm), C.c_void_p(int(rgbaDevicePointer)), C.c_size_t(h * w),
+                                           out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+            return out
         if rgbaDevicePointer is None:
             h, w = self.state.resolution[1], self.launchWidth
             ptr = None

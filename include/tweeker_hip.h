@@ -270,6 +270,13 @@ typedef struct TwkBuildInfo
 } TwkBuildInfo;
 int twk_get_build_info(TwkDevice dev, TwkBuildInfo* info);
 
+/* Layout of the path streams a wavefront pass over the built scene uses, with the materials as they are now. SLIM: every
+ * instance is flattened and no material has cutout opacity — the instance of a hit rides in the hit record's slot word and
+ * the launch index of a shadow ray in its pending record, 8 bytes less per path and bounce. FULL: every other scene, and
+ * every scene under TWK_SLIM_STREAMS=0. The images are the same bit for bit. */
+enum { TWK_STREAMS_FULL = 0, TWK_STREAMS_SLIM = 1 };
+int twk_get_stream_layout(TwkDevice dev, int* layout);
+
 /* Flattening policy of the next twk_build (defaults TWK_FLATTEN_TRIANGLES, TWK_FLATTEN_REFERENCES; see there). */
 int twk_set_flatten_policy(TwkDevice dev, int maxTriangles, int maxReferences);
 

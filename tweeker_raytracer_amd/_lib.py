@@ -103,7 +103,7 @@ SYMBOLS = [
     "twk_last_error", "twk_abi_version", "twk_device_count", "twk_device_create", "twk_device_destroy",
     "twk_set_state", "twk_init_cameras", "twk_init_lights", "twk_init_materials", "twk_update_camera",
     "twk_update_light", "twk_update_material", "twk_init_texture", "twk_add_geometry", "twk_add_instance",
-    "twk_build", "twk_clear_scene", "twk_set_flatten_policy", "twk_set_build_quality", "twk_get_build_info", "twk_launch", "twk_sync", "twk_set_launch_batch", "twk_reserve_launch_batch", "twk_get_launch_width", "twk_read_output",
+    "twk_build", "twk_clear_scene", "twk_set_flatten_policy", "twk_set_build_quality", "twk_get_build_info", "twk_get_stream_layout", "twk_launch", "twk_sync", "twk_set_launch_batch", "twk_reserve_launch_batch", "twk_get_launch_width", "twk_read_output",
     "twk_set_shader_variant", "twk_enable_aov", "twk_read_aov", "twk_set_time_view", "twk_set_next_event_estimation", "twk_set_debug_exceptions", "twk_get_output_device_pointer", "twk_set_output_device_pointer", "twk_set_shared_frame", "twk_compositor", "twk_tonemap", "twk_profile_enable",
     "twk_set_output_format", "twk_get_output_format", "twk_read_output_raw", "twk_read_aov_raw", "twk_compositor_half", "twk_tonemap_half",
     "twk_app_get_output_format",

@@ -142,7 +142,8 @@ struct TwkDevice_t
   unsigned int* h_dropped = nullptr; unsigned int* d_dropped = nullptr; // pinned + device-mapped: LaunchParams::droppedPushes
   int* d_spill = nullptr; size_t spillLanes = 0;
   bool packedQueue = true; // TWK_PACKED_QUEUE=0: A/B
-  int shadeSort = 1;       // TWK_SHADE_SORT=0: slot order (A/B); 1: class order in every launch but the first of a pass; 2: in the first too
+  bool slimStreams = true; // TWK_SLIM_STREAMS=0: A/B (device_types.h LaunchParams::slimSlotBits)
+  int shadeSort = 1;      // TWK_SHADE_SORT=0: slot order (A/B); 1: class order in every launch but the first of a pass; 2: in the first too
   float4* d_firstHit = nullptr; int* d_firstHitInstance = nullptr;
   // denoiser AOVs (Optix7Gui raygeneration.cu:125-164): per-path values of a pass and their running means per launch index
   bool aovEnabled = false; int shaderVariant = TWK_SHADERS_RTIGO3;
@@ -353,6 +354,20 @@ static void refreshParams(TwkDevice dev)
   p.traceStackSpill = dev->d_spill;
   p.droppedPushes = dev->d_dropped;
   p.packedQueue = 0; // renderPass decides per pass
+  p.slimSlotBits = 0; // likewise; twk_debug_trace_queue feeds and reads the full layout
+}
+
+// Slim streams (device_types.h LaunchParams::slimSlotBits) for the scene as refreshParams last described it: the bits of a
+// triangle slot in the hit record's slot word, or 0 = the full layout — a scene with an entered instance (inside one, a slot
+// does not name its instance) or with cutout opacity (the shadow ray's seed word is in use), a scene whose slots and instances
+// do not fit one positive word together, or TWK_SLIM_STREAMS=0.
+static int slimSlotBits(TwkDevice dev)
+{
+  const LaunchParams& p = dev->params;
+  if (!dev->slimStreams || dev->twoLevel || p.hasCutout) return 0;
+  int bits = 1;
+  while (bits < 31 && ((size_t) 1 << bits) < dev->totalTriangles) ++bits;
+  return ((size_t) p.numInstances <= ((size_t) 1 << (31 - bits))) ? bits : 0;
 }
 
 static int traceGridBlocks(TwkDevice dev) { return dev->numCUs * TWK_TRACE_WAVES7; } // the largest persistent grid (sizes the spill stacks); a launch uses numCUs x traceBuild's blocksPerCU
@@ -647,6 +662,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
 
   // launch index + path flags and the LCG state in the constant words of the queued rays (device_types.h LaunchParams::packedQueue)
   p.packedQueue = (dev->packedQueue && !p.hasCutout && (unsigned int) p.numPaths <= TWK_PACKED_PIXEL_MASK) ? 1 : 0;
+  p.slimSlotBits = slimSlotBits(dev);
   const int maxDepth = dev->state.pathLengths[1];
   const int lanes = chooseLanes(dev, p.numPaths);
   // every block of every lane's persistent trace kernel resident at once: the lanes share the CUs' block slots
@@ -816,6 +832,7 @@ try
   if (const char* e = getenv("TWK_TILE_ENTRIES")) dev->tileEntries = (atoi(e) != 0);
   if (const char* e = getenv("TWK_WIDE_ROOT")) dev->wideRoot = (atoi(e) != 0);
   if (const char* e = getenv("TWK_PACKED_QUEUE")) dev->packedQueue = (atoi(e) != 0);
+  if (const char* e = getenv("TWK_SLIM_STREAMS")) dev->slimStreams = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SHADE_SORT")) dev->shadeSort = std::max(0, std::min(2, atoi(e)));
   if (const char* e = getenv("TWK_TRACE_WAVES_RUNTIME")) dev->traceWavesForced = atoi(e); // A/B: 6 or 7 blocks per CU of the persistent trace kernel
   if (const char* e = getenv("TWK_BUILD_QUALITY")) dev->builder.setQuality(atoi(e)); // A/B: 0 LBVH, 1 binned SAH (default)
@@ -1091,6 +1108,17 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_build_info")
+
+int twk_get_stream_layout(TwkDevice dev, int* layout)
+try
+{
+  if (!dev || !layout) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_stream_layout: NULL argument");
+  if (!dev->built) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_stream_layout: twk_build has not been called");
+  refreshParams(dev); // cutout opacity is a property of the materials as they are now
+  *layout = (slimSlotBits(dev) != 0) ? TWK_STREAMS_SLIM : TWK_STREAMS_FULL;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_stream_layout")
 
 int twk_build(TwkDevice dev)
 try

@@ -8,6 +8,7 @@
 //   path state     in the ray queue (per slot): throughput+pdf 16 B, seed+flags 8 B — streamed with the ray;
 //                  per path: radiance 16 B, volume stack 64 B (touched only by additions / glass transmission)
 //   shadow queue   ray 32 B + 4 B launch index + pending contribution 16 B
+//   (flattened scenes without cutout opacity: no instance and no shadow launch-index stream — LaunchParams::slimSlotBits)
 //   BVH2 node      64 B  (two child boxes + two child references)
 //   triangle       48 B  (three float4: vertex, w of the first = primitive index)
 #pragma once
@@ -229,7 +230,21 @@ struct LaunchParams
   int     packedQueue;
   unsigned int queueStride; // slots between the starts of two queue segments (TWK_QUEUE_STRIDE of the pass's or the lane's path count)
   unsigned int* droppedPushes; // pinned host word (device-mapped): pushes the single-ray traversal could not store (trace_device.h TWK_PUSH); stays 0 on every scene twk_build accepts
+  // Slim streams (0: the layout above, every stream written and read). Non-zero: the number of bits a triangle slot takes in the
+  // hit record's slot word. Scenes whose instances are all flattened and that have no cutout opacity (renderPass decides per pass):
+  //   hit record    the slot word is slot | instance << slimSlotBits (a miss: -1, both halves) — a world-space slot belongs to one
+  //                 instance, and traversal holds it (triangles[3 * slot + 1].w) — and hitInstance is neither written nor read;
+  //   shadow queue  shadowPending.w, the seed only the cutout test draws from, is the launch index; shadowPixel is neither
+  //                 written nor read: the result write of a visible shadow ray needs ONE record before it adds to pathRadiance.
+  // 8 bytes less per path and bounce (TWK_SLIM_STREAMS=0 keeps the full layout). shadePath and the host build (oracle/) never see
+  // it: the kernels around shadePath pack and unpack.
+  int     slimSlotBits;
 };
+
+// Slim streams: the hit record's slot word <-> (triangle slot, instance). A miss is -1 on both sides.
+TWK_HD int packSlotWord(int slotBits, int triangleSlot, int instance) { return triangleSlot | (int) ((unsigned int) instance << slotBits); }
+TWK_HD int slotWordInstance(int slotBits, int word) { return word >> slotBits; } // arithmetic shift: -1 stays -1
+TWK_HD int slotWordSlot(int slotBits, int word) { return (word < 0) ? word : (word & ((1 << slotBits) - 1)); }
 
 // Queue segments (round 5). shadeKernel's time was the number of returning atomics on ONE counter word divided by the rate a word
 // sustains (87.8 per microsecond: profiles/r05_shade_diagnosis.md 7). So a queue is TWK_QUEUE_SEGMENTS regions of the same arrays,

@@ -80,8 +80,10 @@ static_assert(TWK_FLAG_DIFFUSE == (1u << 2) && TWK_FLAG_ALBEDO == (1u << 28) && 
 // packed: the queue was written by shadeKernel in the packed form (device_types.h LaunchParams::packedQueue).
 // slot: the VIRTUAL slot (hit records are indexed by it); the queued ray and its path state sit at physicalSlot(slot)
 // (device_types.h "queue segments").
+// slim (device_types.h LaunchParams::slimSlotBits): there is no hitInstance stream; the hit record's slot word holds both, and
+// is taken apart where the record is first used (unpackSlimHit) — done here, the wave would wait for the record it has just requested.
 template<bool PRIMARY>
-TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const QueueSegments& segments, bool packed, ShadeInput& in)
+TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const QueueSegments& segments, bool packed, bool slim, ShadeInput& in)
 {
   const unsigned int numRays = segments.total;
   in.inRange = slot < numRays;
@@ -94,7 +96,7 @@ TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const
       in.rd = make_float4(ray.direction.x, ray.direction.y, ray.direction.z, ray.active ? RT_DEFAULT_MAX : -1.0f);
       in.pixel = slot;
       in.hit = p.hitRecord[slot];
-      in.instanceIndex = p.hitInstance[slot];
+      if (!slim) in.instanceIndex = p.hitInstance[slot];
       in.throughputPdf = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
       // a scene with cutout opacity: the first traversal stored the seed in queue 0 and its opacity tests drew from it
       in.seedFlags = p.hasCutout ? p.raySeedFlags[0][slot] : make_uint2(ray.seed, 0u);
@@ -107,7 +109,7 @@ TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const
     in.ro = p.rayOrg[q][record];
     in.rd = p.rayDir[q][record];
     in.hit = p.hitRecord[slot];
-    in.instanceIndex = p.hitInstance[slot];
+    if (!slim) in.instanceIndex = p.hitInstance[slot];
     in.throughputPdf = p.rayThroughput[q][record];
     if (packed)
     {
@@ -122,6 +124,18 @@ TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const
       in.seedFlags = p.raySeedFlags[q][record];
     }
   }
+}
+
+// Slim streams: the hit record's slot word -> the instance shadePath is given and the triangle slot it finds in the record.
+TWK_D void unpackSlimHit(int slotBits, ShadeInput& in)
+{
+  const int word = __float_as_int(in.hit.w);
+  int instance = slotWordInstance(slotBits, word), slot = slotWordSlot(slotBits, word);
+  // Pinned: left alone, hipcc keeps the word alive next to the two and derives them again where they are used — one register
+  // more through the whole of shadePath, and the five-wave builds, which sit exactly at their 96, spill 8 bytes.
+  asm volatile("" : "+v"(instance), "+v"(slot));
+  in.instanceIndex = instance;
+  in.hit.w = __int_as_float(slot);
 }
 
 // Block barrier that orders LDS only. __syncthreads() also drains the wave's outstanding global loads and stores
@@ -171,10 +185,11 @@ struct ShadeExchange
 // rotate: the sorted window starts at thread `rotate` and wraps — a multiple of 64 that differs from block to block and from
 // window to window. Without it wave 3 of EVERY block would shade the last classes (Lambert, GGX: the expensive ones) and wave 0 the
 // misses; a block's waves sit on the four SIMDs of its CU in order, so one SIMD of every CU would do most of the chip's shading.
-TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, ShadeExchange& x, unsigned int rotate, ShadeInput& in)
+// slimSlotBits != 0 (slim streams): the hit record still holds the slot word, which names the instance; it is taken apart behind the exchange.
+TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, ShadeExchange& x, unsigned int rotate, int slimSlotBits, ShadeInput& in)
 {
   const bool active = in.inRange && in.rd.w >= 0.0f;
-  const unsigned int key = shadeClass(tables, in.instanceIndex, active);
+  const unsigned int key = shadeClass(tables, slimSlotBits ? slotWordInstance(slimSlotBits, __float_as_int(in.hit.w)) : in.instanceIndex, active);
   const unsigned int rank = atomicAdd(classCount + key, 1u); // the order inside a class is the order the adds arrive in: no result depends on it
   ldsBarrier();
   const uint4 lo = *reinterpret_cast<const uint4*>(classCount), hi = *reinterpret_cast<const uint4*>(classCount + 4);
@@ -184,7 +199,7 @@ TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, Sha
   for (unsigned int c = 0; c + 1 < TWK_SHADE_CLASSES; ++c) place += (c < key) ? counts[c] : 0u;
   place &= TWK_SHADE_BLOCK - 1u;
   x.ro[place] = in.ro; x.rd[place] = in.rd; x.hit[place] = in.hit; x.throughputPdf[place] = in.throughputPdf;
-  x.words[place] = make_uint4(in.seedFlags.x, in.seedFlags.y, in.inRange ? in.pixel : 0xFFFFFFFFu, (unsigned int) in.instanceIndex);
+  x.words[place] = make_uint4(in.seedFlags.x, in.seedFlags.y, in.inRange ? in.pixel : 0xFFFFFFFFu, slimSlotBits ? 0u : (unsigned int) in.instanceIndex);
   ldsBarrier();
   if (threadIdx.x < TWK_SHADE_CLASSES) classCount[threadIdx.x] = 0u; // every thread has read the counts; the next window counts behind two more barriers
   in.ro = x.ro[threadIdx.x]; in.rd = x.rd[threadIdx.x]; in.hit = x.hit[threadIdx.x]; in.throughputPdf = x.throughputPdf[threadIdx.x];
@@ -220,7 +235,9 @@ TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, Sha
 #endif
 // SORT: the block shades its window in class order (above; LDS_TABLES builds only). The measurement builds carry the exchange
 // buffer too and take LaunchParams::shadeSort at run time.
-template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT>
+// SLIM: the pass runs the slim streams (device_types.h LaunchParams::slimSlotBits) — a build, not a launch parameter: with both
+// layouts in one kernel the five-wave builds, which sit exactly at their 96 registers, spilled 8 to 12 bytes.
+template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>
 __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (PRIMARY ? TWK_SHADE_WAVES_PRIMARY : TWK_SHADE_WAVES)) shadeKernel(LaunchParams p, int depth)
 {
   // Double-buffered by block iteration: iteration i + 2 rewrites what i used only after every thread has passed a barrier
@@ -234,8 +251,9 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   if (blockIdx.x * blockDim.x >= numRays) return;
   const int q = depth & 1, qn = q ^ 1;
   const bool packedIn = p.packedQueue != 0 && depth > 0, packedOut = p.packedQueue != 0; // queue 0 is computed (PRIMARY) or written by generateKernel
+  constexpr bool slim = SLIM; // no hitInstance stream in, no shadowPixel stream out
   ShadeInput in = {}; // a thread beyond the queue hands its (empty) record to the exchange all the same
-  loadShadeInput<PRIMARY>(p, q, blockIdx.x * blockDim.x + threadIdx.x, segments, packedIn, in);
+  loadShadeInput<PRIMARY>(p, q, blockIdx.x * blockDim.x + threadIdx.x, segments, packedIn, slim, in);
 
   __shared__ unsigned int waveCount[2][2][TWK_SHADE_BLOCK / 64];
   __shared__ unsigned int blockBase[2][2];
@@ -293,7 +311,8 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
     unsigned int* const shadowCount = &p.counters[depth * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_SHADOW + segment * TWK_COUNTER_SEGMENT_STRIDE];
     const unsigned int clockBegin = MEASURE ? (unsigned int) __builtin_readcyclecounter() : 0u;
     const unsigned int iterationBegin = clockBegin;
-    if (EXCHANGE && sorted) sortExchange(tables, classCount, *reinterpret_cast<ShadeExchange*>(exchangeStorage), ((blockIdx.x + base / (gridDim.x * blockDim.x)) & 3u) << 6, in);
+    if (EXCHANGE && sorted) sortExchange(tables, classCount, *reinterpret_cast<ShadeExchange*>(exchangeStorage), ((blockIdx.x + base / (gridDim.x * blockDim.x)) & 3u) << 6, slim ? p.slimSlotBits : 0, in);
+    if (slim && in.inRange) unpackSlimHit(p.slimSlotBits, in);
     const unsigned int slotLanes = MEASURE ? (unsigned int) __popcll(__ballot(in.inRange)) : 0u; // lanes of this wave with a queue slot in THIS window (`in` holds the next window's by the time the tallies are written)
     const unsigned int pixel = in.pixel;
     if (in.inRange && in.rd.w >= 0.0f) // else: beyond the queue, or an inactive launch index (tile column beyond the image)
@@ -334,7 +353,7 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
     const unsigned int afterBarrier1 = MEASURE ? (unsigned int) __builtin_readcyclecounter() : 0u;
     // (hipcc still waits for part of these right here — it copies one component of the hit record to another register
     // behind the loads; pinning the record at its first use makes that worse, every component then gets such a copy)
-    loadShadeInput<PRIMARY>(p, q, base + gridDim.x * blockDim.x + threadIdx.x, segments, packedIn, in);
+    loadShadeInput<PRIMARY>(p, q, base + gridDim.x * blockDim.x + threadIdx.x, segments, packedIn, slim, in);
 #if TWK_PROBE_EXTRA_ATOMICS // timing probe (profiles/r05_shade_diagnosis.md 7): that many more returning atomics per counter word and block iteration, adding a zero the compiler cannot see
     if (threadIdx.x >= 2 && threadIdx.x < 2 + 2 * TWK_PROBE_EXTRA_ATOMICS)
       blockBase[buffer ^ 1u][threadIdx.x & 1u] += atomicAdd((threadIdx.x & 1u) ? nextCount : shadowCount, (unsigned int) p.numPaths >> 31) & 0u;
@@ -371,8 +390,8 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
       const unsigned int s = shadowOffset + (unsigned int) __popcll(shadowMask & laneBelow);
       p.shadowOrg[s]     = make_float4(out.nextPos.x, out.nextPos.y, out.nextPos.z, p.sceneEpsilon);
       p.shadowDir[s]     = make_float4(out.shadowDir.x, out.shadowDir.y, out.shadowDir.z, out.shadowTmax);
-      p.shadowPixel[s]   = pixel;
-      p.shadowPending[s] = make_float4(out.pending.x, out.pending.y, out.pending.z, __uint_as_float(out.shadowSeed));
+      if (!slim) p.shadowPixel[s] = pixel;
+      p.shadowPending[s] = make_float4(out.pending.x, out.pending.y, out.pending.z, __uint_as_float(slim ? pixel : out.shadowSeed)); // slim: no cutout test draws from the seed; the launch index rides there
     }
     if (out.alive)
     {
@@ -611,20 +630,20 @@ void launchGenerate(const LaunchParams& p, hipStream_t stream)
 {
   hipLaunchKernelGGL(generateKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p);
 }
-template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT>
+template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>
 static void launchShadeBuild(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
 {
-  hipLaunchKernelGGL((shadeKernel<ENV, TEX, PRIMARY, LDS_TABLES, MEASURE, SORT>), dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
+  hipLaunchKernelGGL((shadeKernel<ENV, TEX, PRIMARY, LDS_TABLES, MEASURE, SORT, SLIM>), dim3(gridBlocks), dim3(TWK_SHADE_BLOCK), 0, stream, p, depth);
 }
-// The launchers of every build launchShade chooses, indexed by the build's six flags (bit 0 ENV ... bit 5 SORT): SORT is a build
-// of the plain kernel with LDS tables; the measurement builds take the sort decision at run time.
+// The launchers of every build launchShade chooses, indexed by the build's seven flags (bit 0 ENV ... bit 5 SORT, bit 6 SLIM): SORT
+// is a build of the plain kernel with LDS tables; the measurement builds take the sort decision at run time.
 using ShadeLauncher = void (*)(const LaunchParams&, int, int, hipStream_t);
 template<int I>
 constexpr ShadeLauncher shadeLauncher()
 {
-  constexpr bool ENV = I & 1, TEX = I & 2, PRIMARY = I & 4, LDS_TABLES = I & 8, MEASURE = I & 16, SORT = I & 32;
+  constexpr bool ENV = I & 1, TEX = I & 2, PRIMARY = I & 4, LDS_TABLES = I & 8, MEASURE = I & 16, SORT = I & 32, SLIM = I & 64;
   if constexpr (SORT && (!LDS_TABLES || MEASURE)) return nullptr;
-  else return launchShadeBuild<ENV, TEX, PRIMARY, LDS_TABLES, MEASURE, SORT>;
+  else return launchShadeBuild<ENV, TEX, PRIMARY, LDS_TABLES, MEASURE, SORT, SLIM>;
 }
 template<int... I>
 constexpr std::array<ShadeLauncher, sizeof...(I)> shadeLaunchers(std::integer_sequence<int, I...>) { return {shadeLauncher<I>()...}; }
@@ -639,8 +658,8 @@ void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks,
   const bool fitsExchange = TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_SORT_TABLE_BYTES; // the builds with the exchange buffer hold smaller tables
   const bool sort = !measure && fitsExchange && shadeSorted(p.shadeSort, primary);
   const bool lds = (measure || sort) ? fitsExchange : (TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_TABLE_BYTES);
-  static constexpr std::array<ShadeLauncher, 64> launchers = shadeLaunchers(std::make_integer_sequence<int, 64>());
-  const ShadeLauncher launch = launchers[(env ? 1 : 0) | (tex ? 2 : 0) | (primary ? 4 : 0) | (lds ? 8 : 0) | (measure ? 16 : 0) | (sort ? 32 : 0)];
+  static constexpr std::array<ShadeLauncher, 128> launchers = shadeLaunchers(std::make_integer_sequence<int, 128>());
+  const ShadeLauncher launch = launchers[(env ? 1 : 0) | (tex ? 2 : 0) | (primary ? 4 : 0) | (lds ? 8 : 0) | (measure ? 16 : 0) | (sort ? 32 : 0) | (p.slimSlotBits != 0 ? 64 : 0)];
   assert(launch != nullptr);
   launch(p, depth, gridBlocks, stream);
 }

@@ -52,6 +52,7 @@ traceOverflowKernel(LaunchParams p, int depth)
   const unsigned int numClosest = closestSegments.total;
   const int q = depth & 1;
   const bool packed = !CUTOUT && !PRIMARY && p.packedQueue != 0 && depth > 0; // as in traceKernel
+  const bool slim = !CUTOUT && p.slimSlotBits != 0; // as in traceKernel (set for flattened scenes only)
   unsigned int nodeCount = 0, triCount = 0, instCount = 0;
   for (unsigned int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
   {
@@ -83,11 +84,11 @@ traceOverflowKernel(LaunchParams p, int depth)
       tmin = res.t;
     }
     if (COUNT && p.pathTime != nullptr)
-      atomicAdd(&p.pathTime[isShadow ? p.shadowPixel[record] : (PRIMARY ? slot : (packed ? packedPixel : p.rayPixel[q][record]))], float((unsigned int) __builtin_readcyclecounter() - rayClock));
+      atomicAdd(&p.pathTime[isShadow ? (slim ? __float_as_uint(p.shadowPending[record].w) : p.shadowPixel[record]) : (PRIMARY ? slot : (packed ? packedPixel : p.rayPixel[q][record]))], float((unsigned int) __builtin_readcyclecounter() - rayClock));
     if (!isShadow)
     {
-      p.hitRecord[slot]   = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.triangleSlot));
-      p.hitInstance[slot] = res.instance;
+      p.hitRecord[slot] = make_float4(res.t, res.beta, res.gamma, __int_as_float(slim ? packSlotWord(p.slimSlotBits, res.triangleSlot, res.instance) : res.triangleSlot));
+      if (!slim) p.hitInstance[slot] = res.instance;
       if (p.firstHit != nullptr && depth == 0)
       {
         const unsigned int pixel = PRIMARY ? slot : p.rayPixel[q][record];
@@ -98,8 +99,8 @@ traceOverflowKernel(LaunchParams p, int depth)
     else if (res.instance < 0)
     {
       const unsigned int sIdx = record;
-      const unsigned int pixel = p.shadowPixel[sIdx];
       const float4 c = p.shadowPending[sIdx];
+      const unsigned int pixel = slim ? __float_as_uint(c.w) : p.shadowPixel[sIdx];
       float4 r = p.pathRadiance[pixel];
       r.x += c.x; r.y += c.y; r.z += c.z;
       p.pathRadiance[pixel] = r;
@@ -115,23 +116,24 @@ traceOverflowKernel(LaunchParams p, int depth)
   }
 }
 
-template<bool COUNT, bool CUTOUT, bool TWO_LEVEL, bool W7, bool PRIMARY>
+template<bool COUNT, bool CUTOUT, bool TWO_LEVEL, bool W7, bool PRIMARY, bool SLIM>
 static void launchTraceBuild(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
 {
   const int overflowBlocks = gridBlocks < 64 ? gridBlocks : 64; // lanes index the same per-lane spill segments
-  hipLaunchKernelGGL((traceKernel<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY>), dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, depth);
+  hipLaunchKernelGGL((traceKernel<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY, SLIM>), dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, depth);
   hipLaunchKernelGGL((traceOverflowKernel<COUNT, CUTOUT, PRIMARY>), dim3(overflowBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, depth);
 }
 
 // The launchers of every build device_api.hip traceBuild can return, indexed by the build's five flags (bit 0 COUNT ... bit 4
-// PRIMARY); the W7 form exists for flattened, non-PRIMARY launches only (device_types.h traceBlocksPerCU).
+// PRIMARY) and bit 5 SLIM, which the pass decides (LaunchParams::slimSlotBits); the W7 form exists for flattened, non-PRIMARY
+// launches only (device_types.h traceBlocksPerCU), the SLIM form for flattened scenes without cutout opacity.
 using TraceLauncher = void (*)(const LaunchParams&, int, int, hipStream_t);
 template<int I>
 constexpr TraceLauncher traceLauncher()
 {
-  constexpr bool COUNT = I & 1, CUTOUT = I & 2, TWO_LEVEL = I & 4, W7 = I & 8, PRIMARY = I & 16;
-  if constexpr (W7 && (TWO_LEVEL || PRIMARY)) return nullptr;
-  else return launchTraceBuild<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY>;
+  constexpr bool COUNT = I & 1, CUTOUT = I & 2, TWO_LEVEL = I & 4, W7 = I & 8, PRIMARY = I & 16, SLIM = I & 32;
+  if constexpr ((W7 && (TWO_LEVEL || PRIMARY)) || (SLIM && (CUTOUT || TWO_LEVEL))) return nullptr;
+  else return launchTraceBuild<COUNT, CUTOUT, TWO_LEVEL, W7, PRIMARY, SLIM>;
 }
 template<int... I>
 constexpr std::array<TraceLauncher, sizeof...(I)> traceLaunchers(std::integer_sequence<int, I...>) { return {traceLauncher<I>()...}; }
@@ -139,8 +141,8 @@ constexpr std::array<TraceLauncher, sizeof...(I)> traceLaunchers(std::integer_se
 // gridBlocks must be numCUs x build.blocksPerCU (or a lane's share of it): every block of the persistent kernel resident at once.
 void launchTrace(const LaunchParams& p, int depth, bool count, const TraceBuild& build, int gridBlocks, hipStream_t stream)
 {
-  static constexpr std::array<TraceLauncher, 32> launchers = traceLaunchers(std::make_integer_sequence<int, 32>());
-  const TraceLauncher launch = launchers[(count ? 1 : 0) | (build.cutout ? 2 : 0) | (build.twoLevel ? 4 : 0) | (build.w7 ? 8 : 0) | (build.primary ? 16 : 0)];
+  static constexpr std::array<TraceLauncher, 64> launchers = traceLaunchers(std::make_integer_sequence<int, 64>());
+  const TraceLauncher launch = launchers[(count ? 1 : 0) | (build.cutout ? 2 : 0) | (build.twoLevel ? 4 : 0) | (build.w7 ? 8 : 0) | (build.primary ? 16 : 0) | (p.slimSlotBits != 0 ? 32 : 0)];
   assert(launch != nullptr);
   launch(p, depth, gridBlocks, stream);
 }

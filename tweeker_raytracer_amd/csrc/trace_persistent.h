@@ -97,10 +97,14 @@ TWK_D bool cutoutIgnoresCandidate(const LaunchParams& p, const TraceResult& res,
 // PRIMARY: depth 0 of a pass without generateKernel — the lane computes the primary ray of its slot instead of fetching it
 // (shade_kernels.hip "primary rays"). With CUTOUT the seed is stored in queue 0 for the opacity draws.
 // (The builds over compressed 8-ary nodes, round 4, lost on every scene and live in tools/experiments/r04_wide8_nodes.patch.)
-template<bool COUNT, bool CUTOUT, bool TWO_LEVEL, bool W7, bool PRIMARY>
+// SLIM: the pass runs the slim streams (device_types.h LaunchParams::slimSlotBits: no hitInstance, no shadowPixel stream) — a
+// build of its own, not a launch parameter: with both forms of the result write in one kernel every build took one or two
+// more registers, and the measurement build of the seven-block form four more bytes of scratch.
+template<bool COUNT, bool CUTOUT, bool TWO_LEVEL, bool W7, bool PRIMARY, bool SLIM>
 __global__ void __launch_bounds__(TWK_TRACE_BLOCK, traceBlocksPerCU(CUTOUT, TWO_LEVEL, W7, PRIMARY)) // blocks per CU = waves per SIMD: device_types.h
 traceKernel(LaunchParams p, int depth)
 {
+  static_assert(!SLIM || (!CUTOUT && !TWO_LEVEL), "slim streams: flattened scenes without cutout opacity");
   constexpr int STACK_LDS = W7 ? TWK_TRACE_STACK_LDS7 : TWK_TRACE_STACK_LDS;
   constexpr int TOP_NODES = W7 ? TWK_TOP_NODES7 : TWK_TOP_NODES;
   constexpr int STACK_ROWS = STACK_LDS + 1; // + 1 dummy row, see the node step
@@ -124,6 +128,7 @@ traceKernel(LaunchParams p, int depth)
 
   const int q = depth & 1;
   const bool packed = !CUTOUT && !PRIMARY && p.packedQueue != 0 && depth > 0; // device_types.h LaunchParams::packedQueue: the closest-hit rays' .w words are not tmin / tmax
+  constexpr bool slim = SLIM;
   const unsigned int lane = threadIdx.x & 63u;
   const unsigned long long laneBelow = (1ull << lane) - 1ull;
 
@@ -248,8 +253,12 @@ traceKernel(LaunchParams p, int depth)
       else if (state & ST_OVERFLOWED) { state &= ~ST_OVERFLOWED; }
       else if (!isShadow)
       {
-        p.hitRecord[slot]   = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.triangleSlot));
-        p.hitInstance[slot] = res.instance;
+        if (slim) p.hitRecord[slot] = make_float4(res.t, res.beta, res.gamma, __int_as_float(packSlotWord(p.slimSlotBits, res.triangleSlot, res.instance)));
+        else
+        {
+          p.hitRecord[slot]   = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.triangleSlot));
+          p.hitInstance[slot] = res.instance;
+        }
         if (COUNT) ++closestCount;
         if (COUNT && p.pathTime != nullptr) atomicAdd(&p.pathTime[PRIMARY ? slot : (packed ? (__float_as_uint(p.rayOrg[q][TWK_RECORD(slot)].w) & TWK_PACKED_PIXEL_MASK) : p.rayPixel[q][TWK_RECORD(slot)])], float(rayCycles)); // time view: the lane's cycles from taking the ray to its completion
         if (p.firstHit != nullptr && depth == 0)
@@ -262,13 +271,13 @@ traceKernel(LaunchParams p, int depth)
       else
       {
         if (COUNT) ++shadowCount;
-        if (COUNT && p.pathTime != nullptr) atomicAdd(&p.pathTime[p.shadowPixel[TWK_RECORD(slot)]], float(rayCycles));
+        if (COUNT && p.pathTime != nullptr) atomicAdd(&p.pathTime[slim ? __float_as_uint(p.shadowPending[TWK_RECORD(slot)].w) : p.shadowPixel[TWK_RECORD(slot)]], float(rayCycles));
         if (res.instance < 0)
         {
           // visible: add the pending next-event contribution (closesthit.cu:288-299, raygeneration.cu:100)
           const unsigned int s = TWK_RECORD(slot);
-          const unsigned int pixel = p.shadowPixel[s];
           const float4 c = p.shadowPending[s];
+          const unsigned int pixel = slim ? __float_as_uint(c.w) : p.shadowPixel[s]; // slim: the launch index rides in the pending record
           float4 r = p.pathRadiance[pixel];
           r.x += c.x; r.y += c.y; r.z += c.z;
           p.pathRadiance[pixel] = r;

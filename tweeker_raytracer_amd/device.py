@@ -160,6 +160,12 @@ class Device:
         L.check(L.lib.twk_get_build_info(self._h, C.byref(b)))
         return {name: getattr(b, name) for name, _ in L.BuildInfo._fields_}
 
+    def streamLayout(self):
+        """'slim' or 'full': the layout of the path streams a pass over the built scene uses (twk_get_stream_layout)."""
+        layout = C.c_int(0)
+        L.check(L.lib.twk_get_stream_layout(self._h, C.byref(layout)))
+        return "slim" if layout.value == 1 else "full"
+
     def setFlattenPolicy(self, maxTriangles, maxReferences):
         """Build option of the next build(): instances of geometries with <= maxTriangles triangles, or referenced by
         <= maxReferences instances, are intersected in world space in one single-level BVH; (0, 0) = pure two-level."""

@@ -391,6 +391,43 @@ int twk_tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaDevice, 
  * RGBA16F pixels (e.g. a frame of twk_compositor_half), widened, then the same operator. */
 int twk_tonemap_half(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaHalfDevice, size_t numPixels, unsigned char* rgb8Host);
 
+/* ---- denoiser ------------------------------------------------------------------------------ */
+/* Stands at the seam of Optix7Gui's optixDenoiserInvoke (apps/Optix7Gui/src/Application.cpp:942-1001): beauty + albedo +
+ * normal in, denoised picture out, then the tonemapper. The OptiX AI denoiser is a closed network; this is a CLASSICAL filter,
+ * the edge-avoiding a-trous wavelet of Dammertz et al. 2010, guided by the same two AOVs and defined exactly (the float
+ * operations and their order: csrc/denoise_device.h). Per level i = 0 .. iterations-1, step s = 1 << i, 5x5 B3-spline stencil
+ * h = (1/16, 1/4, 3/8, 1/4, 1/16), k = h[dy] h[dx], taps outside the picture skipped:
+ *   w = k exp(-(|c_p-c_q|^2/sigmaColor^2 + |n_p-n_q|^2/sigmaNormal^2 + |a_p-a_q|^2/sigmaAlbedo^2)),  c_p' = sum w c_q / sum w,
+ * terms of guides not in use omitted, sigmaColor the same on every level. A tap with a non-finite colour or guide has weight 0;
+ * a centre with a non-finite colour or guide (or whose demodulated colour overflows) passes through unchanged, as the input's
+ * bits; alpha is always the input's.
+ * ≙ OptixDenoiserOptions::inputKind + OptixDenoiserParams (Optix7Gui Application.cpp:2451-2505) */
+enum { TWK_DENOISER_RGB = 0, TWK_DENOISER_RGB_ALBEDO = 1, TWK_DENOISER_RGB_ALBEDO_NORMAL = 2 };
+typedef struct TwkDenoiser
+{
+  int   inputKind;        /* which guides weigh the taps (≙ USE_DENOISER_ALBEDO / USE_DENOISER_NORMAL, app_config.h) */
+  int   iterations;       /* a-trous levels, step 1 << level; 0..8 */
+  float sigmaColor, sigmaNormal, sigmaAlbedo;
+  int   demodulateAlbedo; /* filter rgb / max(albedo, 0.01), multiply back afterwards; needs an albedo guide */
+  float blendFactor;      /* ≙ OptixDenoiserParams::blendFactor: 0 = denoised only, 1 = input */
+} TwkDenoiser;
+/* RGB_ALBEDO_NORMAL, 3 iterations, sigmaColor 8, sigmaNormal 0.3, sigmaAlbedo 0.1, demodulateAlbedo 1, blendFactor 0 */
+int twk_denoiser_defaults(TwkDenoiser* dn);
+/* Asynchronous on the handle's stream; never writes its inputs. beauty NULL (then albedo and normal must be NULL too, and
+ * width / height are ignored): the handle's own accumulation and AOV buffers, launchWidth x height, are filtered — guided
+ * kinds need twk_enable_aov(1), and a packed tile buffer (distribution 1 with more than one device) is refused. Otherwise
+ * beauty, and the guides the kind uses, are device buffers of width x height pixels in the handle's current output format
+ * (e.g. a composited multi-GPU frame). denoised NULL: the result goes to an internal buffer in the output format (≙
+ * m_d_denoisedBuffer; allocated on first use, again when the resolution or the format changes), which the three calls below
+ * hand out; otherwise to the caller's buffer, which must not overlap an input. RGBA16F input is widened exactly, all
+ * arithmetic and the buffers between levels are f32, the result is narrowed once, round to nearest even. iterations 0 or
+ * blendFactor 1 copy the input's bits. */
+int twk_denoise(TwkDevice dev, const TwkDenoiser* dn, const void* beauty, const void* albedo, const void* normal,
+                int width, int height, void* denoised);
+int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats);        /* RGBA32F, widened exactly, like twk_read_output */
+int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes);             /* in the output format */
+int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes); /* feeds twk_tonemap / twk_tonemap_half */
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);
@@ -479,6 +516,11 @@ int twk_app_info(TwkApp app, TwkAppInfo* info);
 /* "outputFormat 0|1" of the system description (grammar extension ≙ Optix7Gui USE_FP32_OUTPUT: 1 = TWK_OUTPUT_HALF4),
  * default 0; applied by twk_app_init_device. */
 int twk_app_get_output_format(TwkApp app, int* format);
+/* "denoiser 0|1|2|3" (0 = off, default; else inputKind + 1), "denoiserIterations n", "denoiserSigmas color normal albedo" of
+ * the system description (grammar extensions ≙ Optix7Gui's denoiser switches, app_config.h): *enabled and the parameters
+ * twk_denoise is to be called with (twk_denoiser_defaults where a key is absent; demodulateAlbedo 0 for TWK_DENOISER_RGB).
+ * twk_app_init_device enables the AOVs when the key asks for a guided kind. */
+int twk_app_get_denoiser(TwkApp app, int* enabled, TwkDenoiser* dn);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

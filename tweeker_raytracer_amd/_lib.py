@@ -22,6 +22,8 @@ TWK_SUCCESS, TWK_ERROR_INVALID_VALUE, TWK_ERROR_NO_DEVICE, TWK_ERROR_HIP = 0, 1,
 TWK_ERROR_INVALID_STATE, TWK_ERROR_OUT_OF_MEMORY, TWK_ERROR_IO, TWK_ERROR_PARSE = 4, 5, 6, 7
 TWK_OUTPUT_FLOAT4, TWK_OUTPUT_HALF4 = 0, 1  # twk_set_output_format: RGBA32F (default), RGBA16F (≙ Optix7Gui USE_FP32_OUTPUT 0)
 
+TWK_DENOISER_RGB, TWK_DENOISER_RGB_ALBEDO, TWK_DENOISER_RGB_ALBEDO_NORMAL = 0, 1, 2  # TwkDenoiser.inputKind: the guides that weigh the taps
+
 f3 = C.c_float * 3
 f2 = C.c_float * 2
 i2 = C.c_int * 2
@@ -62,6 +64,19 @@ class Tonemapper(C.Structure):
     def __init__(self, gamma=1.0, whitePoint=1.0, colorBalance=(1.0, 1.0, 1.0), burnHighlights=1.0, crushBlacks=0.0,
                  saturation=1.0, brightness=1.0):
         super().__init__(gamma, whitePoint, (C.c_float * 3)(*colorBalance), burnHighlights, crushBlacks, saturation, brightness)
+
+
+class Denoiser(C.Structure):
+    """≙ TwkDenoiser: parameters of twk_denoise, the edge-avoiding a-trous wavelet filter at the optixDenoiserInvoke seam
+    (inputKind + blendFactor ≙ OptixDenoiserOptions / OptixDenoiserParams). Without arguments: twk_denoiser_defaults."""
+    _fields_ = [("inputKind", C.c_int), ("iterations", C.c_int), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float),
+                ("sigmaAlbedo", C.c_float), ("demodulateAlbedo", C.c_int), ("blendFactor", C.c_float)]
+
+    def __init__(self, inputKind=TWK_DENOISER_RGB_ALBEDO_NORMAL, iterations=3, sigmaColor=8.0, sigmaNormal=0.3, sigmaAlbedo=0.1,
+                 demodulateAlbedo=None, blendFactor=0.0):
+        if demodulateAlbedo is None:
+            demodulateAlbedo = inputKind != TWK_DENOISER_RGB
+        super().__init__(int(inputKind), int(iterations), sigmaColor, sigmaNormal, sigmaAlbedo, int(bool(demodulateAlbedo)), blendFactor)
 
 
 class LaunchStats(C.Structure):
@@ -107,6 +122,7 @@ SYMBOLS = [
     "twk_set_shader_variant", "twk_enable_aov", "twk_read_aov", "twk_set_time_view", "twk_set_next_event_estimation", "twk_set_debug_exceptions", "twk_get_output_device_pointer", "twk_set_output_device_pointer", "twk_set_shared_frame", "twk_compositor", "twk_tonemap", "twk_profile_enable",
     "twk_set_output_format", "twk_get_output_format", "twk_read_output_raw", "twk_read_aov_raw", "twk_compositor_half", "twk_tonemap_half",
     "twk_app_get_output_format",
+    "twk_denoiser_defaults", "twk_denoise", "twk_read_denoised", "twk_read_denoised_raw", "twk_get_denoised_device_pointer", "twk_app_get_denoiser",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

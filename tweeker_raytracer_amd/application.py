@@ -100,6 +100,13 @@ class Application:
         return f.value
 
     @property
+    def denoiser(self):
+        """(enabled, Denoiser) from "denoiser", "denoiserIterations", "denoiserSigmas" of the system description."""
+        on, dn = C.c_int(0), L.Denoiser()
+        L.check(L.lib.twk_app_get_denoiser(self._h, C.byref(on), C.byref(dn)))
+        return bool(on.value), dn
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

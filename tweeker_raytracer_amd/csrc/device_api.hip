@@ -4,6 +4,7 @@
 // of a kernel. Without a HIP device every entry point that needs one fails.
 #include "device_types.h"
 #include "bvh_build.h"
+#include "denoise_device.h"
 #include "error_state.h"
 
 #include <algorithm>
@@ -38,6 +39,10 @@ void launchStreamCopy(const float4* src, float4* dst, size_t n, hipStream_t stre
 void launchGatherProbeFill(float4* table, size_t count, unsigned int lines, hipStream_t stream);
 void launchGatherProbe(const float4* table, unsigned int lines, int steps, float* out, int gridBlocks, hipStream_t stream);
 void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
+void launchDenoisePrepare(const void* beauty, const void* albedo, const void* normal, bool half, float4* colour, float4* guideNormal, float4* guideAlbedo,
+                          const DenoiseConstants& k, hipStream_t stream);
+void launchDenoiseLevel(int kind, bool lds, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
+void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
 }
 
 using namespace twk;
@@ -151,6 +156,11 @@ struct TwkDevice_t
   bool timeView = false; float* d_pathTime = nullptr; int timePaths = 0; // twk_set_time_view
   float4* d_pathAlbedo = nullptr; float4* d_pathNormal = nullptr; int aovPaths = 0;
   float4* d_aovAlbedo = nullptr; float4* d_aovNormal = nullptr; int aovPixels = 0;
+  // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) in the output format it was
+  // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
+  void* d_denoised = nullptr; int denoisedWidth = 0, denoisedHeight = 0, denoisedFormat = TWK_OUTPUT_FLOAT4; bool denoisedValid = false;
+  float4* d_denoiseStreams = nullptr; size_t denoiseStreamPixels = 0;
+  int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;
   bool profileEnabled = false;
@@ -834,6 +844,7 @@ try
   if (const char* e = getenv("TWK_PACKED_QUEUE")) dev->packedQueue = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SLIM_STREAMS")) dev->slimStreams = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SHADE_SORT")) dev->shadeSort = std::max(0, std::min(2, atoi(e)));
+  if (const char* e = getenv("TWK_DENOISE_LDS_MAX_STEP")) dev->denoiseLdsMaxStep = std::max(0, std::min(128, atoi(e))); // A/B; 128 = the largest step (iterations <= 8)
   if (const char* e = getenv("TWK_TRACE_WAVES_RUNTIME")) dev->traceWavesForced = atoi(e); // A/B: 6 or 7 blocks per CU of the persistent trace kernel
   if (const char* e = getenv("TWK_BUILD_QUALITY")) dev->builder.setQuality(atoi(e)); // A/B: 0 LBVH, 1 binned SAH (default)
   memset(&dev->buildInfo, 0, sizeof(dev->buildInfo));
@@ -862,6 +873,7 @@ try
   if (dev->h_dropped) { (void) hipHostFree(dev->h_dropped); dev->h_dropped = nullptr; dev->d_dropped = nullptr; }
   freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
   freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal);
+  freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams);
   dev->builder.release();
   for (int k = 1; k < TWK_MAX_LANES; ++k)
   {
@@ -1445,6 +1457,7 @@ try
   // the internal output and AOV buffers are allocated again at the new pixel size, zeroed, by the next ensureStreams
   freeDevice(dev->d_outputInternal);
   freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
+  freeDevice(dev->d_denoised); dev->denoisedValid = false; // a denoised picture is in the format it was filtered in
   dev->outputFormat = format;
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS;
 }
@@ -1640,6 +1653,159 @@ try
   return tonemap(dev, tm, rgbaHalfDevice, true, numPixels, rgb8Host);
 }
 TWK_CATCH("twk_tonemap_half")
+
+// ---- denoiser ---------------------------------------------------------------------------------
+int twk_denoiser_defaults(TwkDenoiser* dn)
+try
+{
+  if (!dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoiser_defaults: NULL argument");
+  dn->inputKind = TWK_DENOISER_RGB_ALBEDO_NORMAL;
+  dn->iterations = 3;
+  dn->sigmaColor = 8.0f; dn->sigmaNormal = 0.3f; dn->sigmaAlbedo = 0.1f;
+  dn->demodulateAlbedo = 1;
+  dn->blendFactor = 0.0f;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoiser_defaults")
+
+static bool overlaps(const void* a, const void* b, size_t bytes)
+{
+  if (!a || !b) return false;
+  const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+  return x < y + bytes && y < x + bytes;
+}
+
+int twk_denoise(TwkDevice dev, const TwkDenoiser* dn, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL device handle");
+  if (!dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL parameters");
+  const int kind = dn->inputKind;
+  if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: unknown inputKind");
+  if (dn->iterations < 0 || dn->iterations > 8) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: iterations must be in [0, 8]");
+  if (!(dn->sigmaColor > 0.0f) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: the sigma of every guide in use must be positive");
+  {
+    // 1 / sigma^2 is what the kernels multiply by: a sigma whose square underflows would make it inf, and 0 x inf the centre tap's NaN
+    const float sigmas[3] = {dn->sigmaColor, (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? dn->sigmaNormal : 1.0f, (kind >= TWK_DENOISER_RGB_ALBEDO) ? dn->sigmaAlbedo : 1.0f};
+    for (const float sigma : sigmas)
+      if (!std::isfinite(1.0f / (sigma * sigma))) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: a sigma is too small: 1 / sigma^2 is not a finite float");
+  }
+  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: blendFactor must be in [0, 1]");
+  if (dn->demodulateAlbedo && kind == TWK_DENOISER_RGB) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: demodulateAlbedo needs an albedo guide (inputKind TWK_DENOISER_RGB has none)");
+  int rc = activate(dev, "twk_denoise"); if (rc) return rc;
+
+  const bool own = (beauty == nullptr);
+  if (own)
+  {
+    if (albedo || normal) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
+    if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: twk_set_state first");
+    if (dev->state.distribution && 1 < dev->count) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
+    beauty = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+    if (!beauty) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: nothing has been rendered");
+    width = dev->launchWidth; height = dev->state.resolution[1];
+    if (kind != TWK_DENOISER_RGB)
+    {
+      if (!dev->aovEnabled || !dev->d_aovAlbedo || !dev->d_aovNormal || (size_t) dev->aovPixels < (size_t) width * height)
+        return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: a guided inputKind on the handle's own buffers needs a render with twk_enable_aov(1)");
+      albedo = dev->d_aovAlbedo;
+      if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = dev->d_aovNormal;
+    }
+  }
+  else
+  {
+    if (width < 1 || height < 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: width and height must be >= 1");
+    if ((kind >= TWK_DENOISER_RGB_ALBEDO && !albedo) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !normal)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL guide buffer for a guide the inputKind uses");
+    if (kind < TWK_DENOISER_RGB_ALBEDO) albedo = nullptr;        // guides the kind does not use are not read
+    if (kind < TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = nullptr;
+  }
+  const size_t numPixels = (size_t) width * height, bytes = numPixels * pixelBytes(dev);
+  if (denoised && (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes)))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: the denoised buffer overlaps an input");
+
+  void* target = denoised;
+  if (!target)
+  {
+    if (!dev->d_denoised || dev->denoisedWidth != width || dev->denoisedHeight != height || dev->denoisedFormat != dev->outputFormat)
+    {
+      HIP_TRY(hipStreamSynchronize(dev->stream));
+      freeDevice(dev->d_denoised); dev->denoisedValid = false;
+      HIP_TRY(hipMalloc(&dev->d_denoised, bytes));
+      dev->denoisedWidth = width; dev->denoisedHeight = height; dev->denoisedFormat = dev->outputFormat;
+    }
+    target = dev->d_denoised;
+  }
+  if (dn->iterations == 0 || dn->blendFactor == 1.0f)
+  {
+    HIP_TRY(hipMemcpyAsync(target, beauty, bytes, hipMemcpyDeviceToDevice, dev->stream)); // the input's bits
+  }
+  else
+  {
+    if (dev->denoiseStreamPixels < numPixels)
+    {
+      HIP_TRY(hipStreamSynchronize(dev->stream));
+      freeDevice(dev->d_denoiseStreams); dev->denoiseStreamPixels = 0;
+      HIP_TRY(hipMalloc(&dev->d_denoiseStreams, numPixels * 4 * sizeof(float4)));
+      dev->denoiseStreamPixels = numPixels;
+    }
+    float4* colour[2] = {dev->d_denoiseStreams, dev->d_denoiseStreams + numPixels};
+    float4* guideNormal = dev->d_denoiseStreams + 2 * numPixels;
+    float4* guideAlbedo = dev->d_denoiseStreams + 3 * numPixels;
+    DenoiseConstants k;
+    k.width = width; k.height = height;
+    k.invColor  = 1.0f / (dn->sigmaColor * dn->sigmaColor);
+    k.invNormal = (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? 1.0f / (dn->sigmaNormal * dn->sigmaNormal) : 0.0f;
+    k.invAlbedo = (kind >= TWK_DENOISER_RGB_ALBEDO) ? 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo) : 0.0f;
+    k.blendFactor = dn->blendFactor;
+    k.demodulate = dn->demodulateAlbedo ? 1 : 0;
+    launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[0], guideNormal, guideAlbedo, k, dev->stream);
+    for (int level = 0; level < dn->iterations; ++level)
+      launchDenoiseLevel(kind, (1 << level) <= dev->denoiseLdsMaxStep, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream);
+    launchDenoiseFinish(beauty, halfOutput(dev), colour[dn->iterations & 1], normal ? guideNormal : nullptr, albedo ? guideAlbedo : nullptr, target, k, dev->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!denoised) dev->denoisedValid = true;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoise")
+
+int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_denoised"); if (rc) return rc;
+  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_denoised: NULL buffer");
+  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_denoised: no twk_denoise into the internal buffer yet");
+  const size_t n = (size_t) dev->denoisedWidth * dev->denoisedHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_denoised: buffer must hold width*height*4 floats of the denoised picture");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return readWidened(dev, dev->d_denoised, rgbaHost, n);
+}
+TWK_CATCH("twk_read_denoised")
+
+int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes)
+try
+{
+  int rc = activate(dev, "twk_read_denoised_raw"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_denoised_raw: NULL buffer");
+  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_denoised_raw: no twk_denoise into the internal buffer yet");
+  if (bytes != (size_t) dev->denoisedWidth * dev->denoisedHeight * pixelBytes(dev)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_denoised_raw: buffer must hold width*height pixels of the output format");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_denoised, bytes, hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_denoised_raw")
+
+int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
+try
+{
+  int rc = activate(dev, "twk_get_denoised_device_pointer"); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_denoised_device_pointer: NULL argument");
+  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_denoised_device_pointer: no twk_denoise into the internal buffer yet");
+  *dptr = dev->d_denoised;
+  if (bytes) *bytes = (size_t) dev->denoisedWidth * dev->denoisedHeight * pixelBytes(dev);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_denoised_device_pointer")
 
 // ---- measurement ------------------------------------------------------------------------------
 int twk_profile_enable(TwkDevice dev, int enable)

@@ -106,6 +106,17 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
     else if (key == "debugExceptions")     { ok = readInt(parser, i[0]); if (ok) debugExceptions = (i[0] != 0) ? 1 : 0; }
     // and for Optix7Gui's USE_FP32_OUTPUT (apps/Optix7Gui/shaders/app_config.h:57-59): 1 = RGBA16F output (USE_FP32_OUTPUT 0)
     else if (key == "outputFormat")        { ok = readInt(parser, i[0]); if (ok) outputFormat = (i[0] == 1) ? 1 : 0; }
+    // and for Optix7Gui's denoiser switches (USE_DENOISER, USE_DENOISER_ALBEDO, USE_DENOISER_NORMAL, app_config.h): consumed by twk_denoise
+    else if (key == "denoiser")            { ok = readInt(parser, i[0]); if (ok) denoiser = (0 <= i[0] && i[0] <= 3) ? i[0] : 0; }
+    else if (key == "denoiserIterations")  { ok = readInt(parser, i[0]); if (ok) denoiserIterations = std::min(8, std::max(0, i[0])); }
+    else if (key == "denoiserSigmas")
+    {
+      ok = readFloat(parser, f[0]) && readFloat(parser, f[1]) && readFloat(parser, f[2]);
+      // iterations are clamped into twk_denoise's range above; a sigma has no nearest valid value, so a line with one <= 0 (which
+      // twk_denoise would refuse) is dropped with a warning and the previous sigmas stay
+      if (ok && f[0] > 0.0f && f[1] > 0.0f && f[2] > 0.0f) { denoiserSigmas[0] = f[0]; denoiserSigmas[1] = f[1]; denoiserSigmas[2] = f[2]; }
+      else if (ok) warnings.push_back("denoiserSigmas must be positive, keeping the previous values");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -153,6 +164,11 @@ std::string Application::systemDescription() const
   if (nextEventEstimation != 1) d << "nextEventEstimation " << nextEventEstimation << std::endl;
   if (debugExceptions != 0) d << "debugExceptions " << debugExceptions << std::endl;
   if (outputFormat != 0) d << "outputFormat " << outputFormat << std::endl;
+  // each key on its own, so that iterations and sigmas set beside "denoiser 0" are settings kept for when it is switched on
+  if (denoiser != 0) d << "denoiser " << denoiser << std::endl;
+  if (denoiserIterations != 3) d << "denoiserIterations " << denoiserIterations << std::endl;
+  if (denoiserSigmas[0] != 8.0f || denoiserSigmas[1] != 0.3f || denoiserSigmas[2] != 0.1f)
+    d << "denoiserSigmas " << denoiserSigmas[0] << " " << denoiserSigmas[1] << " " << denoiserSigmas[2] << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

@@ -84,6 +84,12 @@ public:
   int   nextEventEstimation = 1; // grammar extension "nextEventEstimation": ≙ USE_NEXT_EVENT_ESTIMATION (shaders/config.h:50-52)
   int   debugExceptions = 0;     // grammar extension "debugExceptions": ≙ USE_DEBUG_EXCEPTIONS (config.h:54-56)
   int   outputFormat = 0;        // grammar extension "outputFormat": TWK_OUTPUT_*, 1 ≙ Optix7Gui USE_FP32_OUTPUT 0 (app_config.h:57-59)
+  // grammar extensions "denoiser" (0 off, else TwkDenoiser::inputKind + 1), "denoiserIterations", "denoiserSigmas" (colour, normal,
+  // albedo): where Optix7Gui's display path calls optixDenoiserInvoke (Application.cpp:942-1001); the values are
+  // twk_denoiser_defaults' until a key sets them
+  int   denoiser = 0;
+  int   denoiserIterations = 3;
+  float denoiserSigmas[3] = {8.0f, 0.3f, 0.1f};
   int   shaderVariant = 0; // grammar extension "shaderVariant": 0 rtigo3, 1 Optix7Gui light-hit rule (include/tweeker_hip.h TWK_SHADERS_*)
   int   samplesSqrt   = 1;
   int   resolution[2] = {1, 1};

@@ -97,6 +97,22 @@ try
 }
 TWK_CATCH("twk_app_get_output_format")
 
+int twk_app_get_denoiser(TwkApp app, int* enabled, TwkDenoiser* dn)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser: NULL app");
+  if (!enabled || !dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser: NULL argument");
+  const Application& a = app->app;
+  int rc = twk_denoiser_defaults(dn); if (rc) return rc;
+  *enabled = (a.denoiser != 0) ? 1 : 0;
+  if (a.denoiser != 0) dn->inputKind = a.denoiser - 1;
+  dn->iterations = a.denoiserIterations;
+  dn->sigmaColor = a.denoiserSigmas[0]; dn->sigmaNormal = a.denoiserSigmas[1]; dn->sigmaAlbedo = a.denoiserSigmas[2];
+  if (dn->inputKind == TWK_DENOISER_RGB) dn->demodulateAlbedo = 0; // no albedo guide to divide by
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_denoiser")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -189,6 +205,7 @@ try
   if ((rc = twk_set_next_event_estimation(dev, a.nextEventEstimation))) return rc;
   if ((rc = twk_set_debug_exceptions(dev, a.debugExceptions))) return rc;
   if ((rc = twk_set_output_format(dev, a.outputFormat))) return rc;
+  if (a.denoiser > 1 && (rc = twk_enable_aov(dev, 1))) return rc; // "denoiser 2|3": the filter's guides are the AOVs
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;
   if ((rc = twk_init_materials(dev, a.materials.data(), (int) a.materials.size()))) return rc;

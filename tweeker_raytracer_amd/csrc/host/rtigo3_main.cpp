@@ -126,6 +126,18 @@ int main(int argc, char* argv[])
   if (ordinals.empty()) { std::cerr << "ERROR: no device selected by devicesMask " << info.devicesMask << " (" << visible << " visible)\n"; return 1; }
   const int count = (int) ordinals.size();
 
+  // "denoiser" on: the picture is the tonemapped DENOISED image, as Optix7Gui displays it (optixDenoiserInvoke, then the
+  // texture, Application.cpp:942-1001), filtered after the benchmark line: the frame rate is the renderer's. The guides are the
+  // AOVs of ONE device (they are packed tile buffers on several and are not assembled): decided here, before any GPU work.
+  int denoiserEnabled = 0;
+  TwkDenoiser denoiser;
+  TWK_OK(twk_app_get_denoiser(app, &denoiserEnabled, &denoiser));
+  if (denoiserEnabled && count > 1 && denoiser.inputKind != TWK_DENOISER_RGB)
+  {
+    std::cerr << "ERROR: denoiser " << denoiser.inputKind + 1 << " needs the albedo / normal AOVs of ONE device; with several devices only denoiser 1 (no guides) filters the assembled frame\n";
+    return 1;
+  }
+
   std::vector<TwkDevice> devices((size_t) count, nullptr);
   TwkDeviceState state;
   TWK_OK(twk_app_get_state(app, &state));
@@ -205,15 +217,30 @@ int main(int argc, char* argv[])
   TwkTonemapper tonemapper;
   TWK_OK(twk_app_get_tonemapper(app, &tonemapper));
   std::vector<unsigned char> rgb8(numPixels * 3);
+  // tonemaps `frame` (device memory in the output format on the first device; NULL: the first device's own buffers), denoised
+  // first when the description asks for it
+  auto present = [&](const void* frame) -> int
+  {
+    if (denoiserEnabled)
+    {
+      TWK_OK(twk_denoise(devices[0], &denoiser, frame, nullptr, nullptr, width, height, nullptr));
+      void* denoised = nullptr;
+      TWK_OK(twk_get_denoised_device_pointer(devices[0], &denoised, nullptr));
+      frame = denoised;
+    }
+    if (!frame)    TWK_OK(twk_tonemap(devices[0], &tonemapper, nullptr, numPixels, rgb8.data())); // the handle's buffer, in its format
+    else if (half) TWK_OK(twk_tonemap_half(devices[0], &tonemapper, frame, numPixels, rgb8.data()));
+    else           TWK_OK(twk_tonemap(devices[0], &tonemapper, frame, numPixels, rgb8.data()));
+    return 0;
+  };
   if (count == 1)
   {
-    TWK_OK(twk_tonemap(devices[0], &tonemapper, nullptr, numPixels, rgb8.data()));
+    if (present(nullptr)) return 1;
   }
   else if (sharedFrame)
   {
     // every device wrote its pixels straight into the frame
-    if (half) TWK_OK(twk_tonemap_half(devices[0], &tonemapper, sharedFrame, numPixels, rgb8.data()));
-    else      TWK_OK(twk_tonemap(devices[0], &tonemapper, sharedFrame, numPixels, rgb8.data()));
+    if (present(sharedFrame)) return 1;
   }
   else
   {
@@ -233,17 +260,11 @@ int main(int argc, char* argv[])
     // device-to-device copies return before they have finished and the handle's stream is non-blocking: wait here,
     // or the compositor reads tiles that are still in flight
     HIP_OK(hipDeviceSynchronize());
-    if (half)
-    {
-      TWK_OK(twk_compositor_half(devices[0], tiles, full));
-      TWK_OK(twk_tonemap_half(devices[0], &tonemapper, full, numPixels, rgb8.data()));
-    }
-    else
-    {
-      TWK_OK(twk_compositor(devices[0], tiles, full));
-      TWK_OK(twk_tonemap(devices[0], &tonemapper, full, numPixels, rgb8.data()));
-    }
+    if (half) TWK_OK(twk_compositor_half(devices[0], tiles, full));
+    else      TWK_OK(twk_compositor(devices[0], tiles, full));
+    const int failed = present(full);
     HIP_OK(hipFree(tiles)); HIP_OK(hipFree(full));
+    if (failed) return 1;
   }
   char path[4096];
   TWK_OK(twk_app_screenshot_path(app, 1, path, sizeof(path)));

@@ -11,6 +11,7 @@
 // Per-path RNG draw order is the reference's: jitter rng2; per bounce the BSDF's draws, then NEE rng2
 // [+ rng when more than one light], then Russian roulette rng.
 #include "shade_device.h"
+#include "pixel_formats.h"
 #include "../../include/tweeker_hip.h"
 
 #include <array>
@@ -455,21 +456,7 @@ __global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p)
   accumulateLaunchIndex(p, index);
 }
 
-// Optix7Gui's RGBA16F output (USE_FP32_OUTPUT 0, app_config.h:57-59; Half4 of half_common.h:36-80). alignas(8): one
-// global_load_dwordx2 / global_store_dwordx2 per pixel (a plain struct of four _Float16 loads as a ushort plus a dword).
-struct alignas(8) Half4 { _Float16 x, y, z, w; };
-static_assert(sizeof(Half4) == 8, "RGBA16F pixel");
-
-TWK_D float4 widen(const Half4 h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); } // exact
-TWK_D float4 widen(const float4 v) { return v; }
-// f32 -> f16 round to nearest even (v_cvt_f16_f32 = __float2half; NOT v_cvt_pkrtz_f16_f32, which rounds toward zero):
-// half subnormals are kept (the code object's float_denorm_mode_16_64 is 3), what exceeds 65504 rounds to +-inf.
-TWK_D Half4 narrow(const float4 v)
-{
-  Half4 h;
-  h.x = (_Float16) v.x; h.y = (_Float16) v.y; h.z = (_Float16) v.z; h.w = (_Float16) v.w;
-  return h;
-}
+// Optix7Gui's RGBA16F output: Half4, widen, narrow of pixel_formats.h
 struct StoredAsHalf { TWK_D float4 operator()(const float4 v) const { return widen(narrow(v)); } };
 
 // accumulateKernel on RGBA16F output and AOV buffers (raygeneration.cu:267-317): the lerp operand is the widened half and the

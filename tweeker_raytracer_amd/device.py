@@ -258,6 +258,35 @@ class Device:
         L.check(L.lib.twk_tonemap(self._h, C.byref(tm), ptr, C.c_size_t(h * w), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
 
+    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None):
+        """twk_denoise: the edge-avoiding a-trous wavelet filter (a classical filter, not a learned one) where Optix7Gui calls
+        optixDenoiserInvoke. Asynchronous. params: L.Denoiser (None = the defaults). Without `beauty` the handle's own
+        accumulation and AOV buffers are filtered; otherwise beauty / albedo / normal are device pointers to shape = (height,
+        width) pixels in the handle's output format. denoised: device pointer of the result, None = the internal buffer that
+        readDenoised / denoisedDevicePointer hand out."""
+        dn = params if params is not None else L.Denoiser()
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_denoise(self._h, C.byref(dn), ptr(beauty), ptr(albedo), ptr(normal), int(w), int(h), ptr(denoised)))
+
+    def denoisedDevicePointer(self):
+        """(device pointer, bytes) of the internal denoised buffer, in the output format: feeds tonemap(rgbaDevicePointer=...)."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_denoised_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readDenoised(self, raw=False, shape=None):
+        """The internal denoised buffer: float32 [height, width, 4] (widened exactly in half mode); raw=True: as held, float16
+        in half mode. shape = (height, width) of an explicit-buffer denoise; default: the handle's launchWidth x height."""
+        h, w = shape if shape is not None else (self.state.resolution[1], self.launchWidth)
+        if raw:
+            out = np.empty((h, w, 4), dtype=np.float16 if self.outputFormat == L.TWK_OUTPUT_HALF4 else np.float32)
+            L.check(L.lib.twk_read_denoised_raw(self._h, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)))
+            return out
+        out = np.empty((h, w, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
     def statsEnable(self, enable=True):
         L.check(L.lib.twk_stats_enable(self._h, int(bool(enable))))
 

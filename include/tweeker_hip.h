@@ -446,6 +446,16 @@ int twk_gather_peak(TwkDevice dev, size_t tableBytes, float* gigaLaneLoadsPerSec
 int twk_debug_capture(TwkDevice dev, int enable);
 int twk_debug_read_first_hits(TwkDevice dev, float* tBetaGamma /*3 per px*/, int* instPrim /*2 per px*/, size_t numPixels);
 
+/* Which builds of the shade kernel ran. The dispatcher picks one of 128 launcher slots per shade launch from seven flags: bit 0
+ * ENV (spherical environment), 1 TEX (some material has an albedo texture), 2 PRIMARY (first launch of a pass that computes its
+ * own primary rays), 3 LDS_TABLES (instance + material + light tables fit the block's LDS budget), 4 MEASURE (statistics or time
+ * view), 5 SORT (class-ordered windows), 6 SLIM (TWK_STREAMS_SLIM). twk_debug_shade_builds: the slots launched on this handle
+ * since the last reset, bit I of mask[I / 64]; deferred launches are enqueued first. Recorded on the host, one OR per launch.
+ * twk_debug_shade_build_slots: the slots that hold a build at all (no handle, no GPU needed); a test that wants every build
+ * launched reads the set from here. New calls only, ABI stays 9. */
+int twk_debug_shade_builds(TwkDevice dev, uint64_t mask[2], int reset);
+int twk_debug_shade_build_slots(uint64_t mask[2]);
+
 /* Closest-hit / any-hit query of arbitrary rays through the device BVH (≙ optixTrace contract,
  * raygeneration.cu:84-89, closesthit.cu:281-286). rays: 8 floats each (o.xyz, tmin, d.xyz, tmax).
  * out: t, beta, gamma per ray; ids: instance, primitive (or -1). anyHit != 0: ids[0] = 1 if occluded.

@@ -196,6 +196,16 @@ class Oracle:
         self._chk(self.lib.orc_get_counters(self._h, out))
         return dict(zip(["radianceRays", "shadowRays", "samples", "traceCalls", "boxTests", "triTests"], list(out)))
 
+    def setOutputHalf(self, enable=True):
+        """≙ Device.setOutputFormat(1): the running means are rounded to half after every folded sample; read back widened."""
+        self._chk(self.lib.orc_set_output_half(self._h, int(bool(enable))))
+
+    def stackClamps(self):
+        """(pushes onto a full volume stack, pops off an empty one) over every sample rendered so far."""
+        out = (C.c_uint64 * 2)()
+        self._chk(self.lib.orc_get_stack_clamps(self._h, out))
+        return int(out[0]), int(out[1])
+
     def traceRays(self, rays, anyHit=False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]

@@ -37,12 +37,14 @@ struct Oracle
   bool captureFirstHits = false;
   int  launchWidth = 1;
   int  shaderVariant = TWK_SHADERS_RTIGO3; // which app's __closesthit__radiance rule for light hits (include/tweeker_hip.h)
+  bool halfOutput = false;                 // Optix7Gui's USE_FP32_OUTPUT 0: output and AOVs hold halves (kept widened here), orc_set_output_half
   bool aov = false;                        // Optix7Gui's denoiser AOVs (raygeneration.cu:125-164,239-262)
   std::vector<float4> aovAlbedo, aovNormal;
   uint64_t radianceRays = 0, shadowRays = 0, samples = 0;
+  uint64_t stackPushClamped = 0, stackPopClamped = 0; // volume stack: pushes onto a full stack, pops off an empty one (orc_get_stack_clamps)
 };
 
-struct RayTally { uint64_t radiance = 0, shadow = 0, samples = 0; };
+struct RayTally { uint64_t radiance = 0, shadow = 0, samples = 0, pushClamped = 0, popClamped = 0; };
 static RayTally& rayTally() { static thread_local RayTally t; return t; }
 static std::mutex g_tallyMutex;
 
@@ -52,6 +54,7 @@ static void mergeTallies(Oracle& o)
   std::lock_guard<std::mutex> lock(g_tallyMutex);
   RayTally& r = rayTally();
   o.radianceRays += r.radiance; o.shadowRays += r.shadow; o.samples += r.samples;
+  o.stackPushClamped += r.pushClamped; o.stackPopClamped += r.popClamped;
   r = RayTally();
   TraceCounters& t = traceTally();
   o.scene.counters.rays += t.rays; o.scene.counters.boxTests += t.boxTests; o.scene.counters.triTests += t.triTests;
@@ -493,11 +496,13 @@ static float3 integrator(Oracle& o, PerRayData& prd, Hit* firstHit, float3& albe
     {
       if (prd.flags & FLAG_FRONTFACE)
       {
+        if (stackIdx == MATERIAL_STACK_LAST) rayTally().pushClamped++;
         stackIdx = std::min(stackIdx + 1, (int) MATERIAL_STACK_LAST);
         absorptionStack[stackIdx] = prd.absorption_ior;
       }
       else
       {
+        if (stackIdx == MATERIAL_STACK_EMPTY) rayTally().popClamped++;
         stackIdx = std::max(stackIdx - 1, (int) MATERIAL_STACK_EMPTY);
       }
     }
@@ -505,6 +510,44 @@ static float3 integrator(Oracle& o, PerRayData& prd, Hit* firstHit, float3& albe
     ++depth;
   }
   return radiance;
+}
+
+// float -> half -> float, round to nearest even, subnormals kept, overflow to inf (what __float2half_rn does, half_common.h:36-80).
+static float roundToHalf(const float f)
+{
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint32_t sign = x & 0x80000000u;
+  uint32_t mag = x & 0x7fffffffu;
+  if (mag > 0x7f800000u) return f;                       // NaN
+  if (mag >= 0x477ff000u) mag = 0x7f800000u;             // >= 65520: rounds beyond the largest half 65504
+  else if (mag < 0x38800000u)                            // < 2^-14: half subnormals, multiples of 2^-24
+  {
+    float a;
+    memcpy(&a, &mag, 4);
+    a = nearbyintf(a * 16777216.0f) * (1.0f / 16777216.0f); // both scalings exact; default rounding mode = to nearest even
+    memcpy(&mag, &a, 4);
+  }
+  else
+  {
+    mag += 0x0fffu + ((mag >> 13) & 1u);                 // 13 mantissa bits go
+    mag &= ~0x1fffu;
+  }
+  x = sign | mag;
+  float r;
+  memcpy(&r, &x, 4);
+  return r;
+}
+static float4 roundToHalf(const float4& v) { return make_float4(roundToHalf(v.x), roundToHalf(v.y), roundToHalf(v.z), roundToHalf(v.w)); }
+
+// Half mode (Optix7Gui raygeneration.cu:267-317: the fold reads the widened half and stores a half). One render call folds one
+// sample per pixel, so rounding the buffers behind it is that store; a value that is a half already stays as it is.
+static void roundBuffersToHalf(Oracle& o)
+{
+  if (!o.halfOutput) return;
+  for (float4& v : o.output) v = roundToHalf(v);
+  for (float4& v : o.aovAlbedo) v = roundToHalf(v);
+  for (float4& v : o.aovNormal) v = roundToHalf(v);
 }
 
 // raygeneration.cu:152-164
@@ -876,6 +919,7 @@ int orc_render_rect(OrcHandle o, unsigned int iterationIndex, int x0, int y0, in
     for (int x = x0; x < x1; ++x)
       raygenPathTracer(*o, (unsigned int) x, (unsigned int) y);
   mergeTallies(*o);
+  roundBuffersToHalf(*o);
   return 0;
 }
 
@@ -902,6 +946,7 @@ int orc_render_rect_threads(OrcHandle o, unsigned int iterationIndex, int x0, in
     });
   }
   for (std::thread& t : pool) t.join();
+  roundBuffersToHalf(*o);
   return 0;
 }
 
@@ -957,6 +1002,21 @@ int orc_get_counters(OrcHandle o, uint64_t out[6])
 {
   out[0] = o->radianceRays; out[1] = o->shadowRays; out[2] = o->samples;
   out[3] = o->scene.counters.rays; out[4] = o->scene.counters.boxTests; out[5] = o->scene.counters.triTests;
+  return 0;
+}
+
+// ≙ twk_set_output_format(TWK_OUTPUT_HALF4): what orc_read_output / orc_read_aov return are the halves, widened. Set before the first render.
+int orc_set_output_half(OrcHandle o, int enable)
+{
+  o->halfOutput = (enable != 0);
+  return 0;
+}
+
+// Test tap: how often the integrator's volume stack hit its clamps (raygeneration.cu:131-141) since the handle was created:
+// out[0] transmissions into a medium with the stack full, out[1] transmissions out of one with the stack empty.
+int orc_get_stack_clamps(OrcHandle o, uint64_t out[2])
+{
+  out[0] = o->stackPushClamped; out[1] = o->stackPopClamped;
   return 0;
 }
 

@@ -316,6 +316,9 @@ def test_integrator_loop(texts):
     assert trace == ["optixTrace(sysData.topObject,prd.pos,prd.wi,sysData.sceneEpsilon,prd.distance,0.0f,OptixVisibilityMask(0xFF),OPTIX_RAY_FLAG_NONE,RAYTYPE_RADIANCE,NUM_RAYTYPES,RAYTYPE_RADIANCE,payload.x,payload.y);"]
     body = function_body(texts["orc_render"], "integrator")
     body = re.sub(r"if \(o\.aov\)\s*\{.*?\n    \}\n", "", body, flags=re.S)
+    # the two tallies of the volume stack's clamps (orc_get_stack_clamps, a test tap): whole lines of their own, cut out like the AOV block
+    body, taps = re.subn(r"\n *if \(stackIdx == MATERIAL_STACK_(?:LAST|EMPTY)\) rayTally\(\)\.(?:push|pop)Clamped\+\+;(?=\n)", "", body)
+    assert taps == 2
     orc = statements(body, oracle=True)
     # the oracle's stand-in for the trace and the program dispatch, in place of the single optixTrace statement
     i = orc.index("const Hit h=traceRadiance(o,&prd,prd.pos,prd.wi,sysData.sceneEpsilon,prd.distance);")

@@ -29,7 +29,8 @@ namespace twk {
 void launchTrace(const LaunchParams& p, int depth, bool count, const TraceBuild& build, int gridBlocks, hipStream_t stream);
 void launchTraceQuery(const LaunchParams& p, const float* rays, unsigned int numRays, int anyHit, float* tBetaGamma, int* ids, int gridBlocks, hipStream_t stream);
 void launchGenerate(const LaunchParams& p, hipStream_t stream);
-void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
+int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
+void shadeBuildSlots(uint64_t mask[2]);
 void launchTileEntries(const LaunchParams& p, const float4* topTable, int tilesX, int tilesY, int4* out, hipStream_t stream);
 void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream);
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
@@ -148,6 +149,7 @@ struct TwkDevice_t
   int* d_spill = nullptr; size_t spillLanes = 0;
   bool packedQueue = true; // TWK_PACKED_QUEUE=0: A/B
   bool slimStreams = true; // TWK_SLIM_STREAMS=0: A/B (device_types.h LaunchParams::slimSlotBits)
+  uint64_t shadeBuilds[2] = {0, 0}; // the shadeKernel builds launched since the last reset, by launcher index (twk_debug_shade_builds)
   int shadeSort = 1;      // TWK_SHADE_SORT=0: slot order (A/B); 1: class order in every launch but the first of a pass; 2: in the first too
   float4* d_firstHit = nullptr; int* d_firstHitInstance = nullptr;
   // denoiser AOVs (Optix7Gui raygeneration.cu:125-164): per-path values of a pass and their running means per launch index
@@ -761,7 +763,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
   {
     const bool primary = fusedPrimary && depth == 0;
     for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, laneS[k]); launchTrace(laneP[k], depth, dev->statsEnabled || dev->timeView, primary ? primaryBuild : build, primary ? primaryGrid : traceGrid, laneS[k]); timedLaunchEnd(dev, laneS[k]); }
-    for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_SHADE, laneS[k]); launchShade(laneP[k], depth, primary, shadeGrid[k], laneS[k]); timedLaunchEnd(dev, laneS[k]); }
+    for (int k = 0; k < active; ++k) { timedLaunchBegin(dev, TWK_KERNEL_SHADE, laneS[k]); const int b = launchShade(laneP[k], depth, primary, shadeGrid[k], laneS[k]); dev->shadeBuilds[b >> 6] |= 1ull << (b & 63); timedLaunchEnd(dev, laneS[k]); }
   }
   if (maxDepth > 0)
   {
@@ -1935,6 +1937,26 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_debug_capture")
+
+int twk_debug_shade_builds(TwkDevice dev, uint64_t mask[2], int reset)
+try
+{
+  int rc = activate(dev, "twk_debug_shade_builds"); if (rc) return rc; // deferred launches are enqueued, and recorded, first
+  if (!mask) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_debug_shade_builds: NULL mask");
+  mask[0] = dev->shadeBuilds[0]; mask[1] = dev->shadeBuilds[1];
+  if (reset) dev->shadeBuilds[0] = dev->shadeBuilds[1] = 0;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_debug_shade_builds")
+
+int twk_debug_shade_build_slots(uint64_t mask[2])
+try
+{
+  if (!mask) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_debug_shade_build_slots: NULL mask");
+  twk::shadeBuildSlots(mask);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_debug_shade_build_slots")
 
 int twk_debug_read_first_hits(TwkDevice dev, float* tBetaGamma, int* instPrim, size_t numPixels)
 try

@@ -635,8 +635,17 @@ constexpr ShadeLauncher shadeLauncher()
 template<int... I>
 constexpr std::array<ShadeLauncher, sizeof...(I)> shadeLaunchers(std::integer_sequence<int, I...>) { return {shadeLauncher<I>()...}; }
 
-// primary: depth 0 of a pass whose generateKernel was skipped ("primary rays" above)
-void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream)
+// Which of the 128 slots hold a build (twk_debug_shade_build_slots): bit I of mask[I / 64].
+void shadeBuildSlots(uint64_t mask[2])
+{
+  static constexpr std::array<ShadeLauncher, 128> launchers = shadeLaunchers(std::make_integer_sequence<int, 128>());
+  mask[0] = mask[1] = 0;
+  for (int i = 0; i < 128; ++i) if (launchers[i] != nullptr) mask[i >> 6] |= 1ull << (i & 63);
+}
+
+// primary: depth 0 of a pass whose generateKernel was skipped ("primary rays" above). Returns the index of the build it launched
+// (the host-side record behind twk_debug_shade_builds).
+int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream)
 {
   // the variant without what the scene does not have (shade_device.h shadePath): spherical environment, albedo textures
   const bool env = (p.miss == 2), tex = (p.hasAlbedoTexture != 0);
@@ -646,9 +655,11 @@ void launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks,
   const bool sort = !measure && fitsExchange && shadeSorted(p.shadeSort, primary);
   const bool lds = (measure || sort) ? fitsExchange : (TWK_SHADE_LDS_TABLES && tableBytes <= (size_t) TWK_SHADE_TABLE_BYTES);
   static constexpr std::array<ShadeLauncher, 128> launchers = shadeLaunchers(std::make_integer_sequence<int, 128>());
-  const ShadeLauncher launch = launchers[(env ? 1 : 0) | (tex ? 2 : 0) | (primary ? 4 : 0) | (lds ? 8 : 0) | (measure ? 16 : 0) | (sort ? 32 : 0) | (p.slimSlotBits != 0 ? 64 : 0)];
+  const int index = (env ? 1 : 0) | (tex ? 2 : 0) | (primary ? 4 : 0) | (lds ? 8 : 0) | (measure ? 16 : 0) | (sort ? 32 : 0) | (p.slimSlotBits != 0 ? 64 : 0);
+  const ShadeLauncher launch = launchers[index];
   assert(launch != nullptr);
   launch(p, depth, gridBlocks, stream);
+  return index;
 }
 void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream)
 {

@@ -27,6 +27,21 @@ def _as_array(ctype, items):
     return arr, len(items)
 
 
+SHADE_BUILD_FLAGS = ("ENV", "TEX", "PRIMARY", "LDS_TABLES", "MEASURE", "SORT", "SLIM")  # bit 0 .. bit 6 of a shade launcher index
+
+
+def shade_build_slots():
+    """The launcher indices (0..127) that hold a build of the shade kernel (twk_debug_shade_build_slots); needs no GPU."""
+    mask = (C.c_uint64 * 2)()
+    L.check(L.lib.twk_debug_shade_build_slots(mask))
+    return {i for i in range(128) if (mask[i >> 6] >> (i & 63)) & 1}
+
+
+def shade_build_name(index):
+    """'ENV|LDS_TABLES|SORT' for a launcher index; 'plain' for 0."""
+    return "|".join(n for b, n in enumerate(SHADE_BUILD_FLAGS) if (index >> b) & 1) or "plain"
+
+
 class Device:
     def __init__(self, ordinal=0, index=0, count=1, miss=1):
         self._h = C.c_void_p()
@@ -329,6 +344,12 @@ class Device:
         L.check(L.lib.twk_debug_read_acceleration(self._h, C.byref(info), nodes.ctypes.data_as(C.c_void_p), tris.ctypes.data_as(C.c_void_p),
                                                   inst.ctypes.data_as(C.c_void_p)))
         return {name: getattr(info, name) for name, _ in L.AccelerationInfo._fields_}, nodes, tris, inst
+
+    def debugShadeBuilds(self, reset=True):
+        """The launcher indices of the shade kernel builds launched on this device since the last reset (twk_debug_shade_builds)."""
+        mask = (C.c_uint64 * 2)()
+        L.check(L.lib.twk_debug_shade_builds(self._h, mask, int(bool(reset))))
+        return {i for i in range(128) if (mask[i >> 6] >> (i & 63)) & 1}
 
     def debugCapture(self, enable=True):
         L.check(L.lib.twk_debug_capture(self._h, int(bool(enable))))

@@ -424,6 +424,26 @@ int twk_denoiser_defaults(TwkDenoiser* dn);
  * blendFactor 1 copy the input's bits. */
 int twk_denoise(TwkDevice dev, const TwkDenoiser* dn, const void* beauty, const void* albedo, const void* normal,
                 int width, int height, void* denoised);
+/* The variance-guided, firefly-clamping mode of the same filter: the spatial-variance path of Schied et al. 2017 (SVGF, sections
+ * 4.2 and 4.4), which that paper uses where no temporal history exists. Between prepare and level 0 a moments pass estimates, per
+ * pixel p, mean m1 and variance var of the luminance l = 0.2126 r + 0.7152 g + 0.0722 b over the 7x7 window around p, the centre
+ * left out (a firefly must not vouch for itself), every tap weighted by the guide terms of the formula above alone. With
+ * fireflyThreshold k > 0 a pixel whose luminance exceeds limit = m1 + k sqrt(var) > 0 has its rgb scaled by limit / l_p. In the
+ * levels the colour term is replaced by |l_p - l_q| / (sigmaLuminance sqrt(v_p) + 1e-3), v_p the 3x3 binomial of the variance at
+ * the level's step, and the variance is filtered along: var' = sum w^2 var_q / (sum w)^2. dn->sigmaColor is ignored. Everything
+ * else — buffers, formats, pass-through, alpha, blendFactor, the copies at iterations 0 / blendFactor 1 — is twk_denoise's, and
+ * the result goes to the same internal buffer. What it is: a spatial variance estimate from the picture itself, and a clamp that
+ * biases bright isolated pixels downwards. What it is not: a learned filter, or one that knows the per-sample variance of the
+ * integrator. The float operations and their order: csrc/denoise_device.h. */
+typedef struct TwkDenoiserVariance
+{
+  float fireflyThreshold; /* k of the clamp, in standard deviations of the neighbourhood; 0 = no clamp; >= 0 and finite */
+  float sigmaLuminance;   /* scale of the luminance edge-stop, in standard deviations; > 0 and finite */
+} TwkDenoiserVariance;
+/* fireflyThreshold 3, sigmaLuminance 4 */
+int twk_denoiser_variance_defaults(TwkDenoiserVariance* dv);
+int twk_denoise_variance(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo,
+                         const void* normal, int width, int height, void* denoised);
 int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats);        /* RGBA32F, widened exactly, like twk_read_output */
 int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes);             /* in the output format */
 int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes); /* feeds twk_tonemap / twk_tonemap_half */
@@ -531,6 +551,10 @@ int twk_app_get_output_format(TwkApp app, int* format);
  * twk_denoise is to be called with (twk_denoiser_defaults where a key is absent; demodulateAlbedo 0 for TWK_DENOISER_RGB).
  * twk_app_init_device enables the AOVs when the key asks for a guided kind. */
 int twk_app_get_denoiser(TwkApp app, int* enabled, TwkDenoiser* dn);
+/* "denoiserVariance 0|1" (default 0), "denoiserFirefly k", "denoiserSigmaLuminance sigma": *enabled = the description asks for
+ * twk_denoise_variance in place of twk_denoise (it takes effect when "denoiser" is on), and its parameters
+ * (twk_denoiser_variance_defaults where a key is absent). */
+int twk_app_get_denoiser_variance(TwkApp app, int* enabled, TwkDenoiserVariance* dv);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

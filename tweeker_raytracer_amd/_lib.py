@@ -79,6 +79,15 @@ class Denoiser(C.Structure):
         super().__init__(int(inputKind), int(iterations), sigmaColor, sigmaNormal, sigmaAlbedo, int(bool(demodulateAlbedo)), blendFactor)
 
 
+class DenoiserVariance(C.Structure):
+    """≙ TwkDenoiserVariance: parameters of twk_denoise_variance, the variance-guided, firefly-clamping mode of the filter.
+    Without arguments: twk_denoiser_variance_defaults."""
+    _fields_ = [("fireflyThreshold", C.c_float), ("sigmaLuminance", C.c_float)]
+
+    def __init__(self, fireflyThreshold=3.0, sigmaLuminance=4.0):
+        super().__init__(fireflyThreshold, sigmaLuminance)
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("radianceRays", C.c_uint64), ("shadowRays", C.c_uint64), ("nodesVisited", C.c_uint64),
                 ("trianglesTested", C.c_uint64), ("instancesEntered", C.c_uint64), ("shadedHits", C.c_uint64),
@@ -123,6 +132,7 @@ SYMBOLS = [
     "twk_set_output_format", "twk_get_output_format", "twk_read_output_raw", "twk_read_aov_raw", "twk_compositor_half", "twk_tonemap_half",
     "twk_app_get_output_format",
     "twk_denoiser_defaults", "twk_denoise", "twk_read_denoised", "twk_read_denoised_raw", "twk_get_denoised_device_pointer", "twk_app_get_denoiser",
+    "twk_denoiser_variance_defaults", "twk_denoise_variance", "twk_app_get_denoiser_variance",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

@@ -107,6 +107,14 @@ class Application:
         return bool(on.value), dn
 
     @property
+    def denoiserVariance(self):
+        """(enabled, DenoiserVariance) from "denoiserVariance", "denoiserFirefly", "denoiserSigmaLuminance" of the system
+        description: enabled = twk_denoise_variance stands in for twk_denoise where `denoiser` is on."""
+        on, dv = C.c_int(0), L.DenoiserVariance()
+        L.check(L.lib.twk_app_get_denoiser_variance(self._h, C.byref(on), C.byref(dv)))
+        return bool(on.value), dv
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

@@ -34,6 +34,41 @@
 //   o.k = r.k + blendFactor * (b.k - r.k);  o.w = b.w;  denoised[p] = narrow(o) (RGBA16F: round to nearest even, once)
 //
 // iterations 0 or blendFactor 1: the host copies beauty to denoised, no kernel runs.
+//
+// ---- the variance-guided mode (twk_denoise_variance) ------------------------------------------------------------------------
+// The spatial-variance path of Schied et al., "Spatiotemporal Variance-Guided Filtering" (HPG 2017, sections 4.2 and 4.4), used
+// there when no temporal history exists: a per-pixel variance of the luminance estimated from the picture itself scales the
+// colour edge-stop, and a clamp against the same estimate pulls fireflies down. Still nothing learned, and no per-sample variance:
+// the estimate is spatial. tests/test_gpu_denoise_variance.py restates what follows in numpy float32 and compares bits.
+// prepare and finish are the ones above; the variance rides in .w of the colour streams (finish takes alpha from beauty).
+//
+//   lum(c) = (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z
+//   finiteV(c): c.xyz finite and lum(c) finite (a finite colour near FLT_MAX can have an infinite luminance)
+//
+// moments (pixel p = (x, y), colour of prepare in -> colour out; runs once, before level 0; R = 3):
+//   cp = in[p]; if !finiteV(cp), or a guide in use at p is not finite: out[p] = (cp.xyz, 0), done
+//   s0 = s1 = s2 = 0
+//   for dy = -3 .. 3, for dx = -3 .. 3 (in this order, the centre LEFT OUT): q = (x + dx, y + dy), skipped when outside
+//     cq = in[q]; skipped when a component of cq.xyz is not finite
+//     RGB_ALBEDO_NORMAL: t = distance2(np, nq) * invNormal + distance2(ap, aq) * invAlbedo;  RGB_ALBEDO: t = distance2(ap, aq) * invAlbedo
+//     skipped unless t <= 87 (NaN t: a guide of q that is not finite);  g = expP(-t);            RGB: no t, g = 1
+//     l = lum(cq);  s0 = s0 + g;  s1 = s1 + g * l;  s2 = s2 + g * (l * l)
+//   no tap counted (s0 == 0): out[p] = (cp.xyz, 0), done (no variance, no clamp)
+//   m1 = s1 / s0;  m2 = s2 / s0;  var = fmaxf(m2 - m1 * m1, 0)     (fmaxf: a NaN difference, inf - inf, gives 0)
+//   fireflyThreshold > 0:  limit = m1 + fireflyThreshold * sqrtf(var);  lp = lum(cp)
+//     if lp > limit and limit > 0:  f = limit / lp;  cp.k = cp.k * f   k = x, y, z
+//   out[p] = (cp.xyz, var)
+//
+// level i, step s = 1 << i (colour in -> colour out), what differs from the level above:
+//   cp = in[p]; passes through (out[p] = cp) also when lum(cp) is not finite;  lp = lum(cp)
+//   vs = 0; bs = 0;  for dy = -1 .. 1, for dx = -1 .. 1 (in this order): q = (x + dx s, y + dy s), skipped when outside
+//     cq = in[q]; skipped when a component of cq.xyz or cq.w is not finite
+//     b = b3[dy + 1] * b3[dx + 1], b3 = (1/4, 1/2, 1/4);  vs = vs + b * cq.w;  bs = bs + b
+//   vbar = (bs > 0) ? vs / bs : 0;   invL = 1.0f / (sigmaLuminance * sqrtf(vbar) + 1e-3f)        (epsilon = 1e-3f: in (0, 1000])
+//   per tap, instead of the colour term:  t = fabsf(lp - lum(cq)) * invL;  then the guide terms, the cut-off and w as above
+//     sum.k = sum.k + w * cq.k;  wsum = wsum + w;  vsum = vsum + (w * w) * cq.w
+//   out[p] = (sum.x / wsum, sum.y / wsum, sum.z / wsum, vsum / (wsum * wsum))
+//   wsum >= 9/64 still: the centre's own tap has t = 0 * invL = 0, lp being finite.
 #pragma once
 #include "device_math.h"
 
@@ -45,6 +80,7 @@ struct DenoiseConstants
   float invColor, invNormal, invAlbedo; // 1 / sigma^2
   float blendFactor;
   int   demodulate;
+  float fireflyThreshold, sigmaLuminance; // the variance-guided mode only
 };
 
 TWK_HD bool finite3(const float4& c)
@@ -79,6 +115,78 @@ TWK_HD void denoiseTap(const DenoiseConstants& k, int dx, int dy, const float4& 
   const float w = (stencilWeight(dy) * stencilWeight(dx)) * expP(-t);
   sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
   wsum = wsum + w;
+}
+
+// ---- the variance-guided mode ----
+#define TWK_DENOISE_MOMENTS_RADIUS 3
+#define TWK_DENOISE_LUMINANCE_EPSILON 1e-3f
+
+TWK_HD bool finite1(float v) { return (asUint(v) & 0x7f800000u) != 0x7f800000u; }
+
+TWK_HD float luminance(const float4& c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+
+// One tap of the moments pass: folds the luminance lq of a tap with a finite colour into s0, s1, s2
+template<int KIND>
+TWK_HD void momentsTap(const DenoiseConstants& k, const float4& np, const float4& ap, float lq, const float4& nq, const float4& aq, float& s0, float& s1, float& s2)
+{
+  float g = 1.0f;
+  if (KIND >= 1)
+  {
+    float t = distance2(ap, aq) * k.invAlbedo;
+    if (KIND >= 2) t = distance2(np, nq) * k.invNormal + t;
+    if (!(t <= 87.0f)) return;
+    g = expP(-t);
+  }
+  s0 = s0 + g; s1 = s1 + g * lq; s2 = s2 + g * (lq * lq);
+}
+
+// The end of the moments pass: variance and firefly clamp of the centre cp from the sums; returns (cp.xyz clamped, var)
+TWK_HD float4 momentsFinish(const DenoiseConstants& k, float4 cp, float s0, float s1, float s2)
+{
+  if (!(s0 > 0.0f)) return make_float4(cp.x, cp.y, cp.z, 0.0f);
+  const float m1 = s1 / s0, m2 = s2 / s0;
+  const float var = fmaxf(m2 - m1 * m1, 0.0f);
+  if (k.fireflyThreshold > 0.0f)
+  {
+    const float limit = m1 + k.fireflyThreshold * sqrtf(var);
+    const float lp = luminance(cp);
+    if (lp > limit && limit > 0.0f)
+    {
+      const float f = limit / lp;
+      cp.x = cp.x * f; cp.y = cp.y * f; cp.z = cp.z * f;
+    }
+  }
+  return make_float4(cp.x, cp.y, cp.z, var);
+}
+
+// One tap of the 3 x 3 binomial of the variance (dx, dy = -1 .. 1)
+TWK_HD void varianceBlurTap(int dx, int dy, const float4& cq, float& vs, float& bs)
+{
+  if (!finite3(cq) || !finite1(cq.w)) return;
+  const float b = ((dy == 0) ? 0.5f : 0.25f) * ((dx == 0) ? 0.5f : 0.25f);
+  vs = vs + b * cq.w; bs = bs + b;
+}
+
+TWK_HD float inverseLuminanceSigma(const DenoiseConstants& k, float vs, float bs)
+{
+  const float vbar = (bs > 0.0f) ? vs / bs : 0.0f;
+  return 1.0f / (k.sigmaLuminance * sqrtf(vbar) + TWK_DENOISE_LUMINANCE_EPSILON);
+}
+
+// One tap of a level of the variance-guided mode: like denoiseTap with the luminance edge-stop, and the variance filtered along
+template<int KIND>
+TWK_HD void denoiseVarianceTap(const DenoiseConstants& k, int dx, int dy, float lp, float invL, const float4& np, const float4& ap,
+                               const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum, float& vsum)
+{
+  if (!finite3(cq)) return;
+  float t = fabsf(lp - luminance(cq)) * invL;
+  if (KIND >= 2) t = t + distance2(np, nq) * k.invNormal;
+  if (KIND >= 1) t = t + distance2(ap, aq) * k.invAlbedo;
+  if (!(t <= 87.0f)) return; // weight 0
+  const float w = (stencilWeight(dy) * stencilWeight(dx)) * expP(-t);
+  sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
+  wsum = wsum + w;
+  vsum = vsum + (w * w) * cq.w;
 }
 
 } // namespace twk

@@ -1,5 +1,5 @@
-// Kernels of twk_denoise: the edge-avoiding a-trous wavelet filter defined in denoise_device.h (prepare, one launch per level,
-// finish). Stands where Optix7Gui calls optixDenoiserInvoke (apps/Optix7Gui/src/Application.cpp:942-1001).
+// Kernels of twk_denoise and twk_denoise_variance: the edge-avoiding a-trous wavelet filter defined in denoise_device.h (prepare, the
+// moments pass of the variance-guided mode, one launch per level, finish). Stands where Optix7Gui calls optixDenoiserInvoke (apps/Optix7Gui/src/Application.cpp:942-1001).
 #include "denoise_device.h"
 #include "pixel_formats.h"
 #include "../../include/tweeker_hip.h"
@@ -42,7 +42,9 @@ __global__ void __launch_bounds__(256) denoisePrepareKernel(const Pixel* __restr
   colour[p] = c;
 }
 
-template<int KIND>
+// VAR: the level of the variance-guided mode (denoise_device.h): luminance edge-stop scaled by the 3 x 3 binomial of the variance in
+// in[].w at the level's own step (the inner 3 x 3 of the taps the level loads anyway), the variance filtered along into out[].w
+template<int KIND, bool VAR>
 __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
                                                           float4* __restrict__ out, DenoiseConstants k, int step)
 {
@@ -55,6 +57,27 @@ __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restri
   const float4 np = (KIND >= 2) ? guideNormal[p] : zero;
   const float4 ap = (KIND >= 1) ? guideAlbedo[p] : zero;
   if (!finite3(cp) || !finite3(np) || !finite3(ap)) { out[p] = cp; return; }
+  float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
+  if (VAR)
+  {
+    lp = luminance(cp);
+    if (!finite1(lp)) { out[p] = cp; return; }
+    float vs = 0.0f, bs = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+    {
+      const int qy = y + dy * step;
+      if (qy < 0 || qy >= k.height) continue;
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx)
+      {
+        const int qx = x + dx * step;
+        if (qx < 0 || qx >= k.width) continue;
+        varianceBlurTap(dx, dy, in[(size_t) qy * k.width + qx], vs, bs);
+      }
+    }
+    invL = inverseLuminanceSigma(k, vs, bs);
+  }
   float sx = 0.0f, sy = 0.0f, sz = 0.0f, wsum = 0.0f;
 #pragma unroll
   for (int dy = -2; dy <= 2; ++dy)
@@ -70,10 +93,11 @@ __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restri
       const float4 cq = in[q];
       const float4 nq = (KIND >= 2) ? guideNormal[q] : zero;
       const float4 aq = (KIND >= 1) ? guideAlbedo[q] : zero;
-      denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
+      if (VAR) denoiseVarianceTap<KIND>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum);
+      else     denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
     }
   }
-  out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, cp.w);
+  out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, VAR ? vsum / (wsum * wsum) : cp.w);
 }
 
 // LDS-staged build: the same level with the block's taps staged in LDS. A block takes 32 x 8 pixels of ONE residue class modulo the step — pixels
@@ -85,7 +109,7 @@ __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restri
 // its own, which is where this build stops paying.
 #define TWK_DENOISE_LDS_X (TWK_DENOISE_TILE_X + 4)
 #define TWK_DENOISE_LDS_Y (TWK_DENOISE_TILE_Y + 4)
-template<int KIND>
+template<int KIND, bool VAR>
 __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
                                                              float4* __restrict__ out, DenoiseConstants k, int step)
 {
@@ -123,6 +147,20 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
   const float4 np = (KIND >= 2) ? normal[centre] : zero;
   const float4 ap = (KIND >= 1) ? albedo[centre] : zero;
   if (!finite3(cp) || !finite3(np) || !finite3(ap)) { out[p] = cp; return; }
+  float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
+  if (VAR)
+  {
+    lp = luminance(cp);
+    if (!finite1(lp)) { out[p] = cp; return; }
+    float vs = 0.0f, bs = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+    {
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) varianceBlurTap(dx, dy, colour[centre + dy * TWK_DENOISE_LDS_X + dx], vs, bs); // outside the picture: NaN colour, skipped
+    }
+    invL = inverseLuminanceSigma(k, vs, bs);
+  }
   float sx = 0.0f, sy = 0.0f, sz = 0.0f, wsum = 0.0f;
 #pragma unroll
   for (int dy = -2; dy <= 2; ++dy)
@@ -134,10 +172,75 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
       const float4 cq = colour[q];
       const float4 nq = (KIND >= 2) ? normal[q] : zero;
       const float4 aq = (KIND >= 1) ? albedo[q] : zero;
-      denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
+      if (VAR) denoiseVarianceTap<KIND>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum);
+      else     denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
     }
   }
-  out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, cp.w);
+  out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, VAR ? vsum / (wsum * wsum) : cp.w);
+}
+
+// Moments pass of the variance-guided mode (denoise_device.h): 48 dense taps around every pixel, so the block's 32 x 8 tile is
+// staged with a halo of 3, 38 x 14 = 532 pixels per 256: of the colour only its luminance (one float; NaN where the colour is not
+// finite or the pixel lies outside the picture, which is what a tap is skipped for: the luminance of a finite colour is never NaN),
+// and the guides in use. The centre's own colour is one coalesced global load. Writes the clamped colour and the variance (.w) to
+// another stream: neighbours read the unclamped value.
+#define TWK_DENOISE_MOMENTS_X (TWK_DENOISE_TILE_X + 2 * TWK_DENOISE_MOMENTS_RADIUS)
+#define TWK_DENOISE_MOMENTS_Y (TWK_DENOISE_TILE_Y + 2 * TWK_DENOISE_MOMENTS_RADIUS)
+template<int KIND>
+__global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
+                                                            float4* __restrict__ out, DenoiseConstants k)
+{
+  constexpr int STAGED = TWK_DENOISE_MOMENTS_X * TWK_DENOISE_MOMENTS_Y;
+  __shared__ float  lum[STAGED];
+  __shared__ float4 normal[KIND >= 2 ? STAGED : 1];
+  __shared__ float4 albedo[KIND >= 1 ? STAGED : 1];
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const int x0 = (int) blockIdx.x * TWK_DENOISE_TILE_X, y0 = (int) blockIdx.y * TWK_DENOISE_TILE_Y;
+  for (int i = (int) threadIdx.x; i < STAGED; i += 256)
+  {
+    const int gx = x0 - TWK_DENOISE_MOMENTS_RADIUS + i % TWK_DENOISE_MOMENTS_X;
+    const int gy = y0 - TWK_DENOISE_MOMENTS_RADIUS + i / TWK_DENOISE_MOMENTS_X;
+    float l = asFloat(0x7fc00000u);
+    float4 n = zero, a = zero;
+    if (gx >= 0 && gx < k.width && gy >= 0 && gy < k.height)
+    {
+      const size_t q = (size_t) gy * k.width + gx;
+      const float4 c = in[q];
+      if (finite3(c)) l = luminance(c);
+      if (KIND >= 2) n = guideNormal[q];
+      if (KIND >= 1) a = guideAlbedo[q];
+    }
+    lum[i] = l;
+    if (KIND >= 2) normal[i] = n;
+    if (KIND >= 1) albedo[i] = a;
+  }
+  __syncthreads();
+  const int lx = (int) (threadIdx.x % TWK_DENOISE_TILE_X), ly = (int) (threadIdx.x / TWK_DENOISE_TILE_X);
+  const int x = x0 + lx, y = y0 + ly;
+  if (x >= k.width || y >= k.height) return;
+  const size_t p = (size_t) y * k.width + x;
+  const int centre = (ly + TWK_DENOISE_MOMENTS_RADIUS) * TWK_DENOISE_MOMENTS_X + lx + TWK_DENOISE_MOMENTS_RADIUS;
+  const float4 cp = in[p];
+  const float4 np = (KIND >= 2) ? normal[centre] : zero;
+  const float4 ap = (KIND >= 1) ? albedo[centre] : zero;
+  if (!finite3(cp) || !finite1(lum[centre]) || !finite3(np) || !finite3(ap)) { out[p] = make_float4(cp.x, cp.y, cp.z, 0.0f); return; }
+  float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+  for (int dy = -TWK_DENOISE_MOMENTS_RADIUS; dy <= TWK_DENOISE_MOMENTS_RADIUS; ++dy)
+  {
+#pragma unroll
+    for (int dx = -TWK_DENOISE_MOMENTS_RADIUS; dx <= TWK_DENOISE_MOMENTS_RADIUS; ++dx)
+    {
+      if (dx == 0 && dy == 0) continue;
+      const int q = centre + dy * TWK_DENOISE_MOMENTS_X + dx;
+      const float lq = lum[q];
+      if ((asUint(lq) & 0x7fffffffu) > 0x7f800000u) continue; // NaN: outside, or a colour that is not finite
+      const float4 nq = (KIND >= 2) ? normal[q] : zero;
+      const float4 aq = (KIND >= 1) ? albedo[q] : zero;
+      momentsTap<KIND>(k, np, ap, lq, nq, aq, s0, s1, s2);
+    }
+  }
+  out[p] = momentsFinish(k, cp, s0, s1, s2);
 }
 
 template<typename Pixel> struct PixelOf;
@@ -186,21 +289,41 @@ void launchDenoisePrepare(const void* beauty, const void* albedo, const void* no
                                static_cast<const float4*>(normal), colour, guideNormal, guideAlbedo, k);
 }
 
-// lds: the LDS-staged build of the level (one residue class modulo the step per block)
-void launchDenoiseLevel(int kind, bool lds, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream)
+template<int KIND, bool VAR>
+static void launchDenoiseLevelOf(bool lds, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream)
 {
   if (lds)
   {
     const dim3 ldsGrid(((k.width + step - 1) / step + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X * step, ((k.height + step - 1) / step + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y * step);
-    if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL(denoiseLevelLdsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL>, ldsGrid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
-    else if (kind == TWK_DENOISER_RGB_ALBEDO)   hipLaunchKernelGGL(denoiseLevelLdsKernel<TWK_DENOISER_RGB_ALBEDO>, ldsGrid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
-    else                                        hipLaunchKernelGGL(denoiseLevelLdsKernel<TWK_DENOISER_RGB>, ldsGrid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
+    hipLaunchKernelGGL((denoiseLevelLdsKernel<KIND, VAR>), ldsGrid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
     return;
   }
   const dim3 grid((k.width + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X, (k.height + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y);
-  if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL(denoiseLevelKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
-  else if (kind == TWK_DENOISER_RGB_ALBEDO)   hipLaunchKernelGGL(denoiseLevelKernel<TWK_DENOISER_RGB_ALBEDO>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
-  else                                        hipLaunchKernelGGL(denoiseLevelKernel<TWK_DENOISER_RGB>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
+  hipLaunchKernelGGL((denoiseLevelKernel<KIND, VAR>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
+}
+
+// lds: the LDS-staged build of the level (one residue class modulo the step per block); variance: the level of the variance-guided mode
+void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream)
+{
+  if (variance)
+  {
+    if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
+    else if (kind == TWK_DENOISER_RGB_ALBEDO)   launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO, true>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
+    else                                        launchDenoiseLevelOf<TWK_DENOISER_RGB, true>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
+    return;
+  }
+  if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO_NORMAL, false>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
+  else if (kind == TWK_DENOISER_RGB_ALBEDO)   launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO, false>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
+  else                                        launchDenoiseLevelOf<TWK_DENOISER_RGB, false>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
+}
+
+// the moments + firefly-clamp pass of the variance-guided mode, between prepare and level 0
+void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, hipStream_t stream)
+{
+  const dim3 grid((k.width + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X, (k.height + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y);
+  if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL(denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k);
+  else if (kind == TWK_DENOISER_RGB_ALBEDO)   hipLaunchKernelGGL(denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k);
+  else                                        hipLaunchKernelGGL(denoiseMomentsKernel<TWK_DENOISER_RGB>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k);
 }
 
 // guideNormal / guideAlbedo NULL: the kind does not use the guide

@@ -42,7 +42,8 @@ void launchGatherProbe(const float4* table, unsigned int lines, int steps, float
 void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
 void launchDenoisePrepare(const void* beauty, const void* albedo, const void* normal, bool half, float4* colour, float4* guideNormal, float4* guideAlbedo,
                           const DenoiseConstants& k, hipStream_t stream);
-void launchDenoiseLevel(int kind, bool lds, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
+void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, hipStream_t stream);
+void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
 }
 
@@ -1677,53 +1678,57 @@ static bool overlaps(const void* a, const void* b, size_t bytes)
   return x < y + bytes && y < x + bytes;
 }
 
-int twk_denoise(TwkDevice dev, const TwkDenoiser* dn, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
-try
+// twk_denoise (dv NULL) and twk_denoise_variance: `name` is the entry point, for its error texts
+static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
 {
-  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL device handle");
-  if (!dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL parameters");
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
   const int kind = dn->inputKind;
-  if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: unknown inputKind");
-  if (dn->iterations < 0 || dn->iterations > 8) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: iterations must be in [0, 8]");
-  if (!(dn->sigmaColor > 0.0f) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
-    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: the sigma of every guide in use must be positive");
+  if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "unknown inputKind");
+  if (dn->iterations < 0 || dn->iterations > 8) return refuse(TWK_ERROR_INVALID_VALUE, "iterations must be in [0, 8]");
+  if ((!dv && !(dn->sigmaColor > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
+    return refuse(TWK_ERROR_INVALID_VALUE, "the sigma of every guide in use must be positive");
   {
     // 1 / sigma^2 is what the kernels multiply by: a sigma whose square underflows would make it inf, and 0 x inf the centre tap's NaN
-    const float sigmas[3] = {dn->sigmaColor, (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? dn->sigmaNormal : 1.0f, (kind >= TWK_DENOISER_RGB_ALBEDO) ? dn->sigmaAlbedo : 1.0f};
+    const float sigmas[3] = {dv ? 1.0f : dn->sigmaColor, (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? dn->sigmaNormal : 1.0f, (kind >= TWK_DENOISER_RGB_ALBEDO) ? dn->sigmaAlbedo : 1.0f};
     for (const float sigma : sigmas)
-      if (!std::isfinite(1.0f / (sigma * sigma))) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: a sigma is too small: 1 / sigma^2 is not a finite float");
+      if (!std::isfinite(1.0f / (sigma * sigma))) return refuse(TWK_ERROR_INVALID_VALUE, "a sigma is too small: 1 / sigma^2 is not a finite float");
   }
-  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: blendFactor must be in [0, 1]");
-  if (dn->demodulateAlbedo && kind == TWK_DENOISER_RGB) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: demodulateAlbedo needs an albedo guide (inputKind TWK_DENOISER_RGB has none)");
-  int rc = activate(dev, "twk_denoise"); if (rc) return rc;
+  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "blendFactor must be in [0, 1]");
+  if (dn->demodulateAlbedo && kind == TWK_DENOISER_RGB) return refuse(TWK_ERROR_INVALID_VALUE, "demodulateAlbedo needs an albedo guide (inputKind TWK_DENOISER_RGB has none)");
+  if (dv)
+  {
+    if (!(dv->fireflyThreshold >= 0.0f) || !std::isfinite(dv->fireflyThreshold)) return refuse(TWK_ERROR_INVALID_VALUE, "fireflyThreshold must be >= 0 (0 = no clamp) and finite");
+    if (!(dv->sigmaLuminance > 0.0f) || !std::isfinite(dv->sigmaLuminance)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaLuminance must be > 0 and finite");
+  }
+  int rc = activate(dev, name); if (rc) return rc;
 
   const bool own = (beauty == nullptr);
   if (own)
   {
-    if (albedo || normal) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
-    if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: twk_set_state first");
-    if (dev->state.distribution && 1 < dev->count) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
+    if (albedo || normal) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
+    if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
+    if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
     beauty = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-    if (!beauty) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: nothing has been rendered");
+    if (!beauty) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
     width = dev->launchWidth; height = dev->state.resolution[1];
     if (kind != TWK_DENOISER_RGB)
     {
       if (!dev->aovEnabled || !dev->d_aovAlbedo || !dev->d_aovNormal || (size_t) dev->aovPixels < (size_t) width * height)
-        return twkSetError(TWK_ERROR_INVALID_STATE, "twk_denoise: a guided inputKind on the handle's own buffers needs a render with twk_enable_aov(1)");
+        return refuse(TWK_ERROR_INVALID_STATE, "a guided inputKind on the handle's own buffers needs a render with twk_enable_aov(1)");
       albedo = dev->d_aovAlbedo;
       if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = dev->d_aovNormal;
     }
   }
   else
   {
-    if (width < 1 || height < 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: width and height must be >= 1");
-    if ((kind >= TWK_DENOISER_RGB_ALBEDO && !albedo) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !normal)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL guide buffer for a guide the inputKind uses");
+    if (width < 1 || height < 1) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
+    if ((kind >= TWK_DENOISER_RGB_ALBEDO && !albedo) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !normal)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL guide buffer for a guide the inputKind uses");
     if (kind < TWK_DENOISER_RGB_ALBEDO) albedo = nullptr;        // guides the kind does not use are not read
     if (kind < TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = nullptr;
   }
   const size_t numPixels = (size_t) width * height, bytes = numPixels * pixelBytes(dev);
   if (denoised && (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes)))
-    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: the denoised buffer overlaps an input");
+    return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
 
   void* target = denoised;
   if (!target)
@@ -1755,21 +1760,53 @@ try
     float4* guideAlbedo = dev->d_denoiseStreams + 3 * numPixels;
     DenoiseConstants k;
     k.width = width; k.height = height;
-    k.invColor  = 1.0f / (dn->sigmaColor * dn->sigmaColor);
+    k.invColor  = dv ? 0.0f : 1.0f / (dn->sigmaColor * dn->sigmaColor);
     k.invNormal = (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? 1.0f / (dn->sigmaNormal * dn->sigmaNormal) : 0.0f;
     k.invAlbedo = (kind >= TWK_DENOISER_RGB_ALBEDO) ? 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo) : 0.0f;
     k.blendFactor = dn->blendFactor;
     k.demodulate = dn->demodulateAlbedo ? 1 : 0;
-    launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[0], guideNormal, guideAlbedo, k, dev->stream);
+    k.fireflyThreshold = dv ? dv->fireflyThreshold : 0.0f;
+    k.sigmaLuminance = dv ? dv->sigmaLuminance : 0.0f;
+    // the variance-guided mode: prepare writes the pong stream and the moments pass the ping stream (clamped colour, variance in
+    // .w), so that the levels ping-pong as without it and the mode needs no stream of its own
+    launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[dv ? 1 : 0], guideNormal, guideAlbedo, k, dev->stream);
+    if (dv) launchDenoiseMoments(kind, colour[1], guideNormal, guideAlbedo, colour[0], k, dev->stream);
     for (int level = 0; level < dn->iterations; ++level)
-      launchDenoiseLevel(kind, (1 << level) <= dev->denoiseLdsMaxStep, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream);
+      launchDenoiseLevel(kind, (1 << level) <= dev->denoiseLdsMaxStep, dv != nullptr, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream);
     launchDenoiseFinish(beauty, halfOutput(dev), colour[dn->iterations & 1], normal ? guideNormal : nullptr, albedo ? guideAlbedo : nullptr, target, k, dev->stream);
     HIP_TRY(hipGetLastError());
   }
   if (!denoised) dev->denoisedValid = true;
   return TWK_SUCCESS;
 }
+
+int twk_denoise(TwkDevice dev, const TwkDenoiser* dn, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL device handle");
+  if (!dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL parameters");
+  return denoise("twk_denoise", dev, dn, nullptr, beauty, albedo, normal, width, height, denoised);
+}
 TWK_CATCH("twk_denoise")
+
+int twk_denoiser_variance_defaults(TwkDenoiserVariance* dv)
+try
+{
+  if (!dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoiser_variance_defaults: NULL argument");
+  dv->fireflyThreshold = 3.0f;
+  dv->sigmaLuminance = 4.0f;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoiser_variance_defaults")
+
+int twk_denoise_variance(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance: NULL device handle");
+  if (!dn || !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance: NULL parameters");
+  return denoise("twk_denoise_variance", dev, dn, dv, beauty, albedo, normal, width, height, denoised);
+}
+TWK_CATCH("twk_denoise_variance")
 
 int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats)
 try

@@ -3,6 +3,7 @@
 #include "transform_stack.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <sstream>
 
@@ -117,6 +118,20 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && f[0] > 0.0f && f[1] > 0.0f && f[2] > 0.0f) { denoiserSigmas[0] = f[0]; denoiserSigmas[1] = f[1]; denoiserSigmas[2] = f[2]; }
       else if (ok) warnings.push_back("denoiserSigmas must be positive, keeping the previous values");
     }
+    else if (key == "denoiserVariance")    { ok = readInt(parser, i[0]); if (ok) denoiserVariance = (i[0] == 1) ? 1 : 0; }
+    // as with the sigmas: a value twk_denoise_variance would refuse drops the line, the previous value stays
+    else if (key == "denoiserFirefly")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] >= 0.0f && std::isfinite(f[0])) denoiserFirefly = f[0];
+      else if (ok) warnings.push_back("denoiserFirefly must be >= 0 and finite, keeping the previous value");
+    }
+    else if (key == "denoiserSigmaLuminance")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] > 0.0f && std::isfinite(f[0])) denoiserSigmaLuminance = f[0];
+      else if (ok) warnings.push_back("denoiserSigmaLuminance must be > 0 and finite, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -169,6 +184,9 @@ std::string Application::systemDescription() const
   if (denoiserIterations != 3) d << "denoiserIterations " << denoiserIterations << std::endl;
   if (denoiserSigmas[0] != 8.0f || denoiserSigmas[1] != 0.3f || denoiserSigmas[2] != 0.1f)
     d << "denoiserSigmas " << denoiserSigmas[0] << " " << denoiserSigmas[1] << " " << denoiserSigmas[2] << std::endl;
+  if (denoiserVariance != 0) d << "denoiserVariance " << denoiserVariance << std::endl;
+  if (denoiserFirefly != 3.0f) d << "denoiserFirefly " << denoiserFirefly << std::endl;
+  if (denoiserSigmaLuminance != 4.0f) d << "denoiserSigmaLuminance " << denoiserSigmaLuminance << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

@@ -90,6 +90,11 @@ public:
   int   denoiser = 0;
   int   denoiserIterations = 3;
   float denoiserSigmas[3] = {8.0f, 0.3f, 0.1f};
+  // "denoiserVariance" (1: twk_denoise_variance in place of twk_denoise), "denoiserFirefly", "denoiserSigmaLuminance": the
+  // variance-guided, firefly-clamping mode; twk_denoiser_variance_defaults' values until a key sets them
+  int   denoiserVariance = 0;
+  float denoiserFirefly = 3.0f;
+  float denoiserSigmaLuminance = 4.0f;
   int   shaderVariant = 0; // grammar extension "shaderVariant": 0 rtigo3, 1 Optix7Gui light-hit rule (include/tweeker_hip.h TWK_SHADERS_*)
   int   samplesSqrt   = 1;
   int   resolution[2] = {1, 1};

@@ -113,6 +113,19 @@ try
 }
 TWK_CATCH("twk_app_get_denoiser")
 
+int twk_app_get_denoiser_variance(TwkApp app, int* enabled, TwkDenoiserVariance* dv)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser_variance: NULL app");
+  if (!enabled || !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser_variance: NULL argument");
+  const Application& a = app->app;
+  *enabled = a.denoiserVariance;
+  dv->fireflyThreshold = a.denoiserFirefly;
+  dv->sigmaLuminance = a.denoiserSigmaLuminance;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_denoiser_variance")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {

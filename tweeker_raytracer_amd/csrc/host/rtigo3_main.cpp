@@ -132,6 +132,9 @@ int main(int argc, char* argv[])
   int denoiserEnabled = 0;
   TwkDenoiser denoiser;
   TWK_OK(twk_app_get_denoiser(app, &denoiserEnabled, &denoiser));
+  int denoiserVarianceEnabled = 0; // "denoiserVariance 1": the variance-guided, firefly-clamping mode of the filter
+  TwkDenoiserVariance denoiserVariance;
+  TWK_OK(twk_app_get_denoiser_variance(app, &denoiserVarianceEnabled, &denoiserVariance));
   if (denoiserEnabled && count > 1 && denoiser.inputKind != TWK_DENOISER_RGB)
   {
     std::cerr << "ERROR: denoiser " << denoiser.inputKind + 1 << " needs the albedo / normal AOVs of ONE device; with several devices only denoiser 1 (no guides) filters the assembled frame\n";
@@ -223,7 +226,8 @@ int main(int argc, char* argv[])
   {
     if (denoiserEnabled)
     {
-      TWK_OK(twk_denoise(devices[0], &denoiser, frame, nullptr, nullptr, width, height, nullptr));
+      if (denoiserVarianceEnabled) TWK_OK(twk_denoise_variance(devices[0], &denoiser, &denoiserVariance, frame, nullptr, nullptr, width, height, nullptr));
+      else                         TWK_OK(twk_denoise(devices[0], &denoiser, frame, nullptr, nullptr, width, height, nullptr));
       void* denoised = nullptr;
       TWK_OK(twk_get_denoised_device_pointer(devices[0], &denoised, nullptr));
       frame = denoised;

@@ -273,15 +273,19 @@ class Device:
         L.check(L.lib.twk_tonemap(self._h, C.byref(tm), ptr, C.c_size_t(h * w), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
 
-    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None):
+    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None, variance=None):
         """twk_denoise: the edge-avoiding a-trous wavelet filter (a classical filter, not a learned one) where Optix7Gui calls
         optixDenoiserInvoke. Asynchronous. params: L.Denoiser (None = the defaults). Without `beauty` the handle's own
         accumulation and AOV buffers are filtered; otherwise beauty / albedo / normal are device pointers to shape = (height,
         width) pixels in the handle's output format. denoised: device pointer of the result, None = the internal buffer that
-        readDenoised / denoisedDevicePointer hand out."""
+        readDenoised / denoisedDevicePointer hand out. variance: L.DenoiserVariance = twk_denoise_variance, the variance-guided,
+        firefly-clamping mode of the same filter (params.sigmaColor is ignored then); None = twk_denoise."""
         dn = params if params is not None else L.Denoiser()
         ptr = lambda p: None if p is None else C.c_void_p(int(p))
         h, w = shape if shape is not None else (0, 0)
+        if variance is not None:
+            L.check(L.lib.twk_denoise_variance(self._h, C.byref(dn), C.byref(variance), ptr(beauty), ptr(albedo), ptr(normal), int(w), int(h), ptr(denoised)))
+            return
         L.check(L.lib.twk_denoise(self._h, C.byref(dn), ptr(beauty), ptr(albedo), ptr(normal), int(w), int(h), ptr(denoised)))
 
     def denoisedDevicePointer(self):

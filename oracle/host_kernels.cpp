@@ -20,18 +20,6 @@
 
 using namespace twk;
 
-namespace {
-
-template<typename T> T* carve(std::vector<char>& pool, size_t& offset, size_t count)
-{
-  offset = (offset + 15) & ~(size_t) 15;
-  T* p = reinterpret_cast<T*>(pool.data() + offset);
-  offset += count * sizeof(T);
-  return p;
-}
-
-} // namespace
-
 extern "C" {
 
 // launchParams: what twk_debug_snapshot_scene wrote. Renders iterations [firstIteration, firstIteration + batch) as ONE
@@ -47,20 +35,11 @@ int hostk_render(const void* launchParams, size_t paramsBytes, unsigned int firs
   const size_t numPixels = (size_t) p.numPixels, n = numPixels * (size_t) batch;
   const int maxDepth = p.pathLengths[1];
 
-  std::vector<char> pool(n * (15 * sizeof(float4) + 2 * sizeof(uint2) + 6 * sizeof(unsigned int)) + 4096 + sizeof(unsigned int) * TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2));
-  size_t off = 0;
-  for (int k = 0; k < 2; ++k)
-  {
-    p.rayOrg[k] = carve<float4>(pool, off, n); p.rayDir[k] = carve<float4>(pool, off, n); p.rayThroughput[k] = carve<float4>(pool, off, n);
-    p.raySeedFlags[k] = carve<uint2>(pool, off, n); p.rayPixel[k] = carve<unsigned int>(pool, off, n);
-  }
-  p.hitRecord = carve<float4>(pool, off, n); p.hitInstance = carve<int>(pool, off, n);
-  p.shadowOrg = carve<float4>(pool, off, n); p.shadowDir = carve<float4>(pool, off, n); p.shadowPending = carve<float4>(pool, off, n);
-  p.shadowPixel = carve<unsigned int>(pool, off, n);
-  p.pathRadiance = carve<float4>(pool, off, n);
-  p.volumeStack = carve<float4>(pool, off, 4 * n);
-  p.counters = carve<unsigned int>(pool, off, TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2));
-  memset(p.counters, 0, sizeof(unsigned int) * TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2));
+  // streams and counters of its own: the list and the bytes per path of device_types.h TWK_PATH_STREAMS, no padding (one segment per queue)
+  std::vector<float4> pool((n * kPathStreamBytes + sizeof(float4) - 1) / sizeof(float4));
+  carvePathStreams(p, pool.data(), n);
+  std::vector<unsigned int> counters(TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2), 0u);
+  p.counters = counters.data();
   unsigned int dropped = 0;
   p.droppedPushes = &dropped;
   p.output = reinterpret_cast<float4*>(output);

@@ -91,13 +91,6 @@ struct TileEntriesKey
   int32_t  resolution[2], topRoot, topRoot2, launchWidth, deviceCount, deviceIndex, tileSize[2], valid;
   uint64_t buildSerial;
 };
-#define TWK_MAX_LANES 4
-#define TWK_LANE_QUEUE_PAD (TWK_QUEUE_SEGMENTS * 1024)                       // slots a lane's queue arrays may use beyond its path count (segment gaps: K x (255 + 512) at most)
-#define TWK_STREAM_PAD ((size_t) TWK_MAX_LANES * (TWK_LANE_QUEUE_PAD + 1024)) // ... of all lanes + the rounding of their shares
-// TWK_QUEUE_STRIDE gives a segment room for ceil(windows / K) shade windows of at most 256 slots (N / K rounded up to 256, + 512),
-// so a lane's K segments span at most its path count + K x (255 + 512) slots
-static_assert(TWK_SHADE_BLOCK <= 256, "a shade window (TWK_SHADE_BLOCK slots) fits TWK_QUEUE_STRIDE's rounding");
-static_assert(TWK_QUEUE_SEGMENTS * (255 + 512) <= TWK_LANE_QUEUE_PAD, "a lane's segment gaps fit TWK_LANE_QUEUE_PAD");
 #define TWK_STATS_WORDS 192 // device words of TwkLaunchStats: [0, 24) traversal + shade totals, [24, 96) the shade phases (shade_device.h PhaseScope); twice: the time view's scratch copy
 #define TWK_COUNTER_WORDS (TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2)) // one lane's counter block
 
@@ -385,6 +378,28 @@ static int slimSlotBits(TwkDevice dev)
 
 static int traceGridBlocks(TwkDevice dev) { return dev->numCUs * TWK_TRACE_WAVES7; } // the largest persistent grid (sizes the spill stacks); a launch uses numCUs x traceBuild's blocksPerCU
 
+// Buffers that share one capacity (in elements): when it is short of `want`, or the first buffer is gone, all are freed and
+// allocated again, zeroed on the handle's stream where asked. A failed allocation leaves the capacity 0, so that the next call
+// allocates again, and returns TWK_ERROR_OUT_OF_MEMORY, on which flushPending halves the pass.
+struct GrownBuffer
+{
+  void** pointer; size_t elementBytes; bool zeroed;
+  template<typename T> GrownBuffer(T*& p, size_t elementBytes, bool zeroed = false) : pointer(reinterpret_cast<void**>(&p)), elementBytes(elementBytes), zeroed(zeroed) {}
+};
+template<typename Count> static int growBuffers(TwkDevice dev, Count& capacity, Count want, std::initializer_list<GrownBuffer> buffers)
+{
+  if (want <= capacity && *buffers.begin()->pointer != nullptr) return TWK_SUCCESS;
+  capacity = 0;
+  for (const GrownBuffer& b : buffers) freeDevice(*b.pointer);
+  for (const GrownBuffer& b : buffers)
+  {
+    HIP_TRY(hipMalloc(b.pointer, (size_t) want * b.elementBytes));
+    if (b.zeroed) HIP_TRY(hipMemsetAsync(*b.pointer, 0, (size_t) want * b.elementBytes, dev->stream));
+  }
+  capacity = want;
+  return TWK_SUCCESS;
+}
+
 // `samples`: samples per pixel the next wavefront pass carries; the path streams grow to what passes actually need
 // (a 64-sample pass of a 1920x1080 frame takes 46 GB, a handle that renders two iterations takes 1.4 GB).
 static int ensureStreams(TwkDevice dev, int samples = 1)
@@ -395,55 +410,23 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
     return twkSetError(TWK_ERROR_OUT_OF_MEMORY, "a pass of " + std::to_string(wantPaths) + " paths exceeds the 2^31 path indices of a wavefront pass");
   const int numPixels = (int) wantPixels;
   const int numPaths  = (int) wantPaths;
-  if (numPixels > dev->allocatedPixels || dev->d_outputInternal == nullptr)
-  {
-    freeDevice(dev->d_outputInternal);
-    freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
-    const size_t n = (size_t) numPixels;
-    HIP_TRY(hipMalloc(&dev->d_outputInternal, n * pixelBytes(dev)));
-    HIP_TRY(hipMemsetAsync(dev->d_outputInternal, 0, n * pixelBytes(dev), dev->stream));
-    HIP_TRY(hipMalloc(&dev->d_firstHit, n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&dev->d_firstHitInstance, n * sizeof(int)));
-    dev->allocatedPixels = numPixels;
-  }
+  int rc;
+  if ((rc = growBuffers(dev, dev->allocatedPixels, numPixels, {{dev->d_outputInternal, pixelBytes(dev), true}, {dev->d_firstHit, sizeof(float4)}, {dev->d_firstHitInstance, sizeof(int)}}))) return rc;
   if (numPaths > dev->allocatedPaths || dev->d_streamBlock == nullptr)
   {
     freeDevice(dev->d_streamBlock);
-    const size_t n = (size_t) numPaths;
-    // float4 streams: rayOrg[2], rayDir[2], rayThroughput[2], hitRecord, shadowOrg, shadowDir, shadowPending, radiance, volumeStack[4] = 15
-    // 8-byte: raySeedFlags[2]; 4-byte: rayPixel[2], hitInstance, shadowPixel, overflowSlots[2]   → 280 bytes per path
-    // (+ TWK_STREAM_PAD slots per stream: the segments of a queue leave gaps between them, device_types.h "queue segments")
-    const size_t bytes = (n + TWK_STREAM_PAD) * (15 * sizeof(float4) + 2 * sizeof(uint2) + 6 * sizeof(unsigned int)) + 4096;
-    if (dev->streamBudgetBytes != 0 && n * (15 * sizeof(float4) + 2 * sizeof(uint2) + 6 * sizeof(unsigned int)) > dev->streamBudgetBytes) // (the budget is for what grows with the pass, not for the fixed padding)
+    // kPathStreamBytes per path (device_types.h TWK_PATH_STREAMS) + TWK_STREAM_PAD slots per stream: the segments of a queue leave gaps between them
+    const size_t n = (size_t) numPaths, bytes = (n + TWK_STREAM_PAD) * kPathStreamBytes + 4096;
+    if (dev->streamBudgetBytes != 0 && n * kPathStreamBytes > dev->streamBudgetBytes) // (the budget is for what grows with the pass, not for the fixed padding)
       return twkSetError(TWK_ERROR_OUT_OF_MEMORY, "path streams of " + std::to_string(bytes >> 20) + " MiB exceed TWK_STREAM_BUDGET_MB");
     HIP_TRY(hipMalloc(&dev->d_streamBlock, bytes));
     dev->allocatedPaths = numPaths;
   }
-  if (dev->timeView && dev->allocatedPaths > dev->timePaths)
-  {
-    freeDevice(dev->d_pathTime); dev->timePaths = 0;
-    HIP_TRY(hipMalloc(&dev->d_pathTime, (size_t) dev->allocatedPaths * sizeof(float)));
-    dev->timePaths = dev->allocatedPaths;
-  }
+  if (dev->timeView && (rc = growBuffers(dev, dev->timePaths, dev->allocatedPaths, {{dev->d_pathTime, sizeof(float)}}))) return rc;
   if (dev->aovEnabled)
   {
-    if (dev->allocatedPaths > dev->aovPaths)
-    {
-      freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); dev->aovPaths = 0;
-      HIP_TRY(hipMalloc(&dev->d_pathAlbedo, (size_t) dev->allocatedPaths * sizeof(float4)));
-      HIP_TRY(hipMalloc(&dev->d_pathNormal, (size_t) dev->allocatedPaths * sizeof(float4)));
-      dev->aovPaths = dev->allocatedPaths;
-    }
-    if (dev->allocatedPixels > dev->aovPixels)
-    {
-      freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
-      const size_t bytes = (size_t) dev->allocatedPixels * pixelBytes(dev);
-      HIP_TRY(hipMalloc(&dev->d_aovAlbedo, bytes));
-      HIP_TRY(hipMalloc(&dev->d_aovNormal, bytes));
-      HIP_TRY(hipMemsetAsync(dev->d_aovAlbedo, 0, bytes, dev->stream));
-      HIP_TRY(hipMemsetAsync(dev->d_aovNormal, 0, bytes, dev->stream));
-      dev->aovPixels = dev->allocatedPixels;
-    }
+    if ((rc = growBuffers(dev, dev->aovPaths, dev->allocatedPaths, {{dev->d_pathAlbedo, sizeof(float4)}, {dev->d_pathNormal, sizeof(float4)}}))) return rc;
+    if ((rc = growBuffers(dev, dev->aovPixels, dev->allocatedPixels, {{dev->d_aovAlbedo, pixelBytes(dev), true}, {dev->d_aovNormal, pixelBytes(dev), true}}))) return rc;
   }
   if (!dev->d_counters) HIP_TRY(hipMalloc(&dev->d_counters, sizeof(unsigned int) * TWK_COUNTER_WORDS * TWK_MAX_LANES));
   if (!dev->d_stats) { HIP_TRY(hipMalloc(&dev->d_stats, sizeof(unsigned long long) * TWK_STATS_WORDS)); HIP_TRY(hipMemsetAsync(dev->d_stats, 0, sizeof(unsigned long long) * TWK_STATS_WORDS, dev->stream)); } // TwkLaunchStats words (24 + the shade phases' 3 x 24) + a scratch block of the same size for the time view
@@ -456,29 +439,9 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
   // one full grid of per-lane spill stacks (the lanes of a pass share it); two only under the experiments-only
   // TWK_LANE_TRACE_WAVES knob, which may give every lane more than its share of a grid (264 MB per handle otherwise)
   const size_t lanes = (size_t) (dev->laneTraceWaves > 0 ? 2 : 1) * traceGridBlocks(dev) * TWK_TRACE_BLOCK;
-  if (lanes > dev->spillLanes)
-  {
-    freeDevice(dev->d_spill);
-    HIP_TRY(hipMalloc(&dev->d_spill, lanes * TWK_TRACE_STACK_SPILL * sizeof(int)));
-    dev->spillLanes = lanes;
-  }
+  if ((rc = growBuffers(dev, dev->spillLanes, lanes, {{dev->d_spill, TWK_TRACE_STACK_SPILL * sizeof(int)}}))) return rc;
 
-  // carve the block
-  LaunchParams& p = dev->params;
-  const size_t n = (size_t) dev->allocatedPaths;
-  char* base = static_cast<char*>(dev->d_streamBlock);
-  auto take = [&](size_t elemBytes) { char* r = base; base += (n + TWK_STREAM_PAD) * elemBytes; return r; };
-  p.rayOrg[0] = (float4*) take(16); p.rayOrg[1] = (float4*) take(16);
-  p.rayDir[0] = (float4*) take(16); p.rayDir[1] = (float4*) take(16);
-  p.hitRecord = (float4*) take(16);
-  p.shadowOrg = (float4*) take(16); p.shadowDir = (float4*) take(16); p.shadowPending = (float4*) take(16);
-  p.rayThroughput[0] = (float4*) take(16); p.rayThroughput[1] = (float4*) take(16); p.pathRadiance = (float4*) take(16);
-  p.volumeStack = (float4*) take(64);
-  p.raySeedFlags[0] = (uint2*) take(8); p.raySeedFlags[1] = (uint2*) take(8);
-  p.rayPixel[0] = (unsigned int*) take(4); p.rayPixel[1] = (unsigned int*) take(4);
-  p.hitInstance = (int*) take(4);
-  p.shadowPixel = (unsigned int*) take(4);
-  p.overflowSlots = (unsigned int*) take(8);
+  carvePathStreams(dev->params, dev->d_streamBlock, (size_t) dev->allocatedPaths + TWK_STREAM_PAD);
   return TWK_SUCCESS;
 }
 
@@ -592,7 +555,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count);
 
 static int flushPending(TwkDevice dev)
 {
-  // The streams of a pass take 280 bytes per pixel and iteration. When they do not fit in device memory the pass is
+  // The streams of a pass take kPathStreamBytes (device_types.h) per pixel and iteration. When they do not fit in device memory the pass is
   // cut in halves until they do (the image does not depend on how iterations are grouped) and the handle keeps the
   // smaller limit; only an allocation failure for a single iteration is reported.
   unsigned int first = dev->pendingFirst;
@@ -647,16 +610,10 @@ static LaunchParams laneParams(TwkDevice dev, const LaunchParams& p, int lane, i
   // the queue arrays of a lane reach beyond its path count (the gaps between a queue's segments): their bases leave room for that
   const size_t queueBase = (size_t) lane * (share + TWK_LANE_QUEUE_PAD);
   assert(queueBase + (size_t) TWK_QUEUE_SEGMENTS * q.queueStride <= (size_t) dev->allocatedPaths + TWK_STREAM_PAD); // the lane's segments end inside the stream block
-  for (int k = 0; k < 2; ++k)
-  {
-    q.rayOrg[k] += queueBase; q.rayDir[k] += queueBase; q.rayPixel[k] += queueBase; q.rayThroughput[k] += queueBase; q.raySeedFlags[k] += queueBase;
-  }
-  q.hitRecord += base; q.hitInstance += base;
-  q.shadowOrg += queueBase; q.shadowDir += queueBase; q.shadowPixel += queueBase; q.shadowPending += queueBase;
-  q.pathRadiance += base; q.overflowSlots += 2 * base;
-  q.volumeStack += 4 * base; // [4][numPaths of the lane], indexed level * numPaths + path (shade_device.h)
-  if (q.pathAlbedo) { q.pathAlbedo += base; q.pathNormal += base; }
-  if (q.pathTime) q.pathTime += base;
+  const size_t startQUEUE = queueBase, startPATH = base; // by the index of a stream (device_types.h TWK_PATH_STREAMS)
+#define TWK_LANE_SLICE(member, type, perPath, index) if (q.member) q.member += (perPath) * start##index; // (an optional stream that is off stays nullptr)
+  TWK_PATH_STREAMS(TWK_LANE_SLICE) TWK_OPTIONAL_PATH_STREAMS(TWK_LANE_SLICE)
+#undef TWK_LANE_SLICE
   q.counters = dev->d_counters + (size_t) lane * TWK_COUNTER_WORDS;
   q.traceStackSpill = dev->d_spill + (size_t) lane * traceBlocks * TWK_TRACE_BLOCK * TWK_TRACE_STACK_SPILL;
   return q;
@@ -2169,11 +2126,12 @@ try
   if (rc) return twkSetError(rc, "twk_debug_snapshot_scene: device-to-host copy failed");
   // streams, counters, outputs: the host build allocates its own
   q.tileEntries = nullptr; q.tilesX = 0;
-  for (int k = 0; k < 2; ++k) { q.rayOrg[k] = nullptr; q.rayDir[k] = nullptr; q.rayPixel[k] = nullptr; q.rayThroughput[k] = nullptr; q.raySeedFlags[k] = nullptr; }
-  q.hitRecord = nullptr; q.hitInstance = nullptr; q.shadowOrg = nullptr; q.shadowDir = nullptr; q.shadowPixel = nullptr; q.shadowPending = nullptr;
-  q.pathRadiance = nullptr; q.volumeStack = nullptr; q.pathAlbedo = nullptr; q.pathNormal = nullptr; q.aovAlbedo = nullptr; q.aovNormal = nullptr;
+#define TWK_STREAM_CLEAR(member, type, perPath, index) q.member = nullptr;
+  TWK_PATH_STREAMS(TWK_STREAM_CLEAR) TWK_OPTIONAL_PATH_STREAMS(TWK_STREAM_CLEAR)
+#undef TWK_STREAM_CLEAR
+  q.aovAlbedo = nullptr; q.aovNormal = nullptr;
   q.output = nullptr; q.counters = nullptr; q.stats = nullptr; q.firstHit = nullptr; q.firstHitInstance = nullptr; q.traceStackSpill = nullptr;
-  q.overflowSlots = nullptr; q.droppedPushes = nullptr;
+  q.droppedPushes = nullptr;
   memcpy(launchParams, &q, sizeof(q));
   return TWK_SUCCESS;
 }

@@ -311,6 +311,21 @@ enum { TWK_AOV_ALBEDO = 0, TWK_AOV_NORMAL = 1 };
 int twk_enable_aov(TwkDevice dev, int enable);
 int twk_read_aov(TwkDevice dev, int which, float* rgbaHost, size_t numFloats);
 
+/* Luminance moments of the integrator's samples, an AOV for the denoiser (twk_denoise_variance_sampled) — new calls, ABI stays 9.
+ * While enabled, the kernel that folds a pass's samples into the running mean folds, in the same read, Welford's recurrence over
+ * the luminance l = 0.2126 r + 0.7152 g + 0.0722 b of every sample it keeps (the ones the running mean keeps: NaN samples are
+ * dropped, or replaced by their false colour under twk_set_debug_exceptions) — per sample, in iteration order, n = n + 1;
+ * d = l - mean; mean = mean + d / n; M2 = M2 + d (l - mean) — into one float4 (mean, M2, n, 0) per launch index, laid out
+ * like the AOVs (launchWidth x height, also under twk_set_shared_frame) and ALWAYS f32, in TWK_OUTPUT_HALF4 mode too (the square
+ * of a half-range luminance does not fit a half). A kept sample of iteration 0 starts the triple afresh. M2 / (n - 1) is the
+ * sample variance of the luminance, M2 / ((n - 1) n) the variance of the pixel's mean. A sample that is not finite makes the
+ * triple not finite. The result does not depend on twk_set_launch_batch or on how a pass is cut into lanes. The operations and
+ * their order: csrc/shade_device.h foldSamples. twk_enable_moments(1) allocates the buffer, zeroed (with twk_set_state, whichever
+ * comes later); (0) frees it. With moments off nothing changes: the builds of the kernels without them run. */
+int twk_enable_moments(TwkDevice dev, int enable);
+int twk_read_moments(TwkDevice dev, float* host, size_t numFloats); /* launchWidth*height*4 floats; synchronises */
+int twk_get_moments_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+
 /* ABI 6. Time view, ≙ the reference's compile-time USE_TIME_VIEW (apps/rtigo3/shaders/config.h:60, raygeneration.cu:169-171,
  * 231-244, Device.h:350): while enabled the ALPHA of the accumulation buffer is not 1 but the running mean of
  * (shader-clock cycles the sample's lanes spent in traversal and shading) x TwkDeviceState::clockFactor x 1e-9 — what
@@ -444,6 +459,20 @@ typedef struct TwkDenoiserVariance
 int twk_denoiser_variance_defaults(TwkDenoiserVariance* dv);
 int twk_denoise_variance(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo,
                          const void* normal, int width, int height, void* denoised);
+/* twk_denoise_variance with the MEASURED variance where the integrator has seen enough samples — SVGF's rule the other way
+ * round: that paper falls back to the spatial estimate where it has no history, and a progressive renderer always has some.
+ * `moments` holds width x height float4 (mean, M2, n, .) as twk_enable_moments accumulates them. In the moments pass, a pixel with
+ * n >= minSamples, finite mean, M2 and n, and mean > 0 gets var = M2 / ((n - 1) n) x rho^2 x f^2 — the variance of the pixel's
+ * mean, taken into the space the levels filter in: rho = l_p / mean with demodulateAlbedo (l_p the luminance of the demodulated
+ * colour before the clamp), else 1; f the factor the firefly clamp scaled the pixel by, 1 without. Every other pixel keeps the
+ * spatial estimate. The clamp itself stays spatial (a firefly must not vouch for itself). Everything else is
+ * twk_denoise_variance's, bit for bit; with every pixel below minSamples the result is twk_denoise_variance's. beauty NULL (then
+ * albedo, normal and moments must be NULL too): the handle's own buffers and its own moments — needs a render with
+ * twk_enable_moments(1); a packed tile buffer is refused, and so is minSamples < 2. What it is not: a learned filter, a temporal
+ * one (one frame's samples, no reprojection), or per-sample moments of the demodulated colour (rho rescales the moments of the
+ * beauty's luminance). The float operations and their order: csrc/denoise_device.h. */
+int twk_denoise_variance_sampled(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, int minSamples, const void* beauty,
+                                 const void* albedo, const void* normal, const void* moments, int width, int height, void* denoised);
 int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats);        /* RGBA32F, widened exactly, like twk_read_output */
 int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes);             /* in the output format */
 int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes); /* feeds twk_tonemap / twk_tonemap_half */
@@ -465,6 +494,12 @@ int twk_gather_peak(TwkDevice dev, size_t tableBytes, float* gigaLaneLoadsPerSec
  * Requires twk_debug_capture(dev, 1) before the launch. prim/inst = -1 on miss. */
 int twk_debug_capture(TwkDevice dev, int enable);
 int twk_debug_read_first_hits(TwkDevice dev, float* tBetaGamma /*3 per px*/, int* instPrim /*2 per px*/, size_t numPixels);
+
+/* The raw samples of the last wavefront pass as its accumulate kernel read them: [samples of the pass][launchWidth*height] float4
+ * (radiance rgb, w = 0 for a launch index outside the image), sample s of the pass being iteration (first iteration of the pass)
+ * + s. Deferred launches are rendered first; synchronises. TWK_ERROR_INVALID_STATE before any pass, and after a call that
+ * overwrote the path streams (twk_debug_trace_queue, a reallocation). The tests of the luminance moments fold these. */
+int twk_debug_read_path_radiance(TwkDevice dev, float* host, size_t numFloats);
 
 /* Which builds of the shade kernel ran. The dispatcher picks one of 128 launcher slots per shade launch from seven flags: bit 0
  * ENV (spherical environment), 1 TEX (some material has an albedo texture), 2 PRIMARY (first launch of a pass that computes its
@@ -555,6 +590,11 @@ int twk_app_get_denoiser(TwkApp app, int* enabled, TwkDenoiser* dn);
  * twk_denoise_variance in place of twk_denoise (it takes effect when "denoiser" is on), and its parameters
  * (twk_denoiser_variance_defaults where a key is absent). */
 int twk_app_get_denoiser_variance(TwkApp app, int* enabled, TwkDenoiserVariance* dv);
+/* "denoiserSampledVariance 0|1" (default 0), "denoiserMinSamples n" (n >= 2; default TWK_DENOISER_MIN_SAMPLES): *enabled = the
+ * description asks for twk_denoise_variance_sampled with *minSamples (it takes effect when "denoiser" is on, with the parameters of
+ * twk_app_get_denoiser_variance, whatever "denoiserVariance" says). twk_app_init_device enables the moments when the key asks. */
+#define TWK_DENOISER_MIN_SAMPLES 4
+int twk_app_get_denoiser_sampled(TwkApp app, int* enabled, int* minSamples);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

@@ -13,7 +13,9 @@ level count its ms per frame beside twk_denoise's, both timed in the same proces
 pass (its compulsory stream bytes: the colour read and written, one float4 per guide read) over the same stream-copy peak. The
 moments kernel's own time comes from a kernel trace of one child (rocprofv3 --kernel-trace --stats -- python tools/denoise_time.py
 --child 0 3 50 1), in a run of its own.
-usage (GPU box): python tools/denoise_time.py [--variance] [calls] > table.md"""
+With --sampled the same table compares twk_denoise_variance_sampled (the handle's own luminance moments, the default minSamples)
+with twk_denoise_variance, again in alternating windows: the expected extra is one 16-byte load per pixel in the moments pass.
+usage (GPU box): python tools/denoise_time.py [--variance | --sampled] [calls] > table.md"""
 import json
 import os
 import subprocess
@@ -27,7 +29,7 @@ RES = (1920, 1080)
 CHILD_SECONDS = 180
 
 
-def child(fmt, levels, calls, variance=False):
+def child(fmt, levels, calls, variance=False):  # variance: 0 / False twk_denoise alone, 1 beside twk_denoise_variance, 2 twk_denoise_variance beside twk_denoise_variance_sampled
     import tweeker_raytracer_amd as twk
     L = twk._lib
     scenes = os.path.join(ROOT, "scenes")
@@ -37,6 +39,8 @@ def child(fmt, levels, calls, variance=False):
     app.initDevice(dev)
     dev.setShaderVariant(1)
     dev.enableAov(True)
+    if variance == 2:
+        dev.enableMoments(True)
     dev.setOutputFormat(fmt)
     for it in range(4):
         dev.render(it)
@@ -44,17 +48,23 @@ def child(fmt, levels, calls, variance=False):
     peak = dev.streamPeakGBps(1 << 30, 10)
     dn = L.Denoiser(iterations=levels)
 
+    def denoise(dv):
+        if dv == "sampled":
+            dev.denoise(dn, variance=L.DenoiserVariance(), moments=True)
+        else:
+            dev.denoise(dn, variance=dv)
+
     def window(dv):
         t0 = time.perf_counter()
         for _ in range(calls):
-            dev.denoise(dn, variance=dv)
+            denoise(dv)
         dev.synchronizeStream()
         return (time.perf_counter() - t0) * 1e3 / calls
 
-    modes = [None, L.DenoiserVariance()] if variance else [None]
+    modes = [L.DenoiserVariance(), "sampled"] if variance == 2 else ([None, L.DenoiserVariance()] if variance else [None])
     for dv in modes:
         for _ in range(5):
-            dev.denoise(dn, variance=dv)
+            denoise(dv)
     dev.synchronizeStream()
     windows = [[window(dv) for dv in modes] for _ in range(3 if variance else 1)]  # alternating: plain, variance, plain, ...
     ms = min(w[0] for w in windows) if variance else windows[0][0]
@@ -85,14 +95,25 @@ def run_child(fmt, levels, calls, lds_max_step=None, variance=False):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def main_variance(calls):
+def main_variance(calls, sampled=False):
     rows = []
     for fmt in (0, 1):
         for levels in (3, 5):
-            row = run_child(fmt, levels, calls, variance=True)
+            row = run_child(fmt, levels, calls, variance=2 if sampled else 1)
             if row is None:
                 return 1
             rows.append(row)
+    if sampled:
+        print(f"twk_denoise_variance_sampled beside twk_denoise_variance, {RES[0]}x{RES[1]}, inputKind RGB_ALBEDO_NORMAL, demodulated, the smaller of 3 alternating windows of {calls} calls + 1 sync each, after 5 warm-up calls\n")
+        print("| format | levels | twk_denoise_variance ms | twk_denoise_variance_sampled ms | ratio | extra load bytes | its floor ms |")
+        print("|---|---|---|---|---|---|---|")
+        for r in rows:
+            extra = RES[0] * RES[1] * 16
+            print(f"| {r['format']} | {r['levels']} | {r['ms_per_frame']:.3f} | {r['ms_per_frame_variance']:.3f} | {r['ms_per_frame_variance'] / r['ms_per_frame']:.3f} | {extra / 1e6:.0f} MB | {extra / (r['stream_peak_gbps'] * 1e9) * 1e3:.4f} |")
+        print("\nevery window, ms per frame (twk_denoise_variance, twk_denoise_variance_sampled):\n")
+        for r in rows:
+            print(f"- {r['format']}, {r['levels']} levels: " + "; ".join(f"{a:.3f}, {b:.3f}" for a, b in r["windows"]))
+        return 0
     print(f"twk_denoise_variance beside twk_denoise, {RES[0]}x{RES[1]}, inputKind RGB_ALBEDO_NORMAL, demodulated, the smaller of 3 alternating windows of {calls} calls + 1 sync each, after 5 warm-up calls\n")
     print("| format | levels | twk_denoise ms | twk_denoise_variance ms | ratio | stream peak GB/s | moments stream bytes | floor ms (moments) |")
     print("|---|---|---|---|---|---|---|---|")
@@ -107,10 +128,12 @@ def main_variance(calls):
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        child(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), len(sys.argv) > 5 and sys.argv[5] == "1")
+        child(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]) if len(sys.argv) > 5 else 0)
         return 0
-    argv = [a for a in sys.argv[1:] if a != "--variance"]
+    argv = [a for a in sys.argv[1:] if a not in ("--variance", "--sampled")]
     calls = int(argv[0]) if argv else 100
+    if "--sampled" in sys.argv[1:]:
+        return main_variance(calls, sampled=True)
     if "--variance" in sys.argv[1:]:
         return main_variance(calls)
     rows = []

@@ -23,6 +23,7 @@ TWK_ERROR_INVALID_STATE, TWK_ERROR_OUT_OF_MEMORY, TWK_ERROR_IO, TWK_ERROR_PARSE 
 TWK_OUTPUT_FLOAT4, TWK_OUTPUT_HALF4 = 0, 1  # twk_set_output_format: RGBA32F (default), RGBA16F (≙ Optix7Gui USE_FP32_OUTPUT 0)
 
 TWK_DENOISER_RGB, TWK_DENOISER_RGB_ALBEDO, TWK_DENOISER_RGB_ALBEDO_NORMAL = 0, 1, 2  # TwkDenoiser.inputKind: the guides that weigh the taps
+TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_variance_sampled (include/tweeker_hip.h)
 
 f3 = C.c_float * 3
 f2 = C.c_float * 2
@@ -133,6 +134,7 @@ SYMBOLS = [
     "twk_app_get_output_format",
     "twk_denoiser_defaults", "twk_denoise", "twk_read_denoised", "twk_read_denoised_raw", "twk_get_denoised_device_pointer", "twk_app_get_denoiser",
     "twk_denoiser_variance_defaults", "twk_denoise_variance", "twk_app_get_denoiser_variance",
+    "twk_enable_moments", "twk_read_moments", "twk_get_moments_device_pointer", "twk_debug_read_path_radiance", "twk_denoise_variance_sampled", "twk_app_get_denoiser_sampled",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

@@ -115,6 +115,14 @@ class Application:
         return bool(on.value), dv
 
     @property
+    def denoiserSampled(self):
+        """(enabled, minSamples) from "denoiserSampledVariance", "denoiserMinSamples" of the system description: enabled =
+        twk_denoise_variance_sampled stands in where `denoiser` is on; initDevice enables the device's moments then."""
+        on, n = C.c_int(0), C.c_int(0)
+        L.check(L.lib.twk_app_get_denoiser_sampled(self._h, C.byref(on), C.byref(n)))
+        return bool(on.value), n.value
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

@@ -69,6 +69,24 @@
 //     sum.k = sum.k + w * cq.k;  wsum = wsum + w;  vsum = vsum + (w * w) * cq.w
 //   out[p] = (sum.x / wsum, sum.y / wsum, sum.z / wsum, vsum / (wsum * wsum))
 //   wsum >= 9/64 still: the centre's own tap has t = 0 * invL = 0, lp being finite.
+//
+// ---- the sampled variance (twk_denoise_variance_sampled) -------------------------------------------------------------------
+// SVGF's rule the other way round: where the integrator has seen enough samples of a pixel, the variance the levels are guided
+// by is the MEASURED variance of the pixel's mean, from the luminance moments the accumulate kernels fold (shade_device.h
+// foldSamples: one float4 (mean, M2, n, 0) per pixel, Welford over the luminance of the raw samples); elsewhere the spatial
+// estimate above stays (SVGF section 4.2 falls back the same way). Everything is the variance-guided mode except the value the
+// moments pass writes into .w. tests/test_gpu_denoise_sampled.py restates it in numpy float32 and compares bits.
+//
+// moments pass, SAMPLED build, for a pixel that reaches the sums (finiteV(cp) and finite guides; the early (cp.xyz, 0) stays):
+//   var, and the clamp factor f, as above; f = 1 where no clamp applied, var = 0 and f = 1 where no tap counted (s0 == 0)
+//   (mean, M2, n, .) = moments[p]                                                    (one more coalesced 16-byte load)
+//   if n >= minSamples and mean, M2, n are finite and mean > 0:
+//     v = M2 / ((n - 1) * n)                                   (variance of the mean of n samples; minSamples >= 2, so n - 1 >= 1)
+//     demodulate:  rho = lum(cp) / mean  (cp BEFORE the clamp);  v = v * (rho * rho)       (into the demodulated space of the levels)
+//     var = v * (f * f)                                                                  (the clamp scaled the colour by f)
+//   out[p] = (cp.xyz clamped as above, var)
+// The clamp itself stays spatial: a firefly raises its own sample variance and must not vouch for itself. A product that
+// overflows gives an infinite (0 * inf: NaN) var, which the levels' variance blur skips like any other that is not finite.
 #pragma once
 #include "device_math.h"
 
@@ -123,7 +141,7 @@ TWK_HD void denoiseTap(const DenoiseConstants& k, int dx, int dy, const float4& 
 
 TWK_HD bool finite1(float v) { return (asUint(v) & 0x7f800000u) != 0x7f800000u; }
 
-TWK_HD float luminance(const float4& c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+TWK_HD float luminance(const float4& c) { return luminance3(c.x, c.y, c.z); } // (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z
 
 // One tap of the moments pass: folds the luminance lq of a tap with a finite colour into s0, s1, s2
 template<int KIND>
@@ -140,20 +158,35 @@ TWK_HD void momentsTap(const DenoiseConstants& k, const float4& np, const float4
   s0 = s0 + g; s1 = s1 + g * lq; s2 = s2 + g * (lq * lq);
 }
 
-// The end of the moments pass: variance and firefly clamp of the centre cp from the sums; returns (cp.xyz clamped, var)
-TWK_HD float4 momentsFinish(const DenoiseConstants& k, float4 cp, float s0, float s1, float s2)
+// The end of the moments pass: variance and firefly clamp of the centre cp from the sums; returns (cp.xyz clamped, var).
+// SAMPLED: m = the pixel's luminance moments (mean, M2, n, .); the measured variance of the mean replaces var where n >= minSamples
+template<bool SAMPLED = false>
+TWK_HD float4 momentsFinish(const DenoiseConstants& k, float4 cp, float s0, float s1, float s2, const float4 m = float4(), float minSamples = 0.0f)
 {
-  if (!(s0 > 0.0f)) return make_float4(cp.x, cp.y, cp.z, 0.0f);
-  const float m1 = s1 / s0, m2 = s2 / s0;
-  const float var = fmaxf(m2 - m1 * m1, 0.0f);
-  if (k.fireflyThreshold > 0.0f)
+  float var = 0.0f, f = 1.0f;
+  const float4 c0 = cp;
+  if (s0 > 0.0f)
   {
-    const float limit = m1 + k.fireflyThreshold * sqrtf(var);
-    const float lp = luminance(cp);
-    if (lp > limit && limit > 0.0f)
+    const float m1 = s1 / s0, m2 = s2 / s0;
+    var = fmaxf(m2 - m1 * m1, 0.0f);
+    if (k.fireflyThreshold > 0.0f)
     {
-      const float f = limit / lp;
-      cp.x = cp.x * f; cp.y = cp.y * f; cp.z = cp.z * f;
+      const float limit = m1 + k.fireflyThreshold * sqrtf(var);
+      const float lp = luminance(cp);
+      if (lp > limit && limit > 0.0f)
+      {
+        f = limit / lp;
+        cp.x = cp.x * f; cp.y = cp.y * f; cp.z = cp.z * f;
+      }
+    }
+  }
+  if (SAMPLED)
+  {
+    if (m.z >= minSamples && finite1(m.x) && finite1(m.y) && finite1(m.z) && m.x > 0.0f)
+    {
+      float v = m.y / ((m.z - 1.0f) * m.z);
+      if (k.demodulate) { const float rho = luminance(c0) / m.x; v = v * (rho * rho); }
+      var = v * (f * f);
     }
   }
   return make_float4(cp.x, cp.y, cp.z, var);

@@ -1,4 +1,4 @@
-// Kernels of twk_denoise and twk_denoise_variance: the edge-avoiding a-trous wavelet filter defined in denoise_device.h (prepare, the
+// Kernels of twk_denoise, twk_denoise_variance and twk_denoise_variance_sampled: the edge-avoiding a-trous wavelet filter defined in denoise_device.h (prepare, the
 // moments pass of the variance-guided mode, one launch per level, finish). Stands where Optix7Gui calls optixDenoiserInvoke (apps/Optix7Gui/src/Application.cpp:942-1001).
 #include "denoise_device.h"
 #include "pixel_formats.h"
@@ -186,9 +186,11 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
 // another stream: neighbours read the unclamped value.
 #define TWK_DENOISE_MOMENTS_X (TWK_DENOISE_TILE_X + 2 * TWK_DENOISE_MOMENTS_RADIUS)
 #define TWK_DENOISE_MOMENTS_Y (TWK_DENOISE_TILE_Y + 2 * TWK_DENOISE_MOMENTS_RADIUS)
-template<int KIND>
+// SAMPLED (twk_denoise_variance_sampled): one more coalesced load per pixel, its luminance moments (mean, M2, n, .) as the
+// accumulate kernels fold them; momentsFinish writes the measured variance of the pixel's mean where n >= minSamples.
+template<int KIND, bool SAMPLED>
 __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
-                                                            float4* __restrict__ out, DenoiseConstants k)
+                                                            float4* __restrict__ out, DenoiseConstants k, const float4* __restrict__ sampled, float minSamples)
 {
   constexpr int STAGED = TWK_DENOISE_MOMENTS_X * TWK_DENOISE_MOMENTS_Y;
   __shared__ float  lum[STAGED];
@@ -240,7 +242,8 @@ __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __rest
       momentsTap<KIND>(k, np, ap, lq, nq, aq, s0, s1, s2);
     }
   }
-  out[p] = momentsFinish(k, cp, s0, s1, s2);
+  if (SAMPLED) out[p] = momentsFinish<true>(k, cp, s0, s1, s2, sampled[p], minSamples);
+  else         out[p] = momentsFinish(k, cp, s0, s1, s2);
 }
 
 template<typename Pixel> struct PixelOf;
@@ -317,13 +320,23 @@ void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, con
   else                                        launchDenoiseLevelOf<TWK_DENOISER_RGB, false>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
 }
 
-// the moments + firefly-clamp pass of the variance-guided mode, between prepare and level 0
-void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, hipStream_t stream)
+template<bool SAMPLED>
+static void launchDenoiseMomentsOf(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k,
+                                   const float4* sampled, float minSamples, hipStream_t stream)
 {
   const dim3 grid((k.width + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X, (k.height + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y);
-  if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL(denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k);
-  else if (kind == TWK_DENOISER_RGB_ALBEDO)   hipLaunchKernelGGL(denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k);
-  else                                        hipLaunchKernelGGL(denoiseMomentsKernel<TWK_DENOISER_RGB>, grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k);
+  if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples);
+  else if (kind == TWK_DENOISER_RGB_ALBEDO)   hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples);
+  else                                        hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples);
+}
+
+// the moments + firefly-clamp pass of the variance-guided mode, between prepare and level 0. sampled != NULL: the SAMPLED build —
+// width x height luminance moments (mean, M2, n, .), whose measured variance stands in for the spatial one from minSamples samples on
+void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k,
+                          const float4* sampled, float minSamples, hipStream_t stream)
+{
+  if (sampled) launchDenoiseMomentsOf<true>(kind, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, stream);
+  else         launchDenoiseMomentsOf<false>(kind, in, guideNormal, guideAlbedo, out, k, nullptr, 0.0f, stream);
 }
 
 // guideNormal / guideAlbedo NULL: the kind does not use the guide

@@ -42,7 +42,7 @@ void launchGatherProbe(const float4* table, unsigned int lines, int steps, float
 void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
 void launchDenoisePrepare(const void* beauty, const void* albedo, const void* normal, bool half, float4* colour, float4* guideNormal, float4* guideAlbedo,
                           const DenoiseConstants& k, hipStream_t stream);
-void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, hipStream_t stream);
+void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, const float4* sampled, float minSamples, hipStream_t stream);
 void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
 }
@@ -152,6 +152,9 @@ struct TwkDevice_t
   bool timeView = false; float* d_pathTime = nullptr; int timePaths = 0; // twk_set_time_view
   float4* d_pathAlbedo = nullptr; float4* d_pathNormal = nullptr; int aovPaths = 0;
   float4* d_aovAlbedo = nullptr; float4* d_aovNormal = nullptr; int aovPixels = 0;
+  // twk_enable_moments: luminance moments (mean, M2, n, 0) of the samples per launch index, always f32 (LaunchParams::moments)
+  bool momentsEnabled = false; float4* d_moments = nullptr; int momentsPixels = 0;
+  int lastPassCount = 0, lastPassPixels = 0; // samples per launch index and launch indices of the last pass, while its pathRadiance stream still holds them (twk_debug_read_path_radiance); 0: none
   // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) in the output format it was
   // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
   void* d_denoised = nullptr; int denoisedWidth = 0, denoisedHeight = 0, denoisedFormat = TWK_OUTPUT_FLOAT4; bool denoisedValid = false;
@@ -355,6 +358,7 @@ static void refreshParams(TwkDevice dev)
   p.nextEventEstimation = dev->nextEventEstimation ? 1 : 0; p.debugExceptions = dev->debugExceptions ? 1 : 0;
   p.pathAlbedo = dev->aovEnabled ? dev->d_pathAlbedo : nullptr; p.pathNormal = dev->aovEnabled ? dev->d_pathNormal : nullptr;
   p.aovAlbedo  = dev->aovEnabled ? dev->d_aovAlbedo : nullptr;  p.aovNormal  = dev->aovEnabled ? dev->d_aovNormal : nullptr;
+  p.moments = dev->momentsEnabled ? dev->d_moments : nullptr;
   p.firstHit = dev->captureFirstHits ? dev->d_firstHit : nullptr;
   p.firstHitInstance = dev->captureFirstHits ? dev->d_firstHitInstance : nullptr;
   p.traceStackSpill = dev->d_spill;
@@ -414,7 +418,7 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
   if ((rc = growBuffers(dev, dev->allocatedPixels, numPixels, {{dev->d_outputInternal, pixelBytes(dev), true}, {dev->d_firstHit, sizeof(float4)}, {dev->d_firstHitInstance, sizeof(int)}}))) return rc;
   if (numPaths > dev->allocatedPaths || dev->d_streamBlock == nullptr)
   {
-    freeDevice(dev->d_streamBlock);
+    freeDevice(dev->d_streamBlock); dev->lastPassCount = 0;
     // kPathStreamBytes per path (device_types.h TWK_PATH_STREAMS) + TWK_STREAM_PAD slots per stream: the segments of a queue leave gaps between them
     const size_t n = (size_t) numPaths, bytes = (n + TWK_STREAM_PAD) * kPathStreamBytes + 4096;
     if (dev->streamBudgetBytes != 0 && n * kPathStreamBytes > dev->streamBudgetBytes) // (the budget is for what grows with the pass, not for the fixed padding)
@@ -428,6 +432,7 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
     if ((rc = growBuffers(dev, dev->aovPaths, dev->allocatedPaths, {{dev->d_pathAlbedo, sizeof(float4)}, {dev->d_pathNormal, sizeof(float4)}}))) return rc;
     if ((rc = growBuffers(dev, dev->aovPixels, dev->allocatedPixels, {{dev->d_aovAlbedo, pixelBytes(dev), true}, {dev->d_aovNormal, pixelBytes(dev), true}}))) return rc;
   }
+  if (dev->momentsEnabled && (rc = growBuffers(dev, dev->momentsPixels, dev->allocatedPixels, {{dev->d_moments, sizeof(float4), true}}))) return rc;
   if (!dev->d_counters) HIP_TRY(hipMalloc(&dev->d_counters, sizeof(unsigned int) * TWK_COUNTER_WORDS * TWK_MAX_LANES));
   if (!dev->d_stats) { HIP_TRY(hipMalloc(&dev->d_stats, sizeof(unsigned long long) * TWK_STATS_WORDS)); HIP_TRY(hipMemsetAsync(dev->d_stats, 0, sizeof(unsigned long long) * TWK_STATS_WORDS, dev->stream)); } // TwkLaunchStats words (24 + the shade phases' 3 x 24) + a scratch block of the same size for the time view
   if (!dev->h_dropped)
@@ -738,6 +743,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
   // the running mean folds the samples of the pass in iteration order over ALL lanes' paths: after the join, on the handle's stream
   timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
+  dev->lastPassCount = count; dev->lastPassPixels = p.numPixels;
   return TWK_SUCCESS;
 }
 
@@ -832,7 +838,7 @@ try
   freeDevice(dev->d_counters); freeDevice(dev->d_stats); freeDevice(dev->d_spill); freeDevice(dev->d_pathTime);
   if (dev->h_dropped) { (void) hipHostFree(dev->h_dropped); dev->h_dropped = nullptr; dev->d_dropped = nullptr; }
   freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
-  freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal);
+  freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); freeDevice(dev->d_moments);
   freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams);
   dev->builder.release();
   for (int k = 1; k < TWK_MAX_LANES; ++k)
@@ -1454,6 +1460,44 @@ try
 }
 TWK_CATCH("twk_enable_aov")
 
+int twk_enable_moments(TwkDevice dev, int enable)
+try
+{
+  int rc = activate(dev, "twk_enable_moments"); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  dev->momentsEnabled = (enable != 0);
+  if (!dev->momentsEnabled) { freeDevice(dev->d_moments); dev->momentsPixels = 0; return TWK_SUCCESS; } // enabled again: a zeroed buffer
+  return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first pass after twk_set_state
+}
+TWK_CATCH("twk_enable_moments")
+
+int twk_read_moments(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_moments"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_moments: NULL buffer");
+  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_moments: buffer must hold launchWidth*height*4 floats");
+  if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_moments: twk_enable_moments(1) and twk_set_state first");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_moments, n * sizeof(float4), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_moments")
+
+int twk_get_moments_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
+try
+{
+  int rc = activate(dev, "twk_get_moments_device_pointer"); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_moments_device_pointer: NULL argument");
+  if (!dev->momentsEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_moments_device_pointer: twk_enable_moments(1) and twk_set_state first");
+  if ((rc = ensureStreams(dev))) return rc;
+  *dptr = dev->d_moments;
+  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(float4);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_moments_device_pointer")
+
 int twk_set_time_view(TwkDevice dev, int enable)
 try
 {
@@ -1628,16 +1672,20 @@ try
 }
 TWK_CATCH("twk_denoiser_defaults")
 
-static bool overlaps(const void* a, const void* b, size_t bytes)
+static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
 {
   if (!a || !b) return false;
   const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-  return x < y + bytes && y < x + bytes;
+  return x < y + bBytes && y < x + aBytes;
 }
+static bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
 
-// twk_denoise (dv NULL) and twk_denoise_variance: `name` is the entry point, for its error texts
-static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
+// twk_denoise (dv NULL), twk_denoise_variance and twk_denoise_variance_sampled (minSamples > 0; `moments`: the caller's buffer
+// beside an explicit beauty): `name` is the entry point, for its error texts
+static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised,
+                   int minSamples = 0, const void* moments = nullptr)
 {
+  const bool sampled = (minSamples > 0);
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
   const int kind = dn->inputKind;
   if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "unknown inputKind");
@@ -1662,7 +1710,7 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
   const bool own = (beauty == nullptr);
   if (own)
   {
-    if (albedo || normal) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
+    if (albedo || normal || moments) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
     if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
     if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
     beauty = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
@@ -1675,6 +1723,12 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
       albedo = dev->d_aovAlbedo;
       if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = dev->d_aovNormal;
     }
+    if (sampled)
+    {
+      if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < (size_t) width * height)
+        return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+      moments = dev->d_moments;
+    }
   }
   else
   {
@@ -1682,9 +1736,10 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     if ((kind >= TWK_DENOISER_RGB_ALBEDO && !albedo) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !normal)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL guide buffer for a guide the inputKind uses");
     if (kind < TWK_DENOISER_RGB_ALBEDO) albedo = nullptr;        // guides the kind does not use are not read
     if (kind < TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = nullptr;
+    if (sampled && !moments) return refuse(TWK_ERROR_INVALID_VALUE, "NULL moments buffer beside an explicit beauty buffer");
   }
   const size_t numPixels = (size_t) width * height, bytes = numPixels * pixelBytes(dev);
-  if (denoised && (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes)))
+  if (denoised && (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes) || (sampled && overlaps(denoised, bytes, moments, numPixels * sizeof(float4)))))
     return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
 
   void* target = denoised;
@@ -1727,7 +1782,7 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     // the variance-guided mode: prepare writes the pong stream and the moments pass the ping stream (clamped colour, variance in
     // .w), so that the levels ping-pong as without it and the mode needs no stream of its own
     launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[dv ? 1 : 0], guideNormal, guideAlbedo, k, dev->stream);
-    if (dv) launchDenoiseMoments(kind, colour[1], guideNormal, guideAlbedo, colour[0], k, dev->stream);
+    if (dv) launchDenoiseMoments(kind, colour[1], guideNormal, guideAlbedo, colour[0], k, sampled ? static_cast<const float4*>(moments) : nullptr, (float) minSamples, dev->stream);
     for (int level = 0; level < dn->iterations; ++level)
       launchDenoiseLevel(kind, (1 << level) <= dev->denoiseLdsMaxStep, dv != nullptr, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream);
     launchDenoiseFinish(beauty, halfOutput(dev), colour[dn->iterations & 1], normal ? guideNormal : nullptr, albedo ? guideAlbedo : nullptr, target, k, dev->stream);
@@ -1764,6 +1819,17 @@ try
   return denoise("twk_denoise_variance", dev, dn, dv, beauty, albedo, normal, width, height, denoised);
 }
 TWK_CATCH("twk_denoise_variance")
+
+int twk_denoise_variance_sampled(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, int minSamples, const void* beauty, const void* albedo, const void* normal,
+                                 const void* moments, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance_sampled: NULL device handle");
+  if (!dn || !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance_sampled: NULL parameters");
+  if (minSamples < 2) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance_sampled: minSamples must be >= 2 (one sample has no variance)");
+  return denoise("twk_denoise_variance_sampled", dev, dn, dv, beauty, albedo, normal, width, height, denoised, minSamples, moments);
+}
+TWK_CATCH("twk_denoise_variance_sampled")
 
 int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats)
 try
@@ -1932,6 +1998,20 @@ try
 }
 TWK_CATCH("twk_debug_capture")
 
+int twk_debug_read_path_radiance(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_debug_read_path_radiance"); if (rc) return rc; // deferred launches run first: the last pass is theirs
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_debug_read_path_radiance: NULL buffer");
+  if (dev->lastPassCount <= 0 || !dev->d_streamBlock) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_debug_read_path_radiance: no pass has been rendered (or its streams have been overwritten since)");
+  const size_t n = (size_t) dev->lastPassCount * dev->lastPassPixels;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_debug_read_path_radiance: buffer must hold " + std::to_string(dev->lastPassCount) + " x launchWidth*height*4 floats (the samples per launch index of the last pass)");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->params.pathRadiance, n * sizeof(float4), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_debug_read_path_radiance")
+
 int twk_debug_shade_builds(TwkDevice dev, uint64_t mask[2], int reset)
 try
 {
@@ -2014,6 +2094,7 @@ try
   const size_t pixels = (size_t) dev->launchWidth * (size_t) dev->state.resolution[1];
   if ((rc = ensureStreams(dev, (int) std::min<size_t>((n + pixels - 1) / pixels, (size_t) 1 << 30)))) return rc;
   if ((size_t) dev->allocatedPaths < n) return twkSetError(TWK_ERROR_OUT_OF_MEMORY, "twk_debug_trace_queue: path streams too small");
+  dev->lastPassCount = 0; // the streams of the last pass are overwritten below
   refreshParams(dev);
   LaunchParams p = dev->params;
   p.numPaths = dev->allocatedPaths; p.batchCount = 1; p.firstHit = nullptr; p.firstHitInstance = nullptr; p.pathTime = nullptr;
@@ -2129,7 +2210,7 @@ try
 #define TWK_STREAM_CLEAR(member, type, perPath, index) q.member = nullptr;
   TWK_PATH_STREAMS(TWK_STREAM_CLEAR) TWK_OPTIONAL_PATH_STREAMS(TWK_STREAM_CLEAR)
 #undef TWK_STREAM_CLEAR
-  q.aovAlbedo = nullptr; q.aovNormal = nullptr;
+  q.aovAlbedo = nullptr; q.aovNormal = nullptr; q.moments = nullptr;
   q.output = nullptr; q.counters = nullptr; q.stats = nullptr; q.firstHit = nullptr; q.firstHitInstance = nullptr; q.traceStackSpill = nullptr;
   q.droppedPushes = nullptr;
   memcpy(launchParams, &q, sizeof(q));

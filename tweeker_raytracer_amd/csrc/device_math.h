@@ -37,6 +37,10 @@ static const float kInvPi   = 0.318309886183790671538f; // M_1_PIf (vector_math.
 TWK_HD float    asFloat(uint32_t u) { union { uint32_t u; float f; } c; c.u = u; return c.f; }
 TWK_HD uint32_t asUint(float f)     { union { uint32_t u; float f; } c; c.f = f; return c.u; }
 
+// Luminance of linear rgb (Rec. 709 weights), in this order: what the denoiser's variance-guided mode filters by
+// (denoise_device.h luminance) and what the integrator's luminance moments are taken of (shade_device.h foldSamples).
+TWK_HD float luminance3(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
 // --- sin / cos -------------------------------------------------------------------------------
 TWK_HD void octantReduce(float ax, float& r, int& j)
 {

@@ -239,6 +239,9 @@ struct LaunchParams
   // 8 bytes less per path and bounce (TWK_SLIM_STREAMS=0 keeps the full layout). shadePath and the host build (oracle/) never see
   // it: the kernels around shadePath pack and unpack.
   int     slimSlotBits;
+  // Luminance moments of the samples (twk_enable_moments), nullptr when off: (mean, M2, n, 0) per launch index, indexed like
+  // aovAlbedo, always f32. Folded by the MOMENTS builds of the accumulate kernels (shade_device.h foldSamples).
+  float4* moments;
 };
 
 // Slim streams: the hit record's slot word <-> (triangle slot, instance). A miss is -1 on both sides.

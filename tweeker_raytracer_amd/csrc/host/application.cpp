@@ -132,6 +132,13 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && f[0] > 0.0f && std::isfinite(f[0])) denoiserSigmaLuminance = f[0];
       else if (ok) warnings.push_back("denoiserSigmaLuminance must be > 0 and finite, keeping the previous value");
     }
+    else if (key == "denoiserSampledVariance") { ok = readInt(parser, i[0]); if (ok) denoiserSampledVariance = (i[0] == 1) ? 1 : 0; }
+    else if (key == "denoiserMinSamples")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 2) denoiserMinSamples = i[0];
+      else if (ok) warnings.push_back("denoiserMinSamples must be >= 2, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -187,6 +194,8 @@ std::string Application::systemDescription() const
   if (denoiserVariance != 0) d << "denoiserVariance " << denoiserVariance << std::endl;
   if (denoiserFirefly != 3.0f) d << "denoiserFirefly " << denoiserFirefly << std::endl;
   if (denoiserSigmaLuminance != 4.0f) d << "denoiserSigmaLuminance " << denoiserSigmaLuminance << std::endl;
+  if (denoiserSampledVariance != 0) d << "denoiserSampledVariance " << denoiserSampledVariance << std::endl;
+  if (denoiserMinSamples != TWK_DENOISER_MIN_SAMPLES) d << "denoiserMinSamples " << denoiserMinSamples << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

@@ -95,6 +95,10 @@ public:
   int   denoiserVariance = 0;
   float denoiserFirefly = 3.0f;
   float denoiserSigmaLuminance = 4.0f;
+  // "denoiserSampledVariance" (1: twk_denoise_variance_sampled, the measured variance of the samples where a pixel has seen at
+  // least "denoiserMinSamples" of them), TWK_DENOISER_MIN_SAMPLES until a key sets it
+  int   denoiserSampledVariance = 0;
+  int   denoiserMinSamples = TWK_DENOISER_MIN_SAMPLES;
   int   shaderVariant = 0; // grammar extension "shaderVariant": 0 rtigo3, 1 Optix7Gui light-hit rule (include/tweeker_hip.h TWK_SHADERS_*)
   int   samplesSqrt   = 1;
   int   resolution[2] = {1, 1};

@@ -126,6 +126,17 @@ try
 }
 TWK_CATCH("twk_app_get_denoiser_variance")
 
+int twk_app_get_denoiser_sampled(TwkApp app, int* enabled, int* minSamples)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser_sampled: NULL app");
+  if (!enabled || !minSamples) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser_sampled: NULL argument");
+  *enabled = app->app.denoiserSampledVariance;
+  *minSamples = app->app.denoiserMinSamples;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_denoiser_sampled")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -219,6 +230,7 @@ try
   if ((rc = twk_set_debug_exceptions(dev, a.debugExceptions))) return rc;
   if ((rc = twk_set_output_format(dev, a.outputFormat))) return rc;
   if (a.denoiser > 1 && (rc = twk_enable_aov(dev, 1))) return rc; // "denoiser 2|3": the filter's guides are the AOVs
+  if (a.denoiser != 0 && a.denoiserSampledVariance && (rc = twk_enable_moments(dev, 1))) return rc; // "denoiserSampledVariance 1": the filter's variance is the samples'
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;
   if ((rc = twk_init_materials(dev, a.materials.data(), (int) a.materials.size()))) return rc;

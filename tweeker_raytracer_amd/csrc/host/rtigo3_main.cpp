@@ -135,6 +135,13 @@ int main(int argc, char* argv[])
   int denoiserVarianceEnabled = 0; // "denoiserVariance 1": the variance-guided, firefly-clamping mode of the filter
   TwkDenoiserVariance denoiserVariance;
   TWK_OK(twk_app_get_denoiser_variance(app, &denoiserVarianceEnabled, &denoiserVariance));
+  int denoiserSampledEnabled = 0, denoiserMinSamples = 0; // "denoiserSampledVariance 1": the measured variance of the samples guides the filter
+  TWK_OK(twk_app_get_denoiser_sampled(app, &denoiserSampledEnabled, &denoiserMinSamples));
+  if (denoiserEnabled && denoiserSampledEnabled && count > 1)
+  {
+    std::cerr << "ERROR: denoiserSampledVariance needs the luminance moments of ONE device; they are packed tile buffers on several and are not assembled\n";
+    return 1;
+  }
   if (denoiserEnabled && count > 1 && denoiser.inputKind != TWK_DENOISER_RGB)
   {
     std::cerr << "ERROR: denoiser " << denoiser.inputKind + 1 << " needs the albedo / normal AOVs of ONE device; with several devices only denoiser 1 (no guides) filters the assembled frame\n";
@@ -226,8 +233,9 @@ int main(int argc, char* argv[])
   {
     if (denoiserEnabled)
     {
-      if (denoiserVarianceEnabled) TWK_OK(twk_denoise_variance(devices[0], &denoiser, &denoiserVariance, frame, nullptr, nullptr, width, height, nullptr));
-      else                         TWK_OK(twk_denoise(devices[0], &denoiser, frame, nullptr, nullptr, width, height, nullptr));
+      if (denoiserSampledEnabled)       TWK_OK(twk_denoise_variance_sampled(devices[0], &denoiser, &denoiserVariance, denoiserMinSamples, frame, nullptr, nullptr, nullptr, width, height, nullptr)); // one device: frame is NULL, the handle's own buffers and moments
+      else if (denoiserVarianceEnabled) TWK_OK(twk_denoise_variance(devices[0], &denoiser, &denoiserVariance, frame, nullptr, nullptr, width, height, nullptr));
+      else                              TWK_OK(twk_denoise(devices[0], &denoiser, frame, nullptr, nullptr, width, height, nullptr));
       void* denoised = nullptr;
       TWK_OK(twk_get_denoised_device_pointer(devices[0], &denoised, nullptr));
       frame = denoised;

@@ -1014,8 +1014,19 @@ struct StoredAsFloat { TWK_HD float4 operator()(const float4 v) const { return v
 // iteration order, on the running means dst / dstAlbedo / dstNormal as read from the buffers. After every folded sample the
 // means become `stored(...)` of themselves, what the buffers would hold had the sample been written by a launch of its own, so
 // that a batch equals batchCount separate launches in either output format. Returns whether any sample was folded.
-template<typename Stored>
-TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored)
+//
+// MOMENTS (twk_enable_moments; the MOMENTS builds of the accumulate kernels): the same read of every sample also folds the
+// luminance moments of launch index `index` into *moments = (mean, M2, n, 0), Welford's recurrence in f32, every operation
+// rounded once, in this order — per KEPT sample (the r.w == 0 skip and the keep rule above it are the running mean's), in
+// iteration order, on the radiance as it is folded (the false colour under debugExceptions), before the lerp:
+//   l = (0.2126f r.x + 0.7152f r.y) + 0.0722f r.z                  (device_math.h luminance3: the denoiser's weights and order)
+//   iteration 0:  mean = M2 = n = 0                                 (the triple starts afresh where the running mean does)
+//   n = n + 1;  d = l - mean;  mean = mean + d / n;  M2 = M2 + d * (l - mean)
+// n is a float (exact up to 2^24 samples). A sample that is not finite makes the triple not finite; nothing is caught here, the
+// consumer (denoise_device.h, the SAMPLED moments pass) falls back to its spatial estimate for such a pixel. M2 / (n - 1) is
+// the sample variance of the luminance, M2 / ((n - 1) n) the variance of the pixel's mean. Never rounded to half.
+template<bool MOMENTS = false, typename Stored>
+TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments = nullptr)
 {
   const bool aov = (p.aovAlbedo != nullptr);
   bool touched = false;
@@ -1036,6 +1047,15 @@ TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& 
     if (keep)
     {
       const unsigned int iteration = p.iterationIndex + (unsigned int) s;
+      if (MOMENTS)
+      {
+        const float l = luminance3(radiance.x, radiance.y, radiance.z);
+        if (iteration == 0) { moments->x = 0.0f; moments->y = 0.0f; moments->z = 0.0f; }
+        moments->z = moments->z + 1.0f;
+        const float d = l - moments->x;
+        moments->x = moments->x + d / moments->z;
+        moments->y = moments->y + d * (l - moments->x);
+      }
       V3 albedo = v3(0.0f), normal = v3(0.0f);
       if (aov) { albedo = v3(p.pathAlbedo[path]); normal = v3(p.pathNormal[path]); }
       // time view (raygeneration.cu:231-244): alpha = the sample's clock cycles * clockScale, accumulated like the radiance

@@ -449,11 +449,27 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
 
 // raygeneration.cu:222-253: drop NaN samples, running mean into the RGBA32F buffer, alpha 1. The samples of a batch
 // are folded in iteration order, one lerp each, so the float result equals batchCount separate launches.
+// MOMENTS (LaunchParams::moments != nullptr): the same single read of every sample also folds the launch index's luminance
+// moments (shade_device.h foldSamples), read and written once per pass, one more float4 each way.
+template<bool MOMENTS>
 __global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p)
 {
   const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
   if (index >= (unsigned int) p.numPixels) return;
-  accumulateLaunchIndex(p, index);
+  if (!MOMENTS) { accumulateLaunchIndex(p, index); return; }
+  const bool aov = (p.aovAlbedo != nullptr);
+  size_t outIndex;
+  if (!accumulateTarget(p, index, outIndex)) return;
+  float4 dst = p.output[outIndex];
+  float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 moments = p.moments[index];
+  if (foldSamples<true>(p, index, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments))
+  {
+    p.output[outIndex] = dst;
+    if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
+    p.moments[index] = moments;
+  }
 }
 
 // Optix7Gui's RGBA16F output: Half4, widen, narrow of pixel_formats.h
@@ -461,6 +477,7 @@ struct StoredAsHalf { TWK_D float4 operator()(const float4 v) const { return wid
 
 // accumulateKernel on RGBA16F output and AOV buffers (raygeneration.cu:267-317): the lerp operand is the widened half and the
 // arithmetic the f32 expression of the float build, rounded once per folded sample (foldSamples).
+template<bool MOMENTS>
 __global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
 {
   const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
@@ -474,10 +491,12 @@ __global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
   float4 dst = widen(output[outIndex]);
   float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (foldSamples(p, index, dst, dstAlbedo, dstNormal, StoredAsHalf()))
+  float4 moments = MOMENTS ? p.moments[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // f32 in half mode too: the samples' own luminance, never narrowed
+  if (foldSamples<MOMENTS>(p, index, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments))
   {
     output[outIndex] = narrow(dst); // dst is already a widened half: narrow() is exact here
     if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
+    if (MOMENTS) p.moments[index] = moments;
   }
 }
 
@@ -663,8 +682,15 @@ int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, 
 }
 void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream)
 {
-  if (half) hipLaunchKernelGGL(accumulateHalfKernel, dim3((p.numPixels + 255) / 256), dim3(256), 0, stream, p);
-  else      hipLaunchKernelGGL(accumulateKernel, dim3((p.numPixels + 255) / 256), dim3(256), 0, stream, p);
+  const dim3 grid((p.numPixels + 255) / 256);
+  if (p.moments != nullptr)
+  {
+    if (half) hipLaunchKernelGGL(accumulateHalfKernel<true>, grid, dim3(256), 0, stream, p);
+    else      hipLaunchKernelGGL(accumulateKernel<true>, grid, dim3(256), 0, stream, p);
+    return;
+  }
+  if (half) hipLaunchKernelGGL(accumulateHalfKernel<false>, grid, dim3(256), 0, stream, p);
+  else      hipLaunchKernelGGL(accumulateKernel<false>, grid, dim3(256), 0, stream, p);
 }
 // half: tiles and output are Half4
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,

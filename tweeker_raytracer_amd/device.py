@@ -132,6 +132,29 @@ class Device:
     def enableAov(self, enable=True):
         L.check(L.lib.twk_enable_aov(self._h, int(bool(enable))))
 
+    def enableMoments(self, enable=True):
+        """twk_enable_moments: the accumulate kernel also folds the luminance moments (mean, M2, n, 0) of the samples it keeps,
+        Welford's recurrence in f32, one float4 per launch index, always float32 — what denoise(moments=...) is guided by."""
+        L.check(L.lib.twk_enable_moments(self._h, int(bool(enable))))
+
+    def readMoments(self):
+        """The luminance moments: float32 [height, launchWidth, 4] = (mean, M2, n, 0); M2 / ((n - 1) n) is the variance of the pixel's mean."""
+        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def momentsDevicePointer(self):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_moments_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def debugReadPathRadiance(self, samples):
+        """The raw samples of the last wavefront pass as its accumulate kernel read them (twk_debug_read_path_radiance): float32
+        [samples, height, launchWidth, 4]; `samples` = the iterations that pass rendered together (w = 0: no pixel there)."""
+        out = np.empty((int(samples), self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_debug_read_path_radiance(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
     def setTimeView(self, enable=True):
         """≙ USE_TIME_VIEW: alpha of the accumulation buffer = running mean of the sample's shader-clock cycles x clockFactor x 1e-9."""
         L.check(L.lib.twk_set_time_view(self._h, int(bool(enable))))
@@ -273,16 +296,26 @@ class Device:
         L.check(L.lib.twk_tonemap(self._h, C.byref(tm), ptr, C.c_size_t(h * w), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
 
-    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None, variance=None):
+    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None, variance=None, moments=None, minSamples=None):
         """twk_denoise: the edge-avoiding a-trous wavelet filter (a classical filter, not a learned one) where Optix7Gui calls
         optixDenoiserInvoke. Asynchronous. params: L.Denoiser (None = the defaults). Without `beauty` the handle's own
         accumulation and AOV buffers are filtered; otherwise beauty / albedo / normal are device pointers to shape = (height,
         width) pixels in the handle's output format. denoised: device pointer of the result, None = the internal buffer that
         readDenoised / denoisedDevicePointer hand out. variance: L.DenoiserVariance = twk_denoise_variance, the variance-guided,
-        firefly-clamping mode of the same filter (params.sigmaColor is ignored then); None = twk_denoise."""
+        firefly-clamping mode of the same filter (params.sigmaColor is ignored then); None = twk_denoise.
+        minSamples (an int >= 2) or moments: twk_denoise_variance_sampled — pixels that have seen at least minSamples samples
+        (default L.TWK_DENOISER_MIN_SAMPLES) are guided by the measured variance of their mean instead of the spatial estimate.
+        moments: device pointer to shape float4 (mean, M2, n, .) beside an explicit beauty; without `beauty`, moments=True (or just
+        minSamples) takes the handle's own (enableMoments). variance=None then means DenoiserVariance()."""
         dn = params if params is not None else L.Denoiser()
         ptr = lambda p: None if p is None else C.c_void_p(int(p))
         h, w = shape if shape is not None else (0, 0)
+        if minSamples is not None or (moments is not None and moments is not False):
+            dv = variance if variance is not None else L.DenoiserVariance()
+            m = None if (moments is None or moments is True) else C.c_void_p(int(moments))
+            n = L.TWK_DENOISER_MIN_SAMPLES if minSamples is None else int(minSamples)
+            L.check(L.lib.twk_denoise_variance_sampled(self._h, C.byref(dn), C.byref(dv), n, ptr(beauty), ptr(albedo), ptr(normal), m, int(w), int(h), ptr(denoised)))
+            return
         if variance is not None:
             L.check(L.lib.twk_denoise_variance(self._h, C.byref(dn), C.byref(variance), ptr(beauty), ptr(albedo), ptr(normal), int(w), int(h), ptr(denoised)))
             return

@@ -477,6 +477,73 @@ int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats);        
 int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes);             /* in the output format */
 int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes); /* feeds twk_tonemap / twk_tonemap_half */
 
+/* ---- The temporal seam — new calls, ABI stays 9, no existing struct changes -----------------------------------------------------
+ * The temporal half of SVGF (Schied et al. 2017, section 4.1) in front of the filter above: after a camera move an interactive
+ * viewer restarts at iteration 0 with a handful of samples; these calls reproject the last frame's colour and luminance moments
+ * through the previous camera and merge them with the new frame's samples BY SAMPLE COUNT. The loop of a frame:
+ *   twk_set_sample_offset(frames x spp); twk_launch 0 .. spp-1; twk_render_geometry; twk_temporal_accumulate;
+ *   twk_denoise_variance_sampled on the merged colour and merged moments.
+ * Everything is opt-in; with the switches at their defaults nothing changes. Definition: csrc/temporal_device.h. */
+
+/* Default 0. While set, iteration i draws its random numbers as iteration i + offset does otherwise (the second argument of the
+ * seed's tea<4>); everything that COUNTS samples is unchanged: the running mean's weight 1 / (i + 1), "iteration 0 starts
+ * afresh", the moments' n. A frame restarted at iteration 0 after a camera move sets offset = frames x spp, so that its noise is
+ * independent of the history it is merged with (without it, a pixel reprojected by less than a pixel meets its own random
+ * sequence again). A run-time value of the launch parameters, not a kernel build. Recorded launches are rendered first. */
+int twk_set_sample_offset(TwkDevice dev, unsigned int offset);
+
+/* Geometry AOV: one float4 per launch index, laid out like the moments, always f32: (world position of the primary hit, bits of
+ * (unsigned) instance + 1), or (0, 0, 0, bits 0) for a miss. twk_enable_geometry(1) allocates it, zeroed (with twk_set_state,
+ * whichever comes later); (0) frees it. twk_render_geometry enqueues, on the handle's stream, ONE kernel that traces one
+ * closest-hit ray through the CENTRE of every pixel (the pinhole lens shader with the jitter 0.5, the single-ray traversal of
+ * twk_trace_rays, tmin = the scene epsilon) with the camera as it is now. TWK_ERROR_INVALID_STATE: before twk_build or
+ * twk_set_state, with the geometry off, with a lens shader other than the pinhole (reprojection inverts the pinhole mapping
+ * only), on a packed tile buffer (distribution 1, several devices), and on a scene with a cutout texture in use (the query is
+ * geometric). */
+int twk_enable_geometry(TwkDevice dev, int enable);
+int twk_render_geometry(TwkDevice dev);
+int twk_read_geometry(TwkDevice dev, float* host, size_t numFloats); /* launchWidth*height*4 floats (w: the bits of a uint); synchronises */
+int twk_get_geometry_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+
+/* maxHistory: the cap, in samples, on what the history weighs (>= 1): an old frame fades like an exponential average with
+ * alpha = spp / (maxHistory + spp). positionTolerance: a history tap belongs to the surface point when their world positions
+ * differ by at most positionTolerance x the point's distance to the previous camera (>= 0, finite). */
+typedef struct TwkTemporal { int maxHistory; float positionTolerance; } TwkTemporal;
+#define TWK_TEMPORAL_MAX_HISTORY 32
+#define TWK_TEMPORAL_POSITION_TOLERANCE 0.01f
+int twk_temporal_defaults(TwkTemporal* tp);
+/* One frame's buffers, width x height elements each, device pointers: colour, luminance moments (mean, M2, n, .) as
+ * twk_enable_moments accumulates them, geometry AOV, and the camera the frame was rendered from. */
+typedef struct TwkTemporalFrame { const void* colour; const void* moments; const void* geometry; TwkCameraDefinition camera; } TwkTemporalFrame;
+/* Asynchronous, one kernel on the handle's stream. Per pixel: the surface point of current->geometry is projected through
+ * history->camera, the history's colour and moments are fetched bilinearly at the four pixels around it — those whose geometry
+ * has the same instance word and lies within the tolerance, and whose values are finite with n >= 1 — the history's n is capped
+ * at maxHistory (M2 scaled along), and the two sample sets are merged: colour by sample count, moments by Chan's pairwise form
+ * of Welford. A pixel without history (a miss, a point behind or outside the previous view, no tap that belongs to it, values
+ * that are not finite, n < 1) passes through with the input's bits. tp NULL: twk_temporal_defaults.
+ * EXPLICIT form (current != NULL): current->colour is in the handle's output format (RGBA32F, or RGBA16F widened exactly),
+ * everything else f32 float4; history->colour is a previous call's historyOut. history NULL: no history, every pixel passes
+ * through. current->camera is not read (it is the next call's history->camera). colourOut: the merged colour in the output
+ * format, narrowed once — what twk_denoise_variance_sampled is handed as beauty; historyOut: the same colour unrounded in f32;
+ * momentsOut: the merged moments (mean, M2, n, 0). Any of the three may be NULL. TWK_ERROR_INVALID_VALUE: a NULL input, an output
+ * that overlaps an input or another output (the kernel gathers history at other pixels), maxHistory < 1, a tolerance that is
+ * negative or not finite, and a history camera whose U, V, W are linearly dependent or not finite.
+ * OWN-BUFFER form (current and history NULL; width, height and the outputs must be 0 / NULL): current is the handle's
+ * accumulation buffer, moments, geometry AOV and camera 0 — TWK_ERROR_INVALID_STATE unless twk_enable_moments,
+ * twk_enable_geometry and a twk_render_geometry since the last camera, state or scene change, and on a packed tile buffer. The
+ * history is what the previous call kept (f32 colour, moments, geometry, camera) in double-buffered streams of the handle,
+ * allocated on first use and dropped by twk_temporal_reset, a change of resolution, twk_clear_scene and twk_build. The first call
+ * after that has no history: it copies the frame through and keeps it. The results go to internal buffers:
+ * twk_get_temporal_device_pointers (colour in the output format, merged moments f32; either pair may be NULL), twk_read_temporal
+ * (RGBA32F, widened exactly) and twk_read_temporal_moments. What it is not: see csrc/temporal_device.h — no motion vectors (the
+ * scene is static between builds), no environment reprojection (a miss never has history), pinhole only, one device. */
+int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                            int width, int height, void* colourOut, void* historyOut, void* momentsOut);
+int twk_temporal_reset(TwkDevice dev);
+int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colourBytes, void** moments, size_t* momentsBytes);
+int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats);         /* launchWidth*height*4 floats; synchronises */
+int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);

@@ -25,6 +25,8 @@ TWK_OUTPUT_FLOAT4, TWK_OUTPUT_HALF4 = 0, 1  # twk_set_output_format: RGBA32F (de
 TWK_DENOISER_RGB, TWK_DENOISER_RGB_ALBEDO, TWK_DENOISER_RGB_ALBEDO_NORMAL = 0, 1, 2  # TwkDenoiser.inputKind: the guides that weigh the taps
 TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_variance_sampled (include/tweeker_hip.h)
 
+TWK_TEMPORAL_MAX_HISTORY, TWK_TEMPORAL_POSITION_TOLERANCE = 32, 0.01  # twk_temporal_defaults (include/tweeker_hip.h)
+
 f3 = C.c_float * 3
 f2 = C.c_float * 2
 i2 = C.c_int * 2
@@ -89,6 +91,24 @@ class DenoiserVariance(C.Structure):
         super().__init__(fireflyThreshold, sigmaLuminance)
 
 
+class Temporal(C.Structure):
+    """≙ TwkTemporal: parameters of twk_temporal_accumulate. maxHistory: the cap, in samples, on what the history weighs;
+    positionTolerance: a history tap belongs to the surface when its world position differs by at most this x the distance to
+    the previous camera. Without arguments: twk_temporal_defaults."""
+    _fields_ = [("maxHistory", C.c_int), ("positionTolerance", C.c_float)]
+
+    def __init__(self, maxHistory=TWK_TEMPORAL_MAX_HISTORY, positionTolerance=TWK_TEMPORAL_POSITION_TOLERANCE):
+        super().__init__(int(maxHistory), positionTolerance)
+
+
+class TemporalFrame(C.Structure):
+    """≙ TwkTemporalFrame: one frame's device buffers (colour, luminance moments, geometry AOV; ints or None) and its camera."""
+    _fields_ = [("colour", C.c_void_p), ("moments", C.c_void_p), ("geometry", C.c_void_p), ("camera", CameraDefinition)]
+
+    def __init__(self, colour=None, moments=None, geometry=None, camera=None):
+        super().__init__(colour, moments, geometry, camera if camera is not None else CameraDefinition())
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("radianceRays", C.c_uint64), ("shadowRays", C.c_uint64), ("nodesVisited", C.c_uint64),
                 ("trianglesTested", C.c_uint64), ("instancesEntered", C.c_uint64), ("shadedHits", C.c_uint64),
@@ -135,6 +155,8 @@ SYMBOLS = [
     "twk_denoiser_defaults", "twk_denoise", "twk_read_denoised", "twk_read_denoised_raw", "twk_get_denoised_device_pointer", "twk_app_get_denoiser",
     "twk_denoiser_variance_defaults", "twk_denoise_variance", "twk_app_get_denoiser_variance",
     "twk_enable_moments", "twk_read_moments", "twk_get_moments_device_pointer", "twk_debug_read_path_radiance", "twk_denoise_variance_sampled", "twk_app_get_denoiser_sampled",
+    "twk_set_sample_offset", "twk_enable_geometry", "twk_render_geometry", "twk_read_geometry", "twk_get_geometry_device_pointer",
+    "twk_temporal_defaults", "twk_temporal_accumulate", "twk_temporal_reset", "twk_get_temporal_device_pointers", "twk_read_temporal", "twk_read_temporal_moments",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

@@ -5,6 +5,7 @@
 #include "device_types.h"
 #include "bvh_build.h"
 #include "denoise_device.h"
+#include "temporal_device.h"
 #include "error_state.h"
 
 #include <algorithm>
@@ -45,6 +46,9 @@ void launchDenoisePrepare(const void* beauty, const void* albedo, const void* no
 void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, const float4* sampled, float minSamples, hipStream_t stream);
 void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
+void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream);
+void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
+                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
 }
 
 using namespace twk;
@@ -154,6 +158,15 @@ struct TwkDevice_t
   float4* d_aovAlbedo = nullptr; float4* d_aovNormal = nullptr; int aovPixels = 0;
   // twk_enable_moments: luminance moments (mean, M2, n, 0) of the samples per launch index, always f32 (LaunchParams::moments)
   bool momentsEnabled = false; float4* d_moments = nullptr; int momentsPixels = 0;
+  unsigned int sampleOffset = 0; // twk_set_sample_offset (LaunchParams::sampleOffset)
+  // twk_enable_geometry: the geometry AOV (world position, instance + 1) per launch index, always f32; geometryValid: rendered by
+  // twk_render_geometry since the last change of camera, state or scene
+  bool geometryEnabled = false; float4* d_geometry = nullptr; int geometryPixels = 0; bool geometryValid = false;
+  // twk_temporal_accumulate, own-buffer form: two sets of three f32 streams (colour, moments, geometry) — the set temporalKept holds
+  // what the last call kept (its camera: temporalCamera), the other receives this call's — and the merged colour in the output format
+  float4* d_temporal[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; void* d_temporalColour = nullptr;
+  int temporalWidth = 0, temporalHeight = 0, temporalFormat = TWK_OUTPUT_FLOAT4, temporalKept = 0; bool temporalHasHistory = false, temporalValid = false;
+  TwkCameraDefinition temporalCamera;
   int lastPassCount = 0, lastPassPixels = 0; // samples per launch index and launch indices of the last pass, while its pathRadiance stream still holds them (twk_debug_read_path_radiance); 0: none
   // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) in the output format it was
   // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
@@ -359,6 +372,7 @@ static void refreshParams(TwkDevice dev)
   p.pathAlbedo = dev->aovEnabled ? dev->d_pathAlbedo : nullptr; p.pathNormal = dev->aovEnabled ? dev->d_pathNormal : nullptr;
   p.aovAlbedo  = dev->aovEnabled ? dev->d_aovAlbedo : nullptr;  p.aovNormal  = dev->aovEnabled ? dev->d_aovNormal : nullptr;
   p.moments = dev->momentsEnabled ? dev->d_moments : nullptr;
+  p.sampleOffset = dev->sampleOffset;
   p.firstHit = dev->captureFirstHits ? dev->d_firstHit : nullptr;
   p.firstHitInstance = dev->captureFirstHits ? dev->d_firstHitInstance : nullptr;
   p.traceStackSpill = dev->d_spill;
@@ -433,6 +447,11 @@ static int ensureStreams(TwkDevice dev, int samples = 1)
     if ((rc = growBuffers(dev, dev->aovPixels, dev->allocatedPixels, {{dev->d_aovAlbedo, pixelBytes(dev), true}, {dev->d_aovNormal, pixelBytes(dev), true}}))) return rc;
   }
   if (dev->momentsEnabled && (rc = growBuffers(dev, dev->momentsPixels, dev->allocatedPixels, {{dev->d_moments, sizeof(float4), true}}))) return rc;
+  if (dev->geometryEnabled)
+  {
+    if (dev->geometryPixels < dev->allocatedPixels || !dev->d_geometry) dev->geometryValid = false; // a new, zeroed buffer
+    if ((rc = growBuffers(dev, dev->geometryPixels, dev->allocatedPixels, {{dev->d_geometry, sizeof(float4), true}}))) return rc;
+  }
   if (!dev->d_counters) HIP_TRY(hipMalloc(&dev->d_counters, sizeof(unsigned int) * TWK_COUNTER_WORDS * TWK_MAX_LANES));
   if (!dev->d_stats) { HIP_TRY(hipMalloc(&dev->d_stats, sizeof(unsigned long long) * TWK_STATS_WORDS)); HIP_TRY(hipMemsetAsync(dev->d_stats, 0, sizeof(unsigned long long) * TWK_STATS_WORDS, dev->stream)); } // TwkLaunchStats words (24 + the shade phases' 3 x 24) + a scratch block of the same size for the time view
   if (!dev->h_dropped)
@@ -747,6 +766,14 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
   return TWK_SUCCESS;
 }
 
+// Frees the streams of twk_temporal_accumulate's own-buffer form: the next call has no history
+static void dropTemporal(TwkDevice dev)
+{
+  for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
+  freeDevice(dev->d_temporalColour);
+  dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
+}
+
 // =============================================================================================
 extern "C" {
 
@@ -839,6 +866,7 @@ try
   if (dev->h_dropped) { (void) hipHostFree(dev->h_dropped); dev->h_dropped = nullptr; dev->d_dropped = nullptr; }
   freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
   freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); freeDevice(dev->d_moments);
+  freeDevice(dev->d_geometry); dropTemporal(dev);
   freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams);
   dev->builder.release();
   for (int k = 1; k < TWK_MAX_LANES; ++k)
@@ -864,8 +892,9 @@ try
   if (s->pathLengths[1] < 0 || s->pathLengths[1] > TWK_MAX_DEPTH) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_state: pathLengths.y must be in [0, 64]");
   if (s->lensShader < 0 || s->lensShader > 2) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_state: lensShader must be 0..2");
   HIP_TRY(hipStreamSynchronize(dev->stream)); // Device.cpp:1194-1195
+  if (dev->stateSet && (dev->state.resolution[0] != s->resolution[0] || dev->state.resolution[1] != s->resolution[1])) dropTemporal(dev);
   dev->state = *s;
-  dev->stateSet = true;
+  dev->stateSet = true; dev->geometryValid = false;
   if (s->distribution && 1 < dev->count)
   {
     // DeviceMultiGPULocalCopy.cpp:84-97
@@ -889,7 +918,7 @@ try
   int rc = activate(dev, "twk_init_cameras"); if (rc) return rc;
   if (!c || count < 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_init_cameras: at least one camera is required");
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->cameras.assign(c, c + count);
+  dev->cameras.assign(c, c + count); dev->geometryValid = false;
   if (!dev->d_camera) HIP_TRY(hipMalloc(&dev->d_camera, sizeof(TwkCameraDefinition)));
   HIP_TRY(hipMemcpyAsync(dev->d_camera, dev->cameras.data(), sizeof(TwkCameraDefinition), hipMemcpyHostToDevice, dev->stream)); // the lens shaders read cameraDefinitions[0]
   return TWK_SUCCESS;
@@ -903,6 +932,7 @@ try
   if (!c || idCamera < 0 || idCamera >= (int) dev->cameras.size()) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_update_camera: bad camera id");
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->cameras[idCamera] = *c;
+  if (idCamera == 0) dev->geometryValid = false;
   if (idCamera == 0) HIP_TRY(hipMemcpyAsync(dev->d_camera, dev->cameras.data(), sizeof(TwkCameraDefinition), hipMemcpyHostToDevice, dev->stream));
   return TWK_SUCCESS;
 }
@@ -1010,6 +1040,7 @@ try
   int rc = activate(dev, "twk_clear_scene"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->geometries.clear(); dev->instances.clear(); dev->built = false;
+  dev->geometryValid = false; dropTemporal(dev);
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_clear_scene")
@@ -1309,6 +1340,7 @@ try
   dev->maxInstanceMaterial = maxMaterial; dev->maxInstanceLight = maxLight;
   dev->totalNodes = numNodes; dev->totalTriangles = numTris;
   dev->built = true; ++dev->buildSerial;
+  dev->geometryValid = false; dropTemporal(dev); // the geometry AOV and the temporal history describe the scene that was
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_build")
@@ -1497,6 +1529,76 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_moments_device_pointer")
+
+int twk_set_sample_offset(TwkDevice dev, unsigned int offset)
+try
+{
+  int rc = activate(dev, "twk_set_sample_offset"); if (rc) return rc; // recorded launches are rendered with the offset they were recorded under
+  dev->sampleOffset = offset;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_set_sample_offset")
+
+int twk_enable_geometry(TwkDevice dev, int enable)
+try
+{
+  int rc = activate(dev, "twk_enable_geometry"); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  dev->geometryEnabled = (enable != 0); dev->geometryValid = false;
+  if (!dev->geometryEnabled) { freeDevice(dev->d_geometry); dev->geometryPixels = 0; return TWK_SUCCESS; } // enabled again: a zeroed buffer
+  return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first use after twk_set_state
+}
+TWK_CATCH("twk_enable_geometry")
+
+int twk_render_geometry(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_render_geometry"); if (rc) return rc;
+  if (!dev->built) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: twk_build has not been called");
+  if (!dev->stateSet || dev->cameras.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: twk_set_state and twk_init_cameras first");
+  if (!dev->geometryEnabled) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: twk_enable_geometry(1) first");
+  if (dev->state.lensShader != 0) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: pinhole lens shader only (reprojection inverts the pinhole mapping)");
+  if (dev->state.distribution && 1 < dev->count) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: the handle's buffers are packed tile buffers (distribution 1, more than one device), not pictures");
+  for (const DevMaterial& m : dev->materials) if (m.textureCutout) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: geometric query only, not for scenes with cutout opacity");
+  if ((rc = ensureStreams(dev))) return rc;
+  refreshParams(dev);
+  const size_t numPixels = (size_t) dev->launchWidth * dev->state.resolution[1]; // launchWidth = width here
+  if (!dev->d_geometry || (size_t) dev->geometryPixels < numPixels) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: no geometry buffer");
+  int grid = (int) ((numPixels + TWK_TRACE_BLOCK - 1) / TWK_TRACE_BLOCK);
+  if (grid > dev->numCUs * TWK_TRACE_WAVES) grid = dev->numCUs * TWK_TRACE_WAVES; // within the per-lane spill stacks, like twk_trace_rays
+  launchGeometry(dev->params, dev->d_geometry, grid, dev->stream);
+  HIP_TRY(hipGetLastError());
+  dev->geometryValid = true;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_render_geometry")
+
+int twk_read_geometry(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_geometry"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_geometry: NULL buffer");
+  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_geometry: buffer must hold launchWidth*height*4 floats");
+  if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_geometry: twk_enable_geometry(1) and twk_set_state first");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_geometry, n * sizeof(float4), hipMemcpyDeviceToHost));
+  return checkDroppedPushes(dev, "twk_read_geometry");
+}
+TWK_CATCH("twk_read_geometry")
+
+int twk_get_geometry_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
+try
+{
+  int rc = activate(dev, "twk_get_geometry_device_pointer"); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_geometry_device_pointer: NULL argument");
+  if (!dev->geometryEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_geometry_device_pointer: twk_enable_geometry(1) and twk_set_state first");
+  if ((rc = ensureStreams(dev))) return rc;
+  *dptr = dev->d_geometry;
+  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(float4);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_geometry_device_pointer")
 
 int twk_set_time_view(TwkDevice dev, int enable)
 try
@@ -1868,6 +1970,151 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_denoised_device_pointer")
+
+int twk_temporal_defaults(TwkTemporal* tp)
+try
+{
+  if (!tp) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_temporal_defaults: NULL argument");
+  tp->maxHistory = TWK_TEMPORAL_MAX_HISTORY; tp->positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_defaults")
+
+int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history, int width, int height,
+                            void* colourOut, void* historyOut, void* momentsOut)
+try
+{
+  const char* name = "twk_temporal_accumulate";
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  int rc = activate(dev, name); if (rc) return rc;
+  TwkTemporal defaults; defaults.maxHistory = TWK_TEMPORAL_MAX_HISTORY; defaults.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  if (!tp) tp = &defaults;
+  if (tp->maxHistory < 1) return refuse(TWK_ERROR_INVALID_VALUE, "maxHistory must be >= 1");
+  if (!(tp->positionTolerance >= 0.0f) || !finite1(tp->positionTolerance)) return refuse(TWK_ERROR_INVALID_VALUE, "positionTolerance must be >= 0 and finite");
+  TemporalConstants k;
+  memset(&k, 0, sizeof(k));
+  k.maxHistory = (float) tp->maxHistory; k.tol2 = tp->positionTolerance * tp->positionTolerance;
+
+  const bool own = (current == nullptr);
+  const void* colour; const float4 *moments, *geometry, *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
+  const TwkCameraDefinition* hCamera = nullptr;
+  int keep = 0;
+  if (own)
+  {
+    if (history || colourOut || historyOut || momentsOut || width || height) return refuse(TWK_ERROR_INVALID_VALUE, "a history, outputs or a size without a current frame (pass both frames, or neither for the handle's own buffers)");
+    if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+    if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
+    width = dev->launchWidth; height = dev->state.resolution[1];
+    const size_t n = (size_t) width * height;
+    if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+    if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+    if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
+    colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+    if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+    if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
+    {
+      HIP_TRY(hipStreamSynchronize(dev->stream));
+      dropTemporal(dev);
+      for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
+      HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
+      dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
+    }
+    moments = dev->d_moments; geometry = dev->d_geometry;
+    if (dev->temporalHasHistory)
+    {
+      float4* const* h = dev->d_temporal[dev->temporalKept];
+      hColour = h[0]; hMoments = h[1]; hGeometry = h[2]; hCamera = &dev->temporalCamera;
+    }
+    keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
+    colourOut = dev->d_temporalColour; historyOut = dev->d_temporal[keep][0]; momentsOut = dev->d_temporal[keep][1];
+  }
+  else
+  {
+    if (width < 1 || height < 1 || (size_t) width * (size_t) height >= ((size_t) 1 << 31)) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
+    if (!current->colour || !current->moments || !current->geometry) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer in the current frame");
+    if (history && (!history->colour || !history->moments || !history->geometry)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer in the history frame");
+    colour = current->colour; moments = static_cast<const float4*>(current->moments); geometry = static_cast<const float4*>(current->geometry);
+    if (history)
+    {
+      hColour = static_cast<const float4*>(history->colour); hMoments = static_cast<const float4*>(history->moments); hGeometry = static_cast<const float4*>(history->geometry);
+      hCamera = &history->camera;
+    }
+    const size_t n = (size_t) width * height, wide = n * sizeof(float4), narrowBytes = n * pixelBytes(dev);
+    const void* outs[3] = {colourOut, historyOut, momentsOut}; const size_t outBytes[3] = {narrowBytes, wide, wide};
+    const void* ins[6] = {colour, moments, geometry, hColour, hMoments, hGeometry}; const size_t inBytes[6] = {narrowBytes, wide, wide, wide, wide, wide};
+    for (int o = 0; o < 3; ++o)
+    {
+      for (int i = 0; i < 6; ++i) if (overlaps(outs[o], outBytes[o], ins[i], inBytes[i])) return refuse(TWK_ERROR_INVALID_VALUE, "an output overlaps an input (the kernel gathers the history at other pixels)");
+      for (int j = o + 1; j < 3; ++j) if (overlaps(outs[o], outBytes[o], outs[j], outBytes[j])) return refuse(TWK_ERROR_INVALID_VALUE, "two outputs overlap");
+    }
+  }
+  k.width = width; k.height = height;
+  if (hCamera)
+  {
+    k.hasHistory = 1;
+    if (!temporalCamera(hCamera->P, k)) return refuse(TWK_ERROR_INVALID_VALUE, "the history's camera is degenerate: U, V, W are linearly dependent or not finite");
+  }
+  launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
+  HIP_TRY(hipGetLastError());
+  if (own)
+  {
+    HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, (size_t) width * height * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
+    dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
+  }
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_accumulate")
+
+int twk_temporal_reset(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_temporal_reset"); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  dropTemporal(dev);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_reset")
+
+int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colourBytes, void** moments, size_t* momentsBytes)
+try
+{
+  int rc = activate(dev, "twk_get_temporal_device_pointers"); if (rc) return rc;
+  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_temporal_device_pointers: no twk_temporal_accumulate on the handle's own buffers since the last reset");
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (colour) *colour = dev->d_temporalColour;
+  if (colourBytes) *colourBytes = n * pixelBytes(dev->temporalFormat);
+  if (moments) *moments = dev->d_temporal[dev->temporalKept][1];
+  if (momentsBytes) *momentsBytes = n * sizeof(float4);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_temporal_device_pointers")
+
+int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_temporal"); if (rc) return rc;
+  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal: NULL buffer");
+  if (!dev->temporalValid || dev->temporalFormat != dev->outputFormat) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal: no twk_temporal_accumulate on the handle's own buffers since the last reset");
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal: buffer must hold width*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return readWidened(dev, dev->d_temporalColour, rgbaHost, n);
+}
+TWK_CATCH("twk_read_temporal")
+
+int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_temporal_moments"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_moments: NULL buffer");
+  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal_moments: no twk_temporal_accumulate on the handle's own buffers since the last reset");
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_moments: buffer must hold width*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_temporal[dev->temporalKept][1], n * sizeof(float4), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_temporal_moments")
 
 // ---- measurement ------------------------------------------------------------------------------
 int twk_profile_enable(TwkDevice dev, int enable)

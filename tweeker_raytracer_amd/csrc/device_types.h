@@ -242,6 +242,9 @@ struct LaunchParams
   // Luminance moments of the samples (twk_enable_moments), nullptr when off: (mean, M2, n, 0) per launch index, indexed like
   // aovAlbedo, always f32. Folded by the MOMENTS builds of the accumulate kernels (shade_device.h foldSamples).
   float4* moments;
+  // twk_set_sample_offset (default 0): iteration i seeds its random numbers as iteration i + sampleOffset (shade_device.h
+  // primaryRay); whatever counts samples — the running mean's weight, "iteration 0 starts afresh", the moments' n — does not see it.
+  unsigned int sampleOffset;
 };
 
 // Slim streams: the hit record's slot word <-> (triangle slot, instance). A miss is -1 on both sides.

@@ -917,7 +917,7 @@ TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index)
   unsigned int seed = 0;
   if (active)
   {
-    seed = tea<4>((unsigned int) p.resolution[0] * ly + launchColumn, p.iterationIndex + sampleIndex);
+    seed = tea<4>((unsigned int) p.resolution[0] * ly + launchColumn, (p.iterationIndex + p.sampleOffset) + sampleIndex); // twk_set_sample_offset: 0 unless set
 
     const float screenX = float(p.resolution[0]), screenY = float(p.resolution[1]);
     const float pixelX  = float(launchColumn),    pixelY  = float(ly);

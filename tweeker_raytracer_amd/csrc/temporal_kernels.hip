@@ -1,0 +1,110 @@
+// Kernels of twk_render_geometry and twk_temporal_accumulate: the geometry AOV and the temporal merge defined in temporal_device.h.
+#include "temporal_device.h"
+#include "trace_device.h"
+#include "pixel_formats.h"
+
+namespace twk {
+
+// One closest-hit ray through the centre of every pixel with the single-ray traversal (the routine, LDS stack and spill of
+// traceQueryKernel; the grid is at most numCUs x TWK_TRACE_WAVES blocks, within the per-lane spill stacks).
+__global__ void __launch_bounds__(TWK_TRACE_BLOCK)
+geometryKernel(LaunchParams p, float4* __restrict__ geometry)
+{
+  __shared__ int stackStorage[TWK_TRACE_STACK_LDS * TWK_TRACE_BLOCK];
+  int* ldsStack = stackStorage + threadIdx.x;
+  int* spill = p.traceStackSpill + (size_t) (blockIdx.x * blockDim.x + threadIdx.x) * TWK_TRACE_STACK_SPILL;
+  unsigned int n0 = 0, n1 = 0, n2 = 0;
+  const unsigned int numPixels = (unsigned int) p.resolution[0] * (unsigned int) p.resolution[1];
+  const float* cam = p.camera;
+  const V3 P = v3(cam[0], cam[1], cam[2]);
+  for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < numPixels; i += gridDim.x * blockDim.x)
+  {
+    const int x = (int) (i % (unsigned int) p.resolution[0]), y = (int) (i / (unsigned int) p.resolution[0]);
+    const V3 d = centreRay(cam, x, y, p.resolution[0], p.resolution[1]);
+    TraceResult res;
+    traverse<false>(p, P, d, p.sceneEpsilon, RT_DEFAULT_MAX, false, ldsStack, spill, res, n0, n1, n2);
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (res.instance >= 0)
+      g = make_float4(P.x + res.t * d.x, P.y + res.t * d.y, P.z + res.t * d.z, __uint_as_float((unsigned int) res.instance + 1u));
+    geometry[i] = g;
+  }
+}
+
+template<typename Pixel> struct TemporalPixel;
+template<> struct TemporalPixel<float4> { static TWK_D float4 make(const float4 v) { return v; } };
+template<> struct TemporalPixel<Half4>  { static TWK_D Half4 make(const float4 v) { return narrow(v); } };
+
+// One thread per pixel. The current frame's three streams and the three outputs are coalesced 16-byte (RGBA16F: 8-byte) accesses;
+// the history is four neighbouring 16-byte gathers per stream around the reprojected position, the geometry first: colour and
+// moments are fetched only at the taps that belong to the surface.
+template<typename Pixel>
+__global__ void __launch_bounds__(256) temporalKernel(const Pixel* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ geometry,
+                                                      const float4* __restrict__ historyColour, const float4* __restrict__ historyMoments, const float4* __restrict__ historyGeometry,
+                                                      Pixel* __restrict__ colourOut, float4* __restrict__ historyOut, float4* __restrict__ momentsOut, TemporalConstants k)
+{
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t) k.width * k.height) return;
+  const Pixel raw = colour[p];
+  const float4 cur = widen(raw);
+  const float4 mc = moments[p];
+  const float4 g = geometry[p];
+  TemporalSums s;
+  s.x = 0.0f; s.y = 0.0f; s.z = 0.0f; s.mean = 0.0f; s.M2 = 0.0f; s.n = 0.0f; s.ws = 0.0f;
+  float fx = 0.0f, fy = 0.0f, vv = 0.0f;
+  if (temporalCandidate(k, cur, mc, g) && temporalProject(k, g, fx, fy, vv))
+  {
+    const float fx0 = floorf(fx), fy0 = floorf(fy);
+    const float tx = fx - fx0, ty = fy - fy0;
+    const int x0 = (int) fx0, y0 = (int) fy0; // in [-1, width - 1] x [-1, height - 1]
+#pragma unroll
+    for (int dy = 0; dy <= 1; ++dy)
+    {
+      const int qy = y0 + dy;
+      if (qy < 0 || qy >= k.height) continue;
+#pragma unroll
+      for (int dx = 0; dx <= 1; ++dx)
+      {
+        const int qx = x0 + dx;
+        if (qx < 0 || qx >= k.width) continue;
+        const size_t q = (size_t) qy * k.width + qx;
+        if (!temporalTapGeometry(k, g, historyGeometry[q], vv)) continue;
+        const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+        temporalTap(historyColour[q], historyMoments[q], w, s);
+      }
+    }
+  }
+  if (s.ws > 0.0f)
+  {
+    float4 c, m;
+    temporalMerge(k, s, cur, mc, c, m);
+    if (colourOut) colourOut[p] = TemporalPixel<Pixel>::make(c);
+    if (historyOut) historyOut[p] = c;
+    if (momentsOut) momentsOut[p] = m;
+  }
+  else
+  {
+    if (colourOut) colourOut[p] = raw;
+    if (historyOut) historyOut[p] = cur;
+    if (momentsOut) momentsOut[p] = mc;
+  }
+}
+
+void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream)
+{
+  hipLaunchKernelGGL(geometryKernel, dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, geometry);
+}
+
+void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
+                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream)
+{
+  const size_t numPixels = (size_t) k.width * k.height;
+  const dim3 grid((unsigned int) ((numPixels + 255) / 256));
+  if (half)
+    hipLaunchKernelGGL(temporalKernel<Half4>, grid, dim3(256), 0, stream, static_cast<const Half4*>(colour), moments, geometry, historyColour, historyMoments, historyGeometry,
+                       static_cast<Half4*>(colourOut), historyOut, momentsOut, k);
+  else
+    hipLaunchKernelGGL(temporalKernel<float4>, grid, dim3(256), 0, stream, static_cast<const float4*>(colour), moments, geometry, historyColour, historyMoments, historyGeometry,
+                       static_cast<float4*>(colourOut), historyOut, momentsOut, k);
+}
+
+} // namespace twk

@@ -155,6 +155,65 @@ class Device:
         L.check(L.lib.twk_debug_read_path_radiance(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
+    # ---- the temporal seam (include/tweeker_hip.h "The temporal seam", csrc/temporal_device.h) ----
+    def setSampleOffset(self, offset):
+        """twk_set_sample_offset: iteration i draws its random numbers as iteration i + offset; what counts samples is unchanged.
+        A frame restarted at iteration 0 after a camera move sets frames x spp, so that its noise is independent of the history."""
+        L.check(L.lib.twk_set_sample_offset(self._h, C.c_uint(int(offset))))
+
+    def enableGeometry(self, enable=True):
+        """twk_enable_geometry: one float4 (world position of the primary hit, bits of instance + 1; zeros for a miss) per launch index."""
+        L.check(L.lib.twk_enable_geometry(self._h, int(bool(enable))))
+
+    def renderGeometry(self):
+        """twk_render_geometry: one closest-hit ray through the centre of every pixel with the camera as it is now. Asynchronous."""
+        L.check(L.lib.twk_render_geometry(self._h))
+
+    def readGeometry(self):
+        """The geometry AOV: float32 [height, launchWidth, 4]; [..., 3].view(uint32) is instance + 1, 0 for a miss."""
+        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_geometry(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def geometryDevicePointer(self):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_geometry_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def temporalAccumulate(self, params=None, current=None, history=None, shape=None, colourOut=None, historyOut=None, momentsOut=None):
+        """twk_temporal_accumulate: reprojects the history through its camera and merges it with the current frame's samples by
+        sample count. params: L.Temporal (None = the defaults). Without `current` the handle's own accumulation buffer, moments,
+        geometry AOV and camera are the frame and the history is what the previous call kept (readTemporal, readTemporalMoments,
+        temporalDevicePointers hand out the result). Otherwise current / history are L.TemporalFrame of device pointers to shape =
+        (height, width) pixels (history None: every pixel passes through) and colourOut / historyOut / momentsOut device pointers or None."""
+        tp = params if params is not None else L.Temporal()
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda f: None if f is None else C.byref(f)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate(self._h, C.byref(tp), ref(current), ref(history), int(w), int(h), ptr(colourOut), ptr(historyOut), ptr(momentsOut)))
+
+    def temporalReset(self):
+        """twk_temporal_reset: drops the history of the own-buffer form; the next temporalAccumulate() copies its frame through."""
+        L.check(L.lib.twk_temporal_reset(self._h))
+
+    def temporalDevicePointers(self):
+        """(colour pointer, bytes, moments pointer, bytes) of the own-buffer form's result: denoise(beauty=colour, moments=moments, ...)."""
+        c, cn, m, mn = C.c_void_p(), C.c_size_t(0), C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_temporal_device_pointers(self._h, C.byref(c), C.byref(cn), C.byref(m), C.byref(mn)))
+        return c.value, cn.value, m.value, mn.value
+
+    def readTemporal(self):
+        """The merged colour of the own-buffer form: float32 [height, launchWidth, 4] (widened exactly in half mode)."""
+        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_temporal(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def readTemporalMoments(self):
+        """The merged luminance moments of the own-buffer form: float32 [height, launchWidth, 4] = (mean, M2, n, 0)."""
+        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_temporal_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
     def setTimeView(self, enable=True):
         """≙ USE_TIME_VIEW: alpha of the accumulation buffer = running mean of the sample's shader-clock cycles x clockFactor x 1e-9."""
         L.check(L.lib.twk_set_time_view(self._h, int(bool(enable))))

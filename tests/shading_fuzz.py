@@ -21,7 +21,7 @@ from procedural import albedo_checker, cutout_slots, environment_hdr
 WIDTH, HEIGHT = 61, 37  # neither a multiple of the 8 x 8 tile nor of 256 paths
 
 # Bytes of a record in the tables the shade kernel stages in LDS, and the two budgets launchShade compares their sum with. The host
-# test checks these against the product's sources (static_asserts of device_api.hip, #defines of shade_kernels.hip).
+# test checks these against the product's sources (static_asserts of device_handle.h, #defines of shade_kernels.hip).
 INSTANCE_BYTES, MATERIAL_BYTES, LIGHT_BYTES = 128, 64, 80
 SORT_TABLE_BYTES, TABLE_BYTES = 8192, 20480
 BANDS = ("small", "mid", "large")

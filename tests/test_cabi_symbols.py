@@ -54,24 +54,30 @@ def test_product_does_not_link_or_import_the_oracle():
 
 def test_every_entry_point_is_a_function_try_block():
     """No C++ exception may cross the extern "C" boundary (the reference throws std::runtime_error, inc/CheckMacros.h:38-80;
-    a C caller cannot catch it): every definition of an `int twk_*(...)` entry point in the two files that hold them is a
-    function-try-block ending in TWK_CATCH("<its own name>"), except the few one-liners that cannot throw."""
+    a C caller cannot catch it): every definition of an `int twk_*(...)` entry point in the files that hold them (every
+    csrc/*.hip and host/host_cabi.cpp) is a function-try-block ending in TWK_CATCH("<its own name>"), except the few one-liners
+    that cannot throw; and every declared entry point is defined exactly once across them."""
     cannot_throw = {"twk_abi_version", "twk_app_destroy"}  # return a constant / delete a pointer
-    seen = set()
-    for rel in ("csrc/device_api.hip", "csrc/host/host_cabi.cpp"):
-        text = open(os.path.join(ROOT, "tweeker_raytracer_amd", rel)).read()
+    csrc = os.path.join(ROOT, "tweeker_raytracer_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) + ["host/host_cabi.cpp"]
+    assert len(files) > 2
+    seen = []
+    for rel in files:
+        text = open(os.path.join(csrc, rel)).read()
         for m in re.finditer(r"^int (twk_[a-z0-9_]+)\s*\(([^)]*)\)\s*\n(\S+)", text, flags=re.M):
             name, following = m.group(1), m.group(3)
-            seen.add(name)
+            seen.append(name)
             if name in cannot_throw:
                 continue
             assert following == "try", f"{rel}: {name} is not a function-try-block"
             assert f'TWK_CATCH("{name}")' in text, f"{rel}: {name} has no TWK_CATCH of its own"
         for m in re.finditer(r"^int (twk_[a-z0-9_]+)\s*\([^)]*\)\s*\{", text, flags=re.M):  # one-line definitions
-            seen.add(m.group(1))
+            seen.append(m.group(1))
             assert m.group(1) in cannot_throw, f"{rel}: {m.group(1)} is defined without a try block"
     declared = set(_header_functions()) - {"twk_last_error"}
-    assert declared <= seen, declared - seen
+    assert declared <= set(seen), declared - set(seen)
+    for name in declared:
+        assert seen.count(name) == 1, f"{name} is defined {seen.count(name)} times"
 
 
 def test_bench_carries_pmc_traffic_only_for_the_matching_launch_size():

@@ -1,4 +1,4 @@
-"""-m gpu: a wavefront pass cut into 1, 2, 3 and 4 lanes (TWK_PASS_LANES; device_api.hip laneParams). Every path stream of a
+"""-m gpu: a wavefront pass cut into 1, 2, 3 and 4 lanes (TWK_PASS_LANES; device_pass.hip laneParams). Every path stream of a
 lane starts at an offset of its own kind (device_types.h TWK_PATH_STREAMS: by queue record or by path); a stream that is
 forgotten there, or given the wrong kind, makes two lanes write over each other. So the image of a pass is the same bit for
 bit for every lane count, and the one-lane image is the oracle's.

@@ -1,6 +1,6 @@
 """-m gpu: the build- and pass-level shortcuts of round 3 change no bit of any image.
 
-  * small flattened instances as direct leaves of the top level (device_api.hip twk_build)
+  * small flattened instances as direct leaves of the top level (device_scene.hip twk_build)
   * wide-node cuts chosen by expected node visits (bvh_build.hip refitKernel)
   * seven against six resident blocks per CU of the traversal kernel (device_types.h TWK_TRACE_WAVES7)
   * primary rays computed by the first traversal / shade launch instead of written by generateKernel

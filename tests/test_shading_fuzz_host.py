@@ -36,7 +36,7 @@ def test_same_seed_gives_byte_equal_arrays():
 
 def test_predictions_use_the_products_byte_sizes(twk):
     csrc = os.path.join(ROOT, "tweeker_raytracer_amd", "csrc")
-    api = open(os.path.join(csrc, "device_api.hip")).read()
+    api = open(os.path.join(csrc, "device_handle.h")).read()
     shade = open(os.path.join(csrc, "shade_kernels.hip")).read()
     assert int(re.search(r"static_assert\(sizeof\(DevInstance\) == (\d+)", api).group(1)) == F.INSTANCE_BYTES
     assert int(re.search(r"static_assert\(sizeof\(DevMaterial\) == (\d+)", api).group(1)) == F.MATERIAL_BYTES

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernels of one wavefront pass from a rocprofv3 kernel trace CSV, all queues, in start order, with the queue each ran on:
-shows whether the lanes of a pass (device_api.hip renderPass) overlap. usage: tools/lane_timeline.py <kernel_trace.csv> [pass index]"""
+shows whether the lanes of a pass (device_pass.hip renderPass) overlap. usage: tools/lane_timeline.py <kernel_trace.csv> [pass index]"""
 import csv, sys
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if any(k in r['Kernel_Name'] for k in ('traceKernel<', 'shadeKernel', 'generateKernel', 'accumulateKernel'))]
 rows.sort(key=lambda r: int(r['Start_Timestamp']))

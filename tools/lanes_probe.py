@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pass lanes (device_api.hip renderPass): rate of C2 at several pass sizes with the pass cut into 1 / 2 / 3 lanes
+"""Pass lanes (device_pass.hip renderPass): rate of C2 at several pass sizes with the pass cut into 1 / 2 / 3 lanes
 (TWK_PASS_LANES), the image checked against the one-lane image bit for bit.
 usage (GPU box): python tools/lanes_probe.py [batch ...]"""
 import json

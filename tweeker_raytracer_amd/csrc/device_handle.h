@@ -1,0 +1,226 @@
+// The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
+// readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
+// tonemap, denoiser, temporal), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+#pragma once
+#include "device_types.h"
+#include "bvh_build.h"
+#include "denoise_device.h"
+#include "temporal_device.h"
+#include "error_state.h"
+
+#include <string>
+#include <vector>
+
+namespace twk {
+void launchTrace(const LaunchParams& p, int depth, bool count, const TraceBuild& build, int gridBlocks, hipStream_t stream);
+void launchTraceQuery(const LaunchParams& p, const float* rays, unsigned int numRays, int anyHit, float* tBetaGamma, int* ids, int gridBlocks, hipStream_t stream);
+void launchGenerate(const LaunchParams& p, hipStream_t stream);
+int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
+void shadeBuildSlots(uint64_t mask[2]);
+void launchTileEntries(const LaunchParams& p, const float4* topTable, int tilesX, int tilesY, int4* out, hipStream_t stream);
+void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream);
+void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
+                      int tileSizeX, int tileShiftX, int tileShiftY, hipStream_t stream);
+void launchMathTap(int op, const float* x, const float* y, float* out, size_t n, hipStream_t stream);
+void launchStreamCopy(const float4* src, float4* dst, size_t n, hipStream_t stream);
+void launchGatherProbeFill(float4* table, size_t count, unsigned int lines, hipStream_t stream);
+void launchGatherProbe(const float4* table, unsigned int lines, int steps, float* out, int gridBlocks, hipStream_t stream);
+void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
+void launchDenoisePrepare(const void* beauty, const void* albedo, const void* normal, bool half, float4* colour, float4* guideNormal, float4* guideAlbedo,
+                          const DenoiseConstants& k, hipStream_t stream);
+void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, const float4* sampled, float minSamples, hipStream_t stream);
+void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
+void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
+void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream);
+void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
+                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
+}
+
+using namespace twk;
+
+#define HIP_TRY(call)                                                                              \
+  do {                                                                                             \
+    hipError_t e_ = (call);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return twkSetError((e_ == hipErrorOutOfMemory) ? TWK_ERROR_OUT_OF_MEMORY : TWK_ERROR_HIP,    \
+                         std::string(#call) + " failed: " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + std::to_string(__LINE__) + ")"); \
+  } while (0)
+
+static_assert(sizeof(TwkCameraDefinition) == 48, "CameraDefinition is 48 B (camera_definition.h:34-40)");
+static_assert(sizeof(TwkLightDefinition) == 80, "LightDefinition is 80 B (light_definition.h:42-59)");
+static_assert(sizeof(TwkTriangleAttributes) == 48, "TriangleAttributes is 48 B (vertex_attributes.h:34-40)");
+static_assert(sizeof(DevLight) == sizeof(TwkLightDefinition), "device light layout");
+static_assert(sizeof(DevMaterial) == 64, "MaterialDefinition is 64 B (material_definition.h:37-56)");
+static_assert(sizeof(DevInstance) == 128, "instance record");
+static_assert(sizeof(BvhNode) == 64, "BVH2 node");
+
+struct GeometryHost
+{
+  std::vector<TwkTriangleAttributes> attributes;
+  std::vector<unsigned int>          indices;
+  unsigned int attributeBase = 0, indexBase = 0;
+  int triangleBase = 0, nodeBase = 0, numTriangles = 0;
+  float rootBounds[6];
+};
+
+struct InstanceHost
+{
+  int   geometry;
+  float transform[12];
+  int   material, light;
+};
+
+struct TimedLaunch { hipEvent_t start, stop; int kind; };
+// What a table of primary-ray entry points (trace_kernels.hip tileEntryKernel) was built for: camera bits, frame, tree, tile
+// distribution. Compared with memcmp (as floats, TWK_NODE_CACHED | 1 rounded to TWK_NODE_CACHED | 0, a build serial
+// stopped counting at 2^24, and -0.0 compared equal to +0.0).
+struct TileEntriesKey
+{
+  uint32_t camera[12];
+  int32_t  resolution[2], topRoot, topRoot2, launchWidth, deviceCount, deviceIndex, tileSize[2], valid;
+  uint64_t buildSerial;
+};
+#define TWK_STATS_WORDS 192 // device words of TwkLaunchStats: [0, 24) traversal + shade totals, [24, 96) the shade phases (shade_device.h PhaseScope); twice: the time view's scratch copy
+#define TWK_COUNTER_WORDS (TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2)) // one lane's counter block
+
+struct TwkDevice_t
+{
+  int ordinal = 0, index = 0, count = 1, miss = 1;
+  int numCUs = 256;
+  hipStream_t stream = nullptr;
+
+  TwkDeviceState state;
+  bool stateSet = false;
+  int  launchWidth = 1;
+
+  std::vector<TwkCameraDefinition> cameras;
+  std::vector<TwkLightDefinition>  lights;
+  std::vector<DevMaterial>         materials;
+  std::vector<GeometryHost>        geometries;
+  std::vector<InstanceHost>        instances;
+  bool built = false;
+  bool twoLevel = true;                 // some instance is entered through the top level (else the soup is the whole scene)
+  int  flattenMaxTriangles = TWK_FLATTEN_TRIANGLES, flattenMaxReferences = TWK_FLATTEN_REFERENCES;
+  int  maxInstanceMaterial = -1, maxInstanceLight = -1; // largest indices the built scene's instances use
+  TwkBuildInfo buildInfo;
+
+  // device memory
+  float* d_camera = nullptr;
+  DevLight* d_lights = nullptr;
+  DevMaterial* d_materials = nullptr; int materialCapacity = 0;
+  float* d_attributes = nullptr; unsigned int* d_indices = nullptr;
+  BvhNode* d_nodes = nullptr; BvhNode* d_wideNodes = nullptr /* build-time only: full-precision wide nodes, freed once quantised */; float4* d_wideQ = nullptr; float4* d_triangles = nullptr; float4* d_shadeTriangles = nullptr; DevInstance* d_instances = nullptr;
+  bool directSmallLeaves = true; /* TWK_DIRECT_SMALL_LEAVES=0: A/B */ bool costedCuts = true; /* TWK_COSTED_CUTS=0: A/B */ bool fusedPrimary = true; /* TWK_FUSED_PRIMARY=0: A/B */ bool tileEntries = true; /* TWK_TILE_ENTRIES=0: A/B */ bool wideRoot = true; /* TWK_WIDE_ROOT=0: A/B */ int wideRoot1 = 0, wideRoot2 = TWK_BVH_SENTINEL; size_t wideNodesTotal = 0;
+  int4* d_tileEntries = nullptr; size_t tileEntriesCapacity = 0; TileEntriesKey tileEntriesKey = {}; uint64_t buildSerial = 0; // entry points of the primary rays (trace_kernels.hip tileEntryKernel) and what they were built for
+  float4* d_topNodes = nullptr; float4* d_topNodes7 = nullptr; bool topCache = true; int traceWavesForced = 0 /* TWK_TRACE_WAVES_RUNTIME: 6 or 7, 0 = by scene */; // TWK_TOP_CACHE=0 turns the LDS top-of-tree cache off (A/B)
+  float4* d_texels[3] = {nullptr, nullptr, nullptr};
+  float* d_envCDF_U = nullptr; float* d_envCDF_V = nullptr;
+  int tlasRoot = 0;
+  size_t totalNodes = 0, totalTriangles = 0;
+
+  // per-resolution streams
+  int allocatedPixels = 0;
+  void* d_streamBlock = nullptr; // one allocation carved into the SoA streams
+  // output and AOV running means: RGBA32F, or RGBA16F in the same (float4-typed) pointers when outputFormat is TWK_OUTPUT_HALF4
+  int outputFormat = TWK_OUTPUT_FLOAT4; // twk_set_output_format (≙ Optix7Gui USE_FP32_OUTPUT, app_config.h:57-59)
+  float4* d_outputInternal = nullptr;
+  float4* d_outputExternal = nullptr; size_t outputExternalBytes = 0;
+  bool outputFrame = false; // the external buffer is a shared full frame (twk_set_shared_frame)
+  unsigned int* d_counters = nullptr;
+  unsigned long long* d_stats = nullptr;
+  unsigned int* h_dropped = nullptr; unsigned int* d_dropped = nullptr; // pinned + device-mapped: LaunchParams::droppedPushes
+  int* d_spill = nullptr; size_t spillLanes = 0;
+  bool packedQueue = true; // TWK_PACKED_QUEUE=0: A/B
+  bool slimStreams = true; // TWK_SLIM_STREAMS=0: A/B (device_types.h LaunchParams::slimSlotBits)
+  uint64_t shadeBuilds[2] = {0, 0}; // the shadeKernel builds launched since the last reset, by launcher index (twk_debug_shade_builds)
+  int shadeSort = 1;      // TWK_SHADE_SORT=0: slot order (A/B); 1: class order in every launch but the first of a pass; 2: in the first too
+  float4* d_firstHit = nullptr; int* d_firstHitInstance = nullptr;
+  // denoiser AOVs (Optix7Gui raygeneration.cu:125-164): per-path values of a pass and their running means per launch index
+  bool aovEnabled = false; int shaderVariant = TWK_SHADERS_RTIGO3;
+  bool nextEventEstimation = true, debugExceptions = false; // twk_set_next_event_estimation / twk_set_debug_exceptions (≙ shaders/config.h:50-56)
+  bool timeView = false; float* d_pathTime = nullptr; int timePaths = 0; // twk_set_time_view
+  float4* d_pathAlbedo = nullptr; float4* d_pathNormal = nullptr; int aovPaths = 0;
+  float4* d_aovAlbedo = nullptr; float4* d_aovNormal = nullptr; int aovPixels = 0;
+  // twk_enable_moments: luminance moments (mean, M2, n, 0) of the samples per launch index, always f32 (LaunchParams::moments)
+  bool momentsEnabled = false; float4* d_moments = nullptr; int momentsPixels = 0;
+  unsigned int sampleOffset = 0; // twk_set_sample_offset (LaunchParams::sampleOffset)
+  // twk_enable_geometry: the geometry AOV (world position, instance + 1) per launch index, always f32; geometryValid: rendered by
+  // twk_render_geometry since the last change of camera, state or scene
+  bool geometryEnabled = false; float4* d_geometry = nullptr; int geometryPixels = 0; bool geometryValid = false;
+  // twk_temporal_accumulate, own-buffer form: two sets of three f32 streams (colour, moments, geometry) — the set temporalKept holds
+  // what the last call kept (its camera: temporalCamera), the other receives this call's — and the merged colour in the output format
+  float4* d_temporal[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; void* d_temporalColour = nullptr;
+  int temporalWidth = 0, temporalHeight = 0, temporalFormat = TWK_OUTPUT_FLOAT4, temporalKept = 0; bool temporalHasHistory = false, temporalValid = false;
+  TwkCameraDefinition temporalCamera;
+  int lastPassCount = 0, lastPassPixels = 0; // samples per launch index and launch indices of the last pass, while its pathRadiance stream still holds them (twk_debug_read_path_radiance); 0: none
+  // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) in the output format it was
+  // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
+  void* d_denoised = nullptr; int denoisedWidth = 0, denoisedHeight = 0, denoisedFormat = TWK_OUTPUT_FLOAT4; bool denoisedValid = false;
+  float4* d_denoiseStreams = nullptr; size_t denoiseStreamPixels = 0;
+  int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
+  bool captureFirstHits = false;
+  bool statsEnabled = false;
+  bool profileEnabled = false;
+  std::vector<TimedLaunch> timed; size_t timedUsed = 0;
+  float profileMs[TWK_KERNEL_COUNT] = {0, 0, 0, 0, 0};
+  int   profileLaunches[TWK_KERNEL_COUNT] = {0, 0, 0, 0, 0};
+  // Deferred launches: twk_launch only records the iteration; consecutive iterations are rendered together as one
+  // wavefront pass of up to batchMax samples per pixel when the batch is full or anything observes the device.
+  int   batchMax = 64;
+  size_t streamBudgetBytes = 0; // TWK_STREAM_BUDGET_MB: cap on the path streams of one pass (0 = device memory is the limit)
+  unsigned int pendingFirst = 0;
+  int   pendingCount = 0;
+  int   allocatedPaths = 0;
+
+  // Pass lanes: a wavefront pass may be cut into up to TWK_MAX_LANES independent sub-passes over disjoint path ranges, each a
+  // chain of generate / trace / shade launches on a stream of its own (lane 0 = `stream`), joined before the accumulate
+  // kernel. Small passes are bound by the dependent-launch chain and the longest ray of each launch, not by throughput:
+  // two chains side by side fill each other's gaps (renderPass).
+  hipStream_t laneStream[TWK_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t  laneDone[TWK_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t  laneFork = nullptr;
+  int   lanesForced = 0; // TWK_PASS_LANES: 0 = choose by pass size
+  int   laneTraceWaves = 0; // TWK_LANE_TRACE_WAVES: trace blocks per CU of each lane (0 = TWK_TRACE_WAVES / lanes)
+
+  std::vector<std::vector<char>> hostScene; // twk_debug_snapshot_scene: host copies of the scene arrays
+
+  LaunchParams params;
+  BvhBuilder builder;
+};
+
+template<typename T> inline void freeDevice(T*& p) { if (p) { (void) hipFree(p); p = nullptr; } }
+
+// Bytes of one output / AOV pixel in the handle's output format: RGBA32F 16, RGBA16F 8 (Optix7Gui Half4)
+inline size_t pixelBytes(int format) { return (format == TWK_OUTPUT_HALF4) ? 8 : sizeof(float4); }
+inline size_t pixelBytes(TwkDevice dev) { return pixelBytes(dev->outputFormat); }
+inline bool halfOutput(TwkDevice dev) { return dev->outputFormat == TWK_OUTPUT_HALF4; }
+// Pixels of the buffer the handle accumulates into: the shared W x H frame, or its packed launchWidth x H buffer
+inline size_t outputPixels(TwkDevice dev)
+{
+  return (size_t) ((dev->d_outputExternal && dev->outputFrame) ? dev->state.resolution[0] : dev->launchWidth) * dev->state.resolution[1];
+}
+
+// Scratch device allocation of one call; freed on every return path.
+template<typename T> struct ScopedDeviceBuffer
+{
+  T* ptr = nullptr;
+  ~ScopedDeviceBuffer() { if (ptr) (void) hipFree(ptr); }
+  hipError_t allocate(size_t count) { return hipMalloc(&ptr, count * sizeof(T)); }
+};
+
+// Helpers more than one of the files needs; each is defined in the file that owns it
+namespace twk {
+// device_pass.hip
+int activate(TwkDevice dev, const char* where, bool flush = true);
+int calculateShift(int size);
+TraceBuild traceBuild(TwkDevice dev, bool primary);
+void refreshParams(TwkDevice dev);
+int slimSlotBits(TwkDevice dev);
+int ensureStreams(TwkDevice dev, int samples = 1);
+int checkDroppedPushes(TwkDevice dev, const char* where);
+// device_api.hip
+int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int enable);
+int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);
+// device_post.hip
+void dropTemporal(TwkDevice dev);
+}

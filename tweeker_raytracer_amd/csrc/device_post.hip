@@ -1,0 +1,438 @@
+// What runs on finished pictures: compositor, tonemapper, the a-trous denoiser (≙ optixDenoiserInvoke, Optix7Gui
+// Application.cpp:2478) and the temporal reprojection.
+#include "device_handle.h"
+
+#include <cmath>
+#include <cstring>
+
+// Frees the streams of twk_temporal_accumulate's own-buffer form: the next call has no history
+void twk::dropTemporal(TwkDevice dev)
+{
+  for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
+  freeDevice(dev->d_temporalColour);
+  dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
+}
+
+// =============================================================================================
+extern "C" {
+
+static int compositor(TwkDevice dev, const void* tiles, void* output, bool half, const char* where)
+{
+  int rc = activate(dev, where); if (rc) return rc;
+  if (!tiles || !output) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + ": NULL buffer");
+  if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": twk_set_state first");
+  launchCompositor(tiles, output, half, dev->state.resolution[0], dev->state.resolution[1],
+                   dev->launchWidth, dev->count, dev->state.tileSize[0], calculateShift(dev->state.tileSize[0]), calculateShift(dev->state.tileSize[1]), dev->stream);
+  HIP_TRY(hipGetLastError());
+  return TWK_SUCCESS;
+}
+
+int twk_compositor(TwkDevice dev, const void* tiles, void* output)
+try
+{
+  return compositor(dev, tiles, output, false, "twk_compositor");
+}
+TWK_CATCH("twk_compositor")
+
+int twk_compositor_half(TwkDevice dev, const void* tiles, void* output)
+try
+{
+  return compositor(dev, tiles, output, true, "twk_compositor_half");
+}
+TWK_CATCH("twk_compositor_half")
+
+static int tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* src, bool half, size_t numPixels, unsigned char* rgb8Host)
+{
+  if (numPixels == 0) return TWK_SUCCESS;
+  ScopedDeviceBuffer<unsigned char> ldr;
+  HIP_TRY(ldr.allocate(numPixels * 3));
+  launchTonemap(src, half, ldr.ptr, numPixels, *tm, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rgb8Host, ldr.ptr, numPixels * 3, hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return TWK_SUCCESS;
+}
+
+int twk_tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaDevice, size_t numPixels, unsigned char* rgb8Host)
+try
+{
+  int rc = activate(dev, "twk_tonemap"); if (rc) return rc;
+  if (!tm || !rgb8Host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: NULL argument");
+  if (!(tm->gamma > 0.0f) || !(tm->whitePoint > 0.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: gamma and whitePoint must be positive");
+  if (rgbaDevice) return tonemap(dev, tm, rgbaDevice, false, numPixels, rgb8Host);
+  // the handle's own buffer, in whatever format it holds
+  const float4* src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+  if (!src || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_tonemap: nothing has been rendered");
+  if (numPixels != (size_t) dev->launchWidth * dev->state.resolution[1]) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: numPixels must be launchWidth*height for the handle's own buffer");
+  return tonemap(dev, tm, src, halfOutput(dev), numPixels, rgb8Host);
+}
+TWK_CATCH("twk_tonemap")
+
+int twk_tonemap_half(TwkDevice dev, const TwkTonemapper* tm, const void* rgbaHalfDevice, size_t numPixels, unsigned char* rgb8Host)
+try
+{
+  int rc = activate(dev, "twk_tonemap_half"); if (rc) return rc;
+  if (!tm || !rgbaHalfDevice || !rgb8Host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap_half: NULL argument");
+  if (!(tm->gamma > 0.0f) || !(tm->whitePoint > 0.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap_half: gamma and whitePoint must be positive");
+  return tonemap(dev, tm, rgbaHalfDevice, true, numPixels, rgb8Host);
+}
+TWK_CATCH("twk_tonemap_half")
+
+// ---- denoiser ---------------------------------------------------------------------------------
+int twk_denoiser_defaults(TwkDenoiser* dn)
+try
+{
+  if (!dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoiser_defaults: NULL argument");
+  dn->inputKind = TWK_DENOISER_RGB_ALBEDO_NORMAL;
+  dn->iterations = 3;
+  dn->sigmaColor = 8.0f; dn->sigmaNormal = 0.3f; dn->sigmaAlbedo = 0.1f;
+  dn->demodulateAlbedo = 1;
+  dn->blendFactor = 0.0f;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoiser_defaults")
+
+static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
+{
+  if (!a || !b) return false;
+  const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+  return x < y + bBytes && y < x + aBytes;
+}
+static bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
+
+// twk_denoise (dv NULL), twk_denoise_variance and twk_denoise_variance_sampled (minSamples > 0; `moments`: the caller's buffer
+// beside an explicit beauty): `name` is the entry point, for its error texts
+static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised,
+                   int minSamples = 0, const void* moments = nullptr)
+{
+  const bool sampled = (minSamples > 0);
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  const int kind = dn->inputKind;
+  if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "unknown inputKind");
+  if (dn->iterations < 0 || dn->iterations > 8) return refuse(TWK_ERROR_INVALID_VALUE, "iterations must be in [0, 8]");
+  if ((!dv && !(dn->sigmaColor > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
+    return refuse(TWK_ERROR_INVALID_VALUE, "the sigma of every guide in use must be positive");
+  {
+    // 1 / sigma^2 is what the kernels multiply by: a sigma whose square underflows would make it inf, and 0 x inf the centre tap's NaN
+    const float sigmas[3] = {dv ? 1.0f : dn->sigmaColor, (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? dn->sigmaNormal : 1.0f, (kind >= TWK_DENOISER_RGB_ALBEDO) ? dn->sigmaAlbedo : 1.0f};
+    for (const float sigma : sigmas)
+      if (!std::isfinite(1.0f / (sigma * sigma))) return refuse(TWK_ERROR_INVALID_VALUE, "a sigma is too small: 1 / sigma^2 is not a finite float");
+  }
+  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "blendFactor must be in [0, 1]");
+  if (dn->demodulateAlbedo && kind == TWK_DENOISER_RGB) return refuse(TWK_ERROR_INVALID_VALUE, "demodulateAlbedo needs an albedo guide (inputKind TWK_DENOISER_RGB has none)");
+  if (dv)
+  {
+    if (!(dv->fireflyThreshold >= 0.0f) || !std::isfinite(dv->fireflyThreshold)) return refuse(TWK_ERROR_INVALID_VALUE, "fireflyThreshold must be >= 0 (0 = no clamp) and finite");
+    if (!(dv->sigmaLuminance > 0.0f) || !std::isfinite(dv->sigmaLuminance)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaLuminance must be > 0 and finite");
+  }
+  int rc = activate(dev, name); if (rc) return rc;
+
+  const bool own = (beauty == nullptr);
+  if (own)
+  {
+    if (albedo || normal || moments) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
+    if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
+    if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
+    beauty = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+    if (!beauty) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+    width = dev->launchWidth; height = dev->state.resolution[1];
+    if (kind != TWK_DENOISER_RGB)
+    {
+      if (!dev->aovEnabled || !dev->d_aovAlbedo || !dev->d_aovNormal || (size_t) dev->aovPixels < (size_t) width * height)
+        return refuse(TWK_ERROR_INVALID_STATE, "a guided inputKind on the handle's own buffers needs a render with twk_enable_aov(1)");
+      albedo = dev->d_aovAlbedo;
+      if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = dev->d_aovNormal;
+    }
+    if (sampled)
+    {
+      if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < (size_t) width * height)
+        return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+      moments = dev->d_moments;
+    }
+  }
+  else
+  {
+    if (width < 1 || height < 1) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
+    if ((kind >= TWK_DENOISER_RGB_ALBEDO && !albedo) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !normal)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL guide buffer for a guide the inputKind uses");
+    if (kind < TWK_DENOISER_RGB_ALBEDO) albedo = nullptr;        // guides the kind does not use are not read
+    if (kind < TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = nullptr;
+    if (sampled && !moments) return refuse(TWK_ERROR_INVALID_VALUE, "NULL moments buffer beside an explicit beauty buffer");
+  }
+  const size_t numPixels = (size_t) width * height, bytes = numPixels * pixelBytes(dev);
+  if (denoised && (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes) || (sampled && overlaps(denoised, bytes, moments, numPixels * sizeof(float4)))))
+    return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
+
+  void* target = denoised;
+  if (!target)
+  {
+    if (!dev->d_denoised || dev->denoisedWidth != width || dev->denoisedHeight != height || dev->denoisedFormat != dev->outputFormat)
+    {
+      HIP_TRY(hipStreamSynchronize(dev->stream));
+      freeDevice(dev->d_denoised); dev->denoisedValid = false;
+      HIP_TRY(hipMalloc(&dev->d_denoised, bytes));
+      dev->denoisedWidth = width; dev->denoisedHeight = height; dev->denoisedFormat = dev->outputFormat;
+    }
+    target = dev->d_denoised;
+  }
+  if (dn->iterations == 0 || dn->blendFactor == 1.0f)
+  {
+    HIP_TRY(hipMemcpyAsync(target, beauty, bytes, hipMemcpyDeviceToDevice, dev->stream)); // the input's bits
+  }
+  else
+  {
+    if (dev->denoiseStreamPixels < numPixels)
+    {
+      HIP_TRY(hipStreamSynchronize(dev->stream));
+      freeDevice(dev->d_denoiseStreams); dev->denoiseStreamPixels = 0;
+      HIP_TRY(hipMalloc(&dev->d_denoiseStreams, numPixels * 4 * sizeof(float4)));
+      dev->denoiseStreamPixels = numPixels;
+    }
+    float4* colour[2] = {dev->d_denoiseStreams, dev->d_denoiseStreams + numPixels};
+    float4* guideNormal = dev->d_denoiseStreams + 2 * numPixels;
+    float4* guideAlbedo = dev->d_denoiseStreams + 3 * numPixels;
+    DenoiseConstants k;
+    k.width = width; k.height = height;
+    k.invColor  = dv ? 0.0f : 1.0f / (dn->sigmaColor * dn->sigmaColor);
+    k.invNormal = (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? 1.0f / (dn->sigmaNormal * dn->sigmaNormal) : 0.0f;
+    k.invAlbedo = (kind >= TWK_DENOISER_RGB_ALBEDO) ? 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo) : 0.0f;
+    k.blendFactor = dn->blendFactor;
+    k.demodulate = dn->demodulateAlbedo ? 1 : 0;
+    k.fireflyThreshold = dv ? dv->fireflyThreshold : 0.0f;
+    k.sigmaLuminance = dv ? dv->sigmaLuminance : 0.0f;
+    // the variance-guided mode: prepare writes the pong stream and the moments pass the ping stream (clamped colour, variance in
+    // .w), so that the levels ping-pong as without it and the mode needs no stream of its own
+    launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[dv ? 1 : 0], guideNormal, guideAlbedo, k, dev->stream);
+    if (dv) launchDenoiseMoments(kind, colour[1], guideNormal, guideAlbedo, colour[0], k, sampled ? static_cast<const float4*>(moments) : nullptr, (float) minSamples, dev->stream);
+    for (int level = 0; level < dn->iterations; ++level)
+      launchDenoiseLevel(kind, (1 << level) <= dev->denoiseLdsMaxStep, dv != nullptr, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream);
+    launchDenoiseFinish(beauty, halfOutput(dev), colour[dn->iterations & 1], normal ? guideNormal : nullptr, albedo ? guideAlbedo : nullptr, target, k, dev->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!denoised) dev->denoisedValid = true;
+  return TWK_SUCCESS;
+}
+
+int twk_denoise(TwkDevice dev, const TwkDenoiser* dn, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL device handle");
+  if (!dn) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise: NULL parameters");
+  return denoise("twk_denoise", dev, dn, nullptr, beauty, albedo, normal, width, height, denoised);
+}
+TWK_CATCH("twk_denoise")
+
+int twk_denoiser_variance_defaults(TwkDenoiserVariance* dv)
+try
+{
+  if (!dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoiser_variance_defaults: NULL argument");
+  dv->fireflyThreshold = 3.0f;
+  dv->sigmaLuminance = 4.0f;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoiser_variance_defaults")
+
+int twk_denoise_variance(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance: NULL device handle");
+  if (!dn || !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance: NULL parameters");
+  return denoise("twk_denoise_variance", dev, dn, dv, beauty, albedo, normal, width, height, denoised);
+}
+TWK_CATCH("twk_denoise_variance")
+
+int twk_denoise_variance_sampled(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, int minSamples, const void* beauty, const void* albedo, const void* normal,
+                                 const void* moments, int width, int height, void* denoised)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance_sampled: NULL device handle");
+  if (!dn || !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance_sampled: NULL parameters");
+  if (minSamples < 2) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_variance_sampled: minSamples must be >= 2 (one sample has no variance)");
+  return denoise("twk_denoise_variance_sampled", dev, dn, dv, beauty, albedo, normal, width, height, denoised, minSamples, moments);
+}
+TWK_CATCH("twk_denoise_variance_sampled")
+
+// twk_read_denoised and twk_read_denoised_raw: `raw`, the pixels as they are (`size` in bytes); else RGBA32F (`size` in floats)
+static int readDenoised(TwkDevice dev, void* host, size_t size, bool raw, const char* where)
+{
+  int rc = activate(dev, where); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + ": NULL buffer");
+  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": no twk_denoise into the internal buffer yet");
+  const size_t n = (size_t) dev->denoisedWidth * dev->denoisedHeight;
+  if (size != n * (raw ? pixelBytes(dev) : 4))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + (raw ? ": buffer must hold width*height pixels of the output format" : ": buffer must hold width*height*4 floats of the denoised picture"));
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return readPixels(dev, dev->d_denoised, host, n, raw);
+}
+
+int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats)
+try
+{
+  return readDenoised(dev, rgbaHost, numFloats, false, "twk_read_denoised");
+}
+TWK_CATCH("twk_read_denoised")
+
+int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes)
+try
+{
+  return readDenoised(dev, host, bytes, true, "twk_read_denoised_raw");
+}
+TWK_CATCH("twk_read_denoised_raw")
+
+int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
+try
+{
+  int rc = activate(dev, "twk_get_denoised_device_pointer"); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_denoised_device_pointer: NULL argument");
+  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_denoised_device_pointer: no twk_denoise into the internal buffer yet");
+  *dptr = dev->d_denoised;
+  if (bytes) *bytes = (size_t) dev->denoisedWidth * dev->denoisedHeight * pixelBytes(dev);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_denoised_device_pointer")
+
+int twk_temporal_defaults(TwkTemporal* tp)
+try
+{
+  if (!tp) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_temporal_defaults: NULL argument");
+  tp->maxHistory = TWK_TEMPORAL_MAX_HISTORY; tp->positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_defaults")
+
+int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history, int width, int height,
+                            void* colourOut, void* historyOut, void* momentsOut)
+try
+{
+  const char* name = "twk_temporal_accumulate";
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  int rc = activate(dev, name); if (rc) return rc;
+  TwkTemporal defaults; defaults.maxHistory = TWK_TEMPORAL_MAX_HISTORY; defaults.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  if (!tp) tp = &defaults;
+  if (tp->maxHistory < 1) return refuse(TWK_ERROR_INVALID_VALUE, "maxHistory must be >= 1");
+  if (!(tp->positionTolerance >= 0.0f) || !finite1(tp->positionTolerance)) return refuse(TWK_ERROR_INVALID_VALUE, "positionTolerance must be >= 0 and finite");
+  TemporalConstants k;
+  memset(&k, 0, sizeof(k));
+  k.maxHistory = (float) tp->maxHistory; k.tol2 = tp->positionTolerance * tp->positionTolerance;
+
+  const bool own = (current == nullptr);
+  const void* colour; const float4 *moments, *geometry, *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
+  const TwkCameraDefinition* hCamera = nullptr;
+  int keep = 0;
+  if (own)
+  {
+    if (history || colourOut || historyOut || momentsOut || width || height) return refuse(TWK_ERROR_INVALID_VALUE, "a history, outputs or a size without a current frame (pass both frames, or neither for the handle's own buffers)");
+    if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+    if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
+    width = dev->launchWidth; height = dev->state.resolution[1];
+    const size_t n = (size_t) width * height;
+    if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+    if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+    if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
+    colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+    if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+    if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
+    {
+      HIP_TRY(hipStreamSynchronize(dev->stream));
+      dropTemporal(dev);
+      for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
+      HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
+      dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
+    }
+    moments = dev->d_moments; geometry = dev->d_geometry;
+    if (dev->temporalHasHistory)
+    {
+      float4* const* h = dev->d_temporal[dev->temporalKept];
+      hColour = h[0]; hMoments = h[1]; hGeometry = h[2]; hCamera = &dev->temporalCamera;
+    }
+    keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
+    colourOut = dev->d_temporalColour; historyOut = dev->d_temporal[keep][0]; momentsOut = dev->d_temporal[keep][1];
+  }
+  else
+  {
+    if (width < 1 || height < 1 || (size_t) width * (size_t) height >= ((size_t) 1 << 31)) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
+    if (!current->colour || !current->moments || !current->geometry) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer in the current frame");
+    if (history && (!history->colour || !history->moments || !history->geometry)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer in the history frame");
+    colour = current->colour; moments = static_cast<const float4*>(current->moments); geometry = static_cast<const float4*>(current->geometry);
+    if (history)
+    {
+      hColour = static_cast<const float4*>(history->colour); hMoments = static_cast<const float4*>(history->moments); hGeometry = static_cast<const float4*>(history->geometry);
+      hCamera = &history->camera;
+    }
+    const size_t n = (size_t) width * height, wide = n * sizeof(float4), narrowBytes = n * pixelBytes(dev);
+    const void* outs[3] = {colourOut, historyOut, momentsOut}; const size_t outBytes[3] = {narrowBytes, wide, wide};
+    const void* ins[6] = {colour, moments, geometry, hColour, hMoments, hGeometry}; const size_t inBytes[6] = {narrowBytes, wide, wide, wide, wide, wide};
+    for (int o = 0; o < 3; ++o)
+    {
+      for (int i = 0; i < 6; ++i) if (overlaps(outs[o], outBytes[o], ins[i], inBytes[i])) return refuse(TWK_ERROR_INVALID_VALUE, "an output overlaps an input (the kernel gathers the history at other pixels)");
+      for (int j = o + 1; j < 3; ++j) if (overlaps(outs[o], outBytes[o], outs[j], outBytes[j])) return refuse(TWK_ERROR_INVALID_VALUE, "two outputs overlap");
+    }
+  }
+  k.width = width; k.height = height;
+  if (hCamera)
+  {
+    k.hasHistory = 1;
+    if (!temporalCamera(hCamera->P, k)) return refuse(TWK_ERROR_INVALID_VALUE, "the history's camera is degenerate: U, V, W are linearly dependent or not finite");
+  }
+  launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
+  HIP_TRY(hipGetLastError());
+  if (own)
+  {
+    HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, (size_t) width * height * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
+    dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
+  }
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_accumulate")
+
+int twk_temporal_reset(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_temporal_reset"); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  dropTemporal(dev);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_reset")
+
+int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colourBytes, void** moments, size_t* momentsBytes)
+try
+{
+  int rc = activate(dev, "twk_get_temporal_device_pointers"); if (rc) return rc;
+  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_temporal_device_pointers: no twk_temporal_accumulate on the handle's own buffers since the last reset");
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (colour) *colour = dev->d_temporalColour;
+  if (colourBytes) *colourBytes = n * pixelBytes(dev->temporalFormat);
+  if (moments) *moments = dev->d_temporal[dev->temporalKept][1];
+  if (momentsBytes) *momentsBytes = n * sizeof(float4);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_temporal_device_pointers")
+
+int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_temporal"); if (rc) return rc;
+  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal: NULL buffer");
+  if (!dev->temporalValid || dev->temporalFormat != dev->outputFormat) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal: no twk_temporal_accumulate on the handle's own buffers since the last reset");
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal: buffer must hold width*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return readPixels(dev, dev->d_temporalColour, rgbaHost, n, false);
+}
+TWK_CATCH("twk_read_temporal")
+
+int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_temporal_moments"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_moments: NULL buffer");
+  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal_moments: no twk_temporal_accumulate on the handle's own buffers since the last reset");
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_moments: buffer must hold width*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_temporal[dev->temporalKept][1], n * sizeof(float4), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_temporal_moments")
+
+} // extern "C"

@@ -1,0 +1,345 @@
+// Scene assembly and the acceleration-structure build behind the C ABI (≙ Device::createGeometry / createInstance / createTLAS,
+// reference apps/rtigo3/src/Device.cpp:1339-1500).
+#include "device_handle.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+// Inverse of a row-major 3x4 affine matrix in double, rounded once (OptiX derives the same matrix for
+// optixGetInstanceInverseTransformFromHandle, closesthit.cu:49-52).
+static void invertAffine(const float m[12], float inv[12])
+{
+  const double a00 = m[0], a01 = m[1], a02 = m[2],  t0 = m[3];
+  const double a10 = m[4], a11 = m[5], a12 = m[6],  t1 = m[7];
+  const double a20 = m[8], a21 = m[9], a22 = m[10], t2 = m[11];
+  const double c00 = a11 * a22 - a12 * a21;
+  const double c01 = a12 * a20 - a10 * a22;
+  const double c02 = a10 * a21 - a11 * a20;
+  const double det = a00 * c00 + a01 * c01 + a02 * c02;
+  const double r = 1.0 / det;
+  const double i00 = c00 * r, i01 = (a02 * a21 - a01 * a22) * r, i02 = (a01 * a12 - a02 * a11) * r;
+  const double i10 = c01 * r, i11 = (a00 * a22 - a02 * a20) * r, i12 = (a02 * a10 - a00 * a12) * r;
+  const double i20 = c02 * r, i21 = (a01 * a20 - a00 * a21) * r, i22 = (a00 * a11 - a01 * a10) * r;
+  inv[0] = (float) i00; inv[1] = (float) i01; inv[2]  = (float) i02; inv[3]  = (float) -(i00 * t0 + i01 * t1 + i02 * t2);
+  inv[4] = (float) i10; inv[5] = (float) i11; inv[6]  = (float) i12; inv[7]  = (float) -(i10 * t0 + i11 * t1 + i12 * t2);
+  inv[8] = (float) i20; inv[9] = (float) i21; inv[10] = (float) i22; inv[11] = (float) -(i20 * t0 + i21 * t1 + i22 * t2);
+}
+
+// =============================================================================================
+extern "C" {
+
+int twk_clear_scene(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_clear_scene"); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  dev->geometries.clear(); dev->instances.clear(); dev->built = false;
+  dev->geometryValid = false; dropTemporal(dev);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_clear_scene")
+
+int twk_add_geometry(TwkDevice dev, const TwkTriangleAttributes* attributes, size_t numAttributes,
+                     const unsigned int* indices, size_t numIndices, int* idGeometry)
+try
+{
+  int rc = activate(dev, "twk_add_geometry"); if (rc) return rc;
+  if (!attributes || !indices || numAttributes == 0 || numIndices == 0 || (numIndices % 3) != 0)
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_add_geometry: need attributes and a non-empty multiple of three indices");
+  // a leaf reference holds a 28-bit triangle slot (device_types.h BvhNode): refuse here what twk_build could not address
+  if (numIndices / 3 >= ((size_t) 1 << 28) || numAttributes >= ((size_t) 1 << 32))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_add_geometry: more than 2^28 - 1 triangles (or 2^32 - 1 vertices) in one geometry");
+  for (size_t i = 0; i < numIndices; ++i)
+    if (indices[i] >= numAttributes) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_add_geometry: index out of range");
+  GeometryHost g;
+  g.attributes.assign(attributes, attributes + numAttributes);
+  g.indices.assign(indices, indices + numIndices);
+  g.numTriangles = (int) (numIndices / 3);
+  dev->geometries.push_back(std::move(g));
+  dev->built = false;
+  if (idGeometry) *idGeometry = (int) dev->geometries.size() - 1;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_add_geometry")
+
+int twk_add_instance(TwkDevice dev, int idGeometry, const float transform[12], int idMaterial, int idLight, int* idInstance)
+try
+{
+  int rc = activate(dev, "twk_add_instance"); if (rc) return rc;
+  if (!transform || idGeometry < 0 || idGeometry >= (int) dev->geometries.size()) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_add_instance: bad geometry id");
+  if (idMaterial < 0) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_add_instance: an instance needs a material (Device.cpp:1429)");
+  InstanceHost inst;
+  inst.geometry = idGeometry; inst.material = idMaterial; inst.light = idLight;
+  memcpy(inst.transform, transform, sizeof(float) * 12);
+  dev->instances.push_back(inst);
+  dev->built = false;
+  if (idInstance) *idInstance = (int) dev->instances.size() - 1;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_add_instance")
+
+int twk_set_flatten_policy(TwkDevice dev, int maxTriangles, int maxReferences)
+try
+{
+  int rc = activate(dev, "twk_set_flatten_policy"); if (rc) return rc;
+  if (maxTriangles < 0 || maxReferences < 0) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_flatten_policy: limits must be >= 0");
+  dev->flattenMaxTriangles = maxTriangles; dev->flattenMaxReferences = maxReferences;
+  dev->built = false;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_set_flatten_policy")
+
+int twk_set_build_quality(TwkDevice dev, int quality)
+try
+{
+  int rc = activate(dev, "twk_set_build_quality"); if (rc) return rc;
+  if (quality != TWK_BUILD_LBVH && quality != TWK_BUILD_SAH) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_build_quality: unknown quality");
+  dev->builder.setQuality(quality);
+  dev->built = false;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_set_build_quality")
+
+int twk_get_build_info(TwkDevice dev, TwkBuildInfo* info)
+try
+{
+  if (!dev || !info) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_build_info: NULL argument");
+  if (!dev->built) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_build_info: twk_build has not been called");
+  refreshParams(dev); // the traversal kernel variant depends on the materials as they are now
+  dev->buildInfo.traceBlocksPerCU = (uint64_t) traceBuild(dev, false).blocksPerCU;
+  *info = dev->buildInfo;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_build_info")
+
+int twk_get_stream_layout(TwkDevice dev, int* layout)
+try
+{
+  if (!dev || !layout) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_stream_layout: NULL argument");
+  if (!dev->built) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_stream_layout: twk_build has not been called");
+  refreshParams(dev); // cutout opacity is a property of the materials as they are now
+  *layout = (slimSlotBits(dev) != 0) ? TWK_STREAMS_SLIM : TWK_STREAMS_FULL;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_stream_layout")
+
+int twk_build(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_build"); if (rc) return rc;
+  if (dev->geometries.empty() || dev->instances.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: the scene has no geometry or no instance");
+  dev->built = false; // until this build has succeeded: a failure below leaves no half-built scene to launch on
+  const auto buildStart = std::chrono::steady_clock::now();
+  TwkBuildInfo info;
+  memset(&info, 0, sizeof(info));
+  info.quality = dev->builder.quality();
+  int maxMaterial = -1, maxLight = -1;
+  for (const InstanceHost& inst : dev->instances)
+  {
+    if (inst.material >= (int) dev->materials.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance material index beyond twk_init_materials");
+    if (inst.light >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance light index beyond twk_init_lights");
+    if (inst.material > maxMaterial) maxMaterial = inst.material;
+    if (inst.light > maxLight) maxLight = inst.light;
+  }
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+
+  // Which instances are flattened (include/tweeker_hip.h twk_set_flatten_policy): those of tiny geometries and those
+  // whose geometry is referenced so rarely that instancing saves no memory worth the per-ray instance entry (ray
+  // transform, per-instance Woop constants, exit step). A flattened instance gets world-space triangle slots and an
+  // LBVH of its own whose root is spliced into the top level as an inner node: traversal walks from the top level
+  // straight into it with the untransformed ray.
+  const int numInstances = (int) dev->instances.size();
+  std::vector<int> references(dev->geometries.size(), 0);
+  for (const InstanceHost& inst : dev->instances) references[inst.geometry]++;
+  std::vector<char> flattened(numInstances, 0), needsBlas(dev->geometries.size(), 0);
+  int numEntered = 0, maxFlatTriangles = 0;
+  for (int i = 0; i < numInstances; ++i)
+  {
+    const int g = dev->instances[i].geometry;
+    flattened[i] = (dev->geometries[g].numTriangles <= dev->flattenMaxTriangles) || (references[g] <= dev->flattenMaxReferences);
+    if (flattened[i]) maxFlatTriangles = std::max(maxFlatTriangles, dev->geometries[g].numTriangles);
+    else { needsBlas[g] = 1; ++numEntered; }
+  }
+
+  // shared attribute / index arrays and the node / triangle budgets: one bottom level per geometry that is still
+  // entered through an instance, one world-space tree per flattened instance, the top level
+  size_t numAttr = 0, numIdx = 0, numTris = 0, numNodes = 0;
+  for (size_t k = 0; k < dev->geometries.size(); ++k)
+  {
+    GeometryHost& g = dev->geometries[k];
+    g.attributeBase = (unsigned int) numAttr; g.indexBase = (unsigned int) numIdx;
+    g.triangleBase = (int) numTris; g.nodeBase = (int) numNodes;
+    numAttr += g.attributes.size(); numIdx += g.indices.size();
+    if (needsBlas[k]) { numTris += (size_t) g.numTriangles; numNodes += (size_t) ((g.numTriangles > 1) ? g.numTriangles - 1 : 1); }
+  }
+  std::vector<int> flatTriangleBase(numInstances, -1), flatNodeBase(numInstances, -1);
+  for (int i = 0; i < numInstances; ++i)
+  {
+    if (!flattened[i]) continue;
+    const int n = dev->geometries[dev->instances[i].geometry].numTriangles;
+    flatTriangleBase[i] = (int) numTris; flatNodeBase[i] = (int) numNodes;
+    numTris += (size_t) n; numNodes += (size_t) ((n > 1) ? n - 1 : 1);
+  }
+  const int tlasBase = (int) numNodes;
+  numNodes += (size_t) ((numInstances > 1) ? numInstances - 1 : 1);
+  if (numTris >= ((size_t) 1 << 28) || numAttr >= ((size_t) 1 << 31) || numIdx >= ((size_t) 1 << 31))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: " + std::to_string(numTris) + " triangle slots; a leaf reference holds 28 bits of slot index");
+
+  freeDevice(dev->d_attributes); freeDevice(dev->d_indices); freeDevice(dev->d_nodes); freeDevice(dev->d_wideNodes); freeDevice(dev->d_wideQ); freeDevice(dev->d_triangles); freeDevice(dev->d_shadeTriangles); freeDevice(dev->d_instances);
+  HIP_TRY(hipMalloc(&dev->d_attributes, sizeof(TwkTriangleAttributes) * numAttr));
+  HIP_TRY(hipMalloc(&dev->d_indices, sizeof(unsigned int) * numIdx));
+  HIP_TRY(hipMalloc(&dev->d_nodes, sizeof(BvhNode) * numNodes));
+  HIP_TRY(hipMalloc(&dev->d_wideNodes, sizeof(BvhNode) * 2 * (numNodes + 2))); // + the two nodes of an 8-wide root (wideRootKernel)
+  HIP_TRY(hipMalloc(&dev->d_wideQ, sizeof(float4) * 4 * (numNodes + 2)));
+  HIP_TRY(hipMalloc(&dev->d_triangles, sizeof(float4) * 3 * numTris));
+  HIP_TRY(hipMalloc(&dev->d_shadeTriangles, sizeof(float4) * TWK_SHADE_RECORD * numTris));
+  HIP_TRY(hipMalloc(&dev->d_instances, sizeof(DevInstance) * numInstances));
+  for (const GeometryHost& g : dev->geometries)
+  {
+    HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
+    HIP_TRY(hipMemcpyAsync(dev->d_indices + g.indexBase, g.indices.data(), sizeof(unsigned int) * g.indices.size(), hipMemcpyHostToDevice, dev->stream));
+  }
+
+  if (const char* e = getenv("TWK_MAX_LEAF")) dev->builder.setMaxLeaf(atoi(e)); // tuning knob, default 2 triangles per leaf
+  ScopedDeviceBuffer<float> nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
+  if (dev->costedCuts) HIP_TRY(nodeCost.allocate(numNodes));
+  struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder}; // the array does not outlive this call
+  dev->builder.setNodeCost(nodeCost.ptr);
+  int maxEnteredHeight = 0, maxFlatHeight = 0, topHeight = 0; // binary-tree heights: what a traversal stack may have to hold
+  // bottom level: one LBVH per entered geometry, shared by all of its instances (Device.cpp:1339 caches the GAS per Triangles id)
+  for (size_t k = 0; k < dev->geometries.size(); ++k)
+  {
+    GeometryHost& g = dev->geometries[k];
+    if (!needsBlas[k]) continue;
+    HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes + 12 * (size_t) g.attributeBase, dev->d_indices + g.indexBase, g.numTriangles,
+                                        dev->d_nodes + g.nodeBase, dev->d_wideNodes + 2 * (size_t) g.nodeBase, g.nodeBase, dev->d_triangles, dev->d_shadeTriangles, g.triangleBase, g.rootBounds));
+    info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
+    maxEnteredHeight = std::max(maxEnteredHeight, dev->builder.lastHeight());
+  }
+
+  // instance records (shading reads them for every hit, flattened or not)
+  std::vector<DevInstance> records(numInstances);
+  for (int i = 0; i < numInstances; ++i)
+  {
+    const InstanceHost& inst = dev->instances[i];
+    const GeometryHost& g = dev->geometries[inst.geometry];
+    DevInstance& r = records[i];
+    memset(&r, 0, sizeof(r));
+    memcpy(r.objectToWorld, inst.transform, sizeof(float) * 12);
+    invertAffine(inst.transform, r.worldToObject);
+    r.blasRoot = flattened[i] ? flatNodeBase[i] : g.nodeBase; r.material = inst.material; r.light = inst.light;
+    r.triangleFirst = flattened[i] ? flatTriangleBase[i] : g.triangleBase; r.triangleCount = g.numTriangles;
+    r.attributeBase = g.attributeBase; r.indexBase = g.indexBase; r.geometry = inst.geometry;
+  }
+  HIP_TRY(hipMemcpyAsync(dev->d_instances, records.data(), sizeof(DevInstance) * numInstances, hipMemcpyHostToDevice, dev->stream));
+
+  // world-space trees of the flattened instances + the world boxes of all instances
+  std::vector<float4> boxLo(numInstances), boxHi(numInstances);
+  std::vector<int> leafPayload(numInstances);
+  ScopedDeviceBuffer<int4> soup;
+  if (maxFlatTriangles > 0) HIP_TRY(soup.allocate((size_t) maxFlatTriangles));
+  for (int i = 0; i < numInstances; ++i)
+  {
+    const InstanceHost& inst = dev->instances[i];
+    const GeometryHost& g = dev->geometries[inst.geometry];
+    if (flattened[i])
+    {
+      float bounds[6];
+      dev->builder.soupDescriptors(dev->stream, soup.ptr, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
+                                          dev->d_nodes + flatNodeBase[i], dev->d_wideNodes + 2 * (size_t) flatNodeBase[i], flatNodeBase[i],
+                                          dev->d_triangles, dev->d_shadeTriangles, flatTriangleBase[i], bounds, soup.ptr, dev->d_instances));
+      info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
+      maxFlatHeight = std::max(maxFlatHeight, dev->builder.lastHeight());
+      boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
+      boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
+      leafPayload[i] = ~flatNodeBase[i]; // child reference ~payload = the instance's root node: an inner reference
+      // A flattened instance of no more triangles than a leaf holds (a wall, the area light: two triangles) IS a leaf of the
+      // top level: its slots are referenced directly instead of through a one-node tree of two single-triangle leaves —
+      // one node visit and one leaf step less for every ray that crosses its box (C2: six of the eight instances).
+      if (dev->directSmallLeaves && g.numTriangles <= dev->builder.maxLeaf() && g.numTriangles <= 4)
+      {
+        leafPayload[i] = flatTriangleBase[i] | ((g.numTriangles - 1) << 28) | TWK_LEAF_WORLD;
+        info.directLeafInstances += 1;
+      }
+      continue;
+    }
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int corner = 0; corner < 8; ++corner)
+    {
+      const float x = g.rootBounds[(corner & 1) ? 3 : 0], y = g.rootBounds[(corner & 2) ? 4 : 1], z = g.rootBounds[(corner & 4) ? 5 : 2];
+      const float* m = inst.transform;
+      const float w[3] = { m[0] * x + m[1] * y + m[2] * z + m[3], m[4] * x + m[5] * y + m[6] * z + m[7], m[8] * x + m[9] * y + m[10] * z + m[11] };
+      for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], w[k]); hi[k] = fmaxf(hi[k], w[k]); }
+    }
+    for (int k = 0; k < 3; ++k)
+    {
+      // world box of an object-space box: pad for the rounding of the transform in both directions
+      const float e = 1.0e-5f * fmaxf(1.0f, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
+      lo[k] -= e; hi[k] += e;
+    }
+    boxLo[i] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+    boxHi[i] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    leafPayload[i] = i;
+  }
+  if (numInstances == 1 && flattened[0]) dev->tlasRoot = flatNodeBase[0]; // the one world-space tree IS the scene
+  else
+  {
+    HIP_TRY(dev->builder.buildInstances(dev->stream, boxLo.data(), boxHi.data(), leafPayload.data(), numInstances, dev->d_nodes + tlasBase, dev->d_wideNodes + 2 * (size_t) tlasBase, tlasBase));
+    dev->tlasRoot = tlasBase;
+    topHeight = dev->builder.lastHeight();
+  }
+  // Deepest stack a single-ray traversal can need (trace_device.h traverse(): at most one push per inner node on the path,
+  // plus the sentinel of an instance entry): the top level, then either a spliced world-space tree or an entered
+  // geometry's tree. The persistent kernel hands rays that outgrow its LDS stack to that traversal, whose stack holds
+  // TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL entries; a scene beyond that would lose subtrees silently, so it is refused.
+  const int traversalDepth = topHeight + std::max(maxFlatHeight, (numEntered > 0) ? 1 + maxEnteredHeight : 0);
+  int depthLimit = TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL - 2;
+  if (const char* e = getenv("TWK_MAX_TRAVERSAL_DEPTH")) depthLimit = std::min(depthLimit, atoi(e)); // test hook: a lower limit only
+  if (traversalDepth > depthLimit)
+  {
+    dev->built = false;
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: the acceleration structure is " + std::to_string(traversalDepth) + " levels deep (top " + std::to_string(topHeight) +
+                       ", flattened trees " + std::to_string(maxFlatHeight) + ", entered geometries " + std::to_string(maxEnteredHeight) + "); the traversal stacks hold " +
+                       std::to_string(TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL) + " entries" + (dev->builder.quality() == TWK_BUILD_SAH ? " (try twk_set_build_quality(TWK_BUILD_LBVH))" : ""));
+  }
+  // the persistent trace kernel reads the quantised copy of the wide nodes; the full-precision ones were scratch
+  // the root as two wide nodes where that pays (bvh_build.hip wideRootKernel)
+  dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
+  if (dev->wideRoot)
+  {
+    ScopedDeviceBuffer<int> result;
+    HIP_TRY(result.allocate(1));
+    launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, result.ptr, dev->stream);
+    int has = 0;
+    HIP_TRY(hipMemcpyAsync(&has, result.ptr, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
+  }
+  launchQuantizeWide(dev->d_wideNodes, dev->d_wideQ, (int) dev->wideNodesTotal, dev->stream);
+  if (!dev->d_topNodes) HIP_TRY(hipMalloc(&dev->d_topNodes, sizeof(float4) * 4 * TWK_TOP_NODES));
+  if (!dev->d_topNodes7) HIP_TRY(hipMalloc(&dev->d_topNodes7, sizeof(float4) * 4 * TWK_TOP_NODES7));
+  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
+  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  freeDevice(dev->d_wideNodes);
+
+  info.maxTraversalDepth = (uint64_t) traversalDepth;
+  info.triangleSlots = numTris; info.nodes = numNodes; info.instances = (uint64_t) numInstances; info.flattenedInstances = (uint64_t) (numInstances - numEntered);
+  info.buildMilliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - buildStart).count();
+  dev->buildInfo = info;
+  dev->twoLevel = (numEntered > 0);
+  dev->maxInstanceMaterial = maxMaterial; dev->maxInstanceLight = maxLight;
+  dev->totalNodes = numNodes; dev->totalTriangles = numTris;
+  dev->built = true; ++dev->buildSerial;
+  dev->geometryValid = false; dropTemporal(dev); // the geometry AOV and the temporal history describe the scene that was
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_build")
+
+} // extern "C"

@@ -161,7 +161,7 @@ struct LaunchParams
   const float*       envCDF_U;
   const float*       envCDF_V;
   int   tlasRoot;
-  int   traceWaves;     // blocks per CU of the scene's non-PRIMARY trace build (device_api.hip traceBuild, which sizes the grids); no kernel reads it
+  int   traceWaves;     // blocks per CU of the scene's non-PRIMARY trace build (device_pass.hip traceBuild, which sizes the grids); no kernel reads it
   int   twoLevel;       // 0: every instance is flattened — the BVH is one world-space tree (top level + spliced instance trees) and no kernel ever enters an instance
   int   numInstances;
   int   numLights;
@@ -218,7 +218,7 @@ struct LaunchParams
   int     numPixels;      // launchWidth * height = launch indices of ONE sample per pixel
   int     numPaths;       // numPixels * batchCount: paths of this wavefront pass, path = sample * numPixels + launch index
   int     batchCount;     // iterations rendered together (iterationIndex .. iterationIndex + batchCount - 1)
-  int     pathBase;       // first path of the pass this launch's streams start at (a pass cut into lanes, device_api.hip renderPass); 0 otherwise
+  int     pathBase;       // first path of the pass this launch's streams start at (a pass cut into lanes, device_pass.hip renderPass); 0 otherwise
   // Entry points of the primary rays (trace_kernels.hip tileEntryKernel), nullptr when off: per tile of TWK_ENTRY_TILE x
   // TWK_ENTRY_TILE launch indices two int4 = (count, ref 0..6): the subtrees a ray through that tile can reach, nearest first.
   const int4* tileEntries;
@@ -335,7 +335,7 @@ constexpr __host__ __device__ int traceBlocksPerCU(bool cutout, bool twoLevel, b
        : cutout ? ((primary || twoLevel) ? TWK_TRACE_WAVES_CUTOUT_OTHER : TWK_TRACE_WAVES)
        : (primary && twoLevel) ? TWK_TRACE_WAVES_PRIMARY_TWO_LEVEL : (primary ? TWK_TRACE_WAVES_PRIMARY : TWK_TRACE_WAVES);
 }
-// The build a trace launch runs (COUNT aside, which the launch decides): chosen by device_api.hip traceBuild, launched by
+// The build a trace launch runs (COUNT aside, which the launch decides): chosen by device_pass.hip traceBuild, launched by
 // trace_kernels.hip launchTrace.
 struct TraceBuild
 {
@@ -349,11 +349,11 @@ struct TraceBuild
 #define TWK_ENTRY_REFS 7        // references per tile at most (with the count: two int4)
 #define TWK_TRACE_STACK_SPILL 72  // further entries per lane in HBM
 #define TWK_TRACE_BLOCK       256
-#define TWK_SHADE_BLOCKS_PER_CU 128 // grid of shadeKernel = numCUs x this at most (device_api.hip)
+#define TWK_SHADE_BLOCKS_PER_CU 128 // grid of shadeKernel = numCUs x this at most (device_pass.hip)
 #ifndef TWK_SHADE_BLOCK
 #define TWK_SHADE_BLOCK       256  // threads per shadeKernel block: queue appends are aggregated per block. Measured (ms/step of shade): 128 → 0.48 (atomics), 256 → 0.33, 512 → 0.34 (waves wait at the block's barriers for its slowest wave), 1024 → 0.37
 #endif
-// Passes of at most this many paths are cut into two lanes (device_api.hip chooseLanes); measured on C2, DESIGN.md 2.
+// Passes of at most this many paths are cut into two lanes (device_pass.hip chooseLanes); measured on C2, DESIGN.md 2.
 #ifndef TWK_LANES2_MAX_PATHS
 #define TWK_LANES2_MAX_PATHS 21000000 // passes of at most this many paths run as two lanes. Round 5's final kernels, C2, one against two lanes: 2.1 M paths 1 138 / 1 211 Msamples/s, 4.1 M 1 646 / 1 735, 10.4 M 2 304 / 2 375, 20.7 M 2 760 / 2 766, 29 M 2 962 / 2 863 (a C5 rank's share of 20 iterations, 20.7 M: 2 746 / 2 718). Until then 30 M
 #endif
@@ -365,7 +365,7 @@ struct TraceBuild
 #endif
 
 // The path streams of a wavefront pass, one entry each: X(LaunchParams member, element type, elements per path, index).
-// The index says where the slice of a lane of the pass starts (device_api.hip laneParams):
+// The index says where the slice of a lane of the pass starts (device_pass.hip laneParams):
 //   QUEUE  indexed by queue record:         at the lane's queue base (its share of the slots + room for its segments' gaps)
 //   PATH   indexed by path or launch slot:  at elements per path x the lane's first path
 // The bytes per path, the carve of the stream block, the lanes' offsets, twk_debug_snapshot_scene's clearing and the host

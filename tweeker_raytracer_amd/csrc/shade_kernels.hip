@@ -213,7 +213,7 @@ TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, Sha
 // launch to read back. Both now COMPUTE the primary ray of their slot (shade_device.h primaryRay: 60 integer operations for
 // the seed, two draws, the lens shader) — PRIMARY variants of traceKernel and shadeKernel, launched at depth 0 — and the first
 // shade launch writes the path's radiance instead of adding to it. A scene with cutout opacity keeps ONE word of queue 0: the
-// seed, stored by the first traversal (its opacity tests draw from it) and read by the first shade launch. device_api.hip
+// seed, stored by the first traversal (its opacity tests draw from it) and read by the first shade launch. device_pass.hip
 // renderPass keeps generateKernel for paths without any bounce.
 #ifndef TWK_SHADE_LDS_TABLES
 #define TWK_SHADE_LDS_TABLES 1
@@ -427,7 +427,7 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   if (measurePhases)
   {
     __syncthreads();
-    // stats[24 ..): wave executions, lanes, cycles per phase (device_api.hip twk_stats_get)
+    // stats[24 ..): wave executions, lanes, cycles per phase (device_debug.hip twk_stats_get)
     if (threadIdx.x < 3 * TWK_SHADE_PHASES && phaseWords[threadIdx.x] != 0u) atomicAdd(&p.stats[24 + threadIdx.x], (unsigned long long) phaseWords[threadIdx.x]);
   }
 

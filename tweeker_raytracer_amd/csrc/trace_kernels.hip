@@ -124,7 +124,7 @@ static void launchTraceBuild(const LaunchParams& p, int depth, int gridBlocks, h
   hipLaunchKernelGGL((traceOverflowKernel<COUNT, CUTOUT, PRIMARY>), dim3(overflowBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, depth);
 }
 
-// The launchers of every build device_api.hip traceBuild can return, indexed by the build's five flags (bit 0 COUNT ... bit 4
+// The launchers of every build device_pass.hip traceBuild can return, indexed by the build's five flags (bit 0 COUNT ... bit 4
 // PRIMARY) and bit 5 SLIM, which the pass decides (LaunchParams::slimSlotBits); the W7 form exists for flattened, non-PRIMARY
 // launches only (device_types.h traceBlocksPerCU), the SLIM form for flattened scenes without cutout opacity.
 using TraceLauncher = void (*)(const LaunchParams&, int, int, hipStream_t);

@@ -544,6 +544,40 @@ int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colou
 int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats);         /* launchWidth*height*4 floats; synchronises */
 int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats);
 
+/* ---- The noise estimate and the stopping rule — new calls, ABI stays 9, no existing struct changes -----------------------------
+ * How far a progressive picture is from done, from the integrator's own samples: per launch index the RELATIVE STANDARD ERROR of
+ * the luminance mean, e = sqrt(M2 / ((n - 1) n)) / (mean + darkFloor), out of the luminance moments (mean, M2, n, .) that
+ * twk_enable_moments accumulates, reduced on the device to a summary of integers. The complete definition, operation by
+ * operation, is csrc/noise_device.h; tests/noise_restate.py restates it in numpy. An element is EMPTY (n == 0: the padding of a
+ * packed tile buffer, a pixel whose samples were all dropped), UNKNOWN (a component that is not finite, n < minSamples, M2 < 0,
+ * mean < 0, or an e that is not finite) or VALID. Valid elements are counted into histogram[256] by the exponent and the top three
+ * mantissa bits of e (8 bins per octave from 2^-16 to 2^16, clamped), summed in units of 2^-20 (e capped at 65536) into sumFixed,
+ * and the largest bits of e are kept: integers only, so the summary does not depend on the order of the reduction and equals its
+ * restatement exactly. What it is NOT: an error against ground truth. It is blind to bias (the firefly clamp, clamped or cut
+ * paths), it is not a measure of a denoised picture, and it sees luminance, not colour. */
+typedef struct TwkNoise { int minSamples; float darkFloor; } TwkNoise;
+#define TWK_NOISE_DARK_FLOOR 0.01f
+int twk_noise_defaults(TwkNoise* np); /* minSamples TWK_DENOISER_MIN_SAMPLES, darkFloor TWK_NOISE_DARK_FLOOR */
+typedef struct TwkNoiseSummary { uint64_t valid, unknown, empty, sumFixed; uint32_t maxErrorBits, reserved; uint32_t histogram[256]; } TwkNoiseSummary;
+/* Estimates into the handle's summary buffer; asynchronous on the handle's stream (the summary is zeroed on that stream first), never
+ * writes its input. np NULL: the defaults. moments NULL (numElements must be 0 then): the handle's own moments, launchWidth x height
+ * elements — TWK_ERROR_INVALID_STATE without twk_enable_moments(1) and twk_set_state; ALLOWED on a packed tile buffer (distribution
+ * 1, several devices), whose padding is EMPTY: each device reduces its own buffer and the host merges, no picture is assembled.
+ * Recorded launches are rendered first. Otherwise moments is a device buffer of numElements float4. errorMap: NULL, or a device
+ * buffer of numElements floats that does not overlap moments; it receives e for a VALID element, -1 for UNKNOWN, -2 for EMPTY.
+ * TWK_ERROR_INVALID_VALUE: a NULL handle, minSamples < 2, a darkFloor that is not > 0 and finite, an overlap, numElements that is
+ * not 0 without moments, or is 0 or above 2^31 with them. */
+int twk_estimate_noise(TwkDevice dev, const TwkNoise* np, const void* moments, size_t numElements, void* errorMap);
+int twk_read_noise(TwkDevice dev, TwkNoiseSummary* out); /* the last estimate's summary; synchronises. TWK_ERROR_INVALID_STATE before any estimate on this handle */
+/* Host only, no handle. Merge: two summaries of disjoint element sets — counts, histogram and sumFixed add, maxErrorBits is the
+ * larger. Mean: sumFixed / 2^20 / valid in double, narrowed once. Quantile, q in (0, 1]: the UPPER edge of the first bin at which
+ * the cumulative count reaches ceil(q valid) (the ceiling in exact integer arithmetic), the float whose bits are
+ * (bin + 1 + ((127 - 16) << 3)) << 20 — never below the true quantile and at most 9/8 of it inside the histogram's range. Mean and
+ * quantile are TWK_ERROR_INVALID_STATE where valid == 0. */
+int twk_noise_merge(TwkNoiseSummary* into, const TwkNoiseSummary* other);
+int twk_noise_mean(const TwkNoiseSummary* s, float* mean);
+int twk_noise_quantile(const TwkNoiseSummary* s, float q, float* error);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);
@@ -662,6 +696,12 @@ int twk_app_get_denoiser_variance(TwkApp app, int* enabled, TwkDenoiserVariance*
  * twk_app_get_denoiser_variance, whatever "denoiserVariance" says). twk_app_init_device enables the moments when the key asks. */
 #define TWK_DENOISER_MIN_SAMPLES 4
 int twk_app_get_denoiser_sampled(TwkApp app, int* enabled, int* minSamples);
+/* The stopping rule: "targetNoise e" (default 0 = off; e > 0 and finite), "targetNoiseQuantile q" (default 0.95; in (0, 1]),
+ * "targetNoiseInterval n" (default 16; n >= 1). A value outside its range drops the line with a warning. *enabled = a target is
+ * set: a render loop then calls twk_estimate_noise on every device after every *interval iterations, merges the summaries and ends
+ * at the first check where valid > 0 and twk_noise_quantile(*quantile) <= *target (rtigo3_hip -m 1 does; INTEGRATION.md "The
+ * stopping rule"). twk_app_init_device enables the moments when a target is set. */
+int twk_app_get_target_noise(TwkApp app, int* enabled, float* target, float* quantile, int* interval);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

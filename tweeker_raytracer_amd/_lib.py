@@ -6,6 +6,8 @@ compute entry point fails with TWK_ERROR_NO_DEVICE on a machine without a GPU.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TWK_LIB") or os.path.join(_HERE, "libtweeker_hip.so")  # TWK_LIB: an A/B variant built by tools/ab_variant.sh
 
@@ -26,6 +28,7 @@ TWK_DENOISER_RGB, TWK_DENOISER_RGB_ALBEDO, TWK_DENOISER_RGB_ALBEDO_NORMAL = 0, 1
 TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_variance_sampled (include/tweeker_hip.h)
 
 TWK_TEMPORAL_MAX_HISTORY, TWK_TEMPORAL_POSITION_TOLERANCE = 32, 0.01  # twk_temporal_defaults (include/tweeker_hip.h)
+TWK_NOISE_DARK_FLOOR = 0.01  # twk_noise_defaults (include/tweeker_hip.h); its minSamples is TWK_DENOISER_MIN_SAMPLES
 
 f3 = C.c_float * 3
 f2 = C.c_float * 2
@@ -109,6 +112,51 @@ class TemporalFrame(C.Structure):
         super().__init__(colour, moments, geometry, camera if camera is not None else CameraDefinition())
 
 
+class Noise(C.Structure):
+    """≙ TwkNoise: parameters of twk_estimate_noise. minSamples: a pixel with fewer samples is `unknown`; darkFloor: added to the
+    mean the standard error is divided by. Without arguments: twk_noise_defaults."""
+    _fields_ = [("minSamples", C.c_int), ("darkFloor", C.c_float)]
+
+    def __init__(self, minSamples=TWK_DENOISER_MIN_SAMPLES, darkFloor=TWK_NOISE_DARK_FLOOR):
+        super().__init__(int(minSamples), darkFloor)
+
+
+class NoiseSummary(C.Structure):
+    """≙ TwkNoiseSummary: what twk_estimate_noise reduces a stream of luminance moments to (csrc/noise_device.h). valid / unknown /
+    empty count the elements; the rest describes e, the relative standard error of the luminance mean, over the valid ones."""
+    _fields_ = [("valid", C.c_uint64), ("unknown", C.c_uint64), ("empty", C.c_uint64), ("sumFixed", C.c_uint64),
+                ("maxErrorBits", C.c_uint32), ("reserved", C.c_uint32), ("bins", C.c_uint32 * 256)]
+
+    @property
+    def histogram(self):
+        """uint32 [256]: valid elements by the exponent and top three mantissa bits of e, 8 bins per octave from 2^-16 to 2^16."""
+        return np.ctypeslib.as_array(self.bins).copy()
+
+    @property
+    def maxError(self):
+        """The largest e (0.0 without a valid element)."""
+        return float(np.array([self.maxErrorBits], np.uint32).view(np.float32)[0])
+
+    @property
+    def mean(self):
+        """twk_noise_mean: the mean e of the valid elements (TwkError without one)."""
+        m = C.c_float(0)
+        check(lib.twk_noise_mean(C.byref(self), C.byref(m)))
+        return m.value
+
+    def quantile(self, q):
+        """twk_noise_quantile: the upper edge of the histogram bin that holds the q quantile of e, q in (0, 1]: never below the
+        true quantile, at most 9/8 of it inside the histogram's range (TwkError without a valid element)."""
+        e = C.c_float(0)
+        check(lib.twk_noise_quantile(C.byref(self), C.c_float(q), C.byref(e)))
+        return e.value
+
+    def merge(self, other):
+        """twk_noise_merge: folds the summary of a disjoint set of elements (another device's tiles) into this one; returns self."""
+        check(lib.twk_noise_merge(C.byref(self), C.byref(other)))
+        return self
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("radianceRays", C.c_uint64), ("shadowRays", C.c_uint64), ("nodesVisited", C.c_uint64),
                 ("trianglesTested", C.c_uint64), ("instancesEntered", C.c_uint64), ("shadedHits", C.c_uint64),
@@ -157,6 +205,7 @@ SYMBOLS = [
     "twk_enable_moments", "twk_read_moments", "twk_get_moments_device_pointer", "twk_debug_read_path_radiance", "twk_denoise_variance_sampled", "twk_app_get_denoiser_sampled",
     "twk_set_sample_offset", "twk_enable_geometry", "twk_render_geometry", "twk_read_geometry", "twk_get_geometry_device_pointer",
     "twk_temporal_defaults", "twk_temporal_accumulate", "twk_temporal_reset", "twk_get_temporal_device_pointers", "twk_read_temporal", "twk_read_temporal_moments",
+    "twk_noise_defaults", "twk_estimate_noise", "twk_read_noise", "twk_noise_merge", "twk_noise_mean", "twk_noise_quantile", "twk_app_get_target_noise",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

@@ -123,6 +123,15 @@ class Application:
         return bool(on.value), n.value
 
     @property
+    def targetNoise(self):
+        """(enabled, target, quantile, interval) from "targetNoise", "targetNoiseQuantile", "targetNoiseInterval" of the system
+        description: a render loop checks Device.estimateNoise every `interval` iterations and ends once summary.quantile(quantile)
+        <= target; initDevice enables the device's moments when a target is set."""
+        on, t, q, n = C.c_int(0), C.c_float(0), C.c_float(0), C.c_int(0)
+        L.check(L.lib.twk_app_get_target_noise(self._h, C.byref(on), C.byref(t), C.byref(q), C.byref(n)))
+        return bool(on.value), t.value, q.value, n.value
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

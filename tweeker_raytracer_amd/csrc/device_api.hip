@@ -239,7 +239,7 @@ try
   freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
   freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); freeDevice(dev->d_moments);
   freeDevice(dev->d_geometry); dropTemporal(dev);
-  freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams);
+  freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams); freeDevice(dev->d_noise);
   dev->builder.release();
   for (int k = 1; k < TWK_MAX_LANES; ++k)
   {

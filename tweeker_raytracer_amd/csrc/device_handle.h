@@ -1,11 +1,12 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
-// tonemap, denoiser, temporal), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, temporal, noise estimate), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
 #include "denoise_device.h"
 #include "temporal_device.h"
+#include "noise_device.h"
 #include "error_state.h"
 
 #include <string>
@@ -34,6 +35,7 @@ void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, co
 void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
+void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 }
 
 using namespace twk;
@@ -157,6 +159,8 @@ struct TwkDevice_t
   // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
   void* d_denoised = nullptr; int denoisedWidth = 0, denoisedHeight = 0, denoisedFormat = TWK_OUTPUT_FLOAT4; bool denoisedValid = false;
   float4* d_denoiseStreams = nullptr; size_t denoiseStreamPixels = 0;
+  // twk_estimate_noise: the summary the kernel adds into (noise_device.h), zeroed on the stream before each launch; noiseValid: an estimate has been issued
+  TwkNoiseSummary* d_noise = nullptr; bool noiseValid = false;
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;

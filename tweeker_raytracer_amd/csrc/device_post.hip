@@ -435,4 +435,89 @@ try
 }
 TWK_CATCH("twk_read_temporal_moments")
 
+// ---- noise estimate (noise_device.h) -----------------------------------------------------------
+int twk_noise_defaults(TwkNoise* np)
+try
+{
+  if (!np) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_noise_defaults: NULL argument");
+  np->minSamples = TWK_DENOISER_MIN_SAMPLES; np->darkFloor = TWK_NOISE_DARK_FLOOR;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_noise_defaults")
+
+int twk_estimate_noise(TwkDevice dev, const TwkNoise* np, const void* moments, size_t numElements, void* errorMap)
+try
+{
+  const char* name = "twk_estimate_noise";
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  TwkNoise defaults; defaults.minSamples = TWK_DENOISER_MIN_SAMPLES; defaults.darkFloor = TWK_NOISE_DARK_FLOOR;
+  if (!np) np = &defaults;
+  if (np->minSamples < 2) return refuse(TWK_ERROR_INVALID_VALUE, "minSamples must be >= 2 (one sample has no variance)");
+  if (!(np->darkFloor > 0.0f) || !finite1(np->darkFloor)) return refuse(TWK_ERROR_INVALID_VALUE, "darkFloor must be > 0 and finite");
+  if (!moments && numElements != 0) return refuse(TWK_ERROR_INVALID_VALUE, "numElements without a moments buffer (pass both, or neither for the handle's own moments)");
+  if (moments && (numElements == 0 || numElements > ((size_t) 1 << 31))) return refuse(TWK_ERROR_INVALID_VALUE, "numElements must be in [1, 2^31]");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!moments)
+  {
+    if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
+    numElements = (size_t) dev->launchWidth * dev->state.resolution[1];
+    if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < numElements)
+      return refuse(TWK_ERROR_INVALID_STATE, "the handle has no luminance moments: twk_enable_moments(1) and twk_set_state first");
+    moments = dev->d_moments;
+  }
+  if (overlaps(errorMap, numElements * sizeof(float), moments, numElements * sizeof(float4))) return refuse(TWK_ERROR_INVALID_VALUE, "the error map overlaps the moments");
+  if (!dev->d_noise) HIP_TRY(hipMalloc(&dev->d_noise, sizeof(TwkNoiseSummary)));
+  NoiseConstants k;
+  k.minSamples = (float) np->minSamples; k.darkFloor = np->darkFloor;
+  HIP_TRY(hipMemsetAsync(dev->d_noise, 0, sizeof(TwkNoiseSummary), dev->stream));
+  launchNoise(static_cast<const float4*>(moments), numElements, static_cast<float*>(errorMap), dev->d_noise, k, dev->numCUs, dev->stream);
+  HIP_TRY(hipGetLastError());
+  dev->noiseValid = true;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_estimate_noise")
+
+int twk_read_noise(TwkDevice dev, TwkNoiseSummary* out)
+try
+{
+  int rc = activate(dev, "twk_read_noise"); if (rc) return rc;
+  if (!out) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_noise: NULL argument");
+  if (!dev->d_noise || !dev->noiseValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_noise: no twk_estimate_noise on this handle yet");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(out, dev->d_noise, sizeof(TwkNoiseSummary), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_noise")
+
+int twk_noise_merge(TwkNoiseSummary* into, const TwkNoiseSummary* other)
+try
+{
+  if (!into || !other) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_noise_merge: NULL argument");
+  noiseMerge(*into, *other);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_noise_merge")
+
+int twk_noise_mean(const TwkNoiseSummary* s, float* mean)
+try
+{
+  if (!s || !mean) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_noise_mean: NULL argument");
+  if (s->valid == 0) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_noise_mean: the summary has no valid element");
+  *mean = noiseMean(*s);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_noise_mean")
+
+int twk_noise_quantile(const TwkNoiseSummary* s, float q, float* error)
+try
+{
+  if (!s || !error) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_noise_quantile: NULL argument");
+  if (!(q > 0.0f && q <= 1.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_noise_quantile: q must be in (0, 1]");
+  if (s->valid == 0) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_noise_quantile: the summary has no valid element");
+  *error = noiseBinUpperEdge(noiseQuantileBin(*s, q));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_noise_quantile")
+
 } // extern "C"

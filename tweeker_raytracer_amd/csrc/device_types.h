@@ -426,4 +426,11 @@ inline void carvePathStreams(LaunchParams& p, void* block, size_t slots)
 static_assert(TWK_SHADE_BLOCK <= 256, "a shade window (TWK_SHADE_BLOCK slots) fits TWK_QUEUE_STRIDE's rounding");
 static_assert(TWK_QUEUE_SEGMENTS * (255 + 512) <= TWK_LANE_QUEUE_PAD, "a lane's segment gaps fit TWK_LANE_QUEUE_PAD");
 
+// What noiseKernel takes beside its buffers (noise_device.h): TwkNoise with the sample count as the float it is compared as
+struct NoiseConstants
+{
+  float minSamples; // (float) TwkNoise::minSamples
+  float darkFloor;
+};
+
 } // namespace twk

@@ -139,6 +139,25 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 2) denoiserMinSamples = i[0];
       else if (ok) warnings.push_back("denoiserMinSamples must be >= 2, keeping the previous value");
     }
+    // the stopping rule (twk_estimate_noise, read by twk_app_get_target_noise): as above, a value outside its range drops the line
+    else if (key == "targetNoise")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] >= 0.0f && std::isfinite(f[0])) targetNoise = f[0];
+      else if (ok) warnings.push_back("targetNoise must be > 0 and finite (0 = off), keeping the previous value");
+    }
+    else if (key == "targetNoiseQuantile")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] > 0.0f && f[0] <= 1.0f) targetNoiseQuantile = f[0];
+      else if (ok) warnings.push_back("targetNoiseQuantile must be in (0, 1], keeping the previous value");
+    }
+    else if (key == "targetNoiseInterval")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 1) targetNoiseInterval = i[0];
+      else if (ok) warnings.push_back("targetNoiseInterval must be >= 1, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -196,6 +215,9 @@ std::string Application::systemDescription() const
   if (denoiserSigmaLuminance != 4.0f) d << "denoiserSigmaLuminance " << denoiserSigmaLuminance << std::endl;
   if (denoiserSampledVariance != 0) d << "denoiserSampledVariance " << denoiserSampledVariance << std::endl;
   if (denoiserMinSamples != TWK_DENOISER_MIN_SAMPLES) d << "denoiserMinSamples " << denoiserMinSamples << std::endl;
+  if (targetNoise != 0.0f) d << "targetNoise " << targetNoise << std::endl;
+  if (targetNoiseQuantile != 0.95f) d << "targetNoiseQuantile " << targetNoiseQuantile << std::endl;
+  if (targetNoiseInterval != 16) d << "targetNoiseInterval " << targetNoiseInterval << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

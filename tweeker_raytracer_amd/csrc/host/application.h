@@ -99,6 +99,11 @@ public:
   // least "denoiserMinSamples" of them), TWK_DENOISER_MIN_SAMPLES until a key sets it
   int   denoiserSampledVariance = 0;
   int   denoiserMinSamples = TWK_DENOISER_MIN_SAMPLES;
+  // "targetNoise" (0: off; else the render loop ends once the "targetNoiseQuantile" quantile of twk_estimate_noise's relative
+  // standard error is at most this), checked every "targetNoiseInterval" iterations
+  float targetNoise = 0.0f;
+  float targetNoiseQuantile = 0.95f;
+  int   targetNoiseInterval = 16;
   int   shaderVariant = 0; // grammar extension "shaderVariant": 0 rtigo3, 1 Optix7Gui light-hit rule (include/tweeker_hip.h TWK_SHADERS_*)
   int   samplesSqrt   = 1;
   int   resolution[2] = {1, 1};

@@ -137,6 +137,17 @@ try
 }
 TWK_CATCH("twk_app_get_denoiser_sampled")
 
+int twk_app_get_target_noise(TwkApp app, int* enabled, float* target, float* quantile, int* interval)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_target_noise: NULL app");
+  if (!enabled || !target || !quantile || !interval) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_target_noise: NULL argument");
+  *enabled = (app->app.targetNoise > 0.0f) ? 1 : 0;
+  *target = app->app.targetNoise; *quantile = app->app.targetNoiseQuantile; *interval = app->app.targetNoiseInterval;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_target_noise")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -231,6 +242,7 @@ try
   if ((rc = twk_set_output_format(dev, a.outputFormat))) return rc;
   if (a.denoiser > 1 && (rc = twk_enable_aov(dev, 1))) return rc; // "denoiser 2|3": the filter's guides are the AOVs
   if (a.denoiser != 0 && a.denoiserSampledVariance && (rc = twk_enable_moments(dev, 1))) return rc; // "denoiserSampledVariance 1": the filter's variance is the samples'
+  if (a.targetNoise > 0.0f && (rc = twk_enable_moments(dev, 1))) return rc; // "targetNoise e": the stopping rule reads the samples' moments
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;
   if ((rc = twk_init_materials(dev, a.materials.data(), (int) a.materials.size()))) return rc;

@@ -2,6 +2,9 @@
 //   rtigo3 -s system.txt -d scene.txt -m 1
 // (main.cpp:169-172 → Application::benchmark, Application.cpp:491-531): render samplesSqrt² iterations, wait for the
 // device, print "<iterations> / <seconds> = <fps> fps", store the tonemapped screenshot. Options as Options.cpp:44-156.
+// With "targetNoise e" in the system description the loop may end earlier: every "targetNoiseInterval" iterations each device
+// estimates the noise of its own buffer (twk_estimate_noise), the summaries are merged, and the loop ends once the
+// "targetNoiseQuantile" quantile of the relative standard error is at most e; a second line prints the final mean and quantile.
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -148,6 +151,10 @@ int main(int argc, char* argv[])
     return 1;
   }
 
+  int targetNoiseEnabled = 0, targetNoiseInterval = 0; // "targetNoise e": the stopping rule
+  float targetNoise = 0.0f, targetNoiseQuantile = 0.0f;
+  TWK_OK(twk_app_get_target_noise(app, &targetNoiseEnabled, &targetNoise, &targetNoiseQuantile, &targetNoiseInterval));
+
   std::vector<TwkDevice> devices((size_t) count, nullptr);
   TwkDeviceState state;
   TWK_OK(twk_app_get_state(app, &state));
@@ -206,10 +213,41 @@ int main(int argc, char* argv[])
   const unsigned int spp = (unsigned int) (info.samplesSqrt * info.samplesSqrt);
   const auto start = std::chrono::steady_clock::now();
   unsigned int iterationIndex = 0;
+  TwkNoiseSummary noise;
+  memset(&noise, 0, sizeof(noise));
+  float noiseQuantile = 0.0f;
+  bool noiseChecked = false; // `noise` is the summary of the frame as it stands
+  // every device estimates its own buffer (a packed tile buffer's padding is empty), the host merges; true: the target is met
+  auto checkNoise = [&](bool& met) -> int
+  {
+    memset(&noise, 0, sizeof(noise));
+    for (int i = 0; i < count; ++i) TWK_OK(twk_estimate_noise(devices[(size_t) i], nullptr, nullptr, 0, nullptr));
+    for (int i = 0; i < count; ++i)
+    {
+      TwkNoiseSummary part;
+      TWK_OK(twk_read_noise(devices[(size_t) i], &part));
+      TWK_OK(twk_noise_merge(&noise, &part));
+    }
+    met = false;
+    if (noise.valid > 0)
+    {
+      TWK_OK(twk_noise_quantile(&noise, targetNoiseQuantile, &noiseQuantile));
+      met = (noiseQuantile <= targetNoise);
+    }
+    return 0;
+  };
   while (iterationIndex < spp)
   {
     for (int i = 0; i < count; ++i) TWK_OK(twk_launch(devices[(size_t) i], iterationIndex));
     ++iterationIndex;
+    noiseChecked = false;
+    if (targetNoiseEnabled && iterationIndex % (unsigned int) targetNoiseInterval == 0)
+    {
+      bool met = false;
+      if (checkNoise(met)) return 1;
+      noiseChecked = true;
+      if (met) break;
+    }
   }
   for (int i = 0; i < count; ++i) TWK_OK(twk_sync(devices[(size_t) i]));
   const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
@@ -218,6 +256,21 @@ int main(int argc, char* argv[])
     std::ostringstream stream;
     stream.precision(3);
     stream << std::fixed << iterationIndex << " / " << seconds << " = " << fps << " fps";
+    std::cout << stream.str() << std::endl;
+  }
+  if (targetNoiseEnabled)
+  {
+    bool met = false;
+    if (!noiseChecked && checkNoise(met)) return 1; // samplesSqrt² is no multiple of the interval: the frame's own figures
+    std::ostringstream stream;
+    stream << "noise: " << iterationIndex << " spp";
+    if (noise.valid > 0)
+    {
+      float mean = 0.0f;
+      TWK_OK(twk_noise_mean(&noise, &mean));
+      stream << ", mean " << mean << ", " << targetNoiseQuantile << " quantile at most " << noiseQuantile << ", target " << targetNoise;
+    }
+    else stream << ", no pixel has enough samples yet, target " << targetNoise;
     std::cout << stream.str() << std::endl;
   }
 
@@ -280,6 +333,16 @@ int main(int argc, char* argv[])
   }
   char path[4096];
   TWK_OK(twk_app_screenshot_path(app, 1, path, sizeof(path)));
+  if (targetNoiseEnabled && iterationIndex != spp)
+  {
+    // the name carries the samples rendered: "<prefix>_<spp>spp_<date>..." with the count of this run
+    std::string name(path);
+    const std::string planned = "_" + std::to_string(spp) + "spp_", rendered = "_" + std::to_string(iterationIndex) + "spp_";
+    const size_t at = name.rfind(planned);
+    if (at != std::string::npos) name.replace(at, planned.size(), rendered);
+    if (name.size() + 1 > sizeof(path)) { std::cerr << "ERROR: screenshot path too long\n"; return 1; }
+    memcpy(path, name.c_str(), name.size() + 1);
+  }
   TWK_OK(twk_write_png_rgb8(path, width, height, rgb8.data(), 1));
   std::cout << path << std::endl;
 

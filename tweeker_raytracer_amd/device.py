@@ -398,6 +398,19 @@ class Device:
         L.check(L.lib.twk_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
+    def estimateNoise(self, noise=None, moments=None, numElements=0, errorMap=None):
+        """twk_estimate_noise, then twk_read_noise: how noisy the frame still is, from the integrator's own samples — per element the
+        relative standard error e of the luminance mean out of the luminance moments, reduced on the device to an L.NoiseSummary.
+        noise: L.Noise (None = the defaults). Without `moments` the handle's own (enableMoments; a packed tile buffer is fine, its
+        padding counts as empty); otherwise a device pointer to numElements float4 (mean, M2, n, .). errorMap: device pointer to
+        numElements floats, or None; receives e, -1 for an unknown and -2 for an empty element. Not an error against ground truth:
+        blind to bias, and no measure of a denoised picture."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        L.check(L.lib.twk_estimate_noise(self._h, None if noise is None else C.byref(noise), ptr(moments), C.c_size_t(int(numElements)), ptr(errorMap)))
+        out = L.NoiseSummary()
+        L.check(L.lib.twk_read_noise(self._h, C.byref(out)))
+        return out
+
     def statsEnable(self, enable=True):
         L.check(L.lib.twk_stats_enable(self._h, int(bool(enable))))
 

@@ -285,7 +285,8 @@ int twk_set_flatten_policy(TwkDevice dev, int maxTriangles, int maxReferences);
  * Asynchronous on the handle's stream. One call = one sample per pixel of this device's share:
  * the full W×H frame (distribution 0) or the launchWidth×H checkerboard tile set (distribution 1,
  * raygeneration.cu:152-164,259-344). The accumulation buffer holds the running mean
- * (raygeneration.cu:246-253), RGBA32F, alpha 1. */
+ * (raygeneration.cu:246-253), RGBA32F, alpha 1. After an adaptive pass (twk_launch_adaptive, below) an index other than 0 is
+ * TWK_ERROR_INVALID_STATE, the pixels being at different iterations; index 0 restarts a uniform frame as always. */
 int twk_launch(TwkDevice dev, unsigned int iterationIndex);
 int twk_sync(TwkDevice dev);                                  /* ≙ Device::synchronizeStream */
 /* twk_launch is asynchronous and deferred: consecutive iteration indices are rendered together, up to `iterations`
@@ -578,6 +579,58 @@ int twk_noise_merge(TwkNoiseSummary* into, const TwkNoiseSummary* other);
 int twk_noise_mean(const TwkNoiseSummary* s, float* mean);
 int twk_noise_quantile(const TwkNoiseSummary* s, float q, float* error);
 
+/* ---- Adaptive sampling — new calls, ABI stays 9, no existing struct changes; with the switch at its default no kernel and no bit
+ * of any picture changes --------------------------------------------------------------------------------------------------------
+ * Samples only the pixels the noise estimate says are unfinished. Paths of different pixels never interact, and the iteration index
+ * enters a path in two places only: the seed of its random numbers and the fold into the running means (weight 1 / (iteration + 1),
+ * "iteration 0 starts afresh", the moments). So every launch index i gets a word count[i], the iteration index its next sample uses,
+ * and an adaptive sample of i uses count[i] wherever a uniform launch uses its iteration index. INVARIANT: after any mix of uniform
+ * launches 0 .. K-1 and adaptive passes, a launch index whose count is c holds in colour, both AOVs and moments exactly the bits it
+ * holds after twk_launch(0 .. c-1). What it is NOT: it does not predict how many samples a pixel still needs (every selected pixel
+ * gets the same number per pass), it is driven by the luminance estimate above and so by neither colour, the denoised picture nor
+ * bias, and an adaptive pass uses neither the fused primary builds nor several lanes. */
+typedef struct TwkAdaptive { float targetNoise; int minSamples; float darkFloor; unsigned int maxSamples; } TwkAdaptive;
+#define TWK_ADAPTIVE_TARGET_NOISE 0.05f
+#define TWK_ADAPTIVE_MAX_SAMPLES 4096u
+int twk_adaptive_defaults(TwkAdaptive* ap); /* targetNoise 0.05, minSamples TWK_DENOISER_MIN_SAMPLES, darkFloor TWK_NOISE_DARK_FLOOR, maxSamples 4096 */
+/* (1) allocates count[], the active list and the select's scan scratch, launchWidth x height words each (with twk_set_state, whichever
+ * comes later); (0) frees them and forgets the adaptive state. TWK_ERROR_INVALID_STATE: (1) without twk_enable_moments(1). The
+ * handle remembers the index after the last iteration a uniform launch rendered; before count[] is first read it is filled with
+ * that index. twk_set_state, twk_build, twk_clear_scene, a change of the output format or of the output buffer, twk_enable_moments
+ * and twk_enable_adaptive(0) drop that memory and the active list. */
+int twk_enable_adaptive(TwkDevice dev, int enable);
+/* Selects, in ascending order, the elements an adaptive pass is to sample, and synchronises; *numActive receives their number.
+ * Element i with (mean, M2, n, .) = moments[i] is classified as by twk_estimate_noise with minSamples and darkFloor; the tests are
+ * applied in this order: EMPTY, not selected; counts[i] >= maxSamples, not selected; UNKNOWN, selected; VALID, selected exactly
+ * when e > targetNoise. The complete definition is csrc/adaptive_device.h; tests/adaptive_restate.py restates it in numpy. Never
+ * writes its inputs. ap NULL: the defaults. Own-buffer form (moments, counts, activeOut NULL, numElements 0): the handle's moments,
+ * counts and list, the list twk_launch_adaptive renders; recorded launches are rendered first; ALLOWED on a packed tile buffer
+ * (distribution 1, several devices), whose padding is EMPTY. Explicit form: device buffers of numElements float4, numElements words
+ * and, for the list, numElements words that overlap neither. TWK_ERROR_INVALID_VALUE: a NULL handle or numActive (before any HIP
+ * call), a targetNoise or darkFloor that is not > 0 and finite, minSamples < 2, maxSamples 0, an overlap, some but not all of the
+ * three pointers, numElements that is not 0 without them, or is 0 or above 2^31 with them. TWK_ERROR_INVALID_STATE: the own-buffer
+ * form without twk_enable_moments(1), twk_enable_adaptive(1) and twk_set_state. */
+int twk_adaptive_select(TwkDevice dev, const TwkAdaptive* ap, const void* moments, const void* counts, size_t numElements,
+                        void* activeOut, unsigned int* numActive);
+/* Host only, no handle: the same definition over host arrays (numElements x 4 floats, numElements words; activeOut holds
+ * numElements words). TWK_ERROR_INVALID_VALUE: a NULL array, the parameter refusals above, numElements above 2^31. */
+int twk_adaptive_select_host(const TwkAdaptive* ap, const float* moments, const uint32_t* counts, size_t numElements,
+                             uint32_t* activeOut, size_t* numActive);
+/* Renders `samples` samples of every launch index of the handle's active list as one wavefront pass, asynchronously: sample s of
+ * launch index i runs as iteration count[i] + s (seeded with twk_set_sample_offset's offset added, as a uniform launch is), is
+ * folded by the uniform pass's own fold, and count[i] advances by `samples` (so a count may pass maxSamples by less than `samples`).
+ * The list stays valid: the same list may be rendered again. A list of length 0 is a successful no-op. After the first adaptive pass
+ * twk_launch with an index other than 0 is TWK_ERROR_INVALID_STATE; twk_launch with index 0 restarts a uniform frame. TWK_ERROR_INVALID_VALUE:
+ * a NULL handle, samples outside 1..64. TWK_ERROR_INVALID_STATE: before an own-buffer twk_adaptive_select on this handle; after
+ * anything that dropped the list (a twk_launch, twk_set_state, twk_build, twk_clear_scene, a change of format or output buffer);
+ * with the time view, first-hit capture or statistics on; with twk_set_shared_frame in use. */
+int twk_launch_adaptive(TwkDevice dev, int samples);
+int twk_read_sample_counts(TwkDevice dev, uint32_t* host, size_t numElements); /* launchWidth*height words; synchronises. TWK_ERROR_INVALID_STATE without twk_enable_adaptive(1) and twk_set_state */
+int twk_get_sample_counts_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+/* The active list of the last own-buffer select: *numActive entries into host, which holds `capacity` words (host NULL and capacity
+ * 0: the length alone); synchronises. TWK_ERROR_INVALID_VALUE: capacity below the length. TWK_ERROR_INVALID_STATE: no valid list. */
+int twk_read_active(TwkDevice dev, uint32_t* host, size_t capacity, unsigned int* numActive);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);
@@ -702,6 +755,12 @@ int twk_app_get_denoiser_sampled(TwkApp app, int* enabled, int* minSamples);
  * at the first check where valid > 0 and twk_noise_quantile(*quantile) <= *target (rtigo3_hip -m 1 does; INTEGRATION.md "The
  * stopping rule"). twk_app_init_device enables the moments when a target is set. */
 int twk_app_get_target_noise(TwkApp app, int* enabled, float* target, float* quantile, int* interval);
+/* "adaptiveSampling 0|1" (default 0) and "adaptiveMaxSamples n" (default 4096; n >= 1; a value outside drops the line with a
+ * warning). *enabled = the description asks for adaptive sampling AND sets a target ("adaptiveSampling 1" without "targetNoise" is
+ * dropped with a warning); *ap: target, minSamples and darkFloor as the stopping rule uses them, maxSamples from the description.
+ * twk_app_init_device enables moments and adaptive sampling when the key is on (rtigo3_hip -m 1 runs the loop; INTEGRATION.md "The
+ * adaptive loop"). */
+int twk_app_get_adaptive(TwkApp app, int* enabled, TwkAdaptive* ap);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

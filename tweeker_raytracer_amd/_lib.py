@@ -29,6 +29,7 @@ TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_vari
 
 TWK_TEMPORAL_MAX_HISTORY, TWK_TEMPORAL_POSITION_TOLERANCE = 32, 0.01  # twk_temporal_defaults (include/tweeker_hip.h)
 TWK_NOISE_DARK_FLOOR = 0.01  # twk_noise_defaults (include/tweeker_hip.h); its minSamples is TWK_DENOISER_MIN_SAMPLES
+TWK_ADAPTIVE_TARGET_NOISE, TWK_ADAPTIVE_MAX_SAMPLES = 0.05, 4096  # twk_adaptive_defaults (include/tweeker_hip.h)
 
 f3 = C.c_float * 3
 f2 = C.c_float * 2
@@ -121,6 +122,17 @@ class Noise(C.Structure):
         super().__init__(int(minSamples), darkFloor)
 
 
+class Adaptive(C.Structure):
+    """≙ TwkAdaptive: parameters of twk_adaptive_select. An element is selected when its relative standard error (minSamples and
+    darkFloor as in Noise) is above targetNoise or cannot be told yet, unless it is empty or its sample count has reached
+    maxSamples. Without arguments: twk_adaptive_defaults."""
+    _fields_ = [("targetNoise", C.c_float), ("minSamples", C.c_int), ("darkFloor", C.c_float), ("maxSamples", C.c_uint)]
+
+    def __init__(self, targetNoise=TWK_ADAPTIVE_TARGET_NOISE, minSamples=TWK_DENOISER_MIN_SAMPLES, darkFloor=TWK_NOISE_DARK_FLOOR,
+                 maxSamples=TWK_ADAPTIVE_MAX_SAMPLES):
+        super().__init__(targetNoise, int(minSamples), darkFloor, int(maxSamples))
+
+
 class NoiseSummary(C.Structure):
     """≙ TwkNoiseSummary: what twk_estimate_noise reduces a stream of luminance moments to (csrc/noise_device.h). valid / unknown /
     empty count the elements; the rest describes e, the relative standard error of the luminance mean, over the valid ones."""
@@ -206,6 +218,8 @@ SYMBOLS = [
     "twk_set_sample_offset", "twk_enable_geometry", "twk_render_geometry", "twk_read_geometry", "twk_get_geometry_device_pointer",
     "twk_temporal_defaults", "twk_temporal_accumulate", "twk_temporal_reset", "twk_get_temporal_device_pointers", "twk_read_temporal", "twk_read_temporal_moments",
     "twk_noise_defaults", "twk_estimate_noise", "twk_read_noise", "twk_noise_merge", "twk_noise_mean", "twk_noise_quantile", "twk_app_get_target_noise",
+    "twk_enable_adaptive", "twk_adaptive_defaults", "twk_adaptive_select", "twk_adaptive_select_host", "twk_launch_adaptive", "twk_read_sample_counts",
+    "twk_get_sample_counts_device_pointer", "twk_read_active", "twk_app_get_adaptive",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

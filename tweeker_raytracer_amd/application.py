@@ -132,6 +132,15 @@ class Application:
         return bool(on.value), t.value, q.value, n.value
 
     @property
+    def adaptive(self):
+        """(enabled, Adaptive) from "adaptiveSampling", "adaptiveMaxSamples" of the system description: enabled = the key is on and a
+        "targetNoise" is set; target, minSamples and darkFloor are the stopping rule's. initDevice enables the device's moments and
+        adaptive sampling then."""
+        on, ap = C.c_int(0), L.Adaptive()
+        L.check(L.lib.twk_app_get_adaptive(self._h, C.byref(on), C.byref(ap)))
+        return bool(on.value), ap
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

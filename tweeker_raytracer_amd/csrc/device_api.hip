@@ -240,6 +240,7 @@ try
   freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); freeDevice(dev->d_moments);
   freeDevice(dev->d_geometry); dropTemporal(dev);
   freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams); freeDevice(dev->d_noise);
+  freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); freeDevice(dev->d_adaptiveScratch);
   dev->builder.release();
   for (int k = 1; k < TWK_MAX_LANES; ++k)
   {
@@ -266,7 +267,7 @@ try
   HIP_TRY(hipStreamSynchronize(dev->stream)); // Device.cpp:1194-1195
   if (dev->stateSet && (dev->state.resolution[0] != s->resolution[0] || dev->state.resolution[1] != s->resolution[1])) dropTemporal(dev);
   dev->state = *s;
-  dev->stateSet = true; dev->geometryValid = false;
+  dev->stateSet = true; dev->geometryValid = false; dropAdaptive(dev);
   if (s->distribution && 1 < dev->count)
   {
     // DeviceMultiGPULocalCopy.cpp:84-97
@@ -468,7 +469,7 @@ try
   freeDevice(dev->d_outputInternal);
   freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
   freeDevice(dev->d_denoised); dev->denoisedValid = false; // a denoised picture is in the format it was filtered in
-  dev->outputFormat = format;
+  dev->outputFormat = format; dropAdaptive(dev);
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS;
 }
 TWK_CATCH("twk_set_output_format")
@@ -506,7 +507,7 @@ try
 {
   int rc = activate(dev, "twk_enable_moments"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->momentsEnabled = (enable != 0);
+  dev->momentsEnabled = (enable != 0); dropAdaptive(dev);
   if (!dev->momentsEnabled) { freeDevice(dev->d_moments); dev->momentsPixels = 0; return TWK_SUCCESS; } // enabled again: a zeroed buffer
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first pass after twk_set_state
 }
@@ -653,6 +654,7 @@ static int setExternalOutput(TwkDevice dev, void* dptr, size_t bytes, bool frame
 {
   int rc = activate(dev, where); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
+  dropAdaptive(dev);
   if (dptr == nullptr) { dev->d_outputExternal = nullptr; dev->outputExternalBytes = 0; dev->outputFrame = false; return TWK_SUCCESS; }
   if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": twk_set_state first");
   if (bytes < (size_t) (frame ? dev->state.resolution[0] : dev->launchWidth) * dev->state.resolution[1] * pixelBytes(dev))

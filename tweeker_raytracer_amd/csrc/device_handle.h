@@ -1,12 +1,13 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
-// tonemap, denoiser, temporal, noise estimate), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
 #include "denoise_device.h"
 #include "temporal_device.h"
 #include "noise_device.h"
+#include "adaptive_device.h"
 #include "error_state.h"
 
 #include <string>
@@ -35,6 +36,10 @@ void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, co
 void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
+void launchGenerateActive(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, unsigned int numActive, hipStream_t stream);
+void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, hipStream_t stream);
+unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
+                                   const AdaptiveConstants& k, int numCUs, hipStream_t stream);
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 }
 
@@ -161,6 +166,16 @@ struct TwkDevice_t
   float4* d_denoiseStreams = nullptr; size_t denoiseStreamPixels = 0;
   // twk_estimate_noise: the summary the kernel adds into (noise_device.h), zeroed on the stream before each launch; noiseValid: an estimate has been issued
   TwkNoiseSummary* d_noise = nullptr; bool noiseValid = false;
+  // twk_enable_adaptive: per launch index the iteration its next adaptive sample uses (d_sampleCounts) and the ascending list of
+  // the launch indices the last twk_adaptive_select chose (d_active, numActive of them), both launchWidth x height words, and the
+  // select's scan scratch (adaptive_device.h adaptiveScratchBytes of adaptiveScratchElements elements; also the explicit form's).
+  //   uniformNext     the index after the last iteration a flushed twk_launch rendered
+  //   countsCurrent   d_sampleCounts says what the picture holds; else it is filled with uniformNext before it is read
+  //   adaptiveStarted an adaptive pass has run since the last restart: the picture is no longer uniform, twk_launch(i != 0) is refused
+  //   activeValid     d_active is the list of a select that nothing has invalidated since
+  bool adaptiveEnabled = false; unsigned int* d_sampleCounts = nullptr; unsigned int* d_active = nullptr; int adaptivePixels = 0;
+  void* d_adaptiveScratch = nullptr; size_t adaptiveScratchElements = 0;
+  unsigned int uniformNext = 0, numActive = 0; bool countsCurrent = false, adaptiveStarted = false, activeValid = false;
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;
@@ -222,6 +237,8 @@ void refreshParams(TwkDevice dev);
 int slimSlotBits(TwkDevice dev);
 int ensureStreams(TwkDevice dev, int samples = 1);
 int checkDroppedPushes(TwkDevice dev, const char* where);
+void dropAdaptive(TwkDevice dev);
+int currentSampleCounts(TwkDevice dev);
 // device_api.hip
 int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int enable);
 int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);

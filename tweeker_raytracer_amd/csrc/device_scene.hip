@@ -36,7 +36,7 @@ try
 {
   int rc = activate(dev, "twk_clear_scene"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->geometries.clear(); dev->instances.clear(); dev->built = false;
+  dev->geometries.clear(); dev->instances.clear(); dev->built = false; dropAdaptive(dev);
   dev->geometryValid = false; dropTemporal(dev);
   return TWK_SUCCESS;
 }
@@ -131,6 +131,7 @@ try
 {
   int rc = activate(dev, "twk_build"); if (rc) return rc;
   if (dev->geometries.empty() || dev->instances.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: the scene has no geometry or no instance");
+  dropAdaptive(dev);
   dev->built = false; // until this build has succeeded: a failure below leaves no half-built scene to launch on
   const auto buildStart = std::chrono::steady_clock::now();
   TwkBuildInfo info;

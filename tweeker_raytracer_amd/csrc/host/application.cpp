@@ -158,6 +158,14 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 1) targetNoiseInterval = i[0];
       else if (ok) warnings.push_back("targetNoiseInterval must be >= 1, keeping the previous value");
     }
+    // adaptive sampling (twk_adaptive_select / twk_launch_adaptive, read by twk_app_get_adaptive)
+    else if (key == "adaptiveSampling")    { ok = readInt(parser, i[0]); if (ok) adaptiveSampling = (i[0] == 1) ? 1 : 0; }
+    else if (key == "adaptiveMaxSamples")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 1) adaptiveMaxSamples = i[0];
+      else if (ok) warnings.push_back("adaptiveMaxSamples must be >= 1, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -175,6 +183,12 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
     }
 
     if (!ok) { error = where("system description", parser, key); return false; }
+  }
+
+  if (adaptiveSampling != 0 && !(targetNoise > 0.0f)) // in whichever order the two keys came
+  {
+    adaptiveSampling = 0;
+    warnings.push_back("adaptiveSampling needs a targetNoise to select by, dropping it");
   }
 
   camera.setResolution(resolution[0], resolution[1]); // Application.cpp:207
@@ -218,6 +232,8 @@ std::string Application::systemDescription() const
   if (targetNoise != 0.0f) d << "targetNoise " << targetNoise << std::endl;
   if (targetNoiseQuantile != 0.95f) d << "targetNoiseQuantile " << targetNoiseQuantile << std::endl;
   if (targetNoiseInterval != 16) d << "targetNoiseInterval " << targetNoiseInterval << std::endl;
+  if (adaptiveSampling != 0) d << "adaptiveSampling " << adaptiveSampling << std::endl;
+  if (adaptiveMaxSamples != (int) TWK_ADAPTIVE_MAX_SAMPLES) d << "adaptiveMaxSamples " << adaptiveMaxSamples << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

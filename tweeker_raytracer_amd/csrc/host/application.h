@@ -104,6 +104,10 @@ public:
   float targetNoise = 0.0f;
   float targetNoiseQuantile = 0.95f;
   int   targetNoiseInterval = 16;
+  // "adaptiveSampling" (1: between the stopping rule's checks the render loop samples only the pixels twk_adaptive_select picks
+  // by "targetNoise"; dropped without a target), "adaptiveMaxSamples" (no pixel is selected once it has this many samples)
+  int   adaptiveSampling = 0;
+  int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   int   shaderVariant = 0; // grammar extension "shaderVariant": 0 rtigo3, 1 Optix7Gui light-hit rule (include/tweeker_hip.h TWK_SHADERS_*)
   int   samplesSqrt   = 1;
   int   resolution[2] = {1, 1};

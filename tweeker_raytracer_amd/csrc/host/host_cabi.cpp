@@ -148,6 +148,20 @@ try
 }
 TWK_CATCH("twk_app_get_target_noise")
 
+int twk_app_get_adaptive(TwkApp app, int* enabled, TwkAdaptive* ap)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_adaptive: NULL app");
+  if (!enabled || !ap) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_adaptive: NULL argument");
+  const Application& a = app->app;
+  *enabled = (a.adaptiveSampling != 0 && a.targetNoise > 0.0f) ? 1 : 0;
+  int rc = twk_adaptive_defaults(ap); if (rc) return rc; // minSamples and darkFloor: the ones twk_estimate_noise defaults to, which the stopping rule uses
+  if (a.targetNoise > 0.0f) ap->targetNoise = a.targetNoise;
+  ap->maxSamples = (unsigned int) a.adaptiveMaxSamples;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_adaptive")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -243,6 +257,7 @@ try
   if (a.denoiser > 1 && (rc = twk_enable_aov(dev, 1))) return rc; // "denoiser 2|3": the filter's guides are the AOVs
   if (a.denoiser != 0 && a.denoiserSampledVariance && (rc = twk_enable_moments(dev, 1))) return rc; // "denoiserSampledVariance 1": the filter's variance is the samples'
   if (a.targetNoise > 0.0f && (rc = twk_enable_moments(dev, 1))) return rc; // "targetNoise e": the stopping rule reads the samples' moments
+  if (a.adaptiveSampling != 0 && a.targetNoise > 0.0f && (rc = twk_enable_adaptive(dev, 1))) return rc; // "adaptiveSampling 1": per-pixel sample counts and the active list
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;
   if ((rc = twk_init_materials(dev, a.materials.data(), (int) a.materials.size()))) return rc;

@@ -5,6 +5,10 @@
 // With "targetNoise e" in the system description the loop may end earlier: every "targetNoiseInterval" iterations each device
 // estimates the noise of its own buffer (twk_estimate_noise), the summaries are merged, and the loop ends once the
 // "targetNoiseQuantile" quantile of the relative standard error is at most e; a second line prints the final mean and quantile.
+// With "adaptiveSampling 1" beside it the loop renders uniformly up to the first check only; from then on every device selects the
+// pixels above the target (twk_adaptive_select) and renders "targetNoiseInterval" more samples of those alone
+// (twk_launch_adaptive) between two checks. It ends when the target is met, when no device selects anything, or when the samples
+// spent reach the uniform budget, samplesSqrt² x the pixel count; the second line gains the samples per pixel and the active share.
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -155,6 +159,15 @@ int main(int argc, char* argv[])
   float targetNoise = 0.0f, targetNoiseQuantile = 0.0f;
   TWK_OK(twk_app_get_target_noise(app, &targetNoiseEnabled, &targetNoise, &targetNoiseQuantile, &targetNoiseInterval));
 
+  int adaptiveEnabled = 0; // "adaptiveSampling 1": between the checks only the pixels above the target are sampled
+  TwkAdaptive adaptive;
+  TWK_OK(twk_app_get_adaptive(app, &adaptiveEnabled, &adaptive));
+  if (adaptiveEnabled && count > 1 && (info.strategy == 1 || info.strategy == 2))
+  {
+    std::cerr << "ERROR: adaptiveSampling renders into packed tile buffers (strategy 0 or 3), not into a shared frame (strategy 1 or 2)\n";
+    return 1;
+  }
+
   std::vector<TwkDevice> devices((size_t) count, nullptr);
   TwkDeviceState state;
   TWK_OK(twk_app_get_state(app, &state));
@@ -217,6 +230,7 @@ int main(int argc, char* argv[])
   memset(&noise, 0, sizeof(noise));
   float noiseQuantile = 0.0f;
   bool noiseChecked = false; // `noise` is the summary of the frame as it stands
+  bool adaptivePhase = false; // the first check has not met the target and "adaptiveSampling" is on
   // every device estimates its own buffer (a packed tile buffer's padding is empty), the host merges; true: the target is met
   auto checkNoise = [&](bool& met) -> int
   {
@@ -247,7 +261,43 @@ int main(int argc, char* argv[])
       if (checkNoise(met)) return 1;
       noiseChecked = true;
       if (met) break;
+      if (adaptiveEnabled) { adaptivePhase = true; break; }
     }
+  }
+  // The adaptive loop (INTEGRATION.md "The adaptive loop"): select, render the interval's samples on the selected pixels, check
+  const unsigned long long pixelCount = (unsigned long long) info.resolution[0] * (unsigned long long) info.resolution[1];
+  const unsigned long long budget = (unsigned long long) spp * pixelCount;
+  unsigned long long spent = (unsigned long long) iterationIndex * pixelCount, lastActive = pixelCount;
+  const char* adaptiveEnd = "target met";
+  if (adaptivePhase)
+  {
+    int batch = 64; // samples per pass at most: the launch batch (TWK_BATCH, as the handles read it)
+    if (const char* e = getenv("TWK_BATCH")) batch = std::max(1, std::min(64, atoi(e)));
+    std::vector<unsigned int> numActive((size_t) count, 0u);
+    for (;;)
+    {
+      lastActive = 0;
+      for (int i = 0; i < count; ++i)
+      {
+        TWK_OK(twk_adaptive_select(devices[(size_t) i], &adaptive, nullptr, nullptr, 0, nullptr, &numActive[(size_t) i]));
+        lastActive += numActive[(size_t) i];
+      }
+      if (lastActive == 0) { adaptiveEnd = "nothing selected"; break; }
+      unsigned long long left = std::min<unsigned long long>((unsigned long long) targetNoiseInterval, (budget - spent) / lastActive);
+      if (left == 0) { adaptiveEnd = "budget spent"; break; }
+      while (left > 0)
+      {
+        const int samples = (int) std::min<unsigned long long>(left, (unsigned long long) batch);
+        for (int i = 0; i < count; ++i) TWK_OK(twk_launch_adaptive(devices[(size_t) i], samples));
+        spent += lastActive * (unsigned long long) samples;
+        left -= (unsigned long long) samples;
+      }
+      bool met = false;
+      if (checkNoise(met)) return 1;
+      if (met) break;
+    }
+    noiseChecked = true; // nothing was rendered after the last check
+    iterationIndex = (unsigned int) ((spent + pixelCount - 1) / pixelCount); // the mean samples per pixel, rounded up
   }
   for (int i = 0; i < count; ++i) TWK_OK(twk_sync(devices[(size_t) i]));
   const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
@@ -271,6 +321,20 @@ int main(int argc, char* argv[])
       stream << ", mean " << mean << ", " << targetNoiseQuantile << " quantile at most " << noiseQuantile << ", target " << targetNoise;
     }
     else stream << ", no pixel has enough samples yet, target " << targetNoise;
+    if (adaptivePhase)
+    {
+      unsigned int largest = 0;
+      for (int i = 0; i < count; ++i)
+      {
+        int launchWidth = 0;
+        TWK_OK(twk_get_launch_width(devices[(size_t) i], &launchWidth));
+        std::vector<uint32_t> counts((size_t) launchWidth * (size_t) info.resolution[1]);
+        TWK_OK(twk_read_sample_counts(devices[(size_t) i], counts.data(), counts.size()));
+        for (const uint32_t c : counts) largest = std::max(largest, (unsigned int) c);
+      }
+      stream << ", adaptive: mean " << double(spent) / double(pixelCount) << " spp, max " << largest << " spp, last active share "
+             << double(lastActive) / double(pixelCount) << ", samples " << spent << " of " << budget << ", ended: " << adaptiveEnd;
+    }
     std::cout << stream.str() << std::endl;
   }
 

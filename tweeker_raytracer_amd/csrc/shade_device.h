@@ -897,11 +897,11 @@ TWK_D void shadePath(const LaunchParams& p, int depth, unsigned int pixel, const
 // the first shade launch each compute it instead of passing it through memory — the same function, the same bits.
 struct PrimaryRay { V3 origin, direction; unsigned int seed; bool active; };
 
-TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index)
+// The primary ray of sample `sampleIndex` of launch index `launchIndex` in a pass that starts at iteration `firstIteration`: the one
+// text both a uniform pass (primaryRay below: the pass's iteration index) and an adaptive pass (generateActivePath: the launch
+// index's own sample count stands where the iteration index does) take their rays from.
+TWK_D PrimaryRay primaryRayAt(const LaunchParams& p, const unsigned int launchIndex, const unsigned int firstIteration, const unsigned int sampleIndex)
 {
-  const unsigned int path = index + (unsigned int) p.pathBase; // path of the whole pass; `index` counts within this launch's lane
-  const unsigned int sampleIndex = path / (unsigned int) p.numPixels;
-  const unsigned int launchIndex = path - sampleIndex * (unsigned int) p.numPixels;
   const unsigned int lx = launchIndex % (unsigned int) p.launchWidth;
   const unsigned int ly = launchIndex / (unsigned int) p.launchWidth;
 
@@ -917,7 +917,7 @@ TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index)
   unsigned int seed = 0;
   if (active)
   {
-    seed = tea<4>((unsigned int) p.resolution[0] * ly + launchColumn, (p.iterationIndex + p.sampleOffset) + sampleIndex); // twk_set_sample_offset: 0 unless set
+    seed = tea<4>((unsigned int) p.resolution[0] * ly + launchColumn, (firstIteration + p.sampleOffset) + sampleIndex); // twk_set_sample_offset: 0 unless set
 
     const float screenX = float(p.resolution[0]), screenY = float(p.resolution[1]);
     const float pixelX  = float(launchColumn),    pixelY  = float(ly);
@@ -963,11 +963,17 @@ TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index)
   return r;
 }
 
-// Body of generateKernel for path `index` of the launch (shade_kernels.hip; also what the host build of the kernels runs:
-// oracle/host_kernels.cpp).
-TWK_D void generatePath(const LaunchParams& p, const unsigned int index)
+TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index)
 {
-  const PrimaryRay ray = primaryRay(p, index);
+  const unsigned int path = index + (unsigned int) p.pathBase; // path of the whole pass; `index` counts within this launch's lane
+  const unsigned int sampleIndex = path / (unsigned int) p.numPixels;
+  const unsigned int launchIndex = path - sampleIndex * (unsigned int) p.numPixels;
+  return primaryRayAt(p, launchIndex, p.iterationIndex, sampleIndex);
+}
+
+// What generateKernel stores for path `index` whose primary ray is `ray`: the integrator's prologue and record `index` of queue 0.
+TWK_D void storePrimaryPath(const LaunchParams& p, const unsigned int index, const PrimaryRay& ray)
+{
   const V3 origin = ray.origin, direction = ray.direction;
   const unsigned int seed = ray.seed;
   const bool active = ray.active;
@@ -988,6 +994,22 @@ TWK_D void generatePath(const LaunchParams& p, const unsigned int index)
   p.rayDir[0][index]   = make_float4(direction.x, direction.y, direction.z, active ? RT_DEFAULT_MAX : -1.0f);
   p.rayPixel[0][index] = index;
   if (index == 0) p.counters[0] = (unsigned int) p.numPaths;
+}
+
+// Body of generateKernel for path `index` of the launch (shade_kernels.hip; also what the host build of the kernels runs:
+// oracle/host_kernels.cpp).
+TWK_D void generatePath(const LaunchParams& p, const unsigned int index)
+{
+  storePrimaryPath(p, index, primaryRay(p, index));
+}
+
+// Body of generateActiveKernel for path `index` of an adaptive pass (twk_launch_adaptive): sample index / numActive of the
+// index % numActive-th launch index of the active list, at the iteration that launch index's own sample count says.
+TWK_D void generateActivePath(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, const unsigned int numActive, const unsigned int index)
+{
+  const unsigned int sampleIndex = index / numActive;
+  const unsigned int launchIndex = active[index - sampleIndex * numActive];
+  storePrimaryPath(p, index, primaryRayAt(p, launchIndex, counts[launchIndex], sampleIndex));
 }
 
 // Where launch index `index` accumulates: its slot of the packed tile buffer (single device, LocalCopy), or — shared frame of
@@ -1025,59 +1047,77 @@ struct StoredAsFloat { TWK_HD float4 operator()(const float4 v) const { return v
 // n is a float (exact up to 2^24 samples). A sample that is not finite makes the triple not finite; nothing is caught here, the
 // consumer (denoise_device.h, the SAMPLED moments pass) falls back to its spatial estimate for such a pixel. M2 / (n - 1) is
 // the sample variance of the luminance, M2 / ((n - 1) n) the variance of the pixel's mean. Never rounded to half.
+// foldSample is the fold of ONE sample, the path `path` at iteration `iteration`; foldSamples and foldActiveSamples say which.
+template<bool MOMENTS, typename Stored>
+TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned int iteration, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments)
+{
+  const bool aov = (p.aovAlbedo != nullptr);
+  const float4 r = p.pathRadiance[path];
+  if (r.w == 0.0f) return false; // launch index outside the image (tile padding): never written, like the early return at raygeneration.cu:180-183
+  V3 radiance = v3(r.x, r.y, r.z);
+  bool keep = !(isnan(radiance.x) || isnan(radiance.y) || isnan(radiance.z));
+  if (p.debugExceptions) // raygeneration.cu:205-218: numerical errors in false colours, and every sample is accumulated
+  {
+    if (!keep)                                                             radiance = v3(1000000.0f, 0.0f, 0.0f); // super red
+    else if (isinf(radiance.x) || isinf(radiance.y) || isinf(radiance.z)) radiance = v3(0.0f, 1000000.0f, 0.0f); // super green
+    else if (radiance.x < 0.0f || radiance.y < 0.0f || radiance.z < 0.0f) radiance = v3(0.0f, 0.0f, 1000000.0f); // super blue
+    keep = true;
+  }
+  if (!keep) return false;
+  if (MOMENTS)
+  {
+    const float l = luminance3(radiance.x, radiance.y, radiance.z);
+    if (iteration == 0) { moments->x = 0.0f; moments->y = 0.0f; moments->z = 0.0f; }
+    moments->z = moments->z + 1.0f;
+    const float d = l - moments->x;
+    moments->x = moments->x + d / moments->z;
+    moments->y = moments->y + d * (l - moments->x);
+  }
+  V3 albedo = v3(0.0f), normal = v3(0.0f);
+  if (aov) { albedo = v3(p.pathAlbedo[path]); normal = v3(p.pathNormal[path]); }
+  // time view (raygeneration.cu:231-244): alpha = the sample's clock cycles * clockScale, accumulated like the radiance
+  float alpha = (p.pathTime != nullptr) ? p.pathTime[path] * p.clockScale : 1.0f;
+  if (0 < iteration)
+  {
+    const float t = 1.0f / float(iteration + 1);
+    radiance = lerp(v3(dst.x, dst.y, dst.z), radiance, t);
+    if (p.pathTime != nullptr) alpha = dst.w + t * (alpha - dst.w); // lerp(dst, result, t), fourth component
+    if (aov)
+    {
+      // Optix7Gui raygeneration.cu:243-252: same running mean; the mean normal is renormalised unless it vanished
+      albedo = lerp(v3(dstAlbedo), albedo, t);
+      normal = lerp(v3(dstNormal), normal, t);
+      if (isNotNull(normal)) normal = normalize(normal);
+    }
+  }
+  dst = stored(make_float4(radiance.x, radiance.y, radiance.z, alpha));
+  dstAlbedo = stored(make_float4(albedo.x, albedo.y, albedo.z, 1.0f));
+  dstNormal = stored(make_float4(normal.x, normal.y, normal.z, 0.0f));
+  return true;
+}
+
+// The samples of a uniform pass: sample s of launch index `index` is path s * numPixels + index, at iteration iterationIndex + s.
 template<bool MOMENTS = false, typename Stored>
 TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments = nullptr)
 {
-  const bool aov = (p.aovAlbedo != nullptr);
   bool touched = false;
   for (int s = 0; s < p.batchCount; ++s)
   {
-    const size_t path = (size_t) s * p.numPixels + index;
-    const float4 r = p.pathRadiance[path];
-    if (r.w == 0.0f) continue; // launch index outside the image (tile padding): never written, like the early return at raygeneration.cu:180-183
-    V3 radiance = v3(r.x, r.y, r.z);
-    bool keep = !(isnan(radiance.x) || isnan(radiance.y) || isnan(radiance.z));
-    if (p.debugExceptions) // raygeneration.cu:205-218: numerical errors in false colours, and every sample is accumulated
-    {
-      if (!keep)                                                             radiance = v3(1000000.0f, 0.0f, 0.0f); // super red
-      else if (isinf(radiance.x) || isinf(radiance.y) || isinf(radiance.z)) radiance = v3(0.0f, 1000000.0f, 0.0f); // super green
-      else if (radiance.x < 0.0f || radiance.y < 0.0f || radiance.z < 0.0f) radiance = v3(0.0f, 0.0f, 1000000.0f); // super blue
-      keep = true;
-    }
-    if (keep)
-    {
-      const unsigned int iteration = p.iterationIndex + (unsigned int) s;
-      if (MOMENTS)
-      {
-        const float l = luminance3(radiance.x, radiance.y, radiance.z);
-        if (iteration == 0) { moments->x = 0.0f; moments->y = 0.0f; moments->z = 0.0f; }
-        moments->z = moments->z + 1.0f;
-        const float d = l - moments->x;
-        moments->x = moments->x + d / moments->z;
-        moments->y = moments->y + d * (l - moments->x);
-      }
-      V3 albedo = v3(0.0f), normal = v3(0.0f);
-      if (aov) { albedo = v3(p.pathAlbedo[path]); normal = v3(p.pathNormal[path]); }
-      // time view (raygeneration.cu:231-244): alpha = the sample's clock cycles * clockScale, accumulated like the radiance
-      float alpha = (p.pathTime != nullptr) ? p.pathTime[path] * p.clockScale : 1.0f;
-      if (0 < iteration)
-      {
-        const float t = 1.0f / float(iteration + 1);
-        radiance = lerp(v3(dst.x, dst.y, dst.z), radiance, t);
-        if (p.pathTime != nullptr) alpha = dst.w + t * (alpha - dst.w); // lerp(dst, result, t), fourth component
-        if (aov)
-        {
-          // Optix7Gui raygeneration.cu:243-252: same running mean; the mean normal is renormalised unless it vanished
-          albedo = lerp(v3(dstAlbedo), albedo, t);
-          normal = lerp(v3(dstNormal), normal, t);
-          if (isNotNull(normal)) normal = normalize(normal);
-        }
-      }
-      dst = stored(make_float4(radiance.x, radiance.y, radiance.z, alpha));
-      dstAlbedo = stored(make_float4(albedo.x, albedo.y, albedo.z, 1.0f));
-      dstNormal = stored(make_float4(normal.x, normal.y, normal.z, 0.0f));
-      touched = true;
-    }
+    if (foldSample<MOMENTS>(p, (size_t) s * p.numPixels + index, p.iterationIndex + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
+  }
+  return touched;
+}
+
+// The samples of an adaptive pass (twk_launch_adaptive) for entry k of its active list of numActive launch indices: sample s is
+// path s * numActive + k, at iteration count + s, where count is the launch index's own sample count before the pass.
+template<typename Stored>
+TWK_D bool foldActiveSamples(const LaunchParams& p, const unsigned int k, const unsigned int numActive, const unsigned int count, const int samples,
+                             float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments)
+{
+  bool touched = false;
+  for (int s = 0; s < samples; ++s)
+  {
+    if (foldSample<true>(p, (size_t) s * numActive + k, count + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
   }
   return touched;
 }

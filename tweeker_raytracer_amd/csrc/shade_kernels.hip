@@ -32,6 +32,16 @@ __global__ void __launch_bounds__(256) generateKernel(LaunchParams p)
   generatePath(p, index);
 }
 
+// generateKernel of an adaptive pass (twk_launch_adaptive): one thread per path = (sample, entry of the active list). Queue 0 is
+// written exactly as generateKernel writes it; only the launch index (active[k]) and the iteration (counts[active[k]] + sample)
+// of the primary ray come from the lists (shade_device.h generateActivePath).
+__global__ void __launch_bounds__(256) generateActiveKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ counts, unsigned int numActive)
+{
+  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
+  if (index >= (unsigned int) p.numPaths) return;
+  generateActivePath(p, active, counts, numActive, index);
+}
+
 // ---------------------------------------------------------------------------------------------
 // One thread per ray of queue (depth & 1): shadePath(), then append the continuation ray — with the path's throughput,
 // pdf, RNG state and flags, which travel in the queue next to the ray so that every access of a bounce is a coalesced
@@ -500,6 +510,51 @@ __global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
   }
 }
 
+// The accumulate kernel of an adaptive pass: one thread per entry k of the active list folds the `samples` samples of launch index
+// active[k] (paths s * numActive + k) onto its running means and moments with the fold of the kernels above (shade_device.h
+// foldSample), sample s at iteration counts[active[k]] + s, and advances the launch index's sample count. The moments are always
+// on here (the list was selected from them). HALF: the RGBA16F buffers, as accumulateHalfKernel addresses them.
+template<bool HALF>
+__global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, const unsigned int* __restrict__ active, unsigned int* __restrict__ counts, unsigned int numActive, int samples)
+{
+  const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= numActive) return;
+  const unsigned int index = active[k];
+  const unsigned int count = counts[index];
+  counts[index] = count + (unsigned int) samples;
+  size_t outIndex;
+  if (!accumulateTarget(p, index, outIndex)) return;
+  const bool aov = (p.aovAlbedo != nullptr);
+  float4 moments = p.moments[index];
+  if (HALF)
+  {
+    Half4* output = reinterpret_cast<Half4*>(p.output);
+    Half4* aovAlbedo = reinterpret_cast<Half4*>(p.aovAlbedo);
+    Half4* aovNormal = reinterpret_cast<Half4*>(p.aovNormal);
+    float4 dst = widen(output[outIndex]);
+    float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (foldActiveSamples(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments))
+    {
+      output[outIndex] = narrow(dst);
+      if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
+      p.moments[index] = moments;
+    }
+  }
+  else
+  {
+    float4 dst = p.output[outIndex];
+    float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (foldActiveSamples(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments))
+    {
+      p.output[outIndex] = dst;
+      if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
+      p.moments[index] = moments;
+    }
+  }
+}
+
 // compositor.cu:38-64 for every source device in one launch: tiles is [deviceCount][H][launchWidth]. Pixel: float4 or Half4
 // (a plain 8-byte copy).
 template<typename Pixel>
@@ -636,6 +691,18 @@ void launchGenerate(const LaunchParams& p, hipStream_t stream)
 {
   hipLaunchKernelGGL(generateKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p);
 }
+void launchGenerateActive(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, unsigned int numActive, hipStream_t stream)
+{
+  hipLaunchKernelGGL(generateActiveKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, active, counts, numActive);
+}
+
+void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, hipStream_t stream)
+{
+  const dim3 grid((numActive + 255u) / 256u);
+  if (half) hipLaunchKernelGGL(accumulateActiveKernel<true>, grid, dim3(256), 0, stream, p, active, counts, numActive, samples);
+  else      hipLaunchKernelGGL(accumulateActiveKernel<false>, grid, dim3(256), 0, stream, p, active, counts, numActive, samples);
+}
+
 template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>
 static void launchShadeBuild(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
 {

@@ -411,6 +411,48 @@ class Device:
         L.check(L.lib.twk_read_noise(self._h, C.byref(out)))
         return out
 
+    # ---- adaptive sampling (include/tweeker_hip.h "Adaptive sampling", csrc/adaptive_device.h) ----
+    def enableAdaptive(self, enable=True):
+        """twk_enable_adaptive: per launch index a sample count, the iteration its next adaptive sample uses, and the active list
+        adaptiveSelect fills and renderAdaptive renders. Needs enableMoments first."""
+        L.check(L.lib.twk_enable_adaptive(self._h, int(bool(enable))))
+
+    def adaptiveSelect(self, params=None, moments=None, counts=None, numElements=0, activeOut=None):
+        """twk_adaptive_select: the ascending list of the elements that are not empty, whose count is below params.maxSamples and
+        whose relative standard error is above params.targetNoise or unknown; returns its length (synchronises). params: L.Adaptive
+        (None = the defaults). Without buffers the handle's own moments, counts and list (a packed tile buffer is fine); otherwise
+        device pointers to numElements float4, numElements uint32 and, for the list, numElements uint32."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        n = C.c_uint(0)
+        L.check(L.lib.twk_adaptive_select(self._h, None if params is None else C.byref(params), ptr(moments), ptr(counts), C.c_size_t(int(numElements)),
+                                          ptr(activeOut), C.byref(n)))
+        return n.value
+
+    def renderAdaptive(self, samples):
+        """twk_launch_adaptive: `samples` (1..64) samples of every launch index of the active list, each at the iteration its own
+        count says; asynchronous. Afterwards render(i) is refused for i != 0; render(0) restarts a uniform frame."""
+        L.check(L.lib.twk_launch_adaptive(self._h, int(samples)))
+
+    def readSampleCounts(self):
+        """uint32 [height, launchWidth]: per launch index the iteration index its next sample uses = the samples it has been given."""
+        out = np.empty((self.state.resolution[1], self.launchWidth), dtype=np.uint32)
+        L.check(L.lib.twk_read_sample_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(out.size)))
+        return out
+
+    def sampleCountsDevicePointer(self):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_sample_counts_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readActive(self):
+        """uint32 [numActive]: the launch indices the last adaptiveSelect on the handle's own buffers chose, ascending."""
+        n = C.c_uint(0)
+        L.check(L.lib.twk_read_active(self._h, None, C.c_size_t(0), C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint32)
+        if n.value:
+            L.check(L.lib.twk_read_active(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(out.size), C.byref(n)))
+        return out
+
     def statsEnable(self, enable=True):
         L.check(L.lib.twk_stats_enable(self._h, int(bool(enable))))
 

@@ -631,6 +631,53 @@ int twk_get_sample_counts_device_pointer(TwkDevice dev, void** dptr, size_t* byt
  * 0: the length alone); synchronises. TWK_ERROR_INVALID_VALUE: capacity below the length. TWK_ERROR_INVALID_STATE: no valid list. */
 int twk_read_active(TwkDevice dev, uint32_t* host, size_t capacity, unsigned int* numActive);
 
+/* ---- Planned adaptive pass — new calls, ABI stays 9, no existing struct changes; twk_adaptive_select, twk_launch_adaptive and their
+ * kernels are what they were, and without these calls no bit of any picture changes -------------------------------------------------
+ * Gives each unfinished launch index the samples its own noise estimate predicts. e is the standard error of a mean of n samples and
+ * falls as 1 / sqrt(n), so an element at e reaches the target at about n (e / target)^2 samples: its budget for one pass is that
+ * number less n, within [minBatch, maxBatch] and the room maxSamples leaves. One twk_adaptive_plan turns moments and counts into the
+ * active list and, per entry, the offset of its first path; one twk_launch_adaptive_planned renders the sum of the budgets as ONE
+ * wavefront pass. The INVARIANT above holds: a launch index whose count is c holds exactly the bits of twk_launch(0 .. c-1). What it
+ * is NOT: a guarantee (the estimate is low where samples are few, so early plans under-allocate and the next plan corrects them), and
+ * it is driven by the luminance estimate, so by neither colour, the denoised picture nor bias.
+ * minBatch, maxBatch: 1 <= minBatch <= maxBatch <= 64 (twk_launch_adaptive's own limit). The defaults (TWK_DENOISER_MIN_SAMPLES: one
+ * pass makes an element without an estimate classifiable; 64) are PROVISIONAL: chosen by reasoning, not yet by a measured sweep. */
+typedef struct TwkAdaptivePlan { uint32_t minBatch; uint32_t maxBatch; } TwkAdaptivePlan;
+int twk_adaptive_plan_defaults(TwkAdaptivePlan* plan); /* minBatch TWK_DENOISER_MIN_SAMPLES, maxBatch 64 (provisional) */
+/* Plans, and synchronises once. Element i is in the plan exactly when twk_adaptive_select selects it for the same `ap`; its budget b:
+ * UNKNOWN -> minBatch; VALID -> r = e / targetNoise, q = r r, need = n q, extra = need - n (float32, one rounding each),
+ * b = !(extra < maxBatch) ? maxBatch : ceilf(extra), then max(b, minBatch); last b = min(b, maxSamples - counts[i]). The complete
+ * definition is csrc/adaptive_plan_device.h; tests/adaptive_plan_restate.py restates it in numpy. activeOut receives the planned i in
+ * ascending order (*numActive of them), pathOffsetOut the exclusive prefix sum of their budgets and, at [*numActive], *numPaths: entry k
+ * owns paths pathOffsetOut[k] .. pathOffsetOut[k + 1] - 1. Never writes its inputs. ap, plan NULL: the defaults. Own-buffer form
+ * (moments, counts, activeOut, pathOffsetOut NULL, numElements 0): the handle's moments and counts, and a list and offsets of the
+ * plan's OWN (not twk_read_active's list: a plan leaves the last select's list valid), which twk_launch_adaptive_planned renders;
+ * recorded launches are rendered first; allowed on a packed tile buffer, whose padding is EMPTY and gets budget 0. Explicit form:
+ * device buffers of numElements float4, numElements words, and for the outputs numElements and numElements + 1 words.
+ * TWK_ERROR_INVALID_VALUE: a NULL handle, numActive or numPaths (before any HIP call), the parameter refusals of twk_adaptive_select,
+ * a plan outside 1 <= minBatch <= maxBatch <= 64, an output that overlaps an input or the other output, some but not all of the four
+ * pointers, numElements that is not 0 without them, or is 0 or above 2^31 with them, and a plan of more than INT_MAX paths (the message
+ * names both totals, which are still handed out; a wavefront pass counts its paths in an int). TWK_ERROR_INVALID_STATE: the own-buffer
+ * form without twk_enable_moments(1), twk_enable_adaptive(1) and twk_set_state. */
+int twk_adaptive_plan(TwkDevice dev, const TwkAdaptive* ap, const TwkAdaptivePlan* plan, const void* moments, const void* counts, size_t numElements,
+                      void* activeOut, void* pathOffsetOut, unsigned int* numActive, unsigned long long* numPaths);
+/* Host only, no handle: the same definition over host arrays (numElements x 4 floats, numElements words; activeOut holds numElements
+ * words, pathOffsetOut numElements + 1). TWK_ERROR_INVALID_VALUE: a NULL array, the parameter and plan refusals above, numElements
+ * above 2^31, more than INT_MAX paths. */
+int twk_adaptive_plan_host(const TwkAdaptive* ap, const TwkAdaptivePlan* plan, const float* moments, const uint32_t* counts, size_t numElements,
+                           uint32_t* activeOut, uint32_t* pathOffsetOut, size_t* numActive, unsigned long long* numPaths);
+/* Renders the handle's plan as one wavefront pass of numPaths paths, asynchronously: sample s of entry k runs as iteration
+ * count[active[k]] + s, is folded by the uniform pass's own fold in that order, and the count advances by the entry's budget. The
+ * counts advance, so a plan is rendered ONCE: a second call without a new plan is TWK_ERROR_INVALID_STATE (an empty plan is a
+ * successful no-op and stays). A twk_launch, an own-buffer twk_adaptive_select and everything that drops the active list drop the
+ * plan. A twk_launch_adaptive does NOT: a plan rendered after it runs at the counts as they then are (the invariant holds), with the
+ * budgets computed before it, so a count may pass maxSamples by that pass's samples. The other refusals are twk_launch_adaptive's. */
+int twk_launch_adaptive_planned(TwkDevice dev);
+/* The plan of the last own-buffer twk_adaptive_plan: *numActive entries into active (capacity words) and *numActive + 1 into pathOffset
+ * (capacity + 1 words); both NULL and capacity 0: the two totals alone; synchronises. TWK_ERROR_INVALID_VALUE: capacity below the
+ * length, one buffer without the other. TWK_ERROR_INVALID_STATE: no valid plan (none made, dropped, or already rendered). */
+int twk_read_plan(TwkDevice dev, uint32_t* active, uint32_t* pathOffset, size_t capacity, unsigned int* numActive, unsigned long long* numPaths);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);
@@ -761,6 +808,10 @@ int twk_app_get_target_noise(TwkApp app, int* enabled, float* target, float* qua
  * twk_app_init_device enables moments and adaptive sampling when the key is on (rtigo3_hip -m 1 runs the loop; INTEGRATION.md "The
  * adaptive loop"). */
 int twk_app_get_adaptive(TwkApp app, int* enabled, TwkAdaptive* ap);
+/* "adaptiveBudget 0|1" (default 0), "adaptiveMinBatch n" and "adaptiveMaxBatch n" (defaults: twk_adaptive_plan_defaults; a value that
+ * breaks 1 <= adaptiveMinBatch <= adaptiveMaxBatch <= 64 drops the line with a warning). *enabled = the key is on AND adaptive
+ * sampling itself is enabled (twk_app_get_adaptive); rtigo3_hip -m 1 then runs the planned loop (INTEGRATION.md "The adaptive loop"). */
+int twk_app_get_adaptive_plan(TwkApp app, int* enabled, TwkAdaptivePlan* plan);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

@@ -133,6 +133,16 @@ class Adaptive(C.Structure):
         super().__init__(targetNoise, int(minSamples), darkFloor, int(maxSamples))
 
 
+class AdaptivePlan(C.Structure):
+    """≙ TwkAdaptivePlan: parameters of twk_adaptive_plan beside an Adaptive. A planned element gets the samples its noise estimate
+    predicts, n (e / target)^2 - n, within [minBatch, maxBatch] (1 <= minBatch <= maxBatch <= 64) and the room maxSamples leaves; one
+    without an estimate gets minBatch. Without arguments: twk_adaptive_plan_defaults (provisional)."""
+    _fields_ = [("minBatch", C.c_uint32), ("maxBatch", C.c_uint32)]
+
+    def __init__(self, minBatch=TWK_DENOISER_MIN_SAMPLES, maxBatch=64):
+        super().__init__(int(minBatch), int(maxBatch))
+
+
 class NoiseSummary(C.Structure):
     """≙ TwkNoiseSummary: what twk_estimate_noise reduces a stream of luminance moments to (csrc/noise_device.h). valid / unknown /
     empty count the elements; the rest describes e, the relative standard error of the luminance mean, over the valid ones."""
@@ -220,6 +230,7 @@ SYMBOLS = [
     "twk_noise_defaults", "twk_estimate_noise", "twk_read_noise", "twk_noise_merge", "twk_noise_mean", "twk_noise_quantile", "twk_app_get_target_noise",
     "twk_enable_adaptive", "twk_adaptive_defaults", "twk_adaptive_select", "twk_adaptive_select_host", "twk_launch_adaptive", "twk_read_sample_counts",
     "twk_get_sample_counts_device_pointer", "twk_read_active", "twk_app_get_adaptive",
+    "twk_adaptive_plan_defaults", "twk_adaptive_plan", "twk_adaptive_plan_host", "twk_launch_adaptive_planned", "twk_read_plan", "twk_app_get_adaptive_plan",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

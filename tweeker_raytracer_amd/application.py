@@ -141,6 +141,14 @@ class Application:
         return bool(on.value), ap
 
     @property
+    def adaptivePlan(self):
+        """(enabled, AdaptivePlan) from "adaptiveBudget", "adaptiveMinBatch", "adaptiveMaxBatch" of the system description: enabled =
+        the key is on and adaptive sampling itself is (see adaptive); the render loop then plans each interval's pass."""
+        on, plan = C.c_int(0), L.AdaptivePlan()
+        L.check(L.lib.twk_app_get_adaptive_plan(self._h, C.byref(on), C.byref(plan)))
+        return bool(on.value), plan
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()

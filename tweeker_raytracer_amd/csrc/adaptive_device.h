@@ -13,8 +13,8 @@
 //
 // The active list holds the selected i in ascending order: it equals numpy's flatnonzero of the predicate, whatever the grid.
 //
-// What this is not: a prediction of how many samples a pixel still needs (every selected pixel gets the same number per pass),
-// and, as the estimate it reads, it is blind to bias, to colour and to what a denoiser makes of the picture.
+// What this is not: a prediction of how many samples a pixel still needs (every selected pixel gets the same number per pass; the
+// planned pass, adaptive_plan_device.h, starts from this predicate and adds that prediction), and, as the estimate it reads, it is blind to bias, to colour and to what a denoiser makes of the picture.
 #pragma once
 #include "noise_device.h"
 

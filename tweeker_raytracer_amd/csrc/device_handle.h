@@ -8,6 +8,7 @@
 #include "temporal_device.h"
 #include "noise_device.h"
 #include "adaptive_device.h"
+#include "adaptive_plan_device.h"
 #include "error_state.h"
 
 #include <string>
@@ -40,6 +41,10 @@ void launchGenerateActive(const LaunchParams& p, const unsigned int* active, con
 void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, hipStream_t stream);
 unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
                                    const AdaptiveConstants& k, int numCUs, hipStream_t stream);
+void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, unsigned int numActive, hipStream_t stream);
+void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, hipStream_t stream);
+unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, unsigned int* pathOffset,
+                                       void* scratch, const AdaptiveConstants& k, const AdaptivePlanConstants& plan, int numCUs, hipStream_t stream);
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 }
 
@@ -176,6 +181,14 @@ struct TwkDevice_t
   bool adaptiveEnabled = false; unsigned int* d_sampleCounts = nullptr; unsigned int* d_active = nullptr; int adaptivePixels = 0;
   void* d_adaptiveScratch = nullptr; size_t adaptiveScratchElements = 0;
   unsigned int uniformNext = 0, numActive = 0; bool countsCurrent = false, adaptiveStarted = false, activeValid = false;
+  // twk_adaptive_plan, own-buffer form: the plan's list and path offsets (adaptive_plan_device.h) in buffers of their own, planElements
+  // and planElements + 1 words, so that a plan leaves the select's list what it is. The plan's scratch is d_adaptiveScratch, grown to
+  // adaptivePlanScratchBytes of adaptiveScratchElements elements (never less than the select's): adaptiveScratchPlan. planValid: d_planActive / d_planOffsets are the plan of a call that
+  // nothing has invalidated since — what drops a list drops it, a select does, and the planned pass that renders it does (the
+  // counts advance in the pass, so a plan is rendered once).
+  unsigned int* d_planActive = nullptr; unsigned int* d_planOffsets = nullptr; size_t planElements = 0;
+  bool adaptiveScratchPlan = false;
+  unsigned int planActive = 0, planPaths = 0; bool planValid = false;
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;
@@ -239,6 +252,7 @@ int ensureStreams(TwkDevice dev, int samples = 1);
 int checkDroppedPushes(TwkDevice dev, const char* where);
 void dropAdaptive(TwkDevice dev);
 int currentSampleCounts(TwkDevice dev);
+int ensureStreamsForPaths(TwkDevice dev, size_t paths);
 // device_api.hip
 int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int enable);
 int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);

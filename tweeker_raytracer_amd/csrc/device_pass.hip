@@ -7,7 +7,6 @@
 #include <cstring>
 
 static int flushPending(TwkDevice dev);
-static int ensureStreamsForPaths(TwkDevice dev, size_t paths);
 
 int twk::activate(TwkDevice dev, const char* where, bool flush)
 {
@@ -141,7 +140,7 @@ int twk::ensureStreams(TwkDevice dev, int samples)
 }
 
 // ... for a pass of `paths` paths (an adaptive pass: entries of the active list x samples), never fewer than one per launch index
-static int ensureStreamsForPaths(TwkDevice dev, size_t paths)
+int twk::ensureStreamsForPaths(TwkDevice dev, size_t paths)
 {
   const size_t wantPixels = (size_t) dev->launchWidth * (size_t) dev->state.resolution[1];
   const size_t wantPaths  = std::max(paths, wantPixels);
@@ -170,7 +169,7 @@ static int ensureStreamsForPaths(TwkDevice dev, size_t paths)
   if (dev->momentsEnabled && (rc = growBuffers(dev, dev->momentsPixels, dev->allocatedPixels, {{dev->d_moments, sizeof(float4), true}}))) return rc;
   if (dev->adaptiveEnabled)
   {
-    if (dev->adaptivePixels < dev->allocatedPixels || !dev->d_sampleCounts) { dev->countsCurrent = false; dev->activeValid = false; } // new buffers
+    if (dev->adaptivePixels < dev->allocatedPixels || !dev->d_sampleCounts) { dev->countsCurrent = false; dev->activeValid = false; dev->planValid = false; } // new buffers
     if ((rc = growBuffers(dev, dev->adaptivePixels, dev->allocatedPixels, {{dev->d_sampleCounts, sizeof(unsigned int)}, {dev->d_active, sizeof(unsigned int)}}))) return rc;
   }
   if (dev->geometryEnabled)
@@ -422,6 +421,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
 void twk::dropAdaptive(TwkDevice dev)
 {
   dev->uniformNext = 0; dev->numActive = 0; dev->countsCurrent = false; dev->adaptiveStarted = false; dev->activeValid = false;
+  dev->planValid = false; dev->planActive = 0; dev->planPaths = 0;
 }
 
 // d_sampleCounts as the picture's: after uniform launches only, every launch index is at uniformNext (the buffers are allocated)
@@ -471,6 +471,43 @@ static int renderAdaptivePass(TwkDevice dev, int samples)
   return TWK_SUCCESS;
 }
 
+// Renders the handle's plan (twk_adaptive_plan, own-buffer form) as one wavefront pass of planPaths paths: a sibling of
+// renderAdaptivePass. generatePlannedKernel writes queue 0 (entry-major: entry k owns paths pathOffset[k] .. pathOffset[k + 1] - 1, at
+// the iterations the launch index's own count says), the trace and shade launches are renderPass's non-primary builds on one lane,
+// and accumulatePlannedKernel folds each entry's samples and advances its count by as many. The streams are allocated.
+static int renderPlannedPass(TwkDevice dev)
+{
+  refreshParams(dev);
+  LaunchParams& p = dev->params;
+  p.iterationIndex = 0; // no kernel of this pass reads it: the counts stand in its place
+  p.batchCount = 1;     // nor this: an entry's samples are what its two offsets say
+  p.numPaths = (int) dev->planPaths;
+  p.pathBase = 0;
+  p.queueStride = TWK_QUEUE_STRIDE(p.numPaths);
+  p.packedQueue = (dev->packedQueue && !p.hasCutout && (unsigned int) p.numPaths <= TWK_PACKED_PIXEL_MASK) ? 1 : 0;
+  p.slimSlotBits = slimSlotBits(dev);
+  p.tileEntries = nullptr; p.tilesX = 0;
+  const int maxDepth = dev->state.pathLengths[1];
+  const TraceBuild build = traceBuild(dev, false);
+  const int traceGrid = dev->numCUs * std::max(1, build.blocksPerCU);
+  int shadeGrid = (p.numPaths + TWK_SHADE_BLOCK - 1) / TWK_SHADE_BLOCK;
+  if (shadeGrid > dev->numCUs * TWK_SHADE_BLOCKS_PER_CU) shadeGrid = dev->numCUs * TWK_SHADE_BLOCKS_PER_CU;
+
+  HIP_TRY(hipMemsetAsync(p.counters, 0, sizeof(unsigned int) * TWK_COUNTER_WORDS, dev->stream));
+  timedLaunchBegin(dev, TWK_KERNEL_GENERATE, dev->stream); launchGeneratePlanned(p, dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive, dev->stream); timedLaunchEnd(dev, dev->stream);
+  for (int depth = 0; depth < maxDepth; ++depth)
+  {
+    timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, depth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream);
+    timedLaunchBegin(dev, TWK_KERNEL_SHADE, dev->stream); const int b = launchShade(p, depth, false, shadeGrid, dev->stream); dev->shadeBuilds[b >> 6] |= 1ull << (b & 63); timedLaunchEnd(dev, dev->stream);
+  }
+  if (maxDepth > 0) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, maxDepth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream); } // the shadow rays of the last shade
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulatePlanned(p, halfOutput(dev), dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive, dev->stream); timedLaunchEnd(dev, dev->stream);
+  HIP_TRY(hipGetLastError());
+  dev->lastPassCount = 0; // the radiance stream holds a planned pass's paths, not a uniform pass's
+  dev->adaptiveStarted = true;
+  return TWK_SUCCESS;
+}
+
 // =============================================================================================
 extern "C" {
 
@@ -492,7 +529,7 @@ try
   if (iterationIndex == 0) dev->adaptiveStarted = false;
   else if (dev->adaptiveStarted)
     return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch: the picture holds adaptive samples (twk_launch_adaptive), its pixels are at different iterations: restart at iteration 0, or go on with twk_launch_adaptive");
-  dev->activeValid = false; dev->countsCurrent = false; // the active list was selected from the picture before this launch
+  dev->activeValid = false; dev->planValid = false; dev->countsCurrent = false; // the active list and the plan were made from the picture before this launch
 
   // Asynchronous like optixLaunch: the iteration is recorded; consecutive iterations are rendered together (up to
   // batchMax samples per pixel per wavefront pass). Results are identical to one pass per iteration.
@@ -526,6 +563,25 @@ try
   return renderAdaptivePass(dev, samples);
 }
 TWK_CATCH("twk_launch_adaptive")
+
+int twk_launch_adaptive_planned(TwkDevice dev)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_launch_adaptive_planned: NULL device handle");
+  int rc = activate(dev, "twk_launch_adaptive_planned"); if (rc) return rc;
+  if (!dev->adaptiveEnabled || !dev->momentsEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: twk_enable_moments(1), twk_enable_adaptive(1) and twk_set_state first");
+  if (!dev->built || dev->cameras.empty() || dev->materials.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: twk_build, cameras and materials are required");
+  if (dev->timeView || dev->captureFirstHits || dev->statsEnabled) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: not with the time view, first-hit capture or statistics on (diagnostic builds of the uniform pass)");
+  if (dev->d_outputExternal && dev->outputFrame) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: not with a shared frame (twk_set_shared_frame)");
+  if (!dev->planValid || !dev->countsCurrent || !dev->d_planActive || !dev->d_planOffsets || !dev->d_sampleCounts)
+    return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: no plan: twk_adaptive_plan on the handle's own buffers first (a plan is rendered once; a twk_launch, a twk_adaptive_select, or a change of state, scene, resolution or format, drops it)");
+  if (dev->planActive == 0) return TWK_SUCCESS; // nothing advances: the empty plan stays the picture's plan
+  if ((rc = ensureStreamsForPaths(dev, (size_t) dev->planPaths))) return rc;
+  if (!dev->planValid || !dev->d_moments) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: the handle's buffers were allocated anew: twk_adaptive_plan first");
+  dev->planValid = false; // the counts advance in the pass: the offsets no longer say what the picture needs
+  return renderPlannedPass(dev);
+}
+TWK_CATCH("twk_launch_adaptive_planned")
 
 int twk_set_launch_batch(TwkDevice dev, int iterations)
 try

@@ -166,6 +166,14 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 1) adaptiveMaxSamples = i[0];
       else if (ok) warnings.push_back("adaptiveMaxSamples must be >= 1, keeping the previous value");
     }
+    // the planned adaptive pass (twk_adaptive_plan / twk_launch_adaptive_planned, read by twk_app_get_adaptive_plan)
+    else if (key == "adaptiveBudget")      { ok = readInt(parser, i[0]); if (ok) adaptiveBudget = (i[0] == 1) ? 1 : 0; }
+    else if (key == "adaptiveMinBatch" || key == "adaptiveMaxBatch")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 1 && i[0] <= 64) (key == "adaptiveMinBatch" ? adaptiveMinBatch : adaptiveMaxBatch) = i[0];
+      else if (ok) warnings.push_back(key + " must be in 1..64, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -189,6 +197,12 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
   {
     adaptiveSampling = 0;
     warnings.push_back("adaptiveSampling needs a targetNoise to select by, dropping it");
+  }
+
+  if (adaptiveMinBatch > adaptiveMaxBatch) // in whichever order the two keys came
+  {
+    adaptiveMinBatch = TWK_DENOISER_MIN_SAMPLES; adaptiveMaxBatch = 64;
+    warnings.push_back("adaptiveMinBatch must not exceed adaptiveMaxBatch, dropping both");
   }
 
   camera.setResolution(resolution[0], resolution[1]); // Application.cpp:207
@@ -234,6 +248,9 @@ std::string Application::systemDescription() const
   if (targetNoiseInterval != 16) d << "targetNoiseInterval " << targetNoiseInterval << std::endl;
   if (adaptiveSampling != 0) d << "adaptiveSampling " << adaptiveSampling << std::endl;
   if (adaptiveMaxSamples != (int) TWK_ADAPTIVE_MAX_SAMPLES) d << "adaptiveMaxSamples " << adaptiveMaxSamples << std::endl;
+  if (adaptiveBudget != 0) d << "adaptiveBudget " << adaptiveBudget << std::endl;
+  if (adaptiveMinBatch != TWK_DENOISER_MIN_SAMPLES) d << "adaptiveMinBatch " << adaptiveMinBatch << std::endl;
+  if (adaptiveMaxBatch != 64) d << "adaptiveMaxBatch " << adaptiveMaxBatch << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

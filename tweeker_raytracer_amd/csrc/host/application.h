@@ -108,6 +108,12 @@ public:
   // by "targetNoise"; dropped without a target), "adaptiveMaxSamples" (no pixel is selected once it has this many samples)
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
+  // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel
+  // at the samples its own estimate predicts; in effect only with adaptive sampling itself), "adaptiveMinBatch", "adaptiveMaxBatch"
+  // (1 <= min <= max <= 64; the provisional defaults of twk_adaptive_plan_defaults)
+  int   adaptiveBudget = 0;
+  int   adaptiveMinBatch = TWK_DENOISER_MIN_SAMPLES;
+  int   adaptiveMaxBatch = 64;
   int   shaderVariant = 0; // grammar extension "shaderVariant": 0 rtigo3, 1 Optix7Gui light-hit rule (include/tweeker_hip.h TWK_SHADERS_*)
   int   samplesSqrt   = 1;
   int   resolution[2] = {1, 1};

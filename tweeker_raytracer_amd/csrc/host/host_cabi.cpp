@@ -162,6 +162,18 @@ try
 }
 TWK_CATCH("twk_app_get_adaptive")
 
+int twk_app_get_adaptive_plan(TwkApp app, int* enabled, TwkAdaptivePlan* plan)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_adaptive_plan: NULL app");
+  if (!enabled || !plan) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_adaptive_plan: NULL argument");
+  const Application& a = app->app;
+  *enabled = (a.adaptiveBudget != 0 && a.adaptiveSampling != 0 && a.targetNoise > 0.0f) ? 1 : 0; // only where adaptive sampling itself is on
+  plan->minBatch = (uint32_t) a.adaptiveMinBatch; plan->maxBatch = (uint32_t) a.adaptiveMaxBatch;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_adaptive_plan")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {

@@ -7,8 +7,9 @@
 // "targetNoiseQuantile" quantile of the relative standard error is at most e; a second line prints the final mean and quantile.
 // With "adaptiveSampling 1" beside it the loop renders uniformly up to the first check only; from then on every device selects the
 // pixels above the target (twk_adaptive_select) and renders "targetNoiseInterval" more samples of those alone
-// (twk_launch_adaptive) between two checks. It ends when the target is met, when no device selects anything, or when the samples
-// spent reach the uniform budget, samplesSqrt² x the pixel count; the second line gains the samples per pixel and the active share.
+// (twk_launch_adaptive) between two checks; with "adaptiveBudget 1" too, each interval is instead one plan (twk_adaptive_plan) and
+// one planned pass (twk_launch_adaptive_planned) that gives every selected pixel the samples its own estimate predicts. It ends
+// when the target is met, when no device selects anything, or when the samples spent reach the uniform budget, samplesSqrt² x the pixel count; the second line gains the samples per pixel and the active share.
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -168,6 +169,10 @@ int main(int argc, char* argv[])
     return 1;
   }
 
+  int planEnabled = 0; // "adaptiveBudget 1": each interval is one plan + one planned pass, every pixel at the samples its estimate predicts
+  TwkAdaptivePlan adaptivePlan;
+  TWK_OK(twk_app_get_adaptive_plan(app, &planEnabled, &adaptivePlan));
+
   std::vector<TwkDevice> devices((size_t) count, nullptr);
   TwkDeviceState state;
   TWK_OK(twk_app_get_state(app, &state));
@@ -276,6 +281,35 @@ int main(int argc, char* argv[])
     std::vector<unsigned int> numActive((size_t) count, 0u);
     for (;;)
     {
+      if (planEnabled)
+      {
+        // every device plans its own packed tile buffer (the padding is empty: budget 0); when the plans together ask for more than
+        // the budget has left, every selected pixel gets the same share of what is left instead, as in the fixed loop below
+        TwkAdaptivePlan plan = adaptivePlan;
+        unsigned long long paths = 0;
+        for (int attempt = 0; attempt < 2; ++attempt)
+        {
+          lastActive = 0; paths = 0;
+          for (int i = 0; i < count; ++i)
+          {
+            unsigned long long numPaths = 0;
+            TWK_OK(twk_adaptive_plan(devices[(size_t) i], &adaptive, &plan, nullptr, nullptr, 0, nullptr, nullptr, &numActive[(size_t) i], &numPaths));
+            lastActive += numActive[(size_t) i]; paths += numPaths;
+          }
+          if (lastActive == 0 || paths <= budget - spent) break;
+          const unsigned long long share = std::min<unsigned long long>((budget - spent) / lastActive, (unsigned long long) adaptivePlan.maxBatch);
+          if (share == 0) { paths = 0; break; }
+          plan.minBatch = plan.maxBatch = (uint32_t) share;
+        }
+        if (lastActive == 0) { adaptiveEnd = "nothing selected"; break; }
+        if (paths == 0 || paths > budget - spent) { adaptiveEnd = "budget spent"; break; }
+        for (int i = 0; i < count; ++i) TWK_OK(twk_launch_adaptive_planned(devices[(size_t) i]));
+        spent += paths;
+        bool met = false;
+        if (checkNoise(met)) return 1;
+        if (met) break;
+        continue;
+      }
       lastActive = 0;
       for (int i = 0; i < count; ++i)
       {

@@ -1012,6 +1012,23 @@ TWK_D void generateActivePath(const LaunchParams& p, const unsigned int* active,
   storePrimaryPath(p, index, primaryRayAt(p, launchIndex, counts[launchIndex], sampleIndex));
 }
 
+// Body of generatePlannedKernel for path `index` of a planned adaptive pass (twk_launch_adaptive_planned). The paths are entry-major:
+// entry k of the plan's list owns paths pathOffset[k] .. pathOffset[k + 1] - 1 (adaptive_plan_device.h). The entry of a path is the
+// last k with pathOffset[k] <= index: an upper-bound binary search over the numActive + 1 ascending words (at most 22 dependent
+// reads of an array that stays in L2; entries have a budget of at least 1, so the offsets are strictly ascending). Its sample
+// index - pathOffset[k] runs at the iteration the launch index's own sample count says, as in generateActivePath.
+TWK_D void generatePlannedPath(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, const unsigned int numActive, const unsigned int index)
+{
+  unsigned int low = 0u, high = numActive; // pathOffset[low] <= index < pathOffset[high]
+  while (high - low > 1u)
+  {
+    const unsigned int middle = low + ((high - low) >> 1);
+    if (pathOffset[middle] <= index) low = middle; else high = middle;
+  }
+  const unsigned int launchIndex = active[low];
+  storePrimaryPath(p, index, primaryRayAt(p, launchIndex, counts[launchIndex], index - pathOffset[low]));
+}
+
 // Where launch index `index` accumulates: its slot of the packed tile buffer (single device, LocalCopy), or — shared frame of
 // the ZeroCopy / PeerAccess strategies — the pixel it maps to, as __raygen__path_tracer addresses sysData.outputBuffer
 // (raygeneration.cu:175-183,229): index = y * W + distribute(launch index). False: the launch index has no pixel there.
@@ -1118,6 +1135,20 @@ TWK_D bool foldActiveSamples(const LaunchParams& p, const unsigned int k, const 
   for (int s = 0; s < samples; ++s)
   {
     if (foldSample<true>(p, (size_t) s * numActive + k, count + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
+  }
+  return touched;
+}
+
+// The samples of a planned adaptive pass (twk_launch_adaptive_planned) for an entry whose paths start at `firstPath`: sample s of
+// its `samples` is path firstPath + s, at iteration count + s, where count is the launch index's own sample count before the pass.
+template<typename Stored>
+TWK_D bool foldPlannedSamples(const LaunchParams& p, const unsigned int firstPath, const unsigned int count, const unsigned int samples,
+                              float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments)
+{
+  bool touched = false;
+  for (unsigned int s = 0; s < samples; ++s)
+  {
+    if (foldSample<true>(p, (size_t) firstPath + s, count + s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
   }
   return touched;
 }

@@ -42,6 +42,18 @@ __global__ void __launch_bounds__(256) generateActiveKernel(LaunchParams p, cons
   generateActivePath(p, active, counts, numActive, index);
 }
 
+// generateKernel of a planned adaptive pass (twk_launch_adaptive_planned): one thread per path. The paths are entry-major (entry k of
+// the plan owns paths pathOffset[k] .. pathOffset[k + 1] - 1), so a wave's 64 paths are a few neighbouring launch indices at
+// consecutive iterations; the entry is found by a binary search of pathOffset (shade_device.h generatePlannedPath). Queue 0 is
+// written exactly as generateKernel writes it.
+__global__ void __launch_bounds__(256) generatePlannedKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ pathOffset,
+                                                             const unsigned int* __restrict__ counts, unsigned int numActive)
+{
+  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
+  if (index >= (unsigned int) p.numPaths) return;
+  generatePlannedPath(p, active, pathOffset, counts, numActive, index);
+}
+
 // ---------------------------------------------------------------------------------------------
 // One thread per ray of queue (depth & 1): shadePath(), then append the continuation ray — with the path's throughput,
 // pdf, RNG state and flags, which travel in the queue next to the ray so that every access of a bounce is a coalesced
@@ -555,6 +567,52 @@ __global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, co
   }
 }
 
+// The accumulate kernel of a planned adaptive pass: one thread per entry k of the plan folds the pathOffset[k + 1] - pathOffset[k]
+// samples of launch index active[k] (paths pathOffset[k] + s) onto its running means and moments with the fold of the kernels above,
+// sample s at iteration counts[active[k]] + s, and advances the launch index's sample count by as many. HALF: the RGBA16F buffers.
+template<bool HALF>
+__global__ void __launch_bounds__(256) accumulatePlannedKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ pathOffset,
+                                                               unsigned int* __restrict__ counts, unsigned int numActive)
+{
+  const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= numActive) return;
+  const unsigned int index = active[k];
+  const unsigned int firstPath = pathOffset[k], samples = pathOffset[k + 1] - firstPath;
+  const unsigned int count = counts[index];
+  counts[index] = count + samples;
+  size_t outIndex;
+  if (!accumulateTarget(p, index, outIndex)) return;
+  const bool aov = (p.aovAlbedo != nullptr);
+  float4 moments = p.moments[index];
+  if (HALF)
+  {
+    Half4* output = reinterpret_cast<Half4*>(p.output);
+    Half4* aovAlbedo = reinterpret_cast<Half4*>(p.aovAlbedo);
+    Half4* aovNormal = reinterpret_cast<Half4*>(p.aovNormal);
+    float4 dst = widen(output[outIndex]);
+    float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (foldPlannedSamples(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments))
+    {
+      output[outIndex] = narrow(dst);
+      if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
+      p.moments[index] = moments;
+    }
+  }
+  else
+  {
+    float4 dst = p.output[outIndex];
+    float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (foldPlannedSamples(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments))
+    {
+      p.output[outIndex] = dst;
+      if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
+      p.moments[index] = moments;
+    }
+  }
+}
+
 // compositor.cu:38-64 for every source device in one launch: tiles is [deviceCount][H][launchWidth]. Pixel: float4 or Half4
 // (a plain 8-byte copy).
 template<typename Pixel>
@@ -701,6 +759,18 @@ void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int
   const dim3 grid((numActive + 255u) / 256u);
   if (half) hipLaunchKernelGGL(accumulateActiveKernel<true>, grid, dim3(256), 0, stream, p, active, counts, numActive, samples);
   else      hipLaunchKernelGGL(accumulateActiveKernel<false>, grid, dim3(256), 0, stream, p, active, counts, numActive, samples);
+}
+
+void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, unsigned int numActive, hipStream_t stream)
+{
+  hipLaunchKernelGGL(generatePlannedKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
+}
+
+void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, hipStream_t stream)
+{
+  const dim3 grid((numActive + 255u) / 256u);
+  if (half) hipLaunchKernelGGL(accumulatePlannedKernel<true>, grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
+  else      hipLaunchKernelGGL(accumulatePlannedKernel<false>, grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
 }
 
 template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>

@@ -453,6 +453,32 @@ class Device:
             L.check(L.lib.twk_read_active(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(out.size), C.byref(n)))
         return out
 
+    def adaptivePlan(self, ap=None, plan=None, moments=None, counts=None, numElements=0, activeOut=None, pathOffsetOut=None):
+        """twk_adaptive_plan: the elements adaptiveSelect would choose for `ap`, each with the samples its noise estimate predicts
+        (plan: L.AdaptivePlan; None = the defaults); returns (numActive, numPaths) and synchronises. Without buffers the handle's
+        own moments and counts and a plan of its own, which renderPlanned renders and readPlan reads; otherwise device pointers to
+        numElements float4, numElements uint32 and, for the outputs, numElements and numElements + 1 uint32."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        n, paths = C.c_uint(0), C.c_ulonglong(0)
+        L.check(L.lib.twk_adaptive_plan(self._h, None if ap is None else C.byref(ap), None if plan is None else C.byref(plan), ptr(moments), ptr(counts),
+                                        C.c_size_t(int(numElements)), ptr(activeOut), ptr(pathOffsetOut), C.byref(n), C.byref(paths)))
+        return n.value, paths.value
+
+    def renderPlanned(self):
+        """twk_launch_adaptive_planned: the handle's plan as one wavefront pass, every entry at the iterations its own count says;
+        asynchronous. A plan is rendered once: without a new adaptivePlan a second call is refused."""
+        L.check(L.lib.twk_launch_adaptive_planned(self._h))
+
+    def readPlan(self):
+        """(active uint32 [numActive], pathOffset uint32 [numActive + 1]) of the last adaptivePlan on the handle's own buffers: entry
+        k owns paths pathOffset[k] .. pathOffset[k + 1] - 1, pathOffset[-1] = numPaths."""
+        n, paths = C.c_uint(0), C.c_ulonglong(0)
+        L.check(L.lib.twk_read_plan(self._h, None, None, C.c_size_t(0), C.byref(n), C.byref(paths)))
+        active, offsets = np.empty(n.value, dtype=np.uint32), np.empty(n.value + 1, dtype=np.uint32)
+        L.check(L.lib.twk_read_plan(self._h, active.ctypes.data_as(C.POINTER(C.c_uint32)), offsets.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(active.size),
+                                    C.byref(n), C.byref(paths)))
+        return active, offsets
+
     def statsEnable(self, enable=True):
         L.check(L.lib.twk_stats_enable(self._h, int(bool(enable))))
 

@@ -678,6 +678,62 @@ int twk_launch_adaptive_planned(TwkDevice dev);
  * length, one buffer without the other. TWK_ERROR_INVALID_STATE: no valid plan (none made, dropped, or already rendered). */
 int twk_read_plan(TwkDevice dev, uint32_t* active, uint32_t* pathOffset, size_t capacity, unsigned int* numActive, unsigned long long* numPaths);
 
+/* ---- The firefly cascade — new calls, ABI stays 9, no existing struct changes; with the switch at its default no kernel and no bit
+ * of any picture, AOV, moments word or list changes ------------------------------------------------------------------------------
+ * A firefly-robust estimate in front of the denoiser: the cascaded framebuffer of Zirr, Hanika and Dachsbacher, "Re-weighting
+ * firefly samples for improved finite-sample Monte Carlo estimates" (CGF 2018). The accumulate kernels split every kept sample by
+ * its luminance over `layers` brightness layers with thresholds start, start base, start base^2, ... (per-layer sums, K float4 per
+ * launch index, layer-major [K][launchWidth x height], always f32; layer 0 .w = n, layer K-1 .w = samples rejected as not finite);
+ * twk_cascade_resolve then counts a layer only as far as enough samples landed in it, in the pixel and its eight neighbours:
+ * out = (layer 0 + sum_j w_j layer j) / n, w_j = min(1, c_j / kappa). With more samples every weight goes to 1 and the picture is
+ * the plain mean. The complete definition is csrc/cascade_device.h; tests/cascade_restate.py restates it in numpy. What it is NOT:
+ * learned, temporal, reprojected by twk_temporal_accumulate, colour-aware (the reliability is of the luminance), or unbiased at
+ * finite n (the clamp above the top layer and every w_j < 1 remove energy); of the paper it leaves out the local/global mixing and
+ * the variance term. The running mean, the AOVs, the moments, the noise estimate and the adaptive passes do not see it. */
+typedef struct TwkCascade { int layers; float start; float base; } TwkCascade;
+typedef struct TwkCascadeResolve { float kappa; } TwkCascadeResolve;
+#define TWK_CASCADE_LAYERS 6
+#define TWK_CASCADE_START 1.0f
+#define TWK_CASCADE_BASE 8.0f
+#define TWK_CASCADE_KAPPA 32.0f /* PROVISIONAL: chosen by the sweep in profiles/r15_cascade.md, at the upper edge of its range */
+int twk_cascade_defaults(TwkCascade* cp);                /* layers 6, start 1, base 8 */
+int twk_cascade_resolve_defaults(TwkCascadeResolve* rp); /* kappa TWK_CASCADE_KAPPA (provisional) */
+/* (1) turns the CASCADE builds of the accumulate kernels on and allocates the layers, zeroed (with twk_set_state, whichever comes
+ * later); cp NULL: the defaults. (0) frees them (cp is ignored). The layers are zeroed wherever the moments are (a new allocation),
+ * when the number of launch indices changes, and by a change of parameters while enabled; the same parameters again change nothing.
+ * A kept sample of iteration 0 starts its launch index afresh. Needs neither the moments nor adaptive sampling; adaptive passes
+ * fold into the layers like uniform ones. TWK_ERROR_INVALID_VALUE: a NULL handle, layers outside 2..8, a start that is not > 0 and
+ * finite, a base that is not > 1 and finite, thresholds that reach inf. */
+int twk_enable_cascade(TwkDevice dev, int enable, const TwkCascade* cp);
+/* The layers, [layers][launchWidth*height] float4; recorded launches are rendered first; the read synchronises.
+ * TWK_ERROR_INVALID_STATE without twk_enable_cascade(1) and twk_set_state. */
+int twk_read_cascade(TwkDevice dev, float* host, size_t numFloats); /* numFloats = layers*launchWidth*height*4 */
+int twk_get_cascade_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+/* Resolves; asynchronous on the handle's stream, never writes its input. cp, rp NULL: the defaults. Own-buffer form (layers NULL,
+ * width and height 0, resolved NULL): the handle's layers, which cp must describe (NULL: the parameters they were enabled with),
+ * into the handle's internal resolved buffer in the output format (twk_get_resolved_device_pointer, twk_read_resolved); recorded
+ * launches are rendered first. TWK_ERROR_INVALID_STATE without
+ * twk_enable_cascade(1) and twk_set_state, and on a packed tile buffer (distribution 1 with several devices: the 3x3 window would
+ * cross tile borders — assemble every layer with twk_compositor and use the explicit form). Explicit form: `layers` a device buffer
+ * of [cp->layers][width*height] float4, `resolved` a device buffer of width*height pixels of the handle's output format that does
+ * not overlap it. TWK_ERROR_INVALID_VALUE: a NULL handle (before any HIP call), the parameter refusals of twk_enable_cascade, a
+ * kappa that is not > 0 and finite, an overlap, layers without a size or a resolved buffer, a size without layers, cp that
+ * differs from the handle's own parameters in the own-buffer form, width*height above 2^28. */
+int twk_cascade_resolve(TwkDevice dev, const TwkCascade* cp, const TwkCascadeResolve* rp, const void* layers, int width, int height, void* resolved);
+/* The internal resolved picture of the last own-buffer twk_cascade_resolve: launchWidth*height pixels of the output format. The
+ * pointer feeds twk_tonemap, twk_tonemap_half and the explicit `beauty` of the three twk_denoise* calls unchanged.
+ * twk_read_resolved: RGBA32F, an RGBA16F picture widened exactly; synchronises. TWK_ERROR_INVALID_STATE before such a resolve. */
+int twk_get_resolved_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+int twk_read_resolved(TwkDevice dev, float* rgbaHost, size_t numFloats);
+/* Host only, no handle: the same definition over host arrays. Fold: `samples` is [numSamples][numElements] x 4 floats (radiance rgb,
+ * w == 0: the element has no sample there, as twk_debug_read_path_radiance gives them), sample s at iteration firstIteration + s;
+ * a sample with a NaN component is dropped unless debugExceptions, which folds the false colours of twk_set_debug_exceptions; layers
+ * is [cp->layers][numElements] x 4 floats, read and written. Resolve: layers as above with numElements = width*height; resolved
+ * receives width*height x 4 floats, NOT narrowed. TWK_ERROR_INVALID_VALUE: a NULL array, the parameter refusals above. */
+int twk_cascade_fold_host(const TwkCascade* cp, const float* samples, size_t numSamples, size_t numElements, unsigned int firstIteration,
+                          int debugExceptions, float* layers);
+int twk_cascade_resolve_host(const TwkCascade* cp, const TwkCascadeResolve* rp, const float* layers, int width, int height, float* resolved);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);
@@ -812,6 +868,12 @@ int twk_app_get_adaptive(TwkApp app, int* enabled, TwkAdaptive* ap);
  * breaks 1 <= adaptiveMinBatch <= adaptiveMaxBatch <= 64 drops the line with a warning). *enabled = the key is on AND adaptive
  * sampling itself is enabled (twk_app_get_adaptive); rtigo3_hip -m 1 then runs the planned loop (INTEGRATION.md "The adaptive loop"). */
 int twk_app_get_adaptive_plan(TwkApp app, int* enabled, TwkAdaptivePlan* plan);
+/* "fireflyCascade 0|1" (default 0), "fireflyCascadeLayers n", "fireflyCascadeStart s", "fireflyCascadeBase b", "fireflyCascadeKappa k"
+ * (defaults: twk_cascade_defaults, twk_cascade_resolve_defaults; a value twk_enable_cascade or twk_cascade_resolve would refuse
+ * drops the line with a warning, thresholds that reach inf drop layers, start and base together). The keys are written back only
+ * when they differ from off / the defaults. twk_app_init_device enables the cascade when the key is on; the render loop resolves
+ * (INTEGRATION.md "The firefly cascade"). */
+int twk_app_get_cascade(TwkApp app, int* enabled, TwkCascade* cp, TwkCascadeResolve* rp);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

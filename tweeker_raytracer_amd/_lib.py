@@ -30,6 +30,8 @@ TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_vari
 TWK_TEMPORAL_MAX_HISTORY, TWK_TEMPORAL_POSITION_TOLERANCE = 32, 0.01  # twk_temporal_defaults (include/tweeker_hip.h)
 TWK_NOISE_DARK_FLOOR = 0.01  # twk_noise_defaults (include/tweeker_hip.h); its minSamples is TWK_DENOISER_MIN_SAMPLES
 TWK_ADAPTIVE_TARGET_NOISE, TWK_ADAPTIVE_MAX_SAMPLES = 0.05, 4096  # twk_adaptive_defaults (include/tweeker_hip.h)
+TWK_CASCADE_LAYERS, TWK_CASCADE_START, TWK_CASCADE_BASE = 6, 1.0, 8.0  # twk_cascade_defaults (include/tweeker_hip.h)
+TWK_CASCADE_KAPPA = 32.0  # twk_cascade_resolve_defaults (provisional: profiles/r15_cascade.md)
 
 f3 = C.c_float * 3
 f2 = C.c_float * 2
@@ -143,6 +145,24 @@ class AdaptivePlan(C.Structure):
         super().__init__(int(minBatch), int(maxBatch))
 
 
+class Cascade(C.Structure):
+    """≙ TwkCascade: the firefly cascade's layers (2..8) and their thresholds start, start base, start base^2, ... (start > 0,
+    base > 1). Without arguments: twk_cascade_defaults."""
+    _fields_ = [("layers", C.c_int), ("start", C.c_float), ("base", C.c_float)]
+
+    def __init__(self, layers=TWK_CASCADE_LAYERS, start=TWK_CASCADE_START, base=TWK_CASCADE_BASE):
+        super().__init__(int(layers), start, base)
+
+
+class CascadeResolve(C.Structure):
+    """≙ TwkCascadeResolve: kappa (> 0), the sample count at which a layer is fully trusted. Without arguments:
+    twk_cascade_resolve_defaults (provisional)."""
+    _fields_ = [("kappa", C.c_float)]
+
+    def __init__(self, kappa=TWK_CASCADE_KAPPA):
+        super().__init__(kappa)
+
+
 class NoiseSummary(C.Structure):
     """≙ TwkNoiseSummary: what twk_estimate_noise reduces a stream of luminance moments to (csrc/noise_device.h). valid / unknown /
     empty count the elements; the rest describes e, the relative standard error of the luminance mean, over the valid ones."""
@@ -231,6 +251,8 @@ SYMBOLS = [
     "twk_enable_adaptive", "twk_adaptive_defaults", "twk_adaptive_select", "twk_adaptive_select_host", "twk_launch_adaptive", "twk_read_sample_counts",
     "twk_get_sample_counts_device_pointer", "twk_read_active", "twk_app_get_adaptive",
     "twk_adaptive_plan_defaults", "twk_adaptive_plan", "twk_adaptive_plan_host", "twk_launch_adaptive_planned", "twk_read_plan", "twk_app_get_adaptive_plan",
+    "twk_cascade_defaults", "twk_cascade_resolve_defaults", "twk_enable_cascade", "twk_read_cascade", "twk_get_cascade_device_pointer", "twk_cascade_resolve",
+    "twk_get_resolved_device_pointer", "twk_read_resolved", "twk_cascade_fold_host", "twk_cascade_resolve_host", "twk_app_get_cascade",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

@@ -149,6 +149,15 @@ class Application:
         return bool(on.value), plan
 
     @property
+    def fireflyCascade(self):
+        """(enabled, Cascade, CascadeResolve) from "fireflyCascade", "fireflyCascadeLayers", "fireflyCascadeStart",
+        "fireflyCascadeBase", "fireflyCascadeKappa" of the system description; initDevice enables the device's cascade when the key
+        is on, and a render loop calls Device.cascadeResolve before it shows or denoises the picture."""
+        on, cp, rp = C.c_int(0), L.Cascade(), L.CascadeResolve()
+        L.check(L.lib.twk_app_get_cascade(self._h, C.byref(on), C.byref(cp), C.byref(rp)))
+        return bool(on.value), cp, rp
+
+    @property
     def tonemapper(self):
         """Tonemapper settings of the system description (Application.cpp:1244-1292)."""
         tm = L.Tonemapper()
@@ -171,6 +180,9 @@ class Application:
     def initDevice(self, device, distribution=None):
         """≙ Application.cpp:303,328-332: initState, initCameras, initLights, initMaterials, initScene."""
         L.check(L.lib.twk_app_init_device(self._h, device.handle))
+        on, cascade, _ = self.fireflyCascade
+        if on:
+            device._cascadeLayers = cascade.layers  # the shape Device.readCascade returns
         st = self.state
         if distribution is not None:
             st.distribution = int(distribution)

@@ -239,6 +239,7 @@ try
   freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
   freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); freeDevice(dev->d_moments);
   freeDevice(dev->d_geometry); dropTemporal(dev);
+  freeDevice(dev->d_cascade); freeDevice(dev->d_cascadeLambda); freeDevice(dev->d_resolved);
   freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams); freeDevice(dev->d_noise);
   freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); freeDevice(dev->d_adaptiveScratch); freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets);
   dev->builder.release();

@@ -1,6 +1,6 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
-// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
@@ -9,6 +9,7 @@
 #include "noise_device.h"
 #include "adaptive_device.h"
 #include "adaptive_plan_device.h"
+#include "cascade_device.h"
 #include "error_state.h"
 
 #include <string>
@@ -21,7 +22,7 @@ void launchGenerate(const LaunchParams& p, hipStream_t stream);
 int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
 void shadeBuildSlots(uint64_t mask[2]);
 void launchTileEntries(const LaunchParams& p, const float4* topTable, int tilesX, int tilesY, int4* out, hipStream_t stream);
-void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream);
+void launchAccumulate(const LaunchParams& p, bool half, const CascadeOn& cascade, hipStream_t stream);
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
                       int tileSizeX, int tileShiftX, int tileShiftY, hipStream_t stream);
 void launchMathTap(int op, const float* x, const float* y, float* out, size_t n, hipStream_t stream);
@@ -38,14 +39,15 @@ void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hip
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
 void launchGenerateActive(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, unsigned int numActive, hipStream_t stream);
-void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, hipStream_t stream);
+void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, const CascadeOn& cascade, hipStream_t stream);
 unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
                                    const AdaptiveConstants& k, int numCUs, hipStream_t stream);
 void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, unsigned int numActive, hipStream_t stream);
-void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, hipStream_t stream);
+void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, const CascadeOn& cascade, hipStream_t stream);
 unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, unsigned int* pathOffset,
                                        void* scratch, const AdaptiveConstants& k, const AdaptivePlanConstants& plan, int numCUs, hipStream_t stream);
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
+void launchCascadeResolve(const CascadeConstants& k, float kappa, const float4* layers, float* lambda, int width, int height, void* resolved, bool half, hipStream_t stream);
 }
 
 using namespace twk;
@@ -156,6 +158,13 @@ struct TwkDevice_t
   // twk_enable_moments: luminance moments (mean, M2, n, 0) of the samples per launch index, always f32 (LaunchParams::moments)
   bool momentsEnabled = false; float4* d_moments = nullptr; int momentsPixels = 0;
   unsigned int sampleOffset = 0; // twk_set_sample_offset (LaunchParams::sampleOffset)
+  // twk_enable_cascade: the firefly cascade's layers, [cascade.layers][cascadePixels] float4 with cascadePixels = launchWidth x height
+  // exactly (the layer stride), always f32; the resolve's lambda stream (cascadeLambdaElements floats, shared by both forms) and the
+  // internal resolved picture of the own-buffer form in the output format it was resolved in
+  bool cascadeEnabled = false; TwkCascade cascadeParameters = {TWK_CASCADE_LAYERS, TWK_CASCADE_START, TWK_CASCADE_BASE}; CascadeConstants cascadeK = {};
+  float4* d_cascade = nullptr; int cascadePixels = 0;
+  float* d_cascadeLambda = nullptr; size_t cascadeLambdaElements = 0;
+  void* d_resolved = nullptr; int resolvedWidth = 0, resolvedHeight = 0, resolvedFormat = TWK_OUTPUT_FLOAT4; bool resolvedValid = false;
   // twk_enable_geometry: the geometry AOV (world position, instance + 1) per launch index, always f32; geometryValid: rendered by
   // twk_render_geometry since the last change of camera, state or scene
   bool geometryEnabled = false; float4* d_geometry = nullptr; int geometryPixels = 0; bool geometryValid = false;
@@ -258,4 +267,6 @@ int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int ena
 int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);
 // device_post.hip
 void dropTemporal(TwkDevice dev);
+// device_cascade.hip
+CascadeOn cascadeFold(TwkDevice dev);
 }

@@ -167,6 +167,12 @@ int twk::ensureStreamsForPaths(TwkDevice dev, size_t paths)
     if ((rc = growBuffers(dev, dev->aovPixels, dev->allocatedPixels, {{dev->d_aovAlbedo, pixelBytes(dev), true}, {dev->d_aovNormal, pixelBytes(dev), true}}))) return rc;
   }
   if (dev->momentsEnabled && (rc = growBuffers(dev, dev->momentsPixels, dev->allocatedPixels, {{dev->d_moments, sizeof(float4), true}}))) return rc;
+  if (dev->cascadeEnabled)
+  {
+    // layer-major with the launch indices as the stride: a buffer of exactly launchWidth x height elements per layer, allocated anew (zeroed) when that number changes
+    if (dev->cascadePixels != numPixels) { freeDevice(dev->d_cascade); dev->cascadePixels = 0; dev->resolvedValid = false; }
+    if ((rc = growBuffers(dev, dev->cascadePixels, numPixels, {{dev->d_cascade, (size_t) dev->cascadeK.layers * sizeof(float4), true}}))) return rc;
+  }
   if (dev->adaptiveEnabled)
   {
     if (dev->adaptivePixels < dev->allocatedPixels || !dev->d_sampleCounts) { dev->countsCurrent = false; dev->activeValid = false; dev->planValid = false; } // new buffers
@@ -410,7 +416,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
     HIP_TRY(hipStreamWaitEvent(dev->stream, dev->laneDone[lane], 0));
   }
   // the running mean folds the samples of the pass in iteration order over ALL lanes' paths: after the join, on the handle's stream
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
   dev->lastPassCount = count; dev->lastPassPixels = p.numPixels;
   dev->uniformNext = firstIteration + (unsigned int) count; dev->countsCurrent = false; // (twk_launch has dropped the active list)
@@ -464,7 +470,7 @@ static int renderAdaptivePass(TwkDevice dev, int samples)
     timedLaunchBegin(dev, TWK_KERNEL_SHADE, dev->stream); const int b = launchShade(p, depth, false, shadeGrid, dev->stream); dev->shadeBuilds[b >> 6] |= 1ull << (b & 63); timedLaunchEnd(dev, dev->stream);
   }
   if (maxDepth > 0) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, maxDepth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream); } // the shadow rays of the last shade
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulateActive(p, halfOutput(dev), dev->d_active, dev->d_sampleCounts, dev->numActive, samples, dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulateActive(p, halfOutput(dev), dev->d_active, dev->d_sampleCounts, dev->numActive, samples, cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
   dev->lastPassCount = 0; // the radiance stream holds an adaptive pass's paths, not a uniform pass's
   dev->adaptiveStarted = true;
@@ -501,7 +507,7 @@ static int renderPlannedPass(TwkDevice dev)
     timedLaunchBegin(dev, TWK_KERNEL_SHADE, dev->stream); const int b = launchShade(p, depth, false, shadeGrid, dev->stream); dev->shadeBuilds[b >> 6] |= 1ull << (b & 63); timedLaunchEnd(dev, dev->stream);
   }
   if (maxDepth > 0) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, maxDepth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream); } // the shadow rays of the last shade
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulatePlanned(p, halfOutput(dev), dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive, dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulatePlanned(p, halfOutput(dev), dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive, cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
   dev->lastPassCount = 0; // the radiance stream holds a planned pass's paths, not a uniform pass's
   dev->adaptiveStarted = true;

@@ -174,6 +174,26 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 1 && i[0] <= 64) (key == "adaptiveMinBatch" ? adaptiveMinBatch : adaptiveMaxBatch) = i[0];
       else if (ok) warnings.push_back(key + " must be in 1..64, keeping the previous value");
     }
+    // the firefly cascade (twk_enable_cascade / twk_cascade_resolve, read by twk_app_get_cascade): a value the call would refuse drops the line
+    else if (key == "fireflyCascade")      { ok = readInt(parser, i[0]); if (ok) fireflyCascade = (i[0] == 1) ? 1 : 0; }
+    else if (key == "fireflyCascadeLayers")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 2 && i[0] <= 8) fireflyCascadeLayers = i[0];
+      else if (ok) warnings.push_back("fireflyCascadeLayers must be in 2..8, keeping the previous value");
+    }
+    else if (key == "fireflyCascadeStart" || key == "fireflyCascadeKappa")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] > 0.0f && std::isfinite(f[0])) (key == "fireflyCascadeStart" ? fireflyCascadeStart : fireflyCascadeKappa) = f[0];
+      else if (ok) warnings.push_back(key + " must be > 0 and finite, keeping the previous value");
+    }
+    else if (key == "fireflyCascadeBase")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] > 1.0f && std::isfinite(f[0])) fireflyCascadeBase = f[0];
+      else if (ok) warnings.push_back("fireflyCascadeBase must be > 1 and finite, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -203,6 +223,15 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
   {
     adaptiveMinBatch = TWK_DENOISER_MIN_SAMPLES; adaptiveMaxBatch = 64;
     warnings.push_back("adaptiveMinBatch must not exceed adaptiveMaxBatch, dropping both");
+  }
+
+  // in whichever order the three keys came: thresholds start * base^j that reach inf are what twk_enable_cascade refuses
+  float threshold = fireflyCascadeStart;
+  for (int j = 1; j < fireflyCascadeLayers; ++j) threshold = threshold * fireflyCascadeBase;
+  if (!std::isfinite(threshold))
+  {
+    fireflyCascadeLayers = TWK_CASCADE_LAYERS; fireflyCascadeStart = TWK_CASCADE_START; fireflyCascadeBase = TWK_CASCADE_BASE;
+    warnings.push_back("fireflyCascadeStart * fireflyCascadeBase^(fireflyCascadeLayers - 1) must be finite, dropping all three");
   }
 
   camera.setResolution(resolution[0], resolution[1]); // Application.cpp:207
@@ -251,6 +280,11 @@ std::string Application::systemDescription() const
   if (adaptiveBudget != 0) d << "adaptiveBudget " << adaptiveBudget << std::endl;
   if (adaptiveMinBatch != TWK_DENOISER_MIN_SAMPLES) d << "adaptiveMinBatch " << adaptiveMinBatch << std::endl;
   if (adaptiveMaxBatch != 64) d << "adaptiveMaxBatch " << adaptiveMaxBatch << std::endl;
+  if (fireflyCascade != 0) d << "fireflyCascade " << fireflyCascade << std::endl;
+  if (fireflyCascadeLayers != TWK_CASCADE_LAYERS) d << "fireflyCascadeLayers " << fireflyCascadeLayers << std::endl;
+  if (fireflyCascadeStart != TWK_CASCADE_START) d << "fireflyCascadeStart " << fireflyCascadeStart << std::endl;
+  if (fireflyCascadeBase != TWK_CASCADE_BASE) d << "fireflyCascadeBase " << fireflyCascadeBase << std::endl;
+  if (fireflyCascadeKappa != TWK_CASCADE_KAPPA) d << "fireflyCascadeKappa " << fireflyCascadeKappa << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

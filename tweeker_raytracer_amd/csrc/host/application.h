@@ -106,6 +106,12 @@ public:
   int   targetNoiseInterval = 16;
   // "adaptiveSampling" (1: between the stopping rule's checks the render loop samples only the pixels twk_adaptive_select picks
   // by "targetNoise"; dropped without a target), "adaptiveMaxSamples" (no pixel is selected once it has this many samples)
+  // "fireflyCascade" (1: the accumulate kernels fold the firefly cascade's layers, twk_enable_cascade, and a render loop resolves
+  // them, twk_cascade_resolve, before it shows or denoises the picture), "fireflyCascadeLayers", "fireflyCascadeStart",
+  // "fireflyCascadeBase" (TwkCascade), "fireflyCascadeKappa" (TwkCascadeResolve)
+  int   fireflyCascade = 0;
+  int   fireflyCascadeLayers = TWK_CASCADE_LAYERS;
+  float fireflyCascadeStart = TWK_CASCADE_START, fireflyCascadeBase = TWK_CASCADE_BASE, fireflyCascadeKappa = TWK_CASCADE_KAPPA;
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel

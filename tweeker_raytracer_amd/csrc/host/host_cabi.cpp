@@ -174,6 +174,19 @@ try
 }
 TWK_CATCH("twk_app_get_adaptive_plan")
 
+int twk_app_get_cascade(TwkApp app, int* enabled, TwkCascade* cp, TwkCascadeResolve* rp)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_cascade: NULL app");
+  if (!enabled || !cp || !rp) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_cascade: NULL argument");
+  const Application& a = app->app;
+  *enabled = (a.fireflyCascade != 0) ? 1 : 0;
+  cp->layers = a.fireflyCascadeLayers; cp->start = a.fireflyCascadeStart; cp->base = a.fireflyCascadeBase;
+  rp->kappa = a.fireflyCascadeKappa;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_cascade")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -270,6 +283,11 @@ try
   if (a.denoiser != 0 && a.denoiserSampledVariance && (rc = twk_enable_moments(dev, 1))) return rc; // "denoiserSampledVariance 1": the filter's variance is the samples'
   if (a.targetNoise > 0.0f && (rc = twk_enable_moments(dev, 1))) return rc; // "targetNoise e": the stopping rule reads the samples' moments
   if (a.adaptiveSampling != 0 && a.targetNoise > 0.0f && (rc = twk_enable_adaptive(dev, 1))) return rc; // "adaptiveSampling 1": per-pixel sample counts and the active list
+  if (a.fireflyCascade != 0) // "fireflyCascade 1": the brightness layers beside the running mean
+  {
+    const TwkCascade cascade = {a.fireflyCascadeLayers, a.fireflyCascadeStart, a.fireflyCascadeBase};
+    if ((rc = twk_enable_cascade(dev, 1, &cascade))) return rc;
+  }
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;
   if ((rc = twk_init_materials(dev, a.materials.data(), (int) a.materials.size()))) return rc;

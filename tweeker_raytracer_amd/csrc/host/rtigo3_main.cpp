@@ -10,6 +10,10 @@
 // (twk_launch_adaptive) between two checks; with "adaptiveBudget 1" too, each interval is instead one plan (twk_adaptive_plan) and
 // one planned pass (twk_launch_adaptive_planned) that gives every selected pixel the samples its own estimate predicts. It ends
 // when the target is met, when no device selects anything, or when the samples spent reach the uniform budget, samplesSqrt² x the pixel count; the second line gains the samples per pixel and the active share.
+// With "fireflyCascade 1" the accumulate kernels also fold the firefly cascade's layers (twk_enable_cascade); the screenshot is then
+// the RESOLVED picture (twk_cascade_resolve), which also stands in as the beauty of whichever denoiser mode is on — guides and
+// moments stay the handle's own. The loop, its frame-rate line, the noise estimate and the adaptive passes are what they are
+// without it. One device only: refused before any device is created.
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -172,6 +176,16 @@ int main(int argc, char* argv[])
   int planEnabled = 0; // "adaptiveBudget 1": each interval is one plan + one planned pass, every pixel at the samples its estimate predicts
   TwkAdaptivePlan adaptivePlan;
   TWK_OK(twk_app_get_adaptive_plan(app, &planEnabled, &adaptivePlan));
+
+  int cascadeEnabled = 0; // "fireflyCascade 1": the screenshot is the cascade's resolved picture
+  TwkCascade cascade;
+  TwkCascadeResolve cascadeResolve;
+  TWK_OK(twk_app_get_cascade(app, &cascadeEnabled, &cascade, &cascadeResolve));
+  if (cascadeEnabled && count > 1)
+  {
+    std::cerr << "ERROR: fireflyCascade resolves the layers of ONE device; they are packed tile buffers on several and are not assembled\n";
+    return 1;
+  }
 
   std::vector<TwkDevice> devices((size_t) count, nullptr);
   TwkDeviceState state;
@@ -379,14 +393,14 @@ int main(int argc, char* argv[])
   TWK_OK(twk_app_get_tonemapper(app, &tonemapper));
   std::vector<unsigned char> rgb8(numPixels * 3);
   // tonemaps `frame` (device memory in the output format on the first device; NULL: the first device's own buffers), denoised
-  // first when the description asks for it
-  auto present = [&](const void* frame) -> int
+  // first when the description asks for it; albedo, normal, moments: the guides beside an explicit frame that has them (the cascade's)
+  auto present = [&](const void* frame, const void* albedo = nullptr, const void* normal = nullptr, const void* moments = nullptr) -> int
   {
     if (denoiserEnabled)
     {
-      if (denoiserSampledEnabled)       TWK_OK(twk_denoise_variance_sampled(devices[0], &denoiser, &denoiserVariance, denoiserMinSamples, frame, nullptr, nullptr, nullptr, width, height, nullptr)); // one device: frame is NULL, the handle's own buffers and moments
-      else if (denoiserVarianceEnabled) TWK_OK(twk_denoise_variance(devices[0], &denoiser, &denoiserVariance, frame, nullptr, nullptr, width, height, nullptr));
-      else                              TWK_OK(twk_denoise(devices[0], &denoiser, frame, nullptr, nullptr, width, height, nullptr));
+      if (denoiserSampledEnabled)       TWK_OK(twk_denoise_variance_sampled(devices[0], &denoiser, &denoiserVariance, denoiserMinSamples, frame, albedo, normal, moments, width, height, nullptr)); // one device: frame is NULL, the handle's own buffers and moments
+      else if (denoiserVarianceEnabled) TWK_OK(twk_denoise_variance(devices[0], &denoiser, &denoiserVariance, frame, albedo, normal, width, height, nullptr));
+      else                              TWK_OK(twk_denoise(devices[0], &denoiser, frame, albedo, normal, width, height, nullptr));
       void* denoised = nullptr;
       TWK_OK(twk_get_denoised_device_pointer(devices[0], &denoised, nullptr));
       frame = denoised;
@@ -396,7 +410,31 @@ int main(int argc, char* argv[])
     else           TWK_OK(twk_tonemap(devices[0], &tonemapper, frame, numPixels, rgb8.data()));
     return 0;
   };
-  if (count == 1)
+  if (cascadeEnabled)
+  {
+    // one device: resolve its own layers; the resolved picture is the frame. A denoiser takes it as an explicit beauty, so every
+    // input it uses is passed beside it: copies of the handle's AOVs, and the handle's moments themselves
+    TWK_OK(twk_cascade_resolve(devices[0], &cascade, &cascadeResolve, nullptr, 0, 0, nullptr));
+    void* resolved = nullptr;
+    TWK_OK(twk_get_resolved_device_pointer(devices[0], &resolved, nullptr));
+    void* guides[2] = {nullptr, nullptr}; void* moments = nullptr;
+    if (denoiserEnabled && denoiser.inputKind != TWK_DENOISER_RGB)
+    {
+      std::vector<unsigned char> host(numPixels * pixelBytes);
+      HIP_OK(hipSetDevice(ordinals[0]));
+      for (int which = 0; which < 2; ++which)
+      {
+        TWK_OK(twk_read_aov_raw(devices[0], which == 0 ? TWK_AOV_ALBEDO : TWK_AOV_NORMAL, host.data(), host.size()));
+        HIP_OK(hipMalloc(&guides[which], host.size()));
+        HIP_OK(hipMemcpy(guides[which], host.data(), host.size(), hipMemcpyHostToDevice));
+      }
+    }
+    if (denoiserEnabled && denoiserSampledEnabled) TWK_OK(twk_get_moments_device_pointer(devices[0], &moments, nullptr));
+    const int failed = present(resolved, guides[0], guides[1], moments);
+    for (void* guide : guides) if (guide) HIP_OK(hipFree(guide));
+    if (failed) return 1;
+  }
+  else if (count == 1)
   {
     if (present(nullptr)) return 1;
   }

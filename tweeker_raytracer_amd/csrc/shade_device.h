@@ -10,6 +10,7 @@
 #define TWK_PROBE_GGX_AS_LAMBERT 0
 #endif
 #include "device_types.h"
+#include "cascade_device.h"
 
 namespace twk {
 
@@ -1064,9 +1065,13 @@ struct StoredAsFloat { TWK_HD float4 operator()(const float4 v) const { return v
 // n is a float (exact up to 2^24 samples). A sample that is not finite makes the triple not finite; nothing is caught here, the
 // consumer (denoise_device.h, the SAMPLED moments pass) falls back to its spatial estimate for such a pixel. M2 / (n - 1) is
 // the sample variance of the luminance, M2 / ((n - 1) n) the variance of the pixel's mean. Never rounded to half.
+// CASCADE (twk_enable_cascade; the CASCADE builds of the accumulate kernels): the same read also splits the kept sample over the
+// launch index's brightness layers *cascade (cascade_device.h cascadeFoldSample: the complete definition), held in registers for
+// the pass. Neither build flag changes a bit of dst, dstAlbedo or dstNormal, nor one the other's words.
 // foldSample is the fold of ONE sample, the path `path` at iteration `iteration`; foldSamples and foldActiveSamples say which.
-template<bool MOMENTS, typename Stored>
-TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned int iteration, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments)
+template<bool MOMENTS, bool CASCADE = false, typename Stored>
+TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned int iteration, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments,
+                      const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
 {
   const bool aov = (p.aovAlbedo != nullptr);
   const float4 r = p.pathRadiance[path];
@@ -1090,6 +1095,7 @@ TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned i
     moments->x = moments->x + d / moments->z;
     moments->y = moments->y + d * (l - moments->x);
   }
+  if (CASCADE) cascadeFoldSample(*cascadeConstants, *cascade, iteration, radiance.x, radiance.y, radiance.z);
   V3 albedo = v3(0.0f), normal = v3(0.0f);
   if (aov) { albedo = v3(p.pathAlbedo[path]); normal = v3(p.pathNormal[path]); }
   // time view (raygeneration.cu:231-244): alpha = the sample's clock cycles * clockScale, accumulated like the radiance
@@ -1114,41 +1120,44 @@ TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned i
 }
 
 // The samples of a uniform pass: sample s of launch index `index` is path s * numPixels + index, at iteration iterationIndex + s.
-template<bool MOMENTS = false, typename Stored>
-TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments = nullptr)
+template<bool MOMENTS = false, bool CASCADE = false, typename Stored>
+TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments = nullptr,
+                       const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
 {
   bool touched = false;
   for (int s = 0; s < p.batchCount; ++s)
   {
-    if (foldSample<MOMENTS>(p, (size_t) s * p.numPixels + index, p.iterationIndex + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
+    if (foldSample<MOMENTS, CASCADE>(p, (size_t) s * p.numPixels + index, p.iterationIndex + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
   }
   return touched;
 }
 
 // The samples of an adaptive pass (twk_launch_adaptive) for entry k of its active list of numActive launch indices: sample s is
 // path s * numActive + k, at iteration count + s, where count is the launch index's own sample count before the pass.
-template<typename Stored>
+template<bool CASCADE = false, typename Stored>
 TWK_D bool foldActiveSamples(const LaunchParams& p, const unsigned int k, const unsigned int numActive, const unsigned int count, const int samples,
-                             float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments)
+                             float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments,
+                             const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
 {
   bool touched = false;
   for (int s = 0; s < samples; ++s)
   {
-    if (foldSample<true>(p, (size_t) s * numActive + k, count + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
+    if (foldSample<true, CASCADE>(p, (size_t) s * numActive + k, count + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
   }
   return touched;
 }
 
 // The samples of a planned adaptive pass (twk_launch_adaptive_planned) for an entry whose paths start at `firstPath`: sample s of
 // its `samples` is path firstPath + s, at iteration count + s, where count is the launch index's own sample count before the pass.
-template<typename Stored>
+template<bool CASCADE = false, typename Stored>
 TWK_D bool foldPlannedSamples(const LaunchParams& p, const unsigned int firstPath, const unsigned int count, const unsigned int samples,
-                              float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments)
+                              float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments,
+                              const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
 {
   bool touched = false;
   for (unsigned int s = 0; s < samples; ++s)
   {
-    if (foldSample<true>(p, (size_t) firstPath + s, count + s, dst, dstAlbedo, dstNormal, stored, moments)) touched = true;
+    if (foldSample<true, CASCADE>(p, (size_t) firstPath + s, count + s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
   }
   return touched;
 }

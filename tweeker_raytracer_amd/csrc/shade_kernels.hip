@@ -469,28 +469,55 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   }
 }
 
+// The layers of one launch index over a pass, for either build of an accumulate kernel: CascadeOn loads them at construction, hands
+// the fold its table and sums, and stores them; CascadeOff is empty and hands out null pointers that the CASCADE = false fold never reads.
+template<typename Cascade> struct CascadeFolding;
+template<> struct CascadeFolding<CascadeOff>
+{
+  TWK_D CascadeFolding(const CascadeOff&, size_t, size_t) {}
+  TWK_D const CascadeConstants* constants() const { return nullptr; }
+  TWK_D CascadeSums* sums() { return nullptr; }
+  TWK_D void store() const {}
+};
+template<> struct CascadeFolding<CascadeOn>
+{
+  const CascadeOn& cascade; const size_t stride, index; CascadeSums s;
+  TWK_D CascadeFolding(const CascadeOn& c, size_t stride, size_t index) : cascade(c), stride(stride), index(index) { cascadeLoad(c.k, c.layers, stride, index, s); }
+  TWK_D const CascadeConstants* constants() const { return &cascade.k; }
+  TWK_D CascadeSums* sums() { return &s; }
+  TWK_D void store() const { cascadeStore(cascade.k, cascade.layers, stride, index, s); }
+};
+
 // raygeneration.cu:222-253: drop NaN samples, running mean into the RGBA32F buffer, alpha 1. The samples of a batch
 // are folded in iteration order, one lerp each, so the float result equals batchCount separate launches.
 // MOMENTS (LaunchParams::moments != nullptr): the same single read of every sample also folds the launch index's luminance
 // moments (shade_device.h foldSamples), read and written once per pass, one more float4 each way.
-template<bool MOMENTS>
-__global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p)
+// Cascade (CascadeOn: twk_enable_cascade; CascadeOff is an empty argument and adds no code): the same read also splits every kept
+// sample over the launch index's brightness layers (cascade_device.h). The layers are read once into registers before the fold and
+// written once after it, however many samples the pass folds; layer-major, so every load and store is a coalesced 16 B per lane.
+template<bool MOMENTS, typename Cascade>
+__global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p, Cascade cascade)
 {
   const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
   if (index >= (unsigned int) p.numPixels) return;
-  if (!MOMENTS) { accumulateLaunchIndex(p, index); return; }
-  const bool aov = (p.aovAlbedo != nullptr);
-  size_t outIndex;
-  if (!accumulateTarget(p, index, outIndex)) return;
-  float4 dst = p.output[outIndex];
-  float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float4 moments = p.moments[index];
-  if (foldSamples<true>(p, index, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments))
+  if constexpr (!MOMENTS && !Cascade::on) { accumulateLaunchIndex(p, index); return; }
+  else
   {
-    p.output[outIndex] = dst;
-    if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
-    p.moments[index] = moments;
+    const bool aov = (p.aovAlbedo != nullptr);
+    size_t outIndex;
+    if (!accumulateTarget(p, index, outIndex)) return;
+    float4 dst = p.output[outIndex];
+    float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 moments = MOMENTS ? p.moments[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
+    if (foldSamples<MOMENTS, Cascade::on>(p, index, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments, layers.constants(), layers.sums()))
+    {
+      p.output[outIndex] = dst;
+      if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
+      if (MOMENTS) p.moments[index] = moments;
+      layers.store();
+    }
   }
 }
 
@@ -499,8 +526,8 @@ struct StoredAsHalf { TWK_D float4 operator()(const float4 v) const { return wid
 
 // accumulateKernel on RGBA16F output and AOV buffers (raygeneration.cu:267-317): the lerp operand is the widened half and the
 // arithmetic the f32 expression of the float build, rounded once per folded sample (foldSamples).
-template<bool MOMENTS>
-__global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
+template<bool MOMENTS, typename Cascade>
+__global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p, Cascade cascade)
 {
   const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
   if (index >= (unsigned int) p.numPixels) return;
@@ -514,11 +541,13 @@ __global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
   float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 moments = MOMENTS ? p.moments[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // f32 in half mode too: the samples' own luminance, never narrowed
-  if (foldSamples<MOMENTS>(p, index, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments))
+  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index); // f32 in half mode too
+  if (foldSamples<MOMENTS, Cascade::on>(p, index, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments, layers.constants(), layers.sums()))
   {
     output[outIndex] = narrow(dst); // dst is already a widened half: narrow() is exact here
     if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
     if (MOMENTS) p.moments[index] = moments;
+    layers.store();
   }
 }
 
@@ -526,8 +555,8 @@ __global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p)
 // active[k] (paths s * numActive + k) onto its running means and moments with the fold of the kernels above (shade_device.h
 // foldSample), sample s at iteration counts[active[k]] + s, and advances the launch index's sample count. The moments are always
 // on here (the list was selected from them). HALF: the RGBA16F buffers, as accumulateHalfKernel addresses them.
-template<bool HALF>
-__global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, const unsigned int* __restrict__ active, unsigned int* __restrict__ counts, unsigned int numActive, int samples)
+template<bool HALF, typename Cascade>
+__global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, const unsigned int* __restrict__ active, unsigned int* __restrict__ counts, unsigned int numActive, int samples, Cascade cascade)
 {
   const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= numActive) return;
@@ -538,6 +567,7 @@ __global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, co
   if (!accumulateTarget(p, index, outIndex)) return;
   const bool aov = (p.aovAlbedo != nullptr);
   float4 moments = p.moments[index];
+  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
   if (HALF)
   {
     Half4* output = reinterpret_cast<Half4*>(p.output);
@@ -546,11 +576,12 @@ __global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, co
     float4 dst = widen(output[outIndex]);
     float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldActiveSamples(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments))
+    if (foldActiveSamples<Cascade::on>(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments, layers.constants(), layers.sums()))
     {
       output[outIndex] = narrow(dst);
       if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
       p.moments[index] = moments;
+      layers.store();
     }
   }
   else
@@ -558,11 +589,12 @@ __global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, co
     float4 dst = p.output[outIndex];
     float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldActiveSamples(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments))
+    if (foldActiveSamples<Cascade::on>(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments, layers.constants(), layers.sums()))
     {
       p.output[outIndex] = dst;
       if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
       p.moments[index] = moments;
+      layers.store();
     }
   }
 }
@@ -570,9 +602,9 @@ __global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, co
 // The accumulate kernel of a planned adaptive pass: one thread per entry k of the plan folds the pathOffset[k + 1] - pathOffset[k]
 // samples of launch index active[k] (paths pathOffset[k] + s) onto its running means and moments with the fold of the kernels above,
 // sample s at iteration counts[active[k]] + s, and advances the launch index's sample count by as many. HALF: the RGBA16F buffers.
-template<bool HALF>
+template<bool HALF, typename Cascade>
 __global__ void __launch_bounds__(256) accumulatePlannedKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ pathOffset,
-                                                               unsigned int* __restrict__ counts, unsigned int numActive)
+                                                               unsigned int* __restrict__ counts, unsigned int numActive, Cascade cascade)
 {
   const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= numActive) return;
@@ -584,6 +616,7 @@ __global__ void __launch_bounds__(256) accumulatePlannedKernel(LaunchParams p, c
   if (!accumulateTarget(p, index, outIndex)) return;
   const bool aov = (p.aovAlbedo != nullptr);
   float4 moments = p.moments[index];
+  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
   if (HALF)
   {
     Half4* output = reinterpret_cast<Half4*>(p.output);
@@ -592,11 +625,12 @@ __global__ void __launch_bounds__(256) accumulatePlannedKernel(LaunchParams p, c
     float4 dst = widen(output[outIndex]);
     float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldPlannedSamples(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments))
+    if (foldPlannedSamples<Cascade::on>(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments, layers.constants(), layers.sums()))
     {
       output[outIndex] = narrow(dst);
       if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
       p.moments[index] = moments;
+      layers.store();
     }
   }
   else
@@ -604,11 +638,12 @@ __global__ void __launch_bounds__(256) accumulatePlannedKernel(LaunchParams p, c
     float4 dst = p.output[outIndex];
     float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldPlannedSamples(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments))
+    if (foldPlannedSamples<Cascade::on>(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments, layers.constants(), layers.sums()))
     {
       p.output[outIndex] = dst;
       if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
       p.moments[index] = moments;
+      layers.store();
     }
   }
 }
@@ -754,11 +789,18 @@ void launchGenerateActive(const LaunchParams& p, const unsigned int* active, con
   hipLaunchKernelGGL(generateActiveKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, active, counts, numActive);
 }
 
-void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, hipStream_t stream)
+// cascade.layers != nullptr (twk_enable_cascade): the CASCADE build of the accumulate kernel, here and in the two launchers below
+void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, const CascadeOn& cascade, hipStream_t stream)
 {
   const dim3 grid((numActive + 255u) / 256u);
-  if (half) hipLaunchKernelGGL(accumulateActiveKernel<true>, grid, dim3(256), 0, stream, p, active, counts, numActive, samples);
-  else      hipLaunchKernelGGL(accumulateActiveKernel<false>, grid, dim3(256), 0, stream, p, active, counts, numActive, samples);
+  if (cascade.layers != nullptr)
+  {
+    if (half) hipLaunchKernelGGL((accumulateActiveKernel<true, CascadeOn>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, cascade);
+    else      hipLaunchKernelGGL((accumulateActiveKernel<false, CascadeOn>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, cascade);
+    return;
+  }
+  if (half) hipLaunchKernelGGL((accumulateActiveKernel<true, CascadeOff>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, CascadeOff());
+  else      hipLaunchKernelGGL((accumulateActiveKernel<false, CascadeOff>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, CascadeOff());
 }
 
 void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, unsigned int numActive, hipStream_t stream)
@@ -766,11 +808,17 @@ void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, co
   hipLaunchKernelGGL(generatePlannedKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
 }
 
-void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, hipStream_t stream)
+void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, const CascadeOn& cascade, hipStream_t stream)
 {
   const dim3 grid((numActive + 255u) / 256u);
-  if (half) hipLaunchKernelGGL(accumulatePlannedKernel<true>, grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
-  else      hipLaunchKernelGGL(accumulatePlannedKernel<false>, grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
+  if (cascade.layers != nullptr)
+  {
+    if (half) hipLaunchKernelGGL((accumulatePlannedKernel<true, CascadeOn>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, cascade);
+    else      hipLaunchKernelGGL((accumulatePlannedKernel<false, CascadeOn>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, cascade);
+    return;
+  }
+  if (half) hipLaunchKernelGGL((accumulatePlannedKernel<true, CascadeOff>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, CascadeOff());
+  else      hipLaunchKernelGGL((accumulatePlannedKernel<false, CascadeOff>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, CascadeOff());
 }
 
 template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>
@@ -817,17 +865,23 @@ int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, 
   launch(p, depth, gridBlocks, stream);
   return index;
 }
-void launchAccumulate(const LaunchParams& p, bool half, hipStream_t stream)
+template<bool MOMENTS, typename Cascade>
+static void launchAccumulateBuild(const LaunchParams& p, bool half, const Cascade& cascade, const dim3 grid, hipStream_t stream)
+{
+  if (half) hipLaunchKernelGGL((accumulateHalfKernel<MOMENTS, Cascade>), grid, dim3(256), 0, stream, p, cascade);
+  else      hipLaunchKernelGGL((accumulateKernel<MOMENTS, Cascade>), grid, dim3(256), 0, stream, p, cascade);
+}
+void launchAccumulate(const LaunchParams& p, bool half, const CascadeOn& cascade, hipStream_t stream)
 {
   const dim3 grid((p.numPixels + 255) / 256);
-  if (p.moments != nullptr)
+  if (cascade.layers != nullptr)
   {
-    if (half) hipLaunchKernelGGL(accumulateHalfKernel<true>, grid, dim3(256), 0, stream, p);
-    else      hipLaunchKernelGGL(accumulateKernel<true>, grid, dim3(256), 0, stream, p);
+    if (p.moments != nullptr) launchAccumulateBuild<true>(p, half, cascade, grid, stream);
+    else                      launchAccumulateBuild<false>(p, half, cascade, grid, stream);
     return;
   }
-  if (half) hipLaunchKernelGGL(accumulateHalfKernel<false>, grid, dim3(256), 0, stream, p);
-  else      hipLaunchKernelGGL(accumulateKernel<false>, grid, dim3(256), 0, stream, p);
+  if (p.moments != nullptr) launchAccumulateBuild<true>(p, half, CascadeOff(), grid, stream);
+  else                      launchAccumulateBuild<false>(p, half, CascadeOff(), grid, stream);
 }
 // half: tiles and output are Half4
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,

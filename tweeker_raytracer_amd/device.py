@@ -45,6 +45,7 @@ def shade_build_name(index):
 class Device:
     def __init__(self, ordinal=0, index=0, count=1, miss=1):
         self._h = C.c_void_p()
+        self._cascadeLayers = 0  # layers of the last enableCascade (the shape readCascade returns)
         L.check(L.lib.twk_device_create(C.byref(self._h), int(ordinal), int(index), int(count), int(miss)))
         self.index, self.count, self.miss = index, count, miss
         self.state = None
@@ -427,6 +428,50 @@ class Device:
         L.check(L.lib.twk_adaptive_select(self._h, None if params is None else C.byref(params), ptr(moments), ptr(counts), C.c_size_t(int(numElements)),
                                           ptr(activeOut), C.byref(n)))
         return n.value
+
+    # ---- the firefly cascade (include/tweeker_hip.h "The firefly cascade", csrc/cascade_device.h) ----
+    def enableCascade(self, enable=True, params=None):
+        """twk_enable_cascade: the accumulate kernels also split every kept sample by its luminance over params.layers brightness
+        layers (L.Cascade; None = the defaults), per-layer float32 sums beside the running mean, which does not change. A change
+        of parameters while enabled zeroes the layers."""
+        L.check(L.lib.twk_enable_cascade(self._h, int(bool(enable)), None if params is None else C.byref(params)))
+        self._cascadeLayers = (params.layers if params is not None else L.TWK_CASCADE_LAYERS) if enable else 0
+
+    def readCascade(self):
+        """The layers: float32 [layers, height, launchWidth, 4]; .xyz the layer's weighted radiance sums, [0, ..., 3] the number of
+        kept samples n, [layers - 1, ..., 3] the samples rejected as not finite."""
+        out = np.empty((self._cascadeLayers, self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_cascade(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def cascadeDevicePointer(self):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_cascade_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def cascadeResolve(self, params=None, resolve=None, layers=None, shape=None, resolved=None):
+        """twk_cascade_resolve: out = (layer 0 + sum_j w_j layer j) / n with w_j = min(1, c_j / kappa), c_j the samples that landed
+        around layer j in the pixel's 3x3 window; asynchronous. params: L.Cascade, resolve: L.CascadeResolve (None = the handle's
+        own / the defaults). Without `layers` the handle's own layers into its internal resolved buffer (readResolved,
+        resolvedDevicePointer); otherwise device pointers to [layers][height*width] float4 and to height*width pixels of the
+        output format, shape = (height, width)."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_cascade_resolve(self._h, None if params is None else C.byref(params), None if resolve is None else C.byref(resolve),
+                                          ptr(layers), int(w), int(h), ptr(resolved)))
+
+    def resolvedDevicePointer(self):
+        """(device pointer, bytes) of the internal resolved buffer, in the output format: feeds tonemap(rgbaDevicePointer=...) and
+        denoise(beauty=...)."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_resolved_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readResolved(self):
+        """The internal resolved buffer: float32 [height, launchWidth, 4] (widened exactly in half mode)."""
+        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_resolved(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
 
     def renderAdaptive(self, samples):
         """twk_launch_adaptive: `samples` (1..64) samples of every launch index of the active list, each at the iteration its own

@@ -223,7 +223,21 @@ int twk_device_count(int* count);
 int twk_device_create(TwkDevice* out, int ordinal, int index, int count, int miss);
 int twk_device_destroy(TwkDevice dev); /* ≙ Device::~Device, Device.cpp:320-358 */
 
-int twk_set_state(TwkDevice dev, const TwkDeviceState* state);                  /* ≙ Device::setState      Device.cpp:1192-1256 */
+/* ≙ Device::setState, Device.cpp:1192-1256. May be called again on a live handle (a resized window, a re-tiling):
+ *  - A state whose resolution, tileSize or distribution differs from the current one, or that gives another launchWidth, changes
+ *    which pixel a launch index is and DISCARDS the handle's accumulations: its internal output, both AOVs, the luminance moments, the
+ *    cascade's layers, the geometry AOV, the sample counts and the active and plan lists. They come back zeroed, at the new size, with
+ *    the next call that needs them, as on a fresh handle; the picture restarts at iteration 0. The temporal history is dropped when
+ *    the resolution changes. Path streams and scratch keep their capacity. A state that differs in nothing of these (path lengths,
+ *    lens shader, epsilon, ...) allocates and clears nothing.
+ *  - Device pointers obtained from twk_get_*_device_pointer must be fetched again after such a change; otherwise they are stable.
+ *  - The padding of a packed tile buffer (distribution 1, several devices: launch indices whose column lies outside the picture)
+ *    reads as zeros at all times, in every buffer of the handle: twk_estimate_noise counts it as empty and no list names it.
+ *  - An external output buffer or shared frame (twk_set_output_device_pointer / twk_set_shared_frame) is the caller's: it is never
+ *    cleared here, its stale words beyond the new picture included. One that is too small for the new state is let go: the handle
+ *    accumulates into its internal buffer again, the caller's allocation is not written any more, and twk_get_output_device_pointer
+ *    names the internal buffer; hand a large enough one in again after the call. */
+int twk_set_state(TwkDevice dev, const TwkDeviceState* state);
 int twk_init_cameras(TwkDevice dev, const TwkCameraDefinition* c, int count);   /* ≙ Device::initCameras   Device.cpp:944-968 */
 int twk_init_lights(TwkDevice dev, const TwkLightDefinition* l, int count);     /* ≙ Device::initLights    Device.cpp:970-1000 */
 int twk_init_materials(TwkDevice dev, const TwkMaterialGUI* m, int count);      /* ≙ Device::initMaterials Device.cpp:1002-1056 */

@@ -161,6 +161,21 @@ static void readEnvironmentSwitches(TwkDevice_t* dev)
   if (const char* e = getenv("TWK_BATCH")) { const int b = atoi(e); dev->batchMax = (b < 1) ? 1 : ((b > 64) ? 64 : b); }
 }
 
+// The handle's own accumulations per launch index, freed: the internal output, both AOVs, the moments, the cascade's layers, the
+// geometry AOV, the sample counts and the active and plan lists. The next ensureStreams allocates those that are enabled again, zeroed,
+// at the new state's size, so that the padding of a packed tile buffer holds zeros whatever the handle rendered before. The path
+// streams, spill stacks and scratch keep their capacity; a caller's external output buffer or shared frame is the caller's to clear.
+static void dropAccumulations(TwkDevice dev)
+{
+  freeDevice(dev->d_outputInternal); freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance); dev->allocatedPixels = 0;
+  freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
+  freeDevice(dev->d_moments); dev->momentsPixels = 0;
+  freeDevice(dev->d_cascade); dev->cascadePixels = 0; dev->resolvedValid = false;
+  freeDevice(dev->d_geometry); dev->geometryPixels = 0;
+  freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); dev->adaptivePixels = 0;
+  freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets); dev->planElements = 0;
+}
+
 // =============================================================================================
 extern "C" {
 
@@ -267,16 +282,22 @@ try
   if (s->lensShader < 0 || s->lensShader > 2) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_state: lensShader must be 0..2");
   HIP_TRY(hipStreamSynchronize(dev->stream)); // Device.cpp:1194-1195
   if (dev->stateSet && (dev->state.resolution[0] != s->resolution[0] || dev->state.resolution[1] != s->resolution[1])) dropTemporal(dev);
-  dev->state = *s;
-  dev->stateSet = true; dev->geometryValid = false; dropAdaptive(dev);
+  int launchWidth = s->resolution[0];
   if (s->distribution && 1 < dev->count)
   {
     // DeviceMultiGPULocalCopy.cpp:84-97
     const int width = (s->resolution[0] + dev->count - 1) / dev->count;
     const int mask  = s->tileSize[0] - 1;
-    dev->launchWidth = (width + mask) & ~mask;
+    launchWidth = (width + mask) & ~mask;
   }
-  else dev->launchWidth = s->resolution[0];
+  // The frame's geometry: which pixel a launch index is. When it changes, every accumulation per launch index starts as a fresh
+  // handle's does; a state that keeps it (path lengths, lens shader, epsilon, ...) allocates and clears nothing.
+  const TwkDeviceState& was = dev->state;
+  if (!dev->stateSet || was.resolution[0] != s->resolution[0] || was.resolution[1] != s->resolution[1] || was.tileSize[0] != s->tileSize[0] ||
+      was.tileSize[1] != s->tileSize[1] || was.distribution != s->distribution || dev->launchWidth != launchWidth)
+    dropAccumulations(dev);
+  dev->state = *s; dev->launchWidth = launchWidth;
+  dev->stateSet = true; dev->geometryValid = false; dropAdaptive(dev);
   const size_t needBytes = (size_t) (dev->outputFrame ? s->resolution[0] : dev->launchWidth) * s->resolution[1] * pixelBytes(dev);
   if (dev->d_outputExternal && dev->outputExternalBytes < needBytes)
   {

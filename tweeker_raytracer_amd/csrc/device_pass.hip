@@ -169,8 +169,8 @@ int twk::ensureStreamsForPaths(TwkDevice dev, size_t paths)
   if (dev->momentsEnabled && (rc = growBuffers(dev, dev->momentsPixels, dev->allocatedPixels, {{dev->d_moments, sizeof(float4), true}}))) return rc;
   if (dev->cascadeEnabled)
   {
-    // layer-major with the launch indices as the stride: a buffer of exactly launchWidth x height elements per layer, allocated anew (zeroed) when that number changes
-    if (dev->cascadePixels != numPixels) { freeDevice(dev->d_cascade); dev->cascadePixels = 0; dev->resolvedValid = false; }
+    // layer-major with the launch indices as the stride: a buffer of exactly launchWidth x height elements per layer (twk_set_state
+    // drops it, like every accumulation, when the frame's geometry changes, so a buffer that exists has that size)
     if ((rc = growBuffers(dev, dev->cascadePixels, numPixels, {{dev->d_cascade, (size_t) dev->cascadeK.layers * sizeof(float4), true}}))) return rc;
   }
   if (dev->adaptiveEnabled)

@@ -75,6 +75,9 @@ class Device:
     def setState(self, state):
         L.check(L.lib.twk_set_state(self._h, C.byref(state)))
         self.state = state
+        # twk_set_state lets go of a shared frame that is too small for the new state: the readers are the packed buffer's again
+        if getattr(self, "_sharedFrame", False) and self._sharedFrameBytes < state.resolution[0] * state.resolution[1] * (8 if self.outputFormat == L.TWK_OUTPUT_HALF4 else 16):
+            self._sharedFrame = False
 
     def initCameras(self, cameras):
         arr, n = _as_array(L.CameraDefinition, cameras)
@@ -124,7 +127,7 @@ class Device:
     def setSharedFrame(self, dptr, nbytes):
         """Accumulate into a shared full W x H frame (ZeroCopy / PeerAccess strategies); 0 returns to the packed buffer."""
         L.check(L.lib.twk_set_shared_frame(self._h, C.c_void_p(int(dptr)), C.c_size_t(int(nbytes))))
-        self._sharedFrame = bool(dptr)
+        self._sharedFrame, self._sharedFrameBytes = bool(dptr), int(nbytes)
 
     def setShaderVariant(self, variant):
         """0 = rtigo3 (a light's back face reflects through its BSDF), 1 = Optix7Gui (any light hit ends the path)."""

@@ -748,6 +748,59 @@ int twk_cascade_fold_host(const TwkCascade* cp, const float* samples, size_t num
                           int debugExceptions, float* layers);
 int twk_cascade_resolve_host(const TwkCascade* cp, const TwkCascadeResolve* rp, const float* layers, int width, int height, float* resolved);
 
+/* ---- Assembling a tiled frame — new calls, ABI stays 9, no existing struct changes; without them no kernel and no bit of any
+ * picture changes ----------------------------------------------------------------------------------------------------------------
+ * With distribution 1 and several devices every handle renders its checkerboard share into packed launchWidth x H buffers: the
+ * beauty, the two AOVs, the moments, the sample counts and the cascade's layers. twk_assemble moves every requested plane and layer
+ * of every source device into full W x H buffers on ONE handle (`primary`) in ONE kernel launch, so that what works on whole
+ * pictures (the twk_denoise* calls with explicit buffers, twk_cascade_resolve with explicit layers, twk_estimate_noise with explicit
+ * moments) has something to work on. The map is twk_tile_column's; the complete definition is csrc/assemble_device.h and
+ * tests/assemble_restate.py restates it in numpy. Padding columns (x >= width) are neither read nor written. What it is NOT: a
+ * scatter back to the tiles (temporal accumulation, adaptive selection and planning stay per device), an assembly of the geometry
+ * AOV, or a path for the shared-frame strategies (their beauty is already whole, their other planes are not).
+ *   plane                     element                                   assembled buffer
+ *   TWK_PLANE_OUTPUT          the output format's pixel, 16 or 8 B       [H][W]
+ *   TWK_PLANE_ALBEDO/NORMAL   the output format's pixel, 16 or 8 B       [H][W]
+ *   TWK_PLANE_MOMENTS         float4, always                             [H][W]
+ *   TWK_PLANE_SAMPLE_COUNTS   uint32                                     [H][W]
+ *   TWK_PLANE_CASCADE         float4, K layers [K][H][launchWidth]       [K][H][W]  (the shape twk_cascade_resolve's explicit form takes) */
+enum { TWK_PLANE_OUTPUT = 0, TWK_PLANE_ALBEDO = 1, TWK_PLANE_NORMAL = 2, TWK_PLANE_MOMENTS = 3, TWK_PLANE_SAMPLE_COUNTS = 4, TWK_PLANE_CASCADE = 5, TWK_PLANE_COUNT = 6 };
+#define TWK_PLANE_BIT(plane) (1u << (plane))
+/* One source device's packed buffers, indexed by TWK_PLANE_*; the planes that are not requested are not looked at. */
+typedef struct TwkAssemblySource { const void* plane[TWK_PLANE_COUNT]; } TwkAssemblySource;
+/* planeMask: TWK_PLANE_BIT(p) ored together. sources[d] holds the buffers of the device with index d of deviceCount, which must be
+ * primary's device count; every pointer must be addressable from primary's device (the form an RCCL caller uses: pointers into the
+ * block it gathered). Asynchronous on primary's stream. The assembled buffers belong to primary, are allocated at first use and
+ * sized by its state, output format and cascade layer count; a later call overwrites them. One device is legal: the identity map
+ * cropped to width.
+ * TWK_ERROR_INVALID_VALUE: a NULL handle (before any HIP call), an empty or unknown plane mask, NULL sources, a NULL source pointer
+ * of a requested plane, a deviceCount that is not primary's. TWK_ERROR_INVALID_STATE: before twk_set_state, distribution 0 with
+ * several devices (every handle holds the whole frame), a requested plane whose switch is off on primary (twk_enable_aov,
+ * twk_enable_moments, twk_enable_adaptive, twk_enable_cascade). */
+int twk_assemble(TwkDevice primary, unsigned int planeMask, const TwkAssemblySource* sources, int deviceCount);
+/* The in-process form: the handles' own buffers, devices[] in any order. Recorded launches of every handle are rendered first.
+ * Ordered without a host synchronisation: an event recorded on every source stream is waited for on primary's stream, and the
+ * sources' streams wait for the assembly before they render on. Peers are read directly where hipDeviceCanAccessPeer allows (peer
+ * access is enabled, "already enabled" is fine), else staged with hipMemcpyPeerAsync into a block on primary; TWK_ASSEMBLE_STAGE=1
+ * in the environment when primary is created forces the staging path.
+ * Beyond twk_assemble's refusals. TWK_ERROR_INVALID_VALUE: a NULL entry, handles that disagree with primary in resolution, tile
+ * size, distribution, device count, output format or cascade parameters, indices that are not each of 0..count-1 exactly once.
+ * TWK_ERROR_INVALID_STATE: a handle before twk_set_state, a requested plane whose switch is off on some handle, TWK_PLANE_OUTPUT
+ * from a handle that renders into a shared frame (twk_set_shared_frame). */
+int twk_assemble_devices(TwkDevice primary, unsigned int planeMask, const TwkDevice* devices, int count);
+/* The assembled buffer of one plane on primary and its size in bytes; valid until the next change of shape. twk_read_assembled
+ * copies it to the host as it is (bytes must be its size) and synchronises. TWK_ERROR_INVALID_STATE: the plane has not been assembled
+ * since the handle was created or since twk_set_state changed resolution, tile size or distribution, twk_set_output_format changed
+ * the format, or twk_enable_cascade changed the layers: those drop every assembled buffer. */
+int twk_get_assembled_device_pointer(TwkDevice primary, int plane, void** dptr, size_t* bytes);
+int twk_read_assembled(TwkDevice primary, int plane, void* host, size_t bytes);
+/* Host only, no handle: the same definition over host arrays. sources[d] is device d's [layers][height][launchWidth] elements of
+ * elementBytes (4, 8 or 16) with launchWidth as twk_set_state derives it: width for one device, else twk_launch_width(width,
+ * tileSize[0], deviceCount); destination is [layers][height][width] elements, of which exactly the in-picture ones are written.
+ * TWK_ERROR_INVALID_VALUE: a NULL argument or source, a count or size below 1, a tile size that is no power of two, another
+ * elementBytes. */
+int twk_assemble_host(const void* const* sources, int deviceCount, int width, int height, const int tileSize[2], int elementBytes, int layers, void* destination);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int twk_profile_enable(TwkDevice dev, int enable);   /* hipEvent pair around every kernel launch */
 int twk_profile_reset(TwkDevice dev);
@@ -888,6 +941,10 @@ int twk_app_get_adaptive_plan(TwkApp app, int* enabled, TwkAdaptivePlan* plan);
  * when they differ from off / the defaults. twk_app_init_device enables the cascade when the key is on; the render loop resolves
  * (INTEGRATION.md "The firefly cascade"). */
 int twk_app_get_cascade(TwkApp app, int* enabled, TwkCascade* cp, TwkCascadeResolve* rp);
+/* "tileAssembly 0|1" (default 0; any other value draws a warning and leaves it off), written back only when on. On, with several
+ * devices and strategy 3, rtigo3_hip -m 1 assembles the planes its post steps need with one twk_assemble_devices and runs them on
+ * the assembled frame (INTEGRATION.md "Assembling a tiled frame"); with strategy 1 or 2 it refuses the run. */
+int twk_app_get_tile_assembly(TwkApp app, int* enabled);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

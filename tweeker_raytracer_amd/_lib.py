@@ -32,6 +32,9 @@ TWK_NOISE_DARK_FLOOR = 0.01  # twk_noise_defaults (include/tweeker_hip.h); its m
 TWK_ADAPTIVE_TARGET_NOISE, TWK_ADAPTIVE_MAX_SAMPLES = 0.05, 4096  # twk_adaptive_defaults (include/tweeker_hip.h)
 TWK_CASCADE_LAYERS, TWK_CASCADE_START, TWK_CASCADE_BASE = 6, 1.0, 8.0  # twk_cascade_defaults (include/tweeker_hip.h)
 TWK_CASCADE_KAPPA = 32.0  # twk_cascade_resolve_defaults (provisional: profiles/r15_cascade.md)
+# twk_assemble: the planes of a tiled frame (include/tweeker_hip.h "Assembling a tiled frame"); a plane mask is 1 << plane ored together
+TWK_PLANE_OUTPUT, TWK_PLANE_ALBEDO, TWK_PLANE_NORMAL, TWK_PLANE_MOMENTS, TWK_PLANE_SAMPLE_COUNTS, TWK_PLANE_CASCADE = 0, 1, 2, 3, 4, 5
+TWK_PLANE_COUNT = 6
 
 f3 = C.c_float * 3
 f2 = C.c_float * 2
@@ -163,6 +166,20 @@ class CascadeResolve(C.Structure):
         super().__init__(kappa)
 
 
+class AssemblySource(C.Structure):
+    """≙ TwkAssemblySource: one source device's packed buffers for twk_assemble, device pointers (ints or None) indexed by
+    TWK_PLANE_*. AssemblySource({TWK_PLANE_OUTPUT: ptr, ...}) fills the planes named."""
+    _fields_ = [("plane", C.c_void_p * TWK_PLANE_COUNT)]
+
+    def __init__(self, planes=None):
+        super().__init__()
+        for k, v in (planes or {}).items():
+            self.plane[int(k)] = None if v is None else int(v)
+
+
+TwkAssemblySource = AssemblySource
+
+
 class NoiseSummary(C.Structure):
     """≙ TwkNoiseSummary: what twk_estimate_noise reduces a stream of luminance moments to (csrc/noise_device.h). valid / unknown /
     empty count the elements; the rest describes e, the relative standard error of the luminance mean, over the valid ones."""
@@ -253,6 +270,7 @@ SYMBOLS = [
     "twk_adaptive_plan_defaults", "twk_adaptive_plan", "twk_adaptive_plan_host", "twk_launch_adaptive_planned", "twk_read_plan", "twk_app_get_adaptive_plan",
     "twk_cascade_defaults", "twk_cascade_resolve_defaults", "twk_enable_cascade", "twk_read_cascade", "twk_get_cascade_device_pointer", "twk_cascade_resolve",
     "twk_get_resolved_device_pointer", "twk_read_resolved", "twk_cascade_fold_host", "twk_cascade_resolve_host", "twk_app_get_cascade",
+    "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

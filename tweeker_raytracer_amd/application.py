@@ -149,6 +149,14 @@ class Application:
         return bool(on.value), plan
 
     @property
+    def tileAssembly(self):
+        """"tileAssembly 0|1" of the system description: a several-device render loop assembles the planes its post steps need
+        with one Device.assemble and runs them on the assembled frame."""
+        on = C.c_int(0)
+        L.check(L.lib.twk_app_get_tile_assembly(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @property
     def fireflyCascade(self):
         """(enabled, Cascade, CascadeResolve) from "fireflyCascade", "fireflyCascadeLayers", "fireflyCascadeStart",
         "fireflyCascadeBase", "fireflyCascadeKappa" of the system description; initDevice enables the device's cascade when the key

@@ -158,6 +158,7 @@ static void readEnvironmentSwitches(TwkDevice_t* dev)
   if (const char* e = getenv("TWK_TRACE_WAVES_RUNTIME")) dev->traceWavesForced = atoi(e); // A/B: 6 or 7 blocks per CU of the persistent trace kernel
   if (const char* e = getenv("TWK_BUILD_QUALITY")) dev->builder.setQuality(atoi(e)); // A/B: 0 LBVH, 1 binned SAH (default)
   if (const char* e = getenv("TWK_STREAM_BUDGET_MB")) { const long long mb = atoll(e); dev->streamBudgetBytes = (mb > 0) ? (size_t) mb << 20 : 0; }
+  if (const char* e = getenv("TWK_ASSEMBLE_STAGE")) dev->assembleStage = (atoi(e) != 0); // twk_assemble_devices stages every source (both paths on one GPU)
   if (const char* e = getenv("TWK_BATCH")) { const int b = atoi(e); dev->batchMax = (b < 1) ? 1 : ((b > 64) ? 64 : b); }
 }
 
@@ -174,6 +175,7 @@ static void dropAccumulations(TwkDevice dev)
   freeDevice(dev->d_geometry); dev->geometryPixels = 0;
   freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); dev->adaptivePixels = 0;
   freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets); dev->planElements = 0;
+  dropAssembled(dev); // what the handle assembled as a primary has the old frame's shape
 }
 
 // =============================================================================================
@@ -257,6 +259,9 @@ try
   freeDevice(dev->d_cascade); freeDevice(dev->d_cascadeLambda); freeDevice(dev->d_resolved);
   freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams); freeDevice(dev->d_noise);
   freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); freeDevice(dev->d_adaptiveScratch); freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets);
+  dropAssembled(dev);
+  if (dev->assembleReady) (void) hipEventDestroy(dev->assembleReady);
+  if (dev->assembleDone) (void) hipEventDestroy(dev->assembleDone);
   dev->builder.release();
   for (int k = 1; k < TWK_MAX_LANES; ++k)
   {
@@ -491,6 +496,7 @@ try
   freeDevice(dev->d_outputInternal);
   freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
   freeDevice(dev->d_denoised); dev->denoisedValid = false; // a denoised picture is in the format it was filtered in
+  dropAssembled(dev); // and so is an assembled frame
   dev->outputFormat = format; dropAdaptive(dev);
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS;
 }

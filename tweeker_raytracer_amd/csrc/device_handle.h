@@ -1,6 +1,6 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
-// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_assemble.hip (assembling a tiled frame), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
@@ -10,6 +10,7 @@
 #include "adaptive_device.h"
 #include "adaptive_plan_device.h"
 #include "cascade_device.h"
+#include "assemble_device.h"
 #include "error_state.h"
 
 #include <string>
@@ -48,6 +49,7 @@ unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int
                                        void* scratch, const AdaptiveConstants& k, const AdaptivePlanConstants& plan, int numCUs, hipStream_t stream);
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 void launchCascadeResolve(const CascadeConstants& k, float kappa, const float4* layers, float* lambda, int width, int height, void* resolved, bool half, hipStream_t stream);
+void launchAssemble(const AssembleShape& s, const AssembleTable& table, int count, hipStream_t stream);
 }
 
 using namespace twk;
@@ -198,6 +200,14 @@ struct TwkDevice_t
   unsigned int* d_planActive = nullptr; unsigned int* d_planOffsets = nullptr; size_t planElements = 0;
   bool adaptiveScratchPlan = false;
   unsigned int planActive = 0, planPaths = 0; bool planValid = false;
+  // twk_assemble / twk_assemble_devices with this handle as primary: the assembled W x H buffer of every plane (d_assembled[plane],
+  // in the output format / with the cascade layers it was allocated for; assembledValid: assembled since it was allocated), the
+  // staging block of the peers that cannot be read directly, and the two events that order the streams without a host
+  // synchronisation: assembleReady is recorded on this handle's stream as a source, assembleDone on it as primary.
+  void* d_assembled[TWK_PLANE_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t assembledBytes[TWK_PLANE_COUNT] = {0, 0, 0, 0, 0, 0};
+  bool assembledValid[TWK_PLANE_COUNT] = {false, false, false, false, false, false};
+  void* d_assembleStage = nullptr; size_t assembleStageBytes = 0; bool assembleStage = false; // TWK_ASSEMBLE_STAGE=1: every source is staged (tests both paths on one GPU)
+  hipEvent_t assembleReady = nullptr, assembleDone = nullptr;
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;
@@ -269,4 +279,6 @@ int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, boo
 void dropTemporal(TwkDevice dev);
 // device_cascade.hip
 CascadeOn cascadeFold(TwkDevice dev);
+// device_assemble.hip
+void dropAssembled(TwkDevice dev);
 }

@@ -194,6 +194,13 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && f[0] > 1.0f && std::isfinite(f[0])) fireflyCascadeBase = f[0];
       else if (ok) warnings.push_back("fireflyCascadeBase must be > 1 and finite, keeping the previous value");
     }
+    // assembling a tiled frame (twk_assemble_devices, read by twk_app_get_tile_assembly): exactly 0 or 1; anything else leaves it off
+    else if (key == "tileAssembly")
+    {
+      ok = (parser.nextToken(token) == TOKEN_VAL);
+      if (ok && (token == "0" || token == "1")) tileAssembly = (token == "1") ? 1 : 0;
+      else if (ok) { tileAssembly = 0; warnings.push_back("tileAssembly must be 0 or 1, leaving it off"); }
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -285,6 +292,7 @@ std::string Application::systemDescription() const
   if (fireflyCascadeStart != TWK_CASCADE_START) d << "fireflyCascadeStart " << fireflyCascadeStart << std::endl;
   if (fireflyCascadeBase != TWK_CASCADE_BASE) d << "fireflyCascadeBase " << fireflyCascadeBase << std::endl;
   if (fireflyCascadeKappa != TWK_CASCADE_KAPPA) d << "fireflyCascadeKappa " << fireflyCascadeKappa << std::endl;
+  if (tileAssembly != 0) d << "tileAssembly " << tileAssembly << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

@@ -112,6 +112,9 @@ public:
   int   fireflyCascade = 0;
   int   fireflyCascadeLayers = TWK_CASCADE_LAYERS;
   float fireflyCascadeStart = TWK_CASCADE_START, fireflyCascadeBase = TWK_CASCADE_BASE, fireflyCascadeKappa = TWK_CASCADE_KAPPA;
+  // "tileAssembly" (1: a several-device render loop assembles the planes its post steps need with one twk_assemble_devices and runs
+  // them on the assembled frame)
+  int   tileAssembly = 0;
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel

@@ -187,6 +187,16 @@ try
 }
 TWK_CATCH("twk_app_get_cascade")
 
+int twk_app_get_tile_assembly(TwkApp app, int* enabled)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_tile_assembly: NULL app");
+  if (!enabled) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_tile_assembly: NULL argument");
+  *enabled = (app->app.tileAssembly != 0) ? 1 : 0;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_tile_assembly")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {

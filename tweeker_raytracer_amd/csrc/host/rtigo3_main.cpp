@@ -13,7 +13,11 @@
 // With "fireflyCascade 1" the accumulate kernels also fold the firefly cascade's layers (twk_enable_cascade); the screenshot is then
 // the RESOLVED picture (twk_cascade_resolve), which also stands in as the beauty of whichever denoiser mode is on — guides and
 // moments stay the handle's own. The loop, its frame-rate line, the noise estimate and the adaptive passes are what they are
-// without it. One device only: refused before any device is created.
+// without it. One device only: refused before any device is created — unless the tiled frame is assembled:
+// With "tileAssembly 1", several devices and strategy 3 the guided and sampled-variance denoisers and the cascade are not refused:
+// after the loop ONE twk_assemble_devices on the first device assembles exactly the planes those steps need (beauty or cascade
+// layers, albedo, normal, moments), and they run on the assembled frame through their explicit forms. With strategy 1 or 2 the key
+// is refused (the beauty lives in the shared frame, the other planes do not); on one device it changes nothing.
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -149,12 +153,20 @@ int main(int argc, char* argv[])
   TWK_OK(twk_app_get_denoiser_variance(app, &denoiserVarianceEnabled, &denoiserVariance));
   int denoiserSampledEnabled = 0, denoiserMinSamples = 0; // "denoiserSampledVariance 1": the measured variance of the samples guides the filter
   TWK_OK(twk_app_get_denoiser_sampled(app, &denoiserSampledEnabled, &denoiserMinSamples));
-  if (denoiserEnabled && denoiserSampledEnabled && count > 1)
+  int tileAssembly = 0; // "tileAssembly 1": the planes the post steps need are assembled on the first device (strategy 3)
+  TWK_OK(twk_app_get_tile_assembly(app, &tileAssembly));
+  if (tileAssembly && count > 1 && (info.strategy == 1 || info.strategy == 2))
+  {
+    std::cerr << "ERROR: tileAssembly assembles packed tile buffers (strategy 3); with strategy 1 or 2 the beauty lives in a shared frame and the other planes do not\n";
+    return 1;
+  }
+  const bool assembling = tileAssembly && count > 1 && info.strategy == 3;
+  if (denoiserEnabled && denoiserSampledEnabled && count > 1 && !assembling)
   {
     std::cerr << "ERROR: denoiserSampledVariance needs the luminance moments of ONE device; they are packed tile buffers on several and are not assembled\n";
     return 1;
   }
-  if (denoiserEnabled && count > 1 && denoiser.inputKind != TWK_DENOISER_RGB)
+  if (denoiserEnabled && count > 1 && denoiser.inputKind != TWK_DENOISER_RGB && !assembling)
   {
     std::cerr << "ERROR: denoiser " << denoiser.inputKind + 1 << " needs the albedo / normal AOVs of ONE device; with several devices only denoiser 1 (no guides) filters the assembled frame\n";
     return 1;
@@ -181,7 +193,7 @@ int main(int argc, char* argv[])
   TwkCascade cascade;
   TwkCascadeResolve cascadeResolve;
   TWK_OK(twk_app_get_cascade(app, &cascadeEnabled, &cascade, &cascadeResolve));
-  if (cascadeEnabled && count > 1)
+  if (cascadeEnabled && count > 1 && !assembling)
   {
     std::cerr << "ERROR: fireflyCascade resolves the layers of ONE device; they are packed tile buffers on several and are not assembled\n";
     return 1;
@@ -410,7 +422,30 @@ int main(int argc, char* argv[])
     else           TWK_OK(twk_tonemap(devices[0], &tonemapper, frame, numPixels, rgb8.data()));
     return 0;
   };
-  if (cascadeEnabled)
+  if (assembling)
+  {
+    // several devices, packed tile buffers: one assembly of exactly the planes the post steps read, then their explicit forms on
+    // the assembled pointers (ordered on the first device's stream; no host round trip, no per-plane gather)
+    unsigned int planes = TWK_PLANE_BIT(cascadeEnabled ? TWK_PLANE_CASCADE : TWK_PLANE_OUTPUT);
+    if (denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO) planes |= TWK_PLANE_BIT(TWK_PLANE_ALBEDO);
+    if (denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) planes |= TWK_PLANE_BIT(TWK_PLANE_NORMAL);
+    if (denoiserEnabled && denoiserSampledEnabled) planes |= TWK_PLANE_BIT(TWK_PLANE_MOMENTS);
+    TWK_OK(twk_assemble_devices(devices[0], planes, devices.data(), count));
+    void* assembled[TWK_PLANE_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int p = 0; p < TWK_PLANE_COUNT; ++p) if (planes & TWK_PLANE_BIT(p)) TWK_OK(twk_get_assembled_device_pointer(devices[0], p, &assembled[p], nullptr));
+    void* frame = assembled[TWK_PLANE_OUTPUT]; void* resolved = nullptr;
+    if (cascadeEnabled)
+    {
+      HIP_OK(hipSetDevice(ordinals[0]));
+      HIP_OK(hipMalloc(&resolved, numPixels * pixelBytes));
+      TWK_OK(twk_cascade_resolve(devices[0], &cascade, &cascadeResolve, assembled[TWK_PLANE_CASCADE], width, height, resolved));
+      frame = resolved;
+    }
+    const int failed = present(frame, assembled[TWK_PLANE_ALBEDO], assembled[TWK_PLANE_NORMAL], assembled[TWK_PLANE_MOMENTS]);
+    if (resolved) HIP_OK(hipFree(resolved));
+    if (failed) return 1;
+  }
+  else if (cascadeEnabled)
   {
     // one device: resolve its own layers; the resolved picture is the frame. A denoiser takes it as an explicit beauty, so every
     // input it uses is passed beside it: copies of the handle's AOVs, and the handle's moments themselves

@@ -476,6 +476,53 @@ class Device:
         L.check(L.lib.twk_read_resolved(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
+    # ---- assembling a tiled frame (include/tweeker_hip.h "Assembling a tiled frame", csrc/assemble_device.h) ----
+    @staticmethod
+    def _planeMask(planes):
+        mask = 0
+        for p in planes:
+            mask |= 1 << int(p)
+        return mask
+
+    def assemble(self, devices, planes):
+        """twk_assemble_devices with this handle as primary: the planes (L.TWK_PLANE_*) of every handle of `devices` (all of the
+        frame's devices, any order), from their own packed tile buffers into this handle's assembled width x height buffers, in
+        one launch; asynchronous, ordered by events between the handles' streams."""
+        handles = (C.c_void_p * max(1, len(devices)))(*[d._h.value for d in devices])
+        L.check(L.lib.twk_assemble_devices(self._h, C.c_uint(self._planeMask(planes)), handles, int(len(devices))))
+
+    def assembleFrom(self, sources, planes):
+        """twk_assemble: the same from explicit buffers — sources[d] an L.AssemblySource (or a dict plane -> device pointer) with
+        the packed buffers of the device with index d, addressable from this handle's device (an RCCL caller: pointers into the
+        block it gathered). Asynchronous on this handle's stream."""
+        arr = (L.AssemblySource * max(1, len(sources)))()
+        for d, src in enumerate(sources):
+            arr[d] = src if isinstance(src, L.AssemblySource) else L.AssemblySource(src)
+        L.check(L.lib.twk_assemble(self._h, C.c_uint(self._planeMask(planes)), arr, int(len(sources))))
+
+    def assembledDevicePointer(self, plane):
+        """(device pointer, bytes) of this handle's assembled buffer of `plane`; TwkError before the plane has been assembled."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_assembled_device_pointer(self._h, int(plane), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readAssembled(self, plane):
+        """The assembled buffer of `plane` as it is held (synchronises): beauty and AOVs [height, width, 4] float32 (float16 in half
+        mode), moments [height, width, 4] float32, sample counts [height, width] uint32, the cascade [layers, height, width, 4]
+        float32."""
+        h, w = self.state.resolution[1], self.state.resolution[0]
+        plane = int(plane)
+        if plane == L.TWK_PLANE_SAMPLE_COUNTS:
+            out = np.empty((h, w), dtype=np.uint32)
+        elif plane == L.TWK_PLANE_CASCADE:
+            out = np.empty((self._cascadeLayers, h, w, 4), dtype=np.float32)
+        elif plane == L.TWK_PLANE_MOMENTS:
+            out = np.empty((h, w, 4), dtype=np.float32)
+        else:
+            out = np.empty((h, w, 4), dtype=np.float16 if self.outputFormat == L.TWK_OUTPUT_HALF4 else np.float32)
+        L.check(L.lib.twk_read_assembled(self._h, plane, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)))
+        return out
+
     def renderAdaptive(self, samples):
         """twk_launch_adaptive: `samples` (1..64) samples of every launch index of the active list, each at the iteration its own
         count says; asynchronous. Afterwards render(i) is refused for i != 0; render(0) restarts a uniform frame."""

@@ -701,9 +701,9 @@ int twk_read_plan(TwkDevice dev, uint32_t* active, uint32_t* pathOffset, size_t 
  * twk_cascade_resolve then counts a layer only as far as enough samples landed in it, in the pixel and its eight neighbours:
  * out = (layer 0 + sum_j w_j layer j) / n, w_j = min(1, c_j / kappa). With more samples every weight goes to 1 and the picture is
  * the plain mean. The complete definition is csrc/cascade_device.h; tests/cascade_restate.py restates it in numpy. What it is NOT:
- * learned, temporal, reprojected by twk_temporal_accumulate, colour-aware (the reliability is of the luminance), or unbiased at
- * finite n (the clamp above the top layer and every w_j < 1 remove energy); of the paper it leaves out the local/global mixing and
- * the variance term. The running mean, the AOVs, the moments, the noise estimate and the adaptive passes do not see it. */
+ * learned, colour-aware (the reliability is of the luminance), temporal by itself (the layers are carried over a camera move by "The
+ * cascade through the temporal merge" below, opt-in), or unbiased at finite n (the clamp above the top layer and every w_j < 1
+ * remove energy); of the paper it leaves out the local/global mixing and the variance term. The running mean, the AOVs, the moments, the noise estimate and the adaptive passes do not see it. */
 typedef struct TwkCascade { int layers; float start; float base; } TwkCascade;
 typedef struct TwkCascadeResolve { float kappa; } TwkCascadeResolve;
 #define TWK_CASCADE_LAYERS 6
@@ -747,6 +747,55 @@ int twk_read_resolved(TwkDevice dev, float* rgbaHost, size_t numFloats);
 int twk_cascade_fold_host(const TwkCascade* cp, const float* samples, size_t numSamples, size_t numElements, unsigned int firstIteration,
                           int debugExceptions, float* layers);
 int twk_cascade_resolve_host(const TwkCascade* cp, const TwkCascadeResolve* rp, const float* layers, int width, int height, float* resolved);
+
+/* ---- The cascade through the temporal merge — new calls, ABI stays 9, no existing struct changes; with the switch at its default no
+ * kernel and no bit of any output changes ---------------------------------------------------------------------------------------
+ * twk_temporal_accumulate carries the plain mean over a camera move: a firefly that enters its history stays for up to maxHistory
+ * samples, smeared along the reprojection path; and the cascade restarts at iteration 0, where a 3x3 window of a 1 - 4 spp frame
+ * holds too few samples for any bright layer to be trusted. These calls reproject the cascade's per-layer SUMS the way the plain
+ * mean is reprojected — the same projection, the same four taps, the same test of a tap's geometry, the same cap — and add them to
+ * the frame's. Sums merge linearly: the result is again a cascade, luminance(layer j) / b[j] still counts samples, and
+ * twk_cascade_resolve runs on it unchanged with the history's counts behind its weights. The loop of a frame:
+ *   twk_set_sample_offset; twk_launch 0 .. spp-1; twk_render_geometry; twk_temporal_accumulate (with twk_temporal_enable_cascade(1));
+ *   twk_cascade_resolve on the merged layers (explicit form); twk_denoise_variance_sampled with the resolved picture as beauty and
+ *   the merged moments.
+ * The complete definition is csrc/temporal_cascade_device.h; tests/temporal_cascade_restate.py restates it in numpy. What it is: a
+ * linear, capped, bilinear carry-over of sums and counts. What it is NOT: exact counting — n (layer 0 .w) becomes a weighted, capped
+ * count that is no integer, and the interpolation mixes the counts of neighbouring pixels; alpha and the luminance moments stay the
+ * existing merge's business; no motion vectors, no environment reprojection (a miss never has history), pinhole only, one device,
+ * no tiles; the paper's variance term is not reprojected; the noise estimate and the adaptive passes do not see the merged layers. */
+
+/* EXPLICIT form; asynchronous, one kernel on the handle's stream. currentLayers, historyLayers and layersOut are device buffers of
+ * [cp->layers][width*height] float4 (the shape twk_get_cascade_device_pointer hands out and twk_cascade_resolve takes),
+ * currentGeometry and historyGeometry width*height float4 geometry AOVs, historyCamera the camera the history was rendered from. A
+ * pixel without history (a miss, a position that is not finite, a frame count layer 0 .w that is not finite or < 1, a point behind
+ * or outside the previous view, no tap that belongs to it with a finite count >= 1 and a weight > 0) passes through with the input's
+ * bits. historyLayers NULL (historyGeometry and historyCamera are then not read): every pixel passes through. layersOut is the next
+ * call's historyLayers. tp, cp NULL: twk_temporal_defaults, twk_cascade_defaults. TWK_ERROR_INVALID_VALUE: a NULL handle (before any
+ * HIP call), NULL current layers, current geometry or output, history layers without their geometry or camera, an output that overlaps
+ * an input (the kernel gathers the history at other pixels), the parameter refusals of twk_enable_cascade, maxHistory < 1, a
+ * tolerance that is negative or not finite, a history camera whose U, V, W are linearly dependent or not finite, width or height
+ * < 1, width*height above 2^28. */
+int twk_temporal_accumulate_cascade(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                    const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera,
+                                    int width, int height, void* layersOut);
+/* OWN-BUFFER form: a switch, default 0. While it is on, the own-buffer twk_temporal_accumulate ALSO merges the handle's cascade
+ * layers, with its own tp, the previous geometry and camera it reprojects the plain mean with, before it swaps its history; its
+ * colour and moments are byte for byte what they are with the switch off. The merged layers go to double-buffered layers of the
+ * handle, allocated on first use; they are dropped by whatever drops the temporal history (twk_temporal_reset, a change of
+ * resolution or output format, twk_clear_scene, twk_build), by twk_enable_cascade(0) or with new parameters, and by this switch going
+ * off. The first call after a drop has no history of layers: it copies the frame's layers through and keeps them.
+ * TWK_ERROR_INVALID_STATE: (1) without twk_enable_cascade(1); and the own-buffer twk_temporal_accumulate, beside its own refusals,
+ * while the switch is on and the cascade is off. */
+int twk_temporal_enable_cascade(TwkDevice dev, int enable);
+/* The merged layers the last such call kept: [layers][launchWidth*height] float4 — the explicit `layers` of twk_cascade_resolve
+ * with width = launchWidth. TWK_ERROR_INVALID_STATE before such a call and after a drop. The read synchronises. */
+int twk_get_temporal_cascade_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+int twk_read_temporal_cascade(TwkDevice dev, float* host, size_t numFloats); /* numFloats = layers*launchWidth*height*4 */
+/* Host only, no handle: the same definition over host arrays of the shapes above (4 floats per element). historyLayers NULL: every
+ * pixel passes through. TWK_ERROR_INVALID_VALUE: as the explicit form. */
+int twk_temporal_cascade_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                              const float* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, float* layersOut);
 
 /* ---- Assembling a tiled frame — new calls, ABI stays 9, no existing struct changes; without them no kernel and no bit of any
  * picture changes ----------------------------------------------------------------------------------------------------------------

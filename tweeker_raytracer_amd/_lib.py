@@ -270,6 +270,7 @@ SYMBOLS = [
     "twk_adaptive_plan_defaults", "twk_adaptive_plan", "twk_adaptive_plan_host", "twk_launch_adaptive_planned", "twk_read_plan", "twk_app_get_adaptive_plan",
     "twk_cascade_defaults", "twk_cascade_resolve_defaults", "twk_enable_cascade", "twk_read_cascade", "twk_get_cascade_device_pointer", "twk_cascade_resolve",
     "twk_get_resolved_device_pointer", "twk_read_resolved", "twk_cascade_fold_host", "twk_cascade_resolve_host", "twk_app_get_cascade",
+    "twk_temporal_accumulate_cascade", "twk_temporal_enable_cascade", "twk_get_temporal_cascade_device_pointer", "twk_read_temporal_cascade", "twk_temporal_cascade_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",

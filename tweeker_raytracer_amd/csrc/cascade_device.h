@@ -48,6 +48,8 @@
 // What this leaves out of the paper: its mixing of a local (per pixel) and a global (per layer) reliability — this is the 3x3 count
 // alone; its variance term; and colour — the reliability is of the luminance only, one weight for the three components.
 // What it is not: unbiased at finite n. The top-layer clamp and every w_j < 1 remove energy.
+// Nor temporal by itself: the layers of a moved camera start afresh at iteration 0, and temporal_cascade_device.h carries them over
+// (twk_temporal_enable_cascade, opt-in) — the layers are sums, so reprojected history sums plus a frame's are again a cascade.
 #pragma once
 #include "device_types.h"
 

@@ -78,7 +78,7 @@ try
   if ((rc = activate(dev, name))) return rc; // recorded launches are rendered with the switch they were recorded under
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->resolvedValid = false;
-  if (!enable || !dev->cascadeEnabled || !sameParameters(c, dev->cascadeParameters)) dropAssembled(dev); // assembled layers are of the old parameters
+  if (!enable || !dev->cascadeEnabled || !sameParameters(c, dev->cascadeParameters)) { dropAssembled(dev); dropTemporalCascade(dev); } // assembled and temporally merged layers are of the old parameters
   if (!enable)
   {
     dev->cascadeEnabled = false;

@@ -1,6 +1,6 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
-// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_assemble.hip (assembling a tiled frame), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
@@ -10,6 +10,7 @@
 #include "adaptive_device.h"
 #include "adaptive_plan_device.h"
 #include "cascade_device.h"
+#include "temporal_cascade_device.h"
 #include "assemble_device.h"
 #include "error_state.h"
 
@@ -49,6 +50,8 @@ unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int
                                        void* scratch, const AdaptiveConstants& k, const AdaptivePlanConstants& plan, int numCUs, hipStream_t stream);
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 void launchCascadeResolve(const CascadeConstants& k, float kappa, const float4* layers, float* lambda, int width, int height, void* resolved, bool half, hipStream_t stream);
+void launchTemporalCascade(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, float4* layersOut,
+                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream);
 void launchAssemble(const AssembleShape& s, const AssembleTable& table, int count, hipStream_t stream);
 }
 
@@ -175,6 +178,12 @@ struct TwkDevice_t
   float4* d_temporal[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; void* d_temporalColour = nullptr;
   int temporalWidth = 0, temporalHeight = 0, temporalFormat = TWK_OUTPUT_FLOAT4, temporalKept = 0; bool temporalHasHistory = false, temporalValid = false;
   TwkCameraDefinition temporalCamera;
+  // twk_temporal_enable_cascade: while temporalCascade is set the own-buffer twk_temporal_accumulate also merges the handle's cascade
+  // layers (temporal_cascade_device.h) with the same previous geometry and camera, into two sets of [temporalCascadeLayers]
+  // [temporalCascadePixels] float4 — the set temporalCascadeKept holds what the last call kept, the other receives this call's.
+  // Dropped with the temporal history (dropTemporal) and by twk_enable_cascade off or with new parameters.
+  bool temporalCascade = false; float4* d_temporalCascade[2] = {nullptr, nullptr}; size_t temporalCascadePixels = 0;
+  int temporalCascadeLayers = 0, temporalCascadeKept = 0; bool temporalCascadeHasHistory = false, temporalCascadeValid = false;
   int lastPassCount = 0, lastPassPixels = 0; // samples per launch index and launch indices of the last pass, while its pathRadiance stream still holds them (twk_debug_read_path_radiance); 0: none
   // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) in the output format it was
   // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
@@ -279,6 +288,10 @@ int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, boo
 void dropTemporal(TwkDevice dev);
 // device_cascade.hip
 CascadeOn cascadeFold(TwkDevice dev);
+// device_temporal_cascade.hip
+void dropTemporalCascade(TwkDevice dev);
+const char* temporalCascadeRefusal(TwkDevice dev);
+int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* geometry, const float4* historyGeometry);
 // device_assemble.hip
 void dropAssembled(TwkDevice dev);
 }

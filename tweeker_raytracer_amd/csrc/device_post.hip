@@ -11,6 +11,7 @@ void twk::dropTemporal(TwkDevice dev)
   for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
   freeDevice(dev->d_temporalColour);
   dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
+  dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
 }
 
 // =============================================================================================
@@ -330,6 +331,7 @@ try
     if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
     colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
     if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+    if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
     if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
     {
       HIP_TRY(hipStreamSynchronize(dev->stream));
@@ -373,6 +375,8 @@ try
     k.hasHistory = 1;
     if (!temporalCamera(hCamera->P, k)) return refuse(TWK_ERROR_INVALID_VALUE, "the history's camera is degenerate: U, V, W are linearly dependent or not finite");
   }
+  // twk_temporal_enable_cascade: the handle's layers through the same previous geometry and camera, before the history is swapped
+  if (own && dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, geometry, hGeometry))) return rc;
   launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
   HIP_TRY(hipGetLastError());
   if (own)

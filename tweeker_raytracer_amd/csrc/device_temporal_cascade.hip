@@ -1,0 +1,178 @@
+// The cascade's layers through the temporal merge behind the C ABI (temporal_cascade_device.h: the definition): the explicit form,
+// the switch of the own-buffer form with its double-buffered merged layers and their readers, and the host-only form. The own-buffer
+// merge itself is issued by twk_temporal_accumulate (device_post.hip) through temporalCascadeOwn(), before it swaps its history.
+#include "device_handle.h"
+
+#include <cstring>
+#include <vector>
+
+// Frees the merged layers of the own-buffer form: the next call has no history of layers. The switch stays as it is.
+void twk::dropTemporalCascade(TwkDevice dev)
+{
+  for (int s = 0; s < 2; ++s) freeDevice(dev->d_temporalCascade[s]);
+  dev->temporalCascadePixels = 0; dev->temporalCascadeLayers = 0; dev->temporalCascadeKept = 0;
+  dev->temporalCascadeHasHistory = false; dev->temporalCascadeValid = false;
+}
+
+// Why the own-buffer twk_temporal_accumulate cannot merge the handle's layers (the switch is on); nullptr: it can
+const char* twk::temporalCascadeRefusal(TwkDevice dev)
+{
+  if (!dev->cascadeEnabled) return "twk_temporal_enable_cascade(1) is set but the handle has no cascade layers: twk_enable_cascade(1) first";
+  return nullptr;
+}
+
+// The own-buffer form's merge of the handle's layers, on its stream: k, geometry and historyGeometry (nullptr: the temporal merge
+// has no history) are those of the twk_temporal_accumulate that calls it, before it swaps its history.
+int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* geometry, const float4* historyGeometry)
+{
+  int rc = ensureStreams(dev); if (rc) return rc;
+  const size_t n = (size_t) k.width * k.height;
+  const int K = dev->cascadeK.layers;
+  if (!dev->d_cascade || (size_t) dev->cascadePixels != n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_temporal_accumulate: the handle's cascade layers do not have the frame's shape");
+  if (!dev->d_temporalCascade[0] || dev->temporalCascadePixels != n || dev->temporalCascadeLayers != K)
+  {
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    dropTemporalCascade(dev);
+    for (int s = 0; s < 2; ++s) HIP_TRY(hipMalloc(&dev->d_temporalCascade[s], n * (size_t) K * sizeof(float4)));
+    dev->temporalCascadePixels = n; dev->temporalCascadeLayers = K;
+  }
+  // layers are reprojected only with a history of their own and of the geometry: the first call after a drop copies the frame's through
+  const bool history = dev->temporalCascadeHasHistory && k.hasHistory != 0 && historyGeometry != nullptr;
+  const int keep = dev->temporalCascadeHasHistory ? 1 - dev->temporalCascadeKept : dev->temporalCascadeKept;
+  TemporalConstants kc = k;
+  kc.hasHistory = history ? 1 : 0;
+  launchTemporalCascade(dev->d_cascade, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
+                        dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
+  HIP_TRY(hipGetLastError());
+  dev->temporalCascadeKept = keep; dev->temporalCascadeHasHistory = true; dev->temporalCascadeValid = true;
+  return TWK_SUCCESS;
+}
+
+static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
+{
+  if (!a || !b) return false;
+  const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+  return x < y + bBytes && y < x + aBytes;
+}
+
+// The refusals the explicit and the host-only form share, and the constants both take. history: a history was passed.
+static int temporalCascadeParameters(const char* name, const TwkTemporal* tp, const TwkCascade* cp, bool history, const TwkCameraDefinition* historyCamera, int width, int height,
+                                     TemporalConstants& k, CascadeConstants& c)
+{
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  TwkTemporal temporal; temporal.maxHistory = TWK_TEMPORAL_MAX_HISTORY; temporal.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  if (tp) temporal = *tp;
+  TwkCascade cascade; cascade.layers = TWK_CASCADE_LAYERS; cascade.start = TWK_CASCADE_START; cascade.base = TWK_CASCADE_BASE;
+  if (cp) cascade = *cp;
+  if (const char* why = cascadeConstants(cascade, c)) return refuse(why);
+  if (temporal.maxHistory < 1) return refuse("maxHistory must be >= 1");
+  if (!(temporal.positionTolerance >= 0.0f) || !finite1(temporal.positionTolerance)) return refuse("positionTolerance must be >= 0 and finite");
+  if (width < 1 || height < 1) return refuse("width and height must be >= 1");
+  if ((size_t) width * (size_t) height > ((size_t) 1 << 28)) return refuse("width*height must be at most 2^28");
+  memset(&k, 0, sizeof(k));
+  k.width = width; k.height = height;
+  k.maxHistory = (float) temporal.maxHistory; k.tol2 = temporal.positionTolerance * temporal.positionTolerance;
+  if (history)
+  {
+    k.hasHistory = 1;
+    if (!temporalCamera(historyCamera->P, k)) return refuse("the history's camera is degenerate: U, V, W are linearly dependent or not finite");
+  }
+  return TWK_SUCCESS;
+}
+
+extern "C" {
+
+int twk_temporal_accumulate_cascade(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                    const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, void* layersOut)
+try
+{
+  const char* name = "twk_temporal_accumulate_cascade";
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  if (!currentLayers || !currentGeometry || !layersOut) return refuse(TWK_ERROR_INVALID_VALUE, "NULL current layers, current geometry or output");
+  if (historyLayers && (!historyGeometry || !historyCamera)) return refuse(TWK_ERROR_INVALID_VALUE, "history layers without the history's geometry or camera");
+  TemporalConstants k;
+  CascadeConstants c;
+  int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
+  const size_t n = (size_t) width * height, plane = n * sizeof(float4), layerBytes = plane * (size_t) c.layers;
+  if (overlaps(layersOut, layerBytes, currentLayers, layerBytes) || overlaps(layersOut, layerBytes, currentGeometry, plane) ||
+      (historyLayers && (overlaps(layersOut, layerBytes, historyLayers, layerBytes) || overlaps(layersOut, layerBytes, historyGeometry, plane))))
+    return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps an input (the kernel gathers the history at other pixels)");
+  if ((rc = activate(dev, name))) return rc;
+  launchTemporalCascade(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
+                        historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream);
+  HIP_TRY(hipGetLastError());
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_accumulate_cascade")
+
+int twk_temporal_enable_cascade(TwkDevice dev, int enable)
+try
+{
+  const char* name = "twk_temporal_enable_cascade";
+  int rc = activate(dev, name); if (rc) return rc;
+  if (enable && !dev->cascadeEnabled) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": the handle has no cascade layers: twk_enable_cascade(1) first");
+  if (!enable && dev->temporalCascade)
+  {
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    dropTemporalCascade(dev);
+  }
+  dev->temporalCascade = (enable != 0);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_enable_cascade")
+
+int twk_get_temporal_cascade_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
+try
+{
+  int rc = activate(dev, "twk_get_temporal_cascade_device_pointer"); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_temporal_cascade_device_pointer: NULL argument");
+  if (!dev->temporalCascadeValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_temporal_cascade_device_pointer: no twk_temporal_accumulate with twk_temporal_enable_cascade(1) on the handle's own buffers since the last drop");
+  *dptr = dev->d_temporalCascade[dev->temporalCascadeKept];
+  if (bytes) *bytes = dev->temporalCascadePixels * (size_t) dev->temporalCascadeLayers * sizeof(float4);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_temporal_cascade_device_pointer")
+
+int twk_read_temporal_cascade(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  int rc = activate(dev, "twk_read_temporal_cascade"); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_cascade: NULL buffer");
+  if (!dev->temporalCascadeValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal_cascade: no twk_temporal_accumulate with twk_temporal_enable_cascade(1) on the handle's own buffers since the last drop");
+  const size_t n = dev->temporalCascadePixels * (size_t) dev->temporalCascadeLayers;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_cascade: buffer must hold layers*launchWidth*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_temporalCascade[dev->temporalCascadeKept], n * sizeof(float4), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_temporal_cascade")
+
+int twk_temporal_cascade_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                              const float* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, float* layersOut)
+try
+{
+  const char* name = "twk_temporal_cascade_host";
+  if (!currentLayers || !currentGeometry || !layersOut) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL current layers, current geometry or output");
+  if (historyLayers && (!historyGeometry || !historyCamera)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": history layers without the history's geometry or camera");
+  TemporalConstants k;
+  CascadeConstants c;
+  int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
+  const size_t n = (size_t) width * height, all = n * (size_t) c.layers;
+  // (a host array of floats need not have a float4's alignment)
+  std::vector<float4> layers(all), geometry(n), history(historyLayers ? all : 0), hGeometry(historyLayers ? n : 0), out(all);
+  memcpy(layers.data(), currentLayers, all * sizeof(float4));
+  memcpy(geometry.data(), currentGeometry, n * sizeof(float4));
+  if (historyLayers)
+  {
+    memcpy(history.data(), historyLayers, all * sizeof(float4));
+    memcpy(hGeometry.data(), historyGeometry, n * sizeof(float4));
+  }
+  for (size_t p = 0; p < n; ++p)
+    temporalCascadePixel(k, c, layers.data(), geometry.data(), historyLayers ? history.data() : nullptr, historyLayers ? hGeometry.data() : nullptr, n, p, out.data());
+  memcpy(layersOut, out.data(), all * sizeof(float4));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_cascade_host")
+
+} // extern "C"

@@ -476,6 +476,39 @@ class Device:
         L.check(L.lib.twk_read_resolved(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
+    # ---- the cascade through the temporal merge (include/tweeker_hip.h, csrc/temporal_cascade_device.h) ----
+    def temporalAccumulateCascade(self, params=None, cascade=None, currentLayers=None, currentGeometry=None, historyLayers=None, historyGeometry=None,
+                                  historyCamera=None, shape=None, layersOut=None):
+        """twk_temporal_accumulate_cascade, the explicit form: the history's per-layer sums reprojected through historyCamera (a
+        CameraDefinition) and added to the current frame's; asynchronous. params: L.Temporal, cascade: L.Cascade (None = the
+        defaults). Layers are device pointers to [layers][height*width] float4, the geometries to height*width float4, shape =
+        (height, width). historyLayers None: every pixel passes through. layersOut is the next call's historyLayers and the explicit
+        `layers` of cascadeResolve."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda s: None if s is None else C.byref(s)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_cascade(self._h, ref(params), ref(cascade), ptr(currentLayers), ptr(currentGeometry), ptr(historyLayers),
+                                                      ptr(historyGeometry), ref(historyCamera), int(w), int(h), ptr(layersOut)))
+
+    def enableTemporalCascade(self, enable=True):
+        """twk_temporal_enable_cascade: while on, temporalAccumulate() on the handle's own buffers also merges the handle's cascade
+        layers with the previous geometry and camera (readTemporalCascade, temporalCascadeDevicePointer); its colour and moments do
+        not change. Needs enableCascade(True)."""
+        L.check(L.lib.twk_temporal_enable_cascade(self._h, int(bool(enable))))
+
+    def temporalCascadeDevicePointer(self):
+        """(device pointer, bytes) of the merged layers the last temporalAccumulate() kept: cascadeResolve(layers=..., shape=(height, launchWidth), ...)."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_temporal_cascade_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readTemporalCascade(self):
+        """The merged layers: float32 [layers, height, launchWidth, 4], as readCascade lays them out; [0, ..., 3] is the merged
+        (weighted, capped) sample count."""
+        out = np.empty((self._cascadeLayers, self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_temporal_cascade(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
     # ---- assembling a tiled frame (include/tweeker_hip.h "Assembling a tiled frame", csrc/assemble_device.h) ----
     @staticmethod
     def _planeMask(planes):

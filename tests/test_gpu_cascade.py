@@ -1,4 +1,4 @@
-"""-m gpu: the fold of the firefly cascade (twk_enable_cascade): the CASCADE builds of the four accumulate kernels split every kept
+"""-m gpu: the fold of the firefly cascade (twk_enable_cascade): the CascadeOn builds of the accumulate kernel split every kept
 sample over the launch index's brightness layers in the read that folds the running mean (csrc/cascade_device.h). The samples come
 from the tap twk_debug_read_path_radiance, which tests/test_gpu_moments.py pins to the oracle; the layers must equal the numpy
 restatement tests/cascade_restate.py over them, bit for bit. C2 at 61 x 37, 7 iterations, as there."""
@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cascade_restate as restate
+from test_gpu_adaptive import NAMES, _read
 from test_gpu_half_output import _DeviceBuffer
 from test_gpu_moments import ITERATIONS, RES, _app, _bits, _device, _passes, _same
 from test_moments_host import F, fold_mean, luminance, welford
@@ -70,7 +71,7 @@ def test_with_the_cascade_on_picture_aovs_and_moments_are_the_bits_they_are_with
 @pytest.mark.parametrize("half,aov,moments", [(False, False, False), (True, True, True), (True, False, False), (False, False, True)],
                          ids=["f32", "f16-aov-moments", "f16", "f32-moments"])
 def test_every_uniform_build_folds_the_same_layers(twk, seven, half, aov, moments):
-    """accumulateKernel / accumulateHalfKernel, with and without MOMENTS: the layers are f32 in half mode too, and need neither AOVs
+    """accumulateKernel on float4 and Half4 pixels, with and without MOMENTS: the layers are f32 in half mode too, and need neither AOVs
     nor moments."""
     dev = _cascade_device(twk, half=half, aov=aov, moments=moments)
     _same(_passes(dev, ITERATIONS), seven[0], "samples")
@@ -171,25 +172,34 @@ def test_samples_that_are_not_finite_are_counted_and_add_nothing(twk, emission):
             assert (tap[..., :3] < 0).any() and not got[5, ..., 3].any() and (got[0, ..., :3] < 0).any()
 
 
-def _uniform_layers(twk, counts):
-    """{c: layers after twk_launch(0 .. c-1)} of a fresh handle, read as it passes each c."""
-    dev = _cascade_device(twk, aov=True)
-    have, done = {}, 0
-    for c in sorted(set(int(c) for c in counts)):
-        for it in range(done, c):
-            dev.render(it)
-        done = c
-        have[c] = dev.readCascade()
-    dev.close()
+_uniform_cache = {}
+
+
+def _uniform_layers(twk, counts, half=False):
+    """{c: (layers, [colour, albedo, normal, moments] as test_gpu_adaptive._read reads them) after twk_launch(0 .. c-1)} for every c
+    asked for: a fresh handle in the output format per request that the cache cannot serve, read as it passes each c."""
+    have = _uniform_cache.setdefault(half, {})
+    need = sorted(set(int(c) for c in counts) - set(have))
+    if need:
+        dev = _cascade_device(twk, aov=True, half=half)
+        done = 0
+        for c in need:
+            for it in range(done, c):
+                dev.render(it)
+            done = c
+            have[c] = (dev.readCascade(), _read(dev, half))
+        dev.close()
     return have
 
 
-@pytest.mark.parametrize("planned", [False, True], ids=["select", "plan"])
-def test_after_adaptive_passes_a_pixel_with_count_c_holds_the_layers_of_c_uniform_launches(twk, planned):
-    """accumulateActiveKernel (twk_adaptive_select + twk_launch_adaptive) and accumulatePlannedKernel (twk_adaptive_plan +
-    twk_launch_adaptive_planned), two rounds after four uniform iterations; the target of a round is the median of its valid errors."""
+@pytest.mark.parametrize("planned,half", [(False, False), (True, False), (False, True), (True, True)], ids=["select", "plan", "select-RGBA16F", "plan-RGBA16F"])
+def test_after_adaptive_passes_a_pixel_with_count_c_holds_the_layers_of_c_uniform_launches(twk, planned, half):
+    """accumulateKernel's listed form (twk_adaptive_select + twk_launch_adaptive) and its planned form (twk_adaptive_plan +
+    twk_launch_adaptive_planned) with the cascade on, in either output format, two rounds after four uniform iterations; the target
+    of a round is the median of its valid errors. RGBA16F: the raw colour, both raw AOVs and the moments are compared too, per
+    count, with uniform launches on a fresh handle in the same format (as tests/test_gpu_adaptive.py does with the cascade off)."""
     import noise_restate as nr
-    dev = _cascade_device(twk, aov=True)
+    dev = _cascade_device(twk, aov=True, half=half)
     dev.enableAdaptive(True)
     for it in range(4):
         dev.render(it)
@@ -203,15 +213,21 @@ def test_after_adaptive_passes_a_pixel_with_count_c_holds_the_layers_of_c_unifor
         else:
             assert 0 < dev.adaptiveSelect(ap) < RES[0] * RES[1]
             dev.renderAdaptive(3)
-    counts, got, picture = dev.readSampleCounts(), dev.readCascade(), dev.getOutputBufferHost()
+    counts, got, buffers = dev.readSampleCounts(), dev.readCascade(), _read(dev, half)
+    picture = dev.getOutputBufferHost()
     dev.close()
     distinct = np.unique(counts)
     assert distinct.size >= 3 and distinct.min() == 4
-    ref = _uniform_layers(twk, distinct)
+    ref = _uniform_layers(twk, distinct, half)
     for c in distinct:
         where = counts == c
-        assert np.array_equal(_bits(got[:, where]), _bits(ref[int(c)][:, where])), f"layers differ from twk_launch(0..{int(c) - 1}) at pixels with count {int(c)}"
+        layers, uniform = ref[int(c)]
+        assert np.array_equal(_bits(got[:, where]), _bits(layers[:, where])), f"layers differ from twk_launch(0..{int(c) - 1}) at pixels with count {int(c)}"
         assert (got[0][where][:, 3] == c).all()
+        if half:
+            for name, g, w in zip(NAMES, buffers, uniform):
+                bad = np.nonzero((g[where] != w[where]).any(axis=-1))[0]
+                assert bad.size == 0, f"{name} differs from twk_launch(0..{int(c) - 1}) at {bad.size} of {int(where.sum())} pixels with count {int(c)}"
     assert np.isfinite(picture).all()
 
 

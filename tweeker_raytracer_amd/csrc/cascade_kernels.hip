@@ -16,10 +16,6 @@ __global__ void __launch_bounds__(256) cascadeLambdaKernel(const float4* __restr
   lambda[i] = cascadeLambda(layers[i]);
 }
 
-template<typename Pixel> struct ResolvedPixel;
-template<> struct ResolvedPixel<float4> { static TWK_D float4 make(const float4 v) { return v; } };
-template<> struct ResolvedPixel<Half4>  { static TWK_D Half4 make(const float4 v) { return narrow(v); } };
-
 // One thread per pixel, rows of the grid along the lanes
 template<typename Pixel>
 __global__ void __launch_bounds__(256) cascadeResolveKernel(CascadeConstants k, float kappa, const float4* __restrict__ layers, const float* __restrict__ lambda,
@@ -29,7 +25,7 @@ __global__ void __launch_bounds__(256) cascadeResolveKernel(CascadeConstants k, 
   const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
   if (p >= numPixels) return;
   const int y = (int) (p / (size_t) width), x = (int) (p - (size_t) y * width);
-  out[p] = ResolvedPixel<Pixel>::make(cascadeResolvePixel(k, kappa, layers, lambda, numPixels, width, height, x, y));
+  out[p] = pixelOf<Pixel>(cascadeResolvePixel(k, kappa, layers, lambda, numPixels, width, height, x, y));
 }
 
 // layers [k.layers][width x height] float4, lambda k.layers x width x height floats of scratch, resolved

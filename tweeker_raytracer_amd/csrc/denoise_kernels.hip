@@ -246,10 +246,6 @@ __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __rest
   else         out[p] = momentsFinish(k, cp, s0, s1, s2);
 }
 
-template<typename Pixel> struct PixelOf;
-template<> struct PixelOf<float4> { static TWK_D float4 make(const float4 v) { return v; } };
-template<> struct PixelOf<Half4>  { static TWK_D Half4 make(const float4 v) { return narrow(v); } };
-
 template<typename Pixel>
 __global__ void __launch_bounds__(256) denoiseFinishKernel(const Pixel* __restrict__ beauty, const float4* __restrict__ colour, const float4* __restrict__ guideNormal,
                                                            const float4* __restrict__ guideAlbedo, Pixel* __restrict__ denoised, DenoiseConstants k)
@@ -277,7 +273,7 @@ __global__ void __launch_bounds__(256) denoiseFinishKernel(const Pixel* __restri
   o.y = r.y + k.blendFactor * (b.y - r.y);
   o.z = r.z + k.blendFactor * (b.z - r.z);
   o.w = b.w;
-  denoised[p] = PixelOf<Pixel>::make(o);
+  denoised[p] = pixelOf<Pixel>(o);
 }
 
 static unsigned int pixelBlocks(const DenoiseConstants& k) { return (unsigned int) (((size_t) k.width * k.height + 255) / 256); }

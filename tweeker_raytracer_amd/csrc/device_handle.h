@@ -1,5 +1,5 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
-// readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass), device_post.hip (compositor,
+// readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass in its three forms: uniform, listed, planned — shade_device.h "the samples of a thread"), device_post.hip (compositor,
 // tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
@@ -20,11 +20,13 @@
 namespace twk {
 void launchTrace(const LaunchParams& p, int depth, bool count, const TraceBuild& build, int gridBlocks, hipStream_t stream);
 void launchTraceQuery(const LaunchParams& p, const float* rays, unsigned int numRays, int anyHit, float* tBetaGamma, int* ids, int gridBlocks, hipStream_t stream);
-void launchGenerate(const LaunchParams& p, hipStream_t stream);
 int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, hipStream_t stream);
 void shadeBuildSlots(uint64_t mask[2]);
 void launchTileEntries(const LaunchParams& p, const float4* topTable, int tilesX, int tilesY, int4* out, hipStream_t stream);
-void launchAccumulate(const LaunchParams& p, bool half, const CascadeOn& cascade, hipStream_t stream);
+// generateKernel / accumulateKernel for a pass of the form `samples`: UniformSamples, ListedSamples or PlannedSamples (shade_device.h
+// "the samples of a thread"; shade_kernels.hip instantiates the three). half: RGBA16F buffers; cascade.layers != nullptr: the cascade is on.
+template<typename Samples> void launchGenerate(const LaunchParams& p, const Samples& samples, hipStream_t stream);
+template<typename Samples> void launchAccumulate(const LaunchParams& p, bool half, const Samples& samples, const CascadeOn& cascade, hipStream_t stream);
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
                       int tileSizeX, int tileShiftX, int tileShiftY, hipStream_t stream);
 void launchMathTap(int op, const float* x, const float* y, float* out, size_t n, hipStream_t stream);
@@ -40,12 +42,8 @@ void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, co
 void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
-void launchGenerateActive(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, unsigned int numActive, hipStream_t stream);
-void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, const CascadeOn& cascade, hipStream_t stream);
 unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
                                    const AdaptiveConstants& k, int numCUs, hipStream_t stream);
-void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, unsigned int numActive, hipStream_t stream);
-void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, const CascadeOn& cascade, hipStream_t stream);
 unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, unsigned int* pathOffset,
                                        void* scratch, const AdaptiveConstants& k, const AdaptivePlanConstants& plan, int numCUs, hipStream_t stream);
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);

@@ -1,6 +1,7 @@
 // The path streams of a handle and the wavefront pass over them (≙ optixLaunch, reference apps/rtigo3/src/DeviceSingleGPU.cpp:164):
 // which kernel builds and grids a pass runs, its lanes, the deferred launches.
 #include "device_handle.h"
+#include "shade_device.h" // the forms of a pass: UniformSamples, ListedSamples, PlannedSamples
 
 #include <algorithm>
 #include <cassert>
@@ -299,6 +300,28 @@ static LaunchParams laneParams(TwkDevice dev, const LaunchParams& p, int lane, i
   return q;
 }
 
+// What every form of pass derives from its path count, on the scene as refreshParams has just described it: the queues' segment
+// stride and which layouts the queued rays and the hit records take.
+static void setPassPaths(TwkDevice dev, int numPaths)
+{
+  LaunchParams& p = dev->params;
+  p.numPaths = numPaths;
+  p.pathBase = 0;
+  p.queueStride = TWK_QUEUE_STRIDE(p.numPaths);
+  // launch index + path flags and the LCG state in the constant words of the queued rays (device_types.h LaunchParams::packedQueue)
+  p.packedQueue = (dev->packedQueue && !p.hasCutout && (unsigned int) p.numPaths <= TWK_PACKED_PIXEL_MASK) ? 1 : 0;
+  p.slimSlotBits = slimSlotBits(dev);
+}
+
+// Blocks of a shade launch over `numPaths` paths.
+// Many more blocks than are resident at once (4 per CU): a block that has finished its windows makes room for the next,
+// which evens out what the blocks' windows cost. Measured on C2 (shade ms/step): 4 / 8 / 16 / 64 / 256 / 2048 blocks per
+// CU = 0.310 / 0.309 / 0.305 / 0.294 / 0.290 / 0.298.
+static int shadeGridBlocks(TwkDevice dev, int numPaths)
+{
+  return std::min((numPaths + TWK_SHADE_BLOCK - 1) / TWK_SHADE_BLOCK, dev->numCUs * TWK_SHADE_BLOCKS_PER_CU);
+}
+
 // Runs iterations [firstIteration, firstIteration + count) as one wavefront pass; the streams are allocated.
 static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
 {
@@ -306,13 +329,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
   LaunchParams& p = dev->params;
   p.iterationIndex = firstIteration;
   p.batchCount = count;
-  p.numPaths = p.numPixels * p.batchCount;
-  p.pathBase = 0;
-  p.queueStride = TWK_QUEUE_STRIDE(p.numPaths);
-
-  // launch index + path flags and the LCG state in the constant words of the queued rays (device_types.h LaunchParams::packedQueue)
-  p.packedQueue = (dev->packedQueue && !p.hasCutout && (unsigned int) p.numPaths <= TWK_PACKED_PIXEL_MASK) ? 1 : 0;
-  p.slimSlotBits = slimSlotBits(dev);
+  setPassPaths(dev, p.numPixels * p.batchCount);
   const int maxDepth = dev->state.pathLengths[1];
   const int lanes = chooseLanes(dev, p.numPaths);
   // every block of every lane's persistent trace kernel resident at once: the lanes share the CUs' block slots
@@ -385,17 +402,12 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
     hipStream_t stream = (lane == 0) ? dev->stream : dev->laneStream[lane];
     if (lane > 0) HIP_TRY(hipStreamWaitEvent(stream, dev->laneFork, 0));
     HIP_TRY(hipMemsetAsync(q.counters, 0, sizeof(unsigned int) * TWK_COUNTER_WORDS, stream));
-    // Many more blocks than are resident at once (4 per CU): a block that has finished its windows makes room for the next,
-    // which evens out what the blocks' windows cost. Measured on C2 (shade ms/step): 4 / 8 / 16 / 64 / 256 / 2048 blocks per
-    // CU = 0.310 / 0.309 / 0.305 / 0.294 / 0.290 / 0.298.
-    int grid = (q.numPaths + TWK_SHADE_BLOCK - 1) / TWK_SHADE_BLOCK;
-    if (grid > dev->numCUs * TWK_SHADE_BLOCKS_PER_CU) grid = dev->numCUs * TWK_SHADE_BLOCKS_PER_CU;
-    laneP[active] = q; laneS[active] = stream; shadeGrid[active] = grid; ++active;
+    laneP[active] = q; laneS[active] = stream; shadeGrid[active] = shadeGridBlocks(dev, q.numPaths); ++active;
   }
   for (int k = 0; k < active; ++k)
   {
     if (fusedPrimary) { const unsigned int numPaths = (unsigned int) laneP[k].numPaths; HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) laneP[k].counters, (int) numPaths, 1, laneS[k])); continue; } // length of queue 0
-    timedLaunchBegin(dev, TWK_KERNEL_GENERATE, laneS[k]); launchGenerate(laneP[k], laneS[k]); timedLaunchEnd(dev, laneS[k]);
+    timedLaunchBegin(dev, TWK_KERNEL_GENERATE, laneS[k]); launchGenerate(laneP[k], UniformSamples(), laneS[k]); timedLaunchEnd(dev, laneS[k]);
   }
   for (int depth = 0; depth < wavefrontDepth; ++depth)
   {
@@ -416,7 +428,7 @@ static int renderPass(TwkDevice dev, unsigned int firstIteration, int count)
     HIP_TRY(hipStreamWaitEvent(dev->stream, dev->laneDone[lane], 0));
   }
   // the running mean folds the samples of the pass in iteration order over ALL lanes' paths: after the join, on the handle's stream
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), UniformSamples(), cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
   dev->lastPassCount = count; dev->lastPassPixels = p.numPixels;
   dev->uniformNext = firstIteration + (unsigned int) count; dev->countsCurrent = false; // (twk_launch has dropped the active list)
@@ -440,76 +452,35 @@ int twk::currentSampleCounts(TwkDevice dev)
   return TWK_SUCCESS;
 }
 
-// Renders `samples` samples of every launch index of the active list as one wavefront pass of numActive x samples paths: a sibling
-// of renderPass. generateActiveKernel writes queue 0 (path j = sample j / numActive of entry j % numActive, at the iteration the
-// launch index's own count says), the trace and shade launches are renderPass's non-primary builds on one lane, which index by
-// path only, and accumulateActiveKernel folds the samples per launch index and advances its count. The streams are allocated.
-static int renderAdaptivePass(TwkDevice dev, int samples)
+// Renders a pass of one of the two list forms (shade_device.h ListedSamples: `samples` samples of every entry of the active list;
+// PlannedSamples: the handle's plan) as one wavefront pass of numPaths paths: a sibling of renderPass. generateKernel writes queue 0
+// for the form's paths, at the iterations the launch indices' own counts say; the trace and shade launches are renderPass's
+// non-primary builds on one lane, which index by path only; accumulateKernel folds the samples per launch index and advances its
+// count. The streams are allocated.
+template<typename Samples>
+static int renderListPass(TwkDevice dev, const Samples& samples, size_t numPaths)
 {
   refreshParams(dev);
   LaunchParams& p = dev->params;
-  p.iterationIndex = 0; // no kernel of this pass reads it: the counts stand in its place
-  p.batchCount = samples;
-  p.numPaths = (int) ((size_t) dev->numActive * (size_t) samples);
-  p.pathBase = 0;
-  p.queueStride = TWK_QUEUE_STRIDE(p.numPaths);
-  p.packedQueue = (dev->packedQueue && !p.hasCutout && (unsigned int) p.numPaths <= TWK_PACKED_PIXEL_MASK) ? 1 : 0;
-  p.slimSlotBits = slimSlotBits(dev);
+  p.iterationIndex = 0; // no kernel of this pass reads it, nor batchCount: the form's counts and sample numbers stand in their place
+  setPassPaths(dev, (int) numPaths);
   p.tileEntries = nullptr; p.tilesX = 0;
   const int maxDepth = dev->state.pathLengths[1];
   const TraceBuild build = traceBuild(dev, false);
   const int traceGrid = dev->numCUs * std::max(1, build.blocksPerCU);
-  int shadeGrid = (p.numPaths + TWK_SHADE_BLOCK - 1) / TWK_SHADE_BLOCK;
-  if (shadeGrid > dev->numCUs * TWK_SHADE_BLOCKS_PER_CU) shadeGrid = dev->numCUs * TWK_SHADE_BLOCKS_PER_CU;
+  const int shadeGrid = shadeGridBlocks(dev, p.numPaths);
 
   HIP_TRY(hipMemsetAsync(p.counters, 0, sizeof(unsigned int) * TWK_COUNTER_WORDS, dev->stream));
-  timedLaunchBegin(dev, TWK_KERNEL_GENERATE, dev->stream); launchGenerateActive(p, dev->d_active, dev->d_sampleCounts, dev->numActive, dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_GENERATE, dev->stream); launchGenerate(p, samples, dev->stream); timedLaunchEnd(dev, dev->stream);
   for (int depth = 0; depth < maxDepth; ++depth)
   {
     timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, depth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream);
     timedLaunchBegin(dev, TWK_KERNEL_SHADE, dev->stream); const int b = launchShade(p, depth, false, shadeGrid, dev->stream); dev->shadeBuilds[b >> 6] |= 1ull << (b & 63); timedLaunchEnd(dev, dev->stream);
   }
   if (maxDepth > 0) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, maxDepth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream); } // the shadow rays of the last shade
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulateActive(p, halfOutput(dev), dev->d_active, dev->d_sampleCounts, dev->numActive, samples, cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
+  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulate(p, halfOutput(dev), samples, cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
   HIP_TRY(hipGetLastError());
-  dev->lastPassCount = 0; // the radiance stream holds an adaptive pass's paths, not a uniform pass's
-  dev->adaptiveStarted = true;
-  return TWK_SUCCESS;
-}
-
-// Renders the handle's plan (twk_adaptive_plan, own-buffer form) as one wavefront pass of planPaths paths: a sibling of
-// renderAdaptivePass. generatePlannedKernel writes queue 0 (entry-major: entry k owns paths pathOffset[k] .. pathOffset[k + 1] - 1, at
-// the iterations the launch index's own count says), the trace and shade launches are renderPass's non-primary builds on one lane,
-// and accumulatePlannedKernel folds each entry's samples and advances its count by as many. The streams are allocated.
-static int renderPlannedPass(TwkDevice dev)
-{
-  refreshParams(dev);
-  LaunchParams& p = dev->params;
-  p.iterationIndex = 0; // no kernel of this pass reads it: the counts stand in its place
-  p.batchCount = 1;     // nor this: an entry's samples are what its two offsets say
-  p.numPaths = (int) dev->planPaths;
-  p.pathBase = 0;
-  p.queueStride = TWK_QUEUE_STRIDE(p.numPaths);
-  p.packedQueue = (dev->packedQueue && !p.hasCutout && (unsigned int) p.numPaths <= TWK_PACKED_PIXEL_MASK) ? 1 : 0;
-  p.slimSlotBits = slimSlotBits(dev);
-  p.tileEntries = nullptr; p.tilesX = 0;
-  const int maxDepth = dev->state.pathLengths[1];
-  const TraceBuild build = traceBuild(dev, false);
-  const int traceGrid = dev->numCUs * std::max(1, build.blocksPerCU);
-  int shadeGrid = (p.numPaths + TWK_SHADE_BLOCK - 1) / TWK_SHADE_BLOCK;
-  if (shadeGrid > dev->numCUs * TWK_SHADE_BLOCKS_PER_CU) shadeGrid = dev->numCUs * TWK_SHADE_BLOCKS_PER_CU;
-
-  HIP_TRY(hipMemsetAsync(p.counters, 0, sizeof(unsigned int) * TWK_COUNTER_WORDS, dev->stream));
-  timedLaunchBegin(dev, TWK_KERNEL_GENERATE, dev->stream); launchGeneratePlanned(p, dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive, dev->stream); timedLaunchEnd(dev, dev->stream);
-  for (int depth = 0; depth < maxDepth; ++depth)
-  {
-    timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, depth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream);
-    timedLaunchBegin(dev, TWK_KERNEL_SHADE, dev->stream); const int b = launchShade(p, depth, false, shadeGrid, dev->stream); dev->shadeBuilds[b >> 6] |= 1ull << (b & 63); timedLaunchEnd(dev, dev->stream);
-  }
-  if (maxDepth > 0) { timedLaunchBegin(dev, TWK_KERNEL_TRACE, dev->stream); launchTrace(p, maxDepth, false, build, traceGrid, dev->stream); timedLaunchEnd(dev, dev->stream); } // the shadow rays of the last shade
-  timedLaunchBegin(dev, TWK_KERNEL_ACCUM, dev->stream); launchAccumulatePlanned(p, halfOutput(dev), dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive, cascadeFold(dev), dev->stream); timedLaunchEnd(dev, dev->stream);
-  HIP_TRY(hipGetLastError());
-  dev->lastPassCount = 0; // the radiance stream holds a planned pass's paths, not a uniform pass's
+  dev->lastPassCount = 0; // the radiance stream holds a list pass's paths, not a uniform pass's
   dev->adaptiveStarted = true;
   return TWK_SUCCESS;
 }
@@ -566,7 +537,7 @@ try
   if (dev->numActive == 0) return TWK_SUCCESS;
   if ((rc = ensureStreamsForPaths(dev, (size_t) dev->numActive * (size_t) samples))) return rc;
   if (!dev->activeValid || !dev->d_moments) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive: the handle's buffers were allocated anew: twk_adaptive_select first");
-  return renderAdaptivePass(dev, samples);
+  return renderListPass(dev, ListedSamples{dev->d_active, dev->d_sampleCounts, dev->numActive, (unsigned int) samples}, (size_t) dev->numActive * (size_t) samples);
 }
 TWK_CATCH("twk_launch_adaptive")
 
@@ -585,7 +556,7 @@ try
   if ((rc = ensureStreamsForPaths(dev, (size_t) dev->planPaths))) return rc;
   if (!dev->planValid || !dev->d_moments) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_launch_adaptive_planned: the handle's buffers were allocated anew: twk_adaptive_plan first");
   dev->planValid = false; // the counts advance in the pass: the offsets no longer say what the picture needs
-  return renderPlannedPass(dev);
+  return renderListPass(dev, PlannedSamples{dev->d_planActive, dev->d_planOffsets, dev->d_sampleCounts, dev->planActive}, (size_t) dev->planPaths);
 }
 TWK_CATCH("twk_launch_adaptive_planned")
 

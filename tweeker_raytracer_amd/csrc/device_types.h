@@ -208,7 +208,7 @@ struct LaunchParams
   int     nextEventEstimation; // ≙ USE_NEXT_EVENT_ESTIMATION (shaders/config.h:50-52), a run-time switch here (twk_set_next_event_estimation): 0 = brute-force path tracing, no light sampling, no MIS weights
   int     debugExceptions;     // ≙ USE_DEBUG_EXCEPTIONS (config.h:54-56; raygeneration.cu:205-218): NaN / Inf / negative samples become super red / green / blue instead of NaN being dropped
   int     outputFrame;    // 1: `output` is a shared full W x H frame addressed by absolute pixel (ZeroCopy / PeerAccess strategies), 0: this device's packed launchWidth x H buffer
-  float4* output;         // running mean, RGBA32F; in half mode (twk_set_output_format TWK_OUTPUT_HALF4) the same bytes hold RGBA16F, which only accumulateHalfKernel addresses
+  float4* output;         // running mean, RGBA32F; in half mode (twk_set_output_format TWK_OUTPUT_HALF4) the same bytes hold RGBA16F, which accumulateKernel's Half4 builds address
   unsigned int* counters; // see CounterSlot
   unsigned long long* stats; // TwkLaunchStats as 7 u64, or nullptr
   float4* firstHit;       // debug capture (t, beta, gamma, prim) or nullptr

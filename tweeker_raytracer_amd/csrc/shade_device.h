@@ -899,8 +899,8 @@ TWK_D void shadePath(const LaunchParams& p, int depth, unsigned int pixel, const
 struct PrimaryRay { V3 origin, direction; unsigned int seed; bool active; };
 
 // The primary ray of sample `sampleIndex` of launch index `launchIndex` in a pass that starts at iteration `firstIteration`: the one
-// text both a uniform pass (primaryRay below: the pass's iteration index) and an adaptive pass (generateActivePath: the launch
-// index's own sample count stands where the iteration index does) take their rays from.
+// text every form of pass ("the samples of a thread" below) takes its rays from. In a uniform pass firstIteration is the pass's
+// iteration index; in the two list forms the launch index's own sample count stands in its place.
 TWK_D PrimaryRay primaryRayAt(const LaunchParams& p, const unsigned int launchIndex, const unsigned int firstIteration, const unsigned int sampleIndex)
 {
   const unsigned int lx = launchIndex % (unsigned int) p.launchWidth;
@@ -964,13 +964,106 @@ TWK_D PrimaryRay primaryRayAt(const LaunchParams& p, const unsigned int launchIn
   return r;
 }
 
-TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index)
+// ---------------------------------------------------------------------------------------------
+// The samples of a thread. A pass has one of three forms, and this table is all that differs between them:
+//
+//   form     entry point                  thread -> launch index  paths of that launch index                                   first iteration
+//   uniform  twk_launch                   index                   s * numPixels + index, s < batchCount                        iterationIndex
+//   listed   twk_launch_adaptive          active[k]               s * numActive + k,     s < samples                           counts[active[k]]
+//   planned  twk_launch_adaptive_planned  active[k]               pathOffset[k] + s,     s < pathOffset[k + 1] - pathOffset[k]  counts[active[k]]
+//
+// Each form is a small type that the generate and accumulate kernels take by value and that answers the table's two questions.
+// entry(p, t, e), the accumulate side: has thread t of entries(p) an entry, and if so which launch index it is and which paths and
+// iterations its samples are (SampleEntry). The two list forms also advance the launch index's sample count here, before the
+// launch index is asked for its pixel (accumulateTarget). path(p, index), the generate side: the launch index, first iteration and
+// sample index of path `index` of the launch (SamplePath: primaryRayAt's arguments). momentsAlways: the form runs only with the
+// moments on (its list was made from them), so its accumulate kernel has no build without them.
+struct SampleEntry { unsigned int launchIndex, firstPath, pathStride, firstIteration, samples; }; // sample s < samples: path firstPath + s * pathStride at iteration firstIteration + s
+struct SamplePath  { unsigned int launchIndex, firstIteration, sampleIndex; };
+
+struct UniformSamples
 {
-  const unsigned int path = index + (unsigned int) p.pathBase; // path of the whole pass; `index` counts within this launch's lane
-  const unsigned int sampleIndex = path / (unsigned int) p.numPixels;
-  const unsigned int launchIndex = path - sampleIndex * (unsigned int) p.numPixels;
-  return primaryRayAt(p, launchIndex, p.iterationIndex, sampleIndex);
+  static constexpr bool momentsAlways = false;
+  TWK_HD unsigned int entries(const LaunchParams& p) const { return (unsigned int) p.numPixels; }
+  TWK_D bool entry(const LaunchParams& p, const unsigned int t, SampleEntry& e) const
+  {
+    if (t >= entries(p)) return false;
+    e.launchIndex = t; e.firstPath = t; e.pathStride = (unsigned int) p.numPixels; e.firstIteration = p.iterationIndex; e.samples = (unsigned int) p.batchCount;
+    return true;
+  }
+  TWK_D SamplePath path(const LaunchParams& p, const unsigned int index) const
+  {
+    const unsigned int path = index + (unsigned int) p.pathBase; // path of the whole pass; `index` counts within this launch's lane
+    SamplePath s;
+    s.sampleIndex = path / (unsigned int) p.numPixels;
+    s.launchIndex = path - s.sampleIndex * (unsigned int) p.numPixels;
+    s.firstIteration = p.iterationIndex;
+    return s;
+  }
+};
+
+// `samples` samples of each of the numActive launch indices of the list `active` (adaptive_device.h); counts: every launch index's sample count
+struct ListedSamples
+{
+  static constexpr bool momentsAlways = true;
+  const unsigned int* active; unsigned int* counts; unsigned int numActive, samples;
+  TWK_HD unsigned int entries(const LaunchParams&) const { return numActive; }
+  TWK_D bool entry(const LaunchParams&, const unsigned int k, SampleEntry& e) const
+  {
+    if (k >= numActive) return false;
+    e.launchIndex = active[k]; e.firstPath = k; e.pathStride = numActive; e.firstIteration = counts[e.launchIndex]; e.samples = samples;
+    counts[e.launchIndex] = e.firstIteration + samples;
+    return true;
+  }
+  TWK_D SamplePath path(const LaunchParams&, const unsigned int index) const
+  {
+    SamplePath s;
+    s.sampleIndex = index / numActive;
+    s.launchIndex = active[index - s.sampleIndex * numActive];
+    s.firstIteration = counts[s.launchIndex];
+    return s;
+  }
+};
+
+// The plan's list (adaptive_plan_device.h): entry k of its numActive owns paths pathOffset[k] .. pathOffset[k + 1] - 1, entry-major
+struct PlannedSamples
+{
+  static constexpr bool momentsAlways = true;
+  const unsigned int* active; const unsigned int* pathOffset; unsigned int* counts; unsigned int numActive;
+  TWK_HD unsigned int entries(const LaunchParams&) const { return numActive; }
+  TWK_D bool entry(const LaunchParams&, const unsigned int k, SampleEntry& e) const
+  {
+    if (k >= numActive) return false;
+    e.launchIndex = active[k]; e.firstPath = pathOffset[k]; e.pathStride = 1u; e.firstIteration = counts[e.launchIndex]; e.samples = pathOffset[k + 1] - e.firstPath;
+    counts[e.launchIndex] = e.firstIteration + e.samples;
+    return true;
+  }
+  // The entry of a path is the last k with pathOffset[k] <= index: an upper-bound binary search over the numActive + 1 ascending
+  // words (at most 22 dependent reads of an array that stays in L2; entries have a budget of at least 1, so the offsets are
+  // strictly ascending).
+  TWK_D SamplePath path(const LaunchParams&, const unsigned int index) const
+  {
+    unsigned int low = 0u, high = numActive; // pathOffset[low] <= index < pathOffset[high]
+    while (high - low > 1u)
+    {
+      const unsigned int middle = low + ((high - low) >> 1);
+      if (pathOffset[middle] <= index) low = middle; else high = middle;
+    }
+    SamplePath s;
+    s.launchIndex = active[low];
+    s.firstIteration = counts[s.launchIndex];
+    s.sampleIndex = index - pathOffset[low];
+    return s;
+  }
+};
+
+template<typename Samples>
+TWK_D PrimaryRay primaryRay(const LaunchParams& p, const Samples& samples, const unsigned int index)
+{
+  const SamplePath s = samples.path(p, index);
+  return primaryRayAt(p, s.launchIndex, s.firstIteration, s.sampleIndex);
 }
+TWK_D PrimaryRay primaryRay(const LaunchParams& p, const unsigned int index) { return primaryRay(p, UniformSamples(), index); }
 
 // What generateKernel stores for path `index` whose primary ray is `ray`: the integrator's prologue and record `index` of queue 0.
 TWK_D void storePrimaryPath(const LaunchParams& p, const unsigned int index, const PrimaryRay& ray)
@@ -997,38 +1090,14 @@ TWK_D void storePrimaryPath(const LaunchParams& p, const unsigned int index, con
   if (index == 0) p.counters[0] = (unsigned int) p.numPaths;
 }
 
-// Body of generateKernel for path `index` of the launch (shade_kernels.hip; also what the host build of the kernels runs:
-// oracle/host_kernels.cpp).
-TWK_D void generatePath(const LaunchParams& p, const unsigned int index)
+// Body of generateKernel for path `index` of the launch, in the pass form `samples`; the uniform form under its own name is
+// also what the host build of the kernels runs (oracle/host_kernels.cpp).
+template<typename Samples>
+TWK_D void generatePath(const LaunchParams& p, const Samples& samples, const unsigned int index)
 {
-  storePrimaryPath(p, index, primaryRay(p, index));
+  storePrimaryPath(p, index, primaryRay(p, samples, index));
 }
-
-// Body of generateActiveKernel for path `index` of an adaptive pass (twk_launch_adaptive): sample index / numActive of the
-// index % numActive-th launch index of the active list, at the iteration that launch index's own sample count says.
-TWK_D void generateActivePath(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, const unsigned int numActive, const unsigned int index)
-{
-  const unsigned int sampleIndex = index / numActive;
-  const unsigned int launchIndex = active[index - sampleIndex * numActive];
-  storePrimaryPath(p, index, primaryRayAt(p, launchIndex, counts[launchIndex], sampleIndex));
-}
-
-// Body of generatePlannedKernel for path `index` of a planned adaptive pass (twk_launch_adaptive_planned). The paths are entry-major:
-// entry k of the plan's list owns paths pathOffset[k] .. pathOffset[k + 1] - 1 (adaptive_plan_device.h). The entry of a path is the
-// last k with pathOffset[k] <= index: an upper-bound binary search over the numActive + 1 ascending words (at most 22 dependent
-// reads of an array that stays in L2; entries have a budget of at least 1, so the offsets are strictly ascending). Its sample
-// index - pathOffset[k] runs at the iteration the launch index's own sample count says, as in generateActivePath.
-TWK_D void generatePlannedPath(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, const unsigned int numActive, const unsigned int index)
-{
-  unsigned int low = 0u, high = numActive; // pathOffset[low] <= index < pathOffset[high]
-  while (high - low > 1u)
-  {
-    const unsigned int middle = low + ((high - low) >> 1);
-    if (pathOffset[middle] <= index) low = middle; else high = middle;
-  }
-  const unsigned int launchIndex = active[low];
-  storePrimaryPath(p, index, primaryRayAt(p, launchIndex, counts[launchIndex], index - pathOffset[low]));
-}
+TWK_D void generatePath(const LaunchParams& p, const unsigned int index) { generatePath(p, UniformSamples(), index); }
 
 // Where launch index `index` accumulates: its slot of the packed tile buffer (single device, LocalCopy), or — shared frame of
 // the ZeroCopy / PeerAccess strategies — the pixel it maps to, as __raygen__path_tracer addresses sysData.outputBuffer
@@ -1046,17 +1115,18 @@ TWK_D bool accumulateTarget(const LaunchParams& p, const unsigned int index, siz
   return true;
 }
 
-// The buffers hold what they were given: RGBA32F (accumulateLaunchIndex). The RGBA16F build (shade_kernels.hip
-// accumulateHalfKernel) passes a functor that rounds to half and widens back.
-struct StoredAsFloat { TWK_HD float4 operator()(const float4 v) const { return v; } };
+// What a buffer of `Pixel`s would hold had it been given v: v itself in RGBA32F (float4); v rounded to half and widened back
+// in RGBA16F (pixel_formats.h Half4).
+template<typename Pixel> struct StoredAs { TWK_D float4 operator()(const float4 v) const { return widen(pixelOf<Pixel>(v)); } };
+using StoredAsFloat = StoredAs<float4>;
 
-// The per-sample fold of accumulateKernel (raygeneration.cu:205-253) over the batchCount samples of launch index `index`, in
+// The per-sample fold of accumulateKernel (raygeneration.cu:205-253) over the samples of one launch index in the pass, in
 // iteration order, on the running means dst / dstAlbedo / dstNormal as read from the buffers. After every folded sample the
 // means become `stored(...)` of themselves, what the buffers would hold had the sample been written by a launch of its own, so
 // that a batch equals batchCount separate launches in either output format. Returns whether any sample was folded.
 //
 // MOMENTS (twk_enable_moments; the MOMENTS builds of the accumulate kernels): the same read of every sample also folds the
-// luminance moments of launch index `index` into *moments = (mean, M2, n, 0), Welford's recurrence in f32, every operation
+// luminance moments of the launch index into *moments = (mean, M2, n, 0), Welford's recurrence in f32, every operation
 // rounded once, in this order — per KEPT sample (the r.w == 0 skip and the keep rule above it are the running mean's), in
 // iteration order, on the radiance as it is folded (the false colour under debugExceptions), before the lerp:
 //   l = (0.2126f r.x + 0.7152f r.y) + 0.0722f r.z                  (device_math.h luminance3: the denoiser's weights and order)
@@ -1068,7 +1138,7 @@ struct StoredAsFloat { TWK_HD float4 operator()(const float4 v) const { return v
 // CASCADE (twk_enable_cascade; the CASCADE builds of the accumulate kernels): the same read also splits the kept sample over the
 // launch index's brightness layers *cascade (cascade_device.h cascadeFoldSample: the complete definition), held in registers for
 // the pass. Neither build flag changes a bit of dst, dstAlbedo or dstNormal, nor one the other's words.
-// foldSample is the fold of ONE sample, the path `path` at iteration `iteration`; foldSamples and foldActiveSamples say which.
+// foldSample is the fold of ONE sample, the path `path` at iteration `iteration`; foldSamples says which.
 template<bool MOMENTS, bool CASCADE = false, typename Stored>
 TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned int iteration, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments,
                       const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
@@ -1119,63 +1189,78 @@ TWK_D bool foldSample(const LaunchParams& p, const size_t path, const unsigned i
   return true;
 }
 
-// The samples of a uniform pass: sample s of launch index `index` is path s * numPixels + index, at iteration iterationIndex + s.
+// The samples of entry `e` ("the samples of a thread" above), in iteration order.
 template<bool MOMENTS = false, bool CASCADE = false, typename Stored>
-TWK_D bool foldSamples(const LaunchParams& p, const unsigned int index, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments = nullptr,
+TWK_D bool foldSamples(const LaunchParams& p, const SampleEntry& e, float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments = nullptr,
                        const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
 {
   bool touched = false;
-  for (int s = 0; s < p.batchCount; ++s)
+  for (unsigned int s = 0; s < e.samples; ++s)
   {
-    if (foldSample<MOMENTS, CASCADE>(p, (size_t) s * p.numPixels + index, p.iterationIndex + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
+    if (foldSample<MOMENTS, CASCADE>(p, (size_t) e.firstPath + (size_t) s * e.pathStride, e.firstIteration + s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
   }
   return touched;
 }
 
-// The samples of an adaptive pass (twk_launch_adaptive) for entry k of its active list of numActive launch indices: sample s is
-// path s * numActive + k, at iteration count + s, where count is the launch index's own sample count before the pass.
-template<bool CASCADE = false, typename Stored>
-TWK_D bool foldActiveSamples(const LaunchParams& p, const unsigned int k, const unsigned int numActive, const unsigned int count, const int samples,
-                             float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments,
-                             const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
+// The layers of one launch index over a pass, for either build of the accumulate kernel: CascadeOn loads them at construction, hands
+// the fold its table and sums, and stores them; CascadeOff is empty and hands out null pointers that the CASCADE = false fold never reads.
+template<typename Cascade> struct CascadeFolding;
+template<> struct CascadeFolding<CascadeOff>
 {
-  bool touched = false;
-  for (int s = 0; s < samples; ++s)
-  {
-    if (foldSample<true, CASCADE>(p, (size_t) s * numActive + k, count + (unsigned int) s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
-  }
-  return touched;
-}
+  TWK_D CascadeFolding(const CascadeOff&, size_t, size_t) {}
+  TWK_D const CascadeConstants* constants() const { return nullptr; }
+  TWK_D CascadeSums* sums() { return nullptr; }
+  TWK_D void store() const {}
+};
+template<> struct CascadeFolding<CascadeOn>
+{
+  const CascadeOn& cascade; const size_t stride, index; CascadeSums s;
+  TWK_D CascadeFolding(const CascadeOn& c, size_t stride, size_t index) : cascade(c), stride(stride), index(index) { cascadeLoad(c.k, c.layers, stride, index, s); }
+  TWK_D const CascadeConstants* constants() const { return &cascade.k; }
+  TWK_D CascadeSums* sums() { return &s; }
+  TWK_D void store() const { cascadeStore(cascade.k, cascade.layers, stride, index, s); }
+};
 
-// The samples of a planned adaptive pass (twk_launch_adaptive_planned) for an entry whose paths start at `firstPath`: sample s of
-// its `samples` is path firstPath + s, at iteration count + s, where count is the launch index's own sample count before the pass.
-template<bool CASCADE = false, typename Stored>
-TWK_D bool foldPlannedSamples(const LaunchParams& p, const unsigned int firstPath, const unsigned int count, const unsigned int samples,
-                              float4& dst, float4& dstAlbedo, float4& dstNormal, const Stored stored, float4* moments,
-                              const CascadeConstants* cascadeConstants = nullptr, CascadeSums* cascade = nullptr)
+// Body of accumulateKernel for thread t of the pass form `samples` (raygeneration.cu:222-253; RGBA16F: Optix7Gui
+// raygeneration.cu:267-317): drop NaN samples, running mean into the output and AOV buffers of `Pixel`s, alpha 1. The means are
+// widened as they are read, folded in f32 — one lerp per sample in iteration order, after each of which they are what the buffers
+// would hold (StoredAs), so that a pass equals as many separate launches in either format — and written back as pixels: exact,
+// they are stored values already.
+// MOMENTS (LaunchParams::moments != nullptr): the same single read of every sample also folds the launch index's luminance
+// moments (foldSample), read and written once per pass, one more float4 each way; f32 in either format, never narrowed.
+// Cascade (CascadeOn: twk_enable_cascade; CascadeOff is an empty argument and adds no code): the same read also splits every kept
+// sample over the launch index's brightness layers (cascade_device.h). The layers are read once into registers before the fold and
+// written once after it, however many samples the pass folds; layer-major, so every load and store is a coalesced 16 B per lane.
+template<typename Pixel, bool MOMENTS, typename Samples, typename Cascade>
+TWK_D void accumulateEntry(const LaunchParams& p, const Samples& samples, const unsigned int t, const Cascade& cascade)
 {
-  bool touched = false;
-  for (unsigned int s = 0; s < samples; ++s)
-  {
-    if (foldSample<true, CASCADE>(p, (size_t) firstPath + s, count + s, dst, dstAlbedo, dstNormal, stored, moments, cascadeConstants, cascade)) touched = true;
-  }
-  return touched;
-}
-
-// Body of accumulateKernel for launch index `index` (raygeneration.cu:222-253): the RGBA32F output and AOV buffers.
-TWK_D void accumulateLaunchIndex(const LaunchParams& p, const unsigned int index)
-{
-  const bool aov = (p.aovAlbedo != nullptr);
+  SampleEntry e;
+  if (!samples.entry(p, t, e)) return;
+  const unsigned int index = e.launchIndex;
   size_t outIndex;
   if (!accumulateTarget(p, index, outIndex)) return;
-  float4 dst = p.output[outIndex];
-  float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (foldSamples(p, index, dst, dstAlbedo, dstNormal, StoredAsFloat()))
+  Pixel* const output = reinterpret_cast<Pixel*>(p.output);
+  Pixel* const aovAlbedo = reinterpret_cast<Pixel*>(p.aovAlbedo);
+  Pixel* const aovNormal = reinterpret_cast<Pixel*>(p.aovNormal);
+  const bool aov = (aovAlbedo != nullptr);
+  float4 dst = widen(output[outIndex]);
+  float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 moments = MOMENTS ? p.moments[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
+  if (foldSamples<MOMENTS, Cascade::on>(p, e, dst, dstAlbedo, dstNormal, StoredAs<Pixel>(), &moments, layers.constants(), layers.sums()))
   {
-    p.output[outIndex] = dst;
-    if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
+    output[outIndex] = pixelOf<Pixel>(dst);
+    if (aov) { aovAlbedo[index] = pixelOf<Pixel>(dstAlbedo); aovNormal[index] = pixelOf<Pixel>(dstNormal); }
+    if (MOMENTS) p.moments[index] = moments;
+    layers.store();
   }
+}
+
+// accumulateKernel's plain uniform build for launch index `index` (also what the host build of the kernels runs: oracle/host_kernels.cpp)
+TWK_D void accumulateLaunchIndex(const LaunchParams& p, const unsigned int index)
+{
+  accumulateEntry<float4, false>(p, UniformSamples(), index, CascadeOff());
 }
 
 } // namespace twk

@@ -6,10 +6,12 @@
 //                    light callables (bxdf_*.cu, light_sample.cu) and the integrator loop body after the
 //                    trace raygeneration.cu:91-146
 //   accumulateKernel NaN filter + running mean                              raygeneration.cu:222-253
-//                    (accumulateHalfKernel: Optix7Gui's RGBA16F buffers     raygeneration.cu:267-317)
+//                    (its Half4 builds: Optix7Gui's RGBA16F buffers         raygeneration.cu:267-317)
 //   compositorKernel compositor.cu:38-64 for all source devices at once
 // Per-path RNG draw order is the reference's: jitter rng2; per bounce the BSDF's draws, then NEE rng2
 // [+ rng when more than one light], then Russian roulette rng.
+// generateKernel and accumulateKernel are one kernel each for the three forms of a pass (uniform, listed, planned): what differs
+// between the forms is the `Samples` argument (shade_device.h "the samples of a thread").
 #include "shade_device.h"
 #include "pixel_formats.h"
 #include "../../include/tweeker_hip.h"
@@ -19,39 +21,21 @@
 #include <utility>
 
 namespace twk {
-// One thread per path = (sample, launch index): seed, jitter, lens shader, path state reset, primary ray into
-// queue 0. A pass renders batchCount consecutive iterations at once (path = sample * numPixels + launch index, so a
-// wave still covers 64 neighbouring pixels of one sample); sample s uses iterationIndex + s exactly as a launch of
-// its own would.
+// One thread per path: seed, jitter, lens shader, path state reset, primary ray into queue 0 (shade_device.h generatePath), the
+// same record whatever the form of the pass; `samples` says which launch index, iteration and sample the path is.
+// Uniform: a pass renders batchCount consecutive iterations at once (path = sample * numPixels + launch index, so a wave still
+// covers 64 neighbouring pixels of one sample); sample s uses iterationIndex + s exactly as a launch of its own would.
+// Listed (twk_launch_adaptive): path = sample * numActive + entry of the active list, at the iteration the launch index's own
+// sample count says. Planned (twk_launch_adaptive_planned): the paths are entry-major, so a wave's 64 paths are a few neighbouring
+// launch indices at consecutive iterations; the entry is found by a binary search of the plan's path offsets.
 // The seed index is the absolute pixel W*y + x for every device count (for one device this IS the
 // reference's formula raygeneration.cu:191; for several it makes tiled == single-device bit for bit).
-__global__ void __launch_bounds__(256) generateKernel(LaunchParams p)
+template<typename Samples>
+__global__ void __launch_bounds__(256) generateKernel(LaunchParams p, Samples samples)
 {
   const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
   if (index >= (unsigned int) p.numPaths) return;
-  generatePath(p, index);
-}
-
-// generateKernel of an adaptive pass (twk_launch_adaptive): one thread per path = (sample, entry of the active list). Queue 0 is
-// written exactly as generateKernel writes it; only the launch index (active[k]) and the iteration (counts[active[k]] + sample)
-// of the primary ray come from the lists (shade_device.h generateActivePath).
-__global__ void __launch_bounds__(256) generateActiveKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ counts, unsigned int numActive)
-{
-  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index >= (unsigned int) p.numPaths) return;
-  generateActivePath(p, active, counts, numActive, index);
-}
-
-// generateKernel of a planned adaptive pass (twk_launch_adaptive_planned): one thread per path. The paths are entry-major (entry k of
-// the plan owns paths pathOffset[k] .. pathOffset[k + 1] - 1), so a wave's 64 paths are a few neighbouring launch indices at
-// consecutive iterations; the entry is found by a binary search of pathOffset (shade_device.h generatePlannedPath). Queue 0 is
-// written exactly as generateKernel writes it.
-__global__ void __launch_bounds__(256) generatePlannedKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ pathOffset,
-                                                             const unsigned int* __restrict__ counts, unsigned int numActive)
-{
-  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index >= (unsigned int) p.numPaths) return;
-  generatePlannedPath(p, active, pathOffset, counts, numActive, index);
+  generatePath(p, samples, index);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -469,183 +453,14 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   }
 }
 
-// The layers of one launch index over a pass, for either build of an accumulate kernel: CascadeOn loads them at construction, hands
-// the fold its table and sums, and stores them; CascadeOff is empty and hands out null pointers that the CASCADE = false fold never reads.
-template<typename Cascade> struct CascadeFolding;
-template<> struct CascadeFolding<CascadeOff>
+// One thread per entry of the pass form `samples` — a launch index (uniform), an entry of the active list (listed) or of the plan
+// (planned) — folds the entry's samples onto the launch index's running means in `Pixel`s (float4, or Half4: RGBA16F), its
+// luminance moments (MOMENTS) and its cascade layers (Cascade): shade_device.h accumulateEntry, the one body of every build.
+// The two list forms also advance the launch index's sample count there; they run with the moments on only.
+template<typename Samples, typename Pixel, bool MOMENTS, typename Cascade>
+__global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p, Samples samples, Cascade cascade)
 {
-  TWK_D CascadeFolding(const CascadeOff&, size_t, size_t) {}
-  TWK_D const CascadeConstants* constants() const { return nullptr; }
-  TWK_D CascadeSums* sums() { return nullptr; }
-  TWK_D void store() const {}
-};
-template<> struct CascadeFolding<CascadeOn>
-{
-  const CascadeOn& cascade; const size_t stride, index; CascadeSums s;
-  TWK_D CascadeFolding(const CascadeOn& c, size_t stride, size_t index) : cascade(c), stride(stride), index(index) { cascadeLoad(c.k, c.layers, stride, index, s); }
-  TWK_D const CascadeConstants* constants() const { return &cascade.k; }
-  TWK_D CascadeSums* sums() { return &s; }
-  TWK_D void store() const { cascadeStore(cascade.k, cascade.layers, stride, index, s); }
-};
-
-// raygeneration.cu:222-253: drop NaN samples, running mean into the RGBA32F buffer, alpha 1. The samples of a batch
-// are folded in iteration order, one lerp each, so the float result equals batchCount separate launches.
-// MOMENTS (LaunchParams::moments != nullptr): the same single read of every sample also folds the launch index's luminance
-// moments (shade_device.h foldSamples), read and written once per pass, one more float4 each way.
-// Cascade (CascadeOn: twk_enable_cascade; CascadeOff is an empty argument and adds no code): the same read also splits every kept
-// sample over the launch index's brightness layers (cascade_device.h). The layers are read once into registers before the fold and
-// written once after it, however many samples the pass folds; layer-major, so every load and store is a coalesced 16 B per lane.
-template<bool MOMENTS, typename Cascade>
-__global__ void __launch_bounds__(256) accumulateKernel(LaunchParams p, Cascade cascade)
-{
-  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index >= (unsigned int) p.numPixels) return;
-  if constexpr (!MOMENTS && !Cascade::on) { accumulateLaunchIndex(p, index); return; }
-  else
-  {
-    const bool aov = (p.aovAlbedo != nullptr);
-    size_t outIndex;
-    if (!accumulateTarget(p, index, outIndex)) return;
-    float4 dst = p.output[outIndex];
-    float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 moments = MOMENTS ? p.moments[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
-    if (foldSamples<MOMENTS, Cascade::on>(p, index, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments, layers.constants(), layers.sums()))
-    {
-      p.output[outIndex] = dst;
-      if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
-      if (MOMENTS) p.moments[index] = moments;
-      layers.store();
-    }
-  }
-}
-
-// Optix7Gui's RGBA16F output: Half4, widen, narrow of pixel_formats.h
-struct StoredAsHalf { TWK_D float4 operator()(const float4 v) const { return widen(narrow(v)); } };
-
-// accumulateKernel on RGBA16F output and AOV buffers (raygeneration.cu:267-317): the lerp operand is the widened half and the
-// arithmetic the f32 expression of the float build, rounded once per folded sample (foldSamples).
-template<bool MOMENTS, typename Cascade>
-__global__ void __launch_bounds__(256) accumulateHalfKernel(LaunchParams p, Cascade cascade)
-{
-  const unsigned int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index >= (unsigned int) p.numPixels) return;
-  size_t outIndex;
-  if (!accumulateTarget(p, index, outIndex)) return;
-  Half4* output = reinterpret_cast<Half4*>(p.output);
-  Half4* aovAlbedo = reinterpret_cast<Half4*>(p.aovAlbedo);
-  Half4* aovNormal = reinterpret_cast<Half4*>(p.aovNormal);
-  const bool aov = (aovAlbedo != nullptr);
-  float4 dst = widen(output[outIndex]);
-  float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float4 moments = MOMENTS ? p.moments[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // f32 in half mode too: the samples' own luminance, never narrowed
-  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index); // f32 in half mode too
-  if (foldSamples<MOMENTS, Cascade::on>(p, index, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments, layers.constants(), layers.sums()))
-  {
-    output[outIndex] = narrow(dst); // dst is already a widened half: narrow() is exact here
-    if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
-    if (MOMENTS) p.moments[index] = moments;
-    layers.store();
-  }
-}
-
-// The accumulate kernel of an adaptive pass: one thread per entry k of the active list folds the `samples` samples of launch index
-// active[k] (paths s * numActive + k) onto its running means and moments with the fold of the kernels above (shade_device.h
-// foldSample), sample s at iteration counts[active[k]] + s, and advances the launch index's sample count. The moments are always
-// on here (the list was selected from them). HALF: the RGBA16F buffers, as accumulateHalfKernel addresses them.
-template<bool HALF, typename Cascade>
-__global__ void __launch_bounds__(256) accumulateActiveKernel(LaunchParams p, const unsigned int* __restrict__ active, unsigned int* __restrict__ counts, unsigned int numActive, int samples, Cascade cascade)
-{
-  const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= numActive) return;
-  const unsigned int index = active[k];
-  const unsigned int count = counts[index];
-  counts[index] = count + (unsigned int) samples;
-  size_t outIndex;
-  if (!accumulateTarget(p, index, outIndex)) return;
-  const bool aov = (p.aovAlbedo != nullptr);
-  float4 moments = p.moments[index];
-  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
-  if (HALF)
-  {
-    Half4* output = reinterpret_cast<Half4*>(p.output);
-    Half4* aovAlbedo = reinterpret_cast<Half4*>(p.aovAlbedo);
-    Half4* aovNormal = reinterpret_cast<Half4*>(p.aovNormal);
-    float4 dst = widen(output[outIndex]);
-    float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldActiveSamples<Cascade::on>(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments, layers.constants(), layers.sums()))
-    {
-      output[outIndex] = narrow(dst);
-      if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
-      p.moments[index] = moments;
-      layers.store();
-    }
-  }
-  else
-  {
-    float4 dst = p.output[outIndex];
-    float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldActiveSamples<Cascade::on>(p, k, numActive, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments, layers.constants(), layers.sums()))
-    {
-      p.output[outIndex] = dst;
-      if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
-      p.moments[index] = moments;
-      layers.store();
-    }
-  }
-}
-
-// The accumulate kernel of a planned adaptive pass: one thread per entry k of the plan folds the pathOffset[k + 1] - pathOffset[k]
-// samples of launch index active[k] (paths pathOffset[k] + s) onto its running means and moments with the fold of the kernels above,
-// sample s at iteration counts[active[k]] + s, and advances the launch index's sample count by as many. HALF: the RGBA16F buffers.
-template<bool HALF, typename Cascade>
-__global__ void __launch_bounds__(256) accumulatePlannedKernel(LaunchParams p, const unsigned int* __restrict__ active, const unsigned int* __restrict__ pathOffset,
-                                                               unsigned int* __restrict__ counts, unsigned int numActive, Cascade cascade)
-{
-  const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= numActive) return;
-  const unsigned int index = active[k];
-  const unsigned int firstPath = pathOffset[k], samples = pathOffset[k + 1] - firstPath;
-  const unsigned int count = counts[index];
-  counts[index] = count + samples;
-  size_t outIndex;
-  if (!accumulateTarget(p, index, outIndex)) return;
-  const bool aov = (p.aovAlbedo != nullptr);
-  float4 moments = p.moments[index];
-  CascadeFolding<Cascade> layers(cascade, (size_t) p.numPixels, index);
-  if (HALF)
-  {
-    Half4* output = reinterpret_cast<Half4*>(p.output);
-    Half4* aovAlbedo = reinterpret_cast<Half4*>(p.aovAlbedo);
-    Half4* aovNormal = reinterpret_cast<Half4*>(p.aovNormal);
-    float4 dst = widen(output[outIndex]);
-    float4 dstAlbedo = aov ? widen(aovAlbedo[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 dstNormal = aov ? widen(aovNormal[index]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldPlannedSamples<Cascade::on>(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsHalf(), &moments, layers.constants(), layers.sums()))
-    {
-      output[outIndex] = narrow(dst);
-      if (aov) { aovAlbedo[index] = narrow(dstAlbedo); aovNormal[index] = narrow(dstNormal); }
-      p.moments[index] = moments;
-      layers.store();
-    }
-  }
-  else
-  {
-    float4 dst = p.output[outIndex];
-    float4 dstAlbedo = aov ? p.aovAlbedo[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 dstNormal = aov ? p.aovNormal[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (foldPlannedSamples<Cascade::on>(p, firstPath, count, samples, dst, dstAlbedo, dstNormal, StoredAsFloat(), &moments, layers.constants(), layers.sums()))
-    {
-      p.output[outIndex] = dst;
-      if (aov) { p.aovAlbedo[index] = dstAlbedo; p.aovNormal[index] = dstNormal; }
-      p.moments[index] = moments;
-      layers.store();
-    }
-  }
+  accumulateEntry<Pixel, MOMENTS>(p, samples, blockIdx.x * blockDim.x + threadIdx.x, cascade);
 }
 
 // compositor.cu:38-64 for every source device in one launch: tiles is [deviceCount][H][launchWidth]. Pixel: float4 or Half4
@@ -780,46 +595,38 @@ void launchGatherProbe(const float4* table, unsigned int lines, int steps, float
   hipLaunchKernelGGL(gatherProbeKernel, dim3(gridBlocks), dim3(256), 0, stream, table, lines, steps, out);
 }
 
-void launchGenerate(const LaunchParams& p, hipStream_t stream)
+template<typename Samples>
+void launchGenerate(const LaunchParams& p, const Samples& samples, hipStream_t stream)
 {
-  hipLaunchKernelGGL(generateKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p);
-}
-void launchGenerateActive(const LaunchParams& p, const unsigned int* active, const unsigned int* counts, unsigned int numActive, hipStream_t stream)
-{
-  hipLaunchKernelGGL(generateActiveKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, active, counts, numActive);
+  hipLaunchKernelGGL(generateKernel<Samples>, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, samples);
 }
 
-// cascade.layers != nullptr (twk_enable_cascade): the CASCADE build of the accumulate kernel, here and in the two launchers below
-void launchAccumulateActive(const LaunchParams& p, bool half, const unsigned int* active, unsigned int* counts, unsigned int numActive, int samples, const CascadeOn& cascade, hipStream_t stream)
+// The build of accumulateKernel a pass runs, chosen here for every form: Pixel by the output format, Cascade by cascade.layers
+// != nullptr (twk_enable_cascade), MOMENTS by p.moments != nullptr — the list forms have no build without them.
+template<typename Samples, typename Pixel, typename Cascade>
+static void launchAccumulateBuild(const LaunchParams& p, const Samples& samples, const Cascade& cascade, hipStream_t stream)
 {
-  const dim3 grid((numActive + 255u) / 256u);
-  if (cascade.layers != nullptr)
+  const dim3 grid((samples.entries(p) + 255u) / 256u);
+  if constexpr (!Samples::momentsAlways)
   {
-    if (half) hipLaunchKernelGGL((accumulateActiveKernel<true, CascadeOn>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, cascade);
-    else      hipLaunchKernelGGL((accumulateActiveKernel<false, CascadeOn>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, cascade);
-    return;
+    if (p.moments == nullptr) { hipLaunchKernelGGL((accumulateKernel<Samples, Pixel, false, Cascade>), grid, dim3(256), 0, stream, p, samples, cascade); return; }
   }
-  if (half) hipLaunchKernelGGL((accumulateActiveKernel<true, CascadeOff>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, CascadeOff());
-  else      hipLaunchKernelGGL((accumulateActiveKernel<false, CascadeOff>), grid, dim3(256), 0, stream, p, active, counts, numActive, samples, CascadeOff());
+  hipLaunchKernelGGL((accumulateKernel<Samples, Pixel, true, Cascade>), grid, dim3(256), 0, stream, p, samples, cascade);
 }
-
-void launchGeneratePlanned(const LaunchParams& p, const unsigned int* active, const unsigned int* pathOffset, const unsigned int* counts, unsigned int numActive, hipStream_t stream)
+template<typename Samples>
+void launchAccumulate(const LaunchParams& p, bool half, const Samples& samples, const CascadeOn& cascade, hipStream_t stream)
 {
-  hipLaunchKernelGGL(generatePlannedKernel, dim3((p.numPaths + 255) / 256), dim3(256), 0, stream, p, active, pathOffset, counts, numActive);
+  const bool on = cascade.layers != nullptr;
+  if (half) { if (on) launchAccumulateBuild<Samples, Half4>(p, samples, cascade, stream);  else launchAccumulateBuild<Samples, Half4>(p, samples, CascadeOff(), stream); }
+  else      { if (on) launchAccumulateBuild<Samples, float4>(p, samples, cascade, stream); else launchAccumulateBuild<Samples, float4>(p, samples, CascadeOff(), stream); }
 }
-
-void launchAccumulatePlanned(const LaunchParams& p, bool half, const unsigned int* active, const unsigned int* pathOffset, unsigned int* counts, unsigned int numActive, const CascadeOn& cascade, hipStream_t stream)
-{
-  const dim3 grid((numActive + 255u) / 256u);
-  if (cascade.layers != nullptr)
-  {
-    if (half) hipLaunchKernelGGL((accumulatePlannedKernel<true, CascadeOn>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, cascade);
-    else      hipLaunchKernelGGL((accumulatePlannedKernel<false, CascadeOn>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, cascade);
-    return;
-  }
-  if (half) hipLaunchKernelGGL((accumulatePlannedKernel<true, CascadeOff>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, CascadeOff());
-  else      hipLaunchKernelGGL((accumulatePlannedKernel<false, CascadeOff>), grid, dim3(256), 0, stream, p, active, pathOffset, counts, numActive, CascadeOff());
-}
+// the three forms of a pass (device_handle.h declares the two templates; device_pass.hip launches these)
+template void launchGenerate(const LaunchParams&, const UniformSamples&, hipStream_t);
+template void launchGenerate(const LaunchParams&, const ListedSamples&, hipStream_t);
+template void launchGenerate(const LaunchParams&, const PlannedSamples&, hipStream_t);
+template void launchAccumulate(const LaunchParams&, bool, const UniformSamples&, const CascadeOn&, hipStream_t);
+template void launchAccumulate(const LaunchParams&, bool, const ListedSamples&, const CascadeOn&, hipStream_t);
+template void launchAccumulate(const LaunchParams&, bool, const PlannedSamples&, const CascadeOn&, hipStream_t);
 
 template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>
 static void launchShadeBuild(const LaunchParams& p, int depth, int gridBlocks, hipStream_t stream)
@@ -864,24 +671,6 @@ int launchShade(const LaunchParams& p, int depth, bool primary, int gridBlocks, 
   assert(launch != nullptr);
   launch(p, depth, gridBlocks, stream);
   return index;
-}
-template<bool MOMENTS, typename Cascade>
-static void launchAccumulateBuild(const LaunchParams& p, bool half, const Cascade& cascade, const dim3 grid, hipStream_t stream)
-{
-  if (half) hipLaunchKernelGGL((accumulateHalfKernel<MOMENTS, Cascade>), grid, dim3(256), 0, stream, p, cascade);
-  else      hipLaunchKernelGGL((accumulateKernel<MOMENTS, Cascade>), grid, dim3(256), 0, stream, p, cascade);
-}
-void launchAccumulate(const LaunchParams& p, bool half, const CascadeOn& cascade, hipStream_t stream)
-{
-  const dim3 grid((p.numPixels + 255) / 256);
-  if (cascade.layers != nullptr)
-  {
-    if (p.moments != nullptr) launchAccumulateBuild<true>(p, half, cascade, grid, stream);
-    else                      launchAccumulateBuild<false>(p, half, cascade, grid, stream);
-    return;
-  }
-  if (p.moments != nullptr) launchAccumulateBuild<true>(p, half, CascadeOff(), grid, stream);
-  else                      launchAccumulateBuild<false>(p, half, CascadeOff(), grid, stream);
 }
 // half: tiles and output are Half4
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,

@@ -30,10 +30,6 @@ geometryKernel(LaunchParams p, float4* __restrict__ geometry)
   }
 }
 
-template<typename Pixel> struct TemporalPixel;
-template<> struct TemporalPixel<float4> { static TWK_D float4 make(const float4 v) { return v; } };
-template<> struct TemporalPixel<Half4>  { static TWK_D Half4 make(const float4 v) { return narrow(v); } };
-
 // One thread per pixel. The current frame's three streams and the three outputs are coalesced 16-byte (RGBA16F: 8-byte) accesses;
 // the history is four neighbouring 16-byte gathers per stream around the reprojected position, the geometry first: colour and
 // moments are fetched only at the taps that belong to the surface.
@@ -77,7 +73,7 @@ __global__ void __launch_bounds__(256) temporalKernel(const Pixel* __restrict__ 
   {
     float4 c, m;
     temporalMerge(k, s, cur, mc, c, m);
-    if (colourOut) colourOut[p] = TemporalPixel<Pixel>::make(c);
+    if (colourOut) colourOut[p] = pixelOf<Pixel>(c);
     if (historyOut) historyOut[p] = c;
     if (momentsOut) momentsOut[p] = m;
   }

@@ -551,13 +551,50 @@ typedef struct TwkTemporalFrame { const void* colour; const void* moments; const
  * after that has no history: it copies the frame through and keeps it. The results go to internal buffers:
  * twk_get_temporal_device_pointers (colour in the output format, merged moments f32; either pair may be NULL), twk_read_temporal
  * (RGBA32F, widened exactly) and twk_read_temporal_moments. What it is not: see csrc/temporal_device.h — no motion vectors (the
- * scene is static between builds), no environment reprojection (a miss never has history), pinhole only, one device. */
+ * scene is static between builds), no environment reprojection (a miss never has history), pinhole only; a frame tiled over several
+ * devices is merged by twk_temporal_accumulate_assembled ("The temporal seam on several devices" below). */
 int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
                             int width, int height, void* colourOut, void* historyOut, void* momentsOut);
 int twk_temporal_reset(TwkDevice dev);
 int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colourBytes, void** moments, size_t* momentsBytes);
 int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats);         /* launchWidth*height*4 floats; synchronises */
 int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats);
+
+/* ---- The temporal seam on several devices — new calls, ABI stays 9, no existing struct, enum or constant changes; without them no
+ * kernel's code and no byte of any buffer changes -------------------------------------------------------------------------------
+ * A frame tiled over N handles (distribution 1) through the same loop: every handle traces the geometry of its own tile share
+ * (twk_render_geometry_tile), ONE twk_assemble_devices_with_geometry moves the planes and the geometry to the primary handle, and
+ * twk_temporal_accumulate_assembled merges the assembled frame there and keeps the history there. The loop of a frame:
+ *   on every handle: twk_update_camera(0); twk_set_sample_offset(frames x spp); twk_launch 0 .. spp-1; twk_render_geometry_tile;
+ *   on the primary: twk_assemble_devices_with_geometry(OUTPUT | MOMENTS [| CASCADE]); twk_temporal_accumulate_assembled;
+ *   twk_denoise_variance_sampled / twk_cascade_resolve on the merged buffers, as on one device.
+ * Everything a single handle gives for the same cameras, byte for byte (the renderer seeds by absolute pixel, the assembly moves
+ * bytes, the merge kernels are the same). INTEGRATION.md "The temporal seam on several devices". */
+
+/* twk_render_geometry for a handle whose buffers are packed tile buffers (distribution 1, several devices): ONE kernel, one element
+ * per launch index i = ly * launchWidth + lx. Its pixel column is x = twk_tile_column(lx, ly, tileSize, count, index); x >= width is
+ * padding and is written as a miss, (0, 0, 0, bits 0), without a ray; otherwise the ray through the centre of pixel (x, ly) is traced
+ * exactly as twk_render_geometry traces it and the same value is written to element i (twk_read_geometry,
+ * twk_get_geometry_device_pointer: launchWidth x height float4). On any other handle it IS twk_render_geometry. Refusals
+ * (TWK_ERROR_INVALID_STATE): those of twk_render_geometry except the packed tile buffer — before twk_build or twk_set_state, the
+ * geometry off, a lens shader other than the pinhole, a cutout texture in use. Definition: csrc/temporal_device.h. */
+int twk_render_geometry_tile(TwkDevice dev);
+
+/* twk_temporal_accumulate's own-buffer form on a tiled primary handle, with the planes it assembled as the current frame: colour =
+ * the assembled TWK_PLANE_OUTPUT, moments = the assembled TWK_PLANE_MOMENTS, geometry = the assembled geometry AOV
+ * (twk_assemble_with_geometry / twk_assemble_devices_with_geometry), camera = the primary's camera 0, width x height = the
+ * picture's. The history is the handle's own temporal state, which a tiled handle does not use otherwise, so the result is handed
+ * out by the existing calls, as width x height pixels: twk_get_temporal_device_pointers, twk_read_temporal,
+ * twk_read_temporal_moments; twk_temporal_reset drops it, and the first call after a reset or a resize copies the frame through.
+ * While twk_temporal_enable_cascade(1) is set on the primary it also merges the assembled TWK_PLANE_CASCADE layers
+ * (twk_get_temporal_cascade_device_pointer, twk_read_temporal_cascade: [layers][height][width]). No kernel of its own: the merge
+ * kernels run unchanged on W x H buffers. tp NULL: twk_temporal_defaults.
+ * TWK_ERROR_INVALID_VALUE: a NULL handle (before any HIP call), maxHistory < 1, a tolerance that is negative or not finite.
+ * TWK_ERROR_INVALID_STATE: before twk_set_state and twk_init_cameras; a handle that is not tiled (use twk_temporal_accumulate);
+ * moments or geometry off; cascade merging on without twk_enable_cascade; TWK_PLANE_OUTPUT, TWK_PLANE_MOMENTS, (with cascade
+ * merging) TWK_PLANE_CASCADE or the geometry not assembled, and an assembled geometry that is stale (the primary's camera, state
+ * or scene changed since) — the text names which. */
+int twk_temporal_accumulate_assembled(TwkDevice primary, const TwkTemporal* tp);
 
 /* ---- The noise estimate and the stopping rule — new calls, ABI stays 9, no existing struct changes -----------------------------
  * How far a progressive picture is from done, from the integrator's own samples: per launch index the RELATIVE STANDARD ERROR of
@@ -762,8 +799,8 @@ int twk_cascade_resolve_host(const TwkCascade* cp, const TwkCascadeResolve* rp, 
  * The complete definition is csrc/temporal_cascade_device.h; tests/temporal_cascade_restate.py restates it in numpy. What it is: a
  * linear, capped, bilinear carry-over of sums and counts. What it is NOT: exact counting — n (layer 0 .w) becomes a weighted, capped
  * count that is no integer, and the interpolation mixes the counts of neighbouring pixels; alpha and the luminance moments stay the
- * existing merge's business; no motion vectors, no environment reprojection (a miss never has history), pinhole only, one device,
- * no tiles; the paper's variance term is not reprojected; the noise estimate and the adaptive passes do not see the merged layers. */
+ * existing merge's business; no motion vectors, no environment reprojection (a miss never has history), pinhole only (tiles: the
+ * assembled layers of a tiled frame go through twk_temporal_accumulate_assembled); the paper's variance term is not reprojected; the noise estimate and the adaptive passes do not see the merged layers. */
 
 /* EXPLICIT form; asynchronous, one kernel on the handle's stream. currentLayers, historyLayers and layersOut are device buffers of
  * [cp->layers][width*height] float4 (the shape twk_get_cascade_device_pointer hands out and twk_cascade_resolve takes),
@@ -805,8 +842,8 @@ int twk_temporal_cascade_host(const TwkTemporal* tp, const TwkCascade* cp, const
  * pictures (the twk_denoise* calls with explicit buffers, twk_cascade_resolve with explicit layers, twk_estimate_noise with explicit
  * moments) has something to work on. The map is twk_tile_column's; the complete definition is csrc/assemble_device.h and
  * tests/assemble_restate.py restates it in numpy. Padding columns (x >= width) are neither read nor written. What it is NOT: a
- * scatter back to the tiles (temporal accumulation, adaptive selection and planning stay per device), an assembly of the geometry
- * AOV, or a path for the shared-frame strategies (their beauty is already whole, their other planes are not).
+ * scatter back to the tiles (adaptive selection and planning stay per device), a seventh plane for the geometry AOV (the
+ * _with_geometry forms below assemble it), or a path for the shared-frame strategies (their beauty is already whole, their other planes are not).
  *   plane                     element                                   assembled buffer
  *   TWK_PLANE_OUTPUT          the output format's pixel, 16 or 8 B       [H][W]
  *   TWK_PLANE_ALBEDO/NORMAL   the output format's pixel, 16 or 8 B       [H][W]
@@ -843,6 +880,24 @@ int twk_assemble_devices(TwkDevice primary, unsigned int planeMask, const TwkDev
  * the format, or twk_enable_cascade changed the layers: those drop every assembled buffer. */
 int twk_get_assembled_device_pointer(TwkDevice primary, int plane, void** dptr, size_t* bytes);
 int twk_read_assembled(TwkDevice primary, int plane, void* host, size_t bytes);
+/* The same two forms with the geometry AOV of every tile share (twk_render_geometry_tile) in the same ONE launch: further entries of
+ * the same table (16-byte elements, one layer), the same event ordering, peer access and staging. The geometry is no seventh plane
+ * (TWK_PLANE_COUNT stays 6, bit 6 stays unknown): it has an assembled W x H float4 buffer of its own on primary,
+ * twk_get_assembled_geometry_device_pointer / twk_read_assembled_geometry (numFloats = width*height*4; synchronises). That buffer
+ * is freed whenever the other assembled buffers are, and is marked stale — the two getters and twk_temporal_accumulate_assembled
+ * refuse it — by whatever invalidates primary's own geometry AOV: a change of its camera 0, state or scene. planeMask may be 0 here:
+ * the geometry alone; otherwise it means what it means above.
+ * twk_assemble_with_geometry: geometrySources[d] is device d's packed launchWidth x H geometry, addressable from primary's device.
+ * twk_assemble_devices_with_geometry: the handles' own geometry buffers.
+ * Beyond the refusals above. TWK_ERROR_INVALID_STATE: the geometry off on primary (both forms) or on some handle; in the handle
+ * form, a handle whose geometry is not valid (no twk_render_geometry_tile since its camera, state or scene changed).
+ * TWK_ERROR_INVALID_VALUE: NULL geometrySources or a NULL entry of it; in the handle form, a handle whose camera 0 is not
+ * primary's, byte for byte. The explicit form cannot see the sources' cameras or age: that is the caller's to keep.
+ * There is no twk_assemble_geometry_host: twk_assemble_host with elementBytes 16 and layers 1 is that. */
+int twk_assemble_with_geometry(TwkDevice primary, unsigned int planeMask, const TwkAssemblySource* sources, const void* const* geometrySources, int deviceCount);
+int twk_assemble_devices_with_geometry(TwkDevice primary, unsigned int planeMask, const TwkDevice* devices, int count);
+int twk_get_assembled_geometry_device_pointer(TwkDevice primary, void** dptr, size_t* bytes);
+int twk_read_assembled_geometry(TwkDevice primary, float* host, size_t numFloats);
 /* Host only, no handle: the same definition over host arrays. sources[d] is device d's [layers][height][launchWidth] elements of
  * elementBytes (4, 8 or 16) with launchWidth as twk_set_state derives it: width for one device, else twk_launch_width(width,
  * tileSize[0], deviceCount); destination is [layers][height][width] elements, of which exactly the in-picture ones are written.
@@ -994,6 +1049,16 @@ int twk_app_get_cascade(TwkApp app, int* enabled, TwkCascade* cp, TwkCascadeReso
  * devices and strategy 3, rtigo3_hip -m 1 assembles the planes its post steps need with one twk_assemble_devices and runs them on
  * the assembled frame (INTEGRATION.md "Assembling a tiled frame"); with strategy 1 or 2 it refuses the run. */
 int twk_app_get_tile_assembly(TwkApp app, int* enabled);
+/* The moving-camera loop of rtigo3_hip -m 1: "temporalAccumulation 0|1" (default 0), "temporalFrames n" (1..4096, default 1),
+ * "temporalOrbitStep f" (the fraction of a full turn added to the camera's phi per frame; finite; default
+ * TWK_TEMPORAL_ORBIT_STEP, provisional), "temporalMaxHistory n" (>= 1) and "temporalPositionTolerance t" (>= 0, finite; defaults:
+ * twk_temporal_defaults). A value outside its range drops the line with a warning; the keys are written back only when they differ
+ * from off / the defaults. With the key on, frame f = 0..frames-1 renders samplesSqrt^2 iterations from the camera at phi + f x
+ * step under the sample offset f x samplesSqrt^2, renders the geometry and merges (on several devices: tile shares, one assembly
+ * with geometry, the assembled merge); INTEGRATION.md "The temporal seam on several devices". twk_app_init_device enables moments
+ * and geometry when the key is on. */
+#define TWK_TEMPORAL_ORBIT_STEP 0.001f
+int twk_app_get_temporal(TwkApp app, int* enabled, TwkTemporal* tp, int* frames, float* orbitStep);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

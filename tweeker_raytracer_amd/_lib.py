@@ -272,6 +272,8 @@ SYMBOLS = [
     "twk_get_resolved_device_pointer", "twk_read_resolved", "twk_cascade_fold_host", "twk_cascade_resolve_host", "twk_app_get_cascade",
     "twk_temporal_accumulate_cascade", "twk_temporal_enable_cascade", "twk_get_temporal_cascade_device_pointer", "twk_read_temporal_cascade", "twk_temporal_cascade_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
+    "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",
+    "twk_read_assembled_geometry", "twk_temporal_accumulate_assembled", "twk_app_get_temporal",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

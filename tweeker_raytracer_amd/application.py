@@ -157,6 +157,17 @@ class Application:
         return bool(on.value)
 
     @property
+    def temporal(self):
+        """(enabled, Temporal, frames, orbitStep) from "temporalAccumulation", "temporalMaxHistory", "temporalPositionTolerance",
+        "temporalFrames", "temporalOrbitStep" of the system description: the moving-camera loop of rtigo3_hip -m 1 — frame f renders
+        samplesSqrt² iterations from the camera at phi + f x orbitStep and merges them into the frames before it
+        (Device.temporalAccumulate; on several devices renderGeometryTile, assembleWithGeometry, temporalAccumulateAssembled).
+        initDevice enables the device's moments and geometry when the key is on."""
+        on, tp, n, step = C.c_int(0), L.Temporal(), C.c_int(0), C.c_float(0)
+        L.check(L.lib.twk_app_get_temporal(self._h, C.byref(on), C.byref(tp), C.byref(n), C.byref(step)))
+        return bool(on.value), tp, n.value, step.value
+
+    @property
     def fireflyCascade(self):
         """(enabled, Cascade, CascadeResolve) from "fireflyCascade", "fireflyCascadeLayers", "fireflyCascadeStart",
         "fireflyCascadeBase", "fireflyCascadeKappa" of the system description; initDevice enables the device's cascade when the key

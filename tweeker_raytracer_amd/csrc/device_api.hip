@@ -302,7 +302,7 @@ try
       was.tileSize[1] != s->tileSize[1] || was.distribution != s->distribution || dev->launchWidth != launchWidth)
     dropAccumulations(dev);
   dev->state = *s; dev->launchWidth = launchWidth;
-  dev->stateSet = true; dev->geometryValid = false; dropAdaptive(dev);
+  dev->stateSet = true; staleGeometry(dev); dropAdaptive(dev);
   const size_t needBytes = (size_t) (dev->outputFrame ? s->resolution[0] : dev->launchWidth) * s->resolution[1] * pixelBytes(dev);
   if (dev->d_outputExternal && dev->outputExternalBytes < needBytes)
   {
@@ -318,7 +318,7 @@ try
   int rc = activate(dev, "twk_init_cameras"); if (rc) return rc;
   if (!c || count < 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_init_cameras: at least one camera is required");
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->cameras.assign(c, c + count); dev->geometryValid = false;
+  dev->cameras.assign(c, c + count); staleGeometry(dev);
   if (!dev->d_camera) HIP_TRY(hipMalloc(&dev->d_camera, sizeof(TwkCameraDefinition)));
   HIP_TRY(hipMemcpyAsync(dev->d_camera, dev->cameras.data(), sizeof(TwkCameraDefinition), hipMemcpyHostToDevice, dev->stream)); // the lens shaders read cameraDefinitions[0]
   return TWK_SUCCESS;
@@ -332,7 +332,7 @@ try
   if (!c || idCamera < 0 || idCamera >= (int) dev->cameras.size()) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_update_camera: bad camera id");
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->cameras[idCamera] = *c;
-  if (idCamera == 0) dev->geometryValid = false;
+  if (idCamera == 0) staleGeometry(dev);
   if (idCamera == 0) HIP_TRY(hipMemcpyAsync(dev->d_camera, dev->cameras.data(), sizeof(TwkCameraDefinition), hipMemcpyHostToDevice, dev->stream));
   return TWK_SUCCESS;
 }
@@ -582,7 +582,7 @@ try
 {
   int rc = activate(dev, "twk_enable_geometry"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->geometryEnabled = (enable != 0); dev->geometryValid = false;
+  dev->geometryEnabled = (enable != 0); staleGeometry(dev);
   if (!dev->geometryEnabled) { freeDevice(dev->d_geometry); dev->geometryPixels = 0; return TWK_SUCCESS; } // enabled again: a zeroed buffer
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first use after twk_set_state
 }

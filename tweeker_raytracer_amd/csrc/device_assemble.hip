@@ -1,6 +1,8 @@
 // Assembling a tiled frame behind the C ABI (assemble_device.h: the definition): the assembled buffers a handle owns and what drops
 // them, the table of a launch (assemble_kernels.hip), the explicit form for gathered blocks (twk_assemble), the in-process form over
 // the handles' own buffers with its stream ordering, peer access and staging (twk_assemble_devices), the readers and the host-only form.
+// twk_assemble_with_geometry and twk_assemble_devices_with_geometry are the same two forms with the geometry AOV of every tile share
+// (twk_render_geometry_tile) as further entries of the same table: one launch, an assembled buffer of its own beside the six planes'.
 #include "device_handle.h"
 
 #include <algorithm>
@@ -41,8 +43,12 @@ static const char* planeSwitchOff(TwkDevice dev, int plane)
 void twk::dropAssembled(TwkDevice dev)
 {
   for (int p = 0; p < TWK_PLANE_COUNT; ++p) { freeDevice(dev->d_assembled[p]); dev->assembledBytes[p] = 0; dev->assembledValid[p] = false; }
+  freeDevice(dev->d_assembledGeometry); dev->assembledGeometryBytes = 0; dev->assembledGeometryValid = false;
   freeDevice(dev->d_assembleStage); dev->assembleStageBytes = 0;
 }
+
+// Bytes of the geometry AOV as `columns` x height float4
+static size_t geometryBytes(TwkDevice dev, int columns) { return (size_t) columns * (size_t) dev->state.resolution[1] * sizeof(float4); }
 
 static AssembleShape assembleShape(TwkDevice dev)
 {
@@ -52,23 +58,25 @@ static AssembleShape assembleShape(TwkDevice dev)
   return s;
 }
 
-// What both forms refuse of primary alone, without a HIP call
-static int refusePrimary(const char* name, TwkDevice primary, unsigned int planeMask)
+// What both forms refuse of primary alone, without a HIP call. withGeometry: the geometry AOV is assembled too, an empty mask is legal
+static int refusePrimary(const char* name, TwkDevice primary, unsigned int planeMask, bool withGeometry)
 {
   const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
-  if (planeMask == 0 || (planeMask & ~kAllPlanes)) return refuse(TWK_ERROR_INVALID_VALUE, "the plane mask is empty or names an unknown plane");
+  if ((planeMask == 0 && !withGeometry) || (planeMask & ~kAllPlanes)) return refuse(TWK_ERROR_INVALID_VALUE, withGeometry ? "the plane mask names an unknown plane" : "the plane mask is empty or names an unknown plane");
   if (!primary->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
   if (!primary->state.distribution && 1 < primary->count) return refuse(TWK_ERROR_INVALID_STATE, "distribution 0 with several devices: every handle holds the whole frame, there are no tiles to assemble");
   if ((size_t) primary->state.resolution[1] > (size_t) 65535 * 4) return refuse(TWK_ERROR_INVALID_VALUE, "the height exceeds what one launch covers");
   for (int p = 0; p < TWK_PLANE_COUNT; ++p)
     if ((planeMask >> p) & 1u)
       if (const char* off = planeSwitchOff(primary, p)) return refuse(TWK_ERROR_INVALID_STATE, std::string(kPlaneNames[p]) + " needs " + off + "(1) on the primary handle");
+  if (withGeometry && !primary->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV needs twk_enable_geometry(1) on the primary handle");
   return TWK_SUCCESS;
 }
 
 // Allocates primary's assembled buffers of the requested planes, builds the table and launches; sources[d]: device index d's
-// packed buffers, addressable from primary's device. primary is active.
-static int assembleLaunch(TwkDevice primary, unsigned int planeMask, const std::vector<TwkAssemblySource>& sources)
+// packed buffers, addressable from primary's device. geometry: nullptr, or device index d's packed geometry AOV, which goes out as
+// further entries of the same table. primary is active.
+static int assembleLaunch(TwkDevice primary, unsigned int planeMask, const std::vector<TwkAssemblySource>& sources, const std::vector<const void*>* geometry = nullptr)
 {
   for (int p = 0; p < TWK_PLANE_COUNT; ++p)
   {
@@ -79,6 +87,17 @@ static int assembleLaunch(TwkDevice primary, unsigned int planeMask, const std::
     freeDevice(primary->d_assembled[p]); primary->assembledBytes[p] = 0; primary->assembledValid[p] = false;
     HIP_TRY(hipMalloc(&primary->d_assembled[p], bytes));
     primary->assembledBytes[p] = bytes;
+  }
+  if (geometry)
+  {
+    const size_t bytes = geometryBytes(primary, primary->state.resolution[0]);
+    if (!primary->d_assembledGeometry || primary->assembledGeometryBytes != bytes)
+    {
+      HIP_TRY(hipStreamSynchronize(primary->stream));
+      freeDevice(primary->d_assembledGeometry); primary->assembledGeometryBytes = 0; primary->assembledGeometryValid = false;
+      HIP_TRY(hipMalloc(&primary->d_assembledGeometry, bytes));
+      primary->assembledGeometryBytes = bytes;
+    }
   }
   const AssembleShape s = assembleShape(primary);
   AssembleTable table;
@@ -106,12 +125,29 @@ static int assembleLaunch(TwkDevice primary, unsigned int planeMask, const std::
         }
       }
   }
+  if (geometry)
+    for (int d = 0; d < s.deviceCount; ++d)
+    {
+      AssembleEntry& e = table.entry[used];
+      e.source       = (*geometry)[(size_t) d];
+      e.destination  = primary->d_assembledGeometry;
+      e.device       = (unsigned int) d;
+      e.elementShift = 4;
+      e.groupShift   = assembleGroupShift(s, 4, e.source, e.destination);
+      if (++used == TWK_ASSEMBLE_MAX_ENTRIES)
+      {
+        launchAssemble(s, table, used, primary->stream);
+        HIP_TRY(hipGetLastError());
+        used = 0;
+      }
+    }
   if (used)
   {
     launchAssemble(s, table, used, primary->stream);
     HIP_TRY(hipGetLastError());
   }
   for (int p = 0; p < TWK_PLANE_COUNT; ++p) if ((planeMask >> p) & 1u) primary->assembledValid[p] = true;
+  if (geometry) primary->assembledGeometryValid = true;
   return TWK_SUCCESS;
 }
 
@@ -131,34 +167,38 @@ static const void* ownPlane(TwkDevice dev, int plane)
 
 static bool sameCascade(const TwkCascade& a, const TwkCascade& b) { return a.layers == b.layers && asUint(a.start) == asUint(b.start) && asUint(a.base) == asUint(b.base); }
 
-extern "C" {
-
-int twk_assemble(TwkDevice primary, unsigned int planeMask, const TwkAssemblySource* sources, int deviceCount)
-try
+// twk_assemble (geometrySources unused, withGeometry false) and twk_assemble_with_geometry
+static int assembleExplicit(const char* name, TwkDevice primary, unsigned int planeMask, const TwkAssemblySource* sources, const void* const* geometrySources, int deviceCount, bool withGeometry)
 {
-  const char* name = "twk_assemble";
   const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
   if (!primary) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
-  int rc = refusePrimary(name, primary, planeMask); if (rc) return rc;
-  if (!sources) return refuse(TWK_ERROR_INVALID_VALUE, "NULL sources");
+  int rc = refusePrimary(name, primary, planeMask, withGeometry); if (rc) return rc;
+  if (!sources && planeMask) return refuse(TWK_ERROR_INVALID_VALUE, "NULL sources");
+  if (withGeometry && !geometrySources) return refuse(TWK_ERROR_INVALID_VALUE, "NULL geometry sources");
   if (deviceCount != primary->count) return refuse(TWK_ERROR_INVALID_VALUE, "deviceCount must be the primary handle's device count");
   for (int d = 0; d < deviceCount; ++d)
+  {
     for (int p = 0; p < TWK_PLANE_COUNT; ++p)
       if (((planeMask >> p) & 1u) && !sources[d].plane[p]) return refuse(TWK_ERROR_INVALID_VALUE, std::string("NULL source of ") + kPlaneNames[p] + " for device " + std::to_string(d));
+    if (withGeometry && !geometrySources[d]) return refuse(TWK_ERROR_INVALID_VALUE, "NULL geometry source for device " + std::to_string(d));
+  }
   if ((rc = activate(primary, name))) return rc;
-  return assembleLaunch(primary, planeMask, std::vector<TwkAssemblySource>(sources, sources + deviceCount));
+  std::vector<TwkAssemblySource> planes((size_t) deviceCount);
+  if (planeMask) planes.assign(sources, sources + deviceCount);
+  else memset(planes.data(), 0, planes.size() * sizeof(TwkAssemblySource));
+  if (!withGeometry) return assembleLaunch(primary, planeMask, planes);
+  const std::vector<const void*> geometry(geometrySources, geometrySources + deviceCount);
+  return assembleLaunch(primary, planeMask, planes, &geometry);
 }
-TWK_CATCH("twk_assemble")
 
-int twk_assemble_devices(TwkDevice primary, unsigned int planeMask, const TwkDevice* devices, int count)
-try
+// twk_assemble_devices (withGeometry false) and twk_assemble_devices_with_geometry
+static int assembleDevices(const char* name, TwkDevice primary, unsigned int planeMask, const TwkDevice* devices, int count, bool withGeometry)
 {
-  const char* name = "twk_assemble_devices";
   const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
   if (!primary) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
   if (!devices || count < 1) return refuse(TWK_ERROR_INVALID_VALUE, "NULL devices");
   for (int i = 0; i < count; ++i) if (!devices[i]) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle among the devices");
-  int rc = refusePrimary(name, primary, planeMask); if (rc) return rc;
+  int rc = refusePrimary(name, primary, planeMask, withGeometry); if (rc) return rc;
   if (count != primary->count) return refuse(TWK_ERROR_INVALID_VALUE, "count must be the primary handle's device count");
   std::vector<TwkDevice> byIndex((size_t) count, nullptr);
   for (int i = 0; i < count; ++i)
@@ -179,6 +219,12 @@ try
         if (const char* off = planeSwitchOff(dev, p)) return refuse(TWK_ERROR_INVALID_STATE, std::string(kPlaneNames[p]) + " needs " + off + "(1) on every handle");
     if ((planeMask & TWK_PLANE_BIT(TWK_PLANE_OUTPUT)) && dev->d_outputExternal && dev->outputFrame)
       return refuse(TWK_ERROR_INVALID_STATE, "a handle renders into a shared frame (twk_set_shared_frame): its beauty is not a packed tile buffer");
+    if (!withGeometry) continue;
+    if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV needs twk_enable_geometry(1) on every handle");
+    if (!dev->geometryValid || !dev->d_geometry)
+      return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV of the handle with index " + std::to_string(dev->index) + " is older than its camera, state or scene: twk_render_geometry_tile first");
+    if (dev->cameras.empty() || primary->cameras.empty() || memcmp(&dev->cameras[0], &primary->cameras[0], sizeof(TwkCameraDefinition)) != 0)
+      return refuse(TWK_ERROR_INVALID_VALUE, "camera 0 of the handle with index " + std::to_string(dev->index) + " is not the primary handle's: the tile shares would be of different views");
   }
 
   // every source: recorded launches rendered, buffers allocated, counts current, then an event on its stream
@@ -216,6 +262,7 @@ try
     }
     staged[(size_t) d] = stage ? 1 : 0;
     if (stage) for (int p = 0; p < TWK_PLANE_COUNT; ++p) if ((planeMask >> p) & 1u) stageBytes += segment(planeBytes(primary, p, primary->launchWidth));
+    if (stage && withGeometry) stageBytes += segment(geometryBytes(primary, primary->launchWidth));
   }
   if (stageBytes > primary->assembleStageBytes)
   {
@@ -225,6 +272,7 @@ try
     primary->assembleStageBytes = stageBytes;
   }
   std::vector<TwkAssemblySource> sources((size_t) count);
+  std::vector<const void*> geometry((size_t) count, nullptr);
   size_t offset = 0;
   for (int d = 0; d < count; ++d)
   {
@@ -243,8 +291,17 @@ try
       sources[(size_t) d].plane[p] = to;
       offset += segment(bytes);
     }
+    if (!withGeometry) continue;
+    geometry[(size_t) d] = dev->d_geometry;
+    if (!staged[(size_t) d]) continue;
+    const size_t bytes = geometryBytes(primary, primary->launchWidth);
+    char* to = static_cast<char*>(primary->d_assembleStage) + offset;
+    if (dev->ordinal == primary->ordinal) HIP_TRY(hipMemcpyAsync(to, dev->d_geometry, bytes, hipMemcpyDeviceToDevice, primary->stream));
+    else                                  HIP_TRY(hipMemcpyPeerAsync(to, primary->ordinal, dev->d_geometry, dev->ordinal, bytes, primary->stream));
+    geometry[(size_t) d] = to;
+    offset += segment(bytes);
   }
-  if ((rc = assembleLaunch(primary, planeMask, sources))) return rc;
+  if ((rc = assembleLaunch(primary, planeMask, sources, withGeometry ? &geometry : nullptr))) return rc;
 
   // the sources render on only once their buffers have been read
   bool others = false;
@@ -257,7 +314,36 @@ try
   }
   return TWK_SUCCESS;
 }
+
+extern "C" {
+
+int twk_assemble(TwkDevice primary, unsigned int planeMask, const TwkAssemblySource* sources, int deviceCount)
+try
+{
+  return assembleExplicit("twk_assemble", primary, planeMask, sources, nullptr, deviceCount, false);
+}
+TWK_CATCH("twk_assemble")
+
+int twk_assemble_devices(TwkDevice primary, unsigned int planeMask, const TwkDevice* devices, int count)
+try
+{
+  return assembleDevices("twk_assemble_devices", primary, planeMask, devices, count, false);
+}
 TWK_CATCH("twk_assemble_devices")
+
+int twk_assemble_with_geometry(TwkDevice primary, unsigned int planeMask, const TwkAssemblySource* sources, const void* const* geometrySources, int deviceCount)
+try
+{
+  return assembleExplicit("twk_assemble_with_geometry", primary, planeMask, sources, geometrySources, deviceCount, true);
+}
+TWK_CATCH("twk_assemble_with_geometry")
+
+int twk_assemble_devices_with_geometry(TwkDevice primary, unsigned int planeMask, const TwkDevice* devices, int count)
+try
+{
+  return assembleDevices("twk_assemble_devices_with_geometry", primary, planeMask, devices, count, true);
+}
+TWK_CATCH("twk_assemble_devices_with_geometry")
 
 int twk_get_assembled_device_pointer(TwkDevice primary, int plane, void** dptr, size_t* bytes)
 try
@@ -288,6 +374,36 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_read_assembled")
+
+int twk_get_assembled_geometry_device_pointer(TwkDevice primary, void** dptr, size_t* bytes)
+try
+{
+  const char* name = "twk_get_assembled_geometry_device_pointer";
+  if (!primary) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL device handle");
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL argument");
+  if (!primary->assembledGeometryValid || !primary->d_assembledGeometry)
+    return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": the geometry AOV has not been assembled since the handle's frame last changed shape or its camera, state or scene changed");
+  *dptr = primary->d_assembledGeometry;
+  if (bytes) *bytes = primary->assembledGeometryBytes;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_assembled_geometry_device_pointer")
+
+int twk_read_assembled_geometry(TwkDevice primary, float* host, size_t numFloats)
+try
+{
+  const char* name = "twk_read_assembled_geometry";
+  if (!primary) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL device handle");
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL buffer");
+  if (!primary->assembledGeometryValid || !primary->d_assembledGeometry)
+    return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": the geometry AOV has not been assembled since the handle's frame last changed shape or its camera, state or scene changed");
+  if (numFloats * sizeof(float) != primary->assembledGeometryBytes) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": buffer must hold width*height*4 floats");
+  int rc = activate(primary, name); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(primary->stream));
+  HIP_TRY(hipMemcpy(host, primary->d_assembledGeometry, primary->assembledGeometryBytes, hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_assembled_geometry")
 
 int twk_assemble_host(const void* const* sources, int deviceCount, int width, int height, const int tileSize[2], int elementBytes, int layers, void* destination)
 try

@@ -1,6 +1,6 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass in its three forms: uniform, listed, planned — shade_device.h "the samples of a thread"), device_post.hip (compositor,
-// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame, with or without its geometry AOV), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
@@ -39,7 +39,7 @@ void launchDenoisePrepare(const void* beauty, const void* albedo, const void* no
 void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, const float4* sampled, float minSamples, hipStream_t stream);
 void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
-void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream);
+void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
 unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
@@ -215,6 +215,10 @@ struct TwkDevice_t
   bool assembledValid[TWK_PLANE_COUNT] = {false, false, false, false, false, false};
   void* d_assembleStage = nullptr; size_t assembleStageBytes = 0; bool assembleStage = false; // TWK_ASSEMBLE_STAGE=1: every source is staged (tests both paths on one GPU)
   hipEvent_t assembleReady = nullptr, assembleDone = nullptr;
+  // twk_assemble_with_geometry / twk_assemble_devices_with_geometry: the assembled W x H geometry AOV, float4. It is no seventh
+  // plane (TWK_PLANE_COUNT stays 6): freed with the other assembled buffers (dropAssembled), and stale (assembledGeometryValid
+  // false, the buffer kept) once this handle's camera, state or scene changes — staleGeometry, which is what clears geometryValid
+  void* d_assembledGeometry = nullptr; size_t assembledGeometryBytes = 0; bool assembledGeometryValid = false;
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;
@@ -245,6 +249,9 @@ struct TwkDevice_t
   LaunchParams params;
   BvhBuilder builder;
 };
+
+// The camera, the state or the scene changed: the handle's geometry AOV and the geometry it assembled as a primary are of the old one
+inline void staleGeometry(TwkDevice dev) { dev->geometryValid = false; dev->assembledGeometryValid = false; }
 
 template<typename T> inline void freeDevice(T*& p) { if (p) { (void) hipFree(p); p = nullptr; } }
 
@@ -289,7 +296,7 @@ CascadeOn cascadeFold(TwkDevice dev);
 // device_temporal_cascade.hip
 void dropTemporalCascade(TwkDevice dev);
 const char* temporalCascadeRefusal(TwkDevice dev);
-int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* geometry, const float4* historyGeometry);
+int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry);
 // device_assemble.hip
 void dropAssembled(TwkDevice dev);
 }

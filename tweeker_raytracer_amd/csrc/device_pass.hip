@@ -486,6 +486,32 @@ static int renderListPass(TwkDevice dev, const Samples& samples, size_t numPaths
 }
 
 // =============================================================================================
+// twk_render_geometry (tile = false: a packed tile buffer is refused) and twk_render_geometry_tile (tile = true: a packed tile
+// buffer is traced launch index by launch index, temporal_device.h "the geometry AOV of a tile share"; any other handle is the
+// former call itself)
+static int renderGeometry(TwkDevice dev, const char* name, bool tile)
+{
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": " + text); };
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built) return refuse("twk_build has not been called");
+  if (!dev->stateSet || dev->cameras.empty()) return refuse("twk_set_state and twk_init_cameras first");
+  if (!dev->geometryEnabled) return refuse("twk_enable_geometry(1) first");
+  if (dev->state.lensShader != 0) return refuse("pinhole lens shader only (reprojection inverts the pinhole mapping)");
+  const bool tiled = dev->state.distribution && 1 < dev->count;
+  if (tiled && !tile) return refuse("the handle's buffers are packed tile buffers (distribution 1, more than one device), not pictures");
+  for (const DevMaterial& m : dev->materials) if (m.textureCutout) return refuse("geometric query only, not for scenes with cutout opacity");
+  if ((rc = ensureStreams(dev))) return rc;
+  refreshParams(dev);
+  const size_t numPixels = (size_t) dev->launchWidth * dev->state.resolution[1]; // launchWidth = width unless tiled
+  if (!dev->d_geometry || (size_t) dev->geometryPixels < numPixels) return refuse("no geometry buffer");
+  int grid = (int) ((numPixels + TWK_TRACE_BLOCK - 1) / TWK_TRACE_BLOCK);
+  if (grid > dev->numCUs * TWK_TRACE_WAVES) grid = dev->numCUs * TWK_TRACE_WAVES; // within the per-lane spill stacks, like twk_trace_rays
+  launchGeometry(dev->params, dev->d_geometry, tiled, grid, dev->stream);
+  HIP_TRY(hipGetLastError());
+  dev->geometryValid = true;
+  return TWK_SUCCESS;
+}
+
 extern "C" {
 
 int twk_launch(TwkDevice dev, unsigned int iterationIndex)
@@ -584,24 +610,15 @@ TWK_CATCH("twk_reserve_launch_batch")
 int twk_render_geometry(TwkDevice dev)
 try
 {
-  int rc = activate(dev, "twk_render_geometry"); if (rc) return rc;
-  if (!dev->built) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: twk_build has not been called");
-  if (!dev->stateSet || dev->cameras.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: twk_set_state and twk_init_cameras first");
-  if (!dev->geometryEnabled) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: twk_enable_geometry(1) first");
-  if (dev->state.lensShader != 0) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: pinhole lens shader only (reprojection inverts the pinhole mapping)");
-  if (dev->state.distribution && 1 < dev->count) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: the handle's buffers are packed tile buffers (distribution 1, more than one device), not pictures");
-  for (const DevMaterial& m : dev->materials) if (m.textureCutout) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: geometric query only, not for scenes with cutout opacity");
-  if ((rc = ensureStreams(dev))) return rc;
-  refreshParams(dev);
-  const size_t numPixels = (size_t) dev->launchWidth * dev->state.resolution[1]; // launchWidth = width here
-  if (!dev->d_geometry || (size_t) dev->geometryPixels < numPixels) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_render_geometry: no geometry buffer");
-  int grid = (int) ((numPixels + TWK_TRACE_BLOCK - 1) / TWK_TRACE_BLOCK);
-  if (grid > dev->numCUs * TWK_TRACE_WAVES) grid = dev->numCUs * TWK_TRACE_WAVES; // within the per-lane spill stacks, like twk_trace_rays
-  launchGeometry(dev->params, dev->d_geometry, grid, dev->stream);
-  HIP_TRY(hipGetLastError());
-  dev->geometryValid = true;
-  return TWK_SUCCESS;
+  return renderGeometry(dev, "twk_render_geometry", false);
 }
 TWK_CATCH("twk_render_geometry")
+
+int twk_render_geometry_tile(TwkDevice dev)
+try
+{
+  return renderGeometry(dev, "twk_render_geometry_tile", true);
+}
+TWK_CATCH("twk_render_geometry_tile")
 
 } // extern "C"

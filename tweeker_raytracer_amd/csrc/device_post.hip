@@ -14,6 +14,45 @@ void twk::dropTemporal(TwkDevice dev)
   dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
 }
 
+// The merge of twk_temporal_accumulate's own-buffer form and of twk_temporal_accumulate_assembled, after their refusals: the frame
+// (colour in the output format, moments, geometry; layers: the cascade layers to merge while twk_temporal_enable_cascade is on,
+// nullptr = the handle's own) of width x height pixels against the history the handle kept, which it then replaces. k: maxHistory
+// and tol2 are set.
+static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const void* colour, const float4* moments, const float4* geometry, const float4* layers, int width, int height)
+{
+  const size_t n = (size_t) width * height;
+  if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
+  {
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    dropTemporal(dev);
+    for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
+    HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
+    dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
+  }
+  const float4 *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
+  if (dev->temporalHasHistory)
+  {
+    float4* const* h = dev->d_temporal[dev->temporalKept];
+    hColour = h[0]; hMoments = h[1]; hGeometry = h[2];
+  }
+  const int keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
+  k.width = width; k.height = height;
+  if (dev->temporalHasHistory)
+  {
+    k.hasHistory = 1;
+    if (!temporalCamera(dev->temporalCamera.P, k))
+      return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": the history's camera is degenerate: U, V, W are linearly dependent or not finite");
+  }
+  // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
+  int rc;
+  if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
+  launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_temporalColour, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, n * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
+  dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
+  return TWK_SUCCESS;
+}
+
 // =============================================================================================
 extern "C" {
 
@@ -318,7 +357,6 @@ try
   const bool own = (current == nullptr);
   const void* colour; const float4 *moments, *geometry, *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
   const TwkCameraDefinition* hCamera = nullptr;
-  int keep = 0;
   if (own)
   {
     if (history || colourOut || historyOut || momentsOut || width || height) return refuse(TWK_ERROR_INVALID_VALUE, "a history, outputs or a size without a current frame (pass both frames, or neither for the handle's own buffers)");
@@ -332,22 +370,7 @@ try
     colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
     if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
     if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
-    if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
-    {
-      HIP_TRY(hipStreamSynchronize(dev->stream));
-      dropTemporal(dev);
-      for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
-      HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
-      dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
-    }
-    moments = dev->d_moments; geometry = dev->d_geometry;
-    if (dev->temporalHasHistory)
-    {
-      float4* const* h = dev->d_temporal[dev->temporalKept];
-      hColour = h[0]; hMoments = h[1]; hGeometry = h[2]; hCamera = &dev->temporalCamera;
-    }
-    keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
-    colourOut = dev->d_temporalColour; historyOut = dev->d_temporal[keep][0]; momentsOut = dev->d_temporal[keep][1];
+    return temporalOwn(dev, name, k, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
   }
   else
   {
@@ -375,18 +398,43 @@ try
     k.hasHistory = 1;
     if (!temporalCamera(hCamera->P, k)) return refuse(TWK_ERROR_INVALID_VALUE, "the history's camera is degenerate: U, V, W are linearly dependent or not finite");
   }
-  // twk_temporal_enable_cascade: the handle's layers through the same previous geometry and camera, before the history is swapped
-  if (own && dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, geometry, hGeometry))) return rc;
   launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
   HIP_TRY(hipGetLastError());
-  if (own)
-  {
-    HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, (size_t) width * height * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
-    dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
-  }
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_temporal_accumulate")
+
+int twk_temporal_accumulate_assembled(TwkDevice primary, const TwkTemporal* tp)
+try
+{
+  const char* name = "twk_temporal_accumulate_assembled";
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  TwkDevice dev = primary;
+  int rc = activate(dev, name); if (rc) return rc;
+  TwkTemporal defaults; defaults.maxHistory = TWK_TEMPORAL_MAX_HISTORY; defaults.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  if (!tp) tp = &defaults;
+  if (tp->maxHistory < 1) return refuse(TWK_ERROR_INVALID_VALUE, "maxHistory must be >= 1");
+  if (!(tp->positionTolerance >= 0.0f) || !finite1(tp->positionTolerance)) return refuse(TWK_ERROR_INVALID_VALUE, "positionTolerance must be >= 0 and finite");
+  TemporalConstants k;
+  memset(&k, 0, sizeof(k));
+  k.maxHistory = (float) tp->maxHistory; k.tol2 = tp->positionTolerance * tp->positionTolerance;
+  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+  if (!(dev->state.distribution && 1 < dev->count))
+    return refuse(TWK_ERROR_INVALID_STATE, "the handle is not tiled (distribution 1, more than one device): its own buffers are the picture, twk_temporal_accumulate merges them");
+  if (!dev->momentsEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no luminance moments: render with twk_enable_moments(1)");
+  if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no geometry AOV: twk_enable_geometry(1) and twk_render_geometry_tile");
+  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
+  const int needed[3] = {TWK_PLANE_OUTPUT, TWK_PLANE_MOMENTS, TWK_PLANE_CASCADE};
+  static const char* const neededNames[3] = {"TWK_PLANE_OUTPUT", "TWK_PLANE_MOMENTS", "TWK_PLANE_CASCADE"};
+  for (int j = 0; j < (dev->temporalCascade ? 3 : 2); ++j)
+    if (!dev->assembledValid[needed[j]] || !dev->d_assembled[needed[j]])
+      return refuse(TWK_ERROR_INVALID_STATE, std::string(neededNames[j]) + " has not been assembled on this handle: twk_assemble_devices_with_geometry first");
+  if (!dev->d_assembledGeometry) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV has not been assembled on this handle: twk_assemble_devices_with_geometry first");
+  if (!dev->assembledGeometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the assembled geometry AOV is stale, older than the camera, the state or the scene: twk_render_geometry_tile and twk_assemble_devices_with_geometry first");
+  return temporalOwn(dev, name, k, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS]), static_cast<const float4*>(dev->d_assembledGeometry),
+                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE]) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
+}
+TWK_CATCH("twk_temporal_accumulate_assembled")
 
 int twk_temporal_reset(TwkDevice dev)
 try

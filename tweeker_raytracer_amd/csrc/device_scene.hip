@@ -37,7 +37,7 @@ try
   int rc = activate(dev, "twk_clear_scene"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->geometries.clear(); dev->instances.clear(); dev->built = false; dropAdaptive(dev);
-  dev->geometryValid = false; dropTemporal(dev);
+  staleGeometry(dev); dropTemporal(dev);
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_clear_scene")
@@ -338,7 +338,7 @@ try
   dev->maxInstanceMaterial = maxMaterial; dev->maxInstanceLight = maxLight;
   dev->totalNodes = numNodes; dev->totalTriangles = numTris;
   dev->built = true; ++dev->buildSerial;
-  dev->geometryValid = false; dropTemporal(dev); // the geometry AOV and the temporal history describe the scene that was
+  staleGeometry(dev); dropTemporal(dev); // the geometry AOV and the temporal history describe the scene that was
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_build")

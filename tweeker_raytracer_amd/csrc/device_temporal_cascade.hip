@@ -21,14 +21,19 @@ const char* twk::temporalCascadeRefusal(TwkDevice dev)
   return nullptr;
 }
 
-// The own-buffer form's merge of the handle's layers, on its stream: k, geometry and historyGeometry (nullptr: the temporal merge
-// has no history) are those of the twk_temporal_accumulate that calls it, before it swaps its history.
-int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* geometry, const float4* historyGeometry)
+// The own-buffer form's merge of the frame's layers, on its stream: k, geometry and historyGeometry (nullptr: the temporal merge
+// has no history) are those of the twk_temporal_accumulate or twk_temporal_accumulate_assembled that calls it, before it swaps its
+// history. layers: [layers][k.width x k.height] float4, the assembled ones of a tiled primary; nullptr: the handle's own.
+int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry)
 {
   int rc = ensureStreams(dev); if (rc) return rc;
   const size_t n = (size_t) k.width * k.height;
   const int K = dev->cascadeK.layers;
-  if (!dev->d_cascade || (size_t) dev->cascadePixels != n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_temporal_accumulate: the handle's cascade layers do not have the frame's shape");
+  if (!layers)
+  {
+    if (!dev->d_cascade || (size_t) dev->cascadePixels != n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_temporal_accumulate: the handle's cascade layers do not have the frame's shape");
+    layers = dev->d_cascade;
+  }
   if (!dev->d_temporalCascade[0] || dev->temporalCascadePixels != n || dev->temporalCascadeLayers != K)
   {
     HIP_TRY(hipStreamSynchronize(dev->stream));
@@ -41,7 +46,7 @@ int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const flo
   const int keep = dev->temporalCascadeHasHistory ? 1 - dev->temporalCascadeKept : dev->temporalCascadeKept;
   TemporalConstants kc = k;
   kc.hasHistory = history ? 1 : 0;
-  launchTemporalCascade(dev->d_cascade, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
+  launchTemporalCascade(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
                         dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
   HIP_TRY(hipGetLastError());
   dev->temporalCascadeKept = keep; dev->temporalCascadeHasHistory = true; dev->temporalCascadeValid = true;

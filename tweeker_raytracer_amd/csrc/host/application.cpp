@@ -201,6 +201,33 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && (token == "0" || token == "1")) tileAssembly = (token == "1") ? 1 : 0;
       else if (ok) { tileAssembly = 0; warnings.push_back("tileAssembly must be 0 or 1, leaving it off"); }
     }
+    // the moving-camera loop (twk_temporal_accumulate / twk_temporal_accumulate_assembled, read by twk_app_get_temporal): a value the
+    // calls would refuse drops the line
+    else if (key == "temporalAccumulation") { ok = readInt(parser, i[0]); if (ok) temporalAccumulation = (i[0] == 1) ? 1 : 0; }
+    else if (key == "temporalFrames")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 1 && i[0] <= 4096) temporalFrames = i[0];
+      else if (ok) warnings.push_back("temporalFrames must be in 1..4096, keeping the previous value");
+    }
+    else if (key == "temporalOrbitStep")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && std::isfinite(f[0])) temporalOrbitStep = f[0];
+      else if (ok) warnings.push_back("temporalOrbitStep must be finite, keeping the previous value");
+    }
+    else if (key == "temporalMaxHistory")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && i[0] >= 1) temporalMaxHistory = i[0];
+      else if (ok) warnings.push_back("temporalMaxHistory must be >= 1, keeping the previous value");
+    }
+    else if (key == "temporalPositionTolerance")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok && f[0] >= 0.0f && std::isfinite(f[0])) temporalPositionTolerance = f[0];
+      else if (ok) warnings.push_back("temporalPositionTolerance must be >= 0 and finite, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -293,6 +320,11 @@ std::string Application::systemDescription() const
   if (fireflyCascadeBase != TWK_CASCADE_BASE) d << "fireflyCascadeBase " << fireflyCascadeBase << std::endl;
   if (fireflyCascadeKappa != TWK_CASCADE_KAPPA) d << "fireflyCascadeKappa " << fireflyCascadeKappa << std::endl;
   if (tileAssembly != 0) d << "tileAssembly " << tileAssembly << std::endl;
+  if (temporalAccumulation != 0) d << "temporalAccumulation " << temporalAccumulation << std::endl;
+  if (temporalFrames != 1) d << "temporalFrames " << temporalFrames << std::endl;
+  if (temporalOrbitStep != TWK_TEMPORAL_ORBIT_STEP) d << "temporalOrbitStep " << temporalOrbitStep << std::endl;
+  if (temporalMaxHistory != TWK_TEMPORAL_MAX_HISTORY) d << "temporalMaxHistory " << temporalMaxHistory << std::endl;
+  if (temporalPositionTolerance != TWK_TEMPORAL_POSITION_TOLERANCE) d << "temporalPositionTolerance " << temporalPositionTolerance << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

@@ -115,6 +115,15 @@ public:
   // "tileAssembly" (1: a several-device render loop assembles the planes its post steps need with one twk_assemble_devices and runs
   // them on the assembled frame)
   int   tileAssembly = 0;
+  // "temporalAccumulation" (1: the batch loop is an orbit of "temporalFrames" frames, each samplesSqrt² iterations from a camera
+  // "temporalOrbitStep" of a full turn further in phi, merged into the frames before it by twk_temporal_accumulate — on several
+  // devices through twk_render_geometry_tile, twk_assemble_devices_with_geometry and twk_temporal_accumulate_assembled),
+  // "temporalMaxHistory", "temporalPositionTolerance" (TwkTemporal; twk_temporal_defaults' values until a key sets them)
+  int   temporalAccumulation = 0;
+  int   temporalFrames = 1;
+  float temporalOrbitStep = TWK_TEMPORAL_ORBIT_STEP;
+  int   temporalMaxHistory = TWK_TEMPORAL_MAX_HISTORY;
+  float temporalPositionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel

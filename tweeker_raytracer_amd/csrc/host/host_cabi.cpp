@@ -197,6 +197,19 @@ try
 }
 TWK_CATCH("twk_app_get_tile_assembly")
 
+int twk_app_get_temporal(TwkApp app, int* enabled, TwkTemporal* tp, int* frames, float* orbitStep)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_temporal: NULL app");
+  if (!enabled || !tp || !frames || !orbitStep) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_temporal: NULL argument");
+  const Application& a = app->app;
+  *enabled = (a.temporalAccumulation != 0) ? 1 : 0;
+  tp->maxHistory = a.temporalMaxHistory; tp->positionTolerance = a.temporalPositionTolerance;
+  *frames = a.temporalFrames; *orbitStep = a.temporalOrbitStep;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_temporal")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {
@@ -297,6 +310,11 @@ try
   {
     const TwkCascade cascade = {a.fireflyCascadeLayers, a.fireflyCascadeStart, a.fireflyCascadeBase};
     if ((rc = twk_enable_cascade(dev, 1, &cascade))) return rc;
+  }
+  if (a.temporalAccumulation != 0) // "temporalAccumulation 1": the merge reads the samples' moments and the geometry AOV
+  {
+    if ((rc = twk_enable_moments(dev, 1))) return rc;
+    if ((rc = twk_enable_geometry(dev, 1))) return rc;
   }
   if ((rc = twk_init_cameras(dev, a.cameras.data(), (int) a.cameras.size()))) return rc;
   if ((rc = twk_init_lights(dev, a.lights.data(), (int) a.lights.size()))) return rc;

@@ -18,6 +18,15 @@
 // after the loop ONE twk_assemble_devices on the first device assembles exactly the planes those steps need (beauty or cascade
 // layers, albedo, normal, moments), and they run on the assembled frame through their explicit forms. With strategy 1 or 2 the key
 // is refused (the beauty lives in the shared frame, the other planes do not); on one device it changes nothing.
+// With "temporalAccumulation 1" the batch is the loop of a camera that moves (INTEGRATION.md "The temporal seam on several devices"):
+// an orbit of "temporalFrames" frames, frame f from the camera at phi + f x "temporalOrbitStep" of a turn under the sample offset
+// f x samplesSqrt², each samplesSqrt² iterations, its geometry AOV (twk_render_geometry; twk_render_geometry_tile on several
+// devices), there ONE twk_assemble_devices_with_geometry of the planes the merge and the post steps read, and the merge
+// (twk_temporal_accumulate; twk_temporal_accumulate_assembled on the first device), the cascade's layers through it with
+// "fireflyCascade 1". After the last frame the merged layers are resolved, the denoiser takes the merged colour (or the resolved
+// picture) and the merged moments, and the screenshot is that. The frame-rate line counts frames x samplesSqrt² iterations.
+// Refused before any device is created: with "targetNoise" or "adaptiveSampling", with a "lensShader" other than 0, with strategy 1
+// or 2, and on several devices without "tileAssembly 1".
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -199,6 +208,31 @@ int main(int argc, char* argv[])
     return 1;
   }
 
+  int temporalEnabled = 0, temporalFrames = 1; // "temporalAccumulation 1": the batch is an orbit of merged frames
+  float temporalOrbitStep = 0.0f;
+  TwkTemporal temporal;
+  TWK_OK(twk_app_get_temporal(app, &temporalEnabled, &temporal, &temporalFrames, &temporalOrbitStep));
+  if (temporalEnabled && (targetNoiseEnabled || adaptiveEnabled))
+  {
+    std::cerr << "ERROR: temporalAccumulation renders a fixed orbit of frames; targetNoise and adaptiveSampling end or thin a single frame's loop and do not go with it\n";
+    return 1;
+  }
+  if (temporalEnabled && info.lensShader != 0)
+  {
+    std::cerr << "ERROR: temporalAccumulation reprojects through the pinhole camera: lensShader must be 0\n";
+    return 1;
+  }
+  if (temporalEnabled && count > 1 && (info.strategy == 1 || info.strategy == 2))
+  {
+    std::cerr << "ERROR: temporalAccumulation on several devices merges the assembled packed tile buffers (strategy 3), not a shared frame (strategy 1 or 2)\n";
+    return 1;
+  }
+  if (temporalEnabled && count > 1 && !assembling)
+  {
+    std::cerr << "ERROR: temporalAccumulation on several devices merges the assembled frame on the first device: it needs tileAssembly 1\n";
+    return 1;
+  }
+
   std::vector<TwkDevice> devices((size_t) count, nullptr);
   TwkDeviceState state;
   TWK_OK(twk_app_get_state(app, &state));
@@ -281,6 +315,39 @@ int main(int argc, char* argv[])
     }
     return 0;
   };
+  // the planes the temporal loop's assembly moves beside the geometry: what the merge reads and, of the last frame, the post steps' guides
+  unsigned int temporalPlanes = TWK_PLANE_BIT(TWK_PLANE_OUTPUT) | TWK_PLANE_BIT(TWK_PLANE_MOMENTS);
+  if (cascadeEnabled) temporalPlanes |= TWK_PLANE_BIT(TWK_PLANE_CASCADE);
+  if (temporalEnabled)
+  {
+    if (cascadeEnabled) TWK_OK(twk_temporal_enable_cascade(devices[0], 1));
+    const float aspect = (float) ((double) info.resolution[0] / (double) info.resolution[1]);
+    for (int frame = 0; frame < temporalFrames; ++frame)
+    {
+      TwkCameraDefinition camera;
+      const float phi = (float) ((double) info.phi + (double) frame * (double) temporalOrbitStep);
+      TWK_OK(twk_camera_frustum(info.center, phi, info.theta, info.fov, info.distance, aspect, &camera));
+      for (int i = 0; i < count; ++i)
+      {
+        TWK_OK(twk_update_camera(devices[(size_t) i], 0, &camera));
+        TWK_OK(twk_set_sample_offset(devices[(size_t) i], (unsigned int) frame * spp));
+      }
+      for (unsigned int it = 0; it < spp; ++it) for (int i = 0; i < count; ++i) TWK_OK(twk_launch(devices[(size_t) i], it));
+      if (count == 1)
+      {
+        TWK_OK(twk_render_geometry(devices[0]));
+        TWK_OK(twk_temporal_accumulate(devices[0], &temporal, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr));
+        continue;
+      }
+      for (int i = 0; i < count; ++i) TWK_OK(twk_render_geometry_tile(devices[(size_t) i]));
+      unsigned int planes = temporalPlanes;
+      if (frame == temporalFrames - 1 && denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO) planes |= TWK_PLANE_BIT(TWK_PLANE_ALBEDO);
+      if (frame == temporalFrames - 1 && denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) planes |= TWK_PLANE_BIT(TWK_PLANE_NORMAL);
+      TWK_OK(twk_assemble_devices_with_geometry(devices[0], planes, devices.data(), count));
+      TWK_OK(twk_temporal_accumulate_assembled(devices[0], &temporal));
+    }
+    iterationIndex = (unsigned int) temporalFrames * spp;
+  }
   while (iterationIndex < spp)
   {
     for (int i = 0; i < count; ++i) TWK_OK(twk_launch(devices[(size_t) i], iterationIndex));
@@ -422,7 +489,47 @@ int main(int argc, char* argv[])
     else           TWK_OK(twk_tonemap(devices[0], &tonemapper, frame, numPixels, rgb8.data()));
     return 0;
   };
-  if (assembling)
+  if (temporalEnabled)
+  {
+    // the merged colour (with the cascade: the resolve of the merged layers) and the merged moments of the first device; the guides
+    // are the last frame's: assembled with it on several devices, copies of the handle's own AOVs on one
+    void* merged = nullptr; void* mergedMoments = nullptr; void* resolved = nullptr;
+    TWK_OK(twk_get_temporal_device_pointers(devices[0], &merged, nullptr, &mergedMoments, nullptr));
+    HIP_OK(hipSetDevice(ordinals[0]));
+    if (cascadeEnabled)
+    {
+      void* layers = nullptr;
+      TWK_OK(twk_get_temporal_cascade_device_pointer(devices[0], &layers, nullptr));
+      HIP_OK(hipMalloc(&resolved, numPixels * pixelBytes));
+      TWK_OK(twk_cascade_resolve(devices[0], &cascade, &cascadeResolve, layers, width, height, resolved));
+      merged = resolved;
+    }
+    void* guides[2] = {nullptr, nullptr}; bool ownGuides = false;
+    if (denoiserEnabled && denoiser.inputKind != TWK_DENOISER_RGB)
+    {
+      if (count > 1)
+      {
+        TWK_OK(twk_get_assembled_device_pointer(devices[0], TWK_PLANE_ALBEDO, &guides[0], nullptr));
+        if (denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) TWK_OK(twk_get_assembled_device_pointer(devices[0], TWK_PLANE_NORMAL, &guides[1], nullptr));
+      }
+      else
+      {
+        ownGuides = true;
+        std::vector<unsigned char> host(numPixels * pixelBytes);
+        for (int which = 0; which < 2; ++which)
+        {
+          TWK_OK(twk_read_aov_raw(devices[0], which == 0 ? TWK_AOV_ALBEDO : TWK_AOV_NORMAL, host.data(), host.size()));
+          HIP_OK(hipMalloc(&guides[which], host.size()));
+          HIP_OK(hipMemcpy(guides[which], host.data(), host.size(), hipMemcpyHostToDevice));
+        }
+      }
+    }
+    const int failed = present(merged, guides[0], guides[1], (denoiserEnabled && denoiserSampledEnabled) ? mergedMoments : nullptr);
+    if (ownGuides) for (void* guide : guides) if (guide) HIP_OK(hipFree(guide));
+    if (resolved) HIP_OK(hipFree(resolved));
+    if (failed) return 1;
+  }
+  else if (assembling)
   {
     // several devices, packed tile buffers: one assembly of exactly the planes the post steps read, then their explicit forms on
     // the assembled pointers (ordered on the first device's stream; no host round trip, no per-plane gather)

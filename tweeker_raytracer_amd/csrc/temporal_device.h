@@ -13,6 +13,15 @@
 //   hit:   (P.x + t d.x, P.y + t d.y, P.z + t d.z, bits of (unsigned) instance + 1)      P the camera position, d the direction
 //   miss:  (0, 0, 0, bits 0)
 //
+// ---- the geometry AOV of a tile share (twk_render_geometry_tile) ---------------------------------------------------------------
+// On a handle whose buffers are packed tile buffers (distribution 1, device `index` of `count` > 1), one element per launch index
+// i = ly * launchWidth + lx, 0 <= lx < launchWidth, 0 <= ly < height:
+//   x = distribute(lx, ly) of shade_device.h = twk_tile_column(lx, ly, tileSize, count, index) = assemble_device.h's map
+//   x >= width:  padding, geometry[i] = (0, 0, 0, bits 0), no ray
+//   else:        the ray centreRay(cam, x, ly, width, height), traced and written exactly as above, to geometry[i]
+// so that assembling the shares (assemble_device.h; 16-byte elements, one layer) gives the picture-shaped AOV above, bit for bit.
+// On any other handle the call is twk_render_geometry. The kernel is a second build of geometryKernel (temporal_kernels.hip).
+//
 // ---- the temporal merge (twk_temporal_accumulate) -------------------------------------------------------------------------------
 // Streams, one element per pixel: the current frame's colour (the handle's output format, widened exactly), its luminance moments
 // (mean, M2, n, .) as shade_device.h foldSamples accumulates them and its geometry AOV; the history's colour (f32, a previous
@@ -57,7 +66,11 @@
 // means (the exact pairwise merge of the taps would add it): across a luminance edge inside one surface the interpolated variance
 // is too small by that spread. hn is a weighted mean of sample counts, not a count. A pixel that MISSED never has history: the
 // environment would have to be reprojected by direction, which is left out. Objects do not move (the scene is static between
-// twk_build calls), the lens is the pinhole, and there is one device: no motion vectors, no fisheye or sphere, no tiles.
+// twk_build calls) and the lens is the pinhole: no motion vectors, no fisheye or sphere. The merge itself works on whole pictures.
+// A frame tiled over several devices is merged on ONE of them: every device traces the geometry of its own share (above), the
+// shares and the planes are assembled there in one launch (twk_assemble_devices_with_geometry) and
+// twk_temporal_accumulate_assembled runs this same merge on the assembled W x H buffers, with that handle's history. Nothing is
+// scattered back to the tiles, and the merge does not read the packed tiles itself.
 #pragma once
 #include "denoise_device.h"
 

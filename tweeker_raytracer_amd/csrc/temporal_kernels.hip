@@ -1,12 +1,17 @@
-// Kernels of twk_render_geometry and twk_temporal_accumulate: the geometry AOV and the temporal merge defined in temporal_device.h.
+// Kernels of twk_render_geometry, twk_render_geometry_tile and twk_temporal_accumulate: the geometry AOV and the temporal merge defined in temporal_device.h.
 #include "temporal_device.h"
 #include "trace_device.h"
+#include "shade_device.h" // distribute(): the pixel column of a launch index
 #include "pixel_formats.h"
 
 namespace twk {
 
 // One closest-hit ray through the centre of every pixel with the single-ray traversal (the routine, LDS stack and spill of
-// traceQueryKernel; the grid is at most numCUs x TWK_TRACE_WAVES blocks, within the per-lane spill stacks).
+// traceQueryKernel; the grid is at most numCUs x TWK_TRACE_WAVES blocks, within the per-lane spill stacks). Tiled = false: the
+// handle's buffer is the picture, element i is pixel i. Tiled = true (twk_render_geometry_tile on a packed tile buffer): element i
+// is launch index (lx, ly) of launchWidth x height, its pixel column is distribute(lx, ly), and padding (x >= width) is written as
+// a miss without a ray. A build of its own, so that the single-device kernel is the code it was.
+template<bool Tiled>
 __global__ void __launch_bounds__(TWK_TRACE_BLOCK)
 geometryKernel(LaunchParams p, float4* __restrict__ geometry)
 {
@@ -14,16 +19,23 @@ geometryKernel(LaunchParams p, float4* __restrict__ geometry)
   int* ldsStack = stackStorage + threadIdx.x;
   int* spill = p.traceStackSpill + (size_t) (blockIdx.x * blockDim.x + threadIdx.x) * TWK_TRACE_STACK_SPILL;
   unsigned int n0 = 0, n1 = 0, n2 = 0;
-  const unsigned int numPixels = (unsigned int) p.resolution[0] * (unsigned int) p.resolution[1];
+  const unsigned int columns = (unsigned int) (Tiled ? p.launchWidth : p.resolution[0]);
+  const unsigned int numPixels = columns * (unsigned int) p.resolution[1];
   const float* cam = p.camera;
   const V3 P = v3(cam[0], cam[1], cam[2]);
   for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < numPixels; i += gridDim.x * blockDim.x)
   {
-    const int x = (int) (i % (unsigned int) p.resolution[0]), y = (int) (i / (unsigned int) p.resolution[0]);
+    int x = (int) (i % columns);
+    const int y = (int) (i / columns);
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (Tiled)
+    {
+      x = (int) distribute(p, (unsigned int) x, (unsigned int) y);
+      if (x >= p.resolution[0]) { geometry[i] = g; continue; }
+    }
     const V3 d = centreRay(cam, x, y, p.resolution[0], p.resolution[1]);
     TraceResult res;
     traverse<false>(p, P, d, p.sceneEpsilon, RT_DEFAULT_MAX, false, ldsStack, spill, res, n0, n1, n2);
-    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (res.instance >= 0)
       g = make_float4(P.x + res.t * d.x, P.y + res.t * d.y, P.z + res.t * d.z, __uint_as_float((unsigned int) res.instance + 1u));
     geometry[i] = g;
@@ -85,9 +97,10 @@ __global__ void __launch_bounds__(256) temporalKernel(const Pixel* __restrict__ 
   }
 }
 
-void launchGeometry(const LaunchParams& p, float4* geometry, int gridBlocks, hipStream_t stream)
+void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream)
 {
-  hipLaunchKernelGGL(geometryKernel, dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, geometry);
+  if (tiled) hipLaunchKernelGGL(geometryKernel<true>, dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, geometry);
+  else       hipLaunchKernelGGL(geometryKernel<false>, dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, geometry);
 }
 
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,

@@ -173,6 +173,13 @@ class Device:
         """twk_render_geometry: one closest-hit ray through the centre of every pixel with the camera as it is now. Asynchronous."""
         L.check(L.lib.twk_render_geometry(self._h))
 
+    def renderGeometryTile(self):
+        """twk_render_geometry_tile: renderGeometry for a handle whose buffers are packed tile buffers (distribution 1, several
+        devices) — one ray per launch index through the centre of the pixel twk_tile_column maps it to, padding written as a miss;
+        on any other handle it is renderGeometry itself. Asynchronous. TwkError (INVALID_STATE) before build or setState, with the
+        geometry off, with a lens shader other than the pinhole, and on a scene with a cutout texture in use."""
+        L.check(L.lib.twk_render_geometry_tile(self._h))
+
     def readGeometry(self):
         """The geometry AOV: float32 [height, launchWidth, 4]; [..., 3].view(uint32) is instance + 1, 0 for a miss."""
         out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
@@ -206,15 +213,32 @@ class Device:
         L.check(L.lib.twk_get_temporal_device_pointers(self._h, C.byref(c), C.byref(cn), C.byref(m), C.byref(mn)))
         return c.value, cn.value, m.value, mn.value
 
+    def _temporalWidth(self):
+        """Columns of the temporal result: the picture's width on a tiled handle (temporalAccumulateAssembled), else launchWidth."""
+        return self.state.resolution[0] if (self.state.distribution and self.count > 1) else self.launchWidth
+
+    def temporalAccumulateAssembled(self, params=None):
+        """twk_temporal_accumulate_assembled, on a tiled primary: temporalAccumulate()'s own-buffer form with the planes this handle
+        assembled as the current frame — the assembled beauty, moments and geometry (assembleWithGeometry), this handle's camera 0,
+        width x height pixels — against the history this handle kept; with enableTemporalCascade also the assembled cascade
+        layers. readTemporal, readTemporalMoments, temporalDevicePointers, readTemporalCascade, temporalCascadeDevicePointer and
+        temporalReset work as on one device, [height, width]. params: L.Temporal (None = the defaults). TwkError (INVALID_STATE)
+        before setState, on a handle that is not tiled (use temporalAccumulate), with moments or geometry off, with cascade merging
+        on but no cascade, and while the beauty, the moments, the cascade (when merged) or the geometry has not been assembled or
+        the assembled geometry is stale — the text names which."""
+        L.check(L.lib.twk_temporal_accumulate_assembled(self._h, None if params is None else C.byref(params)))
+
     def readTemporal(self):
-        """The merged colour of the own-buffer form: float32 [height, launchWidth, 4] (widened exactly in half mode)."""
-        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        """The merged colour of the own-buffer form: float32 [height, launchWidth, 4] (widened exactly in half mode); [height, width,
+        4] on a tiled primary (temporalAccumulateAssembled)."""
+        out = np.empty((self.state.resolution[1], self._temporalWidth(), 4), dtype=np.float32)
         L.check(L.lib.twk_read_temporal(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
     def readTemporalMoments(self):
-        """The merged luminance moments of the own-buffer form: float32 [height, launchWidth, 4] = (mean, M2, n, 0)."""
-        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        """The merged luminance moments of the own-buffer form: float32 [height, launchWidth, 4] = (mean, M2, n, 0); [height, width,
+        4] on a tiled primary."""
+        out = np.empty((self.state.resolution[1], self._temporalWidth(), 4), dtype=np.float32)
         L.check(L.lib.twk_read_temporal_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
@@ -503,9 +527,9 @@ class Device:
         return p.value, n.value
 
     def readTemporalCascade(self):
-        """The merged layers: float32 [layers, height, launchWidth, 4], as readCascade lays them out; [0, ..., 3] is the merged
-        (weighted, capped) sample count."""
-        out = np.empty((self._cascadeLayers, self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        """The merged layers: float32 [layers, height, launchWidth, 4], as readCascade lays them out ([layers, height, width, 4] on
+        a tiled primary); [0, ..., 3] is the merged (weighted, capped) sample count."""
+        out = np.empty((self._cascadeLayers, self.state.resolution[1], self._temporalWidth(), 4), dtype=np.float32)
         L.check(L.lib.twk_read_temporal_cascade(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
@@ -532,6 +556,40 @@ class Device:
         for d, src in enumerate(sources):
             arr[d] = src if isinstance(src, L.AssemblySource) else L.AssemblySource(src)
         L.check(L.lib.twk_assemble(self._h, C.c_uint(self._planeMask(planes)), arr, int(len(sources))))
+
+    def assembleWithGeometry(self, devices, planes):
+        """twk_assemble_devices_with_geometry with this handle as primary: assemble(devices, planes) and, in the same launch, the
+        geometry AOV of every handle's tile share (renderGeometryTile) into this handle's assembled width x height geometry
+        (readAssembledGeometry, assembledGeometryDevicePointer). planes may be empty: the geometry alone. Beyond assemble's
+        refusals, TwkError when the geometry is off on a handle, when a handle's geometry is not valid (no renderGeometryTile since
+        its camera, state or scene changed) and when a handle's camera 0 is not this handle's, byte for byte."""
+        handles = (C.c_void_p * max(1, len(devices)))(*[d._h.value for d in devices])
+        L.check(L.lib.twk_assemble_devices_with_geometry(self._h, C.c_uint(self._planeMask(planes)), handles, int(len(devices))))
+
+    def assembleFromWithGeometry(self, sources, geometrySources, planes):
+        """twk_assemble_with_geometry: assembleFrom(sources, planes) and, in the same launch, geometrySources[d] — a device pointer to
+        the packed launchWidth x height geometry of the device with index d, addressable from this handle's device. planes may be
+        empty (sources is then not looked at). Beyond assembleFrom's refusals, TwkError when the geometry is off on this handle and
+        for a missing or NULL geometry source. The sources' cameras and age are the caller's to keep."""
+        arr = (L.AssemblySource * max(1, len(sources)))()
+        for d, src in enumerate(sources):
+            arr[d] = src if isinstance(src, L.AssemblySource) else L.AssemblySource(src)
+        geometry = (C.c_void_p * max(1, len(geometrySources)))(*[None if g is None else int(g) for g in geometrySources])
+        L.check(L.lib.twk_assemble_with_geometry(self._h, C.c_uint(self._planeMask(planes)), arr, geometry, int(len(geometrySources))))
+
+    def assembledGeometryDevicePointer(self):
+        """(device pointer, bytes) of this handle's assembled geometry AOV; TwkError before it has been assembled, after the
+        assembled buffers were dropped, and once this handle's camera, state or scene has changed (it is stale)."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_assembled_geometry_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readAssembledGeometry(self):
+        """The assembled geometry AOV (synchronises): float32 [height, width, 4], laid out like readGeometry on one device. TwkError
+        where assembledGeometryDevicePointer raises it: not assembled, dropped, or stale."""
+        out = np.empty((self.state.resolution[1], self.state.resolution[0], 4), dtype=np.float32)
+        L.check(L.lib.twk_read_assembled_geometry(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
 
     def assembledDevicePointer(self, plane):
         """(device pointer, bytes) of this handle's assembled buffer of `plane`; TwkError before the plane has been assembled."""

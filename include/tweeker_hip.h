@@ -488,6 +488,39 @@ int twk_denoise_variance(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiser
  * beauty's luminance). The float operations and their order: csrc/denoise_device.h. */
 int twk_denoise_variance_sampled(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, int minSamples, const void* beauty,
                                  const void* albedo, const void* normal, const void* moments, int width, int height, void* denoised);
+/* The geometry guide — new calls, ABI stays 9, TwkDenoiser stays 28 bytes, TwkDenoiserVariance does not grow. The geometric half of
+ * SVGF's edge-stopping function (Schied et al. 2017, section 4.4) as a fourth guide of the three modes above: albedo and normal
+ * cannot tell a white block from the white wall parallel to it; the world position of the first hit can. A tap is weighed by
+ * exp(-(d / (sigmaPosition |gp - P|))^2), d its distance from the centre's tangent plane (the plane through the centre's world
+ * position gp whose normal is the centre's normal guide taken back to world space), |gp - P| the centre's distance from the camera —
+ * TwkTemporal::positionTolerance's convention. A hit and a miss never mix, and with instanceStop neither do two instances.
+ * `geometry`: width x height float4, always f32, as twk_render_geometry writes them — (world position, bits of instance + 1), a miss
+ * (0, 0, 0, bits 0); `camera`: the 12 floats P, U, V, W it was traced from (a TwkCameraDefinition's first 12), NULL: the handle's
+ * camera 0. dv NULL: twk_denoise's mode; dv and minSamples 0: twk_denoise_variance's; dv and minSamples >= 2:
+ * twk_denoise_variance_sampled's with `moments` (NULL otherwise). inputKind must be TWK_DENOISER_RGB_ALBEDO_NORMAL (else
+ * TWK_ERROR_INVALID_VALUE), and 1 / sigmaPosition^2 a finite positive float; every other refusal is the mode's own.
+ * beauty NULL (then every other input NULL): the handle's accumulation, AOVs, moments and geometry AOV — TWK_ERROR_INVALID_STATE
+ * without twk_enable_geometry(1), with a geometry AOV older than the camera, the state or the scene (twk_render_geometry first), and
+ * on a packed tile buffer. Explicit buffers: a NULL geometry, or one the denoised buffer overlaps, is TWK_ERROR_INVALID_VALUE. The
+ * result goes where the three calls above put theirs. With a geometry of misses only the result is, bit for bit, that of the mode's
+ * own call. What it is not: a depth-gradient stop, a guide for lenses other than the pinhole or for cutout scenes (the geometry AOV
+ * refuses those), or a term of the firefly clamp's threshold. The float operations and their order: csrc/denoise_device.h. */
+typedef struct TwkDenoiserGeometry
+{
+  float sigmaPosition; /* distance from the centre's tangent plane, relative to the centre's distance from the camera */
+  int   instanceStop;  /* 1: a tap on another instance weighs 0 */
+} TwkDenoiserGeometry;
+#define TWK_DENOISER_SIGMA_POSITION 0.01f /* the pick of the sweep's rule: profiles/r20_denoise_geometry.md */
+/* sigmaPosition TWK_DENOISER_SIGMA_POSITION, instanceStop 0 */
+int twk_denoiser_geometry_defaults(TwkDenoiserGeometry* dg);
+int twk_denoise_geometry(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserGeometry* dg, const TwkDenoiserVariance* dv, int minSamples,
+                         const void* beauty, const void* albedo, const void* normal, const void* moments, const void* geometry,
+                         const float* camera, int width, int height, void* denoised);
+/* twk_denoise_geometry on the host: no handle, RGBA32F host buffers, the same definition compiled for the host (all three modes;
+ * camera must be given). How the definition is checked without a GPU. */
+int twk_denoise_geometry_host(const TwkDenoiser* dn, const TwkDenoiserGeometry* dg, const TwkDenoiserVariance* dv, int minSamples,
+                              const float* beauty, const float* albedo, const float* normal, const float* moments, const float* geometry,
+                              const float* camera, int width, int height, float* denoised);
 int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats);        /* RGBA32F, widened exactly, like twk_read_output */
 int twk_read_denoised_raw(TwkDevice dev, void* host, size_t bytes);             /* in the output format */
 int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes); /* feeds twk_tonemap / twk_tonemap_half */
@@ -1023,6 +1056,10 @@ int twk_app_get_denoiser_variance(TwkApp app, int* enabled, TwkDenoiserVariance*
  * twk_app_get_denoiser_variance, whatever "denoiserVariance" says). twk_app_init_device enables the moments when the key asks. */
 #define TWK_DENOISER_MIN_SAMPLES 4
 int twk_app_get_denoiser_sampled(TwkApp app, int* enabled, int* minSamples);
+/* "denoiserGeometry 0|1" (default 0), "denoiserSigmaPosition s", "denoiserInstanceStop 0|1": *enabled = the description asks for
+ * twk_denoise_geometry in the mode the other keys choose (it takes effect where "denoiser 3" is on), and its parameters
+ * (twk_denoiser_geometry_defaults where a key is absent). twk_app_init_device enables the geometry AOV when the key asks. */
+int twk_app_get_denoiser_geometry(TwkApp app, int* enabled, TwkDenoiserGeometry* dg);
 /* The stopping rule: "targetNoise e" (default 0 = off; e > 0 and finite), "targetNoiseQuantile q" (default 0.95; in (0, 1]),
  * "targetNoiseInterval n" (default 16; n >= 1). A value outside its range drops the line with a warning. *enabled = a target is
  * set: a render loop then calls twk_estimate_noise on every device after every *interval iterations, merges the summaries and ends

@@ -25,6 +25,7 @@ TWK_ERROR_INVALID_STATE, TWK_ERROR_OUT_OF_MEMORY, TWK_ERROR_IO, TWK_ERROR_PARSE 
 TWK_OUTPUT_FLOAT4, TWK_OUTPUT_HALF4 = 0, 1  # twk_set_output_format: RGBA32F (default), RGBA16F (≙ Optix7Gui USE_FP32_OUTPUT 0)
 
 TWK_DENOISER_RGB, TWK_DENOISER_RGB_ALBEDO, TWK_DENOISER_RGB_ALBEDO_NORMAL = 0, 1, 2  # TwkDenoiser.inputKind: the guides that weigh the taps
+TWK_DENOISER_SIGMA_POSITION = 0.01  # twk_denoiser_geometry_defaults (include/tweeker_hip.h)
 TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_variance_sampled (include/tweeker_hip.h)
 
 TWK_TEMPORAL_MAX_HISTORY, TWK_TEMPORAL_POSITION_TOLERANCE = 32, 0.01  # twk_temporal_defaults (include/tweeker_hip.h)
@@ -98,6 +99,15 @@ class DenoiserVariance(C.Structure):
 
     def __init__(self, fireflyThreshold=3.0, sigmaLuminance=4.0):
         super().__init__(fireflyThreshold, sigmaLuminance)
+
+
+class DenoiserGeometry(C.Structure):
+    """≙ TwkDenoiserGeometry: parameters of twk_denoise_geometry, the geometry guide of the filter (plane and instance stops from
+    the geometry AOV). Without arguments: twk_denoiser_geometry_defaults."""
+    _fields_ = [("sigmaPosition", C.c_float), ("instanceStop", C.c_int)]
+
+    def __init__(self, sigmaPosition=TWK_DENOISER_SIGMA_POSITION, instanceStop=0):
+        super().__init__(sigmaPosition, int(bool(instanceStop)))
 
 
 class Temporal(C.Structure):
@@ -262,6 +272,7 @@ SYMBOLS = [
     "twk_denoiser_defaults", "twk_denoise", "twk_read_denoised", "twk_read_denoised_raw", "twk_get_denoised_device_pointer", "twk_app_get_denoiser",
     "twk_denoiser_variance_defaults", "twk_denoise_variance", "twk_app_get_denoiser_variance",
     "twk_enable_moments", "twk_read_moments", "twk_get_moments_device_pointer", "twk_debug_read_path_radiance", "twk_denoise_variance_sampled", "twk_app_get_denoiser_sampled",
+    "twk_denoiser_geometry_defaults", "twk_denoise_geometry", "twk_denoise_geometry_host", "twk_app_get_denoiser_geometry",
     "twk_set_sample_offset", "twk_enable_geometry", "twk_render_geometry", "twk_read_geometry", "twk_get_geometry_device_pointer",
     "twk_temporal_defaults", "twk_temporal_accumulate", "twk_temporal_reset", "twk_get_temporal_device_pointers", "twk_read_temporal", "twk_read_temporal_moments",
     "twk_noise_defaults", "twk_estimate_noise", "twk_read_noise", "twk_noise_merge", "twk_noise_mean", "twk_noise_quantile", "twk_app_get_target_noise",

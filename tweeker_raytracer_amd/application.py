@@ -123,6 +123,15 @@ class Application:
         return bool(on.value), n.value
 
     @property
+    def denoiserGeometry(self):
+        """(enabled, DenoiserGeometry) from "denoiserGeometry", "denoiserSigmaPosition", "denoiserInstanceStop" of the system
+        description: enabled = twk_denoise_geometry stands in, in the mode the other keys choose, where `denoiser 3` is on;
+        initDevice enables the device's geometry AOV then."""
+        on, dg = C.c_int(0), L.DenoiserGeometry()
+        L.check(L.lib.twk_app_get_denoiser_geometry(self._h, C.byref(on), C.byref(dg)))
+        return bool(on.value), dg
+
+    @property
     def targetNoise(self):
         """(enabled, target, quantile, interval) from "targetNoise", "targetNoiseQuantile", "targetNoiseInterval" of the system
         description: a render loop checks Device.estimateNoise every `interval` iterations and ends once summary.quantile(quantile)

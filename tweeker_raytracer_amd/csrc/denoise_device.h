@@ -87,6 +87,40 @@
 //   out[p] = (cp.xyz clamped as above, var)
 // The clamp itself stays spatial: a firefly raises its own sample variance and must not vouch for itself. A product that
 // overflows gives an infinite (0 * inf: NaN) var, which the levels' variance blur skips like any other that is not finite.
+//
+// ---- the geometry guide (twk_denoise_geometry) -------------------------------------------------------------------------------
+// The geometric half of SVGF's edge-stopping function (Schied et al. 2017, section 4.4) as a fourth guide of the three modes
+// above, for inputKind RGB_ALBEDO_NORMAL only: a tap is weighed down by its distance from the centre's tangent plane, and, on
+// request, cut off at another instance. tests/denoise_geometry_restate.py restates it in numpy float32 and compares bits.
+// Further inputs: the geometry AOV, one float4 per pixel, always f32 and read where it lies (no staging copy in prepare):
+// (world position, bits of instance + 1), a miss (0, 0, 0, bits 0); and the camera it was traced from, P, U, V, W.
+//
+// host, once per call, in f32:  Un, Vn, Wn = normalize(U), normalize(V), normalize(W) (device_math.h; shade_device.h writes the
+//   normal AOV as (N.Un, N.Vn, -N.Wn) with the same three);  invPosition = 1.0f / (sigmaPosition * sigmaPosition)
+//   (refused unless invPosition is a finite positive float and Un, Vn, Wn are finite)
+//   dot3(a, b) = (a.x b.x + a.y b.y) + a.z b.z
+//
+// centre p, in the levels and in the moments pass, after the existing pass-through tests (np is finite here):
+//   gp = geometry[p];  a miss centre (bits(gp.w) == 0): no plane term, N and invG are not used
+//   a hit centre:  v = gp.xyz - P;  vv = dot3(v, v)
+//     N.k = (Un.k * np.x + Vn.k * np.y) - Wn.k * np.z      k = x, y, z     (the world-space normal back from the normal guide; NOT
+//       renormalised: an averaged normal shorter than 1 only weakens the stop)
+//     invG = invPosition / vv
+//     the pixel passes through the pass exactly as for a guide that is not finite (level: out[p] = cp; moments: out[p] =
+//     (cp.xyz, 0)) when gp.xyz is not finite, when vv is zero or not finite, or when N or invG is not finite. prepare and finish
+//     do not read the geometry: such a pixel's unfiltered colour goes through finish like any other.
+//     (The last two are added to the first statement of this guide: a tiny vv makes invG inf and a huge finite np makes N inf,
+//     and then the centre's own tap would have d = 0, (d * d) * invG = NaN or d = 0 * inf = NaN, weight 0, and wsum could be 0.
+//     With them the centre's own tap adds exactly 0 and wsum >= 9/64 stands.)
+//
+// tap q, one more term in t after the albedo term and before the t <= 87 cut-off (denoiseTap, denoiseVarianceTap, momentsTap):
+//   gq = geometry[q];  exactly one of bits(gp.w), bits(gq.w) is 0 (hit and miss never mix): weight 0
+//   both 0: nothing is added
+//   both hits:  instanceStop and bits(gp.w) != bits(gq.w): weight 0
+//     e = gq.xyz - gp.xyz;  d = dot3(e, N);  t = t + (d * d) * invG          (a NaN t gives weight 0, as above)
+// On a plane d is 0 at every step, so the term is not scaled by the level's step. sigmaPosition is a distance from the centre's
+// tangent plane relative to the centre's distance from the camera: TwkTemporal::positionTolerance's convention.
+// With a geometry of misses only, every tap adds nothing and the three modes compute the bits they compute without the guide.
 #pragma once
 #include "device_math.h"
 
@@ -113,6 +147,69 @@ TWK_HD float distance2(const float4& a, const float4& b)
   return (ex * ex + ey * ey) + ez * ez;
 }
 
+TWK_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+TWK_HD bool finite1(float v) { return (asUint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// ---- the geometry guide ----
+struct DenoiseGeometryConstants
+{
+  float P[3], Un[3], Vn[3], Wn[3]; // the camera the geometry AOV was traced from, U, V, W normalised
+  float invPosition;               // 1 / sigmaPosition^2
+  int   instanceStop;
+};
+
+// The host's part: cam = P, U, V, W (12 floats). False: the call is refused (sigmaPosition, or a camera vector that does not normalise).
+TWK_HD bool denoiseGeometryConstants(const float* cam, float sigmaPosition, int instanceStop, DenoiseGeometryConstants& g)
+{
+  const V3 Un = normalize(v3(cam[3], cam[4], cam[5])), Vn = normalize(v3(cam[6], cam[7], cam[8])), Wn = normalize(v3(cam[9], cam[10], cam[11]));
+  g.P[0] = cam[0]; g.P[1] = cam[1]; g.P[2] = cam[2];
+  g.Un[0] = Un.x; g.Un[1] = Un.y; g.Un[2] = Un.z;
+  g.Vn[0] = Vn.x; g.Vn[1] = Vn.y; g.Vn[2] = Vn.z;
+  g.Wn[0] = Wn.x; g.Wn[1] = Wn.y; g.Wn[2] = Wn.z;
+  g.invPosition = 1.0f / (sigmaPosition * sigmaPosition);
+  g.instanceStop = instanceStop ? 1 : 0;
+  bool ok = finite1(g.invPosition) && g.invPosition > 0.0f;
+  for (int i = 0; i < 3; ++i) ok = ok && finite1(g.P[i]) && finite1(g.Un[i]) && finite1(g.Vn[i]) && finite1(g.Wn[i]);
+  return ok;
+}
+
+// What a centre keeps for its taps, computed once per thread
+struct DenoiseGeometryCentre
+{
+  float4 gp;
+  float  nx, ny, nz, invG;
+  int    instanceStop;
+};
+
+// False: the pixel passes through
+TWK_HD bool denoiseGeometryCentre(const DenoiseGeometryConstants& g, const float4& gp, const float4& np, DenoiseGeometryCentre& c)
+{
+  c.gp = gp; c.nx = 0.0f; c.ny = 0.0f; c.nz = 0.0f; c.invG = 0.0f; c.instanceStop = g.instanceStop;
+  if (asUint(gp.w) == 0u) return true; // a miss: no plane term
+  if (!finite3(gp)) return false;
+  const float vx = gp.x - g.P[0], vy = gp.y - g.P[1], vz = gp.z - g.P[2];
+  const float vv = dot3(vx, vy, vz, vx, vy, vz);
+  if (!finite1(vv) || vv == 0.0f) return false;
+  c.nx = (g.Un[0] * np.x + g.Vn[0] * np.y) - g.Wn[0] * np.z;
+  c.ny = (g.Un[1] * np.x + g.Vn[1] * np.y) - g.Wn[1] * np.z;
+  c.nz = (g.Un[2] * np.x + g.Vn[2] * np.y) - g.Wn[2] * np.z;
+  c.invG = g.invPosition / vv;
+  return finite1(c.nx) && finite1(c.ny) && finite1(c.nz) && finite1(c.invG);
+}
+
+// The term of tap gq, added to t. False: weight 0
+TWK_HD bool denoiseGeometryTap(const DenoiseGeometryCentre& c, const float4& gq, float& t)
+{
+  const uint32_t bp = asUint(c.gp.w), bq = asUint(gq.w);
+  if ((bp == 0u) != (bq == 0u)) return false; // hit and miss never mix
+  if (bp == 0u) return true;
+  if (c.instanceStop && bp != bq) return false;
+  const float d = dot3(gq.x - c.gp.x, gq.y - c.gp.y, gq.z - c.gp.z, c.nx, c.ny, c.nz);
+  t = t + (d * d) * c.invG;
+  return true;
+}
+
 TWK_HD float stencilWeight(int d) // d = -2 .. 2: B3 spline 1/16, 1/4, 3/8, 1/4, 1/16
 {
   return (d == 0) ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f);
@@ -120,15 +217,17 @@ TWK_HD float stencilWeight(int d) // d = -2 .. 2: B3 spline 1/16, 1/4, 3/8, 1/4,
 
 TWK_HD float3 clampedAlbedo(const float4& a) { return make_float3(fmaxf(a.x, 0.01f), fmaxf(a.y, 0.01f), fmaxf(a.z, 0.01f)); }
 
-// One tap of a level: folds colour cq at stencil offset (dx, dy) into sum / wsum. KIND: TWK_DENOISER_*
-template<int KIND>
+// One tap of a level: folds colour cq at stencil offset (dx, dy) into sum / wsum. KIND: TWK_DENOISER_*; GEO: the geometry guide
+template<int KIND, bool GEO = false>
 TWK_HD void denoiseTap(const DenoiseConstants& k, int dx, int dy, const float4& cp, const float4& np, const float4& ap,
-                       const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum)
+                       const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum,
+                       const DenoiseGeometryCentre& gc = DenoiseGeometryCentre(), const float4& gq = float4())
 {
   if (!finite3(cq)) return;
   float t = distance2(cp, cq) * k.invColor;
   if (KIND >= 2) t = t + distance2(np, nq) * k.invNormal;
   if (KIND >= 1) t = t + distance2(ap, aq) * k.invAlbedo;
+  if (GEO) { if (!denoiseGeometryTap(gc, gq, t)) return; }
   if (!(t <= 87.0f)) return; // weight 0
   const float w = (stencilWeight(dy) * stencilWeight(dx)) * expP(-t);
   sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
@@ -139,19 +238,19 @@ TWK_HD void denoiseTap(const DenoiseConstants& k, int dx, int dy, const float4& 
 #define TWK_DENOISE_MOMENTS_RADIUS 3
 #define TWK_DENOISE_LUMINANCE_EPSILON 1e-3f
 
-TWK_HD bool finite1(float v) { return (asUint(v) & 0x7f800000u) != 0x7f800000u; }
-
 TWK_HD float luminance(const float4& c) { return luminance3(c.x, c.y, c.z); } // (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z
 
 // One tap of the moments pass: folds the luminance lq of a tap with a finite colour into s0, s1, s2
-template<int KIND>
-TWK_HD void momentsTap(const DenoiseConstants& k, const float4& np, const float4& ap, float lq, const float4& nq, const float4& aq, float& s0, float& s1, float& s2)
+template<int KIND, bool GEO = false>
+TWK_HD void momentsTap(const DenoiseConstants& k, const float4& np, const float4& ap, float lq, const float4& nq, const float4& aq, float& s0, float& s1, float& s2,
+                       const DenoiseGeometryCentre& gc = DenoiseGeometryCentre(), const float4& gq = float4())
 {
   float g = 1.0f;
   if (KIND >= 1)
   {
     float t = distance2(ap, aq) * k.invAlbedo;
     if (KIND >= 2) t = distance2(np, nq) * k.invNormal + t;
+    if (GEO) { if (!denoiseGeometryTap(gc, gq, t)) return; }
     if (!(t <= 87.0f)) return;
     g = expP(-t);
   }
@@ -207,14 +306,16 @@ TWK_HD float inverseLuminanceSigma(const DenoiseConstants& k, float vs, float bs
 }
 
 // One tap of a level of the variance-guided mode: like denoiseTap with the luminance edge-stop, and the variance filtered along
-template<int KIND>
+template<int KIND, bool GEO = false>
 TWK_HD void denoiseVarianceTap(const DenoiseConstants& k, int dx, int dy, float lp, float invL, const float4& np, const float4& ap,
-                               const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum, float& vsum)
+                               const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum, float& vsum,
+                               const DenoiseGeometryCentre& gc = DenoiseGeometryCentre(), const float4& gq = float4())
 {
   if (!finite3(cq)) return;
   float t = fabsf(lp - luminance(cq)) * invL;
   if (KIND >= 2) t = t + distance2(np, nq) * k.invNormal;
   if (KIND >= 1) t = t + distance2(ap, aq) * k.invAlbedo;
+  if (GEO) { if (!denoiseGeometryTap(gc, gq, t)) return; }
   if (!(t <= 87.0f)) return; // weight 0
   const float w = (stencilWeight(dy) * stencilWeight(dx)) * expP(-t);
   sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;

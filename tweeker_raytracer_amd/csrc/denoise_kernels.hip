@@ -44,9 +44,11 @@ __global__ void __launch_bounds__(256) denoisePrepareKernel(const Pixel* __restr
 
 // VAR: the level of the variance-guided mode (denoise_device.h): luminance edge-stop scaled by the 3 x 3 binomial of the variance in
 // in[].w at the level's own step (the inner 3 x 3 of the taps the level loads anyway), the variance filtered along into out[].w
-template<int KIND, bool VAR>
+// GEO: the geometry guide (denoise_device.h; KIND 2 only): one more 16-byte stream per tap, read where the caller keeps it; the
+// centre's normal and invG once per thread. The GEO = false builds read neither of the two last arguments.
+template<int KIND, bool VAR, bool GEO = false>
 __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
-                                                          float4* __restrict__ out, DenoiseConstants k, int step)
+                                                          float4* __restrict__ out, DenoiseConstants k, int step, const float4* __restrict__ geometry, DenoiseGeometryConstants g)
 {
   const int x = (int) blockIdx.x * TWK_DENOISE_TILE_X + (int) (threadIdx.x % TWK_DENOISE_TILE_X);
   const int y = (int) blockIdx.y * TWK_DENOISE_TILE_Y + (int) (threadIdx.x / TWK_DENOISE_TILE_X);
@@ -57,6 +59,8 @@ __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restri
   const float4 np = (KIND >= 2) ? guideNormal[p] : zero;
   const float4 ap = (KIND >= 1) ? guideAlbedo[p] : zero;
   if (!finite3(cp) || !finite3(np) || !finite3(ap)) { out[p] = cp; return; }
+  DenoiseGeometryCentre gc;
+  if (GEO) { if (!denoiseGeometryCentre(g, geometry[p], np, gc)) { out[p] = cp; return; } }
   float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
   if (VAR)
   {
@@ -93,8 +97,14 @@ __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restri
       const float4 cq = in[q];
       const float4 nq = (KIND >= 2) ? guideNormal[q] : zero;
       const float4 aq = (KIND >= 1) ? guideAlbedo[q] : zero;
-      if (VAR) denoiseVarianceTap<KIND>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum);
-      else     denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
+      if (GEO)
+      {
+        const float4 gq = geometry[q];
+        if (VAR) denoiseVarianceTap<KIND, true>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum, gc, gq);
+        else     denoiseTap<KIND, true>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum, gc, gq);
+      }
+      else if (VAR) denoiseVarianceTap<KIND>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum);
+      else          denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
     }
   }
   out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, VAR ? vsum / (wsum * wsum) : cp.w);
@@ -109,14 +119,17 @@ __global__ void __launch_bounds__(256) denoiseLevelKernel(const float4* __restri
 // its own, which is where this build stops paying.
 #define TWK_DENOISE_LDS_X (TWK_DENOISE_TILE_X + 4)
 #define TWK_DENOISE_LDS_Y (TWK_DENOISE_TILE_Y + 4)
-template<int KIND, bool VAR>
+// GEO: the geometry is staged as a fourth 36 x 12 array (27.6 KB per block instead of 20.7); outside the picture it is staged as a
+// miss, and the tap is skipped for its NaN colour before the geometry is looked at.
+template<int KIND, bool VAR, bool GEO = false>
 __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
-                                                             float4* __restrict__ out, DenoiseConstants k, int step)
+                                                             float4* __restrict__ out, DenoiseConstants k, int step, const float4* __restrict__ geometry, DenoiseGeometryConstants g)
 {
   constexpr int STAGED = TWK_DENOISE_LDS_X * TWK_DENOISE_LDS_Y;
   __shared__ float4 colour[STAGED];
   __shared__ float4 normal[KIND >= 2 ? STAGED : 1];
   __shared__ float4 albedo[KIND >= 1 ? STAGED : 1];
+  __shared__ float4 position[GEO ? STAGED : 1];
   const int rx = (int) blockIdx.x % step, tx = (int) blockIdx.x / step;
   const int ry = (int) blockIdx.y % step, ty = (int) blockIdx.y / step;
   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -124,17 +137,19 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
   {
     const int gx = rx + (tx * TWK_DENOISE_TILE_X - 2 + i % TWK_DENOISE_LDS_X) * step;
     const int gy = ry + (ty * TWK_DENOISE_TILE_Y - 2 + i / TWK_DENOISE_LDS_X) * step;
-    float4 c = make_float4(asFloat(0x7fc00000u), 0.0f, 0.0f, 0.0f), n = zero, a = zero;
+    float4 c = make_float4(asFloat(0x7fc00000u), 0.0f, 0.0f, 0.0f), n = zero, a = zero, gg = zero;
     if (gx >= 0 && gx < k.width && gy >= 0 && gy < k.height)
     {
       const size_t q = (size_t) gy * k.width + gx;
       c = in[q];
       if (KIND >= 2) n = guideNormal[q];
       if (KIND >= 1) a = guideAlbedo[q];
+      if (GEO) gg = geometry[q];
     }
     colour[i] = c;
     if (KIND >= 2) normal[i] = n;
     if (KIND >= 1) albedo[i] = a;
+    if (GEO) position[i] = gg;
   }
   __syncthreads();
   const int lx = (int) (threadIdx.x % TWK_DENOISE_TILE_X), ly = (int) (threadIdx.x / TWK_DENOISE_TILE_X);
@@ -147,6 +162,8 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
   const float4 np = (KIND >= 2) ? normal[centre] : zero;
   const float4 ap = (KIND >= 1) ? albedo[centre] : zero;
   if (!finite3(cp) || !finite3(np) || !finite3(ap)) { out[p] = cp; return; }
+  DenoiseGeometryCentre gc;
+  if (GEO) { if (!denoiseGeometryCentre(g, position[centre], np, gc)) { out[p] = cp; return; } }
   float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
   if (VAR)
   {
@@ -172,8 +189,14 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
       const float4 cq = colour[q];
       const float4 nq = (KIND >= 2) ? normal[q] : zero;
       const float4 aq = (KIND >= 1) ? albedo[q] : zero;
-      if (VAR) denoiseVarianceTap<KIND>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum);
-      else     denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
+      if (GEO)
+      {
+        const float4 gq = position[q];
+        if (VAR) denoiseVarianceTap<KIND, true>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum, gc, gq);
+        else     denoiseTap<KIND, true>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum, gc, gq);
+      }
+      else if (VAR) denoiseVarianceTap<KIND>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum);
+      else          denoiseTap<KIND>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum);
     }
   }
   out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, VAR ? vsum / (wsum * wsum) : cp.w);
@@ -188,14 +211,17 @@ __global__ void __launch_bounds__(256) denoiseLevelLdsKernel(const float4* __res
 #define TWK_DENOISE_MOMENTS_Y (TWK_DENOISE_TILE_Y + 2 * TWK_DENOISE_MOMENTS_RADIUS)
 // SAMPLED (twk_denoise_variance_sampled): one more coalesced load per pixel, its luminance moments (mean, M2, n, .) as the
 // accumulate kernels fold them; momentsFinish writes the measured variance of the pixel's mean where n >= minSamples.
-template<int KIND, bool SAMPLED>
+// GEO: the geometry guide, staged beside the other guides (8.5 KB more); the GEO = false builds read neither of the two last arguments
+template<int KIND, bool SAMPLED, bool GEO = false>
 __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __restrict__ in, const float4* __restrict__ guideNormal, const float4* __restrict__ guideAlbedo,
-                                                            float4* __restrict__ out, DenoiseConstants k, const float4* __restrict__ sampled, float minSamples)
+                                                            float4* __restrict__ out, DenoiseConstants k, const float4* __restrict__ sampled, float minSamples,
+                                                            const float4* __restrict__ geometry, DenoiseGeometryConstants g)
 {
   constexpr int STAGED = TWK_DENOISE_MOMENTS_X * TWK_DENOISE_MOMENTS_Y;
   __shared__ float  lum[STAGED];
   __shared__ float4 normal[KIND >= 2 ? STAGED : 1];
   __shared__ float4 albedo[KIND >= 1 ? STAGED : 1];
+  __shared__ float4 position[GEO ? STAGED : 1];
   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   const int x0 = (int) blockIdx.x * TWK_DENOISE_TILE_X, y0 = (int) blockIdx.y * TWK_DENOISE_TILE_Y;
   for (int i = (int) threadIdx.x; i < STAGED; i += 256)
@@ -203,7 +229,7 @@ __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __rest
     const int gx = x0 - TWK_DENOISE_MOMENTS_RADIUS + i % TWK_DENOISE_MOMENTS_X;
     const int gy = y0 - TWK_DENOISE_MOMENTS_RADIUS + i / TWK_DENOISE_MOMENTS_X;
     float l = asFloat(0x7fc00000u);
-    float4 n = zero, a = zero;
+    float4 n = zero, a = zero, gg = zero;
     if (gx >= 0 && gx < k.width && gy >= 0 && gy < k.height)
     {
       const size_t q = (size_t) gy * k.width + gx;
@@ -211,10 +237,12 @@ __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __rest
       if (finite3(c)) l = luminance(c);
       if (KIND >= 2) n = guideNormal[q];
       if (KIND >= 1) a = guideAlbedo[q];
+      if (GEO) gg = geometry[q];
     }
     lum[i] = l;
     if (KIND >= 2) normal[i] = n;
     if (KIND >= 1) albedo[i] = a;
+    if (GEO) position[i] = gg;
   }
   __syncthreads();
   const int lx = (int) (threadIdx.x % TWK_DENOISE_TILE_X), ly = (int) (threadIdx.x / TWK_DENOISE_TILE_X);
@@ -226,6 +254,8 @@ __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __rest
   const float4 np = (KIND >= 2) ? normal[centre] : zero;
   const float4 ap = (KIND >= 1) ? albedo[centre] : zero;
   if (!finite3(cp) || !finite1(lum[centre]) || !finite3(np) || !finite3(ap)) { out[p] = make_float4(cp.x, cp.y, cp.z, 0.0f); return; }
+  DenoiseGeometryCentre gc;
+  if (GEO) { if (!denoiseGeometryCentre(g, position[centre], np, gc)) { out[p] = make_float4(cp.x, cp.y, cp.z, 0.0f); return; } }
   float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
   for (int dy = -TWK_DENOISE_MOMENTS_RADIUS; dy <= TWK_DENOISE_MOMENTS_RADIUS; ++dy)
@@ -239,7 +269,8 @@ __global__ void __launch_bounds__(256) denoiseMomentsKernel(const float4* __rest
       if ((asUint(lq) & 0x7fffffffu) > 0x7f800000u) continue; // NaN: outside, or a colour that is not finite
       const float4 nq = (KIND >= 2) ? normal[q] : zero;
       const float4 aq = (KIND >= 1) ? albedo[q] : zero;
-      momentsTap<KIND>(k, np, ap, lq, nq, aq, s0, s1, s2);
+      if (GEO) momentsTap<KIND, true>(k, np, ap, lq, nq, aq, s0, s1, s2, gc, position[q]);
+      else     momentsTap<KIND>(k, np, ap, lq, nq, aq, s0, s1, s2);
     }
   }
   if (SAMPLED) out[p] = momentsFinish<true>(k, cp, s0, s1, s2, sampled[p], minSamples);
@@ -288,22 +319,31 @@ void launchDenoisePrepare(const void* beauty, const void* albedo, const void* no
                                static_cast<const float4*>(normal), colour, guideNormal, guideAlbedo, k);
 }
 
-template<int KIND, bool VAR>
-static void launchDenoiseLevelOf(bool lds, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream)
+template<int KIND, bool VAR, bool GEO = false>
+static void launchDenoiseLevelOf(bool lds, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream,
+                                 const float4* geometry = nullptr, const DenoiseGeometryConstants& g = DenoiseGeometryConstants())
 {
   if (lds)
   {
     const dim3 ldsGrid(((k.width + step - 1) / step + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X * step, ((k.height + step - 1) / step + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y * step);
-    hipLaunchKernelGGL((denoiseLevelLdsKernel<KIND, VAR>), ldsGrid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
+    hipLaunchKernelGGL((denoiseLevelLdsKernel<KIND, VAR, GEO>), ldsGrid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step, geometry, g);
     return;
   }
   const dim3 grid((k.width + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X, (k.height + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y);
-  hipLaunchKernelGGL((denoiseLevelKernel<KIND, VAR>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step);
+  hipLaunchKernelGGL((denoiseLevelKernel<KIND, VAR, GEO>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, step, geometry, g);
 }
 
 // lds: the LDS-staged build of the level (one residue class modulo the step per block); variance: the level of the variance-guided mode
-void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream)
+// geometry != NULL (kind RGB_ALBEDO_NORMAL only, the caller's check): the GEO builds, with the camera and sigma of *g
+void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream,
+                        const float4* geometry, const DenoiseGeometryConstants* g)
 {
+  if (geometry)
+  {
+    if (variance) launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO_NORMAL, true, true>(lds, in, guideNormal, guideAlbedo, out, k, step, stream, geometry, *g);
+    else          launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO_NORMAL, false, true>(lds, in, guideNormal, guideAlbedo, out, k, step, stream, geometry, *g);
+    return;
+  }
   if (variance)
   {
     if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) launchDenoiseLevelOf<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(lds, in, guideNormal, guideAlbedo, out, k, step, stream);
@@ -318,21 +358,24 @@ void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, con
 
 template<bool SAMPLED>
 static void launchDenoiseMomentsOf(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k,
-                                   const float4* sampled, float minSamples, hipStream_t stream)
+                                   const float4* sampled, float minSamples, hipStream_t stream, const float4* geometry, const DenoiseGeometryConstants* g)
 {
   const dim3 grid((k.width + TWK_DENOISE_TILE_X - 1) / TWK_DENOISE_TILE_X, (k.height + TWK_DENOISE_TILE_Y - 1) / TWK_DENOISE_TILE_Y);
-  if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples);
-  else if (kind == TWK_DENOISER_RGB_ALBEDO)   hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples);
-  else                                        hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples);
+  const DenoiseGeometryConstants none = DenoiseGeometryConstants();
+  if (geometry)                                    hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL, SAMPLED, true>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, geometry, *g);
+  else if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO_NORMAL, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, geometry, none);
+  else if (kind == TWK_DENOISER_RGB_ALBEDO)        hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB_ALBEDO, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, geometry, none);
+  else                                             hipLaunchKernelGGL((denoiseMomentsKernel<TWK_DENOISER_RGB, SAMPLED>), grid, dim3(256), 0, stream, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, geometry, none);
 }
 
 // the moments + firefly-clamp pass of the variance-guided mode, between prepare and level 0. sampled != NULL: the SAMPLED build —
 // width x height luminance moments (mean, M2, n, .), whose measured variance stands in for the spatial one from minSamples samples on
+// geometry != NULL (kind RGB_ALBEDO_NORMAL only): the GEO builds
 void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k,
-                          const float4* sampled, float minSamples, hipStream_t stream)
+                          const float4* sampled, float minSamples, hipStream_t stream, const float4* geometry, const DenoiseGeometryConstants* g)
 {
-  if (sampled) launchDenoiseMomentsOf<true>(kind, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, stream);
-  else         launchDenoiseMomentsOf<false>(kind, in, guideNormal, guideAlbedo, out, k, nullptr, 0.0f, stream);
+  if (sampled) launchDenoiseMomentsOf<true>(kind, in, guideNormal, guideAlbedo, out, k, sampled, minSamples, stream, geometry, g);
+  else         launchDenoiseMomentsOf<false>(kind, in, guideNormal, guideAlbedo, out, k, nullptr, 0.0f, stream, geometry, g);
 }
 
 // guideNormal / guideAlbedo NULL: the kind does not use the guide

@@ -154,7 +154,7 @@ static void readEnvironmentSwitches(TwkDevice_t* dev)
   if (const char* e = getenv("TWK_PACKED_QUEUE")) dev->packedQueue = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SLIM_STREAMS")) dev->slimStreams = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SHADE_SORT")) dev->shadeSort = std::max(0, std::min(2, atoi(e)));
-  if (const char* e = getenv("TWK_DENOISE_LDS_MAX_STEP")) dev->denoiseLdsMaxStep = std::max(0, std::min(128, atoi(e))); // A/B; 128 = the largest step (iterations <= 8)
+  if (const char* e = getenv("TWK_DENOISE_LDS_MAX_STEP")) dev->denoiseLdsMaxStep = dev->denoiseGeometryLdsMaxStep = std::max(0, std::min(128, atoi(e))); // A/B; 128 = the largest step (iterations <= 8)
   if (const char* e = getenv("TWK_TRACE_WAVES_RUNTIME")) dev->traceWavesForced = atoi(e); // A/B: 6 or 7 blocks per CU of the persistent trace kernel
   if (const char* e = getenv("TWK_BUILD_QUALITY")) dev->builder.setQuality(atoi(e)); // A/B: 0 LBVH, 1 binned SAH (default)
   if (const char* e = getenv("TWK_STREAM_BUDGET_MB")) { const long long mb = atoll(e); dev->streamBudgetBytes = (mb > 0) ? (size_t) mb << 20 : 0; }

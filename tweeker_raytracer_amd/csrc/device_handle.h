@@ -36,8 +36,10 @@ void launchGatherProbe(const float4* table, unsigned int lines, int steps, float
 void launchTonemap(const void* hdr, bool half, unsigned char* ldr, size_t numPixels, const TwkTonemapper& tm, hipStream_t stream);
 void launchDenoisePrepare(const void* beauty, const void* albedo, const void* normal, bool half, float4* colour, float4* guideNormal, float4* guideAlbedo,
                           const DenoiseConstants& k, hipStream_t stream);
-void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, const float4* sampled, float minSamples, hipStream_t stream);
-void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream);
+void launchDenoiseMoments(int kind, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, const float4* sampled, float minSamples, hipStream_t stream,
+                          const float4* geometry = nullptr, const DenoiseGeometryConstants* g = nullptr);
+void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, const float4* guideNormal, const float4* guideAlbedo, float4* out, const DenoiseConstants& k, int step, hipStream_t stream,
+                        const float4* geometry = nullptr, const DenoiseGeometryConstants* g = nullptr);
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
 void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
@@ -219,6 +221,7 @@ struct TwkDevice_t
   // plane (TWK_PLANE_COUNT stays 6): freed with the other assembled buffers (dropAssembled), and stale (assembledGeometryValid
   // false, the buffer kept) once this handle's camera, state or scene changes — staleGeometry, which is what clears geometryValid
   void* d_assembledGeometry = nullptr; size_t assembledGeometryBytes = 0; bool assembledGeometryValid = false;
+  int denoiseGeometryLdsMaxStep = 16; // the same border for the GEO builds (twk_denoise_geometry, four streams per tap): staged also wins at steps 8 and 16, by 0.04 ms each at 1080p (profiles/r20_denoise_geometry.md); steps above 16 are not measured and stay direct; TWK_DENOISE_LDS_MAX_STEP sets both
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
   bool statsEnabled = false;

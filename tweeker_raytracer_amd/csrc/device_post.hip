@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 // Frees the streams of twk_temporal_accumulate's own-buffer form: the next call has no history
 void twk::dropTemporal(TwkDevice dev)
@@ -141,14 +142,22 @@ static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
 static bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
 
 // twk_denoise (dv NULL), twk_denoise_variance and twk_denoise_variance_sampled (minSamples > 0; `moments`: the caller's buffer
-// beside an explicit beauty): `name` is the entry point, for its error texts
+// beside an explicit beauty): `name` is the entry point, for its error texts. dg (twk_denoise_geometry): the geometry guide, with
+// `geometry` the caller's buffer beside an explicit beauty and `camera` (12 floats P, U, V, W; NULL: the handle's camera 0) the one
+// the geometry was traced from
 static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const void* beauty, const void* albedo, const void* normal, int width, int height, void* denoised,
-                   int minSamples = 0, const void* moments = nullptr)
+                   int minSamples = 0, const void* moments = nullptr, const TwkDenoiserGeometry* dg = nullptr, const void* geometry = nullptr, const float* camera = nullptr)
 {
   const bool sampled = (minSamples > 0);
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
   const int kind = dn->inputKind;
   if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "unknown inputKind");
+  if (dg)
+  {
+    if (kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "the geometry guide needs inputKind TWK_DENOISER_RGB_ALBEDO_NORMAL (the plane's normal comes from the normal guide)");
+    const float invPosition = 1.0f / (dg->sigmaPosition * dg->sigmaPosition);
+    if (!(dg->sigmaPosition > 0.0f) || !std::isfinite(invPosition) || !(invPosition > 0.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaPosition must be > 0 and 1 / sigmaPosition^2 a finite positive float");
+  }
   if (dn->iterations < 0 || dn->iterations > 8) return refuse(TWK_ERROR_INVALID_VALUE, "iterations must be in [0, 8]");
   if ((!dv && !(dn->sigmaColor > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
     return refuse(TWK_ERROR_INVALID_VALUE, "the sigma of every guide in use must be positive");
@@ -170,7 +179,7 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
   const bool own = (beauty == nullptr);
   if (own)
   {
-    if (albedo || normal || moments) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
+    if (albedo || normal || moments || geometry) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
     if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
     if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
     beauty = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
@@ -189,6 +198,13 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
         return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
       moments = dev->d_moments;
     }
+    if (dg)
+    {
+      if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < (size_t) width * height)
+        return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+      if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
+      geometry = dev->d_geometry;
+    }
   }
   else
   {
@@ -197,8 +213,20 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     if (kind < TWK_DENOISER_RGB_ALBEDO) albedo = nullptr;        // guides the kind does not use are not read
     if (kind < TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = nullptr;
     if (sampled && !moments) return refuse(TWK_ERROR_INVALID_VALUE, "NULL moments buffer beside an explicit beauty buffer");
+    if (dg && !geometry) return refuse(TWK_ERROR_INVALID_VALUE, "NULL geometry buffer beside an explicit beauty buffer");
   }
   const size_t numPixels = (size_t) width * height, bytes = numPixels * pixelBytes(dev);
+  DenoiseGeometryConstants g = DenoiseGeometryConstants();
+  if (dg)
+  {
+    if (!camera)
+    {
+      if (dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "no camera given and the handle has none: twk_init_cameras first");
+      camera = dev->cameras[0].P;
+    }
+    if (!denoiseGeometryConstants(camera, dg->sigmaPosition, dg->instanceStop, g)) return refuse(TWK_ERROR_INVALID_VALUE, "the camera is degenerate: P is not finite, or U, V or W does not normalise");
+    if (overlaps(denoised, bytes, geometry, numPixels * sizeof(float4))) return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
+  }
   if (denoised && (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes) || (sampled && overlaps(denoised, bytes, moments, numPixels * sizeof(float4)))))
     return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
 
@@ -242,9 +270,13 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     // the variance-guided mode: prepare writes the pong stream and the moments pass the ping stream (clamped colour, variance in
     // .w), so that the levels ping-pong as without it and the mode needs no stream of its own
     launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[dv ? 1 : 0], guideNormal, guideAlbedo, k, dev->stream);
-    if (dv) launchDenoiseMoments(kind, colour[1], guideNormal, guideAlbedo, colour[0], k, sampled ? static_cast<const float4*>(moments) : nullptr, (float) minSamples, dev->stream);
+    // the geometry guide: its stream is read where it lies (already f32). With four streams per tap the staged build of the level
+    // wins up to step 16 (measured per step, profiles/r20_denoise_geometry.md), so the GEO builds have a border of their own.
+    const int ldsMaxStep = dg ? dev->denoiseGeometryLdsMaxStep : dev->denoiseLdsMaxStep;
+    const float4* guideGeometry = dg ? static_cast<const float4*>(geometry) : nullptr;
+    if (dv) launchDenoiseMoments(kind, colour[1], guideNormal, guideAlbedo, colour[0], k, sampled ? static_cast<const float4*>(moments) : nullptr, (float) minSamples, dev->stream, guideGeometry, &g);
     for (int level = 0; level < dn->iterations; ++level)
-      launchDenoiseLevel(kind, (1 << level) <= dev->denoiseLdsMaxStep, dv != nullptr, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream);
+      launchDenoiseLevel(kind, (1 << level) <= ldsMaxStep, dv != nullptr, colour[level & 1], guideNormal, guideAlbedo, colour[(level + 1) & 1], k, 1 << level, dev->stream, guideGeometry, &g);
     launchDenoiseFinish(beauty, halfOutput(dev), colour[dn->iterations & 1], normal ? guideNormal : nullptr, albedo ? guideAlbedo : nullptr, target, k, dev->stream);
     HIP_TRY(hipGetLastError());
   }
@@ -290,6 +322,169 @@ try
   return denoise("twk_denoise_variance_sampled", dev, dn, dv, beauty, albedo, normal, width, height, denoised, minSamples, moments);
 }
 TWK_CATCH("twk_denoise_variance_sampled")
+
+int twk_denoiser_geometry_defaults(TwkDenoiserGeometry* dg)
+try
+{
+  if (!dg) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoiser_geometry_defaults: NULL argument");
+  dg->sigmaPosition = TWK_DENOISER_SIGMA_POSITION;
+  dg->instanceStop = 0;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoiser_geometry_defaults")
+
+int twk_denoise_geometry(TwkDevice dev, const TwkDenoiser* dn, const TwkDenoiserGeometry* dg, const TwkDenoiserVariance* dv, int minSamples, const void* beauty, const void* albedo,
+                         const void* normal, const void* moments, const void* geometry, const float* camera, int width, int height, void* denoised)
+try
+{
+  const char* name = "twk_denoise_geometry";
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: NULL device handle");
+  if (!dn || !dg) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: NULL parameters");
+  if (minSamples != 0 && !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: minSamples without the parameters of the variance-guided mode");
+  if (minSamples != 0 && minSamples < 2) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: minSamples must be 0 (no sampled variance) or >= 2 (one sample has no variance)");
+  if (minSamples == 0 && moments) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: a moments buffer without minSamples");
+  return denoise(name, dev, dn, dv, beauty, albedo, normal, width, height, denoised, minSamples, moments, dg, geometry, camera);
+}
+TWK_CATCH("twk_denoise_geometry")
+
+// The host form: the kernels of denoise_kernels.hip as loops over the same shared functions (denoise_device.h compiled for the
+// host), RGBA32F, all three modes. The pixels of a pass are independent, so the order of the loops plays no part.
+namespace {
+struct HostDenoise
+{
+  int width, height;
+  DenoiseConstants k;
+  DenoiseGeometryConstants g;
+  const float4 *normal, *albedo, *geometry;
+
+  bool inside(int x, int y) const { return x >= 0 && x < width && y >= 0 && y < height; }
+
+  void moments(const float4* in, float4* out, const float4* sampled, float minSamples) const
+  {
+    for (int y = 0; y < height; ++y) for (int x = 0; x < width; ++x)
+    {
+      const size_t p = (size_t) y * width + x;
+      const float4 cp = in[p], np = normal[p], ap = albedo[p];
+      DenoiseGeometryCentre gc;
+      if (!finite3(cp) || !finite1(luminance(cp)) || !finite3(np) || !finite3(ap) || !denoiseGeometryCentre(g, geometry[p], np, gc)) { out[p] = make_float4(cp.x, cp.y, cp.z, 0.0f); continue; }
+      float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+      for (int dy = -TWK_DENOISE_MOMENTS_RADIUS; dy <= TWK_DENOISE_MOMENTS_RADIUS; ++dy) for (int dx = -TWK_DENOISE_MOMENTS_RADIUS; dx <= TWK_DENOISE_MOMENTS_RADIUS; ++dx)
+      {
+        if ((dx == 0 && dy == 0) || !inside(x + dx, y + dy)) continue;
+        const size_t q = (size_t) (y + dy) * width + (x + dx);
+        if (!finite3(in[q])) continue;
+        momentsTap<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(k, np, ap, luminance(in[q]), normal[q], albedo[q], s0, s1, s2, gc, geometry[q]);
+      }
+      out[p] = sampled ? momentsFinish<true>(k, cp, s0, s1, s2, sampled[p], minSamples) : momentsFinish(k, cp, s0, s1, s2);
+    }
+  }
+
+  void level(const float4* in, float4* out, int step, bool variance) const
+  {
+    for (int y = 0; y < height; ++y) for (int x = 0; x < width; ++x)
+    {
+      const size_t p = (size_t) y * width + x;
+      const float4 cp = in[p], np = normal[p], ap = albedo[p];
+      DenoiseGeometryCentre gc;
+      if (!finite3(cp) || !finite3(np) || !finite3(ap) || !denoiseGeometryCentre(g, geometry[p], np, gc)) { out[p] = cp; continue; }
+      float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
+      if (variance)
+      {
+        lp = luminance(cp);
+        if (!finite1(lp)) { out[p] = cp; continue; }
+        float vs = 0.0f, bs = 0.0f;
+        for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx)
+          if (inside(x + dx * step, y + dy * step)) varianceBlurTap(dx, dy, in[(size_t) (y + dy * step) * width + (x + dx * step)], vs, bs);
+        invL = inverseLuminanceSigma(k, vs, bs);
+      }
+      float sx = 0.0f, sy = 0.0f, sz = 0.0f, wsum = 0.0f;
+      for (int dy = -2; dy <= 2; ++dy) for (int dx = -2; dx <= 2; ++dx)
+      {
+        if (!inside(x + dx * step, y + dy * step)) continue;
+        const size_t q = (size_t) (y + dy * step) * width + (x + dx * step);
+        if (variance) denoiseVarianceTap<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(k, dx, dy, lp, invL, np, ap, in[q], normal[q], albedo[q], sx, sy, sz, wsum, vsum, gc, geometry[q]);
+        else          denoiseTap<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(k, dx, dy, cp, np, ap, in[q], normal[q], albedo[q], sx, sy, sz, wsum, gc, geometry[q]);
+      }
+      out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, variance ? vsum / (wsum * wsum) : cp.w);
+    }
+  }
+};
+} // namespace
+
+int twk_denoise_geometry_host(const TwkDenoiser* dn, const TwkDenoiserGeometry* dg, const TwkDenoiserVariance* dv, int minSamples, const float* beauty, const float* albedo,
+                              const float* normal, const float* moments, const float* geometry, const float* camera, int width, int height, float* denoised)
+try
+{
+  const char* name = "twk_denoise_geometry_host";
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  if (!dn || !dg) return refuse(TWK_ERROR_INVALID_VALUE, "NULL parameters");
+  if (dn->inputKind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "the geometry guide needs inputKind TWK_DENOISER_RGB_ALBEDO_NORMAL (the plane's normal comes from the normal guide)");
+  if (dn->iterations < 0 || dn->iterations > 8) return refuse(TWK_ERROR_INVALID_VALUE, "iterations must be in [0, 8]");
+  const float sigmas[3] = {dv ? 1.0f : dn->sigmaColor, dn->sigmaNormal, dn->sigmaAlbedo};
+  for (const float sigma : sigmas)
+    if (!(sigma > 0.0f) || !std::isfinite(1.0f / (sigma * sigma))) return refuse(TWK_ERROR_INVALID_VALUE, "the sigma of every guide in use must be positive and 1 / sigma^2 a finite float");
+  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "blendFactor must be in [0, 1]");
+  if (dv)
+  {
+    if (!(dv->fireflyThreshold >= 0.0f) || !std::isfinite(dv->fireflyThreshold)) return refuse(TWK_ERROR_INVALID_VALUE, "fireflyThreshold must be >= 0 (0 = no clamp) and finite");
+    if (!(dv->sigmaLuminance > 0.0f) || !std::isfinite(dv->sigmaLuminance)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaLuminance must be > 0 and finite");
+  }
+  if (minSamples != 0 && (!dv || minSamples < 2)) return refuse(TWK_ERROR_INVALID_VALUE, "minSamples must be 0 (no sampled variance) or >= 2 beside the parameters of the variance-guided mode");
+  if ((minSamples != 0) != (moments != nullptr)) return refuse(TWK_ERROR_INVALID_VALUE, "a moments buffer goes with minSamples >= 2, and only with it");
+  {
+    const float invPosition = 1.0f / (dg->sigmaPosition * dg->sigmaPosition);
+    if (!(dg->sigmaPosition > 0.0f) || !std::isfinite(invPosition) || !(invPosition > 0.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaPosition must be > 0 and 1 / sigmaPosition^2 a finite positive float");
+  }
+  if (width < 1 || height < 1) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
+  if (!beauty || !albedo || !normal || !geometry || !camera || !denoised) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer or camera");
+  const size_t n = (size_t) width * height, bytes = n * sizeof(float4);
+  if (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes) || overlaps(denoised, geometry, bytes) || overlaps(denoised, moments, bytes))
+    return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
+  HostDenoise h;
+  if (!denoiseGeometryConstants(camera, dg->sigmaPosition, dg->instanceStop, h.g)) return refuse(TWK_ERROR_INVALID_VALUE, "the camera is degenerate: P is not finite, or U, V or W does not normalise");
+  if (dn->iterations == 0 || dn->blendFactor == 1.0f) { memcpy(denoised, beauty, bytes); return TWK_SUCCESS; }
+  const float4* b = reinterpret_cast<const float4*>(beauty);
+  h.width = width; h.height = height;
+  h.k.width = width; h.k.height = height;
+  h.k.invColor  = dv ? 0.0f : 1.0f / (dn->sigmaColor * dn->sigmaColor);
+  h.k.invNormal = 1.0f / (dn->sigmaNormal * dn->sigmaNormal);
+  h.k.invAlbedo = 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo);
+  h.k.blendFactor = dn->blendFactor;
+  h.k.demodulate = dn->demodulateAlbedo ? 1 : 0;
+  h.k.fireflyThreshold = dv ? dv->fireflyThreshold : 0.0f;
+  h.k.sigmaLuminance = dv ? dv->sigmaLuminance : 0.0f;
+  h.geometry = reinterpret_cast<const float4*>(geometry);
+  std::vector<float4> streams[2] = {std::vector<float4>(n), std::vector<float4>(n)}, guideNormal(n), guideAlbedo(n);
+  h.normal = guideNormal.data(); h.albedo = guideAlbedo.data();
+  float4* colour[2] = {streams[0].data(), streams[1].data()};
+  // prepare
+  float4* prepared = colour[dv ? 1 : 0];
+  for (size_t p = 0; p < n; ++p)
+  {
+    const float4 bp = b[p], a = reinterpret_cast<const float4*>(albedo)[p], nn = reinterpret_cast<const float4*>(normal)[p];
+    float4 c = bp;
+    guideAlbedo[p] = make_float4(a.x, a.y, a.z, 0.0f);
+    if (h.k.demodulate) { const float3 d = clampedAlbedo(a); c.x = bp.x / d.x; c.y = bp.y / d.y; c.z = bp.z / d.z; }
+    guideNormal[p] = make_float4(nn.x, nn.y, nn.z, 0.0f);
+    prepared[p] = c;
+  }
+  if (dv) h.moments(colour[1], colour[0], reinterpret_cast<const float4*>(moments), (float) minSamples);
+  for (int level = 0; level < dn->iterations; ++level) h.level(colour[level & 1], colour[(level + 1) & 1], 1 << level, dv != nullptr);
+  // finish
+  const float4* last = colour[dn->iterations & 1];
+  float4* out = reinterpret_cast<float4*>(denoised);
+  for (size_t p = 0; p < n; ++p)
+  {
+    const float4 bp = b[p], a = guideAlbedo[p];
+    float4 r = last[p];
+    bool through = !finite3(bp) || !finite3(guideNormal[p]) || !finite3(a);
+    if (h.k.demodulate) { const float3 d = clampedAlbedo(a); r.x = r.x * d.x; r.y = r.y * d.y; r.z = r.z * d.z; }
+    if (through || !finite3(r)) { out[p] = bp; continue; }
+    out[p] = make_float4(r.x + h.k.blendFactor * (bp.x - r.x), r.y + h.k.blendFactor * (bp.y - r.y), r.z + h.k.blendFactor * (bp.z - r.z), bp.w);
+  }
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_denoise_geometry_host")
 
 // twk_read_denoised and twk_read_denoised_raw: `raw`, the pixels as they are (`size` in bytes); else RGBA32F (`size` in floats)
 static int readDenoised(TwkDevice dev, void* host, size_t size, bool raw, const char* where)

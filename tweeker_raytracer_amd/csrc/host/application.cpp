@@ -139,6 +139,16 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 2) denoiserMinSamples = i[0];
       else if (ok) warnings.push_back("denoiserMinSamples must be >= 2, keeping the previous value");
     }
+    else if (key == "denoiserGeometry")     { ok = readInt(parser, i[0]); if (ok) denoiserGeometry = (i[0] == 1) ? 1 : 0; }
+    else if (key == "denoiserInstanceStop") { ok = readInt(parser, i[0]); if (ok) denoiserInstanceStop = (i[0] == 1) ? 1 : 0; }
+    else if (key == "denoiserSigmaPosition")
+    {
+      // what twk_denoise_geometry would refuse drops the line: 1 / sigma^2 must be a finite positive float
+      ok = readFloat(parser, f[0]);
+      const float inv = 1.0f / (f[0] * f[0]);
+      if (ok && f[0] > 0.0f && std::isfinite(inv) && inv > 0.0f) denoiserSigmaPosition = f[0];
+      else if (ok) warnings.push_back("denoiserSigmaPosition must be > 0 with 1 / sigma^2 a finite positive float, keeping the previous value");
+    }
     // the stopping rule (twk_estimate_noise, read by twk_app_get_target_noise): as above, a value outside its range drops the line
     else if (key == "targetNoise")
     {
@@ -306,6 +316,9 @@ std::string Application::systemDescription() const
   if (denoiserSigmaLuminance != 4.0f) d << "denoiserSigmaLuminance " << denoiserSigmaLuminance << std::endl;
   if (denoiserSampledVariance != 0) d << "denoiserSampledVariance " << denoiserSampledVariance << std::endl;
   if (denoiserMinSamples != TWK_DENOISER_MIN_SAMPLES) d << "denoiserMinSamples " << denoiserMinSamples << std::endl;
+  if (denoiserGeometry != 0) d << "denoiserGeometry " << denoiserGeometry << std::endl;
+  if (denoiserSigmaPosition != TWK_DENOISER_SIGMA_POSITION) d << "denoiserSigmaPosition " << denoiserSigmaPosition << std::endl;
+  if (denoiserInstanceStop != 0) d << "denoiserInstanceStop " << denoiserInstanceStop << std::endl;
   if (targetNoise != 0.0f) d << "targetNoise " << targetNoise << std::endl;
   if (targetNoiseQuantile != 0.95f) d << "targetNoiseQuantile " << targetNoiseQuantile << std::endl;
   if (targetNoiseInterval != 16) d << "targetNoiseInterval " << targetNoiseInterval << std::endl;

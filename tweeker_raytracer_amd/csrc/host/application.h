@@ -99,6 +99,11 @@ public:
   // least "denoiserMinSamples" of them), TWK_DENOISER_MIN_SAMPLES until a key sets it
   int   denoiserSampledVariance = 0;
   int   denoiserMinSamples = TWK_DENOISER_MIN_SAMPLES;
+  // "denoiserGeometry" (1: twk_denoise_geometry, the geometry guide, where "denoiser 3" is on), "denoiserSigmaPosition",
+  // "denoiserInstanceStop": twk_denoiser_geometry_defaults until a key sets them
+  int   denoiserGeometry = 0;
+  float denoiserSigmaPosition = TWK_DENOISER_SIGMA_POSITION;
+  int   denoiserInstanceStop = 0;
   // "targetNoise" (0: off; else the render loop ends once the "targetNoiseQuantile" quantile of twk_estimate_noise's relative
   // standard error is at most this), checked every "targetNoiseInterval" iterations
   float targetNoise = 0.0f;

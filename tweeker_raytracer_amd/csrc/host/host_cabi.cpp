@@ -137,6 +137,19 @@ try
 }
 TWK_CATCH("twk_app_get_denoiser_sampled")
 
+int twk_app_get_denoiser_geometry(TwkApp app, int* enabled, TwkDenoiserGeometry* dg)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser_geometry: NULL app");
+  if (!enabled || !dg) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_denoiser_geometry: NULL argument");
+  const Application& a = app->app;
+  *enabled = a.denoiserGeometry;
+  dg->sigmaPosition = a.denoiserSigmaPosition;
+  dg->instanceStop = a.denoiserInstanceStop;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_denoiser_geometry")
+
 int twk_app_get_target_noise(TwkApp app, int* enabled, float* target, float* quantile, int* interval)
 try
 {
@@ -304,6 +317,7 @@ try
   if ((rc = twk_set_output_format(dev, a.outputFormat))) return rc;
   if (a.denoiser > 1 && (rc = twk_enable_aov(dev, 1))) return rc; // "denoiser 2|3": the filter's guides are the AOVs
   if (a.denoiser != 0 && a.denoiserSampledVariance && (rc = twk_enable_moments(dev, 1))) return rc; // "denoiserSampledVariance 1": the filter's variance is the samples'
+  if (a.denoiser == 3 && a.denoiserGeometry != 0 && (rc = twk_enable_geometry(dev, 1))) return rc; // "denoiserGeometry 1": the filter's fourth guide is the geometry AOV
   if (a.targetNoise > 0.0f && (rc = twk_enable_moments(dev, 1))) return rc; // "targetNoise e": the stopping rule reads the samples' moments
   if (a.adaptiveSampling != 0 && a.targetNoise > 0.0f && (rc = twk_enable_adaptive(dev, 1))) return rc; // "adaptiveSampling 1": per-pixel sample counts and the active list
   if (a.fireflyCascade != 0) // "fireflyCascade 1": the brightness layers beside the running mean

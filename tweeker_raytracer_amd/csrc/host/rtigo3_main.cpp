@@ -27,6 +27,11 @@
 // picture) and the merged moments, and the screenshot is that. The frame-rate line counts frames x samplesSqrt² iterations.
 // Refused before any device is created: with "targetNoise" or "adaptiveSampling", with a "lensShader" other than 0, with strategy 1
 // or 2, and on several devices without "tileAssembly 1".
+// With "denoiserGeometry 1" beside "denoiser 3" the filter, in whichever mode is on, is twk_denoise_geometry: the geometry AOV is
+// traced once before the screenshot is filtered (twk_render_geometry; on several devices with "tileAssembly 1"
+// twk_render_geometry_tile and ONE twk_assemble_devices_with_geometry), the temporal loop uses its last frame's own geometry, and
+// the camera is the first device's camera 0. Refused before any device is created: a "lensShader" other than 0, a scene with
+// cutout opacity, and several devices without an assembled frame.
 // The interactive mode (-m 0: GLFW window, imgui) needs a display and is not part of this build.
 //
 // Multi-GPU: `strategy` > 0 in the system description renders with every visible device selected by `devicesMask`
@@ -170,6 +175,33 @@ int main(int argc, char* argv[])
     return 1;
   }
   const bool assembling = tileAssembly && count > 1 && info.strategy == 3;
+  // "denoiserGeometry 1" beside "denoiser 3": the filter's fourth guide is the geometry AOV (twk_denoise_geometry), traced once
+  // before the screenshot is filtered. What the geometry AOV refuses is refused here, before any device is created.
+  int denoiserGeometryKey = 0;
+  TwkDenoiserGeometry denoiserGeometry;
+  TWK_OK(twk_app_get_denoiser_geometry(app, &denoiserGeometryKey, &denoiserGeometry));
+  const bool geometryGuide = denoiserEnabled && denoiserGeometryKey && denoiser.inputKind == TWK_DENOISER_RGB_ALBEDO_NORMAL;
+  if (geometryGuide && info.lensShader != 0)
+  {
+    std::cerr << "ERROR: denoiserGeometry reads the geometry AOV, which is traced through the pinhole camera: lensShader must be 0\n";
+    return 1;
+  }
+  if (geometryGuide && count > 1 && !assembling)
+  {
+    std::cerr << "ERROR: denoiserGeometry on several devices reads the assembled geometry AOV on the first device: it needs tileAssembly 1 (strategy 3)\n";
+    return 1;
+  }
+  if (geometryGuide)
+  {
+    std::vector<TwkMaterialGUI> materials((size_t) std::max(1, info.numMaterials));
+    TWK_OK(twk_app_get_materials(app, materials.data(), (int) materials.size()));
+    for (int m = 0; m < info.numMaterials; ++m)
+      if (materials[(size_t) m].useCutoutTexture)
+      {
+        std::cerr << "ERROR: denoiserGeometry reads the geometry AOV, a geometric query: not for scenes with cutout opacity\n";
+        return 1;
+      }
+  }
   if (denoiserEnabled && denoiserSampledEnabled && count > 1 && !assembling)
   {
     std::cerr << "ERROR: denoiserSampledVariance needs the luminance moments of ONE device; they are packed tile buffers on several and are not assembled\n";
@@ -473,11 +505,15 @@ int main(int argc, char* argv[])
   std::vector<unsigned char> rgb8(numPixels * 3);
   // tonemaps `frame` (device memory in the output format on the first device; NULL: the first device's own buffers), denoised
   // first when the description asks for it; albedo, normal, moments: the guides beside an explicit frame that has them (the cascade's)
-  auto present = [&](const void* frame, const void* albedo = nullptr, const void* normal = nullptr, const void* moments = nullptr) -> int
+  // geometry: the geometry AOV beside an explicit frame ("denoiserGeometry 1"; its camera is the first device's camera 0)
+  auto present = [&](const void* frame, const void* albedo = nullptr, const void* normal = nullptr, const void* moments = nullptr, const void* geometry = nullptr) -> int
   {
     if (denoiserEnabled)
     {
-      if (denoiserSampledEnabled)       TWK_OK(twk_denoise_variance_sampled(devices[0], &denoiser, &denoiserVariance, denoiserMinSamples, frame, albedo, normal, moments, width, height, nullptr)); // one device: frame is NULL, the handle's own buffers and moments
+      if (geometryGuide)
+        TWK_OK(twk_denoise_geometry(devices[0], &denoiser, &denoiserGeometry, (denoiserSampledEnabled || denoiserVarianceEnabled) ? &denoiserVariance : nullptr,
+                                    denoiserSampledEnabled ? denoiserMinSamples : 0, frame, albedo, normal, denoiserSampledEnabled ? moments : nullptr, geometry, nullptr, width, height, nullptr));
+      else if (denoiserSampledEnabled)       TWK_OK(twk_denoise_variance_sampled(devices[0], &denoiser, &denoiserVariance, denoiserMinSamples, frame, albedo, normal, moments, width, height, nullptr)); // one device: frame is NULL, the handle's own buffers and moments
       else if (denoiserVarianceEnabled) TWK_OK(twk_denoise_variance(devices[0], &denoiser, &denoiserVariance, frame, albedo, normal, width, height, nullptr));
       else                              TWK_OK(twk_denoise(devices[0], &denoiser, frame, albedo, normal, width, height, nullptr));
       void* denoised = nullptr;
@@ -524,7 +560,13 @@ int main(int argc, char* argv[])
         }
       }
     }
-    const int failed = present(merged, guides[0], guides[1], (denoiserEnabled && denoiserSampledEnabled) ? mergedMoments : nullptr);
+    void* frameGeometry = nullptr; // the last frame's own geometry: assembled on several devices, the handle's on one
+    if (geometryGuide)
+    {
+      if (count > 1) TWK_OK(twk_get_assembled_geometry_device_pointer(devices[0], &frameGeometry, nullptr));
+      else           TWK_OK(twk_get_geometry_device_pointer(devices[0], &frameGeometry, nullptr));
+    }
+    const int failed = present(merged, guides[0], guides[1], (denoiserEnabled && denoiserSampledEnabled) ? mergedMoments : nullptr, frameGeometry);
     if (ownGuides) for (void* guide : guides) if (guide) HIP_OK(hipFree(guide));
     if (resolved) HIP_OK(hipFree(resolved));
     if (failed) return 1;
@@ -537,7 +579,14 @@ int main(int argc, char* argv[])
     if (denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO) planes |= TWK_PLANE_BIT(TWK_PLANE_ALBEDO);
     if (denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) planes |= TWK_PLANE_BIT(TWK_PLANE_NORMAL);
     if (denoiserEnabled && denoiserSampledEnabled) planes |= TWK_PLANE_BIT(TWK_PLANE_MOMENTS);
-    TWK_OK(twk_assemble_devices(devices[0], planes, devices.data(), count));
+    void* assembledGeometry = nullptr;
+    if (geometryGuide)
+    {
+      for (int i = 0; i < count; ++i) TWK_OK(twk_render_geometry_tile(devices[(size_t) i]));
+      TWK_OK(twk_assemble_devices_with_geometry(devices[0], planes, devices.data(), count));
+      TWK_OK(twk_get_assembled_geometry_device_pointer(devices[0], &assembledGeometry, nullptr));
+    }
+    else TWK_OK(twk_assemble_devices(devices[0], planes, devices.data(), count));
     void* assembled[TWK_PLANE_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int p = 0; p < TWK_PLANE_COUNT; ++p) if (planes & TWK_PLANE_BIT(p)) TWK_OK(twk_get_assembled_device_pointer(devices[0], p, &assembled[p], nullptr));
     void* frame = assembled[TWK_PLANE_OUTPUT]; void* resolved = nullptr;
@@ -548,7 +597,7 @@ int main(int argc, char* argv[])
       TWK_OK(twk_cascade_resolve(devices[0], &cascade, &cascadeResolve, assembled[TWK_PLANE_CASCADE], width, height, resolved));
       frame = resolved;
     }
-    const int failed = present(frame, assembled[TWK_PLANE_ALBEDO], assembled[TWK_PLANE_NORMAL], assembled[TWK_PLANE_MOMENTS]);
+    const int failed = present(frame, assembled[TWK_PLANE_ALBEDO], assembled[TWK_PLANE_NORMAL], assembled[TWK_PLANE_MOMENTS], assembledGeometry);
     if (resolved) HIP_OK(hipFree(resolved));
     if (failed) return 1;
   }
@@ -572,12 +621,19 @@ int main(int argc, char* argv[])
       }
     }
     if (denoiserEnabled && denoiserSampledEnabled) TWK_OK(twk_get_moments_device_pointer(devices[0], &moments, nullptr));
-    const int failed = present(resolved, guides[0], guides[1], moments);
+    void* geometry = nullptr;
+    if (geometryGuide)
+    {
+      TWK_OK(twk_render_geometry(devices[0]));
+      TWK_OK(twk_get_geometry_device_pointer(devices[0], &geometry, nullptr));
+    }
+    const int failed = present(resolved, guides[0], guides[1], moments, geometry);
     for (void* guide : guides) if (guide) HIP_OK(hipFree(guide));
     if (failed) return 1;
   }
   else if (count == 1)
   {
+    if (geometryGuide) TWK_OK(twk_render_geometry(devices[0])); // once, before the screenshot is filtered: the own-buffer form reads it
     if (present(nullptr)) return 1;
   }
   else if (sharedFrame)

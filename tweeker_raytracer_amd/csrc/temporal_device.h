@@ -86,7 +86,7 @@ struct TemporalConstants
   float D;
 };
 
-TWK_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+// dot3, the left-to-right dot product: denoise_device.h (the geometry guide of the denoiser uses the same one)
 
 // The previous camera's part of the constants; cam = P', U', V', W' (12 floats). False: degenerate (D zero or not finite).
 TWK_HD bool temporalCamera(const float* cam, TemporalConstants& k)

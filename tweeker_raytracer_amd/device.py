@@ -383,7 +383,8 @@ class Device:
         L.check(L.lib.twk_tonemap(self._h, C.byref(tm), ptr, C.c_size_t(h * w), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
 
-    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None, variance=None, moments=None, minSamples=None):
+    def denoise(self, params=None, beauty=None, albedo=None, normal=None, shape=None, denoised=None, variance=None, moments=None, minSamples=None,
+                geometry=None, geometryBuffer=None, camera=None):
         """twk_denoise: the edge-avoiding a-trous wavelet filter (a classical filter, not a learned one) where Optix7Gui calls
         optixDenoiserInvoke. Asynchronous. params: L.Denoiser (None = the defaults). Without `beauty` the handle's own
         accumulation and AOV buffers are filtered; otherwise beauty / albedo / normal are device pointers to shape = (height,
@@ -393,10 +394,26 @@ class Device:
         minSamples (an int >= 2) or moments: twk_denoise_variance_sampled — pixels that have seen at least minSamples samples
         (default L.TWK_DENOISER_MIN_SAMPLES) are guided by the measured variance of their mean instead of the spatial estimate.
         moments: device pointer to shape float4 (mean, M2, n, .) beside an explicit beauty; without `beauty`, moments=True (or just
-        minSamples) takes the handle's own (enableMoments). variance=None then means DenoiserVariance()."""
+        minSamples) takes the handle's own (enableMoments). variance=None then means DenoiserVariance().
+        geometry: L.DenoiserGeometry = twk_denoise_geometry, the same three modes with the geometry guide (plane and instance
+        stops; inputKind RGB_ALBEDO_NORMAL only). geometryBuffer: device pointer to shape float4 (world position, instance + 1)
+        beside an explicit beauty; without `beauty` the handle's own geometry AOV (enableGeometry, renderGeometry). camera: the 12
+        floats P, U, V, W the geometry was traced from (a CameraDefinition or a sequence), None = the handle's camera 0."""
         dn = params if params is not None else L.Denoiser()
         ptr = lambda p: None if p is None else C.c_void_p(int(p))
         h, w = shape if shape is not None else (0, 0)
+        if geometry is not None:
+            sampled = minSamples is not None or (moments is not None and moments is not False)
+            dv = variance if (variance is not None or not sampled) else L.DenoiserVariance()
+            m = None if (moments is None or moments is True or moments is False) else C.c_void_p(int(moments))
+            n = 0 if not sampled else (L.TWK_DENOISER_MIN_SAMPLES if minSamples is None else int(minSamples))
+            cam = None
+            if camera is not None:
+                values = bytes(camera)[:48] if isinstance(camera, C.Structure) else None
+                cam = (C.c_float * 12).from_buffer_copy(values) if values is not None else (C.c_float * 12)(*[float(v) for v in camera])
+            L.check(L.lib.twk_denoise_geometry(self._h, C.byref(dn), C.byref(geometry), None if dv is None else C.byref(dv), n, ptr(beauty), ptr(albedo), ptr(normal), m,
+                                               ptr(geometryBuffer), cam, int(w), int(h), ptr(denoised)))
+            return
         if minSamples is not None or (moments is not None and moments is not False):
             dv = variance if variance is not None else L.DenoiserVariance()
             m = None if (moments is None or moments is True) else C.c_void_p(int(moments))

@@ -1,15 +1,15 @@
 """-m gpu: twk_denoise_geometry, the geometry guide of the a-trous denoiser (plane and instance stops from the geometry AOV), in the
 three modes of the filter. The device result equals tests/denoise_geometry_restate.py (csrc/denoise_device.h in numpy float32) and
 the host form twk_denoise_geometry_host in every bit, in both output formats, with every level on the direct-load and on the
-LDS-staged build; with a geometry of misses only its bytes are those of the three existing calls; on the Cornell box the own-buffer
+LDS-staged build, also at the smallest shapes, where most taps lie outside the picture; with a geometry of misses only its bytes are those of the three existing calls; on the Cornell box the own-buffer
 form equals the explicit form; a stale geometry is refused."""
 import numpy as np
 import pytest
 
 from conftest import load_app
-from denoise_geometry_restate import CAMERA, restate, step_scene, synthetic
+from denoise_geometry_restate import CAMERA, instance_bits, restate, step_scene, synthetic, world_positions
 from test_denoise_geometry_host import MODES, _exp, _mode, _sqrt, host
-from test_gpu_denoise import BUILDS, _choose_build
+from test_gpu_denoise import BUILDS, _choose_build, _restate
 from test_gpu_half_output import _DeviceBuffer
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +93,68 @@ def test_device_equals_restatement_and_host_form(twk, orc, half, lds_max_step, m
                     _same(got, on_host, what + ", host form")
         for buf, a in zip(up.buffers, (beauty, albedo, normal, moments, geometry)):
             _same(buf.download(a.shape, a.dtype), a, "input after twk_denoise_geometry")
+        up.free()
+    dev.close()
+    app.close()
+
+
+BORDER_SHAPES = [(1, 1), (3, 5), (37, 61)]  # (height, width)
+_border_cache = {}
+
+
+def _border_case(L, orc, shape):
+    """Inputs and the three restatements of one border shape, computed once and shared by both builds: noise over two depths and two
+    instances, with one column of misses (the middle one; the single pixel of 1x1 is a hit)."""
+    if shape not in _border_cache:
+        h, w = shape
+        rng = np.random.default_rng(1000 * w + h)
+        beauty = rng.gamma(2.0, 0.5, (h, w, 4)).astype(F)
+        albedo = np.ones((h, w, 4), F)
+        albedo[..., :3] = rng.uniform(0.3, 0.4, (h, w, 3)).astype(F)
+        normal = np.zeros((h, w, 4), F)
+        normal[..., 2] = 1.0
+        normal[..., :2] = rng.normal(0.0, 0.05, (h, w, 2)).astype(F)
+        depth = np.full((h, w), 3.0)
+        depth[:, (w * 3) // 4:] = 3.2
+        ids = np.ones((h, w), np.uint32)
+        ids[h // 2:, : w // 4] = 2
+        geometry = np.zeros((h, w, 4), F)
+        geometry[..., :3] = world_positions(h, w, depth)
+        if w > 1:
+            ids[:, w // 2] = 0
+            geometry[:, w // 2, :3] = 0.0
+            normal[:, w // 2, :3] = 0.0
+        geometry[..., 3] = instance_bits(ids)
+        dn, dg, dv = L.Denoiser(iterations=5, sigmaColor=1.5), L.DenoiserGeometry(sigmaPosition=0.05), L.DenoiserVariance()
+        expect = {"plain": _restate(beauty, albedo, normal, dn, _exp(orc))[0]}
+        for mode, variance in (("geometry", None), ("geometry, variance", dv)):
+            expect[mode] = restate(beauty, albedo, normal, geometry, CAMERA, dn, dg, _exp(orc), _sqrt(orc), dv=variance)[0]
+        _border_cache[shape] = ((beauty, albedo, normal, geometry), (dn, dg, dv), expect)
+    return _border_cache[shape]
+
+
+@pytest.mark.parametrize("lds_max_step", ["0", "128"], ids=["direct", "staged"])
+def test_the_border_on_either_build(twk, orc, lds_max_step, monkeypatch):
+    """Where a tap lies outside the picture is the one thing the two builds of the level tell differently (a bounds test; a NaN
+    colour staged in LDS). 1x1: every tap but the centre is outside; 5x3: narrower than the halo of either pass; 61x37: no multiple
+    of the 32x8 tile and narrower than the reach 2 x 16 of step 16. 5 levels, RGBA32F, explicit buffers, every level on the direct
+    and on the staged build: twk_denoise equals test_gpu_denoise._restate, twk_denoise_geometry plain and variance-guided equal
+    denoise_geometry_restate.restate, in every bit."""
+    L = twk._lib
+    _choose_build(monkeypatch, lds_max_step)
+    app, dev = _device(twk)
+    for shape in BORDER_SHAPES:
+        arrays, (dn, dg, dv), expect = _border_case(L, orc, shape)
+        hits = arrays[3][..., 3].view(np.uint32) != 0
+        assert hits.any() and (shape == (1, 1) or (~hits).all(axis=0).sum() == 1)
+        up = _Uploaded(twk, arrays)
+        pb, pa, pn, pg = up.pointers
+        for mode in expect:
+            if mode == "plain":
+                dev.denoise(dn, pb, pa, pn, shape=shape)
+            else:
+                dev.denoise(dn, pb, pa, pn, shape=shape, variance=dv if "variance" in mode else None, geometry=dg, geometryBuffer=pg, camera=CAMERA)
+            _same(dev.readDenoised(raw=True, shape=shape), expect[mode], f"{shape[1]}x{shape[0]}, {mode}, TWK_DENOISE_LDS_MAX_STEP {lds_max_step}")
         up.free()
     dev.close()
     app.close()

@@ -121,6 +121,16 @@
 // On a plane d is 0 at every step, so the term is not scaled by the level's step. sigmaPosition is a distance from the centre's
 // tangent plane relative to the centre's distance from the camera: TwkTemporal::positionTolerance's convention.
 // With a geometry of misses only, every tap adds nothing and the three modes compute the bits they compute without the guide.
+//
+// ---- where this is written down -----------------------------------------------------------------------------------------------
+// The statements above exist once in C++, at the end of this file: denoisePreparePixel, denoiseMomentsPixel, denoiseLevelPixel and
+// denoiseFinishPixel are what one pixel does in a pass, over the per-tap functions (denoiseTap, denoiseVarianceTap, momentsTap, ...).
+// The level and the moments body read their taps through a tap source, which alone knows where a tap lies and which taps exist.
+// Both builds of the level kernel and the moments kernel (denoise_kernels.hip: DenoiseGlobalTaps on the streams, DenoiseStagedTaps
+// on a block's LDS arrays) and the host form twk_denoise_geometry_host (device_post.hip: DenoiseGlobalTaps on host pointers) call
+// these same bodies; none restates a loop, a skip rule or a pass-through rule. The only other statements of the definition are
+// the numpy ones of the tests: tests/test_gpu_denoise.py, test_gpu_denoise_variance.py, test_gpu_denoise_sampled.py and
+// tests/denoise_geometry_restate.py.
 #pragma once
 #include "device_math.h"
 
@@ -218,10 +228,10 @@ TWK_HD float stencilWeight(int d) // d = -2 .. 2: B3 spline 1/16, 1/4, 3/8, 1/4,
 TWK_HD float3 clampedAlbedo(const float4& a) { return make_float3(fmaxf(a.x, 0.01f), fmaxf(a.y, 0.01f), fmaxf(a.z, 0.01f)); }
 
 // One tap of a level: folds colour cq at stencil offset (dx, dy) into sum / wsum. KIND: TWK_DENOISER_*; GEO: the geometry guide
-template<int KIND, bool GEO = false>
+template<int KIND, bool GEO>
 TWK_HD void denoiseTap(const DenoiseConstants& k, int dx, int dy, const float4& cp, const float4& np, const float4& ap,
                        const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum,
-                       const DenoiseGeometryCentre& gc = DenoiseGeometryCentre(), const float4& gq = float4())
+                       const DenoiseGeometryCentre& gc, const float4& gq)
 {
   if (!finite3(cq)) return;
   float t = distance2(cp, cq) * k.invColor;
@@ -241,9 +251,9 @@ TWK_HD void denoiseTap(const DenoiseConstants& k, int dx, int dy, const float4& 
 TWK_HD float luminance(const float4& c) { return luminance3(c.x, c.y, c.z); } // (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z
 
 // One tap of the moments pass: folds the luminance lq of a tap with a finite colour into s0, s1, s2
-template<int KIND, bool GEO = false>
+template<int KIND, bool GEO>
 TWK_HD void momentsTap(const DenoiseConstants& k, const float4& np, const float4& ap, float lq, const float4& nq, const float4& aq, float& s0, float& s1, float& s2,
-                       const DenoiseGeometryCentre& gc = DenoiseGeometryCentre(), const float4& gq = float4())
+                       const DenoiseGeometryCentre& gc, const float4& gq)
 {
   float g = 1.0f;
   if (KIND >= 1)
@@ -259,8 +269,8 @@ TWK_HD void momentsTap(const DenoiseConstants& k, const float4& np, const float4
 
 // The end of the moments pass: variance and firefly clamp of the centre cp from the sums; returns (cp.xyz clamped, var).
 // SAMPLED: m = the pixel's luminance moments (mean, M2, n, .); the measured variance of the mean replaces var where n >= minSamples
-template<bool SAMPLED = false>
-TWK_HD float4 momentsFinish(const DenoiseConstants& k, float4 cp, float s0, float s1, float s2, const float4 m = float4(), float minSamples = 0.0f)
+template<bool SAMPLED>
+TWK_HD float4 momentsFinish(const DenoiseConstants& k, float4 cp, float s0, float s1, float s2, const float4 m, float minSamples)
 {
   float var = 0.0f, f = 1.0f;
   const float4 c0 = cp;
@@ -306,10 +316,10 @@ TWK_HD float inverseLuminanceSigma(const DenoiseConstants& k, float vs, float bs
 }
 
 // One tap of a level of the variance-guided mode: like denoiseTap with the luminance edge-stop, and the variance filtered along
-template<int KIND, bool GEO = false>
+template<int KIND, bool GEO>
 TWK_HD void denoiseVarianceTap(const DenoiseConstants& k, int dx, int dy, float lp, float invL, const float4& np, const float4& ap,
                                const float4& cq, const float4& nq, const float4& aq, float& sx, float& sy, float& sz, float& wsum, float& vsum,
-                               const DenoiseGeometryCentre& gc = DenoiseGeometryCentre(), const float4& gq = float4())
+                               const DenoiseGeometryCentre& gc, const float4& gq)
 {
   if (!finite3(cq)) return;
   float t = fabsf(lp - luminance(cq)) * invL;
@@ -321,6 +331,190 @@ TWK_HD void denoiseVarianceTap(const DenoiseConstants& k, int dx, int dy, float 
   sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
   wsum = wsum + w;
   vsum = vsum + (w * w) * cq.w;
+}
+
+// ---- where the taps of a pixel come from ----
+// A source names the centre and the taps of one pixel by an Index into its four arrays (colour, normal, albedo, geometry; an array
+// the build does not use is never read): row(dy, r) names a row of taps and tap(r, dx, q) one tap of it; either is false
+// where there is none, so a whole row is tested once, before its taps. luminance(q), for the moments pass: NaN where the colour is not finite.
+
+// The picture where it lies, on the device or on the host: a tap outside the picture is absent
+struct DenoiseGlobalTaps
+{
+  typedef int    Row;
+  typedef size_t Index;
+  const float4 *colour, *normal, *albedo, *geometry;
+  int    width, height, x, y, step;
+  size_t centre;
+
+  TWK_HD DenoiseGlobalTaps(const float4* colour_, const float4* normal_, const float4* albedo_, const float4* geometry_, int width_, int height_, int x_, int y_, int step_)
+    : colour(colour_), normal(normal_), albedo(albedo_), geometry(geometry_), width(width_), height(height_), x(x_), y(y_), step(step_), centre((size_t) y_ * width_ + x_) {}
+  TWK_HD bool row(int dy, int& qy) const
+  {
+    qy = y + dy * step;
+    return qy >= 0 && qy < height;
+  }
+  TWK_HD bool tap(int qy, int dx, size_t& q) const
+  {
+    const int qx = x + dx * step;
+    if (qx < 0 || qx >= width) return false;
+    q = (size_t) qy * width + qx;
+    return true;
+  }
+  TWK_HD float luminance(size_t q) const { const float4 c = colour[q]; return finite3(c) ? twk::luminance(c) : asFloat(0x7fc00000u); }
+};
+
+// A block's taps staged densely, STRIDE entries per row (denoise_kernels.hip): every tap is present; what lies outside the picture
+// was staged with a NaN colour. The arrays are given AT the centre's entry, so that a tap is a constant offset from it
+// (one base register and the offset field of ds_read; by index the staged VAR builds took 15 VGPRs more: profiles/r21_denoise_one_body.md 3).
+// Colour: float4, or float in the moments pass, which stages the luminance alone.
+template<int STRIDE, typename Colour>
+struct DenoiseStagedTaps
+{
+  typedef int Row;
+  typedef int Index;
+  static constexpr int centre = 0;
+  const Colour* colour;
+  const float4 *normal, *albedo, *geometry;
+
+  TWK_HD bool  row(int dy, int& r) const { r = dy * STRIDE; return true; }
+  TWK_HD bool  tap(int r, int dx, int& q) const { q = r + dx; return true; }
+  TWK_HD float luminance(int q) const { return colour[q]; }
+};
+
+// ---- the four passes, one pixel each: the definition at the top of this file, statement for statement ----
+template<typename Pixel>
+TWK_HD void denoisePreparePixel(const DenoiseConstants& k, size_t p, const Pixel* beauty, const Pixel* albedo, const Pixel* normal, float4* colour, float4* guideNormal, float4* guideAlbedo)
+{
+  const float4 b = widen(beauty[p]);
+  float4 c = b;
+  if (albedo)
+  {
+    const float4 a = widen(albedo[p]);
+    guideAlbedo[p] = make_float4(a.x, a.y, a.z, 0.0f);
+    if (k.demodulate)
+    {
+      const float3 d = clampedAlbedo(a);
+      c.x = b.x / d.x; c.y = b.y / d.y; c.z = b.z / d.z;
+    }
+  }
+  if (normal)
+  {
+    const float4 n = widen(normal[p]);
+    guideNormal[p] = make_float4(n.x, n.y, n.z, 0.0f);
+  }
+  colour[p] = c;
+}
+
+// SAMPLED: *m, the pixel's luminance moments, read once the sums are made. cp: the centre's colour (the staged source keeps luminances only)
+template<int KIND, bool SAMPLED, bool GEO, typename Taps>
+TWK_HD float4 denoiseMomentsPixel(const DenoiseConstants& k, const DenoiseGeometryConstants& g, const Taps& s, const float4 cp, const float4* m, float minSamples)
+{
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float4 np = (KIND >= 2) ? s.normal[s.centre] : zero;
+  const float4 ap = (KIND >= 1) ? s.albedo[s.centre] : zero;
+  if (!finite3(cp) || !finite1(s.luminance(s.centre)) || !finite3(np) || !finite3(ap)) return make_float4(cp.x, cp.y, cp.z, 0.0f);
+  DenoiseGeometryCentre gc = DenoiseGeometryCentre();
+  if (GEO) { if (!denoiseGeometryCentre(g, s.geometry[s.centre], np, gc)) return make_float4(cp.x, cp.y, cp.z, 0.0f); }
+  float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+  for (int dy = -TWK_DENOISE_MOMENTS_RADIUS; dy <= TWK_DENOISE_MOMENTS_RADIUS; ++dy)
+  {
+    typename Taps::Row   r;
+    typename Taps::Index q;
+    if (!s.row(dy, r)) continue;
+#pragma unroll
+    for (int dx = -TWK_DENOISE_MOMENTS_RADIUS; dx <= TWK_DENOISE_MOMENTS_RADIUS; ++dx)
+    {
+      if ((dx == 0 && dy == 0) || !s.tap(r, dx, q)) continue;
+      const float lq = s.luminance(q);
+      if ((asUint(lq) & 0x7fffffffu) > 0x7f800000u) continue; // NaN: a colour that is not finite
+      const float4 nq = (KIND >= 2) ? s.normal[q] : zero;
+      const float4 aq = (KIND >= 1) ? s.albedo[q] : zero;
+      momentsTap<KIND, GEO>(k, np, ap, lq, nq, aq, s0, s1, s2, gc, GEO ? s.geometry[q] : zero);
+    }
+  }
+  return momentsFinish<SAMPLED>(k, cp, s0, s1, s2, SAMPLED ? *m : zero, minSamples);
+}
+
+// VAR: the level of the variance-guided mode
+template<int KIND, bool VAR, bool GEO, typename Taps>
+TWK_HD float4 denoiseLevelPixel(const DenoiseConstants& k, const DenoiseGeometryConstants& g, const Taps& s)
+{
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float4 cp = s.colour[s.centre];
+  const float4 np = (KIND >= 2) ? s.normal[s.centre] : zero;
+  const float4 ap = (KIND >= 1) ? s.albedo[s.centre] : zero;
+  if (!finite3(cp) || !finite3(np) || !finite3(ap)) return cp;
+  DenoiseGeometryCentre gc = DenoiseGeometryCentre();
+  if (GEO) { if (!denoiseGeometryCentre(g, s.geometry[s.centre], np, gc)) return cp; }
+  float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
+  if (VAR)
+  {
+    lp = luminance(cp);
+    if (!finite1(lp)) return cp;
+    float vs = 0.0f, bs = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+    {
+      typename Taps::Row   r;
+      typename Taps::Index q;
+      if (!s.row(dy, r)) continue;
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx)
+      {
+        if (s.tap(r, dx, q)) varianceBlurTap(dx, dy, s.colour[q], vs, bs);
+      }
+    }
+    invL = inverseLuminanceSigma(k, vs, bs);
+  }
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f, wsum = 0.0f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy)
+  {
+    typename Taps::Row   r;
+    typename Taps::Index q;
+    if (!s.row(dy, r)) continue;
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx)
+    {
+      if (!s.tap(r, dx, q)) continue;
+      const float4 cq = s.colour[q];
+      const float4 nq = (KIND >= 2) ? s.normal[q] : zero;
+      const float4 aq = (KIND >= 1) ? s.albedo[q] : zero;
+      const float4 gq = GEO ? s.geometry[q] : zero;
+      if (VAR) denoiseVarianceTap<KIND, GEO>(k, dx, dy, lp, invL, np, ap, cq, nq, aq, sx, sy, sz, wsum, vsum, gc, gq);
+      else     denoiseTap<KIND, GEO>(k, dx, dy, cp, np, ap, cq, nq, aq, sx, sy, sz, wsum, gc, gq);
+    }
+  }
+  return make_float4(sx / wsum, sy / wsum, sz / wsum, VAR ? vsum / (wsum * wsum) : cp.w);
+}
+
+template<typename Pixel>
+TWK_HD void denoiseFinishPixel(const DenoiseConstants& k, size_t p, const Pixel* beauty, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, Pixel* denoised)
+{
+  const Pixel raw = beauty[p];
+  const float4 b = widen(raw);
+  float4 r = colour[p];
+  bool through = !finite3(b);
+  if (guideNormal) through = through || !finite3(guideNormal[p]);
+  if (guideAlbedo)
+  {
+    const float4 a = guideAlbedo[p];
+    through = through || !finite3(a);
+    if (k.demodulate)
+    {
+      const float3 d = clampedAlbedo(a);
+      r.x = r.x * d.x; r.y = r.y * d.y; r.z = r.z * d.z;
+    }
+  }
+  if (through || !finite3(r)) { denoised[p] = raw; return; } // !finite3(r): the demodulated colour overflowed
+  float4 o;
+  o.x = r.x + k.blendFactor * (b.x - r.x);
+  o.y = r.y + k.blendFactor * (b.y - r.y);
+  o.z = r.z + k.blendFactor * (b.z - r.z);
+  o.w = b.w;
+  denoised[p] = pixelOf<Pixel>(o);
 }
 
 } // namespace twk

@@ -43,9 +43,9 @@ TWK_HD float luminance3(float r, float g, float b) { return (0.2126f * r + 0.715
 
 // A pixel of format `Pixel` from an f32 value, and the f32 value of a pixel. RGBA32F here: a float4 is what it was given;
 // pixel_formats.h adds RGBA16F (Half4) to both.
-template<typename Pixel> TWK_D Pixel pixelOf(const float4 v);
-template<> TWK_D float4 pixelOf<float4>(const float4 v) { return v; }
-TWK_D float4 widen(const float4 v) { return v; }
+template<typename Pixel> TWK_HD Pixel pixelOf(const float4 v);
+template<> TWK_HD float4 pixelOf<float4>(const float4 v) { return v; }
+TWK_HD float4 widen(const float4 v) { return v; }
 
 // --- sin / cos -------------------------------------------------------------------------------
 TWK_HD void octantReduce(float ax, float& r, int& j)

@@ -141,6 +141,46 @@ static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
 }
 static bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
 
+// Every check of the parameters' values, for the device form and the host form alike, and the constants the passes take (k but
+// for its width and height). `name` is the entry point, for the error texts; dv NULL: not the variance-guided mode; dg NULL: no
+// geometry guide; minSamples 0: no sampled variance; `moments`: the caller gave a moments buffer
+static int denoiseParameters(const char* name, const TwkDenoiser* dn, const TwkDenoiserVariance* dv, const TwkDenoiserGeometry* dg, int minSamples, bool moments, DenoiseConstants& k)
+{
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, (std::string(name) + ": " + text).c_str()); };
+  const int kind = dn->inputKind;
+  if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse("unknown inputKind");
+  if (minSamples != 0 && !dv) return refuse("minSamples without the parameters of the variance-guided mode");
+  if (minSamples != 0 && minSamples < 2) return refuse("minSamples must be 0 (no sampled variance) or >= 2 (one sample has no variance)");
+  if (minSamples == 0 && moments) return refuse("a moments buffer without minSamples");
+  if (dg)
+  {
+    if (kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse("the geometry guide needs inputKind TWK_DENOISER_RGB_ALBEDO_NORMAL (the plane's normal comes from the normal guide)");
+    const float invPosition = 1.0f / (dg->sigmaPosition * dg->sigmaPosition);
+    if (!(dg->sigmaPosition > 0.0f) || !std::isfinite(invPosition) || !(invPosition > 0.0f)) return refuse("sigmaPosition must be > 0 and 1 / sigmaPosition^2 a finite positive float");
+  }
+  if (dn->iterations < 0 || dn->iterations > 8) return refuse("iterations must be in [0, 8]");
+  if ((!dv && !(dn->sigmaColor > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
+    return refuse("the sigma of every guide in use must be positive");
+  k.width = 0; k.height = 0;
+  k.invColor  = dv ? 0.0f : 1.0f / (dn->sigmaColor * dn->sigmaColor);
+  k.invNormal = (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? 1.0f / (dn->sigmaNormal * dn->sigmaNormal) : 0.0f;
+  k.invAlbedo = (kind >= TWK_DENOISER_RGB_ALBEDO) ? 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo) : 0.0f;
+  k.blendFactor = dn->blendFactor;
+  k.demodulate = dn->demodulateAlbedo ? 1 : 0;
+  k.fireflyThreshold = dv ? dv->fireflyThreshold : 0.0f;
+  k.sigmaLuminance = dv ? dv->sigmaLuminance : 0.0f;
+  // 1 / sigma^2 is what the passes multiply by: a sigma whose square underflows would make it inf, and 0 x inf the centre tap's NaN
+  if (!std::isfinite(k.invColor) || !std::isfinite(k.invNormal) || !std::isfinite(k.invAlbedo)) return refuse("a sigma is too small: 1 / sigma^2 is not a finite float");
+  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return refuse("blendFactor must be in [0, 1]");
+  if (dn->demodulateAlbedo && kind == TWK_DENOISER_RGB) return refuse("demodulateAlbedo needs an albedo guide (inputKind TWK_DENOISER_RGB has none)");
+  if (dv)
+  {
+    if (!(dv->fireflyThreshold >= 0.0f) || !std::isfinite(dv->fireflyThreshold)) return refuse("fireflyThreshold must be >= 0 (0 = no clamp) and finite");
+    if (!(dv->sigmaLuminance > 0.0f) || !std::isfinite(dv->sigmaLuminance)) return refuse("sigmaLuminance must be > 0 and finite");
+  }
+  return TWK_SUCCESS;
+}
+
 // twk_denoise (dv NULL), twk_denoise_variance and twk_denoise_variance_sampled (minSamples > 0; `moments`: the caller's buffer
 // beside an explicit beauty): `name` is the entry point, for its error texts. dg (twk_denoise_geometry): the geometry guide, with
 // `geometry` the caller's buffer beside an explicit beauty and `camera` (12 floats P, U, V, W; NULL: the handle's camera 0) the one
@@ -151,30 +191,9 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
   const bool sampled = (minSamples > 0);
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
   const int kind = dn->inputKind;
-  if (kind != TWK_DENOISER_RGB && kind != TWK_DENOISER_RGB_ALBEDO && kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "unknown inputKind");
-  if (dg)
-  {
-    if (kind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "the geometry guide needs inputKind TWK_DENOISER_RGB_ALBEDO_NORMAL (the plane's normal comes from the normal guide)");
-    const float invPosition = 1.0f / (dg->sigmaPosition * dg->sigmaPosition);
-    if (!(dg->sigmaPosition > 0.0f) || !std::isfinite(invPosition) || !(invPosition > 0.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaPosition must be > 0 and 1 / sigmaPosition^2 a finite positive float");
-  }
-  if (dn->iterations < 0 || dn->iterations > 8) return refuse(TWK_ERROR_INVALID_VALUE, "iterations must be in [0, 8]");
-  if ((!dv && !(dn->sigmaColor > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO && !(dn->sigmaAlbedo > 0.0f)) || (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL && !(dn->sigmaNormal > 0.0f)))
-    return refuse(TWK_ERROR_INVALID_VALUE, "the sigma of every guide in use must be positive");
-  {
-    // 1 / sigma^2 is what the kernels multiply by: a sigma whose square underflows would make it inf, and 0 x inf the centre tap's NaN
-    const float sigmas[3] = {dv ? 1.0f : dn->sigmaColor, (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? dn->sigmaNormal : 1.0f, (kind >= TWK_DENOISER_RGB_ALBEDO) ? dn->sigmaAlbedo : 1.0f};
-    for (const float sigma : sigmas)
-      if (!std::isfinite(1.0f / (sigma * sigma))) return refuse(TWK_ERROR_INVALID_VALUE, "a sigma is too small: 1 / sigma^2 is not a finite float");
-  }
-  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "blendFactor must be in [0, 1]");
-  if (dn->demodulateAlbedo && kind == TWK_DENOISER_RGB) return refuse(TWK_ERROR_INVALID_VALUE, "demodulateAlbedo needs an albedo guide (inputKind TWK_DENOISER_RGB has none)");
-  if (dv)
-  {
-    if (!(dv->fireflyThreshold >= 0.0f) || !std::isfinite(dv->fireflyThreshold)) return refuse(TWK_ERROR_INVALID_VALUE, "fireflyThreshold must be >= 0 (0 = no clamp) and finite");
-    if (!(dv->sigmaLuminance > 0.0f) || !std::isfinite(dv->sigmaLuminance)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaLuminance must be > 0 and finite");
-  }
-  int rc = activate(dev, name); if (rc) return rc;
+  DenoiseConstants k;
+  int rc = denoiseParameters(name, dn, dv, dg, minSamples, moments != nullptr, k); if (rc) return rc;
+  rc = activate(dev, name); if (rc) return rc;
 
   const bool own = (beauty == nullptr);
   if (own)
@@ -258,15 +277,7 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     float4* colour[2] = {dev->d_denoiseStreams, dev->d_denoiseStreams + numPixels};
     float4* guideNormal = dev->d_denoiseStreams + 2 * numPixels;
     float4* guideAlbedo = dev->d_denoiseStreams + 3 * numPixels;
-    DenoiseConstants k;
     k.width = width; k.height = height;
-    k.invColor  = dv ? 0.0f : 1.0f / (dn->sigmaColor * dn->sigmaColor);
-    k.invNormal = (kind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) ? 1.0f / (dn->sigmaNormal * dn->sigmaNormal) : 0.0f;
-    k.invAlbedo = (kind >= TWK_DENOISER_RGB_ALBEDO) ? 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo) : 0.0f;
-    k.blendFactor = dn->blendFactor;
-    k.demodulate = dn->demodulateAlbedo ? 1 : 0;
-    k.fireflyThreshold = dv ? dv->fireflyThreshold : 0.0f;
-    k.sigmaLuminance = dv ? dv->sigmaLuminance : 0.0f;
     // the variance-guided mode: prepare writes the pong stream and the moments pass the ping stream (clamped colour, variance in
     // .w), so that the levels ping-pong as without it and the mode needs no stream of its own
     launchDenoisePrepare(beauty, albedo, normal, halfOutput(dev), colour[dv ? 1 : 0], guideNormal, guideAlbedo, k, dev->stream);
@@ -340,77 +351,13 @@ try
   const char* name = "twk_denoise_geometry";
   if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: NULL device handle");
   if (!dn || !dg) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: NULL parameters");
-  if (minSamples != 0 && !dv) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: minSamples without the parameters of the variance-guided mode");
-  if (minSamples != 0 && minSamples < 2) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: minSamples must be 0 (no sampled variance) or >= 2 (one sample has no variance)");
-  if (minSamples == 0 && moments) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_denoise_geometry: a moments buffer without minSamples");
   return denoise(name, dev, dn, dv, beauty, albedo, normal, width, height, denoised, minSamples, moments, dg, geometry, camera);
 }
 TWK_CATCH("twk_denoise_geometry")
 
-// The host form: the kernels of denoise_kernels.hip as loops over the same shared functions (denoise_device.h compiled for the
-// host), RGBA32F, all three modes. The pixels of a pass are independent, so the order of the loops plays no part.
-namespace {
-struct HostDenoise
-{
-  int width, height;
-  DenoiseConstants k;
-  DenoiseGeometryConstants g;
-  const float4 *normal, *albedo, *geometry;
-
-  bool inside(int x, int y) const { return x >= 0 && x < width && y >= 0 && y < height; }
-
-  void moments(const float4* in, float4* out, const float4* sampled, float minSamples) const
-  {
-    for (int y = 0; y < height; ++y) for (int x = 0; x < width; ++x)
-    {
-      const size_t p = (size_t) y * width + x;
-      const float4 cp = in[p], np = normal[p], ap = albedo[p];
-      DenoiseGeometryCentre gc;
-      if (!finite3(cp) || !finite1(luminance(cp)) || !finite3(np) || !finite3(ap) || !denoiseGeometryCentre(g, geometry[p], np, gc)) { out[p] = make_float4(cp.x, cp.y, cp.z, 0.0f); continue; }
-      float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-      for (int dy = -TWK_DENOISE_MOMENTS_RADIUS; dy <= TWK_DENOISE_MOMENTS_RADIUS; ++dy) for (int dx = -TWK_DENOISE_MOMENTS_RADIUS; dx <= TWK_DENOISE_MOMENTS_RADIUS; ++dx)
-      {
-        if ((dx == 0 && dy == 0) || !inside(x + dx, y + dy)) continue;
-        const size_t q = (size_t) (y + dy) * width + (x + dx);
-        if (!finite3(in[q])) continue;
-        momentsTap<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(k, np, ap, luminance(in[q]), normal[q], albedo[q], s0, s1, s2, gc, geometry[q]);
-      }
-      out[p] = sampled ? momentsFinish<true>(k, cp, s0, s1, s2, sampled[p], minSamples) : momentsFinish(k, cp, s0, s1, s2);
-    }
-  }
-
-  void level(const float4* in, float4* out, int step, bool variance) const
-  {
-    for (int y = 0; y < height; ++y) for (int x = 0; x < width; ++x)
-    {
-      const size_t p = (size_t) y * width + x;
-      const float4 cp = in[p], np = normal[p], ap = albedo[p];
-      DenoiseGeometryCentre gc;
-      if (!finite3(cp) || !finite3(np) || !finite3(ap) || !denoiseGeometryCentre(g, geometry[p], np, gc)) { out[p] = cp; continue; }
-      float lp = 0.0f, invL = 0.0f, vsum = 0.0f;
-      if (variance)
-      {
-        lp = luminance(cp);
-        if (!finite1(lp)) { out[p] = cp; continue; }
-        float vs = 0.0f, bs = 0.0f;
-        for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx)
-          if (inside(x + dx * step, y + dy * step)) varianceBlurTap(dx, dy, in[(size_t) (y + dy * step) * width + (x + dx * step)], vs, bs);
-        invL = inverseLuminanceSigma(k, vs, bs);
-      }
-      float sx = 0.0f, sy = 0.0f, sz = 0.0f, wsum = 0.0f;
-      for (int dy = -2; dy <= 2; ++dy) for (int dx = -2; dx <= 2; ++dx)
-      {
-        if (!inside(x + dx * step, y + dy * step)) continue;
-        const size_t q = (size_t) (y + dy * step) * width + (x + dx * step);
-        if (variance) denoiseVarianceTap<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(k, dx, dy, lp, invL, np, ap, in[q], normal[q], albedo[q], sx, sy, sz, wsum, vsum, gc, geometry[q]);
-        else          denoiseTap<TWK_DENOISER_RGB_ALBEDO_NORMAL, true>(k, dx, dy, cp, np, ap, in[q], normal[q], albedo[q], sx, sy, sz, wsum, gc, geometry[q]);
-      }
-      out[p] = make_float4(sx / wsum, sy / wsum, sz / wsum, variance ? vsum / (wsum * wsum) : cp.w);
-    }
-  }
-};
-} // namespace
-
+// The host form: the passes of denoise_kernels.hip as plain loops over the pixels, calling the same four bodies (denoise_device.h
+// compiled for the host) with the global tap source on host pointers. RGBA32F, all three modes. The pixels of a pass are
+// independent, so the order of the loops plays no part.
 int twk_denoise_geometry_host(const TwkDenoiser* dn, const TwkDenoiserGeometry* dg, const TwkDenoiserVariance* dv, int minSamples, const float* beauty, const float* albedo,
                               const float* normal, const float* moments, const float* geometry, const float* camera, int width, int height, float* denoised)
 try
@@ -418,70 +365,43 @@ try
   const char* name = "twk_denoise_geometry_host";
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
   if (!dn || !dg) return refuse(TWK_ERROR_INVALID_VALUE, "NULL parameters");
-  if (dn->inputKind != TWK_DENOISER_RGB_ALBEDO_NORMAL) return refuse(TWK_ERROR_INVALID_VALUE, "the geometry guide needs inputKind TWK_DENOISER_RGB_ALBEDO_NORMAL (the plane's normal comes from the normal guide)");
-  if (dn->iterations < 0 || dn->iterations > 8) return refuse(TWK_ERROR_INVALID_VALUE, "iterations must be in [0, 8]");
-  const float sigmas[3] = {dv ? 1.0f : dn->sigmaColor, dn->sigmaNormal, dn->sigmaAlbedo};
-  for (const float sigma : sigmas)
-    if (!(sigma > 0.0f) || !std::isfinite(1.0f / (sigma * sigma))) return refuse(TWK_ERROR_INVALID_VALUE, "the sigma of every guide in use must be positive and 1 / sigma^2 a finite float");
-  if (!(dn->blendFactor >= 0.0f && dn->blendFactor <= 1.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "blendFactor must be in [0, 1]");
-  if (dv)
-  {
-    if (!(dv->fireflyThreshold >= 0.0f) || !std::isfinite(dv->fireflyThreshold)) return refuse(TWK_ERROR_INVALID_VALUE, "fireflyThreshold must be >= 0 (0 = no clamp) and finite");
-    if (!(dv->sigmaLuminance > 0.0f) || !std::isfinite(dv->sigmaLuminance)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaLuminance must be > 0 and finite");
-  }
-  if (minSamples != 0 && (!dv || minSamples < 2)) return refuse(TWK_ERROR_INVALID_VALUE, "minSamples must be 0 (no sampled variance) or >= 2 beside the parameters of the variance-guided mode");
-  if ((minSamples != 0) != (moments != nullptr)) return refuse(TWK_ERROR_INVALID_VALUE, "a moments buffer goes with minSamples >= 2, and only with it");
-  {
-    const float invPosition = 1.0f / (dg->sigmaPosition * dg->sigmaPosition);
-    if (!(dg->sigmaPosition > 0.0f) || !std::isfinite(invPosition) || !(invPosition > 0.0f)) return refuse(TWK_ERROR_INVALID_VALUE, "sigmaPosition must be > 0 and 1 / sigmaPosition^2 a finite positive float");
-  }
+  DenoiseConstants k;
+  const int rc = denoiseParameters(name, dn, dv, dg, minSamples, moments != nullptr, k); if (rc) return rc;
   if (width < 1 || height < 1) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
-  if (!beauty || !albedo || !normal || !geometry || !camera || !denoised) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer or camera");
+  if (!beauty || !albedo || !normal || !geometry || !camera || !denoised || (minSamples != 0 && !moments)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer or camera");
   const size_t n = (size_t) width * height, bytes = n * sizeof(float4);
   if (overlaps(denoised, beauty, bytes) || overlaps(denoised, albedo, bytes) || overlaps(denoised, normal, bytes) || overlaps(denoised, geometry, bytes) || overlaps(denoised, moments, bytes))
     return refuse(TWK_ERROR_INVALID_VALUE, "the denoised buffer overlaps an input");
-  HostDenoise h;
-  if (!denoiseGeometryConstants(camera, dg->sigmaPosition, dg->instanceStop, h.g)) return refuse(TWK_ERROR_INVALID_VALUE, "the camera is degenerate: P is not finite, or U, V or W does not normalise");
+  DenoiseGeometryConstants g;
+  if (!denoiseGeometryConstants(camera, dg->sigmaPosition, dg->instanceStop, g)) return refuse(TWK_ERROR_INVALID_VALUE, "the camera is degenerate: P is not finite, or U, V or W does not normalise");
   if (dn->iterations == 0 || dn->blendFactor == 1.0f) { memcpy(denoised, beauty, bytes); return TWK_SUCCESS; }
-  const float4* b = reinterpret_cast<const float4*>(beauty);
-  h.width = width; h.height = height;
-  h.k.width = width; h.k.height = height;
-  h.k.invColor  = dv ? 0.0f : 1.0f / (dn->sigmaColor * dn->sigmaColor);
-  h.k.invNormal = 1.0f / (dn->sigmaNormal * dn->sigmaNormal);
-  h.k.invAlbedo = 1.0f / (dn->sigmaAlbedo * dn->sigmaAlbedo);
-  h.k.blendFactor = dn->blendFactor;
-  h.k.demodulate = dn->demodulateAlbedo ? 1 : 0;
-  h.k.fireflyThreshold = dv ? dv->fireflyThreshold : 0.0f;
-  h.k.sigmaLuminance = dv ? dv->sigmaLuminance : 0.0f;
-  h.geometry = reinterpret_cast<const float4*>(geometry);
+  constexpr int KIND = TWK_DENOISER_RGB_ALBEDO_NORMAL;
+  k.width = width; k.height = height;
+  const float4 *b = reinterpret_cast<const float4*>(beauty), *geo = reinterpret_cast<const float4*>(geometry), *sampled = reinterpret_cast<const float4*>(moments);
   std::vector<float4> streams[2] = {std::vector<float4>(n), std::vector<float4>(n)}, guideNormal(n), guideAlbedo(n);
-  h.normal = guideNormal.data(); h.albedo = guideAlbedo.data();
   float4* colour[2] = {streams[0].data(), streams[1].data()};
-  // prepare
-  float4* prepared = colour[dv ? 1 : 0];
-  for (size_t p = 0; p < n; ++p)
+  // every pixel of a pass: f(source of the pixel's taps at `step` in stream `in`, p)
+  const auto pixels = [&](const float4* in, int step, auto f)
   {
-    const float4 bp = b[p], a = reinterpret_cast<const float4*>(albedo)[p], nn = reinterpret_cast<const float4*>(normal)[p];
-    float4 c = bp;
-    guideAlbedo[p] = make_float4(a.x, a.y, a.z, 0.0f);
-    if (h.k.demodulate) { const float3 d = clampedAlbedo(a); c.x = bp.x / d.x; c.y = bp.y / d.y; c.z = bp.z / d.z; }
-    guideNormal[p] = make_float4(nn.x, nn.y, nn.z, 0.0f);
-    prepared[p] = c;
-  }
-  if (dv) h.moments(colour[1], colour[0], reinterpret_cast<const float4*>(moments), (float) minSamples);
-  for (int level = 0; level < dn->iterations; ++level) h.level(colour[level & 1], colour[(level + 1) & 1], 1 << level, dv != nullptr);
-  // finish
-  const float4* last = colour[dn->iterations & 1];
-  float4* out = reinterpret_cast<float4*>(denoised);
-  for (size_t p = 0; p < n; ++p)
+    for (int y = 0; y < height; ++y) for (int x = 0; x < width; ++x)
+    {
+      const DenoiseGlobalTaps taps(in, guideNormal.data(), guideAlbedo.data(), geo, width, height, x, y, step);
+      f(taps, taps.centre);
+    }
+  };
+  for (size_t p = 0; p < n; ++p) denoisePreparePixel(k, p, b, reinterpret_cast<const float4*>(albedo), reinterpret_cast<const float4*>(normal), colour[dv ? 1 : 0], guideNormal.data(), guideAlbedo.data());
+  if (dv)
+    pixels(colour[1], 1, [&](const DenoiseGlobalTaps& taps, size_t p)
+    {
+      colour[0][p] = sampled ? denoiseMomentsPixel<KIND, true, true>(k, g, taps, colour[1][p], sampled + p, (float) minSamples)
+                             : denoiseMomentsPixel<KIND, false, true>(k, g, taps, colour[1][p], nullptr, 0.0f);
+    });
+  for (int level = 0; level < dn->iterations; ++level)
   {
-    const float4 bp = b[p], a = guideAlbedo[p];
-    float4 r = last[p];
-    bool through = !finite3(bp) || !finite3(guideNormal[p]) || !finite3(a);
-    if (h.k.demodulate) { const float3 d = clampedAlbedo(a); r.x = r.x * d.x; r.y = r.y * d.y; r.z = r.z * d.z; }
-    if (through || !finite3(r)) { out[p] = bp; continue; }
-    out[p] = make_float4(r.x + h.k.blendFactor * (bp.x - r.x), r.y + h.k.blendFactor * (bp.y - r.y), r.z + h.k.blendFactor * (bp.z - r.z), bp.w);
+    float4* out = colour[(level + 1) & 1];
+    pixels(colour[level & 1], 1 << level, [&](const DenoiseGlobalTaps& taps, size_t p) { out[p] = dv ? denoiseLevelPixel<KIND, true, true>(k, g, taps) : denoiseLevelPixel<KIND, false, true>(k, g, taps); });
   }
+  for (size_t p = 0; p < n; ++p) denoiseFinishPixel(k, p, b, colour[dn->iterations & 1], guideNormal.data(), guideAlbedo.data(), reinterpret_cast<float4*>(denoised));
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_denoise_geometry_host")

@@ -9,16 +9,16 @@ namespace twk {
 struct alignas(8) Half4 { _Float16 x, y, z, w; };
 static_assert(sizeof(Half4) == 8, "RGBA16F pixel");
 
-TWK_D float4 widen(const Half4 h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); } // exact
+TWK_HD float4 widen(const Half4 h) { return make_float4((float) h.x, (float) h.y, (float) h.z, (float) h.w); } // exact
 // f32 -> f16 round to nearest even (v_cvt_f16_f32 = __float2half; NOT v_cvt_pkrtz_f16_f32, which rounds toward zero):
 // half subnormals are kept (the code object's float_denorm_mode_16_64 is 3), what exceeds 65504 rounds to +-inf.
-TWK_D Half4 narrow(const float4 v)
+TWK_HD Half4 narrow(const float4 v)
 {
   Half4 h;
   h.x = (_Float16) v.x; h.y = (_Float16) v.y; h.z = (_Float16) v.z; h.w = (_Float16) v.w;
   return h;
 }
 // device_math.h pixelOf / widen say the same for float4: kernels that serve both formats are templates over the pixel type
-template<> TWK_D Half4 pixelOf<Half4>(const float4 v) { return narrow(v); }
+template<> TWK_HD Half4 pixelOf<Half4>(const float4 v) { return narrow(v); }
 
 } // namespace twk

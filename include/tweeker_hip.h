@@ -867,6 +867,61 @@ int twk_read_temporal_cascade(TwkDevice dev, float* host, size_t numFloats); /* 
 int twk_temporal_cascade_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
                               const float* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, float* layersOut);
 
+/* ---- The rectified temporal merge — new calls, ABI stays 9, no existing struct changes; without them no kernel and no bit of any
+ * existing call changes ---------------------------------------------------------------------------------------------------------
+ * twk_update_light and twk_update_material leave the temporal history as it is, and twk_temporal_accumulate then keeps blending up
+ * to maxHistory samples of the OLD lighting into every pixel; twk_temporal_reset is the only other remedy and throws the whole
+ * picture's history away. twk_temporal_accumulate_rectified is twk_temporal_accumulate with a per-pixel TRUST t in [0, 1] in the
+ * reprojected history: over a (2 radius + 1)^2 window of pixels of the same instance it tests the paired differences of the frame's
+ * and the history's luminance means against their own scatter, and where the mean difference exceeds gamma standard errors it
+ * scales the history's sample count (and M2) by t before the merge. The loop of "The temporal seam" with a light edit in it:
+ *   twk_update_light(...);                                            (the history stays)
+ *   twk_set_sample_offset; twk_launch 0 .. spp-1; twk_render_geometry; twk_temporal_accumulate_rectified;
+ *   twk_denoise_variance_sampled(beauty = merged colour, moments = merged moments)
+ * The complete definition, why it has this form and what it is not (luminance only; no re-traced temporal gradient; blind below the
+ * window's noise; no colour clamp) is csrc/temporal_rectify_device.h; tests/temporal_rectify_restate.py restates it in numpy. Two
+ * kernel launches and two f32 float4 scratch streams on the handle (allocated on first use, freed with the temporal history).
+ * Where nothing is tested (t = 1) every output has the bits of twk_temporal_accumulate. The defaults are PROVISIONAL: they come
+ * from a numpy prototype, not from a sweep on rendered frames (profiles/r22_temporal_rectify.md). */
+typedef struct TwkTemporalRectify { int radius; int minTaps; float gamma; } TwkTemporalRectify;
+#define TWK_TEMPORAL_RECTIFY_RADIUS 3
+#define TWK_TEMPORAL_RECTIFY_MIN_TAPS 8
+#define TWK_TEMPORAL_RECTIFY_GAMMA 3.0f
+#define TWK_TEMPORAL_RECTIFY_MAX_RADIUS 4
+int twk_temporal_rectify_defaults(TwkTemporalRectify* rp);
+/* Both forms of twk_temporal_accumulate, with its arguments, its outputs and ALL its refusals, plus trustOut: width x height floats
+ * (explicit form; may be NULL like the other outputs; must not overlap an input or another output), 1 where nothing was tested and
+ * where there is no history, 0 where the test took all of a history that was there. Own-buffer form (current NULL: history, the
+ * outputs and the size must be NULL / 0): the trust is kept on the handle (twk_get_temporal_trust_device_pointer,
+ * twk_read_temporal_trust), the other results where twk_temporal_accumulate keeps them, and while twk_temporal_enable_cascade(1)
+ * is set the layers are merged with the trust (twk_temporal_accumulate_cascade_trusted's definition). Plain and rectified calls
+ * may alternate on one handle: they share the history. tp, rp NULL: the defaults. Asynchronous on the handle's stream.
+ * Beside twk_temporal_accumulate's refusals, TWK_ERROR_INVALID_VALUE: radius outside 1..TWK_TEMPORAL_RECTIFY_MAX_RADIUS;
+ * minTaps < 2; gamma negative or not finite. */
+int twk_temporal_accumulate_rectified(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalRectify* rp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                                      int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut);
+/* The trust plane of the last own-buffer (or assembled) rectified merge: one float per pixel of the temporal result.
+ * TWK_ERROR_INVALID_STATE: the last own-buffer merge on the handle was not a rectified one, or its history has been dropped since. */
+int twk_get_temporal_trust_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+int twk_read_temporal_trust(TwkDevice dev, float* host, size_t numFloats);       /* width*height floats of the temporal result; synchronises */
+/* twk_temporal_accumulate_cascade with a trust stream (width x height floats, a trustOut of the call above for the same frame and
+ * history): after the cap, h[j] *= t, hrej *= t, hn *= t (csrc/temporal_cascade_device.h, "the TRUSTED build"). Same arguments,
+ * same refusals; also TWK_ERROR_INVALID_VALUE for a NULL trust and for an output that overlaps it. */
+int twk_temporal_accumulate_cascade_trusted(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                            const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust,
+                                            int width, int height, void* layersOut);
+/* twk_temporal_accumulate_assembled with the rectified merge: on a tiled primary, the assembled planes as the current frame. Same
+ * refusals as twk_temporal_accumulate_assembled, plus those of the parameters above. */
+int twk_temporal_accumulate_assembled_rectified(TwkDevice primary, const TwkTemporal* tp, const TwkTemporalRectify* rp);
+/* Pure CPU, no device: the definitions compiled for the host, for tests and for integrators without a GPU at hand. Host arrays of
+ * width x height x 4 floats (trustOut: width x height); colour is RGBA32F (the merge's arithmetic does not depend on the output
+ * format: narrow colourOut to get the RGBA16F result); history* all NULL or all given with historyCamera; outputs may be NULL. */
+int twk_temporal_rectify_host(const TwkTemporal* tp, const TwkTemporalRectify* rp, const float* colour, const float* moments, const float* geometry,
+                              const float* historyColour, const float* historyMoments, const float* historyGeometry, const TwkCameraDefinition* historyCamera,
+                              int width, int height, float* colourOut, float* momentsOut, float* trustOut);
+int twk_temporal_cascade_trusted_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                                      const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, int width, int height, float* layersOut);
+
 /* ---- Assembling a tiled frame — new calls, ABI stays 9, no existing struct changes; without them no kernel and no bit of any
  * picture changes ----------------------------------------------------------------------------------------------------------------
  * With distribution 1 and several devices every handle renders its checkerboard share into packed launchWidth x H buffers: the
@@ -1096,6 +1151,13 @@ int twk_app_get_tile_assembly(TwkApp app, int* enabled);
  * and geometry when the key is on. */
 #define TWK_TEMPORAL_ORBIT_STEP 0.001f
 int twk_app_get_temporal(TwkApp app, int* enabled, TwkTemporal* tp, int* frames, float* orbitStep);
+/* The rectified merge in that loop: "temporalRectify 0|1" (default 0: the loop merges with twk_temporal_accumulate; 1: with
+ * twk_temporal_accumulate_rectified, on several devices twk_temporal_accumulate_assembled_rectified), "temporalRectifyGamma g"
+ * (>= 0, finite), "temporalRectifyRadius r" (1..4), "temporalRectifyMinTaps n" (>= 2; defaults: twk_temporal_rectify_defaults). A
+ * value outside its range drops the line with a warning; the keys are written back only when they differ from the defaults.
+ * keys: how many of the four keys the description holds — rtigo3_hip refuses any of them without "temporalAccumulation 1", before
+ * a device is created. */
+int twk_app_get_temporal_rectify(TwkApp app, int* enabled, TwkTemporalRectify* rp, int* keys);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

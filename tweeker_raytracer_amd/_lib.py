@@ -29,6 +29,7 @@ TWK_DENOISER_SIGMA_POSITION = 0.01  # twk_denoiser_geometry_defaults (include/tw
 TWK_DENOISER_MIN_SAMPLES = 4  # default "denoiserMinSamples" of twk_denoise_variance_sampled (include/tweeker_hip.h)
 
 TWK_TEMPORAL_MAX_HISTORY, TWK_TEMPORAL_POSITION_TOLERANCE = 32, 0.01  # twk_temporal_defaults (include/tweeker_hip.h)
+TWK_TEMPORAL_RECTIFY_RADIUS, TWK_TEMPORAL_RECTIFY_MIN_TAPS, TWK_TEMPORAL_RECTIFY_GAMMA, TWK_TEMPORAL_RECTIFY_MAX_RADIUS = 3, 8, 3.0, 4  # twk_temporal_rectify_defaults (provisional)
 TWK_NOISE_DARK_FLOOR = 0.01  # twk_noise_defaults (include/tweeker_hip.h); its minSamples is TWK_DENOISER_MIN_SAMPLES
 TWK_ADAPTIVE_TARGET_NOISE, TWK_ADAPTIVE_MAX_SAMPLES = 0.05, 4096  # twk_adaptive_defaults (include/tweeker_hip.h)
 TWK_CASCADE_LAYERS, TWK_CASCADE_START, TWK_CASCADE_BASE = 6, 1.0, 8.0  # twk_cascade_defaults (include/tweeker_hip.h)
@@ -118,6 +119,17 @@ class Temporal(C.Structure):
 
     def __init__(self, maxHistory=TWK_TEMPORAL_MAX_HISTORY, positionTolerance=TWK_TEMPORAL_POSITION_TOLERANCE):
         super().__init__(int(maxHistory), positionTolerance)
+
+
+class TemporalRectify(C.Structure):
+    """≙ TwkTemporalRectify: parameters of twk_temporal_accumulate_rectified. radius (1..4): the window of the paired test is
+    (2 radius + 1)^2 pixels; minTaps (>= 2): fewer pixels of the centre's instance in the window and nothing is tested; gamma (>= 0):
+    the standard errors a mean difference must exceed before the history is discounted. Without arguments:
+    twk_temporal_rectify_defaults (provisional)."""
+    _fields_ = [("radius", C.c_int), ("minTaps", C.c_int), ("gamma", C.c_float)]
+
+    def __init__(self, radius=TWK_TEMPORAL_RECTIFY_RADIUS, minTaps=TWK_TEMPORAL_RECTIFY_MIN_TAPS, gamma=TWK_TEMPORAL_RECTIFY_GAMMA):
+        super().__init__(int(radius), int(minTaps), gamma)
 
 
 class TemporalFrame(C.Structure):
@@ -281,10 +293,12 @@ SYMBOLS = [
     "twk_adaptive_plan_defaults", "twk_adaptive_plan", "twk_adaptive_plan_host", "twk_launch_adaptive_planned", "twk_read_plan", "twk_app_get_adaptive_plan",
     "twk_cascade_defaults", "twk_cascade_resolve_defaults", "twk_enable_cascade", "twk_read_cascade", "twk_get_cascade_device_pointer", "twk_cascade_resolve",
     "twk_get_resolved_device_pointer", "twk_read_resolved", "twk_cascade_fold_host", "twk_cascade_resolve_host", "twk_app_get_cascade",
+    "twk_temporal_rectify_defaults", "twk_temporal_accumulate_rectified", "twk_get_temporal_trust_device_pointer", "twk_read_temporal_trust",
+    "twk_temporal_accumulate_cascade_trusted", "twk_temporal_accumulate_assembled_rectified", "twk_temporal_rectify_host", "twk_temporal_cascade_trusted_host",
     "twk_temporal_accumulate_cascade", "twk_temporal_enable_cascade", "twk_get_temporal_cascade_device_pointer", "twk_read_temporal_cascade", "twk_temporal_cascade_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",
-    "twk_read_assembled_geometry", "twk_temporal_accumulate_assembled", "twk_app_get_temporal",
+    "twk_read_assembled_geometry", "twk_temporal_accumulate_assembled", "twk_app_get_temporal", "twk_app_get_temporal_rectify",
     "twk_profile_reset", "twk_profile_get", "twk_stats_enable", "twk_stats_get", "twk_stream_peak_gbps", "twk_gather_peak",
     "twk_debug_capture", "twk_debug_shade_builds", "twk_debug_shade_build_slots", "twk_debug_read_first_hits", "twk_trace_rays", "twk_debug_trace_queue", "twk_debug_read_acceleration", "twk_debug_snapshot_scene", "twk_debug_math",
     "twk_app_create", "twk_app_create_from_strings", "twk_app_destroy", "twk_app_info", "twk_app_set_resolution",

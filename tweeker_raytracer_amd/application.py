@@ -177,6 +177,16 @@ class Application:
         return bool(on.value), tp, n.value, step.value
 
     @property
+    def temporalRectify(self):
+        """(enabled, TemporalRectify, keys) from "temporalRectify", "temporalRectifyGamma", "temporalRectifyRadius",
+        "temporalRectifyMinTaps" of the system description: with the key on, the loop of `temporal` merges with
+        Device.temporalAccumulateRectified (on several devices temporalAccumulateAssembledRectified). keys: how many of the four keys
+        the description holds; they mean nothing without "temporalAccumulation 1" and rtigo3_hip refuses them there."""
+        on, rp, keys = C.c_int(0), L.TemporalRectify(), C.c_int(0)
+        L.check(L.lib.twk_app_get_temporal_rectify(self._h, C.byref(on), C.byref(rp), C.byref(keys)))
+        return bool(on.value), rp, keys.value
+
+    @property
     def fireflyCascade(self):
         """(enabled, Cascade, CascadeResolve) from "fireflyCascade", "fireflyCascadeLayers", "fireflyCascadeStart",
         "fireflyCascadeBase", "fireflyCascadeKappa" of the system description; initDevice enables the device's cascade when the key

@@ -11,6 +11,7 @@
 #include "adaptive_plan_device.h"
 #include "cascade_device.h"
 #include "temporal_cascade_device.h"
+#include "temporal_rectify_device.h"
 #include "assemble_device.h"
 #include "error_state.h"
 
@@ -52,6 +53,11 @@ void launchNoise(const float4* moments, size_t numElements, float* errorMap, Twk
 void launchCascadeResolve(const CascadeConstants& k, float kappa, const float4* layers, float* lambda, int width, int height, void* resolved, bool half, hipStream_t stream);
 void launchTemporalCascade(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, float4* layersOut,
                            const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream);
+void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, float4* layersOut,
+                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream);
+void launchTemporalRectify(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
+                           const float4* historyGeometry, float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut,
+                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream);
 void launchAssemble(const AssembleShape& s, const AssembleTable& table, int count, hipStream_t stream);
 }
 
@@ -178,6 +184,11 @@ struct TwkDevice_t
   float4* d_temporal[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; void* d_temporalColour = nullptr;
   int temporalWidth = 0, temporalHeight = 0, temporalFormat = TWK_OUTPUT_FLOAT4, temporalKept = 0; bool temporalHasHistory = false, temporalValid = false;
   TwkCameraDefinition temporalCamera;
+  // twk_temporal_accumulate_rectified (temporal_rectify_device.h): the two scratch streams its first launch writes and its second
+  // reads, rectifyPixels float4 each, shared by the explicit and the own-buffer form; and the own-buffer form's trust plane, one
+  // float per pixel of the temporal result, valid while the last own-buffer merge was a rectified one. Freed by dropTemporal.
+  float4* d_rectify[2] = {nullptr, nullptr}; size_t rectifyPixels = 0;
+  float* d_temporalTrust = nullptr; bool temporalTrustValid = false;
   // twk_temporal_enable_cascade: while temporalCascade is set the own-buffer twk_temporal_accumulate also merges the handle's cascade
   // layers (temporal_cascade_device.h) with the same previous geometry and camera, into two sets of [temporalCascadeLayers]
   // [temporalCascadePixels] float4 — the set temporalCascadeKept holds what the last call kept, the other receives this call's.
@@ -294,12 +305,18 @@ int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int ena
 int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);
 // device_post.hip
 void dropTemporal(TwkDevice dev);
+int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const void* colour, const float4* moments, const float4* geometry,
+                const float4* layers, int width, int height);
+int temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify);
+int temporalAssembledFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify);
+// device_temporal_rectify.hip
+int ensureRectifyScratch(TwkDevice dev, size_t pixels);
 // device_cascade.hip
 CascadeOn cascadeFold(TwkDevice dev);
 // device_temporal_cascade.hip
 void dropTemporalCascade(TwkDevice dev);
 const char* temporalCascadeRefusal(TwkDevice dev);
-int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry);
+int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust = nullptr);
 // device_assemble.hip
 void dropAssembled(TwkDevice dev);
 }

@@ -11,6 +11,9 @@ void twk::dropTemporal(TwkDevice dev)
 {
   for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
   freeDevice(dev->d_temporalColour);
+  for (int s = 0; s < 2; ++s) freeDevice(dev->d_rectify[s]);
+  freeDevice(dev->d_temporalTrust);
+  dev->rectifyPixels = 0; dev->temporalTrustValid = false;
   dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
   dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
 }
@@ -18,8 +21,10 @@ void twk::dropTemporal(TwkDevice dev)
 // The merge of twk_temporal_accumulate's own-buffer form and of twk_temporal_accumulate_assembled, after their refusals: the frame
 // (colour in the output format, moments, geometry; layers: the cascade layers to merge while twk_temporal_enable_cascade is on,
 // nullptr = the handle's own) of width x height pixels against the history the handle kept, which it then replaces. k: maxHistory
-// and tol2 are set.
-static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const void* colour, const float4* moments, const float4* geometry, const float4* layers, int width, int height)
+// and tol2 are set. rectify: nullptr = the plain merge; else the rectified one (temporal_rectify_device.h), which also writes the
+// handle's trust plane and, while twk_temporal_enable_cascade is on, discounts the layers' history by it.
+int twk::temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const void* colour, const float4* moments, const float4* geometry,
+                     const float4* layers, int width, int height)
 {
   const size_t n = (size_t) width * height;
   if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
@@ -46,12 +51,66 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
   }
   // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
   int rc;
-  if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
-  launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_temporalColour, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
-  HIP_TRY(hipGetLastError());
+  if (rectify)
+  {
+    // the trust first: the layers' merge reads it
+    if ((rc = ensureRectifyScratch(dev, n))) return rc;
+    if (!dev->d_temporalTrust) HIP_TRY(hipMalloc(&dev->d_temporalTrust, n * sizeof(float)));
+    launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->d_temporalColour,
+                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream);
+    HIP_TRY(hipGetLastError());
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust))) return rc;
+    dev->temporalTrustValid = true;
+  }
+  else
+  {
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
+    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_temporalColour, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
+    HIP_TRY(hipGetLastError());
+    dev->temporalTrustValid = false; // the trust plane, if any, is an earlier frame's
+  }
   HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, n * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
   dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
   return TWK_SUCCESS;
+}
+
+// The own-buffer form of twk_temporal_accumulate and of twk_temporal_accumulate_rectified after the checks of their arguments: the
+// refusals of the handle's state, then the merge. k: maxHistory and tol2 are set.
+int twk::temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify)
+{
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+  if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
+  const int width = dev->launchWidth, height = dev->state.resolution[1];
+  const size_t n = (size_t) width * height;
+  if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+  if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+  if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
+  const void* colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+  if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
+  return temporalOwn(dev, name, k, rectify, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
+}
+
+// twk_temporal_accumulate_assembled and twk_temporal_accumulate_assembled_rectified after the checks of their parameters
+int twk::temporalAssembledFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify)
+{
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+  if (!(dev->state.distribution && 1 < dev->count))
+    return refuse(TWK_ERROR_INVALID_STATE, "the handle is not tiled (distribution 1, more than one device): its own buffers are the picture, twk_temporal_accumulate merges them");
+  if (!dev->momentsEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no luminance moments: render with twk_enable_moments(1)");
+  if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no geometry AOV: twk_enable_geometry(1) and twk_render_geometry_tile");
+  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
+  const int needed[3] = {TWK_PLANE_OUTPUT, TWK_PLANE_MOMENTS, TWK_PLANE_CASCADE};
+  static const char* const neededNames[3] = {"TWK_PLANE_OUTPUT", "TWK_PLANE_MOMENTS", "TWK_PLANE_CASCADE"};
+  for (int j = 0; j < (dev->temporalCascade ? 3 : 2); ++j)
+    if (!dev->assembledValid[needed[j]] || !dev->d_assembled[needed[j]])
+      return refuse(TWK_ERROR_INVALID_STATE, std::string(neededNames[j]) + " has not been assembled on this handle: twk_assemble_devices_with_geometry first");
+  if (!dev->d_assembledGeometry) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV has not been assembled on this handle: twk_assemble_devices_with_geometry first");
+  if (!dev->assembledGeometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the assembled geometry AOV is stale, older than the camera, the state or the scene: twk_render_geometry_tile and twk_assemble_devices_with_geometry first");
+  return temporalOwn(dev, name, k, rectify, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS]), static_cast<const float4*>(dev->d_assembledGeometry),
+                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE]) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
 }
 
 // =============================================================================================
@@ -475,17 +534,7 @@ try
   if (own)
   {
     if (history || colourOut || historyOut || momentsOut || width || height) return refuse(TWK_ERROR_INVALID_VALUE, "a history, outputs or a size without a current frame (pass both frames, or neither for the handle's own buffers)");
-    if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
-    if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
-    width = dev->launchWidth; height = dev->state.resolution[1];
-    const size_t n = (size_t) width * height;
-    if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
-    if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
-    if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
-    colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-    if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
-    if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
-    return temporalOwn(dev, name, k, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
+    return temporalOwnFrame(dev, name, k, nullptr);
   }
   else
   {
@@ -533,21 +582,7 @@ try
   TemporalConstants k;
   memset(&k, 0, sizeof(k));
   k.maxHistory = (float) tp->maxHistory; k.tol2 = tp->positionTolerance * tp->positionTolerance;
-  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
-  if (!(dev->state.distribution && 1 < dev->count))
-    return refuse(TWK_ERROR_INVALID_STATE, "the handle is not tiled (distribution 1, more than one device): its own buffers are the picture, twk_temporal_accumulate merges them");
-  if (!dev->momentsEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no luminance moments: render with twk_enable_moments(1)");
-  if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no geometry AOV: twk_enable_geometry(1) and twk_render_geometry_tile");
-  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
-  const int needed[3] = {TWK_PLANE_OUTPUT, TWK_PLANE_MOMENTS, TWK_PLANE_CASCADE};
-  static const char* const neededNames[3] = {"TWK_PLANE_OUTPUT", "TWK_PLANE_MOMENTS", "TWK_PLANE_CASCADE"};
-  for (int j = 0; j < (dev->temporalCascade ? 3 : 2); ++j)
-    if (!dev->assembledValid[needed[j]] || !dev->d_assembled[needed[j]])
-      return refuse(TWK_ERROR_INVALID_STATE, std::string(neededNames[j]) + " has not been assembled on this handle: twk_assemble_devices_with_geometry first");
-  if (!dev->d_assembledGeometry) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV has not been assembled on this handle: twk_assemble_devices_with_geometry first");
-  if (!dev->assembledGeometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the assembled geometry AOV is stale, older than the camera, the state or the scene: twk_render_geometry_tile and twk_assemble_devices_with_geometry first");
-  return temporalOwn(dev, name, k, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS]), static_cast<const float4*>(dev->d_assembledGeometry),
-                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE]) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
+  return temporalAssembledFrame(dev, name, k, nullptr);
 }
 TWK_CATCH("twk_temporal_accumulate_assembled")
 

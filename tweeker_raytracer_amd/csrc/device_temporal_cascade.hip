@@ -24,7 +24,8 @@ const char* twk::temporalCascadeRefusal(TwkDevice dev)
 // The own-buffer form's merge of the frame's layers, on its stream: k, geometry and historyGeometry (nullptr: the temporal merge
 // has no history) are those of the twk_temporal_accumulate or twk_temporal_accumulate_assembled that calls it, before it swaps its
 // history. layers: [layers][k.width x k.height] float4, the assembled ones of a tiled primary; nullptr: the handle's own.
-int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry)
+// trust: nullptr = the plain merge; else the trust plane of the rectified merge of the same frame, already written on the stream.
+int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust)
 {
   int rc = ensureStreams(dev); if (rc) return rc;
   const size_t n = (size_t) k.width * k.height;
@@ -46,8 +47,12 @@ int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const flo
   const int keep = dev->temporalCascadeHasHistory ? 1 - dev->temporalCascadeKept : dev->temporalCascadeKept;
   TemporalConstants kc = k;
   kc.hasHistory = history ? 1 : 0;
-  launchTemporalCascade(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
-                        dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
+  if (trust)
+    launchTemporalCascadeTrusted(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr, trust,
+                                 dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
+  else
+    launchTemporalCascade(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
+                          dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
   HIP_TRY(hipGetLastError());
   dev->temporalCascadeKept = keep; dev->temporalCascadeHasHistory = true; dev->temporalCascadeValid = true;
   return TWK_SUCCESS;
@@ -85,17 +90,16 @@ static int temporalCascadeParameters(const char* name, const TwkTemporal* tp, co
   return TWK_SUCCESS;
 }
 
-extern "C" {
-
-int twk_temporal_accumulate_cascade(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
-                                    const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, void* layersOut)
-try
+// The explicit form, plain (trusted false) and trusted (trust: width x height floats)
+static int temporalCascadeExplicit(const char* name, bool trusted, TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                   const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust, int width, int height,
+                                   void* layersOut)
 {
-  const char* name = "twk_temporal_accumulate_cascade";
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, std::string(name) + ": " + text); };
   if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
   if (!currentLayers || !currentGeometry || !layersOut) return refuse(TWK_ERROR_INVALID_VALUE, "NULL current layers, current geometry or output");
   if (historyLayers && (!historyGeometry || !historyCamera)) return refuse(TWK_ERROR_INVALID_VALUE, "history layers without the history's geometry or camera");
+  if (trusted && !trust) return refuse(TWK_ERROR_INVALID_VALUE, "NULL trust");
   TemporalConstants k;
   CascadeConstants c;
   int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
@@ -103,13 +107,68 @@ try
   if (overlaps(layersOut, layerBytes, currentLayers, layerBytes) || overlaps(layersOut, layerBytes, currentGeometry, plane) ||
       (historyLayers && (overlaps(layersOut, layerBytes, historyLayers, layerBytes) || overlaps(layersOut, layerBytes, historyGeometry, plane))))
     return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps an input (the kernel gathers the history at other pixels)");
+  if (trusted && overlaps(layersOut, layerBytes, trust, n * sizeof(float))) return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps the trust");
   if ((rc = activate(dev, name))) return rc;
-  launchTemporalCascade(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
-                        historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream);
+  if (trusted)
+    launchTemporalCascadeTrusted(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
+                                 historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<const float*>(trust), static_cast<float4*>(layersOut), k, c, dev->stream);
+  else
+    launchTemporalCascade(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
+                          historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
+
+// The host-only form, plain and trusted
+static int temporalCascadeHost(const char* name, bool trusted, const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry,
+                               const float* historyLayers, const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, int width, int height,
+                               float* layersOut)
+{
+  if (!currentLayers || !currentGeometry || !layersOut) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL current layers, current geometry or output");
+  if (historyLayers && (!historyGeometry || !historyCamera)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": history layers without the history's geometry or camera");
+  if (trusted && !trust) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL trust");
+  TemporalConstants k;
+  CascadeConstants c;
+  int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
+  const size_t n = (size_t) width * height, all = n * (size_t) c.layers;
+  // (a host array of floats need not have a float4's alignment)
+  std::vector<float4> layers(all), geometry(n), history(historyLayers ? all : 0), hGeometry(historyLayers ? n : 0), out(all);
+  memcpy(layers.data(), currentLayers, all * sizeof(float4));
+  memcpy(geometry.data(), currentGeometry, n * sizeof(float4));
+  if (historyLayers)
+  {
+    memcpy(history.data(), historyLayers, all * sizeof(float4));
+    memcpy(hGeometry.data(), historyGeometry, n * sizeof(float4));
+  }
+  const float4* H = historyLayers ? history.data() : nullptr;
+  const float4* hG = historyLayers ? hGeometry.data() : nullptr;
+  for (size_t p = 0; p < n; ++p)
+  {
+    if (trusted) temporalCascadePixel<true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), trust);
+    else         temporalCascadePixel(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data());
+  }
+  memcpy(layersOut, out.data(), all * sizeof(float4));
+  return TWK_SUCCESS;
+}
+
+extern "C" {
+
+int twk_temporal_accumulate_cascade(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                    const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, void* layersOut)
+try
+{
+  return temporalCascadeExplicit("twk_temporal_accumulate_cascade", false, dev, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, nullptr, width, height, layersOut);
+}
 TWK_CATCH("twk_temporal_accumulate_cascade")
+
+int twk_temporal_accumulate_cascade_trusted(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                            const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust,
+                                            int width, int height, void* layersOut)
+try
+{
+  return temporalCascadeExplicit("twk_temporal_accumulate_cascade_trusted", true, dev, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust, width, height, layersOut);
+}
+TWK_CATCH("twk_temporal_accumulate_cascade_trusted")
 
 int twk_temporal_enable_cascade(TwkDevice dev, int enable)
 try
@@ -157,27 +216,16 @@ int twk_temporal_cascade_host(const TwkTemporal* tp, const TwkCascade* cp, const
                               const float* historyGeometry, const TwkCameraDefinition* historyCamera, int width, int height, float* layersOut)
 try
 {
-  const char* name = "twk_temporal_cascade_host";
-  if (!currentLayers || !currentGeometry || !layersOut) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL current layers, current geometry or output");
-  if (historyLayers && (!historyGeometry || !historyCamera)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": history layers without the history's geometry or camera");
-  TemporalConstants k;
-  CascadeConstants c;
-  int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
-  const size_t n = (size_t) width * height, all = n * (size_t) c.layers;
-  // (a host array of floats need not have a float4's alignment)
-  std::vector<float4> layers(all), geometry(n), history(historyLayers ? all : 0), hGeometry(historyLayers ? n : 0), out(all);
-  memcpy(layers.data(), currentLayers, all * sizeof(float4));
-  memcpy(geometry.data(), currentGeometry, n * sizeof(float4));
-  if (historyLayers)
-  {
-    memcpy(history.data(), historyLayers, all * sizeof(float4));
-    memcpy(hGeometry.data(), historyGeometry, n * sizeof(float4));
-  }
-  for (size_t p = 0; p < n; ++p)
-    temporalCascadePixel(k, c, layers.data(), geometry.data(), historyLayers ? history.data() : nullptr, historyLayers ? hGeometry.data() : nullptr, n, p, out.data());
-  memcpy(layersOut, out.data(), all * sizeof(float4));
-  return TWK_SUCCESS;
+  return temporalCascadeHost("twk_temporal_cascade_host", false, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, nullptr, width, height, layersOut);
 }
 TWK_CATCH("twk_temporal_cascade_host")
+
+int twk_temporal_cascade_trusted_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                                      const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, int width, int height, float* layersOut)
+try
+{
+  return temporalCascadeHost("twk_temporal_cascade_trusted_host", true, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust, width, height, layersOut);
+}
+TWK_CATCH("twk_temporal_cascade_trusted_host")
 
 } // extern "C"

@@ -238,6 +238,30 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && f[0] >= 0.0f && std::isfinite(f[0])) temporalPositionTolerance = f[0];
       else if (ok) warnings.push_back("temporalPositionTolerance must be >= 0 and finite, keeping the previous value");
     }
+    // the rectified merge in that loop (twk_temporal_accumulate_rectified, read by twk_app_get_temporal_rectify): a value the call
+    // would refuse drops the line. Every key counts as seen: a render loop refuses them without "temporalAccumulation 1".
+    else if (key == "temporalRectify") { ok = readInt(parser, i[0]); if (ok) { temporalRectify = (i[0] == 1) ? 1 : 0; ++temporalRectifyKeys; } }
+    else if (key == "temporalRectifyGamma")
+    {
+      ok = readFloat(parser, f[0]);
+      if (ok) ++temporalRectifyKeys;
+      if (ok && f[0] >= 0.0f && std::isfinite(f[0])) temporalRectifyGamma = f[0];
+      else if (ok) warnings.push_back("temporalRectifyGamma must be >= 0 and finite, keeping the previous value");
+    }
+    else if (key == "temporalRectifyRadius")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok) ++temporalRectifyKeys;
+      if (ok && i[0] >= 1 && i[0] <= TWK_TEMPORAL_RECTIFY_MAX_RADIUS) temporalRectifyRadius = i[0];
+      else if (ok) warnings.push_back("temporalRectifyRadius must be in 1..4, keeping the previous value");
+    }
+    else if (key == "temporalRectifyMinTaps")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok) ++temporalRectifyKeys;
+      if (ok && i[0] >= 2) temporalRectifyMinTaps = i[0];
+      else if (ok) warnings.push_back("temporalRectifyMinTaps must be >= 2, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -338,6 +362,10 @@ std::string Application::systemDescription() const
   if (temporalOrbitStep != TWK_TEMPORAL_ORBIT_STEP) d << "temporalOrbitStep " << temporalOrbitStep << std::endl;
   if (temporalMaxHistory != TWK_TEMPORAL_MAX_HISTORY) d << "temporalMaxHistory " << temporalMaxHistory << std::endl;
   if (temporalPositionTolerance != TWK_TEMPORAL_POSITION_TOLERANCE) d << "temporalPositionTolerance " << temporalPositionTolerance << std::endl;
+  if (temporalRectify != 0) d << "temporalRectify " << temporalRectify << std::endl;
+  if (temporalRectifyGamma != TWK_TEMPORAL_RECTIFY_GAMMA) d << "temporalRectifyGamma " << temporalRectifyGamma << std::endl;
+  if (temporalRectifyRadius != TWK_TEMPORAL_RECTIFY_RADIUS) d << "temporalRectifyRadius " << temporalRectifyRadius << std::endl;
+  if (temporalRectifyMinTaps != TWK_TEMPORAL_RECTIFY_MIN_TAPS) d << "temporalRectifyMinTaps " << temporalRectifyMinTaps << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

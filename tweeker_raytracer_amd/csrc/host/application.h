@@ -129,6 +129,14 @@ public:
   float temporalOrbitStep = TWK_TEMPORAL_ORBIT_STEP;
   int   temporalMaxHistory = TWK_TEMPORAL_MAX_HISTORY;
   float temporalPositionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  // "temporalRectify" (1: that loop merges with twk_temporal_accumulate_rectified / twk_temporal_accumulate_assembled_rectified),
+  // "temporalRectifyGamma", "temporalRectifyRadius", "temporalRectifyMinTaps" (TwkTemporalRectify; twk_temporal_rectify_defaults'
+  // values until a key sets them); temporalRectifyKeys: how many of the four keys the description holds
+  int   temporalRectify = 0;
+  float temporalRectifyGamma = TWK_TEMPORAL_RECTIFY_GAMMA;
+  int   temporalRectifyRadius = TWK_TEMPORAL_RECTIFY_RADIUS;
+  int   temporalRectifyMinTaps = TWK_TEMPORAL_RECTIFY_MIN_TAPS;
+  int   temporalRectifyKeys = 0;
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel

@@ -223,6 +223,19 @@ try
 }
 TWK_CATCH("twk_app_get_temporal")
 
+int twk_app_get_temporal_rectify(TwkApp app, int* enabled, TwkTemporalRectify* rp, int* keys)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_temporal_rectify: NULL app");
+  if (!enabled || !rp || !keys) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_temporal_rectify: NULL argument");
+  const Application& a = app->app;
+  *enabled = (a.temporalRectify != 0) ? 1 : 0;
+  rp->radius = a.temporalRectifyRadius; rp->minTaps = a.temporalRectifyMinTaps; rp->gamma = a.temporalRectifyGamma;
+  *keys = a.temporalRectifyKeys;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_temporal_rectify")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {

@@ -26,7 +26,10 @@
 // "fireflyCascade 1". After the last frame the merged layers are resolved, the denoiser takes the merged colour (or the resolved
 // picture) and the merged moments, and the screenshot is that. The frame-rate line counts frames x samplesSqrt² iterations.
 // Refused before any device is created: with "targetNoise" or "adaptiveSampling", with a "lensShader" other than 0, with strategy 1
-// or 2, and on several devices without "tileAssembly 1".
+// or 2, and on several devices without "tileAssembly 1". With "temporalRectify 1" beside it the merge is the rectified one
+// (twk_temporal_accumulate_rectified; twk_temporal_accumulate_assembled_rectified on the first device) with "temporalRectifyGamma",
+// "temporalRectifyRadius" and "temporalRectifyMinTaps"; any of these four keys without "temporalAccumulation 1" is refused before any
+// device is created.
 // With "denoiserGeometry 1" beside "denoiser 3" the filter, in whichever mode is on, is twk_denoise_geometry: the geometry AOV is
 // traced once before the screenshot is filtered (twk_render_geometry; on several devices with "tileAssembly 1"
 // twk_render_geometry_tile and ONE twk_assemble_devices_with_geometry), the temporal loop uses its last frame's own geometry, and
@@ -244,6 +247,14 @@ int main(int argc, char* argv[])
   float temporalOrbitStep = 0.0f;
   TwkTemporal temporal;
   TWK_OK(twk_app_get_temporal(app, &temporalEnabled, &temporal, &temporalFrames, &temporalOrbitStep));
+  int rectifyEnabled = 0, rectifyKeys = 0; // "temporalRectify 1": the orbit's merge is the rectified one
+  TwkTemporalRectify rectify;
+  TWK_OK(twk_app_get_temporal_rectify(app, &rectifyEnabled, &rectify, &rectifyKeys));
+  if (rectifyKeys > 0 && !temporalEnabled)
+  {
+    std::cerr << "ERROR: temporalRectify, temporalRectifyGamma, temporalRectifyRadius and temporalRectifyMinTaps set the merge of the moving-camera loop: they need temporalAccumulation 1\n";
+    return 1;
+  }
   if (temporalEnabled && (targetNoiseEnabled || adaptiveEnabled))
   {
     std::cerr << "ERROR: temporalAccumulation renders a fixed orbit of frames; targetNoise and adaptiveSampling end or thin a single frame's loop and do not go with it\n";
@@ -368,7 +379,8 @@ int main(int argc, char* argv[])
       if (count == 1)
       {
         TWK_OK(twk_render_geometry(devices[0]));
-        TWK_OK(twk_temporal_accumulate(devices[0], &temporal, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr));
+        if (rectifyEnabled) TWK_OK(twk_temporal_accumulate_rectified(devices[0], &temporal, &rectify, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr));
+        else                TWK_OK(twk_temporal_accumulate(devices[0], &temporal, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr));
         continue;
       }
       for (int i = 0; i < count; ++i) TWK_OK(twk_render_geometry_tile(devices[(size_t) i]));
@@ -376,7 +388,8 @@ int main(int argc, char* argv[])
       if (frame == temporalFrames - 1 && denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO) planes |= TWK_PLANE_BIT(TWK_PLANE_ALBEDO);
       if (frame == temporalFrames - 1 && denoiserEnabled && denoiser.inputKind >= TWK_DENOISER_RGB_ALBEDO_NORMAL) planes |= TWK_PLANE_BIT(TWK_PLANE_NORMAL);
       TWK_OK(twk_assemble_devices_with_geometry(devices[0], planes, devices.data(), count));
-      TWK_OK(twk_temporal_accumulate_assembled(devices[0], &temporal));
+      if (rectifyEnabled) TWK_OK(twk_temporal_accumulate_assembled_rectified(devices[0], &temporal, &rectify));
+      else                TWK_OK(twk_temporal_accumulate_assembled(devices[0], &temporal));
     }
     iterationIndex = (unsigned int) temporalFrames * spp;
   }

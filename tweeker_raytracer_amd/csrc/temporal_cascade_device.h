@@ -37,6 +37,14 @@
 // business (temporal_device.h), which this leaves untouched. As there: no motion vectors, no environment reprojection (a miss never
 // has history), the pinhole lens only, one device, no tiles; the paper's variance term is not reprojected, and neither the noise
 // estimate nor the adaptive passes see the merged layers.
+//
+// The TRUSTED build (twk_temporal_accumulate_cascade_trusted; temporal_rectify_device.h defines the trust): beside the streams above
+// one float t per pixel, the trustOut of twk_temporal_accumulate_rectified. After the cap, and only there,
+//   h[j].k = h[j].k * t;  hrej = hrej * t;  hn = hn * t
+// and the last line runs on the results: out[0].w = hn * t + nc. The history is discounted in every layer by the factor its plain
+// mean was discounted by; the merge stays linear, so twk_cascade_resolve runs unchanged on the result. A pass-through pixel does
+// not read t. t = 1 gives the bits of the build without a trust (x * 1 is x); t = 0 leaves the frame's sums plus 0 — a history
+// sum that is not finite gives NaN there, as it would have given inf.
 #pragma once
 #include "temporal_device.h"
 #include "cascade_device.h"
@@ -46,8 +54,10 @@ namespace twk {
 // Pixel p of Lc / geometry -> out; H, hGeometry: the history (H == nullptr: none; k.hasHistory says the same). Every buffer's layer
 // stride is `stride` >= k.width * k.height. The loops over taps and layers have constant trip counts and are unrolled, the layer loop
 // predicated by j < K, so that the small arrays live in registers (cascade_device.h).
+// Trusted: the build that discounts the capped history by trust[p] (above); otherwise trust is not read.
+template<bool Trusted = false>
 TWK_HD void temporalCascadePixel(const TemporalConstants& k, const CascadeConstants& c, const float4* Lc, const float4* geometry, const float4* H,
-                                 const float4* hGeometry, const size_t stride, const size_t p, float4* out)
+                                 const float4* hGeometry, const size_t stride, const size_t p, float4* out, const float* trust = nullptr)
 {
   const int K = c.layers;
   const size_t top = (size_t) (K - 1) * stride;
@@ -109,6 +119,8 @@ TWK_CASCADE_UNROLL
   float hn = sn / ws, hrej = srej / ws, f = 1.0f;
   const bool capped = hn > k.maxHistory;
   if (capped) { f = k.maxHistory / hn; hrej = hrej * f; hn = k.maxHistory; }
+  float t = 1.0f;
+  if (Trusted) { t = trust[p]; hrej = hrej * t; hn = hn * t; }
 TWK_CASCADE_UNROLL
   for (int j = 0; j < TWK_CASCADE_MAX_LAYERS; ++j)
   {
@@ -126,6 +138,7 @@ TWK_CASCADE_UNROLL
     }
     float hx = sx / ws, hy = sy / ws, hz = sz / ws;
     if (capped) { hx = hx * f; hy = hy * f; hz = hz * f; }
+    if (Trusted) { hx = hx * t; hy = hy * t; hz = hz * t; }
     out[(size_t) j * stride + p] = make_float4(hx + cur.x, hy + cur.y, hz + cur.z, (j == 0) ? hn + nc : ((j == K - 1) ? hrej + rc : 0.0f));
   }
 }

@@ -242,6 +242,49 @@ class Device:
         L.check(L.lib.twk_read_temporal_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
         return out
 
+    # ---- the rectified temporal merge (include/tweeker_hip.h "The rectified temporal merge", csrc/temporal_rectify_device.h) ----
+    def temporalAccumulateRectified(self, params=None, rectify=None, current=None, history=None, shape=None, colourOut=None, historyOut=None, momentsOut=None,
+                                    trustOut=None):
+        """twk_temporal_accumulate_rectified: temporalAccumulate with a per-pixel trust in the reprojected history — after
+        updateLight / updateMaterial the history of the old lighting is discounted where a paired test over a window says the frame
+        and the history differ by more than noise. params: L.Temporal, rectify: L.TemporalRectify (None = the defaults). The two
+        forms and their arguments are temporalAccumulate's; trustOut: a device pointer to height*width floats or None. Own-buffer
+        form: readTemporalTrust / temporalTrustDevicePointer hand out the trust, and with enableTemporalCascade the layers are
+        merged with it."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda f: None if f is None else C.byref(f)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_rectified(self._h, ref(params), ref(rectify), ref(current), ref(history), int(w), int(h), ptr(colourOut), ptr(historyOut),
+                                                        ptr(momentsOut), ptr(trustOut)))
+
+    def temporalAccumulateAssembledRectified(self, params=None, rectify=None):
+        """twk_temporal_accumulate_assembled_rectified, on a tiled primary: temporalAccumulateAssembled with the rectified merge."""
+        ref = lambda f: None if f is None else C.byref(f)
+        L.check(L.lib.twk_temporal_accumulate_assembled_rectified(self._h, ref(params), ref(rectify)))
+
+    def temporalTrustDevicePointer(self):
+        """(device pointer, bytes) of the trust plane the last own-buffer rectified merge kept: height*width floats."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_temporal_trust_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def readTemporalTrust(self):
+        """The trust of the last own-buffer rectified merge: float32 [height, launchWidth] ([height, width] on a tiled primary); 1
+        where nothing was tested, 0 where the test took all of the history."""
+        out = np.empty((self.state.resolution[1], self._temporalWidth()), dtype=np.float32)
+        L.check(L.lib.twk_read_temporal_trust(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def temporalAccumulateCascadeTrusted(self, params=None, cascade=None, currentLayers=None, currentGeometry=None, historyLayers=None, historyGeometry=None,
+                                         historyCamera=None, trust=None, shape=None, layersOut=None):
+        """twk_temporal_accumulate_cascade_trusted: temporalAccumulateCascade with the capped history of every layer scaled by
+        trust, a device pointer to height*width floats (a trustOut of temporalAccumulateRectified for the same frame and history)."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda s: None if s is None else C.byref(s)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_cascade_trusted(self._h, ref(params), ref(cascade), ptr(currentLayers), ptr(currentGeometry), ptr(historyLayers),
+                                                              ptr(historyGeometry), ref(historyCamera), ptr(trust), int(w), int(h), ptr(layersOut)))
+
     def setTimeView(self, enable=True):
         """≙ USE_TIME_VIEW: alpha of the accumulation buffer = running mean of the sample's shader-clock cycles x clockFactor x 1e-9."""
         L.check(L.lib.twk_set_time_view(self._h, int(bool(enable))))

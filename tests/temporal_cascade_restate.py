@@ -1,92 +1,65 @@
 """The cascade's layers through the temporal merge (csrc/temporal_cascade_device.h) restated statement for statement in numpy
-float32, with a count per branch, and the synthetic layers the tests feed both sides. The projection and the test of a tap's
-geometry are temporal_restate's arithmetic (temporal_device.h temporalProject / temporalTapGeometry), the thresholds and the
-luminance cascade_restate's. No test in here: tests/test_temporal_cascade_host.py (CPU) and tests/test_gpu_temporal_cascade.py use it."""
+float32, with a count per branch, and the synthetic layers the tests feed both sides. The projection, the footprint's taps and
+the test of a tap's geometry are temporal_restate's (temporal_device.h temporalProject / temporalFootprint / temporalTapGeometry), the
+thresholds and the luminance cascade_restate's. No test in here: tests/test_temporal_cascade_host.py (CPU) and tests/test_gpu_temporal_cascade.py use it."""
 import numpy as np
 
 import cascade_restate
 import temporal_restate
-from temporal_restate import F, U32, _dot3, _finite3, camera_constants
+from temporal_restate import F, U32, _finite3, footprint_taps, project
 
 BRANCHES = ("miss", "geometry_not_finite", "current_n_below_1", "behind", "off_screen", "outside", "id_mismatch", "position", "history_n_below_1",
             "history_rejected_not_finite", "weight_zero", "no_tap", "capped", "uncapped", "history_sum_not_finite", "took")
 
 
-def project(g, cam, width, height):
-    """temporalProject over g [..., 4]: (fx, fy, vv, front, inside), every operation in float32."""
-    (P0, P1, P2), A, B, C, D = camera_constants(cam)
-    with np.errstate(all="ignore"):
-        vx, vy, vz = g[..., 0] - P0, g[..., 1] - P1, g[..., 2] - P2
-        a, b, c = _dot3(vx, vy, vz, *A), _dot3(vx, vy, vz, *B), _dot3(vx, vy, vz, *C)
-        vv = _dot3(vx, vy, vz, vx, vy, vz)
-        front = c * D > F(0.0)
-        fx = ((a / c + F(1.0)) * F(0.5)) * F(width) - F(0.5)
-        fy = ((b / c + F(1.0)) * F(0.5)) * F(height) - F(0.5)
-        inside = (fx >= F(-1.0)) & (fx < F(width)) & (fy >= F(-1.0)) & (fy < F(height))
-    assert fx.dtype == F and fy.dtype == F and vv.dtype == F
-    return fx, fy, vv, front, inside
-
-
-def restate_temporal_cascade(layers, g, history, cam, max_history, tolerance, info=None, taps=None):
-    """twk_temporal_accumulate_cascade on float32 arrays: layers [K, H, W, 4] the current frame's, g [H, W, 4] its geometry; history =
-    (layers [K, H, W, 4], geometry [H, W, 4]) or None; cam the history's camera. Returns (merged layers, took) — took: the pixels
-    that merged history; every other pixel holds the input's bits. info (a dict) receives one count per branch of the definition;
-    taps (a list) receives, per tap in the definition's order, (counted mask, weight, qy, qx)."""
+def merge_cascade(layers, g, history, cam, max_history, tolerance, info=None, taps=None, trust=None):
+    """temporalCascadePixel on float32 arrays: layers [K, H, W, 4] the current frame's, g [H, W, 4] its geometry; history = (layers
+    [K, H, W, 4], geometry [H, W, 4]) or None; cam the history's camera; trust [H, W]: the trusted build, None: the plain one.
+    Returns (merged layers, took, hn) — took: the pixels that merged history, every other pixel holds the input's bits; hn: the
+    history's count after the cap and before the trust, 0 where nothing was taken. info (a dict) receives one count per branch of
+    the definition; taps (a list) receives, per tap in the definition's order, (counted mask, weight, qy, qx)."""
     Lc, g = np.ascontiguousarray(layers, F), np.ascontiguousarray(g, F)
     K, height, width = Lc.shape[:3]
     assert 2 <= K <= cascade_restate.MAX_LAYERS and g.shape == (height, width, 4)
     out = Lc.copy()
-    took = np.zeros((height, width), bool)
     if history is None:
-        return out, took
+        return out, np.zeros((height, width), bool), np.zeros((height, width), F)
     Hl, hg = (np.ascontiguousarray(a, F) for a in history)
     assert Hl.shape == Lc.shape and hg.shape == g.shape
-    max_h, tol2 = F(max_history), F(tolerance) * F(tolerance)
-    gw = g[..., 3].view(U32)
+    max_h = F(max_history)
     nc, rc = Lc[0, ..., 3], Lc[K - 1, ..., 3]
     with np.errstate(all="ignore"):
-        hit = gw != 0
+        hit = g[..., 3].view(U32) != 0
         gfinite = _finite3(g)
         enough_now = np.isfinite(nc) & ~(nc < F(1.0))
         cand = hit & gfinite & enough_now
         fx, fy, vv, front, inside = project(g, cam, width, height)
         ok = cand & front & inside
-        fx0, fy0 = np.floor(fx), np.floor(fy)
-        tx, ty = fx - fx0, fy - fy0
-        x0, y0 = np.where(ok, fx0, F(0)).astype(np.int64), np.where(ok, fy0, F(0)).astype(np.int64)
         s = np.zeros((K, height, width, 3), F)
         sn, srej, ws = (np.zeros((height, width), F) for _ in range(3))
         carried = np.zeros((height, width), bool)
         counts = dict(outside=0, id_mismatch=0, position=0, history_n_below_1=0, history_rejected_not_finite=0, weight_zero=0)
-        for dy in (0, 1):
-            for dx in (0, 1):
-                qx, qy = x0 + dx, y0 + dy
-                inpic = (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
-                qxc, qyc = np.clip(qx, 0, width - 1), np.clip(qy, 0, height - 1)
-                hgq, hq = hg[qyc, qxc], Hl[:, qyc, qxc]
-                same = hgq[..., 3].view(U32) == gw
-                ex, ey, ez = hgq[..., 0] - g[..., 0], hgq[..., 1] - g[..., 1], hgq[..., 2] - g[..., 2]
-                near = (ex * ex + ey * ey) + ez * ez <= tol2 * vv
-                hn_q, hrej_q = hq[0, ..., 3], hq[K - 1, ..., 3]
-                enough = np.isfinite(hn_q) & (hn_q >= F(1.0))
-                rejected_finite = np.isfinite(hrej_q)
-                w = (tx if dx else F(1.0) - tx) * (ty if dy else F(1.0) - ty)
-                positive = w > F(0.0)
-                belongs = ok & inpic & same & near
-                counted = belongs & enough & rejected_finite & positive
-                s = np.where(counted[None, ..., None], s + w[None, ..., None] * hq[..., :3], s)
-                sn = np.where(counted, sn + w * hn_q, sn)
-                srej = np.where(counted, srej + w * hrej_q, srej)
-                ws = np.where(counted, ws + w, ws)
-                carried |= counted & ~np.isfinite(hq[..., :3]).all(axis=(0, -1))
-                counts["outside"] += int((ok & ~inpic).sum())
-                counts["id_mismatch"] += int((ok & inpic & ~same).sum())
-                counts["position"] += int((ok & inpic & same & ~near).sum())
-                counts["history_n_below_1"] += int((belongs & ~enough).sum())
-                counts["history_rejected_not_finite"] += int((belongs & enough & ~rejected_finite).sum())
-                counts["weight_zero"] += int((belongs & enough & rejected_finite & ~positive).sum())
-                if taps is not None:
-                    taps.append((counted, w, qyc, qxc))
+        for w, q, inpic, same, near in footprint_taps(g, hg, fx, fy, vv, ok, tolerance):
+            hq = Hl[(slice(None),) + q]
+            hn_q, hrej_q = hq[0, ..., 3], hq[K - 1, ..., 3]
+            enough = np.isfinite(hn_q) & (hn_q >= F(1.0))
+            rejected_finite = np.isfinite(hrej_q)
+            positive = w > F(0.0)
+            belongs = ok & inpic & same & near
+            counted = belongs & enough & rejected_finite & positive
+            s = np.where(counted[None, ..., None], s + w[None, ..., None] * hq[..., :3], s)
+            sn = np.where(counted, sn + w * hn_q, sn)
+            srej = np.where(counted, srej + w * hrej_q, srej)
+            ws = np.where(counted, ws + w, ws)
+            carried |= counted & ~np.isfinite(hq[..., :3]).all(axis=(0, -1))
+            counts["outside"] += int((ok & ~inpic).sum())
+            counts["id_mismatch"] += int((ok & inpic & ~same).sum())
+            counts["position"] += int((ok & inpic & same & ~near).sum())
+            counts["history_n_below_1"] += int((belongs & ~enough).sum())
+            counts["history_rejected_not_finite"] += int((belongs & enough & ~rejected_finite).sum())
+            counts["weight_zero"] += int((belongs & enough & rejected_finite & ~positive).sum())
+            if taps is not None:
+                taps.append((counted, w) + q)
         took = ws > F(0.0)
         h = s / ws[None, ..., None]
         hn, hrej = sn / ws, srej / ws
@@ -95,6 +68,10 @@ def restate_temporal_cascade(layers, g, history, cam, max_history, tolerance, in
         h = np.where(capped[None, ..., None], h * f[None, ..., None], h)
         hrej = np.where(capped, hrej * f, hrej)
         hn = np.where(capped, max_h, hn)
+        hn_capped = hn
+        if trust is not None:
+            t = np.ascontiguousarray(trust, F).reshape(height, width)
+            h, hrej, hn = h * t[None, ..., None], hrej * t, hn * t
         merged = np.zeros_like(Lc)
         merged[..., :3] = h + Lc[..., :3]
         merged[0, ..., 3] = hn + nc
@@ -106,7 +83,13 @@ def restate_temporal_cascade(layers, g, history, cam, max_history, tolerance, in
         info.update(miss=int((~hit).sum()), geometry_not_finite=int((hit & ~gfinite).sum()), current_n_below_1=int((hit & gfinite & ~enough_now).sum()),
                     behind=int((cand & ~front).sum()), off_screen=int((cand & front & ~inside).sum()), no_tap=int((ok & ~took).sum()),
                     capped=int((took & capped).sum()), uncapped=int((took & ~capped).sum()), history_sum_not_finite=int((took & carried).sum()), took=int(took.sum()))
-    return out, took
+    return out, took, np.where(took, hn_capped, F(0.0)).astype(F)
+
+
+def restate_temporal_cascade(layers, g, history, cam, max_history, tolerance, info=None, taps=None, trust=None):
+    """twk_temporal_accumulate_cascade (trust [H, W]: twk_temporal_accumulate_cascade_trusted) on float32 arrays, merge_cascade's
+    arguments. Returns (merged layers, took)."""
+    return merge_cascade(layers, g, history, cam, max_history, tolerance, info, taps, trust)[:2]
 
 
 # ---- synthetic frames and layers ---------------------------------------------------------------------------------------------------

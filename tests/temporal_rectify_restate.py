@@ -1,65 +1,26 @@
 """The rectified temporal merge of csrc/temporal_rectify_device.h restated statement for statement in numpy float32 (no GPU needed),
 with a count per branch, the trusted build of the cascade's temporal merge (csrc/temporal_cascade_device.h), and the frames the tests
-feed both sides. The camera constants, the dot product, the finiteness test and the synthetic frames are temporal_restate's; the
-gather is written out again because restate_temporal returns only its merged result, not the reprojected history the test needs.
+feed both sides. The gather, the capped history and the synthetic frames are temporal_restate's, the cascade's merge
+temporal_cascade_restate's.
 No test in here: tests/test_temporal_rectify_host.py (CPU) and tests/test_gpu_temporal_rectify*.py use it."""
 import numpy as np
 
 import temporal_cascade_restate
 import temporal_restate
-from temporal_restate import F, U32, _dot3, _finite3, camera_constants
+from temporal_restate import F, U32, capped_history, gather
 
 BRANCHES = ("no_history", "key_zero_with_history", "few_taps", "explained_by_noise", "discounted", "trust_zero", "merged", "passed_through")
 
 
 def reproject(cur, mc, g, history, cam, max_history, tolerance):
-    """Launch 1 on float32 [H, W, 4] arrays: temporal_device.h's gather, the quotients and the cap. Returns (h [H, W, 3], hmean, hM2,
-    hn, took): the reprojected, capped history, all 0 where took is False (hn = 0: no history)."""
+    """Launch 1 on float32 [H, W, 4] arrays: temporal_restate's gather and capped history. Returns (h [H, W, 3], hmean, hM2, hn, took):
+    the reprojected, capped history, all 0 where took is False (hn = 0: no history)."""
     height, width = cur.shape[:2]
     zero = np.zeros((height, width), F)
     if history is None:
         return np.zeros((height, width, 3), F), zero, zero.copy(), zero.copy(), np.zeros((height, width), bool)
-    hc, hm, hg = (np.ascontiguousarray(a, F) for a in history)
-    (P0, P1, P2), A, B, C, D = camera_constants(cam)
-    max_h, tol2 = F(max_history), F(tolerance) * F(tolerance)
-    gw = g[..., 3].view(U32)
-    with np.errstate(all="ignore"):
-        cand = (gw != 0) & _finite3(g) & _finite3(cur) & _finite3(mc) & ~(mc[..., 2] < F(1.0))
-        vx, vy, vz = g[..., 0] - P0, g[..., 1] - P1, g[..., 2] - P2
-        a, b, c = _dot3(vx, vy, vz, *A), _dot3(vx, vy, vz, *B), _dot3(vx, vy, vz, *C)
-        vv = _dot3(vx, vy, vz, vx, vy, vz)
-        front = c * D > F(0.0)
-        fx = ((a / c + F(1.0)) * F(0.5)) * F(width) - F(0.5)
-        fy = ((b / c + F(1.0)) * F(0.5)) * F(height) - F(0.5)
-        inside = (fx >= F(-1.0)) & (fx < F(width)) & (fy >= F(-1.0)) & (fy < F(height))
-        ok = cand & front & inside
-        fx0, fy0 = np.floor(fx), np.floor(fy)
-        tx, ty = fx - fx0, fy - fy0
-        x0, y0 = np.where(ok, fx0, F(0)).astype(np.int64), np.where(ok, fy0, F(0)).astype(np.int64)
-        sx, sy, sz, smean, sm2, sn, ws = (np.zeros((height, width), F) for _ in range(7))
-        for dy in (0, 1):
-            for dx in (0, 1):
-                qx, qy = x0 + dx, y0 + dy
-                inpic = (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
-                qxc, qyc = np.clip(qx, 0, width - 1), np.clip(qy, 0, height - 1)
-                hgq, hcq, hmq = hg[qyc, qxc], hc[qyc, qxc], hm[qyc, qxc]
-                same = hgq[..., 3].view(U32) == gw
-                ex, ey, ez = hgq[..., 0] - g[..., 0], hgq[..., 1] - g[..., 1], hgq[..., 2] - g[..., 2]
-                near = (ex * ex + ey * ey) + ez * ez <= tol2 * vv
-                counted = ok & inpic & same & near & _finite3(hcq) & _finite3(hmq) & (hmq[..., 2] >= F(1.0))
-                w = (tx if dx else F(1.0) - tx) * (ty if dy else F(1.0) - ty)
-                sx = np.where(counted, sx + w * hcq[..., 0], sx)
-                sy = np.where(counted, sy + w * hcq[..., 1], sy)
-                sz = np.where(counted, sz + w * hcq[..., 2], sz)
-                smean = np.where(counted, smean + w * hmq[..., 0], smean)
-                sm2 = np.where(counted, sm2 + w * hmq[..., 1], sm2)
-                sn = np.where(counted, sn + w * hmq[..., 2], sn)
-                ws = np.where(counted, ws + w, ws)
-        took = ws > F(0.0)
-        hx, hy, hz, hmean, hm2, hn = sx / ws, sy / ws, sz / ws, smean / ws, sm2 / ws, sn / ws
-        capped = hn > max_h
-        hm2 = np.where(capped, hm2 * (max_h / hn), hm2)
-        hn = np.where(capped, max_h, hn)
+    sums, took, _ = gather(cur, mc, g, history, cam, tolerance)
+    hx, hy, hz, hmean, hm2, hn, _ = capped_history(sums, max_history)
     h = np.where(took[..., None], np.stack([hx, hy, hz], axis=-1), F(0.0)).astype(F)
     hmean, hm2, hn = (np.where(took, a, F(0.0)).astype(F) for a in (hmean, hm2, hn))
     return h, hmean, hm2, hn, took
@@ -144,44 +105,9 @@ def expect_rectify(colour_raw, moments, geometry, history, cam, max_history, tol
 
 
 def restate_temporal_cascade_trusted(layers, g, history, cam, max_history, tolerance, trust):
-    """The trusted build of temporalCascadePixel: which taps count and with which weight is restate_temporal_cascade's (its `taps`);
-    the sums, the quotients and the cap are repeated here in its order, then h[j] *= t, hrej *= t, hn *= t, then the sums with the
-    frame's. Returns (merged layers, took, hn after the cap)."""
-    Lc, g = np.ascontiguousarray(layers, F), np.ascontiguousarray(g, F)
-    K, height, width = Lc.shape[:3]
-    taps = []
-    plain, took = temporal_cascade_restate.restate_temporal_cascade(Lc, g, history, cam, max_history, tolerance, taps=taps)
-    out = Lc.copy()
-    if history is None:
-        return out, took, np.zeros((height, width), F)
-    Hl = np.ascontiguousarray(history[0], F)
-    t = np.ascontiguousarray(trust, F).reshape(height, width)
-    max_h = F(max_history)
-    with np.errstate(all="ignore"):
-        s = np.zeros((K, height, width, 3), F)
-        sn, srej, ws = (np.zeros((height, width), F) for _ in range(3))
-        for counted, w, qyc, qxc in taps:
-            hq = Hl[:, qyc, qxc]
-            s = np.where(counted[None, ..., None], s + w[None, ..., None] * hq[..., :3], s)
-            sn = np.where(counted, sn + w * hq[0, ..., 3], sn)
-            srej = np.where(counted, srej + w * hq[K - 1, ..., 3], srej)
-            ws = np.where(counted, ws + w, ws)
-        assert np.array_equal(ws > F(0.0), took)
-        h = s / ws[None, ..., None]
-        hn, hrej = sn / ws, srej / ws
-        capped = hn > max_h
-        f = max_h / hn
-        h = np.where(capped[None, ..., None], h * f[None, ..., None], h)
-        hrej = np.where(capped, hrej * f, hrej)
-        hn = np.where(capped, max_h, hn)
-        h, hrej, hn_t = h * t[None, ..., None], hrej * t, hn * t
-        merged = np.zeros_like(Lc)
-        merged[..., :3] = h + Lc[..., :3]
-        merged[0, ..., 3] = hn_t + Lc[0, ..., 3]
-        merged[K - 1, ..., 3] = hrej + Lc[K - 1, ..., 3]
-    assert merged.dtype == F
-    out[:, took] = merged[:, took]
-    return out, took, np.where(took, hn, F(0.0)).astype(F)
+    """The trusted build of temporalCascadePixel: temporal_cascade_restate's merge with h[j] *= t, hrej *= t, hn *= t after the cap.
+    Returns (merged layers, took, hn after the cap)."""
+    return temporal_cascade_restate.merge_cascade(layers, g, history, cam, max_history, tolerance, trust=trust)
 
 
 # ---- frames ------------------------------------------------------------------------------------------------------------------------

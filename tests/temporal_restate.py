@@ -1,5 +1,6 @@
 """The temporal merge of csrc/temporal_device.h restated statement for statement in numpy float32 (no GPU needed), the centre
-rays of the geometry AOV, and the synthetic frames the tests feed both sides. Shared by tests/test_temporal_host.py (CPU) and
+rays of the geometry AOV, and the synthetic frames the tests feed both sides. The projection, the footprint's taps, the gather and
+the capped history are written here once: tests/temporal_rectify_restate.py and tests/temporal_cascade_restate.py call them. Shared by tests/test_temporal_host.py (CPU) and
 tests/test_gpu_temporal.py / tests/test_gpu_geometry.py (which compare the device's bits with it)."""
 import numpy as np
 
@@ -50,25 +51,10 @@ def centre_rays(cam, width, height):
     return P, out
 
 
-def restate_temporal(cur, mc, g, history, cam, max_history, tolerance, info=None):
-    """twk_temporal_accumulate on float32 [H, W, 4] arrays: cur = the current colour WIDENED, mc its moments, g its geometry;
-    history = (colour, moments, geometry) or None; cam = the history's camera. Returns (colour f32, moments f32, took) — took: the
-    pixels that merged history; the others pass through (the caller keeps the input's bits there). info (a dict) receives one
-    count per branch of the definition."""
-    cur, mc, g = (np.ascontiguousarray(a, F) for a in (cur, mc, g))
-    height, width = cur.shape[:2]
-    colour, moments = cur.copy(), mc.copy()
-    took = np.zeros((height, width), bool)
-    if history is None:
-        return colour, moments, took
-    hc, hm, hg = (np.ascontiguousarray(a, F) for a in history)
+def project(g, cam, width, height):
+    """temporalProject over g [..., 4]: (fx, fy, vv, front, inside), every operation in float32."""
     (P0, P1, P2), A, B, C, D = camera_constants(cam)
-    max_h, tol2 = F(max_history), F(tolerance) * F(tolerance)
-    gw = g[..., 3].view(U32)
     with np.errstate(all="ignore"):
-        hit = gw != 0
-        finite = _finite3(g) & _finite3(cur) & _finite3(mc)
-        cand = hit & finite & ~(mc[..., 2] < F(1.0))
         vx, vy, vz = g[..., 0] - P0, g[..., 1] - P1, g[..., 2] - P2
         a, b, c = _dot3(vx, vy, vz, *A), _dot3(vx, vy, vz, *B), _dot3(vx, vy, vz, *C)
         vv = _dot3(vx, vy, vz, vx, vy, vz)
@@ -76,44 +62,99 @@ def restate_temporal(cur, mc, g, history, cam, max_history, tolerance, info=None
         fx = ((a / c + F(1.0)) * F(0.5)) * F(width) - F(0.5)
         fy = ((b / c + F(1.0)) * F(0.5)) * F(height) - F(0.5)
         inside = (fx >= F(-1.0)) & (fx < F(width)) & (fy >= F(-1.0)) & (fy < F(height))
-        ok = cand & front & inside
+    assert fx.dtype == F and fy.dtype == F and vv.dtype == F
+    return fx, fy, vv, front, inside
+
+
+def footprint_taps(g, hg, fx, fy, vv, ok, tolerance):
+    """The four taps of the footprint of (fx, fy) in the definition's order, dy = 0, 1 outer and dx = 0, 1 inner, for the pixels
+    `ok` (candidates that project into the previous view). Per tap: (w, q, inpic, same, near) — the bilinear weight, the history
+    pixel q = (qy, qx) as an index clipped into the picture, and the masks every merge shares: q inside the picture, the history's
+    geometry hg[q] with the instance bits of g, and within the tolerance of g (temporalTapGeometry)."""
+    height, width = g.shape[:2]
+    gw = g[..., 3].view(U32)
+    with np.errstate(all="ignore"):
+        tol2 = F(tolerance) * F(tolerance)
         fx0, fy0 = np.floor(fx), np.floor(fy)
         tx, ty = fx - fx0, fy - fy0
         x0, y0 = np.where(ok, fx0, F(0)).astype(np.int64), np.where(ok, fy0, F(0)).astype(np.int64)
-        sx, sy, sz, smean, sm2, sn, ws = (np.zeros((height, width), F) for _ in range(7))
-        taps = np.zeros((height, width), np.int64)
-        counts = dict(outside=0, id_mismatch=0, position=0, history_not_finite=0, history_n_below_1=0)
-        for dy in (0, 1):
-            for dx in (0, 1):
+    for dy in (0, 1):
+        for dx in (0, 1):
+            with np.errstate(all="ignore"):
                 qx, qy = x0 + dx, y0 + dy
                 inpic = (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
-                qxc, qyc = np.clip(qx, 0, width - 1), np.clip(qy, 0, height - 1)
-                hgq, hcq, hmq = hg[qyc, qxc], hc[qyc, qxc], hm[qyc, qxc]
+                q = (np.clip(qy, 0, height - 1), np.clip(qx, 0, width - 1))
+                hgq = hg[q]
                 same = hgq[..., 3].view(U32) == gw
                 ex, ey, ez = hgq[..., 0] - g[..., 0], hgq[..., 1] - g[..., 1], hgq[..., 2] - g[..., 2]
                 near = (ex * ex + ey * ey) + ez * ez <= tol2 * vv
-                fin = _finite3(hcq) & _finite3(hmq)
-                enough = hmq[..., 2] >= F(1.0)
-                counted = ok & inpic & same & near & fin & enough
                 w = (tx if dx else F(1.0) - tx) * (ty if dy else F(1.0) - ty)
-                sx = np.where(counted, sx + w * hcq[..., 0], sx)
-                sy = np.where(counted, sy + w * hcq[..., 1], sy)
-                sz = np.where(counted, sz + w * hcq[..., 2], sz)
-                smean = np.where(counted, smean + w * hmq[..., 0], smean)
-                sm2 = np.where(counted, sm2 + w * hmq[..., 1], sm2)
-                sn = np.where(counted, sn + w * hmq[..., 2], sn)
-                ws = np.where(counted, ws + w, ws)
-                taps += counted
-                counts["outside"] += int((ok & ~inpic).sum())
-                counts["id_mismatch"] += int((ok & inpic & ~same).sum())
-                counts["position"] += int((ok & inpic & same & ~near).sum())
-                counts["history_not_finite"] += int((ok & inpic & same & near & ~fin).sum())
-                counts["history_n_below_1"] += int((ok & inpic & same & near & fin & ~enough).sum())
+            yield w, q, inpic, same, near
+
+
+def gather(cur, mc, g, history, cam, tolerance):
+    """temporalGather on float32 [H, W, 4] arrays, history = (colour, moments, geometry): the candidates, the projection and the
+    four taps. Returns (sums, took, counts) — sums = (sx, sy, sz, smean, sM2, sn, ws), took = ws > 0, and one count per branch."""
+    hc, hm, hg = (np.ascontiguousarray(a, F) for a in history)
+    height, width = cur.shape[:2]
+    with np.errstate(all="ignore"):
+        hit = g[..., 3].view(U32) != 0
+        finite = _finite3(g) & _finite3(cur) & _finite3(mc)
+        cand = hit & finite & ~(mc[..., 2] < F(1.0))
+        fx, fy, vv, front, inside = project(g, cam, width, height)
+        ok = cand & front & inside
+        sx, sy, sz, smean, sm2, sn, ws = (np.zeros((height, width), F) for _ in range(7))
+        taps = np.zeros((height, width), np.int64)
+        counts = dict(outside=0, id_mismatch=0, position=0, history_not_finite=0, history_n_below_1=0)
+        for w, q, inpic, same, near in footprint_taps(g, hg, fx, fy, vv, ok, tolerance):
+            hcq, hmq = hc[q], hm[q]
+            fin = _finite3(hcq) & _finite3(hmq)
+            enough = hmq[..., 2] >= F(1.0)
+            counted = ok & inpic & same & near & fin & enough
+            sx = np.where(counted, sx + w * hcq[..., 0], sx)
+            sy = np.where(counted, sy + w * hcq[..., 1], sy)
+            sz = np.where(counted, sz + w * hcq[..., 2], sz)
+            smean = np.where(counted, smean + w * hmq[..., 0], smean)
+            sm2 = np.where(counted, sm2 + w * hmq[..., 1], sm2)
+            sn = np.where(counted, sn + w * hmq[..., 2], sn)
+            ws = np.where(counted, ws + w, ws)
+            taps += counted
+            counts["outside"] += int((ok & ~inpic).sum())
+            counts["id_mismatch"] += int((ok & inpic & ~same).sum())
+            counts["position"] += int((ok & inpic & same & ~near).sum())
+            counts["history_not_finite"] += int((ok & inpic & same & near & ~fin).sum())
+            counts["history_n_below_1"] += int((ok & inpic & same & near & fin & ~enough).sum())
         took = ws > F(0.0)
+    counts.update(miss=int((~hit).sum()), current_not_finite=int((hit & ~finite).sum()), current_n_below_1=int((hit & finite & ~cand).sum()),
+                  behind=int((cand & ~front).sum()), off_screen=int((cand & front & ~inside).sum()), no_tap=int((ok & ~took).sum()),
+                  one_tap=int((took & (taps == 1)).sum()), four_taps=int((took & (taps == 4)).sum()), took=int(took.sum()))
+    return (sx, sy, sz, smean, sm2, sn, ws), took, counts
+
+
+def capped_history(sums, max_history):
+    """temporalHistory: the six quotients by ws and the cap. Returns (hx, hy, hz, hmean, hM2, hn, capped), meaningful where ws > 0."""
+    sx, sy, sz, smean, sm2, sn, ws = sums
+    max_h = F(max_history)
+    with np.errstate(all="ignore"):
         hx, hy, hz, hmean, hm2, hn = sx / ws, sy / ws, sz / ws, smean / ws, sm2 / ws, sn / ws
         capped = hn > max_h
         hm2 = np.where(capped, hm2 * (max_h / hn), hm2)
         hn = np.where(capped, max_h, hn)
+    return hx, hy, hz, hmean, hm2, hn, capped
+
+
+def restate_temporal(cur, mc, g, history, cam, max_history, tolerance, info=None):
+    """twk_temporal_accumulate on float32 [H, W, 4] arrays: cur = the current colour WIDENED, mc its moments, g its geometry;
+    history = (colour, moments, geometry) or None; cam = the history's camera. Returns (colour f32, moments f32, took) — took: the
+    pixels that merged history; the others pass through (the caller keeps the input's bits there). info (a dict) receives one
+    count per branch of the definition."""
+    cur, mc, g = (np.ascontiguousarray(a, F) for a in (cur, mc, g))
+    colour, moments = cur.copy(), mc.copy()
+    if history is None:
+        return colour, moments, np.zeros(cur.shape[:2], bool)
+    sums, took, counts = gather(cur, mc, g, history, cam, tolerance)
+    hx, hy, hz, hmean, hm2, hn, capped = capped_history(sums, max_history)
+    with np.errstate(all="ignore"):
         n = hn + mc[..., 2]
         r = mc[..., 2] / n
         merged = np.stack([hx + (cur[..., 0] - hx) * r, hy + (cur[..., 1] - hy) * r, hz + (cur[..., 2] - hz) * r, cur[..., 3]], axis=-1)
@@ -124,10 +165,7 @@ def restate_temporal(cur, mc, g, history, cam, max_history, tolerance, info=None
     moments[took] = merged_m[took]
     if info is not None:
         info.update(counts)
-        info.update(miss=int((~hit).sum()), current_not_finite=int((hit & ~finite).sum()), current_n_below_1=int((hit & finite & ~cand).sum()),
-                    behind=int((cand & ~front).sum()), off_screen=int((cand & front & ~inside).sum()), no_tap=int((ok & ~took).sum()),
-                    capped=int((took & capped).sum()), uncapped=int((took & ~capped).sum()), one_tap=int((took & (taps == 1)).sum()),
-                    four_taps=int((took & (taps == 4)).sum()), took=int(took.sum()))
+        info.update(capped=int((took & capped).sum()), uncapped=int((took & ~capped).sum()))
     return colour, moments, took
 
 

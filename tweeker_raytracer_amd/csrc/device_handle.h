@@ -1,6 +1,6 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass in its three forms: uniform, listed, planned — shade_device.h "the samples of a thread"), device_post.hip (compositor,
-// tonemap, denoiser, temporal, noise estimate), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame, with or without its geometry AOV), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// tonemap, denoiser, noise estimate), device_temporal.hip (the temporal merge, plain and rectified), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame, with or without its geometry AOV), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
@@ -279,6 +279,15 @@ inline size_t outputPixels(TwkDevice dev)
   return (size_t) ((dev->d_outputExternal && dev->outputFrame) ? dev->state.resolution[0] : dev->launchWidth) * dev->state.resolution[1];
 }
 
+// Whether the byte ranges [a, a + aBytes) and [b, b + bBytes) share a byte; a NULL pointer overlaps nothing
+inline bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
+{
+  if (!a || !b) return false;
+  const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+  return x < y + bBytes && y < x + aBytes;
+}
+inline bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
+
 // Scratch device allocation of one call; freed on every return path.
 template<typename T> struct ScopedDeviceBuffer
 {
@@ -303,14 +312,10 @@ int ensureStreamsForPaths(TwkDevice dev, size_t paths);
 // device_api.hip
 int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int enable);
 int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);
-// device_post.hip
+// device_temporal.hip
 void dropTemporal(TwkDevice dev);
-int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const void* colour, const float4* moments, const float4* geometry,
-                const float4* layers, int width, int height);
-int temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify);
-int temporalAssembledFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify);
-// device_temporal_rectify.hip
-int ensureRectifyScratch(TwkDevice dev, size_t pixels);
+int temporalParameters(const char* name, const TwkTemporal* tp, TemporalConstants& k);
+int temporalHistoryCamera(const char* name, const TwkCameraDefinition& camera, TemporalConstants& k);
 // device_cascade.hip
 CascadeOn cascadeFold(TwkDevice dev);
 // device_temporal_cascade.hip

@@ -1,117 +1,10 @@
 // What runs on finished pictures: compositor, tonemapper, the a-trous denoiser (≙ optixDenoiserInvoke, Optix7Gui
-// Application.cpp:2478) and the temporal reprojection.
+// Application.cpp:2478) and the noise estimate. The temporal merge is device_temporal.hip's.
 #include "device_handle.h"
 
 #include <cmath>
 #include <cstring>
 #include <vector>
-
-// Frees the streams of twk_temporal_accumulate's own-buffer form: the next call has no history
-void twk::dropTemporal(TwkDevice dev)
-{
-  for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
-  freeDevice(dev->d_temporalColour);
-  for (int s = 0; s < 2; ++s) freeDevice(dev->d_rectify[s]);
-  freeDevice(dev->d_temporalTrust);
-  dev->rectifyPixels = 0; dev->temporalTrustValid = false;
-  dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
-  dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
-}
-
-// The merge of twk_temporal_accumulate's own-buffer form and of twk_temporal_accumulate_assembled, after their refusals: the frame
-// (colour in the output format, moments, geometry; layers: the cascade layers to merge while twk_temporal_enable_cascade is on,
-// nullptr = the handle's own) of width x height pixels against the history the handle kept, which it then replaces. k: maxHistory
-// and tol2 are set. rectify: nullptr = the plain merge; else the rectified one (temporal_rectify_device.h), which also writes the
-// handle's trust plane and, while twk_temporal_enable_cascade is on, discounts the layers' history by it.
-int twk::temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const void* colour, const float4* moments, const float4* geometry,
-                     const float4* layers, int width, int height)
-{
-  const size_t n = (size_t) width * height;
-  if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
-  {
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    dropTemporal(dev);
-    for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
-    dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
-  }
-  const float4 *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
-  if (dev->temporalHasHistory)
-  {
-    float4* const* h = dev->d_temporal[dev->temporalKept];
-    hColour = h[0]; hMoments = h[1]; hGeometry = h[2];
-  }
-  const int keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
-  k.width = width; k.height = height;
-  if (dev->temporalHasHistory)
-  {
-    k.hasHistory = 1;
-    if (!temporalCamera(dev->temporalCamera.P, k))
-      return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": the history's camera is degenerate: U, V, W are linearly dependent or not finite");
-  }
-  // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
-  int rc;
-  if (rectify)
-  {
-    // the trust first: the layers' merge reads it
-    if ((rc = ensureRectifyScratch(dev, n))) return rc;
-    if (!dev->d_temporalTrust) HIP_TRY(hipMalloc(&dev->d_temporalTrust, n * sizeof(float)));
-    launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->d_temporalColour,
-                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream);
-    HIP_TRY(hipGetLastError());
-    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust))) return rc;
-    dev->temporalTrustValid = true;
-  }
-  else
-  {
-    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
-    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_temporalColour, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
-    HIP_TRY(hipGetLastError());
-    dev->temporalTrustValid = false; // the trust plane, if any, is an earlier frame's
-  }
-  HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, n * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
-  dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
-  return TWK_SUCCESS;
-}
-
-// The own-buffer form of twk_temporal_accumulate and of twk_temporal_accumulate_rectified after the checks of their arguments: the
-// refusals of the handle's state, then the merge. k: maxHistory and tol2 are set.
-int twk::temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify)
-{
-  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
-  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
-  if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
-  const int width = dev->launchWidth, height = dev->state.resolution[1];
-  const size_t n = (size_t) width * height;
-  if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
-  if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
-  if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
-  const void* colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-  if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
-  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
-  return temporalOwn(dev, name, k, rectify, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
-}
-
-// twk_temporal_accumulate_assembled and twk_temporal_accumulate_assembled_rectified after the checks of their parameters
-int twk::temporalAssembledFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify)
-{
-  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
-  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
-  if (!(dev->state.distribution && 1 < dev->count))
-    return refuse(TWK_ERROR_INVALID_STATE, "the handle is not tiled (distribution 1, more than one device): its own buffers are the picture, twk_temporal_accumulate merges them");
-  if (!dev->momentsEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no luminance moments: render with twk_enable_moments(1)");
-  if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no geometry AOV: twk_enable_geometry(1) and twk_render_geometry_tile");
-  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
-  const int needed[3] = {TWK_PLANE_OUTPUT, TWK_PLANE_MOMENTS, TWK_PLANE_CASCADE};
-  static const char* const neededNames[3] = {"TWK_PLANE_OUTPUT", "TWK_PLANE_MOMENTS", "TWK_PLANE_CASCADE"};
-  for (int j = 0; j < (dev->temporalCascade ? 3 : 2); ++j)
-    if (!dev->assembledValid[needed[j]] || !dev->d_assembled[needed[j]])
-      return refuse(TWK_ERROR_INVALID_STATE, std::string(neededNames[j]) + " has not been assembled on this handle: twk_assemble_devices_with_geometry first");
-  if (!dev->d_assembledGeometry) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV has not been assembled on this handle: twk_assemble_devices_with_geometry first");
-  if (!dev->assembledGeometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the assembled geometry AOV is stale, older than the camera, the state or the scene: twk_render_geometry_tile and twk_assemble_devices_with_geometry first");
-  return temporalOwn(dev, name, k, rectify, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS]), static_cast<const float4*>(dev->d_assembledGeometry),
-                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE]) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
-}
 
 // =============================================================================================
 extern "C" {
@@ -191,14 +84,6 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_denoiser_defaults")
-
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
-{
-  if (!a || !b) return false;
-  const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-  return x < y + bBytes && y < x + aBytes;
-}
-static bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
 
 // Every check of the parameters' values, for the device form and the host form alike, and the constants the passes take (k but
 // for its width and height). `name` is the entry point, for the error texts; dv NULL: not the variance-guided mode; dg NULL: no
@@ -503,139 +388,6 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_denoised_device_pointer")
-
-int twk_temporal_defaults(TwkTemporal* tp)
-try
-{
-  if (!tp) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_temporal_defaults: NULL argument");
-  tp->maxHistory = TWK_TEMPORAL_MAX_HISTORY; tp->positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
-  return TWK_SUCCESS;
-}
-TWK_CATCH("twk_temporal_defaults")
-
-int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history, int width, int height,
-                            void* colourOut, void* historyOut, void* momentsOut)
-try
-{
-  const char* name = "twk_temporal_accumulate";
-  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
-  int rc = activate(dev, name); if (rc) return rc;
-  TwkTemporal defaults; defaults.maxHistory = TWK_TEMPORAL_MAX_HISTORY; defaults.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
-  if (!tp) tp = &defaults;
-  if (tp->maxHistory < 1) return refuse(TWK_ERROR_INVALID_VALUE, "maxHistory must be >= 1");
-  if (!(tp->positionTolerance >= 0.0f) || !finite1(tp->positionTolerance)) return refuse(TWK_ERROR_INVALID_VALUE, "positionTolerance must be >= 0 and finite");
-  TemporalConstants k;
-  memset(&k, 0, sizeof(k));
-  k.maxHistory = (float) tp->maxHistory; k.tol2 = tp->positionTolerance * tp->positionTolerance;
-
-  const bool own = (current == nullptr);
-  const void* colour; const float4 *moments, *geometry, *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
-  const TwkCameraDefinition* hCamera = nullptr;
-  if (own)
-  {
-    if (history || colourOut || historyOut || momentsOut || width || height) return refuse(TWK_ERROR_INVALID_VALUE, "a history, outputs or a size without a current frame (pass both frames, or neither for the handle's own buffers)");
-    return temporalOwnFrame(dev, name, k, nullptr);
-  }
-  else
-  {
-    if (width < 1 || height < 1 || (size_t) width * (size_t) height >= ((size_t) 1 << 31)) return refuse(TWK_ERROR_INVALID_VALUE, "width and height must be >= 1");
-    if (!current->colour || !current->moments || !current->geometry) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer in the current frame");
-    if (history && (!history->colour || !history->moments || !history->geometry)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL buffer in the history frame");
-    colour = current->colour; moments = static_cast<const float4*>(current->moments); geometry = static_cast<const float4*>(current->geometry);
-    if (history)
-    {
-      hColour = static_cast<const float4*>(history->colour); hMoments = static_cast<const float4*>(history->moments); hGeometry = static_cast<const float4*>(history->geometry);
-      hCamera = &history->camera;
-    }
-    const size_t n = (size_t) width * height, wide = n * sizeof(float4), narrowBytes = n * pixelBytes(dev);
-    const void* outs[3] = {colourOut, historyOut, momentsOut}; const size_t outBytes[3] = {narrowBytes, wide, wide};
-    const void* ins[6] = {colour, moments, geometry, hColour, hMoments, hGeometry}; const size_t inBytes[6] = {narrowBytes, wide, wide, wide, wide, wide};
-    for (int o = 0; o < 3; ++o)
-    {
-      for (int i = 0; i < 6; ++i) if (overlaps(outs[o], outBytes[o], ins[i], inBytes[i])) return refuse(TWK_ERROR_INVALID_VALUE, "an output overlaps an input (the kernel gathers the history at other pixels)");
-      for (int j = o + 1; j < 3; ++j) if (overlaps(outs[o], outBytes[o], outs[j], outBytes[j])) return refuse(TWK_ERROR_INVALID_VALUE, "two outputs overlap");
-    }
-  }
-  k.width = width; k.height = height;
-  if (hCamera)
-  {
-    k.hasHistory = 1;
-    if (!temporalCamera(hCamera->P, k)) return refuse(TWK_ERROR_INVALID_VALUE, "the history's camera is degenerate: U, V, W are linearly dependent or not finite");
-  }
-  launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
-  HIP_TRY(hipGetLastError());
-  return TWK_SUCCESS;
-}
-TWK_CATCH("twk_temporal_accumulate")
-
-int twk_temporal_accumulate_assembled(TwkDevice primary, const TwkTemporal* tp)
-try
-{
-  const char* name = "twk_temporal_accumulate_assembled";
-  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
-  TwkDevice dev = primary;
-  int rc = activate(dev, name); if (rc) return rc;
-  TwkTemporal defaults; defaults.maxHistory = TWK_TEMPORAL_MAX_HISTORY; defaults.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
-  if (!tp) tp = &defaults;
-  if (tp->maxHistory < 1) return refuse(TWK_ERROR_INVALID_VALUE, "maxHistory must be >= 1");
-  if (!(tp->positionTolerance >= 0.0f) || !finite1(tp->positionTolerance)) return refuse(TWK_ERROR_INVALID_VALUE, "positionTolerance must be >= 0 and finite");
-  TemporalConstants k;
-  memset(&k, 0, sizeof(k));
-  k.maxHistory = (float) tp->maxHistory; k.tol2 = tp->positionTolerance * tp->positionTolerance;
-  return temporalAssembledFrame(dev, name, k, nullptr);
-}
-TWK_CATCH("twk_temporal_accumulate_assembled")
-
-int twk_temporal_reset(TwkDevice dev)
-try
-{
-  int rc = activate(dev, "twk_temporal_reset"); if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  dropTemporal(dev);
-  return TWK_SUCCESS;
-}
-TWK_CATCH("twk_temporal_reset")
-
-int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colourBytes, void** moments, size_t* momentsBytes)
-try
-{
-  int rc = activate(dev, "twk_get_temporal_device_pointers"); if (rc) return rc;
-  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_temporal_device_pointers: no twk_temporal_accumulate on the handle's own buffers since the last reset");
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (colour) *colour = dev->d_temporalColour;
-  if (colourBytes) *colourBytes = n * pixelBytes(dev->temporalFormat);
-  if (moments) *moments = dev->d_temporal[dev->temporalKept][1];
-  if (momentsBytes) *momentsBytes = n * sizeof(float4);
-  return TWK_SUCCESS;
-}
-TWK_CATCH("twk_get_temporal_device_pointers")
-
-int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats)
-try
-{
-  int rc = activate(dev, "twk_read_temporal"); if (rc) return rc;
-  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal: NULL buffer");
-  if (!dev->temporalValid || dev->temporalFormat != dev->outputFormat) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal: no twk_temporal_accumulate on the handle's own buffers since the last reset");
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal: buffer must hold width*height*4 floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  return readPixels(dev, dev->d_temporalColour, rgbaHost, n, false);
-}
-TWK_CATCH("twk_read_temporal")
-
-int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats)
-try
-{
-  int rc = activate(dev, "twk_read_temporal_moments"); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_moments: NULL buffer");
-  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal_moments: no twk_temporal_accumulate on the handle's own buffers since the last reset");
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_moments: buffer must hold width*height*4 floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_temporal[dev->temporalKept][1], n * sizeof(float4), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
-}
-TWK_CATCH("twk_read_temporal_moments")
 
 // ---- noise estimate (noise_device.h) -----------------------------------------------------------
 int twk_noise_defaults(TwkNoise* np)

@@ -1,0 +1,417 @@
+// The picture-shaped temporal merges behind the C ABI: the plain merge (temporal_device.h: the definition) and the rectified one
+// (temporal_rectify_device.h). Their parameters and refusals, the explicit form, the own-buffer and the assembled form (temporalOwn
+// serves both merges), the readers and the rectified merge's host-only form. The cascade's layers through the same reprojection are
+// device_temporal_cascade.hip's, which takes its TwkTemporal checks and its history camera from here.
+#include "device_handle.h"
+
+#include <cstring>
+#include <vector>
+
+// Frees the streams of twk_temporal_accumulate's own-buffer form: the next call has no history
+void twk::dropTemporal(TwkDevice dev)
+{
+  for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
+  freeDevice(dev->d_temporalColour);
+  for (int s = 0; s < 2; ++s) freeDevice(dev->d_rectify[s]);
+  freeDevice(dev->d_temporalTrust);
+  dev->rectifyPixels = 0; dev->temporalTrustValid = false;
+  dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
+  dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
+}
+
+// The two scratch streams of the rectified merge, at least `pixels` float4 each
+static int ensureRectifyScratch(TwkDevice dev, size_t pixels)
+{
+  if (dev->d_rectify[0] && dev->d_rectify[1] && dev->rectifyPixels >= pixels) return TWK_SUCCESS;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  for (int s = 0; s < 2; ++s) freeDevice(dev->d_rectify[s]);
+  dev->rectifyPixels = 0;
+  for (int s = 0; s < 2; ++s) HIP_TRY(hipMalloc(&dev->d_rectify[s], pixels * sizeof(float4)));
+  dev->rectifyPixels = pixels;
+  return TWK_SUCCESS;
+}
+
+static TwkTemporal temporalDefaults()
+{
+  TwkTemporal tp; tp.maxHistory = TWK_TEMPORAL_MAX_HISTORY; tp.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
+  return tp;
+}
+
+static TwkTemporalRectify rectifyDefaults()
+{
+  TwkTemporalRectify rp; rp.radius = TWK_TEMPORAL_RECTIFY_RADIUS; rp.minTaps = TWK_TEMPORAL_RECTIFY_MIN_TAPS; rp.gamma = TWK_TEMPORAL_RECTIFY_GAMMA;
+  return rp;
+}
+
+// The refusals of TwkTemporal's values (tp NULL: the defaults) and the constants they give: k zeroed but for maxHistory and tol2
+int twk::temporalParameters(const char* name, const TwkTemporal* tp, TemporalConstants& k)
+{
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  const TwkTemporal temporal = tp ? *tp : temporalDefaults();
+  if (temporal.maxHistory < 1) return refuse("maxHistory must be >= 1");
+  if (!(temporal.positionTolerance >= 0.0f) || !finite1(temporal.positionTolerance)) return refuse("positionTolerance must be >= 0 and finite");
+  memset(&k, 0, sizeof(k));
+  k.maxHistory = (float) temporal.maxHistory; k.tol2 = temporal.positionTolerance * temporal.positionTolerance;
+  return TWK_SUCCESS;
+}
+
+// There is a history, rendered from `camera`: its part of the constants, or the refusal of a degenerate one
+int twk::temporalHistoryCamera(const char* name, const TwkCameraDefinition& camera, TemporalConstants& k)
+{
+  k.hasHistory = 1;
+  if (!temporalCamera(camera.P, k))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": the history's camera is degenerate: U, V, W are linearly dependent or not finite");
+  return TWK_SUCCESS;
+}
+
+// The refusals of the parameters every form of the rectified merge shares (tp, rp NULL: the defaults), and the constants they give;
+// width, height unset
+static int rectifyParameters(const char* name, const TwkTemporal* tp, const TwkTemporalRectify* rp, TemporalConstants& k, RectifyConstants& r)
+{
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  const int rc = temporalParameters(name, tp, k); if (rc) return rc;
+  const TwkTemporalRectify rectify = rp ? *rp : rectifyDefaults();
+  static_assert(TWK_TEMPORAL_RECTIFY_MAX_RADIUS == TWK_RECTIFY_MAX_RADIUS, "the header's largest radius is the kernel's");
+  if (rectify.radius < 1 || rectify.radius > TWK_RECTIFY_MAX_RADIUS) return refuse("radius must be in 1..4");
+  if (rectify.minTaps < 2) return refuse("minTaps must be >= 2 (a variance needs two taps)");
+  if (!(rectify.gamma >= 0.0f) || !finite1(rectify.gamma)) return refuse("gamma must be >= 0 and finite");
+  r.radius = rectify.radius; r.minTaps = rectify.minTaps; r.gamma2 = rectify.gamma * rectify.gamma;
+  return TWK_SUCCESS;
+}
+
+// The merge of the own-buffer form and of the assembled form, after their refusals: the frame (colour in the output format,
+// moments, geometry; layers: the cascade layers to merge while twk_temporal_enable_cascade is on, nullptr = the handle's own) of
+// width x height pixels against the history the handle kept, which it then replaces. k: maxHistory and tol2 are set. rectify:
+// nullptr = the plain merge; else the rectified one (temporal_rectify_device.h), which also writes the handle's trust plane and,
+// while twk_temporal_enable_cascade is on, discounts the layers' history by it.
+static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const void* colour, const float4* moments, const float4* geometry,
+                       const float4* layers, int width, int height)
+{
+  const size_t n = (size_t) width * height;
+  if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
+  {
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    dropTemporal(dev);
+    for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
+    HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
+    dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
+  }
+  const float4 *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
+  if (dev->temporalHasHistory)
+  {
+    float4* const* h = dev->d_temporal[dev->temporalKept];
+    hColour = h[0]; hMoments = h[1]; hGeometry = h[2];
+  }
+  const int keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
+  k.width = width; k.height = height;
+  int rc;
+  if (dev->temporalHasHistory && (rc = temporalHistoryCamera(name, dev->temporalCamera, k))) return rc;
+  // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
+  if (rectify)
+  {
+    // the trust first: the layers' merge reads it
+    if ((rc = ensureRectifyScratch(dev, n))) return rc;
+    if (!dev->d_temporalTrust) HIP_TRY(hipMalloc(&dev->d_temporalTrust, n * sizeof(float)));
+    launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->d_temporalColour,
+                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream);
+    HIP_TRY(hipGetLastError());
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust))) return rc;
+    dev->temporalTrustValid = true;
+  }
+  else
+  {
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
+    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_temporalColour, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
+    HIP_TRY(hipGetLastError());
+    dev->temporalTrustValid = false; // the trust plane, if any, is an earlier frame's
+  }
+  HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, n * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
+  dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
+  return TWK_SUCCESS;
+}
+
+// The own-buffer form of twk_temporal_accumulate and of twk_temporal_accumulate_rectified after the checks of their arguments: the
+// refusals of the handle's state, then the merge. k: maxHistory and tol2 are set.
+static int temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify)
+{
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, (std::string(name) + ": " + text).c_str()); };
+  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+  if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
+  const int width = dev->launchWidth, height = dev->state.resolution[1];
+  const size_t n = (size_t) width * height;
+  if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+  if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+  if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
+  const void* colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+  if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
+  return temporalOwn(dev, name, k, rectify, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
+}
+
+// twk_temporal_accumulate_assembled and twk_temporal_accumulate_assembled_rectified after the checks of their parameters
+static int temporalAssembledFrame(TwkDevice dev, const char* name, const TemporalConstants& k, const RectifyConstants* rectify)
+{
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
+  if (!(dev->state.distribution && 1 < dev->count))
+    return refuse(TWK_ERROR_INVALID_STATE, "the handle is not tiled (distribution 1, more than one device): its own buffers are the picture, twk_temporal_accumulate merges them");
+  if (!dev->momentsEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no luminance moments: render with twk_enable_moments(1)");
+  if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no geometry AOV: twk_enable_geometry(1) and twk_render_geometry_tile");
+  if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
+  const int needed[3] = {TWK_PLANE_OUTPUT, TWK_PLANE_MOMENTS, TWK_PLANE_CASCADE};
+  static const char* const neededNames[3] = {"TWK_PLANE_OUTPUT", "TWK_PLANE_MOMENTS", "TWK_PLANE_CASCADE"};
+  for (int j = 0; j < (dev->temporalCascade ? 3 : 2); ++j)
+    if (!dev->assembledValid[needed[j]] || !dev->d_assembled[needed[j]])
+      return refuse(TWK_ERROR_INVALID_STATE, std::string(neededNames[j]) + " has not been assembled on this handle: twk_assemble_devices_with_geometry first");
+  if (!dev->d_assembledGeometry) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV has not been assembled on this handle: twk_assemble_devices_with_geometry first");
+  if (!dev->assembledGeometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the assembled geometry AOV is stale, older than the camera, the state or the scene: twk_render_geometry_tile and twk_assemble_devices_with_geometry first");
+  return temporalOwn(dev, name, k, rectify, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS]), static_cast<const float4*>(dev->d_assembledGeometry),
+                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE]) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
+}
+
+// twk_temporal_accumulate (rectify nullptr, no trustOut) and twk_temporal_accumulate_rectified after the checks of their parameters,
+// on an active handle: without a current frame the own-buffer form, else the explicit form's refusals and its launch
+static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                         int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut)
+{
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  if (!current)
+  {
+    if (history || colourOut || historyOut || momentsOut || trustOut || width || height)
+      return refuse("a history, outputs or a size without a current frame (pass both frames, or neither for the handle's own buffers)");
+    return temporalOwnFrame(dev, name, k, rectify);
+  }
+  if (width < 1 || height < 1 || (size_t) width * (size_t) height >= ((size_t) 1 << 31)) return refuse("width and height must be >= 1");
+  if (!current->colour || !current->moments || !current->geometry) return refuse("NULL buffer in the current frame");
+  if (history && (!history->colour || !history->moments || !history->geometry)) return refuse("NULL buffer in the history frame");
+  const void* colour = current->colour;
+  const float4 *moments = static_cast<const float4*>(current->moments), *geometry = static_cast<const float4*>(current->geometry);
+  const float4 *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
+  if (history) { hColour = static_cast<const float4*>(history->colour); hMoments = static_cast<const float4*>(history->moments); hGeometry = static_cast<const float4*>(history->geometry); }
+  const size_t n = (size_t) width * height, wide = n * sizeof(float4), narrowBytes = n * pixelBytes(dev);
+  const void* outs[4] = {colourOut, historyOut, momentsOut, trustOut}; const size_t outBytes[4] = {narrowBytes, wide, wide, n * sizeof(float)};
+  const void* ins[6] = {colour, moments, geometry, hColour, hMoments, hGeometry}; const size_t inBytes[6] = {narrowBytes, wide, wide, wide, wide, wide};
+  for (int o = 0; o < 4; ++o)
+  {
+    for (int i = 0; i < 6; ++i) if (overlaps(outs[o], outBytes[o], ins[i], inBytes[i])) return refuse("an output overlaps an input (the kernel gathers the history at other pixels)");
+    for (int j = o + 1; j < 4; ++j) if (overlaps(outs[o], outBytes[o], outs[j], outBytes[j])) return refuse("two outputs overlap");
+  }
+  k.width = width; k.height = height;
+  int rc;
+  if (history && (rc = temporalHistoryCamera(name, history->camera, k))) return rc;
+  if (rectify)
+  {
+    if ((rc = ensureRectifyScratch(dev, n))) return rc;
+    launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], colourOut, static_cast<float4*>(historyOut),
+                          static_cast<float4*>(momentsOut), static_cast<float*>(trustOut), k, *rectify, dev->stream);
+  }
+  else
+    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
+  HIP_TRY(hipGetLastError());
+  return TWK_SUCCESS;
+}
+
+// The readers' refusal while the handle holds no own-buffer result
+static const char* const noTemporal = ": no twk_temporal_accumulate on the handle's own buffers since the last reset";
+static const char* const noTrust = ": the last merge on the handle's own buffers was no twk_temporal_accumulate_rectified, or its history has been dropped";
+
+extern "C" {
+
+int twk_temporal_defaults(TwkTemporal* tp)
+try
+{
+  if (!tp) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_temporal_defaults: NULL argument");
+  *tp = temporalDefaults();
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_defaults")
+
+int twk_temporal_rectify_defaults(TwkTemporalRectify* rp)
+try
+{
+  if (!rp) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_temporal_rectify_defaults: NULL argument");
+  *rp = rectifyDefaults();
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_rectify_defaults")
+
+int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history, int width, int height,
+                            void* colourOut, void* historyOut, void* momentsOut)
+try
+{
+  const char* name = "twk_temporal_accumulate";
+  int rc = activate(dev, name); if (rc) return rc;
+  TemporalConstants k;
+  if ((rc = temporalParameters(name, tp, k))) return rc;
+  return temporalFrame(dev, name, k, nullptr, current, history, width, height, colourOut, historyOut, momentsOut, nullptr);
+}
+TWK_CATCH("twk_temporal_accumulate")
+
+int twk_temporal_accumulate_rectified(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalRectify* rp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                                      int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut)
+try
+{
+  const char* name = "twk_temporal_accumulate_rectified";
+  int rc = activate(dev, name); if (rc) return rc;
+  TemporalConstants k;
+  RectifyConstants r;
+  if ((rc = rectifyParameters(name, tp, rp, k, r))) return rc;
+  return temporalFrame(dev, name, k, &r, current, history, width, height, colourOut, historyOut, momentsOut, trustOut);
+}
+TWK_CATCH("twk_temporal_accumulate_rectified")
+
+int twk_temporal_accumulate_assembled(TwkDevice primary, const TwkTemporal* tp)
+try
+{
+  const char* name = "twk_temporal_accumulate_assembled";
+  int rc = activate(primary, name); if (rc) return rc;
+  TemporalConstants k;
+  if ((rc = temporalParameters(name, tp, k))) return rc;
+  return temporalAssembledFrame(primary, name, k, nullptr);
+}
+TWK_CATCH("twk_temporal_accumulate_assembled")
+
+int twk_temporal_accumulate_assembled_rectified(TwkDevice primary, const TwkTemporal* tp, const TwkTemporalRectify* rp)
+try
+{
+  const char* name = "twk_temporal_accumulate_assembled_rectified";
+  int rc = activate(primary, name); if (rc) return rc;
+  TemporalConstants k;
+  RectifyConstants r;
+  if ((rc = rectifyParameters(name, tp, rp, k, r))) return rc;
+  return temporalAssembledFrame(primary, name, k, &r);
+}
+TWK_CATCH("twk_temporal_accumulate_assembled_rectified")
+
+int twk_temporal_reset(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_temporal_reset"); if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  dropTemporal(dev);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_reset")
+
+int twk_get_temporal_device_pointers(TwkDevice dev, void** colour, size_t* colourBytes, void** moments, size_t* momentsBytes)
+try
+{
+  const std::string name = "twk_get_temporal_device_pointers";
+  int rc = activate(dev, name.c_str()); if (rc) return rc;
+  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTemporal);
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (colour) *colour = dev->d_temporalColour;
+  if (colourBytes) *colourBytes = n * pixelBytes(dev->temporalFormat);
+  if (moments) *moments = dev->d_temporal[dev->temporalKept][1];
+  if (momentsBytes) *momentsBytes = n * sizeof(float4);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_temporal_device_pointers")
+
+int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats)
+try
+{
+  const std::string name = "twk_read_temporal";
+  int rc = activate(dev, name.c_str()); if (rc) return rc;
+  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL buffer");
+  if (!dev->temporalValid || dev->temporalFormat != dev->outputFormat) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTemporal);
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": buffer must hold width*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return readPixels(dev, dev->d_temporalColour, rgbaHost, n, false);
+}
+TWK_CATCH("twk_read_temporal")
+
+int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  const std::string name = "twk_read_temporal_moments";
+  int rc = activate(dev, name.c_str()); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL buffer");
+  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTemporal);
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": buffer must hold width*height*4 floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_temporal[dev->temporalKept][1], n * sizeof(float4), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_temporal_moments")
+
+int twk_get_temporal_trust_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
+try
+{
+  const std::string name = "twk_get_temporal_trust_device_pointer";
+  int rc = activate(dev, name.c_str()); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL argument");
+  if (!dev->temporalValid || !dev->temporalTrustValid || !dev->d_temporalTrust) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTrust);
+  *dptr = dev->d_temporalTrust;
+  if (bytes) *bytes = (size_t) dev->temporalWidth * dev->temporalHeight * sizeof(float);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_temporal_trust_device_pointer")
+
+int twk_read_temporal_trust(TwkDevice dev, float* host, size_t numFloats)
+try
+{
+  const std::string name = "twk_read_temporal_trust";
+  int rc = activate(dev, name.c_str()); if (rc) return rc;
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL buffer");
+  if (!dev->temporalValid || !dev->temporalTrustValid || !dev->d_temporalTrust) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTrust);
+  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
+  if (numFloats != n) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": buffer must hold width*height floats");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  HIP_TRY(hipMemcpy(host, dev->d_temporalTrust, n * sizeof(float), hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_temporal_trust")
+
+int twk_temporal_rectify_host(const TwkTemporal* tp, const TwkTemporalRectify* rp, const float* colour, const float* moments, const float* geometry,
+                              const float* historyColour, const float* historyMoments, const float* historyGeometry, const TwkCameraDefinition* historyCamera,
+                              int width, int height, float* colourOut, float* momentsOut, float* trustOut)
+try
+{
+  const char* name = "twk_temporal_rectify_host";
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  if (!colour || !moments || !geometry) return refuse("NULL buffer in the current frame");
+  const bool history = historyColour || historyMoments || historyGeometry;
+  if (history && (!historyColour || !historyMoments || !historyGeometry || !historyCamera)) return refuse("a history without its colour, moments, geometry or camera");
+  TemporalConstants k;
+  RectifyConstants r;
+  int rc = rectifyParameters(name, tp, rp, k, r); if (rc) return rc;
+  if (width < 1 || height < 1 || (size_t) width * (size_t) height > ((size_t) 1 << 28)) return refuse("width and height must be >= 1, width*height at most 2^28");
+  k.width = width; k.height = height;
+  if (history && (rc = temporalHistoryCamera(name, *historyCamera, k))) return rc;
+  const size_t n = (size_t) width * height;
+  // (a host array of floats need not have a float4's alignment)
+  std::vector<float4> cur(n), mc(n), g(n), hc(history ? n : 0), hm(history ? n : 0), hg(history ? n : 0), A(n), B(n);
+  memcpy(cur.data(), colour, n * sizeof(float4)); memcpy(mc.data(), moments, n * sizeof(float4)); memcpy(g.data(), geometry, n * sizeof(float4));
+  if (history) { memcpy(hc.data(), historyColour, n * sizeof(float4)); memcpy(hm.data(), historyMoments, n * sizeof(float4)); memcpy(hg.data(), historyGeometry, n * sizeof(float4)); }
+  // launch 1
+  for (size_t p = 0; p < n; ++p) rectifyReproject(k, cur[p], mc[p], g[p], hc.data(), hm.data(), hg.data(), A[p], B[p]);
+  // launch 2: the staged words of the whole picture with a halo of `radius` zeros around it, as one tile
+  const int R = r.radius, pitch = width + 2 * R;
+  std::vector<float> d((size_t) pitch * (height + 2 * R), 0.0f);
+  std::vector<unsigned int> key(d.size(), 0u);
+  for (int y = 0; y < height; ++y)
+    for (int x = 0; x < width; ++x)
+    {
+      const size_t p = (size_t) y * width + x, s = (size_t) (y + R) * pitch + (x + R);
+      rectifyStage(mc[p], B[p], d[s], key[s]);
+    }
+  for (int y = 0; y < height; ++y)
+    for (int x = 0; x < width; ++x)
+    {
+      const size_t p = (size_t) y * width + x;
+      const float t = rectifyTrust<0>(r, d.data(), key.data(), pitch, (y + R) * pitch + (x + R), B[p].z, mc[p].z);
+      float4 c = cur[p], m = mc[p];
+      float trust;
+      if (!rectifyMerge(t, cur[p], mc[p], A[p], B[p], c, m, trust)) { c = cur[p]; m = mc[p]; }
+      if (colourOut) memcpy(colourOut + 4 * p, &c, sizeof(float4));
+      if (momentsOut) memcpy(momentsOut + 4 * p, &m, sizeof(float4));
+      if (trustOut) trustOut[p] = trust;
+    }
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_rectify_host")
+
+} // extern "C"

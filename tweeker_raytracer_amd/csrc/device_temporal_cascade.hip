@@ -1,6 +1,7 @@
 // The cascade's layers through the temporal merge behind the C ABI (temporal_cascade_device.h: the definition): the explicit form,
 // the switch of the own-buffer form with its double-buffered merged layers and their readers, and the host-only form. The own-buffer
-// merge itself is issued by twk_temporal_accumulate (device_post.hip) through temporalCascadeOwn(), before it swaps its history.
+// merge itself is issued by twk_temporal_accumulate (device_temporal.hip) through temporalCascadeOwn(), before it swaps its history.
+// The checks of TwkTemporal and the history's camera are device_temporal.hip's temporalParameters and temporalHistoryCamera.
 #include "device_handle.h"
 
 #include <cstring>
@@ -58,36 +59,19 @@ int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const flo
   return TWK_SUCCESS;
 }
 
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
-{
-  if (!a || !b) return false;
-  const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-  return x < y + bBytes && y < x + aBytes;
-}
-
 // The refusals the explicit and the host-only form share, and the constants both take. history: a history was passed.
 static int temporalCascadeParameters(const char* name, const TwkTemporal* tp, const TwkCascade* cp, bool history, const TwkCameraDefinition* historyCamera, int width, int height,
                                      TemporalConstants& k, CascadeConstants& c)
 {
   const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
-  TwkTemporal temporal; temporal.maxHistory = TWK_TEMPORAL_MAX_HISTORY; temporal.positionTolerance = TWK_TEMPORAL_POSITION_TOLERANCE;
-  if (tp) temporal = *tp;
   TwkCascade cascade; cascade.layers = TWK_CASCADE_LAYERS; cascade.start = TWK_CASCADE_START; cascade.base = TWK_CASCADE_BASE;
   if (cp) cascade = *cp;
   if (const char* why = cascadeConstants(cascade, c)) return refuse(why);
-  if (temporal.maxHistory < 1) return refuse("maxHistory must be >= 1");
-  if (!(temporal.positionTolerance >= 0.0f) || !finite1(temporal.positionTolerance)) return refuse("positionTolerance must be >= 0 and finite");
+  const int rc = temporalParameters(name, tp, k); if (rc) return rc;
   if (width < 1 || height < 1) return refuse("width and height must be >= 1");
   if ((size_t) width * (size_t) height > ((size_t) 1 << 28)) return refuse("width*height must be at most 2^28");
-  memset(&k, 0, sizeof(k));
   k.width = width; k.height = height;
-  k.maxHistory = (float) temporal.maxHistory; k.tol2 = temporal.positionTolerance * temporal.positionTolerance;
-  if (history)
-  {
-    k.hasHistory = 1;
-    if (!temporalCamera(historyCamera->P, k)) return refuse("the history's camera is degenerate: U, V, W are linearly dependent or not finite");
-  }
-  return TWK_SUCCESS;
+  return history ? temporalHistoryCamera(name, *historyCamera, k) : TWK_SUCCESS;
 }
 
 // The explicit form, plain (trusted false) and trusted (trust: width x height floats)

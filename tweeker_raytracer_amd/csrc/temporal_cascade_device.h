@@ -5,8 +5,9 @@
 // unchanged — with the counts of the history behind its weights instead of one frame's 1 - 4 samples. The definition below is
 // complete and is compiled once for the kernel (temporal_cascade_kernels.hip) and once for the host (twk_temporal_cascade_host);
 // tests/temporal_cascade_restate.py restates it statement for statement in numpy float32. All arithmetic is f32, every operation
-// rounded once, in the order written (-ffp-contract=off, csrc/Makefile). The projection and the test of a tap's geometry are
-// temporal_device.h's own functions, not restated.
+// rounded once, in the order written (-ffp-contract=off, csrc/Makefile). The projection, the footprint with its weights and the
+// test of a tap's geometry are temporal_device.h's own functions (temporalProject, temporalFootprint, temporalTapWeight,
+// temporalTapGeometry), not restated; the test of a tap's counts, the w > 0 rule and the per-layer sums are this header's.
 //
 // Streams, per pixel p of a width x height grid: the current layers Lc[j] and the history layers H[j], [K][width x height] float4,
 // layer-major as cascade_device.h stores them; the current geometry AOV g and the history's hg; the history camera (temporalCamera).
@@ -75,19 +76,17 @@ TWK_CASCADE_UNROLL
     float fx = 0.0f, fy = 0.0f, vv = 0.0f;
     if (asUint(g.w) != 0u && finite3(g) && cascadeFinite(nc) && !(nc < 1.0f) && temporalProject(k, g, fx, fy, vv))
     {
-      const float fx0 = floorf(fx), fy0 = floorf(fy);
-      const float tx = fx - fx0, ty = fy - fy0;
-      const int x0 = (int) fx0, y0 = (int) fy0; // in [-1, width - 1] x [-1, height - 1]
-      q00 = (long long) y0 * k.width + x0;
+      const TemporalFootprint f = temporalFootprint(fx, fy);
+      q00 = (long long) f.y0 * k.width + f.x0;
 TWK_CASCADE_UNROLL
       for (int dy = 0; dy <= 1; ++dy)
       {
-        const int qy = y0 + dy;
+        const int qy = f.y0 + dy;
         if (qy < 0 || qy >= k.height) continue;
 TWK_CASCADE_UNROLL
         for (int dx = 0; dx <= 1; ++dx)
         {
-          const int qx = x0 + dx;
+          const int qx = f.x0 + dx;
           if (qx < 0 || qx >= k.width) continue;
           const int t = 2 * dy + dx;
           const size_t qi = (size_t) qy * k.width + qx;
@@ -96,7 +95,7 @@ TWK_CASCADE_UNROLL
           if (!cascadeFinite(h0.w) || !(h0.w >= 1.0f)) continue;
           const float4 h1 = H[top + qi];
           if (!cascadeFinite(h1.w)) continue;
-          const float wt = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+          const float wt = temporalTapWeight(f, dx, dy);
           if (!(wt > 0.0f)) continue;
           w[t] = wt; hFirst[t] = h0; hLast[t] = h1;
           sn = sn + wt * h0.w; srej = srej + wt * h1.w; ws = ws + wt;

@@ -59,6 +59,10 @@
 //     d = mc.x - hmean;  mean = hmean + d * r;  M2 = (hM2 + mc.y) + (d * d) * (hn * r)
 //   colourOut[p] = narrow(colour.xyz, cur.w) (RGBA16F: round to nearest even, once);  historyOut[p] = (colour.xyz, cur.w) in f32;
 //   momentsOut[p] = (mean, M2, n, 0)
+// Each statement is written once below: temporalGather (from the candidate test to the last tap; its footprint x0, y0, tx, ty and the
+// weight w are temporalFootprint and temporalTapWeight, which the cascade's merge shares), temporalHistory (the quotients and the
+// cap), temporalBlend (the merge), and the store of the three outputs in temporal_store.h. The rectified merge
+// (temporal_rectify_device.h) calls the same functions; it is not a second copy.
 //
 // What this approximates, and what it is not. The history is measured in SAMPLES: the cap scales M2 with n, which leaves the
 // sample variance M2 / n of the history where it was and bounds its weight, so an old frame fades the way an exponential
@@ -138,6 +142,25 @@ TWK_HD bool temporalTapGeometry(const TemporalConstants& k, const float4& g, con
   return asUint(hg.w) == asUint(g.w) && distance2(hg, g) <= k.tol2 * vv;
 }
 
+// The four history pixels around the reprojected position (fx, fy), which temporalProject has bounded: the corner (x0, y0) in
+// [-1, width - 1] x [-1, height - 1] and the fractions; tap (dx, dy) is pixel (x0 + dx, y0 + dy)
+struct TemporalFootprint { int x0, y0; float tx, ty; };
+
+TWK_HD TemporalFootprint temporalFootprint(float fx, float fy)
+{
+  const float fx0 = floorf(fx), fy0 = floorf(fy);
+  TemporalFootprint f;
+  f.tx = fx - fx0; f.ty = fy - fy0;
+  f.x0 = (int) fx0; f.y0 = (int) fy0;
+  return f;
+}
+
+// The bilinear weight of tap (dx, dy)
+TWK_HD float temporalTapWeight(const TemporalFootprint& f, int dx, int dy)
+{
+  return (dx ? f.tx : 1.0f - f.tx) * (dy ? f.ty : 1.0f - f.ty);
+}
+
 struct TemporalSums { float x, y, z, mean, M2, n, ws; };
 
 // One counted tap: the history's colour hc and moments hm with bilinear weight w
@@ -149,22 +172,65 @@ TWK_HD void temporalTap(const float4& hc, const float4& hm, float w, TemporalSum
   s.ws = s.ws + w;
 }
 
-// The merge of the interpolated history (s.ws > 0) with the frame's cur, mc: the merged colour (alpha = cur.w) and moments
-TWK_HD void temporalMerge(const TemporalConstants& k, const TemporalSums& s, const float4& cur, const float4& mc, float4& colour, float4& moments)
+// The gather at pixel p, from the candidate test to the last tap: s.ws > 0 says there is history. The history's geometry is read
+// first; its colour and moments only at the taps that belong to the surface. (cur, mc and g by value: by reference the kernel's
+// load of g is split into xyz and w and temporalKernel grows by 30 instructions.)
+TWK_HD void temporalGather(const TemporalConstants& k, const float4 cur, const float4 mc, const float4 g, const float4* historyColour, const float4* historyMoments,
+                           const float4* historyGeometry, TemporalSums& s)
 {
-  const float hx = s.x / s.ws, hy = s.y / s.ws, hz = s.z / s.ws;
-  const float hmean = s.mean / s.ws;
-  float hM2 = s.M2 / s.ws, hn = s.n / s.ws;
-  if (hn > k.maxHistory) { hM2 = hM2 * (k.maxHistory / hn); hn = k.maxHistory; }
-  const float n = hn + mc.z;
+  s.x = 0.0f; s.y = 0.0f; s.z = 0.0f; s.mean = 0.0f; s.M2 = 0.0f; s.n = 0.0f; s.ws = 0.0f;
+  float fx = 0.0f, fy = 0.0f, vv = 0.0f;
+  if (!(temporalCandidate(k, cur, mc, g) && temporalProject(k, g, fx, fy, vv))) return;
+  const TemporalFootprint f = temporalFootprint(fx, fy);
+#pragma unroll
+  for (int dy = 0; dy <= 1; ++dy)
+  {
+    const int qy = f.y0 + dy;
+    if (qy < 0 || qy >= k.height) continue;
+#pragma unroll
+    for (int dx = 0; dx <= 1; ++dx)
+    {
+      const int qx = f.x0 + dx;
+      if (qx < 0 || qx >= k.width) continue;
+      const size_t q = (size_t) qy * k.width + qx;
+      if (!temporalTapGeometry(k, g, historyGeometry[q], vv)) continue;
+      temporalTap(historyColour[q], historyMoments[q], temporalTapWeight(f, dx, dy), s);
+    }
+  }
+}
+
+// The interpolated history of a pixel: colour, luminance mean and M2, and its count n in samples
+struct TemporalHistory { float x, y, z, mean, M2, n; };
+
+// The quotients by s.ws (> 0) and the cap of the count at maxHistory
+TWK_HD TemporalHistory temporalHistory(const TemporalConstants& k, const TemporalSums& s)
+{
+  TemporalHistory h;
+  h.x = s.x / s.ws; h.y = s.y / s.ws; h.z = s.z / s.ws;
+  h.mean = s.mean / s.ws;
+  h.M2 = s.M2 / s.ws; h.n = s.n / s.ws;
+  if (h.n > k.maxHistory) { h.M2 = h.M2 * (k.maxHistory / h.n); h.n = k.maxHistory; }
+  return h;
+}
+
+// The merge by count of a history h with the frame's cur, mc: the merged colour (alpha = cur.w) and moments
+TWK_HD void temporalBlend(const TemporalHistory& h, const float4& cur, const float4& mc, float4& colour, float4& moments)
+{
+  const float n = h.n + mc.z;
   const float r = mc.z / n;
-  colour.x = hx + (cur.x - hx) * r; colour.y = hy + (cur.y - hy) * r; colour.z = hz + (cur.z - hz) * r;
+  colour.x = h.x + (cur.x - h.x) * r; colour.y = h.y + (cur.y - h.y) * r; colour.z = h.z + (cur.z - h.z) * r;
   colour.w = cur.w;
-  const float d = mc.x - hmean;
-  moments.x = hmean + d * r;
-  moments.y = (hM2 + mc.y) + (d * d) * (hn * r);
+  const float d = mc.x - h.mean;
+  moments.x = h.mean + d * r;
+  moments.y = (h.M2 + mc.y) + (d * d) * (h.n * r);
   moments.z = n;
   moments.w = 0.0f;
+}
+
+// The merge of the interpolated history (s.ws > 0) with the frame's cur, mc
+TWK_HD void temporalMerge(const TemporalConstants& k, const TemporalSums& s, const float4& cur, const float4& mc, float4& colour, float4& moments)
+{
+  temporalBlend(temporalHistory(k, s), cur, mc, colour, moments);
 }
 
 } // namespace twk

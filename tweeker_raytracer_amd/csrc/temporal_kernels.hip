@@ -2,7 +2,7 @@
 #include "temporal_device.h"
 #include "trace_device.h"
 #include "shade_device.h" // distribute(): the pixel column of a launch index
-#include "pixel_formats.h"
+#include "temporal_store.h"
 
 namespace twk {
 
@@ -57,44 +57,15 @@ __global__ void __launch_bounds__(256) temporalKernel(const Pixel* __restrict__ 
   const float4 mc = moments[p];
   const float4 g = geometry[p];
   TemporalSums s;
-  s.x = 0.0f; s.y = 0.0f; s.z = 0.0f; s.mean = 0.0f; s.M2 = 0.0f; s.n = 0.0f; s.ws = 0.0f;
-  float fx = 0.0f, fy = 0.0f, vv = 0.0f;
-  if (temporalCandidate(k, cur, mc, g) && temporalProject(k, g, fx, fy, vv))
-  {
-    const float fx0 = floorf(fx), fy0 = floorf(fy);
-    const float tx = fx - fx0, ty = fy - fy0;
-    const int x0 = (int) fx0, y0 = (int) fy0; // in [-1, width - 1] x [-1, height - 1]
-#pragma unroll
-    for (int dy = 0; dy <= 1; ++dy)
-    {
-      const int qy = y0 + dy;
-      if (qy < 0 || qy >= k.height) continue;
-#pragma unroll
-      for (int dx = 0; dx <= 1; ++dx)
-      {
-        const int qx = x0 + dx;
-        if (qx < 0 || qx >= k.width) continue;
-        const size_t q = (size_t) qy * k.width + qx;
-        if (!temporalTapGeometry(k, g, historyGeometry[q], vv)) continue;
-        const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
-        temporalTap(historyColour[q], historyMoments[q], w, s);
-      }
-    }
-  }
+  temporalGather(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s);
   if (s.ws > 0.0f)
   {
     float4 c, m;
     temporalMerge(k, s, cur, mc, c, m);
-    if (colourOut) colourOut[p] = pixelOf<Pixel>(c);
-    if (historyOut) historyOut[p] = c;
-    if (momentsOut) momentsOut[p] = m;
+    temporalStoreMerged(p, c, m, colourOut, historyOut, momentsOut);
   }
   else
-  {
-    if (colourOut) colourOut[p] = raw;
-    if (historyOut) historyOut[p] = cur;
-    if (momentsOut) momentsOut[p] = mc;
-  }
+    temporalStorePassThrough(p, raw, cur, mc, colourOut, historyOut, momentsOut);
 }
 
 void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream)

@@ -2,7 +2,7 @@
 // twk_update_light and twk_update_material leave the temporal history as it is, and the plain merge then blends up to maxHistory
 // samples of the old lighting into every pixel. The merge measures history in SAMPLES, so the remedy is in samples too: decide per
 // pixel how many of the history's samples are still worth having, and cap them there. Nothing of temporal_device.h changes; this
-// header uses its functions and restates only what it must (the tail of temporalMerge, with the discounted count). The definition
+// header calls its functions (temporalGather, temporalHistory, temporalBlend) and adds only the trust between them. The definition
 // below is complete and is compiled once for the kernels (temporal_rectify_kernels.hip) and once for the host
 // (twk_temporal_rectify_host); tests/temporal_rectify_restate.py restates it statement for statement in numpy float32. All
 // arithmetic is f32, every operation rounded once, in the order written (-ffp-contract=off, csrc/Makefile).
@@ -10,8 +10,8 @@
 // Parameters (TwkTemporalRectify): radius R in 1..4, minTaps >= 2, gamma >= 0 and finite; g2 = gamma * gamma, once, on the host.
 //
 // ---- launch 1, reproject ----------------------------------------------------------------------------------------------------------
-// pixel p: exactly temporal_device.h's gather (temporalCandidate, temporalProject, the four taps in their order, temporalTapGeometry,
-// temporalTap). With ws > 0 the quotients and the cap that open temporalMerge:
+// pixel p: temporal_device.h's gather, temporalGather itself (temporalCandidate, temporalProject, the four taps in their order,
+// temporalTapGeometry, temporalTap). With ws > 0 the quotients and the cap that open its merge, temporalHistory itself:
 //   hx = sx / ws;  hy = sy / ws;  hz = sz / ws;  hmean = smean / ws;  hM2 = sM2 / ws;  hn = sn / ws
 //   if hn > maxHistory:  hM2 = hM2 * (maxHistory / hn);  hn = maxHistory
 // written to two f32 float4 scratch streams of the handle:  A[p] = (hx, hy, hz, 0);  B[p] = (hmean, hM2, hn, g.w)   (g.w: its bits)
@@ -33,7 +33,7 @@
 //   !(hn' > 0): the pixel PASSES THROUGH — colourOut[p] = colour[p] (its bits), historyOut[p] = cur, momentsOut[p] = mc — and
 //     trustOut[p] = 0 if hn > 0 (the test, or the underflow of hn * t, took all of a history that was there), else t = 1 (nothing
 //     was there and nothing was tested).
-//   else the remaining statements of temporalMerge with hn', hM2':
+//   else the remaining statements of the plain merge, temporalBlend itself, with hn', hM2':
 //     n = hn' + mc.z;  r = mc.z / n;  colour.k = h.k + (cur.k - h.k) * r;  d = mc.x - hmean;  mean = hmean + d * r;
 //     M2 = (hM2' + mc.y) + (d * d) * (hn' * r);  outputs as temporal_device.h writes them;  trustOut[p] = t
 // t = 1 gives hn' = hn and hM2' = hM2 exactly: where nothing is tested, every output has the bits of twk_temporal_accumulate.
@@ -75,34 +75,6 @@ struct RectifyConstants
   float gamma2; // gamma * gamma
 };
 
-// temporal_device.h's gather at pixel p (the loop of temporalKernel, statement for statement): s.ws > 0 says there is history
-TWK_HD void rectifyGather(const TemporalConstants& k, const float4& cur, const float4& mc, const float4& g, const float4* historyColour, const float4* historyMoments,
-                          const float4* historyGeometry, TemporalSums& s)
-{
-  s.x = 0.0f; s.y = 0.0f; s.z = 0.0f; s.mean = 0.0f; s.M2 = 0.0f; s.n = 0.0f; s.ws = 0.0f;
-  float fx = 0.0f, fy = 0.0f, vv = 0.0f;
-  if (!(temporalCandidate(k, cur, mc, g) && temporalProject(k, g, fx, fy, vv))) return;
-  const float fx0 = floorf(fx), fy0 = floorf(fy);
-  const float tx = fx - fx0, ty = fy - fy0;
-  const int x0 = (int) fx0, y0 = (int) fy0; // in [-1, width - 1] x [-1, height - 1]
-#pragma unroll
-  for (int dy = 0; dy <= 1; ++dy)
-  {
-    const int qy = y0 + dy;
-    if (qy < 0 || qy >= k.height) continue;
-#pragma unroll
-    for (int dx = 0; dx <= 1; ++dx)
-    {
-      const int qx = x0 + dx;
-      if (qx < 0 || qx >= k.width) continue;
-      const size_t q = (size_t) qy * k.width + qx;
-      if (!temporalTapGeometry(k, g, historyGeometry[q], vv)) continue;
-      const float w = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
-      temporalTap(historyColour[q], historyMoments[q], w, s);
-    }
-  }
-}
-
 // Launch 1 at one pixel: the reprojected, capped history as the two scratch words A = (hx, hy, hz, 0), B = (hmean, hM2, hn, g.w)
 TWK_HD void rectifyReproject(const TemporalConstants& k, const float4& cur, const float4& mc, const float4& g, const float4* historyColour, const float4* historyMoments,
                              const float4* historyGeometry, float4& A, float4& B)
@@ -110,13 +82,11 @@ TWK_HD void rectifyReproject(const TemporalConstants& k, const float4& cur, cons
   A = make_float4(0.0f, 0.0f, 0.0f, 0.0f); B = A;
   if (k.hasHistory == 0) return;
   TemporalSums s;
-  rectifyGather(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s);
+  temporalGather(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s);
   if (!(s.ws > 0.0f)) return;
-  A.x = s.x / s.ws; A.y = s.y / s.ws; A.z = s.z / s.ws;
-  const float hmean = s.mean / s.ws;
-  float hM2 = s.M2 / s.ws, hn = s.n / s.ws;
-  if (hn > k.maxHistory) { hM2 = hM2 * (k.maxHistory / hn); hn = k.maxHistory; }
-  B = make_float4(hmean, hM2, hn, g.w);
+  const TemporalHistory h = temporalHistory(k, s);
+  A.x = h.x; A.y = h.y; A.z = h.z;
+  B = make_float4(h.mean, h.M2, h.n, g.w);
 }
 
 // The two staged words of pixel q from its moments and its scratch word B
@@ -162,17 +132,11 @@ TWK_HD float rectifyTrust(const RectifyConstants& r, const float* d, const unsig
 // Launch 2's merge at one pixel, the trust t known: false = pass through (the caller writes the frame's bits); trust = trustOut[p]
 TWK_HD bool rectifyMerge(float t, const float4& cur, const float4& mc, const float4& A, const float4& B, float4& colour, float4& moments, float& trust)
 {
-  const float hn = B.z * t, hM2 = B.y * t;
-  if (!(hn > 0.0f)) { trust = (B.z > 0.0f) ? 0.0f : t; return false; }
-  const float n = hn + mc.z;
-  const float r = mc.z / n;
-  colour.x = A.x + (cur.x - A.x) * r; colour.y = A.y + (cur.y - A.y) * r; colour.z = A.z + (cur.z - A.z) * r;
-  colour.w = cur.w;
-  const float d = mc.x - B.x;
-  moments.x = B.x + d * r;
-  moments.y = (hM2 + mc.y) + (d * d) * (hn * r);
-  moments.z = n;
-  moments.w = 0.0f;
+  TemporalHistory h;
+  h.x = A.x; h.y = A.y; h.z = A.z; h.mean = B.x;
+  h.n = B.z * t; h.M2 = B.y * t;
+  if (!(h.n > 0.0f)) { trust = (B.z > 0.0f) ? 0.0f : t; return false; }
+  temporalBlend(h, cur, mc, colour, moments);
   trust = t;
   return true;
 }

@@ -1,6 +1,6 @@
 // Kernels of twk_temporal_accumulate_rectified: the two launches temporal_rectify_device.h defines.
 #include "temporal_rectify_device.h"
-#include "pixel_formats.h"
+#include "temporal_store.h"
 
 // The window radius of the test kernel: below TWK_RECTIFY_RUNTIME_FROM it is a template parameter (one build per radius and format,
 // the window loops unrolled, the window's d held in registers between the two passes), from there on a run-time value (one build
@@ -73,18 +73,8 @@ rectifyMergeKernel(const Pixel* __restrict__ colour, const float4* __restrict__ 
   const float t = rectifyTrust<R>(r, sd, sk, PITCH, (ly + radius) * PITCH + lx + radius, B.z, mc.z);
   float4 c, m;
   float trust;
-  if (rectifyMerge(t, cur, mc, A, B, c, m, trust))
-  {
-    if (colourOut) colourOut[p] = pixelOf<Pixel>(c);
-    if (historyOut) historyOut[p] = c;
-    if (momentsOut) momentsOut[p] = m;
-  }
-  else
-  {
-    if (colourOut) colourOut[p] = raw;
-    if (historyOut) historyOut[p] = cur;
-    if (momentsOut) momentsOut[p] = mc;
-  }
+  if (rectifyMerge(t, cur, mc, A, B, c, m, trust)) temporalStoreMerged(p, c, m, colourOut, historyOut, momentsOut);
+  else temporalStorePassThrough(p, raw, cur, mc, colourOut, historyOut, momentsOut);
   if (trustOut) trustOut[p] = trust;
 }
 

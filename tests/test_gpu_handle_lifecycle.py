@@ -3,7 +3,8 @@ schedule). Every comparison is np.array_equal on uint32 / uint16 words: there ar
   2a  reused handle == fresh handle, key by key, for every transition of the table, in RGBA32F and RGBA16F; the tiled cases check
       their own sensitivity before the move and the padding after it; the one-handle cases are anchored to the CPU oracle
   2b  a twk_set_state that leaves the frame's geometry alone keeps the buffers (the device pointers do not change)
-  2c  external output buffers and shared frames through a shrink and a grow, with guarded slack behind every allocation"""
+  2c  external output buffers and shared frames through a shrink and a grow, with guarded slack behind every allocation
+  2d  three handles created, run through the schedule and destroyed in turn; a fourth renders what the first did"""
 import numpy as np
 import pytest
 
@@ -165,6 +166,23 @@ def test_a_state_change_that_keeps_the_geometry_keeps_the_buffers(twk):
     sizes = [n for _, n in _pointers(fresh)]
     assert sizes == [24 * 16 * 16, 24 * 16 * 16, 24 * 16 * 16 * twk._lib.TWK_CASCADE_LAYERS, 24 * 16 * 16]
     fresh.close()
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["rgba32f", "rgba16f"])
+def test_a_destroyed_handle_leaves_nothing_to_the_next(twk, half):
+    """Three handles with every feature on are created, run through the whole schedule and destroyed, one after the other in one
+    process: twk_device_destroy frees every buffer the schedule made the handle allocate. A fourth, fresh handle's snapshot then
+    equals the first's key by key, word by word: nothing of a destroyed handle reaches the next one."""
+    shape = lc.Shape(24, 16)
+    app = lc.make_app(twk, load_app, shape)
+    shots = []
+    for _ in range(4):
+        dev = lc.new_device(twk, app, shape, half=half)
+        shots.append(lc.snapshot(twk, dev, app, False))
+        dev.close()
+    assert set(shots[3]) == set(shots[0])
+    problems = _problems(shots[3], shots[0])
+    assert not problems, f"the fourth handle against the first: {len(problems)} differences\n  " + "\n  ".join(problems)
 
 
 class _Guarded:

@@ -30,38 +30,33 @@ static void adaptiveDefaults(TwkAdaptive& a)
   a.targetNoise = TWK_ADAPTIVE_TARGET_NOISE; a.minSamples = TWK_DENOISER_MIN_SAMPLES; a.darkFloor = TWK_NOISE_DARK_FLOOR; a.maxSamples = TWK_ADAPTIVE_MAX_SAMPLES;
 }
 
+// The scan scratch, for a select of numElements elements (also the explicit form's). Its capacity counts elements.
 static int ensureAdaptiveScratch(TwkDevice dev, size_t numElements)
 {
-  if (dev->d_adaptiveScratch && dev->adaptiveScratchElements >= numElements) return TWK_SUCCESS;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  freeDevice(dev->d_adaptiveScratch); dev->adaptiveScratchElements = 0; dev->adaptiveScratchPlan = false;
-  HIP_TRY(hipMalloc(&dev->d_adaptiveScratch, adaptiveScratchBytes(numElements)));
-  dev->adaptiveScratchElements = numElements;
-  return TWK_SUCCESS;
+  if (!dev->d_adaptiveScratch.holds(numElements)) dev->adaptiveScratchPlan = false;
+  return growIdle(dev, dev->d_adaptiveScratch, numElements, adaptiveScratchBytes(numElements));
 }
 
 // ... for a plan: the same buffer at the plan's larger size, which holds a select of as many elements too
 static int ensureAdaptivePlanScratch(TwkDevice dev, size_t numElements)
 {
-  if (dev->d_adaptiveScratch && dev->adaptiveScratchPlan && dev->adaptiveScratchElements >= numElements) return TWK_SUCCESS;
+  if (dev->adaptiveScratchPlan && dev->d_adaptiveScratch.holds(numElements)) return TWK_SUCCESS;
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  const size_t elements = std::max(numElements, dev->d_adaptiveScratch ? dev->adaptiveScratchElements : (size_t) 0);
-  freeDevice(dev->d_adaptiveScratch); dev->adaptiveScratchElements = 0; dev->adaptiveScratchPlan = false;
-  HIP_TRY(hipMalloc(&dev->d_adaptiveScratch, std::max(adaptivePlanScratchBytes(elements), adaptiveScratchBytes(elements))));
-  dev->adaptiveScratchElements = elements; dev->adaptiveScratchPlan = true;
+  const size_t elements = std::max(numElements, dev->d_adaptiveScratch.capacity());
+  dev->adaptiveScratchPlan = false;
+  const int rc = dev->d_adaptiveScratch.allocate(elements, false, nullptr, std::max(adaptivePlanScratchBytes(elements), adaptiveScratchBytes(elements))); if (rc) return rc;
+  dev->adaptiveScratchPlan = true;
   return TWK_SUCCESS;
 }
 
-// The plan's own list and offsets of the own-buffer form
+// The plan's own list and offsets of the own-buffer form: numElements and numElements + 1 words
 static int ensurePlanBuffers(TwkDevice dev, size_t numElements)
 {
-  if (dev->d_planActive && dev->d_planOffsets && dev->planElements >= numElements) return TWK_SUCCESS;
+  if (dev->d_planActive.holds(numElements) && dev->d_planOffsets.holds(numElements + 1)) return TWK_SUCCESS;
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets); dev->planElements = 0; dev->planValid = false;
-  HIP_TRY(hipMalloc(&dev->d_planActive, numElements * sizeof(unsigned int)));
-  HIP_TRY(hipMalloc(&dev->d_planOffsets, (numElements + 1) * sizeof(unsigned int)));
-  dev->planElements = numElements;
-  return TWK_SUCCESS;
+  dev->d_planActive.release(); dev->d_planOffsets.release(); dev->planValid = false;
+  const int rc = dev->d_planActive.allocate(numElements);
+  return rc ? rc : dev->d_planOffsets.allocate(numElements + 1);
 }
 
 static void adaptivePlanDefaults(TwkAdaptivePlan& p) { p.minBatch = TWK_DENOISER_MIN_SAMPLES; p.maxBatch = TWK_ADAPTIVE_PLAN_MAX_BATCH; }
@@ -101,15 +96,15 @@ try
   dev->adaptiveEnabled = (enable != 0);
   if (!dev->adaptiveEnabled)
   {
-    freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); dev->adaptivePixels = 0;
-    freeDevice(dev->d_adaptiveScratch); dev->adaptiveScratchElements = 0; dev->adaptiveScratchPlan = false;
-    freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets); dev->planElements = 0;
+    dev->d_sampleCounts.release(); dev->d_active.release();
+    dev->d_adaptiveScratch.release(); dev->adaptiveScratchPlan = false;
+    dev->d_planActive.release(); dev->d_planOffsets.release();
     dropAdaptive(dev);
     return TWK_SUCCESS;
   }
   if (!dev->stateSet) return TWK_SUCCESS; // allocated by the first use after twk_set_state
   if ((rc = ensureStreams(dev))) return rc;
-  return ensureAdaptiveScratch(dev, (size_t) dev->launchWidth * dev->state.resolution[1]);
+  return ensureAdaptiveScratch(dev, launchIndices(dev));
 }
 TWK_CATCH("twk_enable_adaptive")
 
@@ -139,11 +134,10 @@ try
   {
     if (!dev->stateSet || !dev->momentsEnabled || !dev->adaptiveEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers need twk_enable_moments(1), twk_enable_adaptive(1) and twk_set_state");
     if ((rc = ensureStreams(dev))) return rc;
-    numElements = (size_t) dev->launchWidth * dev->state.resolution[1];
-    if (!dev->d_moments || (size_t) dev->momentsPixels < numElements || !dev->d_sampleCounts || (size_t) dev->adaptivePixels < numElements)
-      return refuse(TWK_ERROR_INVALID_STATE, "the handle has no moments or sample counts");
+    numElements = launchIndices(dev);
+    if (!(moments = ownMoments(dev, numElements)) || !(counts = ownSampleCounts(dev, numElements))) return refuse(TWK_ERROR_INVALID_STATE, "the handle has no moments or sample counts");
     if ((rc = currentSampleCounts(dev))) return rc;
-    moments = dev->d_moments; counts = dev->d_sampleCounts; activeOut = dev->d_active;
+    activeOut = dev->d_active;
     dev->activeValid = false; dev->planValid = false; // a select supersedes the plan: the loop goes on with one or the other
   }
   if ((rc = ensureAdaptiveScratch(dev, numElements))) return rc;
@@ -223,12 +217,11 @@ try
   {
     if (!dev->stateSet || !dev->momentsEnabled || !dev->adaptiveEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers need twk_enable_moments(1), twk_enable_adaptive(1) and twk_set_state");
     if ((rc = ensureStreams(dev))) return rc;
-    numElements = (size_t) dev->launchWidth * dev->state.resolution[1];
-    if (!dev->d_moments || (size_t) dev->momentsPixels < numElements || !dev->d_sampleCounts || (size_t) dev->adaptivePixels < numElements)
-      return refuse(TWK_ERROR_INVALID_STATE, "the handle has no moments or sample counts");
+    numElements = launchIndices(dev);
+    if (!(moments = ownMoments(dev, numElements)) || !(counts = ownSampleCounts(dev, numElements))) return refuse(TWK_ERROR_INVALID_STATE, "the handle has no moments or sample counts");
     if ((rc = currentSampleCounts(dev))) return rc;
     if ((rc = ensurePlanBuffers(dev, numElements))) return rc;
-    moments = dev->d_moments; counts = dev->d_sampleCounts; activeOut = dev->d_planActive; pathOffsetOut = dev->d_planOffsets;
+    activeOut = dev->d_planActive; pathOffsetOut = dev->d_planOffsets;
     dev->planValid = false;
   }
   if ((rc = ensureAdaptivePlanScratch(dev, numElements))) return rc;
@@ -299,27 +292,25 @@ try
   int rc = activate(dev, "twk_read_sample_counts"); if (rc) return rc;
   if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_sample_counts: NULL buffer");
   if (!dev->adaptiveEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_sample_counts: twk_enable_adaptive(1) and twk_set_state first");
-  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
+  const size_t n = launchIndices(dev);
   if (numElements != n) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_sample_counts: buffer must hold launchWidth*height words");
-  if ((rc = ensureStreams(dev))) return rc;
+  if ((rc = ensureStreams(dev))) return rc; // (allocated and made current only now that the call is known to read them)
   if ((rc = currentSampleCounts(dev))) return rc;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_sampleCounts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  return copyBack(dev, "twk_read_sample_counts", dev->d_sampleCounts, n, sizeof(uint32_t), host);
 }
 TWK_CATCH("twk_read_sample_counts")
 
 int twk_get_sample_counts_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_sample_counts_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_sample_counts_device_pointer: NULL argument");
-  if (!dev->adaptiveEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_sample_counts_device_pointer: twk_enable_adaptive(1) and twk_set_state first");
-  if ((rc = ensureStreams(dev))) return rc;
-  if ((rc = currentSampleCounts(dev))) return rc;
-  *dptr = dev->d_sampleCounts;
-  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(uint32_t);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_sample_counts_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!dev->adaptiveEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_sample_counts_device_pointer: twk_enable_adaptive(1) and twk_set_state first");
+    int rc = ensureStreams(dev); if (rc) return rc;
+    rc = currentSampleCounts(dev);
+    pointer = dev->d_sampleCounts; size = launchIndices(dev) * sizeof(uint32_t);
+    return rc;
+  });
 }
 TWK_CATCH("twk_get_sample_counts_device_pointer")
 

@@ -3,7 +3,9 @@
 // Host code here only moves data and enqueues kernels; nothing is ever computed on the CPU in place
 // of a kernel. Without a HIP device every entry point that needs one fails.
 // This file: the error state, the handle's life, the setters of state, camera, lights, materials and textures, the run-time
-// switches, and the output, AOV, moments and geometry buffers with their readers (device_handle.h names the other files).
+// switches, and the output, AOV, moments and geometry buffers with their readers (device_handle.h names the other files); and what
+// every reader of every file ends in: readBack, copyBack, readPixels. twk_device_destroy frees no buffer by name: the handle's
+// buffers are DeviceArray members (device_buffers.h).
 #include "device_handle.h"
 
 #include <algorithm>
@@ -46,6 +48,27 @@ int twk::readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels
   float* rgbaHost = static_cast<float*>(host);
   for (size_t i = 0; i < halves.size(); ++i) rgbaHost[i] = halfToFloat(halves[i]);
   return TWK_SUCCESS;
+}
+
+// What every reader ends in, on an active handle: everything enqueued runs, then `count` elements go to the host (elementBytes 0:
+// pixels of the output format, widened to RGBA32F); dropped: the buffer is a pass's result, so a lost traversal push is reported
+int twk::copyBack(TwkDevice dev, const char* name, const void* source, size_t count, size_t elementBytes, void* host, bool dropped)
+{
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  if (elementBytes == 0) { const int rc = readPixels(dev, source, host, count, false); if (rc) return rc; }
+  else HIP_TRY(hipMemcpy(host, source, count * elementBytes, hipMemcpyDeviceToHost));
+  return dropped ? checkDroppedPushes(dev, name) : TWK_SUCCESS;
+}
+
+// One reader, on an active handle: `given` is the size the caller passed, in its own unit of `unit` per element (sizeText: what
+// the buffer must hold)
+int twk::readBack(TwkDevice dev, const char* name, const Readback& r, void* host, size_t given, size_t unit, const char* sizeText, bool dropped)
+{
+  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL buffer");
+  if (!r.source && r.ownShape) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": " + r.refusal);
+  if (given != r.count * unit) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": buffer must hold " + sizeText);
+  if (!r.source) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": " + r.refusal);
+  return copyBack(dev, name, r.source, r.count, r.elementBytes, host, dropped);
 }
 
 // The on/off switches that only set one flag of the handle, once everything enqueued has run with the old value
@@ -168,13 +191,13 @@ static void readEnvironmentSwitches(TwkDevice_t* dev)
 // streams, spill stacks and scratch keep their capacity; a caller's external output buffer or shared frame is the caller's to clear.
 static void dropAccumulations(TwkDevice dev)
 {
-  freeDevice(dev->d_outputInternal); freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance); dev->allocatedPixels = 0;
-  freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
-  freeDevice(dev->d_moments); dev->momentsPixels = 0;
-  freeDevice(dev->d_cascade); dev->cascadePixels = 0; dev->resolvedValid = false;
-  freeDevice(dev->d_geometry); dev->geometryPixels = 0;
-  freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); dev->adaptivePixels = 0;
-  freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets); dev->planElements = 0;
+  dev->d_outputInternal.release(); dev->d_firstHit.release(); dev->d_firstHitInstance.release();
+  dev->d_aovAlbedo.release(); dev->d_aovNormal.release();
+  dev->d_moments.release();
+  dev->d_cascade.release(); dev->resolved.valid = false;
+  dev->d_geometry.release();
+  dev->d_sampleCounts.release(); dev->d_active.release();
+  dev->d_planActive.release(); dev->d_planOffsets.release();
   dropAssembled(dev); // what the handle assembled as a primary has the old frame's shape
 }
 
@@ -245,21 +268,6 @@ try
   (void) hipSetDevice(dev->ordinal);
   if (dev->stream) (void) hipStreamSynchronize(dev->stream);
   for (TimedLaunch& t : dev->timed) { (void) hipEventDestroy(t.start); (void) hipEventDestroy(t.stop); }
-  freeDevice(dev->d_camera); freeDevice(dev->d_lights); freeDevice(dev->d_materials);
-  freeDevice(dev->d_attributes); freeDevice(dev->d_indices);
-  freeDevice(dev->d_nodes); freeDevice(dev->d_wideNodes); freeDevice(dev->d_wideQ); freeDevice(dev->d_triangles); freeDevice(dev->d_shadeTriangles); freeDevice(dev->d_instances);
-  for (int k = 0; k < 3; ++k) freeDevice(dev->d_texels[k]);
-  freeDevice(dev->d_envCDF_U); freeDevice(dev->d_envCDF_V); freeDevice(dev->d_topNodes); freeDevice(dev->d_topNodes7); freeDevice(dev->d_tileEntries);
-  freeDevice(dev->d_streamBlock); freeDevice(dev->d_outputInternal);
-  freeDevice(dev->d_counters); freeDevice(dev->d_stats); freeDevice(dev->d_spill); freeDevice(dev->d_pathTime);
-  if (dev->h_dropped) { (void) hipHostFree(dev->h_dropped); dev->h_dropped = nullptr; dev->d_dropped = nullptr; }
-  freeDevice(dev->d_firstHit); freeDevice(dev->d_firstHitInstance);
-  freeDevice(dev->d_pathAlbedo); freeDevice(dev->d_pathNormal); freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); freeDevice(dev->d_moments);
-  freeDevice(dev->d_geometry); dropTemporal(dev);
-  freeDevice(dev->d_cascade); freeDevice(dev->d_cascadeLambda); freeDevice(dev->d_resolved);
-  freeDevice(dev->d_denoised); freeDevice(dev->d_denoiseStreams); freeDevice(dev->d_noise);
-  freeDevice(dev->d_sampleCounts); freeDevice(dev->d_active); freeDevice(dev->d_adaptiveScratch); freeDevice(dev->d_planActive); freeDevice(dev->d_planOffsets);
-  dropAssembled(dev);
   if (dev->assembleReady) (void) hipEventDestroy(dev->assembleReady);
   if (dev->assembleDone) (void) hipEventDestroy(dev->assembleDone);
   dev->builder.release();
@@ -270,7 +278,8 @@ try
   }
   if (dev->laneFork) (void) hipEventDestroy(dev->laneFork);
   if (dev->stream) (void) hipStreamDestroy(dev->stream);
-  delete dev;
+  if (dev->h_dropped) (void) hipHostFree(dev->h_dropped);
+  delete dev; // every device buffer is a DeviceArray member: freed here
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_device_destroy")
@@ -319,7 +328,7 @@ try
   if (!c || count < 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_init_cameras: at least one camera is required");
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->cameras.assign(c, c + count); staleGeometry(dev);
-  if (!dev->d_camera) HIP_TRY(hipMalloc(&dev->d_camera, sizeof(TwkCameraDefinition)));
+  if ((rc = dev->d_camera.ensure(sizeof(TwkCameraDefinition) / sizeof(float)))) return rc;
   HIP_TRY(hipMemcpyAsync(dev->d_camera, dev->cameras.data(), sizeof(TwkCameraDefinition), hipMemcpyHostToDevice, dev->stream)); // the lens shaders read cameraDefinitions[0]
   return TWK_SUCCESS;
 }
@@ -346,11 +355,11 @@ try
   if (dev->built && count <= dev->maxInstanceLight)
     return twkSetError(TWK_ERROR_INVALID_STATE, "twk_init_lights: the built scene has an instance with light index " + std::to_string(dev->maxInstanceLight) + "; " + std::to_string(count) + " lights would leave it dangling (twk_clear_scene first)");
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  freeDevice(dev->d_lights);
+  dev->d_lights.release();
   dev->lights.assign(l, l + count);
   if (count > 0)
   {
-    HIP_TRY(hipMalloc(&dev->d_lights, sizeof(DevLight) * count));
+    if ((rc = dev->d_lights.allocate((size_t) count))) return rc;
     HIP_TRY(hipMemcpyAsync(dev->d_lights, dev->lights.data(), sizeof(DevLight) * count, hipMemcpyHostToDevice, dev->stream));
   }
   return TWK_SUCCESS;
@@ -383,12 +392,7 @@ try
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->materials.resize(count);
   for (int i = 0; i < count; ++i) dev->materials[i] = convertMaterial(m[i]);
-  if (count > dev->materialCapacity)
-  {
-    freeDevice(dev->d_materials);
-    HIP_TRY(hipMalloc(&dev->d_materials, sizeof(DevMaterial) * count));
-    dev->materialCapacity = count;
-  }
+  if ((rc = dev->d_materials.ensure((size_t) count))) return rc;
   HIP_TRY(hipMemcpyAsync(dev->d_materials, dev->materials.data(), sizeof(DevMaterial) * count, hipMemcpyHostToDevice, dev->stream));
   return TWK_SUCCESS;
 }
@@ -413,9 +417,8 @@ try
   int rc = activate(dev, "twk_init_texture"); if (rc) return rc;
   if (slot < 0 || slot > 2 || !rgba || width < 1 || height < 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_init_texture: bad arguments");
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  freeDevice(dev->d_texels[slot]);
   const size_t bytes = sizeof(float4) * (size_t) width * height;
-  HIP_TRY(hipMalloc(&dev->d_texels[slot], bytes));
+  if ((rc = dev->d_texels[slot].allocate((size_t) width * height))) return rc;
   HIP_TRY(hipMemcpy(dev->d_texels[slot], rgba, bytes, hipMemcpyHostToDevice));
   DevTexture& t = dev->params.textures[slot];
   t.texels = dev->d_texels[slot]; t.width = width; t.height = height; t.clampV = (slot == TWK_TEXTURE_ENVIRONMENT) ? 1 : 0; t.pad = 0;
@@ -423,9 +426,8 @@ try
   {
     std::vector<float> cdfU, cdfV; float integral = 1.0f;
     calculateSphericalCDF(rgba, (unsigned int) width, (unsigned int) height, cdfU, cdfV, integral);
-    freeDevice(dev->d_envCDF_U); freeDevice(dev->d_envCDF_V);
-    HIP_TRY(hipMalloc(&dev->d_envCDF_U, sizeof(float) * cdfU.size()));
-    HIP_TRY(hipMalloc(&dev->d_envCDF_V, sizeof(float) * cdfV.size()));
+    dev->d_envCDF_U.release(); dev->d_envCDF_V.release();
+    if ((rc = dev->d_envCDF_U.allocate(cdfU.size())) || (rc = dev->d_envCDF_V.allocate(cdfV.size()))) return rc;
     HIP_TRY(hipMemcpy(dev->d_envCDF_U, cdfU.data(), sizeof(float) * cdfU.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dev->d_envCDF_V, cdfV.data(), sizeof(float) * cdfV.size(), hipMemcpyHostToDevice));
     dev->params.envWidth = (unsigned int) width; dev->params.envHeight = (unsigned int) height; dev->params.envIntegral = integral;
@@ -456,16 +458,8 @@ TWK_CATCH("twk_get_launch_width")
 static int readOutput(TwkDevice dev, void* host, size_t size, bool raw, const char* where)
 {
   int rc = activate(dev, where); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + ": NULL buffer");
-  const size_t n = outputPixels(dev);
-  if (size != n * (raw ? pixelBytes(dev) : 4))
-    return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + (raw ? ": buffer must hold launchWidth*height pixels (width*height with a shared frame) of the output format"
-                                                                           : ": buffer must hold launchWidth*height*4 floats (width*height*4 with a shared frame)"));
-  const float4* src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-  if (!src) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": nothing has been rendered");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  if ((rc = readPixels(dev, src, host, n, raw))) return rc;
-  return checkDroppedPushes(dev, where);
+  return readBack(dev, where, {ownOutput(dev), "nothing has been rendered", outputPixels(dev), raw ? pixelBytes(dev) : 0, false}, host, size, raw ? pixelBytes(dev) : 4,
+                  raw ? "launchWidth*height pixels (width*height with a shared frame) of the output format" : "launchWidth*height*4 floats (width*height*4 with a shared frame)", true);
 }
 
 int twk_read_output(TwkDevice dev, float* rgbaHost, size_t numFloats)
@@ -493,9 +487,9 @@ try
     return twkSetError(TWK_ERROR_INVALID_STATE, "twk_set_output_format: the external output buffer is too small for the new format");
   HIP_TRY(hipStreamSynchronize(dev->stream));
   // the internal output and AOV buffers are allocated again at the new pixel size, zeroed, by the next ensureStreams
-  freeDevice(dev->d_outputInternal);
-  freeDevice(dev->d_aovAlbedo); freeDevice(dev->d_aovNormal); dev->aovPixels = 0;
-  freeDevice(dev->d_denoised); dev->denoisedValid = false; // a denoised picture is in the format it was filtered in
+  dev->d_outputInternal.release(); // (its group with it: ensureStreams)
+  dev->d_aovAlbedo.release(); dev->d_aovNormal.release();
+  dev->denoised.release(); // a denoised picture is in the format it was filtered in
   dropAssembled(dev); // and so is an assembled frame
   dev->outputFormat = format; dropAdaptive(dev);
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS;
@@ -536,7 +530,7 @@ try
   int rc = activate(dev, "twk_enable_moments"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->momentsEnabled = (enable != 0); dropAdaptive(dev);
-  if (!dev->momentsEnabled) { freeDevice(dev->d_moments); dev->momentsPixels = 0; return TWK_SUCCESS; } // enabled again: a zeroed buffer
+  if (!dev->momentsEnabled) { dev->d_moments.release(); return TWK_SUCCESS; } // enabled again: a zeroed buffer
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first pass after twk_set_state
 }
 TWK_CATCH("twk_enable_moments")
@@ -545,26 +539,21 @@ int twk_read_moments(TwkDevice dev, float* host, size_t numFloats)
 try
 {
   int rc = activate(dev, "twk_read_moments"); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_moments: NULL buffer");
-  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_moments: buffer must hold launchWidth*height*4 floats");
-  if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_moments: twk_enable_moments(1) and twk_set_state first");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_moments, n * sizeof(float4), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  const size_t n = launchIndices(dev);
+  return readBack(dev, "twk_read_moments", {ownMoments(dev, n), "twk_enable_moments(1) and twk_set_state first", n, sizeof(float4), false}, host, numFloats, 4, "launchWidth*height*4 floats");
 }
 TWK_CATCH("twk_read_moments")
 
 int twk_get_moments_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_moments_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_moments_device_pointer: NULL argument");
-  if (!dev->momentsEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_moments_device_pointer: twk_enable_moments(1) and twk_set_state first");
-  if ((rc = ensureStreams(dev))) return rc;
-  *dptr = dev->d_moments;
-  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(float4);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_moments_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!dev->momentsEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_moments_device_pointer: twk_enable_moments(1) and twk_set_state first");
+    const int rc = ensureStreams(dev);
+    pointer = dev->d_moments; size = launchIndices(dev) * sizeof(float4);
+    return rc;
+  });
 }
 TWK_CATCH("twk_get_moments_device_pointer")
 
@@ -583,7 +572,7 @@ try
   int rc = activate(dev, "twk_enable_geometry"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->geometryEnabled = (enable != 0); staleGeometry(dev);
-  if (!dev->geometryEnabled) { freeDevice(dev->d_geometry); dev->geometryPixels = 0; return TWK_SUCCESS; } // enabled again: a zeroed buffer
+  if (!dev->geometryEnabled) { dev->d_geometry.release(); return TWK_SUCCESS; } // enabled again: a zeroed buffer
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first use after twk_set_state
 }
 TWK_CATCH("twk_enable_geometry")
@@ -592,26 +581,21 @@ int twk_read_geometry(TwkDevice dev, float* host, size_t numFloats)
 try
 {
   int rc = activate(dev, "twk_read_geometry"); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_geometry: NULL buffer");
-  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_geometry: buffer must hold launchWidth*height*4 floats");
-  if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_geometry: twk_enable_geometry(1) and twk_set_state first");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_geometry, n * sizeof(float4), hipMemcpyDeviceToHost));
-  return checkDroppedPushes(dev, "twk_read_geometry");
+  const size_t n = launchIndices(dev);
+  return readBack(dev, "twk_read_geometry", {ownGeometry(dev, n), "twk_enable_geometry(1) and twk_set_state first", n, sizeof(float4), false}, host, numFloats, 4, "launchWidth*height*4 floats", true);
 }
 TWK_CATCH("twk_read_geometry")
 
 int twk_get_geometry_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_geometry_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_geometry_device_pointer: NULL argument");
-  if (!dev->geometryEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_geometry_device_pointer: twk_enable_geometry(1) and twk_set_state first");
-  if ((rc = ensureStreams(dev))) return rc;
-  *dptr = dev->d_geometry;
-  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * sizeof(float4);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_geometry_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!dev->geometryEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_geometry_device_pointer: twk_enable_geometry(1) and twk_set_state first");
+    const int rc = ensureStreams(dev);
+    pointer = dev->d_geometry; size = launchIndices(dev) * sizeof(float4);
+    return rc;
+  });
 }
 TWK_CATCH("twk_get_geometry_device_pointer")
 
@@ -641,13 +625,9 @@ static int readAov(TwkDevice dev, int which, void* host, size_t size, bool raw, 
 {
   int rc = activate(dev, where); if (rc) return rc;
   if (!host || (which != TWK_AOV_ALBEDO && which != TWK_AOV_NORMAL)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + ": bad arguments");
-  const size_t n = (size_t) dev->launchWidth * dev->state.resolution[1];
-  if (size != n * (raw ? pixelBytes(dev) : 4))
-    return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + (raw ? ": buffer must hold launchWidth*height pixels of the output format" : ": buffer must hold launchWidth*height*4 floats"));
-  const float4* src = (which == TWK_AOV_ALBEDO) ? dev->d_aovAlbedo : dev->d_aovNormal;
-  if (!dev->aovEnabled || !src || (size_t) dev->aovPixels < n) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": nothing has been rendered with twk_enable_aov(1)");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  return readPixels(dev, src, host, n, raw);
+  const size_t n = launchIndices(dev);
+  return readBack(dev, where, {(which == TWK_AOV_ALBEDO) ? ownAlbedo(dev, n) : ownNormal(dev, n), "nothing has been rendered with twk_enable_aov(1)", n, raw ? pixelBytes(dev) : 0, false}, host, size,
+                  raw ? pixelBytes(dev) : 4, raw ? "launchWidth*height pixels of the output format" : "launchWidth*height*4 floats");
 }
 
 int twk_read_aov(TwkDevice dev, int which, float* rgbaHost, size_t numFloats)
@@ -667,13 +647,13 @@ TWK_CATCH("twk_read_aov_raw")
 int twk_get_output_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_output_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_output_device_pointer: NULL argument");
-  if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_output_device_pointer: twk_set_state first");
-  if ((rc = ensureStreams(dev))) return rc;
-  *dptr = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-  if (bytes) *bytes = (size_t) dev->launchWidth * dev->state.resolution[1] * pixelBytes(dev);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_output_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_output_device_pointer: twk_set_state first");
+    const int rc = ensureStreams(dev);
+    pointer = ownOutput(dev); size = launchIndices(dev) * pixelBytes(dev);
+    return rc;
+  });
 }
 TWK_CATCH("twk_get_output_device_pointer")
 

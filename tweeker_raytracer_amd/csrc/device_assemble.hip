@@ -3,6 +3,7 @@
 // the handles' own buffers with its stream ordering, peer access and staging (twk_assemble_devices), the readers and the host-only form.
 // twk_assemble_with_geometry and twk_assemble_devices_with_geometry are the same two forms with the geometry AOV of every tile share
 // (twk_render_geometry_tile) as further entries of the same table: one launch, an assembled buffer of its own beside the six planes'.
+// An assembled buffer is a DeviceArray of exactly the plane's bytes (ensureAssembled) with a valid flag beside it.
 #include "device_handle.h"
 
 #include <algorithm>
@@ -42,9 +43,19 @@ static const char* planeSwitchOff(TwkDevice dev, int plane)
 // Frees the assembled buffers and the staging block: the getters refuse until the next assemble. Everything enqueued has run.
 void twk::dropAssembled(TwkDevice dev)
 {
-  for (int p = 0; p < TWK_PLANE_COUNT; ++p) { freeDevice(dev->d_assembled[p]); dev->assembledBytes[p] = 0; dev->assembledValid[p] = false; }
-  freeDevice(dev->d_assembledGeometry); dev->assembledGeometryBytes = 0; dev->assembledGeometryValid = false;
-  freeDevice(dev->d_assembleStage); dev->assembleStageBytes = 0;
+  for (int p = 0; p < TWK_PLANE_COUNT; ++p) { dev->d_assembled[p].release(); dev->assembledValid[p] = false; }
+  dev->d_assembledGeometry.release(); dev->assembledGeometryValid = false;
+  dev->d_assembleStage.release();
+}
+
+// An assembled buffer of exactly `bytes`: one of another size, or none, is freed once everything enqueued has run and allocated
+// again, not valid
+static int ensureAssembled(TwkDevice primary, DeviceArray<void>& buffer, bool& valid, size_t bytes)
+{
+  if (buffer && buffer.capacity() == bytes) return TWK_SUCCESS;
+  HIP_TRY(hipStreamSynchronize(primary->stream));
+  valid = false;
+  return buffer.allocate(bytes);
 }
 
 // Bytes of the geometry AOV as `columns` x height float4
@@ -78,27 +89,10 @@ static int refusePrimary(const char* name, TwkDevice primary, unsigned int plane
 // further entries of the same table. primary is active.
 static int assembleLaunch(TwkDevice primary, unsigned int planeMask, const std::vector<TwkAssemblySource>& sources, const std::vector<const void*>* geometry = nullptr)
 {
+  int rc;
   for (int p = 0; p < TWK_PLANE_COUNT; ++p)
-  {
-    if (!((planeMask >> p) & 1u)) continue;
-    const size_t bytes = planeBytes(primary, p, primary->state.resolution[0]);
-    if (primary->d_assembled[p] && primary->assembledBytes[p] == bytes) continue;
-    HIP_TRY(hipStreamSynchronize(primary->stream));
-    freeDevice(primary->d_assembled[p]); primary->assembledBytes[p] = 0; primary->assembledValid[p] = false;
-    HIP_TRY(hipMalloc(&primary->d_assembled[p], bytes));
-    primary->assembledBytes[p] = bytes;
-  }
-  if (geometry)
-  {
-    const size_t bytes = geometryBytes(primary, primary->state.resolution[0]);
-    if (!primary->d_assembledGeometry || primary->assembledGeometryBytes != bytes)
-    {
-      HIP_TRY(hipStreamSynchronize(primary->stream));
-      freeDevice(primary->d_assembledGeometry); primary->assembledGeometryBytes = 0; primary->assembledGeometryValid = false;
-      HIP_TRY(hipMalloc(&primary->d_assembledGeometry, bytes));
-      primary->assembledGeometryBytes = bytes;
-    }
-  }
+    if (((planeMask >> p) & 1u) && (rc = ensureAssembled(primary, primary->d_assembled[p], primary->assembledValid[p], planeBytes(primary, p, primary->state.resolution[0])))) return rc;
+  if (geometry && (rc = ensureAssembled(primary, primary->d_assembledGeometry, primary->assembledGeometryValid, geometryBytes(primary, primary->state.resolution[0])))) return rc;
   const AssembleShape s = assembleShape(primary);
   AssembleTable table;
   memset(&table, 0, sizeof(table));
@@ -113,7 +107,7 @@ static int assembleLaunch(TwkDevice primary, unsigned int planeMask, const std::
       {
         AssembleEntry& e = table.entry[used];
         e.source       = static_cast<const char*>(sources[(size_t) d].plane[p]) + ((layer * sourceLayer) << shift);
-        e.destination  = static_cast<char*>(primary->d_assembled[p]) + ((layer * assembledLayer) << shift);
+        e.destination  = static_cast<char*>(primary->d_assembled[p].get()) + ((layer * assembledLayer) << shift);
         e.device       = (unsigned int) d;
         e.elementShift = shift;
         e.groupShift   = assembleGroupShift(s, shift, e.source, e.destination);
@@ -156,7 +150,7 @@ static const void* ownPlane(TwkDevice dev, int plane)
 {
   switch (plane)
   {
-    case TWK_PLANE_OUTPUT:        return dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+    case TWK_PLANE_OUTPUT:        return ownOutput(dev);
     case TWK_PLANE_ALBEDO:        return dev->d_aovAlbedo;
     case TWK_PLANE_NORMAL:        return dev->d_aovNormal;
     case TWK_PLANE_MOMENTS:       return dev->d_moments;
@@ -264,12 +258,10 @@ static int assembleDevices(const char* name, TwkDevice primary, unsigned int pla
     if (stage) for (int p = 0; p < TWK_PLANE_COUNT; ++p) if ((planeMask >> p) & 1u) stageBytes += segment(planeBytes(primary, p, primary->launchWidth));
     if (stage && withGeometry) stageBytes += segment(geometryBytes(primary, primary->launchWidth));
   }
-  if (stageBytes > primary->assembleStageBytes)
+  if (stageBytes > primary->d_assembleStage.capacity())
   {
     HIP_TRY(hipStreamSynchronize(primary->stream));
-    freeDevice(primary->d_assembleStage); primary->assembleStageBytes = 0;
-    HIP_TRY(hipMalloc(&primary->d_assembleStage, stageBytes));
-    primary->assembleStageBytes = stageBytes;
+    if ((rc = primary->d_assembleStage.allocate(stageBytes))) return rc;
   }
   std::vector<TwkAssemblySource> sources((size_t) count);
   std::vector<const void*> geometry((size_t) count, nullptr);
@@ -285,7 +277,7 @@ static int assembleDevices(const char* name, TwkDevice primary, unsigned int pla
       if (!own) return refuse(TWK_ERROR_INVALID_STATE, std::string(kPlaneNames[p]) + " has no buffer on device " + std::to_string(d));
       if (!staged[(size_t) d]) { sources[(size_t) d].plane[p] = own; continue; }
       const size_t bytes = planeBytes(primary, p, primary->launchWidth);
-      char* to = static_cast<char*>(primary->d_assembleStage) + offset;
+      char* to = static_cast<char*>(primary->d_assembleStage.get()) + offset;
       if (dev->ordinal == primary->ordinal) HIP_TRY(hipMemcpyAsync(to, own, bytes, hipMemcpyDeviceToDevice, primary->stream));
       else                                  HIP_TRY(hipMemcpyPeerAsync(to, primary->ordinal, own, dev->ordinal, bytes, primary->stream));
       sources[(size_t) d].plane[p] = to;
@@ -295,7 +287,7 @@ static int assembleDevices(const char* name, TwkDevice primary, unsigned int pla
     geometry[(size_t) d] = dev->d_geometry;
     if (!staged[(size_t) d]) continue;
     const size_t bytes = geometryBytes(primary, primary->launchWidth);
-    char* to = static_cast<char*>(primary->d_assembleStage) + offset;
+    char* to = static_cast<char*>(primary->d_assembleStage.get()) + offset;
     if (dev->ordinal == primary->ordinal) HIP_TRY(hipMemcpyAsync(to, dev->d_geometry, bytes, hipMemcpyDeviceToDevice, primary->stream));
     else                                  HIP_TRY(hipMemcpyPeerAsync(to, primary->ordinal, dev->d_geometry, dev->ordinal, bytes, primary->stream));
     geometry[(size_t) d] = to;
@@ -354,7 +346,7 @@ try
   if (!primary->assembledValid[plane] || !primary->d_assembled[plane])
     return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": " + kPlaneNames[plane] + " has not been assembled since the handle's frame last changed shape");
   *dptr = primary->d_assembled[plane];
-  if (bytes) *bytes = primary->assembledBytes[plane];
+  if (bytes) *bytes = primary->d_assembled[plane].capacity();
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_assembled_device_pointer")
@@ -367,11 +359,9 @@ try
   if (!host || plane < 0 || plane >= TWK_PLANE_COUNT) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL buffer or unknown plane");
   if (!primary->assembledValid[plane] || !primary->d_assembled[plane])
     return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": " + kPlaneNames[plane] + " has not been assembled since the handle's frame last changed shape");
-  if (bytes != primary->assembledBytes[plane]) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": buffer must hold the assembled plane, " + std::to_string(primary->assembledBytes[plane]) + " bytes");
+  if (bytes != primary->d_assembled[plane].capacity()) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": buffer must hold the assembled plane, " + std::to_string(primary->d_assembled[plane].capacity()) + " bytes");
   int rc = activate(primary, name); if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(primary->stream));
-  HIP_TRY(hipMemcpy(host, primary->d_assembled[plane], bytes, hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  return copyBack(primary, name, primary->d_assembled[plane], bytes, 1, host);
 }
 TWK_CATCH("twk_read_assembled")
 
@@ -384,7 +374,7 @@ try
   if (!primary->assembledGeometryValid || !primary->d_assembledGeometry)
     return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": the geometry AOV has not been assembled since the handle's frame last changed shape or its camera, state or scene changed");
   *dptr = primary->d_assembledGeometry;
-  if (bytes) *bytes = primary->assembledGeometryBytes;
+  if (bytes) *bytes = primary->d_assembledGeometry.capacity();
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_assembled_geometry_device_pointer")
@@ -397,11 +387,9 @@ try
   if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL buffer");
   if (!primary->assembledGeometryValid || !primary->d_assembledGeometry)
     return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": the geometry AOV has not been assembled since the handle's frame last changed shape or its camera, state or scene changed");
-  if (numFloats * sizeof(float) != primary->assembledGeometryBytes) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": buffer must hold width*height*4 floats");
+  if (numFloats * sizeof(float) != primary->d_assembledGeometry.capacity()) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": buffer must hold width*height*4 floats");
   int rc = activate(primary, name); if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(primary->stream));
-  HIP_TRY(hipMemcpy(host, primary->d_assembledGeometry, primary->assembledGeometryBytes, hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  return copyBack(primary, name, primary->d_assembledGeometry, primary->d_assembledGeometry.capacity(), 1, host);
 }
 TWK_CATCH("twk_read_assembled_geometry")
 

@@ -25,25 +25,16 @@ static int resolveParameters(const char* name, const TwkCascadeResolve* rp, floa
 
 static bool sameParameters(const TwkCascade& a, const TwkCascade& b) { return a.layers == b.layers && asUint(a.start) == asUint(b.start) && asUint(a.base) == asUint(b.base); }
 
-static size_t cascadeElements(TwkDevice dev) { return (size_t) dev->launchWidth * dev->state.resolution[1]; }
+// The floats4 of the handle's layers: every layer exactly the launch indices
+static size_t cascadeElements(TwkDevice dev) { return launchIndices(dev) * (size_t) dev->cascadeK.layers; }
 
 // What an accumulate launch folds into: the handle's layers and table, or layers == nullptr with the cascade off
 CascadeOn twk::cascadeFold(TwkDevice dev)
 {
   CascadeOn c;
-  c.layers = (dev->cascadeEnabled && (size_t) dev->cascadePixels == cascadeElements(dev)) ? dev->d_cascade : nullptr;
+  c.layers = (dev->cascadeEnabled && dev->d_cascade.capacity() == cascadeElements(dev)) ? dev->d_cascade.get() : nullptr;
   c.k = dev->cascadeK;
   return c;
-}
-
-static int ensureLambda(TwkDevice dev, size_t elements)
-{
-  if (dev->d_cascadeLambda && dev->cascadeLambdaElements >= elements) return TWK_SUCCESS;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  freeDevice(dev->d_cascadeLambda); dev->cascadeLambdaElements = 0;
-  HIP_TRY(hipMalloc(&dev->d_cascadeLambda, elements * sizeof(float)));
-  dev->cascadeLambdaElements = elements;
-  return TWK_SUCCESS;
 }
 
 extern "C" {
@@ -77,19 +68,17 @@ try
   if (enable && (rc = cascadeParameters(name, cp, defaults, c, k))) return rc;
   if ((rc = activate(dev, name))) return rc; // recorded launches are rendered with the switch they were recorded under
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->resolvedValid = false;
+  dev->resolved.valid = false;
   if (!enable || !dev->cascadeEnabled || !sameParameters(c, dev->cascadeParameters)) { dropAssembled(dev); dropTemporalCascade(dev); } // assembled and temporally merged layers are of the old parameters
   if (!enable)
   {
     dev->cascadeEnabled = false;
-    freeDevice(dev->d_cascade); dev->cascadePixels = 0;
-    freeDevice(dev->d_cascadeLambda); dev->cascadeLambdaElements = 0;
-    freeDevice(dev->d_resolved); dev->resolvedWidth = dev->resolvedHeight = 0;
+    dev->d_cascade.release(); dev->d_cascadeLambda.release(); dev->resolved.release();
     return TWK_SUCCESS;
   }
   if (dev->cascadeEnabled && sameParameters(c, dev->cascadeParameters)) return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS;
   // switched on, or new parameters: zeroed layers (a buffer of its own size when the number of layers changed)
-  freeDevice(dev->d_cascade); dev->cascadePixels = 0;
+  dev->d_cascade.release();
   dev->cascadeEnabled = true; dev->cascadeParameters = c; dev->cascadeK = k;
   return dev->stateSet ? ensureStreams(dev) : TWK_SUCCESS; // allocated, zeroed, here or by the first pass after twk_set_state
 }
@@ -101,26 +90,24 @@ try
   int rc = activate(dev, "twk_read_cascade"); if (rc) return rc;
   if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_cascade: NULL buffer");
   if (!dev->cascadeEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_cascade: twk_enable_cascade(1) and twk_set_state first");
-  const size_t n = cascadeElements(dev) * (size_t) dev->cascadeK.layers;
+  const size_t n = cascadeElements(dev);
   if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_cascade: buffer must hold layers*launchWidth*height*4 floats");
-  if ((rc = ensureStreams(dev))) return rc;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_cascade, n * sizeof(float4), hipMemcpyDeviceToHost));
-  return checkDroppedPushes(dev, "twk_read_cascade");
+  if ((rc = ensureStreams(dev))) return rc; // (the layers of a handle that has not rendered yet: allocated, zeroed, only now that the call is known to read them)
+  return copyBack(dev, "twk_read_cascade", dev->d_cascade, n, sizeof(float4), host, true);
 }
 TWK_CATCH("twk_read_cascade")
 
 int twk_get_cascade_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_cascade_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_cascade_device_pointer: NULL argument");
-  if (!dev->cascadeEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_cascade_device_pointer: twk_enable_cascade(1) and twk_set_state first");
-  if ((rc = ensureStreams(dev))) return rc;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  *dptr = dev->d_cascade;
-  if (bytes) *bytes = cascadeElements(dev) * (size_t) dev->cascadeK.layers * sizeof(float4);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_cascade_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!dev->cascadeEnabled || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_cascade_device_pointer: twk_enable_cascade(1) and twk_set_state first");
+    const int rc = ensureStreams(dev); if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    pointer = dev->d_cascade; size = cascadeElements(dev) * sizeof(float4);
+    return (int) TWK_SUCCESS;
+  });
 }
 TWK_CATCH("twk_get_cascade_device_pointer")
 
@@ -155,19 +142,13 @@ try
     if (!sameParameters(c, dev->cascadeParameters)) return refuse(TWK_ERROR_INVALID_VALUE, "cp differs from the parameters the handle's layers were enabled with");
     if ((rc = ensureStreams(dev))) return rc;
     width = dev->launchWidth; height = dev->state.resolution[1];
-    if (!dev->d_resolved || dev->resolvedWidth != width || dev->resolvedHeight != height || dev->resolvedFormat != dev->outputFormat)
-    {
-      HIP_TRY(hipStreamSynchronize(dev->stream));
-      freeDevice(dev->d_resolved); dev->resolvedValid = false;
-      HIP_TRY(hipMalloc(&dev->d_resolved, (size_t) width * height * pixelBytes(dev)));
-      dev->resolvedWidth = width; dev->resolvedHeight = height; dev->resolvedFormat = dev->outputFormat;
-    }
-    layers = dev->d_cascade; resolved = dev->d_resolved;
+    if ((rc = ensurePicture(dev, dev->resolved, width, height))) return rc;
+    layers = dev->d_cascade; resolved = dev->resolved.pixels;
   }
-  if ((rc = ensureLambda(dev, (size_t) width * height * (size_t) k.layers))) return rc;
+  if ((rc = growIdle(dev, dev->d_cascadeLambda, (size_t) width * height * (size_t) k.layers))) return rc;
   launchCascadeResolve(k, kappa, static_cast<const float4*>(layers), dev->d_cascadeLambda, width, height, resolved, halfOutput(dev), dev->stream);
   HIP_TRY(hipGetLastError());
-  if (own) dev->resolvedValid = true;
+  if (own) dev->resolved.valid = true;
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_cascade_resolve")
@@ -175,13 +156,13 @@ TWK_CATCH("twk_cascade_resolve")
 int twk_get_resolved_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_resolved_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_resolved_device_pointer: NULL argument");
-  if (!dev->resolvedValid || !dev->d_resolved || dev->resolvedFormat != dev->outputFormat)
-    return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_resolved_device_pointer: no twk_cascade_resolve on the handle's own layers since they last changed shape");
-  *dptr = dev->d_resolved;
-  if (bytes) *bytes = (size_t) dev->resolvedWidth * dev->resolvedHeight * pixelBytes(dev);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_resolved_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!(pointer = currentPicture(dev, dev->resolved)))
+      return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_resolved_device_pointer: no twk_cascade_resolve on the handle's own layers since they last changed shape");
+    size = dev->resolved.count() * pixelBytes(dev);
+    return (int) TWK_SUCCESS;
+  });
 }
 TWK_CATCH("twk_get_resolved_device_pointer")
 
@@ -189,13 +170,8 @@ int twk_read_resolved(TwkDevice dev, float* rgbaHost, size_t numFloats)
 try
 {
   int rc = activate(dev, "twk_read_resolved"); if (rc) return rc;
-  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_resolved: NULL buffer");
-  if (!dev->resolvedValid || !dev->d_resolved || dev->resolvedFormat != dev->outputFormat)
-    return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_resolved: no twk_cascade_resolve on the handle's own layers since they last changed shape");
-  const size_t n = (size_t) dev->resolvedWidth * dev->resolvedHeight;
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_resolved: buffer must hold launchWidth*height*4 floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  return readPixels(dev, dev->d_resolved, rgbaHost, n, false);
+  return readBack(dev, "twk_read_resolved", {currentPicture(dev, dev->resolved), "no twk_cascade_resolve on the handle's own layers since they last changed shape", dev->resolved.count(), 0, true},
+                  rgbaHost, numFloats, 4, "launchWidth*height*4 floats");
 }
 TWK_CATCH("twk_read_resolved")
 

@@ -116,16 +116,16 @@ try
   int rc = activate(dev, "twk_gather_peak"); if (rc) return rc;
   if (!gigaLaneLoadsPerSecond || tableBytes < 128 * 1024 || tableBytes > ((size_t) 1 << 36)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_gather_peak: bad arguments");
   const unsigned int lines = (unsigned int) (tableBytes / 128);
-  ScopedDeviceBuffer<float4> table; ScopedDeviceBuffer<float> out;
-  HIP_TRY(table.allocate((size_t) lines * 8));
-  HIP_TRY(out.allocate(1));
-  launchGatherProbeFill(table.ptr, (size_t) lines * 8, lines, dev->stream);
+  DeviceArray<float4> table; DeviceArray<float> out;
+  if ((rc = table.allocate((size_t) lines * 8))) return rc;
+  if ((rc = out.allocate(1))) return rc;
+  launchGatherProbeFill(table, (size_t) lines * 8, lines, dev->stream);
   const int blocks = dev->numCUs * 6, steps = 1000; // 6 waves per SIMD, as the traversal kernel runs
-  launchGatherProbe(table.ptr, lines, 50, out.ptr, blocks, dev->stream); // warm-up: table into the caches
+  launchGatherProbe(table, lines, 50, out, blocks, dev->stream); // warm-up: table into the caches
   hipEvent_t e0, e1;
   (void) hipEventCreate(&e0); (void) hipEventCreate(&e1);
   (void) hipEventRecord(e0, dev->stream);
-  launchGatherProbe(table.ptr, lines, steps, out.ptr, blocks, dev->stream);
+  launchGatherProbe(table, lines, steps, out, blocks, dev->stream);
   (void) hipEventRecord(e1, dev->stream);
   hipError_t e = hipStreamSynchronize(dev->stream);
   float ms = 0.0f;
@@ -211,16 +211,16 @@ try
   if (!dev->stateSet) { dev->launchWidth = 1; }
   if ((rc = ensureStreams(dev))) return rc;
   refreshParams(dev);
-  ScopedDeviceBuffer<float> d_rays, d_out; ScopedDeviceBuffer<int> d_ids;
-  HIP_TRY(d_rays.allocate(numRays * 8));
-  HIP_TRY(d_out.allocate(numRays * 3));
-  HIP_TRY(d_ids.allocate(numRays * 2));
-  HIP_TRY(hipMemcpyAsync(d_rays.ptr, rays, numRays * 8 * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+  DeviceArray<float> d_rays, d_out; DeviceArray<int> d_ids;
+  if ((rc = d_rays.allocate(numRays * 8))) return rc;
+  if ((rc = d_out.allocate(numRays * 3))) return rc;
+  if ((rc = d_ids.allocate(numRays * 2))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_rays, rays, numRays * 8 * sizeof(float), hipMemcpyHostToDevice, dev->stream));
   int grid = (int) ((numRays + TWK_TRACE_BLOCK - 1) / TWK_TRACE_BLOCK);
   if (grid > dev->numCUs * TWK_TRACE_WAVES) grid = dev->numCUs * TWK_TRACE_WAVES;
-  launchTraceQuery(dev->params, d_rays.ptr, (unsigned int) numRays, anyHit, d_out.ptr, d_ids.ptr, grid, dev->stream);
-  HIP_TRY(hipMemcpyAsync(tBetaGamma, d_out.ptr, numRays * 3 * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-  HIP_TRY(hipMemcpyAsync(ids, d_ids.ptr, numRays * 2 * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+  launchTraceQuery(dev->params, d_rays, (unsigned int) numRays, anyHit, d_out, d_ids, grid, dev->stream);
+  HIP_TRY(hipMemcpyAsync(tBetaGamma, d_out, numRays * 3 * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipMemcpyAsync(ids, d_ids, numRays * 2 * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
   HIP_TRY(hipStreamSynchronize(dev->stream));
   return checkDroppedPushes(dev, "twk_trace_rays");
 }
@@ -240,11 +240,11 @@ try
   if (!dev->stateSet) { dev->launchWidth = 1; }
   const size_t pixels = (size_t) dev->launchWidth * (size_t) dev->state.resolution[1];
   if ((rc = ensureStreams(dev, (int) std::min<size_t>((n + pixels - 1) / pixels, (size_t) 1 << 30)))) return rc;
-  if ((size_t) dev->allocatedPaths < n) return twkSetError(TWK_ERROR_OUT_OF_MEMORY, "twk_debug_trace_queue: path streams too small");
+  if (dev->d_streamBlock.capacity() < n) return twkSetError(TWK_ERROR_OUT_OF_MEMORY, "twk_debug_trace_queue: path streams too small");
   dev->lastPassCount = 0; // the streams of the last pass are overwritten below
   refreshParams(dev);
   LaunchParams p = dev->params;
-  p.numPaths = dev->allocatedPaths; p.batchCount = 1; p.firstHit = nullptr; p.firstHitInstance = nullptr; p.pathTime = nullptr;
+  p.numPaths = (int) dev->d_streamBlock.capacity(); p.batchCount = 1; p.firstHit = nullptr; p.firstHitInstance = nullptr; p.pathTime = nullptr;
   p.stats = dev->statsEnabled ? dev->d_stats : nullptr; // twk_stats_enable: visit counts and the number of rays that overflowed the LDS stack (tests/test_gpu_big_scenes.py)
   // the rays of one bounce: radiance rays in queue 1, the shadow rays "emitted by shade 0" in the shadow queue
   std::vector<float4> org(n), dir(n);
@@ -371,14 +371,14 @@ try
   int rc = activate(dev, "twk_debug_math"); if (rc) return rc;
   if (op < 0 || op > 9 || !x || !out || ((op == 3 || op == 9) && !y)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_debug_math: bad arguments");
   if (n == 0) return TWK_SUCCESS;
-  ScopedDeviceBuffer<float> dx, dy, dout;
-  HIP_TRY(dx.allocate(n));
-  HIP_TRY(dy.allocate(n));
-  HIP_TRY(dout.allocate(n));
-  HIP_TRY(hipMemcpyAsync(dx.ptr, x, n * sizeof(float), hipMemcpyHostToDevice, dev->stream));
-  HIP_TRY(hipMemcpyAsync(dy.ptr, y ? y : x, n * sizeof(float), hipMemcpyHostToDevice, dev->stream));
-  launchMathTap(op, dx.ptr, dy.ptr, dout.ptr, n, dev->stream);
-  HIP_TRY(hipMemcpyAsync(out, dout.ptr, n * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+  DeviceArray<float> dx, dy, dout;
+  if ((rc = dx.allocate(n))) return rc;
+  if ((rc = dy.allocate(n))) return rc;
+  if ((rc = dout.allocate(n))) return rc;
+  HIP_TRY(hipMemcpyAsync(dx, x, n * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+  HIP_TRY(hipMemcpyAsync(dy, y ? y : x, n * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+  launchMathTap(op, dx, dy, dout, n, dev->stream);
+  HIP_TRY(hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
   HIP_TRY(hipStreamSynchronize(dev->stream));
   return TWK_SUCCESS;
 }

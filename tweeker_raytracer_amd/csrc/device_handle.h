@@ -1,6 +1,12 @@
 // The handle behind the C ABI (TwkDevice_t) and what the host files that implement the ABI share: device_api.hip (handle, setters,
 // readers), device_scene.hip (scene and build), device_pass.hip (streams and the wavefront pass in its three forms: uniform, listed, planned — shade_device.h "the samples of a thread"), device_post.hip (compositor,
 // tonemap, denoiser, noise estimate), device_temporal.hip (the temporal merge, plain and rectified), device_adaptive.hip (adaptive sampling: switch, select, readers), device_cascade.hip (the firefly cascade: switch, layers, resolve), device_temporal_cascade.hip (the cascade's layers through the temporal merge), device_assemble.hip (assembling a tiled frame, with or without its geometry AOV), device_debug.hip (measurement and parity taps). Internal: no kernel file includes it.
+// Device memory has one home. Every buffer the handle allocates is a DeviceArray member (device_buffers.h: pointer + capacity in
+// elements, freed by its destructor), so a new buffer is one member and one ensure() where it is used, and twk_device_destroy
+// lists none. A result picture kept for readers is a DevicePicture (ensurePicture, currentPicture). "The handle's own X, or
+// nothing" is ownOutput / ownAlbedo / ownNormal / ownMoments / ownGeometry / ownSampleCounts. Every reader ends in readBack (or
+// its tail copyBack), every twk_get_*_device_pointer is getPointer. Borrowed pointers (d_outputExternal) and the pinned, mapped
+// h_dropped / d_dropped stay plain fields.
 #pragma once
 #include "device_types.h"
 #include "bvh_build.h"
@@ -13,7 +19,7 @@
 #include "temporal_cascade_device.h"
 #include "temporal_rectify_device.h"
 #include "assemble_device.h"
-#include "error_state.h"
+#include "device_buffers.h"
 
 #include <string>
 #include <vector>
@@ -63,14 +69,6 @@ void launchAssemble(const AssembleShape& s, const AssembleTable& table, int coun
 
 using namespace twk;
 
-#define HIP_TRY(call)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return twkSetError((e_ == hipErrorOutOfMemory) ? TWK_ERROR_OUT_OF_MEMORY : TWK_ERROR_HIP,    \
-                         std::string(#call) + " failed: " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + std::to_string(__LINE__) + ")"); \
-  } while (0)
-
 static_assert(sizeof(TwkCameraDefinition) == 48, "CameraDefinition is 48 B (camera_definition.h:34-40)");
 static_assert(sizeof(TwkLightDefinition) == 80, "LightDefinition is 80 B (light_definition.h:42-59)");
 static_assert(sizeof(TwkTriangleAttributes) == 48, "TriangleAttributes is 48 B (vertex_attributes.h:34-40)");
@@ -108,6 +106,16 @@ struct TileEntriesKey
 #define TWK_STATS_WORDS 192 // device words of TwkLaunchStats: [0, 24) traversal + shade totals, [24, 96) the shade phases (shade_device.h PhaseScope); twice: the time view's scratch copy
 #define TWK_COUNTER_WORDS (TWK_COUNTERS_PER_DEPTH * (TWK_MAX_DEPTH + 2)) // one lane's counter block
 
+// A result picture the handle keeps for its readers: width x height pixels in the output format it was made in, `valid` once a
+// call has written it (ensurePicture and currentPicture, below the handle)
+struct DevicePicture
+{
+  DeviceArray<void> pixels; int width = 0, height = 0, format = TWK_OUTPUT_FLOAT4; bool valid = false;
+  size_t count() const { return (size_t) width * height; }
+  bool shaped(int w, int h, int f) const { return pixels != nullptr && width == w && height == h && format == f; }
+  void release() { pixels.release(); width = height = 0; valid = false; }
+};
+
 struct TwkDevice_t
 {
   int ordinal = 0, index = 0, count = 1, miss = 1;
@@ -130,108 +138,108 @@ struct TwkDevice_t
   TwkBuildInfo buildInfo;
 
   // device memory
-  float* d_camera = nullptr;
-  DevLight* d_lights = nullptr;
-  DevMaterial* d_materials = nullptr; int materialCapacity = 0;
-  float* d_attributes = nullptr; unsigned int* d_indices = nullptr;
-  BvhNode* d_nodes = nullptr; BvhNode* d_wideNodes = nullptr /* build-time only: full-precision wide nodes, freed once quantised */; float4* d_wideQ = nullptr; float4* d_triangles = nullptr; float4* d_shadeTriangles = nullptr; DevInstance* d_instances = nullptr;
+  DeviceArray<float> d_camera;
+  DeviceArray<DevLight> d_lights;
+  DeviceArray<DevMaterial> d_materials;
+  DeviceArray<float> d_attributes; DeviceArray<unsigned int> d_indices;
+  DeviceArray<BvhNode> d_nodes, d_wideNodes /* build-time only: full-precision wide nodes, freed once quantised */; DeviceArray<float4> d_wideQ, d_triangles, d_shadeTriangles; DeviceArray<DevInstance> d_instances;
   bool directSmallLeaves = true; /* TWK_DIRECT_SMALL_LEAVES=0: A/B */ bool costedCuts = true; /* TWK_COSTED_CUTS=0: A/B */ bool fusedPrimary = true; /* TWK_FUSED_PRIMARY=0: A/B */ bool tileEntries = true; /* TWK_TILE_ENTRIES=0: A/B */ bool wideRoot = true; /* TWK_WIDE_ROOT=0: A/B */ int wideRoot1 = 0, wideRoot2 = TWK_BVH_SENTINEL; size_t wideNodesTotal = 0;
-  int4* d_tileEntries = nullptr; size_t tileEntriesCapacity = 0; TileEntriesKey tileEntriesKey = {}; uint64_t buildSerial = 0; // entry points of the primary rays (trace_kernels.hip tileEntryKernel) and what they were built for
-  float4* d_topNodes = nullptr; float4* d_topNodes7 = nullptr; bool topCache = true; int traceWavesForced = 0 /* TWK_TRACE_WAVES_RUNTIME: 6 or 7, 0 = by scene */; // TWK_TOP_CACHE=0 turns the LDS top-of-tree cache off (A/B)
-  float4* d_texels[3] = {nullptr, nullptr, nullptr};
-  float* d_envCDF_U = nullptr; float* d_envCDF_V = nullptr;
+  DeviceArray<int4> d_tileEntries; TileEntriesKey tileEntriesKey = {}; uint64_t buildSerial = 0; // entry points of the primary rays (trace_kernels.hip tileEntryKernel) and what they were built for
+  DeviceArray<float4> d_topNodes, d_topNodes7; bool topCache = true; int traceWavesForced = 0 /* TWK_TRACE_WAVES_RUNTIME: 6 or 7, 0 = by scene */; // TWK_TOP_CACHE=0 turns the LDS top-of-tree cache off (A/B)
+  DeviceArray<float4> d_texels[3];
+  DeviceArray<float> d_envCDF_U, d_envCDF_V;
   int tlasRoot = 0;
   size_t totalNodes = 0, totalTriangles = 0;
 
   // per-resolution streams
-  int allocatedPixels = 0;
-  void* d_streamBlock = nullptr; // one allocation carved into the SoA streams
+  DeviceArray<void> d_streamBlock; // one allocation carved into the SoA streams; its capacity: the paths of the largest pass it holds
   // output and AOV running means: RGBA32F, or RGBA16F in the same (float4-typed) pointers when outputFormat is TWK_OUTPUT_HALF4
   int outputFormat = TWK_OUTPUT_FLOAT4; // twk_set_output_format (≙ Optix7Gui USE_FP32_OUTPUT, app_config.h:57-59)
-  float4* d_outputInternal = nullptr;
+  DeviceArray<float4> d_outputInternal; // its capacity in pixels is what the other per-launch-index buffers grow to
   float4* d_outputExternal = nullptr; size_t outputExternalBytes = 0;
   bool outputFrame = false; // the external buffer is a shared full frame (twk_set_shared_frame)
-  unsigned int* d_counters = nullptr;
-  unsigned long long* d_stats = nullptr;
+  DeviceArray<unsigned int> d_counters;
+  DeviceArray<unsigned long long> d_stats;
   unsigned int* h_dropped = nullptr; unsigned int* d_dropped = nullptr; // pinned + device-mapped: LaunchParams::droppedPushes
-  int* d_spill = nullptr; size_t spillLanes = 0;
+  DeviceArray<int> d_spill;
   bool packedQueue = true; // TWK_PACKED_QUEUE=0: A/B
   bool slimStreams = true; // TWK_SLIM_STREAMS=0: A/B (device_types.h LaunchParams::slimSlotBits)
   uint64_t shadeBuilds[2] = {0, 0}; // the shadeKernel builds launched since the last reset, by launcher index (twk_debug_shade_builds)
   int shadeSort = 1;      // TWK_SHADE_SORT=0: slot order (A/B); 1: class order in every launch but the first of a pass; 2: in the first too
-  float4* d_firstHit = nullptr; int* d_firstHitInstance = nullptr;
+  DeviceArray<float4> d_firstHit; DeviceArray<int> d_firstHitInstance;
   // denoiser AOVs (Optix7Gui raygeneration.cu:125-164): per-path values of a pass and their running means per launch index
   bool aovEnabled = false; int shaderVariant = TWK_SHADERS_RTIGO3;
   bool nextEventEstimation = true, debugExceptions = false; // twk_set_next_event_estimation / twk_set_debug_exceptions (≙ shaders/config.h:50-56)
-  bool timeView = false; float* d_pathTime = nullptr; int timePaths = 0; // twk_set_time_view
-  float4* d_pathAlbedo = nullptr; float4* d_pathNormal = nullptr; int aovPaths = 0;
-  float4* d_aovAlbedo = nullptr; float4* d_aovNormal = nullptr; int aovPixels = 0;
+  bool timeView = false; DeviceArray<float> d_pathTime; // twk_set_time_view
+  DeviceArray<float4> d_pathAlbedo, d_pathNormal;
+  DeviceArray<float4> d_aovAlbedo, d_aovNormal;
   // twk_enable_moments: luminance moments (mean, M2, n, 0) of the samples per launch index, always f32 (LaunchParams::moments)
-  bool momentsEnabled = false; float4* d_moments = nullptr; int momentsPixels = 0;
+  bool momentsEnabled = false; DeviceArray<float4> d_moments;
   unsigned int sampleOffset = 0; // twk_set_sample_offset (LaunchParams::sampleOffset)
-  // twk_enable_cascade: the firefly cascade's layers, [cascade.layers][cascadePixels] float4 with cascadePixels = launchWidth x height
-  // exactly (the layer stride), always f32; the resolve's lambda stream (cascadeLambdaElements floats, shared by both forms) and the
-  // internal resolved picture of the own-buffer form in the output format it was resolved in
+  // twk_enable_cascade: the firefly cascade's layers, [cascade.layers][launchWidth x height] float4, exactly that many (the layer
+  // stride), always f32; the resolve's lambda stream (floats, shared by both forms) and the internal resolved picture of the
+  // own-buffer form
   bool cascadeEnabled = false; TwkCascade cascadeParameters = {TWK_CASCADE_LAYERS, TWK_CASCADE_START, TWK_CASCADE_BASE}; CascadeConstants cascadeK = {};
-  float4* d_cascade = nullptr; int cascadePixels = 0;
-  float* d_cascadeLambda = nullptr; size_t cascadeLambdaElements = 0;
-  void* d_resolved = nullptr; int resolvedWidth = 0, resolvedHeight = 0, resolvedFormat = TWK_OUTPUT_FLOAT4; bool resolvedValid = false;
+  DeviceArray<float4> d_cascade;
+  DeviceArray<float> d_cascadeLambda;
+  DevicePicture resolved;
   // twk_enable_geometry: the geometry AOV (world position, instance + 1) per launch index, always f32; geometryValid: rendered by
   // twk_render_geometry since the last change of camera, state or scene
-  bool geometryEnabled = false; float4* d_geometry = nullptr; int geometryPixels = 0; bool geometryValid = false;
+  bool geometryEnabled = false; DeviceArray<float4> d_geometry; bool geometryValid = false;
   // twk_temporal_accumulate, own-buffer form: two sets of three f32 streams (colour, moments, geometry) — the set temporalKept holds
-  // what the last call kept (its camera: temporalCamera), the other receives this call's — and the merged colour in the output format
-  float4* d_temporal[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; void* d_temporalColour = nullptr;
-  int temporalWidth = 0, temporalHeight = 0, temporalFormat = TWK_OUTPUT_FLOAT4, temporalKept = 0; bool temporalHasHistory = false, temporalValid = false;
+  // what the last call kept (its camera: temporalCamera), the other receives this call's — and the merged colour, the picture
+  // whose shape the streams share
+  DeviceArray<float4> d_temporal[2][3]; DevicePicture temporalColour;
+  int temporalKept = 0; bool temporalHasHistory = false;
   TwkCameraDefinition temporalCamera;
   // twk_temporal_accumulate_rectified (temporal_rectify_device.h): the two scratch streams its first launch writes and its second
-  // reads, rectifyPixels float4 each, shared by the explicit and the own-buffer form; and the own-buffer form's trust plane, one
+  // reads, shared by the explicit and the own-buffer form; and the own-buffer form's trust plane, one
   // float per pixel of the temporal result, valid while the last own-buffer merge was a rectified one. Freed by dropTemporal.
-  float4* d_rectify[2] = {nullptr, nullptr}; size_t rectifyPixels = 0;
-  float* d_temporalTrust = nullptr; bool temporalTrustValid = false;
+  DeviceArray<float4> d_rectify[2];
+  DeviceArray<float> d_temporalTrust; bool temporalTrustValid = false;
   // twk_temporal_enable_cascade: while temporalCascade is set the own-buffer twk_temporal_accumulate also merges the handle's cascade
   // layers (temporal_cascade_device.h) with the same previous geometry and camera, into two sets of [temporalCascadeLayers]
-  // [temporalCascadePixels] float4 — the set temporalCascadeKept holds what the last call kept, the other receives this call's.
+  // [pixels of the frame] float4 — the set temporalCascadeKept holds what the last call kept, the other receives this call's.
   // Dropped with the temporal history (dropTemporal) and by twk_enable_cascade off or with new parameters.
-  bool temporalCascade = false; float4* d_temporalCascade[2] = {nullptr, nullptr}; size_t temporalCascadePixels = 0;
+  bool temporalCascade = false; DeviceArray<float4> d_temporalCascade[2];
   int temporalCascadeLayers = 0, temporalCascadeKept = 0; bool temporalCascadeHasHistory = false, temporalCascadeValid = false;
   int lastPassCount = 0, lastPassPixels = 0; // samples per launch index and launch indices of the last pass, while its pathRadiance stream still holds them (twk_debug_read_path_radiance); 0: none
-  // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) in the output format it was
-  // filtered in, and the four f32 streams of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h)
-  void* d_denoised = nullptr; int denoisedWidth = 0, denoisedHeight = 0, denoisedFormat = TWK_OUTPUT_FLOAT4; bool denoisedValid = false;
-  float4* d_denoiseStreams = nullptr; size_t denoiseStreamPixels = 0;
+  // twk_denoise: the internal denoised picture (≙ m_d_denoisedBuffer, Optix7Gui Application.cpp:2478) and the four f32 streams
+  // of the filter (colour ping, colour pong, normal guide, albedo guide; denoise_device.h) in one array
+  DevicePicture denoised;
+  DeviceArray<float4> d_denoiseStreams;
   // twk_estimate_noise: the summary the kernel adds into (noise_device.h), zeroed on the stream before each launch; noiseValid: an estimate has been issued
-  TwkNoiseSummary* d_noise = nullptr; bool noiseValid = false;
+  DeviceArray<TwkNoiseSummary> d_noise; bool noiseValid = false;
   // twk_enable_adaptive: per launch index the iteration its next adaptive sample uses (d_sampleCounts) and the ascending list of
   // the launch indices the last twk_adaptive_select chose (d_active, numActive of them), both launchWidth x height words, and the
-  // select's scan scratch (adaptive_device.h adaptiveScratchBytes of adaptiveScratchElements elements; also the explicit form's).
+  // select's scan scratch (adaptive_device.h adaptiveScratchBytes of as many elements as its capacity says; also the explicit form's).
   //   uniformNext     the index after the last iteration a flushed twk_launch rendered
   //   countsCurrent   d_sampleCounts says what the picture holds; else it is filled with uniformNext before it is read
   //   adaptiveStarted an adaptive pass has run since the last restart: the picture is no longer uniform, twk_launch(i != 0) is refused
   //   activeValid     d_active is the list of a select that nothing has invalidated since
-  bool adaptiveEnabled = false; unsigned int* d_sampleCounts = nullptr; unsigned int* d_active = nullptr; int adaptivePixels = 0;
-  void* d_adaptiveScratch = nullptr; size_t adaptiveScratchElements = 0;
+  bool adaptiveEnabled = false; DeviceArray<unsigned int> d_sampleCounts, d_active;
+  DeviceArray<void> d_adaptiveScratch;
   unsigned int uniformNext = 0, numActive = 0; bool countsCurrent = false, adaptiveStarted = false, activeValid = false;
-  // twk_adaptive_plan, own-buffer form: the plan's list and path offsets (adaptive_plan_device.h) in buffers of their own, planElements
-  // and planElements + 1 words, so that a plan leaves the select's list what it is. The plan's scratch is d_adaptiveScratch, grown to
-  // adaptivePlanScratchBytes of adaptiveScratchElements elements (never less than the select's): adaptiveScratchPlan. planValid: d_planActive / d_planOffsets are the plan of a call that
+  // twk_adaptive_plan, own-buffer form: the plan's list and path offsets (adaptive_plan_device.h) in buffers of their own, n
+  // and n + 1 words, so that a plan leaves the select's list what it is. The plan's scratch is d_adaptiveScratch, grown to
+  // adaptivePlanScratchBytes of its elements (never less than the select's): adaptiveScratchPlan. planValid: d_planActive / d_planOffsets are the plan of a call that
   // nothing has invalidated since — what drops a list drops it, a select does, and the planned pass that renders it does (the
   // counts advance in the pass, so a plan is rendered once).
-  unsigned int* d_planActive = nullptr; unsigned int* d_planOffsets = nullptr; size_t planElements = 0;
+  DeviceArray<unsigned int> d_planActive, d_planOffsets;
   bool adaptiveScratchPlan = false;
   unsigned int planActive = 0, planPaths = 0; bool planValid = false;
   // twk_assemble / twk_assemble_devices with this handle as primary: the assembled W x H buffer of every plane (d_assembled[plane],
-  // in the output format / with the cascade layers it was allocated for; assembledValid: assembled since it was allocated), the
+  // of exactly the bytes of the output format / the cascade layers it was allocated for; assembledValid: assembled since it was allocated), the
   // staging block of the peers that cannot be read directly, and the two events that order the streams without a host
   // synchronisation: assembleReady is recorded on this handle's stream as a source, assembleDone on it as primary.
-  void* d_assembled[TWK_PLANE_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t assembledBytes[TWK_PLANE_COUNT] = {0, 0, 0, 0, 0, 0};
+  DeviceArray<void> d_assembled[TWK_PLANE_COUNT];
   bool assembledValid[TWK_PLANE_COUNT] = {false, false, false, false, false, false};
-  void* d_assembleStage = nullptr; size_t assembleStageBytes = 0; bool assembleStage = false; // TWK_ASSEMBLE_STAGE=1: every source is staged (tests both paths on one GPU)
+  DeviceArray<void> d_assembleStage; bool assembleStage = false; // TWK_ASSEMBLE_STAGE=1: every source is staged (tests both paths on one GPU)
   hipEvent_t assembleReady = nullptr, assembleDone = nullptr;
   // twk_assemble_with_geometry / twk_assemble_devices_with_geometry: the assembled W x H geometry AOV, float4. It is no seventh
   // plane (TWK_PLANE_COUNT stays 6): freed with the other assembled buffers (dropAssembled), and stale (assembledGeometryValid
   // false, the buffer kept) once this handle's camera, state or scene changes — staleGeometry, which is what clears geometryValid
-  void* d_assembledGeometry = nullptr; size_t assembledGeometryBytes = 0; bool assembledGeometryValid = false;
+  DeviceArray<void> d_assembledGeometry; bool assembledGeometryValid = false;
   int denoiseGeometryLdsMaxStep = 16; // the same border for the GEO builds (twk_denoise_geometry, four streams per tap): staged also wins at steps 8 and 16, by 0.04 ms each at 1080p (profiles/r20_denoise_geometry.md); steps above 16 are not measured and stay direct; TWK_DENOISE_LDS_MAX_STEP sets both
   int denoiseLdsMaxStep = 4; // levels of a step up to this run the LDS-staged build, larger steps the direct-load build (measured per step: DESIGN.md 4.3); TWK_DENOISE_LDS_MAX_STEP (A/B): 0 = every level direct, 128 = every level staged
   bool captureFirstHits = false;
@@ -246,7 +254,6 @@ struct TwkDevice_t
   size_t streamBudgetBytes = 0; // TWK_STREAM_BUDGET_MB: cap on the path streams of one pass (0 = device memory is the limit)
   unsigned int pendingFirst = 0;
   int   pendingCount = 0;
-  int   allocatedPaths = 0;
 
   // Pass lanes: a wavefront pass may be cut into up to TWK_MAX_LANES independent sub-passes over disjoint path ranges, each a
   // chain of generate / trace / shade launches on a stream of its own (lane 0 = `stream`), joined before the accumulate
@@ -267,8 +274,6 @@ struct TwkDevice_t
 // The camera, the state or the scene changed: the handle's geometry AOV and the geometry it assembled as a primary are of the old one
 inline void staleGeometry(TwkDevice dev) { dev->geometryValid = false; dev->assembledGeometryValid = false; }
 
-template<typename T> inline void freeDevice(T*& p) { if (p) { (void) hipFree(p); p = nullptr; } }
-
 // Bytes of one output / AOV pixel in the handle's output format: RGBA32F 16, RGBA16F 8 (Optix7Gui Half4)
 inline size_t pixelBytes(int format) { return (format == TWK_OUTPUT_HALF4) ? 8 : sizeof(float4); }
 inline size_t pixelBytes(TwkDevice dev) { return pixelBytes(dev->outputFormat); }
@@ -277,6 +282,49 @@ inline bool halfOutput(TwkDevice dev) { return dev->outputFormat == TWK_OUTPUT_H
 inline size_t outputPixels(TwkDevice dev)
 {
   return (size_t) ((dev->d_outputExternal && dev->outputFrame) ? dev->state.resolution[0] : dev->launchWidth) * dev->state.resolution[1];
+}
+
+// The handle's launch indices: the elements of each of its per-launch-index buffers
+inline size_t launchIndices(TwkDevice dev) { return (size_t) dev->launchWidth * dev->state.resolution[1]; }
+
+// "The handle's own X, or nothing": the stream when its switch is on and it holds at least n elements, else nullptr. What else a
+// caller asks of it (geometryValid, "a packed tile buffer is no picture") is the caller's check, with its own text.
+template<typename T> inline T* ownStream(bool enabled, const DeviceArray<T>& stream, size_t n) { return (enabled && stream.holds(n)) ? stream.get() : nullptr; }
+inline float4* ownAlbedo(TwkDevice dev, size_t n) { return ownStream(dev->aovEnabled, dev->d_aovAlbedo, n); }
+inline float4* ownNormal(TwkDevice dev, size_t n) { return ownStream(dev->aovEnabled, dev->d_aovNormal, n); }
+inline float4* ownMoments(TwkDevice dev, size_t n) { return ownStream(dev->momentsEnabled, dev->d_moments, n); }
+inline float4* ownGeometry(TwkDevice dev, size_t n) { return ownStream(dev->geometryEnabled, dev->d_geometry, n); }
+inline unsigned int* ownSampleCounts(TwkDevice dev, size_t n) { return ownStream(dev->adaptiveEnabled, dev->d_sampleCounts, n); }
+// ... and the buffer the handle accumulates into, the caller's or its own, once the internal one holds n pixels (it has no switch)
+inline float4* ownOutput(TwkDevice dev, size_t n = 0)
+{
+  if (dev->d_outputInternal.capacity() < n) return nullptr;
+  return dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal.get();
+}
+
+// Grows a scratch array that launches on the handle's stream may still use: everything enqueued runs before it is freed
+template<typename T> inline int growIdle(TwkDevice dev, DeviceArray<T>& array, size_t count, size_t bytes = 0)
+{
+  if (array.holds(count)) return TWK_SUCCESS;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return array.allocate(count, false, nullptr, bytes);
+}
+
+// `picture` as width x height pixels of the handle's output format. One of another shape or format (compared exactly, not "large
+// enough"), or none, is freed once everything enqueued has run and allocated again, not valid.
+inline int ensurePicture(TwkDevice dev, DevicePicture& picture, int width, int height)
+{
+  if (picture.shaped(width, height, dev->outputFormat)) return TWK_SUCCESS;
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  picture.release();
+  const int rc = picture.pixels.allocate((size_t) width * height * pixelBytes(dev)); if (rc) return rc;
+  picture.width = width; picture.height = height; picture.format = dev->outputFormat;
+  return TWK_SUCCESS;
+}
+// The picture for a reader: nullptr unless a call has written it and it is in the current output format
+inline void* currentPicture(TwkDevice dev, const DevicePicture& picture)
+{
+  return (picture.valid && picture.format == dev->outputFormat) ? picture.pixels.get() : nullptr;
 }
 
 // Whether the byte ranges [a, a + aBytes) and [b, b + bBytes) share a byte; a NULL pointer overlaps nothing
@@ -288,13 +336,11 @@ inline bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
 }
 inline bool overlaps(const void* a, const void* b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
 
-// Scratch device allocation of one call; freed on every return path.
-template<typename T> struct ScopedDeviceBuffer
-{
-  T* ptr = nullptr;
-  ~ScopedDeviceBuffer() { if (ptr) (void) hipFree(ptr); }
-  hipError_t allocate(size_t count) { return hipMalloc(&ptr, count * sizeof(T)); }
-};
+// What a reader copies to the host: `count` elements of `elementBytes` at `source`; source nullptr: there is nothing to read and
+// the call is refused with `refusal`. elementBytes 0: pixels of the output format, widened exactly to RGBA32F (readPixels).
+// ownShape: the count is the source's own (a result's width x height), so that without a source there is no size to hold the
+// caller's against and the refusal comes first; else the count is the state's, and the caller's size is checked first.
+struct Readback { const void* source; const char* refusal; size_t count, elementBytes; bool ownShape; };
 
 // Helpers more than one of the files needs; each is defined in the file that owns it
 namespace twk {
@@ -312,6 +358,8 @@ int ensureStreamsForPaths(TwkDevice dev, size_t paths);
 // device_api.hip
 int setSwitch(TwkDevice dev, const char* where, bool TwkDevice_t::*flag, int enable);
 int readPixels(TwkDevice dev, const void* src, void* host, size_t numPixels, bool raw);
+int copyBack(TwkDevice dev, const char* name, const void* source, size_t count, size_t elementBytes, void* host, bool dropped = false);
+int readBack(TwkDevice dev, const char* name, const Readback& r, void* host, size_t given, size_t unit, const char* sizeText, bool dropped = false);
 // device_temporal.hip
 void dropTemporal(TwkDevice dev);
 int temporalParameters(const char* name, const TwkTemporal* tp, TemporalConstants& k);
@@ -324,4 +372,17 @@ const char* temporalCascadeRefusal(TwkDevice dev);
 int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust = nullptr);
 // device_assemble.hip
 void dropAssembled(TwkDevice dev);
+}
+
+// One twk_get_*_device_pointer: source(pointer, size) is the entry point's own check and answer, run on the active handle once
+// the argument is known to be there; what it returns but TWK_SUCCESS is the call's refusal
+template<typename Source> inline int getPointer(TwkDevice dev, const char* name, void** dptr, size_t* bytes, const Source& source)
+{
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL argument");
+  void* pointer = nullptr; size_t size = 0;
+  if ((rc = source(pointer, size))) return rc;
+  *dptr = pointer;
+  if (bytes) *bytes = size;
+  return TWK_SUCCESS;
 }

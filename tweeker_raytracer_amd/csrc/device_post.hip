@@ -1,5 +1,6 @@
 // What runs on finished pictures: compositor, tonemapper, the a-trous denoiser (≙ optixDenoiserInvoke, Optix7Gui
-// Application.cpp:2478) and the noise estimate. The temporal merge is device_temporal.hip's.
+// Application.cpp:2478) and the noise estimate. The temporal merge is device_temporal.hip's. The internal denoised picture is a
+// DevicePicture, the filter's streams a scratch array grown by growIdle (device_handle.h).
 #include "device_handle.h"
 
 #include <cmath>
@@ -37,11 +38,11 @@ TWK_CATCH("twk_compositor_half")
 static int tonemap(TwkDevice dev, const TwkTonemapper* tm, const void* src, bool half, size_t numPixels, unsigned char* rgb8Host)
 {
   if (numPixels == 0) return TWK_SUCCESS;
-  ScopedDeviceBuffer<unsigned char> ldr;
-  HIP_TRY(ldr.allocate(numPixels * 3));
-  launchTonemap(src, half, ldr.ptr, numPixels, *tm, dev->stream);
+  DeviceArray<unsigned char> ldr;
+  const int rc = ldr.allocate(numPixels * 3); if (rc) return rc;
+  launchTonemap(src, half, ldr, numPixels, *tm, dev->stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(rgb8Host, ldr.ptr, numPixels * 3, hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipMemcpyAsync(rgb8Host, ldr, numPixels * 3, hipMemcpyDeviceToHost, dev->stream));
   HIP_TRY(hipStreamSynchronize(dev->stream));
   return TWK_SUCCESS;
 }
@@ -54,9 +55,9 @@ try
   if (!(tm->gamma > 0.0f) || !(tm->whitePoint > 0.0f)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: gamma and whitePoint must be positive");
   if (rgbaDevice) return tonemap(dev, tm, rgbaDevice, false, numPixels, rgb8Host);
   // the handle's own buffer, in whatever format it holds
-  const float4* src = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+  const float4* src = ownOutput(dev);
   if (!src || !dev->stateSet) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_tonemap: nothing has been rendered");
-  if (numPixels != (size_t) dev->launchWidth * dev->state.resolution[1]) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: numPixels must be launchWidth*height for the handle's own buffer");
+  if (numPixels != launchIndices(dev)) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_tonemap: numPixels must be launchWidth*height for the handle's own buffer");
   return tonemap(dev, tm, src, halfOutput(dev), numPixels, rgb8Host);
 }
 TWK_CATCH("twk_tonemap")
@@ -145,28 +146,21 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     if (albedo || normal || moments || geometry) return refuse(TWK_ERROR_INVALID_VALUE, "guides without a beauty buffer (pass every input, or none for the handle's own buffers)");
     if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
     if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture; denoise the composited frame");
-    beauty = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
+    beauty = ownOutput(dev);
     if (!beauty) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
     width = dev->launchWidth; height = dev->state.resolution[1];
+    const size_t n = launchIndices(dev);
     if (kind != TWK_DENOISER_RGB)
     {
-      if (!dev->aovEnabled || !dev->d_aovAlbedo || !dev->d_aovNormal || (size_t) dev->aovPixels < (size_t) width * height)
-        return refuse(TWK_ERROR_INVALID_STATE, "a guided inputKind on the handle's own buffers needs a render with twk_enable_aov(1)");
+      if (!ownAlbedo(dev, n) || !ownNormal(dev, n)) return refuse(TWK_ERROR_INVALID_STATE, "a guided inputKind on the handle's own buffers needs a render with twk_enable_aov(1)");
       albedo = dev->d_aovAlbedo;
       if (kind == TWK_DENOISER_RGB_ALBEDO_NORMAL) normal = dev->d_aovNormal;
     }
-    if (sampled)
-    {
-      if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < (size_t) width * height)
-        return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
-      moments = dev->d_moments;
-    }
+    if (sampled && !(moments = ownMoments(dev, n))) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
     if (dg)
     {
-      if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < (size_t) width * height)
-        return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+      if (!(geometry = ownGeometry(dev, n))) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
       if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
-      geometry = dev->d_geometry;
     }
   }
   else
@@ -196,14 +190,8 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
   void* target = denoised;
   if (!target)
   {
-    if (!dev->d_denoised || dev->denoisedWidth != width || dev->denoisedHeight != height || dev->denoisedFormat != dev->outputFormat)
-    {
-      HIP_TRY(hipStreamSynchronize(dev->stream));
-      freeDevice(dev->d_denoised); dev->denoisedValid = false;
-      HIP_TRY(hipMalloc(&dev->d_denoised, bytes));
-      dev->denoisedWidth = width; dev->denoisedHeight = height; dev->denoisedFormat = dev->outputFormat;
-    }
-    target = dev->d_denoised;
+    if ((rc = ensurePicture(dev, dev->denoised, width, height))) return rc;
+    target = dev->denoised.pixels;
   }
   if (dn->iterations == 0 || dn->blendFactor == 1.0f)
   {
@@ -211,13 +199,7 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
   }
   else
   {
-    if (dev->denoiseStreamPixels < numPixels)
-    {
-      HIP_TRY(hipStreamSynchronize(dev->stream));
-      freeDevice(dev->d_denoiseStreams); dev->denoiseStreamPixels = 0;
-      HIP_TRY(hipMalloc(&dev->d_denoiseStreams, numPixels * 4 * sizeof(float4)));
-      dev->denoiseStreamPixels = numPixels;
-    }
+    if ((rc = growIdle(dev, dev->d_denoiseStreams, numPixels * 4))) return rc;
     float4* colour[2] = {dev->d_denoiseStreams, dev->d_denoiseStreams + numPixels};
     float4* guideNormal = dev->d_denoiseStreams + 2 * numPixels;
     float4* guideAlbedo = dev->d_denoiseStreams + 3 * numPixels;
@@ -235,7 +217,7 @@ static int denoise(const char* name, TwkDevice dev, const TwkDenoiser* dn, const
     launchDenoiseFinish(beauty, halfOutput(dev), colour[dn->iterations & 1], normal ? guideNormal : nullptr, albedo ? guideAlbedo : nullptr, target, k, dev->stream);
     HIP_TRY(hipGetLastError());
   }
-  if (!denoised) dev->denoisedValid = true;
+  if (!denoised) dev->denoised.valid = true;
   return TWK_SUCCESS;
 }
 
@@ -354,13 +336,8 @@ TWK_CATCH("twk_denoise_geometry_host")
 static int readDenoised(TwkDevice dev, void* host, size_t size, bool raw, const char* where)
 {
   int rc = activate(dev, where); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + ": NULL buffer");
-  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, std::string(where) + ": no twk_denoise into the internal buffer yet");
-  const size_t n = (size_t) dev->denoisedWidth * dev->denoisedHeight;
-  if (size != n * (raw ? pixelBytes(dev) : 4))
-    return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(where) + (raw ? ": buffer must hold width*height pixels of the output format" : ": buffer must hold width*height*4 floats of the denoised picture"));
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  return readPixels(dev, dev->d_denoised, host, n, raw);
+  return readBack(dev, where, {currentPicture(dev, dev->denoised), "no twk_denoise into the internal buffer yet", dev->denoised.count(), raw ? pixelBytes(dev) : 0, true}, host, size,
+                  raw ? pixelBytes(dev) : 4, raw ? "width*height pixels of the output format" : "width*height*4 floats of the denoised picture");
 }
 
 int twk_read_denoised(TwkDevice dev, float* rgbaHost, size_t numFloats)
@@ -380,12 +357,12 @@ TWK_CATCH("twk_read_denoised_raw")
 int twk_get_denoised_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_denoised_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_denoised_device_pointer: NULL argument");
-  if (!dev->d_denoised || !dev->denoisedValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_denoised_device_pointer: no twk_denoise into the internal buffer yet");
-  *dptr = dev->d_denoised;
-  if (bytes) *bytes = (size_t) dev->denoisedWidth * dev->denoisedHeight * pixelBytes(dev);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_denoised_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!(pointer = currentPicture(dev, dev->denoised))) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_denoised_device_pointer: no twk_denoise into the internal buffer yet");
+    size = dev->denoised.count() * pixelBytes(dev);
+    return (int) TWK_SUCCESS;
+  });
 }
 TWK_CATCH("twk_get_denoised_device_pointer")
 
@@ -415,13 +392,11 @@ try
   if (!moments)
   {
     if (!dev->stateSet) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state first");
-    numElements = (size_t) dev->launchWidth * dev->state.resolution[1];
-    if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < numElements)
-      return refuse(TWK_ERROR_INVALID_STATE, "the handle has no luminance moments: twk_enable_moments(1) and twk_set_state first");
-    moments = dev->d_moments;
+    numElements = launchIndices(dev);
+    if (!(moments = ownMoments(dev, numElements))) return refuse(TWK_ERROR_INVALID_STATE, "the handle has no luminance moments: twk_enable_moments(1) and twk_set_state first");
   }
   if (overlaps(errorMap, numElements * sizeof(float), moments, numElements * sizeof(float4))) return refuse(TWK_ERROR_INVALID_VALUE, "the error map overlaps the moments");
-  if (!dev->d_noise) HIP_TRY(hipMalloc(&dev->d_noise, sizeof(TwkNoiseSummary)));
+  if ((rc = dev->d_noise.ensure(1))) return rc;
   NoiseConstants k;
   k.minSamples = (float) np->minSamples; k.darkFloor = np->darkFloor;
   HIP_TRY(hipMemsetAsync(dev->d_noise, 0, sizeof(TwkNoiseSummary), dev->stream));

@@ -189,15 +189,12 @@ try
   if (numTris >= ((size_t) 1 << 28) || numAttr >= ((size_t) 1 << 31) || numIdx >= ((size_t) 1 << 31))
     return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: " + std::to_string(numTris) + " triangle slots; a leaf reference holds 28 bits of slot index");
 
-  freeDevice(dev->d_attributes); freeDevice(dev->d_indices); freeDevice(dev->d_nodes); freeDevice(dev->d_wideNodes); freeDevice(dev->d_wideQ); freeDevice(dev->d_triangles); freeDevice(dev->d_shadeTriangles); freeDevice(dev->d_instances);
-  HIP_TRY(hipMalloc(&dev->d_attributes, sizeof(TwkTriangleAttributes) * numAttr));
-  HIP_TRY(hipMalloc(&dev->d_indices, sizeof(unsigned int) * numIdx));
-  HIP_TRY(hipMalloc(&dev->d_nodes, sizeof(BvhNode) * numNodes));
-  HIP_TRY(hipMalloc(&dev->d_wideNodes, sizeof(BvhNode) * 2 * (numNodes + 2))); // + the two nodes of an 8-wide root (wideRootKernel)
-  HIP_TRY(hipMalloc(&dev->d_wideQ, sizeof(float4) * 4 * (numNodes + 2)));
-  HIP_TRY(hipMalloc(&dev->d_triangles, sizeof(float4) * 3 * numTris));
-  HIP_TRY(hipMalloc(&dev->d_shadeTriangles, sizeof(float4) * TWK_SHADE_RECORD * numTris));
-  HIP_TRY(hipMalloc(&dev->d_instances, sizeof(DevInstance) * numInstances));
+  // the old scene's arrays are freed before the first of the new one's is asked for
+  dev->d_attributes.release(); dev->d_indices.release(); dev->d_nodes.release(); dev->d_wideNodes.release(); dev->d_wideQ.release(); dev->d_triangles.release(); dev->d_shadeTriangles.release(); dev->d_instances.release();
+  if ((rc = dev->d_attributes.allocate(sizeof(TwkTriangleAttributes) / sizeof(float) * numAttr)) || (rc = dev->d_indices.allocate(numIdx)) || (rc = dev->d_nodes.allocate(numNodes)) ||
+      (rc = dev->d_wideNodes.allocate(2 * (numNodes + 2))) || // + the two nodes of an 8-wide root (wideRootKernel)
+      (rc = dev->d_wideQ.allocate(4 * (numNodes + 2))) || (rc = dev->d_triangles.allocate(3 * numTris)) || (rc = dev->d_shadeTriangles.allocate(TWK_SHADE_RECORD * numTris)) ||
+      (rc = dev->d_instances.allocate((size_t) numInstances))) return rc;
   for (const GeometryHost& g : dev->geometries)
   {
     HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
@@ -205,10 +202,10 @@ try
   }
 
   if (const char* e = getenv("TWK_MAX_LEAF")) dev->builder.setMaxLeaf(atoi(e)); // tuning knob, default 2 triangles per leaf
-  ScopedDeviceBuffer<float> nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
-  if (dev->costedCuts) HIP_TRY(nodeCost.allocate(numNodes));
+  DeviceArray<float> nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
+  if (dev->costedCuts && (rc = nodeCost.allocate(numNodes))) return rc;
   struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder}; // the array does not outlive this call
-  dev->builder.setNodeCost(nodeCost.ptr);
+  dev->builder.setNodeCost(nodeCost);
   int maxEnteredHeight = 0, maxFlatHeight = 0, topHeight = 0; // binary-tree heights: what a traversal stack may have to hold
   // bottom level: one LBVH per entered geometry, shared by all of its instances (Device.cpp:1339 caches the GAS per Triangles id)
   for (size_t k = 0; k < dev->geometries.size(); ++k)
@@ -240,8 +237,8 @@ try
   // world-space trees of the flattened instances + the world boxes of all instances
   std::vector<float4> boxLo(numInstances), boxHi(numInstances);
   std::vector<int> leafPayload(numInstances);
-  ScopedDeviceBuffer<int4> soup;
-  if (maxFlatTriangles > 0) HIP_TRY(soup.allocate((size_t) maxFlatTriangles));
+  DeviceArray<int4> soup;
+  if (maxFlatTriangles > 0 && (rc = soup.allocate((size_t) maxFlatTriangles))) return rc;
   for (int i = 0; i < numInstances; ++i)
   {
     const InstanceHost& inst = dev->instances[i];
@@ -249,11 +246,11 @@ try
     if (flattened[i])
     {
       float bounds[6];
-      dev->builder.soupDescriptors(dev->stream, soup.ptr, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
+      dev->builder.soupDescriptors(dev->stream, soup, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
       HIP_TRY(hipGetLastError());
       HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
                                           dev->d_nodes + flatNodeBase[i], dev->d_wideNodes + 2 * (size_t) flatNodeBase[i], flatNodeBase[i],
-                                          dev->d_triangles, dev->d_shadeTriangles, flatTriangleBase[i], bounds, soup.ptr, dev->d_instances));
+                                          dev->d_triangles, dev->d_shadeTriangles, flatTriangleBase[i], bounds, soup, dev->d_instances));
       info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
       maxFlatHeight = std::max(maxFlatHeight, dev->builder.lastHeight());
       boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
@@ -313,22 +310,21 @@ try
   dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
   if (dev->wideRoot)
   {
-    ScopedDeviceBuffer<int> result;
-    HIP_TRY(result.allocate(1));
-    launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, result.ptr, dev->stream);
+    DeviceArray<int> result;
+    if ((rc = result.allocate(1))) return rc;
+    launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, result, dev->stream);
     int has = 0;
-    HIP_TRY(hipMemcpyAsync(&has, result.ptr, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+    HIP_TRY(hipMemcpyAsync(&has, result, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
     HIP_TRY(hipStreamSynchronize(dev->stream));
     if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
   }
   launchQuantizeWide(dev->d_wideNodes, dev->d_wideQ, (int) dev->wideNodesTotal, dev->stream);
-  if (!dev->d_topNodes) HIP_TRY(hipMalloc(&dev->d_topNodes, sizeof(float4) * 4 * TWK_TOP_NODES));
-  if (!dev->d_topNodes7) HIP_TRY(hipMalloc(&dev->d_topNodes7, sizeof(float4) * 4 * TWK_TOP_NODES7));
+  if ((rc = dev->d_topNodes.ensure(4 * TWK_TOP_NODES)) || (rc = dev->d_topNodes7.ensure(4 * TWK_TOP_NODES7))) return rc;
   launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
   launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  freeDevice(dev->d_wideNodes);
+  dev->d_wideNodes.release();
 
   info.maxTraversalDepth = (uint64_t) traversalDepth;
   info.triangleSlots = numTris; info.nodes = numNodes; info.instances = (uint64_t) numInstances; info.flattenedInstances = (uint64_t) (numInstances - numEntered);

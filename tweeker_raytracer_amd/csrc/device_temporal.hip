@@ -1,7 +1,8 @@
 // The picture-shaped temporal merges behind the C ABI: the plain merge (temporal_device.h: the definition) and the rectified one
 // (temporal_rectify_device.h). Their parameters and refusals, the explicit form, the own-buffer and the assembled form (temporalOwn
 // serves both merges), the readers and the rectified merge's host-only form. The cascade's layers through the same reprojection are
-// device_temporal_cascade.hip's, which takes its TwkTemporal checks and its history camera from here.
+// device_temporal_cascade.hip's, which takes its TwkTemporal checks and its history camera from here. The merged colour is a
+// DevicePicture (device_handle.h); the history streams have its shape and are dropped and allocated with it.
 #include "device_handle.h"
 
 #include <cstring>
@@ -10,25 +11,19 @@
 // Frees the streams of twk_temporal_accumulate's own-buffer form: the next call has no history
 void twk::dropTemporal(TwkDevice dev)
 {
-  for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) freeDevice(dev->d_temporal[s][k]);
-  freeDevice(dev->d_temporalColour);
-  for (int s = 0; s < 2; ++s) freeDevice(dev->d_rectify[s]);
-  freeDevice(dev->d_temporalTrust);
-  dev->rectifyPixels = 0; dev->temporalTrustValid = false;
-  dev->temporalWidth = 0; dev->temporalHeight = 0; dev->temporalHasHistory = false; dev->temporalValid = false;
+  for (int s = 0; s < 2; ++s) for (int k = 0; k < 3; ++k) dev->d_temporal[s][k].release();
+  dev->temporalColour.release();
+  for (int s = 0; s < 2; ++s) dev->d_rectify[s].release();
+  dev->d_temporalTrust.release();
+  dev->temporalTrustValid = false; dev->temporalHasHistory = false;
   dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
 }
 
 // The two scratch streams of the rectified merge, at least `pixels` float4 each
 static int ensureRectifyScratch(TwkDevice dev, size_t pixels)
 {
-  if (dev->d_rectify[0] && dev->d_rectify[1] && dev->rectifyPixels >= pixels) return TWK_SUCCESS;
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  for (int s = 0; s < 2; ++s) freeDevice(dev->d_rectify[s]);
-  dev->rectifyPixels = 0;
-  for (int s = 0; s < 2; ++s) HIP_TRY(hipMalloc(&dev->d_rectify[s], pixels * sizeof(float4)));
-  dev->rectifyPixels = pixels;
-  return TWK_SUCCESS;
+  const int rc = growIdle(dev, dev->d_rectify[0], pixels);
+  return rc ? rc : growIdle(dev, dev->d_rectify[1], pixels);
 }
 
 static TwkTemporal temporalDefaults()
@@ -88,31 +83,32 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
                        const float4* layers, int width, int height)
 {
   const size_t n = (size_t) width * height;
-  if (dev->temporalWidth != width || dev->temporalHeight != height || dev->temporalFormat != dev->outputFormat || !dev->d_temporalColour)
+  int rc;
+  if (!dev->temporalColour.shaped(width, height, dev->outputFormat))
   {
+    // the history has the picture's shape and goes with it: dropped (once everything enqueued has run), then allocated with it
     HIP_TRY(hipStreamSynchronize(dev->stream));
     dropTemporal(dev);
-    for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) HIP_TRY(hipMalloc(&dev->d_temporal[s][j], n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&dev->d_temporalColour, n * pixelBytes(dev)));
-    dev->temporalWidth = width; dev->temporalHeight = height; dev->temporalFormat = dev->outputFormat; dev->temporalKept = 0;
+    for (int s = 0; s < 2; ++s) for (int j = 0; j < 3; ++j) if ((rc = dev->d_temporal[s][j].allocate(n))) return rc;
+    if ((rc = ensurePicture(dev, dev->temporalColour, width, height))) return rc;
+    dev->temporalKept = 0;
   }
   const float4 *hColour = nullptr, *hMoments = nullptr, *hGeometry = nullptr;
   if (dev->temporalHasHistory)
   {
-    float4* const* h = dev->d_temporal[dev->temporalKept];
+    const DeviceArray<float4>* h = dev->d_temporal[dev->temporalKept];
     hColour = h[0]; hMoments = h[1]; hGeometry = h[2];
   }
   const int keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
   k.width = width; k.height = height;
-  int rc;
   if (dev->temporalHasHistory && (rc = temporalHistoryCamera(name, dev->temporalCamera, k))) return rc;
   // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
   if (rectify)
   {
     // the trust first: the layers' merge reads it
     if ((rc = ensureRectifyScratch(dev, n))) return rc;
-    if (!dev->d_temporalTrust) HIP_TRY(hipMalloc(&dev->d_temporalTrust, n * sizeof(float)));
-    launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->d_temporalColour,
+    if ((rc = dev->d_temporalTrust.ensure(n))) return rc;
+    launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->temporalColour.pixels,
                           dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream);
     HIP_TRY(hipGetLastError());
     if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust))) return rc;
@@ -121,12 +117,12 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
   else
   {
     if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
-    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_temporalColour, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
+    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->temporalColour.pixels, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
     HIP_TRY(hipGetLastError());
     dev->temporalTrustValid = false; // the trust plane, if any, is an earlier frame's
   }
   HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, n * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
-  dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalValid = true;
+  dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalColour.valid = true;
   return TWK_SUCCESS;
 }
 
@@ -139,11 +135,11 @@ static int temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConst
   if (dev->state.distribution && 1 < dev->count) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffer is a packed tile buffer (distribution 1, more than one device), not a picture");
   const int width = dev->launchWidth, height = dev->state.resolution[1];
   const size_t n = (size_t) width * height;
-  if (!dev->momentsEnabled || !dev->d_moments || (size_t) dev->momentsPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
-  if (!dev->geometryEnabled || !dev->d_geometry || (size_t) dev->geometryPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
+  if (!ownMoments(dev, n)) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no luminance moments: render with twk_enable_moments(1)");
+  if (!ownGeometry(dev, n)) return refuse(TWK_ERROR_INVALID_STATE, "the handle's own buffers have no geometry AOV: twk_enable_geometry(1) and twk_render_geometry");
   if (!dev->geometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV is older than the camera, the state or the scene: twk_render_geometry first");
-  const void* colour = dev->d_outputExternal ? dev->d_outputExternal : dev->d_outputInternal;
-  if (!colour || (size_t) dev->allocatedPixels < n) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
+  const void* colour = ownOutput(dev, n);
+  if (!colour) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
   if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
   return temporalOwn(dev, name, k, rectify, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
 }
@@ -165,8 +161,8 @@ static int temporalAssembledFrame(TwkDevice dev, const char* name, const Tempora
       return refuse(TWK_ERROR_INVALID_STATE, std::string(neededNames[j]) + " has not been assembled on this handle: twk_assemble_devices_with_geometry first");
   if (!dev->d_assembledGeometry) return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV has not been assembled on this handle: twk_assemble_devices_with_geometry first");
   if (!dev->assembledGeometryValid) return refuse(TWK_ERROR_INVALID_STATE, "the assembled geometry AOV is stale, older than the camera, the state or the scene: twk_render_geometry_tile and twk_assemble_devices_with_geometry first");
-  return temporalOwn(dev, name, k, rectify, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS]), static_cast<const float4*>(dev->d_assembledGeometry),
-                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE]) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
+  return temporalOwn(dev, name, k, rectify, dev->d_assembled[TWK_PLANE_OUTPUT], static_cast<const float4*>(dev->d_assembled[TWK_PLANE_MOMENTS].get()), static_cast<const float4*>(dev->d_assembledGeometry.get()),
+                     dev->temporalCascade ? static_cast<const float4*>(dev->d_assembled[TWK_PLANE_CASCADE].get()) : nullptr, dev->state.resolution[0], dev->state.resolution[1]);
 }
 
 // twk_temporal_accumulate (rectify nullptr, no trustOut) and twk_temporal_accumulate_rectified after the checks of their parameters,
@@ -212,8 +208,8 @@ static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, c
 }
 
 // The readers' refusal while the handle holds no own-buffer result
-static const char* const noTemporal = ": no twk_temporal_accumulate on the handle's own buffers since the last reset";
-static const char* const noTrust = ": the last merge on the handle's own buffers was no twk_temporal_accumulate_rectified, or its history has been dropped";
+static const char* const noTemporal = "no twk_temporal_accumulate on the handle's own buffers since the last reset";
+static const char* const noTrust = "the last merge on the handle's own buffers was no twk_temporal_accumulate_rectified, or its history has been dropped";
 
 extern "C" {
 
@@ -298,12 +294,12 @@ try
 {
   const std::string name = "twk_get_temporal_device_pointers";
   int rc = activate(dev, name.c_str()); if (rc) return rc;
-  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTemporal);
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (colour) *colour = dev->d_temporalColour;
-  if (colourBytes) *colourBytes = n * pixelBytes(dev->temporalFormat);
+  const DevicePicture& picture = dev->temporalColour;
+  if (!picture.valid) return twkSetError(TWK_ERROR_INVALID_STATE, name + ": " + noTemporal);
+  if (colour) *colour = picture.pixels;
+  if (colourBytes) *colourBytes = picture.count() * pixelBytes(picture.format);
   if (moments) *moments = dev->d_temporal[dev->temporalKept][1];
-  if (momentsBytes) *momentsBytes = n * sizeof(float4);
+  if (momentsBytes) *momentsBytes = picture.count() * sizeof(float4);
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_get_temporal_device_pointers")
@@ -311,57 +307,40 @@ TWK_CATCH("twk_get_temporal_device_pointers")
 int twk_read_temporal(TwkDevice dev, float* rgbaHost, size_t numFloats)
 try
 {
-  const std::string name = "twk_read_temporal";
-  int rc = activate(dev, name.c_str()); if (rc) return rc;
-  if (!rgbaHost) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL buffer");
-  if (!dev->temporalValid || dev->temporalFormat != dev->outputFormat) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTemporal);
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": buffer must hold width*height*4 floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  return readPixels(dev, dev->d_temporalColour, rgbaHost, n, false);
+  int rc = activate(dev, "twk_read_temporal"); if (rc) return rc;
+  return readBack(dev, "twk_read_temporal", {currentPicture(dev, dev->temporalColour), noTemporal, dev->temporalColour.count(), 0, true}, rgbaHost, numFloats, 4, "width*height*4 floats");
 }
 TWK_CATCH("twk_read_temporal")
 
 int twk_read_temporal_moments(TwkDevice dev, float* host, size_t numFloats)
 try
 {
-  const std::string name = "twk_read_temporal_moments";
-  int rc = activate(dev, name.c_str()); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL buffer");
-  if (!dev->temporalValid) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTemporal);
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": buffer must hold width*height*4 floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_temporal[dev->temporalKept][1], n * sizeof(float4), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  int rc = activate(dev, "twk_read_temporal_moments"); if (rc) return rc;
+  const float4* kept = dev->temporalColour.valid ? dev->d_temporal[dev->temporalKept][1].get() : nullptr;
+  return readBack(dev, "twk_read_temporal_moments", {kept, noTemporal, dev->temporalColour.count(), sizeof(float4), true}, host, numFloats, 4, "width*height*4 floats");
 }
 TWK_CATCH("twk_read_temporal_moments")
+
+// The trust plane of the last own-buffer merge, if that was a rectified one
+static float* ownTrust(TwkDevice dev) { return (dev->temporalColour.valid && dev->temporalTrustValid) ? dev->d_temporalTrust.get() : nullptr; }
 
 int twk_get_temporal_trust_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  const std::string name = "twk_get_temporal_trust_device_pointer";
-  int rc = activate(dev, name.c_str()); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL argument");
-  if (!dev->temporalValid || !dev->temporalTrustValid || !dev->d_temporalTrust) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTrust);
-  *dptr = dev->d_temporalTrust;
-  if (bytes) *bytes = (size_t) dev->temporalWidth * dev->temporalHeight * sizeof(float);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_temporal_trust_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!(pointer = ownTrust(dev))) return twkSetError(TWK_ERROR_INVALID_STATE, std::string("twk_get_temporal_trust_device_pointer: ") + noTrust);
+    size = dev->temporalColour.count() * sizeof(float);
+    return (int) TWK_SUCCESS;
+  });
 }
 TWK_CATCH("twk_get_temporal_trust_device_pointer")
 
 int twk_read_temporal_trust(TwkDevice dev, float* host, size_t numFloats)
 try
 {
-  const std::string name = "twk_read_temporal_trust";
-  int rc = activate(dev, name.c_str()); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": NULL buffer");
-  if (!dev->temporalValid || !dev->temporalTrustValid || !dev->d_temporalTrust) return twkSetError(TWK_ERROR_INVALID_STATE, name + noTrust);
-  const size_t n = (size_t) dev->temporalWidth * dev->temporalHeight;
-  if (numFloats != n) return twkSetError(TWK_ERROR_INVALID_VALUE, name + ": buffer must hold width*height floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_temporalTrust, n * sizeof(float), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  int rc = activate(dev, "twk_read_temporal_trust"); if (rc) return rc;
+  return readBack(dev, "twk_read_temporal_trust", {ownTrust(dev), noTrust, dev->temporalColour.count(), sizeof(float), true}, host, numFloats, 1, "width*height floats");
 }
 TWK_CATCH("twk_read_temporal_trust")
 

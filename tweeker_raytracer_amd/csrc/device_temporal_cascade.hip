@@ -10,8 +10,8 @@
 // Frees the merged layers of the own-buffer form: the next call has no history of layers. The switch stays as it is.
 void twk::dropTemporalCascade(TwkDevice dev)
 {
-  for (int s = 0; s < 2; ++s) freeDevice(dev->d_temporalCascade[s]);
-  dev->temporalCascadePixels = 0; dev->temporalCascadeLayers = 0; dev->temporalCascadeKept = 0;
+  for (int s = 0; s < 2; ++s) dev->d_temporalCascade[s].release();
+  dev->temporalCascadeLayers = 0; dev->temporalCascadeKept = 0;
   dev->temporalCascadeHasHistory = false; dev->temporalCascadeValid = false;
 }
 
@@ -33,15 +33,15 @@ int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const flo
   const int K = dev->cascadeK.layers;
   if (!layers)
   {
-    if (!dev->d_cascade || (size_t) dev->cascadePixels != n) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_temporal_accumulate: the handle's cascade layers do not have the frame's shape");
+    if (dev->d_cascade.capacity() != n * (size_t) K) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_temporal_accumulate: the handle's cascade layers do not have the frame's shape");
     layers = dev->d_cascade;
   }
-  if (!dev->d_temporalCascade[0] || dev->temporalCascadePixels != n || dev->temporalCascadeLayers != K)
+  if (dev->d_temporalCascade[0].capacity() != n * (size_t) K || dev->temporalCascadeLayers != K) // (exactly the frame's pixels of exactly K layers)
   {
     HIP_TRY(hipStreamSynchronize(dev->stream));
     dropTemporalCascade(dev);
-    for (int s = 0; s < 2; ++s) HIP_TRY(hipMalloc(&dev->d_temporalCascade[s], n * (size_t) K * sizeof(float4)));
-    dev->temporalCascadePixels = n; dev->temporalCascadeLayers = K;
+    for (int s = 0; s < 2; ++s) if ((rc = dev->d_temporalCascade[s].allocate(n * (size_t) K))) return rc;
+    dev->temporalCascadeLayers = K;
   }
   // layers are reprojected only with a history of their own and of the geometry: the first call after a drop copies the frame's through
   const bool history = dev->temporalCascadeHasHistory && k.hasHistory != 0 && historyGeometry != nullptr;
@@ -170,15 +170,19 @@ try
 }
 TWK_CATCH("twk_temporal_enable_cascade")
 
+// The merged layers the last own-buffer merge kept, if there was one since the last drop
+static float4* keptLayers(TwkDevice dev) { return dev->temporalCascadeValid ? dev->d_temporalCascade[dev->temporalCascadeKept].get() : nullptr; }
+static const char* const noLayers = "no twk_temporal_accumulate with twk_temporal_enable_cascade(1) on the handle's own buffers since the last drop";
+
 int twk_get_temporal_cascade_device_pointer(TwkDevice dev, void** dptr, size_t* bytes)
 try
 {
-  int rc = activate(dev, "twk_get_temporal_cascade_device_pointer"); if (rc) return rc;
-  if (!dptr) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_temporal_cascade_device_pointer: NULL argument");
-  if (!dev->temporalCascadeValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_temporal_cascade_device_pointer: no twk_temporal_accumulate with twk_temporal_enable_cascade(1) on the handle's own buffers since the last drop");
-  *dptr = dev->d_temporalCascade[dev->temporalCascadeKept];
-  if (bytes) *bytes = dev->temporalCascadePixels * (size_t) dev->temporalCascadeLayers * sizeof(float4);
-  return TWK_SUCCESS;
+  return getPointer(dev, "twk_get_temporal_cascade_device_pointer", dptr, bytes, [dev](void*& pointer, size_t& size)
+  {
+    if (!dev->temporalCascadeValid) return twkSetError(TWK_ERROR_INVALID_STATE, std::string("twk_get_temporal_cascade_device_pointer: ") + noLayers);
+    pointer = keptLayers(dev); size = dev->d_temporalCascade[dev->temporalCascadeKept].capacity() * sizeof(float4);
+    return (int) TWK_SUCCESS;
+  });
 }
 TWK_CATCH("twk_get_temporal_cascade_device_pointer")
 
@@ -186,13 +190,8 @@ int twk_read_temporal_cascade(TwkDevice dev, float* host, size_t numFloats)
 try
 {
   int rc = activate(dev, "twk_read_temporal_cascade"); if (rc) return rc;
-  if (!host) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_cascade: NULL buffer");
-  if (!dev->temporalCascadeValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_read_temporal_cascade: no twk_temporal_accumulate with twk_temporal_enable_cascade(1) on the handle's own buffers since the last drop");
-  const size_t n = dev->temporalCascadePixels * (size_t) dev->temporalCascadeLayers;
-  if (numFloats != n * 4) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_read_temporal_cascade: buffer must hold layers*launchWidth*height*4 floats");
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  HIP_TRY(hipMemcpy(host, dev->d_temporalCascade[dev->temporalCascadeKept], n * sizeof(float4), hipMemcpyDeviceToHost));
-  return TWK_SUCCESS;
+  return readBack(dev, "twk_read_temporal_cascade", {keptLayers(dev), noLayers, dev->d_temporalCascade[dev->temporalCascadeKept].capacity(), sizeof(float4), true}, host, numFloats, 4,
+                  "layers*launchWidth*height*4 floats");
 }
 TWK_CATCH("twk_read_temporal_cascade")
 

@@ -281,6 +281,8 @@ typedef struct TwkBuildInfo
   uint64_t traceBlocksPerCU;    /* ABI 5: resident blocks per CU of the persistent traversal kernel for this scene with the materials as they are now: 7 (every instance flattened, at most 1 M nodes — with or without cutout opacity), 5 (two-level with cutout opacity), else 6 */
   uint64_t wide8Nodes;          /* ABI 8: reserved, 0 — the compressed 8-ary nodes of round 4 lost on every scene and are an experiment patch now (tools/experiments/r04_wide8_nodes.patch) */
   uint64_t wide8Levels;         /* ABI 8: reserved, 0 */
+  uint64_t pairLeaves;          /* leaves that hold a pair: triangles 2k, 2k + 1 of a geometry with the index triples (a, b, c), (c, d, a), built as one primitive (over every tree of the scene; 0 under TWK_TRIANGLE_PAIRS=0) */
+  uint64_t pairTriangles;       /* triangle slots in those leaves: two each */
 } TwkBuildInfo;
 int twk_get_build_info(TwkDevice dev, TwkBuildInfo* info);
 

@@ -259,7 +259,8 @@ class BuildInfo(C.Structure):
                 ("buildMilliseconds", C.c_double), ("triangleSlots", C.c_uint64), ("nodes", C.c_uint64),
                 ("instances", C.c_uint64), ("flattenedInstances", C.c_uint64), ("maxTraversalDepth", C.c_uint64),
                 ("directLeafInstances", C.c_uint64), ("traceBlocksPerCU", C.c_uint64),
-                ("wide8Nodes", C.c_uint64), ("wide8Levels", C.c_uint64)]
+                ("wide8Nodes", C.c_uint64), ("wide8Levels", C.c_uint64),
+                ("pairLeaves", C.c_uint64), ("pairTriangles", C.c_uint64)]
 
 
 class AppInfo(C.Structure):

@@ -1,5 +1,6 @@
 #pragma once
 #include "device_types.h"
+#include <vector>
 
 namespace twk {
 
@@ -13,6 +14,29 @@ void launchTopCache(const float4* wideQ, int root, int root2, float4* top, int n
 // nodes firstNew, firstNew + 1 when it pays; result[0] (device) says whether.
 void launchWideRoot(BvhNode* wide, int root, int firstNew, int* result, hipStream_t stream);
 
+// Pair leaves: rewrites, in the `count` quantised wide nodes, every reference to a world-space leaf of two slots at which a pair
+// begins (pairFlags, per slot, from BvhBuilder::buildTriangles) and writes the pair's record (device_types.h "triangle pairs").
+// Before launchTopCache, so that the cached copies and the tile entry lists inherit the references.
+void launchPairLeaves(float4* wideQ, int count, const int* pairFlags, int numSlots, const float4* triangles, float4* pairs, hipStream_t stream);
+
+// Build primitives of a geometry's triangles for BvhBuilder::buildTriangles: triangles 2k, 2k + 1 with the index triples
+// (a, b, c), (c, d, a) — what every mesh generator emits per quad — are one primitive (first triangle | sign bit), every other
+// triangle is one of its own. Indices are compared, not positions. Returns the number of pairs.
+inline size_t trianglePairs(const unsigned int* indices, int numTriangles, std::vector<int>& primFirst)
+{
+  primFirst.clear();
+  size_t pairs = 0;
+  for (int t = 0; t < numTriangles; )
+  {
+    const unsigned int* i = indices + 3 * (size_t) t;
+    const bool pair = (t % 2 == 0) && t + 1 < numTriangles && i[3] == i[2] && i[5] == i[0];
+    primFirst.push_back(pair ? (int) ((unsigned int) t | 0x80000000u) : t);
+    pairs += pair ? 1 : 0;
+    t += pair ? 2 : 1;
+  }
+  return pairs;
+}
+
 // Scratch-owning LBVH builder, reused for every geometry (bottom level) and for the instance level.
 class BvhBuilder
 {
@@ -25,9 +49,15 @@ public:
   // slots at outTriangles[3 * triangleBase ..] (+ the 128-byte shading records at outShadeTriangles[TWK_SHADE_RECORD * triangleBase ..]). rootBounds receives the (padded) object-space box.
   // soup != nullptr: the world-space soup of the flattened instances instead — numTriangles descriptors (bvh_build.hip
   // soupVertices), attributes / indices are the SHARED arrays, leaves carry TWK_LEAF_WORLD, rootBounds is a world box.
+  // Pairs (hostPrimFirst != nullptr, a host array): the build runs over numPrims BUILD PRIMITIVES instead of triangles — primitive b
+  // is triangle hostPrimFirst[b] & 0x7fffffff, and with the sign bit set the triangle after it too (the two halves of a quad,
+  // trianglePairs()): one box, one centroid, so the two land in one leaf, in consecutive slots, first triangle first. Leaves still
+  // hold at most maxLeaf triangles; the formats of nodes and slots do not change. outPairFlags[triangleBase + slot] (device) says
+  // whether a pair begins at the slot. Needs maxLeaf >= 2, else the triangles are built one by one.
   hipError_t buildTriangles(hipStream_t stream, const float* attributes, const unsigned int* indices, int numTriangles,
                             BvhNode* outNodes, BvhNode* outWide, int nodeBase, float4* outTriangles, float4* outShadeTriangles, int triangleBase, float rootBounds[6],
-                            const int4* soup = nullptr, const DevInstance* instances = nullptr);
+                            const int4* soup = nullptr, const DevInstance* instances = nullptr,
+                            const int* hostPrimFirst = nullptr, int numPrims = 0, int* outPairFlags = nullptr);
   // Descriptors of one flattened instance: its geometry's triangles 0..count-1 become soup primitives first..first+count-1.
   void soupDescriptors(hipStream_t stream, int4* soup, int first, int count, int instance, int attributeBase, int indexBase);
 
@@ -70,6 +100,10 @@ private:
   float4* m_nodeLo = nullptr; float4* m_nodeHi = nullptr;
   unsigned int* m_bounds = nullptr;
   int* m_leafPayload = nullptr; // top level: leaf payload per instance
+  // pairs: first triangle (sign bit: and the next) per build primitive; triangles and first slot per sorted position
+  bool m_paired = false;
+  int* m_primFirst = nullptr; int* m_slotCounts = nullptr; int* m_slotOff = nullptr;
+  void* m_slotScanTemp = nullptr; size_t m_slotScanBytes = 0;
   // binned-SAH builder scratch (bvh_sah.hip)
   int  m_quality = 1;
   int  m_sahCapacity = 0;

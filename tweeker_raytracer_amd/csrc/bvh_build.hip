@@ -52,28 +52,37 @@ TWK_D void soupVertices(const int4& d, const float* __restrict__ attributes, con
 
 // Triangle boxes of one geometry (object space), or of the world-space soup of the flattened instances (soup != nullptr:
 // attributes / indices are then the shared arrays). attributes: 12 floats per vertex (position first), indices: 3 per triangle.
+// primFirst != nullptr (bvh_build.h "pairs"): box i is the box of BUILD PRIMITIVE i — triangle primFirst[i] & 0x7fffffff, and with
+// the sign bit set the triangle after it too: the two halves of a quad are one primitive of the build.
 __global__ void triangleBoxesKernel(const float* __restrict__ attributes, const unsigned int* __restrict__ indices,
-                                    const int4* __restrict__ soup, const DevInstance* __restrict__ instances,
+                                    const int4* __restrict__ soup, const DevInstance* __restrict__ instances, const int* __restrict__ primFirst,
                                     int count, float4* __restrict__ primLo, float4* __restrict__ primHi, unsigned int* bounds)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  V3 va, vb, vc;
-  if (soup != nullptr)
+  const float inf = __uint_as_float(0x7f800000u);
+  float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
+  const int first = primFirst ? (primFirst[i] & 0x7fffffff) : i, triangles = (primFirst && primFirst[i] < 0) ? 2 : 1;
+  for (int k = 0; k < triangles; ++k)
   {
-    const float *a, *b, *c;
-    soupVertices(soup[i], attributes, indices, instances, a, b, c, va, vb, vc);
+    const int tri = first + k;
+    V3 va, vb, vc;
+    if (soup != nullptr)
+    {
+      const float *a, *b, *c;
+      soupVertices(soup[tri], attributes, indices, instances, a, b, c, va, vb, vc);
+    }
+    else
+    {
+      const unsigned int i0 = indices[3 * tri], i1 = indices[3 * tri + 1], i2 = indices[3 * tri + 2];
+      const float* a = attributes + 12 * (size_t) i0;
+      const float* b = attributes + 12 * (size_t) i1;
+      const float* c = attributes + 12 * (size_t) i2;
+      va = v3(a[0], a[1], a[2]); vb = v3(b[0], b[1], b[2]); vc = v3(c[0], c[1], c[2]);
+    }
+    lo[0] = fminf(lo[0], fminf(fminf(va.x, vb.x), vc.x)); lo[1] = fminf(lo[1], fminf(fminf(va.y, vb.y), vc.y)); lo[2] = fminf(lo[2], fminf(fminf(va.z, vb.z), vc.z));
+    hi[0] = fmaxf(hi[0], fmaxf(fmaxf(va.x, vb.x), vc.x)); hi[1] = fmaxf(hi[1], fmaxf(fmaxf(va.y, vb.y), vc.y)); hi[2] = fmaxf(hi[2], fmaxf(fmaxf(va.z, vb.z), vc.z));
   }
-  else
-  {
-    const unsigned int i0 = indices[3 * i], i1 = indices[3 * i + 1], i2 = indices[3 * i + 2];
-    const float* a = attributes + 12 * (size_t) i0;
-    const float* b = attributes + 12 * (size_t) i1;
-    const float* c = attributes + 12 * (size_t) i2;
-    va = v3(a[0], a[1], a[2]); vb = v3(b[0], b[1], b[2]); vc = v3(c[0], c[1], c[2]);
-  }
-  const float lo[3] = { fminf(fminf(va.x, vb.x), vc.x), fminf(fminf(va.y, vb.y), vc.y), fminf(fminf(va.z, vb.z), vc.z) };
-  const float hi[3] = { fmaxf(fmaxf(va.x, vb.x), vc.x), fmaxf(fmaxf(va.y, vb.y), vc.y), fmaxf(fmaxf(va.z, vb.z), vc.z) };
   primLo[i] = make_float4(lo[0], lo[1], lo[2], 0.0f);
   primHi[i] = make_float4(hi[0], hi[1], hi[2], 0.0f);
   for (int k = 0; k < 3; ++k)
@@ -195,6 +204,15 @@ TWK_D void padBox(float4& lo, float4& hi)
   hi.x += e; hi.y += e; hi.z += e;
 }
 
+// Reference of the leaf over sorted positions [first, first + positions) when it holds at most maxLeaf triangles, else 0 (no
+// leaf reference is 0: ~0 is -1).
+TWK_D int leafReference(const int* __restrict__ slotOff, int leafBase, int leafFlag, int first, int positions, int maxLeaf)
+{
+  const int slot = slotOff ? slotOff[first] : first, triangles = slotOff ? slotOff[first + positions] - slot : positions;
+  if (positions > 1 && triangles > maxLeaf) return 0;
+  return ~((leafBase + slot) | ((triangles - 1) << 28) | leafFlag);
+}
+
 TWK_D void writeNode(BvhNode* node, const float4& lo0, const float4& hi0, const float4& lo1, const float4& hi1, int c0, int c1)
 {
   float4* p = reinterpret_cast<float4*>(node);
@@ -257,6 +275,8 @@ TWK_D void writeWideNode(BvhNode* wide, const WideEntry* e)
 // position; a child subtree that covers at most maxLeaf sorted positions is referenced as ONE leaf (its slots are
 // contiguous because the leaves of a radix tree are in key order), which removes the bottom levels of the tree.
 // leafFlag = TWK_LEAF_WORLD for the world-space soup of the flattened instances (device_types.h), else 0.
+// slotOff != nullptr (bvh_build.h "pairs"): a sorted position holds a build primitive of one or two triangles, slotOff[position]
+// is its first slot relative to leafBase (slotOff[count] = all slots), and a subtree is collapsed by its TRIANGLES.
 // leafMode 1 (top level): child reference = ~leafPayload[primitive index]: payload = instance index gives a leaf;
 // payload = ~(root node of the soup) gives an INNER reference — the soup's tree becomes a subtree of the top level.
 __global__ void refitKernel(const unsigned long long* __restrict__ keys, int count,
@@ -266,7 +286,8 @@ __global__ void refitKernel(const unsigned long long* __restrict__ keys, int cou
                             const int2* __restrict__ range,
                             unsigned int* __restrict__ tickets, float4* nodeLo, float4* nodeHi,
                             BvhNode* outNodes, BvhNode* __restrict__ outWide, int nodeBase, int leafMode, int leafBase, int maxLeaf,
-                            const int* __restrict__ leafPayload, int leafFlag, float* nodeCost /* indexed by absolute node index; nullptr: every wide node = the four grandchildren */)
+                            const int* __restrict__ leafPayload, int leafFlag, float* nodeCost /* indexed by absolute node index; nullptr: every wide node = the four grandchildren */,
+                            const int* __restrict__ slotOff)
 {
   const int leaf = blockIdx.x * blockDim.x + threadIdx.x;
   if (leaf >= count) return;
@@ -287,26 +308,28 @@ __global__ void refitKernel(const unsigned long long* __restrict__ keys, int cou
     {
       const unsigned int prim = (unsigned int) (keys[~l] & 0xffffffffull);
       lo0 = primLo[prim]; hi0 = primHi[prim]; padBox(lo0, hi0);
-      c0 = (leafMode == 0) ? ~((leafBase + ~l) | leafFlag) : ~leafPayload[prim];
+      c0 = (leafMode == 0) ? leafReference(slotOff, leafBase, leafFlag, ~l, 1, maxLeaf) : ~leafPayload[prim];
     }
     else
     {
       lo0 = nodeLo[l]; hi0 = nodeHi[l];
       const int2 rg = range[l];
-      c0 = (leafMode == 0 && rg.y <= maxLeaf) ? ~((leafBase + rg.x) | ((rg.y - 1) << 28) | leafFlag) : nodeBase + l;
+      const int collapsed = (leafMode == 0 && rg.y <= maxLeaf) ? leafReference(slotOff, leafBase, leafFlag, rg.x, rg.y, maxLeaf) : 0;
+      c0 = collapsed ? collapsed : nodeBase + l;
       if (c0 >= 0) height0 = __float_as_int(lo0.w);
     }
     if (r < 0)
     {
       const unsigned int prim = (unsigned int) (keys[~r] & 0xffffffffull);
       lo1 = primLo[prim]; hi1 = primHi[prim]; padBox(lo1, hi1);
-      c1 = (leafMode == 0) ? ~((leafBase + ~r) | leafFlag) : ~leafPayload[prim];
+      c1 = (leafMode == 0) ? leafReference(slotOff, leafBase, leafFlag, ~r, 1, maxLeaf) : ~leafPayload[prim];
     }
     else
     {
       lo1 = nodeLo[r]; hi1 = nodeHi[r];
       const int2 rg = range[r];
-      c1 = (leafMode == 0 && rg.y <= maxLeaf) ? ~((leafBase + rg.x) | ((rg.y - 1) << 28) | leafFlag) : nodeBase + r;
+      const int collapsed = (leafMode == 0 && rg.y <= maxLeaf) ? leafReference(slotOff, leafBase, leafFlag, rg.x, rg.y, maxLeaf) : 0;
+      c1 = collapsed ? collapsed : nodeBase + r;
       if (c1 >= 0) height1 = __float_as_int(lo1.w);
     }
     writeNode(&outNodes[node], lo0, hi0, lo1, hi1, c0, c1);
@@ -368,10 +391,10 @@ __global__ void refitKernel(const unsigned long long* __restrict__ keys, int cou
 // A single primitive has no inner node: emit one node whose second child can never be hit.
 __global__ void singleLeafKernel(const float4* __restrict__ primLo, const float4* __restrict__ primHi,
                                  BvhNode* outNodes, BvhNode* outWide, float4* nodeLo, float4* nodeHi, int leafMode, int leafBase,
-                                 const int* __restrict__ leafPayload, int leafFlag, float* nodeCost)
+                                 const int* __restrict__ leafPayload, int leafFlag, float* nodeCost, const int* __restrict__ slotOff)
 {
   if (nodeCost != nullptr) nodeCost[0] = 1.0f;
-  const int leafRef = (leafMode == 0) ? ~(leafBase | leafFlag) : ~leafPayload[0];
+  const int leafRef = (leafMode == 0) ? leafReference(slotOff, leafBase, leafFlag, 0, 1, 4) : ~leafPayload[0];
   float4 lo = primLo[0], hi = primHi[0];
   padBox(lo, hi);
   const float inf = __uint_as_float(0x7f800000u);
@@ -393,14 +416,10 @@ __global__ void singleLeafKernel(const float4* __restrict__ primLo, const float4
 //           once here), then the three vertex normals                                   — every hit
 //   [3..5.x] the three vertex tangents                                                  — GGX materials (TBN) only
 //   [5.y..7.y] the three vertex texture coordinates                                     — textured materials only
-__global__ void emitTrianglesKernel(const float* __restrict__ attributes, const unsigned int* __restrict__ indices,
-                                    const int4* __restrict__ soup, const DevInstance* __restrict__ instances,
-                                    const unsigned long long* __restrict__ keys, int count, float4* __restrict__ triangles,
-                                    float4* __restrict__ shadeTriangles)
+TWK_D void emitTriangle(const float* __restrict__ attributes, const unsigned int* __restrict__ indices,
+                        const int4* __restrict__ soup, const DevInstance* __restrict__ instances,
+                        unsigned int prim, int slot, float4* __restrict__ triangles, float4* __restrict__ shadeTriangles)
 {
-  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= count) return;
-  const unsigned int prim = (unsigned int) (keys[slot] & 0xffffffffull);
   const float *a, *b, *c;
   if (soup != nullptr)
   {
@@ -434,6 +453,35 @@ __global__ void emitTrianglesKernel(const float* __restrict__ attributes, const 
   out[5] = make_float4(c[5], a[9], a[10], a[11]);
   out[6] = make_float4(b[9], b[10], b[11], c[9]);
   out[7] = make_float4(c[10], c[11], 0.0f, 0.0f);
+}
+
+// One thread per sorted position. primFirst / slotOff != nullptr (bvh_build.h "pairs"): the position holds a build primitive of
+// one or two triangles, which take consecutive slots from slotOff[position] on, first triangle first; pairFlags[slot] says
+// whether a pair begins at the slot.
+__global__ void emitTrianglesKernel(const float* __restrict__ attributes, const unsigned int* __restrict__ indices,
+                                    const int4* __restrict__ soup, const DevInstance* __restrict__ instances,
+                                    const unsigned long long* __restrict__ keys, int count, float4* __restrict__ triangles,
+                                    float4* __restrict__ shadeTriangles, const int* __restrict__ primFirst, const int* __restrict__ slotOff,
+                                    int* __restrict__ pairFlags)
+{
+  const int position = blockIdx.x * blockDim.x + threadIdx.x;
+  if (position >= count) return;
+  const unsigned int prim = (unsigned int) (keys[position] & 0xffffffffull);
+  if (primFirst == nullptr) { emitTriangle(attributes, indices, soup, instances, prim, position, triangles, shadeTriangles); return; }
+  const int first = primFirst[prim] & 0x7fffffff, slot = slotOff[position];
+  const bool pair = primFirst[prim] < 0;
+  emitTriangle(attributes, indices, soup, instances, (unsigned int) first, slot, triangles, shadeTriangles);
+  if (pair) emitTriangle(attributes, indices, soup, instances, (unsigned int) first + 1u, slot + 1, triangles, shadeTriangles);
+  if (pairFlags != nullptr) { pairFlags[slot] = pair ? 1 : 0; if (pair) pairFlags[slot + 1] = 0; }
+}
+
+// Triangles of the build primitive at each sorted position (bvh_build.h "pairs"); counts[count] = 0, so that the exclusive scan over
+// count + 1 entries ends with the number of slots.
+__global__ void slotCountsKernel(const unsigned long long* __restrict__ keys, const int* __restrict__ primFirst, int count, int* __restrict__ counts)
+{
+  const int position = blockIdx.x * blockDim.x + threadIdx.x;
+  if (position > count) return;
+  counts[position] = (position == count) ? 0 : ((primFirst[(unsigned int) (keys[position] & 0xffffffffull)] < 0) ? 2 : 1);
 }
 
 // Quantised copy of the wide nodes (device_types.h "quantised wide node"), one thread per inner node index. The grid
@@ -610,6 +658,42 @@ __global__ void wideRootKernel(BvhNode* wide, int root, int firstNew, int* resul
   result[0] = 1;
 }
 
+// Pair leaves (device_types.h "triangle pairs"), one thread per quantised wide node: a reference to a world-space leaf of two
+// slots at which a pair begins gets its record written at pairs[4 * (first slot / 2)] — two pairs never share a slot, so the index
+// is theirs alone — and loses TWK_LEAF_WORLD, which is how the persistent kernel knows it. A leaf referenced from several entries
+// (an unused entry repeats the first, the 8-wide root copies its entries) is written by each of them with the same words.
+__global__ void pairLeavesKernel(float4* __restrict__ wideQ, int count, const int* __restrict__ pairFlags, int numSlots,
+                                 const float4* __restrict__ triangles, float4* __restrict__ pairs)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float4 refs = wideQ[4 * (size_t) i + 3];
+  int r[4] = {__float_as_int(refs.x), __float_as_int(refs.y), __float_as_int(refs.z), __float_as_int(refs.w)};
+  bool changed = false;
+  for (int k = 0; k < 4; ++k)
+  {
+    if (r[k] >= 0) continue;
+    const int payload = ~r[k];
+    const int first = payload & 0x0fffffff;
+    if (!(payload & TWK_LEAF_WORLD) || ((payload >> 28) & 3) != 1 || first + 1 >= numSlots || !pairFlags[first]) continue;
+    const float4* t = triangles + 3 * (size_t) first;
+    const float4 a0 = t[0], b0 = t[1], c0 = t[2], a1 = t[3], b1 = t[4];
+    float4* out = pairs + 4 * (size_t) (first >> 1);
+    out[0] = make_float4(a0.x, a0.y, a0.z, a0.w);                 // w0, primitive of the first triangle
+    out[1] = make_float4(b0.x, b0.y, b0.z, a1.w);                 // w1, primitive of the second
+    out[2] = make_float4(c0.x, c0.y, c0.z, b0.w);                 // w2, instance
+    out[3] = make_float4(b1.x, b1.y, b1.z, __int_as_float(first)); // w3, first slot
+    r[k] = ~(payload & ~TWK_LEAF_WORLD);
+    changed = true;
+  }
+  if (changed) wideQ[4 * (size_t) i + 3] = make_float4(__int_as_float(r[0]), __int_as_float(r[1]), __int_as_float(r[2]), __int_as_float(r[3]));
+}
+
+void launchPairLeaves(float4* wideQ, int count, const int* pairFlags, int numSlots, const float4* triangles, float4* pairs, hipStream_t stream)
+{
+  if (count > 0) hipLaunchKernelGGL(pairLeavesKernel, dim3((count + 255) / 256), dim3(256), 0, stream, wideQ, count, pairFlags, numSlots, triangles, pairs);
+}
+
 void launchWideRoot(BvhNode* wide, int root, int firstNew, int* result, hipStream_t stream)
 {
   hipLaunchKernelGGL(wideRootKernel, dim3(1), dim3(1), 0, stream, wide, root, firstNew, result);
@@ -636,6 +720,13 @@ hipError_t BvhBuilder::reserve(int count)
   BVH_CHECK(hipMalloc(&m_nodeHi, sizeof(float4) * n));
   BVH_CHECK(hipMalloc(&m_bounds, sizeof(unsigned int) * 8));
   BVH_CHECK(hipMalloc(&m_leafPayload, sizeof(int) * n));
+  // pairs: first triangle per build primitive, triangles and first slot per sorted position (+ 1: the total)
+  BVH_CHECK(hipMalloc(&m_primFirst, sizeof(int) * (n + 1)));
+  BVH_CHECK(hipMalloc(&m_slotCounts, sizeof(int) * (n + 1)));
+  BVH_CHECK(hipMalloc(&m_slotOff, sizeof(int) * (n + 1)));
+  m_slotScanBytes = 0;
+  BVH_CHECK(rocprim::exclusive_scan(nullptr, m_slotScanBytes, m_slotCounts, m_slotOff, 0, n + 1, rocprim::plus<int>(), (hipStream_t) 0));
+  BVH_CHECK(hipMalloc(&m_slotScanTemp, m_slotScanBytes > 0 ? m_slotScanBytes : 16));
   m_sortBytes = 0;
   BVH_CHECK(rocprim::radix_sort_keys(nullptr, m_sortBytes, m_keysIn, m_keysOut, n, 0, 64, (hipStream_t) 0));
   BVH_CHECK(hipMalloc(&m_sortTemp, m_sortBytes > 0 ? m_sortBytes : 16));
@@ -645,12 +736,13 @@ hipError_t BvhBuilder::reserve(int count)
 
 void BvhBuilder::release()
 {
-  void* p[] = { m_primLo, m_primHi, m_keysIn, m_keysOut, m_left, m_right, m_innerParent, m_leafParent, m_range, m_tickets, m_nodeLo, m_nodeHi, m_bounds, m_sortTemp, m_leafPayload };
+  void* p[] = { m_primLo, m_primHi, m_keysIn, m_keysOut, m_left, m_right, m_innerParent, m_leafParent, m_range, m_tickets, m_nodeLo, m_nodeHi, m_bounds, m_sortTemp, m_leafPayload, m_primFirst, m_slotCounts, m_slotOff, m_slotScanTemp };
   for (void* q : p) if (q) (void) hipFree(q);
   m_primLo = m_primHi = m_nodeLo = m_nodeHi = nullptr;
   m_keysIn = m_keysOut = nullptr;
   m_left = m_right = m_innerParent = m_leafParent = nullptr; m_range = nullptr;
   m_tickets = nullptr; m_bounds = nullptr; m_sortTemp = nullptr; m_leafPayload = nullptr;
+  m_primFirst = m_slotCounts = m_slotOff = nullptr; m_slotScanTemp = nullptr; m_slotScanBytes = 0;
   m_capacity = 0;
   releaseSah();
 }
@@ -659,11 +751,21 @@ hipError_t BvhBuilder::buildFromBoxes(hipStream_t stream, int count, BvhNode* ou
 {
   const int block = 256;
   const int grid  = (count + block - 1) / block;
+  const int* slotOff = (leafMode == 0 && m_paired) ? m_slotOff : nullptr;
+  // pairs: the slots of the sorted positions, once their order is known
+  auto slotOffsets = [&]() -> hipError_t
+  {
+    if (slotOff == nullptr) return hipSuccess;
+    hipLaunchKernelGGL(slotCountsKernel, dim3((count + block) / block), dim3(block), 0, stream, m_keysOut, m_primFirst, count, m_slotCounts);
+    size_t bytes = m_slotScanBytes;
+    return rocprim::exclusive_scan(m_slotScanTemp, bytes, m_slotCounts, m_slotOff, 0, (size_t) count + 1, rocprim::plus<int>(), stream);
+  };
   if (count == 1)
   {
-    hipLaunchKernelGGL(singleLeafKernel, dim3(1), dim3(1), 0, stream, m_primLo, m_primHi, outNodes, outWide, m_nodeLo, m_nodeHi, leafMode, leafBase, m_leafPayload, leafFlag, m_nodeCost ? m_nodeCost + nodeBase : nullptr);
-    // keysOut[0] must still name primitive 0 for emitTriangles
+    // keysOut[0] must name primitive 0 for emitTriangles
     BVH_CHECK(hipMemsetAsync(m_keysOut, 0, sizeof(unsigned long long), stream));
+    BVH_CHECK(slotOffsets());
+    hipLaunchKernelGGL(singleLeafKernel, dim3(1), dim3(1), 0, stream, m_primLo, m_primHi, outNodes, outWide, m_nodeLo, m_nodeHi, leafMode, leafBase, m_leafPayload, leafFlag, m_nodeCost ? m_nodeCost + nodeBase : nullptr, slotOff);
     return hipGetLastError();
   }
   if (m_quality == 1)
@@ -676,24 +778,32 @@ hipError_t BvhBuilder::buildFromBoxes(hipStream_t stream, int count, BvhNode* ou
     BVH_CHECK(rocprim::radix_sort_keys(m_sortTemp, m_sortBytes, m_keysIn, m_keysOut, (size_t) count, 0, 64, stream));
     hipLaunchKernelGGL(radixTreeKernel, dim3(grid), dim3(block), 0, stream, m_keysOut, count, m_left, m_right, m_innerParent, m_leafParent, m_range);
   }
+  BVH_CHECK(slotOffsets());
   BVH_CHECK(hipMemsetAsync(m_tickets, 0, sizeof(unsigned int) * count, stream));
   hipLaunchKernelGGL(refitKernel, dim3(grid), dim3(block), 0, stream, m_keysOut, count, m_primLo, m_primHi, m_left, m_right,
-                     m_innerParent, m_leafParent, m_range, m_tickets, m_nodeLo, m_nodeHi, outNodes, outWide, nodeBase, leafMode, leafBase, m_maxLeaf, m_leafPayload, leafFlag, m_nodeCost);
+                     m_innerParent, m_leafParent, m_range, m_tickets, m_nodeLo, m_nodeHi, outNodes, outWide, nodeBase, leafMode, leafBase, m_maxLeaf, m_leafPayload, leafFlag, m_nodeCost, slotOff);
   BVH_CHECK(hipGetLastError());
   return (leafMode == 0) ? accumulateSahCost(stream, count) : hipSuccess;
 }
 
 hipError_t BvhBuilder::buildTriangles(hipStream_t stream, const float* attributes, const unsigned int* indices, int numTriangles,
                                       BvhNode* outNodes, BvhNode* outWide, int nodeBase, float4* outTriangles, float4* outShadeTriangles, int triangleBase, float rootBounds[6],
-                                      const int4* soup, const DevInstance* instances)
+                                      const int4* soup, const DevInstance* instances, const int* hostPrimFirst, int numPrims, int* outPairFlags)
 {
   BVH_CHECK(reserve(numTriangles));
+  // pairs: the build runs over numPrims build primitives of one or two triangles each
+  m_paired = (hostPrimFirst != nullptr) && m_maxLeaf >= 2;
+  struct PairedScope { bool& paired; ~PairedScope() { paired = false; } } pairedScope{m_paired};
+  const int count = m_paired ? numPrims : numTriangles;
+  if (m_paired) BVH_CHECK(hipMemcpyAsync(m_primFirst, hostPrimFirst, sizeof(int) * (size_t) count, hipMemcpyHostToDevice, stream));
+  const int* primFirst = m_paired ? m_primFirst : nullptr;
   const int block = 256;
-  const int grid  = (numTriangles + block - 1) / block;
+  const int grid  = (count + block - 1) / block;
   hipLaunchKernelGGL(initBoundsKernel, dim3(1), dim3(64), 0, stream, m_bounds);
-  hipLaunchKernelGGL(triangleBoxesKernel, dim3(grid), dim3(block), 0, stream, attributes, indices, soup, instances, numTriangles, m_primLo, m_primHi, m_bounds);
-  BVH_CHECK(buildFromBoxes(stream, numTriangles, outNodes, outWide, nodeBase, 0, triangleBase, soup ? TWK_LEAF_WORLD : 0));
-  hipLaunchKernelGGL(emitTrianglesKernel, dim3(grid), dim3(block), 0, stream, attributes, indices, soup, instances, m_keysOut, numTriangles, outTriangles + 3 * (size_t) triangleBase, outShadeTriangles + TWK_SHADE_RECORD * (size_t) triangleBase);
+  hipLaunchKernelGGL(triangleBoxesKernel, dim3(grid), dim3(block), 0, stream, attributes, indices, soup, instances, primFirst, count, m_primLo, m_primHi, m_bounds);
+  BVH_CHECK(buildFromBoxes(stream, count, outNodes, outWide, nodeBase, 0, triangleBase, soup ? TWK_LEAF_WORLD : 0));
+  hipLaunchKernelGGL(emitTrianglesKernel, dim3(grid), dim3(block), 0, stream, attributes, indices, soup, instances, m_keysOut, count, outTriangles + 3 * (size_t) triangleBase, outShadeTriangles + TWK_SHADE_RECORD * (size_t) triangleBase,
+                     primFirst, m_paired ? m_slotOff : nullptr, (m_paired && outPairFlags) ? outPairFlags + triangleBase : nullptr);
   BVH_CHECK(hipGetLastError());
   float4 lo, hi;
   BVH_CHECK(hipMemcpyAsync(&lo, m_nodeLo, sizeof(float4), hipMemcpyDeviceToHost, stream));

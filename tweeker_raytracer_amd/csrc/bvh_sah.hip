@@ -435,18 +435,22 @@ __global__ void sahRootKernel(int count, int* innerParent, int2* range, SahActiv
 // half-area(node) / half-area(root), inner nodes and leaf primitives separately (cost = Cn * inner + Ct * leaf).
 __global__ void sahCostKernel(int count, int maxLeaf, const int* __restrict__ left, const int* __restrict__ right, const int* __restrict__ innerParent,
                               const int2* __restrict__ range, const float4* __restrict__ nodeLo, const float4* __restrict__ nodeHi,
-                              const unsigned long long* __restrict__ keys, const float4* __restrict__ primLo, const float4* __restrict__ primHi, double* out)
+                              const unsigned long long* __restrict__ keys, const float4* __restrict__ primLo, const float4* __restrict__ primHi, double* out,
+                              const int* __restrict__ slotOff /* bvh_build.h "pairs": first slot per sorted position, or nullptr = the position */)
 {
+  // triangles below sorted positions [first, first + positions), and whether the refit made one leaf of them
+  auto trianglesOf = [&](int2 rg) { return slotOff ? slotOff[rg.x + rg.y] - slotOff[rg.x] : rg.y; };
+  auto isLeaf = [&](int2 rg) { return rg.y <= maxLeaf && trianglesOf(rg) <= maxLeaf; };
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count - 1) return;
   const float rootArea = sahHalfArea(nodeHi[0].x - nodeLo[0].x, nodeHi[0].y - nodeLo[0].y, nodeHi[0].z - nodeLo[0].z);
   if (!(rootArea > 0.0f)) return;
   const int2 rg = range[i];
   const int parent = innerParent[i];
-  const bool collapsed = (rg.y <= maxLeaf);
-  if (collapsed && parent >= 0 && range[parent].y <= maxLeaf) return; // inside a collapsed subtree: not part of the final tree
+  const bool collapsed = isLeaf(rg);
+  if (collapsed && parent >= 0 && isLeaf(range[parent])) return; // inside a collapsed subtree: not part of the final tree
   const float area = sahHalfArea(nodeHi[i].x - nodeLo[i].x, nodeHi[i].y - nodeLo[i].y, nodeHi[i].z - nodeLo[i].z) / rootArea;
-  if (collapsed && parent >= 0) { atomicAdd(&out[1], (double) area * rg.y); return; } // a leaf of rg.y triangles
+  if (collapsed && parent >= 0) { atomicAdd(&out[1], (double) area * trianglesOf(rg)); return; } // a leaf of that many triangles
   atomicAdd(&out[0], (double) area);
   const int refs[2] = {left[i], right[i]};
   for (int side = 0; side < 2; ++side)
@@ -454,7 +458,7 @@ __global__ void sahCostKernel(int count, int maxLeaf, const int* __restrict__ le
     if (refs[side] >= 0) continue;
     const unsigned int prim = (unsigned int) (keys[~refs[side]] & 0xffffffffull); // a single-primitive leaf right below an inner node
     const float4 lo = primLo[prim], hi = primHi[prim];
-    atomicAdd(&out[1], (double) (sahHalfArea(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z) / rootArea));
+    atomicAdd(&out[1], (double) (sahHalfArea(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z) / rootArea) * trianglesOf(make_int2(~refs[side], 1)));
   }
 }
 
@@ -572,7 +576,7 @@ hipError_t BvhBuilder::accumulateSahCost(hipStream_t stream, int count)
   SAH_CHECK(reserveSah(1));
   SAH_CHECK(hipMemsetAsync(m_sahCost, 0, sizeof(double) * 2, stream));
   hipLaunchKernelGGL(sahCostKernel, dim3((count + 255) / 256), dim3(256), 0, stream, count, m_maxLeaf, m_left, m_right, m_innerParent, m_range, m_nodeLo, m_nodeHi,
-                     m_keysOut, m_primLo, m_primHi, m_sahCost);
+                     m_keysOut, m_primLo, m_primHi, m_sahCost, m_paired ? m_slotOff : nullptr);
   double h[2] = {0.0, 0.0};
   SAH_CHECK(hipMemcpyAsync(h, m_sahCost, sizeof(h), hipMemcpyDeviceToHost, stream));
   SAH_CHECK(hipStreamSynchronize(stream));

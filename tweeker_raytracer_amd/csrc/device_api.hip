@@ -176,6 +176,7 @@ static void readEnvironmentSwitches(TwkDevice_t* dev)
   if (const char* e = getenv("TWK_WIDE_ROOT")) dev->wideRoot = (atoi(e) != 0);
   if (const char* e = getenv("TWK_PACKED_QUEUE")) dev->packedQueue = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SLIM_STREAMS")) dev->slimStreams = (atoi(e) != 0);
+  if (const char* e = getenv("TWK_TRIANGLE_PAIRS")) dev->trianglePairs = (atoi(e) != 0);
   if (const char* e = getenv("TWK_SHADE_SORT")) dev->shadeSort = std::max(0, std::min(2, atoi(e)));
   if (const char* e = getenv("TWK_DENOISE_LDS_MAX_STEP")) dev->denoiseLdsMaxStep = dev->denoiseGeometryLdsMaxStep = std::max(0, std::min(128, atoi(e))); // A/B; 128 = the largest step (iterations <= 8)
   if (const char* e = getenv("TWK_TRACE_WAVES_RUNTIME")) dev->traceWavesForced = atoi(e); // A/B: 6 or 7 blocks per CU of the persistent trace kernel

@@ -301,6 +301,22 @@ try
 }
 TWK_CATCH("twk_debug_trace_queue")
 
+} // extern "C"
+
+// The references of pair leaves (device_types.h "triangle pairs") in a host copy of the quantised wide nodes, back in the form the
+// build gave them: whoever reads the acceleration structure on the host walks slots, not pair records. References are rewritten
+// in flattened scenes only, where every leaf is a world-space leaf.
+static void canonicalLeafReferences(TwkDevice dev, void* wideQ, size_t nodes)
+{
+  if (dev->d_trianglePairs.capacity() == 0) return;
+  int* words = static_cast<int*>(wideQ);
+  for (size_t i = 0; i < nodes; ++i)
+    for (int k = 12; k < 16; ++k)
+      if (words[16 * i + k] < 0) words[16 * i + k] = ~(~words[16 * i + k] | TWK_LEAF_WORLD);
+}
+
+extern "C" {
+
 int twk_debug_read_acceleration(TwkDevice dev, TwkAccelerationInfo* info, void* wideNodes, void* triangles, void* instances)
 try
 {
@@ -311,7 +327,11 @@ try
   info->root2 = (dev->wideRoot2 == TWK_BVH_SENTINEL) ? -1 : dev->wideRoot2; info->nodeFloats = 16;
   info->numNodes = (uint64_t) dev->wideNodesTotal; info->numTriangleSlots = dev->totalTriangles; info->numInstances = dev->instances.size(); // 4-ary nodes: the binary nodes' + the two of an 8-wide root
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  if (wideNodes) HIP_TRY(hipMemcpy(wideNodes, dev->d_wideQ, sizeof(float) * (size_t) info->nodeFloats * info->numNodes, hipMemcpyDeviceToHost));
+  if (wideNodes)
+  {
+    HIP_TRY(hipMemcpy(wideNodes, dev->d_wideQ, sizeof(float) * (size_t) info->nodeFloats * info->numNodes, hipMemcpyDeviceToHost));
+    canonicalLeafReferences(dev, wideNodes, (size_t) info->numNodes);
+  }
   if (triangles) HIP_TRY(hipMemcpy(triangles, dev->d_triangles, sizeof(float4) * 3 * dev->totalTriangles, hipMemcpyDeviceToHost));
   if (instances) HIP_TRY(hipMemcpy(instances, dev->d_instances, sizeof(DevInstance) * dev->instances.size(), hipMemcpyDeviceToHost));
   return TWK_SUCCESS;
@@ -338,6 +358,8 @@ try
   };
   q.nodes          = static_cast<const BvhNode*>(host(dev->d_nodes, sizeof(BvhNode) * dev->totalNodes));
   q.wideQ          = static_cast<const float4*>(host(dev->d_wideQ, sizeof(float4) * 4 * dev->wideNodesTotal));
+  if (q.wideQ) canonicalLeafReferences(dev, dev->hostScene.back().data(), dev->wideNodesTotal);
+  q.trianglePairs  = nullptr; // the host build walks the binary nodes and the slots
   q.topNodes       = static_cast<const float4*>(host(dev->d_topNodes, sizeof(float4) * 4 * TWK_TOP_NODES));
   q.topNodes7      = static_cast<const float4*>(host(dev->d_topNodes7, sizeof(float4) * 4 * TWK_TOP_NODES7));
   q.triangles      = static_cast<const float4*>(host(dev->d_triangles, sizeof(float4) * 3 * dev->totalTriangles));

@@ -164,6 +164,7 @@ struct TwkDevice_t
   DeviceArray<int> d_spill;
   bool packedQueue = true; // TWK_PACKED_QUEUE=0: A/B
   bool slimStreams = true; // TWK_SLIM_STREAMS=0: A/B (device_types.h LaunchParams::slimSlotBits)
+  bool trianglePairs = true; DeviceArray<float4> d_trianglePairs; // TWK_TRIANGLE_PAIRS=0: A/B (device_types.h "triangle pairs"); the records, empty when no reference names one
   uint64_t shadeBuilds[2] = {0, 0}; // the shadeKernel builds launched since the last reset, by launcher index (twk_debug_shade_builds)
   int shadeSort = 1;      // TWK_SHADE_SORT=0: slot order (A/B); 1: class order in every launch but the first of a pass; 2: in the first too
   DeviceArray<float4> d_firstHit; DeviceArray<int> d_firstHitInstance;

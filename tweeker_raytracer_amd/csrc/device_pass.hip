@@ -48,7 +48,7 @@ void twk::refreshParams(TwkDevice dev)
   p.attributes = dev->d_attributes; p.indices = dev->d_indices;
   p.materials = dev->d_materials; p.lights = dev->d_lights; p.camera = dev->d_camera;
   p.tlasRoot = dev->tlasRoot;
-  p.topNodes = dev->d_topNodes; p.topNodes7 = dev->d_topNodes7;
+  p.topNodes = dev->d_topNodes; p.topNodes7 = dev->d_topNodes7; p.trianglePairs = dev->d_trianglePairs;
   p.topRoot = dev->topCache ? (TWK_NODE_CACHED | 0) : dev->wideRoot1;
   p.topRoot2 = (dev->wideRoot2 == TWK_BVH_SENTINEL) ? TWK_BVH_SENTINEL : (dev->topCache ? (TWK_NODE_CACHED | 1) : dev->wideRoot2);
   p.twoLevel = dev->twoLevel ? 1 : 0;

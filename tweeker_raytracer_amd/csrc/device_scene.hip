@@ -195,6 +195,9 @@ try
       (rc = dev->d_wideNodes.allocate(2 * (numNodes + 2))) || // + the two nodes of an 8-wide root (wideRootKernel)
       (rc = dev->d_wideQ.allocate(4 * (numNodes + 2))) || (rc = dev->d_triangles.allocate(3 * numTris)) || (rc = dev->d_shadeTriangles.allocate(TWK_SHADE_RECORD * numTris)) ||
       (rc = dev->d_instances.allocate((size_t) numInstances))) return rc;
+  // unused nodes stay zero: a tree over pairs has fewer nodes than its triangles reserve
+  HIP_TRY(hipMemsetAsync(dev->d_nodes, 0, sizeof(BvhNode) * numNodes, dev->stream));
+  HIP_TRY(hipMemsetAsync(dev->d_wideNodes, 0, sizeof(BvhNode) * 2 * (numNodes + 2), dev->stream));
   for (const GeometryHost& g : dev->geometries)
   {
     HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
@@ -202,6 +205,21 @@ try
   }
 
   if (const char* e = getenv("TWK_MAX_LEAF")) dev->builder.setMaxLeaf(atoi(e)); // tuning knob, default 2 triangles per leaf
+  // Triangle pairs (device_types.h): the two halves of a quad are one primitive of every tree's build. pairFlags: per slot, whether
+  // a pair begins there — what the references of pair leaves are found by once the trees stand.
+  const bool pairs = dev->trianglePairs && dev->builder.maxLeaf() >= 2;
+  std::vector<std::vector<int>> primFirst(dev->geometries.size());
+  std::vector<size_t> geometryPairs(dev->geometries.size(), 0);
+  if (pairs)
+    for (size_t k = 0; k < dev->geometries.size(); ++k)
+      geometryPairs[k] = trianglePairs(dev->geometries[k].indices.data(), dev->geometries[k].numTriangles, primFirst[k]);
+  DeviceArray<int> pairFlags;
+  dev->d_trianglePairs.release();
+  if (pairs)
+  {
+    if ((rc = pairFlags.allocate(numTris))) return rc;
+    HIP_TRY(hipMemsetAsync(pairFlags, 0, sizeof(int) * numTris, dev->stream));
+  }
   DeviceArray<float> nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
   if (dev->costedCuts && (rc = nodeCost.allocate(numNodes))) return rc;
   struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder}; // the array does not outlive this call
@@ -213,7 +231,9 @@ try
     GeometryHost& g = dev->geometries[k];
     if (!needsBlas[k]) continue;
     HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes + 12 * (size_t) g.attributeBase, dev->d_indices + g.indexBase, g.numTriangles,
-                                        dev->d_nodes + g.nodeBase, dev->d_wideNodes + 2 * (size_t) g.nodeBase, g.nodeBase, dev->d_triangles, dev->d_shadeTriangles, g.triangleBase, g.rootBounds));
+                                        dev->d_nodes + g.nodeBase, dev->d_wideNodes + 2 * (size_t) g.nodeBase, g.nodeBase, dev->d_triangles, dev->d_shadeTriangles, g.triangleBase, g.rootBounds,
+                                        nullptr, nullptr, pairs ? primFirst[k].data() : nullptr, (int) primFirst[k].size(), pairFlags));
+    info.pairLeaves += geometryPairs[k];
     info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
     maxEnteredHeight = std::max(maxEnteredHeight, dev->builder.lastHeight());
   }
@@ -250,7 +270,9 @@ try
       HIP_TRY(hipGetLastError());
       HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
                                           dev->d_nodes + flatNodeBase[i], dev->d_wideNodes + 2 * (size_t) flatNodeBase[i], flatNodeBase[i],
-                                          dev->d_triangles, dev->d_shadeTriangles, flatTriangleBase[i], bounds, soup, dev->d_instances));
+                                          dev->d_triangles, dev->d_shadeTriangles, flatTriangleBase[i], bounds, soup, dev->d_instances,
+                                          pairs ? primFirst[inst.geometry].data() : nullptr, (int) primFirst[inst.geometry].size(), pairFlags));
+      info.pairLeaves += geometryPairs[inst.geometry];
       info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
       maxFlatHeight = std::max(maxFlatHeight, dev->builder.lastHeight());
       boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
@@ -319,6 +341,13 @@ try
     if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
   }
   launchQuantizeWide(dev->d_wideNodes, dev->d_wideQ, (int) dev->wideNodesTotal, dev->stream);
+  // pair leaves get their records and their references in the structures the persistent kernel reads: a flattened scene only
+  // (device_types.h "triangle pairs": a two-level scene's references have no free bit)
+  if (pairs && numEntered == 0 && info.pairLeaves > 0)
+  {
+    if ((rc = dev->d_trianglePairs.allocate(4 * (numTris / 2 + 1)))) return rc;
+    launchPairLeaves(dev->d_wideQ, (int) dev->wideNodesTotal, pairFlags, (int) numTris, dev->d_triangles, dev->d_trianglePairs, dev->stream);
+  }
   if ((rc = dev->d_topNodes.ensure(4 * TWK_TOP_NODES)) || (rc = dev->d_topNodes7.ensure(4 * TWK_TOP_NODES7))) return rc;
   launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
   launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
@@ -327,6 +356,7 @@ try
   dev->d_wideNodes.release();
 
   info.maxTraversalDepth = (uint64_t) traversalDepth;
+  info.pairTriangles = 2 * info.pairLeaves;
   info.triangleSlots = numTris; info.nodes = numNodes; info.instances = (uint64_t) numInstances; info.flattenedInstances = (uint64_t) (numInstances - numEntered);
   info.buildMilliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - buildStart).count();
   dev->buildInfo = info;

@@ -245,7 +245,23 @@ struct LaunchParams
   // twk_set_sample_offset (default 0): iteration i seeds its random numbers as iteration i + sampleOffset (shade_device.h
   // primaryRay); whatever counts samples — the running mean's weight, "iteration 0 starts afresh", the moments' n — does not see it.
   unsigned int sampleOffset;
+  // Triangle pairs (below), 4 float4 per record at index (first slot / 2); nullptr when no reference names one.
+  const float4* trianglePairs;
 };
+
+// Triangle pairs. The two halves of a quad — triangles 2k, 2k + 1 of a geometry with the index triples (a, b, c), (c, d, a), what
+// every mesh generator emits — are ONE primitive of the build (bvh_build.h trianglePairs): they share a leaf, in consecutive slots,
+// first triangle first. Slots, binary nodes and shading records are what they always were. Beside them a pair has a record of its
+// four distinct vertices, 64 bytes instead of the 96 of its two slots:
+//   [0] w0.xyz, primitive of T0   [1] w1.xyz, primitive of T1   [2] w2.xyz, instance   [3] w3.xyz, first slot
+//   T0 = (w0, w1, w2) is slot `first`, T1 = (w2, w3, w0) slot `first + 1`.
+// In a scene whose instances are all flattened every leaf reference carries TWK_LEAF_WORLD, so the bit says nothing there: in
+// the structures only the persistent kernel reads (wideQ, the two top-of-tree copies, the tile entry lists made from them) the
+// reference of a pair leaf has the bit CLEARED, and its record is trianglePairs[4 * (first slot >> 1)] (two pairs never share a
+// slot). The flattened, cutout-free builds of traceKernel test such a leaf with four loads and one woopIntersectPair
+// (trace_device.h); the cutout builds mask the bit off as they always did and run the slot loop. Two-level scenes have no free
+// bit in a reference (bit 30 tells a world-space leaf from an instance there): their trees are built from the same pairs, their
+// references are not rewritten. TWK_TRIANGLE_PAIRS=0: no pairs in the build, no rewritten reference.
 
 // Slim streams: the hit record's slot word <-> (triangle slot, instance). A miss is -1 on both sides.
 TWK_HD int packSlotWord(int slotBits, int triangleSlot, int instance) { return triangleSlot | (int) ((unsigned int) instance << slotBits); }

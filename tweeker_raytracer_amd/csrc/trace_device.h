@@ -146,6 +146,112 @@ TWK_D bool woopIntersect(const WoopConstants& w, const V3& o, const V3& p0, cons
   return !mixedSigns & (det != 0.0f) & (tt > tmin);
 }
 
+// The two halves of a quad in one test (device_types.h "triangle pairs"): T0 = (p0, p1, p2) and T1 = (p2, p3, p0), each with the
+// very results of its own woopIntersect — hit, t, beta, gamma bit for bit. What the two share is computed once: the shared
+// vertices p0 and p2 are subtracted, permuted and sheared once, and the edge function of the shared diagonal is T0's V
+// negated: T1's V is fl(fl(Cx Ay) - fl(Cy Ax)) and T0's fl(fl(Ax Cy) - fl(Ay Cx)), the same two products subtracted the other way
+// round, and rounding to nearest is symmetric. Only a ZERO differs under negation (x - x is +0 either way round), and a zero V
+// sends either triangle to its double-precision fallback, which for T1 starts from T1's own operands. The fallback is decided
+// per triangle: T1 takes the negation of T0's SINGLE-precision V whatever T0 itself went on to use.
+// In three steps, so that a caller can fetch p3 only when T0 is done and never holds four raw vertices (the seven-block build of
+// traceKernel has 72 registers): woopPairShared(p0, p2), woopPairFirst(p1) = T0, woopPairSecond(p3) = T1.
+// The two fallbacks convert the same four shared coordinates to double and multiply the same two pairs of them, and hipcc hoists
+// what two branches share in front of both: four conversions and two double-precision products in EVERY pair test, twelve
+// registers held across it. On the device the shared coordinates therefore enter a fallback through an empty asm, which ties
+// their conversions to the branch. (The values are what they were.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TWK_WOOP_PAIR_RARE(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+#else
+#define TWK_WOOP_PAIR_RARE(a, b, c, d)
+#endif
+struct WoopPairShared { float Ax, Ay, Az, Cx, Cy, Cz, Vs; }; // the sheared shared vertices; T0's V in single precision
+
+TWK_D void woopPairShared(const WoopConstants& w, const V3& o, const V3& p0, const V3& p2, WoopPairShared& s)
+{
+  const WoopPermutation f = woopFlags(w.perm);
+  const V3 A = p0 - o, C = p2 - o;
+  float Akx, Aky, Akz, Ckx, Cky, Ckz;
+  woopPermute(f, A, Akx, Aky, Akz);
+  woopPermute(f, C, Ckx, Cky, Ckz);
+  s.Ax = Akx - w.Sx * Akz; s.Ay = Aky - w.Sy * Akz;
+  s.Cx = Ckx - w.Sx * Ckz; s.Cy = Cky - w.Sy * Ckz;
+  s.Az = w.Sz * Akz; s.Cz = w.Sz * Ckz;
+  s.Vs = s.Ax * s.Cy - s.Ay * s.Cx;
+}
+
+// The rest of a test once its three edge functions stand: woopIntersect's own lines. (Az, Bz, Cz) belong to (U, V, W).
+TWK_D bool woopFinish(float U, float V, float W, float Az, float Bz, float Cz, float tmin, float& t, float& beta, float& gamma)
+{
+  const bool mixedSigns = ((U < 0.0f) | (V < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (V > 0.0f) | (W > 0.0f));
+  const float det = U + V + W;
+  const float T = U * Az + V * Bz + W * Cz;
+  const float rcpDet = 1.0f / det;
+  const float tt = T * rcpDet;
+  t     = tt;
+  beta  = V * rcpDet;
+  gamma = W * rcpDet;
+  return !mixedSigns & (det != 0.0f) & (tt > tmin);
+}
+
+// T0 = woopIntersect(p0, p1, p2)
+TWK_D bool woopPairFirst(const WoopConstants& w, const V3& o, const WoopPairShared& s, const V3& p1, float tmin, float& t, float& beta, float& gamma)
+{
+  const V3 B = p1 - o;
+  float Bkx, Bky, Bkz;
+  woopPermute(woopFlags(w.perm), B, Bkx, Bky, Bkz);
+  const float Bx = Bkx - w.Sx * Bkz, By = Bky - w.Sy * Bkz;
+  float U = s.Cx * By - s.Cy * Bx;
+  float V = s.Vs;
+  float W = Bx * s.Ay - By * s.Ax;
+  if ((U == 0.0f) | (V == 0.0f) | (W == 0.0f))
+  {
+    float Ax = s.Ax, Ay = s.Ay, Cx = s.Cx, Cy = s.Cy;
+    TWK_WOOP_PAIR_RARE(Ax, Ay, Cx, Cy)
+    const double CxBy = (double) Cx * (double) By, CyBx = (double) Cy * (double) Bx;
+    U = (float) (CxBy - CyBx);
+    const double AxCy = (double) Ax * (double) Cy, AyCx = (double) Ay * (double) Cx;
+    V = (float) (AxCy - AyCx);
+    const double BxAy = (double) Bx * (double) Ay, ByAx = (double) By * (double) Ax;
+    W = (float) (BxAy - ByAx);
+  }
+  return woopFinish(U, V, W, s.Az, w.Sz * Bkz, s.Cz, tmin, t, beta, gamma);
+}
+
+// T1 = woopIntersect(p2, p3, p0): its A is the shared C, its B is p3, its C is the shared A
+TWK_D bool woopPairSecond(const WoopConstants& w, const V3& o, const WoopPairShared& s, const V3& p3, float tmin, float& t, float& beta, float& gamma)
+{
+  const V3 D = p3 - o;
+  float Dkx, Dky, Dkz;
+  woopPermute(woopFlags(w.perm), D, Dkx, Dky, Dkz);
+  const float Dx = Dkx - w.Sx * Dkz, Dy = Dky - w.Sy * Dkz;
+  float U = s.Ax * Dy - s.Ay * Dx;
+  float V = -s.Vs;
+  float W = Dx * s.Cy - Dy * s.Cx;
+  if ((U == 0.0f) | (V == 0.0f) | (W == 0.0f))
+  {
+    float Ax = s.Ax, Ay = s.Ay, Cx = s.Cx, Cy = s.Cy;
+    TWK_WOOP_PAIR_RARE(Ax, Ay, Cx, Cy)
+    const double AxDy = (double) Ax * (double) Dy, AyDx = (double) Ay * (double) Dx;
+    U = (float) (AxDy - AyDx);
+    const double CxAy = (double) Cx * (double) Ay, CyAx = (double) Cy * (double) Ax;
+    V = (float) (CxAy - CyAx);
+    const double DxCy = (double) Dx * (double) Cy, DyCx = (double) Dy * (double) Cx;
+    W = (float) (DxCy - DyCx);
+  }
+  return woopFinish(U, V, W, s.Cz, w.Sz * Dkz, s.Az, tmin, t, beta, gamma);
+}
+
+struct WoopPairResult { bool hit0, hit1; float t0, beta0, gamma0, t1, beta1, gamma1; };
+
+TWK_D void woopIntersectPair(const WoopConstants& w, const V3& o, const V3& p0, const V3& p1, const V3& p2, const V3& p3,
+                             float tmin, WoopPairResult& r)
+{
+  WoopPairShared s;
+  woopPairShared(w, o, p0, p2, s);
+  r.hit0 = woopPairFirst(w, o, s, p1, tmin, r.t0, r.beta0, r.gamma0);
+  r.hit1 = woopPairSecond(w, o, s, p3, tmin, r.t1, r.beta1, r.gamma1);
+}
+
 struct TraceResult
 {
   float t, beta, gamma;

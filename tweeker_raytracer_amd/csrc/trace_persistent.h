@@ -108,6 +108,9 @@ traceKernel(LaunchParams p, int depth)
   constexpr int STACK_LDS = W7 ? TWK_TRACE_STACK_LDS7 : TWK_TRACE_STACK_LDS;
   constexpr int TOP_NODES = W7 ? TWK_TOP_NODES7 : TWK_TOP_NODES;
   constexpr int STACK_ROWS = STACK_LDS + 1; // + 1 dummy row, see the node step
+  // Pair leaves (device_types.h "triangle pairs"): the flattened, cutout-free builds test a leaf whose reference lacks
+  // TWK_LEAF_WORLD as ONE four-vertex record. (The cutout builds visit candidates in slot order and keep the slot loop.)
+  constexpr bool PAIRS = !CUTOUT && !TWO_LEVEL;
   __shared__ int stackStorage[STACK_ROWS * TWK_TRACE_BLOCK];
   __shared__ float4 topCache[TOP_NODES * TWK_TOP_STRIDE];         // device_types.h TWK_NODE_CACHED / TWK_TOP8_NODES
   int* ldsStack = stackStorage + threadIdx.x;
@@ -348,7 +351,14 @@ traceKernel(LaunchParams p, int depth)
             woopSetup(dir, woop); // world-space constants: flattened instances are tested without entering anything
             currentInstance = -1; sp = 0; guard = 0;
             node = p.topRoot;
-            if (p.topRoot2 != TWK_BVH_SENTINEL) { ldsStack[0] = p.topRoot2; sp = 1; } // the root's second node (wideRootKernel)
+            if (p.topRoot2 != TWK_BVH_SENTINEL)
+            {
+              // the root's second node (wideRootKernel). Pinned to a scalar register HERE: left alone, hipcc copies the launch
+              // parameter into a vector register once, ahead of the outer loop, and holds it there for the whole kernel.
+              int root2 = p.topRoot2;
+              asm volatile("" : "+s"(root2));
+              ldsStack[0] = root2; sp = 1;
+            }
             if (COUNT) rayClock = (unsigned int) __builtin_readcyclecounter();
             if (PRIMARY && entryA.x > 0)
             {
@@ -523,6 +533,7 @@ traceKernel(LaunchParams p, int depth)
           {
             // a leaf of 1..4 consecutive triangle slots (bvh_build.hip: at most TWK_MAX_LEAF, default 2; a flattened instance: all of its triangles)
             triFirst = payload & 0x0fffffff; triLast = triFirst + ((payload >> 28) & 3);
+            if (PAIRS && !(payload & TWK_LEAF_WORLD)) triLast = triFirst - 2; // a pair leaf: no pass of the slot loop, see the triangle phase
             pop = 1u;
           }
         }
@@ -543,6 +554,29 @@ traceKernel(LaunchParams p, int depth)
         {                                                                                                                      \
           pop = 0u; state = (state & ~ST_HAS_RAY) | ST_DONE; triLast = -1;                                                     \
         }                                                                                                                      \
+      }
+      // A pair leaf: four lane loads instead of six, the two shared vertices transformed once, the shared diagonal's edge function
+      // computed once, and both triangles in one pass with all of the leaf's lanes. Merged in slot order, the second only while
+      // the ray is still alive: ties and any-hit termination are those of two passes of the loop below.
+      // (The leaf step marks it with triLast == triFirst - 2. A lane without a leaf has 0 and -1; a lane whose any-hit ray ends in
+      // the slot loop has -1 too, whatever its first slot, which is why this block comes BEFORE the loop.)
+      if (PAIRS && triLast == triFirst - 2)
+      {
+        const float4* rec = p.trianglePairs + 4 * (size_t) (triFirst >> 1);
+        const float4 w0 = rec[0], w1 = rec[1], w2 = rec[2], w3 = rec[3];
+        if (COUNT) triCount += 2;
+        TWK_WAVE_STEP(triWaveSteps)
+        const int prim = __float_as_int(w0.w), pairInstance = __float_as_int(w2.w); // T1's primitive is the next one
+        WoopPairShared shared;
+        woopPairShared(woop, ray.o, v3(w0), v3(w2), shared);
+        float t, beta, gamma;
+        const bool hit0 = woopPairFirst(woop, ray.o, shared, v3(w1), tmin, t, beta, gamma);
+        TWK_MERGE_HIT(hit0, t, beta, gamma, pairInstance, prim, triFirst)
+        // (Fetching the fourth vertex only now, its address tied to T0's result by an empty asm, takes four registers fewer — 66
+        // against 70 of the seven-block build's 72 — and a second round trip: the frame rate was the same within its spread,
+        // profiles/r07_triangle_pairs.md.)
+        const bool hit1 = woopPairSecond(woop, ray.o, shared, v3(w3), tmin, t, beta, gamma) & ((state & ST_HAS_RAY) != 0u);
+        TWK_MERGE_HIT(hit1, t, beta, gamma, pairInstance, prim + 1, triFirst + 1)
       }
       // (Postponed leaves, slots stored by component, pair fetch, handing a leaf's second triangle to an idle lane: all built,
       // measured and not kept — DESIGN.md 4.1.)

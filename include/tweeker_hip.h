@@ -585,8 +585,8 @@ typedef struct TwkTemporalFrame { const void* colour; const void* moments; const
  * allocated on first use and dropped by twk_temporal_reset, a change of resolution, twk_clear_scene and twk_build. The first call
  * after that has no history: it copies the frame through and keeps it. The results go to internal buffers:
  * twk_get_temporal_device_pointers (colour in the output format, merged moments f32; either pair may be NULL), twk_read_temporal
- * (RGBA32F, widened exactly) and twk_read_temporal_moments. What it is not: see csrc/temporal_device.h — no motion vectors (the
- * scene is static between builds), no environment reprojection (a miss never has history), pinhole only; a frame tiled over several
+ * (RGBA32F, widened exactly) and twk_read_temporal_moments. What it is not: see csrc/temporal_device.h — motion of one matrix per
+ * instance only, after twk_update_instance_transform ("Moving an object" below), no environment reprojection (a miss never has history), pinhole only; a frame tiled over several
  * devices is merged by twk_temporal_accumulate_assembled ("The temporal seam on several devices" below). */
 int twk_temporal_accumulate(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
                             int width, int height, void* colourOut, void* historyOut, void* momentsOut);
@@ -834,7 +834,7 @@ int twk_cascade_resolve_host(const TwkCascade* cp, const TwkCascadeResolve* rp, 
  * The complete definition is csrc/temporal_cascade_device.h; tests/temporal_cascade_restate.py restates it in numpy. What it is: a
  * linear, capped, bilinear carry-over of sums and counts. What it is NOT: exact counting — n (layer 0 .w) becomes a weighted, capped
  * count that is no integer, and the interpolation mixes the counts of neighbouring pixels; alpha and the luminance moments stay the
- * existing merge's business; no motion vectors, no environment reprojection (a miss never has history), pinhole only (tiles: the
+ * existing merge's business; motion of one matrix per instance only ("Moving an object" below), no environment reprojection (a miss never has history), pinhole only (tiles: the
  * assembled layers of a tiled frame go through twk_temporal_accumulate_assembled); the paper's variance term is not reprojected; the noise estimate and the adaptive passes do not see the merged layers. */
 
 /* EXPLICIT form; asynchronous, one kernel on the handle's stream. currentLayers, historyLayers and layersOut are device buffers of
@@ -923,6 +923,74 @@ int twk_temporal_rectify_host(const TwkTemporal* tp, const TwkTemporalRectify* r
                               int width, int height, float* colourOut, float* momentsOut, float* trustOut);
 int twk_temporal_cascade_trusted_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
                                       const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, int width, int height, float* layersOut);
+
+/* ---- Moving an object: the instance-transform update and motion in the temporal merges — new calls, ABI stays 9, no existing
+ * struct, enum or constant changes; without them no kernel and no bit of any existing call changes --------------------------------
+ * twk_update_instance_transform moves an instance and KEEPS the temporal history (twk_clear_scene + twk_build would drop it). The
+ * merges then look the history up where the object was: a surface point of instance i now at world g was at
+ * g' = M_prev,i . M_cur,i^-1 . g when the history was taken — one matrix per instance, TwkInstanceMotion. The own-buffer and the
+ * assembled forms of twk_temporal_accumulate and twk_temporal_accumulate_rectified do this by themselves; the explicit forms with a
+ * table are the *_moving calls below. The loop of "The temporal seam" with a moving object in it:
+ *   twk_update_instance_transform(dev, id, M);                            (the history stays; the geometry AOV is stale)
+ *   twk_set_sample_offset; twk_launch 0 .. spp-1; twk_render_geometry; twk_temporal_accumulate [_rectified];
+ * The complete definition is csrc/temporal_motion_device.h; tests/temporal_motion_restate.py restates it in numpy. What it is not:
+ * no deforming geometry or vertex updates, no per-vertex motion, no motion blur, no moving lights (an instance that carries a
+ * light is refused), no selective rebuild (every update rebuilds the whole acceleration structure, as twk_build does), no
+ * environment reprojection, pinhole only. Shadows and inter-reflections that the move changes ELSEWHERE are stale history like a
+ * light edit's: the rectified merge discounts them.
+ *
+ * One record per instance, indexed by instance: previousFromCurrent is X = M_prev . M_cur^-1, row-major 3 x 4; moved = 0 says the
+ * instance is where it was, and X (written as the identity) is never read. reserved: 0. */
+typedef struct TwkInstanceMotion { float previousFromCurrent[12]; unsigned int moved; unsigned int reserved[3]; } TwkInstanceMotion; /* 64 bytes */
+/* Pure CPU, no device. moved = 0 when the 24 words of previous and current are bit-equal; else X is computed in double from the
+ * float inputs in a fixed operation order (the cofactor inverse of current, then the product row by row, left to right) and each
+ * element is rounded to float once. TWK_ERROR_INVALID_VALUE: a NULL argument, an input that is not finite, a current whose 3 x 3
+ * determinant is zero or not finite. */
+int twk_instance_motion(const float previous[12], const float current[12], TwkInstanceMotion* out);
+/* ≙ an OptiX instance-transform update followed by an IAS rebuild. Replaces the instance's object-to-world matrix (row-major 3 x 4,
+ * as twk_add_instance takes it) and rebuilds the acceleration structure with the code of twk_build; synchronises, and
+ * twk_get_build_info then describes this rebuild. After it the handle renders like a fresh handle built with the new transforms,
+ * byte for byte; the geometry AOV is stale (twk_render_geometry first), adaptive state is dropped as twk_build drops it, and the
+ * temporal history — colour, moments, geometry, camera, cascade layers, trust — is KEPT, together with the transforms of every
+ * instance as of the frame the history was taken (refreshed when a merge swaps the history). Several updates may happen between
+ * two merges. On several devices every handle is updated by the caller. TWK_ERROR_INVALID_STATE: before a successful twk_build.
+ * TWK_ERROR_INVALID_VALUE: a NULL handle or transform (before any HIP call), an id out of range, a transform that is not finite or
+ * whose 3 x 3 determinant is zero or not finite, and an instance with idLight >= 0 (the light definition holds the emitter's
+ * position and would disagree; moving emitters is not supported). A rebuild that fails leaves the handle unbuilt, as twk_build does. */
+int twk_update_instance_transform(TwkDevice dev, int idInstance, const float transform[12]);
+/* The instance's transform as it is now. TWK_ERROR_INVALID_VALUE: a NULL argument, an id out of range. */
+int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12]);
+/* EXPLICIT form of twk_temporal_accumulate (rp NULL; trustOut must then be NULL) or of twk_temporal_accumulate_rectified (rp given),
+ * with a table: motion is a DEVICE pointer to numMotion records, 16-byte aligned, indexed by instance; an instance beyond the table
+ * is unmoved. motion NULL or numMotion 0 launches the existing kernels: byte for byte the existing call. Otherwise, per candidate
+ * pixel, g' = X g for a moved instance (no history unless g' is finite), the projection and the taps' position test run on g', and
+ * everything after is the existing merge. All refusals of those calls apply; also TWK_ERROR_INVALID_VALUE: current NULL (there is
+ * no own-buffer form: the own-buffer calls build their table themselves), numMotion < 0, a table that is not 16-byte aligned, an
+ * output that overlaps the table. Asynchronous on the handle's stream; the table is read by the launch, not copied. */
+int twk_temporal_accumulate_moving(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalRectify* rp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                                   const TwkInstanceMotion* motion, int numMotion, int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut);
+/* twk_temporal_accumulate_cascade (trust NULL) or twk_temporal_accumulate_cascade_trusted (trust given) with a table, as above. */
+int twk_temporal_accumulate_cascade_moving(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                           const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust,
+                                           const TwkInstanceMotion* motion, int numMotion, int width, int height, void* layersOut);
+/* Pure CPU, no device: the same definitions compiled for the host, on host arrays as twk_temporal_rectify_host and
+ * twk_temporal_cascade_trusted_host take them; motion is a HOST array of numMotion records (NULL or 0: none, and the results are
+ * those of the existing host forms). rp NULL: the plain merge (trustOut must be NULL); trust NULL: the untrusted cascade merge. */
+int twk_temporal_moving_host(const TwkTemporal* tp, const TwkTemporalRectify* rp, const float* colour, const float* moments, const float* geometry,
+                             const float* historyColour, const float* historyMoments, const float* historyGeometry, const TwkCameraDefinition* historyCamera,
+                             const TwkInstanceMotion* motion, int numMotion, int width, int height, float* colourOut, float* momentsOut, float* trustOut);
+int twk_temporal_cascade_moving_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                                     const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, const TwkInstanceMotion* motion, int numMotion,
+                                     int width, int height, float* layersOut);
+/* OWN-BUFFER and ASSEMBLED forms (twk_temporal_accumulate, twk_temporal_accumulate_rectified, twk_temporal_accumulate_assembled,
+ * twk_temporal_accumulate_assembled_rectified): while every instance's transform is bit-equal to the one it had when the history
+ * was taken — the only state there is without twk_update_instance_transform — they launch what they always launched. Otherwise
+ * they build the table on the host (twk_instance_motion per instance), upload it to a buffer of the handle (freed with the
+ * history) and launch the Moving builds, the cascade's own-buffer merge included. This call hands out the table the last such
+ * merge used: *count records, 0 if it used none; host may be NULL when capacity is 0. TWK_ERROR_INVALID_VALUE: a NULL handle or
+ * count, a capacity below the count (*count is written all the same: a first call with capacity 0 asks for it). On tiles, twk_assemble_devices_with_geometry refuses (TWK_ERROR_INVALID_STATE) a source handle
+ * whose instance transforms are not bit-equal to the primary's. */
+int twk_read_temporal_motion(TwkDevice dev, TwkInstanceMotion* host, size_t capacity, int* count);
 
 /* ---- Assembling a tiled frame — new calls, ABI stays 9, no existing struct changes; without them no kernel and no bit of any
  * picture changes ----------------------------------------------------------------------------------------------------------------
@@ -1160,6 +1228,12 @@ int twk_app_get_temporal(TwkApp app, int* enabled, TwkTemporal* tp, int* frames,
  * keys: how many of the four keys the description holds — rtigo3_hip refuses any of them without "temporalAccumulation 1", before
  * a device is created. */
 int twk_app_get_temporal_rectify(TwkApp app, int* enabled, TwkTemporalRectify* rp, int* keys);
+/* An object that moves in that loop: "temporalInstanceStep <idInstance> <dx> <dy> <dz>" (idInstance >= 0, a finite step; another line
+ * is dropped with a warning). Before every frame after the first, rtigo3_hip translates that instance by one more step with
+ * twk_update_instance_transform on every device; the merges then carry its history along ("Moving an object" above). *idInstance
+ * -1: the description has no such key. rtigo3_hip refuses the key without "temporalAccumulation 1", for an id beyond the scene's
+ * instances and for an instance that carries a light. TwkAppInfo is unchanged. */
+int twk_app_get_temporal_motion(TwkApp app, int* idInstance, float step[3]);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

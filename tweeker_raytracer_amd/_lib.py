@@ -140,6 +140,13 @@ class TemporalFrame(C.Structure):
         super().__init__(colour, moments, geometry, camera if camera is not None else CameraDefinition())
 
 
+class InstanceMotion(C.Structure):
+    """≙ TwkInstanceMotion (64 bytes): one instance's record of a motion table — previousFromCurrent, the row-major 3 x 4 matrix that
+    carries a point of the instance in this frame to where it was in the history's frame, and moved (0: the instance is where it
+    was, the matrix is not read). instance_motion(previous, current) fills one."""
+    _fields_ = [("previousFromCurrent", C.c_float * 12), ("moved", C.c_uint), ("reserved", C.c_uint * 3)]
+
+
 class Noise(C.Structure):
     """≙ TwkNoise: parameters of twk_estimate_noise. minSamples: a pixel with fewer samples is `unknown`; darkFloor: added to the
     mean the standard error is divided by. Without arguments: twk_noise_defaults."""
@@ -297,6 +304,8 @@ SYMBOLS = [
     "twk_temporal_rectify_defaults", "twk_temporal_accumulate_rectified", "twk_get_temporal_trust_device_pointer", "twk_read_temporal_trust",
     "twk_temporal_accumulate_cascade_trusted", "twk_temporal_accumulate_assembled_rectified", "twk_temporal_rectify_host", "twk_temporal_cascade_trusted_host",
     "twk_temporal_accumulate_cascade", "twk_temporal_enable_cascade", "twk_get_temporal_cascade_device_pointer", "twk_read_temporal_cascade", "twk_temporal_cascade_host",
+    "twk_instance_motion", "twk_update_instance_transform", "twk_get_instance_transform", "twk_temporal_accumulate_moving", "twk_temporal_accumulate_cascade_moving",
+    "twk_temporal_moving_host", "twk_temporal_cascade_moving_host", "twk_read_temporal_motion", "twk_app_get_temporal_motion",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",
     "twk_read_assembled_geometry", "twk_temporal_accumulate_assembled", "twk_app_get_temporal", "twk_app_get_temporal_rectify",

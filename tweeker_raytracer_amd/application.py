@@ -187,6 +187,15 @@ class Application:
         return bool(on.value), rp, keys.value
 
     @property
+    def temporalMotion(self):
+        """(idInstance, (dx, dy, dz)) from "temporalInstanceStep" of the system description: in the loop of `temporal`, that instance is
+        translated by one more step before every frame after the first (Device.updateInstanceTransform on every device).
+        idInstance -1: no such key. rtigo3_hip refuses the key without "temporalAccumulation 1" and for an instance with a light."""
+        inst, step = C.c_int(-1), (C.c_float * 3)()
+        L.check(L.lib.twk_app_get_temporal_motion(self._h, C.byref(inst), step))
+        return inst.value, tuple(step)
+
+    @property
     def fireflyCascade(self):
         """(enabled, Cascade, CascadeResolve) from "fireflyCascade", "fireflyCascadeLayers", "fireflyCascadeStart",
         "fireflyCascadeBase", "fireflyCascadeKappa" of the system description; initDevice enables the device's cascade when the key

@@ -219,6 +219,13 @@ static int assembleDevices(const char* name, TwkDevice primary, unsigned int pla
       return refuse(TWK_ERROR_INVALID_STATE, "the geometry AOV of the handle with index " + std::to_string(dev->index) + " is older than its camera, state or scene: twk_render_geometry_tile first");
     if (dev->cameras.empty() || primary->cameras.empty() || memcmp(&dev->cameras[0], &primary->cameras[0], sizeof(TwkCameraDefinition)) != 0)
       return refuse(TWK_ERROR_INVALID_VALUE, "camera 0 of the handle with index " + std::to_string(dev->index) + " is not the primary handle's: the tile shares would be of different views");
+    // twk_update_instance_transform is made on every handle by the caller: a share of a scene whose object is elsewhere is refused
+    // (handles of the same instances only: what else they may differ in is as it was)
+    if (dev->instances.size() == primary->instances.size())
+      for (size_t i = 0; i < dev->instances.size(); ++i)
+        if (memcmp(dev->instances[i].transform, primary->instances[i].transform, sizeof(float) * 12) != 0)
+          return refuse(TWK_ERROR_INVALID_STATE, "instance " + std::to_string(i) + " of the handle with index " + std::to_string(dev->index) +
+                                                 " is not where the primary handle has it: twk_update_instance_transform on every handle");
   }
 
   // every source: recorded launches rendered, buffers allocated, counts current, then an event on its stream

@@ -50,7 +50,8 @@ void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, con
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
 void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
-                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream);
+                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream,
+                    const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
 unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
                                    const AdaptiveConstants& k, int numCUs, hipStream_t stream);
 unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, unsigned int* pathOffset,
@@ -58,12 +59,12 @@ unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 void launchCascadeResolve(const CascadeConstants& k, float kappa, const float4* layers, float* lambda, int width, int height, void* resolved, bool half, hipStream_t stream);
 void launchTemporalCascade(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, float4* layersOut,
-                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream);
+                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
 void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, float4* layersOut,
-                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream);
+                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
 void launchTemporalRectify(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                            const float4* historyGeometry, float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut,
-                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream);
+                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
 void launchAssemble(const AssembleShape& s, const AssembleTable& table, int count, hipStream_t stream);
 }
 
@@ -193,6 +194,12 @@ struct TwkDevice_t
   DeviceArray<float4> d_temporal[2][3]; DevicePicture temporalColour;
   int temporalKept = 0; bool temporalHasHistory = false;
   TwkCameraDefinition temporalCamera;
+  // twk_update_instance_transform keeps the history, so beside its camera the history has the transform of every instance as of
+  // its frame (temporalTransforms, 12 floats each, refreshed when a merge swaps the history). A merge that finds an instance
+  // elsewhere builds the table of temporal_motion_device.h on the host (temporalMotion; empty: the last own-buffer merge used
+  // none — twk_read_temporal_motion) and uploads it to d_temporalMotion, grown while idle. All dropped by dropTemporal.
+  std::vector<float> temporalTransforms;
+  std::vector<TwkInstanceMotion> temporalMotion; DeviceArray<TwkInstanceMotion> d_temporalMotion;
   // twk_temporal_accumulate_rectified (temporal_rectify_device.h): the two scratch streams its first launch writes and its second
   // reads, shared by the explicit and the own-buffer form; and the own-buffer form's trust plane, one
   // float per pixel of the temporal result, valid while the last own-buffer merge was a rectified one. Freed by dropTemporal.
@@ -370,7 +377,8 @@ CascadeOn cascadeFold(TwkDevice dev);
 // device_temporal_cascade.hip
 void dropTemporalCascade(TwkDevice dev);
 const char* temporalCascadeRefusal(TwkDevice dev);
-int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust = nullptr);
+int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust = nullptr,
+                       const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
 // device_assemble.hip
 void dropAssembled(TwkDevice dev);
 }

@@ -1,6 +1,7 @@
 // Scene assembly and the acceleration-structure build behind the C ABI (≙ Device::createGeometry / createInstance / createTLAS,
 // reference apps/rtigo3/src/Device.cpp:1339-1500).
 #include "device_handle.h"
+#include "temporal_motion_device.h" // instanceTransformUsable
 
 #include <algorithm>
 #include <chrono>
@@ -126,10 +127,12 @@ try
 }
 TWK_CATCH("twk_get_stream_layout")
 
-int twk_build(TwkDevice dev)
-try
+// Internal, no entry point: the build of the acceleration structure from the handle's geometries and instances as they are, on an
+// active handle — the body of twk_build and of twk_update_instance_transform (its refusals name twk_build, whose they are). Drops
+// the adaptive state and leaves the geometry AOV stale; the temporal history is the caller's business.
+static int buildScene(TwkDevice dev)
 {
-  int rc = activate(dev, "twk_build"); if (rc) return rc;
+  int rc;
   if (dev->geometries.empty() || dev->instances.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: the scene has no geometry or no instance");
   dropAdaptive(dev);
   dev->built = false; // until this build has succeeded: a failure below leaves no half-built scene to launch on
@@ -364,9 +367,47 @@ try
   dev->maxInstanceMaterial = maxMaterial; dev->maxInstanceLight = maxLight;
   dev->totalNodes = numNodes; dev->totalTriangles = numTris;
   dev->built = true; ++dev->buildSerial;
-  staleGeometry(dev); dropTemporal(dev); // the geometry AOV and the temporal history describe the scene that was
+  staleGeometry(dev); // the geometry AOV describes the scene that was
+  return TWK_SUCCESS;
+}
+
+int twk_build(TwkDevice dev)
+try
+{
+  int rc = activate(dev, "twk_build"); if (rc) return rc;
+  if ((rc = buildScene(dev))) return rc;
+  dropTemporal(dev); // the temporal history describes the scene that was
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_build")
+
+int twk_update_instance_transform(TwkDevice dev, int idInstance, const float transform[12])
+try
+{
+  const char* name = "twk_update_instance_transform";
+  const auto refuse = [name](int code, const char* text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  if (!transform) return refuse(TWK_ERROR_INVALID_VALUE, "NULL transform");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  if (idInstance < 0 || idInstance >= (int) dev->instances.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad instance id");
+  if (!instanceTransformUsable(transform)) return refuse(TWK_ERROR_INVALID_VALUE, "the transform is not finite, or its 3 x 3 determinant is zero or not finite");
+  if (dev->instances[idInstance].light >= 0)
+    return refuse(TWK_ERROR_INVALID_VALUE, "the instance carries a light (idLight >= 0): its light definition holds the emitter's position and would disagree; moving emitters is not supported");
+  memcpy(dev->instances[idInstance].transform, transform, sizeof(float) * 12);
+  return buildScene(dev); // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
+}
+TWK_CATCH("twk_update_instance_transform")
+
+int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12])
+try
+{
+  const char* name = "twk_get_instance_transform";
+  if (!dev || !transform) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + (dev ? ": NULL transform" : ": NULL device handle"));
+  if (idInstance < 0 || idInstance >= (int) dev->instances.size()) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": bad instance id");
+  memcpy(transform, dev->instances[idInstance].transform, sizeof(float) * 12);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_instance_transform")
 
 } // extern "C"

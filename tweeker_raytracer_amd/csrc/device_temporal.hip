@@ -4,6 +4,7 @@
 // device_temporal_cascade.hip's, which takes its TwkTemporal checks and its history camera from here. The merged colour is a
 // DevicePicture (device_handle.h); the history streams have its shape and are dropped and allocated with it.
 #include "device_handle.h"
+#include "temporal_motion_host.h"
 
 #include <cstring>
 #include <vector>
@@ -16,6 +17,7 @@ void twk::dropTemporal(TwkDevice dev)
   for (int s = 0; s < 2; ++s) dev->d_rectify[s].release();
   dev->d_temporalTrust.release();
   dev->temporalTrustValid = false; dev->temporalHasHistory = false;
+  dev->d_temporalMotion.release(); dev->temporalMotion.clear(); dev->temporalTransforms.clear();
   dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
 }
 
@@ -74,9 +76,38 @@ static int rectifyParameters(const char* name, const TwkTemporal* tp, const TwkT
   return TWK_SUCCESS;
 }
 
+// The table of the own-buffer merge about to be issued: one record per instance when the history's snapshot of the transforms
+// differs from the transforms as they are, uploaded on the stream; none (temporalMotion empty) while no instance has moved —
+// the only state there is without twk_update_instance_transform — or without a history.
+static int ownMotion(TwkDevice dev, const char* name)
+{
+  dev->temporalMotion.clear();
+  const size_t count = dev->instances.size();
+  if (!dev->temporalHasHistory || dev->temporalTransforms.size() != 12 * count) return TWK_SUCCESS;
+  bool moved = false;
+  for (size_t i = 0; i < count && !moved; ++i) moved = memcmp(&dev->temporalTransforms[12 * i], dev->instances[i].transform, 12 * sizeof(float)) != 0;
+  if (!moved) return TWK_SUCCESS;
+  std::vector<TwkInstanceMotion> table(count);
+  for (size_t i = 0; i < count; ++i)
+  {
+    const float* previous = &dev->temporalTransforms[12 * i];
+    const float* current = dev->instances[i].transform;
+    memset(&table[i], 0, sizeof(TwkInstanceMotion));
+    if (memcmp(previous, current, 12 * sizeof(float)) == 0) { table[i].previousFromCurrent[0] = table[i].previousFromCurrent[5] = table[i].previousFromCurrent[10] = 1.0f; continue; }
+    if (!instanceMotion(previous, current, table[i]))
+      return twkSetError(TWK_ERROR_INVALID_STATE, std::string(name) + ": instance " + std::to_string(i) + " has moved and its transform, now or in the history's frame, is singular or not finite");
+  }
+  const int rc = growIdle(dev, dev->d_temporalMotion, count); if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(dev->d_temporalMotion, table.data(), count * sizeof(TwkInstanceMotion), hipMemcpyHostToDevice, dev->stream));
+  HIP_TRY(hipStreamSynchronize(dev->stream)); // (the table is pageable host memory that goes out of use here; a move is rare and has just rebuilt the scene)
+  dev->temporalMotion.swap(table);
+  return TWK_SUCCESS;
+}
+
 // The merge of the own-buffer form and of the assembled form, after their refusals: the frame (colour in the output format,
 // moments, geometry; layers: the cascade layers to merge while twk_temporal_enable_cascade is on, nullptr = the handle's own) of
-// width x height pixels against the history the handle kept, which it then replaces. k: maxHistory and tol2 are set. rectify:
+// width x height pixels against the history the handle kept, which it then replaces — looked up where each instance was when
+// twk_update_instance_transform has moved one since (ownMotion). k: maxHistory and tol2 are set. rectify:
 // nullptr = the plain merge; else the rectified one (temporal_rectify_device.h), which also writes the handle's trust plane and,
 // while twk_temporal_enable_cascade is on, discounts the layers' history by it.
 static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const void* colour, const float4* moments, const float4* geometry,
@@ -102,6 +133,9 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
   const int keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
   k.width = width; k.height = height;
   if (dev->temporalHasHistory && (rc = temporalHistoryCamera(name, dev->temporalCamera, k))) return rc;
+  if ((rc = ownMotion(dev, name))) return rc;
+  const TwkInstanceMotion* motion = dev->temporalMotion.empty() ? nullptr : dev->d_temporalMotion.get();
+  const unsigned int numMotion = (unsigned int) dev->temporalMotion.size();
   // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
   if (rectify)
   {
@@ -109,20 +143,23 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
     if ((rc = ensureRectifyScratch(dev, n))) return rc;
     if ((rc = dev->d_temporalTrust.ensure(n))) return rc;
     launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->temporalColour.pixels,
-                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream);
+                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream, motion, numMotion);
     HIP_TRY(hipGetLastError());
-    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust))) return rc;
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust, motion, numMotion))) return rc;
     dev->temporalTrustValid = true;
   }
   else
   {
-    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry))) return rc;
-    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->temporalColour.pixels, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream);
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, nullptr, motion, numMotion))) return rc;
+    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->temporalColour.pixels, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream,
+                   motion, numMotion);
     HIP_TRY(hipGetLastError());
     dev->temporalTrustValid = false; // the trust plane, if any, is an earlier frame's
   }
   HIP_TRY(hipMemcpyAsync(dev->d_temporal[keep][2], geometry, n * sizeof(float4), hipMemcpyDeviceToDevice, dev->stream));
   dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalColour.valid = true;
+  dev->temporalTransforms.resize(12 * dev->instances.size()); // the history now is this frame: its instances are where they are
+  for (size_t i = 0; i < dev->instances.size(); ++i) memcpy(&dev->temporalTransforms[12 * i], dev->instances[i].transform, 12 * sizeof(float));
   return TWK_SUCCESS;
 }
 
@@ -166,9 +203,10 @@ static int temporalAssembledFrame(TwkDevice dev, const char* name, const Tempora
 }
 
 // twk_temporal_accumulate (rectify nullptr, no trustOut) and twk_temporal_accumulate_rectified after the checks of their parameters,
-// on an active handle: without a current frame the own-buffer form, else the explicit form's refusals and its launch
+// on an active handle: without a current frame the own-buffer form, else the explicit form's refusals and its launch. motion,
+// numMotion: the table of twk_temporal_accumulate_moving (a device pointer; nullptr or 0: none, the launches of the other two).
 static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
-                         int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut)
+                         int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0)
 {
   const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
   if (!current)
@@ -192,6 +230,10 @@ static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, c
     for (int i = 0; i < 6; ++i) if (overlaps(outs[o], outBytes[o], ins[i], inBytes[i])) return refuse("an output overlaps an input (the kernel gathers the history at other pixels)");
     for (int j = o + 1; j < 4; ++j) if (overlaps(outs[o], outBytes[o], outs[j], outBytes[j])) return refuse("two outputs overlap");
   }
+  if (!motion || !history) numMotion = 0; // (without a history nothing is reprojected)
+  if (numMotion > 0 && ((uintptr_t) motion & 15u) != 0) return refuse("the motion table is not 16-byte aligned");
+  for (int o = 0; o < 4 && numMotion > 0; ++o)
+    if (overlaps(outs[o], outBytes[o], motion, (size_t) numMotion * sizeof(TwkInstanceMotion))) return refuse("an output overlaps the motion table");
   k.width = width; k.height = height;
   int rc;
   if (history && (rc = temporalHistoryCamera(name, history->camera, k))) return rc;
@@ -199,10 +241,11 @@ static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, c
   {
     if ((rc = ensureRectifyScratch(dev, n))) return rc;
     launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], colourOut, static_cast<float4*>(historyOut),
-                          static_cast<float4*>(momentsOut), static_cast<float*>(trustOut), k, *rectify, dev->stream);
+                          static_cast<float4*>(momentsOut), static_cast<float*>(trustOut), k, *rectify, dev->stream, motion, (unsigned int) numMotion);
   }
   else
-    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream);
+    launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream,
+                   motion, (unsigned int) numMotion);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
@@ -255,6 +298,46 @@ try
   return temporalFrame(dev, name, k, &r, current, history, width, height, colourOut, historyOut, momentsOut, trustOut);
 }
 TWK_CATCH("twk_temporal_accumulate_rectified")
+
+int twk_temporal_accumulate_moving(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalRectify* rp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                                   const TwkInstanceMotion* motion, int numMotion, int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut)
+try
+{
+  const char* name = "twk_temporal_accumulate_moving";
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  int rc = activate(dev, name); if (rc) return rc;
+  TemporalConstants k;
+  RectifyConstants r;
+  if ((rc = rp ? rectifyParameters(name, tp, rp, k, r) : temporalParameters(name, tp, k))) return rc;
+  if (!current) return refuse("NULL current frame (the explicit form only: twk_temporal_accumulate's own-buffer form builds its table itself)");
+  if (!rp && trustOut) return refuse("a trustOut without TwkTemporalRectify (rp NULL is the plain merge)");
+  if (numMotion < 0) return refuse("numMotion must be >= 0");
+  return temporalFrame(dev, name, k, rp ? &r : nullptr, current, history, width, height, colourOut, historyOut, momentsOut, trustOut, motion, numMotion);
+}
+TWK_CATCH("twk_temporal_accumulate_moving")
+
+int twk_read_temporal_motion(TwkDevice dev, TwkInstanceMotion* host, size_t capacity, int* count)
+try
+{
+  const char* name = "twk_read_temporal_motion";
+  if (!dev || !count) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + (dev ? ": NULL count" : ": NULL device handle"));
+  const size_t used = dev->temporalMotion.size();
+  *count = (int) used; // (written before the capacity is held against it: a call with capacity 0 asks for the count)
+  if (capacity < used || (used > 0 && !host)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": the table has " + std::to_string(used) + " records, more than the capacity given");
+  if (used > 0) memcpy(host, dev->temporalMotion.data(), used * sizeof(TwkInstanceMotion));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_read_temporal_motion")
+
+int twk_instance_motion(const float previous[12], const float current[12], TwkInstanceMotion* out)
+try
+{
+  if (!previous || !current || !out) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_instance_motion: NULL argument");
+  if (!instanceMotion(previous, current, *out))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_instance_motion: an input is not finite, or the 3 x 3 determinant of current is zero or not finite");
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_instance_motion")
 
 int twk_temporal_accumulate_assembled(TwkDevice primary, const TwkTemporal* tp)
 try
@@ -360,37 +443,34 @@ try
   if (width < 1 || height < 1 || (size_t) width * (size_t) height > ((size_t) 1 << 28)) return refuse("width and height must be >= 1, width*height at most 2^28");
   k.width = width; k.height = height;
   if (history && (rc = temporalHistoryCamera(name, *historyCamera, k))) return rc;
-  const size_t n = (size_t) width * height;
-  // (a host array of floats need not have a float4's alignment)
-  std::vector<float4> cur(n), mc(n), g(n), hc(history ? n : 0), hm(history ? n : 0), hg(history ? n : 0), A(n), B(n);
-  memcpy(cur.data(), colour, n * sizeof(float4)); memcpy(mc.data(), moments, n * sizeof(float4)); memcpy(g.data(), geometry, n * sizeof(float4));
-  if (history) { memcpy(hc.data(), historyColour, n * sizeof(float4)); memcpy(hm.data(), historyMoments, n * sizeof(float4)); memcpy(hg.data(), historyGeometry, n * sizeof(float4)); }
-  // launch 1
-  for (size_t p = 0; p < n; ++p) rectifyReproject(k, cur[p], mc[p], g[p], hc.data(), hm.data(), hg.data(), A[p], B[p]);
-  // launch 2: the staged words of the whole picture with a halo of `radius` zeros around it, as one tile
-  const int R = r.radius, pitch = width + 2 * R;
-  std::vector<float> d((size_t) pitch * (height + 2 * R), 0.0f);
-  std::vector<unsigned int> key(d.size(), 0u);
-  for (int y = 0; y < height; ++y)
-    for (int x = 0; x < width; ++x)
-    {
-      const size_t p = (size_t) y * width + x, s = (size_t) (y + R) * pitch + (x + R);
-      rectifyStage(mc[p], B[p], d[s], key[s]);
-    }
-  for (int y = 0; y < height; ++y)
-    for (int x = 0; x < width; ++x)
-    {
-      const size_t p = (size_t) y * width + x;
-      const float t = rectifyTrust<0>(r, d.data(), key.data(), pitch, (y + R) * pitch + (x + R), B[p].z, mc[p].z);
-      float4 c = cur[p], m = mc[p];
-      float trust;
-      if (!rectifyMerge(t, cur[p], mc[p], A[p], B[p], c, m, trust)) { c = cur[p]; m = mc[p]; }
-      if (colourOut) memcpy(colourOut + 4 * p, &c, sizeof(float4));
-      if (momentsOut) memcpy(momentsOut + 4 * p, &m, sizeof(float4));
-      if (trustOut) trustOut[p] = trust;
-    }
+  const TemporalHostFrame frame((size_t) width * height, colour, moments, geometry, historyColour, historyMoments, historyGeometry);
+  temporalRectifyHost<false>(k, r, frame, nullptr, 0u, colourOut, momentsOut, trustOut);
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_temporal_rectify_host")
+
+int twk_temporal_moving_host(const TwkTemporal* tp, const TwkTemporalRectify* rp, const float* colour, const float* moments, const float* geometry,
+                             const float* historyColour, const float* historyMoments, const float* historyGeometry, const TwkCameraDefinition* historyCamera,
+                             const TwkInstanceMotion* motion, int numMotion, int width, int height, float* colourOut, float* momentsOut, float* trustOut)
+try
+{
+  const char* name = "twk_temporal_moving_host";
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  if (!colour || !moments || !geometry) return refuse("NULL buffer in the current frame");
+  const bool history = historyColour || historyMoments || historyGeometry;
+  if (history && (!historyColour || !historyMoments || !historyGeometry || !historyCamera)) return refuse("a history without its colour, moments, geometry or camera");
+  if (!rp && trustOut) return refuse("a trustOut without TwkTemporalRectify (rp NULL is the plain merge)");
+  if (numMotion < 0) return refuse("numMotion must be >= 0");
+  TemporalConstants k;
+  RectifyConstants r;
+  int rc = rp ? rectifyParameters(name, tp, rp, k, r) : temporalParameters(name, tp, k); if (rc) return rc;
+  if (width < 1 || height < 1 || (size_t) width * (size_t) height > ((size_t) 1 << 28)) return refuse("width and height must be >= 1, width*height at most 2^28");
+  k.width = width; k.height = height;
+  if (history && (rc = temporalHistoryCamera(name, *historyCamera, k))) return rc;
+  const TemporalHostFrame frame((size_t) width * height, colour, moments, geometry, historyColour, historyMoments, historyGeometry);
+  temporalMergeHost(k, rp ? &r : nullptr, frame, motion, motion ? (unsigned int) numMotion : 0u, colourOut, momentsOut, trustOut);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_moving_host")
 
 } // extern "C"

@@ -3,6 +3,7 @@
 // merge itself is issued by twk_temporal_accumulate (device_temporal.hip) through temporalCascadeOwn(), before it swaps its history.
 // The checks of TwkTemporal and the history's camera are device_temporal.hip's temporalParameters and temporalHistoryCamera.
 #include "device_handle.h"
+#include "temporal_motion_host.h"
 
 #include <cstring>
 #include <vector>
@@ -26,7 +27,9 @@ const char* twk::temporalCascadeRefusal(TwkDevice dev)
 // has no history) are those of the twk_temporal_accumulate or twk_temporal_accumulate_assembled that calls it, before it swaps its
 // history. layers: [layers][k.width x k.height] float4, the assembled ones of a tiled primary; nullptr: the handle's own.
 // trust: nullptr = the plain merge; else the trust plane of the rectified merge of the same frame, already written on the stream.
-int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust)
+// motion, numMotion: the table that merge uses (a device pointer; nullptr or 0: none).
+int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust,
+                            const TwkInstanceMotion* motion, unsigned int numMotion)
 {
   int rc = ensureStreams(dev); if (rc) return rc;
   const size_t n = (size_t) k.width * k.height;
@@ -50,10 +53,10 @@ int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const flo
   kc.hasHistory = history ? 1 : 0;
   if (trust)
     launchTemporalCascadeTrusted(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr, trust,
-                                 dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
+                                 dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream, motion, numMotion);
   else
     launchTemporalCascade(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
-                          dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream);
+                          dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream, motion, numMotion);
   HIP_TRY(hipGetLastError());
   dev->temporalCascadeKept = keep; dev->temporalCascadeHasHistory = true; dev->temporalCascadeValid = true;
   return TWK_SUCCESS;
@@ -74,10 +77,11 @@ static int temporalCascadeParameters(const char* name, const TwkTemporal* tp, co
   return history ? temporalHistoryCamera(name, *historyCamera, k) : TWK_SUCCESS;
 }
 
-// The explicit form, plain (trusted false) and trusted (trust: width x height floats)
+// The explicit form, plain (trusted false) and trusted (trust: width x height floats). moving: twk_temporal_accumulate_cascade_moving,
+// whose table (motion, numMotion; nullptr or 0: none) is checked here; the others pass none.
 static int temporalCascadeExplicit(const char* name, bool trusted, TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
                                    const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust, int width, int height,
-                                   void* layersOut)
+                                   void* layersOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0)
 {
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, std::string(name) + ": " + text); };
   if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
@@ -92,46 +96,35 @@ static int temporalCascadeExplicit(const char* name, bool trusted, TwkDevice dev
       (historyLayers && (overlaps(layersOut, layerBytes, historyLayers, layerBytes) || overlaps(layersOut, layerBytes, historyGeometry, plane))))
     return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps an input (the kernel gathers the history at other pixels)");
   if (trusted && overlaps(layersOut, layerBytes, trust, n * sizeof(float))) return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps the trust");
+  if (numMotion < 0) return refuse(TWK_ERROR_INVALID_VALUE, "numMotion must be >= 0");
+  if (!motion || !historyLayers) numMotion = 0; // (without a history nothing is reprojected)
+  if (numMotion > 0 && ((uintptr_t) motion & 15u) != 0) return refuse(TWK_ERROR_INVALID_VALUE, "the motion table is not 16-byte aligned");
+  if (numMotion > 0 && overlaps(layersOut, layerBytes, motion, (size_t) numMotion * sizeof(TwkInstanceMotion))) return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps the motion table");
   if ((rc = activate(dev, name))) return rc;
   if (trusted)
     launchTemporalCascadeTrusted(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
-                                 historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<const float*>(trust), static_cast<float4*>(layersOut), k, c, dev->stream);
+                                 historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<const float*>(trust), static_cast<float4*>(layersOut), k, c, dev->stream,
+                                 motion, (unsigned int) numMotion);
   else
     launchTemporalCascade(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
-                          historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream);
+                          historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream, motion, (unsigned int) numMotion);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
 
-// The host-only form, plain and trusted
+// The host-only form, plain and trusted, with a table (twk_temporal_cascade_moving_host; a host array) or without
 static int temporalCascadeHost(const char* name, bool trusted, const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry,
                                const float* historyLayers, const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, int width, int height,
-                               float* layersOut)
+                               float* layersOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0)
 {
   if (!currentLayers || !currentGeometry || !layersOut) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL current layers, current geometry or output");
   if (historyLayers && (!historyGeometry || !historyCamera)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": history layers without the history's geometry or camera");
   if (trusted && !trust) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL trust");
+  if (numMotion < 0) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": numMotion must be >= 0");
   TemporalConstants k;
   CascadeConstants c;
   int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
-  const size_t n = (size_t) width * height, all = n * (size_t) c.layers;
-  // (a host array of floats need not have a float4's alignment)
-  std::vector<float4> layers(all), geometry(n), history(historyLayers ? all : 0), hGeometry(historyLayers ? n : 0), out(all);
-  memcpy(layers.data(), currentLayers, all * sizeof(float4));
-  memcpy(geometry.data(), currentGeometry, n * sizeof(float4));
-  if (historyLayers)
-  {
-    memcpy(history.data(), historyLayers, all * sizeof(float4));
-    memcpy(hGeometry.data(), historyGeometry, n * sizeof(float4));
-  }
-  const float4* H = historyLayers ? history.data() : nullptr;
-  const float4* hG = historyLayers ? hGeometry.data() : nullptr;
-  for (size_t p = 0; p < n; ++p)
-  {
-    if (trusted) temporalCascadePixel<true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), trust);
-    else         temporalCascadePixel(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data());
-  }
-  memcpy(layersOut, out.data(), all * sizeof(float4));
+  temporalCascadeHostLayers(k, c, currentLayers, currentGeometry, historyLayers, historyGeometry, trusted ? trust : nullptr, motion, motion ? (unsigned int) numMotion : 0u, layersOut);
   return TWK_SUCCESS;
 }
 
@@ -153,6 +146,16 @@ try
   return temporalCascadeExplicit("twk_temporal_accumulate_cascade_trusted", true, dev, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust, width, height, layersOut);
 }
 TWK_CATCH("twk_temporal_accumulate_cascade_trusted")
+
+int twk_temporal_accumulate_cascade_moving(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                           const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust,
+                                           const TwkInstanceMotion* motion, int numMotion, int width, int height, void* layersOut)
+try
+{
+  return temporalCascadeExplicit("twk_temporal_accumulate_cascade_moving", trust != nullptr, dev, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust,
+                                 width, height, layersOut, motion, numMotion);
+}
+TWK_CATCH("twk_temporal_accumulate_cascade_moving")
 
 int twk_temporal_enable_cascade(TwkDevice dev, int enable)
 try
@@ -210,5 +213,15 @@ try
   return temporalCascadeHost("twk_temporal_cascade_trusted_host", true, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust, width, height, layersOut);
 }
 TWK_CATCH("twk_temporal_cascade_trusted_host")
+
+int twk_temporal_cascade_moving_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                                     const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, const TwkInstanceMotion* motion, int numMotion,
+                                     int width, int height, float* layersOut)
+try
+{
+  return temporalCascadeHost("twk_temporal_cascade_moving_host", trust != nullptr, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust, width, height,
+                             layersOut, motion, numMotion);
+}
+TWK_CATCH("twk_temporal_cascade_moving_host")
 
 } // extern "C"

@@ -262,6 +262,14 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 2) temporalRectifyMinTaps = i[0];
       else if (ok) warnings.push_back("temporalRectifyMinTaps must be >= 2, keeping the previous value");
     }
+    // an object that moves in that loop (twk_update_instance_transform, read by twk_app_get_temporal_motion): a line the call would
+    // refuse is dropped. A render loop refuses the key without "temporalAccumulation 1" and for an instance that carries a light.
+    else if (key == "temporalInstanceStep")
+    {
+      ok = readInt(parser, i[0]) && readFloat(parser, f[0]) && readFloat(parser, f[1]) && readFloat(parser, f[2]);
+      if (ok && i[0] >= 0 && std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) { temporalInstance = i[0]; for (int k = 0; k < 3; ++k) temporalInstanceStep[k] = f[k]; }
+      else if (ok) warnings.push_back("temporalInstanceStep needs an instance id >= 0 and a finite step, dropping the line");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -366,6 +374,7 @@ std::string Application::systemDescription() const
   if (temporalRectifyGamma != TWK_TEMPORAL_RECTIFY_GAMMA) d << "temporalRectifyGamma " << temporalRectifyGamma << std::endl;
   if (temporalRectifyRadius != TWK_TEMPORAL_RECTIFY_RADIUS) d << "temporalRectifyRadius " << temporalRectifyRadius << std::endl;
   if (temporalRectifyMinTaps != TWK_TEMPORAL_RECTIFY_MIN_TAPS) d << "temporalRectifyMinTaps " << temporalRectifyMinTaps << std::endl;
+  if (temporalInstance >= 0) d << "temporalInstanceStep " << temporalInstance << " " << temporalInstanceStep[0] << " " << temporalInstanceStep[1] << " " << temporalInstanceStep[2] << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

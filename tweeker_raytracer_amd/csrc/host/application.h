@@ -137,6 +137,10 @@ public:
   int   temporalRectifyRadius = TWK_TEMPORAL_RECTIFY_RADIUS;
   int   temporalRectifyMinTaps = TWK_TEMPORAL_RECTIFY_MIN_TAPS;
   int   temporalRectifyKeys = 0;
+  // "temporalInstanceStep <idInstance> <dx> <dy> <dz>" (read by twk_app_get_temporal_motion): before every frame of that loop after
+  // the first, the instance is translated by one more step (twk_update_instance_transform on every device). temporalInstance -1: no key.
+  int   temporalInstance = -1;
+  float temporalInstanceStep[3] = {0.0f, 0.0f, 0.0f};
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel

@@ -236,6 +236,18 @@ try
 }
 TWK_CATCH("twk_app_get_temporal_rectify")
 
+int twk_app_get_temporal_motion(TwkApp app, int* idInstance, float step[3])
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_temporal_motion: NULL app");
+  if (!idInstance || !step) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_temporal_motion: NULL argument");
+  const Application& a = app->app;
+  *idInstance = a.temporalInstance;
+  for (int k = 0; k < 3; ++k) step[k] = a.temporalInstanceStep[k];
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_temporal_motion")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {

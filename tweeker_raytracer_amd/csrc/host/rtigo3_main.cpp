@@ -29,7 +29,10 @@
 // or 2, and on several devices without "tileAssembly 1". With "temporalRectify 1" beside it the merge is the rectified one
 // (twk_temporal_accumulate_rectified; twk_temporal_accumulate_assembled_rectified on the first device) with "temporalRectifyGamma",
 // "temporalRectifyRadius" and "temporalRectifyMinTaps"; any of these four keys without "temporalAccumulation 1" is refused before any
-// device is created.
+// device is created. With "temporalInstanceStep <idInstance> <dx> <dy> <dz>" beside it that instance is translated by one more step
+// before every frame after the first (twk_update_instance_transform on every device, which keeps the history; the merges carry it
+// along); refused before any device is created without "temporalAccumulation 1", for an id beyond the scene's instances and for an
+// instance that carries a light.
 // With "denoiserGeometry 1" beside "denoiser 3" the filter, in whichever mode is on, is twk_denoise_geometry: the geometry AOV is
 // traced once before the screenshot is filtered (twk_render_geometry; on several devices with "tileAssembly 1"
 // twk_render_geometry_tile and ONE twk_assemble_devices_with_geometry), the temporal loop uses its last frame's own geometry, and
@@ -255,6 +258,28 @@ int main(int argc, char* argv[])
     std::cerr << "ERROR: temporalRectify, temporalRectifyGamma, temporalRectifyRadius and temporalRectifyMinTaps set the merge of the moving-camera loop: they need temporalAccumulation 1\n";
     return 1;
   }
+  int movingInstance = -1; // "temporalInstanceStep": an instance translated by one more step before every frame after the first
+  float movingStep[3] = {0.0f, 0.0f, 0.0f};
+  TWK_OK(twk_app_get_temporal_motion(app, &movingInstance, movingStep));
+  if (movingInstance >= 0 && !temporalEnabled)
+  {
+    std::cerr << "ERROR: temporalInstanceStep moves an object in the moving-camera loop: it needs temporalAccumulation 1\n";
+    return 1;
+  }
+  if (movingInstance >= 0)
+  {
+    int light = -1;
+    if (movingInstance >= info.numInstances || twk_app_get_instance(app, movingInstance, nullptr, nullptr, nullptr, &light) != TWK_SUCCESS)
+    {
+      std::cerr << "ERROR: temporalInstanceStep names instance " << movingInstance << "; the scene has " << info.numInstances << "\n";
+      return 1;
+    }
+    if (light >= 0)
+    {
+      std::cerr << "ERROR: temporalInstanceStep names an instance that carries a light: moving emitters is not supported\n";
+      return 1;
+    }
+  }
   if (temporalEnabled && (targetNoiseEnabled || adaptiveEnabled))
   {
     std::cerr << "ERROR: temporalAccumulation renders a fixed orbit of frames; targetNoise and adaptiveSampling end or thin a single frame's loop and do not go with it\n";
@@ -370,6 +395,14 @@ int main(int argc, char* argv[])
       TwkCameraDefinition camera;
       const float phi = (float) ((double) info.phi + (double) frame * (double) temporalOrbitStep);
       TWK_OK(twk_camera_frustum(info.center, phi, info.theta, info.fov, info.distance, aspect, &camera));
+      if (movingInstance >= 0 && frame > 0)
+        for (int i = 0; i < count; ++i)
+        {
+          float transform[12];
+          TWK_OK(twk_get_instance_transform(devices[(size_t) i], movingInstance, transform));
+          for (int k = 0; k < 3; ++k) transform[4 * k + 3] += movingStep[k];
+          TWK_OK(twk_update_instance_transform(devices[(size_t) i], movingInstance, transform));
+        }
       for (int i = 0; i < count; ++i)
       {
         TWK_OK(twk_update_camera(devices[(size_t) i], 0, &camera));

@@ -35,7 +35,8 @@
 // every sum with it, which leaves each layer's mean contribution where it was and bounds the history's weight at maxHistory samples.
 // The bilinear interpolation mixes the sums AND the counts of neighbouring pixels: a layer count c_j of the resolve then speaks of a
 // neighbourhood one pixel wider than its 3x3 window. Alpha and the luminance moments are not here: they are the existing merge's
-// business (temporal_device.h), which this leaves untouched. As there: no motion vectors, no environment reprojection (a miss never
+// business (temporal_device.h), which this leaves untouched. As there: objects move by one matrix per instance in the Moving builds
+// only (temporal_motion_device.h; a candidate here is a hit with finite g.xyz and nc >= 1), no environment reprojection (a miss never
 // has history), the pinhole lens only, one device, no tiles; the paper's variance term is not reprojected, and neither the noise
 // estimate nor the adaptive passes see the merged layers.
 //
@@ -56,9 +57,12 @@ namespace twk {
 // stride is `stride` >= k.width * k.height. The loops over taps and layers have constant trip counts and are unrolled, the layer loop
 // predicated by j < K, so that the small arrays live in registers (cascade_device.h).
 // Trusted: the build that discounts the capped history by trust[p] (above); otherwise trust is not read.
-template<bool Trusted = false>
+// Moving: the build that carries g to where its instance was in the history's frame before the projection and the taps' test
+// (temporal_motion_device.h temporalMove, with the table motion[numMotion]; g' not finite: no history); otherwise the table is not read.
+template<bool Trusted = false, bool Moving = false>
 TWK_HD void temporalCascadePixel(const TemporalConstants& k, const CascadeConstants& c, const float4* Lc, const float4* geometry, const float4* H,
-                                 const float4* hGeometry, const size_t stride, const size_t p, float4* out, const float* trust = nullptr)
+                                 const float4* hGeometry, const size_t stride, const size_t p, float4* out, const float* trust = nullptr,
+                                 const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u)
 {
   const int K = c.layers;
   const size_t top = (size_t) (K - 1) * stride;
@@ -73,8 +77,9 @@ TWK_CASCADE_UNROLL
   if (k.hasHistory != 0)
   {
     const float4 g = geometry[p];
+    float4 gp = g;
     float fx = 0.0f, fy = 0.0f, vv = 0.0f;
-    if (asUint(g.w) != 0u && finite3(g) && cascadeFinite(nc) && !(nc < 1.0f) && temporalProject(k, g, fx, fy, vv))
+    if (asUint(g.w) != 0u && finite3(g) && cascadeFinite(nc) && !(nc < 1.0f) && (!Moving || temporalMove(motion, numMotion, g, gp)) && temporalProject(k, gp, fx, fy, vv))
     {
       const TemporalFootprint f = temporalFootprint(fx, fy);
       q00 = (long long) f.y0 * k.width + f.x0;
@@ -90,7 +95,7 @@ TWK_CASCADE_UNROLL
           if (qx < 0 || qx >= k.width) continue;
           const int t = 2 * dy + dx;
           const size_t qi = (size_t) qy * k.width + qx;
-          if (!temporalTapGeometry(k, g, hGeometry[qi], vv)) continue;
+          if (!temporalTapGeometry(k, gp, hGeometry[qi], vv)) continue;
           const float4 h0 = H[qi];
           if (!cascadeFinite(h0.w) || !(h0.w >= 1.0f)) continue;
           const float4 h1 = H[top + qi];

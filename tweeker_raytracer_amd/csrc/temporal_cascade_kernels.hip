@@ -32,19 +32,55 @@ __global__ void __launch_bounds__(256) temporalCascadeTrustedKernel(const float4
   temporalCascadePixel<true>(k, c, layers, geometry, historyLayers, historyGeometry, numPixels, p, layersOut, trust);
 }
 
-// trust: k.width x k.height floats, not nullptr
-void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, float4* layersOut,
-                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream)
+// The Moving builds of the two kernels above (temporal_motion_device.h): the same thread per pixel, plus one 64-byte record of the
+// table per candidate pixel, read before the projection; Staged: from the block's LDS copy (motionTable). Kernels of their own, so
+// that the two above are the code they were.
+template<bool Trusted, bool Staged>
+__global__ void __launch_bounds__(256) temporalCascadeMovingKernel(const float4* __restrict__ layers, const float4* __restrict__ geometry, const float4* __restrict__ historyLayers,
+                                                                   const float4* __restrict__ historyGeometry, const float* __restrict__ trust,
+                                                                   const TwkInstanceMotion* __restrict__ motion, unsigned int numMotion, float4* __restrict__ layersOut,
+                                                                   TemporalConstants k, CascadeConstants c)
 {
+  __shared__ TwkInstanceMotion staged[Staged ? TWK_MOTION_LDS_RECORDS : 1];
+  const TwkInstanceMotion* table = motionTable<Staged>(motion, numMotion, staged, 256u);
+  const size_t numPixels = (size_t) k.width * k.height;
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= numPixels) return;
+  temporalCascadePixel<Trusted, true>(k, c, layers, geometry, historyLayers, historyGeometry, numPixels, p, layersOut, trust, table, numMotion);
+}
+
+template<bool Trusted>
+static void launchCascadeMoving(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust,
+                                const TwkInstanceMotion* motion, unsigned int numMotion, float4* layersOut, const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream)
+{
+  const size_t numPixels = (size_t) k.width * k.height;
+  const dim3 grid((unsigned int) ((numPixels + 255) / 256));
+#if TWK_MOTION_STAGED_RECORDS > 0
+  if (numMotion <= TWK_MOTION_STAGED_RECORDS)
+  {
+    hipLaunchKernelGGL((temporalCascadeMovingKernel<Trusted, true>), grid, dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, trust, motion, numMotion, layersOut, k, c);
+    return;
+  }
+#endif
+  hipLaunchKernelGGL((temporalCascadeMovingKernel<Trusted, false>), grid, dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, trust, motion, numMotion, layersOut, k, c);
+}
+
+// trust: k.width x k.height floats, not nullptr. motion, numMotion: the table of the Moving build; nullptr or 0: the kernel above
+void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, float4* layersOut,
+                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
+{
+  if (motion && numMotion > 0u) { launchCascadeMoving<true>(layers, geometry, historyLayers, historyGeometry, trust, motion, numMotion, layersOut, k, c, stream); return; }
   const size_t numPixels = (size_t) k.width * k.height;
   hipLaunchKernelGGL(temporalCascadeTrustedKernel, dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, trust,
                      layersOut, k, c);
 }
 
-// layers, layersOut and historyLayers [c.layers][k.width x k.height] float4; historyLayers / historyGeometry nullptr with k.hasHistory 0
+// layers, layersOut and historyLayers [c.layers][k.width x k.height] float4; historyLayers / historyGeometry nullptr with k.hasHistory 0.
+// motion, numMotion: the table of the Moving build; nullptr or 0: the kernel above
 void launchTemporalCascade(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, float4* layersOut,
-                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream)
+                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
 {
+  if (motion && numMotion > 0u) { launchCascadeMoving<false>(layers, geometry, historyLayers, historyGeometry, nullptr, motion, numMotion, layersOut, k, c, stream); return; }
   const size_t numPixels = (size_t) k.width * k.height;
   hipLaunchKernelGGL(temporalCascadeKernel, dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, layersOut, k, c);
 }

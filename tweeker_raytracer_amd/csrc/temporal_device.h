@@ -69,14 +69,17 @@
 // average with alpha = spp / (maxHistory + spp) does. The bilinear interpolation of M2 ignores the spread of the four taps'
 // means (the exact pairwise merge of the taps would add it): across a luminance edge inside one surface the interpolated variance
 // is too small by that spread. hn is a weighted mean of sample counts, not a count. A pixel that MISSED never has history: the
-// environment would have to be reprojected by direction, which is left out. Objects do not move (the scene is static between
-// twk_build calls) and the lens is the pinhole: no motion vectors, no fisheye or sphere. The merge itself works on whole pictures.
+// environment would have to be reprojected by direction, which is left out. The lens is the pinhole: no fisheye or sphere. Objects
+// move by one matrix per instance, in the Moving builds only (temporal_motion_device.h: twk_update_instance_transform keeps the
+// history and the merges look it up where the instance was); the builds without it take the scene as static between the history's
+// frame and this one. No per-vertex motion, no deformation, no motion blur. The merge itself works on whole pictures.
 // A frame tiled over several devices is merged on ONE of them: every device traces the geometry of its own share (above), the
 // shares and the planes are assembled there in one launch (twk_assemble_devices_with_geometry) and
 // twk_temporal_accumulate_assembled runs this same merge on the assembled W x H buffers, with that handle's history. Nothing is
 // scattered back to the tiles, and the merge does not read the packed tiles itself.
 #pragma once
 #include "denoise_device.h"
+#include "temporal_motion_device.h"
 
 namespace twk {
 
@@ -174,13 +177,19 @@ TWK_HD void temporalTap(const float4& hc, const float4& hm, float w, TemporalSum
 
 // The gather at pixel p, from the candidate test to the last tap: s.ws > 0 says there is history. The history's geometry is read
 // first; its colour and moments only at the taps that belong to the surface. (cur, mc and g by value: by reference the kernel's
-// load of g is split into xyz and w and temporalKernel grows by 30 instructions.)
+// load of g is split into xyz and w and temporalKernel grows by 30 instructions.) Moving: the build that first carries g to where
+// its instance was in the history's frame (temporal_motion_device.h temporalMove, with the table motion[numMotion]); otherwise the
+// table is not read.
+template<bool Moving = false>
 TWK_HD void temporalGather(const TemporalConstants& k, const float4 cur, const float4 mc, const float4 g, const float4* historyColour, const float4* historyMoments,
-                           const float4* historyGeometry, TemporalSums& s)
+                           const float4* historyGeometry, TemporalSums& s, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u)
 {
   s.x = 0.0f; s.y = 0.0f; s.z = 0.0f; s.mean = 0.0f; s.M2 = 0.0f; s.n = 0.0f; s.ws = 0.0f;
   float fx = 0.0f, fy = 0.0f, vv = 0.0f;
-  if (!(temporalCandidate(k, cur, mc, g) && temporalProject(k, g, fx, fy, vv))) return;
+  if (!temporalCandidate(k, cur, mc, g)) return;
+  float4 gp = g;
+  if (Moving && !temporalMove(motion, numMotion, g, gp)) return;
+  if (!temporalProject(k, gp, fx, fy, vv)) return;
   const TemporalFootprint f = temporalFootprint(fx, fy);
 #pragma unroll
   for (int dy = 0; dy <= 1; ++dy)
@@ -193,7 +202,7 @@ TWK_HD void temporalGather(const TemporalConstants& k, const float4 cur, const f
       const int qx = f.x0 + dx;
       if (qx < 0 || qx >= k.width) continue;
       const size_t q = (size_t) qy * k.width + qx;
-      if (!temporalTapGeometry(k, g, historyGeometry[q], vv)) continue;
+      if (!temporalTapGeometry(k, gp, historyGeometry[q], vv)) continue;
       temporalTap(historyColour[q], historyMoments[q], temporalTapWeight(f, dx, dy), s);
     }
   }

@@ -68,6 +68,45 @@ __global__ void __launch_bounds__(256) temporalKernel(const Pixel* __restrict__ 
     temporalStorePassThrough(p, raw, cur, mc, colourOut, historyOut, momentsOut);
 }
 
+// temporalKernel's Moving build (temporal_motion_device.h): the same thread per pixel and the same streams, plus one 64-byte record
+// of the table per candidate pixel, read before the projection — a wave's pixels see one or two instances, so its loads fall into
+// one or two cache lines. Staged: the table from the block's LDS copy (motionTable). A kernel of its own, so that the one above is
+// the code it was.
+template<typename Pixel, bool Staged>
+__global__ void __launch_bounds__(256) temporalMovingKernel(const Pixel* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ geometry,
+                                                            const float4* __restrict__ historyColour, const float4* __restrict__ historyMoments, const float4* __restrict__ historyGeometry,
+                                                            const TwkInstanceMotion* __restrict__ motion, unsigned int numMotion,
+                                                            Pixel* __restrict__ colourOut, float4* __restrict__ historyOut, float4* __restrict__ momentsOut, TemporalConstants k)
+{
+  __shared__ TwkInstanceMotion staged[Staged ? TWK_MOTION_LDS_RECORDS : 1];
+  const TwkInstanceMotion* table = motionTable<Staged>(motion, numMotion, staged, 256u);
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t) k.width * k.height) return;
+  const Pixel raw = colour[p];
+  const float4 cur = widen(raw);
+  const float4 mc = moments[p];
+  const float4 g = geometry[p];
+  TemporalSums s;
+  temporalGather<true>(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s, table, numMotion);
+  if (s.ws > 0.0f)
+  {
+    float4 c, m;
+    temporalMerge(k, s, cur, mc, c, m);
+    temporalStoreMerged(p, c, m, colourOut, historyOut, momentsOut);
+  }
+  else
+    temporalStorePassThrough(p, raw, cur, mc, colourOut, historyOut, momentsOut);
+}
+
+template<typename Pixel, bool Staged>
+static void launchMoving(const void* colour, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments, const float4* historyGeometry,
+                         const TwkInstanceMotion* motion, unsigned int numMotion, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream)
+{
+  const size_t numPixels = (size_t) k.width * k.height;
+  hipLaunchKernelGGL((temporalMovingKernel<Pixel, Staged>), dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, static_cast<const Pixel*>(colour), moments, geometry,
+                     historyColour, historyMoments, historyGeometry, motion, numMotion, static_cast<Pixel*>(colourOut), historyOut, momentsOut, k);
+}
+
 void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream)
 {
   if (tiled) hipLaunchKernelGGL(geometryKernel<true>, dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, geometry);
@@ -75,8 +114,23 @@ void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gri
 }
 
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
-                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream)
+                    const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream,
+                    const TwkInstanceMotion* motion, unsigned int numMotion)
 {
+  if (motion && numMotion > 0u) // the Moving build; without a table the kernel below, as it always was
+  {
+#if TWK_MOTION_STAGED_RECORDS > 0
+    if (numMotion <= TWK_MOTION_STAGED_RECORDS)
+    {
+      if (half) launchMoving<Half4, true>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, motion, numMotion, colourOut, historyOut, momentsOut, k, stream);
+      else      launchMoving<float4, true>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, motion, numMotion, colourOut, historyOut, momentsOut, k, stream);
+      return;
+    }
+#endif
+    if (half) launchMoving<Half4, false>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, motion, numMotion, colourOut, historyOut, momentsOut, k, stream);
+    else      launchMoving<float4, false>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, motion, numMotion, colourOut, historyOut, momentsOut, k, stream);
+    return;
+  }
   const size_t numPixels = (size_t) k.width * k.height;
   const dim3 grid((unsigned int) ((numPixels + 255) / 256));
   if (half)

@@ -29,6 +29,25 @@ __global__ void __launch_bounds__(256) rectifyReprojectKernel(const Pixel* __res
   scratchB[p] = B;
 }
 
+// Launch 1's Moving build (temporal_motion_device.h): as above, plus one 64-byte record of the table per candidate pixel, read
+// before the projection; Staged: from the block's LDS copy (motionTable). Launch 2 is the same for both. A kernel of its own, so
+// that the one above is the code it was.
+template<typename Pixel, bool Staged>
+__global__ void __launch_bounds__(256) rectifyReprojectMovingKernel(const Pixel* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ geometry,
+                                                                    const float4* __restrict__ historyColour, const float4* __restrict__ historyMoments,
+                                                                    const float4* __restrict__ historyGeometry, const TwkInstanceMotion* __restrict__ motion, unsigned int numMotion,
+                                                                    float4* __restrict__ scratchA, float4* __restrict__ scratchB, TemporalConstants k)
+{
+  __shared__ TwkInstanceMotion staged[Staged ? TWK_MOTION_LDS_RECORDS : 1];
+  const TwkInstanceMotion* table = motionTable<Staged>(motion, numMotion, staged, 256u);
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t) k.width * k.height) return;
+  float4 A, B;
+  rectifyReproject<true>(k, widen(colour[p]), moments[p], geometry[p], historyColour, historyMoments, historyGeometry, A, B, table, numMotion);
+  scratchA[p] = A;
+  scratchB[p] = B;
+}
+
 // Launch 2. A block is a 32 x 8 pixel tile: thread t is pixel (t % 32, t / 32) of it, so a wave is two rows of 32 pixels and every
 // global access of the merge is a coalesced 16-byte (RGBA16F colour: 8-byte) one. The block first stages d and key of the tile and
 // a halo of `radius` pixels into LDS, (32 + 2 radius) x (8 + 2 radius) pairs of words — at radius 4, 40 x 16 x 8 = 5120 bytes; the
@@ -81,13 +100,22 @@ rectifyMergeKernel(const Pixel* __restrict__ colour, const float4* __restrict__ 
 template<typename Pixel>
 static void launchRectify(const void* colour, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments, const float4* historyGeometry,
                           float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut, const TemporalConstants& k,
-                          const RectifyConstants& r, hipStream_t stream)
+                          const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
 {
   const size_t numPixels = (size_t) k.width * k.height;
   const Pixel* in = static_cast<const Pixel*>(colour);
   Pixel* out = static_cast<Pixel*>(colourOut);
-  hipLaunchKernelGGL(rectifyReprojectKernel<Pixel>, dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, in, moments, geometry, historyColour, historyMoments,
-                     historyGeometry, scratchA, scratchB, k);
+  const dim3 pixels((unsigned int) ((numPixels + 255) / 256));
+  if (!(motion && numMotion > 0u)) // without a table launch 1 as it always was
+    hipLaunchKernelGGL(rectifyReprojectKernel<Pixel>, pixels, dim3(256), 0, stream, in, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, k);
+#if TWK_MOTION_STAGED_RECORDS > 0
+  else if (numMotion <= TWK_MOTION_STAGED_RECORDS)
+    hipLaunchKernelGGL((rectifyReprojectMovingKernel<Pixel, true>), pixels, dim3(256), 0, stream, in, moments, geometry, historyColour, historyMoments, historyGeometry, motion, numMotion,
+                       scratchA, scratchB, k);
+#endif
+  else
+    hipLaunchKernelGGL((rectifyReprojectMovingKernel<Pixel, false>), pixels, dim3(256), 0, stream, in, moments, geometry, historyColour, historyMoments, historyGeometry, motion, numMotion,
+                       scratchA, scratchB, k);
   const dim3 grid((unsigned int) ((k.width + TWK_RECTIFY_TILE_X - 1) / TWK_RECTIFY_TILE_X), (unsigned int) ((k.height + TWK_RECTIFY_TILE_Y - 1) / TWK_RECTIFY_TILE_Y));
   const dim3 block(TWK_RECTIFY_TILE_X * TWK_RECTIFY_TILE_Y);
 #define TWK_RECTIFY_LAUNCH(R) hipLaunchKernelGGL((rectifyMergeKernel<Pixel, R>), grid, block, 0, stream, in, moments, scratchA, scratchB, out, historyOut, momentsOut, trustOut, k, r)
@@ -109,12 +137,13 @@ static void launchRectify(const void* colour, const float4* moments, const float
 
 // Both launches on `stream`. scratchA, scratchB: k.width x k.height float4 each, the handle's; history* nullptr with k.hasHistory 0
 // (every pixel then passes through with trust 1). r.radius in 1 .. TWK_RECTIFY_MAX_RADIUS: the caller has refused anything else.
+// motion, numMotion: the table of launch 1's Moving build; nullptr or 0: none, the launches as they always were.
 void launchTemporalRectify(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                            const float4* historyGeometry, float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut,
-                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream)
+                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
 {
-  if (half) launchRectify<Half4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream);
-  else      launchRectify<float4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream);
+  if (half) launchRectify<Half4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream, motion, numMotion);
+  else      launchRectify<float4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream, motion, numMotion);
 }
 
 } // namespace twk

@@ -13,6 +13,17 @@ from . import _lib as L
 KERNEL_CLASSES = ("generate", "trace", "shade", "accumulate", "tail")
 
 
+def instance_motion(previous, current):
+    """twk_instance_motion (pure CPU): the L.InstanceMotion record of an instance whose object-to-world matrix was `previous` when the
+    history was taken and is `current` now (12 floats each, row-major 3 x 4). moved = 0 when the two are bit-equal. TwkError for an
+    input that is not finite and for a singular `current`."""
+    p = np.ascontiguousarray(previous, dtype=np.float32).reshape(12)
+    c = np.ascontiguousarray(current, dtype=np.float32).reshape(12)
+    out = L.InstanceMotion()
+    L.check(L.lib.twk_instance_motion(p.ctypes.data_as(C.POINTER(C.c_float)), c.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out)))
+    return out
+
+
 def device_count():
     n = C.c_int(0)
     L.check(L.lib.twk_device_count(C.byref(n)))
@@ -284,6 +295,52 @@ class Device:
         h, w = shape if shape is not None else (0, 0)
         L.check(L.lib.twk_temporal_accumulate_cascade_trusted(self._h, ref(params), ref(cascade), ptr(currentLayers), ptr(currentGeometry), ptr(historyLayers),
                                                               ptr(historyGeometry), ref(historyCamera), ptr(trust), int(w), int(h), ptr(layersOut)))
+
+    # ---- moving an object (include/tweeker_hip.h "Moving an object", csrc/temporal_motion_device.h) ----
+    def updateInstanceTransform(self, idInstance, transform):
+        """twk_update_instance_transform: replaces the instance's object-to-world matrix (12 floats, row-major 3 x 4) and rebuilds
+        the acceleration structure as build() does, but KEEPS the temporal history: the next own-buffer temporalAccumulate /
+        temporalAccumulateRectified (or their assembled forms) looks the history up where the instance was. The geometry AOV is
+        stale afterwards. TwkError: before build(), a bad id, a transform that is not finite or singular, an instance with a light."""
+        t = (C.c_float * 12)(*[float(x) for x in np.asarray(transform, dtype=np.float32).reshape(12)])
+        L.check(L.lib.twk_update_instance_transform(self._h, int(idInstance), t))
+
+    def instanceTransform(self, idInstance):
+        """twk_get_instance_transform: the instance's transform as it is now, float32 [12]."""
+        t = (C.c_float * 12)()
+        L.check(L.lib.twk_get_instance_transform(self._h, int(idInstance), t))
+        return np.array(t, dtype=np.float32)
+
+    def temporalAccumulateMoving(self, params=None, rectify=None, current=None, history=None, motion=None, numMotion=0, shape=None, colourOut=None, historyOut=None,
+                                 momentsOut=None, trustOut=None):
+        """twk_temporal_accumulate_moving: the explicit form of temporalAccumulate (rectify None) or of temporalAccumulateRectified
+        with a motion table — motion: a device pointer to numMotion L.InstanceMotion records (16-byte aligned), indexed by instance.
+        motion None or numMotion 0: the existing calls, byte for byte."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda f: None if f is None else C.byref(f)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_moving(self._h, ref(params), ref(rectify), ref(current), ref(history), ptr(motion), int(numMotion), int(w), int(h),
+                                                     ptr(colourOut), ptr(historyOut), ptr(momentsOut), ptr(trustOut)))
+
+    def temporalAccumulateCascadeMoving(self, params=None, cascade=None, currentLayers=None, currentGeometry=None, historyLayers=None, historyGeometry=None,
+                                        historyCamera=None, trust=None, motion=None, numMotion=0, shape=None, layersOut=None):
+        """twk_temporal_accumulate_cascade_moving: temporalAccumulateCascade (trust None) or temporalAccumulateCascadeTrusted with a
+        motion table, as temporalAccumulateMoving takes it."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda s: None if s is None else C.byref(s)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_cascade_moving(self._h, ref(params), ref(cascade), ptr(currentLayers), ptr(currentGeometry), ptr(historyLayers),
+                                                             ptr(historyGeometry), ref(historyCamera), ptr(trust), ptr(motion), int(numMotion), int(w), int(h), ptr(layersOut)))
+
+    def readTemporalMotion(self):
+        """twk_read_temporal_motion: the motion table the last own-buffer (or assembled) merge used, a ctypes array of
+        L.InstanceMotion, one per instance; empty when it used none (no instance had moved since the history's frame)."""
+        n = C.c_int(0)
+        if L.lib.twk_read_temporal_motion(self._h, None, C.c_size_t(0), C.byref(n)) == L.TWK_SUCCESS:
+            return (L.InstanceMotion * 0)()
+        table = (L.InstanceMotion * max(1, n.value))()  # (a capacity that is too small is refused, with the count written)
+        L.check(L.lib.twk_read_temporal_motion(self._h, table, C.c_size_t(len(table)), C.byref(n)))
+        return table
 
     def setTimeView(self, enable=True):
         """≙ USE_TIME_VIEW: alpha of the accumulation buffer = running mean of the sample's shader-clock cycles x clockFactor x 1e-9."""

@@ -935,8 +935,8 @@ int twk_temporal_cascade_trusted_host(const TwkTemporal* tp, const TwkCascade* c
  *   twk_set_sample_offset; twk_launch 0 .. spp-1; twk_render_geometry; twk_temporal_accumulate [_rectified];
  * The complete definition is csrc/temporal_motion_device.h; tests/temporal_motion_restate.py restates it in numpy. What it is not:
  * no deforming geometry or vertex updates, no per-vertex motion, no motion blur, no moving lights (an instance that carries a
- * light is refused), no selective rebuild (every update rebuilds the whole acceleration structure, as twk_build does), no
- * environment reprojection, pinhole only. Shadows and inter-reflections that the move changes ELSEWHERE are stale history like a
+ * light is refused), no environment reprojection, pinhole only. By default every update rebuilds the whole acceleration structure, as
+ * twk_build does; "Selective instance updates" below rebuilds only what the moved instances change. Shadows and inter-reflections that the move changes ELSEWHERE are stale history like a
  * light edit's: the rectified merge discounts them.
  *
  * One record per instance, indexed by instance: previousFromCurrent is X = M_prev . M_cur^-1, row-major 3 x 4; moved = 0 says the
@@ -960,6 +960,55 @@ int twk_instance_motion(const float previous[12], const float current[12], TwkIn
 int twk_update_instance_transform(TwkDevice dev, int idInstance, const float transform[12]);
 /* The instance's transform as it is now. TWK_ERROR_INVALID_VALUE: a NULL argument, an id out of range. */
 int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12]);
+/* ---- Selective instance updates — new calls, ABI stays 9; in the default mode every existing call launches what it launched ----
+ * A handle built in TWK_UPDATE_SELECTIVE keeps the by-products of its build — the full-precision wide nodes (128 B per node), the
+ * expected-visit cost per node (4 B, with costed cuts), the pair flags (4 B per triangle slot, with pairs) and, on the host, every
+ * tree's box, height, SAH terms and leaf payload — and its transform updates rebuild only: the world-space tree of each moved
+ * FLATTENED instance, at the node and slot range it already has; the top level; the 8-wide root; and the quantised copy and pair
+ * references of exactly those node ranges, in one launch. A moved ENTERED instance changes its instance record and its box in the
+ * top level; no bottom-level tree is ever rebuilt. Afterwards the handle equals, byte for byte, a fresh handle built with the
+ * current transforms. Everything else about an update is as "Moving an object" says: the temporal history stays, adaptive state is
+ * dropped, the geometry AOV is stale, and an update that fails (an allocation, a HIP error, the depth refusal, with twk_build's
+ * text) leaves the handle unbuilt until twk_build. What it is not: no refit (a moved flattened instance gets a new tree), no vertex
+ * updates, no adding or removing of instances, no change of flatten policy or build quality between updates (those need twk_build),
+ * no moving emitters. Measured: profiles/r24_selective_update.md. */
+#define TWK_UPDATE_FULL      0 /* default: an update rebuilds everything twk_build builds; nothing is kept */
+#define TWK_UPDATE_SELECTIVE 1
+/* The mode of the NEXT twk_build: a handle built in full mode keeps doing full updates until it is built again (TwkUpdateInfo.selective
+ * says which ran). TWK_ERROR_INVALID_VALUE: a NULL handle (before any HIP call), any other mode. */
+int twk_set_update_mode(TwkDevice dev, int mode);
+/* Several moves, one rebuild: transforms holds 12 floats per entry. Works in both modes (full mode: one rebuild of everything for
+ * count moves). Every refusal of twk_update_instance_transform applies per entry and names it ("entry k"); also
+ * TWK_ERROR_INVALID_VALUE: count < 1, a NULL array, an id listed twice. A refused batch changes nothing.
+ * twk_update_instance_transform is its count == 1 case. */
+int twk_update_instance_transforms(TwkDevice dev, int count, const int* idInstances, const float* transforms);
+/* What the last update did. selective: which path ran; treesRebuilt: world-space trees of moved flattened instances (full: every tree); nodesRequantised:
+ * wide nodes the tail quantised (selective: the plan's total; full: all); slotsRewritten: triangle slots written; keptBytes: device
+ * memory the selective mode keeps beyond a full-mode handle's (0 in full mode); milliseconds: host wall time of the update, also
+ * TwkBuildInfo.buildMilliseconds. */
+typedef struct TwkUpdateInfo
+{
+  int selective, instancesMoved, treesRebuilt, topLevelRebuilt;
+  uint64_t nodesRequantised, slotsRewritten, instanceRecordsUploaded, keptBytes;
+  double milliseconds;
+} TwkUpdateInfo;
+/* TWK_ERROR_INVALID_VALUE: a NULL argument. TWK_ERROR_INVALID_STATE: before the handle's first update, and after an update whose
+ * rebuild failed (a refused update changes nothing and leaves the record of the update before it). */
+int twk_get_update_info(TwkDevice dev, TwkUpdateInfo* info);
+/* Pure CPU, no device: the plan of a selective update (csrc/update_plan.h, the code twk_build lays its scene out with). In:
+ * instanceGeometry[numInstances], geometryTriangles[numGeometries], the flatten policy, maxLeaf (triangles per leaf, default 2; an
+ * instance of no more triangles than that is a direct leaf of the top level) and the moved ids (numMoved may be 0: the layout
+ * only). Out: plan; flattened[numInstances] (0/1) and trees[numMoved] (the flattened moved instances, ascending; plan->treesRebuilt
+ * of them) and ranges[2 * (numMoved + 2)] ((first node, count) pairs; plan->numRanges of them: the rebuilt trees ascending, the top
+ * level, the two root slots), each NULL or given. TWK_ERROR_INVALID_VALUE: NULL input or plan, counts < 1, a geometry index or moved
+ * id out of range, a moved id listed twice, a negative triangle count. */
+typedef struct TwkUpdatePlan
+{
+  int instances, flattenedInstances, directLeafInstances, enteredGeometries, treesRebuilt, topLevelRebuilt, numRanges, tlasBase;
+  uint64_t nodes, triangleSlots, nodesRequantised, slotsRewritten;
+} TwkUpdatePlan;
+int twk_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                         int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges);
 /* EXPLICIT form of twk_temporal_accumulate (rp NULL; trustOut must then be NULL) or of twk_temporal_accumulate_rectified (rp given),
  * with a table: motion is a DEVICE pointer to numMotion records, 16-byte aligned, indexed by instance; an instance beyond the table
  * is unmoved. motion NULL or numMotion 0 launches the existing kernels: byte for byte the existing call. Otherwise, per candidate
@@ -1234,6 +1283,10 @@ int twk_app_get_temporal_rectify(TwkApp app, int* enabled, TwkTemporalRectify* r
  * -1: the description has no such key. rtigo3_hip refuses the key without "temporalAccumulation 1", for an id beyond the scene's
  * instances and for an instance that carries a light. TwkAppInfo is unchanged. */
 int twk_app_get_temporal_motion(TwkApp app, int* idInstance, float step[3]);
+/* "selectiveUpdate 0|1" of the system description (default 0; written back only when on): a render loop sets
+ * twk_set_update_mode(dev, TWK_UPDATE_SELECTIVE) on every device before twk_app_init_device, so that the updates of
+ * "temporalInstanceStep" are selective ("Selective instance updates" above). TWK_ERROR_INVALID_VALUE: a NULL argument. */
+int twk_app_get_selective_update(TwkApp app, int* enabled);
 int twk_app_set_resolution(TwkApp app, int width, int height); /* re-derives the camera frustum (aspect) */
 int twk_app_get_state(TwkApp app, TwkDeviceState* state);
 int twk_app_get_cameras(TwkApp app, TwkCameraDefinition* out, int capacity);

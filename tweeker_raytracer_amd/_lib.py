@@ -270,6 +270,23 @@ class BuildInfo(C.Structure):
                 ("pairLeaves", C.c_uint64), ("pairTriangles", C.c_uint64)]
 
 
+TWK_UPDATE_FULL, TWK_UPDATE_SELECTIVE = 0, 1  # twk_set_update_mode (include/tweeker_hip.h "Selective instance updates")
+
+
+class UpdateInfo(C.Structure):
+    """≙ TwkUpdateInfo: what the last instance-transform update of a handle did (twk_get_update_info)."""
+    _fields_ = [("selective", C.c_int), ("instancesMoved", C.c_int), ("treesRebuilt", C.c_int), ("topLevelRebuilt", C.c_int),
+                ("nodesRequantised", C.c_uint64), ("slotsRewritten", C.c_uint64), ("instanceRecordsUploaded", C.c_uint64),
+                ("keptBytes", C.c_uint64), ("milliseconds", C.c_double)]
+
+
+class UpdatePlan(C.Structure):
+    """≙ TwkUpdatePlan: the layout of a scene and what a selective update of some of its instances touches (twk_update_plan_host)."""
+    _fields_ = [("instances", C.c_int), ("flattenedInstances", C.c_int), ("directLeafInstances", C.c_int), ("enteredGeometries", C.c_int),
+                ("treesRebuilt", C.c_int), ("topLevelRebuilt", C.c_int), ("numRanges", C.c_int), ("tlasBase", C.c_int),
+                ("nodes", C.c_uint64), ("triangleSlots", C.c_uint64), ("nodesRequantised", C.c_uint64), ("slotsRewritten", C.c_uint64)]
+
+
 class AppInfo(C.Structure):
     _fields_ = [("strategy", C.c_int), ("devicesMask", C.c_int), ("light", C.c_int), ("miss", C.c_int),
                 ("lensShader", C.c_int), ("samplesSqrt", C.c_int), ("resolution", i2), ("tileSize", i2),
@@ -306,6 +323,7 @@ SYMBOLS = [
     "twk_temporal_accumulate_cascade", "twk_temporal_enable_cascade", "twk_get_temporal_cascade_device_pointer", "twk_read_temporal_cascade", "twk_temporal_cascade_host",
     "twk_instance_motion", "twk_update_instance_transform", "twk_get_instance_transform", "twk_temporal_accumulate_moving", "twk_temporal_accumulate_cascade_moving",
     "twk_temporal_moving_host", "twk_temporal_cascade_moving_host", "twk_read_temporal_motion", "twk_app_get_temporal_motion",
+    "twk_set_update_mode", "twk_update_instance_transforms", "twk_get_update_info", "twk_update_plan_host", "twk_app_get_selective_update",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",
     "twk_read_assembled_geometry", "twk_temporal_accumulate_assembled", "twk_app_get_temporal", "twk_app_get_temporal_rectify",

@@ -196,6 +196,14 @@ class Application:
         return inst.value, tuple(step)
 
     @property
+    def selectiveUpdate(self):
+        """"selectiveUpdate 0|1" of the system description: a render loop calls Device.setUpdateMode(TWK_UPDATE_SELECTIVE) on every
+        device before initDevice, and the updates of `temporalMotion` then rebuild only what the instance changes."""
+        on = C.c_int(0)
+        L.check(L.lib.twk_app_get_selective_update(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @property
     def fireflyCascade(self):
         """(enabled, Cascade, CascadeResolve) from "fireflyCascade", "fireflyCascadeLayers", "fireflyCascadeStart",
         "fireflyCascadeBase", "fireflyCascadeKappa" of the system description; initDevice enables the device's cascade when the key

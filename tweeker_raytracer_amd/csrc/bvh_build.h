@@ -19,6 +19,12 @@ void launchWideRoot(BvhNode* wide, int root, int firstNew, int* result, hipStrea
 // Before launchTopCache, so that the cached copies and the tile entry lists inherit the references.
 void launchPairLeaves(float4* wideQ, int count, const int* pairFlags, int numSlots, const float4* triangles, float4* pairs, hipStream_t stream);
 
+// launchQuantizeWide and launchPairLeaves in one launch over node ranges only (bvh_build.hip rangedTailKernel): ranges (device) holds
+// numRanges pairs (first node, position of that node among the concatenated ranges), total = the nodes of all ranges. pairFlags
+// nullptr: no pair rewrite.
+void launchRangedTail(const BvhNode* wide, float4* wideQ, const int2* ranges, int numRanges, int total, const int* pairFlags, int numSlots,
+                      const float4* triangles, float4* pairs, hipStream_t stream);
+
 // Build primitives of a geometry's triangles for BvhBuilder::buildTriangles: triangles 2k, 2k + 1 with the index triples
 // (a, b, c), (c, d, a) — what every mesh generator emits per quad — are one primitive (first triangle | sign bit), every other
 // triangle is one of its own. Indices are compared, not positions. Returns the number of pairs.
@@ -73,6 +79,9 @@ public:
   // over its leaf primitives), measured after every build.
   double lastSahInner() const { return m_lastSahInner; }
   double lastSahLeaf() const { return m_lastSahLeaf; }
+  // A tree over ONE build primitive has no terms of its own and leaves those of the tree built before it standing; a scene's build
+  // starts from none, so that what it reports does not depend on what the handle built earlier.
+  void   clearLastSah() { m_lastSahInner = 0.0; m_lastSahLeaf = 0.0; }
   // Height of the binary tree built last (inner nodes on the longest root-to-leaf path, after the leaf collapse): what a
   // single-ray traversal may have to keep on its stack.
   int    lastHeight() const { return m_lastHeight; }

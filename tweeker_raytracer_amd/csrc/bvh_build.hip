@@ -484,14 +484,11 @@ __global__ void slotCountsKernel(const unsigned long long* __restrict__ keys, co
   counts[position] = (position == count) ? 0 : ((primFirst[(unsigned int) (keys[position] & 0xffffffffull)] < 0) ? 2 : 1);
 }
 
-// Quantised copy of the wide nodes (device_types.h "quantised wide node"), one thread per inner node index. The grid
+// Quantised copy of one wide node (device_types.h "quantised wide node"). The grid
 // cell of an axis is the smallest power of two with extent / cell < 254; lo planes are rounded down and hi planes up,
 // and each is checked against the float expression the traversal evaluates (origin + q * cell).
-__global__ void quantizeWideKernel(const BvhNode* __restrict__ wide, float4* __restrict__ out, int count)
+TWK_D void quantizeWideNode(const float4* __restrict__ w, float4* __restrict__ o)
 {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const float4* w = reinterpret_cast<const float4*>(wide + 2 * (size_t) i);
   const float inf = __uint_as_float(0x7f800000u);
   float lo[4][3], hi[4][3];
   int ref[4];
@@ -525,7 +522,6 @@ __global__ void quantizeWideKernel(const BvhNode* __restrict__ wide, float4* __r
       qhi[c] |= (unsigned int) qh << (8 * k);
     }
   }
-  float4* o = out + 4 * (size_t) i;
   o[0] = make_float4(org[0], org[1], org[2], cell[0]);
   o[1] = make_float4(cell[1], cell[2], __uint_as_float(qlo[0]), __uint_as_float(qlo[1]));
   o[2] = make_float4(__uint_as_float(qlo[2]), __uint_as_float(qhi[0]), __uint_as_float(qhi[1]), __uint_as_float(qhi[2]));
@@ -535,6 +531,14 @@ __global__ void quantizeWideKernel(const BvhNode* __restrict__ wide, float4* __r
   while (first < 3 && !valid[first]) ++first;
   o[3] = make_float4(__int_as_float(valid[0] ? ref[0] : ref[first]), __int_as_float(valid[1] ? ref[1] : ref[first]),
                      __int_as_float(valid[2] ? ref[2] : ref[first]), __int_as_float(valid[3] ? ref[3] : ref[first]));
+}
+
+// One thread per inner node index. The node's body is quantizeWideNode: the eight float4 at w in, the four float4 at o out.
+__global__ void quantizeWideKernel(const BvhNode* __restrict__ wide, float4* __restrict__ out, int count)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  quantizeWideNode(reinterpret_cast<const float4*>(wide + 2 * (size_t) i), out + 4 * (size_t) i);
 }
 
 void launchQuantizeWide(const BvhNode* wide, float4* out, int count, hipStream_t stream)
@@ -658,17 +662,12 @@ __global__ void wideRootKernel(BvhNode* wide, int root, int firstNew, int* resul
   result[0] = 1;
 }
 
-// Pair leaves (device_types.h "triangle pairs"), one thread per quantised wide node: a reference to a world-space leaf of two
+// Pair leaves (device_types.h "triangle pairs"), the four references of one quantised wide node: a reference to a world-space leaf of two
 // slots at which a pair begins gets its record written at pairs[4 * (first slot / 2)] — two pairs never share a slot, so the index
 // is theirs alone — and loses TWK_LEAF_WORLD, which is how the persistent kernel knows it. A leaf referenced from several entries
 // (an unused entry repeats the first, the 8-wide root copies its entries) is written by each of them with the same words.
-__global__ void pairLeavesKernel(float4* __restrict__ wideQ, int count, const int* __restrict__ pairFlags, int numSlots,
-                                 const float4* __restrict__ triangles, float4* __restrict__ pairs)
+TWK_D bool pairLeafReferences(int r[4], const int* __restrict__ pairFlags, int numSlots, const float4* __restrict__ triangles, float4* __restrict__ pairs)
 {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const float4 refs = wideQ[4 * (size_t) i + 3];
-  int r[4] = {__float_as_int(refs.x), __float_as_int(refs.y), __float_as_int(refs.z), __float_as_int(refs.w)};
   bool changed = false;
   for (int k = 0; k < 4; ++k)
   {
@@ -686,12 +685,73 @@ __global__ void pairLeavesKernel(float4* __restrict__ wideQ, int count, const in
     r[k] = ~(payload & ~TWK_LEAF_WORLD);
     changed = true;
   }
-  if (changed) wideQ[4 * (size_t) i + 3] = make_float4(__int_as_float(r[0]), __int_as_float(r[1]), __int_as_float(r[2]), __int_as_float(r[3]));
+  return changed;
+}
+
+// One thread per quantised wide node; the node's body is pairLeafReferences on its four references.
+__global__ void pairLeavesKernel(float4* __restrict__ wideQ, int count, const int* __restrict__ pairFlags, int numSlots,
+                                 const float4* __restrict__ triangles, float4* __restrict__ pairs)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float4 refs = wideQ[4 * (size_t) i + 3];
+  int r[4] = {__float_as_int(refs.x), __float_as_int(refs.y), __float_as_int(refs.z), __float_as_int(refs.w)};
+  if (pairLeafReferences(r, pairFlags, numSlots, triangles, pairs))
+    wideQ[4 * (size_t) i + 3] = make_float4(__int_as_float(r[0]), __int_as_float(r[1]), __int_as_float(r[2]), __int_as_float(r[3]));
 }
 
 void launchPairLeaves(float4* wideQ, int count, const int* pairFlags, int numSlots, const float4* triangles, float4* pairs, hipStream_t stream)
 {
   if (count > 0) hipLaunchKernelGGL(pairLeavesKernel, dim3((count + 255) / 256), dim3(256), 0, stream, wideQ, count, pairFlags, numSlots, triangles, pairs);
+}
+
+// The ranged tail of a selective update (device_scene.hip updateSelective): quantizeWideKernel and pairLeavesKernel in one launch,
+// over the node ranges that changed instead of the whole scene. ranges[r] = (first node, position of that node among the
+// concatenated ranges), ascending in both, numRanges >= 1; one thread per position below `total` finds its range by binary search —
+// in LDS while the table fits TWK_TAIL_RANGES_LDS entries (8 KB), in global memory beyond. The thread reads its 128-byte wide node
+// once, as eight 16-byte loads, and writes its 64-byte quantised node once, as four 16-byte stores; the pair rewrite works on the
+// references in registers in between. A node's quantisation and its pair rewrite depend on no other node, so the fusion is exact.
+// pairFlags == nullptr: no pair leaves in this scene. The records of pairs that a rebuilt tree no longer has stay where they are:
+// `pairs` is sized by slots, nothing references them, and a fresh build's array holds as little there (it is not zeroed either).
+#define TWK_TAIL_RANGES_LDS 1024
+__global__ void __launch_bounds__(256) rangedTailKernel(const BvhNode* __restrict__ wide, float4* __restrict__ wideQ, const int2* __restrict__ ranges, int numRanges, int total,
+                                                        const int* __restrict__ pairFlags, int numSlots, const float4* __restrict__ triangles, float4* __restrict__ pairs)
+{
+  __shared__ int2 table[TWK_TAIL_RANGES_LDS];
+  const bool staged = numRanges <= TWK_TAIL_RANGES_LDS; // uniform over the grid
+  if (staged)
+  {
+    for (int k = threadIdx.x; k < numRanges; k += blockDim.x) table[k] = ranges[k];
+    __syncthreads();
+  }
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int lo = 0, hi = numRanges - 1; // the last range that starts at or before position t
+  while (lo < hi)
+  {
+    const int mid = (lo + hi + 1) >> 1;
+    const int start = staged ? table[mid].y : ranges[mid].y;
+    if (start <= t) lo = mid; else hi = mid - 1;
+  }
+  const int2 range = staged ? table[lo] : ranges[lo];
+  const size_t node = (size_t) range.x + (size_t) (t - range.y);
+  float4 q[4];
+  quantizeWideNode(reinterpret_cast<const float4*>(wide + 2 * node), q);
+  if (pairFlags != nullptr)
+  {
+    int r[4] = {__float_as_int(q[3].x), __float_as_int(q[3].y), __float_as_int(q[3].z), __float_as_int(q[3].w)};
+    if (pairLeafReferences(r, pairFlags, numSlots, triangles, pairs))
+      q[3] = make_float4(__int_as_float(r[0]), __int_as_float(r[1]), __int_as_float(r[2]), __int_as_float(r[3]));
+  }
+  float4* o = wideQ + 4 * node;
+  o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
+}
+
+void launchRangedTail(const BvhNode* wide, float4* wideQ, const int2* ranges, int numRanges, int total, const int* pairFlags, int numSlots,
+                      const float4* triangles, float4* pairs, hipStream_t stream)
+{
+  if (total > 0 && numRanges > 0)
+    hipLaunchKernelGGL(rangedTailKernel, dim3((total + 255) / 256), dim3(256), 0, stream, wide, wideQ, ranges, numRanges, total, pairFlags, numSlots, triangles, pairs);
 }
 
 void launchWideRoot(BvhNode* wide, int root, int firstNew, int* result, hipStream_t stream)

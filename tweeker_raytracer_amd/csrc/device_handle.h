@@ -20,6 +20,7 @@
 #include "temporal_rectify_device.h"
 #include "assemble_device.h"
 #include "device_buffers.h"
+#include "update_plan.h"
 
 #include <string>
 #include <vector>
@@ -272,6 +273,26 @@ struct TwkDevice_t
   hipEvent_t  laneFork = nullptr;
   int   lanesForced = 0; // TWK_PASS_LANES: 0 = choose by pass size
   int   laneTraceWaves = 0; // TWK_LANE_TRACE_WAVES: trace blocks per CU of each lane (0 = TWK_TRACE_WAVES / lanes)
+
+  // Selective instance updates (include/tweeker_hip.h; device_scene.hip updateSelective). updateMode: twk_set_update_mode, read by
+  // the next build. kept.valid: the built scene was built in selective mode and its by-products are still here — d_wideNodes (above),
+  // d_nodeCost (with costedCuts) and d_pairFlags (with pairs) on the device, and on the host the layout, per tree its box, payload,
+  // height and SAH terms, and the build primitives of every geometry. A full-mode build holds none of it past its end (KeptScope).
+  // d_updateSoup / d_updateRanges / d_updateResult: scratch of the updates, grown on demand.
+  struct TreeTerms { double sahInner = 0.0, sahLeaf = 0.0; int height = 0; };
+  struct KeptBuild
+  {
+    bool valid = false, pairs = false, pairRewrite = false;
+    SceneLayout layout;
+    std::vector<TreeTerms> geometryTerms, instanceTerms; // per entered geometry's tree, per flattened instance's tree
+    std::vector<float4> boxLo, boxHi; std::vector<int> leafPayload; int topHeight = 0;
+    std::vector<std::vector<int>> primFirst;
+    void clear() { *this = KeptBuild(); }
+  } kept;
+  int updateMode = TWK_UPDATE_FULL;
+  DeviceArray<float> d_nodeCost; DeviceArray<int> d_pairFlags;
+  DeviceArray<int4> d_updateSoup; DeviceArray<int2> d_updateRanges; DeviceArray<int> d_updateResult;
+  TwkUpdateInfo updateInfo = {}; bool updateInfoValid = false;
 
   std::vector<std::vector<char>> hostScene; // twk_debug_snapshot_scene: host copies of the scene arrays
 

@@ -127,10 +127,54 @@ try
 }
 TWK_CATCH("twk_get_stream_layout")
 
+// The device record of instance i of a scene laid out as `layout` says, with the transform the instance has now
+static void instanceRecord(TwkDevice dev, const SceneLayout& layout, int i, DevInstance& r)
+{
+  const InstanceHost& inst = dev->instances[i];
+  const GeometryHost& g = dev->geometries[inst.geometry];
+  memset(&r, 0, sizeof(r));
+  memcpy(r.objectToWorld, inst.transform, sizeof(float) * 12);
+  invertAffine(inst.transform, r.worldToObject);
+  r.blasRoot = layout.flattened[i] ? layout.flatNodeBase[i] : g.nodeBase; r.material = inst.material; r.light = inst.light;
+  r.triangleFirst = layout.flattened[i] ? layout.flatTriangleBase[i] : g.triangleBase; r.triangleCount = g.numTriangles;
+  r.attributeBase = g.attributeBase; r.indexBase = g.indexBase; r.geometry = inst.geometry;
+}
+
+// World box of an entered instance: its geometry's object-space root box through the transform
+static void enteredWorldBox(const float rootBounds[6], const float m[12], float4& boxLo, float4& boxHi)
+{
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int corner = 0; corner < 8; ++corner)
+  {
+    const float x = rootBounds[(corner & 1) ? 3 : 0], y = rootBounds[(corner & 2) ? 4 : 1], z = rootBounds[(corner & 4) ? 5 : 2];
+    const float w[3] = { m[0] * x + m[1] * y + m[2] * z + m[3], m[4] * x + m[5] * y + m[6] * z + m[7], m[8] * x + m[9] * y + m[10] * z + m[11] };
+    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], w[k]); hi[k] = fmaxf(hi[k], w[k]); }
+  }
+  for (int k = 0; k < 3; ++k)
+  {
+    // world box of an object-space box: pad for the rounding of the transform in both directions
+    const float e = 1.0e-5f * fmaxf(1.0f, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
+    lo[k] -= e; hi[k] += e;
+  }
+  boxLo = make_float4(lo[0], lo[1], lo[2], 0.0f);
+  boxHi = make_float4(hi[0], hi[1], hi[2], 0.0f);
+}
+
+// The depth refusal of a build: the text of twk_build, for the selective update too
+static int refuseDepth(TwkDevice dev, int traversalDepth, int topHeight, int maxFlatHeight, int maxEnteredHeight)
+{
+  dev->built = false;
+  return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: the acceleration structure is " + std::to_string(traversalDepth) + " levels deep (top " + std::to_string(topHeight) +
+                     ", flattened trees " + std::to_string(maxFlatHeight) + ", entered geometries " + std::to_string(maxEnteredHeight) + "); the traversal stacks hold " +
+                     std::to_string(TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL) + " entries" + (dev->builder.quality() == TWK_BUILD_SAH ? " (try twk_set_build_quality(TWK_BUILD_LBVH))" : ""));
+}
+
 // Internal, no entry point: the build of the acceleration structure from the handle's geometries and instances as they are, on an
-// active handle — the body of twk_build and of twk_update_instance_transform (its refusals name twk_build, whose they are). Drops
+// active handle — the body of twk_build and of a full-mode twk_update_instance_transform[s] (its refusals name twk_build, whose they are). Drops
 // the adaptive state and leaves the geometry AOV stale; the temporal history is the caller's business.
-static int buildScene(TwkDevice dev)
+// keep: the build keeps its by-products for selective updates — twk_build passes the handle's update mode, an update of a scene that
+// was built without them passes false whatever the mode has been set to since (the mode takes effect at the next twk_build).
+static int buildScene(TwkDevice dev, bool keep)
 {
   int rc;
   if (dev->geometries.empty() || dev->instances.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: the scene has no geometry or no instance");
@@ -155,43 +199,36 @@ static int buildScene(TwkDevice dev)
   // transform, per-instance Woop constants, exit step). A flattened instance gets world-space triangle slots and an
   // LBVH of its own whose root is spliced into the top level as an inner node: traversal walks from the top level
   // straight into it with the untransformed ray.
+  // The decision and the ranges it gives every tree are update_plan.h's (sceneLayout), which the selective update plans with too.
   const int numInstances = (int) dev->instances.size();
-  std::vector<int> references(dev->geometries.size(), 0);
-  for (const InstanceHost& inst : dev->instances) references[inst.geometry]++;
-  std::vector<char> flattened(numInstances, 0), needsBlas(dev->geometries.size(), 0);
-  int numEntered = 0, maxFlatTriangles = 0;
-  for (int i = 0; i < numInstances; ++i)
-  {
-    const int g = dev->instances[i].geometry;
-    flattened[i] = (dev->geometries[g].numTriangles <= dev->flattenMaxTriangles) || (references[g] <= dev->flattenMaxReferences);
-    if (flattened[i]) maxFlatTriangles = std::max(maxFlatTriangles, dev->geometries[g].numTriangles);
-    else { needsBlas[g] = 1; ++numEntered; }
-  }
+  if (const char* e = getenv("TWK_MAX_LEAF")) dev->builder.setMaxLeaf(atoi(e)); // tuning knob, default 2 triangles per leaf
+  std::vector<int> instanceGeometry((size_t) numInstances), geometryTriangles(dev->geometries.size());
+  for (int i = 0; i < numInstances; ++i) instanceGeometry[i] = dev->instances[i].geometry;
+  for (size_t k = 0; k < dev->geometries.size(); ++k) geometryTriangles[k] = dev->geometries[k].numTriangles;
+  SceneLayout layout;
+  sceneLayout(instanceGeometry.data(), numInstances, geometryTriangles.data(), (int) dev->geometries.size(), dev->flattenMaxTriangles, dev->flattenMaxReferences,
+              dev->builder.maxLeaf(), dev->directSmallLeaves, layout);
+  const std::vector<char>& flattened = layout.flattened; const std::vector<char>& needsBlas = layout.needsBlas;
+  const std::vector<int>& flatTriangleBase = layout.flatTriangleBase; const std::vector<int>& flatNodeBase = layout.flatNodeBase;
+  const int numEntered = layout.numEntered, maxFlatTriangles = layout.maxFlatTriangles, tlasBase = layout.tlasBase;
+  const size_t numTris = layout.numTriangles, numNodes = layout.numNodes;
 
   // shared attribute / index arrays and the node / triangle budgets: one bottom level per geometry that is still
   // entered through an instance, one world-space tree per flattened instance, the top level
-  size_t numAttr = 0, numIdx = 0, numTris = 0, numNodes = 0;
+  size_t numAttr = 0, numIdx = 0;
   for (size_t k = 0; k < dev->geometries.size(); ++k)
   {
     GeometryHost& g = dev->geometries[k];
     g.attributeBase = (unsigned int) numAttr; g.indexBase = (unsigned int) numIdx;
-    g.triangleBase = (int) numTris; g.nodeBase = (int) numNodes;
+    g.triangleBase = layout.geometryTriangleBase[k]; g.nodeBase = layout.geometryNodeBase[k];
     numAttr += g.attributes.size(); numIdx += g.indices.size();
-    if (needsBlas[k]) { numTris += (size_t) g.numTriangles; numNodes += (size_t) ((g.numTriangles > 1) ? g.numTriangles - 1 : 1); }
   }
-  std::vector<int> flatTriangleBase(numInstances, -1), flatNodeBase(numInstances, -1);
-  for (int i = 0; i < numInstances; ++i)
-  {
-    if (!flattened[i]) continue;
-    const int n = dev->geometries[dev->instances[i].geometry].numTriangles;
-    flatTriangleBase[i] = (int) numTris; flatNodeBase[i] = (int) numNodes;
-    numTris += (size_t) n; numNodes += (size_t) ((n > 1) ? n - 1 : 1);
-  }
-  const int tlasBase = (int) numNodes;
-  numNodes += (size_t) ((numInstances > 1) ? numInstances - 1 : 1);
   if (numTris >= ((size_t) 1 << 28) || numAttr >= ((size_t) 1 << 31) || numIdx >= ((size_t) 1 << 31))
     return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: " + std::to_string(numTris) + " triangle slots; a leaf reference holds 28 bits of slot index");
 
+  // What a selective-mode build keeps past its end is released by anything else: a full-mode build, a failure
+  struct KeptScope { TwkDevice dev; bool keep = false; ~KeptScope() { if (!keep) { dev->d_wideNodes.release(); dev->d_nodeCost.release(); dev->d_pairFlags.release(); dev->d_updateSoup.release(); dev->d_updateRanges.release(); dev->d_updateResult.release(); dev->kept.clear(); } } } keptScope{dev};
+  dev->kept.clear(); dev->d_nodeCost.release(); dev->d_pairFlags.release();
   // the old scene's arrays are freed before the first of the new one's is asked for
   dev->d_attributes.release(); dev->d_indices.release(); dev->d_nodes.release(); dev->d_wideNodes.release(); dev->d_wideQ.release(); dev->d_triangles.release(); dev->d_shadeTriangles.release(); dev->d_instances.release();
   if ((rc = dev->d_attributes.allocate(sizeof(TwkTriangleAttributes) / sizeof(float) * numAttr)) || (rc = dev->d_indices.allocate(numIdx)) || (rc = dev->d_nodes.allocate(numNodes)) ||
@@ -207,7 +244,6 @@ static int buildScene(TwkDevice dev)
     HIP_TRY(hipMemcpyAsync(dev->d_indices + g.indexBase, g.indices.data(), sizeof(unsigned int) * g.indices.size(), hipMemcpyHostToDevice, dev->stream));
   }
 
-  if (const char* e = getenv("TWK_MAX_LEAF")) dev->builder.setMaxLeaf(atoi(e)); // tuning knob, default 2 triangles per leaf
   // Triangle pairs (device_types.h): the two halves of a quad are one primitive of every tree's build. pairFlags: per slot, whether
   // a pair begins there — what the references of pair leaves are found by once the trees stand.
   const bool pairs = dev->trianglePairs && dev->builder.maxLeaf() >= 2;
@@ -216,18 +252,20 @@ static int buildScene(TwkDevice dev)
   if (pairs)
     for (size_t k = 0; k < dev->geometries.size(); ++k)
       geometryPairs[k] = trianglePairs(dev->geometries[k].indices.data(), dev->geometries[k].numTriangles, primFirst[k]);
-  DeviceArray<int> pairFlags;
+  DeviceArray<int>& pairFlags = dev->d_pairFlags;
   dev->d_trianglePairs.release();
   if (pairs)
   {
     if ((rc = pairFlags.allocate(numTris))) return rc;
     HIP_TRY(hipMemsetAsync(pairFlags, 0, sizeof(int) * numTris, dev->stream));
   }
-  DeviceArray<float> nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
+  DeviceArray<float>& nodeCost = dev->d_nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
   if (dev->costedCuts && (rc = nodeCost.allocate(numNodes))) return rc;
-  struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder}; // the array does not outlive this call
+  struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder}; // the builder knows the array during a build only
   dev->builder.setNodeCost(nodeCost);
+  dev->builder.clearLastSah();
   int maxEnteredHeight = 0, maxFlatHeight = 0, topHeight = 0; // binary-tree heights: what a traversal stack may have to hold
+  std::vector<TwkDevice_t::TreeTerms> geometryTerms(dev->geometries.size()), instanceTerms((size_t) numInstances); // what a selective-mode build keeps of every tree
   // bottom level: one LBVH per entered geometry, shared by all of its instances (Device.cpp:1339 caches the GAS per Triangles id)
   for (size_t k = 0; k < dev->geometries.size(); ++k)
   {
@@ -239,22 +277,12 @@ static int buildScene(TwkDevice dev)
     info.pairLeaves += geometryPairs[k];
     info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
     maxEnteredHeight = std::max(maxEnteredHeight, dev->builder.lastHeight());
+    geometryTerms[k].sahInner = dev->builder.lastSahInner(); geometryTerms[k].sahLeaf = dev->builder.lastSahLeaf(); geometryTerms[k].height = dev->builder.lastHeight();
   }
 
   // instance records (shading reads them for every hit, flattened or not)
   std::vector<DevInstance> records(numInstances);
-  for (int i = 0; i < numInstances; ++i)
-  {
-    const InstanceHost& inst = dev->instances[i];
-    const GeometryHost& g = dev->geometries[inst.geometry];
-    DevInstance& r = records[i];
-    memset(&r, 0, sizeof(r));
-    memcpy(r.objectToWorld, inst.transform, sizeof(float) * 12);
-    invertAffine(inst.transform, r.worldToObject);
-    r.blasRoot = flattened[i] ? flatNodeBase[i] : g.nodeBase; r.material = inst.material; r.light = inst.light;
-    r.triangleFirst = flattened[i] ? flatTriangleBase[i] : g.triangleBase; r.triangleCount = g.numTriangles;
-    r.attributeBase = g.attributeBase; r.indexBase = g.indexBase; r.geometry = inst.geometry;
-  }
+  for (int i = 0; i < numInstances; ++i) instanceRecord(dev, layout, i, records[i]);
   HIP_TRY(hipMemcpyAsync(dev->d_instances, records.data(), sizeof(DevInstance) * numInstances, hipMemcpyHostToDevice, dev->stream));
 
   // world-space trees of the flattened instances + the world boxes of all instances
@@ -278,38 +306,24 @@ static int buildScene(TwkDevice dev)
       info.pairLeaves += geometryPairs[inst.geometry];
       info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
       maxFlatHeight = std::max(maxFlatHeight, dev->builder.lastHeight());
+      instanceTerms[i].sahInner = dev->builder.lastSahInner(); instanceTerms[i].sahLeaf = dev->builder.lastSahLeaf(); instanceTerms[i].height = dev->builder.lastHeight();
       boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
       boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
       leafPayload[i] = ~flatNodeBase[i]; // child reference ~payload = the instance's root node: an inner reference
       // A flattened instance of no more triangles than a leaf holds (a wall, the area light: two triangles) IS a leaf of the
       // top level: its slots are referenced directly instead of through a one-node tree of two single-triangle leaves —
       // one node visit and one leaf step less for every ray that crosses its box (C2: six of the eight instances).
-      if (dev->directSmallLeaves && g.numTriangles <= dev->builder.maxLeaf() && g.numTriangles <= 4)
+      if (layout.directLeaf[i])
       {
         leafPayload[i] = flatTriangleBase[i] | ((g.numTriangles - 1) << 28) | TWK_LEAF_WORLD;
         info.directLeafInstances += 1;
       }
       continue;
     }
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int corner = 0; corner < 8; ++corner)
-    {
-      const float x = g.rootBounds[(corner & 1) ? 3 : 0], y = g.rootBounds[(corner & 2) ? 4 : 1], z = g.rootBounds[(corner & 4) ? 5 : 2];
-      const float* m = inst.transform;
-      const float w[3] = { m[0] * x + m[1] * y + m[2] * z + m[3], m[4] * x + m[5] * y + m[6] * z + m[7], m[8] * x + m[9] * y + m[10] * z + m[11] };
-      for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], w[k]); hi[k] = fmaxf(hi[k], w[k]); }
-    }
-    for (int k = 0; k < 3; ++k)
-    {
-      // world box of an object-space box: pad for the rounding of the transform in both directions
-      const float e = 1.0e-5f * fmaxf(1.0f, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
-      lo[k] -= e; hi[k] += e;
-    }
-    boxLo[i] = make_float4(lo[0], lo[1], lo[2], 0.0f);
-    boxHi[i] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    enteredWorldBox(g.rootBounds, inst.transform, boxLo[i], boxHi[i]);
     leafPayload[i] = i;
   }
-  if (numInstances == 1 && flattened[0]) dev->tlasRoot = flatNodeBase[0]; // the one world-space tree IS the scene
+  if (layout.single) dev->tlasRoot = flatNodeBase[0]; // the one world-space tree IS the scene
   else
   {
     HIP_TRY(dev->builder.buildInstances(dev->stream, boxLo.data(), boxHi.data(), leafPayload.data(), numInstances, dev->d_nodes + tlasBase, dev->d_wideNodes + 2 * (size_t) tlasBase, tlasBase));
@@ -323,13 +337,7 @@ static int buildScene(TwkDevice dev)
   const int traversalDepth = topHeight + std::max(maxFlatHeight, (numEntered > 0) ? 1 + maxEnteredHeight : 0);
   int depthLimit = TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL - 2;
   if (const char* e = getenv("TWK_MAX_TRAVERSAL_DEPTH")) depthLimit = std::min(depthLimit, atoi(e)); // test hook: a lower limit only
-  if (traversalDepth > depthLimit)
-  {
-    dev->built = false;
-    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: the acceleration structure is " + std::to_string(traversalDepth) + " levels deep (top " + std::to_string(topHeight) +
-                       ", flattened trees " + std::to_string(maxFlatHeight) + ", entered geometries " + std::to_string(maxEnteredHeight) + "); the traversal stacks hold " +
-                       std::to_string(TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL) + " entries" + (dev->builder.quality() == TWK_BUILD_SAH ? " (try twk_set_build_quality(TWK_BUILD_LBVH))" : ""));
-  }
+  if (traversalDepth > depthLimit) return refuseDepth(dev, traversalDepth, topHeight, maxFlatHeight, maxEnteredHeight);
   // the persistent trace kernel reads the quantised copy of the wide nodes; the full-precision ones were scratch
   // the root as two wide nodes where that pays (bvh_build.hip wideRootKernel)
   dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
@@ -356,7 +364,18 @@ static int buildScene(TwkDevice dev)
   launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(dev->stream));
-  dev->d_wideNodes.release();
+  if (keep)
+  {
+    // selective mode: the by-products stay (include/tweeker_hip.h "Selective instance updates")
+    TwkDevice_t::KeptBuild& kept = dev->kept;
+    kept.pairs = pairs; kept.pairRewrite = (dev->d_trianglePairs.capacity() != 0);
+    kept.layout = std::move(layout);
+    kept.geometryTerms = std::move(geometryTerms); kept.instanceTerms = std::move(instanceTerms);
+    kept.boxLo = std::move(boxLo); kept.boxHi = std::move(boxHi); kept.leafPayload = std::move(leafPayload); kept.topHeight = topHeight;
+    kept.primFirst = std::move(primFirst);
+    kept.valid = true; keptScope.keep = true;
+  }
+  else dev->d_wideNodes.release();
 
   info.maxTraversalDepth = (uint64_t) traversalDepth;
   info.pairTriangles = 2 * info.pairLeaves;
@@ -375,29 +394,274 @@ int twk_build(TwkDevice dev)
 try
 {
   int rc = activate(dev, "twk_build"); if (rc) return rc;
-  if ((rc = buildScene(dev))) return rc;
+  if ((rc = buildScene(dev, dev->updateMode == TWK_UPDATE_SELECTIVE))) return rc;
   dropTemporal(dev); // the temporal history describes the scene that was
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_build")
 
+} // extern "C"
+
+// Device memory a selective-mode handle keeps beyond a full-mode one's
+static uint64_t keptBytes(TwkDevice dev)
+{
+  return (uint64_t) (sizeof(BvhNode) * dev->d_wideNodes.capacity() + sizeof(float) * dev->d_nodeCost.capacity() + sizeof(int) * dev->d_pairFlags.capacity() +
+                     sizeof(int4) * dev->d_updateSoup.capacity() + sizeof(int2) * dev->d_updateRanges.capacity() + sizeof(int) * dev->d_updateResult.capacity());
+}
+
+// Internal, no entry point: the update of a handle built in selective mode (include/tweeker_hip.h "Selective instance updates") after
+// the transforms of the instances `moved` (distinct) have been replaced. Everything it launches is what buildScene launches for the
+// same tree with the same arguments at the same bases, on arrays that hold what buildScene's held at that point — so the result is
+// a fresh build's, byte for byte. A failure leaves the handle unbuilt (twk_build recovers it).
+static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
+{
+  int rc;
+  TwkDevice_t::KeptBuild& kept = dev->kept;
+  const SceneLayout& layout = kept.layout;
+  dropAdaptive(dev);
+  dev->built = false; // until this update has succeeded
+  const auto start = std::chrono::steady_clock::now();
+  for (const InstanceHost& inst : dev->instances)
+  {
+    if (inst.material >= (int) dev->materials.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance material index beyond twk_init_materials");
+    if (inst.light >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance light index beyond twk_init_lights");
+  }
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+
+  const int numInstances = (int) dev->instances.size();
+  std::vector<int> instanceGeometry((size_t) numInstances), geometryTriangles(dev->geometries.size());
+  for (int i = 0; i < numInstances; ++i) instanceGeometry[i] = dev->instances[i].geometry;
+  for (size_t k = 0; k < dev->geometries.size(); ++k) geometryTriangles[k] = dev->geometries[k].numTriangles;
+  UpdatePlan plan;
+  updatePlan(layout, instanceGeometry.data(), geometryTriangles.data(), moved, numMoved, plan);
+  const size_t numNodes = layout.numNodes, numTris = layout.numTriangles;
+
+  // the records of the moved instances only (the new object-to-world matrix and its inverse); they live until the first synchronise
+  std::vector<DevInstance> records((size_t) numMoved);
+  for (int k = 0; k < numMoved; ++k)
+  {
+    instanceRecord(dev, layout, moved[k], records[k]);
+    HIP_TRY(hipMemcpyAsync(dev->d_instances + moved[k], &records[k], sizeof(DevInstance), hipMemcpyHostToDevice, dev->stream));
+  }
+
+  // the world-space tree of every moved flattened instance, at the bases it has; a fresh build starts from zeroed node arrays and
+  // pair flags, and what a tree leaves unused of its range must stay zero
+  struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder};
+  dev->builder.setNodeCost(dev->d_nodeCost);
+  int maxTriangles = 0;
+  for (int i : plan.trees) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
+  if (maxTriangles > 0 && (rc = dev->d_updateSoup.ensure((size_t) maxTriangles))) return rc;
+  for (int i : plan.trees)
+  {
+    const InstanceHost& inst = dev->instances[i];
+    const GeometryHost& g = dev->geometries[inst.geometry];
+    const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], nodes = treeNodes(g.numTriangles);
+    HIP_TRY(hipMemsetAsync(dev->d_nodes + nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
+    HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
+    if (kept.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + triangleBase, 0, sizeof(int) * (size_t) g.numTriangles, dev->stream));
+    float bounds[6];
+    dev->builder.soupDescriptors(dev->stream, dev->d_updateSoup, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
+                                        dev->d_nodes + nodeBase, dev->d_wideNodes + 2 * (size_t) nodeBase, nodeBase,
+                                        dev->d_triangles, dev->d_shadeTriangles, triangleBase, bounds, dev->d_updateSoup, dev->d_instances,
+                                        kept.pairs ? kept.primFirst[inst.geometry].data() : nullptr, (int) kept.primFirst[inst.geometry].size(), dev->d_pairFlags));
+    kept.instanceTerms[i].sahInner = dev->builder.lastSahInner(); kept.instanceTerms[i].sahLeaf = dev->builder.lastSahLeaf(); kept.instanceTerms[i].height = dev->builder.lastHeight();
+    kept.boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
+    kept.boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
+    // its payload in the top level (its root, or its slots as a direct leaf) names bases, which do not move
+  }
+  // a moved entered instance: its box in the top level, nothing else — no bottom-level tree is rebuilt
+  for (int k = 0; k < numMoved; ++k)
+    if (!layout.flattened[moved[k]])
+      enteredWorldBox(dev->geometries[dev->instances[moved[k]].geometry].rootBounds, dev->instances[moved[k]].transform, kept.boxLo[moved[k]], kept.boxHi[moved[k]]);
+
+  // the top level over the kept and the new boxes: its emission reads the binary nodes and the costs of the spliced roots
+  if (plan.topLevel)
+  {
+    HIP_TRY(dev->builder.buildInstances(dev->stream, kept.boxLo.data(), kept.boxHi.data(), kept.leafPayload.data(), numInstances, dev->d_nodes + layout.tlasBase,
+                                        dev->d_wideNodes + 2 * (size_t) layout.tlasBase, layout.tlasBase));
+    dev->tlasRoot = layout.tlasBase;
+    kept.topHeight = dev->builder.lastHeight();
+  }
+  else { dev->tlasRoot = layout.flatNodeBase[0]; kept.topHeight = 0; }
+
+  // the depth, from the kept heights, and buildScene's refusal
+  int maxEnteredHeight = 0, maxFlatHeight = 0;
+  for (size_t k = 0; k < dev->geometries.size(); ++k) if (layout.needsBlas[k]) maxEnteredHeight = std::max(maxEnteredHeight, kept.geometryTerms[k].height);
+  for (int i = 0; i < numInstances; ++i) if (layout.flattened[i]) maxFlatHeight = std::max(maxFlatHeight, kept.instanceTerms[i].height);
+  const int topHeight = kept.topHeight;
+  const int traversalDepth = topHeight + std::max(maxFlatHeight, (layout.numEntered > 0) ? 1 + maxEnteredHeight : 0);
+  int depthLimit = TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL - 2;
+  if (const char* e = getenv("TWK_MAX_TRAVERSAL_DEPTH")) depthLimit = std::min(depthLimit, atoi(e)); // test hook: a lower limit only
+  if (traversalDepth > depthLimit) return refuseDepth(dev, traversalDepth, topHeight, maxFlatHeight, maxEnteredHeight);
+
+  // the 8-wide root again, from zeroed root slots as in a fresh build: it opens entries of other trees' full-precision wide nodes
+  dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
+  HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * numNodes, 0, sizeof(BvhNode) * 4, dev->stream));
+  if (dev->wideRoot)
+  {
+    if ((rc = dev->d_updateResult.ensure(1))) return rc;
+    launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, dev->d_updateResult, dev->stream);
+    int has = 0;
+    HIP_TRY(hipMemcpyAsync(&has, dev->d_updateResult, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
+  }
+
+  // the ranged tail: the quantised copy and the pair references of the changed node ranges, in one launch. The records of pairs a
+  // rebuilt tree no longer has stay in d_trianglePairs (sized by slots, it does not move): nothing references them.
+  std::vector<int2> table(plan.ranges.size());
+  int position = 0;
+  for (size_t r = 0; r < plan.ranges.size(); ++r) { table[r] = make_int2(plan.ranges[r].first, position); position += plan.ranges[r].count; }
+  if ((rc = dev->d_updateRanges.ensure(table.size()))) return rc;
+  HIP_TRY(hipMemcpyAsync(dev->d_updateRanges, table.data(), sizeof(int2) * table.size(), hipMemcpyHostToDevice, dev->stream));
+  launchRangedTail(dev->d_wideNodes, dev->d_wideQ, dev->d_updateRanges, (int) table.size(), position, kept.pairRewrite ? dev->d_pairFlags.get() : nullptr, (int) numTris,
+                   dev->d_triangles, dev->d_trianglePairs, dev->stream);
+  if ((rc = dev->d_topNodes.ensure(4 * TWK_TOP_NODES)) || (rc = dev->d_topNodes7.ensure(4 * TWK_TOP_NODES7))) return rc;
+  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
+  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(dev->stream)); // `table` and `records` may go away
+
+  // the build info, from the kept terms in the order a build sums them
+  TwkBuildInfo info = dev->buildInfo; // counts, pair leaves, quality: no transform changes them
+  // A tree over one build primitive has no SAH terms of its own: a build adds those of the tree built before it again (none before
+  // the first: BvhBuilder::clearLastSah), and so does this sum.
+  info.sahInnerCost = 0.0; info.sahLeafCost = 0.0;
+  TwkDevice_t::TreeTerms last;
+  const auto add = [&](const TwkDevice_t::TreeTerms& own, size_t geometry)
+  {
+    const size_t primitives = kept.pairs ? kept.primFirst[geometry].size() : (size_t) dev->geometries[geometry].numTriangles;
+    if (primitives > 1) last = own;
+    info.sahInnerCost += last.sahInner; info.sahLeafCost += last.sahLeaf;
+  };
+  for (size_t k = 0; k < dev->geometries.size(); ++k) if (layout.needsBlas[k]) add(kept.geometryTerms[k], k);
+  for (int i = 0; i < numInstances; ++i) if (layout.flattened[i]) add(kept.instanceTerms[i], (size_t) instanceGeometry[i]);
+  info.maxTraversalDepth = (uint64_t) traversalDepth;
+  info.buildMilliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - start).count();
+  dev->buildInfo = info;
+  dev->twoLevel = (layout.numEntered > 0);
+  dev->built = true; ++dev->buildSerial; // everything keyed on the serial (tile entry points, refreshParams) is stale, as after a build
+  staleGeometry(dev);
+
+  TwkUpdateInfo& u = dev->updateInfo;
+  memset(&u, 0, sizeof(u));
+  u.selective = 1; u.instancesMoved = numMoved; u.treesRebuilt = (int) plan.trees.size(); u.topLevelRebuilt = plan.topLevel ? 1 : 0;
+  u.nodesRequantised = (uint64_t) plan.totalNodes; u.slotsRewritten = (uint64_t) plan.totalSlots; u.instanceRecordsUploaded = (uint64_t) numMoved;
+  u.keptBytes = keptBytes(dev); u.milliseconds = info.buildMilliseconds;
+  dev->updateInfoValid = true;
+  return TWK_SUCCESS;
+}
+
+// The body of twk_update_instance_transform (batch false: its texts) and of twk_update_instance_transforms (each refusal names its entry)
+static int updateTransforms(TwkDevice dev, const char* name, bool batch, int count, const int* ids, const float* transforms)
+{
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  // the batch's own arguments first, so that they are refused without the handle being looked at; the single call keeps its order
+  if (batch && count < 1) return refuse(TWK_ERROR_INVALID_VALUE, "count must be at least 1");
+  if (batch && (!ids || !transforms)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL array of ids or transforms");
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  if (!batch && !transforms) return refuse(TWK_ERROR_INVALID_VALUE, "NULL transform");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  for (int k = 0; k < count; ++k)
+  {
+    const std::string entry = batch ? "entry " + std::to_string(k) + ": " : "";
+    const int id = ids[k];
+    const float* transform = transforms + 12 * (size_t) k;
+    if (id < 0 || id >= (int) dev->instances.size()) return refuse(TWK_ERROR_INVALID_VALUE, entry + "bad instance id");
+    if (!instanceTransformUsable(transform)) return refuse(TWK_ERROR_INVALID_VALUE, entry + "the transform is not finite, or its 3 x 3 determinant is zero or not finite");
+    if (dev->instances[id].light >= 0)
+      return refuse(TWK_ERROR_INVALID_VALUE, entry + "the instance carries a light (idLight >= 0): its light definition holds the emitter's position and would disagree; moving emitters is not supported");
+    for (int j = 0; j < k; ++j) if (ids[j] == id) return refuse(TWK_ERROR_INVALID_VALUE, entry + "instance " + std::to_string(id) + " is listed twice (also entry " + std::to_string(j) + ")");
+  }
+  // nothing was changed up to here: a refused batch changes nothing
+  for (int k = 0; k < count; ++k) memcpy(dev->instances[ids[k]].transform, transforms + 12 * (size_t) k, sizeof(float) * 12);
+  dev->updateInfoValid = false; // an update that fails from here on leaves no record: twk_get_update_info describes a finished update
+  // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
+  if (dev->kept.valid) return updateSelective(dev, ids, count);
+  if ((rc = buildScene(dev, false))) return rc;
+  TwkUpdateInfo& u = dev->updateInfo;
+  memset(&u, 0, sizeof(u));
+  u.selective = 0; u.instancesMoved = count; u.treesRebuilt = dev->buildInfo.trees; u.topLevelRebuilt = (dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1) ? 0 : 1;
+  u.nodesRequantised = (uint64_t) dev->wideNodesTotal; u.slotsRewritten = (uint64_t) dev->totalTriangles; u.instanceRecordsUploaded = (uint64_t) dev->instances.size();
+  u.keptBytes = 0; u.milliseconds = dev->buildInfo.buildMilliseconds;
+  dev->updateInfoValid = true;
+  return TWK_SUCCESS;
+}
+
+extern "C" {
+
 int twk_update_instance_transform(TwkDevice dev, int idInstance, const float transform[12])
 try
 {
-  const char* name = "twk_update_instance_transform";
-  const auto refuse = [name](int code, const char* text) { return twkSetError(code, std::string(name) + ": " + text); };
-  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
-  if (!transform) return refuse(TWK_ERROR_INVALID_VALUE, "NULL transform");
-  int rc = activate(dev, name); if (rc) return rc;
-  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
-  if (idInstance < 0 || idInstance >= (int) dev->instances.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad instance id");
-  if (!instanceTransformUsable(transform)) return refuse(TWK_ERROR_INVALID_VALUE, "the transform is not finite, or its 3 x 3 determinant is zero or not finite");
-  if (dev->instances[idInstance].light >= 0)
-    return refuse(TWK_ERROR_INVALID_VALUE, "the instance carries a light (idLight >= 0): its light definition holds the emitter's position and would disagree; moving emitters is not supported");
-  memcpy(dev->instances[idInstance].transform, transform, sizeof(float) * 12);
-  return buildScene(dev); // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
+  return updateTransforms(dev, "twk_update_instance_transform", false, 1, &idInstance, transform);
 }
 TWK_CATCH("twk_update_instance_transform")
+
+int twk_update_instance_transforms(TwkDevice dev, int count, const int* idInstances, const float* transforms)
+try
+{
+  return updateTransforms(dev, "twk_update_instance_transforms", true, count, idInstances, transforms);
+}
+TWK_CATCH("twk_update_instance_transforms")
+
+int twk_set_update_mode(TwkDevice dev, int mode)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_update_mode: NULL device handle");
+  if (mode != TWK_UPDATE_FULL && mode != TWK_UPDATE_SELECTIVE) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_set_update_mode: unknown mode " + std::to_string(mode));
+  dev->updateMode = mode; // read by the next twk_build: the built scene keeps updating the way it was built
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_set_update_mode")
+
+int twk_get_update_info(TwkDevice dev, TwkUpdateInfo* info)
+try
+{
+  if (!dev || !info) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_update_info: NULL argument");
+  if (!dev->updateInfoValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_update_info: no update has been made on this handle");
+  *info = dev->updateInfo;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_update_info")
+
+int twk_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                         int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges)
+try
+{
+  const char* name = "twk_update_plan_host";
+  const auto refuse = [name](const std::string& text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  if (!instanceGeometry || !geometryTriangles || !plan || (numMoved > 0 && !moved)) return refuse("NULL argument");
+  if (numInstances < 1 || numGeometries < 1 || numMoved < 0 || flattenMaxTriangles < 0 || flattenMaxReferences < 0) return refuse("counts must be at least 1 and limits at least 0");
+  for (int k = 0; k < numGeometries; ++k) if (geometryTriangles[k] < 1) return refuse("geometry " + std::to_string(k) + " has no triangle");
+  for (int i = 0; i < numInstances; ++i) if (instanceGeometry[i] < 0 || instanceGeometry[i] >= numGeometries) return refuse("instance " + std::to_string(i) + ": bad geometry index");
+  for (int k = 0; k < numMoved; ++k)
+  {
+    if (moved[k] < 0 || moved[k] >= numInstances) return refuse("entry " + std::to_string(k) + ": bad instance id");
+    for (int j = 0; j < k; ++j) if (moved[j] == moved[k]) return refuse("entry " + std::to_string(k) + ": instance " + std::to_string(moved[k]) + " is listed twice");
+  }
+  SceneLayout layout;
+  sceneLayout(instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, std::max(1, std::min(4, maxLeaf)) /* BvhBuilder::setMaxLeaf */, true, layout);
+  UpdatePlan p;
+  updatePlan(layout, instanceGeometry, geometryTriangles, moved, numMoved, p);
+  memset(plan, 0, sizeof(*plan));
+  plan->instances = numInstances; plan->flattenedInstances = numInstances - layout.numEntered; plan->tlasBase = layout.tlasBase;
+  for (int i = 0; i < numInstances; ++i) plan->directLeafInstances += layout.directLeaf[i] ? 1 : 0;
+  for (int k = 0; k < numGeometries; ++k) plan->enteredGeometries += layout.needsBlas[k] ? 1 : 0;
+  plan->nodes = layout.numNodes; plan->triangleSlots = layout.numTriangles;
+  if (numMoved > 0)
+  {
+    plan->treesRebuilt = (int) p.trees.size(); plan->topLevelRebuilt = p.topLevel ? 1 : 0; plan->numRanges = (int) p.ranges.size();
+    plan->nodesRequantised = p.totalNodes; plan->slotsRewritten = p.totalSlots;
+    if (trees) for (size_t k = 0; k < p.trees.size(); ++k) trees[k] = p.trees[k];
+    if (ranges) for (size_t k = 0; k < p.ranges.size(); ++k) { ranges[2 * k] = p.ranges[k].first; ranges[2 * k + 1] = p.ranges[k].count; }
+  }
+  if (flattened) for (int i = 0; i < numInstances; ++i) flattened[i] = layout.flattened[i] ? 1 : 0;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_update_plan_host")
 
 int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12])
 try

@@ -270,6 +270,12 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && i[0] >= 0 && std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) { temporalInstance = i[0]; for (int k = 0; k < 3; ++k) temporalInstanceStep[k] = f[k]; }
       else if (ok) warnings.push_back("temporalInstanceStep needs an instance id >= 0 and a finite step, dropping the line");
     }
+    else if (key == "selectiveUpdate")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && (i[0] == 0 || i[0] == 1)) selectiveUpdate = i[0];
+      else if (ok) warnings.push_back("selectiveUpdate must be 0 or 1, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -375,6 +381,7 @@ std::string Application::systemDescription() const
   if (temporalRectifyRadius != TWK_TEMPORAL_RECTIFY_RADIUS) d << "temporalRectifyRadius " << temporalRectifyRadius << std::endl;
   if (temporalRectifyMinTaps != TWK_TEMPORAL_RECTIFY_MIN_TAPS) d << "temporalRectifyMinTaps " << temporalRectifyMinTaps << std::endl;
   if (temporalInstance >= 0) d << "temporalInstanceStep " << temporalInstance << " " << temporalInstanceStep[0] << " " << temporalInstanceStep[1] << " " << temporalInstanceStep[2] << std::endl;
+  if (selectiveUpdate != 0) d << "selectiveUpdate " << selectiveUpdate << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

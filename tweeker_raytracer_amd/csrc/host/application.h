@@ -140,6 +140,9 @@ public:
   // "temporalInstanceStep <idInstance> <dx> <dy> <dz>" (read by twk_app_get_temporal_motion): before every frame of that loop after
   // the first, the instance is translated by one more step (twk_update_instance_transform on every device). temporalInstance -1: no key.
   int   temporalInstance = -1;
+  // "selectiveUpdate 0|1" (read by twk_app_get_selective_update): a render loop sets twk_set_update_mode(TWK_UPDATE_SELECTIVE) on
+  // every device before the build, so that the updates of "temporalInstanceStep" rebuild only what the instance changes
+  int   selectiveUpdate = 0;
   float temporalInstanceStep[3] = {0.0f, 0.0f, 0.0f};
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;

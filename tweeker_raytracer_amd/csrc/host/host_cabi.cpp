@@ -248,6 +248,16 @@ try
 }
 TWK_CATCH("twk_app_get_temporal_motion")
 
+int twk_app_get_selective_update(TwkApp app, int* enabled)
+try
+{
+  if (!app) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_selective_update: NULL app");
+  if (!enabled) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_app_get_selective_update: NULL argument");
+  *enabled = (app->app.selectiveUpdate != 0) ? 1 : 0;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_app_get_selective_update")
+
 int twk_app_set_resolution(TwkApp app, int width, int height)
 try
 {

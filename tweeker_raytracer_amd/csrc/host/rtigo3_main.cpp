@@ -317,6 +317,11 @@ int main(int argc, char* argv[])
     if (!loadPicture(picture, w, h, rgba)) continue;
     for (int i = 0; i < count; ++i) TWK_OK(twk_init_texture(devices[(size_t) i], picture.slot, rgba.data(), w, h));
   }
+  // "selectiveUpdate 1": the mode is read by the build, so it is set before the scene is handed over
+  int selectiveUpdate = 0;
+  TWK_OK(twk_app_get_selective_update(app, &selectiveUpdate));
+  if (selectiveUpdate)
+    for (int i = 0; i < count; ++i) TWK_OK(twk_set_update_mode(devices[(size_t) i], TWK_UPDATE_SELECTIVE));
   for (int i = 0; i < count; ++i) TWK_OK(twk_app_init_device(app, devices[(size_t) i]));
 
   // Buffer strategy (Raytracer.cpp:125-176 picks the Device flavour): 1 = zero copy — one pinned host frame mapped into
@@ -402,6 +407,11 @@ int main(int argc, char* argv[])
           TWK_OK(twk_get_instance_transform(devices[(size_t) i], movingInstance, transform));
           for (int k = 0; k < 3; ++k) transform[4 * k + 3] += movingStep[k];
           TWK_OK(twk_update_instance_transform(devices[(size_t) i], movingInstance, transform));
+          // which path the update took and what it touched, per device: the only way to see from outside that "selectiveUpdate 1" took effect
+          TwkUpdateInfo update;
+          TWK_OK(twk_get_update_info(devices[(size_t) i], &update));
+          std::cerr << "INFO: frame " << frame << ", device " << i << ": instance " << movingInstance << " moved by a " << (update.selective ? "selective" : "full") << " update, "
+                    << update.treesRebuilt << " tree(s) rebuilt, " << update.nodesRequantised << " node(s) requantised" << std::endl;
         }
       for (int i = 0; i < count; ++i)
       {

@@ -24,6 +24,29 @@ def instance_motion(previous, current):
     return out
 
 
+def update_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, moved=(), maxLeaf=2):
+    """twk_update_plan_host (pure CPU): how a scene of instances instanceGeometry[i] over geometries of geometryTriangles[g]
+    triangles is laid out under flattenPolicy = (maxTriangles, maxReferences), and what a selective update of the instances `moved`
+    touches. Returns a dict: L.UpdatePlan's fields, `flattened` (bool per instance), `trees` (the moved flattened instances,
+    ascending) and `ranges` ([(first node, count), ...]: the rebuilt trees, the top level, the two root slots)."""
+    ig = np.ascontiguousarray(instanceGeometry, dtype=np.int32).reshape(-1)
+    gt = np.ascontiguousarray(geometryTriangles, dtype=np.int32).reshape(-1)
+    mv = np.ascontiguousarray(list(moved), dtype=np.int32).reshape(-1)
+    plan = L.UpdatePlan()
+    flattened = np.zeros(max(1, ig.size), np.uint8)
+    trees = np.zeros(max(1, mv.size), np.int32)
+    ranges = np.zeros(2 * (mv.size + 2), np.int32)
+    ip = C.POINTER(C.c_int)
+    L.check(L.lib.twk_update_plan_host(ig.ctypes.data_as(ip), int(ig.size), gt.ctypes.data_as(ip), int(gt.size), int(flattenPolicy[0]), int(flattenPolicy[1]), int(maxLeaf),
+                                       mv.ctypes.data_as(ip) if mv.size else None, int(mv.size), C.byref(plan), flattened.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                       trees.ctypes.data_as(ip), ranges.ctypes.data_as(ip)))
+    out = {name: getattr(plan, name) for name, _ in L.UpdatePlan._fields_}
+    out["flattened"] = [bool(f) for f in flattened[:ig.size]]
+    out["trees"] = [int(t) for t in trees[:plan.treesRebuilt]]
+    out["ranges"] = [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(plan.numRanges)]
+    return out
+
+
 def device_count():
     n = C.c_int(0)
     L.check(L.lib.twk_device_count(C.byref(n)))
@@ -304,6 +327,35 @@ class Device:
         stale afterwards. TwkError: before build(), a bad id, a transform that is not finite or singular, an instance with a light."""
         t = (C.c_float * 12)(*[float(x) for x in np.asarray(transform, dtype=np.float32).reshape(12)])
         L.check(L.lib.twk_update_instance_transform(self._h, int(idInstance), t))
+
+    # ---- selective instance updates (include/tweeker_hip.h "Selective instance updates", csrc/update_plan.h) ----
+    def setUpdateMode(self, mode):
+        """twk_set_update_mode: L.TWK_UPDATE_FULL (default: an update rebuilds everything) or L.TWK_UPDATE_SELECTIVE — the next
+        build() keeps its by-products (about 136 B per node) and the updates of that scene rebuild only what the moved instances
+        change. A scene built in full mode keeps updating fully until it is built again. TwkError: any other mode."""
+        L.check(L.lib.twk_set_update_mode(self._h, int(mode)))
+
+    def updateInstanceTransforms(self, ids, transforms):
+        """twk_update_instance_transforms: several moves (ids: ints; transforms: 12 floats each, row-major 3 x 4), one rebuild, in
+        either mode. Every refusal of updateInstanceTransform applies per entry and names it; also refused: no entry, an id listed
+        twice. A refused batch changes nothing."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1)
+        if t.size != 12 * ids.size:
+            raise ValueError("updateInstanceTransforms: 12 floats per id")
+        L.check(L.lib.twk_update_instance_transforms(self._h, int(ids.size), ids.ctypes.data_as(C.POINTER(C.c_int)), t.ctypes.data_as(C.POINTER(C.c_float))))
+
+    @staticmethod
+    def updatePlanHost(instanceGeometry, geometryTriangles, flattenPolicy, moved=(), maxLeaf=2):
+        """twk_update_plan_host, pure CPU: update_plan_host of this module."""
+        return update_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, moved, maxLeaf)
+
+    def updateInfo(self):
+        """twk_get_update_info: what the last update did, a dict of L.UpdateInfo's fields (selective, instancesMoved, treesRebuilt,
+        topLevelRebuilt, nodesRequantised, slotsRewritten, instanceRecordsUploaded, keptBytes, milliseconds). TwkError before one."""
+        u = L.UpdateInfo()
+        L.check(L.lib.twk_get_update_info(self._h, C.byref(u)))
+        return {name: getattr(u, name) for name, _ in L.UpdateInfo._fields_}
 
     def instanceTransform(self, idInstance):
         """twk_get_instance_transform: the instance's transform as it is now, float32 [12]."""

@@ -1191,6 +1191,18 @@ int twk_debug_snapshot_scene(TwkDevice dev, void* launchParams, size_t paramsByt
  * op 0 sin, 1 cos, 2 exp, 3 atan2(x[i], y[i]), 4 acos, 5 atan, 6 sqrt, 7 1/x, 8 log, 9 pow(x[i], y[i]). */
 int twk_debug_math(TwkDevice dev, int op, const float* x, const float* y, float* out, size_t n);
 
+/* The traversal kernel's short divisions (csrc/trace_device.h exactReciprocal, exactQuotients: v_rcp_f32 and fused corrections in
+ * place of the 11-instruction IEEE expansion) against the compiler's own `/`, both computed in one kernel.
+ * mode 0: the reciprocal of the `count` bit patterns first, first + 1, ... (count <= 2^32; x, d unused);
+ * mode 1: the quotients x[i] / d[i] and the reciprocal 1 / d[i] of `count` caller's pairs, |x[i]| <= |d[i]| as woopSetup has them;
+ * mode 2: the same over `count` pairs drawn on the device from the seed `first` (half with |d| in [0.5, 1), half over every binade;
+ *         x up to 70 binades below d, denormals and zeros included).
+ * mismatches: results that differ from `/` in any bit (two NaNs count as equal); fallbacks: operands outside the proven range,
+ * which the helpers hand to `/` themselves; offenders: the first eight mismatching operands, two words each (mode 0: the bit
+ * pattern, 0; otherwise the bits of x and of d), may be NULL. Serves the tests; no rendering path calls it. New call only, ABI stays 9. */
+int twk_debug_exact_division(TwkDevice dev, int mode, uint32_t first, uint64_t count, const float* x, const float* d,
+                             uint64_t* mismatches, uint64_t* fallbacks, uint32_t offenders[16]);
+
 /* ---- host scene layer (rtigo3 Application: description files, meshes, camera) -------------- */
 typedef struct TwkApp_t* TwkApp;
 

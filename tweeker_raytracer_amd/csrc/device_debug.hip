@@ -406,4 +406,34 @@ try
 }
 TWK_CATCH("twk_debug_math")
 
+int twk_debug_exact_division(TwkDevice dev, int mode, uint32_t first, uint64_t count, const float* x, const float* d,
+                             uint64_t* mismatches, uint64_t* fallbacks, uint32_t offenders[16])
+try
+{
+  int rc = activate(dev, "twk_debug_exact_division"); if (rc) return rc;
+  if (mode < 0 || mode > 2 || !mismatches || !fallbacks || (mode == 1 && count && (!x || !d)) || (mode == 0 && count > ((uint64_t) 1 << 32)))
+    return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_debug_exact_division: bad arguments");
+  *mismatches = 0; *fallbacks = 0;
+  if (offenders) memset(offenders, 0, 16 * sizeof(uint32_t));
+  if (count == 0) return TWK_SUCCESS;
+  DeviceArray<float> dx, dd;
+  DeviceArray<unsigned long long> tally;
+  if ((rc = tally.allocate(18, true, dev->stream))) return rc;
+  if (mode == 1)
+  {
+    if ((rc = dx.allocate(count))) return rc;
+    if ((rc = dd.allocate(count))) return rc;
+    HIP_TRY(hipMemcpyAsync(dx, x, count * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+    HIP_TRY(hipMemcpyAsync(dd, d, count * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+  }
+  launchExactDivisionTap(mode, first, count, dx, dd, tally, dev->stream);
+  unsigned long long host[18];
+  HIP_TRY(hipMemcpyAsync(host, tally, sizeof(host), hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  *mismatches = host[0]; *fallbacks = host[1];
+  if (offenders) for (int k = 0; k < 16; ++k) offenders[k] = (uint32_t) host[2 + k];
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_debug_exact_division")
+
 } // extern "C"

@@ -38,6 +38,7 @@ template<typename Samples> void launchAccumulate(const LaunchParams& p, bool hal
 void launchCompositor(const void* tiles, void* output, bool half, int width, int height, int launchWidth, int deviceCount,
                       int tileSizeX, int tileShiftX, int tileShiftY, hipStream_t stream);
 void launchMathTap(int op, const float* x, const float* y, float* out, size_t n, hipStream_t stream);
+void launchExactDivisionTap(int mode, unsigned int first, unsigned long long count, const float* x, const float* d, unsigned long long* tally /* 18 words, zeroed */, hipStream_t stream);
 void launchStreamCopy(const float4* src, float4* dst, size_t n, hipStream_t stream);
 void launchGatherProbeFill(float4* table, size_t count, unsigned int lines, hipStream_t stream);
 void launchGatherProbe(const float4* table, unsigned int lines, int steps, float* out, int gridBlocks, hipStream_t stream);

@@ -51,13 +51,91 @@ TWK_D bool slabTest(const TraceRay& r, float lox, float loy, float loz, float hi
 TWK_D bool slabTestGrid(float ax, float ay, float az, float bx, float by, float bz,
                         float qnx, float qny, float qnz, float qfx, float qfy, float qfz, float tmin, float tmax, float& tnear)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // The same maxima and minima, as the two instructions hipcc itself picks for them, written out: tmin and tmax reach this
+  // function from another basic block, hipcc cannot know that they are no signalling NaNs and quiets both with a v_max_f32 x, x
+  // in EVERY node step, in front of instructions that quiet their operands anyway.
+  float tn, tf;
+  asm("v_max_f32 %0, %1, %2\n\tv_max3_f32 %0, %3, %4, %0" : "=&v"(tn) : "v"(__builtin_fmaf(qnz, az, bz)), "v"(tmin), "v"(__builtin_fmaf(qnx, ax, bx)), "v"(__builtin_fmaf(qny, ay, by)));
+  asm("v_min_f32 %0, %1, %2\n\tv_min3_f32 %0, %3, %4, %0" : "=&v"(tf) : "v"(__builtin_fmaf(qfz, az, bz)), "v"(tmax), "v"(__builtin_fmaf(qfx, ax, bx)), "v"(__builtin_fmaf(qfy, ay, by)));
+#else
   const float tn = fmaxf(fmaxf(__builtin_fmaf(qnx, ax, bx), __builtin_fmaf(qny, ay, by)), fmaxf(__builtin_fmaf(qnz, az, bz), tmin));
   const float tf = fminf(fminf(__builtin_fmaf(qfx, ax, bx), __builtin_fmaf(qfy, ay, by)), fminf(__builtin_fmaf(qfz, az, bz), tmax));
+#endif
   tnear = tn;
   // the same widening as slabTest's tn * (1 - 2.5e-6) <= tf * (1 + 2.5e-6), as ONE product: tn >= tmin >= 0 here, so dividing by
   // the left factor keeps the direction, and 1.0000051 > (1 + 2.5e-6) / (1 - 2.5e-6) keeps it conservative (four multiplies
   // fewer per node step of the issue-bound traversal kernel)
   return tn <= tf * 1.0000051f;
+}
+
+// The divisions that are part of the RESULT (1 / det of the triangle test, the shear constants of woopSetup), correctly rounded
+// like the `/` they stand for, in fewer instructions. hipcc expands an IEEE division into 11 instructions (v_div_scale x 2,
+// v_rcp, v_fma x 4, v_mul, v_div_fmas, v_div_fixup), most of which only serve operands near the ends of the exponent range.
+// A correctly rounded result does not depend on the sequence that produced it, so a shorter one changes no bit of any image.
+//   reciprocal: v_rcp_f32 and ONE Newton step, r = rcp(x), e = fma(-x, r, 1), r' = fma(e, r, r). Markstein's theorem gives
+//     RN(1 / x) from a 1-ulp start except possibly for an all-ones significand; on gfx950 the sweep of all 2^32 bit patterns
+//     (tests/test_gpu_exact_division.py, twk_debug_exact_division) finds NO mismatch, all-ones included, wherever neither x nor
+//     1 / x is denormal: 2^-126 <= |x| <= 2^126. (v_rcp_f32 alone misses on 452 428 200 of those patterns; with 1 / x denormal
+//     the refined value misses on all but two, tools/probes/exact_rcp_probe.hip.) The residual itself tells the range: inside
+//     it |e| stays below 2^-21; outside, v_rcp_f32 — which flushes denormals on either side — returns 0 (|x| > 2^126,
+//     infinity), infinity (zero, denormals) or NaN, and e is 1, infinite or NaN. So ONE comparison, |e| <= 2^-20, sends
+//     everything else to the `/` it always took, and the same sweep counts what fails it: the 67 108 862 patterns outside
+//     the range, no other.
+//   quotient x / d with r = RN(1 / d): q = x r, e = fma(-d, q, x), q' = fma(e, r, q) (Markstein: q' = RN(x / d) when r is the
+//     correctly rounded reciprocal, q is within an ulp of the quotient and e is EXACT). Guarded range, for |x| <= |d|:
+//     2^-60 <= |x| and |d| <= 2^60. Then |d| >= 2^-60 too, r is a normal number in the reciprocal's proven range, |q| >= 2^-121
+//     is normal (so its error is an ulp, not an underflow), and the residual x - d q, a multiple of ulp(d) ulp(q) >= 2^-47 |x| / 2
+//     >= 2^-108, is representable, so the fma delivers it exactly. Outside — a zero or tiny component (an axis-parallel ray: the
+//     sequence would also lose the sign of a zero quotient), a non-finite or NaN one, an absurdly scaled direction — the three
+//     `/` stand as before. No guard for an all-ones significand of d: the reciprocal is proven exact there, and the quotient
+//     theorem asks nothing else of d (the test's constructed cases include it).
+// The fallbacks sit behind a branch no wave of a real scene takes (the empty asm keeps hipcc from turning the branch into both
+// sequences and a select). The host build of this header keeps `/`: the oracle and the host kernels are the reference.
+TWK_D bool exactQuotientsProven(float x, float y, float d) { const float ax = fabsf(x), ay = fabsf(y), ad = fabsf(d); return (ax >= 0x1p-60f) & (ay >= 0x1p-60f) & (ad <= 0x1p60f); }
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TWK_EXACT_RARE(a) asm volatile("" : "+v"(a));
+TWK_D float exactReciprocalShort(float x)
+{
+  const float r = __builtin_amdgcn_rcpf(x);
+  const float e = __builtin_fmaf(-x, r, 1.0f);
+  return __builtin_fmaf(e, r, r);
+}
+TWK_D float exactQuotientShort(float x, float d, float r) // r = RN(1 / d)
+{
+  const float q = x * r;
+  const float e = __builtin_fmaf(-d, q, x);
+  return __builtin_fmaf(e, r, q);
+}
+#else
+#define TWK_EXACT_RARE(a)
+TWK_D float exactReciprocalShort(float x) { return 1.0f / x; }
+TWK_D float exactQuotientShort(float x, float d, float) { return x / d; }
+#endif
+
+TWK_D float exactReciprocal(float x, bool& fallback) // == 1.0f / x; fallback: x was outside the proven range
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  float r = __builtin_amdgcn_rcpf(x);
+  const float e = __builtin_fmaf(-x, r, 1.0f);
+  r = __builtin_fmaf(e, r, r);
+  fallback = !(fabsf(e) <= 0x1p-20f);
+  if (__builtin_expect(fallback, 0)) { TWK_EXACT_RARE(x) r = 1.0f / x; }
+  return r;
+#else
+  fallback = false;
+  return 1.0f / x;
+#endif
+}
+TWK_D float exactReciprocal(float x) { bool fallback; return exactReciprocal(x, fallback); }
+
+// (x / d, y / d, 1 / d) for |x|, |y| <= |d|
+TWK_D void exactQuotients(float x, float y, float d, float& qx, float& qy, float& r)
+{
+  r  = exactReciprocalShort(d);
+  qx = exactQuotientShort(x, d, r);
+  qy = exactQuotientShort(y, d, r);
+  if (__builtin_expect(!exactQuotientsProven(x, y, d), 0)) { TWK_EXACT_RARE(d) qx = x / d; qy = y / d; r = 1.0f / d; }
 }
 
 // Woop-Benthin-Wald ray constants. The axis permutation (kx, ky, kz) is a cyclic shift of (x, y, z) chosen by the
@@ -98,9 +176,7 @@ TWK_D void woopSetup(const V3& d, WoopConstants& w)
   float dx, dy, dz;
   woopPermute(f, d, dx, dy, dz);
   w.perm = (f.zIsX ? 1u : 0u) | (f.zIsY ? 2u : 0u);
-  w.Sx = dx / dz;
-  w.Sy = dy / dz;
-  w.Sz = 1.0f / dz;
+  exactQuotients(dx, dy, dz, w.Sx, w.Sy, w.Sz); // dx / dz, dy / dz, 1 / dz: dz is the dominant component
 }
 
 // Straight-line: every lane runs the whole test and the verdict is one flag (a wave leaves early only when all of its
@@ -138,7 +214,7 @@ TWK_D bool woopIntersect(const WoopConstants& w, const V3& o, const V3& p0, cons
   const float det = U + V + W;
   const float Az = w.Sz * Akz, Bz = w.Sz * Bkz, Cz = w.Sz * Ckz;
   const float T = U * Az + V * Bz + W * Cz;
-  const float rcpDet = 1.0f / det;
+  const float rcpDet = exactReciprocal(det);
   const float tt = T * rcpDet;
   t     = tt;
   beta  = V * rcpDet;
@@ -185,7 +261,7 @@ TWK_D bool woopFinish(float U, float V, float W, float Az, float Bz, float Cz, f
   const bool mixedSigns = ((U < 0.0f) | (V < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (V > 0.0f) | (W > 0.0f));
   const float det = U + V + W;
   const float T = U * Az + V * Bz + W * Cz;
-  const float rcpDet = 1.0f / det;
+  const float rcpDet = exactReciprocal(det);
   const float tt = T * rcpDet;
   t     = tt;
   beta  = V * rcpDet;

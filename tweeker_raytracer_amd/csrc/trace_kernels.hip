@@ -276,6 +276,61 @@ void launchTileEntries(const LaunchParams& p, const float4* topTable, int tilesX
   hipLaunchKernelGGL(tileEntryKernel, dim3((tiles + 63) / 64), dim3(64), 0, stream, p, topTable, tilesX, tilesY, out);
 }
 
+// twk_debug_exact_division: the short divisions of trace_device.h against the compiler's own `/`, compared in the same kernel.
+// tally: [0] mismatches (any differing bit; two NaNs are equal), [1] operands that took the guarded `/` path, [2 + 2k], [3 + 2k] the
+// k-th of the first eight offenders (mode 0: the bit pattern and 0; quotients: the bits of x and of d).
+// mode 0: exactReciprocal over the bit patterns first + i. mode 1: exactQuotients(x[i], x[i], d[i]), all three results.
+// mode 2: the same over pairs drawn here from seed `first`, |x| <= |d|: every other pair with |d| in [0.5, 1) like the dominant
+// component of a unit direction, the others with d anywhere in the normal range; x up to 70 binades below d, into the denormals.
+__device__ unsigned int exactDivisionHash(unsigned int h) { h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16; return h; }
+__device__ bool sameFloat(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
+
+__global__ void __launch_bounds__(256)
+exactDivisionKernel(int mode, unsigned int first, unsigned long long count, const float* __restrict__ xs, const float* __restrict__ ds, unsigned long long* __restrict__ tally)
+{
+  const unsigned long long stride = (unsigned long long) gridDim.x * blockDim.x;
+  for (unsigned long long i = (unsigned long long) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride)
+  {
+    float x, d = 0.0f;
+    bool same, fallback;
+    if (mode == 0)
+    {
+      x = __uint_as_float(first + (unsigned int) i);
+      same = sameFloat(exactReciprocal(x, fallback), 1.0f / x);
+    }
+    else
+    {
+      if (mode == 1) { x = xs[i]; d = ds[i]; }
+      else
+      {
+        const unsigned int a = exactDivisionHash((unsigned int) i ^ exactDivisionHash(first + (unsigned int) (i >> 32))), b = exactDivisionHash(a + 0x9e3779b9u), c = exactDivisionHash(b + 0x9e3779b9u);
+        const int ed = (i & 1ull) ? 126 : 1 + (int) (c % 254u);
+        const int ex = max(0, ed - (int) ((c >> 16) % 71u));
+        d = __uint_as_float((a & 0x807fffffu) | ((unsigned int) ed << 23));
+        x = __uint_as_float((b & 0x807fffffu) | ((unsigned int) ex << 23));
+        if (fabsf(x) > fabsf(d)) { const float s = x; x = d; d = s; }
+      }
+      float qx, qy, r;
+      exactQuotients(x, x, d, qx, qy, r);
+      const bool sameX = sameFloat(qx, x / d), sameY = sameFloat(qy, x / d), sameR = sameFloat(r, 1.0f / d);
+      same = sameX & sameY & sameR;
+      fallback = !exactQuotientsProven(x, x, d);
+    }
+    if (fallback) atomicAdd(&tally[1], 1ull);
+    if (!same)
+    {
+      const unsigned long long k = atomicAdd(&tally[0], 1ull);
+      if (k < 8ull) { tally[2 + 2 * k] = __float_as_uint(x); tally[3 + 2 * k] = __float_as_uint(d); }
+    }
+  }
+}
+
+void launchExactDivisionTap(int mode, unsigned int first, unsigned long long count, const float* x, const float* d, unsigned long long* tally, hipStream_t stream)
+{
+  const unsigned long long blocks = (count + 255ull) / 256ull;
+  hipLaunchKernelGGL(exactDivisionKernel, dim3((unsigned int) (blocks < 16384ull ? blocks : 16384ull)), dim3(256), 0, stream, mode, first, count, x, d, tally);
+}
+
 void launchTraceQuery(const LaunchParams& p, const float* rays, unsigned int numRays, int anyHit, float* tBetaGamma, int* ids, int gridBlocks, hipStream_t stream)
 {
   hipLaunchKernelGGL(traceQueryKernel, dim3(gridBlocks), dim3(TWK_TRACE_BLOCK), 0, stream, p, rays, numRays, anyHit, tBetaGamma, ids);

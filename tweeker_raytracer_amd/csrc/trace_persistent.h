@@ -393,6 +393,12 @@ traceKernel(LaunchParams p, int depth)
       // per node). A lane whose stack would overflow abandons this traversal and re-traces its ray with the
       // spilling traverse() (cold path, not taken on the LBVHs of the shipped scenes).
       // (a lane without a ray holds node = TWK_BVH_SENTINEL: one comparison decides who steps)
+      // What keeps a corrupted tree from hanging the GPU: the steps of THIS round, counted once for the wave in a scalar register
+      // (a count per lane was a vector add and a vector compare in every step). A well-formed tree never gets near the bound — a
+      // round ends as soon as half of its lanes are at a leaf — and lanes caught in a cycle either stay while others leave for
+      // their leaves, until the pool is dry and they are the round's only lanes, or are most of the round: either way that round
+      // no longer ends by itself, reaches the bound, and ends every ray still in it.
+      unsigned int roundSteps = 0;
       while ((unsigned int) node < (unsigned int) TWK_BVH_SENTINEL)
       {
         {
@@ -414,8 +420,8 @@ traceKernel(LaunchParams p, int depth)
             const float4* w = p.wideQ + 4 * (size_t) node;
             n0 = w[0]; n1 = w[1]; n2 = w[2]; n3 = w[3];
           }
-          ++guard;
-          if (COUNT) ++nodeCount;
+          ++roundSteps;
+          if (COUNT) { ++guard; ++nodeCount; } // guard: the ray's own steps, for TwkLaunchStats' longest ray
           TWK_WAVE_STEP(nodeWaveSteps)
           int r0 = __float_as_int(n3.x), r1 = __float_as_int(n3.y), r2 = __float_as_int(n3.z), r3 = __float_as_int(n3.w);
           // Pin the references here: left alone, hipcc fetches them with separate loads AFTER the box tests — more
@@ -451,7 +457,7 @@ traceKernel(LaunchParams p, int depth)
           TWK_CE(t0, r0, t1, r1) TWK_CE(t2, r2, t3, r3) TWK_CE(t0, r0, t2, r2) TWK_CE(t1, r1, t3, r3) TWK_CE(t1, r1, t2, r2)
   #undef TWK_CE
           const int hits = (int) h0 + (int) h1 + (int) h2 + (int) h3;
-          bool stop = (guard > (1u << 22));
+          bool stop = (roundSteps > (1u << 22));
           bool overflow = false;
           if (hits > 0)
           {
@@ -556,9 +562,17 @@ traceKernel(LaunchParams p, int depth)
         }                                                                                                                      \
       }
       // A pair leaf: four lane loads instead of six, the two shared vertices transformed once, the shared diagonal's edge function
-      // computed once, and both triangles in one pass with all of the leaf's lanes. Merged in slot order, the second only while
-      // the ray is still alive: ties and any-hit termination are those of two passes of the loop below.
-      // (The leaf step marks it with triLast == triFirst - 2. A lane without a leaf has 0 and -1; a lane whose any-hit ray ends in
+      // computed once, and both triangles in one pass with all of the leaf's lanes. ONE merge for the two: the better of T0 and T1
+      // is chosen first and merged into `res` as two merges in slot order would have. Both share their instance and T0 has the
+      // smaller primitive, so under the comparator above T0 precedes T1 exactly when t0 <= t1.
+      //   closest hit: the comparator is a strict order on (t, instance, primitive) — against a `res` without a hit, on t alone —
+      //     and two merges leave the least of {res, T0, T1}, which is the least of {res, least of {T0, T1}}. A candidate that ties
+      //     with `res` in t meets the same instance / primitive clause as before.
+      //   any hit: the ray ends at the FIRST accepted triangle, so T0 must win whenever it would have been accepted, whatever t1 is.
+      //     A live any-hit ray has no hit yet (its first ends it), so `res.instance < 0` and accepted means t < res.t: T0 is taken
+      //     when t0 < res.t. When T0 hits without being accepted, t0 >= res.t, and a T1 that is accepted has t1 < res.t <= t0 and
+      //     is chosen by the closest-hit rule; the slot written is that of the triangle that ended the ray, as before.
+      // (The leaf step marks a pair with triLast == triFirst - 2. A lane without a leaf has 0 and -1; a lane whose any-hit ray ends in
       // the slot loop has -1 too, whatever its first slot, which is why this block comes BEFORE the loop.)
       if (PAIRS && triLast == triFirst - 2)
       {
@@ -569,14 +583,16 @@ traceKernel(LaunchParams p, int depth)
         const int prim = __float_as_int(w0.w), pairInstance = __float_as_int(w2.w); // T1's primitive is the next one
         WoopPairShared shared;
         woopPairShared(woop, ray.o, v3(w0), v3(w2), shared);
-        float t, beta, gamma;
+        float t, beta, gamma, t1, beta1, gamma1;
         const bool hit0 = woopPairFirst(woop, ray.o, shared, v3(w1), tmin, t, beta, gamma);
-        TWK_MERGE_HIT(hit0, t, beta, gamma, pairInstance, prim, triFirst)
         // (Fetching the fourth vertex only now, its address tied to T0's result by an empty asm, takes four registers fewer — 66
         // against 70 of the seven-block build's 72 — and a second round trip: the frame rate was the same within its spread,
         // profiles/r07_triangle_pairs.md.)
-        const bool hit1 = woopPairSecond(woop, ray.o, shared, v3(w3), tmin, t, beta, gamma) & ((state & ST_HAS_RAY) != 0u);
-        TWK_MERGE_HIT(hit1, t, beta, gamma, pairInstance, prim + 1, triFirst + 1)
+        const bool hit1 = woopPairSecond(woop, ray.o, shared, v3(w3), tmin, t1, beta1, gamma1);
+        const bool second = hit1 & !(hit0 & ((t <= t1) | (((state & ST_ANY_HIT) != 0u) & (t < res.t))));
+        t = second ? t1 : t; beta = second ? beta1 : beta; gamma = second ? gamma1 : gamma;
+        const int which = second ? 1 : 0;
+        TWK_MERGE_HIT(hit0 | hit1, t, beta, gamma, pairInstance, prim + which, triFirst + which)
       }
       // (Postponed leaves, slots stored by component, pair fetch, handing a leaf's second triangle to an idle lane: all built,
       // measured and not kept — DESIGN.md 4.1.)

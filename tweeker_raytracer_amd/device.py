@@ -911,3 +911,23 @@ class Device:
                                      yy.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)),
                                      C.c_size_t(x.size)))
         return out
+
+    def debugExactDivision(self, first=0, count=0, x=None, d=None, seed=None):
+        """The traversal kernel's short divisions against `/` on the device (twk_debug_exact_division): the reciprocal of the bit
+        patterns first .. first + count - 1; or, with x and d, the quotients x / d and 1 / d of those pairs (|x| <= |d|); or, with
+        seed, of `count` pairs drawn on the device. Returns (mismatches, operands that took the `/` fallback, first offenders as
+        [(bits, bits), ...])."""
+        fp = C.POINTER(C.c_float)
+        mism, fall, off = C.c_uint64(0), C.c_uint64(0), (C.c_uint32 * 16)()
+        if x is not None:
+            xx = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+            dd = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
+            assert xx.size == dd.size
+            args = (1, 0, C.c_uint64(xx.size), xx.ctypes.data_as(fp), dd.ctypes.data_as(fp))
+        elif seed is not None:
+            args = (2, C.c_uint32(int(seed)), C.c_uint64(int(count)), None, None)
+        else:
+            args = (0, C.c_uint32(int(first)), C.c_uint64(int(count)), None, None)
+        L.check(L.lib.twk_debug_exact_division(self._h, *args, C.byref(mism), C.byref(fall), off))
+        n = min(8, mism.value)
+        return mism.value, fall.value, [(off[2 * k], off[2 * k + 1]) for k in range(n)]

@@ -279,6 +279,8 @@ struct TwkDevice_t
   // the next build. kept.valid: the built scene was built in selective mode and its by-products are still here — d_wideNodes (above),
   // d_nodeCost (with costedCuts) and d_pairFlags (with pairs) on the device, and on the host the layout, per tree its box, payload,
   // height and SAH terms, and the build primitives of every geometry. A full-mode build holds none of it past its end (KeptScope).
+  // KeptBuild is also the working state of a build: buildScene fills a local one through the stage functions updateSelective amends
+  // this one with, and moves it here, valid, when a selective-mode build has succeeded.
   // d_updateSoup / d_updateRanges / d_updateResult: scratch of the updates, grown on demand.
   struct TreeTerms { double sahInner = 0.0, sahLeaf = 0.0; int height = 0; };
   struct KeptBuild

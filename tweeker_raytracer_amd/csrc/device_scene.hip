@@ -160,13 +160,143 @@ static void enteredWorldBox(const float rootBounds[6], const float m[12], float4
   boxHi = make_float4(hi[0], hi[1], hi[2], 0.0f);
 }
 
-// The depth refusal of a build: the text of twk_build, for the selective update too
-static int refuseDepth(TwkDevice dev, int traversalDepth, int topHeight, int maxFlatHeight, int maxEnteredHeight)
+// The stages of a scene's build. buildScene runs each over the whole scene, updateSelective over what its plan names, both on one
+// SceneState: buildScene's own, which a selective-mode build moves into the handle, and from then on the handle's. So an updated
+// handle equals a fresh build byte for byte. Their refusals name twk_build, whose they are, whoever runs the stage.
+using SceneState = TwkDevice_t::KeptBuild;
+
+// The builder knows the node-cost array during a build or an update only
+struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } };
+
+// Every instance's material and light exist; the largest indices go into the handle, which reads them of a built scene only
+static int checkInstanceTables(TwkDevice dev)
 {
-  dev->built = false;
-  return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: the acceleration structure is " + std::to_string(traversalDepth) + " levels deep (top " + std::to_string(topHeight) +
+  dev->maxInstanceMaterial = -1; dev->maxInstanceLight = -1;
+  for (const InstanceHost& inst : dev->instances)
+  {
+    if (inst.material >= (int) dev->materials.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance material index beyond twk_init_materials");
+    if (inst.light >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance light index beyond twk_init_lights");
+    dev->maxInstanceMaterial = std::max(dev->maxInstanceMaterial, inst.material);
+    dev->maxInstanceLight = std::max(dev->maxInstanceLight, inst.light);
+  }
+  return TWK_SUCCESS;
+}
+
+// What update_plan.h lays a scene out from and plans an update with
+static void layoutInputs(TwkDevice dev, std::vector<int>& instanceGeometry, std::vector<int>& geometryTriangles)
+{
+  instanceGeometry.resize(dev->instances.size()); geometryTriangles.resize(dev->geometries.size());
+  for (size_t i = 0; i < dev->instances.size(); ++i) instanceGeometry[i] = dev->instances[i].geometry;
+  for (size_t k = 0; k < dev->geometries.size(); ++k) geometryTriangles[k] = dev->geometries[k].numTriangles;
+}
+
+static TwkDevice_t::TreeTerms lastTerms(const BvhBuilder& b) { return {b.lastSahInner(), b.lastSahLeaf(), b.lastHeight()}; }
+
+// The world-space tree of flattened instance i at the bases the layout gives it, over `soup` (scratch for its triangles); its terms and
+// world box go into the state. Reads d_instances[i]. Zeroes nothing: its node ranges and pair flags are zero before the call.
+static int buildFlattenedTree(TwkDevice dev, SceneState& state, int i, int4* soup)
+{
+  const InstanceHost& inst = dev->instances[i];
+  const GeometryHost& g = dev->geometries[inst.geometry];
+  const int nodeBase = state.layout.flatNodeBase[i], triangleBase = state.layout.flatTriangleBase[i];
+  float bounds[6];
+  dev->builder.soupDescriptors(dev->stream, soup, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
+                                      dev->d_nodes + nodeBase, dev->d_wideNodes + 2 * (size_t) nodeBase, nodeBase,
+                                      dev->d_triangles, dev->d_shadeTriangles, triangleBase, bounds, soup, dev->d_instances,
+                                      state.pairs ? state.primFirst[inst.geometry].data() : nullptr, (int) state.primFirst[inst.geometry].size(), dev->d_pairFlags));
+  state.instanceTerms[i] = lastTerms(dev->builder);
+  state.boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
+  state.boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
+  return TWK_SUCCESS;
+}
+
+// The top level over the state's boxes and payloads: its emission reads the binary nodes and the costs of the spliced roots
+static int buildTopLevel(TwkDevice dev, SceneState& state)
+{
+  const SceneLayout& layout = state.layout;
+  if (layout.single) { dev->tlasRoot = layout.flatNodeBase[0]; state.topHeight = 0; return TWK_SUCCESS; } // the one world-space tree IS the scene
+  HIP_TRY(dev->builder.buildInstances(dev->stream, state.boxLo.data(), state.boxHi.data(), state.leafPayload.data(), (int) dev->instances.size(), dev->d_nodes + layout.tlasBase,
+                                      dev->d_wideNodes + 2 * (size_t) layout.tlasBase, layout.tlasBase));
+  dev->tlasRoot = layout.tlasBase; state.topHeight = dev->builder.lastHeight();
+  return TWK_SUCCESS;
+}
+
+// Deepest stack a single-ray traversal can need (trace_device.h traverse(): at most one push per inner node on the path,
+// plus the sentinel of an instance entry): the top level, then either a spliced world-space tree or an entered
+// geometry's tree. The persistent kernel hands rays that outgrow its LDS stack to that traversal, whose stack holds
+// TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL entries; a scene beyond that would lose subtrees silently, so it is refused.
+static int checkDepth(TwkDevice dev, const SceneState& state, int* traversalDepth)
+{
+  const SceneLayout& layout = state.layout;
+  int maxEnteredHeight = 0, maxFlatHeight = 0; // binary-tree heights: what a traversal stack may have to hold
+  for (size_t k = 0; k < dev->geometries.size(); ++k) if (layout.needsBlas[k]) maxEnteredHeight = std::max(maxEnteredHeight, state.geometryTerms[k].height);
+  for (size_t i = 0; i < dev->instances.size(); ++i) if (layout.flattened[i]) maxFlatHeight = std::max(maxFlatHeight, state.instanceTerms[i].height);
+  *traversalDepth = state.topHeight + std::max(maxFlatHeight, (layout.numEntered > 0) ? 1 + maxEnteredHeight : 0);
+  int depthLimit = TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL - 2;
+  if (const char* e = getenv("TWK_MAX_TRAVERSAL_DEPTH")) depthLimit = std::min(depthLimit, atoi(e)); // test hook: a lower limit only
+  if (*traversalDepth <= depthLimit) return TWK_SUCCESS;
+  return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_build: the acceleration structure is " + std::to_string(*traversalDepth) + " levels deep (top " + std::to_string(state.topHeight) +
                      ", flattened trees " + std::to_string(maxFlatHeight) + ", entered geometries " + std::to_string(maxEnteredHeight) + "); the traversal stacks hold " +
                      std::to_string(TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL) + " entries" + (dev->builder.quality() == TWK_BUILD_SAH ? " (try twk_set_build_quality(TWK_BUILD_LBVH))" : ""));
+}
+
+// The root as two wide nodes where that pays (bvh_build.hip wideRootKernel), in the two slots behind the scene's last node, which must
+// be zero: it opens entries of other trees' full-precision wide nodes. scratch: one word for the kernel's answer.
+static int openWideRoot(TwkDevice dev, size_t numNodes, DeviceArray<int>& scratch)
+{
+  int rc;
+  dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
+  if (!dev->wideRoot) return TWK_SUCCESS;
+  if ((rc = scratch.ensure(1))) return rc;
+  launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, scratch, dev->stream);
+  int has = 0;
+  HIP_TRY(hipMemcpyAsync(&has, scratch, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
+  return TWK_SUCCESS;
+}
+
+// The top-of-tree caches of the persistent kernel, from the quantised wide nodes as they stand, and the wait that ends the device work
+static int fillTopCaches(TwkDevice dev)
+{
+  int rc;
+  if ((rc = dev->d_topNodes.ensure(4 * TWK_TOP_NODES)) || (rc = dev->d_topNodes7.ensure(4 * TWK_TOP_NODES7))) return rc;
+  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
+  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  return TWK_SUCCESS;
+}
+
+// The SAH terms of the scene: those of its trees in build order — the entered geometries ascending, then the flattened instances
+// ascending. A tree over one build primitive has no terms of its own: the builder leaves those of the tree built before it standing
+// (none before the first: BvhBuilder::clearLastSah), so the sum takes the terms of the tree before it in this order again.
+static void sahTotals(TwkDevice dev, const SceneState& state, TwkBuildInfo& info)
+{
+  info.sahInnerCost = 0.0; info.sahLeafCost = 0.0;
+  TwkDevice_t::TreeTerms last;
+  const auto tree = [&](const TwkDevice_t::TreeTerms& own, size_t geometry)
+  {
+    const size_t primitives = state.pairs ? state.primFirst[geometry].size() : (size_t) dev->geometries[geometry].numTriangles;
+    if (primitives > 1) last = own;
+    info.sahInnerCost += last.sahInner; info.sahLeafCost += last.sahLeaf;
+  };
+  for (size_t k = 0; k < dev->geometries.size(); ++k) if (state.layout.needsBlas[k]) tree(state.geometryTerms[k], k);
+  for (size_t i = 0; i < dev->instances.size(); ++i) if (state.layout.flattened[i]) tree(state.instanceTerms[i], (size_t) dev->instances[i].geometry);
+}
+
+// The end of a build and of an update: the build info is the handle's, the scene is built
+static void finishBuild(TwkDevice dev, const SceneState& state, TwkBuildInfo info, int traversalDepth, std::chrono::steady_clock::time_point start)
+{
+  sahTotals(dev, state, info);
+  info.maxTraversalDepth = (uint64_t) traversalDepth;
+  info.buildMilliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - start).count();
+  dev->buildInfo = info;
+  dev->twoLevel = (state.layout.numEntered > 0);
+  dev->built = true; ++dev->buildSerial; // everything keyed on the serial (tile entry points, refreshParams) is stale
+  staleGeometry(dev); // the geometry AOV describes the scene that was
 }
 
 // Internal, no entry point: the build of the acceleration structure from the handle's geometries and instances as they are, on an
@@ -184,14 +314,7 @@ static int buildScene(TwkDevice dev, bool keep)
   TwkBuildInfo info;
   memset(&info, 0, sizeof(info));
   info.quality = dev->builder.quality();
-  int maxMaterial = -1, maxLight = -1;
-  for (const InstanceHost& inst : dev->instances)
-  {
-    if (inst.material >= (int) dev->materials.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance material index beyond twk_init_materials");
-    if (inst.light >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance light index beyond twk_init_lights");
-    if (inst.material > maxMaterial) maxMaterial = inst.material;
-    if (inst.light > maxLight) maxLight = inst.light;
-  }
+  if ((rc = checkInstanceTables(dev))) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
 
   // Which instances are flattened (include/tweeker_hip.h twk_set_flatten_policy): those of tiny geometries and those
@@ -202,15 +325,12 @@ static int buildScene(TwkDevice dev, bool keep)
   // The decision and the ranges it gives every tree are update_plan.h's (sceneLayout), which the selective update plans with too.
   const int numInstances = (int) dev->instances.size();
   if (const char* e = getenv("TWK_MAX_LEAF")) dev->builder.setMaxLeaf(atoi(e)); // tuning knob, default 2 triangles per leaf
-  std::vector<int> instanceGeometry((size_t) numInstances), geometryTriangles(dev->geometries.size());
-  for (int i = 0; i < numInstances; ++i) instanceGeometry[i] = dev->instances[i].geometry;
-  for (size_t k = 0; k < dev->geometries.size(); ++k) geometryTriangles[k] = dev->geometries[k].numTriangles;
-  SceneLayout layout;
+  std::vector<int> instanceGeometry, geometryTriangles;
+  layoutInputs(dev, instanceGeometry, geometryTriangles);
+  SceneState state; // what this build produces; a selective-mode build keeps it in the handle
   sceneLayout(instanceGeometry.data(), numInstances, geometryTriangles.data(), (int) dev->geometries.size(), dev->flattenMaxTriangles, dev->flattenMaxReferences,
-              dev->builder.maxLeaf(), dev->directSmallLeaves, layout);
-  const std::vector<char>& flattened = layout.flattened; const std::vector<char>& needsBlas = layout.needsBlas;
-  const std::vector<int>& flatTriangleBase = layout.flatTriangleBase; const std::vector<int>& flatNodeBase = layout.flatNodeBase;
-  const int numEntered = layout.numEntered, maxFlatTriangles = layout.maxFlatTriangles, tlasBase = layout.tlasBase;
+              dev->builder.maxLeaf(), dev->directSmallLeaves, state.layout);
+  const SceneLayout& layout = state.layout;
   const size_t numTris = layout.numTriangles, numNodes = layout.numNodes;
 
   // shared attribute / index arrays and the node / triangle budgets: one bottom level per geometry that is still
@@ -246,147 +366,88 @@ static int buildScene(TwkDevice dev, bool keep)
 
   // Triangle pairs (device_types.h): the two halves of a quad are one primitive of every tree's build. pairFlags: per slot, whether
   // a pair begins there — what the references of pair leaves are found by once the trees stand.
-  const bool pairs = dev->trianglePairs && dev->builder.maxLeaf() >= 2;
-  std::vector<std::vector<int>> primFirst(dev->geometries.size());
+  state.pairs = dev->trianglePairs && dev->builder.maxLeaf() >= 2;
+  state.primFirst.resize(dev->geometries.size());
   std::vector<size_t> geometryPairs(dev->geometries.size(), 0);
-  if (pairs)
+  if (state.pairs)
     for (size_t k = 0; k < dev->geometries.size(); ++k)
-      geometryPairs[k] = trianglePairs(dev->geometries[k].indices.data(), dev->geometries[k].numTriangles, primFirst[k]);
-  DeviceArray<int>& pairFlags = dev->d_pairFlags;
+      geometryPairs[k] = trianglePairs(dev->geometries[k].indices.data(), dev->geometries[k].numTriangles, state.primFirst[k]);
   dev->d_trianglePairs.release();
-  if (pairs)
+  if (state.pairs)
   {
-    if ((rc = pairFlags.allocate(numTris))) return rc;
-    HIP_TRY(hipMemsetAsync(pairFlags, 0, sizeof(int) * numTris, dev->stream));
+    if ((rc = dev->d_pairFlags.allocate(numTris))) return rc;
+    HIP_TRY(hipMemsetAsync(dev->d_pairFlags, 0, sizeof(int) * numTris, dev->stream));
   }
-  DeviceArray<float>& nodeCost = dev->d_nodeCost; // expected wide-node visits below each node: what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
-  if (dev->costedCuts && (rc = nodeCost.allocate(numNodes))) return rc;
-  struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder}; // the builder knows the array during a build only
-  dev->builder.setNodeCost(nodeCost);
+  // d_nodeCost: expected wide-node visits below each node, what the wide nodes' cuts are chosen by (bvh_build.hip refitKernel)
+  if (dev->costedCuts && (rc = dev->d_nodeCost.allocate(numNodes))) return rc;
+  NodeCostScope nodeCostScope{dev->builder};
+  dev->builder.setNodeCost(dev->d_nodeCost);
   dev->builder.clearLastSah();
-  int maxEnteredHeight = 0, maxFlatHeight = 0, topHeight = 0; // binary-tree heights: what a traversal stack may have to hold
-  std::vector<TwkDevice_t::TreeTerms> geometryTerms(dev->geometries.size()), instanceTerms((size_t) numInstances); // what a selective-mode build keeps of every tree
+  state.geometryTerms.resize(dev->geometries.size()); state.instanceTerms.resize((size_t) numInstances);
   // bottom level: one LBVH per entered geometry, shared by all of its instances (Device.cpp:1339 caches the GAS per Triangles id)
   for (size_t k = 0; k < dev->geometries.size(); ++k)
   {
     GeometryHost& g = dev->geometries[k];
-    if (!needsBlas[k]) continue;
+    if (!layout.needsBlas[k]) continue;
     HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes + 12 * (size_t) g.attributeBase, dev->d_indices + g.indexBase, g.numTriangles,
                                         dev->d_nodes + g.nodeBase, dev->d_wideNodes + 2 * (size_t) g.nodeBase, g.nodeBase, dev->d_triangles, dev->d_shadeTriangles, g.triangleBase, g.rootBounds,
-                                        nullptr, nullptr, pairs ? primFirst[k].data() : nullptr, (int) primFirst[k].size(), pairFlags));
-    info.pairLeaves += geometryPairs[k];
-    info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
-    maxEnteredHeight = std::max(maxEnteredHeight, dev->builder.lastHeight());
-    geometryTerms[k].sahInner = dev->builder.lastSahInner(); geometryTerms[k].sahLeaf = dev->builder.lastSahLeaf(); geometryTerms[k].height = dev->builder.lastHeight();
+                                        nullptr, nullptr, state.pairs ? state.primFirst[k].data() : nullptr, (int) state.primFirst[k].size(), dev->d_pairFlags));
+    state.geometryTerms[k] = lastTerms(dev->builder);
+    info.pairLeaves += geometryPairs[k]; info.trees += 1;
   }
 
-  // instance records (shading reads them for every hit, flattened or not)
+  // instance records (shading reads them for every hit, flattened or not); every flattened tree's build reads its own
   std::vector<DevInstance> records(numInstances);
   for (int i = 0; i < numInstances; ++i) instanceRecord(dev, layout, i, records[i]);
   HIP_TRY(hipMemcpyAsync(dev->d_instances, records.data(), sizeof(DevInstance) * numInstances, hipMemcpyHostToDevice, dev->stream));
 
-  // world-space trees of the flattened instances + the world boxes of all instances
-  std::vector<float4> boxLo(numInstances), boxHi(numInstances);
-  std::vector<int> leafPayload(numInstances);
-  DeviceArray<int4> soup;
-  if (maxFlatTriangles > 0 && (rc = soup.allocate((size_t) maxFlatTriangles))) return rc;
+  // world-space trees of the flattened instances + the world boxes and top-level payloads of all instances
+  state.boxLo.resize((size_t) numInstances); state.boxHi.resize((size_t) numInstances); state.leafPayload.resize((size_t) numInstances);
+  DeviceArray<int4> soup; DeviceArray<int> rootResult; // this build's own scratch, where an update uses the handle's
+  if (layout.maxFlatTriangles > 0 && (rc = soup.allocate((size_t) layout.maxFlatTriangles))) return rc;
   for (int i = 0; i < numInstances; ++i)
   {
     const InstanceHost& inst = dev->instances[i];
     const GeometryHost& g = dev->geometries[inst.geometry];
-    if (flattened[i])
+    if (!layout.flattened[i])
     {
-      float bounds[6];
-      dev->builder.soupDescriptors(dev->stream, soup, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
-                                          dev->d_nodes + flatNodeBase[i], dev->d_wideNodes + 2 * (size_t) flatNodeBase[i], flatNodeBase[i],
-                                          dev->d_triangles, dev->d_shadeTriangles, flatTriangleBase[i], bounds, soup, dev->d_instances,
-                                          pairs ? primFirst[inst.geometry].data() : nullptr, (int) primFirst[inst.geometry].size(), pairFlags));
-      info.pairLeaves += geometryPairs[inst.geometry];
-      info.sahInnerCost += dev->builder.lastSahInner(); info.sahLeafCost += dev->builder.lastSahLeaf(); info.trees += 1;
-      maxFlatHeight = std::max(maxFlatHeight, dev->builder.lastHeight());
-      instanceTerms[i].sahInner = dev->builder.lastSahInner(); instanceTerms[i].sahLeaf = dev->builder.lastSahLeaf(); instanceTerms[i].height = dev->builder.lastHeight();
-      boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
-      boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
-      leafPayload[i] = ~flatNodeBase[i]; // child reference ~payload = the instance's root node: an inner reference
-      // A flattened instance of no more triangles than a leaf holds (a wall, the area light: two triangles) IS a leaf of the
-      // top level: its slots are referenced directly instead of through a one-node tree of two single-triangle leaves —
-      // one node visit and one leaf step less for every ray that crosses its box (C2: six of the eight instances).
-      if (layout.directLeaf[i])
-      {
-        leafPayload[i] = flatTriangleBase[i] | ((g.numTriangles - 1) << 28) | TWK_LEAF_WORLD;
-        info.directLeafInstances += 1;
-      }
+      enteredWorldBox(g.rootBounds, inst.transform, state.boxLo[i], state.boxHi[i]);
+      state.leafPayload[i] = i;
       continue;
     }
-    enteredWorldBox(g.rootBounds, inst.transform, boxLo[i], boxHi[i]);
-    leafPayload[i] = i;
+    if ((rc = buildFlattenedTree(dev, state, i, soup))) return rc;
+    info.pairLeaves += geometryPairs[inst.geometry]; info.trees += 1;
+    state.leafPayload[i] = ~layout.flatNodeBase[i]; // child reference ~payload = the instance's root node: an inner reference
+    // A flattened instance of no more triangles than a leaf holds (a wall, the area light: two triangles) IS a leaf of the
+    // top level: its slots are referenced directly instead of through a one-node tree of two single-triangle leaves —
+    // one node visit and one leaf step less for every ray that crosses its box (C2: six of the eight instances).
+    if (layout.directLeaf[i])
+    {
+      state.leafPayload[i] = layout.flatTriangleBase[i] | ((g.numTriangles - 1) << 28) | TWK_LEAF_WORLD;
+      info.directLeafInstances += 1;
+    }
   }
-  if (layout.single) dev->tlasRoot = flatNodeBase[0]; // the one world-space tree IS the scene
-  else
-  {
-    HIP_TRY(dev->builder.buildInstances(dev->stream, boxLo.data(), boxHi.data(), leafPayload.data(), numInstances, dev->d_nodes + tlasBase, dev->d_wideNodes + 2 * (size_t) tlasBase, tlasBase));
-    dev->tlasRoot = tlasBase;
-    topHeight = dev->builder.lastHeight();
-  }
-  // Deepest stack a single-ray traversal can need (trace_device.h traverse(): at most one push per inner node on the path,
-  // plus the sentinel of an instance entry): the top level, then either a spliced world-space tree or an entered
-  // geometry's tree. The persistent kernel hands rays that outgrow its LDS stack to that traversal, whose stack holds
-  // TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL entries; a scene beyond that would lose subtrees silently, so it is refused.
-  const int traversalDepth = topHeight + std::max(maxFlatHeight, (numEntered > 0) ? 1 + maxEnteredHeight : 0);
-  int depthLimit = TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL - 2;
-  if (const char* e = getenv("TWK_MAX_TRAVERSAL_DEPTH")) depthLimit = std::min(depthLimit, atoi(e)); // test hook: a lower limit only
-  if (traversalDepth > depthLimit) return refuseDepth(dev, traversalDepth, topHeight, maxFlatHeight, maxEnteredHeight);
-  // the persistent trace kernel reads the quantised copy of the wide nodes; the full-precision ones were scratch
-  // the root as two wide nodes where that pays (bvh_build.hip wideRootKernel)
-  dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
-  if (dev->wideRoot)
-  {
-    DeviceArray<int> result;
-    if ((rc = result.allocate(1))) return rc;
-    launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, result, dev->stream);
-    int has = 0;
-    HIP_TRY(hipMemcpyAsync(&has, result, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
-  }
+  int traversalDepth = 0;
+  if ((rc = buildTopLevel(dev, state)) || (rc = checkDepth(dev, state, &traversalDepth)) || (rc = openWideRoot(dev, numNodes, rootResult))) return rc;
+  // the whole-array tail. The persistent trace kernel reads the quantised copy of the wide nodes; the full-precision ones were scratch
   launchQuantizeWide(dev->d_wideNodes, dev->d_wideQ, (int) dev->wideNodesTotal, dev->stream);
   // pair leaves get their records and their references in the structures the persistent kernel reads: a flattened scene only
   // (device_types.h "triangle pairs": a two-level scene's references have no free bit)
-  if (pairs && numEntered == 0 && info.pairLeaves > 0)
+  if (state.pairs && layout.numEntered == 0 && info.pairLeaves > 0)
   {
     if ((rc = dev->d_trianglePairs.allocate(4 * (numTris / 2 + 1)))) return rc;
-    launchPairLeaves(dev->d_wideQ, (int) dev->wideNodesTotal, pairFlags, (int) numTris, dev->d_triangles, dev->d_trianglePairs, dev->stream);
+    launchPairLeaves(dev->d_wideQ, (int) dev->wideNodesTotal, dev->d_pairFlags, (int) numTris, dev->d_triangles, dev->d_trianglePairs, dev->stream);
   }
-  if ((rc = dev->d_topNodes.ensure(4 * TWK_TOP_NODES)) || (rc = dev->d_topNodes7.ensure(4 * TWK_TOP_NODES7))) return rc;
-  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
-  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  if (keep)
-  {
-    // selective mode: the by-products stay (include/tweeker_hip.h "Selective instance updates")
-    TwkDevice_t::KeptBuild& kept = dev->kept;
-    kept.pairs = pairs; kept.pairRewrite = (dev->d_trianglePairs.capacity() != 0);
-    kept.layout = std::move(layout);
-    kept.geometryTerms = std::move(geometryTerms); kept.instanceTerms = std::move(instanceTerms);
-    kept.boxLo = std::move(boxLo); kept.boxHi = std::move(boxHi); kept.leafPayload = std::move(leafPayload); kept.topHeight = topHeight;
-    kept.primFirst = std::move(primFirst);
-    kept.valid = true; keptScope.keep = true;
-  }
-  else dev->d_wideNodes.release();
+  state.pairRewrite = (dev->d_trianglePairs.capacity() != 0);
+  if ((rc = fillTopCaches(dev))) return rc;
+  if (!keep) dev->d_wideNodes.release();
 
-  info.maxTraversalDepth = (uint64_t) traversalDepth;
   info.pairTriangles = 2 * info.pairLeaves;
-  info.triangleSlots = numTris; info.nodes = numNodes; info.instances = (uint64_t) numInstances; info.flattenedInstances = (uint64_t) (numInstances - numEntered);
-  info.buildMilliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - buildStart).count();
-  dev->buildInfo = info;
-  dev->twoLevel = (numEntered > 0);
-  dev->maxInstanceMaterial = maxMaterial; dev->maxInstanceLight = maxLight;
+  info.triangleSlots = numTris; info.nodes = numNodes; info.instances = (uint64_t) numInstances; info.flattenedInstances = (uint64_t) (numInstances - layout.numEntered);
   dev->totalNodes = numNodes; dev->totalTriangles = numTris;
-  dev->built = true; ++dev->buildSerial;
-  staleGeometry(dev); // the geometry AOV describes the scene that was
+  finishBuild(dev, state, info, traversalDepth, buildStart);
+  // selective mode: the by-products stay (include/tweeker_hip.h "Selective instance updates"), and the state with them
+  if (keep) { state.valid = true; dev->kept = std::move(state); keptScope.keep = true; }
   return TWK_SUCCESS;
 }
 
@@ -409,29 +470,34 @@ static uint64_t keptBytes(TwkDevice dev)
                      sizeof(int4) * dev->d_updateSoup.capacity() + sizeof(int2) * dev->d_updateRanges.capacity() + sizeof(int) * dev->d_updateResult.capacity());
 }
 
+// What an update did (twk_get_update_info). keptBytes: a full update is a full-mode build, which keeps nothing past its end
+static void recordUpdate(TwkDevice dev, bool selective, int moved, int trees, bool topLevel, size_t nodes, size_t slots, size_t records)
+{
+  TwkUpdateInfo& u = dev->updateInfo;
+  memset(&u, 0, sizeof(u));
+  u.selective = selective ? 1 : 0; u.instancesMoved = moved; u.treesRebuilt = trees; u.topLevelRebuilt = topLevel ? 1 : 0;
+  u.nodesRequantised = (uint64_t) nodes; u.slotsRewritten = (uint64_t) slots; u.instanceRecordsUploaded = (uint64_t) records;
+  u.keptBytes = keptBytes(dev); u.milliseconds = dev->buildInfo.buildMilliseconds;
+  dev->updateInfoValid = true;
+}
+
 // Internal, no entry point: the update of a handle built in selective mode (include/tweeker_hip.h "Selective instance updates") after
-// the transforms of the instances `moved` (distinct) have been replaced. Everything it launches is what buildScene launches for the
-// same tree with the same arguments at the same bases, on arrays that hold what buildScene's held at that point — so the result is
-// a fresh build's, byte for byte. A failure leaves the handle unbuilt (twk_build recovers it).
+// the transforms of the instances `moved` (distinct) have been replaced. It runs buildScene's stages (above) for what the plan names,
+// on arrays that hold what buildScene's held at that point — so the result is a fresh build's, byte for byte. A failure leaves the
+// handle unbuilt (twk_build recovers it).
 static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
 {
   int rc;
-  TwkDevice_t::KeptBuild& kept = dev->kept;
-  const SceneLayout& layout = kept.layout;
+  SceneState& state = dev->kept;
+  const SceneLayout& layout = state.layout;
   dropAdaptive(dev);
   dev->built = false; // until this update has succeeded
   const auto start = std::chrono::steady_clock::now();
-  for (const InstanceHost& inst : dev->instances)
-  {
-    if (inst.material >= (int) dev->materials.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance material index beyond twk_init_materials");
-    if (inst.light >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: instance light index beyond twk_init_lights");
-  }
+  if ((rc = checkInstanceTables(dev))) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
 
-  const int numInstances = (int) dev->instances.size();
-  std::vector<int> instanceGeometry((size_t) numInstances), geometryTriangles(dev->geometries.size());
-  for (int i = 0; i < numInstances; ++i) instanceGeometry[i] = dev->instances[i].geometry;
-  for (size_t k = 0; k < dev->geometries.size(); ++k) geometryTriangles[k] = dev->geometries[k].numTriangles;
+  std::vector<int> instanceGeometry, geometryTriangles;
+  layoutInputs(dev, instanceGeometry, geometryTriangles);
   UpdatePlan plan;
   updatePlan(layout, instanceGeometry.data(), geometryTriangles.data(), moved, numMoved, plan);
   const size_t numNodes = layout.numNodes, numTris = layout.numTriangles;
@@ -446,68 +512,31 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
 
   // the world-space tree of every moved flattened instance, at the bases it has; a fresh build starts from zeroed node arrays and
   // pair flags, and what a tree leaves unused of its range must stay zero
-  struct NodeCostScope { BvhBuilder& b; ~NodeCostScope() { b.setNodeCost(nullptr); } } nodeCostScope{dev->builder};
+  NodeCostScope nodeCostScope{dev->builder};
   dev->builder.setNodeCost(dev->d_nodeCost);
   int maxTriangles = 0;
   for (int i : plan.trees) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
   if (maxTriangles > 0 && (rc = dev->d_updateSoup.ensure((size_t) maxTriangles))) return rc;
   for (int i : plan.trees)
   {
-    const InstanceHost& inst = dev->instances[i];
-    const GeometryHost& g = dev->geometries[inst.geometry];
-    const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], nodes = treeNodes(g.numTriangles);
+    const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], triangles = geometryTriangles[instanceGeometry[i]], nodes = treeNodes(triangles);
     HIP_TRY(hipMemsetAsync(dev->d_nodes + nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
     HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
-    if (kept.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + triangleBase, 0, sizeof(int) * (size_t) g.numTriangles, dev->stream));
-    float bounds[6];
-    dev->builder.soupDescriptors(dev->stream, dev->d_updateSoup, 0, g.numTriangles, i, (int) g.attributeBase, (int) g.indexBase);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes, dev->d_indices, g.numTriangles,
-                                        dev->d_nodes + nodeBase, dev->d_wideNodes + 2 * (size_t) nodeBase, nodeBase,
-                                        dev->d_triangles, dev->d_shadeTriangles, triangleBase, bounds, dev->d_updateSoup, dev->d_instances,
-                                        kept.pairs ? kept.primFirst[inst.geometry].data() : nullptr, (int) kept.primFirst[inst.geometry].size(), dev->d_pairFlags));
-    kept.instanceTerms[i].sahInner = dev->builder.lastSahInner(); kept.instanceTerms[i].sahLeaf = dev->builder.lastSahLeaf(); kept.instanceTerms[i].height = dev->builder.lastHeight();
-    kept.boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
-    kept.boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
+    if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + triangleBase, 0, sizeof(int) * (size_t) triangles, dev->stream));
+    if ((rc = buildFlattenedTree(dev, state, i, dev->d_updateSoup))) return rc;
     // its payload in the top level (its root, or its slots as a direct leaf) names bases, which do not move
   }
   // a moved entered instance: its box in the top level, nothing else — no bottom-level tree is rebuilt
   for (int k = 0; k < numMoved; ++k)
     if (!layout.flattened[moved[k]])
-      enteredWorldBox(dev->geometries[dev->instances[moved[k]].geometry].rootBounds, dev->instances[moved[k]].transform, kept.boxLo[moved[k]], kept.boxHi[moved[k]]);
+      enteredWorldBox(dev->geometries[dev->instances[moved[k]].geometry].rootBounds, dev->instances[moved[k]].transform, state.boxLo[moved[k]], state.boxHi[moved[k]]);
 
-  // the top level over the kept and the new boxes: its emission reads the binary nodes and the costs of the spliced roots
-  if (plan.topLevel)
-  {
-    HIP_TRY(dev->builder.buildInstances(dev->stream, kept.boxLo.data(), kept.boxHi.data(), kept.leafPayload.data(), numInstances, dev->d_nodes + layout.tlasBase,
-                                        dev->d_wideNodes + 2 * (size_t) layout.tlasBase, layout.tlasBase));
-    dev->tlasRoot = layout.tlasBase;
-    kept.topHeight = dev->builder.lastHeight();
-  }
-  else { dev->tlasRoot = layout.flatNodeBase[0]; kept.topHeight = 0; }
-
-  // the depth, from the kept heights, and buildScene's refusal
-  int maxEnteredHeight = 0, maxFlatHeight = 0;
-  for (size_t k = 0; k < dev->geometries.size(); ++k) if (layout.needsBlas[k]) maxEnteredHeight = std::max(maxEnteredHeight, kept.geometryTerms[k].height);
-  for (int i = 0; i < numInstances; ++i) if (layout.flattened[i]) maxFlatHeight = std::max(maxFlatHeight, kept.instanceTerms[i].height);
-  const int topHeight = kept.topHeight;
-  const int traversalDepth = topHeight + std::max(maxFlatHeight, (layout.numEntered > 0) ? 1 + maxEnteredHeight : 0);
-  int depthLimit = TWK_TRACE_STACK_LDS + TWK_TRACE_STACK_SPILL - 2;
-  if (const char* e = getenv("TWK_MAX_TRAVERSAL_DEPTH")) depthLimit = std::min(depthLimit, atoi(e)); // test hook: a lower limit only
-  if (traversalDepth > depthLimit) return refuseDepth(dev, traversalDepth, topHeight, maxFlatHeight, maxEnteredHeight);
-
-  // the 8-wide root again, from zeroed root slots as in a fresh build: it opens entries of other trees' full-precision wide nodes
-  dev->wideRoot1 = dev->tlasRoot; dev->wideRoot2 = TWK_BVH_SENTINEL; dev->wideNodesTotal = numNodes;
+  // the top level over the kept and the new boxes; the depth, from the kept and the new heights
+  int traversalDepth = 0;
+  if ((rc = buildTopLevel(dev, state)) || (rc = checkDepth(dev, state, &traversalDepth))) return rc;
+  // the 8-wide root again, from zeroed root slots as in a fresh build
   HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * numNodes, 0, sizeof(BvhNode) * 4, dev->stream));
-  if (dev->wideRoot)
-  {
-    if ((rc = dev->d_updateResult.ensure(1))) return rc;
-    launchWideRoot(dev->d_wideNodes, dev->tlasRoot, (int) numNodes, dev->d_updateResult, dev->stream);
-    int has = 0;
-    HIP_TRY(hipMemcpyAsync(&has, dev->d_updateResult, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    if (has) { dev->wideRoot1 = (int) numNodes; dev->wideRoot2 = (int) numNodes + 1; dev->wideNodesTotal = numNodes + 2; }
-  }
+  if ((rc = openWideRoot(dev, numNodes, dev->d_updateResult))) return rc;
 
   // the ranged tail: the quantised copy and the pair references of the changed node ranges, in one launch. The records of pairs a
   // rebuilt tree no longer has stay in d_trianglePairs (sized by slots, it does not move): nothing references them.
@@ -516,41 +545,13 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
   for (size_t r = 0; r < plan.ranges.size(); ++r) { table[r] = make_int2(plan.ranges[r].first, position); position += plan.ranges[r].count; }
   if ((rc = dev->d_updateRanges.ensure(table.size()))) return rc;
   HIP_TRY(hipMemcpyAsync(dev->d_updateRanges, table.data(), sizeof(int2) * table.size(), hipMemcpyHostToDevice, dev->stream));
-  launchRangedTail(dev->d_wideNodes, dev->d_wideQ, dev->d_updateRanges, (int) table.size(), position, kept.pairRewrite ? dev->d_pairFlags.get() : nullptr, (int) numTris,
+  launchRangedTail(dev->d_wideNodes, dev->d_wideQ, dev->d_updateRanges, (int) table.size(), position, state.pairRewrite ? dev->d_pairFlags.get() : nullptr, (int) numTris,
                    dev->d_triangles, dev->d_trianglePairs, dev->stream);
-  if ((rc = dev->d_topNodes.ensure(4 * TWK_TOP_NODES)) || (rc = dev->d_topNodes7.ensure(4 * TWK_TOP_NODES7))) return rc;
-  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes, TWK_TOP_NODES, dev->stream);
-  launchTopCache(dev->d_wideQ, dev->wideRoot1, dev->wideRoot2, dev->d_topNodes7, TWK_TOP_NODES7, dev->stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(dev->stream)); // `table` and `records` may go away
+  if ((rc = fillTopCaches(dev))) return rc; // waits for the stream: `table` and `records` may go away
 
-  // the build info, from the kept terms in the order a build sums them
-  TwkBuildInfo info = dev->buildInfo; // counts, pair leaves, quality: no transform changes them
-  // A tree over one build primitive has no SAH terms of its own: a build adds those of the tree built before it again (none before
-  // the first: BvhBuilder::clearLastSah), and so does this sum.
-  info.sahInnerCost = 0.0; info.sahLeafCost = 0.0;
-  TwkDevice_t::TreeTerms last;
-  const auto add = [&](const TwkDevice_t::TreeTerms& own, size_t geometry)
-  {
-    const size_t primitives = kept.pairs ? kept.primFirst[geometry].size() : (size_t) dev->geometries[geometry].numTriangles;
-    if (primitives > 1) last = own;
-    info.sahInnerCost += last.sahInner; info.sahLeafCost += last.sahLeaf;
-  };
-  for (size_t k = 0; k < dev->geometries.size(); ++k) if (layout.needsBlas[k]) add(kept.geometryTerms[k], k);
-  for (int i = 0; i < numInstances; ++i) if (layout.flattened[i]) add(kept.instanceTerms[i], (size_t) instanceGeometry[i]);
-  info.maxTraversalDepth = (uint64_t) traversalDepth;
-  info.buildMilliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - start).count();
-  dev->buildInfo = info;
-  dev->twoLevel = (layout.numEntered > 0);
-  dev->built = true; ++dev->buildSerial; // everything keyed on the serial (tile entry points, refreshParams) is stale, as after a build
-  staleGeometry(dev);
-
-  TwkUpdateInfo& u = dev->updateInfo;
-  memset(&u, 0, sizeof(u));
-  u.selective = 1; u.instancesMoved = numMoved; u.treesRebuilt = (int) plan.trees.size(); u.topLevelRebuilt = plan.topLevel ? 1 : 0;
-  u.nodesRequantised = (uint64_t) plan.totalNodes; u.slotsRewritten = (uint64_t) plan.totalSlots; u.instanceRecordsUploaded = (uint64_t) numMoved;
-  u.keptBytes = keptBytes(dev); u.milliseconds = info.buildMilliseconds;
-  dev->updateInfoValid = true;
+  // the build info: counts, pair leaves, quality — no transform changes them — and what the changed trees change
+  finishBuild(dev, state, dev->buildInfo, traversalDepth, start);
+  recordUpdate(dev, true, numMoved, (int) plan.trees.size(), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
   return TWK_SUCCESS;
 }
 
@@ -582,12 +583,7 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
   if (dev->kept.valid) return updateSelective(dev, ids, count);
   if ((rc = buildScene(dev, false))) return rc;
-  TwkUpdateInfo& u = dev->updateInfo;
-  memset(&u, 0, sizeof(u));
-  u.selective = 0; u.instancesMoved = count; u.treesRebuilt = dev->buildInfo.trees; u.topLevelRebuilt = (dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1) ? 0 : 1;
-  u.nodesRequantised = (uint64_t) dev->wideNodesTotal; u.slotsRewritten = (uint64_t) dev->totalTriangles; u.instanceRecordsUploaded = (uint64_t) dev->instances.size();
-  u.keptBytes = 0; u.milliseconds = dev->buildInfo.buildMilliseconds;
-  dev->updateInfoValid = true;
+  recordUpdate(dev, false, count, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, dev->instances.size());
   return TWK_SUCCESS;
 }
 

@@ -10,6 +10,8 @@
 // wave-level ray dealing and while-while loop (every ray is walked by traverse() instead — same hits by construction of
 // the tie rule, tests/test_gpu_host_kernels.py holds the images equal bit for bit) and the block-aggregated queue
 // appends (a plain sequential append: another queue order, the same paths).
+// The records between the stages are read and written by the product's own path_queue.h, in its full form (no packed queue,
+// no slim streams: the pool below carves every stream).
 // Used by tests (-m gpu: it needs a device-built scene) and by bench.py's cpu_baseline leg, never by the product.
 #include "host_kernels_shim.h"
 #include "../tweeker_raytracer_amd/csrc/shade_device.h"
@@ -61,32 +63,19 @@ int hostk_render(const void* launchParams, size_t paramsBytes, unsigned int firs
     const unsigned int numClosest = p.counters[depth * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_CLOSEST];
     const unsigned int numShadow = (depth > 0) ? p.counters[(depth - 1) * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_SHADOW] : 0u;
     const int q = depth & 1;
-    for (unsigned int slot = 0; slot < numClosest; ++slot)
+    for (unsigned int slot = 0; slot < numClosest + numShadow; ++slot)
     {
-      const float4 o = p.rayOrg[q][slot], d = p.rayDir[q][slot];
+      // one segment per queue: a slot is its own record
+      const bool isShadow = !(slot < numClosest);
+      const unsigned int record = isShadow ? slot - numClosest : slot;
+      const QueuedRay ray = isShadow ? loadShadowRay(p, record) : loadClosestRay(p, q, record, false);
       TraceResult res;
       nodeCount = triCount = instCount = 0;
-      traverse<true>(p, v3(o), v3(d), o.w, d.w, false, ldsStack.data(), spill.data(), res, nodeCount, triCount, instCount);
-      nodes += nodeCount; tris += triCount; insts += instCount; ++radianceRays;
-      p.hitRecord[slot] = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.triangleSlot));
-      p.hitInstance[slot] = res.instance;
-    }
-    for (unsigned int s = 0; s < numShadow; ++s)
-    {
-      const float4 o = p.shadowOrg[s], d = p.shadowDir[s];
-      TraceResult res;
-      nodeCount = triCount = instCount = 0;
-      traverse<true>(p, v3(o), v3(d), o.w, d.w, true, ldsStack.data(), spill.data(), res, nodeCount, triCount, instCount);
-      nodes += nodeCount; tris += triCount; insts += instCount; ++shadowRays;
-      if (res.instance < 0)
-      {
-        // visible: add the pending next-event contribution (trace_kernels.hip, closesthit.cu:288-299)
-        const unsigned int pixel = p.shadowPixel[s];
-        const float4 c = p.shadowPending[s];
-        float4 r = p.pathRadiance[pixel];
-        r.x += c.x; r.y += c.y; r.z += c.z;
-        p.pathRadiance[pixel] = r;
-      }
+      traverse<true>(p, v3(ray.o), v3(ray.d), ray.o.w, ray.d.w, isShadow, ldsStack.data(), spill.data(), res, nodeCount, triCount, instCount);
+      nodes += nodeCount; tris += triCount; insts += instCount;
+      if (isShadow) ++shadowRays; else ++radianceRays;
+      // the hit record, or a visible shadow ray's pending contribution: what both trace kernels leave behind
+      storeRayResult<false>(p, depth, /* primary */ false, /* packed */ false, /* slim */ false, slot, isShadow, res, 0u, [&]() { return record; });
     }
   };
 
@@ -100,32 +89,18 @@ int hostk_render(const void* launchParams, size_t paramsBytes, unsigned int firs
     unsigned int& shadowCount = p.counters[depth * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_SHADOW];
     for (unsigned int slot = 0; slot < numRays; ++slot)
     {
-      const float4 ro = p.rayOrg[q][slot], rd = p.rayDir[q][slot];
-      if (!(rd.w >= 0.0f)) continue; // an inactive launch index (tile column beyond the image)
-      const unsigned int pixel = p.rayPixel[q][slot];
+      float4 ro, rd, hit;
+      unsigned int pixel;
+      int instanceIndex;
       ShadeOutput out;
       out.alive = false; out.wantShadow = false;
-      out.throughputPdf = p.rayThroughput[q][slot];
-      out.seedFlags = p.raySeedFlags[q][slot];
-      shadePath<true, true>(p, depth, pixel, ro, rd, p.hitRecord[slot], p.hitInstance[slot], out);
+      loadQueuedPath(p, q, slot, false, ro, rd, out.throughputPdf, out.seedFlags, pixel);
+      if (!(rd.w >= 0.0f)) continue; // an inactive launch index (tile column beyond the image)
+      loadHit(p, slot, false, hit, instanceIndex);
+      shadePath<true, true>(p, depth, pixel, ro, rd, hit, instanceIndex, out);
       ++shaded;
-      if (out.wantShadow)
-      {
-        const unsigned int s = shadowCount++;
-        p.shadowOrg[s]     = make_float4(out.nextPos.x, out.nextPos.y, out.nextPos.z, p.sceneEpsilon);
-        p.shadowDir[s]     = make_float4(out.shadowDir.x, out.shadowDir.y, out.shadowDir.z, out.shadowTmax);
-        p.shadowPixel[s]   = pixel;
-        p.shadowPending[s] = make_float4(out.pending.x, out.pending.y, out.pending.z, __uint_as_float(out.shadowSeed));
-      }
-      if (out.alive)
-      {
-        const unsigned int k = nextCount++;
-        p.rayOrg[qn][k]   = make_float4(out.nextPos.x, out.nextPos.y, out.nextPos.z, p.sceneEpsilon);
-        p.rayDir[qn][k]   = make_float4(out.nextDir.x, out.nextDir.y, out.nextDir.z, RT_DEFAULT_MAX);
-        p.rayPixel[qn][k] = pixel;
-        p.rayThroughput[qn][k] = out.throughputPdf;
-        p.raySeedFlags[qn][k]  = out.seedFlags;
-      }
+      if (out.wantShadow) storeShadowRay(p, shadowCount++, false, out.nextPos, out.shadowDir, out.shadowTmax, out.pending, pixel, out.shadowSeed);
+      if (out.alive) storeContinuation(p, qn, nextCount++, false, out.nextPos, out.nextDir, pixel, out.seedFlags, out.throughputPdf);
     }
   }
   if (maxDepth > 0) trace(maxDepth); // the shadow rays of the last shade

@@ -1,5 +1,5 @@
 // ORACLE-SIDE TEST INFRASTRUCTURE — host stand-ins for the handful of device intrinsics the product's kernel headers use,
-// so that tweeker_raytracer_amd/csrc/{device_math,device_types,shade_device,trace_device}.h compile with g++ as they are
+// so that tweeker_raytracer_amd/csrc/{device_math,device_types,path_queue,shade_device,trace_device}.h compile with g++ as they are
 // (HIP's own headers already make __device__ / __forceinline__ / float4 / make_float4 ... host constructs under g++).
 // Only oracle/host_kernels.cpp includes this.
 #pragma once
@@ -24,6 +24,7 @@ template<typename T> static inline T __shfl(T v, int) { return v; }
 static const struct { unsigned int x, y, z; } threadIdx = {0u, 0u, 0u};
 static inline unsigned int atomicAdd(unsigned int* p, unsigned int v) { const unsigned int old = *p; *p = old + v; return old; }
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { const unsigned long long old = *p; *p = old + v; return old; }
+static inline float atomicAdd(float* p, float v) { const float old = *p; *p = old + v; return old; } // path_queue.h storeRayResult: the time view's add
 #ifndef __HIP_MEMORY_SCOPE_SYSTEM
 #define __HIP_MEMORY_SCOPE_SYSTEM 5
 #endif

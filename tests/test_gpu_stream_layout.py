@@ -3,7 +3,9 @@ that has no cutout opacity runs without the hitInstance and shadowPixel streams:
 record's slot word, the launch index of a shadow ray in its pending record. Every other scene keeps the full layout.
   * C2 (Cornell box), C3 (intro_07 with cutout opacity) and C4 instances (two-level) are bit-identical to the oracle;
   * Device.streamLayout() (twk_get_stream_layout) says which layout a pass over the scene runs: C2 slim, the other two full;
-  * TWK_SLIM_STREAMS=0 puts C2 on the full layout, with the same image bit for bit.
+  * TWK_SLIM_STREAMS=0 puts C2 on the full layout, with the same image bit for bit;
+  * the four forms of a record (csrc/path_queue.h: TWK_PACKED_QUEUE x TWK_SLIM_STREAMS) render the same image bit for bit, the
+    measurement builds of the time view included.
 Several iterations as ONE deferred pass, and deep enough for shadow rays and continuation rays of every bounce."""
 import numpy as np
 import pytest
@@ -124,3 +126,43 @@ def test_statistics_and_time_view_builds_run_the_slim_layout(twk):
     counted = dev.getOutputBufferHost().copy()
     dev.close()
     assert np.array_equal(_bits(counted), _bits(plain))
+
+
+def _cornell_forms(twk, monkeypatch, timeView):
+    """The Cornell scene at 64 x 48, four iterations as one pass (paths up to ten segments long), once per form of the records:
+    {(packed, slim): image}. The switches are read when the handle is created."""
+    app = load_app(twk, "system_rtigo3_cornell_box.txt", "scene_rtigo3_cornell_box.txt", (64, 48))
+    assert app.state.pathLengths[1] >= 4
+    images = {}
+    for packed in (1, 0):
+        for slim in (1, 0):
+            monkeypatch.setenv("TWK_PACKED_QUEUE", str(packed))
+            monkeypatch.setenv("TWK_SLIM_STREAMS", str(slim))
+            dev = twk.Device(ordinal=0, miss=app.info.miss)
+            app.initDevice(dev)
+            dev.setLaunchBatch(4)
+            dev.setTimeView(timeView)
+            assert dev.streamLayout() == ("slim" if slim else "full")
+            for it in range(4):
+                dev.render(it)
+            dev.synchronizeStream()
+            images[(packed, slim)] = dev.getOutputBufferHost().copy()
+            dev.close()
+    return images
+
+
+def test_every_form_of_a_record_renders_the_same_image(twk, monkeypatch):
+    """Full and packed closest-hit records x full and slim hit and shadow records: no test turned TWK_PACKED_QUEUE off before, so
+    the full continuation record of a cutout-free scene was unpinned. With the time view on, the COUNT builds of the trace
+    kernels find a ray's launch index in the packed word, rayPixel, shadowPending.w or shadowPixel: same colour, a time for
+    every path."""
+    plain = _cornell_forms(twk, monkeypatch, False)
+    want = plain[(1, 1)]
+    assert np.isfinite(want).all() and want[..., :3].max() > 0.5 and np.all(want[..., 3] == 1.0)
+    for form, image in plain.items():
+        assert np.array_equal(_bits(image), _bits(want)), f"(packed, slim) = {form}: {(_bits(image) != _bits(want)).any(axis=2).sum()} pixels differ"
+    timed = _cornell_forms(twk, monkeypatch, True)
+    for form, image in timed.items():
+        assert np.array_equal(_bits(image[..., :3]), _bits(want[..., :3])), f"time view, (packed, slim) = {form}"
+        alpha = image[..., 3]
+        assert np.isfinite(alpha).all() and (alpha > 0.0).all(), f"time view, (packed, slim) = {form}"

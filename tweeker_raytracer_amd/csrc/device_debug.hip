@@ -70,14 +70,15 @@ try
   HIP_TRY(hipStreamSynchronize(dev->stream));
   unsigned long long h[TWK_STATS_WORDS / 2];
   HIP_TRY(hipMemcpy(h, dev->d_stats, sizeof(h), hipMemcpyDeviceToHost));
-  stats->radianceRays = h[0]; stats->shadowRays = h[1]; stats->nodesVisited = h[2]; stats->trianglesTested = h[3];
-  stats->instancesEntered = h[4]; stats->shadedHits = h[5]; stats->missed = h[6]; stats->maxNodesPerRay = h[7];
-  stats->overflowRays = h[12]; // tailRays .. tailInstancesEntered (words 8-11): the tail kernel is not part of this build, they stay 0
-  stats->nodeWaveSteps = h[13]; stats->triangleWaveSteps = h[14]; stats->leafWaveSteps = h[15];
-  stats->cachedNodesVisited = h[16]; stats->droppedStackPushes = dev->h_dropped ? *dev->h_dropped : 0u;
-  for (int i = 0; i < 6; ++i) stats->waveCycles[i] = h[18 + i];
-  const int TWK_SHADE_PHASES = TWK_SHADE_PHASE_COUNT; static_assert(24 + 3 * TWK_SHADE_PHASE_COUNT <= TWK_STATS_WORDS / 2, "shade phase words"); // shade_device.h asserts TWK_SHADE_PHASES == TWK_SHADE_PHASE_COUNT
-  for (int i = 0; i < TWK_SHADE_PHASES; ++i) { stats->shadePhaseWaveSteps[i] = h[24 + i]; stats->shadePhaseLanes[i] = h[24 + TWK_SHADE_PHASES + i]; stats->shadePhaseCycles[i] = h[24 + 2 * TWK_SHADE_PHASES + i]; }
+  // the words by name: device_types.h StatWord
+  stats->radianceRays = h[TWK_STAT_RADIANCE_RAYS]; stats->shadowRays = h[TWK_STAT_SHADOW_RAYS]; stats->nodesVisited = h[TWK_STAT_NODES_VISITED]; stats->trianglesTested = h[TWK_STAT_TRIANGLES_TESTED];
+  stats->instancesEntered = h[TWK_STAT_INSTANCES_ENTERED]; stats->shadedHits = h[TWK_STAT_SHADED_HITS]; stats->missed = h[TWK_STAT_MISSED]; stats->maxNodesPerRay = h[TWK_STAT_MAX_NODES_PER_RAY];
+  stats->overflowRays = h[TWK_STAT_OVERFLOW_RAYS]; // tailRays .. tailInstancesEntered (words 8-11): the tail kernel is not part of this build, they stay 0
+  stats->nodeWaveSteps = h[TWK_STAT_NODE_WAVE_STEPS]; stats->triangleWaveSteps = h[TWK_STAT_TRIANGLE_WAVE_STEPS]; stats->leafWaveSteps = h[TWK_STAT_LEAF_WAVE_STEPS];
+  stats->cachedNodesVisited = h[TWK_STAT_CACHED_NODES]; stats->droppedStackPushes = dev->h_dropped ? *dev->h_dropped : 0u;
+  for (int i = 0; i < 6; ++i) stats->waveCycles[i] = h[TWK_STAT_WAVE_CYCLES + i];
+  const int TWK_SHADE_PHASES = TWK_SHADE_PHASE_COUNT; static_assert(TWK_STAT_SHADE_PHASES + 3 * TWK_SHADE_PHASE_COUNT <= TWK_STATS_WORDS / 2, "shade phase words"); // shade_device.h asserts TWK_SHADE_PHASES == TWK_SHADE_PHASE_COUNT
+  for (int i = 0; i < TWK_SHADE_PHASES; ++i) { stats->shadePhaseWaveSteps[i] = h[TWK_STAT_SHADE_PHASES + i]; stats->shadePhaseLanes[i] = h[TWK_STAT_SHADE_PHASES + TWK_SHADE_PHASES + i]; stats->shadePhaseCycles[i] = h[TWK_STAT_SHADE_PHASES + 2 * TWK_SHADE_PHASES + i]; }
   if (reset) HIP_TRY(hipMemset(dev->d_stats, 0, sizeof(h)));
   return TWK_SUCCESS;
 }

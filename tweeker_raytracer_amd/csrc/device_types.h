@@ -8,7 +8,8 @@
 //   path state     in the ray queue (per slot): throughput+pdf 16 B, seed+flags 8 B — streamed with the ray;
 //                  per path: radiance 16 B, volume stack 64 B (touched only by additions / glass transmission)
 //   shadow queue   ray 32 B + 4 B launch index + pending contribution 16 B
-//   (flattened scenes without cutout opacity: no instance and no shadow launch-index stream — LaunchParams::slimSlotBits)
+//   (what each word of a queue, shadow and hit record means, in its full, packed and slim form: path_queue.h, which also
+//   holds every read and write of one)
 //   BVH2 node      64 B  (two child boxes + two child references)
 //   triangle       48 B  (three float4: vertex, w of the first = primitive index)
 #pragma once
@@ -43,8 +44,7 @@ static const float DENOMINATOR_EPSILON = 1.0e-6f;
 // survives FLAG_CLEAR_MASK, raygeneration.cu:66), bits 8-15 depth, bits 16-18 volume stack index + 1.
 #define TWK_PATH_DEPTH_SHIFT 8
 #define TWK_PATH_STACK_SHIFT 16
-// Packed queue records (LaunchParams::packedQueue): origin.w = launch index (27 bits) | FLAG_DIFFUSE << 27 | FLAG_ALBEDO << 28 |
-// (volume stack index + 1) << 29; direction.w = the LCG state.
+// Packed queue records (path_queue.h): the launch index takes the low bits of origin.w.
 #define TWK_PACKED_PIXEL_BITS 27
 #define TWK_PACKED_PIXEL_MASK ((1u << TWK_PACKED_PIXEL_BITS) - 1u)
 
@@ -210,7 +210,7 @@ struct LaunchParams
   int     outputFrame;    // 1: `output` is a shared full W x H frame addressed by absolute pixel (ZeroCopy / PeerAccess strategies), 0: this device's packed launchWidth x H buffer
   float4* output;         // running mean, RGBA32F; in half mode (twk_set_output_format TWK_OUTPUT_HALF4) the same bytes hold RGBA16F, which accumulateKernel's Half4 builds address
   unsigned int* counters; // see CounterSlot
-  unsigned long long* stats; // TwkLaunchStats as 7 u64, or nullptr
+  unsigned long long* stats; // TwkLaunchStats as u64 words (StatWord below), or nullptr
   float4* firstHit;       // debug capture (t, beta, gamma, prim) or nullptr
   int*    firstHitInstance;
   int*    traceStackSpill; // per persistent lane overflow stack
@@ -223,22 +223,10 @@ struct LaunchParams
   // TWK_ENTRY_TILE launch indices two int4 = (count, ref 0..6): the subtrees a ray through that tile can reach, nearest first.
   const int4* tileEntries;
   int     tilesX;
-  // 1: the queues shadeKernel writes (every depth >= 1) carry launch index + path flags in the .w of the origin and the LCG state in
-  // the .w of the direction — the tmin / tmax of a continuation ray are the constants sceneEpsilon / RT_DEFAULT_MAX — and the
-  // rayPixel / raySeedFlags streams are neither written nor read: 12 bytes less per path and bounce on both sides (TWK_PACKED_*).
-  // Scenes without cutout opacity (its candidate loop keeps a per-ray tmin in the record), passes of fewer than 2^27 paths.
-  int     packedQueue;
+  int     packedQueue;    // 1: the queues shadeKernel writes are PACKED records (path_queue.h); TWK_PACKED_QUEUE=0: off
   unsigned int queueStride; // slots between the starts of two queue segments (TWK_QUEUE_STRIDE of the pass's or the lane's path count)
   unsigned int* droppedPushes; // pinned host word (device-mapped): pushes the single-ray traversal could not store (trace_device.h TWK_PUSH); stays 0 on every scene twk_build accepts
-  // Slim streams (0: the layout above, every stream written and read). Non-zero: the number of bits a triangle slot takes in the
-  // hit record's slot word. Scenes whose instances are all flattened and that have no cutout opacity (renderPass decides per pass):
-  //   hit record    the slot word is slot | instance << slimSlotBits (a miss: -1, both halves) — a world-space slot belongs to one
-  //                 instance, and traversal holds it (triangles[3 * slot + 1].w) — and hitInstance is neither written nor read;
-  //   shadow queue  shadowPending.w, the seed only the cutout test draws from, is the launch index; shadowPixel is neither
-  //                 written nor read: the result write of a visible shadow ray needs ONE record before it adds to pathRadiance.
-  // 8 bytes less per path and bounce (TWK_SLIM_STREAMS=0 keeps the full layout). shadePath and the host build (oracle/) never see
-  // it: the kernels around shadePath pack and unpack.
-  int     slimSlotBits;
+  int     slimSlotBits;   // non-zero: the pass runs SLIM records (path_queue.h) — the bits a triangle slot takes in the hit record's slot word; 0: every stream written and read
   // Luminance moments of the samples (twk_enable_moments), nullptr when off: (mean, M2, n, 0) per launch index, indexed like
   // aovAlbedo, always f32. Folded by the MOMENTS builds of the accumulate kernels (shade_device.h foldSamples).
   float4* moments;
@@ -262,11 +250,6 @@ struct LaunchParams
 // (trace_device.h); the cutout builds mask the bit off as they always did and run the slot loop. Two-level scenes have no free
 // bit in a reference (bit 30 tells a world-space leaf from an instance there): their trees are built from the same pairs, their
 // references are not rewritten. TWK_TRIANGLE_PAIRS=0: no pairs in the build, no rewritten reference.
-
-// Slim streams: the hit record's slot word <-> (triangle slot, instance). A miss is -1 on both sides.
-TWK_HD int packSlotWord(int slotBits, int triangleSlot, int instance) { return triangleSlot | (int) ((unsigned int) instance << slotBits); }
-TWK_HD int slotWordInstance(int slotBits, int word) { return word >> slotBits; } // arithmetic shift: -1 stays -1
-TWK_HD int slotWordSlot(int slotBits, int word) { return (word < 0) ? word : (word & ((1 << slotBits) - 1)); }
 
 // Queue segments (round 5). shadeKernel's time was the number of returning atomics on ONE counter word divided by the rate a word
 // sustains (87.8 per microsecond: profiles/r05_shade_diagnosis.md 7). So a queue is TWK_QUEUE_SEGMENTS regions of the same arrays,
@@ -310,6 +293,18 @@ TWK_HD unsigned int physicalSlot(const QueueSegments& s, unsigned int stride, un
   return k * stride + (v - f);
 }
 #define TWK_MAX_DEPTH 64
+
+// Words of LaunchParams::stats (u64 each), as the kernels add to them and twk_stats_get (device_debug.hip) reads them.
+enum StatWord
+{
+  TWK_STAT_RADIANCE_RAYS = 0, TWK_STAT_SHADOW_RAYS, TWK_STAT_NODES_VISITED, TWK_STAT_TRIANGLES_TESTED, TWK_STAT_INSTANCES_ENTERED,
+  TWK_STAT_SHADED_HITS = 5, TWK_STAT_MISSED, TWK_STAT_MAX_NODES_PER_RAY, // shadeKernel's two; the longest ray (atomicMax)
+  // words 8-11: the tail kernel's (tailRays .. tailInstancesEntered), which is not part of this build: unused, they stay 0
+  TWK_STAT_OVERFLOW_RAYS = 12,
+  TWK_STAT_NODE_WAVE_STEPS = 13, TWK_STAT_TRIANGLE_WAVE_STEPS, TWK_STAT_LEAF_WAVE_STEPS, TWK_STAT_CACHED_NODES, // word 17: unused
+  TWK_STAT_WAVE_CYCLES = 18,  // six words: the five phases of traceKernel's outer loop, then the whole kernel
+  TWK_STAT_SHADE_PHASES = 24  // 3 x TWK_SHADE_PHASES words: wave executions, lanes, cycles per phase (shade_device.h PhaseScope)
+};
 
 #ifndef TWK_TRACE_STACK_LDS
 #define TWK_TRACE_STACK_LDS   20  // entries per lane in LDS

@@ -9,7 +9,7 @@
 #ifndef TWK_PROBE_GGX_AS_LAMBERT
 #define TWK_PROBE_GGX_AS_LAMBERT 0
 #endif
-#include "device_types.h"
+#include "path_queue.h"
 #include "cascade_device.h"
 
 namespace twk {
@@ -1079,14 +1079,7 @@ TWK_D void storePrimaryPath(const LaunchParams& p, const unsigned int index, con
     p.pathAlbedo[index] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); // Optix7Gui raygeneration.cu:66-71: black, null vector
     p.pathNormal[index] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
-  p.rayThroughput[0][index] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-  p.raySeedFlags[0][index]  = make_uint2(seed, 0u);
-
-  // Inactive launch indices (tile columns beyond the image) still own a slot so that queue 0 is the
-  // identity mapping; they carry tmax < tmin and never hit anything, and shade drops them.
-  p.rayOrg[0][index]   = make_float4(origin.x, origin.y, origin.z, p.sceneEpsilon);
-  p.rayDir[0][index]   = make_float4(direction.x, direction.y, direction.z, active ? RT_DEFAULT_MAX : -1.0f);
-  p.rayPixel[0][index] = index;
+  storePrimaryRecord(p, index, origin, direction, active, seed); // path_queue.h: unit throughput, the ray, its launch index
   if (index == 0) p.counters[0] = (unsigned int) p.numPaths;
 }
 

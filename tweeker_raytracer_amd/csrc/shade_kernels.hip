@@ -12,6 +12,7 @@
 // [+ rng when more than one light], then Russian roulette rng.
 // generateKernel and accumulateKernel are one kernel each for the three forms of a pass (uniform, listed, planned): what differs
 // between the forms is the `Samples` argument (shade_device.h "the samples of a thread").
+// The queue, shadow and hit records shadeKernel reads and appends are defined in path_queue.h, in all their forms.
 #include "shade_device.h"
 #include "pixel_formats.h"
 #include "../../include/tweeker_hip.h"
@@ -72,23 +73,11 @@ struct ShadeInput
   bool inRange;
 };
 
-// Packed queue records (device_types.h LaunchParams::packedQueue): the path word <-> the five bits next to the launch index.
-TWK_D unsigned int packPathWord(unsigned int pixel, unsigned int word)
-{
-  return pixel | (((word >> 2) & 1u) << 27) | (((word >> 28) & 1u) << 28) | (((word >> TWK_PATH_STACK_SHIFT) & 7u) << 29);
-}
-TWK_D unsigned int unpackPathWord(unsigned int packed)
-{
-  return (((packed >> 27) & 1u) << 2) | (((packed >> 28) & 1u) << 28) | ((packed >> 29) << TWK_PATH_STACK_SHIFT);
-}
-static_assert(TWK_FLAG_DIFFUSE == (1u << 2) && TWK_FLAG_ALBEDO == (1u << 28) && TWK_PACKED_PIXEL_BITS == 27, "packPathWord's bit positions");
-
+// The record of one queue slot, through path_queue.h, which defines its full, packed and slim form.
 // PRIMARY ("primary rays" below): queue 0 was never written; the slot's ray and path state are computed.
-// packed: the queue was written by shadeKernel in the packed form (device_types.h LaunchParams::packedQueue).
 // slot: the VIRTUAL slot (hit records are indexed by it); the queued ray and its path state sit at physicalSlot(slot)
 // (device_types.h "queue segments").
-// slim (device_types.h LaunchParams::slimSlotBits): there is no hitInstance stream; the hit record's slot word holds both, and
-// is taken apart where the record is first used (unpackSlimHit) — done here, the wave would wait for the record it has just requested.
+// slim: the hit record's slot word still holds the instance; it is taken apart where the record is first used (unpackSlimHit).
 template<bool PRIMARY>
 TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const QueueSegments& segments, bool packed, bool slim, ShadeInput& in)
 {
@@ -102,28 +91,28 @@ TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const
       in.ro = make_float4(ray.origin.x, ray.origin.y, ray.origin.z, p.sceneEpsilon);
       in.rd = make_float4(ray.direction.x, ray.direction.y, ray.direction.z, ray.active ? RT_DEFAULT_MAX : -1.0f);
       in.pixel = slot;
-      in.hit = p.hitRecord[slot];
-      if (!slim) in.instanceIndex = p.hitInstance[slot];
+      loadHit(p, slot, slim, in.hit, in.instanceIndex);
       in.throughputPdf = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
       // a scene with cutout opacity: the first traversal stored the seed in queue 0 and its opacity tests drew from it
-      in.seedFlags = p.hasCutout ? p.raySeedFlags[0][slot] : make_uint2(ray.seed, 0u);
+      in.seedFlags = p.hasCutout ? loadPrimarySeedFlags(p, slot) : make_uint2(ray.seed, 0u);
     }
     return;
   }
   if (in.inRange)
   {
+    // As written, not through path_queue.h loadQueuedPath (which defines this layout): through it the sorted builds come out in another
+    // register allocation and shade measured 1 % slower; loadHit alone leaves every build instruction for instruction as it was.
     const unsigned int record = physicalSlot(segments, p.queueStride, slot);
     in.ro = p.rayOrg[q][record];
     in.rd = p.rayDir[q][record];
-    in.hit = p.hitRecord[slot];
-    if (!slim) in.instanceIndex = p.hitInstance[slot];
+    loadHit(p, slot, slim, in.hit, in.instanceIndex);
     in.throughputPdf = p.rayThroughput[q][record];
     if (packed)
     {
       const unsigned int word = __float_as_uint(in.ro.w);
       in.pixel = word & TWK_PACKED_PIXEL_MASK;
       in.seedFlags = make_uint2(__float_as_uint(in.rd.w), unpackPathWord(word));
-      in.ro.w = p.sceneEpsilon; in.rd.w = RT_DEFAULT_MAX; // what a continuation ray's record holds there otherwise
+      in.ro.w = p.sceneEpsilon; in.rd.w = RT_DEFAULT_MAX;
     }
     else
     {
@@ -131,18 +120,6 @@ TWK_D void loadShadeInput(const LaunchParams& p, int q, unsigned int slot, const
       in.seedFlags = p.raySeedFlags[q][record];
     }
   }
-}
-
-// Slim streams: the hit record's slot word -> the instance shadePath is given and the triangle slot it finds in the record.
-TWK_D void unpackSlimHit(int slotBits, ShadeInput& in)
-{
-  const int word = __float_as_int(in.hit.w);
-  int instance = slotWordInstance(slotBits, word), slot = slotWordSlot(slotBits, word);
-  // Pinned: left alone, hipcc keeps the word alive next to the two and derives them again where they are used — one register
-  // more through the whole of shadePath, and the five-wave builds, which sit exactly at their 96, spill 8 bytes.
-  asm volatile("" : "+v"(instance), "+v"(slot));
-  in.instanceIndex = instance;
-  in.hit.w = __int_as_float(slot);
 }
 
 // Block barrier that orders LDS only. __syncthreads() also drains the wave's outstanding global loads and stores
@@ -196,7 +173,7 @@ struct ShadeExchange
 TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, ShadeExchange& x, unsigned int rotate, int slimSlotBits, ShadeInput& in)
 {
   const bool active = in.inRange && in.rd.w >= 0.0f;
-  const unsigned int key = shadeClass(tables, slimSlotBits ? slotWordInstance(slimSlotBits, __float_as_int(in.hit.w)) : in.instanceIndex, active);
+  const unsigned int key = shadeClass(tables, slimSlotBits ? slimHitInstance(slimSlotBits, in.hit) : in.instanceIndex, active);
   const unsigned int rank = atomicAdd(classCount + key, 1u); // the order inside a class is the order the adds arrive in: no result depends on it
   ldsBarrier();
   const uint4 lo = *reinterpret_cast<const uint4*>(classCount), hi = *reinterpret_cast<const uint4*>(classCount + 4);
@@ -242,7 +219,7 @@ TWK_D void sortExchange(const ShadeTables& tables, unsigned int* classCount, Sha
 #endif
 // SORT: the block shades its window in class order (above; LDS_TABLES builds only). The measurement builds carry the exchange
 // buffer too and take LaunchParams::shadeSort at run time.
-// SLIM: the pass runs the slim streams (device_types.h LaunchParams::slimSlotBits) — a build, not a launch parameter: with both
+// SLIM: the pass runs the slim records (path_queue.h) — a build, not a launch parameter: with both
 // layouts in one kernel the five-wave builds, which sit exactly at their 96 registers, spilled 8 to 12 bytes.
 template<bool ENV, bool TEX, bool PRIMARY, bool LDS_TABLES, bool MEASURE, bool SORT, bool SLIM>
 __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (PRIMARY ? TWK_SHADE_WAVES_PRIMARY : TWK_SHADE_WAVES)) shadeKernel(LaunchParams p, int depth)
@@ -257,8 +234,8 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   const unsigned int numRays = segments.total;
   if (blockIdx.x * blockDim.x >= numRays) return;
   const int q = depth & 1, qn = q ^ 1;
-  const bool packedIn = p.packedQueue != 0 && depth > 0, packedOut = p.packedQueue != 0; // queue 0 is computed (PRIMARY) or written by generateKernel
-  constexpr bool slim = SLIM; // no hitInstance stream in, no shadowPixel stream out
+  const bool packedIn = packedInput(p, depth), packedOut = packedOutput(p); // the form of the queue read and of the queue written: path_queue.h
+  constexpr bool slim = SLIM; // slim hit records in, slim shadow records out
   ShadeInput in = {}; // a thread beyond the queue hands its (empty) record to the exchange all the same
   loadShadeInput<PRIMARY>(p, q, blockIdx.x * blockDim.x + threadIdx.x, segments, packedIn, slim, in);
 
@@ -319,7 +296,7 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
     const unsigned int clockBegin = MEASURE ? (unsigned int) __builtin_readcyclecounter() : 0u;
     const unsigned int iterationBegin = clockBegin;
     if (EXCHANGE && sorted) sortExchange(tables, classCount, *reinterpret_cast<ShadeExchange*>(exchangeStorage), ((blockIdx.x + base / (gridDim.x * blockDim.x)) & 3u) << 6, slim ? p.slimSlotBits : 0, in);
-    if (slim && in.inRange) unpackSlimHit(p.slimSlotBits, in);
+    if (slim && in.inRange) unpackSlimHit(p.slimSlotBits, in.hit, in.instanceIndex);
     const unsigned int slotLanes = MEASURE ? (unsigned int) __popcll(__ballot(in.inRange)) : 0u; // lanes of this wave with a queue slot in THIS window (`in` holds the next window's by the time the tallies are written)
     const unsigned int pixel = in.pixel;
     if (in.inRange && in.rd.w >= 0.0f) // else: beyond the queue, or an inactive launch index (tile column beyond the image)
@@ -395,29 +372,16 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
     if (out.wantShadow)
     {
       const unsigned int s = shadowOffset + (unsigned int) __popcll(shadowMask & laneBelow);
+      // As written, not through path_queue.h storeShadowRay (which defines this layout): same reason as the load above.
       p.shadowOrg[s]     = make_float4(out.nextPos.x, out.nextPos.y, out.nextPos.z, p.sceneEpsilon);
       p.shadowDir[s]     = make_float4(out.shadowDir.x, out.shadowDir.y, out.shadowDir.z, out.shadowTmax);
       if (!slim) p.shadowPixel[s] = pixel;
-      p.shadowPending[s] = make_float4(out.pending.x, out.pending.y, out.pending.z, __uint_as_float(slim ? pixel : out.shadowSeed)); // slim: no cutout test draws from the seed; the launch index rides there
+      p.shadowPending[s] = make_float4(out.pending.x, out.pending.y, out.pending.z, __uint_as_float(slim ? pixel : out.shadowSeed));
     }
     if (out.alive)
     {
       const unsigned int n = nextOffset + (unsigned int) __popcll(nextMask & laneBelow);
-      if (packedOut)
-      {
-        // launch index + path flags and the LCG state ride in the record's two constant words: 12 bytes less written here, 12
-        // less read by the next shade launch (the big shade launches sit at the HBM rate)
-        p.rayOrg[qn][n] = make_float4(out.nextPos.x, out.nextPos.y, out.nextPos.z, __uint_as_float(packPathWord(pixel, out.seedFlags.y)));
-        p.rayDir[qn][n] = make_float4(out.nextDir.x, out.nextDir.y, out.nextDir.z, __uint_as_float(out.seedFlags.x));
-      }
-      else
-      {
-        p.rayOrg[qn][n]   = make_float4(out.nextPos.x, out.nextPos.y, out.nextPos.z, p.sceneEpsilon);
-        p.rayDir[qn][n]   = make_float4(out.nextDir.x, out.nextDir.y, out.nextDir.z, RT_DEFAULT_MAX);
-        p.rayPixel[qn][n] = pixel;
-        p.raySeedFlags[qn][n]  = out.seedFlags;
-      }
-      p.rayThroughput[qn][n] = out.throughputPdf;
+      storeContinuation(p, qn, n, packedOut, out.nextPos, out.nextDir, pixel, out.seedFlags, out.throughputPdf);
     }
     buffer ^= 1u;
     if (measurePhases && lane == 0)
@@ -433,8 +397,8 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
   if (measurePhases)
   {
     __syncthreads();
-    // stats[24 ..): wave executions, lanes, cycles per phase (device_debug.hip twk_stats_get)
-    if (threadIdx.x < 3 * TWK_SHADE_PHASES && phaseWords[threadIdx.x] != 0u) atomicAdd(&p.stats[24 + threadIdx.x], (unsigned long long) phaseWords[threadIdx.x]);
+    // wave executions, lanes, cycles per phase (device_debug.hip twk_stats_get)
+    if (threadIdx.x < 3 * TWK_SHADE_PHASES && phaseWords[threadIdx.x] != 0u) atomicAdd(&p.stats[TWK_STAT_SHADE_PHASES + threadIdx.x], (unsigned long long) phaseWords[threadIdx.x]);
   }
 
   if (p.stats != nullptr)
@@ -447,8 +411,8 @@ __global__ void __launch_bounds__(TWK_SHADE_BLOCK, ENV ? TWK_SHADE_WAVES_ENV : (
     }
     if ((threadIdx.x & 63) == 0)
     {
-      if (statHit)  atomicAdd(&p.stats[5], (unsigned long long) statHit);
-      if (statMiss) atomicAdd(&p.stats[6], (unsigned long long) statMiss);
+      if (statHit)  atomicAdd(&p.stats[TWK_STAT_SHADED_HITS], (unsigned long long) statHit);
+      if (statMiss) atomicAdd(&p.stats[TWK_STAT_MISSED], (unsigned long long) statMiss);
     }
   }
 }

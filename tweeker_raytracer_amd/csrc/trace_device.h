@@ -2,7 +2,7 @@
 // watertight triangle test (Woop, Benthin, Wald, JCGT 2013), and the single-ray two-level traversal whose stack
 // continues from LDS into HBM. See trace_kernels.hip for the contract these stand in for (optixTrace).
 #pragma once
-#include "device_types.h"
+#include "path_queue.h" // TraceResult, the ray and hit records
 
 namespace twk {
 
@@ -327,13 +327,6 @@ TWK_D void woopIntersectPair(const WoopConstants& w, const V3& o, const V3& p0, 
   r.hit0 = woopPairFirst(w, o, s, p1, tmin, r.t0, r.beta0, r.gamma0);
   r.hit1 = woopPairSecond(w, o, s, p3, tmin, r.t1, r.beta1, r.gamma1);
 }
-
-struct TraceResult
-{
-  float t, beta, gamma;
-  int   instance, primitive;
-  int   triangleSlot; // slot of the hit triangle in the leaf-ordered arrays (what shading indexes)
-};
 
 // COUNT: tally node / triangle / instance visits (measurement builds only).
 template<bool COUNT>

@@ -1,5 +1,5 @@
 // Launchers of the persistent traversal kernel (trace_persistent.h), the kernel that re-traces the rays whose LDS stack
-// overflowed, the stand-alone query kernel and the entry points of the primary rays.
+// overflowed, the stand-alone query kernel and the entry points of the primary rays. (The records of a pass: path_queue.h.)
 #include "trace_persistent.h"
 
 #include <array>
@@ -51,8 +51,7 @@ traceOverflowKernel(LaunchParams p, int depth)
   const QueueSegments shadowSegments  = (depth > 0) ? queueSegments(&p.counters[(depth - 1) * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_SHADOW]) : noSegments();
   const unsigned int numClosest = closestSegments.total;
   const int q = depth & 1;
-  const bool packed = !CUTOUT && !PRIMARY && p.packedQueue != 0 && depth > 0; // as in traceKernel
-  const bool slim = !CUTOUT && p.slimSlotBits != 0; // as in traceKernel (set for flattened scenes only)
+  const bool packed = tracePacked(p, depth, CUTOUT, PRIMARY), slim = traceSlim(p, CUTOUT); // the form of this launch's records: path_queue.h
   unsigned int nodeCount = 0, triCount = 0, instCount = 0;
   for (unsigned int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
   {
@@ -69,12 +68,10 @@ traceOverflowKernel(LaunchParams p, int depth)
     }
     else
     {
-      o = isShadow ? p.shadowOrg[record] : p.rayOrg[q][record];
-      d = isShadow ? p.shadowDir[record] : p.rayDir[q][record];
+      const QueuedRay r = isShadow ? loadShadowRay(p, record) : loadClosestRay(p, q, record, packed);
+      o = r.o; d = r.d;
     }
-    const unsigned int packedPixel = __float_as_uint(o.w) & TWK_PACKED_PIXEL_MASK;
-    if (packed && !isShadow) { o.w = p.sceneEpsilon; d.w = RT_DEFAULT_MAX; }
-    float tmin = (PRIMARY && CUTOUT) ? p.hitRecord[slot].x : o.w; // carries the distance of the last ignored cutout candidate, if any
+    float tmin = (PRIMARY && CUTOUT) ? loadOverflowTmin(p, slot) : o.w; // carries the distance of the last ignored cutout candidate, if any
     const unsigned int rayClock = COUNT ? (unsigned int) __builtin_readcyclecounter() : 0u; // time view: this lane's cycles for the re-trace
     TraceResult res;
     for (;;)
@@ -83,36 +80,16 @@ traceOverflowKernel(LaunchParams p, int depth)
       if (!(CUTOUT && res.instance >= 0 && cutoutIgnoresCandidate(p, res, isShadow, q, record, PRIMARY))) break;
       tmin = res.t;
     }
-    if (COUNT && p.pathTime != nullptr)
-      atomicAdd(&p.pathTime[isShadow ? (slim ? __float_as_uint(p.shadowPending[record].w) : p.shadowPixel[record]) : (PRIMARY ? slot : (packed ? packedPixel : p.rayPixel[q][record]))], float((unsigned int) __builtin_readcyclecounter() - rayClock));
-    if (!isShadow)
-    {
-      p.hitRecord[slot] = make_float4(res.t, res.beta, res.gamma, __int_as_float(slim ? packSlotWord(p.slimSlotBits, res.triangleSlot, res.instance) : res.triangleSlot));
-      if (!slim) p.hitInstance[slot] = res.instance;
-      if (p.firstHit != nullptr && depth == 0)
-      {
-        const unsigned int pixel = PRIMARY ? slot : p.rayPixel[q][record];
-        p.firstHit[pixel] = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.primitive));
-        p.firstHitInstance[pixel] = res.instance;
-      }
-    }
-    else if (res.instance < 0)
-    {
-      const unsigned int sIdx = record;
-      const float4 c = p.shadowPending[sIdx];
-      const unsigned int pixel = slim ? __float_as_uint(c.w) : p.shadowPixel[sIdx];
-      float4 r = p.pathRadiance[pixel];
-      r.x += c.x; r.y += c.y; r.z += c.z;
-      p.pathRadiance[pixel] = r;
-    }
+    const unsigned int rayCycles = COUNT ? (unsigned int) __builtin_readcyclecounter() - rayClock : 0u;
+    storeRayResult<COUNT>(p, depth, PRIMARY, packed, slim, slot, isShadow, res, rayCycles, [&]() { return record; });
   }
   if (COUNT)
   {
     // the persistent kernel already counted these rays and its partial visits; add the re-trace's visits
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.stats[12], (unsigned long long) count);
-    atomicAdd(&p.stats[2], (unsigned long long) nodeCount);
-    atomicAdd(&p.stats[3], (unsigned long long) triCount);
-    atomicAdd(&p.stats[4], (unsigned long long) instCount);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.stats[TWK_STAT_OVERFLOW_RAYS], (unsigned long long) count);
+    atomicAdd(&p.stats[TWK_STAT_NODES_VISITED], (unsigned long long) nodeCount);
+    atomicAdd(&p.stats[TWK_STAT_TRIANGLES_TESTED], (unsigned long long) triCount);
+    atomicAdd(&p.stats[TWK_STAT_INSTANCES_ENTERED], (unsigned long long) instCount);
   }
 }
 

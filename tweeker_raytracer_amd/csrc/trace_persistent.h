@@ -14,6 +14,8 @@
 // Triangle test: watertight algorithm of Woop, Benthin, Wald (JCGT 2013), single precision with the
 // double fallback on zero edge functions, no fused multiply-add. Ties in t go to the smaller
 // (instance, primitive) pair, so the result does not depend on traversal order.
+//
+// The ray, shadow and hit records this kernel reads and writes are defined in path_queue.h, in all their forms.
 #pragma once
 #include "trace_device.h"
 #include "shade_device.h" // tex2D, rng, tea for the cutout-opacity test
@@ -22,9 +24,9 @@ namespace twk {
 
 // Cutout opacity (anyhit.cu:46-80 radiance, :94-132 shadow): stochastic alpha test of ONE candidate hit. Candidates
 // are visited closest-first; radiance rays draw from the path's seed, shadow rays from the stream forked when the ray
-// was emitted (shadowPending.w, see shadePath). Returns true when the candidate is ignored; the caller then restarts
-// the traversal strictly behind it. The new tmin is written back to the ray record so that a re-trace by
-// traceOverflowKernel continues behind the same candidate.
+// was emitted (see shadePath) — the seed in the ray's record, path_queue.h drawFromRaySeed. Returns true when the candidate is
+// ignored; the caller then restarts the traversal strictly behind it. The new tmin is written back to the ray record so that a
+// re-trace by traceOverflowKernel continues behind the same candidate.
 // primary: a ray of the fused first launch (PRIMARY builds): queue 0 holds its seed (stored at the refill) but no ray record —
 // the new tmin stays in the caller's register and is handed to traceOverflowKernel through the hit record (see there).
 // record: the physical index of the ray's record in its queue (device_types.h "queue segments").
@@ -39,23 +41,9 @@ TWK_D bool cutoutIgnoresCandidate(const LaunchParams& p, const TraceResult& res,
   const V3 texcoord = v3(s5.y, s5.z, s5.w) * alpha + v3(s6.x, s6.y, s6.z) * res.beta + v3(s6.w, s7.x, s7.y) * res.gamma;
   const float opacity = intensity(v3(tex2D(p.textures[1], texcoord.x, texcoord.y)));
   if (!(opacity < 1.0f)) return false;
-  float draw;
-  if (isShadow)
-  {
-    float4 pend = p.shadowPending[record];
-    unsigned int seed = __float_as_uint(pend.w);
-    draw = rng(seed);
-    pend.w = __uint_as_float(seed);
-    p.shadowPending[record] = pend;
-  }
-  else
-  {
-    uint2 sf = p.raySeedFlags[q][record];
-    draw = rng(sf.x);
-    p.raySeedFlags[q][record] = sf;
-  }
+  const float draw = drawFromRaySeed(p, isShadow, q, record, [](unsigned int& seed) { return rng(seed); });
   if (!(opacity <= draw)) return false;
-  if (isShadow) p.shadowOrg[record].w = res.t; else if (!primary) p.rayOrg[q][record].w = res.t;
+  if (isShadow || !primary) storeRayTmin(p, isShadow, q, record, res.t);
   return true;
 }
 
@@ -97,7 +85,7 @@ TWK_D bool cutoutIgnoresCandidate(const LaunchParams& p, const TraceResult& res,
 // PRIMARY: depth 0 of a pass without generateKernel — the lane computes the primary ray of its slot instead of fetching it
 // (shade_kernels.hip "primary rays"). With CUTOUT the seed is stored in queue 0 for the opacity draws.
 // (The builds over compressed 8-ary nodes, round 4, lost on every scene and live in tools/experiments/r04_wide8_nodes.patch.)
-// SLIM: the pass runs the slim streams (device_types.h LaunchParams::slimSlotBits: no hitInstance, no shadowPixel stream) — a
+// SLIM: the pass runs the slim records (path_queue.h: no instance stream, no launch-index stream of the shadow queue) — a
 // build of its own, not a launch parameter: with both forms of the result write in one kernel every build took one or two
 // more registers, and the measurement build of the seven-block form four more bytes of scratch.
 template<bool COUNT, bool CUTOUT, bool TWO_LEVEL, bool W7, bool PRIMARY, bool SLIM>
@@ -130,7 +118,7 @@ traceKernel(LaunchParams p, int depth)
 #define TWK_RECORD(slot_) (((slot_) < numClosest) ? (PRIMARY ? (slot_) : physicalSlot(closestSegments, p.queueStride, (slot_))) : physicalSlot(shadowSegments, p.queueStride, (slot_) - numClosest))
 
   const int q = depth & 1;
-  const bool packed = !CUTOUT && !PRIMARY && p.packedQueue != 0 && depth > 0; // device_types.h LaunchParams::packedQueue: the closest-hit rays' .w words are not tmin / tmax
+  const bool packed = tracePacked(p, depth, CUTOUT, PRIMARY); // the form of this launch's records: path_queue.h
   constexpr bool slim = SLIM;
   const unsigned int lane = threadIdx.x & 63u;
   const unsigned long long laneBelow = (1ull << lane) - 1ull;
@@ -220,7 +208,7 @@ traceKernel(LaunchParams p, int depth)
         state = (state & ~ST_RETRACE) | ST_OVERFLOWED;
         const unsigned int k = atomicAdd(&p.counters[depth * TWK_COUNTERS_PER_DEPTH + TWK_COUNTER_OVERFLOW], 1u);
         p.overflowSlots[k] = slot;
-        if (PRIMARY && CUTOUT) p.hitRecord[slot] = make_float4(tmin, 0.0f, 0.0f, 0.0f); // where the re-trace continues: behind the candidates ignored so far
+        if (PRIMARY && CUTOUT) storeOverflowTmin(p, slot, tmin); // where the re-trace continues: behind the candidates ignored so far
       }
       if (COUNT) maxSteps = max(maxSteps, guard);
       const bool ignoredCandidate = CUTOUT && !(state & ST_OVERFLOWED) && res.instance >= 0 &&
@@ -241,8 +229,8 @@ traceKernel(LaunchParams p, int depth)
         else
         {
           const unsigned int record = TWK_RECORD(slot);
-          o = isShadow ? p.shadowOrg[record] : p.rayOrg[q][record];
-          d = isShadow ? p.shadowDir[record] : p.rayDir[q][record];
+          const QueuedRay r = isShadow ? loadShadowRay(p, record) : loadClosestRay(p, q, record, packed);
+          o = r.o; d = r.d;
         }
         org = v3(o); dir = v3(d);
         res.t = d.w; res.beta = 0.0f; res.gamma = 0.0f; res.instance = -1; res.primitive = -1; res.triangleSlot = -1;
@@ -254,37 +242,11 @@ traceKernel(LaunchParams p, int depth)
         state |= ST_HAS_RAY;
       }
       else if (state & ST_OVERFLOWED) { state &= ~ST_OVERFLOWED; }
-      else if (!isShadow)
-      {
-        if (slim) p.hitRecord[slot] = make_float4(res.t, res.beta, res.gamma, __int_as_float(packSlotWord(p.slimSlotBits, res.triangleSlot, res.instance)));
-        else
-        {
-          p.hitRecord[slot]   = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.triangleSlot));
-          p.hitInstance[slot] = res.instance;
-        }
-        if (COUNT) ++closestCount;
-        if (COUNT && p.pathTime != nullptr) atomicAdd(&p.pathTime[PRIMARY ? slot : (packed ? (__float_as_uint(p.rayOrg[q][TWK_RECORD(slot)].w) & TWK_PACKED_PIXEL_MASK) : p.rayPixel[q][TWK_RECORD(slot)])], float(rayCycles)); // time view: the lane's cycles from taking the ray to its completion
-        if (p.firstHit != nullptr && depth == 0)
-        {
-          const unsigned int pixel = PRIMARY ? slot : p.rayPixel[q][TWK_RECORD(slot)];
-          p.firstHit[pixel] = make_float4(res.t, res.beta, res.gamma, __int_as_float(res.primitive));
-          p.firstHitInstance[pixel] = res.instance;
-        }
-      }
       else
       {
-        if (COUNT) ++shadowCount;
-        if (COUNT && p.pathTime != nullptr) atomicAdd(&p.pathTime[slim ? __float_as_uint(p.shadowPending[TWK_RECORD(slot)].w) : p.shadowPixel[TWK_RECORD(slot)]], float(rayCycles));
-        if (res.instance < 0)
-        {
-          // visible: add the pending next-event contribution (closesthit.cu:288-299, raygeneration.cu:100)
-          const unsigned int s = TWK_RECORD(slot);
-          const float4 c = p.shadowPending[s];
-          const unsigned int pixel = slim ? __float_as_uint(c.w) : p.shadowPixel[s]; // slim: the launch index rides in the pending record
-          float4 r = p.pathRadiance[pixel];
-          r.x += c.x; r.y += c.y; r.z += c.z;
-          p.pathRadiance[pixel] = r;
-        }
+        if (COUNT) { if (isShadow) ++shadowCount; else ++closestCount; }
+        // hit record / the visible shadow ray's contribution; time view: the lane's cycles from taking the ray to its completion
+        storeRayResult<COUNT>(p, depth, PRIMARY, packed, slim, slot, isShadow, res, rayCycles, [=]() { return TWK_RECORD(slot); });
       }
     }
 
@@ -325,7 +287,7 @@ traceKernel(LaunchParams p, int depth)
               o = make_float4(pr.origin.x, pr.origin.y, pr.origin.z, p.sceneEpsilon);
               d = make_float4(pr.direction.x, pr.direction.y, pr.direction.z, pr.active ? RT_DEFAULT_MAX : -1.0f);
               state = ST_HAS_RAY;
-              if (CUTOUT) p.raySeedFlags[0][slot] = make_uint2(pr.seed, 0u); // the opacity test of this segment draws from the seed in the queue (cutoutIgnoresCandidate), and shade(0) takes it from there
+              if (CUTOUT) storePrimarySeed(p, slot, pr.seed); // the opacity test of this segment draws from the seed in the queue (cutoutIgnoresCandidate), and shade(0) takes it from there
               if (p.tileEntries != nullptr)
               {
                 const unsigned int launchIndex = (slot + (unsigned int) p.pathBase) % (unsigned int) p.numPixels;
@@ -336,14 +298,13 @@ traceKernel(LaunchParams p, int depth)
             }
             else if (slot < numClosest)
             {
-              const unsigned int record = physicalSlot(closestSegments, p.queueStride, slot);
-              o = p.rayOrg[q][record]; d = p.rayDir[q][record]; state = ST_HAS_RAY;
-              if (packed) { o.w = p.sceneEpsilon; d.w = RT_DEFAULT_MAX; }
+              const QueuedRay r = loadClosestRay(p, q, physicalSlot(closestSegments, p.queueStride, slot), packed);
+              o = r.o; d = r.d; state = ST_HAS_RAY;
             }
             else
             {
-              const unsigned int record = physicalSlot(shadowSegments, p.queueStride, slot - numClosest);
-              o = p.shadowOrg[record]; d = p.shadowDir[record]; state = ST_HAS_RAY | ST_SHADOW | (CUTOUT ? 0u : ST_ANY_HIT);
+              const QueuedRay r = loadShadowRay(p, physicalSlot(shadowSegments, p.queueStride, slot - numClosest));
+              o = r.o; d = r.d; state = ST_HAS_RAY | ST_SHADOW | (CUTOUT ? 0u : ST_ANY_HIT);
             }
             org = v3(o); dir = v3(d); tmin = o.w;
             res.t = d.w; res.beta = 0.0f; res.gamma = 0.0f; res.instance = -1; res.primitive = -1; res.triangleSlot = -1;
@@ -628,20 +589,20 @@ traceKernel(LaunchParams p, int depth)
   if (COUNT)
   {
     const unsigned long long kernelEnd = __builtin_readcyclecounter(); // before the counters' own atomics, which queue up behind each other
-    atomicAdd(&p.stats[0], (unsigned long long) closestCount);
-    atomicAdd(&p.stats[1], (unsigned long long) shadowCount);
-    atomicAdd(&p.stats[2], (unsigned long long) nodeCount);
-    atomicAdd(&p.stats[3], (unsigned long long) triCount);
-    atomicAdd(&p.stats[4], (unsigned long long) instCount);
-    atomicMax(&p.stats[7], (unsigned long long) maxSteps);
-    if (nodeWaveSteps) atomicAdd(&p.stats[13], (unsigned long long) nodeWaveSteps);
-    if (triWaveSteps)  atomicAdd(&p.stats[14], (unsigned long long) triWaveSteps);
-    if (leafWaveSteps) atomicAdd(&p.stats[15], (unsigned long long) leafWaveSteps);
-    if (cachedCount)   atomicAdd(&p.stats[16], (unsigned long long) cachedCount);
+    atomicAdd(&p.stats[TWK_STAT_RADIANCE_RAYS], (unsigned long long) closestCount);
+    atomicAdd(&p.stats[TWK_STAT_SHADOW_RAYS], (unsigned long long) shadowCount);
+    atomicAdd(&p.stats[TWK_STAT_NODES_VISITED], (unsigned long long) nodeCount);
+    atomicAdd(&p.stats[TWK_STAT_TRIANGLES_TESTED], (unsigned long long) triCount);
+    atomicAdd(&p.stats[TWK_STAT_INSTANCES_ENTERED], (unsigned long long) instCount);
+    atomicMax(&p.stats[TWK_STAT_MAX_NODES_PER_RAY], (unsigned long long) maxSteps);
+    if (nodeWaveSteps) atomicAdd(&p.stats[TWK_STAT_NODE_WAVE_STEPS], (unsigned long long) nodeWaveSteps);
+    if (triWaveSteps)  atomicAdd(&p.stats[TWK_STAT_TRIANGLE_WAVE_STEPS], (unsigned long long) triWaveSteps);
+    if (leafWaveSteps) atomicAdd(&p.stats[TWK_STAT_LEAF_WAVE_STEPS], (unsigned long long) leafWaveSteps);
+    if (cachedCount)   atomicAdd(&p.stats[TWK_STAT_CACHED_NODES], (unsigned long long) cachedCount);
     if (lane == 0)
     {
-      for (int k = 0; k < 5; ++k) atomicAdd(&p.stats[18 + k], phaseCycles[k]);
-      atomicAdd(&p.stats[23], kernelEnd - kernelStart);
+      for (int k = 0; k < 5; ++k) atomicAdd(&p.stats[TWK_STAT_WAVE_CYCLES + k], phaseCycles[k]);
+      atomicAdd(&p.stats[TWK_STAT_WAVE_CYCLES + 5], kernelEnd - kernelStart);
     }
   }
 #undef TWK_WAVE_STEP

@@ -934,7 +934,7 @@ int twk_temporal_cascade_trusted_host(const TwkTemporal* tp, const TwkCascade* c
  *   twk_update_instance_transform(dev, id, M);                            (the history stays; the geometry AOV is stale)
  *   twk_set_sample_offset; twk_launch 0 .. spp-1; twk_render_geometry; twk_temporal_accumulate [_rectified];
  * The complete definition is csrc/temporal_motion_device.h; tests/temporal_motion_restate.py restates it in numpy. What it is not:
- * no deforming geometry or vertex updates, no per-vertex motion, no motion blur, no moving lights (an instance that carries a
+ * no deforming geometry here (vertex updates and per-vertex motion: "Deforming an object" below), no motion blur, no moving lights (an instance that carries a
  * light is refused), no environment reprojection, pinhole only. By default every update rebuilds the whole acceleration structure, as
  * twk_build does; "Selective instance updates" below rebuilds only what the moved instances change. Shadows and inter-reflections that the move changes ELSEWHERE are stale history like a
  * light edit's: the rectified merge discounts them.
@@ -970,7 +970,7 @@ int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12
  * current transforms. Everything else about an update is as "Moving an object" says: the temporal history stays, adaptive state is
  * dropped, the geometry AOV is stale, and an update that fails (an allocation, a HIP error, the depth refusal, with twk_build's
  * text) leaves the handle unbuilt until twk_build. What it is not: no refit (a moved flattened instance gets a new tree), no vertex
- * updates, no adding or removing of instances, no change of flatten policy or build quality between updates (those need twk_build),
+ * updates by these calls (twk_update_geometry_vertices: "Deforming an object" below), no adding or removing of instances, no change of flatten policy or build quality between updates (those need twk_build),
  * no moving emitters. Measured: profiles/r24_selective_update.md. */
 #define TWK_UPDATE_FULL      0 /* default: an update rebuilds everything twk_build builds; nothing is kept */
 #define TWK_UPDATE_SELECTIVE 1
@@ -1009,6 +1009,95 @@ typedef struct TwkUpdatePlan
 } TwkUpdatePlan;
 int twk_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
                          int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges);
+/* ---- Deforming an object: the vertex update and the previous-position plane — new calls, ABI stays 9, no existing struct, enum or
+ * constant changes; while no vertex update has been made every existing call launches the kernels it launched --------------------
+ * twk_update_geometry_vertices replaces the vertices of one geometry (≙ rebuilding an OptiX GAS on a new vertex buffer, which the
+ * reference's Device::createGeometry cannot do) and KEEPS the temporal history; twk_render_geometry_motion then says, per pixel,
+ * where the surface point it sees was when the history was taken. The complete definition of that plane is
+ * csrc/temporal_carry_device.h; tests/temporal_carry_restate.py restates it in numpy. What it is not: no topology change (the indices
+ * stay), no refit (a changed tree is rebuilt, or the equality below would not hold), no device-pointer source for the vertices, no
+ * emitting geometry, no motion blur, no tiled frames (the assembled forms refuse while a geometry is deformed), pinhole only, no
+ * rtigo3_hip key. The merges read the plane through their Carried builds, further below. Measured: profiles/r25_vertex_update.md (tools/vertex_update_time.py).
+ *
+ * Replaces all TwkTriangleAttributes of geometry idGeometry (positions, tangents, normals, texcoords; the caller keeps them
+ * consistent); the indices, and so topology and triangle pairing, stay. Rebuilds the acceleration structure and synchronises;
+ * twk_get_build_info then describes this rebuild. Afterwards the handle equals, byte for byte, a fresh handle that was given the new
+ * vertices through twk_clear_scene ... twk_build: acceleration structure, scene arrays, build info except its time, every picture.
+ * A handle built in full mode rebuilds everything; one built in TWK_UPDATE_SELECTIVE uploads the geometry's attributes and rebuilds
+ * the bottom-level tree of the geometry at the node and slot range it has (if some instance enters it — the first bottom-level tree
+ * the selective path rebuilds), the world box of every entered instance of it, the world-space tree of every flattened instance of
+ * it, the top level, the 8-wide root, and the quantised copy and pair references of exactly those ranges. twk_get_update_info
+ * describes it: instancesMoved 0, treesRebuilt = the bottom-level tree, if any, plus the flattened trees, instanceRecordsUploaded 0.
+ * As for a transform update the temporal history is kept, adaptive state is dropped and the geometry AOV is stale.
+ * The first update of a geometry since the history's frame keeps the geometry's object-space positions as of that frame (several
+ * updates between two merges keep the oldest): the geometry is DEFORMED (twk_get_geometry_deformed) until an own-buffer merge swaps
+ * the history or twk_temporal_reset, twk_build or twk_clear_scene drop it. Without a history nothing is kept.
+ * A refused call changes nothing; a rebuild that fails leaves the handle unbuilt, as twk_build does. TWK_ERROR_INVALID_VALUE: a NULL
+ * handle or array (before any HIP call), an id out of range, numAttributes different from the geometry's vertex count, a position
+ * that is not finite, a geometry that an instance with idLight >= 0 references (the light definition holds the emitter's shape and
+ * would disagree). TWK_ERROR_INVALID_STATE: before a successful twk_build. */
+int twk_update_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes);
+/* Whether the handle holds previous positions of the geometry (above). TWK_ERROR_INVALID_VALUE: a NULL argument, an id out of range. */
+int twk_get_geometry_deformed(TwkDevice dev, int idGeometry, int* deformed);
+/* twk_update_plan_host with updated geometries as well as moved instances (either count may be 0): the plan of
+ * twk_update_geometry_vertices is the one with numMoved 0 and the one geometry. plan->treesRebuilt counts the bottom-level trees of
+ * the updated geometries that some instance enters and the world-space trees of the flattened instances among the moved ones and
+ * among the instances of the updated geometries; trees[] lists them, a bottom-level tree as ~geometry (negative) first, and ranges[]
+ * their node ranges in the same order (ascending and disjoint), then the top level and the two root slots: give both room for
+ * numGeometries + numInstances + 2 entries. Refusals as twk_update_plan_host's, plus an updated id out of range or listed twice. */
+int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                                int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,
+                                TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges);
+/* One record per instance beside its TwkInstanceMotion (csrc/temporal_carry_device.h): previousObjectToWorld is the instance's
+ * object-to-world matrix as of the history's frame, row-major 3 x 4; deformed = 0 says its geometry holds no previous positions and
+ * nothing else is read; positionBase / indexBase: the first previous position / first index of its geometry in the arrays given. */
+typedef struct TwkInstanceCarry { float previousObjectToWorld[12]; unsigned int deformed, positionBase, indexBase, reserved; } TwkInstanceCarry; /* 64 bytes */
+/* twk_render_geometry with a second plane: one launch of a kernel of its own (picture-shaped handles only) writes the geometry AOV
+ * exactly as twk_render_geometry does and, beside it, one float4 per pixel, always f32: a miss (0, 0, 0, bits 0); a hit
+ * (g'.xyz, bits of g.w), where g' is where the surface point was when the history was taken — on a deformed geometry the hit's
+ * barycentrics on the triangle's previous vertices through the instance's object-to-world matrix of that frame, on an instance that
+ * has only moved X g of TwkInstanceMotion (the same bits), else g itself. Without a history, and after a merge has swapped it, every
+ * hit's g' is g. The plane goes stale with the geometry AOV and when a merge swaps the history. Refusals: those of
+ * twk_render_geometry, with its texts (a packed tile buffer included); TWK_ERROR_INVALID_VALUE: a NULL handle. */
+int twk_render_geometry_motion(TwkDevice dev);
+/* The plane: width x height float4. TWK_ERROR_INVALID_STATE: no valid plane (twk_render_geometry_motion first). */
+int twk_get_previous_position_device_pointer(TwkDevice dev, void** dptr, size_t* bytes);
+int twk_read_previous_positions(TwkDevice dev, float* host, size_t numFloats);
+/* Pure CPU, no device: the plane of numPixels pixels from host arrays with the code the kernel runs. hits: (t, beta, gamma) per
+ * pixel; instance (< 0: a miss) and primitive (local to the geometry) per pixel; geometry: the geometry AOV, four floats per pixel;
+ * indices[numIndices]; previousPositions: four floats per vertex, numPositions of them; motion[numMotion] and carry[numCarry],
+ * indexed by instance (an instance beyond a table is unmoved / not deformed); plane: four floats per pixel.
+ * TWK_ERROR_INVALID_VALUE: a NULL argument, numPixels outside 1..2^28, a negative count or a count without its array, a deformed
+ * hit whose primitive or vertices lie beyond the arrays given. */
+int twk_previous_positions_host(const float* hits, const int* instance, const int* primitive, const float* geometry, size_t numPixels, const unsigned int* indices, size_t numIndices,
+                                const float* previousPositions, size_t numPositions, const TwkInstanceMotion* motion, int numMotion, const TwkInstanceCarry* carry, int numCarry, float* plane);
+/* The merges read the plane: the Carried builds (csrc/temporal_carry_device.h temporalCarry). Per candidate pixel p,
+ * gp = previousPositions[p]; there is no history unless bits(gp.w) == bits(g.w) and gp.xyz is finite; everything after that is the
+ * existing merge — the projection of gp, the taps' position test against gp, the cap, the blend, the trust. One more coalesced
+ * 16-byte read per pixel, no table (the plane holds X g of a moved instance already); kernels of their own.
+ * OWN-BUFFER forms (twk_temporal_accumulate, twk_temporal_accumulate_rectified and the cascade merge they drive): while no geometry
+ * is deformed they do exactly what they did — the table, or nothing. While one is deformed they need a valid plane and otherwise
+ * refuse with TWK_ERROR_INVALID_STATE ("... twk_render_geometry_motion first"); with it they launch the Carried builds, and
+ * twk_read_temporal_motion then reports no table. On a tiled frame twk_temporal_accumulate_assembled[_rectified] and
+ * twk_assemble_devices_with_geometry refuse while a geometry is deformed on the primary handle (TWK_ERROR_INVALID_STATE).
+ * EXPLICIT forms: the arguments of twk_temporal_accumulate_moving / twk_temporal_accumulate_cascade_moving with previousPositions
+ * (a DEVICE pointer to width x height float4, 16-byte aligned) in place of the table; rp NULL: the plain merge (trustOut must be
+ * NULL), rp given: the rectified one; trust NULL: the cascade's plain merge, given: the trusted one. previousPositions NULL, or no
+ * history, launches the existing kernels: byte for byte the existing call. Every refusal of those calls applies; also
+ * TWK_ERROR_INVALID_VALUE: previousPositions not 16-byte aligned, an output overlapping it. */
+int twk_temporal_accumulate_carried(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalRectify* rp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                                    const void* previousPositions, int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut);
+int twk_temporal_accumulate_cascade_carried(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                            const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust,
+                                            const void* previousPositions, int width, int height, void* layersOut);
+/* Pure CPU, no device: twk_temporal_moving_host / twk_temporal_cascade_moving_host with the plane (host, four floats per pixel) in
+ * place of the table, the same headers compiled for the host. previousPositions NULL: the existing host forms. Refusals as theirs. */
+int twk_temporal_carried_host(const TwkTemporal* tp, const TwkTemporalRectify* rp, const float* colour, const float* moments, const float* geometry,
+                              const float* historyColour, const float* historyMoments, const float* historyGeometry, const TwkCameraDefinition* historyCamera,
+                              const float* previousPositions, int width, int height, float* colourOut, float* momentsOut, float* trustOut);
+int twk_temporal_cascade_carried_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                                      const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, const float* previousPositions,
+                                      int width, int height, float* layersOut);
 /* EXPLICIT form of twk_temporal_accumulate (rp NULL; trustOut must then be NULL) or of twk_temporal_accumulate_rectified (rp given),
  * with a table: motion is a DEVICE pointer to numMotion records, 16-byte aligned, indexed by instance; an instance beyond the table
  * is unmoved. motion NULL or numMotion 0 launches the existing kernels: byte for byte the existing call. Otherwise, per candidate

@@ -147,6 +147,13 @@ class InstanceMotion(C.Structure):
     _fields_ = [("previousFromCurrent", C.c_float * 12), ("moved", C.c_uint), ("reserved", C.c_uint * 3)]
 
 
+class InstanceCarry(C.Structure):
+    """≙ TwkInstanceCarry (64 bytes): one instance's record beside its InstanceMotion for the previous-position plane
+    (csrc/temporal_carry_device.h) — previousObjectToWorld, the instance's row-major 3 x 4 matrix as of the history's frame; deformed
+    (0: nothing else is read); positionBase / indexBase, where its geometry's previous positions / indices begin."""
+    _fields_ = [("previousObjectToWorld", C.c_float * 12), ("deformed", C.c_uint), ("positionBase", C.c_uint), ("indexBase", C.c_uint), ("reserved", C.c_uint)]
+
+
 class Noise(C.Structure):
     """≙ TwkNoise: parameters of twk_estimate_noise. minSamples: a pixel with fewer samples is `unknown`; darkFloor: added to the
     mean the standard error is divided by. Without arguments: twk_noise_defaults."""
@@ -324,6 +331,9 @@ SYMBOLS = [
     "twk_instance_motion", "twk_update_instance_transform", "twk_get_instance_transform", "twk_temporal_accumulate_moving", "twk_temporal_accumulate_cascade_moving",
     "twk_temporal_moving_host", "twk_temporal_cascade_moving_host", "twk_read_temporal_motion", "twk_app_get_temporal_motion",
     "twk_set_update_mode", "twk_update_instance_transforms", "twk_get_update_info", "twk_update_plan_host", "twk_app_get_selective_update",
+    "twk_update_geometry_vertices", "twk_get_geometry_deformed", "twk_vertex_update_plan_host", "twk_render_geometry_motion", "twk_get_previous_position_device_pointer",
+    "twk_read_previous_positions", "twk_previous_positions_host",
+    "twk_temporal_accumulate_carried", "twk_temporal_accumulate_cascade_carried", "twk_temporal_carried_host", "twk_temporal_cascade_carried_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",
     "twk_read_assembled_geometry", "twk_temporal_accumulate_assembled", "twk_app_get_temporal", "twk_app_get_temporal_rectify",

@@ -194,6 +194,8 @@ static int assembleDevices(const char* name, TwkDevice primary, unsigned int pla
   for (int i = 0; i < count; ++i) if (!devices[i]) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle among the devices");
   int rc = refusePrimary(name, primary, planeMask, withGeometry); if (rc) return rc;
   if (count != primary->count) return refuse(TWK_ERROR_INVALID_VALUE, "count must be the primary handle's device count");
+  if (withGeometry && geometryDeformed(primary))
+    return refuse(TWK_ERROR_INVALID_STATE, "a geometry is deformed (twk_update_geometry_vertices since the history's frame): the previous-position plane is not built on tiled frames; twk_temporal_reset first");
   std::vector<TwkDevice> byIndex((size_t) count, nullptr);
   for (int i = 0; i < count; ++i)
   {

@@ -51,9 +51,12 @@ void launchDenoiseLevel(int kind, bool lds, bool variance, const float4* in, con
                         const float4* geometry = nullptr, const DenoiseGeometryConstants* g = nullptr);
 void launchDenoiseFinish(const void* beauty, bool half, const float4* colour, const float4* guideNormal, const float4* guideAlbedo, void* denoised, const DenoiseConstants& k, hipStream_t stream);
 void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gridBlocks, hipStream_t stream);
+// temporal_carry_kernels.hip
+void launchGeometryMotion(const LaunchParams& p, float4* geometry, float4* plane, const TwkInstanceMotion* motion, unsigned int numMotion, const TwkInstanceCarry* carry,
+                          unsigned int numCarry, const float4* previousPositions, int gridBlocks, hipStream_t stream);
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream,
-                    const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
+                    const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u, const float4* carried = nullptr);
 unsigned int* launchAdaptiveSelect(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, void* scratch,
                                    const AdaptiveConstants& k, int numCUs, hipStream_t stream);
 unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int* counts, size_t numElements, unsigned int* active, unsigned int* pathOffset,
@@ -61,12 +64,12 @@ unsigned long long* launchAdaptivePlan(const float4* moments, const unsigned int
 void launchNoise(const float4* moments, size_t numElements, float* errorMap, TwkNoiseSummary* summary, const NoiseConstants& k, int numCUs, hipStream_t stream);
 void launchCascadeResolve(const CascadeConstants& k, float kappa, const float4* layers, float* lambda, int width, int height, void* resolved, bool half, hipStream_t stream);
 void launchTemporalCascade(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, float4* layersOut,
-                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
+                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u, const float4* carried = nullptr);
 void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, float4* layersOut,
-                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
+                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u, const float4* carried = nullptr);
 void launchTemporalRectify(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                            const float4* historyGeometry, float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut,
-                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
+                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u, const float4* carried = nullptr);
 void launchAssemble(const AssembleShape& s, const AssembleTable& table, int count, hipStream_t stream);
 }
 
@@ -202,6 +205,16 @@ struct TwkDevice_t
   // none — twk_read_temporal_motion) and uploads it to d_temporalMotion, grown while idle. All dropped by dropTemporal.
   std::vector<float> temporalTransforms;
   std::vector<TwkInstanceMotion> temporalMotion; DeviceArray<TwkInstanceMotion> d_temporalMotion;
+  // twk_update_geometry_vertices keeps the history too: the first update of a geometry since the history's frame keeps its positions
+  // as of that frame (previousPositions[geometry], one float4 per vertex; empty: not deformed), until a merge swaps the history or
+  // dropTemporal drops it. twk_render_geometry_motion (temporal_carry_device.h) uploads them packed (d_previousPositions) with the two
+  // records per instance and writes the previous-position plane beside the geometry AOV; previousPlaneValid goes with geometryValid.
+  std::vector<std::vector<float4>> previousPositions;
+  DeviceArray<float4> d_previousPositions, d_previousPlane; DeviceArray<TwkInstanceMotion> d_carryMotion; DeviceArray<TwkInstanceCarry> d_carry;
+  bool previousPlaneValid = false;
+  // what d_carryMotion and d_carry hold, and whether d_previousPositions holds previousPositions as they are: the uploads and the wait
+  // after them are skipped while nothing has changed since the last plane
+  std::vector<TwkInstanceMotion> carryMotionUploaded; std::vector<TwkInstanceCarry> carryUploaded; bool previousPositionsUploaded = false;
   // twk_temporal_accumulate_rectified (temporal_rectify_device.h): the two scratch streams its first launch writes and its second
   // reads, shared by the explicit and the own-buffer form; and the own-buffer form's trust plane, one
   // float per pixel of the temporal result, valid while the last own-buffer merge was a rectified one. Freed by dropTemporal.
@@ -304,7 +317,14 @@ struct TwkDevice_t
 };
 
 // The camera, the state or the scene changed: the handle's geometry AOV and the geometry it assembled as a primary are of the old one
-inline void staleGeometry(TwkDevice dev) { dev->geometryValid = false; dev->assembledGeometryValid = false; }
+inline void staleGeometry(TwkDevice dev) { dev->geometryValid = false; dev->assembledGeometryValid = false; dev->previousPlaneValid = false; }
+
+// Whether the handle holds previous positions of some geometry (twk_update_geometry_vertices since the history's frame)
+inline bool geometryDeformed(TwkDevice dev)
+{
+  for (const std::vector<float4>& kept : dev->previousPositions) if (!kept.empty()) return true;
+  return false;
+}
 
 // Bytes of one output / AOV pixel in the handle's output format: RGBA32F 16, RGBA16F 8 (Optix7Gui Half4)
 inline size_t pixelBytes(int format) { return (format == TWK_OUTPUT_HALF4) ? 8 : sizeof(float4); }
@@ -394,6 +414,10 @@ int copyBack(TwkDevice dev, const char* name, const void* source, size_t count, 
 int readBack(TwkDevice dev, const char* name, const Readback& r, void* host, size_t given, size_t unit, const char* sizeText, bool dropped = false);
 // device_temporal.hip
 void dropTemporal(TwkDevice dev);
+// device_temporal_carry.hip
+void keepPreviousPositions(TwkDevice dev, int idGeometry);
+void dropPreviousPositions(TwkDevice dev, bool release);
+// device_temporal.hip
 int temporalParameters(const char* name, const TwkTemporal* tp, TemporalConstants& k);
 int temporalHistoryCamera(const char* name, const TwkCameraDefinition& camera, TemporalConstants& k);
 // device_cascade.hip
@@ -402,7 +426,7 @@ CascadeOn cascadeFold(TwkDevice dev);
 void dropTemporalCascade(TwkDevice dev);
 const char* temporalCascadeRefusal(TwkDevice dev);
 int temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust = nullptr,
-                       const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u);
+                       const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u, const float4* carried = nullptr);
 // device_assemble.hip
 void dropAssembled(TwkDevice dev);
 }

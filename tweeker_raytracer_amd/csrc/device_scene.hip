@@ -485,7 +485,10 @@ static void recordUpdate(TwkDevice dev, bool selective, int moved, int trees, bo
 // the transforms of the instances `moved` (distinct) have been replaced. It runs buildScene's stages (above) for what the plan names,
 // on arrays that hold what buildScene's held at that point — so the result is a fresh build's, byte for byte. A failure leaves the
 // handle unbuilt (twk_build recovers it).
-static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
+// updated: geometries (distinct) whose attributes have been replaced on the host, numUpdated of them — a vertex update
+// (twk_update_geometry_vertices): their slices of d_attributes are uploaded, the bottom-level tree of an entered one is rebuilt at the
+// node and slot range it has, and the trees and boxes of their instances follow (update_plan.h updatePlanWith).
+static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0)
 {
   int rc;
   SceneState& state = dev->kept;
@@ -499,7 +502,7 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
   std::vector<int> instanceGeometry, geometryTriangles;
   layoutInputs(dev, instanceGeometry, geometryTriangles);
   UpdatePlan plan;
-  updatePlan(layout, instanceGeometry.data(), geometryTriangles.data(), moved, numMoved, plan);
+  updatePlanWith(layout, instanceGeometry.data(), geometryTriangles.data(), moved, numMoved, updated, numUpdated, plan);
   const size_t numNodes = layout.numNodes, numTris = layout.numTriangles;
 
   // the records of the moved instances only (the new object-to-world matrix and its inverse); they live until the first synchronise
@@ -514,6 +517,24 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
   // pair flags, and what a tree leaves unused of its range must stay zero
   NodeCostScope nodeCostScope{dev->builder};
   dev->builder.setNodeCost(dev->d_nodeCost);
+  // the new vertices, and the bottom-level tree of every updated geometry that is entered: buildScene's call on the range it has
+  for (int k = 0; k < numUpdated; ++k)
+  {
+    const GeometryHost& g = dev->geometries[updated[k]];
+    HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
+  }
+  for (int k : plan.geometries)
+  {
+    GeometryHost& g = dev->geometries[k];
+    const int nodes = treeNodes(g.numTriangles);
+    HIP_TRY(hipMemsetAsync(dev->d_nodes + g.nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
+    HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) g.nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
+    if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + g.triangleBase, 0, sizeof(int) * (size_t) g.numTriangles, dev->stream));
+    HIP_TRY(dev->builder.buildTriangles(dev->stream, dev->d_attributes + 12 * (size_t) g.attributeBase, dev->d_indices + g.indexBase, g.numTriangles,
+                                        dev->d_nodes + g.nodeBase, dev->d_wideNodes + 2 * (size_t) g.nodeBase, g.nodeBase, dev->d_triangles, dev->d_shadeTriangles, g.triangleBase, g.rootBounds,
+                                        nullptr, nullptr, state.pairs ? state.primFirst[k].data() : nullptr, (int) state.primFirst[k].size(), dev->d_pairFlags));
+    state.geometryTerms[k] = lastTerms(dev->builder);
+  }
   int maxTriangles = 0;
   for (int i : plan.trees) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
   if (maxTriangles > 0 && (rc = dev->d_updateSoup.ensure((size_t) maxTriangles))) return rc;
@@ -530,6 +551,8 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
   for (int k = 0; k < numMoved; ++k)
     if (!layout.flattened[moved[k]])
       enteredWorldBox(dev->geometries[dev->instances[moved[k]].geometry].rootBounds, dev->instances[moved[k]].transform, state.boxLo[moved[k]], state.boxHi[moved[k]]);
+  // an entered instance of an updated geometry: the new root box through its transform
+  for (int i : plan.boxes) enteredWorldBox(dev->geometries[dev->instances[i].geometry].rootBounds, dev->instances[i].transform, state.boxLo[i], state.boxHi[i]);
 
   // the top level over the kept and the new boxes; the depth, from the kept and the new heights
   int traversalDepth = 0;
@@ -551,7 +574,7 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved)
 
   // the build info: counts, pair leaves, quality — no transform changes them — and what the changed trees change
   finishBuild(dev, state, dev->buildInfo, traversalDepth, start);
-  recordUpdate(dev, true, numMoved, (int) plan.trees.size(), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
+  recordUpdate(dev, true, numMoved, (int) (plan.geometries.size() + plan.trees.size()), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
   return TWK_SUCCESS;
 }
 
@@ -587,7 +610,90 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   return TWK_SUCCESS;
 }
 
+// The body of twk_update_plan_host (no updated geometry) and of twk_vertex_update_plan_host
+static int updatePlanHost(const char* name, const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                          int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updated, int numUpdated,
+                          TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges)
+{
+  const auto refuse = [name](const std::string& text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  if (!instanceGeometry || !geometryTriangles || !plan || (numMoved > 0 && !moved) || (numUpdated > 0 && !updated)) return refuse("NULL argument");
+  if (numInstances < 1 || numGeometries < 1 || numMoved < 0 || numUpdated < 0 || flattenMaxTriangles < 0 || flattenMaxReferences < 0) return refuse("counts must be at least 1 and limits at least 0");
+  for (int k = 0; k < numGeometries; ++k) if (geometryTriangles[k] < 1) return refuse("geometry " + std::to_string(k) + " has no triangle");
+  for (int i = 0; i < numInstances; ++i) if (instanceGeometry[i] < 0 || instanceGeometry[i] >= numGeometries) return refuse("instance " + std::to_string(i) + ": bad geometry index");
+  for (int k = 0; k < numMoved; ++k)
+  {
+    if (moved[k] < 0 || moved[k] >= numInstances) return refuse("entry " + std::to_string(k) + ": bad instance id");
+    for (int j = 0; j < k; ++j) if (moved[j] == moved[k]) return refuse("entry " + std::to_string(k) + ": instance " + std::to_string(moved[k]) + " is listed twice");
+  }
+  for (int k = 0; k < numUpdated; ++k)
+  {
+    if (updated[k] < 0 || updated[k] >= numGeometries) return refuse("updated entry " + std::to_string(k) + ": bad geometry id");
+    for (int j = 0; j < k; ++j) if (updated[j] == updated[k]) return refuse("updated entry " + std::to_string(k) + ": geometry " + std::to_string(updated[k]) + " is listed twice");
+  }
+  SceneLayout layout;
+  sceneLayout(instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, std::max(1, std::min(4, maxLeaf)) /* BvhBuilder::setMaxLeaf */, true, layout);
+  UpdatePlan p;
+  updatePlanWith(layout, instanceGeometry, geometryTriangles, moved, numMoved, updated, numUpdated, p);
+  memset(plan, 0, sizeof(*plan));
+  plan->instances = numInstances; plan->flattenedInstances = numInstances - layout.numEntered; plan->tlasBase = layout.tlasBase;
+  for (int i = 0; i < numInstances; ++i) plan->directLeafInstances += layout.directLeaf[i] ? 1 : 0;
+  for (int k = 0; k < numGeometries; ++k) plan->enteredGeometries += layout.needsBlas[k] ? 1 : 0;
+  plan->nodes = layout.numNodes; plan->triangleSlots = layout.numTriangles;
+  if (numMoved > 0 || numUpdated > 0)
+  {
+    plan->treesRebuilt = (int) (p.geometries.size() + p.trees.size()); plan->topLevelRebuilt = p.topLevel ? 1 : 0; plan->numRanges = (int) p.ranges.size();
+    plan->nodesRequantised = p.totalNodes; plan->slotsRewritten = p.totalSlots;
+    // a rebuilt bottom-level tree is listed as ~geometry, before the flattened instances
+    if (trees) for (size_t k = 0; k < p.geometries.size(); ++k) trees[k] = ~p.geometries[k];
+    if (trees) for (size_t k = 0; k < p.trees.size(); ++k) trees[p.geometries.size() + k] = p.trees[k];
+    if (ranges) for (size_t k = 0; k < p.ranges.size(); ++k) { ranges[2 * k] = p.ranges[k].first; ranges[2 * k + 1] = p.ranges[k].count; }
+  }
+  if (flattened) for (int i = 0; i < numInstances; ++i) flattened[i] = layout.flattened[i] ? 1 : 0;
+  return TWK_SUCCESS;
+}
+
 extern "C" {
+
+int twk_update_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
+try
+{
+  const char* name = "twk_update_geometry_vertices";
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  if (!attributes) return refuse(TWK_ERROR_INVALID_VALUE, "NULL attributes");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  if (idGeometry < 0 || idGeometry >= (int) dev->geometries.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad geometry id");
+  GeometryHost& g = dev->geometries[idGeometry];
+  if (numAttributes != g.attributes.size())
+    return refuse(TWK_ERROR_INVALID_VALUE, "the geometry has " + std::to_string(g.attributes.size()) + " vertices, not " + std::to_string(numAttributes) + " (the indices stay: no topology change)");
+  for (size_t v = 0; v < numAttributes; ++v)
+    if (!std::isfinite(attributes[v].vertex[0]) || !std::isfinite(attributes[v].vertex[1]) || !std::isfinite(attributes[v].vertex[2]))
+      return refuse(TWK_ERROR_INVALID_VALUE, "vertex " + std::to_string(v) + ": the position is not finite");
+  for (size_t i = 0; i < dev->instances.size(); ++i)
+    if (dev->instances[i].geometry == idGeometry && dev->instances[i].light >= 0)
+      return refuse(TWK_ERROR_INVALID_VALUE, "instance " + std::to_string(i) + " of the geometry carries a light (idLight >= 0): its light definition holds the emitter's shape and would disagree; deforming emitters is not supported");
+  // nothing was changed up to here: a refused call changes nothing
+  keepPreviousPositions(dev, idGeometry); // the positions as of the history's frame, before the first update since (device_temporal.hip)
+  g.attributes.assign(attributes, attributes + numAttributes);
+  dev->updateInfoValid = false;
+  // the temporal history stays: the merges look it up where the surface was (twk_render_geometry_motion, temporal_carry_device.h)
+  if (dev->kept.valid) return updateSelective(dev, nullptr, 0, &idGeometry, 1);
+  if ((rc = buildScene(dev, false))) return rc;
+  recordUpdate(dev, false, 0, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, 0);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_update_geometry_vertices")
+
+int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                                int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,
+                                TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges)
+try
+{
+  return updatePlanHost("twk_vertex_update_plan_host", instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, maxLeaf,
+                        moved, numMoved, updatedGeometries, numUpdated, plan, flattened, trees, ranges);
+}
+TWK_CATCH("twk_vertex_update_plan_host")
 
 int twk_update_instance_transform(TwkDevice dev, int idInstance, const float transform[12])
 try
@@ -627,35 +733,8 @@ int twk_update_plan_host(const int* instanceGeometry, int numInstances, const in
                          int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges)
 try
 {
-  const char* name = "twk_update_plan_host";
-  const auto refuse = [name](const std::string& text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
-  if (!instanceGeometry || !geometryTriangles || !plan || (numMoved > 0 && !moved)) return refuse("NULL argument");
-  if (numInstances < 1 || numGeometries < 1 || numMoved < 0 || flattenMaxTriangles < 0 || flattenMaxReferences < 0) return refuse("counts must be at least 1 and limits at least 0");
-  for (int k = 0; k < numGeometries; ++k) if (geometryTriangles[k] < 1) return refuse("geometry " + std::to_string(k) + " has no triangle");
-  for (int i = 0; i < numInstances; ++i) if (instanceGeometry[i] < 0 || instanceGeometry[i] >= numGeometries) return refuse("instance " + std::to_string(i) + ": bad geometry index");
-  for (int k = 0; k < numMoved; ++k)
-  {
-    if (moved[k] < 0 || moved[k] >= numInstances) return refuse("entry " + std::to_string(k) + ": bad instance id");
-    for (int j = 0; j < k; ++j) if (moved[j] == moved[k]) return refuse("entry " + std::to_string(k) + ": instance " + std::to_string(moved[k]) + " is listed twice");
-  }
-  SceneLayout layout;
-  sceneLayout(instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, std::max(1, std::min(4, maxLeaf)) /* BvhBuilder::setMaxLeaf */, true, layout);
-  UpdatePlan p;
-  updatePlan(layout, instanceGeometry, geometryTriangles, moved, numMoved, p);
-  memset(plan, 0, sizeof(*plan));
-  plan->instances = numInstances; plan->flattenedInstances = numInstances - layout.numEntered; plan->tlasBase = layout.tlasBase;
-  for (int i = 0; i < numInstances; ++i) plan->directLeafInstances += layout.directLeaf[i] ? 1 : 0;
-  for (int k = 0; k < numGeometries; ++k) plan->enteredGeometries += layout.needsBlas[k] ? 1 : 0;
-  plan->nodes = layout.numNodes; plan->triangleSlots = layout.numTriangles;
-  if (numMoved > 0)
-  {
-    plan->treesRebuilt = (int) p.trees.size(); plan->topLevelRebuilt = p.topLevel ? 1 : 0; plan->numRanges = (int) p.ranges.size();
-    plan->nodesRequantised = p.totalNodes; plan->slotsRewritten = p.totalSlots;
-    if (trees) for (size_t k = 0; k < p.trees.size(); ++k) trees[k] = p.trees[k];
-    if (ranges) for (size_t k = 0; k < p.ranges.size(); ++k) { ranges[2 * k] = p.ranges[k].first; ranges[2 * k + 1] = p.ranges[k].count; }
-  }
-  if (flattened) for (int i = 0; i < numInstances; ++i) flattened[i] = layout.flattened[i] ? 1 : 0;
-  return TWK_SUCCESS;
+  return updatePlanHost("twk_update_plan_host", instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, maxLeaf,
+                        moved, numMoved, nullptr, 0, plan, flattened, trees, ranges);
 }
 TWK_CATCH("twk_update_plan_host")
 

@@ -18,6 +18,7 @@ void twk::dropTemporal(TwkDevice dev)
   dev->d_temporalTrust.release();
   dev->temporalTrustValid = false; dev->temporalHasHistory = false;
   dev->d_temporalMotion.release(); dev->temporalMotion.clear(); dev->temporalTransforms.clear();
+  dropPreviousPositions(dev, true);
   dropTemporalCascade(dev); // the merged layers of twk_temporal_enable_cascade are history of the same frames
 }
 
@@ -133,7 +134,11 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
   const int keep = dev->temporalHasHistory ? 1 - dev->temporalKept : dev->temporalKept;
   k.width = width; k.height = height;
   if (dev->temporalHasHistory && (rc = temporalHistoryCamera(name, dev->temporalCamera, k))) return rc;
-  if ((rc = ownMotion(dev, name))) return rc;
+  // while a geometry is deformed the Carried builds run: g' from the previous-position plane (temporal_carry_device.h), which holds
+  // X g of a moved instance already, so no table is built; the callers have refused a deformed geometry without a valid plane
+  const float4* carried = (dev->temporalHasHistory && geometryDeformed(dev)) ? dev->d_previousPlane.get() : nullptr;
+  if (carried) dev->temporalMotion.clear();
+  else if ((rc = ownMotion(dev, name))) return rc;
   const TwkInstanceMotion* motion = dev->temporalMotion.empty() ? nullptr : dev->d_temporalMotion.get();
   const unsigned int numMotion = (unsigned int) dev->temporalMotion.size();
   // twk_temporal_enable_cascade: the layers through the same previous geometry and camera, before the history is swapped
@@ -143,16 +148,16 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
     if ((rc = ensureRectifyScratch(dev, n))) return rc;
     if ((rc = dev->d_temporalTrust.ensure(n))) return rc;
     launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], dev->temporalColour.pixels,
-                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream, motion, numMotion);
+                          dev->d_temporal[keep][0], dev->d_temporal[keep][1], dev->d_temporalTrust, k, *rectify, dev->stream, motion, numMotion, carried);
     HIP_TRY(hipGetLastError());
-    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust, motion, numMotion))) return rc;
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, dev->d_temporalTrust, motion, numMotion, carried))) return rc;
     dev->temporalTrustValid = true;
   }
   else
   {
-    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, nullptr, motion, numMotion))) return rc;
+    if (dev->temporalCascade && (rc = temporalCascadeOwn(dev, k, layers, geometry, hGeometry, nullptr, motion, numMotion, carried))) return rc;
     launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->temporalColour.pixels, dev->d_temporal[keep][0], dev->d_temporal[keep][1], k, dev->stream,
-                   motion, numMotion);
+                   motion, numMotion, carried);
     HIP_TRY(hipGetLastError());
     dev->temporalTrustValid = false; // the trust plane, if any, is an earlier frame's
   }
@@ -160,6 +165,7 @@ static int temporalOwn(TwkDevice dev, const char* name, TemporalConstants k, con
   dev->temporalKept = keep; dev->temporalCamera = dev->cameras[0]; dev->temporalHasHistory = true; dev->temporalColour.valid = true;
   dev->temporalTransforms.resize(12 * dev->instances.size()); // the history now is this frame: its instances are where they are
   for (size_t i = 0; i < dev->instances.size(); ++i) memcpy(&dev->temporalTransforms[12 * i], dev->instances[i].transform, 12 * sizeof(float));
+  dropPreviousPositions(dev, false); // ... and its vertices are where they are: no geometry is deformed, the plane describes the history that was
   return TWK_SUCCESS;
 }
 
@@ -178,6 +184,8 @@ static int temporalOwnFrame(TwkDevice dev, const char* name, const TemporalConst
   const void* colour = ownOutput(dev, n);
   if (!colour) return refuse(TWK_ERROR_INVALID_STATE, "nothing has been rendered");
   if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
+  if (dev->temporalHasHistory && geometryDeformed(dev) && !(dev->previousPlaneValid && dev->d_previousPlane.holds(n)))
+    return refuse(TWK_ERROR_INVALID_STATE, "a geometry is deformed (twk_update_geometry_vertices since the history's frame) and there is no valid previous-position plane: twk_render_geometry_motion first");
   return temporalOwn(dev, name, k, rectify, colour, dev->d_moments, dev->d_geometry, nullptr, width, height);
 }
 
@@ -188,6 +196,7 @@ static int temporalAssembledFrame(TwkDevice dev, const char* name, const Tempora
   if (!dev->stateSet || dev->cameras.empty()) return refuse(TWK_ERROR_INVALID_STATE, "twk_set_state and twk_init_cameras first");
   if (!(dev->state.distribution && 1 < dev->count))
     return refuse(TWK_ERROR_INVALID_STATE, "the handle is not tiled (distribution 1, more than one device): its own buffers are the picture, twk_temporal_accumulate merges them");
+  if (geometryDeformed(dev)) return refuse(TWK_ERROR_INVALID_STATE, "a geometry is deformed (twk_update_geometry_vertices since the history's frame): the previous-position plane is not built on tiled frames; twk_temporal_reset first");
   if (!dev->momentsEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no luminance moments: render with twk_enable_moments(1)");
   if (!dev->geometryEnabled) return refuse(TWK_ERROR_INVALID_STATE, "the frame has no geometry AOV: twk_enable_geometry(1) and twk_render_geometry_tile");
   if (dev->temporalCascade) if (const char* why = temporalCascadeRefusal(dev)) return refuse(TWK_ERROR_INVALID_STATE, why);
@@ -206,7 +215,8 @@ static int temporalAssembledFrame(TwkDevice dev, const char* name, const Tempora
 // on an active handle: without a current frame the own-buffer form, else the explicit form's refusals and its launch. motion,
 // numMotion: the table of twk_temporal_accumulate_moving (a device pointer; nullptr or 0: none, the launches of the other two).
 static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, const RectifyConstants* rectify, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
-                         int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0)
+                         int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0,
+                         const void* previousPositions = nullptr)
 {
   const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
   if (!current)
@@ -234,6 +244,10 @@ static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, c
   if (numMotion > 0 && ((uintptr_t) motion & 15u) != 0) return refuse("the motion table is not 16-byte aligned");
   for (int o = 0; o < 4 && numMotion > 0; ++o)
     if (overlaps(outs[o], outBytes[o], motion, (size_t) numMotion * sizeof(TwkInstanceMotion))) return refuse("an output overlaps the motion table");
+  // the previous-position plane of a Carried build (twk_temporal_accumulate_carried); without a history nothing is reprojected
+  const float4* carried = history ? static_cast<const float4*>(previousPositions) : nullptr;
+  if (carried && ((uintptr_t) carried & 15u) != 0) return refuse("the previous positions are not 16-byte aligned");
+  for (int o = 0; o < 4 && carried; ++o) if (overlaps(outs[o], outBytes[o], carried, wide)) return refuse("an output overlaps the previous positions");
   k.width = width; k.height = height;
   int rc;
   if (history && (rc = temporalHistoryCamera(name, history->camera, k))) return rc;
@@ -241,11 +255,11 @@ static int temporalFrame(TwkDevice dev, const char* name, TemporalConstants k, c
   {
     if ((rc = ensureRectifyScratch(dev, n))) return rc;
     launchTemporalRectify(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, dev->d_rectify[0], dev->d_rectify[1], colourOut, static_cast<float4*>(historyOut),
-                          static_cast<float4*>(momentsOut), static_cast<float*>(trustOut), k, *rectify, dev->stream, motion, (unsigned int) numMotion);
+                          static_cast<float4*>(momentsOut), static_cast<float*>(trustOut), k, *rectify, dev->stream, motion, (unsigned int) numMotion, carried);
   }
   else
     launchTemporal(colour, halfOutput(dev), moments, geometry, hColour, hMoments, hGeometry, colourOut, static_cast<float4*>(historyOut), static_cast<float4*>(momentsOut), k, dev->stream,
-                   motion, (unsigned int) numMotion);
+                   motion, (unsigned int) numMotion, carried);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
@@ -315,6 +329,22 @@ try
   return temporalFrame(dev, name, k, rp ? &r : nullptr, current, history, width, height, colourOut, historyOut, momentsOut, trustOut, motion, numMotion);
 }
 TWK_CATCH("twk_temporal_accumulate_moving")
+
+int twk_temporal_accumulate_carried(TwkDevice dev, const TwkTemporal* tp, const TwkTemporalRectify* rp, const TwkTemporalFrame* current, const TwkTemporalFrame* history,
+                                    const void* previousPositions, int width, int height, void* colourOut, void* historyOut, void* momentsOut, void* trustOut)
+try
+{
+  const char* name = "twk_temporal_accumulate_carried";
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  int rc = activate(dev, name); if (rc) return rc;
+  TemporalConstants k;
+  RectifyConstants r;
+  if ((rc = rp ? rectifyParameters(name, tp, rp, k, r) : temporalParameters(name, tp, k))) return rc;
+  if (!current) return refuse("NULL current frame (the explicit form only: twk_temporal_accumulate's own-buffer form reads the handle's plane itself)");
+  if (!rp && trustOut) return refuse("a trustOut without TwkTemporalRectify (rp NULL is the plain merge)");
+  return temporalFrame(dev, name, k, rp ? &r : nullptr, current, history, width, height, colourOut, historyOut, momentsOut, trustOut, nullptr, 0, previousPositions);
+}
+TWK_CATCH("twk_temporal_accumulate_carried")
 
 int twk_read_temporal_motion(TwkDevice dev, TwkInstanceMotion* host, size_t capacity, int* count)
 try
@@ -472,5 +502,28 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_temporal_moving_host")
+
+int twk_temporal_carried_host(const TwkTemporal* tp, const TwkTemporalRectify* rp, const float* colour, const float* moments, const float* geometry,
+                              const float* historyColour, const float* historyMoments, const float* historyGeometry, const TwkCameraDefinition* historyCamera,
+                              const float* previousPositions, int width, int height, float* colourOut, float* momentsOut, float* trustOut)
+try
+{
+  const char* name = "twk_temporal_carried_host";
+  const auto refuse = [name](const char* text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  if (!colour || !moments || !geometry) return refuse("NULL buffer in the current frame");
+  const bool history = historyColour || historyMoments || historyGeometry;
+  if (history && (!historyColour || !historyMoments || !historyGeometry || !historyCamera)) return refuse("a history without its colour, moments, geometry or camera");
+  if (!rp && trustOut) return refuse("a trustOut without TwkTemporalRectify (rp NULL is the plain merge)");
+  TemporalConstants k;
+  RectifyConstants r;
+  int rc = rp ? rectifyParameters(name, tp, rp, k, r) : temporalParameters(name, tp, k); if (rc) return rc;
+  if (width < 1 || height < 1 || (size_t) width * (size_t) height > ((size_t) 1 << 28)) return refuse("width and height must be >= 1, width*height at most 2^28");
+  k.width = width; k.height = height;
+  if (history && (rc = temporalHistoryCamera(name, *historyCamera, k))) return rc;
+  const TemporalHostFrame frame((size_t) width * height, colour, moments, geometry, historyColour, historyMoments, historyGeometry);
+  temporalMergeHost(k, rp ? &r : nullptr, frame, nullptr, 0u, colourOut, momentsOut, trustOut, history ? previousPositions : nullptr);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_temporal_carried_host")
 
 } // extern "C"

@@ -29,7 +29,7 @@ const char* twk::temporalCascadeRefusal(TwkDevice dev)
 // trust: nullptr = the plain merge; else the trust plane of the rectified merge of the same frame, already written on the stream.
 // motion, numMotion: the table that merge uses (a device pointer; nullptr or 0: none).
 int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const float4* layers, const float4* geometry, const float4* historyGeometry, const float* trust,
-                            const TwkInstanceMotion* motion, unsigned int numMotion)
+                            const TwkInstanceMotion* motion, unsigned int numMotion, const float4* carried)
 {
   int rc = ensureStreams(dev); if (rc) return rc;
   const size_t n = (size_t) k.width * k.height;
@@ -53,10 +53,10 @@ int twk::temporalCascadeOwn(TwkDevice dev, const TemporalConstants& k, const flo
   kc.hasHistory = history ? 1 : 0;
   if (trust)
     launchTemporalCascadeTrusted(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr, trust,
-                                 dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream, motion, numMotion);
+                                 dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream, motion, numMotion, history ? carried : nullptr);
   else
     launchTemporalCascade(layers, geometry, history ? dev->d_temporalCascade[dev->temporalCascadeKept] : nullptr, history ? historyGeometry : nullptr,
-                          dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream, motion, numMotion);
+                          dev->d_temporalCascade[keep], kc, dev->cascadeK, dev->stream, motion, numMotion, history ? carried : nullptr);
   HIP_TRY(hipGetLastError());
   dev->temporalCascadeKept = keep; dev->temporalCascadeHasHistory = true; dev->temporalCascadeValid = true;
   return TWK_SUCCESS;
@@ -81,7 +81,7 @@ static int temporalCascadeParameters(const char* name, const TwkTemporal* tp, co
 // whose table (motion, numMotion; nullptr or 0: none) is checked here; the others pass none.
 static int temporalCascadeExplicit(const char* name, bool trusted, TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
                                    const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust, int width, int height,
-                                   void* layersOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0)
+                                   void* layersOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0, const void* previousPositions = nullptr)
 {
   const auto refuse = [name](int code, const char* text) { return twkSetError(code, std::string(name) + ": " + text); };
   if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
@@ -100,14 +100,18 @@ static int temporalCascadeExplicit(const char* name, bool trusted, TwkDevice dev
   if (!motion || !historyLayers) numMotion = 0; // (without a history nothing is reprojected)
   if (numMotion > 0 && ((uintptr_t) motion & 15u) != 0) return refuse(TWK_ERROR_INVALID_VALUE, "the motion table is not 16-byte aligned");
   if (numMotion > 0 && overlaps(layersOut, layerBytes, motion, (size_t) numMotion * sizeof(TwkInstanceMotion))) return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps the motion table");
+  // the previous-position plane of a Carried build (twk_temporal_accumulate_cascade_carried); without a history nothing is reprojected
+  const float4* carried = historyLayers ? static_cast<const float4*>(previousPositions) : nullptr;
+  if (carried && ((uintptr_t) carried & 15u) != 0) return refuse(TWK_ERROR_INVALID_VALUE, "the previous positions are not 16-byte aligned");
+  if (carried && overlaps(layersOut, layerBytes, carried, plane)) return refuse(TWK_ERROR_INVALID_VALUE, "the output overlaps the previous positions");
   if ((rc = activate(dev, name))) return rc;
   if (trusted)
     launchTemporalCascadeTrusted(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
                                  historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<const float*>(trust), static_cast<float4*>(layersOut), k, c, dev->stream,
-                                 motion, (unsigned int) numMotion);
+                                 motion, (unsigned int) numMotion, carried);
   else
     launchTemporalCascade(static_cast<const float4*>(currentLayers), static_cast<const float4*>(currentGeometry), static_cast<const float4*>(historyLayers),
-                          historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream, motion, (unsigned int) numMotion);
+                          historyLayers ? static_cast<const float4*>(historyGeometry) : nullptr, static_cast<float4*>(layersOut), k, c, dev->stream, motion, (unsigned int) numMotion, carried);
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
 }
@@ -115,7 +119,7 @@ static int temporalCascadeExplicit(const char* name, bool trusted, TwkDevice dev
 // The host-only form, plain and trusted, with a table (twk_temporal_cascade_moving_host; a host array) or without
 static int temporalCascadeHost(const char* name, bool trusted, const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry,
                                const float* historyLayers, const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, int width, int height,
-                               float* layersOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0)
+                               float* layersOut, const TwkInstanceMotion* motion = nullptr, int numMotion = 0, const float* previousPositions = nullptr)
 {
   if (!currentLayers || !currentGeometry || !layersOut) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL current layers, current geometry or output");
   if (historyLayers && (!historyGeometry || !historyCamera)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": history layers without the history's geometry or camera");
@@ -124,7 +128,8 @@ static int temporalCascadeHost(const char* name, bool trusted, const TwkTemporal
   TemporalConstants k;
   CascadeConstants c;
   int rc = temporalCascadeParameters(name, tp, cp, historyLayers != nullptr, historyCamera, width, height, k, c); if (rc) return rc;
-  temporalCascadeHostLayers(k, c, currentLayers, currentGeometry, historyLayers, historyGeometry, trusted ? trust : nullptr, motion, motion ? (unsigned int) numMotion : 0u, layersOut);
+  temporalCascadeHostLayers(k, c, currentLayers, currentGeometry, historyLayers, historyGeometry, trusted ? trust : nullptr, motion, motion ? (unsigned int) numMotion : 0u, layersOut,
+                            historyLayers ? previousPositions : nullptr);
   return TWK_SUCCESS;
 }
 
@@ -156,6 +161,16 @@ try
                                  width, height, layersOut, motion, numMotion);
 }
 TWK_CATCH("twk_temporal_accumulate_cascade_moving")
+
+int twk_temporal_accumulate_cascade_carried(TwkDevice dev, const TwkTemporal* tp, const TwkCascade* cp, const void* currentLayers, const void* currentGeometry,
+                                            const void* historyLayers, const void* historyGeometry, const TwkCameraDefinition* historyCamera, const void* trust,
+                                            const void* previousPositions, int width, int height, void* layersOut)
+try
+{
+  return temporalCascadeExplicit("twk_temporal_accumulate_cascade_carried", trust != nullptr, dev, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust,
+                                 width, height, layersOut, nullptr, 0, previousPositions);
+}
+TWK_CATCH("twk_temporal_accumulate_cascade_carried")
 
 int twk_temporal_enable_cascade(TwkDevice dev, int enable)
 try
@@ -223,5 +238,15 @@ try
                              layersOut, motion, numMotion);
 }
 TWK_CATCH("twk_temporal_cascade_moving_host")
+
+int twk_temporal_cascade_carried_host(const TwkTemporal* tp, const TwkCascade* cp, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
+                                      const float* historyGeometry, const TwkCameraDefinition* historyCamera, const float* trust, const float* previousPositions,
+                                      int width, int height, float* layersOut)
+try
+{
+  return temporalCascadeHost("twk_temporal_cascade_carried_host", trust != nullptr, tp, cp, currentLayers, currentGeometry, historyLayers, historyGeometry, historyCamera, trust, width, height,
+                             layersOut, nullptr, 0, previousPositions);
+}
+TWK_CATCH("twk_temporal_cascade_carried_host")
 
 } // extern "C"

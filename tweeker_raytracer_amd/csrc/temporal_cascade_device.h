@@ -59,10 +59,12 @@ namespace twk {
 // Trusted: the build that discounts the capped history by trust[p] (above); otherwise trust is not read.
 // Moving: the build that carries g to where its instance was in the history's frame before the projection and the taps' test
 // (temporal_motion_device.h temporalMove, with the table motion[numMotion]; g' not finite: no history); otherwise the table is not read.
-template<bool Trusted = false, bool Moving = false>
+// Carried: the build that takes g' from the previous-position plane instead (temporal_carry_device.h temporalCarry on plane[p]: no
+// history unless its instance word is g's and it is finite); otherwise the plane is not read.
+template<bool Trusted = false, bool Moving = false, bool Carried = false>
 TWK_HD void temporalCascadePixel(const TemporalConstants& k, const CascadeConstants& c, const float4* Lc, const float4* geometry, const float4* H,
                                  const float4* hGeometry, const size_t stride, const size_t p, float4* out, const float* trust = nullptr,
-                                 const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u)
+                                 const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u, const float4* plane = nullptr)
 {
   const int K = c.layers;
   const size_t top = (size_t) (K - 1) * stride;
@@ -79,7 +81,8 @@ TWK_CASCADE_UNROLL
     const float4 g = geometry[p];
     float4 gp = g;
     float fx = 0.0f, fy = 0.0f, vv = 0.0f;
-    if (asUint(g.w) != 0u && finite3(g) && cascadeFinite(nc) && !(nc < 1.0f) && (!Moving || temporalMove(motion, numMotion, g, gp)) && temporalProject(k, gp, fx, fy, vv))
+    if (asUint(g.w) != 0u && finite3(g) && cascadeFinite(nc) && !(nc < 1.0f) && (!Moving || temporalMove(motion, numMotion, g, gp)) &&
+        (!Carried || temporalCarry(plane[p], g, gp)) && temporalProject(k, gp, fx, fy, vv))
     {
       const TemporalFootprint f = temporalFootprint(fx, fy);
       q00 = (long long) f.y0 * k.width + f.x0;

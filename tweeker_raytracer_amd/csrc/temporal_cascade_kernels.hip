@@ -49,6 +49,28 @@ __global__ void __launch_bounds__(256) temporalCascadeMovingKernel(const float4*
   temporalCascadePixel<Trusted, true>(k, c, layers, geometry, historyLayers, historyGeometry, numPixels, p, layersOut, trust, table, numMotion);
 }
 
+// The Carried builds (temporal_carry_device.h): the same thread per pixel, plus one coalesced 16-byte read of the previous-position
+// plane where the pixel is a candidate; no table. Kernels of their own, so that the ones above are the code they were.
+template<bool Trusted>
+__global__ void __launch_bounds__(256) temporalCascadeCarriedKernel(const float4* __restrict__ layers, const float4* __restrict__ geometry, const float4* __restrict__ historyLayers,
+                                                                    const float4* __restrict__ historyGeometry, const float* __restrict__ trust, const float4* __restrict__ plane,
+                                                                    float4* __restrict__ layersOut, TemporalConstants k, CascadeConstants c)
+{
+  const size_t numPixels = (size_t) k.width * k.height;
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= numPixels) return;
+  temporalCascadePixel<Trusted, false, true>(k, c, layers, geometry, historyLayers, historyGeometry, numPixels, p, layersOut, trust, nullptr, 0u, plane);
+}
+
+template<bool Trusted>
+static void launchCascadeCarried(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, const float4* plane,
+                                 float4* layersOut, const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream)
+{
+  const size_t numPixels = (size_t) k.width * k.height;
+  hipLaunchKernelGGL(temporalCascadeCarriedKernel<Trusted>, dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, trust,
+                     plane, layersOut, k, c);
+}
+
 template<bool Trusted>
 static void launchCascadeMoving(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust,
                                 const TwkInstanceMotion* motion, unsigned int numMotion, float4* layersOut, const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream)
@@ -67,8 +89,9 @@ static void launchCascadeMoving(const float4* layers, const float4* geometry, co
 
 // trust: k.width x k.height floats, not nullptr. motion, numMotion: the table of the Moving build; nullptr or 0: the kernel above
 void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, const float* trust, float4* layersOut,
-                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
+                                  const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion, const float4* carried)
 {
+  if (carried) { launchCascadeCarried<true>(layers, geometry, historyLayers, historyGeometry, trust, carried, layersOut, k, c, stream); return; }
   if (motion && numMotion > 0u) { launchCascadeMoving<true>(layers, geometry, historyLayers, historyGeometry, trust, motion, numMotion, layersOut, k, c, stream); return; }
   const size_t numPixels = (size_t) k.width * k.height;
   hipLaunchKernelGGL(temporalCascadeTrustedKernel, dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, trust,
@@ -78,8 +101,9 @@ void launchTemporalCascadeTrusted(const float4* layers, const float4* geometry, 
 // layers, layersOut and historyLayers [c.layers][k.width x k.height] float4; historyLayers / historyGeometry nullptr with k.hasHistory 0.
 // motion, numMotion: the table of the Moving build; nullptr or 0: the kernel above
 void launchTemporalCascade(const float4* layers, const float4* geometry, const float4* historyLayers, const float4* historyGeometry, float4* layersOut,
-                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
+                           const TemporalConstants& k, const CascadeConstants& c, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion, const float4* carried)
 {
+  if (carried) { launchCascadeCarried<false>(layers, geometry, historyLayers, historyGeometry, nullptr, carried, layersOut, k, c, stream); return; }
   if (motion && numMotion > 0u) { launchCascadeMoving<false>(layers, geometry, historyLayers, historyGeometry, nullptr, motion, numMotion, layersOut, k, c, stream); return; }
   const size_t numPixels = (size_t) k.width * k.height;
   hipLaunchKernelGGL(temporalCascadeKernel, dim3((unsigned int) ((numPixels + 255) / 256)), dim3(256), 0, stream, layers, geometry, historyLayers, historyGeometry, layersOut, k, c);

@@ -72,14 +72,15 @@
 // environment would have to be reprojected by direction, which is left out. The lens is the pinhole: no fisheye or sphere. Objects
 // move by one matrix per instance, in the Moving builds only (temporal_motion_device.h: twk_update_instance_transform keeps the
 // history and the merges look it up where the instance was); the builds without it take the scene as static between the history's
-// frame and this one. No per-vertex motion, no deformation, no motion blur. The merge itself works on whole pictures.
+// frame and this one. A deformed mesh (twk_update_geometry_vertices) is followed by the Carried builds, which take g' per pixel from
+// the previous-position plane (temporal_carry_device.h). No motion blur. The merge itself works on whole pictures.
 // A frame tiled over several devices is merged on ONE of them: every device traces the geometry of its own share (above), the
 // shares and the planes are assembled there in one launch (twk_assemble_devices_with_geometry) and
 // twk_temporal_accumulate_assembled runs this same merge on the assembled W x H buffers, with that handle's history. Nothing is
 // scattered back to the tiles, and the merge does not read the packed tiles itself.
 #pragma once
 #include "denoise_device.h"
-#include "temporal_motion_device.h"
+#include "temporal_carry_device.h" // temporalMove (temporal_motion_device.h) and temporalCarry
 
 namespace twk {
 
@@ -180,15 +181,19 @@ TWK_HD void temporalTap(const float4& hc, const float4& hm, float w, TemporalSum
 // load of g is split into xyz and w and temporalKernel grows by 30 instructions.) Moving: the build that first carries g to where
 // its instance was in the history's frame (temporal_motion_device.h temporalMove, with the table motion[numMotion]); otherwise the
 // table is not read.
-template<bool Moving = false>
+// Carried: the build that takes g' from the previous-position plane instead (temporal_carry_device.h temporalCarry; carried: the
+// plane's element of this pixel); otherwise it is not read.
+template<bool Moving = false, bool Carried = false>
 TWK_HD void temporalGather(const TemporalConstants& k, const float4 cur, const float4 mc, const float4 g, const float4* historyColour, const float4* historyMoments,
-                           const float4* historyGeometry, TemporalSums& s, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u)
+                           const float4* historyGeometry, TemporalSums& s, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u,
+                           const float4 carried = make_float4(0.0f, 0.0f, 0.0f, 0.0f))
 {
   s.x = 0.0f; s.y = 0.0f; s.z = 0.0f; s.mean = 0.0f; s.M2 = 0.0f; s.n = 0.0f; s.ws = 0.0f;
   float fx = 0.0f, fy = 0.0f, vv = 0.0f;
   if (!temporalCandidate(k, cur, mc, g)) return;
   float4 gp = g;
   if (Moving && !temporalMove(motion, numMotion, g, gp)) return;
+  if (Carried && !temporalCarry(carried, g, gp)) return;
   if (!temporalProject(k, gp, fx, fy, vv)) return;
   const TemporalFootprint f = temporalFootprint(fx, fy);
 #pragma unroll

@@ -98,6 +98,32 @@ __global__ void __launch_bounds__(256) temporalMovingKernel(const Pixel* __restr
     temporalStorePassThrough(p, raw, cur, mc, colourOut, historyOut, momentsOut);
 }
 
+// temporalKernel's Carried build (temporal_carry_device.h): the same thread per pixel and the same streams, plus one coalesced 16-byte
+// read of the previous-position plane per pixel; no table. A kernel of its own, so that the ones above are the code they were.
+template<typename Pixel>
+__global__ void __launch_bounds__(256) temporalCarriedKernel(const Pixel* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ geometry,
+                                                             const float4* __restrict__ historyColour, const float4* __restrict__ historyMoments, const float4* __restrict__ historyGeometry,
+                                                             const float4* __restrict__ plane, Pixel* __restrict__ colourOut, float4* __restrict__ historyOut, float4* __restrict__ momentsOut,
+                                                             TemporalConstants k)
+{
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t) k.width * k.height) return;
+  const Pixel raw = colour[p];
+  const float4 cur = widen(raw);
+  const float4 mc = moments[p];
+  const float4 g = geometry[p];
+  TemporalSums s;
+  temporalGather<false, true>(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s, nullptr, 0u, plane[p]);
+  if (s.ws > 0.0f)
+  {
+    float4 c, m;
+    temporalMerge(k, s, cur, mc, c, m);
+    temporalStoreMerged(p, c, m, colourOut, historyOut, momentsOut);
+  }
+  else
+    temporalStorePassThrough(p, raw, cur, mc, colourOut, historyOut, momentsOut);
+}
+
 template<typename Pixel, bool Staged>
 static void launchMoving(const void* colour, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments, const float4* historyGeometry,
                          const TwkInstanceMotion* motion, unsigned int numMotion, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream)
@@ -115,8 +141,20 @@ void launchGeometry(const LaunchParams& p, float4* geometry, bool tiled, int gri
 
 void launchTemporal(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                     const float4* historyGeometry, void* colourOut, float4* historyOut, float4* momentsOut, const TemporalConstants& k, hipStream_t stream,
-                    const TwkInstanceMotion* motion, unsigned int numMotion)
+                    const TwkInstanceMotion* motion, unsigned int numMotion, const float4* carried)
 {
+  if (carried) // the Carried build: g' from the plane, no table
+  {
+    const size_t pixels = (size_t) k.width * k.height;
+    const dim3 blocks((unsigned int) ((pixels + 255) / 256));
+    if (half)
+      hipLaunchKernelGGL(temporalCarriedKernel<Half4>, blocks, dim3(256), 0, stream, static_cast<const Half4*>(colour), moments, geometry, historyColour, historyMoments, historyGeometry,
+                         carried, static_cast<Half4*>(colourOut), historyOut, momentsOut, k);
+    else
+      hipLaunchKernelGGL(temporalCarriedKernel<float4>, blocks, dim3(256), 0, stream, static_cast<const float4*>(colour), moments, geometry, historyColour, historyMoments, historyGeometry,
+                         carried, static_cast<float4*>(colourOut), historyOut, momentsOut, k);
+    return;
+  }
   if (motion && numMotion > 0u) // the Moving build; without a table the kernel below, as it always was
   {
 #if TWK_MOTION_STAGED_RECORDS > 0

@@ -35,7 +35,8 @@
 // wave-uniform (a wave's 64 pixels see one or two instances), so the loads of a wave fall into one or two cache lines — or, for a
 // table of at most TWK_MOTION_STAGED_RECORDS records, into the block's LDS copy of it (below: measured, the faster of the two).
 //
-// What it is not. One rigid or affine matrix per INSTANCE: no deforming geometry, no per-vertex motion, no motion blur. The light
+// What it is not. One rigid or affine matrix per INSTANCE: no deforming geometry and no per-vertex motion here (temporal_carry_device.h:
+// the previous-position plane of a deformed mesh and the Carried builds that read it), no motion blur. The light
 // an emitting instance carries does not move with it (twk_update_instance_transform refuses such an instance). Shadows and
 // inter-reflections the move changes elsewhere in the picture are stale history like any light edit: the rectified merge discounts
 // them, the plain merge fades them at the cap. A miss never has history, and the lens is the pinhole.

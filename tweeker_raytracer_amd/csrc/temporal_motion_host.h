@@ -27,15 +27,17 @@ struct TemporalHostFrame
 };
 
 // temporalKernel / temporalMovingKernel on the host: colourOut, momentsOut (either may be nullptr) width x height x 4 floats
-template<bool Moving>
-inline void temporalPlainHost(const TemporalConstants& k, const TemporalHostFrame& f, const TwkInstanceMotion* motion, unsigned int numMotion, float* colourOut, float* momentsOut)
+// Carried: the Carried build, plane (width x height float4) in place of the table
+template<bool Moving, bool Carried = false>
+inline void temporalPlainHost(const TemporalConstants& k, const TemporalHostFrame& f, const TwkInstanceMotion* motion, unsigned int numMotion, float* colourOut, float* momentsOut,
+                              const float4* plane = nullptr)
 {
   const size_t n = (size_t) k.width * k.height;
   for (size_t p = 0; p < n; ++p)
   {
     float4 c = f.cur[p], m = f.mc[p];
     TemporalSums s;
-    temporalGather<Moving>(k, f.cur[p], f.mc[p], f.g[p], f.hc.data(), f.hm.data(), f.hg.data(), s, motion, numMotion);
+    temporalGather<Moving, Carried>(k, f.cur[p], f.mc[p], f.g[p], f.hc.data(), f.hm.data(), f.hg.data(), s, motion, numMotion, Carried ? plane[p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     if (s.ws > 0.0f) temporalMerge(k, s, f.cur[p], f.mc[p], c, m);
     if (colourOut) memcpy(colourOut + 4 * p, &c, sizeof(float4));
     if (momentsOut) memcpy(momentsOut + 4 * p, &m, sizeof(float4));
@@ -43,15 +45,16 @@ inline void temporalPlainHost(const TemporalConstants& k, const TemporalHostFram
 }
 
 // The two launches of the rectified merge on the host; trustOut (may be nullptr) width x height floats
-template<bool Moving>
+template<bool Moving, bool Carried = false>
 inline void temporalRectifyHost(const TemporalConstants& k, const RectifyConstants& r, const TemporalHostFrame& f, const TwkInstanceMotion* motion, unsigned int numMotion,
-                                float* colourOut, float* momentsOut, float* trustOut)
+                                float* colourOut, float* momentsOut, float* trustOut, const float4* plane = nullptr)
 {
   const int width = k.width, height = k.height;
   const size_t n = (size_t) width * height;
   std::vector<float4> A(n), B(n);
   // launch 1
-  for (size_t p = 0; p < n; ++p) rectifyReproject<Moving>(k, f.cur[p], f.mc[p], f.g[p], f.hc.data(), f.hm.data(), f.hg.data(), A[p], B[p], motion, numMotion);
+  for (size_t p = 0; p < n; ++p) rectifyReproject<Moving, Carried>(k, f.cur[p], f.mc[p], f.g[p], f.hc.data(), f.hm.data(), f.hg.data(), A[p], B[p], motion, numMotion,
+                                                                    Carried ? plane[p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
   // launch 2: the staged words of the whole picture with a halo of `radius` zeros around it, as one tile
   const int R = r.radius, pitch = width + 2 * R;
   std::vector<float> d((size_t) pitch * (height + 2 * R), 0.0f);
@@ -78,8 +81,16 @@ inline void temporalRectifyHost(const TemporalConstants& k, const RectifyConstan
 
 // The plain (r nullptr) or the rectified merge, with a table (motion, numMotion > 0) or without
 inline void temporalMergeHost(const TemporalConstants& k, const RectifyConstants* r, const TemporalHostFrame& f, const TwkInstanceMotion* motion, unsigned int numMotion,
-                              float* colourOut, float* momentsOut, float* trustOut)
+                              float* colourOut, float* momentsOut, float* trustOut, const float* previousPositions = nullptr)
 {
+  if (previousPositions) // the Carried builds: the plane in place of the table
+  {
+    std::vector<float4> plane((size_t) k.width * k.height);
+    memcpy(plane.data(), previousPositions, plane.size() * sizeof(float4));
+    if (r) temporalRectifyHost<false, true>(k, *r, f, nullptr, 0u, colourOut, momentsOut, trustOut, plane.data());
+    else   temporalPlainHost<false, true>(k, f, nullptr, 0u, colourOut, momentsOut, plane.data());
+    return;
+  }
   const bool moving = motion && numMotion > 0u;
   if (r) { if (moving) temporalRectifyHost<true>(k, *r, f, motion, numMotion, colourOut, momentsOut, trustOut); else temporalRectifyHost<false>(k, *r, f, nullptr, 0u, colourOut, momentsOut, trustOut); }
   else   { if (moving) temporalPlainHost<true>(k, f, motion, numMotion, colourOut, momentsOut); else temporalPlainHost<false>(k, f, nullptr, 0u, colourOut, momentsOut); }
@@ -88,9 +99,12 @@ inline void temporalMergeHost(const TemporalConstants& k, const RectifyConstants
 // The cascade's merge on the host: layers [c.layers][width x height x 4] floats; historyLayers nullptr: none (k.hasHistory 0);
 // trust nullptr: the plain build, else the trusted one
 inline void temporalCascadeHostLayers(const TemporalConstants& k, const CascadeConstants& c, const float* currentLayers, const float* currentGeometry, const float* historyLayers,
-                                      const float* historyGeometry, const float* trust, const TwkInstanceMotion* motion, unsigned int numMotion, float* layersOut)
+                                      const float* historyGeometry, const float* trust, const TwkInstanceMotion* motion, unsigned int numMotion, float* layersOut,
+                                      const float* previousPositions = nullptr)
 {
   const size_t n = (size_t) k.width * k.height, all = n * (size_t) c.layers;
+  std::vector<float4> plane(previousPositions ? n : 0);
+  if (previousPositions) memcpy(plane.data(), previousPositions, n * sizeof(float4));
   std::vector<float4> layers(all), geometry(n), history(historyLayers ? all : 0), hGeometry(historyLayers ? n : 0), out(all);
   memcpy(layers.data(), currentLayers, all * sizeof(float4));
   memcpy(geometry.data(), currentGeometry, n * sizeof(float4));
@@ -104,6 +118,12 @@ inline void temporalCascadeHostLayers(const TemporalConstants& k, const CascadeC
   const bool moving = motion && numMotion > 0u;
   for (size_t p = 0; p < n; ++p)
   {
+    if (previousPositions) // the Carried builds
+    {
+      if (trust) temporalCascadePixel<true, false, true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), trust, nullptr, 0u, plane.data());
+      else       temporalCascadePixel<false, false, true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), nullptr, nullptr, 0u, plane.data());
+      continue;
+    }
     if (trust) { if (moving) temporalCascadePixel<true, true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), trust, motion, numMotion);
                  else        temporalCascadePixel<true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), trust); }
     else       { if (moving) temporalCascadePixel<false, true>(k, c, layers.data(), geometry.data(), H, hG, n, p, out.data(), nullptr, motion, numMotion);

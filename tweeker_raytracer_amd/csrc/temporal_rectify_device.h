@@ -77,14 +77,16 @@ struct RectifyConstants
 
 // Launch 1 at one pixel: the reprojected, capped history as the two scratch words A = (hx, hy, hz, 0), B = (hmean, hM2, hn, g.w).
 // Moving: temporalGather's Moving build (temporal_motion_device.h); launch 2 is the same for both.
-template<bool Moving = false>
+// Carried: temporalGather's Carried build (temporal_carry_device.h; carried: the plane's element of this pixel).
+template<bool Moving = false, bool Carried = false>
 TWK_HD void rectifyReproject(const TemporalConstants& k, const float4& cur, const float4& mc, const float4& g, const float4* historyColour, const float4* historyMoments,
-                             const float4* historyGeometry, float4& A, float4& B, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u)
+                             const float4* historyGeometry, float4& A, float4& B, const TwkInstanceMotion* motion = nullptr, unsigned int numMotion = 0u,
+                             const float4 carried = make_float4(0.0f, 0.0f, 0.0f, 0.0f))
 {
   A = make_float4(0.0f, 0.0f, 0.0f, 0.0f); B = A;
   if (k.hasHistory == 0) return;
   TemporalSums s;
-  temporalGather<Moving>(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s, motion, numMotion);
+  temporalGather<Moving, Carried>(k, cur, mc, g, historyColour, historyMoments, historyGeometry, s, motion, numMotion, carried);
   if (!(s.ws > 0.0f)) return;
   const TemporalHistory h = temporalHistory(k, s);
   A.x = h.x; A.y = h.y; A.z = h.z;

@@ -48,6 +48,22 @@ __global__ void __launch_bounds__(256) rectifyReprojectMovingKernel(const Pixel*
   scratchB[p] = B;
 }
 
+// Launch 1's Carried build (temporal_carry_device.h): as the first kernel, plus one coalesced 16-byte read of the previous-position
+// plane per pixel; no table. Launch 2 is the same for all three. A kernel of its own, so that the ones above are the code they were.
+template<typename Pixel>
+__global__ void __launch_bounds__(256) rectifyReprojectCarriedKernel(const Pixel* __restrict__ colour, const float4* __restrict__ moments, const float4* __restrict__ geometry,
+                                                                     const float4* __restrict__ historyColour, const float4* __restrict__ historyMoments,
+                                                                     const float4* __restrict__ historyGeometry, const float4* __restrict__ plane,
+                                                                     float4* __restrict__ scratchA, float4* __restrict__ scratchB, TemporalConstants k)
+{
+  const size_t p = (size_t) blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t) k.width * k.height) return;
+  float4 A, B;
+  rectifyReproject<false, true>(k, widen(colour[p]), moments[p], geometry[p], historyColour, historyMoments, historyGeometry, A, B, nullptr, 0u, plane[p]);
+  scratchA[p] = A;
+  scratchB[p] = B;
+}
+
 // Launch 2. A block is a 32 x 8 pixel tile: thread t is pixel (t % 32, t / 32) of it, so a wave is two rows of 32 pixels and every
 // global access of the merge is a coalesced 16-byte (RGBA16F colour: 8-byte) one. The block first stages d and key of the tile and
 // a halo of `radius` pixels into LDS, (32 + 2 radius) x (8 + 2 radius) pairs of words — at radius 4, 40 x 16 x 8 = 5120 bytes; the
@@ -100,13 +116,15 @@ rectifyMergeKernel(const Pixel* __restrict__ colour, const float4* __restrict__ 
 template<typename Pixel>
 static void launchRectify(const void* colour, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments, const float4* historyGeometry,
                           float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut, const TemporalConstants& k,
-                          const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
+                          const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion, const float4* carried)
 {
   const size_t numPixels = (size_t) k.width * k.height;
   const Pixel* in = static_cast<const Pixel*>(colour);
   Pixel* out = static_cast<Pixel*>(colourOut);
   const dim3 pixels((unsigned int) ((numPixels + 255) / 256));
-  if (!(motion && numMotion > 0u)) // without a table launch 1 as it always was
+  if (carried) // the Carried build: g' from the plane, no table
+    hipLaunchKernelGGL(rectifyReprojectCarriedKernel<Pixel>, pixels, dim3(256), 0, stream, in, moments, geometry, historyColour, historyMoments, historyGeometry, carried, scratchA, scratchB, k);
+  else if (!(motion && numMotion > 0u)) // without a table launch 1 as it always was
     hipLaunchKernelGGL(rectifyReprojectKernel<Pixel>, pixels, dim3(256), 0, stream, in, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, k);
 #if TWK_MOTION_STAGED_RECORDS > 0
   else if (numMotion <= TWK_MOTION_STAGED_RECORDS)
@@ -140,10 +158,10 @@ static void launchRectify(const void* colour, const float4* moments, const float
 // motion, numMotion: the table of launch 1's Moving build; nullptr or 0: none, the launches as they always were.
 void launchTemporalRectify(const void* colour, bool half, const float4* moments, const float4* geometry, const float4* historyColour, const float4* historyMoments,
                            const float4* historyGeometry, float4* scratchA, float4* scratchB, void* colourOut, float4* historyOut, float4* momentsOut, float* trustOut,
-                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion)
+                           const TemporalConstants& k, const RectifyConstants& r, hipStream_t stream, const TwkInstanceMotion* motion, unsigned int numMotion, const float4* carried)
 {
-  if (half) launchRectify<Half4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream, motion, numMotion);
-  else      launchRectify<float4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream, motion, numMotion);
+  if (half) launchRectify<Half4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream, motion, numMotion, carried);
+  else      launchRectify<float4>(colour, moments, geometry, historyColour, historyMoments, historyGeometry, scratchA, scratchB, colourOut, historyOut, momentsOut, trustOut, k, r, stream, motion, numMotion, carried);
 }
 
 } // namespace twk

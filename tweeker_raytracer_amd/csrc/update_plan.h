@@ -69,19 +69,40 @@ struct NodeRange { int first, count; };
 // changes its world box and nothing else. ranges: every rebuilt tree's node range in ascending order, then the top level's (it is
 // rebuilt whenever there is one), then the two root slots behind the last node (bvh_build.hip wideRootKernel) — disjoint and
 // ascending, because a flattened instance's range grows with its index and the top level follows them all.
+// A vertex update (updatePlanWith: `updated` geometries, distinct, in range) adds what new vertices change: the bottom-level tree of
+// an updated geometry that some instance enters, the world box of every entered instance of it, and the world-space tree of every
+// flattened instance of it. A bottom-level range lies before every flattened one (sceneLayout), so the ranges stay ascending.
 struct UpdatePlan
 {
-  std::vector<int>       trees;  // the flattened instances among `moved`, ascending: their world-space trees are rebuilt
+  std::vector<int>       geometries; // the entered geometries among `updated`, ascending: their bottom-level trees are rebuilt
+  std::vector<int>       boxes;      // the entered instances of `updated` geometries, ascending: their world boxes change
+  std::vector<int>       trees;  // the flattened instances among `moved` and of `updated` geometries, ascending: their world-space trees are rebuilt
   std::vector<NodeRange> ranges;
   bool   topLevel = false;
   size_t totalNodes = 0, totalSlots = 0; // nodes the ranged tail quantises, triangle slots the rebuilt trees rewrite
 };
 
-inline void updatePlan(const SceneLayout& s, const int* instanceGeometry, const int* geometryTriangles, const int* moved, int numMoved, UpdatePlan& p)
+inline void updatePlanWith(const SceneLayout& s, const int* instanceGeometry, const int* geometryTriangles, const int* moved, int numMoved,
+                           const int* updated, int numUpdated, UpdatePlan& p)
 {
   p = UpdatePlan();
+  const int numInstances = (int) s.flattened.size();
+  std::vector<char> changed(s.needsBlas.size(), 0); // per geometry: its vertices are new
+  for (int k = 0; k < numUpdated; ++k) changed[(size_t) updated[k]] = 1;
+  for (size_t g = 0; g < changed.size(); ++g) if (changed[g] && s.needsBlas[g]) p.geometries.push_back((int) g);
   for (int k = 0; k < numMoved; ++k) if (s.flattened[(size_t) moved[k]]) p.trees.push_back(moved[k]);
+  for (int i = 0; i < numInstances && numUpdated > 0; ++i)
+  {
+    if (!changed[(size_t) instanceGeometry[i]]) continue;
+    if (!s.flattened[(size_t) i]) p.boxes.push_back(i);
+    else if (std::find(p.trees.begin(), p.trees.end(), i) == p.trees.end()) p.trees.push_back(i);
+  }
   std::sort(p.trees.begin(), p.trees.end());
+  for (int g : p.geometries)
+  {
+    p.ranges.push_back({s.geometryNodeBase[(size_t) g], treeNodes(geometryTriangles[g])});
+    p.totalSlots += (size_t) geometryTriangles[g];
+  }
   for (int i : p.trees)
   {
     const int n = geometryTriangles[instanceGeometry[i]];
@@ -92,6 +113,11 @@ inline void updatePlan(const SceneLayout& s, const int* instanceGeometry, const 
   if (p.topLevel) p.ranges.push_back({s.tlasBase, (int) (s.numNodes - (size_t) s.tlasBase)});
   p.ranges.push_back({(int) s.numNodes, 2});
   for (const NodeRange& r : p.ranges) p.totalNodes += (size_t) r.count;
+}
+
+inline void updatePlan(const SceneLayout& s, const int* instanceGeometry, const int* geometryTriangles, const int* moved, int numMoved, UpdatePlan& p)
+{
+  updatePlanWith(s, instanceGeometry, geometryTriangles, moved, numMoved, nullptr, 0, p);
 }
 
 } // namespace twk

@@ -47,6 +47,52 @@ def update_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, moved=(
     return out
 
 
+def vertex_update_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, updated=(), moved=(), maxLeaf=2):
+    """twk_vertex_update_plan_host (pure CPU): update_plan_host with the geometries `updated` (new vertices) as well as the instances
+    `moved`. `trees` lists a rebuilt bottom-level tree as ~geometry (negative) before the flattened instances; `ranges` has their node
+    ranges in the same order, then the top level and the two root slots."""
+    ig = np.ascontiguousarray(instanceGeometry, dtype=np.int32).reshape(-1)
+    gt = np.ascontiguousarray(geometryTriangles, dtype=np.int32).reshape(-1)
+    mv = np.ascontiguousarray(list(moved), dtype=np.int32).reshape(-1)
+    up = np.ascontiguousarray(list(updated), dtype=np.int32).reshape(-1)
+    plan = L.UpdatePlan()
+    room = int(ig.size + gt.size + 2)
+    flattened = np.zeros(max(1, ig.size), np.uint8)
+    trees = np.zeros(room, np.int32)
+    ranges = np.zeros(2 * room, np.int32)
+    ip = C.POINTER(C.c_int)
+    L.check(L.lib.twk_vertex_update_plan_host(ig.ctypes.data_as(ip), int(ig.size), gt.ctypes.data_as(ip), int(gt.size), int(flattenPolicy[0]), int(flattenPolicy[1]), int(maxLeaf),
+                                              mv.ctypes.data_as(ip) if mv.size else None, int(mv.size), up.ctypes.data_as(ip) if up.size else None, int(up.size), C.byref(plan),
+                                              flattened.ctypes.data_as(C.POINTER(C.c_ubyte)), trees.ctypes.data_as(ip), ranges.ctypes.data_as(ip)))
+    out = {name: getattr(plan, name) for name, _ in L.UpdatePlan._fields_}
+    out["flattened"] = [bool(f) for f in flattened[:ig.size]]
+    out["trees"] = [int(t) for t in trees[:plan.treesRebuilt]]
+    out["ranges"] = [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(plan.numRanges)]
+    return out
+
+
+def previous_positions_host(hits, instance, primitive, geometry, indices, previousPositions, motion=None, carry=None):
+    """twk_previous_positions_host (pure CPU): the previous-position plane of twk_render_geometry_motion from host arrays — hits
+    float32 [n, 3] (t, beta, gamma), instance and primitive int32 [n] (instance < 0: a miss), geometry float32 [n, 4] (the geometry
+    AOV), indices uint32, previousPositions float32 [m, 4], motion / carry: ctypes arrays of L.InstanceMotion / L.InstanceCarry indexed
+    by instance (None: none). Returns float32 [n, 4]."""
+    hits = np.ascontiguousarray(hits, dtype=np.float32).reshape(-1, 3)
+    inst = np.ascontiguousarray(instance, dtype=np.int32).reshape(-1)
+    prim = np.ascontiguousarray(primitive, dtype=np.int32).reshape(-1)
+    geo = np.ascontiguousarray(geometry, dtype=np.float32).reshape(-1, 4)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    pos = np.ascontiguousarray(previousPositions, dtype=np.float32).reshape(-1, 4)
+    if not (hits.shape[0] == inst.size == prim.size == geo.shape[0]):
+        raise ValueError("previous_positions_host: one hit, instance, primitive and geometry element per pixel")
+    out = np.empty((hits.shape[0], 4), np.float32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+    L.check(L.lib.twk_previous_positions_host(hits.ctypes.data_as(fp), inst.ctypes.data_as(ip), prim.ctypes.data_as(ip), geo.ctypes.data_as(fp), C.c_size_t(hits.shape[0]),
+                                              idx.ctypes.data_as(C.POINTER(C.c_uint)) if idx.size else None, C.c_size_t(idx.size), pos.ctypes.data_as(fp) if pos.size else None,
+                                              C.c_size_t(pos.shape[0]), motion, int(len(motion)) if motion is not None else 0, carry, int(len(carry)) if carry is not None else 0,
+                                              out.ctypes.data_as(fp)))
+    return out
+
+
 def device_count():
     n = C.c_int(0)
     L.check(L.lib.twk_device_count(C.byref(n)))
@@ -345,6 +391,39 @@ class Device:
             raise ValueError("updateInstanceTransforms: 12 floats per id")
         L.check(L.lib.twk_update_instance_transforms(self._h, int(ids.size), ids.ctypes.data_as(C.POINTER(C.c_int)), t.ctypes.data_as(C.POINTER(C.c_float))))
 
+    # ---- deforming an object (include/tweeker_hip.h "Deforming an object", csrc/temporal_carry_device.h) ----
+    def updateGeometryVertices(self, idGeometry, attributes):
+        """twk_update_geometry_vertices: replaces all attributes of a geometry (float32 [n, 12]: vertex, tangent, normal, texcoord; n
+        is the geometry's vertex count, the indices stay) and rebuilds the acceleration structure — everything in full mode, only what
+        the new vertices change in selective mode (updateInfo). The temporal history is kept and the geometry is deformed
+        (geometryDeformed) until a merge swaps the history; the geometry AOV is stale. TwkError: before build(), a bad id, another
+        vertex count, a position that is not finite, a geometry an instance with a light references."""
+        attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
+        L.check(L.lib.twk_update_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
+
+    def geometryDeformed(self, idGeometry):
+        """twk_get_geometry_deformed: whether the handle holds the geometry's positions as of the history's frame."""
+        d = C.c_int(0)
+        L.check(L.lib.twk_get_geometry_deformed(self._h, int(idGeometry), C.byref(d)))
+        return bool(d.value)
+
+    def renderGeometryMotion(self):
+        """twk_render_geometry_motion: renderGeometry, and beside the geometry AOV the previous-position plane (readPreviousPositions):
+        per hit pixel where its surface point was when the temporal history was taken. The first call after an update (or a merge) uploads
+        the per-instance records and the previous positions and waits for the upload; while nothing has changed it is asynchronous."""
+        L.check(L.lib.twk_render_geometry_motion(self._h))
+
+    def readPreviousPositions(self):
+        """The previous-position plane: float32 [height, width, 4]; [..., 3].view(uint32) is instance + 1, 0 for a miss."""
+        out = np.empty((self.state.resolution[1], self.launchWidth, 4), dtype=np.float32)
+        L.check(L.lib.twk_read_previous_positions(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def previousPositionsDevicePointer(self):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        L.check(L.lib.twk_get_previous_position_device_pointer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     @staticmethod
     def updatePlanHost(instanceGeometry, geometryTriangles, flattenPolicy, moved=(), maxLeaf=2):
         """twk_update_plan_host, pure CPU: update_plan_host of this module."""
@@ -383,6 +462,27 @@ class Device:
         h, w = shape if shape is not None else (0, 0)
         L.check(L.lib.twk_temporal_accumulate_cascade_moving(self._h, ref(params), ref(cascade), ptr(currentLayers), ptr(currentGeometry), ptr(historyLayers),
                                                              ptr(historyGeometry), ref(historyCamera), ptr(trust), ptr(motion), int(numMotion), int(w), int(h), ptr(layersOut)))
+
+    def temporalAccumulateCarried(self, params=None, rectify=None, current=None, history=None, previousPositions=None, shape=None, colourOut=None, historyOut=None,
+                                  momentsOut=None, trustOut=None):
+        """twk_temporal_accumulate_carried: the explicit form of temporalAccumulate (rectify None) or of temporalAccumulateRectified
+        that takes g' from a previous-position plane — previousPositions: a device pointer to height x width float4 (16-byte aligned),
+        as previousPositionsDevicePointer hands out. previousPositions None: the existing calls, byte for byte."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda f: None if f is None else C.byref(f)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_carried(self._h, ref(params), ref(rectify), ref(current), ref(history), ptr(previousPositions), int(w), int(h),
+                                                      ptr(colourOut), ptr(historyOut), ptr(momentsOut), ptr(trustOut)))
+
+    def temporalAccumulateCascadeCarried(self, params=None, cascade=None, currentLayers=None, currentGeometry=None, historyLayers=None, historyGeometry=None, historyCamera=None,
+                                         trust=None, previousPositions=None, shape=None, layersOut=None):
+        """twk_temporal_accumulate_cascade_carried: the explicit merge of the cascade's layers (trust None: plain; given: trusted) that
+        takes g' from a previous-position plane. previousPositions None: the existing calls, byte for byte."""
+        ptr = lambda p: None if p is None else C.c_void_p(int(p))
+        ref = lambda f: None if f is None else C.byref(f)
+        h, w = shape if shape is not None else (0, 0)
+        L.check(L.lib.twk_temporal_accumulate_cascade_carried(self._h, ref(params), ref(cascade), ptr(currentLayers), ptr(currentGeometry), ptr(historyLayers),
+                                                              ptr(historyGeometry), ref(historyCamera), ptr(trust), ptr(previousPositions), int(w), int(h), ptr(layersOut)))
 
     def readTemporalMotion(self):
         """twk_read_temporal_motion: the motion table the last own-buffer (or assembled) merge used, a ctypes array of

@@ -6,12 +6,12 @@ buffer a render leaves — byte for byte, no tolerance: the same kernels run on 
 
 The scenes are tests/selective_scenes.py's (flat, two-level, mixed, single, many), at 33 x 21 and 2 spp, in SAH and LBVH quality; cameras,
 lights and materials are the Cornell box's."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import lifecycle as lc
+import scene_snapshot as snapshot
 import selective_scenes as S
 from conftest import load_app
 
@@ -23,11 +23,6 @@ CORNELL_WALLS = (0, 1, 3, 4)  # the Cornell box's light, floor, back wall and le
 QUALITIES = pytest.mark.parametrize("quality", [1, 0], ids=["sah", "lbvh"])
 F = np.float32
 
-
-class _SceneHead(C.Structure):
-    """The first fields of LaunchParams (csrc/device_types.h), which twk_debug_snapshot_scene fills with HOST copies of the scene arrays.
-    Fields and array sizes are selective_scenes.py's, which tests/test_update_plan_host.py holds against the headers."""
-    _fields_ = [(name, getattr(C, kind)) for name, kind in S.SCENE_HEAD]
 
 # scenes with two movable objects and a wall: what a sequence and a batch need. `single` has one instance and cannot take part.
 SEVERAL = ["flat", "two-level", "mixed", "many"]
@@ -80,29 +75,12 @@ def _device(twk, app, parts, name, quality, selective, transforms=None, half=Fal
     return dev
 
 
-def _params_bytes(orc):
-    lib = orc._load(orc.HOST_KERNELS_PATH)
-    lib.hostk_params_bytes.restype = C.c_size_t
-    return lib.hostk_params_bytes()
-
-
 def _structure(twk, orc, dev):
-    """Everything the build leaves that a reader can get at, as words."""
-    L = twk._lib
-    info, nodes, tris, inst = dev.readAcceleration()
-    out = {"info": np.array([info[k] for k in sorted(info)], np.int64), "wideQ": lc._words(nodes), "slots": lc._words(tris), "instances": lc._words(inst)}
-    build = dev.buildInfo()
+    """Everything the build leaves that a reader can get at, as words (scene_snapshot.py reads it)."""
+    arrays, info, build = snapshot.read_scene(twk, orc, dev)
+    out = {key: (value if key == "topRoots" else lc._words(value)) for key, value in arrays.items()}
+    out["info"] = np.array([info[k] for k in sorted(info)], np.int64)
     out["buildInfo"] = np.array([build[k] for k in sorted(build) if k != "buildMilliseconds"], np.float64).view(np.uint64)
-    params = C.create_string_buffer(_params_bytes(orc))
-    L.check(L.lib.twk_debug_snapshot_scene(dev.handle, params, C.c_size_t(len(params))))
-    head = _SceneHead.from_buffer(params)
-    copy = lambda pointer, nbytes: np.frombuffer(C.string_at(pointer, nbytes), np.uint32).copy()
-    out["binaryNodes"] = copy(head.nodes, S.NODE_BYTES * build["nodes"])
-    out["shadeRecords"] = copy(head.shadeTriangles, S.SHADE_RECORD_BYTES * build["triangleSlots"])
-    out["snapshotSlots"] = copy(head.triangles, S.SLOT_BYTES * build["triangleSlots"])
-    out["topNodes"] = copy(head.topNodes, S.QUANTISED_NODE_BYTES * S.TOP_NODES)
-    out["topNodes7"] = copy(head.topNodes7, S.QUANTISED_NODE_BYTES * S.TOP_NODES7)
-    out["topRoots"] = np.array([head.topRoot, head.topRoot2], np.int64)
     return out, info, build
 
 

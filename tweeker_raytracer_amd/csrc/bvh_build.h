@@ -79,8 +79,8 @@ public:
   // over its leaf primitives), measured after every build.
   double lastSahInner() const { return m_lastSahInner; }
   double lastSahLeaf() const { return m_lastSahLeaf; }
-  // A tree over ONE build primitive has no terms of its own and leaves those of the tree built before it standing; a scene's build
-  // starts from none, so that what it reports does not depend on what the handle built earlier.
+  // A tree over ONE build primitive has no terms of its own and leaves those of the tree built before it standing (the scene's sum
+  // skips such a tree: device_scene.hip sahTotals); a scene's build starts from none.
   void   clearLastSah() { m_lastSahInner = 0.0; m_lastSahLeaf = 0.0; }
   // Height of the binary tree built last (inner nodes on the longest root-to-leaf path, after the leaf collapse): what a
   // single-ray traversal may have to keep on its stack.

@@ -270,18 +270,17 @@ static int fillTopCaches(TwkDevice dev)
   return TWK_SUCCESS;
 }
 
-// The SAH terms of the scene: those of its trees in build order — the entered geometries ascending, then the flattened instances
-// ascending. A tree over one build primitive has no terms of its own: the builder leaves those of the tree built before it standing
-// (none before the first: BvhBuilder::clearLastSah), so the sum takes the terms of the tree before it in this order again.
+// The SAH terms of the scene: the sum of those of its trees — the entered geometries ascending, then the flattened instances
+// ascending. A tree over one build primitive has no inner node and no terms: it adds nothing. (The builder leaves the terms of the
+// tree built before it standing, and the sum used to take those again: a one-quad wall built after a sphere counted as another
+// sphere. tests/test_gpu_bvh_audit.py holds the sum against the trees read back.)
 static void sahTotals(TwkDevice dev, const SceneState& state, TwkBuildInfo& info)
 {
   info.sahInnerCost = 0.0; info.sahLeafCost = 0.0;
-  TwkDevice_t::TreeTerms last;
   const auto tree = [&](const TwkDevice_t::TreeTerms& own, size_t geometry)
   {
     const size_t primitives = state.pairs ? state.primFirst[geometry].size() : (size_t) dev->geometries[geometry].numTriangles;
-    if (primitives > 1) last = own;
-    info.sahInnerCost += last.sahInner; info.sahLeafCost += last.sahLeaf;
+    if (primitives > 1) { info.sahInnerCost += own.sahInner; info.sahLeafCost += own.sahLeaf; }
   };
   for (size_t k = 0; k < dev->geometries.size(); ++k) if (state.layout.needsBlas[k]) tree(state.geometryTerms[k], k);
   for (size_t i = 0; i < dev->instances.size(); ++i) if (state.layout.flattened[i]) tree(state.instanceTerms[i], (size_t) dev->instances[i].geometry);

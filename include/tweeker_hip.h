@@ -969,7 +969,7 @@ int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12
  * top level; no bottom-level tree is ever rebuilt. Afterwards the handle equals, byte for byte, a fresh handle built with the
  * current transforms. Everything else about an update is as "Moving an object" says: the temporal history stays, adaptive state is
  * dropped, the geometry AOV is stale, and an update that fails (an allocation, a HIP error, the depth refusal, with twk_build's
- * text) leaves the handle unbuilt until twk_build. What it is not: no refit (a moved flattened instance gets a new tree), no vertex
+ * text) leaves the handle unbuilt until twk_build. What it is not: not a refit (a moved flattened instance gets a new tree; "Refit" below refits deformed meshes only), no vertex
  * updates by these calls (twk_update_geometry_vertices: "Deforming an object" below), no adding or removing of instances, no change of flatten policy or build quality between updates (those need twk_build),
  * no moving emitters. Measured: profiles/r24_selective_update.md. */
 #define TWK_UPDATE_FULL      0 /* default: an update rebuilds everything twk_build builds; nothing is kept */
@@ -1015,7 +1015,7 @@ int twk_update_plan_host(const int* instanceGeometry, int numInstances, const in
  * reference's Device::createGeometry cannot do) and KEEPS the temporal history; twk_render_geometry_motion then says, per pixel,
  * where the surface point it sees was when the history was taken. The complete definition of that plane is
  * csrc/temporal_carry_device.h; tests/temporal_carry_restate.py restates it in numpy. What it is not: no topology change (the indices
- * stay), no refit (a changed tree is rebuilt, or the equality below would not hold), no device-pointer source for the vertices, no
+ * stay), not a refit (a changed tree is rebuilt, or the equality below would not hold; twk_refit_geometry_vertices, "Refit" below, is the call that keeps the topology), no device-pointer source for the vertices, no
  * emitting geometry, no motion blur, no tiled frames (the assembled forms refuse while a geometry is deformed), pinhole only, no
  * rtigo3_hip key. The merges read the plane through their Carried builds, further below. Measured: profiles/r25_vertex_update.md (tools/vertex_update_time.py).
  *
@@ -1048,6 +1048,59 @@ int twk_get_geometry_deformed(TwkDevice dev, int idGeometry, int* deformed);
 int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
                                 int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,
                                 TwkUpdatePlan* plan, unsigned char* flattened, int* trees, int* ranges);
+/* ---- Refit: a deformed mesh's trees updated in place — new calls, ABI stays 9; the full and the selective mode launch what they
+ * launched -------------------------------------------------------------------------------------------------------------------------
+ * twk_refit_geometry_vertices is twk_update_geometry_vertices for a handle built in TWK_UPDATE_SELECTIVE (≙ an OptiX build with
+ * OPTIX_BUILD_OPERATION_UPDATE): the same arguments, the same refusals with the same texts under its own name, the same treatment
+ * of everything around the trees — the previous positions are kept (the geometry counts as deformed), the temporal history stays,
+ * adaptive state is dropped, the geometry AOV is stale, twk_get_build_info and twk_get_update_info (selective 1, treesRebuilt = the
+ * trees really rebuilt) describe the call. But the bottom-level tree of the geometry (if some instance enters it) and the world-space
+ * tree of every flattened instance of it are REFIT, not rebuilt (csrc/bvh_refit.h is the complete definition): every slot and shading
+ * record is written again from the primitive word the slot holds, every leaf box follows the build's rule (padBox once per build
+ * primitive), every inner box is the union of its children's, every wide node keeps the cut it had, and the node costs follow. The
+ * references, the slot order, the pair flags and the heights do not change. A direct-leaf instance (no tree of its own) takes the
+ * rebuild's path and counts in treesRebuilt. The top level, the 8-wide root and the ranged tail run as in the selective update.
+ * The result is a LEGAL tree for the new vertices (tests/bvh_audit.py holds it to every check a build's tree passes), not the tree a
+ * fresh build would choose: its quality decays as the mesh moves away from the vertices it was built from. TwkRefitInfo says by how
+ * much — sahNow / sahBuilt — and the caller decides when to call twk_update_geometry_vertices, which rebuilds: there is no fallback
+ * in the library. A refit with the vertices the tree was built from changes no byte; a refit back to them restores every byte.
+ * What it is not: no refit of a MOVED flattened instance (transform updates stay rebuilds), no restructuring or rotations, no new
+ * cuts, no topology change, no emitters, no tiled frames while a geometry is deformed, no device-pointer source, no rtigo3_hip key.
+ * Additional refusal: TWK_ERROR_INVALID_STATE on a handle whose scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode
+ * before twk_build): nothing a refit needs was kept. Measured: profiles/r28_refit.md (tools/refit_time.py). */
+int twk_refit_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes);
+/* What the last refit did. treesRefit / treesRebuilt: trees refit in place / rebuilt (direct-leaf instances); nodesRefit: nodes of
+ * the refit trees' ranges; slotsRewritten: triangle slots written; sahBuilt: the sum of sahInner + sahLeaf of the refit trees as of
+ * their last real build (twk_build, twk_update_geometry_vertices, a transform update of a flattened instance — each resets the
+ * tree's count and its sahBuilt); sahNow: the same sum after this refit; refitsSinceBuild: the largest number of refits any of the
+ * refit trees has taken since it was last built; milliseconds: host wall time, also TwkBuildInfo.buildMilliseconds. */
+typedef struct TwkRefitInfo
+{
+  int treesRefit, treesRebuilt, topLevelRebuilt, refitsSinceBuild;
+  uint64_t nodesRefit, slotsRewritten;
+  double sahBuilt, sahNow, milliseconds;
+} TwkRefitInfo;
+/* TWK_ERROR_INVALID_VALUE: a NULL argument. TWK_ERROR_INVALID_STATE: no refit has been made on this handle since it was last built. */
+int twk_get_refit_info(TwkDevice dev, TwkRefitInfo* info);
+/* Pure CPU, no device: the refit of ONE tree from host arrays, with the header's code. All arrays are the TREE's own: nodes
+ * [numNodes x 16 floats] binary nodes and wideNodes [numNodes x 32 floats] full-precision wide nodes (in / out), nodeCost [numNodes]
+ * (in / out, or NULL: the cuts were not costed), slots [numSlots x 12 floats] (in: the primitive word of each slot; out: the
+ * vertices) and shadeRecords [numSlots x 32 floats] (out), pairFlags [numSlots] (or NULL), the geometry's attributes and indices
+ * (numIndices = 3 x numSlots). References in the nodes are absolute: node nodeBase + i stands at nodes[16 i], slot slotBase + s at
+ * slots[12 s]. leafFlag 0: an object-space tree (transform ignored); TWK_LEAF_WORLD (0x40000000): the world-space tree of instance
+ * idInstance under `transform` (row-major 3 x 4), whose slots get the instance word. terms[2] (or NULL): sahInner, sahLeaf;
+ * rootBounds[6] (or NULL): the tree's box. TWK_ERROR_INVALID_VALUE: a NULL array, a count < 1 or out of range, numIndices different
+ * from 3 x numSlots, an index beyond the attributes, a leafFlag that is neither, a world-space tree without transform or with a
+ * negative instance, a reference that leaves the ranges given or names a node twice, a primitive word beyond the indices. */
+int twk_refit_tree_host(float* nodes, float* wideNodes, float* nodeCost, float* slots, float* shadeRecords, const int* pairFlags,
+                        const TwkTriangleAttributes* attributes, size_t numAttributes, const unsigned int* indices, size_t numIndices,
+                        int nodeBase, int numNodes, int slotBase, int numSlots, int leafFlag, const float* transform, int idInstance,
+                        double* terms, float* rootBounds);
+/* The three device arrays a selective handle keeps, for comparing the device with the host form: wide [32 x (nodes + 2) floats]
+ * (the full-precision wide nodes and the two root slots), nodeCost [nodes floats], pairFlags [triangleSlots ints]; each NULL or
+ * given with its count of elements. TWK_ERROR_INVALID_STATE: the handle is not built in TWK_UPDATE_SELECTIVE, or does not keep an
+ * array that is asked for (no costed cuts, no pairs). TWK_ERROR_INVALID_VALUE: a NULL handle, a count that is not the array's. */
+int twk_debug_read_kept_build(TwkDevice dev, float* wide, size_t numWideFloats, float* nodeCost, size_t numNodeCost, int* pairFlags, size_t numPairFlags);
 /* One record per instance beside its TwkInstanceMotion (csrc/temporal_carry_device.h): previousObjectToWorld is the instance's
  * object-to-world matrix as of the history's frame, row-major 3 x 4; deformed = 0 says its geometry holds no previous positions and
  * nothing else is read; positionBase / indexBase: the first previous position / first index of its geometry in the arrays given. */

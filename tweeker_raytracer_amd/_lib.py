@@ -287,6 +287,13 @@ class UpdateInfo(C.Structure):
                 ("keptBytes", C.c_uint64), ("milliseconds", C.c_double)]
 
 
+class RefitInfo(C.Structure):
+    """≙ TwkRefitInfo: what the last refit of a handle did (twk_get_refit_info)."""
+    _fields_ = [("treesRefit", C.c_int), ("treesRebuilt", C.c_int), ("topLevelRebuilt", C.c_int), ("refitsSinceBuild", C.c_int),
+                ("nodesRefit", C.c_uint64), ("slotsRewritten", C.c_uint64), ("sahBuilt", C.c_double), ("sahNow", C.c_double),
+                ("milliseconds", C.c_double)]
+
+
 class UpdatePlan(C.Structure):
     """≙ TwkUpdatePlan: the layout of a scene and what a selective update of some of its instances touches (twk_update_plan_host)."""
     _fields_ = [("instances", C.c_int), ("flattenedInstances", C.c_int), ("directLeafInstances", C.c_int), ("enteredGeometries", C.c_int),
@@ -333,6 +340,7 @@ SYMBOLS = [
     "twk_set_update_mode", "twk_update_instance_transforms", "twk_get_update_info", "twk_update_plan_host", "twk_app_get_selective_update",
     "twk_update_geometry_vertices", "twk_get_geometry_deformed", "twk_vertex_update_plan_host", "twk_render_geometry_motion", "twk_get_previous_position_device_pointer",
     "twk_read_previous_positions", "twk_previous_positions_host",
+    "twk_refit_geometry_vertices", "twk_get_refit_info", "twk_refit_tree_host", "twk_debug_read_kept_build",
     "twk_temporal_accumulate_carried", "twk_temporal_accumulate_cascade_carried", "twk_temporal_carried_host", "twk_temporal_cascade_carried_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",

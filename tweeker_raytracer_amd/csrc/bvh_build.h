@@ -25,6 +25,17 @@ void launchPairLeaves(float4* wideQ, int count, const int* pairFlags, int numSlo
 void launchRangedTail(const BvhNode* wide, float4* wideQ, const int2* ranges, int numRanges, int total, const int* pairFlags, int numSlots,
                       const float4* triangles, float4* pairs, hipStream_t stream);
 
+// The refit of one tree in place (bvh_refit.h is the definition, bvh_refit.hip the kernels): the slots [slotBase, slotBase + numSlots) and
+// their shading records again from `attributes` / `indices` — the geometry's own, or with `soup` (one descriptor per triangle of the
+// geometry, BvhBuilder::soupDescriptors from 0) the shared arrays and `instances` — then every box, wide node and node cost of the
+// nodes [nodeBase, nodeBase + numNodes) bottom-up, with the references, the cuts and the pair flags the tree has. All arrays are the
+// scene's (absolute indices); nodeCost / pairFlags nullptr: the scene has none. scratch: refitScratchWords(numNodes) words.
+// Waits for the stream; rootBounds receives the tree's new box, terms its SAH terms (inner, leaf; zero for a one-primitive tree).
+size_t refitScratchWords(int numNodes);
+hipError_t launchRefitTree(hipStream_t stream, const float* attributes, const unsigned int* indices, const int4* soup, const DevInstance* instances,
+                           BvhNode* nodes, BvhNode* wide, float* nodeCost, float4* triangles, float4* shadeTriangles, const int* pairFlags,
+                           int nodeBase, int numNodes, int slotBase, int numSlots, unsigned int* scratch, float rootBounds[6], double terms[2]);
+
 // Build primitives of a geometry's triangles for BvhBuilder::buildTriangles: triangles 2k, 2k + 1 with the index triples
 // (a, b, c), (c, d, a) — what every mesh generator emits per quad — are one primitive (first triangle | sign bit), every other
 // triangle is one of its own. Indices are compared, not positions. Returns the number of pairs.

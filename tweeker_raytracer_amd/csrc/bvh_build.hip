@@ -8,6 +8,7 @@
 // instance boxes (top level, world space).
 #include "device_types.h"
 #include "bvh_build.h"
+#include "bvh_refit.h" // padBox, the binary and the wide node, soupVertices, emitTriangle: one text with the refit
 
 #include <cstring>
 #include <cstdlib>
@@ -30,24 +31,6 @@ __global__ void initBoundsKernel(unsigned int* bounds)
 {
   if (threadIdx.x < 3) bounds[threadIdx.x] = 0xffffffffu;      // min
   else if (threadIdx.x < 6) bounds[threadIdx.x] = 0u;          // max
-}
-
-// Soup descriptor of one flattened triangle: x = instance, y = first vertex of its geometry in the shared attribute
-// array, z = first index of the TRIANGLE in the shared index array, w = primitive index inside the geometry.
-// Vertex c of a soup triangle, in world space: the geometry's object-space position through the instance's
-// object-to-world matrix — m0*x + m1*y + m2*z + m3 in fp32, the expression transformPoint (closesthit.cu:88-98) and
-// the oracle evaluate.
-TWK_D void soupVertices(const int4& d, const float* __restrict__ attributes, const unsigned int* __restrict__ indices,
-                        const DevInstance* __restrict__ instances, const float*& a, const float*& b, const float*& c, V3& wa, V3& wb, V3& wc)
-{
-  const unsigned int i0 = indices[d.z], i1 = indices[d.z + 1], i2 = indices[d.z + 2];
-  a = attributes + 12 * ((size_t) d.y + i0);
-  b = attributes + 12 * ((size_t) d.y + i1);
-  c = attributes + 12 * ((size_t) d.y + i2);
-  const float* m = instances[d.x].objectToWorld;
-  wa = transformPoint(m, v3(a[0], a[1], a[2]));
-  wb = transformPoint(m, v3(b[0], b[1], b[2]));
-  wc = transformPoint(m, v3(c[0], c[1], c[2]));
 }
 
 // Triangle boxes of one geometry (object space), or of the world-space soup of the flattened instances (soup != nullptr:
@@ -186,24 +169,6 @@ __global__ void radixTreeKernel(const unsigned long long* __restrict__ keys, int
   if (i == 0) innerParent[0] = -1;
 }
 
-TWK_D void padBox(float4& lo, float4& hi)
-{
-  // The watertight triangle test reports t with an ABSOLUTE error that scales with the triangle's size and with the
-  // magnitude of its coordinates (the edge functions are differences of products of vertex-minus-origin terms), not
-  // with t: a ray that starts 2e-4 above a 16-unit floor triangle gets a t that is off by 3e-7, 1e-3 of its value —
-  // measured: with axis-tight boxes (a flat floor: pad 1e-30 in y) the slab interval [3.52942e-4, 3.52942e-4] was
-  // culled against a current best of 3.52938e-4 although the triangle test would have returned 3.5266e-4. Every
-  // primitive box therefore grows on ALL axes by 2^-17 (128 ulp) of (largest coordinate magnitude + box diagonal):
-  // two orders of magnitude above the observed error, 0.03 % of a 0.03-unit triangle. Errors that scale with the
-  // distance travelled are covered by the relative widening of the slab test itself (trace_device.h).
-  const float k = 7.6293945e-6f; // 2^-17
-  const float m = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(hi.x)), fmaxf(fabsf(lo.y), fabsf(hi.y))), fmaxf(fabsf(lo.z), fabsf(hi.z)));
-  const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-  const float e = k * (m + sqrtf(dx * dx + dy * dy + dz * dz)) + 1.0e-30f;
-  lo.x -= e; lo.y -= e; lo.z -= e;
-  hi.x += e; hi.y += e; hi.z += e;
-}
-
 // Reference of the leaf over sorted positions [first, first + positions) when it holds at most maxLeaf triangles, else 0 (no
 // leaf reference is 0: ~0 is -1).
 TWK_D int leafReference(const int* __restrict__ slotOff, int leafBase, int leafFlag, int first, int positions, int maxLeaf)
@@ -211,63 +176,6 @@ TWK_D int leafReference(const int* __restrict__ slotOff, int leafBase, int leafF
   const int slot = slotOff ? slotOff[first] : first, triangles = slotOff ? slotOff[first + positions] - slot : positions;
   if (positions > 1 && triangles > maxLeaf) return 0;
   return ~((leafBase + slot) | ((triangles - 1) << 28) | leafFlag);
-}
-
-TWK_D void writeNode(BvhNode* node, const float4& lo0, const float4& hi0, const float4& lo1, const float4& hi1, int c0, int c1)
-{
-  float4* p = reinterpret_cast<float4*>(node);
-  p[0] = make_float4(lo0.x, lo0.y, lo0.z, hi0.x);
-  p[1] = make_float4(hi0.y, hi0.z, lo1.x, lo1.y);
-  p[2] = make_float4(lo1.z, hi1.x, hi1.y, hi1.z);
-  p[3] = make_float4(__int_as_float(c0), __int_as_float(c1), 0.0f, 0.0f);
-}
-
-// Wide (4-ary) node of inner node i = the children of its children, 128 bytes (layout at writeWideNode): a traversal step over a wide node crosses two levels of the binary tree
-// with one round of loads instead of two dependent ones. A child that is a leaf occupies one entry; unused entries
-// get an empty box. Wide nodes share the index space of the binary nodes (every inner node has one; only those at
-// even depth below the root are ever visited).
-struct WideEntry { float4 lo, hi; int ref; };
-// (Round 3, measured and not kept: opening twice the inner entry with the largest surface area instead of taking the four
-// grandchildren — node visits per ray 7.64 -> 7.43 on C2, triangle tests 3.07 -> 3.28, C2 -7 %: profiles/r03y_wide_collapse_greedy.txt.)
-TWK_D float wideHalfArea(const float4& lo, const float4& hi)
-{
-  const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-  return dx * dy + dy * dz + dz * dx;
-}
-
-TWK_D void emptyEntry(WideEntry& e)
-{
-  const float inf = __uint_as_float(0x7f800000u);
-  // lo = hi = +inf: every plane distance is +inf or -inf on both sides, so the slab interval is empty for any ray.
-  // (An inverted box lo > hi does NOT work: the slab test orders the two plane distances itself.)
-  e.lo = make_float4(inf, inf, inf, 0.0f); e.hi = make_float4(inf, inf, inf, 0.0f); e.ref = ~0;
-}
-
-// Expands child `ref` (box lo/hi) into one entry (leaf) or the two entries of its own children (inner node).
-TWK_D void expandChild(const BvhNode* outNodes, int nodeBase, int ref, const float4& lo, const float4& hi, WideEntry* e, int& n)
-{
-  if (ref < 0) { e[n].lo = lo; e[n].hi = hi; e[n].ref = ref; ++n; return; }
-  const float4* c = reinterpret_cast<const float4*>(outNodes + (ref - nodeBase));
-  const float4 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
-  e[n].lo = make_float4(c0.x, c0.y, c0.z, 0.0f); e[n].hi = make_float4(c0.w, c1.x, c1.y, 0.0f); e[n].ref = __float_as_int(c3.x); ++n;
-  e[n].lo = make_float4(c1.z, c1.w, c2.x, 0.0f); e[n].hi = make_float4(c2.y, c2.z, c2.w, 0.0f); e[n].ref = __float_as_int(c3.y); ++n;
-}
-
-// Wide node layout, 8 float4: (lo_k.xyz, ref_k) and (hi_k.xyz, unused) for k = 0..3, with the four references in
-// the .w of the FIRST four float4 — (lo0,ref0) (hi0,ref1) (lo1,ref2) (hi1,ref3) (lo2,-) (hi2,-) (lo3,-) (hi3,-) —
-// so that they arrive with the box data the first slab tests need. (With the references in a float4 of their own
-// the compiler sank those loads behind the box tests: two extra dependent L2 round trips per traversal step.)
-TWK_D void writeWideNode(BvhNode* wide, const WideEntry* e)
-{
-  float4* p = reinterpret_cast<float4*>(wide);
-  p[0] = make_float4(e[0].lo.x, e[0].lo.y, e[0].lo.z, __int_as_float(e[0].ref));
-  p[1] = make_float4(e[0].hi.x, e[0].hi.y, e[0].hi.z, __int_as_float(e[1].ref));
-  p[2] = make_float4(e[1].lo.x, e[1].lo.y, e[1].lo.z, __int_as_float(e[2].ref));
-  p[3] = make_float4(e[1].hi.x, e[1].hi.y, e[1].hi.z, __int_as_float(e[3].ref));
-  p[4] = make_float4(e[2].lo.x, e[2].lo.y, e[2].lo.z, 0.0f);
-  p[5] = make_float4(e[2].hi.x, e[2].hi.y, e[2].hi.z, 0.0f);
-  p[6] = make_float4(e[3].lo.x, e[3].lo.y, e[3].lo.z, 0.0f);
-  p[7] = make_float4(e[3].hi.x, e[3].hi.y, e[3].hi.z, 0.0f);
 }
 
 // One thread per leaf walks up; the second thread to arrive at an inner node (ticket == 1) owns it.
@@ -406,53 +314,6 @@ __global__ void singleLeafKernel(const float4* __restrict__ primLo, const float4
   writeWideNode(outWide, e);
   lo.w = __int_as_float(1); // height of this one-node tree (refitKernel keeps heights in nodeLo[].w)
   nodeLo[0] = lo; nodeHi[0] = hi;
-}
-
-// Triangle slots in leaf order: three float4 per slot, w of the first = primitive index. The same pass writes the
-// 128-byte shading record of the slot (one cache line, eight float4), ordered by who needs what, so that shading does
-// not chase indices → three 48-byte vertex records and fetches only the part its material uses — every fetch here is
-// one divergent lane address, and a CU takes one of those per clock (tools/gather_probe.hip):
-//   [0..2]  geometric normal cross(v1 - v0, v2 - v0) as closesthit.cu:150 computes it (same float operations, done
-//           once here), then the three vertex normals                                   — every hit
-//   [3..5.x] the three vertex tangents                                                  — GGX materials (TBN) only
-//   [5.y..7.y] the three vertex texture coordinates                                     — textured materials only
-TWK_D void emitTriangle(const float* __restrict__ attributes, const unsigned int* __restrict__ indices,
-                        const int4* __restrict__ soup, const DevInstance* __restrict__ instances,
-                        unsigned int prim, int slot, float4* __restrict__ triangles, float4* __restrict__ shadeTriangles)
-{
-  const float *a, *b, *c;
-  if (soup != nullptr)
-  {
-    // world-space positions for traversal, tagged with primitive and instance; the shading record below stays in
-    // object space (shading transforms normals / tangents with the instance matrices as for any other hit)
-    const int4 d = soup[prim];
-    V3 wa, wb, wc;
-    soupVertices(d, attributes, indices, instances, a, b, c, wa, wb, wc);
-    triangles[3 * (size_t) slot + 0] = make_float4(wa.x, wa.y, wa.z, __int_as_float(d.w));
-    triangles[3 * (size_t) slot + 1] = make_float4(wb.x, wb.y, wb.z, __int_as_float(d.x));
-    triangles[3 * (size_t) slot + 2] = make_float4(wc.x, wc.y, wc.z, 0.0f);
-  }
-  else
-  {
-    const unsigned int i0 = indices[3 * prim], i1 = indices[3 * prim + 1], i2 = indices[3 * prim + 2];
-    a = attributes + 12 * (size_t) i0;
-    b = attributes + 12 * (size_t) i1;
-    c = attributes + 12 * (size_t) i2;
-    triangles[3 * (size_t) slot + 0] = make_float4(a[0], a[1], a[2], __uint_as_float(prim));
-    triangles[3 * (size_t) slot + 1] = make_float4(b[0], b[1], b[2], 0.0f);
-    triangles[3 * (size_t) slot + 2] = make_float4(c[0], c[1], c[2], 0.0f);
-  }
-  const V3 v0 = v3(a[0], a[1], a[2]), v1 = v3(b[0], b[1], b[2]), v2 = v3(c[0], c[1], c[2]);
-  const V3 ng = cross(v1 - v0, v2 - v0);
-  float4* out = shadeTriangles + TWK_SHADE_RECORD * (size_t) slot;
-  out[0] = make_float4(ng.x, ng.y, ng.z, a[6]);
-  out[1] = make_float4(a[7], a[8], b[6], b[7]);
-  out[2] = make_float4(b[8], c[6], c[7], c[8]);
-  out[3] = make_float4(a[3], a[4], a[5], b[3]);
-  out[4] = make_float4(b[4], b[5], c[3], c[4]);
-  out[5] = make_float4(c[5], a[9], a[10], a[11]);
-  out[6] = make_float4(b[9], b[10], b[11], c[9]);
-  out[7] = make_float4(c[10], c[11], 0.0f, 0.0f);
 }
 
 // One thread per sorted position. primFirst / slotOff != nullptr (bvh_build.h "pairs"): the position holds a build primitive of

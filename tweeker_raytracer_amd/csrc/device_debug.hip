@@ -339,6 +339,28 @@ try
 }
 TWK_CATCH("twk_debug_read_acceleration")
 
+int twk_debug_read_kept_build(TwkDevice dev, float* wide, size_t numWideFloats, float* nodeCost, size_t numNodeCost, int* pairFlags, size_t numPairFlags)
+try
+{
+  const char* name = "twk_debug_read_kept_build";
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built || !dev->kept.valid) return refuse(TWK_ERROR_INVALID_STATE, "the handle holds no scene built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build)");
+  const size_t wideFloats = 32 * (dev->totalNodes + 2);
+  if (wide && (!dev->d_wideNodes.holds(2 * (dev->totalNodes + 2)))) return refuse(TWK_ERROR_INVALID_STATE, "the full-precision wide nodes are not kept");
+  if (nodeCost && !dev->d_nodeCost.holds(dev->totalNodes)) return refuse(TWK_ERROR_INVALID_STATE, "no node costs are kept (costed cuts are off)");
+  if (pairFlags && !dev->d_pairFlags.holds(dev->totalTriangles)) return refuse(TWK_ERROR_INVALID_STATE, "no pair flags are kept (the scene was built without pairs)");
+  if ((wide && numWideFloats != wideFloats) || (nodeCost && numNodeCost != dev->totalNodes) || (pairFlags && numPairFlags != dev->totalTriangles))
+    return refuse(TWK_ERROR_INVALID_VALUE, "the arrays hold " + std::to_string(wideFloats) + " wide-node floats, " + std::to_string(dev->totalNodes) + " node costs and " + std::to_string(dev->totalTriangles) + " pair flags");
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  if (wide) HIP_TRY(hipMemcpy(wide, dev->d_wideNodes, sizeof(float) * wideFloats, hipMemcpyDeviceToHost));
+  if (nodeCost) HIP_TRY(hipMemcpy(nodeCost, dev->d_nodeCost, sizeof(float) * dev->totalNodes, hipMemcpyDeviceToHost));
+  if (pairFlags) HIP_TRY(hipMemcpy(pairFlags, dev->d_pairFlags, sizeof(int) * dev->totalTriangles, hipMemcpyDeviceToHost));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_debug_read_kept_build")
+
 int twk_debug_snapshot_scene(TwkDevice dev, void* launchParams, size_t paramsBytes)
 try
 {

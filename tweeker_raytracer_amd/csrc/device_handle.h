@@ -295,7 +295,9 @@ struct TwkDevice_t
   // KeptBuild is also the working state of a build: buildScene fills a local one through the stage functions updateSelective amends
   // this one with, and moves it here, valid, when a selective-mode build has succeeded.
   // d_updateSoup / d_updateRanges / d_updateResult: scratch of the updates, grown on demand.
-  struct TreeTerms { double sahInner = 0.0, sahLeaf = 0.0; int height = 0; };
+  // sahBuilt / refits (twk_refit_geometry_vertices, TwkRefitInfo): sahInner + sahLeaf as of the tree's last real build, and the refits
+  // it has taken since; every real build of the tree writes fresh terms and so resets both
+  struct TreeTerms { double sahInner = 0.0, sahLeaf = 0.0; int height = 0; double sahBuilt = 0.0; int refits = 0; };
   struct KeptBuild
   {
     bool valid = false, pairs = false, pairRewrite = false;
@@ -309,6 +311,9 @@ struct TwkDevice_t
   DeviceArray<float> d_nodeCost; DeviceArray<int> d_pairFlags;
   DeviceArray<int4> d_updateSoup; DeviceArray<int2> d_updateRanges; DeviceArray<int> d_updateResult;
   TwkUpdateInfo updateInfo = {}; bool updateInfoValid = false;
+  // twk_refit_geometry_vertices: what the last refit did (valid until the next build), and the scratch of a tree's refit (bvh_build.h refitScratchWords)
+  TwkRefitInfo refitInfo = {}; bool refitInfoValid = false;
+  DeviceArray<unsigned int> d_refitScratch;
 
   std::vector<std::vector<char>> hostScene; // twk_debug_snapshot_scene: host copies of the scene arrays
 

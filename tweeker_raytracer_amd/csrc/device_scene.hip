@@ -2,6 +2,7 @@
 // reference apps/rtigo3/src/Device.cpp:1339-1500).
 #include "device_handle.h"
 #include "temporal_motion_device.h" // instanceTransformUsable
+#include "bvh_refit.h"              // the host form of a tree's refit
 
 #include <algorithm>
 #include <chrono>
@@ -190,7 +191,8 @@ static void layoutInputs(TwkDevice dev, std::vector<int>& instanceGeometry, std:
   for (size_t k = 0; k < dev->geometries.size(); ++k) geometryTriangles[k] = dev->geometries[k].numTriangles;
 }
 
-static TwkDevice_t::TreeTerms lastTerms(const BvhBuilder& b) { return {b.lastSahInner(), b.lastSahLeaf(), b.lastHeight()}; }
+// The terms of the tree built last; a real build: no refit since, and sahBuilt is what it measured
+static TwkDevice_t::TreeTerms lastTerms(const BvhBuilder& b) { return {b.lastSahInner(), b.lastSahLeaf(), b.lastHeight(), b.lastSahInner() + b.lastSahLeaf(), 0}; }
 
 // The world-space tree of flattened instance i at the bases the layout gives it, over `soup` (scratch for its triangles); its terms and
 // world box go into the state. Reads d_instances[i]. Zeroes nothing: its node ranges and pair flags are zero before the call.
@@ -309,6 +311,7 @@ static int buildScene(TwkDevice dev, bool keep)
   if (dev->geometries.empty() || dev->instances.empty()) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_build: the scene has no geometry or no instance");
   dropAdaptive(dev);
   dev->built = false; // until this build has succeeded: a failure below leaves no half-built scene to launch on
+  dev->refitInfoValid = false; // twk_get_refit_info describes a refit of the scene as built
   const auto buildStart = std::chrono::steady_clock::now();
   TwkBuildInfo info;
   memset(&info, 0, sizeof(info));
@@ -480,6 +483,30 @@ static void recordUpdate(TwkDevice dev, bool selective, int moved, int trees, bo
   dev->updateInfoValid = true;
 }
 
+// The refit of one tree of geometry `geometry` at the node and slot bases given (bvh_refit.h): the bottom-level tree (soup nullptr) or
+// a flattened instance's world-space tree (soup: its descriptors). Its box goes to rootBounds, its new SAH terms into `terms` (the
+// height stays: a refit changes no tree's height), and the call into `info`. A tree over one build primitive has no terms (sahTotals).
+static int refitTree(TwkDevice dev, SceneState& state, int geometry, TwkDevice_t::TreeTerms& terms, const int4* soup, int nodeBase, int triangleBase, float rootBounds[6], TwkRefitInfo& info)
+{
+  int rc;
+  const GeometryHost& g = dev->geometries[geometry];
+  const int nodes = treeNodes(g.numTriangles);
+  if ((rc = dev->d_refitScratch.ensure(refitScratchWords(nodes)))) return rc;
+  double now[2];
+  HIP_TRY(launchRefitTree(dev->stream, soup ? dev->d_attributes.get() : dev->d_attributes + 12 * (size_t) g.attributeBase, soup ? dev->d_indices.get() : dev->d_indices + g.indexBase,
+                          soup, soup ? dev->d_instances.get() : nullptr, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles, dev->d_shadeTriangles,
+                          state.pairs ? dev->d_pairFlags.get() : nullptr, nodeBase, nodes, triangleBase, g.numTriangles, dev->d_refitScratch, rootBounds, now));
+  const size_t primitives = state.pairs ? state.primFirst[(size_t) geometry].size() : (size_t) g.numTriangles;
+  terms.refits += 1;
+  if (primitives > 1)
+  {
+    terms.sahInner = now[0]; terms.sahLeaf = now[1];
+    info.sahBuilt += terms.sahBuilt; info.sahNow += now[0] + now[1];
+  }
+  info.treesRefit += 1; info.nodesRefit += (uint64_t) nodes; info.refitsSinceBuild = std::max(info.refitsSinceBuild, terms.refits);
+  return TWK_SUCCESS;
+}
+
 // Internal, no entry point: the update of a handle built in selective mode (include/tweeker_hip.h "Selective instance updates") after
 // the transforms of the instances `moved` (distinct) have been replaced. It runs buildScene's stages (above) for what the plan names,
 // on arrays that hold what buildScene's held at that point — so the result is a fresh build's, byte for byte. A failure leaves the
@@ -487,7 +514,10 @@ static void recordUpdate(TwkDevice dev, bool selective, int moved, int trees, bo
 // updated: geometries (distinct) whose attributes have been replaced on the host, numUpdated of them — a vertex update
 // (twk_update_geometry_vertices): their slices of d_attributes are uploaded, the bottom-level tree of an entered one is rebuilt at the
 // node and slot range it has, and the trees and boxes of their instances follow (update_plan.h updatePlanWith).
-static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0)
+// refit (twk_refit_geometry_vertices): the trees of the updated geometries are refit in place (refitTree, above) instead of zeroed and
+// rebuilt — all but a direct-leaf instance's, which has no tree of its own and takes the rebuild's path. The stages around the trees
+// are the same; the handle is then a legal scene for the new vertices, not a fresh build's.
+static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false)
 {
   int rc;
   SceneState& state = dev->kept;
@@ -522,10 +552,17 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
     const GeometryHost& g = dev->geometries[updated[k]];
     HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
   }
+  TwkRefitInfo refitInfo;
+  memset(&refitInfo, 0, sizeof(refitInfo));
   for (int k : plan.geometries)
   {
     GeometryHost& g = dev->geometries[k];
     const int nodes = treeNodes(g.numTriangles);
+    if (refit)
+    {
+      if ((rc = refitTree(dev, state, k, state.geometryTerms[k], nullptr, g.nodeBase, g.triangleBase, g.rootBounds, refitInfo))) return rc;
+      continue;
+    }
     HIP_TRY(hipMemsetAsync(dev->d_nodes + g.nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
     HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) g.nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
     if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + g.triangleBase, 0, sizeof(int) * (size_t) g.numTriangles, dev->stream));
@@ -540,6 +577,17 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
   for (int i : plan.trees)
   {
     const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], triangles = geometryTriangles[instanceGeometry[i]], nodes = treeNodes(triangles);
+    if (refit && !layout.directLeaf[i])
+    {
+      float bounds[6];
+      dev->builder.soupDescriptors(dev->stream, dev->d_updateSoup, 0, triangles, i, (int) dev->geometries[instanceGeometry[i]].attributeBase, (int) dev->geometries[instanceGeometry[i]].indexBase);
+      HIP_TRY(hipGetLastError());
+      if ((rc = refitTree(dev, state, instanceGeometry[i], state.instanceTerms[i], dev->d_updateSoup, nodeBase, triangleBase, bounds, refitInfo))) return rc;
+      state.boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
+      state.boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
+      continue;
+    }
+    refitInfo.treesRebuilt += 1;
     HIP_TRY(hipMemsetAsync(dev->d_nodes + nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
     HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
     if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + triangleBase, 0, sizeof(int) * (size_t) triangles, dev->stream));
@@ -573,7 +621,12 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
 
   // the build info: counts, pair leaves, quality — no transform changes them — and what the changed trees change
   finishBuild(dev, state, dev->buildInfo, traversalDepth, start);
-  recordUpdate(dev, true, numMoved, (int) (plan.geometries.size() + plan.trees.size()), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
+  recordUpdate(dev, true, numMoved, refit ? refitInfo.treesRebuilt : (int) (plan.geometries.size() + plan.trees.size()), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
+  if (refit)
+  {
+    refitInfo.topLevelRebuilt = plan.topLevel ? 1 : 0; refitInfo.slotsRewritten = (uint64_t) plan.totalSlots; refitInfo.milliseconds = dev->buildInfo.buildMilliseconds;
+    dev->refitInfo = refitInfo; dev->refitInfoValid = true;
+  }
   return TWK_SUCCESS;
 }
 
@@ -651,17 +704,17 @@ static int updatePlanHost(const char* name, const int* instanceGeometry, int num
   return TWK_SUCCESS;
 }
 
-extern "C" {
-
-int twk_update_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
-try
+// The front half of twk_update_geometry_vertices and of twk_refit_geometry_vertices (refit: its one refusal more): the refusals under
+// the caller's name, then — nothing was changed up to there — the previous positions kept and the new vertices on the host
+static int replaceVertices(TwkDevice dev, const char* name, bool refit, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
 {
-  const char* name = "twk_update_geometry_vertices";
   const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
   if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
   if (!attributes) return refuse(TWK_ERROR_INVALID_VALUE, "NULL attributes");
   int rc = activate(dev, name); if (rc) return rc;
   if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  if (refit && !dev->kept.valid)
+    return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
   if (idGeometry < 0 || idGeometry >= (int) dev->geometries.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad geometry id");
   GeometryHost& g = dev->geometries[idGeometry];
   if (numAttributes != g.attributes.size())
@@ -676,6 +729,15 @@ try
   keepPreviousPositions(dev, idGeometry); // the positions as of the history's frame, before the first update since (device_temporal.hip)
   g.attributes.assign(attributes, attributes + numAttributes);
   dev->updateInfoValid = false;
+  return TWK_SUCCESS;
+}
+
+extern "C" {
+
+int twk_update_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
+try
+{
+  int rc = replaceVertices(dev, "twk_update_geometry_vertices", false, idGeometry, attributes, numAttributes); if (rc) return rc;
   // the temporal history stays: the merges look it up where the surface was (twk_render_geometry_motion, temporal_carry_device.h)
   if (dev->kept.valid) return updateSelective(dev, nullptr, 0, &idGeometry, 1);
   if ((rc = buildScene(dev, false))) return rc;
@@ -683,6 +745,74 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_update_geometry_vertices")
+
+int twk_refit_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
+try
+{
+  int rc = replaceVertices(dev, "twk_refit_geometry_vertices", true, idGeometry, attributes, numAttributes); if (rc) return rc;
+  return updateSelective(dev, nullptr, 0, &idGeometry, 1, true);
+}
+TWK_CATCH("twk_refit_geometry_vertices")
+
+int twk_get_refit_info(TwkDevice dev, TwkRefitInfo* info)
+try
+{
+  if (!dev || !info) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_refit_info: NULL argument");
+  if (!dev->refitInfoValid) return twkSetError(TWK_ERROR_INVALID_STATE, "twk_get_refit_info: no refit has been made on this handle since it was last built");
+  *info = dev->refitInfo;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_refit_info")
+
+int twk_refit_tree_host(float* nodes, float* wideNodes, float* nodeCost, float* slots, float* shadeRecords, const int* pairFlags,
+                        const TwkTriangleAttributes* attributes, size_t numAttributes, const unsigned int* indices, size_t numIndices,
+                        int nodeBase, int numNodes, int slotBase, int numSlots, int leafFlag, const float* transform, int idInstance,
+                        double* terms, float* rootBounds)
+try
+{
+  const auto refuse = [](const std::string& text) { return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_refit_tree_host: " + text); };
+  if (!nodes || !wideNodes || !slots || !shadeRecords || !attributes || !indices) return refuse("NULL argument");
+  if (numNodes < 1 || numSlots < 1 || nodeBase < 0 || slotBase < 0 || numAttributes < 1 || (size_t) numSlots >= ((size_t) 1 << 28) || (size_t) slotBase + (size_t) numSlots > ((size_t) 1 << 28) ||
+      (size_t) nodeBase + (size_t) numNodes > (size_t) TWK_BVH_SENTINEL)
+    return refuse("counts must be at least 1, bases at least 0, and the ranges within what a reference holds");
+  if (numIndices != 3 * (size_t) numSlots) return refuse("numIndices is " + std::to_string(numIndices) + ", not three per slot (" + std::to_string(3 * (size_t) numSlots) + ")");
+  if (leafFlag != 0 && leafFlag != TWK_LEAF_WORLD) return refuse("leafFlag is neither 0 nor TWK_LEAF_WORLD");
+  if (leafFlag != 0 && (!transform || idInstance < 0 || idInstance >= (1 << 24))) return refuse("a world-space tree needs its transform and an instance id of at least 0 (and below 2^24)");
+  for (size_t i = 0; i < numIndices; ++i) if (indices[i] >= numAttributes) return refuse("index " + std::to_string(i) + " is beyond the attributes");
+  // the caller's arrays need not be 16-byte aligned: the header's code works on copies
+  std::vector<BvhNode> n((size_t) numNodes), w(2 * (size_t) numNodes);
+  std::vector<float4> t(3 * (size_t) numSlots), shade(TWK_SHADE_RECORD * (size_t) numSlots);
+  memcpy(n.data(), nodes, sizeof(BvhNode) * n.size()); memcpy(w.data(), wideNodes, sizeof(BvhNode) * w.size()); memcpy(t.data(), slots, sizeof(float4) * t.size());
+  std::vector<float> cost;
+  if (nodeCost) cost.assign(nodeCost, nodeCost + numNodes);
+  RefitTree tree;
+  tree.nodes = n.data(); tree.wide = w.data(); tree.nodeCost = nodeCost ? cost.data() : nullptr; tree.triangles = t.data(); tree.pairFlags = pairFlags;
+  tree.nodeBase = nodeBase; tree.numNodes = numNodes; tree.slotBase = slotBase; tree.numSlots = numSlots;
+  std::vector<int> parents;
+  if (const char* why = refitTreeRefusal(tree, (size_t) numSlots, parents)) return refuse(why);
+  for (int i = 0; i < numNodes; ++i)
+  {
+    int c[2];
+    refitChildren(tree.nodes + i, c[0], c[1]);
+    if (refitUnused(c[0], c[1])) continue;
+    for (int k = 0; k < 2; ++k)
+      if (c[k] < 0 && !(k == 1 && refitNeverHit(tree.nodes + i)) && ((~c[k]) & TWK_LEAF_WORLD) != leafFlag) return refuse("node " + std::to_string(nodeBase + i) + ": a leaf reference's TWK_LEAF_WORLD is not leafFlag");
+  }
+  // a world-space tree: the soup descriptors and the one instance record emitTriangle reads, as buildFlattenedTree makes them
+  std::vector<int4> soup;
+  std::vector<DevInstance> instances;
+  if (leafFlag != 0) refitSoupHost(numSlots, idInstance, transform, soup, instances);
+  double sums[2];
+  float bounds[6];
+  refitTreeHost(tree, parents, reinterpret_cast<const float*>(attributes), indices, leafFlag ? soup.data() : nullptr, leafFlag ? instances.data() : nullptr, t.data(), shade.data(), sums, bounds);
+  memcpy(nodes, n.data(), sizeof(BvhNode) * n.size()); memcpy(wideNodes, w.data(), sizeof(BvhNode) * w.size()); memcpy(slots, t.data(), sizeof(float4) * t.size());
+  memcpy(shadeRecords, shade.data(), sizeof(float4) * shade.size());
+  if (nodeCost) memcpy(nodeCost, cost.data(), sizeof(float) * cost.size());
+  if (terms) { terms[0] = sums[0]; terms[1] = sums[1]; }
+  if (rootBounds) memcpy(rootBounds, bounds, sizeof(bounds));
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_refit_tree_host")
 
 int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
                                 int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,

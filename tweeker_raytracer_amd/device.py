@@ -93,6 +93,31 @@ def previous_positions_host(hits, instance, primitive, geometry, indices, previo
     return out
 
 
+def refit_tree_host(nodes, wideNodes, nodeCost, slots, pairFlags, attributes, indices, nodeBase, slotBase, leafFlag=0, transform=None, idInstance=-1):
+    """twk_refit_tree_host (pure CPU): the refit of ONE tree (csrc/bvh_refit.h) from host arrays, all the tree's own — nodes float32
+    [n, 16], wideNodes float32 [n, 32], nodeCost float32 [n] or None, slots float32 [t, 12] (the primitive word of each is read),
+    pairFlags int32 [t] or None, the geometry's attributes [v, 12] and indices; references are absolute (nodeBase, slotBase). leafFlag
+    0x40000000: the world-space tree of instance idInstance under `transform`. Nothing given is changed. Returns a dict: nodes,
+    wideNodes, nodeCost (or None), slots, shadeRecords float32 [t, 32], terms (sahInner, sahLeaf), rootBounds float32 [6]."""
+    copy = lambda a, kind, row: np.array(a, dtype=kind).reshape(-1, row) if row else np.array(a, dtype=kind).reshape(-1)
+    n, w, s = copy(nodes, np.float32, 16), copy(wideNodes, np.float32, 32), copy(slots, np.float32, 12)
+    cost = None if nodeCost is None else copy(nodeCost, np.float32, 0)
+    flags = None if pairFlags is None else np.ascontiguousarray(pairFlags, dtype=np.int32).reshape(-1)
+    attrs = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    if w.shape[0] != n.shape[0] or (cost is not None and cost.size != n.shape[0]) or (flags is not None and flags.size != s.shape[0]):
+        raise ValueError("refit_tree_host: one wide node and one cost per node, one pair flag per slot")
+    shade = np.zeros((s.shape[0], 32), np.float32)
+    terms, bounds = (C.c_double * 2)(), (C.c_float * 6)()
+    t = None if transform is None else np.ascontiguousarray(transform, dtype=np.float32).reshape(12)
+    fp = C.POINTER(C.c_float)
+    L.check(L.lib.twk_refit_tree_host(n.ctypes.data_as(fp), w.ctypes.data_as(fp), None if cost is None else cost.ctypes.data_as(fp), s.ctypes.data_as(fp), shade.ctypes.data_as(fp),
+                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int)), attrs.ctypes.data_as(C.c_void_p), C.c_size_t(attrs.shape[0]),
+                                      idx.ctypes.data_as(C.POINTER(C.c_uint)), C.c_size_t(idx.size), int(nodeBase), int(n.shape[0]), int(slotBase), int(s.shape[0]), int(leafFlag),
+                                      None if t is None else t.ctypes.data_as(fp), int(idInstance), terms, bounds))
+    return {"nodes": n, "wideNodes": w, "nodeCost": cost, "slots": s, "shadeRecords": shade, "terms": (terms[0], terms[1]), "rootBounds": np.array(bounds, dtype=np.float32)}
+
+
 def device_count():
     n = C.c_int(0)
     L.check(L.lib.twk_device_count(C.byref(n)))
@@ -400,6 +425,37 @@ class Device:
         vertex count, a position that is not finite, a geometry an instance with a light references."""
         attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
         L.check(L.lib.twk_update_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
+
+    # ---- refit (include/tweeker_hip.h "Refit", csrc/bvh_refit.h) ----
+    def refitGeometryVertices(self, idGeometry, attributes):
+        """twk_refit_geometry_vertices: updateGeometryVertices on a handle built in selective mode, but the geometry's trees are refit
+        in place — new boxes, the topology, the references and the wide nodes' cuts kept — instead of rebuilt. The handle is then a
+        legal scene for the new vertices, not a fresh build's; refitInfo says how far its SAH cost has drifted, and
+        updateGeometryVertices rebuilds. TwkError: updateGeometryVertices' refusals, and a handle not built in selective mode."""
+        attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
+        L.check(L.lib.twk_refit_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
+
+    def refitInfo(self):
+        """twk_get_refit_info: what the last refit did, a dict of L.RefitInfo's fields (treesRefit, treesRebuilt, topLevelRebuilt,
+        refitsSinceBuild, nodesRefit, slotsRewritten, sahBuilt, sahNow, milliseconds). TwkError before one."""
+        r = L.RefitInfo()
+        L.check(L.lib.twk_get_refit_info(self._h, C.byref(r)))
+        return {name: getattr(r, name) for name, _ in L.RefitInfo._fields_}
+
+    def debugReadKeptBuild(self):
+        """twk_debug_read_kept_build: what a selective handle keeps on the device — (wide float32 [nodes + 2, 32], the full-precision
+        wide nodes and the two root slots; nodeCost float32 [nodes]; pairFlags int32 [slots]), nodeCost / pairFlags None where the
+        handle keeps none. TwkError on a handle not built in selective mode."""
+        b = self.buildInfo()
+        nodes, slots = int(b["nodes"]), int(b["triangleSlots"])
+        wide = np.zeros((nodes + 2, 32), np.float32)
+        L.check(L.lib.twk_debug_read_kept_build(self._h, wide.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(wide.size), None, C.c_size_t(0), None, C.c_size_t(0)))
+        cost, flags = np.zeros(nodes, np.float32), np.zeros(slots, np.int32)
+        if L.lib.twk_debug_read_kept_build(self._h, None, C.c_size_t(0), cost.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(cost.size), None, C.c_size_t(0)) != L.TWK_SUCCESS:
+            cost = None
+        if L.lib.twk_debug_read_kept_build(self._h, None, C.c_size_t(0), None, C.c_size_t(0), flags.ctypes.data_as(C.POINTER(C.c_int)), C.c_size_t(flags.size)) != L.TWK_SUCCESS:
+            flags = None
+        return wide, cost, flags
 
     def geometryDeformed(self, idGeometry):
         """twk_get_geometry_deformed: whether the handle holds the geometry's positions as of the history's frame."""

@@ -1015,7 +1015,7 @@ int twk_update_plan_host(const int* instanceGeometry, int numInstances, const in
  * reference's Device::createGeometry cannot do) and KEEPS the temporal history; twk_render_geometry_motion then says, per pixel,
  * where the surface point it sees was when the history was taken. The complete definition of that plane is
  * csrc/temporal_carry_device.h; tests/temporal_carry_restate.py restates it in numpy. What it is not: no topology change (the indices
- * stay), not a refit (a changed tree is rebuilt, or the equality below would not hold; twk_refit_geometry_vertices, "Refit" below, is the call that keeps the topology), no device-pointer source for the vertices, no
+ * stay), not a refit (a changed tree is rebuilt, or the equality below would not hold; twk_refit_geometry_vertices, "Refit" below, is the call that keeps the topology), no device-pointer source for the vertices in THIS call (twk_update_geometry_vertices_device, "A device-pointer source" below, takes one), no
  * emitting geometry, no motion blur, no tiled frames (the assembled forms refuse while a geometry is deformed), pinhole only, no
  * rtigo3_hip key. The merges read the plane through their Carried builds, further below. Measured: profiles/r25_vertex_update.md (tools/vertex_update_time.py).
  *
@@ -1065,7 +1065,7 @@ int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, c
  * much — sahNow / sahBuilt — and the caller decides when to call twk_update_geometry_vertices, which rebuilds: there is no fallback
  * in the library. A refit with the vertices the tree was built from changes no byte; a refit back to them restores every byte.
  * What it is not: no refit of a MOVED flattened instance (transform updates stay rebuilds), no restructuring or rotations, no new
- * cuts, no topology change, no emitters, no tiled frames while a geometry is deformed, no device-pointer source, no rtigo3_hip key.
+ * cuts, no topology change, no emitters, no tiled frames while a geometry is deformed, no device-pointer source in this call (twk_refit_geometry_vertices_device takes one), no rtigo3_hip key.
  * Additional refusal: TWK_ERROR_INVALID_STATE on a handle whose scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode
  * before twk_build): nothing a refit needs was kept. Measured: profiles/r28_refit.md (tools/refit_time.py). */
 int twk_refit_geometry_vertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes);
@@ -1101,6 +1101,50 @@ int twk_refit_tree_host(float* nodes, float* wideNodes, float* nodeCost, float* 
  * given with its count of elements. TWK_ERROR_INVALID_STATE: the handle is not built in TWK_UPDATE_SELECTIVE, or does not keep an
  * array that is asked for (no costed cuts, no pairs). TWK_ERROR_INVALID_VALUE: a NULL handle, a count that is not the array's. */
 int twk_debug_read_kept_build(TwkDevice dev, float* wide, size_t numWideFloats, float* nodeCost, size_t numNodeCost, int* pairFlags, size_t numPairFlags);
+/* ---- A device-pointer source for the vertices — new calls, ABI stays 9; every existing call launches what it launched ------------
+ * twk_update_geometry_vertices_device and twk_refit_geometry_vertices_device are the two calls above for vertices that already live
+ * on the device (skinning, cloth, a simulation step, a torch tensor; ≙ OptixBuildInputTriangleArray::vertexBuffers, a device pointer
+ * with vertexStrideInBytes): no copy to the host, no host loop over the vertices, no upload. csrc/vertex_source_device.h is the
+ * complete definition; tests/vertex_source_restate.py restates the frames in numpy.
+ * The source is ONE of: attributes — numVertices TwkTriangleAttributes records, 16-byte aligned; positions — x, y, z floats per
+ * vertex, positionStride bytes apart (0 means 12), 4-byte aligned, with recomputeFrames 0 (tangents and normals stay) or 1 (they
+ * follow the new positions: the area-weighted sum of the adjacent triangles' normals in a fixed order, the tangent made
+ * perpendicular to it; an unusable sum keeps the old vector; texture coordinates always stay).
+ * THE CONTRACT: after the call the handle equals, byte for byte, a handle that was given the same records through the host call of
+ * the same name — acceleration structure, scene arrays, TwkBuildInfo / TwkUpdateInfo / TwkRefitInfo apart from the millisecond
+ * fields, every picture, the previous-position plane. "The same records": in attributes mode the source read back; in positions
+ * mode twk_vertex_frames_host(positions, ..., before = the geometry's records before the call), and with recomputeFrames 0 those
+ * `before` records with vertex[] replaced. twk_read_geometry_vertices returns them.
+ * STREAM RULE: the source is read on the handle's stream. The caller must have finished producing it — by synchronising its own
+ * stream or waiting on its event — before the call; on return the source has been consumed and may be overwritten.
+ * What it is not: no welding, no angle weights, no creases, no skinning (no bones, no weights), no index or topology change, no
+ * emitters, no asynchronous refit (the call's own waits stay), no tiled frames while a geometry is deformed, no rtigo3_hip key.
+ * Refusals, all under the call's own name, after which nothing has changed: every refusal of the host call of the same name (a NULL
+ * handle, before twk_build, a refit on a handle not built in TWK_UPDATE_SELECTIVE, a bad id, a wrong vertex count, a geometry with
+ * an instance that carries a light); TWK_ERROR_INVALID_VALUE: a NULL source, both pointers or neither, a stride below 12 or no
+ * multiple of 4 (or any with attributes), recomputeFrames above 1 (or 1 with attributes), a reserved word that is not 0, a
+ * misaligned pointer, a pointer that hipPointerGetAttributes does not report as device or managed memory the handle's device can
+ * read (a plain host pointer: nothing is dereferenced), an allocation that ends before the last vertex, a source that overlaps the
+ * handle's own attribute array, and a position that is not finite — "vertex <lowest such index>: the position is not finite", found
+ * by a read-only launch before anything is written. Measured: profiles/r29_vertex_source.md (tools/vertex_source_time.py). */
+typedef struct TwkVertexSource
+{
+  const void* attributes;       /* device pointer to numVertices TwkTriangleAttributes (48 B each), or NULL */
+  const void* positions;        /* device pointer to x,y,z floats per vertex, or NULL; exactly one of the two is set */
+  size_t      positionStride;   /* bytes between two positions: >= 12, a multiple of 4; 0 means 12 */
+  unsigned    recomputeFrames;  /* positions mode only: 1 = normals and tangents from the new positions, 0 = keep them */
+  unsigned    reserved[3];      /* must be 0 */
+} TwkVertexSource;
+int twk_update_geometry_vertices_device(TwkDevice dev, int idGeometry, const TwkVertexSource* source, size_t numVertices);
+int twk_refit_geometry_vertices_device(TwkDevice dev, int idGeometry, const TwkVertexSource* source, size_t numVertices);
+/* Pure CPU, no device: the records of a positions-mode source with recomputeFrames 1, with the code the kernel runs. positions:
+ * three floats per vertex; before / after: numVertices records (they may be the same array). TWK_ERROR_INVALID_VALUE: a NULL
+ * argument, numVertices 0, numIndices 0 or no multiple of three, an index beyond the vertices. */
+int twk_vertex_frames_host(const float* positions, size_t numVertices, const unsigned int* indices, size_t numIndices,
+                           const TwkTriangleAttributes* before, TwkTriangleAttributes* after);
+/* The geometry's current records, wherever they were last written (a device-pointer source leaves them on the device: one copy
+ * back). capacity: records `out` has room for. TWK_ERROR_INVALID_VALUE: a NULL argument, a bad id, a capacity below the count. */
+int twk_read_geometry_vertices(TwkDevice dev, int idGeometry, TwkTriangleAttributes* out, size_t capacity);
 /* One record per instance beside its TwkInstanceMotion (csrc/temporal_carry_device.h): previousObjectToWorld is the instance's
  * object-to-world matrix as of the history's frame, row-major 3 x 4; deformed = 0 says its geometry holds no previous positions and
  * nothing else is read; positionBase / indexBase: the first previous position / first index of its geometry in the arrays given. */

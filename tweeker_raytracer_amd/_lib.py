@@ -294,6 +294,13 @@ class RefitInfo(C.Structure):
                 ("milliseconds", C.c_double)]
 
 
+class VertexSource(C.Structure):
+    """≙ TwkVertexSource: vertices that live on the device (twk_update_geometry_vertices_device, twk_refit_geometry_vertices_device):
+    exactly one of attributes (48-byte records) and positions (x, y, z floats, positionStride bytes apart; 0 means 12) is set."""
+    _fields_ = [("attributes", C.c_void_p), ("positions", C.c_void_p), ("positionStride", C.c_size_t), ("recomputeFrames", C.c_uint),
+                ("reserved", C.c_uint * 3)]
+
+
 class UpdatePlan(C.Structure):
     """≙ TwkUpdatePlan: the layout of a scene and what a selective update of some of its instances touches (twk_update_plan_host)."""
     _fields_ = [("instances", C.c_int), ("flattenedInstances", C.c_int), ("directLeafInstances", C.c_int), ("enteredGeometries", C.c_int),
@@ -341,6 +348,7 @@ SYMBOLS = [
     "twk_update_geometry_vertices", "twk_get_geometry_deformed", "twk_vertex_update_plan_host", "twk_render_geometry_motion", "twk_get_previous_position_device_pointer",
     "twk_read_previous_positions", "twk_previous_positions_host",
     "twk_refit_geometry_vertices", "twk_get_refit_info", "twk_refit_tree_host", "twk_debug_read_kept_build",
+    "twk_update_geometry_vertices_device", "twk_refit_geometry_vertices_device", "twk_vertex_frames_host", "twk_read_geometry_vertices",
     "twk_temporal_accumulate_carried", "twk_temporal_accumulate_cascade_carried", "twk_temporal_carried_host", "twk_temporal_cascade_carried_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",

@@ -22,6 +22,7 @@
 #include "device_buffers.h"
 #include "update_plan.h"
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -83,9 +84,22 @@ static_assert(sizeof(DevMaterial) == 64, "MaterialDefinition is 64 B (material_d
 static_assert(sizeof(DevInstance) == 128, "instance record");
 static_assert(sizeof(BvhNode) == 64, "BVH2 node");
 
+// What a geometry holds on the device beside its slice of d_attributes once a device-pointer source has written that slice
+// (vertex_source_device.h; device_vertex_source.hip). mirrorStale: the slice is newer than GeometryHost::attributes — every reader of
+// the mirror calls refreshMirror first, and an upload of the mirror is skipped (the slice is what it would bring). The adjacency table
+// of the frames is built at the first call that recomputes them; d_kept holds the previous positions while
+// TwkDevice_t::previousOnDevice says so. All of it goes with the geometry (twk_clear_scene).
+struct GeometryDevice
+{
+  bool mirrorStale = false;
+  DeviceArray<unsigned int> d_adjacencyOffsets, d_adjacencyTriangles;
+  DeviceArray<float4> d_kept;
+};
+
 struct GeometryHost
 {
-  std::vector<TwkTriangleAttributes> attributes;
+  std::vector<TwkTriangleAttributes> attributes; // the host mirror of the geometry's slice of d_attributes (stale: GeometryDevice)
+  std::unique_ptr<GeometryDevice> device;
   std::vector<unsigned int>          indices;
   unsigned int attributeBase = 0, indexBase = 0;
   int triangleBase = 0, nodeBase = 0, numTriangles = 0;
@@ -209,7 +223,10 @@ struct TwkDevice_t
   // as of that frame (previousPositions[geometry], one float4 per vertex; empty: not deformed), until a merge swaps the history or
   // dropTemporal drops it. twk_render_geometry_motion (temporal_carry_device.h) uploads them packed (d_previousPositions) with the two
   // records per instance and writes the previous-position plane beside the geometry AOV; previousPlaneValid goes with geometryValid.
-  std::vector<std::vector<float4>> previousPositions;
+  // previousOnDevice[geometry]: the vector has its size (what says "deformed", and what the bases are summed from) but its content
+  // lives in the geometry's d_kept, written by the ingest kernel of a device-pointer source; twk_render_geometry_motion packs it with
+  // a device-to-device copy. Cleared with previousPositions.
+  std::vector<std::vector<float4>> previousPositions; std::vector<char> previousOnDevice;
   DeviceArray<float4> d_previousPositions, d_previousPlane; DeviceArray<TwkInstanceMotion> d_carryMotion; DeviceArray<TwkInstanceCarry> d_carry;
   bool previousPlaneValid = false;
   // what d_carryMotion and d_carry hold, and whether d_previousPositions holds previousPositions as they are: the uploads and the wait
@@ -314,6 +331,7 @@ struct TwkDevice_t
   // twk_refit_geometry_vertices: what the last refit did (valid until the next build), and the scratch of a tree's refit (bvh_build.h refitScratchWords)
   TwkRefitInfo refitInfo = {}; bool refitInfoValid = false;
   DeviceArray<unsigned int> d_refitScratch;
+  DeviceArray<unsigned int> d_sourceCheck; // one word: the lowest vertex of a device-pointer source whose position is not finite
 
   std::vector<std::vector<char>> hostScene; // twk_debug_snapshot_scene: host copies of the scene arrays
 
@@ -422,6 +440,10 @@ void dropTemporal(TwkDevice dev);
 // device_temporal_carry.hip
 void keepPreviousPositions(TwkDevice dev, int idGeometry);
 void dropPreviousPositions(TwkDevice dev, bool release);
+// device_vertex_source.hip
+int refreshMirror(TwkDevice dev, int idGeometry);
+int ingestVertexSource(TwkDevice dev, const char* name, bool refit, int idGeometry, const TwkVertexSource* source, size_t numVertices);
+inline bool mirrorStale(const GeometryHost& g) { return g.device && g.device->mirrorStale; }
 // device_temporal.hip
 int temporalParameters(const char* name, const TwkTemporal* tp, TemporalConstants& k);
 int temporalHistoryCamera(const char* name, const TwkCameraDefinition& camera, TemporalConstants& k);

@@ -318,6 +318,8 @@ static int buildScene(TwkDevice dev, bool keep)
   info.quality = dev->builder.quality();
   if ((rc = checkInstanceTables(dev))) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
+  // the mirrors a device-pointer source left stale, while the attribute array they are read from still stands (vertex_source_device.h)
+  for (size_t k = 0; k < dev->geometries.size(); ++k) if ((rc = refreshMirror(dev, (int) k))) return rc;
 
   // Which instances are flattened (include/tweeker_hip.h twk_set_flatten_policy): those of tiny geometries and those
   // whose geometry is referenced so rarely that instancing saves no memory worth the per-ray instance entry (ray
@@ -550,6 +552,7 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
   for (int k = 0; k < numUpdated; ++k)
   {
     const GeometryHost& g = dev->geometries[updated[k]];
+    if (mirrorStale(g)) continue; // a device-pointer source has written the slice already (vertex_source_device.h): it is what the upload would bring
     HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
   }
   TwkRefitInfo refitInfo;
@@ -726,8 +729,10 @@ static int replaceVertices(TwkDevice dev, const char* name, bool refit, int idGe
     if (dev->instances[i].geometry == idGeometry && dev->instances[i].light >= 0)
       return refuse(TWK_ERROR_INVALID_VALUE, "instance " + std::to_string(i) + " of the geometry carries a light (idLight >= 0): its light definition holds the emitter's shape and would disagree; deforming emitters is not supported");
   // nothing was changed up to here: a refused call changes nothing
+  if (dev->temporalHasHistory && (rc = refreshMirror(dev, idGeometry))) return rc; // keepPreviousPositions reads the mirror
   keepPreviousPositions(dev, idGeometry); // the positions as of the history's frame, before the first update since (device_temporal.hip)
   g.attributes.assign(attributes, attributes + numAttributes);
+  if (g.device) g.device->mirrorStale = false; // whole again, and newer than the slice a device-pointer source wrote: the upload brings it
   dev->updateInfoValid = false;
   return TWK_SUCCESS;
 }
@@ -753,6 +758,27 @@ try
   return updateSelective(dev, nullptr, 0, &idGeometry, 1, true);
 }
 TWK_CATCH("twk_refit_geometry_vertices")
+
+// The two calls with a device-pointer source (vertex_source_device.h; device_vertex_source.hip ingestVertexSource): the slice of
+// d_attributes is written on the device, and the rebuild or refit that follows is the one above
+int twk_update_geometry_vertices_device(TwkDevice dev, int idGeometry, const TwkVertexSource* source, size_t numVertices)
+try
+{
+  int rc = ingestVertexSource(dev, "twk_update_geometry_vertices_device", false, idGeometry, source, numVertices); if (rc) return rc;
+  if (dev->kept.valid) return updateSelective(dev, nullptr, 0, &idGeometry, 1);
+  if ((rc = buildScene(dev, false))) return rc; // reads the slice back into the mirror before the arrays are allocated again
+  recordUpdate(dev, false, 0, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, 0);
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_update_geometry_vertices_device")
+
+int twk_refit_geometry_vertices_device(TwkDevice dev, int idGeometry, const TwkVertexSource* source, size_t numVertices)
+try
+{
+  int rc = ingestVertexSource(dev, "twk_refit_geometry_vertices_device", true, idGeometry, source, numVertices); if (rc) return rc;
+  return updateSelective(dev, nullptr, 0, &idGeometry, 1, true);
+}
+TWK_CATCH("twk_refit_geometry_vertices_device")
 
 int twk_get_refit_info(TwkDevice dev, TwkRefitInfo* info)
 try

@@ -10,7 +10,7 @@
 // enqueued has run: the callers of dropTemporal wait first); else they stay for the next plane.
 void twk::dropPreviousPositions(TwkDevice dev, bool release)
 {
-  dev->previousPositions.clear(); dev->previousPlaneValid = false; dev->previousPositionsUploaded = false;
+  dev->previousPositions.clear(); dev->previousOnDevice.clear(); dev->previousPlaneValid = false; dev->previousPositionsUploaded = false;
   if (release) { dev->carryMotionUploaded.clear(); dev->carryUploaded.clear(); }
   if (release) { dev->d_previousPositions.release(); dev->d_previousPlane.release(); dev->d_carryMotion.release(); dev->d_carry.release(); }
 }
@@ -91,7 +91,11 @@ try
   if (!sameTables || !samePositions)
   {
     std::vector<float4> positions; // packed in geometry order, as the bases say
-    if (!samePositions)
+    // a geometry whose previous positions a device-pointer source kept (vertex_source_device.h) holds them on the device: it is
+    // packed by a device-to-device copy at its base, and the host vectors of the others are uploaded one by one
+    bool onDevice = false;
+    for (size_t k = 0; k < dev->previousOnDevice.size() && k < dev->previousPositions.size(); ++k) onDevice = onDevice || (dev->previousOnDevice[k] && !dev->previousPositions[k].empty());
+    if (!samePositions && !onDevice)
     {
       positions.reserve(numPositions);
       for (size_t k = 0; k < dev->previousPositions.size() && k < dev->geometries.size(); ++k) positions.insert(positions.end(), dev->previousPositions[k].begin(), dev->previousPositions[k].end());
@@ -102,6 +106,16 @@ try
     HIP_TRY(hipMemcpyAsync(dev->d_carryMotion, motion.data(), count * sizeof(TwkInstanceMotion), hipMemcpyHostToDevice, dev->stream));
     HIP_TRY(hipMemcpyAsync(dev->d_carry, carry.data(), count * sizeof(TwkInstanceCarry), hipMemcpyHostToDevice, dev->stream));
     if (!positions.empty()) HIP_TRY(hipMemcpyAsync(dev->d_previousPositions, positions.data(), positions.size() * sizeof(float4), hipMemcpyHostToDevice, dev->stream));
+    if (!samePositions && onDevice)
+      for (size_t k = 0; k < dev->previousPositions.size() && k < dev->geometries.size(); ++k)
+      {
+        const std::vector<float4>& kept = dev->previousPositions[k];
+        if (kept.empty()) continue;
+        const bool device = k < dev->previousOnDevice.size() && dev->previousOnDevice[k] != 0;
+        if (device && !(dev->geometries[k].device && dev->geometries[k].device->d_kept.holds(kept.size()))) return refuse("geometry " + std::to_string(k) + ": its kept previous positions are gone");
+        HIP_TRY(hipMemcpyAsync(dev->d_previousPositions + positionBase[k], device ? (const void*) dev->geometries[k].device->d_kept.get() : (const void*) kept.data(), kept.size() * sizeof(float4),
+                               device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, dev->stream));
+      }
     HIP_TRY(hipStreamSynchronize(dev->stream)); // (the tables are pageable host memory that goes out of use here)
     dev->carryMotionUploaded = motion; dev->carryUploaded = carry; dev->previousPositionsUploaded = true;
   }

@@ -118,6 +118,65 @@ def refit_tree_host(nodes, wideNodes, nodeCost, slots, pairFlags, attributes, in
     return {"nodes": n, "wideNodes": w, "nodeCost": cost, "slots": s, "shadeRecords": shade, "terms": (terms[0], terms[1]), "rootBounds": np.array(bounds, dtype=np.float32)}
 
 
+def vertex_frames_host(positions, indices, before):
+    """twk_vertex_frames_host (pure CPU): the records a positions-mode device source with recomputeFrames 1 leaves (csrc/
+    vertex_source_device.h) — positions float32 [n, 3], indices uint32, before float32 [n, 12] (the geometry's records before the call).
+    Returns float32 [n, 12]: vertex from positions, normal and tangent from the new positions, texcoord kept."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    old = np.ascontiguousarray(before, dtype=np.float32).reshape(-1, 12)
+    if old.shape[0] != pos.shape[0]:
+        raise ValueError("vertex_frames_host: one record per position")
+    out = np.empty_like(old)
+    L.check(L.lib.twk_vertex_frames_host(pos.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(pos.shape[0]), idx.ctypes.data_as(C.POINTER(C.c_uint)), C.c_size_t(idx.size),
+                                         old.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def _vertex_source(source, numVertices, positions, stride, recomputeFrames):
+    """(L.VertexSource, vertex count) of `source`: an integer device address (numVertices and, for positions, `positions=True` given),
+    or an object with data_ptr() (a torch tensor) or __cuda_array_interface__ — float32 [n, 12] contiguous: records; float32 [n, 3]
+    with unit stride along a row: positions, rows any multiple of 4 bytes >= 12 apart (a strided view is passed as it is, no copy)."""
+    if isinstance(source, (int, np.integer)):
+        if numVertices is None:
+            raise ValueError("a device address needs numVertices")
+        address, n, is_positions, row = int(source), int(numVertices), bool(positions), (0 if stride is None else int(stride))
+    else:
+        if hasattr(source, "data_ptr"):
+            shape, item = tuple(source.shape), source.element_size()
+            strides, address, kind = tuple(s * item for s in source.stride()), int(source.data_ptr()), str(source.dtype).split(".")[-1]
+        elif hasattr(source, "__cuda_array_interface__"):
+            cai = source.__cuda_array_interface__
+            shape, item, address, kind = tuple(cai["shape"]), int(cai["typestr"][2:]), int(cai["data"][0]), {"<f4": "float32"}.get(cai["typestr"], cai["typestr"])
+            strides = tuple(cai["strides"]) if cai.get("strides") else tuple(item * int(np.prod(shape[k + 1:])) for k in range(len(shape)))
+        else:
+            raise TypeError("a device vertex source is an address, or has data_ptr() or __cuda_array_interface__")
+        if kind != "float32" or len(shape) != 2 or shape[1] not in (3, 12):
+            raise ValueError(f"a device vertex source is float32 [n, 12] (records) or [n, 3] (positions), not {kind} {list(shape)}")
+        if strides[1] != 4:
+            raise ValueError(f"the floats of a vertex are 4 bytes apart, not {strides[1]}")
+        n, is_positions, row = shape[0], shape[1] == 3, strides[0]
+        if positions is not None and bool(positions) != is_positions:
+            raise ValueError("positions= disagrees with the source's shape")
+        if numVertices is not None and int(numVertices) != n:
+            raise ValueError(f"numVertices {numVertices} is not the source's {n}")
+        if is_positions and n > 1 and (row < 12 or row % 4):
+            raise ValueError(f"positions are {row} bytes apart: at least 12 and a multiple of 4")
+        if not is_positions and n > 1 and row != 48:
+            raise ValueError(f"records are {row} bytes apart, not 48: pass a contiguous [n, 12] tensor")
+        if stride is not None and is_positions and n > 1 and int(stride) != row:
+            raise ValueError("stride= disagrees with the source's strides")
+        row = row if is_positions and n > 1 else (0 if stride is None else int(stride))
+    src = L.VertexSource()
+    if is_positions:
+        src.positions, src.positionStride, src.recomputeFrames = address, row, 1 if recomputeFrames else 0
+    else:
+        if recomputeFrames:
+            raise ValueError("recomputeFrames goes with positions")
+        src.attributes = address
+    return src, n
+
+
 def device_count():
     n = C.c_int(0)
     L.check(L.lib.twk_device_count(C.byref(n)))
@@ -434,6 +493,28 @@ class Device:
         updateGeometryVertices rebuilds. TwkError: updateGeometryVertices' refusals, and a handle not built in selective mode."""
         attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
         L.check(L.lib.twk_refit_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
+
+    # ---- a device-pointer source (include/tweeker_hip.h "A device-pointer source", csrc/vertex_source_device.h) ----
+    def updateGeometryVerticesDevice(self, idGeometry, source, numVertices=None, positions=None, stride=None, recomputeFrames=False):
+        """twk_update_geometry_vertices_device: updateGeometryVertices from vertices that live on the device — `source` is a torch
+        tensor (or a strided view of one, passed without a copy), an object with __cuda_array_interface__, or an integer address with
+        numVertices: float32 [n, 12] records, or [n, 3] positions (recomputeFrames: normals and tangents follow the new positions,
+        else they stay; texcoords always stay). The source is read on the handle's stream: finish producing it first (synchronise the
+        stream that wrote it); on return it has been consumed. The handle then equals one given the same records through
+        updateGeometryVertices. TwkError: its refusals, a pointer that is not device memory, a position that is not finite."""
+        src, n = _vertex_source(source, numVertices, positions, stride, recomputeFrames)
+        L.check(L.lib.twk_update_geometry_vertices_device(self._h, int(idGeometry), C.byref(src), C.c_size_t(n)))
+
+    def refitGeometryVerticesDevice(self, idGeometry, source, numVertices=None, positions=None, stride=None, recomputeFrames=False):
+        """twk_refit_geometry_vertices_device: refitGeometryVertices from a device source (updateGeometryVerticesDevice's arguments)."""
+        src, n = _vertex_source(source, numVertices, positions, stride, recomputeFrames)
+        L.check(L.lib.twk_refit_geometry_vertices_device(self._h, int(idGeometry), C.byref(src), C.c_size_t(n)))
+
+    def readGeometryVertices(self, idGeometry, numVertices):
+        """twk_read_geometry_vertices: the geometry's current records, float32 [numVertices, 12], wherever they were last written."""
+        out = np.empty((int(numVertices), 12), np.float32)
+        L.check(L.lib.twk_read_geometry_vertices(self._h, int(idGeometry), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.shape[0])))
+        return out
 
     def refitInfo(self):
         """twk_get_refit_info: what the last refit did, a dict of L.RefitInfo's fields (treesRefit, treesRebuilt, topLevelRebuilt,

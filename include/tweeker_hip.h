@@ -969,7 +969,7 @@ int twk_get_instance_transform(TwkDevice dev, int idInstance, float transform[12
  * top level; no bottom-level tree is ever rebuilt. Afterwards the handle equals, byte for byte, a fresh handle built with the
  * current transforms. Everything else about an update is as "Moving an object" says: the temporal history stays, adaptive state is
  * dropped, the geometry AOV is stale, and an update that fails (an allocation, a HIP error, the depth refusal, with twk_build's
- * text) leaves the handle unbuilt until twk_build. What it is not: not a refit (a moved flattened instance gets a new tree; "Refit" below refits deformed meshes only), no vertex
+ * text) leaves the handle unbuilt until twk_build. What it is not: not a refit (a moved flattened instance gets a new tree; twk_refit_instance_transform, "Refit of a moved instance" below, is the call that keeps the tree), no vertex
  * updates by these calls (twk_update_geometry_vertices: "Deforming an object" below), no adding or removing of instances, no change of flatten policy or build quality between updates (those need twk_build),
  * no moving emitters. Measured: profiles/r24_selective_update.md. */
 #define TWK_UPDATE_FULL      0 /* default: an update rebuilds everything twk_build builds; nothing is kept */
@@ -1064,7 +1064,7 @@ int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, c
  * fresh build would choose: its quality decays as the mesh moves away from the vertices it was built from. TwkRefitInfo says by how
  * much — sahNow / sahBuilt — and the caller decides when to call twk_update_geometry_vertices, which rebuilds: there is no fallback
  * in the library. A refit with the vertices the tree was built from changes no byte; a refit back to them restores every byte.
- * What it is not: no refit of a MOVED flattened instance (transform updates stay rebuilds), no restructuring or rotations, no new
+ * What it is not: no refit of a MOVED flattened instance by THIS call (twk_refit_instance_transform, "Refit of a moved instance" below, is that call), no restructuring or rotations, no new
  * cuts, no topology change, no emitters, no tiled frames while a geometry is deformed, no device-pointer source in this call (twk_refit_geometry_vertices_device takes one), no rtigo3_hip key.
  * Additional refusal: TWK_ERROR_INVALID_STATE on a handle whose scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode
  * before twk_build): nothing a refit needs was kept. Measured: profiles/r28_refit.md (tools/refit_time.py). */
@@ -1101,6 +1101,48 @@ int twk_refit_tree_host(float* nodes, float* wideNodes, float* nodeCost, float* 
  * given with its count of elements. TWK_ERROR_INVALID_STATE: the handle is not built in TWK_UPDATE_SELECTIVE, or does not keep an
  * array that is asked for (no costed cuts, no pairs). TWK_ERROR_INVALID_VALUE: a NULL handle, a count that is not the array's. */
 int twk_debug_read_kept_build(TwkDevice dev, float* wide, size_t numWideFloats, float* nodeCost, size_t numNodeCost, int* pairFlags, size_t numPairFlags);
+/* ---- Refit of a moved instance: a dragged object without a tree build — new calls, ABI stays 9; every existing call launches what
+ * it launched ----------------------------------------------------------------------------------------------------------------------
+ * twk_refit_instance_transform[s] are twk_update_instance_transform[s] for a handle built in TWK_UPDATE_SELECTIVE: the same
+ * arguments, the same refusals in the same order with the same texts under their own names (a NULL handle or array before any HIP
+ * call, before twk_build, a bad id, a transform that is not finite or singular, an instance that carries a light, an id listed
+ * twice, count < 1; a refused batch changes nothing), and the same treatment of everything around the trees: the temporal history
+ * and the transforms as of its frame are kept — twk_read_temporal_motion and the merges work afterwards unchanged — adaptive state is
+ * dropped, the geometry AOV is stale. What each moved instance gets: an ENTERED one its world box in the top level, as in the
+ * selective update; a DIRECT-LEAF one (two triangles, a leaf of the top level itself) the rebuild's path, counted in treesRebuilt;
+ * every other FLATTENED one a REFIT IN PLACE of its world-space tree: every slot is written again from the primitive word it holds,
+ * through the new matrix, with the build's expression; every leaf box, inner box, wide node (with the cut it had) and node cost
+ * follows as csrc/bvh_refit.h defines; the SAH terms follow. The 128-byte shading records are not touched: they are object-space,
+ * and a transform does not change them. All trees of a call are refit by ONE launch sequence with ONE host wait
+ * (csrc/bvh_refit_batch.hip; csrc/refit_batch_plan.h plans it). Then the top level, the depth check, the 8-wide root, the ranged
+ * tail, the top caches, as in the selective update. twk_get_update_info (selective 1, instancesMoved = count, treesRebuilt = the
+ * direct leaves) and twk_get_refit_info describe the call; each refit tree's count of refits goes up by one.
+ * The result is a LEGAL scene for the new transforms, not a fresh build's. For a translation or a uniform scale the refit tree is
+ * the tree a rebuild would choose, moved; under a rotation or an unequal scale its boxes grow looser than a rebuild's, and
+ * TwkRefitInfo.sahNow / sahBuilt says by how much: the caller decides when to call twk_update_instance_transform, which rebuilds
+ * the tree and resets its count. There is no fallback in the library. A refit with the transforms the scene was built with changes
+ * no byte; a refit back to them restores every byte.
+ * What it is not: no restructuring, no new cuts, no automatic refit-or-rebuild choice, no moving emitters, no rtigo3_hip key; on a
+ * tiled frame every handle is moved by the same call, as for twk_update_instance_transform.
+ * Additional refusal, after "before twk_build": TWK_ERROR_INVALID_STATE on a handle whose scene was not built in
+ * TWK_UPDATE_SELECTIVE. Measured: profiles/r31_instance_refit.md (tools/instance_refit_time.py). */
+int twk_refit_instance_transform(TwkDevice dev, int idInstance, const float transform[12]);
+int twk_refit_instance_transforms(TwkDevice dev, int count, const int* idInstances, const float* transforms);
+/* Pure CPU, no device: how the trees of one batched refit share its launches (csrc/refit_batch_plan.h, the code the call plans
+ * with). Tree k has treeNodes[k] nodes and treeSlots[k] slots and occupies ceil(n / 256) consecutive node blocks and ceil(s / 256)
+ * consecutive slot blocks, so that no block straddles two trees. Out, each NULL or given: nodeOffsets / slotOffsets [numTrees] (the
+ * nodes / slots of the trees before it: where its parents and tickets / its soup descriptors stand), nodeBlockFirst /
+ * slotBlockFirst [numTrees] (its first block: where its partial sums stand), nodeBlocks [2 x plan->nodeBlocks] / slotBlocks
+ * [2 x plan->slotBlocks] (per block: its tree, the tree-local index of its first thread). The block counts are those sums of
+ * ceilings (or call once with the tables NULL). TWK_ERROR_INVALID_VALUE: a NULL input or plan, numTrees < 1, a tree with less than
+ * one node or slot, 2^31 or more nodes, slots or threads in all. */
+typedef struct TwkRefitBatchPlan
+{
+  int trees, nodeBlocks, slotBlocks, blockThreads;
+  uint64_t nodes, slots;
+} TwkRefitBatchPlan;
+int twk_refit_batch_plan_host(const int* treeNodes, const int* treeSlots, int numTrees, TwkRefitBatchPlan* plan, int* nodeOffsets, int* slotOffsets,
+                              int* nodeBlockFirst, int* slotBlockFirst, int* nodeBlocks, int* slotBlocks);
 /* ---- A device-pointer source for the vertices — new calls, ABI stays 9; every existing call launches what it launched ------------
  * twk_update_geometry_vertices_device and twk_refit_geometry_vertices_device are the two calls above for vertices that already live
  * on the device (skinning, cloth, a simulation step, a torch tensor; ≙ OptixBuildInputTriangleArray::vertexBuffers, a device pointer

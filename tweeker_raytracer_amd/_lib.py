@@ -294,6 +294,12 @@ class RefitInfo(C.Structure):
                 ("milliseconds", C.c_double)]
 
 
+class RefitBatchPlan(C.Structure):
+    """≙ TwkRefitBatchPlan: the totals of a batched refit's block plan (twk_refit_batch_plan_host)."""
+    _fields_ = [("trees", C.c_int), ("nodeBlocks", C.c_int), ("slotBlocks", C.c_int), ("blockThreads", C.c_int),
+                ("nodes", C.c_uint64), ("slots", C.c_uint64)]
+
+
 class VertexSource(C.Structure):
     """≙ TwkVertexSource: vertices that live on the device (twk_update_geometry_vertices_device, twk_refit_geometry_vertices_device):
     exactly one of attributes (48-byte records) and positions (x, y, z floats, positionStride bytes apart; 0 means 12) is set."""
@@ -348,6 +354,7 @@ SYMBOLS = [
     "twk_update_geometry_vertices", "twk_get_geometry_deformed", "twk_vertex_update_plan_host", "twk_render_geometry_motion", "twk_get_previous_position_device_pointer",
     "twk_read_previous_positions", "twk_previous_positions_host",
     "twk_refit_geometry_vertices", "twk_get_refit_info", "twk_refit_tree_host", "twk_debug_read_kept_build",
+    "twk_refit_instance_transform", "twk_refit_instance_transforms", "twk_refit_batch_plan_host",
     "twk_update_geometry_vertices_device", "twk_refit_geometry_vertices_device", "twk_vertex_frames_host", "twk_read_geometry_vertices",
     "twk_temporal_accumulate_carried", "twk_temporal_accumulate_cascade_carried", "twk_temporal_carried_host", "twk_temporal_cascade_carried_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",

@@ -1,5 +1,6 @@
 #pragma once
 #include "device_types.h"
+#include "refit_batch_plan.h"
 #include <vector>
 
 namespace twk {
@@ -35,6 +36,18 @@ size_t refitScratchWords(int numNodes);
 hipError_t launchRefitTree(hipStream_t stream, const float* attributes, const unsigned int* indices, const int4* soup, const DevInstance* instances,
                            BvhNode* nodes, BvhNode* wide, float* nodeCost, float4* triangles, float4* shadeTriangles, const int* pairFlags,
                            int nodeBase, int numNodes, int slotBase, int numSlots, unsigned int* scratch, float rootBounds[6], double terms[2]);
+
+// The refit of the world-space trees of MOVED flattened instances, all trees of a call in one launch sequence and one wait
+// (bvh_refit_batch.hip; refit_batch_plan.h plans the blocks): tree k has the nodes [nodeBase[k], + numNodes[k]) and the slots
+// [slotBase[k], + numSlots[k]), its soup descriptors stand at soup[plan.slotOffset[k]] (BvhBuilder::soupDescriptors from there), and
+// `instances` holds the new matrices. Every slot gets its three world-space float4 again — the shading records are not touched, a
+// transform does not change them — then boxes, wide nodes and node costs follow as in launchRefitTree. scratch:
+// refitBatchScratchWords(plan) words. Waits for the stream once; rootBounds[6 k ..] receives tree k's box, terms[2 k ..] its SAH
+// terms, bit-equal to what launchRefitTree returns for the tree alone.
+size_t refitBatchScratchWords(const RefitBatchPlan& plan);
+hipError_t launchRefitTrees(hipStream_t stream, const float* attributes, const unsigned int* indices, const int4* soup, const DevInstance* instances,
+                            BvhNode* nodes, BvhNode* wide, float* nodeCost, float4* triangles, const int* pairFlags, const RefitBatchPlan& plan,
+                            const int* nodeBase, const int* numNodes, const int* slotBase, const int* numSlots, unsigned int* scratch, float* rootBounds, double* terms);
 
 // Build primitives of a geometry's triangles for BvhBuilder::buildTriangles: triangles 2k, 2k + 1 with the index triples
 // (a, b, c), (c, d, a) — what every mesh generator emits per quad — are one primitive (first triangle | sign bit), every other

@@ -9,7 +9,8 @@
 // two children gives way to its own children, read from the references the wide node holds.
 // Written: every slot and its shading record (emitTriangle, as the build emits them), every leaf's box, every inner box as the
 // fminf / fmaxf union of its children's, every full-precision wide node with the cut it had, and nodeCost by refitKernel's formula for
-// that cut.
+// that cut. The refit of a tree whose INSTANCE moved (twk_refit_instance_transform, bvh_refit_batch.hip) writes the same, except that
+// it leaves the shading records alone: moveTriangle instead of emitTriangle.
 //
 // ---- a leaf's box (refitLeafBox) ------------------------------------------------------------------------------------------------
 // The build's rule: a leaf covers `count` consecutive slots; pairFlags groups them into build primitives (a pair is ONE primitive
@@ -182,6 +183,22 @@ TWK_HD void emitTriangle(const float* __restrict__ attributes, const unsigned in
   out[7] = make_float4(c[10], c[11], 0.0f, 0.0f);
 }
 
+// The slot of a world-space tree whose INSTANCE moved (twk_refit_instance_transform, bvh_refit_batch.hip): emitTriangle's three
+// world-space float4 through the matrix the instance record holds now, and nothing else. The shading record is built from the
+// object-space a, b, c alone (above: the geometric normal of the untransformed triangle, the vertices' normals, tangents and texture
+// coordinates as the geometry holds them) — a transform changes none of its 128 bytes, so it is neither read nor written.
+TWK_HD void moveTriangle(const float* __restrict__ attributes, const unsigned int* __restrict__ indices, const int4* __restrict__ soup,
+                         const DevInstance* __restrict__ instances, unsigned int prim, int slot, float4* __restrict__ triangles)
+{
+  const float *a, *b, *c;
+  const int4 d = soup[prim];
+  V3 wa, wb, wc;
+  soupVertices(d, attributes, indices, instances, a, b, c, wa, wb, wc);
+  triangles[3 * (size_t) slot + 0] = make_float4(wa.x, wa.y, wa.z, asFloat((uint32_t) d.w));
+  triangles[3 * (size_t) slot + 1] = make_float4(wb.x, wb.y, wb.z, asFloat((uint32_t) d.x));
+  triangles[3 * (size_t) slot + 2] = make_float4(wc.x, wc.y, wc.z, 0.0f);
+}
+
 // ---- the refit -------------------------------------------------------------------------------------------------------------------
 
 // One tree as a refit sees it. Every array is the TREE's: node nodeBase + i stands at nodes[i] (its wide node at wide[2 * i], its
@@ -193,6 +210,9 @@ struct RefitTree
   const float4* triangles; const int* pairFlags;
   int nodeBase, numNodes, slotBase, numSlots;
 };
+// One tree of a batched refit (bvh_refit_batch.hip), as the device table holds it: the tree, and where its parents and tickets
+// (nodeOffset) and its soup descriptors (slotOffset) stand among the batch's (refit_batch_plan.h). 64 bytes.
+struct RefitBatchTree { RefitTree tree; int nodeOffset, slotOffset; };
 
 TWK_HD void refitChildren(const BvhNode* node, int& c0, int& c1)
 {

@@ -485,6 +485,20 @@ static void recordUpdate(TwkDevice dev, bool selective, int moved, int trees, bo
   dev->updateInfoValid = true;
 }
 
+// A tree of geometry `geometry` over `nodes` nodes has been refit, with the SAH terms `now`: its terms (the height stays: a refit
+// changes no tree's height) and the call's record. A tree over one build primitive has no terms (sahTotals).
+static void countRefit(TwkDevice dev, const SceneState& state, int geometry, TwkDevice_t::TreeTerms& terms, const double now[2], int nodes, TwkRefitInfo& info)
+{
+  const size_t primitives = state.pairs ? state.primFirst[(size_t) geometry].size() : (size_t) dev->geometries[(size_t) geometry].numTriangles;
+  terms.refits += 1;
+  if (primitives > 1)
+  {
+    terms.sahInner = now[0]; terms.sahLeaf = now[1];
+    info.sahBuilt += terms.sahBuilt; info.sahNow += now[0] + now[1];
+  }
+  info.treesRefit += 1; info.nodesRefit += (uint64_t) nodes; info.refitsSinceBuild = std::max(info.refitsSinceBuild, terms.refits);
+}
+
 // The refit of one tree of geometry `geometry` at the node and slot bases given (bvh_refit.h): the bottom-level tree (soup nullptr) or
 // a flattened instance's world-space tree (soup: its descriptors). Its box goes to rootBounds, its new SAH terms into `terms` (the
 // height stays: a refit changes no tree's height), and the call into `info`. A tree over one build primitive has no terms (sahTotals).
@@ -498,14 +512,7 @@ static int refitTree(TwkDevice dev, SceneState& state, int geometry, TwkDevice_t
   HIP_TRY(launchRefitTree(dev->stream, soup ? dev->d_attributes.get() : dev->d_attributes + 12 * (size_t) g.attributeBase, soup ? dev->d_indices.get() : dev->d_indices + g.indexBase,
                           soup, soup ? dev->d_instances.get() : nullptr, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles, dev->d_shadeTriangles,
                           state.pairs ? dev->d_pairFlags.get() : nullptr, nodeBase, nodes, triangleBase, g.numTriangles, dev->d_refitScratch, rootBounds, now));
-  const size_t primitives = state.pairs ? state.primFirst[(size_t) geometry].size() : (size_t) g.numTriangles;
-  terms.refits += 1;
-  if (primitives > 1)
-  {
-    terms.sahInner = now[0]; terms.sahLeaf = now[1];
-    info.sahBuilt += terms.sahBuilt; info.sahNow += now[0] + now[1];
-  }
-  info.treesRefit += 1; info.nodesRefit += (uint64_t) nodes; info.refitsSinceBuild = std::max(info.refitsSinceBuild, terms.refits);
+  countRefit(dev, state, geometry, terms, now, nodes, info);
   return TWK_SUCCESS;
 }
 
@@ -519,7 +526,11 @@ static int refitTree(TwkDevice dev, SceneState& state, int geometry, TwkDevice_t
 // refit (twk_refit_geometry_vertices): the trees of the updated geometries are refit in place (refitTree, above) instead of zeroed and
 // rebuilt — all but a direct-leaf instance's, which has no tree of its own and takes the rebuild's path. The stages around the trees
 // are the same; the handle is then a legal scene for the new vertices, not a fresh build's.
-static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false)
+// refitMoved (twk_refit_instance_transform[s], with refit and no updated geometry): the world-space trees of the moved flattened
+// instances are refit too, but all in one batch (bvh_refit_batch.hip launchRefitTrees) behind the rebuilds of the direct leaves among
+// them: their soup descriptors at the running slot offsets of refit_batch_plan.h, one upload, one launch sequence, one wait, then
+// boxes and terms per tree. The shading records stay as they are: a transform does not change them.
+static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false, bool refitMoved = false)
 {
   int rc;
   SceneState& state = dev->kept;
@@ -576,10 +587,31 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
   }
   int maxTriangles = 0;
   for (int i : plan.trees) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
+  // the batch of a transform refit: every moved flattened instance with a tree of its own, ascending
+  std::vector<int> batch, batchNodeBase, batchNodes, batchSlotBase, batchSlots;
+  RefitBatchPlan batchPlan;
+  if (refitMoved)
+  {
+    for (int i : plan.trees)
+    {
+      if (layout.directLeaf[i]) continue;
+      const int triangles = geometryTriangles[instanceGeometry[i]];
+      batch.push_back(i);
+      batchNodeBase.push_back(layout.flatNodeBase[i]); batchNodes.push_back(treeNodes(triangles));
+      batchSlotBase.push_back(layout.flatTriangleBase[i]); batchSlots.push_back(triangles);
+    }
+    if (!batch.empty())
+    {
+      if (const char* why = refitBatchPlan(batchNodes.data(), batchSlots.data(), (int) batch.size(), batchPlan)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string("twk_build: the refit batch: ") + why);
+      maxTriangles = std::max(maxTriangles, (int) batchPlan.totalSlots); // the descriptors of all its trees, side by side
+      if ((rc = dev->d_refitScratch.ensure(refitBatchScratchWords(batchPlan)))) return rc;
+    }
+  }
   if (maxTriangles > 0 && (rc = dev->d_updateSoup.ensure((size_t) maxTriangles))) return rc;
   for (int i : plan.trees)
   {
     const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], triangles = geometryTriangles[instanceGeometry[i]], nodes = treeNodes(triangles);
+    if (refitMoved && !layout.directLeaf[i]) continue; // in the batch, below
     if (refit && !layout.directLeaf[i])
     {
       float bounds[6];
@@ -596,6 +628,28 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
     if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + triangleBase, 0, sizeof(int) * (size_t) triangles, dev->stream));
     if ((rc = buildFlattenedTree(dev, state, i, dev->d_updateSoup))) return rc;
     // its payload in the top level (its root, or its slots as a direct leaf) names bases, which do not move
+  }
+  if (!batch.empty())
+  {
+    // behind the rebuilds, in stream order: they used the first descriptors of d_updateSoup
+    for (size_t k = 0; k < batch.size(); ++k)
+    {
+      const GeometryHost& g = dev->geometries[instanceGeometry[batch[k]]];
+      dev->builder.soupDescriptors(dev->stream, dev->d_updateSoup, batchPlan.slotOffset[k], batchSlots[k], batch[k], (int) g.attributeBase, (int) g.indexBase);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<float> bounds(6 * batch.size());
+    std::vector<double> now(2 * batch.size());
+    HIP_TRY(launchRefitTrees(dev->stream, dev->d_attributes, dev->d_indices, dev->d_updateSoup, dev->d_instances, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles,
+                             state.pairs ? dev->d_pairFlags.get() : nullptr, batchPlan, batchNodeBase.data(), batchNodes.data(), batchSlotBase.data(), batchSlots.data(),
+                             dev->d_refitScratch, bounds.data(), now.data()));
+    for (size_t k = 0; k < batch.size(); ++k)
+    {
+      const int i = batch[k];
+      countRefit(dev, state, instanceGeometry[i], state.instanceTerms[i], &now[2 * k], batchNodes[k], refitInfo);
+      state.boxLo[i] = make_float4(bounds[6 * k], bounds[6 * k + 1], bounds[6 * k + 2], 0.0f);
+      state.boxHi[i] = make_float4(bounds[6 * k + 3], bounds[6 * k + 4], bounds[6 * k + 5], 0.0f);
+    }
   }
   // a moved entered instance: its box in the top level, nothing else — no bottom-level tree is rebuilt
   for (int k = 0; k < numMoved; ++k)
@@ -634,7 +688,8 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
 }
 
 // The body of twk_update_instance_transform (batch false: its texts) and of twk_update_instance_transforms (each refusal names its entry)
-static int updateTransforms(TwkDevice dev, const char* name, bool batch, int count, const int* ids, const float* transforms)
+// and of twk_refit_instance_transform[s] (refit: the same refusals in the same order and the refit's one more, then the refit path)
+static int updateTransforms(TwkDevice dev, const char* name, bool batch, int count, const int* ids, const float* transforms, bool refit = false)
 {
   const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
   // the batch's own arguments first, so that they are refused without the handle being looked at; the single call keeps its order
@@ -644,6 +699,8 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   if (!batch && !transforms) return refuse(TWK_ERROR_INVALID_VALUE, "NULL transform");
   int rc = activate(dev, name); if (rc) return rc;
   if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  if (refit && !dev->kept.valid)
+    return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
   for (int k = 0; k < count; ++k)
   {
     const std::string entry = batch ? "entry " + std::to_string(k) + ": " : "";
@@ -659,7 +716,7 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   for (int k = 0; k < count; ++k) memcpy(dev->instances[ids[k]].transform, transforms + 12 * (size_t) k, sizeof(float) * 12);
   dev->updateInfoValid = false; // an update that fails from here on leaves no record: twk_get_update_info describes a finished update
   // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
-  if (dev->kept.valid) return updateSelective(dev, ids, count);
+  if (dev->kept.valid) return updateSelective(dev, ids, count, nullptr, 0, refit, refit);
   if ((rc = buildScene(dev, false))) return rc;
   recordUpdate(dev, false, count, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, dev->instances.size());
   return TWK_SUCCESS;
@@ -863,6 +920,44 @@ try
   return updateTransforms(dev, "twk_update_instance_transforms", true, count, idInstances, transforms);
 }
 TWK_CATCH("twk_update_instance_transforms")
+
+int twk_refit_instance_transform(TwkDevice dev, int idInstance, const float transform[12])
+try
+{
+  return updateTransforms(dev, "twk_refit_instance_transform", false, 1, &idInstance, transform, true);
+}
+TWK_CATCH("twk_refit_instance_transform")
+
+int twk_refit_instance_transforms(TwkDevice dev, int count, const int* idInstances, const float* transforms)
+try
+{
+  return updateTransforms(dev, "twk_refit_instance_transforms", true, count, idInstances, transforms, true);
+}
+TWK_CATCH("twk_refit_instance_transforms")
+
+int twk_refit_batch_plan_host(const int* treeNodes, const int* treeSlots, int numTrees, TwkRefitBatchPlan* plan, int* nodeOffsets, int* slotOffsets,
+                              int* nodeBlockFirst, int* slotBlockFirst, int* nodeBlocks, int* slotBlocks)
+try
+{
+  const auto refuse = [](const std::string& text) { return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_refit_batch_plan_host: " + text); };
+  if (!plan || (numTrees > 0 && (!treeNodes || !treeSlots))) return refuse("NULL argument");
+  RefitBatchPlan p;
+  if (const char* why = refitBatchPlan(treeNodes, treeSlots, numTrees, p)) return refuse(why);
+  memset(plan, 0, sizeof(*plan));
+  plan->trees = numTrees; plan->nodeBlocks = p.totalNodeBlocks; plan->slotBlocks = p.totalSlotBlocks; plan->blockThreads = REFIT_BATCH_BLOCK;
+  plan->nodes = (uint64_t) p.totalNodes; plan->slots = (uint64_t) p.totalSlots;
+  for (int k = 0; k < numTrees; ++k)
+  {
+    if (nodeOffsets) nodeOffsets[k] = p.nodeOffset[(size_t) k];
+    if (slotOffsets) slotOffsets[k] = p.slotOffset[(size_t) k];
+    if (nodeBlockFirst) nodeBlockFirst[k] = p.nodeBlockFirst[(size_t) k];
+    if (slotBlockFirst) slotBlockFirst[k] = p.slotBlockFirst[(size_t) k];
+  }
+  if (nodeBlocks) for (size_t b = 0; b < p.nodeBlocks.size(); ++b) { nodeBlocks[2 * b] = p.nodeBlocks[b].tree; nodeBlocks[2 * b + 1] = p.nodeBlocks[b].first; }
+  if (slotBlocks) for (size_t b = 0; b < p.slotBlocks.size(); ++b) { slotBlocks[2 * b] = p.slotBlocks[b].tree; slotBlocks[2 * b + 1] = p.slotBlocks[b].first; }
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_refit_batch_plan_host")
 
 int twk_set_update_mode(TwkDevice dev, int mode)
 try

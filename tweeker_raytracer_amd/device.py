@@ -71,6 +71,27 @@ def vertex_update_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, 
     return out
 
 
+def refit_batch_plan_host(treeNodes, treeSlots):
+    """twk_refit_batch_plan_host (pure CPU): how trees of treeNodes[k] nodes and treeSlots[k] slots share the launches of one batched
+    refit (csrc/refit_batch_plan.h). Returns a dict: L.RefitBatchPlan's fields, nodeOffsets / slotOffsets / nodeBlockFirst /
+    slotBlockFirst (int32 per tree) and nodeBlockTable / slotBlockTable (int32 [blocks, 2]: the block's tree, the tree-local index of its
+    first thread)."""
+    n = np.ascontiguousarray(treeNodes, dtype=np.int32).reshape(-1)
+    s = np.ascontiguousarray(treeSlots, dtype=np.int32).reshape(-1)
+    if n.size != s.size:
+        raise ValueError("refit_batch_plan_host: one node count and one slot count per tree")
+    ip = C.POINTER(C.c_int)
+    at = lambda a: a.ctypes.data_as(ip) if a.size else None
+    plan = L.RefitBatchPlan()
+    L.check(L.lib.twk_refit_batch_plan_host(at(n), at(s), int(n.size), C.byref(plan), None, None, None, None, None, None))  # the totals first
+    per_tree = [np.zeros(n.size, np.int32) for _ in range(4)]
+    nodeBlocks, slotBlocks = np.zeros((plan.nodeBlocks, 2), np.int32), np.zeros((plan.slotBlocks, 2), np.int32)
+    L.check(L.lib.twk_refit_batch_plan_host(at(n), at(s), int(n.size), C.byref(plan), *[at(a) for a in per_tree], at(nodeBlocks), at(slotBlocks)))
+    out = {name: getattr(plan, name) for name, _ in L.RefitBatchPlan._fields_}
+    out.update(zip(("nodeOffsets", "slotOffsets", "nodeBlockFirst", "slotBlockFirst"), per_tree), nodeBlockTable=nodeBlocks, slotBlockTable=slotBlocks)
+    return out
+
+
 def previous_positions_host(hits, instance, primitive, geometry, indices, previousPositions, motion=None, carry=None):
     """twk_previous_positions_host (pure CPU): the previous-position plane of twk_render_geometry_motion from host arrays — hits
     float32 [n, 3] (t, beta, gamma), instance and primitive int32 [n] (instance < 0: a miss), geometry float32 [n, 4] (the geometry
@@ -493,6 +514,25 @@ class Device:
         updateGeometryVertices rebuilds. TwkError: updateGeometryVertices' refusals, and a handle not built in selective mode."""
         attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
         L.check(L.lib.twk_refit_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
+
+    # ---- refit of a moved instance (include/tweeker_hip.h "Refit of a moved instance", csrc/bvh_refit_batch.hip) ----
+    def refitInstanceTransform(self, idInstance, transform):
+        """twk_refit_instance_transform: updateInstanceTransform on a handle built in selective mode, but the world-space tree of a
+        moved flattened instance is refit in place — slots through the new matrix, boxes, wide nodes and costs updated, topology,
+        cuts and shading records kept — instead of rebuilt (a direct leaf is rebuilt, an entered instance gets its world box).
+        refitInfo says how far the SAH cost has drifted; updateInstanceTransform rebuilds. TwkError: updateInstanceTransform's
+        refusals, and a handle not built in selective mode."""
+        t = (C.c_float * 12)(*[float(x) for x in np.asarray(transform, dtype=np.float32).reshape(12)])
+        L.check(L.lib.twk_refit_instance_transform(self._h, int(idInstance), t))
+
+    def refitInstanceTransforms(self, ids, transforms):
+        """twk_refit_instance_transforms: several moves (updateInstanceTransforms' arguments and refusals), every moved tree refit
+        by one launch sequence and one host wait. A refused batch changes nothing."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1)
+        if t.size != 12 * ids.size:
+            raise ValueError("refitInstanceTransforms: 12 floats per id")
+        L.check(L.lib.twk_refit_instance_transforms(self._h, int(ids.size), ids.ctypes.data_as(C.POINTER(C.c_int)), t.ctypes.data_as(C.POINTER(C.c_float))))
 
     # ---- a device-pointer source (include/tweeker_hip.h "A device-pointer source", csrc/vertex_source_device.h) ----
     def updateGeometryVerticesDevice(self, idGeometry, source, numVertices=None, positions=None, stride=None, recomputeFrames=False):

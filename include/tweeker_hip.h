@@ -1187,6 +1187,77 @@ int twk_vertex_frames_host(const float* positions, size_t numVertices, const uns
 /* The geometry's current records, wherever they were last written (a device-pointer source leaves them on the device: one copy
  * back). capacity: records `out` has room for. TWK_ERROR_INVALID_VALUE: a NULL argument, a bad id, a capacity below the count. */
 int twk_read_geometry_vertices(TwkDevice dev, int idGeometry, TwkTriangleAttributes* out, size_t capacity);
+/* ---- A frame's edits in one call: deformed meshes and moved instances — new calls, ABI stays 9; every existing call launches what
+ * it launched ----------------------------------------------------------------------------------------------------------------------
+ * twk_refit_scene takes what a frame edits — numGeometries geometries with new vertices, each from host records (attributes) or from
+ * a device source (source; "A device-pointer source" above), and numInstances instances with new transforms — and refits the handle
+ * ONCE. THE SEQUENCE it stands for: twk_refit_geometry_vertices or twk_refit_geometry_vertices_device for every geometry entry in
+ * the order given, then twk_refit_instance_transforms for the instances. After twk_refit_scene the handle holds, byte for byte, what
+ * the sequence leaves: binary and quantised nodes, slots, shading records, instance records, both top-level caches, the kept arrays
+ * (twk_debug_read_kept_build), the attribute array (twk_read_geometry_vertices), twk_get_instance_transform, the previous positions
+ * and the transform snapshot of the temporal history, every picture — a refit tree is a function of its topology, the vertices and
+ * the matrix alone. What differs is the bookkeeping: every tree is refit once, so its count of refits goes up by ONE (also the tree
+ * of an instance that is both moved and of an edited geometry), and TwkRefitInfo / TwkUpdateInfo describe the one call — treesRefit,
+ * nodesRefit, sahBuilt and sahNow count each refit tree once, treesRebuilt the direct-leaf instances (the rebuild's path, as in the
+ * calls above), slotsRewritten the slots of all those trees, instancesMoved = numInstances. (TwkUpdateInfo.keptBytes may be lower than
+ * after the sequence: the call writes no soup descriptors and so never grows that scratch.)
+ * Each instance gets what its kind needs: a moved or edited ENTERED one its world box (from its geometry's new root box where that
+ * was refit in this call), a DIRECT LEAF the rebuild, every other FLATTENED one a refit in place. All refit trees — bottom-level
+ * trees of edited geometries, world-space trees of instances of edited geometries, world-space trees of moved instances — go through
+ * ONE upload, five launches, one read-back and ONE host wait, whatever their number and kinds (csrc/bvh_refit_scene.hip;
+ * csrc/refit_scene_plan.h says which tree is of which kind): the slot kernel makes every soup descriptor in registers, so no
+ * descriptor launch runs per tree. All device sources are checked before anything is written: one check launch per source into one
+ * result array, ONE read-back and wait, then the ingest launches. The stages around the trees (top level, depth check, 8-wide root,
+ * ranged tail, top caches) run once, as in the selective update. numGeometries == 0 makes the call twk_refit_instance_transforms;
+ * numInstances == 0 with one entry makes it the vertex refit.
+ * STREAM RULE: as for a device-pointer source — every source is read on the handle's stream, must have been produced before the
+ * call, and has been consumed on return.
+ * What it is not: no rebuilding counterpart, no asynchronous form (the batch's wait and the selective update's own waits stay), no
+ * emitters, no topology change, no restructuring or new cuts, no automatic refit-or-rebuild choice, no tiled frames while a geometry
+ * is deformed, no rtigo3_hip key; the four refit calls above keep their own launches.
+ * Refusals, all under the name twk_refit_scene, in this order, after which nothing has changed:
+ *  1. TWK_ERROR_INVALID_VALUE: a negative count, both counts 0, a NULL array with a positive count;
+ *  2. a NULL handle; TWK_ERROR_INVALID_STATE: before twk_build, a handle not built in TWK_UPDATE_SELECTIVE;
+ *  3. per geometry entry in order, "geometry entry k: " in front: neither or both of attributes and source, reserved not 0, a
+ *     geometry listed twice; then the texts of twk_refit_geometry_vertices for a host entry (a bad id, a wrong vertex count, a
+ *     position that is not finite, an instance of the geometry that carries a light) or of twk_refit_geometry_vertices_device for a
+ *     device entry (those, and the source's own: both pointers or neither, a reserved word, recomputeFrames, the stride, the
+ *     alignment, memory the device cannot read, an allocation that ends early, an overlap with the handle's attribute array);
+ *  4. per instance entry, "entry k: " in front, the texts of twk_refit_instance_transforms (a bad id, a transform that is not finite
+ *     or singular, an instance that carries a light, an id listed twice);
+ *  5. last, a device source with a position that is not finite: "geometry entry k: vertex v: the position is not finite", k the
+ *     lowest such entry and v its lowest such vertex.
+ * Measured: profiles/r32_scene_refit.md (tools/scene_refit_time.py). */
+typedef struct TwkGeometryEdit
+{
+  int32_t  idGeometry;
+  uint32_t reserved;                        /* 0 */
+  uint64_t numVertices;
+  const TwkTriangleAttributes* attributes;  /* host records, or NULL */
+  const TwkVertexSource*       source;      /* device source, or NULL; exactly one of the two */
+} TwkGeometryEdit;                          /* 32 bytes */
+int twk_refit_scene(TwkDevice dev, int numGeometries, const TwkGeometryEdit* geometries, int numInstances, const int* idInstances, const float* transforms);
+/* Pure CPU, no device: the batch of a twk_refit_scene call on a scene laid out as twk_vertex_update_plan_host lays it out
+ * (csrc/refit_scene_plan.h, the code the call plans with), for the instances `moved` and the geometries `updatedGeometries`. The
+ * trees in batch order: the bottom-level trees of the updated entered geometries, ascending, listed as ~geometry, then the plan's
+ * flattened instances that are no direct leaves, ascending. Out, each NULL or given, [plan->trees] (at most numGeometries +
+ * numInstances): trees, kinds (0: bottom-level tree of an edited geometry, 176 bytes written per slot; 1: world-space tree of an
+ * instance of an edited geometry, 176; 2: world-space tree of a moved instance of an unedited geometry, 48), nodeBases / nodeCounts /
+ * slotBases / slotCounts (its ranges in the scene's arrays), and twk_refit_batch_plan_host's tables for those trees: nodeOffsets,
+ * slotOffsets, nodeBlockFirst, slotBlockFirst, nodeBlocks [2 x plan->nodeBlocks], slotBlocks [2 x plan->slotBlocks] (call once with
+ * the tables NULL for the counts). plan: the totals — directLeaves: instances that take the rebuild's path; boxes: entered instances
+ * whose world box is written; slotsRewritten: the slots of the batch and of the direct leaves; slotBytes: bytes the slot kernel
+ * writes. Refusals: twk_vertex_update_plan_host's, and 2^31 or more nodes, slots or threads in the batch. */
+typedef struct TwkSceneRefitPlan
+{
+  int trees, nodeBlocks, slotBlocks, blockThreads;
+  int directLeaves, boxes, topLevelRebuilt, reserved;
+  uint64_t nodes, slots, slotsRewritten, slotBytes;
+} TwkSceneRefitPlan;
+int twk_scene_refit_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                              int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,
+                              TwkSceneRefitPlan* plan, int* trees, int* kinds, int* nodeBases, int* nodeCounts, int* slotBases, int* slotCounts,
+                              int* nodeOffsets, int* slotOffsets, int* nodeBlockFirst, int* slotBlockFirst, int* nodeBlocks, int* slotBlocks);
 /* One record per instance beside its TwkInstanceMotion (csrc/temporal_carry_device.h): previousObjectToWorld is the instance's
  * object-to-world matrix as of the history's frame, row-major 3 x 4; deformed = 0 says its geometry holds no previous positions and
  * nothing else is read; positionBase / indexBase: the first previous position / first index of its geometry in the arrays given. */

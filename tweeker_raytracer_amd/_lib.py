@@ -307,6 +307,19 @@ class VertexSource(C.Structure):
                 ("reserved", C.c_uint * 3)]
 
 
+class GeometryEdit(C.Structure):
+    """≙ TwkGeometryEdit: one geometry entry of twk_refit_scene — host records (attributes) or a device source (source: a pointer to a
+    VertexSource), exactly one of the two."""
+    _fields_ = [("idGeometry", C.c_int32), ("reserved", C.c_uint32), ("numVertices", C.c_uint64), ("attributes", C.c_void_p), ("source", C.POINTER(VertexSource))]
+
+
+class SceneRefitPlan(C.Structure):
+    """≙ TwkSceneRefitPlan: the totals of a twk_refit_scene call's batch (twk_scene_refit_plan_host)."""
+    _fields_ = [("trees", C.c_int), ("nodeBlocks", C.c_int), ("slotBlocks", C.c_int), ("blockThreads", C.c_int),
+                ("directLeaves", C.c_int), ("boxes", C.c_int), ("topLevelRebuilt", C.c_int), ("reserved", C.c_int),
+                ("nodes", C.c_uint64), ("slots", C.c_uint64), ("slotsRewritten", C.c_uint64), ("slotBytes", C.c_uint64)]
+
+
 class UpdatePlan(C.Structure):
     """≙ TwkUpdatePlan: the layout of a scene and what a selective update of some of its instances touches (twk_update_plan_host)."""
     _fields_ = [("instances", C.c_int), ("flattenedInstances", C.c_int), ("directLeafInstances", C.c_int), ("enteredGeometries", C.c_int),
@@ -356,6 +369,7 @@ SYMBOLS = [
     "twk_refit_geometry_vertices", "twk_get_refit_info", "twk_refit_tree_host", "twk_debug_read_kept_build",
     "twk_refit_instance_transform", "twk_refit_instance_transforms", "twk_refit_batch_plan_host",
     "twk_update_geometry_vertices_device", "twk_refit_geometry_vertices_device", "twk_vertex_frames_host", "twk_read_geometry_vertices",
+    "twk_refit_scene", "twk_scene_refit_plan_host",
     "twk_temporal_accumulate_carried", "twk_temporal_accumulate_cascade_carried", "twk_temporal_carried_host", "twk_temporal_cascade_carried_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",

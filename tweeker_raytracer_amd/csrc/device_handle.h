@@ -443,6 +443,10 @@ void dropPreviousPositions(TwkDevice dev, bool release);
 // device_vertex_source.hip
 int refreshMirror(TwkDevice dev, int idGeometry);
 int ingestVertexSource(TwkDevice dev, const char* name, bool refit, int idGeometry, const TwkVertexSource* source, size_t numVertices);
+// its two halves, for twk_refit_scene, which checks every entry before it writes any: what the check and ingest launches are given
+struct VertexSourceView { const void* pointer = nullptr; size_t stride = 0; bool records = false, recompute = false; };
+int checkVertexSource(TwkDevice dev, const std::string& where, int idGeometry, const TwkVertexSource* source, size_t numVertices, VertexSourceView& view);
+int storeVertexSource(TwkDevice dev, int idGeometry, const VertexSourceView& view);
 inline bool mirrorStale(const GeometryHost& g) { return g.device && g.device->mirrorStale; }
 // device_temporal.hip
 int temporalParameters(const char* name, const TwkTemporal* tp, TemporalConstants& k);

@@ -3,6 +3,8 @@
 #include "device_handle.h"
 #include "temporal_motion_device.h" // instanceTransformUsable
 #include "bvh_refit.h"              // the host form of a tree's refit
+#include "bvh_refit_scene.h"        // the batch of a twk_refit_scene call
+#include "vertex_source_device.h"   // the finite check of twk_refit_scene's device sources
 
 #include <algorithm>
 #include <chrono>
@@ -530,7 +532,12 @@ static int refitTree(TwkDevice dev, SceneState& state, int geometry, TwkDevice_t
 // instances are refit too, but all in one batch (bvh_refit_batch.hip launchRefitTrees) behind the rebuilds of the direct leaves among
 // them: their soup descriptors at the running slot offsets of refit_batch_plan.h, one upload, one launch sequence, one wait, then
 // boxes and terms per tree. The shading records stay as they are: a transform does not change them.
-static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false, bool refitMoved = false)
+// refitAll (twk_refit_scene, with refit): every tree the plan names but a direct leaf's — the bottom-level trees of the updated
+// geometries, the world-space trees of their flattened instances and of the moved flattened instances — is refit ONCE, all in one
+// batch of mixed kinds (refit_scene_plan.h; bvh_refit_scene.hip launchRefitSceneTrees) behind the rebuilds of the direct leaves. No
+// soup descriptor is written for the batch: its slot kernel makes each in registers.
+static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false, bool refitMoved = false,
+                           bool refitAll = false)
 {
   int rc;
   SceneState& state = dev->kept;
@@ -572,6 +579,7 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
   {
     GeometryHost& g = dev->geometries[k];
     const int nodes = treeNodes(g.numTriangles);
+    if (refitAll) continue; // in the scene's batch, below
     if (refit)
     {
       if ((rc = refitTree(dev, state, k, state.geometryTerms[k], nullptr, g.nodeBase, g.triangleBase, g.rootBounds, refitInfo))) return rc;
@@ -607,11 +615,21 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
       if ((rc = dev->d_refitScratch.ensure(refitBatchScratchWords(batchPlan)))) return rc;
     }
   }
+  // the batch of a scene refit: the plan's trees by kind, in refit_scene_plan.h's order
+  RefitScenePlan scenePlan;
+  if (refitAll)
+  {
+    if (const char* why = refitScenePlan(layout, instanceGeometry.data(), geometryTriangles.data(), plan, moved, numMoved, updated, numUpdated, scenePlan))
+      return twkSetError(TWK_ERROR_INVALID_VALUE, std::string("twk_refit_scene: the refit batch: ") + why); // twk_refit_scene has planned the same batch before it stored anything: never taken
+    maxTriangles = 0; // descriptors for the rebuilds of the direct leaves only
+    for (int i : scenePlan.directLeaves) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
+    if (!scenePlan.tree.empty() && (rc = dev->d_refitScratch.ensure(refitSceneScratchWords(scenePlan)))) return rc;
+  }
   if (maxTriangles > 0 && (rc = dev->d_updateSoup.ensure((size_t) maxTriangles))) return rc;
   for (int i : plan.trees)
   {
     const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], triangles = geometryTriangles[instanceGeometry[i]], nodes = treeNodes(triangles);
-    if (refitMoved && !layout.directLeaf[i]) continue; // in the batch, below
+    if ((refitMoved || refitAll) && !layout.directLeaf[i]) continue; // in the batch, below
     if (refit && !layout.directLeaf[i])
     {
       float bounds[6];
@@ -647,6 +665,35 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
     {
       const int i = batch[k];
       countRefit(dev, state, instanceGeometry[i], state.instanceTerms[i], &now[2 * k], batchNodes[k], refitInfo);
+      state.boxLo[i] = make_float4(bounds[6 * k], bounds[6 * k + 1], bounds[6 * k + 2], 0.0f);
+      state.boxHi[i] = make_float4(bounds[6 * k + 3], bounds[6 * k + 4], bounds[6 * k + 5], 0.0f);
+    }
+  }
+  if (!scenePlan.tree.empty())
+  {
+    // behind the rebuilds, in stream order; the bottom-level trees first, so that the boxes below see the new root boxes
+    const size_t numTrees = scenePlan.tree.size();
+    std::vector<RefitSceneKind> kinds(numTrees);
+    for (size_t k = 0; k < numTrees; ++k)
+    {
+      const GeometryHost& g = dev->geometries[scenePlan.geometry[k]];
+      kinds[k] = {scenePlan.kind[k], scenePlan.kind[k] == REFIT_SCENE_GEOMETRY ? -1 : scenePlan.tree[k], (int) g.attributeBase, (int) g.indexBase};
+    }
+    std::vector<float> bounds(6 * numTrees);
+    std::vector<double> now(2 * numTrees);
+    HIP_TRY(launchRefitSceneTrees(dev->stream, dev->d_attributes, dev->d_indices, dev->d_instances, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles,
+                                  dev->d_shadeTriangles, state.pairs ? dev->d_pairFlags.get() : nullptr, scenePlan, kinds.data(), dev->d_refitScratch, bounds.data(), now.data()));
+    for (size_t k = 0; k < numTrees; ++k)
+    {
+      const int geometry = scenePlan.geometry[k];
+      if (scenePlan.kind[k] == REFIT_SCENE_GEOMETRY)
+      {
+        countRefit(dev, state, geometry, state.geometryTerms[geometry], &now[2 * k], scenePlan.nodes[k], refitInfo);
+        memcpy(dev->geometries[geometry].rootBounds, &bounds[6 * k], sizeof(float) * 6);
+        continue;
+      }
+      const int i = scenePlan.tree[k];
+      countRefit(dev, state, geometry, state.instanceTerms[i], &now[2 * k], scenePlan.nodes[k], refitInfo);
       state.boxLo[i] = make_float4(bounds[6 * k], bounds[6 * k + 1], bounds[6 * k + 2], 0.0f);
       state.boxHi[i] = make_float4(bounds[6 * k + 3], bounds[6 * k + 4], bounds[6 * k + 5], 0.0f);
     }
@@ -687,6 +734,24 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
   return TWK_SUCCESS;
 }
 
+// The entries of a transform call on a built handle, each refused with the transform update's text (batch: "entry k: " in front)
+static int checkTransformEntries(TwkDevice dev, const char* name, bool batch, int count, const int* ids, const float* transforms)
+{
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  for (int k = 0; k < count; ++k)
+  {
+    const std::string entry = batch ? "entry " + std::to_string(k) + ": " : "";
+    const int id = ids[k];
+    const float* transform = transforms + 12 * (size_t) k;
+    if (id < 0 || id >= (int) dev->instances.size()) return refuse(TWK_ERROR_INVALID_VALUE, entry + "bad instance id");
+    if (!instanceTransformUsable(transform)) return refuse(TWK_ERROR_INVALID_VALUE, entry + "the transform is not finite, or its 3 x 3 determinant is zero or not finite");
+    if (dev->instances[id].light >= 0)
+      return refuse(TWK_ERROR_INVALID_VALUE, entry + "the instance carries a light (idLight >= 0): its light definition holds the emitter's position and would disagree; moving emitters is not supported");
+    for (int j = 0; j < k; ++j) if (ids[j] == id) return refuse(TWK_ERROR_INVALID_VALUE, entry + "instance " + std::to_string(id) + " is listed twice (also entry " + std::to_string(j) + ")");
+  }
+  return TWK_SUCCESS;
+}
+
 // The body of twk_update_instance_transform (batch false: its texts) and of twk_update_instance_transforms (each refusal names its entry)
 // and of twk_refit_instance_transform[s] (refit: the same refusals in the same order and the refit's one more, then the refit path)
 static int updateTransforms(TwkDevice dev, const char* name, bool batch, int count, const int* ids, const float* transforms, bool refit = false)
@@ -701,17 +766,7 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
   if (refit && !dev->kept.valid)
     return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
-  for (int k = 0; k < count; ++k)
-  {
-    const std::string entry = batch ? "entry " + std::to_string(k) + ": " : "";
-    const int id = ids[k];
-    const float* transform = transforms + 12 * (size_t) k;
-    if (id < 0 || id >= (int) dev->instances.size()) return refuse(TWK_ERROR_INVALID_VALUE, entry + "bad instance id");
-    if (!instanceTransformUsable(transform)) return refuse(TWK_ERROR_INVALID_VALUE, entry + "the transform is not finite, or its 3 x 3 determinant is zero or not finite");
-    if (dev->instances[id].light >= 0)
-      return refuse(TWK_ERROR_INVALID_VALUE, entry + "the instance carries a light (idLight >= 0): its light definition holds the emitter's position and would disagree; moving emitters is not supported");
-    for (int j = 0; j < k; ++j) if (ids[j] == id) return refuse(TWK_ERROR_INVALID_VALUE, entry + "instance " + std::to_string(id) + " is listed twice (also entry " + std::to_string(j) + ")");
-  }
+  if ((rc = checkTransformEntries(dev, name, batch, count, ids, transforms))) return rc;
   // nothing was changed up to here: a refused batch changes nothing
   for (int k = 0; k < count; ++k) memcpy(dev->instances[ids[k]].transform, transforms + 12 * (size_t) k, sizeof(float) * 12);
   dev->updateInfoValid = false; // an update that fails from here on leaves no record: twk_get_update_info describes a finished update
@@ -764,6 +819,36 @@ static int updatePlanHost(const char* name, const int* instanceGeometry, int num
   return TWK_SUCCESS;
 }
 
+// A geometry's new host records, refused with the vertex update's texts behind `where` (the call's name, and its entry in twk_refit_scene)
+static int checkVertices(TwkDevice dev, const std::string& where, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
+{
+  const auto refuse = [&where](int code, const std::string& text) { return twkSetError(code, where + text); };
+  if (idGeometry < 0 || idGeometry >= (int) dev->geometries.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad geometry id");
+  const GeometryHost& g = dev->geometries[idGeometry];
+  if (numAttributes != g.attributes.size())
+    return refuse(TWK_ERROR_INVALID_VALUE, "the geometry has " + std::to_string(g.attributes.size()) + " vertices, not " + std::to_string(numAttributes) + " (the indices stay: no topology change)");
+  for (size_t v = 0; v < numAttributes; ++v)
+    if (!std::isfinite(attributes[v].vertex[0]) || !std::isfinite(attributes[v].vertex[1]) || !std::isfinite(attributes[v].vertex[2]))
+      return refuse(TWK_ERROR_INVALID_VALUE, "vertex " + std::to_string(v) + ": the position is not finite");
+  for (size_t i = 0; i < dev->instances.size(); ++i)
+    if (dev->instances[i].geometry == idGeometry && dev->instances[i].light >= 0)
+      return refuse(TWK_ERROR_INVALID_VALUE, "instance " + std::to_string(i) + " of the geometry carries a light (idLight >= 0): its light definition holds the emitter's shape and would disagree; deforming emitters is not supported");
+  return TWK_SUCCESS;
+}
+
+// ... and, once nothing is refused any more, the previous positions kept and the new vertices on the host
+static int storeVertices(TwkDevice dev, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
+{
+  int rc;
+  GeometryHost& g = dev->geometries[idGeometry];
+  if (dev->temporalHasHistory && (rc = refreshMirror(dev, idGeometry))) return rc; // keepPreviousPositions reads the mirror
+  keepPreviousPositions(dev, idGeometry); // the positions as of the history's frame, before the first update since (device_temporal.hip)
+  g.attributes.assign(attributes, attributes + numAttributes);
+  if (g.device) g.device->mirrorStale = false; // whole again, and newer than the slice a device-pointer source wrote: the upload brings it
+  dev->updateInfoValid = false;
+  return TWK_SUCCESS;
+}
+
 // The front half of twk_update_geometry_vertices and of twk_refit_geometry_vertices (refit: its one refusal more): the refusals under
 // the caller's name, then — nothing was changed up to there — the previous positions kept and the new vertices on the host
 static int replaceVertices(TwkDevice dev, const char* name, bool refit, int idGeometry, const TwkTriangleAttributes* attributes, size_t numAttributes)
@@ -775,23 +860,9 @@ static int replaceVertices(TwkDevice dev, const char* name, bool refit, int idGe
   if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
   if (refit && !dev->kept.valid)
     return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
-  if (idGeometry < 0 || idGeometry >= (int) dev->geometries.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad geometry id");
-  GeometryHost& g = dev->geometries[idGeometry];
-  if (numAttributes != g.attributes.size())
-    return refuse(TWK_ERROR_INVALID_VALUE, "the geometry has " + std::to_string(g.attributes.size()) + " vertices, not " + std::to_string(numAttributes) + " (the indices stay: no topology change)");
-  for (size_t v = 0; v < numAttributes; ++v)
-    if (!std::isfinite(attributes[v].vertex[0]) || !std::isfinite(attributes[v].vertex[1]) || !std::isfinite(attributes[v].vertex[2]))
-      return refuse(TWK_ERROR_INVALID_VALUE, "vertex " + std::to_string(v) + ": the position is not finite");
-  for (size_t i = 0; i < dev->instances.size(); ++i)
-    if (dev->instances[i].geometry == idGeometry && dev->instances[i].light >= 0)
-      return refuse(TWK_ERROR_INVALID_VALUE, "instance " + std::to_string(i) + " of the geometry carries a light (idLight >= 0): its light definition holds the emitter's shape and would disagree; deforming emitters is not supported");
+  if ((rc = checkVertices(dev, std::string(name) + ": ", idGeometry, attributes, numAttributes))) return rc;
   // nothing was changed up to here: a refused call changes nothing
-  if (dev->temporalHasHistory && (rc = refreshMirror(dev, idGeometry))) return rc; // keepPreviousPositions reads the mirror
-  keepPreviousPositions(dev, idGeometry); // the positions as of the history's frame, before the first update since (device_temporal.hip)
-  g.attributes.assign(attributes, attributes + numAttributes);
-  if (g.device) g.device->mirrorStale = false; // whole again, and newer than the slice a device-pointer source wrote: the upload brings it
-  dev->updateInfoValid = false;
-  return TWK_SUCCESS;
+  return storeVertices(dev, idGeometry, attributes, numAttributes);
 }
 
 extern "C" {
@@ -958,6 +1029,121 @@ try
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_refit_batch_plan_host")
+
+// A frame's edits in one call (include/tweeker_hip.h "A frame's edits in one call"): every entry is checked before anything is
+// written — the call's own arguments, the handle, the geometry entries in order, the instance entries, last the finite check of all
+// device sources (one launch per source into one result array, ONE read-back and wait) — then the vertices are stored as the vertex
+// calls store them, the transforms as the transform calls do, and updateSelective refits every tree once (refitAll).
+int twk_refit_scene(TwkDevice dev, int numGeometries, const TwkGeometryEdit* geometries, int numInstances, const int* idInstances, const float* transforms)
+try
+{
+  const char* name = "twk_refit_scene";
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (numGeometries < 0 || numInstances < 0) return refuse(TWK_ERROR_INVALID_VALUE, "the counts must be at least 0");
+  if (numGeometries == 0 && numInstances == 0) return refuse(TWK_ERROR_INVALID_VALUE, "both counts are 0: nothing to refit");
+  if (numGeometries > 0 && !geometries) return refuse(TWK_ERROR_INVALID_VALUE, "NULL array of geometry entries");
+  if (numInstances > 0 && (!idInstances || !transforms)) return refuse(TWK_ERROR_INVALID_VALUE, "NULL array of ids or transforms");
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  if (!dev->kept.valid)
+    return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
+  std::vector<VertexSourceView> views((size_t) numGeometries);
+  std::vector<int> updated((size_t) numGeometries);
+  int numSources = 0;
+  for (int k = 0; k < numGeometries; ++k)
+  {
+    const TwkGeometryEdit& e = geometries[k];
+    const std::string entry = std::string(name) + ": geometry entry " + std::to_string(k) + ": ";
+    if ((e.attributes != nullptr) == (e.source != nullptr)) return twkSetError(TWK_ERROR_INVALID_VALUE, entry + "the entry sets exactly one of attributes and source");
+    if (e.reserved != 0) return twkSetError(TWK_ERROR_INVALID_VALUE, entry + "the reserved word is not 0");
+    for (int j = 0; j < k; ++j)
+      if (geometries[j].idGeometry == e.idGeometry) return twkSetError(TWK_ERROR_INVALID_VALUE, entry + "geometry " + std::to_string(e.idGeometry) + " is listed twice (also geometry entry " + std::to_string(j) + ")");
+    if (e.attributes) rc = checkVertices(dev, entry, e.idGeometry, e.attributes, (size_t) e.numVertices);
+    else { rc = checkVertexSource(dev, entry, e.idGeometry, e.source, (size_t) e.numVertices, views[(size_t) k]); ++numSources; }
+    if (rc) return rc;
+    updated[(size_t) k] = e.idGeometry;
+  }
+  if ((rc = checkTransformEntries(dev, name, true, numInstances, idInstances, transforms))) return rc;
+  if (numSources > 0)
+  {
+    // read-only, and read before anything is written: word k is the lowest vertex of entry k whose position is not finite
+    std::vector<unsigned int> lowest((size_t) numGeometries, 0xffffffffu);
+    if ((rc = dev->d_sourceCheck.ensure((size_t) numGeometries))) return rc;
+    HIP_TRY(hipMemsetAsync(dev->d_sourceCheck, 0xff, sizeof(unsigned int) * (size_t) numGeometries, dev->stream));
+    for (int k = 0; k < numGeometries; ++k)
+      if (geometries[k].source) launchVertexSourceCheck(views[(size_t) k].pointer, views[(size_t) k].stride, (unsigned int) geometries[k].numVertices, dev->d_sourceCheck + k, dev->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lowest.data(), dev->d_sourceCheck, sizeof(unsigned int) * (size_t) numGeometries, hipMemcpyDeviceToHost, dev->stream));
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    for (int k = 0; k < numGeometries; ++k)
+      if (lowest[(size_t) k] != 0xffffffffu)
+        return refuse(TWK_ERROR_INVALID_VALUE, "geometry entry " + std::to_string(k) + ": vertex " + std::to_string(lowest[(size_t) k]) + ": the position is not finite");
+  }
+  {
+    // the batch as updateSelective will plan it: a batch that cannot be planned is refused here, before anything is stored
+    std::vector<int> instanceGeometry, geometryTriangles;
+    layoutInputs(dev, instanceGeometry, geometryTriangles);
+    UpdatePlan plan;
+    updatePlanWith(dev->kept.layout, instanceGeometry.data(), geometryTriangles.data(), idInstances, numInstances, updated.data(), numGeometries, plan);
+    RefitScenePlan scenePlan;
+    if (const char* why = refitScenePlan(dev->kept.layout, instanceGeometry.data(), geometryTriangles.data(), plan, idInstances, numInstances, updated.data(), numGeometries, scenePlan))
+      return refuse(TWK_ERROR_INVALID_VALUE, std::string("the refit batch: ") + why);
+  }
+  // nothing was changed up to here: a refused call changes nothing
+  for (int k = 0; k < numGeometries; ++k)
+  {
+    const TwkGeometryEdit& e = geometries[k];
+    if ((rc = e.attributes ? storeVertices(dev, e.idGeometry, e.attributes, (size_t) e.numVertices) : storeVertexSource(dev, e.idGeometry, views[(size_t) k]))) return rc;
+  }
+  for (int k = 0; k < numInstances; ++k) memcpy(dev->instances[idInstances[k]].transform, transforms + 12 * (size_t) k, sizeof(float) * 12);
+  dev->updateInfoValid = false;
+  // the temporal history stays, as after the calls this one stands for
+  return updateSelective(dev, idInstances, numInstances, updated.data(), numGeometries, true, false, true);
+}
+TWK_CATCH("twk_refit_scene")
+
+int twk_scene_refit_plan_host(const int* instanceGeometry, int numInstances, const int* geometryTriangles, int numGeometries, int flattenMaxTriangles,
+                              int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,
+                              TwkSceneRefitPlan* plan, int* trees, int* kinds, int* nodeBases, int* nodeCounts, int* slotBases, int* slotCounts,
+                              int* nodeOffsets, int* slotOffsets, int* nodeBlockFirst, int* slotBlockFirst, int* nodeBlocks, int* slotBlocks)
+try
+{
+  const char* name = "twk_scene_refit_plan_host";
+  if (!plan) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL argument");
+  TwkUpdatePlan update; // the inputs' refusals are the update plan's, under this call's name
+  int rc = updatePlanHost(name, instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, maxLeaf, moved, numMoved,
+                          updatedGeometries, numUpdated, &update, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  SceneLayout layout;
+  sceneLayout(instanceGeometry, numInstances, geometryTriangles, numGeometries, flattenMaxTriangles, flattenMaxReferences, std::max(1, std::min(4, maxLeaf)), true, layout);
+  UpdatePlan u;
+  updatePlanWith(layout, instanceGeometry, geometryTriangles, moved, numMoved, updatedGeometries, numUpdated, u);
+  RefitScenePlan p;
+  if (const char* why = refitScenePlan(layout, instanceGeometry, geometryTriangles, u, moved, numMoved, updatedGeometries, numUpdated, p)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + why);
+  memset(plan, 0, sizeof(*plan));
+  plan->trees = (int) p.tree.size(); plan->nodeBlocks = p.batch.totalNodeBlocks; plan->slotBlocks = p.batch.totalSlotBlocks; plan->blockThreads = REFIT_BATCH_BLOCK;
+  plan->directLeaves = (int) p.directLeaves.size(); plan->topLevelRebuilt = u.topLevel ? 1 : 0;
+  plan->boxes = (int) p.boxes.size();
+  plan->nodes = (uint64_t) p.batch.totalNodes; plan->slots = (uint64_t) p.batch.totalSlots; plan->slotsRewritten = (uint64_t) u.totalSlots; plan->slotBytes = (uint64_t) p.slotBytes;
+  for (size_t k = 0; k < p.tree.size(); ++k)
+  {
+    if (trees) trees[k] = p.tree[k];
+    if (kinds) kinds[k] = p.kind[k];
+    if (nodeBases) nodeBases[k] = p.nodeBase[k];
+    if (nodeCounts) nodeCounts[k] = p.nodes[k];
+    if (slotBases) slotBases[k] = p.slotBase[k];
+    if (slotCounts) slotCounts[k] = p.slots[k];
+    if (nodeOffsets) nodeOffsets[k] = p.batch.nodeOffset[k];
+    if (slotOffsets) slotOffsets[k] = p.batch.slotOffset[k];
+    if (nodeBlockFirst) nodeBlockFirst[k] = p.batch.nodeBlockFirst[k];
+    if (slotBlockFirst) slotBlockFirst[k] = p.batch.slotBlockFirst[k];
+  }
+  if (nodeBlocks) for (size_t b = 0; b < p.batch.nodeBlocks.size(); ++b) { nodeBlocks[2 * b] = p.batch.nodeBlocks[b].tree; nodeBlocks[2 * b + 1] = p.batch.nodeBlocks[b].first; }
+  if (slotBlocks) for (size_t b = 0; b < p.batch.slotBlocks.size(); ++b) { slotBlocks[2 * b] = p.batch.slotBlocks[b].tree; slotBlocks[2 * b + 1] = p.batch.slotBlocks[b].first; }
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_scene_refit_plan_host")
 
 int twk_set_update_mode(TwkDevice dev, int mode)
 try

@@ -62,17 +62,12 @@ static int ensureAdjacency(TwkDevice dev, GeometryHost& g)
   return TWK_SUCCESS;
 }
 
-// The front half of twk_update_geometry_vertices_device and of twk_refit_geometry_vertices_device: replaceVertices' refusals under
-// the caller's name, the source's own, the check launch — nothing was changed up to there — then the ingest on the handle's stream.
-int twk::ingestVertexSource(TwkDevice dev, const char* name, bool refit, int idGeometry, const TwkVertexSource* source, size_t numVertices)
+// A geometry's device-pointer source, refused with the texts of twk_update_geometry_vertices_device behind `where` (the call's name,
+// and its entry in twk_refit_scene): the vertex update's refusals, then the source's own. Reads nothing of the source. view: what the
+// launches are given.
+int twk::checkVertexSource(TwkDevice dev, const std::string& where, int idGeometry, const TwkVertexSource* source, size_t numVertices, VertexSourceView& view)
 {
-  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
-  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
-  if (!source) return refuse(TWK_ERROR_INVALID_VALUE, "NULL source");
-  int rc = activate(dev, name); if (rc) return rc;
-  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
-  if (refit && !dev->kept.valid)
-    return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
+  const auto refuse = [&where](int code, const std::string& text) { return twkSetError(code, where + text); };
   if (idGeometry < 0 || idGeometry >= (int) dev->geometries.size()) return refuse(TWK_ERROR_INVALID_VALUE, "bad geometry id");
   GeometryHost& g = dev->geometries[idGeometry];
   const size_t n = g.attributes.size();
@@ -90,25 +85,24 @@ int twk::ingestVertexSource(TwkDevice dev, const char* name, bool refit, int idG
   const size_t bytes = (n - 1) * stride + (records ? sizeof(TwkTriangleAttributes) : 12);
   std::string why;
   if (!deviceReadable(dev, pointer, bytes, why)) return refuse(TWK_ERROR_INVALID_VALUE, std::string(records ? "attributes: " : "positions: ") + why);
-  float* slice = dev->d_attributes + 12 * (size_t) g.attributeBase;
   if (!dev->d_attributes.holds(12 * ((size_t) g.attributeBase + n))) return refuse(TWK_ERROR_INVALID_STATE, "the built scene holds no attribute array");
   if (overlaps(pointer, bytes, dev->d_attributes.get(), sizeof(float) * dev->d_attributes.capacity())) return refuse(TWK_ERROR_INVALID_VALUE, "the source overlaps the handle's own attribute array");
   for (size_t i = 0; i < dev->instances.size(); ++i)
     if (dev->instances[i].geometry == idGeometry && dev->instances[i].light >= 0)
       return refuse(TWK_ERROR_INVALID_VALUE, "instance " + std::to_string(i) + " of the geometry carries a light (idLight >= 0): its light definition holds the emitter's shape and would disagree; deforming emitters is not supported");
+  view.pointer = pointer; view.stride = stride; view.records = records; view.recompute = source->recomputeFrames != 0;
+  return TWK_SUCCESS;
+}
 
-  // the check launch: read-only, and read before anything is written. The host call can look before it writes; this one cannot.
-  if ((rc = dev->d_sourceCheck.ensure(1))) return rc;
-  unsigned int lowest = 0xffffffffu;
-  HIP_TRY(hipMemsetAsync(dev->d_sourceCheck, 0xff, sizeof(unsigned int), dev->stream));
-  launchVertexSourceCheck(pointer, stride, (unsigned int) n, dev->d_sourceCheck, dev->stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(&lowest, dev->d_sourceCheck, sizeof(unsigned int), hipMemcpyDeviceToHost, dev->stream));
-  HIP_TRY(hipStreamSynchronize(dev->stream));
-  if (lowest != 0xffffffffu) return refuse(TWK_ERROR_INVALID_VALUE, "vertex " + std::to_string(lowest) + ": the position is not finite");
-
+// ... and, once the source has passed its check launch, the ingest into the geometry's slice on the handle's stream
+int twk::storeVertexSource(TwkDevice dev, int idGeometry, const VertexSourceView& view)
+{
+  int rc;
+  GeometryHost& g = dev->geometries[idGeometry];
+  const size_t n = g.attributes.size();
+  float* slice = dev->d_attributes + 12 * (size_t) g.attributeBase;
   if (!g.device) g.device.reset(new GeometryDevice());
-  if (!records && source->recomputeFrames && (rc = ensureAdjacency(dev, g))) return rc;
+  if (!view.records && view.recompute && (rc = ensureAdjacency(dev, g))) return rc;
   // keepPreviousPositions' rule, with the content on the device: the vector gets its size (what says "deformed"), the kernel the array
   const bool keep = dev->temporalHasHistory && ((size_t) idGeometry >= dev->previousPositions.size() || dev->previousPositions[idGeometry].empty());
   if (keep && (rc = g.device->d_kept.ensure(n))) return rc;
@@ -120,13 +114,39 @@ int twk::ingestVertexSource(TwkDevice dev, const char* name, bool refit, int idG
     dev->previousPositionsUploaded = false;
   }
   float4* kept = keep ? g.device->d_kept.get() : nullptr;
-  if (records) launchIngestAttributes(static_cast<const float4*>(pointer), reinterpret_cast<float4*>(slice), kept, (unsigned int) n, dev->stream);
-  else launchIngestPositions(pointer, stride, source->recomputeFrames != 0, dev->d_indices + g.indexBase, g.device->d_adjacencyOffsets, g.device->d_adjacencyTriangles,
+  if (view.records) launchIngestAttributes(static_cast<const float4*>(view.pointer), reinterpret_cast<float4*>(slice), kept, (unsigned int) n, dev->stream);
+  else launchIngestPositions(view.pointer, view.stride, view.recompute, dev->d_indices + g.indexBase, g.device->d_adjacencyOffsets, g.device->d_adjacencyTriangles,
                              reinterpret_cast<float4*>(slice), kept, (unsigned int) n, dev->stream);
   g.device->mirrorStale = true; // before the launch is known to have been taken: a slice half written is not the mirror's either
   dev->updateInfoValid = false;
   HIP_TRY(hipGetLastError());
   return TWK_SUCCESS;
+}
+
+// The front half of twk_update_geometry_vertices_device and of twk_refit_geometry_vertices_device: replaceVertices' refusals under
+// the caller's name, the source's own, the check launch — nothing was changed up to there — then the ingest on the handle's stream.
+int twk::ingestVertexSource(TwkDevice dev, const char* name, bool refit, int idGeometry, const TwkVertexSource* source, size_t numVertices)
+{
+  const auto refuse = [name](int code, const std::string& text) { return twkSetError(code, std::string(name) + ": " + text); };
+  if (!dev) return refuse(TWK_ERROR_INVALID_VALUE, "NULL device handle");
+  if (!source) return refuse(TWK_ERROR_INVALID_VALUE, "NULL source");
+  int rc = activate(dev, name); if (rc) return rc;
+  if (!dev->built) return refuse(TWK_ERROR_INVALID_STATE, "twk_build has not been called");
+  if (refit && !dev->kept.valid)
+    return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
+  VertexSourceView view;
+  if ((rc = checkVertexSource(dev, std::string(name) + ": ", idGeometry, source, numVertices, view))) return rc;
+
+  // the check launch: read-only, and read before anything is written. The host call can look before it writes; this one cannot.
+  if ((rc = dev->d_sourceCheck.ensure(1))) return rc;
+  unsigned int lowest = 0xffffffffu;
+  HIP_TRY(hipMemsetAsync(dev->d_sourceCheck, 0xff, sizeof(unsigned int), dev->stream));
+  launchVertexSourceCheck(view.pointer, view.stride, (unsigned int) numVertices, dev->d_sourceCheck, dev->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(&lowest, dev->d_sourceCheck, sizeof(unsigned int), hipMemcpyDeviceToHost, dev->stream));
+  HIP_TRY(hipStreamSynchronize(dev->stream));
+  if (lowest != 0xffffffffu) return refuse(TWK_ERROR_INVALID_VALUE, "vertex " + std::to_string(lowest) + ": the position is not finite");
+  return storeVertexSource(dev, idGeometry, view);
 }
 
 extern "C" {

@@ -92,6 +92,32 @@ def refit_batch_plan_host(treeNodes, treeSlots):
     return out
 
 
+def scene_refit_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, updated=(), moved=(), maxLeaf=2):
+    """twk_scene_refit_plan_host (pure CPU): the batch of a refitScene call (csrc/refit_scene_plan.h) on a scene laid out as
+    vertex_update_plan_host lays it out, for the geometries `updated` and the instances `moved`. Returns a dict: L.SceneRefitPlan's
+    fields, per tree (int32) trees (~geometry for a bottom-level tree, else the instance), kinds (0, 1, 2), nodeBases, nodeCounts,
+    slotBases, slotCounts, nodeOffsets, slotOffsets, nodeBlockFirst, slotBlockFirst, and nodeBlockTable / slotBlockTable (int32
+    [blocks, 2]: the block's tree, the tree-local index of its first thread)."""
+    ig = np.ascontiguousarray(instanceGeometry, dtype=np.int32).reshape(-1)
+    gt = np.ascontiguousarray(geometryTriangles, dtype=np.int32).reshape(-1)
+    mv = np.ascontiguousarray(list(moved), dtype=np.int32).reshape(-1)
+    up = np.ascontiguousarray(list(updated), dtype=np.int32).reshape(-1)
+    ip = C.POINTER(C.c_int)
+    at = lambda a: a.ctypes.data_as(ip) if a.size else None
+    plan = L.SceneRefitPlan()
+    head = (at(ig), int(ig.size), at(gt), int(gt.size), int(flattenPolicy[0]), int(flattenPolicy[1]), int(maxLeaf), at(mv), int(mv.size), at(up), int(up.size), C.byref(plan))
+    L.check(L.lib.twk_scene_refit_plan_host(*head, *([None] * 12)))  # the totals first
+    names = ("trees", "kinds", "nodeBases", "nodeCounts", "slotBases", "slotCounts", "nodeOffsets", "slotOffsets", "nodeBlockFirst", "slotBlockFirst")
+    count = plan.trees
+    per_tree = [np.zeros(count, np.int32) for _ in names]
+    nodeBlocks, slotBlocks = np.zeros((plan.nodeBlocks, 2), np.int32), np.zeros((plan.slotBlocks, 2), np.int32)
+    L.check(L.lib.twk_scene_refit_plan_host(*head, *[at(a) for a in per_tree], at(nodeBlocks), at(slotBlocks)))
+    out = {name: getattr(plan, name) for name, _ in L.SceneRefitPlan._fields_ if name != "trees"}
+    out["numTrees"] = count
+    out.update(zip(names, per_tree), nodeBlockTable=nodeBlocks, slotBlockTable=slotBlocks)
+    return out
+
+
 def previous_positions_host(hits, instance, primitive, geometry, indices, previousPositions, motion=None, carry=None):
     """twk_previous_positions_host (pure CPU): the previous-position plane of twk_render_geometry_motion from host arrays — hits
     float32 [n, 3] (t, beta, gamma), instance and primitive int32 [n] (instance < 0: a miss), geometry float32 [n, 4] (the geometry
@@ -549,6 +575,35 @@ class Device:
         """twk_refit_geometry_vertices_device: refitGeometryVertices from a device source (updateGeometryVerticesDevice's arguments)."""
         src, n = _vertex_source(source, numVertices, positions, stride, recomputeFrames)
         L.check(L.lib.twk_refit_geometry_vertices_device(self._h, int(idGeometry), C.byref(src), C.c_size_t(n)))
+
+    # ---- a frame's edits in one call (include/tweeker_hip.h "A frame's edits in one call", csrc/refit_scene_plan.h) ----
+    def refitScene(self, geometries=(), ids=(), transforms=()):
+        """twk_refit_scene: the vertex refits of `geometries` and the transform refits of the instances `ids` in ONE call — every tree
+        refit once, all in one batch with one host wait. geometries: a list of (idGeometry, array) — float32 [n, 12] host records, as
+        refitGeometryVertices takes them — or (idGeometry, dict) — a device source, the dict holding refitGeometryVerticesDevice's
+        arguments (source, and numVertices / positions / stride / recomputeFrames where needed). ids / transforms: as
+        refitInstanceTransforms takes them. The handle then holds, byte for byte, what the single calls in that order leave; refitInfo
+        and updateInfo describe the one call. TwkError: the single calls' refusals under the name twk_refit_scene, a geometry entry's
+        with "geometry entry k: " in front; a refused call changes nothing."""
+        geometries = list(geometries)
+        edits = (L.GeometryEdit * max(1, len(geometries)))()
+        keep = []  # the arrays and sources the entries point to, alive until the call returns
+        for k, (idGeometry, what) in enumerate(geometries):
+            edits[k].idGeometry, edits[k].reserved = int(idGeometry), 0
+            if isinstance(what, dict):
+                src, n = _vertex_source(what["source"], what.get("numVertices"), what.get("positions"), what.get("stride"), what.get("recomputeFrames", False))
+                keep.append(src)
+                edits[k].numVertices, edits[k].source = n, C.pointer(src)
+            else:
+                a = np.ascontiguousarray(what, dtype=np.float32).reshape(-1, 12)
+                keep.append(a)
+                edits[k].numVertices, edits[k].attributes = a.shape[0], a.ctypes.data
+        ids = np.ascontiguousarray(list(ids), dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1)
+        if t.size != 12 * ids.size:
+            raise ValueError("refitScene: 12 floats per id")
+        L.check(L.lib.twk_refit_scene(self._h, len(geometries), edits if geometries else None, int(ids.size),
+                                      ids.ctypes.data_as(C.POINTER(C.c_int)) if ids.size else None, t.ctypes.data_as(C.POINTER(C.c_float)) if ids.size else None))
 
     def readGeometryVertices(self, idGeometry, numVertices):
         """twk_read_geometry_vertices: the geometry's current records, float32 [numVertices, 12], wherever they were last written."""

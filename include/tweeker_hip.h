@@ -1258,6 +1258,43 @@ int twk_scene_refit_plan_host(const int* instanceGeometry, int numInstances, con
                               int flattenMaxReferences, int maxLeaf, const int* moved, int numMoved, const int* updatedGeometries, int numUpdated,
                               TwkSceneRefitPlan* plan, int* trees, int* kinds, int* nodeBases, int* nodeCounts, int* slotBases, int* slotCounts,
                               int* nodeOffsets, int* slotOffsets, int* nodeBlockFirst, int* slotBlockFirst, int* nodeBlocks, int* slotBlocks);
+/* ---- Moving a light: emitters through the transform calls — new calls and an opt-in switch, ABI stays 9; no kernel changes --------
+ * twk_enable_emitter_motion(dev, 1) makes the five transform entries — twk_update_instance_transform[s],
+ * twk_refit_instance_transform[s] and the instance list of twk_refit_scene — accept an instance that carries a light (idLight >= 0)
+ * and carry the light's definition along: the call sets the transforms as always, sets the light's definition to the one derived
+ * below, uploads that one 80-byte record on the handle's stream, and then rebuilds, updates or refits exactly as for any other
+ * instance (the light quad is an ordinary two-triangle instance). With the switch at its default 0 every call refuses such an
+ * instance with the text it always had. twk_get_emitter_motion reads the switch, twk_get_light the definition as it is now.
+ * THE RULE (csrc/light_motion.h is the complete definition; tests/light_motion_restate.py restates it in numpy): a light's ANCHOR is
+ * the pair (its definition, its instance's transform) at the moment an emitter of that light is first moved. Every moved definition
+ * is derived from the anchor, never from the one before it: a transform with the anchor transform's 48 bytes gives back the anchor
+ * definition's 80 bytes (A -> B -> A is exact); otherwise D = T_new . inv(T_anchor) in double (the inverse and summation order of
+ * twk_instance_motion, D not rounded), position = (float)(D p0), vecU = (float)(D_lin U0), vecV = (float)(D_lin V0), then in float
+ * n = cross(vecU, vecV), area = |n|, normal = n / area (≙ createLights, reference Application.cpp:616-618), and normal is negated
+ * when det(D_lin) < 0 — the emitter's lit side follows the inverse transpose, which a mirror does not flip, cross(vecU, vecV) does.
+ * type, emission and the unused words are copied. twk_update_light on the light drops its anchor: the next move anchors on the new
+ * definition and the transform of that moment. twk_init_lights, twk_build and twk_clear_scene drop every anchor.
+ * THE CONTRACT: after an accepted call the handle equals, byte for byte, a fresh handle built with the new transform and
+ * twk_get_light's definition (for the refit calls: the refit contract of twk_refit_instance_transform instead of the acceleration
+ * structure's bytes). The temporal history stays, and its transform snapshot covers the emitter like every instance: the merges
+ * follow the emitter's own pixels through the motion table; what the moved light changes elsewhere is stale history like any light
+ * edit (twk_temporal_accumulate_rectified discounts it).
+ * What it is not: no deforming or re-meshing of an emitter (the vertex calls keep refusing an emitting geometry), no moving
+ * environment light, no light carried by several instances, no shape but the parallelogram, not on by default, and no guarantee that
+ * the caller's definition matched the quad in the first place — the rule moves whatever definition it was given.
+ * Refusals with the switch on, all TWK_ERROR_INVALID_VALUE under the call's name ("entry k: " in front in the batch forms), after
+ * every refusal the call had before, in entry order, and before anything is changed: the light is not a TWK_LIGHT_PARALLELOGRAM;
+ * the light is carried by more than one instance (the text names both); the derived area is zero or not finite, or a derived
+ * component is not finite. twk_enable_emitter_motion: a NULL handle, a switch that is neither 0 nor 1. twk_get_emitter_motion,
+ * twk_get_light: a NULL argument, a bad light id. Measured: profiles/r33_emitter_motion.md (tools/emitter_motion_time.py). */
+int twk_enable_emitter_motion(TwkDevice dev, int on);
+int twk_get_emitter_motion(TwkDevice dev, int* on);
+int twk_get_light(TwkDevice dev, int idLight, TwkLightDefinition* out);
+/* Pure CPU, no device, no HIP call: the rule above — `out` is `anchor` moved from anchorTransform to transform (row-major 3 x 4
+ * object-to-world matrices; out may be anchor). TWK_ERROR_INVALID_VALUE: a NULL argument, an anchor that is no
+ * TWK_LIGHT_PARALLELOGRAM, a transform that is not finite or an anchor transform whose 3 x 3 determinant is zero or not finite, a
+ * derived area that is zero or not finite or a derived component that is not finite; `out` is then untouched. */
+int twk_light_moved_host(const TwkLightDefinition* anchor, const float anchorTransform[12], const float transform[12], TwkLightDefinition* out);
 /* One record per instance beside its TwkInstanceMotion (csrc/temporal_carry_device.h): previousObjectToWorld is the instance's
  * object-to-world matrix as of the history's frame, row-major 3 x 4; deformed = 0 says its geometry holds no previous positions and
  * nothing else is read; positionBase / indexBase: the first previous position / first index of its geometry in the arrays given. */

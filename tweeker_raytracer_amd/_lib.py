@@ -370,6 +370,7 @@ SYMBOLS = [
     "twk_refit_instance_transform", "twk_refit_instance_transforms", "twk_refit_batch_plan_host",
     "twk_update_geometry_vertices_device", "twk_refit_geometry_vertices_device", "twk_vertex_frames_host", "twk_read_geometry_vertices",
     "twk_refit_scene", "twk_scene_refit_plan_host",
+    "twk_enable_emitter_motion", "twk_get_emitter_motion", "twk_get_light", "twk_light_moved_host",
     "twk_temporal_accumulate_carried", "twk_temporal_accumulate_cascade_carried", "twk_temporal_carried_host", "twk_temporal_cascade_carried_host",
     "twk_assemble", "twk_assemble_devices", "twk_get_assembled_device_pointer", "twk_read_assembled", "twk_assemble_host", "twk_app_get_tile_assembly",
     "twk_render_geometry_tile", "twk_assemble_with_geometry", "twk_assemble_devices_with_geometry", "twk_get_assembled_geometry_device_pointer",

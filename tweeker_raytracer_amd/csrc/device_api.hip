@@ -357,7 +357,7 @@ try
     return twkSetError(TWK_ERROR_INVALID_STATE, "twk_init_lights: the built scene has an instance with light index " + std::to_string(dev->maxInstanceLight) + "; " + std::to_string(count) + " lights would leave it dangling (twk_clear_scene first)");
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->d_lights.release();
-  dev->lights.assign(l, l + count);
+  dev->lights.assign(l, l + count); dropLightAnchors(dev);
   if (count > 0)
   {
     if ((rc = dev->d_lights.allocate((size_t) count))) return rc;
@@ -374,10 +374,53 @@ try
   if (!l || idLight < 0 || idLight >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_update_light: bad light id");
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->lights[idLight] = *l;
+  if ((size_t) idLight < dev->lightAnchors.size()) dev->lightAnchors[idLight].valid = false; // the next move anchors on this definition (light_motion.h)
   HIP_TRY(hipMemcpyAsync(dev->d_lights + idLight, &dev->lights[idLight], sizeof(DevLight), hipMemcpyHostToDevice, dev->stream));
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_update_light")
+
+int twk_get_light(TwkDevice dev, int idLight, TwkLightDefinition* out)
+try
+{
+  const char* name = "twk_get_light";
+  if (!dev || !out) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + (dev ? ": NULL definition" : ": NULL device handle"));
+  if (idLight < 0 || idLight >= (int) dev->lights.size()) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": bad light id");
+  *out = dev->lights[idLight];
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_light")
+
+int twk_enable_emitter_motion(TwkDevice dev, int on)
+try
+{
+  if (!dev) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_enable_emitter_motion: NULL device handle");
+  if (on != 0 && on != 1) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_enable_emitter_motion: the switch is " + std::to_string(on) + ", neither 0 nor 1");
+  dev->emitterMotion = (on == 1); // read by the transform calls; the anchors stay: a light that has moved keeps deriving from where it started
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_enable_emitter_motion")
+
+int twk_get_emitter_motion(TwkDevice dev, int* on)
+try
+{
+  if (!dev || !on) return twkSetError(TWK_ERROR_INVALID_VALUE, "twk_get_emitter_motion: NULL argument");
+  *on = dev->emitterMotion ? 1 : 0;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_get_emitter_motion")
+
+int twk_light_moved_host(const TwkLightDefinition* anchor, const float anchorTransform[12], const float transform[12], TwkLightDefinition* out)
+try
+{
+  const char* name = "twk_light_moved_host";
+  if (!anchor || !anchorTransform || !transform || !out) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": NULL argument");
+  TwkLightDefinition moved; // `out` may be `anchor`
+  if (const char* why = lightMoved(*anchor, anchorTransform, transform, moved)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + why);
+  *out = moved;
+  return TWK_SUCCESS;
+}
+TWK_CATCH("twk_light_moved_host")
 
 int twk_init_materials(TwkDevice dev, const TwkMaterialGUI* m, int count)
 try

@@ -21,6 +21,7 @@
 #include "assemble_device.h"
 #include "device_buffers.h"
 #include "update_plan.h"
+#include "light_motion.h"
 
 #include <memory>
 #include <string>
@@ -332,6 +333,10 @@ struct TwkDevice_t
   TwkRefitInfo refitInfo = {}; bool refitInfoValid = false;
   DeviceArray<unsigned int> d_refitScratch;
   DeviceArray<unsigned int> d_sourceCheck; // one word: the lowest vertex of a device-pointer source whose position is not finite
+  // twk_enable_emitter_motion (light_motion.h): while emitterMotion is set the transform calls accept an instance that carries a
+  // light and move its definition with it, always from the light's anchor (lightAnchors[light], grown on demand; dropLightAnchors)
+  bool emitterMotion = false;
+  std::vector<LightAnchor> lightAnchors;
 
   std::vector<std::vector<char>> hostScene; // twk_debug_snapshot_scene: host copies of the scene arrays
 
@@ -341,6 +346,9 @@ struct TwkDevice_t
 
 // The camera, the state or the scene changed: the handle's geometry AOV and the geometry it assembled as a primary are of the old one
 inline void staleGeometry(TwkDevice dev) { dev->geometryValid = false; dev->assembledGeometryValid = false; dev->previousPlaneValid = false; }
+
+// Every light's anchor goes (twk_init_lights, twk_build, twk_clear_scene): the next move of an emitter anchors anew
+inline void dropLightAnchors(TwkDevice dev) { dev->lightAnchors.clear(); }
 
 // Whether the handle holds previous positions of some geometry (twk_update_geometry_vertices since the history's frame)
 inline bool geometryDeformed(TwkDevice dev)

@@ -41,7 +41,7 @@ try
   int rc = activate(dev, "twk_clear_scene"); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
   dev->geometries.clear(); dev->instances.clear(); dev->built = false; dropAdaptive(dev);
-  staleGeometry(dev); dropTemporal(dev);
+  staleGeometry(dev); dropTemporal(dev); dropLightAnchors(dev);
   return TWK_SUCCESS;
 }
 TWK_CATCH("twk_clear_scene")
@@ -461,6 +461,7 @@ int twk_build(TwkDevice dev)
 try
 {
   int rc = activate(dev, "twk_build"); if (rc) return rc;
+  dropLightAnchors(dev); // a built scene starts where its instances and lights are: the next move of an emitter anchors anew
   if ((rc = buildScene(dev, dev->updateMode == TWK_UPDATE_SELECTIVE))) return rc;
   dropTemporal(dev); // the temporal history describes the scene that was
   return TWK_SUCCESS;
@@ -745,9 +746,55 @@ static int checkTransformEntries(TwkDevice dev, const char* name, bool batch, in
     const float* transform = transforms + 12 * (size_t) k;
     if (id < 0 || id >= (int) dev->instances.size()) return refuse(TWK_ERROR_INVALID_VALUE, entry + "bad instance id");
     if (!instanceTransformUsable(transform)) return refuse(TWK_ERROR_INVALID_VALUE, entry + "the transform is not finite, or its 3 x 3 determinant is zero or not finite");
-    if (dev->instances[id].light >= 0)
+    if (dev->instances[id].light >= 0 && !dev->emitterMotion)
       return refuse(TWK_ERROR_INVALID_VALUE, entry + "the instance carries a light (idLight >= 0): its light definition holds the emitter's position and would disagree; moving emitters is not supported");
     for (int j = 0; j < k; ++j) if (ids[j] == id) return refuse(TWK_ERROR_INVALID_VALUE, entry + "instance " + std::to_string(id) + " is listed twice (also entry " + std::to_string(j) + ")");
+  }
+  return TWK_SUCCESS;
+}
+
+// Emitters among the entries of a transform call that checkTransformEntries has passed, with twk_enable_emitter_motion on
+// (light_motion.h): per entry that carries a light, in entry order, the refusals — a light that is no parallelogram, a light a second
+// instance carries, a derived definition that is degenerate — and what applyEmitterMoves will write. Changes nothing.
+struct EmitterMove { int light; bool anchors; LightAnchor anchor; TwkLightDefinition moved; };
+static int planEmitterMoves(TwkDevice dev, const char* name, bool batch, int count, const int* ids, const float* transforms, std::vector<EmitterMove>& moves)
+{
+  const auto refuse = [name](const std::string& text) { return twkSetError(TWK_ERROR_INVALID_VALUE, std::string(name) + ": " + text); };
+  moves.clear();
+  for (int k = 0; k < count; ++k)
+  {
+    const int id = ids[k], light = dev->instances[id].light;
+    if (light < 0) continue;
+    const std::string entry = (batch ? "entry " + std::to_string(k) + ": " : std::string()) + "instance " + std::to_string(id) + " carries light " + std::to_string(light) + ": ";
+    if (dev->lights[light].type != TWK_LIGHT_PARALLELOGRAM) return refuse(entry + lightNotParallelogram);
+    for (size_t j = 0; j < dev->instances.size(); ++j)
+      if ((int) j != id && dev->instances[j].light == light)
+        return refuse(entry + "the light is carried by more than one instance (instances " + std::to_string(std::min((int) j, id)) + " and " + std::to_string(std::max((int) j, id)) +
+                      "): one definition cannot follow both");
+    EmitterMove m;
+    m.light = light;
+    m.anchors = !((size_t) light < dev->lightAnchors.size() && dev->lightAnchors[light].valid);
+    if (m.anchors) { m.anchor.valid = true; m.anchor.definition = dev->lights[light]; memcpy(m.anchor.transform, dev->instances[id].transform, sizeof(float) * 12); }
+    else m.anchor = dev->lightAnchors[light];
+    if (const char* why = lightMoved(m.anchor.definition, m.anchor.transform, transforms + 12 * (size_t) k, m.moved)) return refuse(entry + why);
+    moves.push_back(m);
+  }
+  return TWK_SUCCESS;
+}
+
+// ... and, once nothing is refused any more and the instances have their transforms: the anchors taken, the definitions set, each
+// uploaded on the handle's stream (in stream order behind everything that still reads the table, before the rebuild or refit)
+static int applyEmitterMoves(TwkDevice dev, const std::vector<EmitterMove>& moves)
+{
+  for (const EmitterMove& m : moves)
+  {
+    if (m.anchors)
+    {
+      if (dev->lightAnchors.size() < dev->lights.size()) dev->lightAnchors.resize(dev->lights.size());
+      dev->lightAnchors[m.light] = m.anchor;
+    }
+    dev->lights[m.light] = m.moved;
+    HIP_TRY(hipMemcpyAsync(dev->d_lights + m.light, &dev->lights[m.light], sizeof(DevLight), hipMemcpyHostToDevice, dev->stream));
   }
   return TWK_SUCCESS;
 }
@@ -767,8 +814,11 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   if (refit && !dev->kept.valid)
     return refuse(TWK_ERROR_INVALID_STATE, "the scene was not built in TWK_UPDATE_SELECTIVE (twk_set_update_mode before twk_build): nothing a refit needs was kept");
   if ((rc = checkTransformEntries(dev, name, batch, count, ids, transforms))) return rc;
+  std::vector<EmitterMove> emitters;
+  if ((rc = planEmitterMoves(dev, name, batch, count, ids, transforms, emitters))) return rc;
   // nothing was changed up to here: a refused batch changes nothing
   for (int k = 0; k < count; ++k) memcpy(dev->instances[ids[k]].transform, transforms + 12 * (size_t) k, sizeof(float) * 12);
+  if ((rc = applyEmitterMoves(dev, emitters))) return rc;
   dev->updateInfoValid = false; // an update that fails from here on leaves no record: twk_get_update_info describes a finished update
   // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
   if (dev->kept.valid) return updateSelective(dev, ids, count, nullptr, 0, refit, refit);
@@ -1090,6 +1140,8 @@ try
     if (const char* why = refitScenePlan(dev->kept.layout, instanceGeometry.data(), geometryTriangles.data(), plan, idInstances, numInstances, updated.data(), numGeometries, scenePlan))
       return refuse(TWK_ERROR_INVALID_VALUE, std::string("the refit batch: ") + why);
   }
+  std::vector<EmitterMove> emitters;
+  if ((rc = planEmitterMoves(dev, name, true, numInstances, idInstances, transforms, emitters))) return rc;
   // nothing was changed up to here: a refused call changes nothing
   for (int k = 0; k < numGeometries; ++k)
   {
@@ -1097,6 +1149,7 @@ try
     if ((rc = e.attributes ? storeVertices(dev, e.idGeometry, e.attributes, (size_t) e.numVertices) : storeVertexSource(dev, e.idGeometry, views[(size_t) k]))) return rc;
   }
   for (int k = 0; k < numInstances; ++k) memcpy(dev->instances[idInstances[k]].transform, transforms + 12 * (size_t) k, sizeof(float) * 12);
+  if ((rc = applyEmitterMoves(dev, emitters))) return rc;
   dev->updateInfoValid = false;
   // the temporal history stays, as after the calls this one stands for
   return updateSelective(dev, idInstances, numInstances, updated.data(), numGeometries, true, false, true);

@@ -276,6 +276,13 @@ bool Application::loadSystemDescription(const std::string& text, std::string& er
       if (ok && (i[0] == 0 || i[0] == 1)) selectiveUpdate = i[0];
       else if (ok) warnings.push_back("selectiveUpdate must be 0 or 1, keeping the previous value");
     }
+    // the light may move in that loop (twk_enable_emitter_motion): "temporalInstanceStep" is then accepted on the light's instance
+    else if (key == "movingEmitters")
+    {
+      ok = readInt(parser, i[0]);
+      if (ok && (i[0] == 0 || i[0] == 1)) movingEmitters = i[0];
+      else if (ok) warnings.push_back("movingEmitters must be 0 or 1, keeping the previous value");
+    }
     // tonemapper settings (Application.cpp:1244-1292), consumed by twk_tonemap / screenshot
     else if (key == "gamma")          { ok = readFloat(parser, tonemapper.gamma); }
     else if (key == "whitePoint")     { ok = readFloat(parser, tonemapper.whitePoint); }
@@ -382,6 +389,7 @@ std::string Application::systemDescription() const
   if (temporalRectifyMinTaps != TWK_TEMPORAL_RECTIFY_MIN_TAPS) d << "temporalRectifyMinTaps " << temporalRectifyMinTaps << std::endl;
   if (temporalInstance >= 0) d << "temporalInstanceStep " << temporalInstance << " " << temporalInstanceStep[0] << " " << temporalInstanceStep[1] << " " << temporalInstanceStep[2] << std::endl;
   if (selectiveUpdate != 0) d << "selectiveUpdate " << selectiveUpdate << std::endl;
+  if (movingEmitters != 0) d << "movingEmitters " << movingEmitters << std::endl;
   d << "center " << camera.center[0] << " " << camera.center[1] << " " << camera.center[2] << std::endl;
   d << "camera " << camera.phi << " " << camera.theta << " " << camera.fov << " " << camera.distance << std::endl;
   if (!prefixScreenshot.empty()) d << "prefixScreenshot " << prefixScreenshot << std::endl;

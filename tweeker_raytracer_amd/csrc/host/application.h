@@ -144,6 +144,9 @@ public:
   // every device before the build, so that the updates of "temporalInstanceStep" rebuild only what the instance changes
   int   selectiveUpdate = 0;
   float temporalInstanceStep[3] = {0.0f, 0.0f, 0.0f};
+  // "movingEmitters 0|1" (written back by twk_app_system_description, where a render loop reads it): the loop sets
+  // twk_enable_emitter_motion on every device, so that "temporalInstanceStep" may name the instance that carries the light
+  int   movingEmitters = 0;
   int   adaptiveSampling = 0;
   int   adaptiveMaxSamples = (int) TWK_ADAPTIVE_MAX_SAMPLES;
   // "adaptiveBudget" (1: each interval of the adaptive loop is one twk_adaptive_plan + one twk_launch_adaptive_planned, every pixel

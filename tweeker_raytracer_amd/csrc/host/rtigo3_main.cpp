@@ -32,7 +32,8 @@
 // device is created. With "temporalInstanceStep <idInstance> <dx> <dy> <dz>" beside it that instance is translated by one more step
 // before every frame after the first (twk_update_instance_transform on every device, which keeps the history; the merges carry it
 // along); refused before any device is created without "temporalAccumulation 1", for an id beyond the scene's instances and for an
-// instance that carries a light.
+// instance that carries a light — unless "movingEmitters 1" stands beside it: then twk_enable_emitter_motion is set on every device
+// before the loop and the light's definition moves with its instance (include/tweeker_hip.h "Moving a light").
 // With "denoiserGeometry 1" beside "denoiser 3" the filter, in whichever mode is on, is twk_denoise_geometry: the geometry AOV is
 // traced once before the screenshot is filtered (twk_render_geometry; on several devices with "tileAssembly 1"
 // twk_render_geometry_tile and ONE twk_assemble_devices_with_geometry), the temporal loop uses its last frame's own geometry, and
@@ -266,6 +267,16 @@ int main(int argc, char* argv[])
     std::cerr << "ERROR: temporalInstanceStep moves an object in the moving-camera loop: it needs temporalAccumulation 1\n";
     return 1;
   }
+  // "movingEmitters 1": read where the application writes its settings back, in the loader's own grammar (a key on a line of its own)
+  bool movingEmitters = false;
+  {
+    size_t length = 0;
+    TWK_OK(twk_app_system_description(app, nullptr, 0, &length));
+    std::vector<char> text(length + 1, 0);
+    TWK_OK(twk_app_system_description(app, text.data(), text.size(), nullptr));
+    std::istringstream lines(text.data());
+    for (std::string line; std::getline(lines, line);) if (line == "movingEmitters 1") movingEmitters = true;
+  }
   if (movingInstance >= 0)
   {
     int light = -1;
@@ -274,7 +285,7 @@ int main(int argc, char* argv[])
       std::cerr << "ERROR: temporalInstanceStep names instance " << movingInstance << "; the scene has " << info.numInstances << "\n";
       return 1;
     }
-    if (light >= 0)
+    if (light >= 0 && !movingEmitters)
     {
       std::cerr << "ERROR: temporalInstanceStep names an instance that carries a light: moving emitters is not supported\n";
       return 1;
@@ -323,6 +334,8 @@ int main(int argc, char* argv[])
   if (selectiveUpdate)
     for (int i = 0; i < count; ++i) TWK_OK(twk_set_update_mode(devices[(size_t) i], TWK_UPDATE_SELECTIVE));
   for (int i = 0; i < count; ++i) TWK_OK(twk_app_init_device(app, devices[(size_t) i]));
+  if (movingEmitters)
+    for (int i = 0; i < count; ++i) TWK_OK(twk_enable_emitter_motion(devices[(size_t) i], 1));
 
   // Buffer strategy (Raytracer.cpp:125-176 picks the Device flavour): 1 = zero copy — one pinned host frame mapped into
   // every device (DeviceMultiGPUZeroCopy.cpp:106-118); 2 = peer access — one frame on the first device, written by its

@@ -37,7 +37,7 @@
 //
 // What it is not. One rigid or affine matrix per INSTANCE: no deforming geometry and no per-vertex motion here (temporal_carry_device.h:
 // the previous-position plane of a deformed mesh and the Carried builds that read it), no motion blur. The light
-// an emitting instance carries does not move with it (twk_update_instance_transform refuses such an instance). Shadows and
+// an emitting instance carries moves with it only under twk_enable_emitter_motion (light_motion.h; else the instance is refused). Shadows and
 // inter-reflections the move changes elsewhere in the picture are stale history like any light edit: the rectified merge discounts
 // them, the plain merge fades them at the cap. A miss never has history, and the lens is the pinhole.
 #pragma once

@@ -24,6 +24,18 @@ def instance_motion(previous, current):
     return out
 
 
+def light_moved_host(anchor, anchorTransform, transform):
+    """twk_light_moved_host (pure CPU, csrc/light_motion.h): the L.LightDefinition that `anchor` — the definition of a parallelogram
+    light whose instance had the object-to-world matrix anchorTransform — becomes when the instance is moved to `transform` (12 floats
+    each, row-major 3 x 4). A transform with the anchor transform's bits returns the anchor's bytes. TwkError: a light that is no
+    parallelogram, a transform that is not finite, a singular anchor transform, a degenerate result."""
+    a = np.ascontiguousarray(anchorTransform, dtype=np.float32).reshape(12)
+    t = np.ascontiguousarray(transform, dtype=np.float32).reshape(12)
+    out = L.LightDefinition()
+    L.check(L.lib.twk_light_moved_host(C.byref(anchor), a.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out)))
+    return out
+
+
 def update_plan_host(instanceGeometry, geometryTriangles, flattenPolicy, moved=(), maxLeaf=2):
     """twk_update_plan_host (pure CPU): how a scene of instances instanceGeometry[i] over geometries of geometryTriangles[g]
     triangles is laid out under flattenPolicy = (maxTriangles, maxReferences), and what a selective update of the instances `moved`
@@ -307,6 +319,25 @@ class Device:
 
     def updateLight(self, idLight, light):
         L.check(L.lib.twk_update_light(self._h, int(idLight), C.byref(light)))
+
+    # ---- moving a light (include/tweeker_hip.h "Moving a light", csrc/light_motion.h) ----
+    def getLight(self, idLight):
+        """twk_get_light: the light's definition as it is now, an L.LightDefinition."""
+        out = L.LightDefinition()
+        L.check(L.lib.twk_get_light(self._h, int(idLight), C.byref(out)))
+        return out
+
+    def enableEmitterMotion(self, on=True):
+        """twk_enable_emitter_motion: while on, updateInstanceTransform[s], refitInstanceTransform[s] and refitScene's moved list accept
+        an instance that carries a parallelogram light and move the light's definition with it, always derived from the light's anchor
+        (light_moved_host). Off, the default: they refuse such an instance as they always did."""
+        L.check(L.lib.twk_enable_emitter_motion(self._h, int(bool(on))))
+
+    def emitterMotion(self):
+        """twk_get_emitter_motion: whether the switch is on."""
+        on = C.c_int(0)
+        L.check(L.lib.twk_get_emitter_motion(self._h, C.byref(on)))
+        return bool(on.value)
 
     def updateMaterial(self, idMaterial, material):
         L.check(L.lib.twk_update_material(self._h, int(idMaterial), C.byref(material)))

@@ -1059,7 +1059,9 @@ int twk_vertex_update_plan_host(const int* instanceGeometry, int numInstances, c
  * record is written again from the primitive word the slot holds, every leaf box follows the build's rule (padBox once per build
  * primitive), every inner box is the union of its children's, every wide node keeps the cut it had, and the node costs follow. The
  * references, the slot order, the pair flags and the heights do not change. A direct-leaf instance (no tree of its own) takes the
- * rebuild's path and counts in treesRebuilt. The top level, the 8-wide root and the ranged tail run as in the selective update.
+ * rebuild's path and counts in treesRebuilt. All refit trees of the call go through ONE launch sequence with ONE host wait
+ * (csrc/bvh_refit.hip, the one batch every refit call runs; csrc/refit_scene_plan.h says which trees and of which kind). The top
+ * level, the 8-wide root and the ranged tail run as in the selective update.
  * The result is a LEGAL tree for the new vertices (tests/bvh_audit.py holds it to every check a build's tree passes), not the tree a
  * fresh build would choose: its quality decays as the mesh moves away from the vertices it was built from. TwkRefitInfo says by how
  * much — sahNow / sahBuilt — and the caller decides when to call twk_update_geometry_vertices, which rebuilds: there is no fallback
@@ -1114,7 +1116,7 @@ int twk_debug_read_kept_build(TwkDevice dev, float* wide, size_t numWideFloats, 
  * through the new matrix, with the build's expression; every leaf box, inner box, wide node (with the cut it had) and node cost
  * follows as csrc/bvh_refit.h defines; the SAH terms follow. The 128-byte shading records are not touched: they are object-space,
  * and a transform does not change them. All trees of a call are refit by ONE launch sequence with ONE host wait
- * (csrc/bvh_refit_batch.hip; csrc/refit_batch_plan.h plans it). Then the top level, the depth check, the 8-wide root, the ranged
+ * (csrc/bvh_refit.hip, the one batch every refit call runs; csrc/refit_batch_plan.h plans its blocks). Then the top level, the depth check, the 8-wide root, the ranged
  * tail, the top caches, as in the selective update. twk_get_update_info (selective 1, instancesMoved = count, treesRebuilt = the
  * direct leaves) and twk_get_refit_info describe the call; each refit tree's count of refits goes up by one.
  * The result is a LEGAL scene for the new transforms, not a fresh build's. For a translation or a uniform scale the refit tree is
@@ -1131,7 +1133,7 @@ int twk_refit_instance_transforms(TwkDevice dev, int count, const int* idInstanc
 /* Pure CPU, no device: how the trees of one batched refit share its launches (csrc/refit_batch_plan.h, the code the call plans
  * with). Tree k has treeNodes[k] nodes and treeSlots[k] slots and occupies ceil(n / 256) consecutive node blocks and ceil(s / 256)
  * consecutive slot blocks, so that no block straddles two trees. Out, each NULL or given: nodeOffsets / slotOffsets [numTrees] (the
- * nodes / slots of the trees before it: where its parents and tickets / its soup descriptors stand), nodeBlockFirst /
+ * nodes / slots of the trees before it; at the node offset stand its parents and tickets), nodeBlockFirst /
  * slotBlockFirst [numTrees] (its first block: where its partial sums stand), nodeBlocks [2 x plan->nodeBlocks] / slotBlocks
  * [2 x plan->slotBlocks] (per block: its tree, the tree-local index of its first thread). The block counts are those sums of
  * ceilings (or call once with the tables NULL). TWK_ERROR_INVALID_VALUE: a NULL input or plan, numTrees < 1, a tree with less than
@@ -1199,13 +1201,13 @@ int twk_read_geometry_vertices(TwkDevice dev, int idGeometry, TwkTriangleAttribu
  * the matrix alone. What differs is the bookkeeping: every tree is refit once, so its count of refits goes up by ONE (also the tree
  * of an instance that is both moved and of an edited geometry), and TwkRefitInfo / TwkUpdateInfo describe the one call — treesRefit,
  * nodesRefit, sahBuilt and sahNow count each refit tree once, treesRebuilt the direct-leaf instances (the rebuild's path, as in the
- * calls above), slotsRewritten the slots of all those trees, instancesMoved = numInstances. (TwkUpdateInfo.keptBytes may be lower than
- * after the sequence: the call writes no soup descriptors and so never grows that scratch.)
+ * calls above), slotsRewritten the slots of all those trees, instancesMoved = numInstances. (TwkUpdateInfo.keptBytes equals the
+ * sequence's: no refit call writes soup descriptors for a refit tree, so none grows that scratch.)
  * Each instance gets what its kind needs: a moved or edited ENTERED one its world box (from its geometry's new root box where that
  * was refit in this call), a DIRECT LEAF the rebuild, every other FLATTENED one a refit in place. All refit trees — bottom-level
  * trees of edited geometries, world-space trees of instances of edited geometries, world-space trees of moved instances — go through
- * ONE upload, five launches, one read-back and ONE host wait, whatever their number and kinds (csrc/bvh_refit_scene.hip;
- * csrc/refit_scene_plan.h says which tree is of which kind): the slot kernel makes every soup descriptor in registers, so no
+ * ONE upload, five launches, one read-back and ONE host wait, whatever their number and kinds (csrc/bvh_refit.hip, the batch the
+ * single refit calls run too; csrc/refit_scene_plan.h says which tree is of which kind): the slot kernel makes every soup descriptor in registers, so no
  * descriptor launch runs per tree. All device sources are checked before anything is written: one check launch per source into one
  * result array, ONE read-back and wait, then the ingest launches. The stages around the trees (top level, depth check, 8-wide root,
  * ranged tail, top caches) run once, as in the selective update. numGeometries == 0 makes the call twk_refit_instance_transforms;

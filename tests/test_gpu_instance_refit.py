@@ -1,4 +1,4 @@
-"""-m gpu: the refit of MOVED flattened instances (twk_refit_instance_transform[s], csrc/bvh_refit_batch.hip). A refit handle is not a
+"""-m gpu: the refit of MOVED flattened instances (twk_refit_instance_transform[s], csrc/bvh_refit.hip). A refit handle is not a
 fresh build's, so it is held to what a LEGAL tree is — tests/bvh_audit.py, whole — and to the exact invariants of a refit:
   (a) the audit of the scene with the new transforms passes whole
   (b) binary nodes, wide nodes, node costs and slots of every refit tree equal twk_refit_tree_host applied, with the new transform, to

@@ -1,5 +1,5 @@
-"""-m gpu: the refit (twk_refit_geometry_vertices, csrc/bvh_refit.h). A refit handle is not a fresh build's, so it is held to what a
-LEGAL tree is — tests/bvh_audit.py, whole — and to the exact invariants a refit has of its own:
+"""-m gpu: the refit (twk_refit_geometry_vertices, csrc/bvh_refit.h; its trees are one batch of csrc/bvh_refit.hip). A refit
+handle is not a fresh build's, so it is held to what a LEGAL tree is — tests/bvh_audit.py, whole — and to the exact invariants a refit has of its own:
   (a) the audit of the scene with the new vertices passes whole
   (b) binary nodes, wide nodes, node costs, slots and shading records of the refit ranges equal twk_refit_tree_host applied to the
       read-back taken before the refit, bit for bit

@@ -1,4 +1,4 @@
-"""-m gpu: a frame's edits in one call (twk_refit_scene, csrc/bvh_refit_scene.hip). THE SEQUENCE is refitGeometryVertices (or its
+"""-m gpu: a frame's edits in one call (twk_refit_scene, csrc/bvh_refit.hip). THE SEQUENCE is refitGeometryVertices (or its
 device form) per geometry entry in order, then refitInstanceTransforms. Every comparison is bit for bit:
   (1) a handle that took refitScene equals a handle that took the sequence: the read-back, the scene arrays, the kept arrays,
       readGeometryVertices, instanceTransform, and on the selective_scenes and "three-kinds" a 4 spp picture at 64 x 36 in both output

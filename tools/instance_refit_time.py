@@ -11,9 +11,9 @@ Configurations: the Cornell box (C2; the sphere has 32 040 triangles, flattened)
 Batch: eight flattened instances of one 32 040-triangle sphere moved by one twk_refit_instance_transforms call, by eight
 twk_refit_instance_transform calls, and by one twk_update_instance_transforms call.
 
-Kernels: a child of this tool under `rocprofv3 --kernel-trace` refits the C2 sphere RUNS + 1 times by either call; the durations of
-refitMovedSlotsKernel and refitSlotsKernel on the same tree stand beside the stream-copy floor (twk_stream_peak_gbps, same process)
-of the Moved kernel's compulsory bytes: 48 B written per slot, 3 x 12 B of positions and 12 B of indices read.
+Kernels: a child of this tool under `rocprofv3 --kernel-trace` refits the moved C2 sphere RUNS + 1 times; the durations of the
+batch's four kernels stand beside the stream-copy floor (twk_stream_peak_gbps, same process) of the compulsory bytes of
+refitSceneSlotsKernel on a moved tree: 48 B written per slot, 3 x 12 B of positions and 12 B of indices read.
 
 Quality: sahNow / sahBuilt after each of four moves of the C2 sphere (a translation by 1e4, a rotation with unequal scales, a mirror,
 a squash of one axis to 1e-3) and after 100 rotation steps of 3.6 degrees; and a 1920 x 1080 sample pass on the refit handle over
@@ -155,18 +155,16 @@ def batch():
 
 
 def kernels_child(path):
-    """Under the kernel trace: RUNS + 1 refits of the C2 sphere's tree by either call."""
+    """Under the kernel trace: RUNS + 1 refits of the moved C2 sphere's tree."""
     system, scene, _ = texts()
     app = twk.Application(system_text=system, scene_text=scene)
     app.setResolution(256, 256)
-    geometry, base = app.instance(SPHERE)[0], app.instance(SPHERE)[1]
-    attributes = np.array(app.geometry(geometry)[0], np.float32)
+    base = app.instance(SPHERE)[1]
     dev = device(app)
     rate = dev.streamPeakGBps()
     for run in range(RUNS + 1):
         dev.refitInstanceTransform(SPHERE, stepped(base, run))
         info = dev.refitInfo()
-        dev.refitGeometryVertices(geometry, attributes)
     json.dump({"rate": rate, "slots": info["slotsRewritten"], "nodes": info["nodesRefit"]}, open(path, "w"))
     dev.close()
     app.close()
@@ -179,7 +177,7 @@ def kernels():
                        check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300)
         facts = json.load(open(run))
         traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-        names = ("refitMovedSlotsKernel", "refitSlotsKernel", "refitBatchParentsKernel", "refitParentsKernel", "refitBatchNodesKernel", "refitNodesKernel", "refitBatchTermsKernel", "refitTermsKernel")
+        names = ("refitSceneSlotsKernel", "refitBatchParentsKernel", "refitBatchNodesKernel", "refitBatchTermsKernel")
         groups = {}
         for r in csv.DictReader(open(traces[0])):
             name = next((k for k in names if k in r["Kernel_Name"]), None)
@@ -190,7 +188,7 @@ def kernels():
     floor = 1.0e6 * compulsory / (rate * 1.0e9)
     print()
     print(f"Kernel trace, the C2 sphere's tree ({slots} slots, {facts['nodes']} nodes), microseconds: median (min .. max) over the dispatches after the first. "
-          f"Floor of refitMovedSlotsKernel's compulsory bytes ({compulsory / 1e6:.2f} MB at {rate:.0f} GB/s): {floor:.2f} us.")
+          f"Floor of refitSceneSlotsKernel's compulsory bytes on a moved tree ({compulsory / 1e6:.2f} MB at {rate:.0f} GB/s): {floor:.2f} us.")
     print()
     print("| kernel | dispatches | us |")
     print("|---|---|---|")

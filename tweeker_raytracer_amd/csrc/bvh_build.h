@@ -1,6 +1,6 @@
 #pragma once
 #include "device_types.h"
-#include "refit_batch_plan.h"
+#include "refit_scene_plan.h"
 #include <vector>
 
 namespace twk {
@@ -26,28 +26,18 @@ void launchPairLeaves(float4* wideQ, int count, const int* pairFlags, int numSlo
 void launchRangedTail(const BvhNode* wide, float4* wideQ, const int2* ranges, int numRanges, int total, const int* pairFlags, int numSlots,
                       const float4* triangles, float4* pairs, hipStream_t stream);
 
-// The refit of one tree in place (bvh_refit.h is the definition, bvh_refit.hip the kernels): the slots [slotBase, slotBase + numSlots) and
-// their shading records again from `attributes` / `indices` — the geometry's own, or with `soup` (one descriptor per triangle of the
-// geometry, BvhBuilder::soupDescriptors from 0) the shared arrays and `instances` — then every box, wide node and node cost of the
-// nodes [nodeBase, nodeBase + numNodes) bottom-up, with the references, the cuts and the pair flags the tree has. All arrays are the
-// scene's (absolute indices); nodeCost / pairFlags nullptr: the scene has none. scratch: refitScratchWords(numNodes) words.
-// Waits for the stream; rootBounds receives the tree's new box, terms its SAH terms (inner, leaf; zero for a one-primitive tree).
-size_t refitScratchWords(int numNodes);
-hipError_t launchRefitTree(hipStream_t stream, const float* attributes, const unsigned int* indices, const int4* soup, const DevInstance* instances,
-                           BvhNode* nodes, BvhNode* wide, float* nodeCost, float4* triangles, float4* shadeTriangles, const int* pairFlags,
-                           int nodeBase, int numNodes, int slotBase, int numSlots, unsigned int* scratch, float rootBounds[6], double terms[2]);
-
-// The refit of the world-space trees of MOVED flattened instances, all trees of a call in one launch sequence and one wait
-// (bvh_refit_batch.hip; refit_batch_plan.h plans the blocks): tree k has the nodes [nodeBase[k], + numNodes[k]) and the slots
-// [slotBase[k], + numSlots[k]), its soup descriptors stand at soup[plan.slotOffset[k]] (BvhBuilder::soupDescriptors from there), and
-// `instances` holds the new matrices. Every slot gets its three world-space float4 again — the shading records are not touched, a
-// transform does not change them — then boxes, wide nodes and node costs follow as in launchRefitTree. scratch:
-// refitBatchScratchWords(plan) words. Waits for the stream once; rootBounds[6 k ..] receives tree k's box, terms[2 k ..] its SAH
-// terms, bit-equal to what launchRefitTree returns for the tree alone.
-size_t refitBatchScratchWords(const RefitBatchPlan& plan);
-hipError_t launchRefitTrees(hipStream_t stream, const float* attributes, const unsigned int* indices, const int4* soup, const DevInstance* instances,
-                            BvhNode* nodes, BvhNode* wide, float* nodeCost, float4* triangles, const int* pairFlags, const RefitBatchPlan& plan,
-                            const int* nodeBase, const int* numNodes, const int* slotBase, const int* numSlots, unsigned int* scratch, float* rootBounds, double* terms);
+// The refit of the plan's trees in place (bvh_refit.h is the definition, bvh_refit.hip the kernels; refit_scene_plan.h says which
+// trees and of which kind, refit_batch_plan.h which block works on which tree): ONE upload (tree table, kind table, block tables), the
+// slots launch (every slot again by its tree's kind, the soup descriptor made in registers — no descriptor array is read or written),
+// one memset, the parents, nodes and terms launches, one read-back and one wait, whatever the number and the kinds of the trees —
+// every box, wide node and node cost bottom-up, with the references, the cuts and the pair flags each tree has. kinds[k]: tree k's
+// record, with the bases of ITS geometry. All arrays are the scene's (absolute indices); nodeCost / pairFlags nullptr: the scene has
+// none. scratch: refitSceneScratchWords(plan) words. rootBounds[6 k ..] receives tree k's box, terms[2 k ..] its SAH terms (inner,
+// leaf; zero for a one-primitive tree) — a tree's bits do not depend on what else is in the batch.
+size_t refitSceneScratchWords(const RefitScenePlan& plan);
+hipError_t launchRefitSceneTrees(hipStream_t stream, const float* attributes, const unsigned int* indices, const DevInstance* instances, BvhNode* nodes, BvhNode* wide,
+                                 float* nodeCost, float4* triangles, float4* shadeTriangles, const int* pairFlags, const RefitScenePlan& plan, const RefitSceneKind* kinds,
+                                 unsigned int* scratch, float* rootBounds, double* terms);
 
 // Build primitives of a geometry's triangles for BvhBuilder::buildTriangles: triangles 2k, 2k + 1 with the index triples
 // (a, b, c), (c, d, a) — what every mesh generator emits per quad — are one primitive (first triangle | sign bit), every other

@@ -9,7 +9,7 @@
 // two children gives way to its own children, read from the references the wide node holds.
 // Written: every slot and its shading record (emitTriangle, as the build emits them), every leaf's box, every inner box as the
 // fminf / fmaxf union of its children's, every full-precision wide node with the cut it had, and nodeCost by refitKernel's formula for
-// that cut. The refit of a tree whose INSTANCE moved (twk_refit_instance_transform, bvh_refit_batch.hip) writes the same, except that
+// that cut. The refit of a tree whose INSTANCE moved (twk_refit_instance_transform, kind 2 of refit_scene_plan.h) writes the same, except that
 // it leaves the shading records alone: moveTriangle instead of emitTriangle.
 //
 // ---- a leaf's box (refitLeafBox) ------------------------------------------------------------------------------------------------
@@ -183,7 +183,7 @@ TWK_HD void emitTriangle(const float* __restrict__ attributes, const unsigned in
   out[7] = make_float4(c[10], c[11], 0.0f, 0.0f);
 }
 
-// The slot of a world-space tree whose INSTANCE moved (twk_refit_instance_transform, bvh_refit_batch.hip): emitTriangle's three
+// The slot of a world-space tree whose INSTANCE moved (twk_refit_instance_transform, kind 2 of refit_scene_plan.h): emitTriangle's three
 // world-space float4 through the matrix the instance record holds now, and nothing else. The shading record is built from the
 // object-space a, b, c alone (above: the geometric normal of the untransformed triangle, the vertices' normals, tangents and texture
 // coordinates as the geometry holds them) — a transform changes none of its 128 bytes, so it is neither read nor written.
@@ -210,8 +210,8 @@ struct RefitTree
   const float4* triangles; const int* pairFlags;
   int nodeBase, numNodes, slotBase, numSlots;
 };
-// One tree of a batched refit (bvh_refit_batch.hip), as the device table holds it: the tree, and where its parents and tickets
-// (nodeOffset) and its soup descriptors (slotOffset) stand among the batch's (refit_batch_plan.h). 64 bytes.
+// One tree of a batched refit (bvh_refit.hip), as the device table holds it: the tree, and how many nodes (nodeOffset: where its
+// parents and tickets stand) and slots (slotOffset) the trees before it have (refit_batch_plan.h). 64 bytes.
 struct RefitBatchTree { RefitTree tree; int nodeOffset, slotOffset; };
 
 TWK_HD void refitChildren(const BvhNode* node, int& c0, int& c1)

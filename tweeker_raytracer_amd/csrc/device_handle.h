@@ -329,7 +329,7 @@ struct TwkDevice_t
   DeviceArray<float> d_nodeCost; DeviceArray<int> d_pairFlags;
   DeviceArray<int4> d_updateSoup; DeviceArray<int2> d_updateRanges; DeviceArray<int> d_updateResult;
   TwkUpdateInfo updateInfo = {}; bool updateInfoValid = false;
-  // twk_refit_geometry_vertices: what the last refit did (valid until the next build), and the scratch of a tree's refit (bvh_build.h refitScratchWords)
+  // the twk_refit_* calls: what the last refit did (valid until the next build), and the scratch of a call's batch (bvh_build.h refitSceneScratchWords)
   TwkRefitInfo refitInfo = {}; bool refitInfoValid = false;
   DeviceArray<unsigned int> d_refitScratch;
   DeviceArray<unsigned int> d_sourceCheck; // one word: the lowest vertex of a device-pointer source whose position is not finite

@@ -3,7 +3,6 @@
 #include "device_handle.h"
 #include "temporal_motion_device.h" // instanceTransformUsable
 #include "bvh_refit.h"              // the host form of a tree's refit
-#include "bvh_refit_scene.h"        // the batch of a twk_refit_scene call
 #include "vertex_source_device.h"   // the finite check of twk_refit_scene's device sources
 
 #include <algorithm>
@@ -502,20 +501,55 @@ static void countRefit(TwkDevice dev, const SceneState& state, int geometry, Twk
   info.treesRefit += 1; info.nodesRefit += (uint64_t) nodes; info.refitsSinceBuild = std::max(info.refitsSinceBuild, terms.refits);
 }
 
-// The refit of one tree of geometry `geometry` at the node and slot bases given (bvh_refit.h): the bottom-level tree (soup nullptr) or
-// a flattened instance's world-space tree (soup: its descriptors). Its box goes to rootBounds, its new SAH terms into `terms` (the
-// height stays: a refit changes no tree's height), and the call into `info`. A tree over one build primitive has no terms (sahTotals).
-static int refitTree(TwkDevice dev, SceneState& state, int geometry, TwkDevice_t::TreeTerms& terms, const int4* soup, int nodeBase, int triangleBase, float rootBounds[6], TwkRefitInfo& info)
+// An update of a handle that kept nothing: the scene built again in full mode, and the record of it
+static int updateFull(TwkDevice dev, int moved, size_t records)
 {
   int rc;
-  const GeometryHost& g = dev->geometries[geometry];
-  const int nodes = treeNodes(g.numTriangles);
-  if ((rc = dev->d_refitScratch.ensure(refitScratchWords(nodes)))) return rc;
-  double now[2];
-  HIP_TRY(launchRefitTree(dev->stream, soup ? dev->d_attributes.get() : dev->d_attributes + 12 * (size_t) g.attributeBase, soup ? dev->d_indices.get() : dev->d_indices + g.indexBase,
-                          soup, soup ? dev->d_instances.get() : nullptr, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles, dev->d_shadeTriangles,
-                          state.pairs ? dev->d_pairFlags.get() : nullptr, nodeBase, nodes, triangleBase, g.numTriangles, dev->d_refitScratch, rootBounds, now));
-  countRefit(dev, state, geometry, terms, now, nodes, info);
+  if ((rc = buildScene(dev, false))) return rc;
+  recordUpdate(dev, false, moved, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, records);
+  return TWK_SUCCESS;
+}
+
+// What a selective update works from: the update plan of the call's moved instances and updated geometries (update_plan.h) and, for
+// a refit, the trees of its one batch (refit_scene_plan.h). Why the batch cannot be planned, or nullptr. Changes nothing:
+// twk_refit_scene asks before it stores anything, updateSelective when it runs.
+struct UpdatePlans { std::vector<int> instanceGeometry, geometryTriangles; UpdatePlan plan; RefitScenePlan refit; };
+static const char* planUpdate(TwkDevice dev, const int* moved, int numMoved, const int* updated, int numUpdated, bool refit, UpdatePlans& p)
+{
+  layoutInputs(dev, p.instanceGeometry, p.geometryTriangles);
+  updatePlanWith(dev->kept.layout, p.instanceGeometry.data(), p.geometryTriangles.data(), moved, numMoved, updated, numUpdated, p.plan);
+  if (!refit) return nullptr;
+  return refitScenePlan(dev->kept.layout, p.instanceGeometry.data(), p.geometryTriangles.data(), p.plan, moved, numMoved, updated, numUpdated, p.refit);
+}
+
+// The refit stage of a selective update: every tree of the plan in place, all in one batch (bvh_refit.hip launchRefitSceneTrees), in
+// stream order behind the rebuilds of the direct leaves. Then, per tree in the plan's order — geometries ascending, then instances
+// ascending — its box to where the top level reads it (a bottom-level tree's to the geometry's rootBounds, so that the boxes of its
+// entered instances follow; a world-space tree's to the instance's box), its new SAH terms, and the call into `info`.
+static int refitTrees(TwkDevice dev, SceneState& state, const RefitScenePlan& plan, TwkRefitInfo& info)
+{
+  int rc;
+  const size_t numTrees = plan.tree.size();
+  if (numTrees == 0) return TWK_SUCCESS;
+  if ((rc = dev->d_refitScratch.ensure(refitSceneScratchWords(plan)))) return rc;
+  std::vector<RefitSceneKind> kinds(numTrees);
+  for (size_t k = 0; k < numTrees; ++k)
+  {
+    const GeometryHost& g = dev->geometries[plan.geometry[k]];
+    kinds[k] = {plan.kind[k], plan.kind[k] == REFIT_SCENE_GEOMETRY ? -1 : plan.tree[k], (int) g.attributeBase, (int) g.indexBase};
+  }
+  std::vector<float> bounds(6 * numTrees);
+  std::vector<double> now(2 * numTrees);
+  HIP_TRY(launchRefitSceneTrees(dev->stream, dev->d_attributes, dev->d_indices, dev->d_instances, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles,
+                                dev->d_shadeTriangles, state.pairs ? dev->d_pairFlags.get() : nullptr, plan, kinds.data(), dev->d_refitScratch, bounds.data(), now.data()));
+  for (size_t k = 0; k < numTrees; ++k)
+  {
+    const int geometry = plan.geometry[k], i = plan.tree[k];
+    const float* b = &bounds[6 * k];
+    if (plan.kind[k] == REFIT_SCENE_GEOMETRY) memcpy(dev->geometries[geometry].rootBounds, b, sizeof(float) * 6);
+    else { state.boxLo[i] = make_float4(b[0], b[1], b[2], 0.0f); state.boxHi[i] = make_float4(b[3], b[4], b[5], 0.0f); }
+    countRefit(dev, state, geometry, plan.kind[k] == REFIT_SCENE_GEOMETRY ? state.geometryTerms[geometry] : state.instanceTerms[i], &now[2 * k], plan.nodes[k], info);
+  }
   return TWK_SUCCESS;
 }
 
@@ -523,22 +557,13 @@ static int refitTree(TwkDevice dev, SceneState& state, int geometry, TwkDevice_t
 // the transforms of the instances `moved` (distinct) have been replaced. It runs buildScene's stages (above) for what the plan names,
 // on arrays that hold what buildScene's held at that point — so the result is a fresh build's, byte for byte. A failure leaves the
 // handle unbuilt (twk_build recovers it).
-// updated: geometries (distinct) whose attributes have been replaced on the host, numUpdated of them — a vertex update
-// (twk_update_geometry_vertices): their slices of d_attributes are uploaded, the bottom-level tree of an entered one is rebuilt at the
-// node and slot range it has, and the trees and boxes of their instances follow (update_plan.h updatePlanWith).
-// refit (twk_refit_geometry_vertices): the trees of the updated geometries are refit in place (refitTree, above) instead of zeroed and
-// rebuilt — all but a direct-leaf instance's, which has no tree of its own and takes the rebuild's path. The stages around the trees
-// are the same; the handle is then a legal scene for the new vertices, not a fresh build's.
-// refitMoved (twk_refit_instance_transform[s], with refit and no updated geometry): the world-space trees of the moved flattened
-// instances are refit too, but all in one batch (bvh_refit_batch.hip launchRefitTrees) behind the rebuilds of the direct leaves among
-// them: their soup descriptors at the running slot offsets of refit_batch_plan.h, one upload, one launch sequence, one wait, then
-// boxes and terms per tree. The shading records stay as they are: a transform does not change them.
-// refitAll (twk_refit_scene, with refit): every tree the plan names but a direct leaf's — the bottom-level trees of the updated
-// geometries, the world-space trees of their flattened instances and of the moved flattened instances — is refit ONCE, all in one
-// batch of mixed kinds (refit_scene_plan.h; bvh_refit_scene.hip launchRefitSceneTrees) behind the rebuilds of the direct leaves. No
-// soup descriptor is written for the batch: its slot kernel makes each in registers.
-static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false, bool refitMoved = false,
-                           bool refitAll = false)
+// updated: geometries (distinct) whose attributes have been replaced, numUpdated of them: their slices of d_attributes are uploaded,
+// the bottom-level tree of an entered one is rebuilt at the node and slot range it has, and the trees and boxes of their instances
+// follow (update_plan.h updatePlanWith).
+// refit (the twk_refit_* calls): only a direct-leaf instance, which has no tree of its own, takes the rebuild's path; every other
+// tree the plan names is refit in place (refitTrees, above) instead of zeroed and rebuilt. The stages around the trees are the same;
+// the handle is then a legal scene for the new vertices and transforms, not a fresh build's.
+static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const int* updated = nullptr, int numUpdated = 0, bool refit = false)
 {
   int rc;
   SceneState& state = dev->kept;
@@ -549,10 +574,11 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
   if ((rc = checkInstanceTables(dev))) return rc;
   HIP_TRY(hipStreamSynchronize(dev->stream));
 
-  std::vector<int> instanceGeometry, geometryTriangles;
-  layoutInputs(dev, instanceGeometry, geometryTriangles);
-  UpdatePlan plan;
-  updatePlanWith(layout, instanceGeometry.data(), geometryTriangles.data(), moved, numMoved, updated, numUpdated, plan);
+  UpdatePlans plans;
+  if (const char* why = planUpdate(dev, moved, numMoved, updated, numUpdated, refit, plans)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string("twk_build: the refit batch: ") + why);
+  const UpdatePlan& plan = plans.plan;
+  const std::vector<int>& instanceGeometry = plans.instanceGeometry;
+  const std::vector<int>& geometryTriangles = plans.geometryTriangles;
   const size_t numNodes = layout.numNodes, numTris = layout.numTriangles;
 
   // the records of the moved instances only (the new object-to-world matrix and its inverse); they live until the first synchronise
@@ -563,29 +589,21 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
     HIP_TRY(hipMemcpyAsync(dev->d_instances + moved[k], &records[k], sizeof(DevInstance), hipMemcpyHostToDevice, dev->stream));
   }
 
-  // the world-space tree of every moved flattened instance, at the bases it has; a fresh build starts from zeroed node arrays and
-  // pair flags, and what a tree leaves unused of its range must stay zero
   NodeCostScope nodeCostScope{dev->builder};
   dev->builder.setNodeCost(dev->d_nodeCost);
-  // the new vertices, and the bottom-level tree of every updated geometry that is entered: buildScene's call on the range it has
+  // the new vertices
   for (int k = 0; k < numUpdated; ++k)
   {
     const GeometryHost& g = dev->geometries[updated[k]];
     if (mirrorStale(g)) continue; // a device-pointer source has written the slice already (vertex_source_device.h): it is what the upload would bring
     HIP_TRY(hipMemcpyAsync(dev->d_attributes + 12 * (size_t) g.attributeBase, g.attributes.data(), sizeof(TwkTriangleAttributes) * g.attributes.size(), hipMemcpyHostToDevice, dev->stream));
   }
-  TwkRefitInfo refitInfo;
-  memset(&refitInfo, 0, sizeof(refitInfo));
-  for (int k : plan.geometries)
+  // the bottom-level tree of every updated geometry that is entered: buildScene's call on the range it has. A fresh build starts
+  // from zeroed node arrays and pair flags, and what a tree leaves unused of its range must stay zero
+  if (!refit) for (int k : plan.geometries)
   {
     GeometryHost& g = dev->geometries[k];
     const int nodes = treeNodes(g.numTriangles);
-    if (refitAll) continue; // in the scene's batch, below
-    if (refit)
-    {
-      if ((rc = refitTree(dev, state, k, state.geometryTerms[k], nullptr, g.nodeBase, g.triangleBase, g.rootBounds, refitInfo))) return rc;
-      continue;
-    }
     HIP_TRY(hipMemsetAsync(dev->d_nodes + g.nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
     HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) g.nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
     if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + g.triangleBase, 0, sizeof(int) * (size_t) g.numTriangles, dev->stream));
@@ -594,111 +612,23 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
                                         nullptr, nullptr, state.pairs ? state.primFirst[k].data() : nullptr, (int) state.primFirst[k].size(), dev->d_pairFlags));
     state.geometryTerms[k] = lastTerms(dev->builder);
   }
+  // the world-space tree of every flattened instance the plan names, at the bases it has — of a refit, the direct leaves only
+  const std::vector<int>& rebuilt = refit ? plans.refit.directLeaves : plan.trees;
   int maxTriangles = 0;
-  for (int i : plan.trees) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
-  // the batch of a transform refit: every moved flattened instance with a tree of its own, ascending
-  std::vector<int> batch, batchNodeBase, batchNodes, batchSlotBase, batchSlots;
-  RefitBatchPlan batchPlan;
-  if (refitMoved)
-  {
-    for (int i : plan.trees)
-    {
-      if (layout.directLeaf[i]) continue;
-      const int triangles = geometryTriangles[instanceGeometry[i]];
-      batch.push_back(i);
-      batchNodeBase.push_back(layout.flatNodeBase[i]); batchNodes.push_back(treeNodes(triangles));
-      batchSlotBase.push_back(layout.flatTriangleBase[i]); batchSlots.push_back(triangles);
-    }
-    if (!batch.empty())
-    {
-      if (const char* why = refitBatchPlan(batchNodes.data(), batchSlots.data(), (int) batch.size(), batchPlan)) return twkSetError(TWK_ERROR_INVALID_VALUE, std::string("twk_build: the refit batch: ") + why);
-      maxTriangles = std::max(maxTriangles, (int) batchPlan.totalSlots); // the descriptors of all its trees, side by side
-      if ((rc = dev->d_refitScratch.ensure(refitBatchScratchWords(batchPlan)))) return rc;
-    }
-  }
-  // the batch of a scene refit: the plan's trees by kind, in refit_scene_plan.h's order
-  RefitScenePlan scenePlan;
-  if (refitAll)
-  {
-    if (const char* why = refitScenePlan(layout, instanceGeometry.data(), geometryTriangles.data(), plan, moved, numMoved, updated, numUpdated, scenePlan))
-      return twkSetError(TWK_ERROR_INVALID_VALUE, std::string("twk_refit_scene: the refit batch: ") + why); // twk_refit_scene has planned the same batch before it stored anything: never taken
-    maxTriangles = 0; // descriptors for the rebuilds of the direct leaves only
-    for (int i : scenePlan.directLeaves) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
-    if (!scenePlan.tree.empty() && (rc = dev->d_refitScratch.ensure(refitSceneScratchWords(scenePlan)))) return rc;
-  }
+  for (int i : rebuilt) maxTriangles = std::max(maxTriangles, geometryTriangles[instanceGeometry[i]]);
   if (maxTriangles > 0 && (rc = dev->d_updateSoup.ensure((size_t) maxTriangles))) return rc;
-  for (int i : plan.trees)
+  for (int i : rebuilt)
   {
     const int nodeBase = layout.flatNodeBase[i], triangleBase = layout.flatTriangleBase[i], triangles = geometryTriangles[instanceGeometry[i]], nodes = treeNodes(triangles);
-    if ((refitMoved || refitAll) && !layout.directLeaf[i]) continue; // in the batch, below
-    if (refit && !layout.directLeaf[i])
-    {
-      float bounds[6];
-      dev->builder.soupDescriptors(dev->stream, dev->d_updateSoup, 0, triangles, i, (int) dev->geometries[instanceGeometry[i]].attributeBase, (int) dev->geometries[instanceGeometry[i]].indexBase);
-      HIP_TRY(hipGetLastError());
-      if ((rc = refitTree(dev, state, instanceGeometry[i], state.instanceTerms[i], dev->d_updateSoup, nodeBase, triangleBase, bounds, refitInfo))) return rc;
-      state.boxLo[i] = make_float4(bounds[0], bounds[1], bounds[2], 0.0f);
-      state.boxHi[i] = make_float4(bounds[3], bounds[4], bounds[5], 0.0f);
-      continue;
-    }
-    refitInfo.treesRebuilt += 1;
     HIP_TRY(hipMemsetAsync(dev->d_nodes + nodeBase, 0, sizeof(BvhNode) * (size_t) nodes, dev->stream));
     HIP_TRY(hipMemsetAsync(dev->d_wideNodes + 2 * (size_t) nodeBase, 0, sizeof(BvhNode) * 2 * (size_t) nodes, dev->stream));
     if (state.pairs) HIP_TRY(hipMemsetAsync(dev->d_pairFlags + triangleBase, 0, sizeof(int) * (size_t) triangles, dev->stream));
     if ((rc = buildFlattenedTree(dev, state, i, dev->d_updateSoup))) return rc;
     // its payload in the top level (its root, or its slots as a direct leaf) names bases, which do not move
   }
-  if (!batch.empty())
-  {
-    // behind the rebuilds, in stream order: they used the first descriptors of d_updateSoup
-    for (size_t k = 0; k < batch.size(); ++k)
-    {
-      const GeometryHost& g = dev->geometries[instanceGeometry[batch[k]]];
-      dev->builder.soupDescriptors(dev->stream, dev->d_updateSoup, batchPlan.slotOffset[k], batchSlots[k], batch[k], (int) g.attributeBase, (int) g.indexBase);
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<float> bounds(6 * batch.size());
-    std::vector<double> now(2 * batch.size());
-    HIP_TRY(launchRefitTrees(dev->stream, dev->d_attributes, dev->d_indices, dev->d_updateSoup, dev->d_instances, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles,
-                             state.pairs ? dev->d_pairFlags.get() : nullptr, batchPlan, batchNodeBase.data(), batchNodes.data(), batchSlotBase.data(), batchSlots.data(),
-                             dev->d_refitScratch, bounds.data(), now.data()));
-    for (size_t k = 0; k < batch.size(); ++k)
-    {
-      const int i = batch[k];
-      countRefit(dev, state, instanceGeometry[i], state.instanceTerms[i], &now[2 * k], batchNodes[k], refitInfo);
-      state.boxLo[i] = make_float4(bounds[6 * k], bounds[6 * k + 1], bounds[6 * k + 2], 0.0f);
-      state.boxHi[i] = make_float4(bounds[6 * k + 3], bounds[6 * k + 4], bounds[6 * k + 5], 0.0f);
-    }
-  }
-  if (!scenePlan.tree.empty())
-  {
-    // behind the rebuilds, in stream order; the bottom-level trees first, so that the boxes below see the new root boxes
-    const size_t numTrees = scenePlan.tree.size();
-    std::vector<RefitSceneKind> kinds(numTrees);
-    for (size_t k = 0; k < numTrees; ++k)
-    {
-      const GeometryHost& g = dev->geometries[scenePlan.geometry[k]];
-      kinds[k] = {scenePlan.kind[k], scenePlan.kind[k] == REFIT_SCENE_GEOMETRY ? -1 : scenePlan.tree[k], (int) g.attributeBase, (int) g.indexBase};
-    }
-    std::vector<float> bounds(6 * numTrees);
-    std::vector<double> now(2 * numTrees);
-    HIP_TRY(launchRefitSceneTrees(dev->stream, dev->d_attributes, dev->d_indices, dev->d_instances, dev->d_nodes, dev->d_wideNodes, dev->d_nodeCost, dev->d_triangles,
-                                  dev->d_shadeTriangles, state.pairs ? dev->d_pairFlags.get() : nullptr, scenePlan, kinds.data(), dev->d_refitScratch, bounds.data(), now.data()));
-    for (size_t k = 0; k < numTrees; ++k)
-    {
-      const int geometry = scenePlan.geometry[k];
-      if (scenePlan.kind[k] == REFIT_SCENE_GEOMETRY)
-      {
-        countRefit(dev, state, geometry, state.geometryTerms[geometry], &now[2 * k], scenePlan.nodes[k], refitInfo);
-        memcpy(dev->geometries[geometry].rootBounds, &bounds[6 * k], sizeof(float) * 6);
-        continue;
-      }
-      const int i = scenePlan.tree[k];
-      countRefit(dev, state, geometry, state.instanceTerms[i], &now[2 * k], scenePlan.nodes[k], refitInfo);
-      state.boxLo[i] = make_float4(bounds[6 * k], bounds[6 * k + 1], bounds[6 * k + 2], 0.0f);
-      state.boxHi[i] = make_float4(bounds[6 * k + 3], bounds[6 * k + 4], bounds[6 * k + 5], 0.0f);
-    }
-  }
+  TwkRefitInfo refitInfo;
+  memset(&refitInfo, 0, sizeof(refitInfo));
+  if (refit && (rc = refitTrees(dev, state, plans.refit, refitInfo))) return rc;
   // a moved entered instance: its box in the top level, nothing else — no bottom-level tree is rebuilt
   for (int k = 0; k < numMoved; ++k)
     if (!layout.flattened[moved[k]])
@@ -726,10 +656,10 @@ static int updateSelective(TwkDevice dev, const int* moved, int numMoved, const 
 
   // the build info: counts, pair leaves, quality — no transform changes them — and what the changed trees change
   finishBuild(dev, state, dev->buildInfo, traversalDepth, start);
-  recordUpdate(dev, true, numMoved, refit ? refitInfo.treesRebuilt : (int) (plan.geometries.size() + plan.trees.size()), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
+  recordUpdate(dev, true, numMoved, (int) ((refit ? 0 : plan.geometries.size()) + rebuilt.size()), plan.topLevel, plan.totalNodes, plan.totalSlots, (size_t) numMoved);
   if (refit)
   {
-    refitInfo.topLevelRebuilt = plan.topLevel ? 1 : 0; refitInfo.slotsRewritten = (uint64_t) plan.totalSlots; refitInfo.milliseconds = dev->buildInfo.buildMilliseconds;
+    refitInfo.treesRebuilt = (int) rebuilt.size(); refitInfo.topLevelRebuilt = plan.topLevel ? 1 : 0; refitInfo.slotsRewritten = (uint64_t) plan.totalSlots; refitInfo.milliseconds = dev->buildInfo.buildMilliseconds;
     dev->refitInfo = refitInfo; dev->refitInfoValid = true;
   }
   return TWK_SUCCESS;
@@ -821,10 +751,8 @@ static int updateTransforms(TwkDevice dev, const char* name, bool batch, int cou
   if ((rc = applyEmitterMoves(dev, emitters))) return rc;
   dev->updateInfoValid = false; // an update that fails from here on leaves no record: twk_get_update_info describes a finished update
   // the temporal history stays: the merges look it up where the instance was (device_temporal.hip ownMotion)
-  if (dev->kept.valid) return updateSelective(dev, ids, count, nullptr, 0, refit, refit);
-  if ((rc = buildScene(dev, false))) return rc;
-  recordUpdate(dev, false, count, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, dev->instances.size());
-  return TWK_SUCCESS;
+  if (dev->kept.valid) return updateSelective(dev, ids, count, nullptr, 0, refit);
+  return updateFull(dev, count, dev->instances.size());
 }
 
 // The body of twk_update_plan_host (no updated geometry) and of twk_vertex_update_plan_host
@@ -923,9 +851,7 @@ try
   int rc = replaceVertices(dev, "twk_update_geometry_vertices", false, idGeometry, attributes, numAttributes); if (rc) return rc;
   // the temporal history stays: the merges look it up where the surface was (twk_render_geometry_motion, temporal_carry_device.h)
   if (dev->kept.valid) return updateSelective(dev, nullptr, 0, &idGeometry, 1);
-  if ((rc = buildScene(dev, false))) return rc;
-  recordUpdate(dev, false, 0, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, 0);
-  return TWK_SUCCESS;
+  return updateFull(dev, 0, 0);
 }
 TWK_CATCH("twk_update_geometry_vertices")
 
@@ -944,9 +870,7 @@ try
 {
   int rc = ingestVertexSource(dev, "twk_update_geometry_vertices_device", false, idGeometry, source, numVertices); if (rc) return rc;
   if (dev->kept.valid) return updateSelective(dev, nullptr, 0, &idGeometry, 1);
-  if ((rc = buildScene(dev, false))) return rc; // reads the slice back into the mirror before the arrays are allocated again
-  recordUpdate(dev, false, 0, dev->buildInfo.trees, !(dev->instances.size() == 1 && dev->buildInfo.flattenedInstances == 1), dev->wideNodesTotal, dev->totalTriangles, 0);
-  return TWK_SUCCESS;
+  return updateFull(dev, 0, 0); // the build reads the slice back into the mirror before the arrays are allocated again
 }
 TWK_CATCH("twk_update_geometry_vertices_device")
 
@@ -1083,7 +1007,7 @@ TWK_CATCH("twk_refit_batch_plan_host")
 // A frame's edits in one call (include/tweeker_hip.h "A frame's edits in one call"): every entry is checked before anything is
 // written — the call's own arguments, the handle, the geometry entries in order, the instance entries, last the finite check of all
 // device sources (one launch per source into one result array, ONE read-back and wait) — then the vertices are stored as the vertex
-// calls store them, the transforms as the transform calls do, and updateSelective refits every tree once (refitAll).
+// calls store them, the transforms as the transform calls do, and updateSelective refits every tree once.
 int twk_refit_scene(TwkDevice dev, int numGeometries, const TwkGeometryEdit* geometries, int numInstances, const int* idInstances, const float* transforms)
 try
 {
@@ -1132,13 +1056,8 @@ try
   }
   {
     // the batch as updateSelective will plan it: a batch that cannot be planned is refused here, before anything is stored
-    std::vector<int> instanceGeometry, geometryTriangles;
-    layoutInputs(dev, instanceGeometry, geometryTriangles);
-    UpdatePlan plan;
-    updatePlanWith(dev->kept.layout, instanceGeometry.data(), geometryTriangles.data(), idInstances, numInstances, updated.data(), numGeometries, plan);
-    RefitScenePlan scenePlan;
-    if (const char* why = refitScenePlan(dev->kept.layout, instanceGeometry.data(), geometryTriangles.data(), plan, idInstances, numInstances, updated.data(), numGeometries, scenePlan))
-      return refuse(TWK_ERROR_INVALID_VALUE, std::string("the refit batch: ") + why);
+    UpdatePlans plans;
+    if (const char* why = planUpdate(dev, idInstances, numInstances, updated.data(), numGeometries, true, plans)) return refuse(TWK_ERROR_INVALID_VALUE, std::string("the refit batch: ") + why);
   }
   std::vector<EmitterMove> emitters;
   if ((rc = planEmitterMoves(dev, name, true, numInstances, idInstances, transforms, emitters))) return rc;
@@ -1152,7 +1071,7 @@ try
   if ((rc = applyEmitterMoves(dev, emitters))) return rc;
   dev->updateInfoValid = false;
   // the temporal history stays, as after the calls this one stands for
-  return updateSelective(dev, idInstances, numInstances, updated.data(), numGeometries, true, false, true);
+  return updateSelective(dev, idInstances, numInstances, updated.data(), numGeometries, true);
 }
 TWK_CATCH("twk_refit_scene")
 

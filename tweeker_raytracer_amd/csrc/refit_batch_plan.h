@@ -1,15 +1,15 @@
-// How the trees of one batched refit (bvh_refit_batch.hip launchRefitTrees) share its launches: the one place that decides which
-// block of a launch works on which tree, and where each tree's parents, tickets, soup descriptors and per-block partial sums stand.
+// How the trees of one batched refit (bvh_refit.hip launchRefitSceneTrees) share its launches: the one place that decides which
+// block of a launch works on which tree, and where each tree's parents, tickets and per-block partial sums stand.
 // Plain C++, no HIP: the launcher plans with refitBatchPlan, and twk_refit_batch_plan_host hands the plan out without a device.
 //
 // Tree k has n_k nodes and s_k slots. It occupies ceil(n_k / 256) consecutive NODE blocks of the parents, nodes and terms launches
 // and ceil(s_k / 256) consecutive SLOT blocks of the slots launch, the trees in the order given. Per block, a table entry names the
 // tree and the tree-local index of the block's first thread: thread j of the block works on local index first + j, or on nothing when
 // that is beyond the tree — so a block never straddles two trees, and block b of tree k covers the local indices
-// [256 b, 256 b + 256), the range block b of the tree's own launch (launchRefitTree) covers. The 256-thread reduction of the terms is
-// therefore the same sums in the same order, and the host adds a tree's blocks by index as launchRefitTree does: bit-equal terms.
-// Parents and tickets (one word per node) stand at the running node offset, soup descriptors (one per slot) at the running slot
-// offset, a tree's partial sums at its first node block.
+// [256 b, 256 b + 256), the range block b of a launch for the tree alone would cover. The 256-thread reduction of the terms is
+// therefore the same sums in the same order whatever else is in the batch, and the host adds a tree's blocks by index: a tree's terms
+// are bit-equal in every batch. Parents and tickets (one word per node) stand at the running node offset, a tree's partial sums at
+// its first node block; the running slot offset counts the slots of the trees before it.
 #pragma once
 #include <cstddef>
 #include <vector>

@@ -1,6 +1,6 @@
-// The trees of one twk_refit_scene call (bvh_refit_scene.hip launchRefitSceneTrees; device_scene.hip refitScene is the caller): the
-// one place that turns an UpdatePlan (update_plan.h) and the scene's layout into the list of trees the call's ONE batch refits, and
-// says what kind each is. Plain C++, no HIP: the call plans with refitScenePlan, and twk_scene_refit_plan_host hands the plan out
+// The trees of one refit call — a vertex refit, an instance refit or twk_refit_scene (bvh_refit.hip launchRefitSceneTrees;
+// device_scene.hip refitTrees is the caller): the one place that turns an UpdatePlan (update_plan.h) and the scene's layout into the
+// list of trees the call's ONE batch refits, and says what kind each is. A vertex refit gives kinds 0 and 1, an instance refit kind 2 only. Plain C++, no HIP: the call plans with refitScenePlan, and twk_scene_refit_plan_host hands the plan out
 // without a device.
 //
 // The order: the bottom-level trees of the edited geometries that some instance enters, ascending by geometry, then the plan's

@@ -563,7 +563,7 @@ class Device:
         attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
         L.check(L.lib.twk_update_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
 
-    # ---- refit (include/tweeker_hip.h "Refit", csrc/bvh_refit.h) ----
+    # ---- refit (include/tweeker_hip.h "Refit", csrc/bvh_refit.h; every refit call runs the one batch of csrc/bvh_refit.hip) ----
     def refitGeometryVertices(self, idGeometry, attributes):
         """twk_refit_geometry_vertices: updateGeometryVertices on a handle built in selective mode, but the geometry's trees are refit
         in place — new boxes, the topology, the references and the wide nodes' cuts kept — instead of rebuilt. The handle is then a
@@ -572,7 +572,7 @@ class Device:
         attributes = np.ascontiguousarray(attributes, dtype=np.float32).reshape(-1, 12)
         L.check(L.lib.twk_refit_geometry_vertices(self._h, int(idGeometry), attributes.ctypes.data_as(C.c_void_p), C.c_size_t(attributes.shape[0])))
 
-    # ---- refit of a moved instance (include/tweeker_hip.h "Refit of a moved instance", csrc/bvh_refit_batch.hip) ----
+    # ---- refit of a moved instance (include/tweeker_hip.h "Refit of a moved instance", kind 2 of csrc/refit_scene_plan.h) ----
     def refitInstanceTransform(self, idInstance, transform):
         """twk_refit_instance_transform: updateInstanceTransform on a handle built in selective mode, but the world-space tree of a
         moved flattened instance is refit in place — slots through the new matrix, boxes, wide nodes and costs updated, topology,
